@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- PE-link inference throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4}] [--pairs R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4}] [--pairs R] [--full] [--dump-outputs DIR]
 
 ``--config i`` = BASELINE.json configs[i] (default 2, the configuration the metric is quoted on):
 synthetic strains of one ancestor genome, the compacted de Bruijn graph of those strains taken
@@ -13,15 +13,19 @@ counters, vs_pe_count over all pairs (locus sort, seed probe, extension, accepta
 node_mat/short_mat counters) and, for N > 1, the RCCL all-reduce of the counters.
 Weak scaling: every rank works on its own R pairs (disjoint slices of one seeded stream).
 
-After the timed PE steps rank 0 runs the graph stages once on the counters of the last step
-(edge cleaning, disentanglement, path extraction: `strain_extract_s`, the second half of
-BASELINE.json's metric; replicas only, no collective) -- configs 1 and 2 by default.
+A plain run sets up, warms up, times the steps, writes the outputs of the last step when
+``--dump-outputs DIR`` is given (dump_outputs) and prints its line.  Everything else is measured
+with ``--full`` only: after the timed PE steps rank 0 runs the graph stages once on the counters
+of the last step (edge cleaning, disentanglement, path extraction: `strain_extract_s`, the second
+half of BASELINE.json's metric; replicas only, no collective) -- configs 0, 1, 2 and 5 by default,
+or alone with ``--extract`` --, then the FASTQ ingest leg, the CPU baseline and the stream-copy /
+PMC traffic figures of `roofline`.
 
 Prints ONE JSON line (rank 0).  `roofline` uses the algorithmic bytes per pair of SURVEY.md 8(d)
 (2*ceil(L/4) + 2*(L-k)*8 + 16 = 1612 B at L=150,k=55; 2110 B at L=250,k=127) over the main
-kernel's HIP-event time; `cpu_baseline` times the C restatement of the reference algorithm
-(oracle/, 1 thread) on a prefix of the same read stream and checks that the GPU gives the same
-counters on that prefix.
+kernel's HIP-event time; `cpu_baseline` (--full) times the C restatement of the reference
+algorithm (oracle/, 1 thread) on a prefix of the same read stream and checks that the GPU gives
+the same counters on that prefix.
 """
 import argparse
 import json
@@ -163,12 +167,20 @@ def main():
                          "(the N = 1 workload of the config) between them -- the question north_star asks at configs[2]")
     ap.add_argument("--dirty", type=float, default=0.0,
                     help="fraction of read BASES replaced by lower-case / IUPAC bytes (real FASTQ holds such bytes; 0 = none)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample time (0 = skip)")
-    ap.add_argument("--no-extract", action="store_true", help="skip the strain-extract leg (kernel experiments)")
-    ap.add_argument("--extract", action="store_true", help="run the strain-extract leg also for configs 3 / 4")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the strain-extract leg, the FASTQ ingest leg, "
+                         "the CPU baseline (and its check of the GPU counters), the stream-copy and PMC traffic figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample time (0 = skip; --full only)")
+    ap.add_argument("--no-extract", action="store_true", help="skip the strain-extract leg (kernel experiments; --full only)")
+    ap.add_argument("--extract", action="store_true",
+                    help="run the strain-extract leg: with --full also for configs 3 / 4, without it the only leg after the steps")
     ap.add_argument("--ingest-pairs", type=int, default=4_000_000,
-                    help="pairs written as FASTQ text and timed through the native ingest (0 = skip)")
+                    help="pairs written as FASTQ text and timed through the native ingest (0 = skip; --full only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[args.config]
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -249,7 +261,8 @@ def main():
     n_nodes = len(g.seqs)
     dense_bytes = 2 * n_nodes * n_nodes * 4
     counters = [host.PeCounter(ctx) for _ in range(2 if use_dist else 1)]
-    if rank == 0 and (cfg["extract"] or args.extract) and not args.no_extract:
+    want_extract = ((args.full and cfg["extract"]) or args.extract) and not args.no_extract
+    if rank == 0 and want_extract:
         counters[0].reserve_link_table()  # (as the pipeline does where it makes its counters: pe_inference.count_links)
     main_stream = torch.cuda.current_stream()
     side_stream = torch.cuda.Stream() if use_dist else None
@@ -414,12 +427,15 @@ def main():
             keys = sorted({k for t in tims for k in t})
             out["exchange_timing"] = {k: float(np.mean([t[k] for t in tims if k in t])) for k in keys}
             out["exchange_timing"]["exchanges"] = len(tims)
-        out["roofline"].update(pmc_traffic(args.config, R, kernel_name) if not args.dirty else {"traffic": None})
-        out["roofline"].update(stream_copy(dev, achieved))
-        want_extract = (cfg["extract"] or args.extract) and not args.no_extract
+        if args.dump_outputs:
+            out["outputs_dumped"] = dump_outputs(args.dump_outputs, counter)
+        if args.full:
+            out["roofline"].update(pmc_traffic(args.config, R, kernel_name) if not args.dirty else {"traffic": None})
+            out["roofline"].update(stream_copy(dev, achieved))
         if not want_extract:
             out["strain_extract_s"] = None
-            out["strain_extract"] = {"skipped": "--no-extract" if args.no_extract else "configs 3/4 run it with --extract"}
+            out["strain_extract"] = {"skipped": "--no-extract" if args.no_extract else
+                                     "configs 3/4 run it with --extract" if args.full else "run with --full or --extract"}
         else:
             try:
                 ex = strain_extract(ctx, counter, pre, names, logger, work_dir, genomes=st.genomes)
@@ -433,9 +449,9 @@ def main():
                 out["strain_extract_s"] = None
                 out["strain_extract"] = {"error": repr(err)}
                 extract_failed = True
-        if world == 1 and args.ingest_pairs > 0 and not args.no_extract:
+        if args.full and world == 1 and args.ingest_pairs > 0 and not args.no_extract:
             out["fastq_ingest"] = fastq_ingest(ctx, host, st, cum, seed, L, k, sub_thresh, n_thresh, min(args.ingest_pairs, R), work_dir)
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(ctx, host, st, g, cum, seed, L, k, sub_thresh, n_thresh, R, args.cpu_seconds, args.config)
         print(json.dumps(out))
     if use_dist:
@@ -443,8 +459,92 @@ def main():
 
         dist.barrier()
         dist.destroy_process_group()
+    import shutil
+
+    shutil.rmtree(work_dir, ignore_errors=True)
     if extract_failed:
         sys.exit(1)
+
+
+# --dump-outputs: a matrix of at most this many cells is written whole, a larger one as this many cells drawn by
+# numpy.random.default_rng(DUMP_SEED) (2 x 16 MiB in float64 either way)
+DUMP_CELLS = 1 << 21
+DUMP_SEED = 20250101
+
+
+def dump_outputs(out_dir, counter):
+    """What the last timed step computed, as a caller of ``PeCounter.result()`` receives it (node_mat, short_mat, the
+    three read totals; the caller's node numbering), written as DIR/<name>.npy in float64 -- every value is an integer
+    below 2**53, so exact.  node_mat / short_mat with at most DUMP_CELLS cells are written whole; of larger ones the
+    same seeded sample of cells (``<name>_sample``: flat indices of the N x N matrix drawn by default_rng(DUMP_SEED),
+    sorted) together with the row and column sums of node_mat and the row sums of the symmetric short_mat
+    (short_mat + short_mat.T less its diagonal), all read on the device: the matrices of configs[4] are 2 x 12 GB.
+    Returns the names and sizes for the result line."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = counter.n
+    mats, wide = counter.mats, counter.wide
+    files = {}
+
+    def save(name, arr):
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        files[name] = list(arr.shape)
+
+    node_mat = short_mat = None
+    if n * n <= DUMP_CELLS:
+        node_mat, short_mat, stats = counter.result()
+        save("node_mat", node_mat)
+        save("short_mat", short_mat)
+    else:
+        stats = tuple(int(x) for x in counter.stats.cpu().tolist())
+    save("stats", np.array(stats))
+
+    dev = mats.device
+    rank = torch.from_numpy(counter.node_rank if counter.node_rank is not None else np.arange(n, dtype=np.int64)).to(dev)
+
+    def cells(m, a, b):  # uint32 counts (+ folded int64 totals) at internal cells (a, b), as int64
+        flat = mats[m].reshape(-1)
+        i = a * mats.shape[-1] + b
+        v = flat[i].to(torch.int64) & 0xFFFFFFFF
+        if wide is not None:
+            v += wide[m].reshape(-1)[i]
+        return v
+
+    # row / column sums in the internal numbering, a slab of rows at a time (no int64 copy of a whole matrix)
+    sums = []
+    for m in (0, 1):
+        rows = torch.zeros(n, dtype=torch.int64, device=dev)
+        cols = torch.zeros(n, dtype=torch.int64, device=dev)
+        for lo in range(0, n, 1024):
+            hi = min(n, lo + 1024)
+            slab = mats[m, lo:hi, :n].to(torch.int64) & 0xFFFFFFFF
+            if wide is not None:
+                slab += wide[m, lo:hi, :n]
+            rows[lo:hi] = slab.sum(1)
+            cols += slab.sum(0)
+            del slab
+        sums.append((rows, cols))
+    idx = torch.arange(n, dtype=torch.int64, device=dev)
+    save("node_mat_row_sums", sums[0][0][rank].cpu().numpy())
+    save("node_mat_col_sums", sums[0][1][rank].cpu().numpy())
+    short_sym = sums[1][0] + sums[1][1] - cells(1, idx, idx)
+    save("short_mat_sym_row_sums", short_sym[rank].cpu().numpy())
+
+    if node_mat is None:
+        flat = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n * n, size=DUMP_CELLS, dtype=np.int64))
+        f = torch.from_numpy(flat).to(dev)
+        u, v = f // n, f % n
+        a, b = rank[u], rank[v]
+        save("node_mat_sample", cells(0, a, b).cpu().numpy())
+        if counter.node_rank is None:
+            short = cells(1, u, v)
+        else:  # (PeCounter.user_order: mirrored, then the upper triangle of the caller's numbering)
+            short = torch.where(a == b, cells(1, a, a), cells(1, a, b) + cells(1, b, a))
+            short = torch.where(u <= v, short, torch.zeros_like(short))
+        save("short_mat_sample", short.cpu().numpy())
+    return files
 
 
 def launch_ranks(n):

@@ -991,3 +991,51 @@ def test_counter_matrices_come_back_in_the_callers_numbering():
     want_short[0, 3] += 5
     node, short, _ = c.result()
     assert np.array_equal(node, want_node) and np.array_equal(short, want_short)
+
+
+@pytest.mark.parametrize("n,numbered,folded", [(40, True, True), (1500, True, True), (1500, False, False)])
+def test_bench_dump_outputs_are_what_result_returns(tmp_path, n, numbered, folded):
+    """bench.py --dump-outputs on CPU counters: node_mat / short_mat whole when they are small, else the seeded sample
+    of cells, plus the row sums -- each equal to what ``PeCounter.result()`` hands a caller, also under an index
+    numbering of its own, with cells above 2^31 and with folded int64 totals."""
+    import torch
+
+    import bench
+
+    rng = np.random.default_rng(n)
+    c = _cpu_counter(n, 0)
+    if numbered:
+        order = rng.permutation(n)
+        rank = np.empty(n, dtype=np.int64)
+        rank[order] = np.arange(n)
+        c.node_order, c.node_rank = order, rank
+    node = rng.integers(0, 50, size=(n, n)) * (rng.random((n, n)) < 0.3)
+    short = np.triu(rng.integers(0, 50, size=(n, n)) * (rng.random((n, n)) < 0.3))  # (smaller, larger) internal number
+    node[1, 2] = 2 ** 31 + 7
+    c.mats.copy_(torch.from_numpy(np.stack([node, short]).astype(np.uint32).view(np.int32)))
+    c.stats.copy_(torch.tensor([3, 1, 4]))
+    if folded:
+        c.fold()
+        c.mats.copy_(torch.from_numpy(np.stack([node, short]).astype(np.uint32).view(np.int32)))
+    want_node, want_short, want_stats = c.result()
+    files = bench.dump_outputs(str(tmp_path), c)
+
+    def load(name):
+        arr = np.load(str(tmp_path / (name + ".npy")))
+        assert arr.dtype == np.float64 and list(arr.shape) == files[name]
+        return arr
+
+    assert sum(os.path.getsize(str(tmp_path / (k + ".npy"))) for k in files) <= 64 << 20
+    assert tuple(load("stats")) == want_stats
+    assert np.array_equal(load("node_mat_row_sums"), want_node.sum(1))
+    assert np.array_equal(load("node_mat_col_sums"), want_node.sum(0))
+    sym = want_short + want_short.T - np.diag(np.diag(want_short))
+    assert np.array_equal(load("short_mat_sym_row_sums"), sym.sum(1))
+    if n * n <= bench.DUMP_CELLS:
+        assert np.array_equal(load("node_mat"), want_node) and np.array_equal(load("short_mat"), want_short)
+        assert "node_mat_sample" not in files
+    else:
+        cells = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n * n, size=bench.DUMP_CELLS, dtype=np.int64))
+        assert np.array_equal(load("node_mat_sample"), want_node.reshape(-1)[cells])
+        assert np.array_equal(load("short_mat_sample"), want_short.reshape(-1)[cells])
+        assert "node_mat" not in files

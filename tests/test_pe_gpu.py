@@ -944,6 +944,50 @@ def test_bench_step_with_two_ranks_on_one_gpu(tmp_path):
     assert 0 < out["exchange_timing"]["occupied_stretches_of_the_union"] < 0.5 * out["exchange_timing"]["stretches"]
 
 
+def _bench_line(args, timeout=900):
+    proc = subprocess.run([sys.executable, "bench.py"] + args, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain `bench.py --dump-outputs DIR` run: no leg after the timed steps, and the counters of its last step written
+    as float64 arrays -- the same arrays from two runs with the same arguments, agreeing with the line's pe_stats."""
+    runs = []
+    for r in range(2):
+        d = tmp_path / ("out%d" % r)
+        out = _bench_line(["--gpus", "1", "--config", "1", "--pairs", "200000", "--steps", "3", "--warmup", "1",
+                           "--dump-outputs", str(d)])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "pairs/s" and out["higher_is_better"] is True
+        assert abs(out["value"] - 200000 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+        assert "cpu_baseline" not in out and "fastq_ingest" not in out and out["strain_extract_s"] is None
+        assert "measured_stream_copy_GBs" not in out["roofline"]
+        arrays = {name[:-4]: np.load(str(d / name)) for name in os.listdir(str(d))}
+        assert sorted(arrays) == sorted(out["outputs_dumped"]) and all(a.dtype == np.float64 for a in arrays.values())
+        st = out["pe_stats"]
+        assert tuple(arrays["stats"]) == (st["n_reads"], st["short_reads"], st["used_reads"])
+        n = out["config"]["nodes"]
+        assert arrays["node_mat"].shape == arrays["short_mat"].shape == (n, n)  # (853 nodes: whole matrices)
+        assert arrays["node_mat"].sum() == st["node_mat_sum"] > 0 and arrays["short_mat"].sum() == st["short_mat_sum"] > 0
+        assert np.array_equal(arrays["node_mat_row_sums"], arrays["node_mat"].sum(1))
+        runs.append(arrays)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
+
+
+def test_bench_full_run_keeps_every_leg():
+    """`bench.py --full`: the legs a plain run leaves out are still measured -- the strain-extract leg, the FASTQ ingest,
+    the CPU baseline with its check of the GPU counters, the stream-copy figure."""
+    out = _bench_line(["--gpus", "1", "--config", "0", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "1",
+                       "--ingest-pairs", "100000"])
+    assert out["strain_extract_s"] is not None and out["strain_extract"]["strains"] > 0
+    assert out["fastq_ingest"]["pairs"] == 100000
+    assert out["cpu_baseline"]["gpu_matches_on_sample"] is True
+    assert out["roofline"]["measured_stream_copy_GBs"] > 0
+
+
 def test_two_gpu_rccl_step_and_sharded_drop_in(tmp_path):
     """On a box with two or more GPUs: `bench.py --gpus 2` and the sharded PE drop-in with one rank per GPU and RCCL as the
     collective (backend "nccl" IS RCCL on ROCm) -- the path the 1-GPU boxes of this pool can only run over gloo.  Skips

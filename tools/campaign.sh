@@ -63,6 +63,6 @@ case "$cmd" in
     python -m pytest tests -m gpu -q 2>&1 | grep -v "^RCCL\|^HIP ver\|^ROCm\|^Host\|^Librccl" | tail -30 > gpurun_out/${tag}_gpu_tests.log; tail -3 gpurun_out/${tag}_gpu_tests.log ;;
   final)
     tag="${1:-r5}"
-    bash "$0" suite $tag; bash "$0" fuzz 420 200 300; bash "$0" profiles "2 1 3 4 0" $tag; bash "$0" bench "2 1 0 3 4" $tag; bash "$0" extract "2 3 4" $tag ;;
+    bash "$0" suite $tag; bash "$0" fuzz 420 200 300; bash "$0" profiles "2 1 3 4 0" $tag; bash "$0" bench "2 1 0 3 4" $tag --full; bash "$0" extract "2 3 4" $tag ;;
   *) echo "unknown subcommand $cmd"; exit 2 ;;
 esac

@@ -4,7 +4,7 @@
 R="$GRAFT_REPO_ROOT"; TAG="${1:-r2}"; CFG="${2:-2}"; shift; shift
 OUT="$R/gpurun_out/prof_$TAG"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$R/bench.py" --config $CFG --steps 5 --warmup 1 --cpu-seconds 0 --ingest-pairs 0 "$@" > "$OUT/trace_bench.json" 2> "$OUT/trace.err"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$R/bench.py" --config $CFG --steps 5 --warmup 1 --full --cpu-seconds 0 --ingest-pairs 0 "$@" > "$OUT/trace_bench.json" 2> "$OUT/trace.err"
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -- python3 "$R/bench.py" --config $CFG --steps 2 --warmup 1 --cpu-seconds 0 --no-extract "$@" > "$OUT/pmc_fetch_bench.json" 2> "$OUT/pmc_fetch.err"
 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -- python3 "$R/bench.py" --config $CFG --steps 2 --warmup 1 --cpu-seconds 0 --no-extract "$@" > "$OUT/pmc_write_bench.json" 2> "$OUT/pmc_write.err"
 timeout 600 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_ATOMIC_sum --output-format csv -d "$OUT/pmc_l2" -- python3 "$R/bench.py" --config $CFG --steps 2 --warmup 1 --cpu-seconds 0 --no-extract "$@" > "$OUT/pmc_l2_bench.json" 2> "$OUT/pmc_l2.err"
