@@ -84,15 +84,14 @@ def _rank_main(rank, world, port, case_dir, k, q):
     # the oracle stands in for the device kernel here: what is under test is the shard + reduce logic
     node, short, stats = pe_oracle_c.Oracle(seqs, k).count_pairs(f[lo:hi], r[lo:hi])
     mats = torch.from_numpy(np.stack([node, short]).astype(np.int32))
-    st = torch.from_numpy(stats.astype(np.int64))
-    vdist.all_reduce_counts(mats, st)
+    _, st = vdist.sum_counts(mats, tail=torch.from_numpy(stats.astype(np.int64)))
     if rank == 0:
         q.put((mats.numpy().astype(np.int64), st.numpy()))
     dist.barrier()
     dist.destroy_process_group()
 
 
-def test_two_rank_read_sharding_and_allreduce_gloo():
+def test_two_rank_read_sharding_and_sum_counts_gloo():
     import torch.multiprocessing as mp
 
     name, d, meta = [c for c in pe_cases() if c[0] == "hiv_like_k55"][0]
@@ -114,41 +113,38 @@ def test_two_rank_read_sharding_and_allreduce_gloo():
 
 
 def _rank_overlap(rank, world, port, q):
-    """bench.py's step scheme on CPU tensors: two counter buffers, the all-reduce of step i is only
-    waited for when its buffer comes up again (step i+2) or at the end."""
-    import torch
+    """bench.py's step scheme on CPU tensors: two counters summed with all_reduce(predict=True), the sum of step i is only
+    settled when its buffer comes up again (step i+2) or at the end."""
     import torch.distributed as dist
 
-    from vstrains_amd import dist as vdist
-
     dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    bufs = [(torch.zeros((2, 5, 5), dtype=torch.int32), torch.zeros(3, dtype=torch.int64)) for _ in range(2)]
-    pending = [[], []]
+    counters = [_cpu_counter(16, 0) for _ in range(2)]  # (2 x 16 x 16 cells: 8 stretches, more than one slab)
     seen = []
     for step in range(5):
-        b = step % 2
-        for wk in pending[b]:
-            wk.wait()
+        c = counters[step % 2]
+        c.settle()
         if step >= 2:
-            seen.append((step - 2, bufs[b][0].clone(), bufs[b][1].clone()))  # result of step-2, now final
-        mats, st = bufs[b]
-        mats.zero_()
-        st.zero_()
-        mats += (rank + 1) * (step + 1)
-        st += rank + 10 * step
-        pending[b] = vdist.all_reduce_counts_async(mats, st)
-    for b in range(2):
-        for wk in pending[b]:
-            wk.wait()
-    seen.append((3, bufs[1][0].clone(), bufs[1][1].clone()))
-    seen.append((4, bufs[0][0].clone(), bufs[0][1].clone()))
+            seen.append((step - 2, c.mats.clone(), c.stats.clone()))  # result of step-2, now final
+        c.mats.zero_()
+        c.stats.zero_()
+        c.pairs_in_buffer = 10
+        c.mats += (rank + 1) * (step + 1)
+        c.stats += rank + 10 * step
+        for other in counters:  # (the two buffers share what is known about the union, as in bench.py)
+            if c._xstate_cap() is None and other._xstate_cap() is not None:
+                c._xstate_cap(other._xstate_cap())
+        c.all_reduce(predict=True)
+    for c in counters:
+        c.settle()
+    seen.append((3, counters[1].mats.clone(), counters[1].stats.clone()))
+    seen.append((4, counters[0].mats.clone(), counters[0].stats.clone()))
     if rank == 0:
         q.put([(i, m.numpy(), s_.numpy()) for i, m, s_ in seen])
     dist.barrier()
     dist.destroy_process_group()
 
 
-def test_overlapped_allreduce_with_two_buffers_gloo():
+def test_overlapped_predicted_exchange_with_two_counters_gloo():
     import torch.multiprocessing as mp
 
     ctxm = mp.get_context("spawn")
@@ -237,13 +233,14 @@ def _rank_range(rank, world, port, q):
         _set_cell(c, 0, 1, 1, 3)
     c.all_reduce()
     out.append(("mixed", c.wide is not None, c.pairs_in_buffer, c.result()))
-    # the overlapped form refuses what it cannot hold
+    # the predicted form refuses what it cannot hold
     d = _cpu_counter(4, 2 ** 30)
+    d._xstate_cap(64)
     try:
-        d.all_reduce_async()
-        out.append(("async", False, 0, None))
+        d.all_reduce(predict=True)
+        out.append(("predicted", False, 0, None))
     except OverflowError:
-        out.append(("async", True, 0, None))
+        out.append(("predicted", True, 0, None))
     # the two exchanges on random mostly-zero counters, cell for cell (values beyond 2^31 included): a banded one (few
     # occupied stretches: compact), a dense one (falls back to the whole buffer), sizes that leave a tail of < 64 cells
     import torch
@@ -260,10 +257,10 @@ def _rank_range(rank, world, port, q):
                 m[0, 3, 4] = -7  # (uint32 2^32 - 7 in int32 storage)
             dense, compact = m.clone(), m.clone()
             dist.all_reduce(dense, op=dist.ReduceOp.SUM)
-            modes.append(vdist.sum_counts_compact(compact))
+            modes.append(vdist.sum_counts(compact)[0])
             assert torch.equal(dense, compact)
             off = m.clone()
-            assert vdist.sum_counts_compact(off, allow_compact=False) == "dense" and torch.equal(off, dense)
+            assert vdist.sum_counts(off, flags=vdist.flag_bytes(no_compact=True))[0] == "dense" and torch.equal(off, dense)
     assert modes[:4] == ["compact", "dense", "compact", "dense"], modes
     assert vdist.strong_share(10, 0, 2) == (0, 5) and vdist.strong_share(11, 1, 2) == (5, 11)
     if rank == 0:
@@ -273,9 +270,9 @@ def _rank_range(rank, world, port, q):
 
 
 @pytest.mark.parametrize("exchange", ["dense", "compact"])
-def test_counter_range_across_two_ranks_gloo(exchange, monkeypatch):
+def test_counter_range_and_sum_counts_across_two_ranks_gloo(exchange, monkeypatch):
     """... and the same sums when the ranks sum the occupied 64-cell stretches of their counters instead of the whole
-    buffers (dist.sum_counts_compact: what PeCounter.all_reduce does by default; "dense": turned off)."""
+    buffers (dist.sum_counts: what PeCounter.all_reduce does by default; "dense": turned off)."""
     import torch.multiprocessing as mp
 
     monkeypatch.setenv("VS_COMPACT_ALLREDUCE", "1" if exchange == "compact" else "0")
@@ -320,7 +317,7 @@ def _rank_exchange_shapes(rank, world, port, q):
         dense, compact = m.clone(), m.clone()
         dist.all_reduce(dense, op=dist.ReduceOp.SUM)
         timing = {}
-        how = vdist.sum_counts_compact(compact, tile_map=tiles, timing=timing)
+        how = vdist.sum_counts(compact, tile_map=tiles, timing=timing)[0]
         assert torch.equal(dense, compact), n
         res.append((n, how, timing["occupied_stretches_of_the_union"] > vdist.SLAB_STRETCHES, sorted(k for k in timing if isinstance(timing[k], float))))
     # (2) one rank cannot get its staging buffer: every rank takes the dense ring, nobody is left in a collective
@@ -332,18 +329,18 @@ def _rank_exchange_shapes(rank, world, port, q):
     m[0, rank, 3] = 5 + rank
     dense = m.clone()
     dist.all_reduce(dense, op=dist.ReduceOp.SUM)
-    how = vdist.sum_counts_compact(m)
+    how = vdist.sum_counts(m)[0]
     assert torch.equal(dense, m)
     res.append(("no staging buffer on rank 1", how))
     vdist._staging_buffer = plain
-    assert vdist.sum_counts_compact(m.clone()) == "compact"  # (and the next call is compact again)
+    assert vdist.sum_counts(m.clone())[0] == "compact"  # (and the next call is compact again)
     if rank == 0:
         q.put(res)
     dist.barrier()
     dist.destroy_process_group()
 
 
-def test_compact_exchange_from_the_tile_map_in_slabs_and_without_a_staging_buffer():
+def test_sum_counts_from_the_tile_map_in_slabs_and_without_a_staging_buffer():
     """Round 5: the occupancy of a large counter comes from its dirty-tile map (no scan of the
     buffer), the occupied stretches go through the ring in bounded slabs (256 MB of staging whatever the union's size), and
     a rank that cannot allocate its staging buffer tells its peers before any of them enters the collective -- all take
@@ -367,7 +364,7 @@ def test_compact_exchange_from_the_tile_map_in_slabs_and_without_a_staging_buffe
 
 
 def _rank_packed_eight(rank, world, port, q):
-    """Eight gloo ranks through PeCounter.all_reduce / dist.sum_counts_packed (r6: two collectives per sum)."""
+    """Eight gloo ranks through PeCounter.all_reduce (two collectives per sum)."""
     import os
 
     import torch
@@ -421,13 +418,18 @@ def _rank_packed_eight(rank, world, port, q):
     _set_cell(c, 0, 1, 1, 2 ** 28 + rank)
     c.all_reduce()
     res["nofold"] = (c.wide is None, c.pairs_in_buffer, int(c.result()[0][1, 1]))
-    # (4) only rank 0 needs the sums (the drop-in's writer): reduce instead of all-reduce
-    c = _cpu_counter(n, 5)
-    c.mats.copy_(banded(300 + rank, 6))
-    mine = c.mats.clone()
-    want = dense_sum(c.mats)
-    c.all_reduce(dst=0)
-    res["dst"] = bool(torch.equal(c.mats, want)) if rank == 0 else bool(torch.equal(c.mats, mine))
+    # (4) the drop-in's sum: every rank holds the full counters, stats and pairs afterwards, through the compact form and
+    # through the dense branch (a veto)
+    for veto in (False, True):
+        c = _cpu_counter(n, 5 + rank)
+        c.mats.copy_(banded(300 + rank, 6))
+        c.stats += torch.tensor([1, rank, 2], dtype=torch.int64)
+        want = dense_sum(c.mats)
+        if veto and rank == 6:
+            os.environ["VS_COMPACT_ALLREDUCE"] = "0"
+        c.all_reduce()
+        os.environ.pop("VS_COMPACT_ALLREDUCE", None)
+        res["every rank, veto" if veto else "every rank"] = (c.last_all_reduce, bool(torch.equal(c.mats, want)), c.stats.tolist(), c.pairs_in_buffer)
     # (5) the steady state of fixed-size steps: the first exchange learns the union's size, the following ones are PREDICTED
     # (no host wait, two collectives); a step whose union outgrows the prediction is completed by settle()
     c = _cpu_counter(n, 0)
@@ -453,10 +455,10 @@ def _rank_packed_eight(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def test_packed_exchange_eight_ranks_gloo():
+def test_packed_exchange_eight_ranks_full_sums_on_every_rank_gloo():
     """Round 6: PeCounter.all_reduce is TWO collectives -- MAX over [occupancy | flag bytes],
     SUM over [occupied stretches | stats row] -- on eight ranks with uneven shards, a rank without pairs, a rank that vetoes
-    the compact form, counters beyond 2^31 that force the fold, a reduce to the writer only, and the predicted steady state
+    the compact form, counters beyond 2^31 that force the fold, the full sums on every rank, and the predicted steady state
     (no host wait; a union that outgrows the prediction is repaired by settle())."""
     import torch.multiprocessing as mp
 
@@ -480,7 +482,8 @@ def test_packed_exchange_eight_ranks_gloo():
         wide, pairs, s77, n29, _ = r["fold"]
         assert wide and pairs == 0 and s77 == sum(2 ** 32 - 1 - k for k in range(8)) and n29 == sum(2 ** 31 + k for k in range(8))
         assert r["nofold"] == (True, 2 ** 25 + 7 * 17, 8 * 2 ** 28 + 28)
-        assert r["dst"]
+        assert r["every rank"] == ("compact", True, [8, 28, 16], sum(5 + k for k in range(8)))
+        assert r["every rank, veto"] == ("dense", True, [8, 28, 16], sum(5 + k for k in range(8)))
         st = r["steady"]
         assert st[0][0] == 2 and st[0][1] == 1                    # the first exchange asks the device once
         for coll, waits, same, stats, coll_after in st[1:]:
@@ -489,12 +492,90 @@ def test_packed_exchange_eight_ranks_gloo():
         assert st[4][4] == 2
 
 
-def test_async_allreduce_without_process_group_is_a_no_op():
+def _run_ranks(target, world, port_offset, timeout=120):
+    """``target(rank, world, port, q)`` on ``world`` spawned gloo ranks, each putting one result: -> the results by rank.
+    The ranks are killed if that fails (a rank left waiting in a collective would outlive the test)."""
+    import torch.multiprocessing as mp
+
+    ctxm = mp.get_context("spawn")
+    q = ctxm.Queue()
+    port = 29500 + ((os.getpid() + port_offset) % 500)
+    procs = [ctxm.Process(target=target, args=(rk, world, port, q)) for rk in range(world)]
+    for p in procs:
+        p.start()
+    try:
+        got = dict(q.get(timeout=timeout) for _ in range(world))
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+    return [got[rk] for rk in range(world)]
+
+
+def _rank_asymmetric_staging(rank, world, port, q):
+    import torch
+    import torch.distributed as dist
+
+    from vstrains_amd import dist as vdist
+
+    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
+    vdist._staging.clear()
+    if rank == 1:  # (an earlier, larger exchange left this rank's cached staging buffer bigger than its peer's)
+        vdist._staging_buffer(torch.zeros((1, 64), dtype=torch.int32), 1000)
+    vdist.SLAB_STRETCHES = 5
+    c = _cpu_counter(100, 10)  # (2 x 100 x 100 cells: 312 stretches)
+    c.mats[0, :15, :] = rank + 1  # (24 occupied stretches, and one more per rank: six slabs)
+    c.mats[1, 40 + rank, 7] = 3
+    want = c.mats.clone()
+    dist.all_reduce(want, op=dist.ReduceOp.SUM)
+    c.all_reduce()
+    q.put((rank, (c.last_all_reduce, c.last_collectives, bool(torch.equal(c.mats, want)))))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_slabs_are_cut_alike_whatever_each_rank_has_staged_gloo():
+    """The slab height of the compact exchange follows from the counter's size alone: a rank whose cached staging buffer
+    is larger than its peer's cuts the union into the same slabs, and issues the same SUMs."""
+    res = _run_ranks(_rank_asymmetric_staging, 2, 401)
+    assert res[0] == res[1] == ("compact", 1 + 6, True), res
+
+
+def _rank_settle_bound(rank, world, port, q):
+    import torch.distributed as dist
+
+    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
+    # 2 * (2^30 - 1) pairs * 2 ranks fit in a uint32 cell, so rank 0's own check passes; the agreed bound on the largest
+    # rank's pairs (bit length 30, top byte 255: 2^30) does not
+    c = _cpu_counter(100, 2 ** 30 - 1 if rank == 0 else 1000)
+    c._xstate_cap(64)
+    c.mats[0, 3, rank] = 5
+    c.all_reduce(predict=True)
+    try:
+        c.settle()
+        raised = False
+    except RuntimeError:
+        raised = True
+    q.put((rank, raised))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_settle_raises_on_every_rank_when_the_agreed_bound_does_not_fit_gloo():
+    assert _run_ranks(_rank_settle_bound, 2, 457) == [True, True]
+
+
+def test_sum_without_process_group_is_a_no_op():
     import torch
 
     from vstrains_amd import dist as vdist
 
-    assert vdist.all_reduce_counts_async(torch.zeros((2, 2, 2), dtype=torch.int32), torch.zeros(3, dtype=torch.int64)) == []
+    mats, tail = torch.arange(2 * 9 * 9, dtype=torch.int32).view(2, 9, 9), torch.tensor([1, 2, 3])
+    how, out = vdist.sum_counts(mats, tail=tail)
+    assert how is None and out is tail and torch.equal(mats, torch.arange(2 * 9 * 9, dtype=torch.int32).view(2, 9, 9))
 
 
 def test_shard_range_covers_everything_once():

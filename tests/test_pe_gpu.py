@@ -860,7 +860,7 @@ def test_sharded_drop_in_two_ranks_on_one_gpu(tmp_path, exchange, ranks):
     directory and writes the files -- byte-identical to the reference's.  One GPU here, so both
     ranks use device 0 and the sum goes through gloo (RCCL needs a device per rank; the RCCL call
     itself is exercised by the one-rank tests and by bench.py --gpus N).  (r6) Also with EIGHT ranks on the one device: eight
-    cooperative FASTQ shards, the packed two-collective sum reduced to rank 0 (the only rank that writes)."""
+    cooperative FASTQ shards, the packed two-collective sum on every rank (rank 0 alone writes)."""
     import socket
 
     name, d, meta = [c for c in pe_cases() if c[0] == "errors_k21"][0]
@@ -868,7 +868,7 @@ def test_sharded_drop_in_two_ranks_on_one_gpu(tmp_path, exchange, ranks):
     out.mkdir()
     (out / "stale_file").write_text("x")  # rank 0 wipes the directory (PE_Inference.py:93-96); nobody else may
     # ("compact": the ranks sum the occupied 64-cell stretches of their counters instead of the whole buffers,
-    # dist.sum_counts_compact -- the default; "dense": turned off for every rank)
+    # dist.sum_counts -- the default; "dense": turned off for every rank)
     env = dict(os.environ, VS_DIST_BACKEND="gloo", VS_DIST_DEVICE="0", VS_COMPACT_ALLREDUCE="1" if exchange == "compact" else "0")
     for attempt in range(3):  # (a port that was free when asked for may be taken a moment later: ask again)
         with socket.socket() as sk:
@@ -1046,7 +1046,7 @@ def test_randomized_campaign_short(mode):
 
 def test_occupied_stretches_kernel_equals_the_torch_expression(host, ctx):
     """vs_counts_occupied (round 5: the one pass over a counter buffer that finds its non-zero 64-cell stretches for the
-    multi-GPU exchange, dist.sum_counts_compact) against the torch expression it replaces, on uint32 counters and int64
+    multi-GPU exchange, dist.sum_counts) against the torch expression it replaces, on uint32 counters and int64
     totals, banded, dense, empty, and sizes that are no multiple of anything."""
     import torch
 

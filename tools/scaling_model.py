@@ -50,7 +50,7 @@ def main():
                                 "host_and_launch_ms": d["ms_per_step"] - r["kernel_ms_avg"] - r["accumulate_ms_avg"] - r["locus_sort_ms_avg"] - r["slow_kernel_ms_avg"]}
         print(n, res["share"][str(n)], flush=True)
     # the exchange's local phases, alone on the device: this process as a one-rank gloo group, the config's counters of a
-    # per-rank share in HBM, dist.sum_counts_compact with its phase timer (a device synchronisation after every phase --
+    # per-rank share in HBM, dist.sum_counts with its phase timer (a device synchronisation after every phase --
     # nothing else runs, so the waits are the phases').  The all-reduce of a one-rank group is free: the ring is modelled.
     ex = {}
     code = r"""
@@ -78,8 +78,8 @@ for rep in range(8):
     t = {}
     # (r6) the packed exchange: the first call learns the union's size, the others are PREDICTED -- the steady state of the
     # bench's steps: two collectives, no host wait
-    how, _, _ = vdist.sum_counts_packed(c.mats, tail=stats, tile_map=c.tile_map, timing=t, occupancy_fn=c._occupied, state=state, predict=rep > 0)
-    vdist.settle_exchange(state)
+    how, _ = vdist.sum_counts(c.mats, tail=stats, tile_map=c.tile_map, timing=t, occupancy_fn=c._occupied, state=state, predict=rep > 0)
+    vdist.settle(state)
     t["collectives"] = state.collectives
     if rep == 0:
         t0 = t

@@ -5,6 +5,7 @@ index, and one sum all-reduce (RCCL over xGMI when the backend is "nccl") folds 
 Integer addition commutes: any partition gives bit-identical results."""
 from __future__ import annotations
 
+import time
 from typing import Tuple
 
 
@@ -21,38 +22,6 @@ def group_size() -> int:
     if dist.is_available() and dist.is_initialized():
         return dist.get_world_size()
     return 1
-
-
-def all_reduce_counts(mats, stats):
-    """In-place sum over ranks of the [2, N, N] counter tensor (int32 storage of uint32 cells, or
-    int64 totals; may be None) and of a small int64 tensor (the 3 stats, or PeCounter's flags)."""
-    import torch.distributed as dist
-
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        if mats is not None:
-            dist.all_reduce(mats, op=dist.ReduceOp.SUM)
-        if stats is not None:
-            dist.all_reduce(stats, op=dist.ReduceOp.SUM)
-
-
-def all_reduce_max(t):
-    """In-place maximum over the ranks of a small tensor."""
-    import torch.distributed as dist
-
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-
-
-def all_reduce_counts_async(mats, stats):
-    """Same sums, enqueued behind the work already on the current stream and NOT waited for: returns
-    the work handles (``w.wait()`` makes the then-current stream wait), or [] when there is no process
-    group.  The caller keeps counting into a second buffer meanwhile (bench.py)."""
-    import torch.distributed as dist
-
-    if not (dist.is_available() and dist.is_initialized()):
-        return []
-    return [dist.all_reduce(mats, op=dist.ReduceOp.SUM, async_op=True),
-            dist.all_reduce(stats, op=dist.ReduceOp.SUM, async_op=True)]
 
 
 # ---- exchange of the occupied stretches only -----------------------------------------------------------------------
@@ -111,19 +80,61 @@ def _occupancy_from_tiles(tile_map, n: int, m: int):
     return occ
 
 
-# One bounded staging buffer per (device, dtype) for the gathered stretches: the exchange walks the occupied stretches in
-# slabs of at most SLAB_STRETCHES, so its transient is bounded (1 GB of int32 cells) whatever the union's size -- a counter
-# of 23.7 GB half occupied used to ask for 12 GB on top of the counters.  (ADVICE r4.)
+# ---- the packed exchange: two collectives per sum ---------------------------------------------------------------------
+#   C1  MAX over ONE uint8 tensor: [occupancy map of the 64-cell stretches (or the counter's dirty-tile map, from which
+#       every rank derives the same occupancy) | FLAG_BYTES flag bytes].  MAX over bytes is OR for 0 / 1 flags.
+#   C2  SUM over ONE staging tensor: [the occupied stretches of the union | one row that carries the caller's small int64
+#       sums -- the three stats, the pairs in the buffers -- as 16-bit limbs in the cells' dtype | the leftover cells].
+# A rank that issued a differently shaped collective than its peers would hang the group or sum garbage, so the exchange
+# is agree -> plan -> execute: everything a rank allocates is taken before C1 (a failure becomes a flag), and every
+# decision after C1 is a function of values every rank holds -- the number of stretches m (same N), the agreed flag bytes
+# and the union's size u.  A union of more than ``slab_rows(m)`` stretches takes one SUM per slab; a dense union, a veto or
+# a rank without staging memory send the whole tensor through the ring, and the tail row after it.
+FLAG_BYTES = 8
+FLAG_NO_COMPACT, FLAG_WIDE, FLAG_NO_STAGING, FLAG_PAIRS_LOG2 = 0, 1, 2, 3
+LIMBS = 4  # 16-bit limbs per int64 of the tail: exact while every addend is below 2^63 and there are fewer than 2^15 ranks
+U32_LIMIT = 2 ** 32
+
+
+def flag_bytes(no_compact: bool = False, wide: bool = False, pairs: int = 0):
+    """One rank's flag bytes (uint8 [FLAG_BYTES]): it vetoes the compact form, it holds int64 totals, and its pairs in the
+    buffers as (bit length, top eight bits) -- MAX over the bytes bounds the largest rank's pairs from above."""
+    import torch
+
+    fl = torch.zeros(FLAG_BYTES, dtype=torch.uint8)
+    fl[FLAG_NO_COMPACT] = 1 if no_compact else 0
+    fl[FLAG_WIDE] = 1 if wide else 0
+    bits = int(pairs).bit_length()
+    fl[FLAG_PAIRS_LOG2] = bits
+    fl[FLAG_PAIRS_LOG2 + 1] = (pairs >> (bits - 8)) if bits > 8 else pairs
+    return fl
+
+
+def must_fold(fl, world: int) -> bool:
+    """From the agreed flag bytes (a list): some rank holds int64 totals, or uint32 cells cannot hold the sum -- a cell grows
+    by at most 2 per pair, and the bound on the largest rank's pairs times the ranks says how many pairs there may be."""
+    bits, top = int(fl[FLAG_PAIRS_LOG2]), int(fl[FLAG_PAIRS_LOG2 + 1])
+    bound = ((top + 1) << (bits - 8)) if bits > 8 else 255
+    return bool(fl[FLAG_WIDE]) or 2 * bound * world >= U32_LIMIT
+
+
+# One staging buffer per (device, dtype), grown only: the exchange walks the occupied stretches in slabs of at most
+# SLAB_STRETCHES, so its transient is bounded (1 GB of int32 cells) whatever the union's size.  (ADVICE r4.)
 SLAB_STRETCHES = 1 << 22
 _staging = {}
 
 
-def _staging_buffer(head, want_rows: int):
-    """[rows, 64] buffer of ``head``'s dtype on its device, rows = min(want_rows, SLAB_STRETCHES + 1), grown only; None when
-    the allocation fails (the caller says so in the flag bytes of the first collective: no rank is left waiting)."""
+def slab_rows(m: int) -> int:
+    """Stretches per SUM for a counter of ``m`` stretches: a compact union (u <= m / 2) fits in one slab while m / 2 <=
+    SLAB_STRETCHES.  A function of m alone, so every rank cuts the union alike."""
+    return min(m // 2 + 1, SLAB_STRETCHES)
+
+
+def _staging_buffer(head, rows: int):
+    """At least ``rows`` rows of 64 cells of ``head``'s dtype on its device; None when the allocation fails (the caller
+    says so in its flag bytes, before the first collective: no rank is left waiting)."""
     import torch
 
-    rows = max(3, min(int(want_rows), SLAB_STRETCHES + 2))
     key = (str(head.device), head.dtype)
     buf = _staging.get(key)
     if buf is not None and buf.shape[0] >= rows:
@@ -134,21 +145,6 @@ def _staging_buffer(head, want_rows: int):
         return None
     _staging[key] = buf
     return buf
-
-
-# ---- the packed exchange (r6): two collectives per sum ----------------------------------------------------------------
-# a step's exchange was an agreement all-reduce, the occupancy MAX, a host wait on torch.nonzero, a status
-# MAX, the slab SUMs, the stats SUM and the tile-map MAX -- six or seven collectives whose latency on eight ranks nobody has
-# measured.  Now:
-#   C1  MAX over ONE uint8 tensor: [occupancy map of the 64-cell stretches (or the counter's dirty-tile map, from which
-#       every rank derives the same occupancy) | FLAG_BYTES flag bytes].  MAX over bytes is OR for 0 / 1 flags.
-#   C2  SUM over ONE staging tensor: [the occupied stretches of the union | one more row that carries the caller's small
-#       int64 sums -- the three stats, the pairs in the buffers -- as 16-bit limbs in the cells' dtype].
-# (a union of more than SLAB_STRETCHES stretches takes one SUM per slab; a dense union, a veto or a rank without staging
-# memory send the whole tensor through the ring, and the tail row after it.)
-FLAG_BYTES = 8
-FLAG_NO_COMPACT, FLAG_WIDE, FLAG_NO_STAGING, FLAG_PAIRS_LOG2 = 0, 1, 2, 3
-LIMBS = 4  # 16-bit limbs per int64 of the tail: exact while every addend is below 2^63 and there are fewer than 2^15 ranks
 
 
 def _tail_encode(tail, row):
@@ -175,230 +171,192 @@ def _tail_decode(row, k):
 
 
 class ExchangeState:
-    """What a counter keeps between its exchanges: the union size of the last one (the next is staged for 1.25 times that
-    without asking the device), and the unsettled predicted exchange."""
+    """What a counter keeps between its exchanges: ``cap``, the union size the next predicted exchange is staged for (1.25
+    times the last one's, learnt only from an exchange on which every rank held its staging buffer -- the cache keeps it),
+    the predicted exchange that is not settled yet, and the collectives and host waits of the most recent call."""
 
     def __init__(self):
         self.cap = None
         self.pending = None
-        self.collectives = 0   # of the most recent call
+        self.collectives = 0
         self.host_waits = 0
 
 
-def sum_counts_packed(mats, tail=None, flags=None, tile_map=None, timing=None, occupancy_fn=None, state=None, predict=False, dst=None,
-                      on_flags=None):
-    """In-place sum over the ranks of a counter tensor (int32 storage of uint32 cells, or int64 totals), of ``tail`` (small
-    int64 tensor, summed) and OR of ``flags`` (uint8 [FLAG_BYTES]; byte FLAG_PAIRS_LOG2 is MAXed as a number), in TWO
-    collectives (see above).  -> (how, flags_of_all_ranks, summed_tail): how is "compact" or "dense", the same on every rank.
+class Exchange:
+    """One sum over the ranks of a counter tensor (int32 storage of uint32 cells, or int64 totals), of ``tail`` (small int64
+    tensor) and OR of ``flags`` (uint8 [FLAG_BYTES]), from C1 on.  Made by ``agree``; then ``read`` + ``sum``, or
+    ``sum_predicted`` + ``settle``."""
 
-    ``predict`` (needs ``state`` with a union size from an earlier call): no host wait at all -- the gather is sized from
-    the previous union (``torch.nonzero_static``), the device keeps the real size, and ``settle_exchange(state)`` -- called
-    when the sums are consumed, steps later -- looks at it and at the flags and sums the stretches that did not fit then.
-    ``dst``: the SUM collectives reduce to that rank only (the drop-in's writer); the other ranks' tensors keep their own
-    counts.  ``on_flags``: called with the flag bytes of all ranks (a list) once the host has them; if it returns a tensor,
-    THAT is what has to be summed instead (PeCounter folds into int64 totals when the uint32 buffers cannot hold the sum):
-    the exchange starts over on it -- the rare path, two more collectives."""
-    import time
+    def __init__(self, mats, tail, flags, tile_map, timing, occupancy_fn, state):
+        import torch
 
-    import torch
-    import torch.distributed as dist
+        self.mats, self.timing, self.state = mats, timing, state
+        dev = mats.device
+        flat = mats.view(-1)
+        self.m = m = flat.numel() // STRETCH
+        self.head = flat[: m * STRETCH].view(m, STRETCH)
+        self.left = flat[m * STRETCH:]  # the cells behind the last whole stretch (fewer than 64): they ride in a row of their own
+        self.rows = slab_rows(m)
+        self.k_tail = 0 if tail is None else int(tail.numel())
+        assert self.k_tail <= 16
+        mine = torch.zeros(FLAG_BYTES, dtype=torch.uint8, device=dev) if flags is None else flags.to(device=dev, dtype=torch.uint8).clone()
+        t = time.perf_counter()
+        # everything this rank needs BEFORE the first collective: the staging buffer (or a flag that it has none), and the two
+        # rows behind the stretches -- the tail's limbs and the leftover cells
+        self.buf = _staging_buffer(self.head, self.rows + 2) if m else None
+        if m and self.buf is None:
+            mine[FLAG_NO_STAGING] = 1
+        self.extra = torch.zeros((2, STRETCH), dtype=mats.dtype, device=dev)
+        if self.k_tail:
+            _tail_encode(tail, self.extra[0])
+        self.extra[1][: self.left.numel()] = self.left
+        # C1 = [occupancy map (unless the tile map stands for it) | the counter's dirty-tile map, if it keeps one | flag bytes]
+        n = mats.shape[-1]
+        use_tiles = tile_map is not None and mats.dim() == 3 and mats.shape[0] == 2 and mats.shape[1] == n and n >= STRETCH
+        occ_local = None if use_tiles else ((occupancy_fn(self.head) if occupancy_fn is not None else _occupancy(self.head)) if m
+                                            else torch.zeros(0, dtype=torch.uint8, device=dev))
+        n_occ = 0 if occ_local is None else occ_local.numel()
+        n_tiles = 0 if tile_map is None else tile_map.numel()
+        nb = n_occ + n_tiles
+        c1 = torch.empty(nb + FLAG_BYTES, dtype=torch.uint8, device=dev)
+        if n_occ:
+            c1[:n_occ] = occ_local
+        if n_tiles:
+            c1[n_occ:nb] = tile_map
+        c1[nb:] = mine
+        t = self._mark("occupancy", t)
+        self._reduce(c1, "MAX")
+        self._t = self._mark("occupancy_allreduce", t)
+        self.flags = c1[nb:]
+        if n_tiles:
+            tile_map.copy_(c1[n_occ:nb])  # (the sum brings the other ranks' cells: their tiles are dirty here too)
+        self.occ = _occupancy_from_tiles(tile_map, n, m) if use_tiles else c1[:n_occ]
 
-    def mark(name, t0):
-        if timing is not None:
-            if mats.is_cuda:
-                torch.cuda.synchronize(mats.device)
-            timing[name] = timing.get(name, 0.0) + time.perf_counter() - t0
+    def _mark(self, name, t0):
+        import torch
+
+        if self.timing is not None:
+            if self.mats.is_cuda:
+                torch.cuda.synchronize(self.mats.device)
+            self.timing[name] = self.timing.get(name, 0.0) + time.perf_counter() - t0
         return time.perf_counter()
 
+    def _reduce(self, t, op="SUM"):
+        import torch.distributed as dist
+
+        self.state.collectives += 1
+        dist.all_reduce(t, op=getattr(dist.ReduceOp, op))
+
+    def read(self):
+        """One host wait: the agreed flag bytes (a list) and the union's size."""
+        import torch
+
+        word = torch.cat([self.flags.to(torch.int64), self.occ.sum(dtype=torch.int64).view(1)]).cpu()
+        self.state.host_waits += 1
+        fl, u = word[:FLAG_BYTES].tolist(), int(word[FLAG_BYTES])
+        self._t = self._mark("nonzero", self._t)
+        if self.timing is not None:
+            self.timing["stretches"] = self.m
+            self.timing["occupied_stretches_of_the_union"] = u
+        return fl, u
+
+    def sum(self, fl, u):
+        """C2 from the agreed ``fl`` and ``u``: -> (how, summed tail or None); how is "compact" or "dense"."""
+        import torch
+
+        if not fl[FLAG_NO_STAGING]:
+            self.state.cap = max(64, int(1.25 * u) + 16)
+        if self.m == 0 or fl[FLAG_NO_COMPACT] or fl[FLAG_NO_STAGING] or u > COMPACT_MAX_FILL * self.m:
+            t = time.perf_counter()
+            self._reduce(self.mats)
+            if self.k_tail:
+                self._reduce(self.extra[0])
+            self._mark("ring", t)
+            return "dense", (_tail_decode(self.extra[0], self.k_tail) if self.k_tail else None)
+        idx = torch.nonzero_static(self.occ, size=u, fill_value=0).view(-1)
+        return "compact", self._sum_slabs(idx, u, extra=True)
+
+    def sum_predicted(self):
+        """C2 sized from ``state.cap`` instead of the union (no host wait): the first min(cap, slab) stretches of the union;
+        ``settle`` sums the rest.  -> the summed tail."""
+        import torch
+
+        if self.m == 0:
+            return self.sum(*self.read())[1]
+        cap = min(self.state.cap, self.rows)
+        idx = torch.nonzero_static(self.occ, size=cap, fill_value=0).view(-1)
+        out = self._sum_slabs(idx, cap, extra=True)
+        self.cap = cap
+        self.state.pending = self
+        return out
+
+    def _sum_slabs(self, idx, n, extra):
+        """Sum the stretches ``head[idx]`` (n of them) over the ranks through the staging buffer, ``rows`` at a time; with
+        ``extra``, the tail row and the leftover cells ride behind the last slab (one SUM even when n is 0).
+        -> the summed tail, if it rode."""
+        import torch
+
+        head, rows, out = self.head, self.rows, None
+        for lo in range(0, max(n, 1 if extra else 0), rows):
+            k = min(rows, n - lo)
+            last = extra and lo + rows >= n
+            stage = self.buf[: k + (2 if last else 0)]
+            part = idx[lo:lo + k]
+            t = time.perf_counter() if lo else self._t  # (the first slab's gather includes finding the stretches)
+            torch.index_select(head, 0, part, out=stage[:k])
+            if last:
+                stage[k:].copy_(self.extra)
+            t = self._mark("gather", t)
+            self._reduce(stage)
+            t = self._mark("ring", t)
+            head.index_copy_(0, part, stage[:k])
+            if last:
+                self.left.copy_(stage[k + 1][: self.left.numel()])
+                out = _tail_decode(stage[k], self.k_tail) if self.k_tail else None
+            self._mark("scatter", t)
+        return out
+
+
+def agree(mats, tail=None, flags=None, tile_map=None, timing=None, occupancy_fn=None, state=None) -> Exchange:
+    """C1 of a sum: the staging buffer taken, the occupancy of the union and the flags of all ranks on the device."""
+    return Exchange(mats, tail, flags, tile_map, timing, occupancy_fn, state if state is not None else ExchangeState())
+
+
+def sum_counts(mats, tail=None, flags=None, tile_map=None, timing=None, occupancy_fn=None, state=None, predict=False):
+    """In-place sum over the ranks of a counter tensor and of ``tail`` in two collectives (see above); ``predict`` (needs
+    ``state`` with a cap from an earlier call): no host wait, ``settle(state)`` completes it.  -> (how, summed tail); how is
+    "compact" or "dense", the same on every rank.  Same integers as ``all_reduce(SUM)`` on the whole tensor: the stretches
+    that are left out are zero on every rank.  Without a process group there is nothing to sum: (None, tail)."""
+    import torch.distributed as dist
+
+    if not (dist.is_available() and dist.is_initialized()):
+        return None, tail
     if state is None:
         state = ExchangeState()
     state.collectives = state.host_waits = 0
-
-    def c_sum(t):
-        state.collectives += 1
-        if dst is None:
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        else:
-            dist.reduce(t, dst=dst, op=dist.ReduceOp.SUM)
-
-    mine = dst is None or dist.get_rank() == dst
-    dev = mats.device
-    flat = mats.view(-1)
-    m = flat.numel() // STRETCH
-    head = flat[: m * STRETCH].view(m, STRETCH)
-    k_tail = 0 if tail is None else int(tail.numel())
-    assert k_tail <= 16
-    my_flags = torch.zeros(FLAG_BYTES, dtype=torch.uint8, device=dev) if flags is None else flags.to(device=dev, dtype=torch.uint8).clone()
-    t = time.perf_counter()
-    n = mats.shape[-1]
-    use_tiles = tile_map is not None and mats.dim() == 3 and mats.shape[0] == 2 and mats.shape[1] == n and n >= STRETCH
-    # the staging buffer BEFORE the first collective: a rank that cannot have it says so in its flag bytes
-    want = (state.cap + 2) if (predict and state.cap is not None) else min(m // 2 + 3, 1 << 20)
-    buf = _staging_buffer(head, want) if m else None
-    if m and buf is None:
-        my_flags[FLAG_NO_STAGING] = 1
-    # C1 = [occupancy map (unless the tile map stands for it) | the counter's dirty-tile map, if it keeps one | flag bytes]
-    occ_local = None if use_tiles else ((occupancy_fn(head) if occupancy_fn is not None else _occupancy(head)) if m
-                                        else torch.zeros(0, dtype=torch.uint8, device=dev))
-    n_occ = 0 if occ_local is None else occ_local.numel()
-    n_tiles = 0 if tile_map is None else tile_map.numel()
-    nb = n_occ + n_tiles
-    c1 = torch.empty(nb + FLAG_BYTES, dtype=torch.uint8, device=dev)
-    if n_occ:
-        c1[:n_occ] = occ_local
-    if n_tiles:
-        c1[n_occ:nb] = tile_map
-    c1[nb:] = my_flags
-    t = mark("occupancy", t)
-    state.collectives += 1
-    dist.all_reduce(c1, op=dist.ReduceOp.MAX)
-    t = mark("occupancy_allreduce", t)
-    all_flags = c1[nb:]
-    if n_tiles:
-        tile_map.copy_(c1[n_occ:nb])  # (the sum brings the other ranks' cells: their tiles are dirty here too)
-    occ = _occupancy_from_tiles(tile_map, n, m) if use_tiles else c1[:n_occ]
-
-    def tail_only():  # (dense branch: the tail goes through on its own)
-        if not k_tail:
-            return None
-        row = torch.empty(STRETCH, dtype=mats.dtype, device=dev)
-        _tail_encode(tail, row)
-        c_sum(row)
-        return _tail_decode(row, k_tail)
-
-    left = flat[m * STRETCH:]  # the cells behind the last whole stretch (fewer than 64): they ride in a row of their own
-    n_left = int(left.numel())
-
-    def extra_rows(stage, at):  # stage[at] <- the tail's limbs, stage[at + 1] <- the leftover cells
-        if k_tail:
-            _tail_encode(tail, stage[at])
-        else:
-            stage[at].zero_()
-        stage[at + 1].zero_()
-        if n_left:
-            stage[at + 1][:n_left] = left
-
-    def extra_back(stage, at):
-        if n_left and mine:
-            left.copy_(stage[at + 1][:n_left])
-        return _tail_decode(stage[at], k_tail) if k_tail else None
-
-    if predict and state.cap is not None and m and buf is not None:
-        cap = min(state.cap, buf.shape[0] - 2)
-        idx = torch.nonzero_static(occ, size=cap, fill_value=0).view(-1)
-        stage = buf[: cap + 2]
-        torch.index_select(head, 0, idx, out=stage[:cap])
-        extra_rows(stage, cap)
-        t = mark("gather", t)
-        c_sum(stage)
-        t = mark("ring", t)
-        if mine:
-            head.index_copy_(0, idx, stage[:cap])
-        out_tail = extra_back(stage, cap)
-        mark("scatter", t)
-        state.pending = {"u": occ.sum(dtype=torch.int64), "cap": cap, "flags": all_flags, "occ": occ, "head": head, "dst": dst}
-        return "compact", all_flags, out_tail
-
-    # one host wait: the flags and the union's size together
-    if m:
-        word = torch.cat([all_flags.to(torch.int64), occ.sum(dtype=torch.int64).view(1)]).cpu()
-        state.host_waits += 1
-        fl, u = word[:FLAG_BYTES].tolist(), int(word[FLAG_BYTES])
-    else:
-        fl, u = all_flags.cpu().tolist(), 0
-        state.host_waits += 1
-    t = mark("nonzero", t)
-    if timing is not None:
-        timing["stretches"] = m
-        timing["occupied_stretches_of_the_union"] = u
-    if on_flags is not None:
-        other = on_flags(fl)
-        if other is not None:
-            done = state.collectives
-            clean = torch.zeros(FLAG_BYTES, dtype=torch.uint8)
-            clean[FLAG_NO_COMPACT] = 1 if fl[FLAG_NO_COMPACT] else 0
-            res = sum_counts_packed(other, tail, clean, tile_map=None, timing=timing, occupancy_fn=occupancy_fn, state=state, dst=dst)
-            state.collectives += done
-            return res
-    state.cap = max(64, int(1.25 * u) + 16)
-    if m == 0 or fl[FLAG_NO_COMPACT] or fl[FLAG_NO_STAGING] or u > COMPACT_MAX_FILL * m:
-        t = time.perf_counter()
-        c_sum(mats)
-        out_tail = tail_only()
-        mark("ring", t)
-        return "dense", all_flags, out_tail
-    idx = torch.nonzero_static(occ, size=u, fill_value=0).view(-1)
-    bigger = _staging_buffer(head, u + 2)  # (grown when it can be: fewer slabs; the old one serves otherwise)
-    if bigger is not None:
-        buf = bigger
-    rows = buf.shape[0] - 2
-    out_tail = None
-    lo = 0
-    while True:
-        part = idx[lo:lo + rows]
-        k = int(part.numel())
-        last = lo + k >= u
-        stage = buf[: k + (2 if last else 0)]
-        t = time.perf_counter()
-        if k:
-            torch.index_select(head, 0, part, out=stage[:k])
-        if last:
-            extra_rows(stage, k)
-        t = mark("gather", t)
-        c_sum(stage)
-        t = mark("ring", t)
-        if mine and k:
-            head.index_copy_(0, part, stage[:k])
-        if last:
-            out_tail = extra_back(stage, k)
-        mark("scatter", t)
-        lo += k
-        if last:
-            break
-    return "compact", all_flags, out_tail
+    x = agree(mats, tail, flags, tile_map, timing, occupancy_fn, state)
+    if predict and state.cap is not None:
+        return "compact", x.sum_predicted()
+    return x.sum(*x.read())
 
 
-def settle_exchange(state) -> None:
+def settle(state) -> None:
     """The deferred half of a predicted exchange: ONE host read (the union's real size and the flag bytes, both long since
     computed), then -- every rank alike, they all hold the same numbers -- the stretches beyond the predicted size summed
-    now, and the prediction raised.  Raises if a flag says the predicted exchange was not allowed (a rank vetoed the compact
-    form, held int64 totals or had no staging memory): the bench's steady state checks those statically."""
+    now, and the prediction raised.  Raises on every rank if the agreed flags say the predicted exchange was not allowed (a
+    rank vetoed the compact form, held int64 totals or had no staging memory, or the bound on the pairs does not fit
+    uint32 cells): the bench's steady state checks those statically, each rank for itself."""
     import torch
-    import torch.distributed as dist
 
-    p = state.pending
-    if p is None:
+    x = state.pending
+    if x is None:
         return
     state.pending = None
-    word = torch.cat([p["flags"].to(torch.int64), p["u"].view(1)]).cpu()
-    state.host_waits += 1
-    fl, u, cap = word[:FLAG_BYTES].tolist(), int(word[FLAG_BYTES]), p["cap"]
-    if fl[FLAG_NO_COMPACT] or fl[FLAG_WIDE] or fl[FLAG_NO_STAGING]:
-        raise RuntimeError("a predicted exchange ran although a rank's flags forbid it: %r" % (fl,))
-    if u > cap:
-        head, dst = p["head"], p["dst"]
-        rest = torch.nonzero_static(p["occ"], size=u, fill_value=0).view(-1)[cap:]
-        mine = dst is None or dist.get_rank() == dst
-        for lo in range(0, int(rest.numel()), SLAB_STRETCHES):
-            part = rest[lo:lo + SLAB_STRETCHES]
-            stage = head.index_select(0, part)
-            state.collectives += 1
-            if dst is None:
-                dist.all_reduce(stage, op=dist.ReduceOp.SUM)
-            else:
-                dist.reduce(stage, dst=dst, op=dist.ReduceOp.SUM)
-            if mine:
-                head.index_copy_(0, part, stage)
+    x.timing = None  # (its exchange's timing was reported already)
+    fl, u = x.read()
+    if fl[FLAG_NO_COMPACT] or fl[FLAG_NO_STAGING] or must_fold(fl, group_size()):
+        raise RuntimeError("a predicted exchange ran although the ranks' flags forbid it: %r" % (fl,))
+    if u > x.cap:
+        rest = torch.nonzero_static(x.occ, size=u, fill_value=0).view(-1)[x.cap:]
+        x._sum_slabs(rest, u - x.cap, extra=False)
     state.cap = max(state.cap or 0, int(1.25 * u) + 16, 64)
-
-
-def sum_counts_compact(mats, allow_compact: bool = True, tile_map=None, timing=None, occupancy_fn=None) -> str:
-    """In-place sum over the ranks of a counter tensor by way of its occupied 64-cell stretches: ``sum_counts_packed``
-    without a tail.  Returns "compact" or "dense" (what was done; the same on every rank).  Same integers as
-    ``all_reduce(SUM)`` on the whole tensor: the stretches that are left out are zero on every rank."""
-    import torch
-
-    flags = torch.zeros(FLAG_BYTES, dtype=torch.uint8)
-    if not allow_compact:
-        flags[FLAG_NO_COMPACT] = 1
-    return sum_counts_packed(mats, flags=flags, tile_map=tile_map, timing=timing, occupancy_fn=occupancy_fn)[0]

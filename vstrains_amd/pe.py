@@ -10,6 +10,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
+from .dist import U32_LIMIT, ExchangeState
 
 
 # ---- text inputs ---------------------------------------------------------------------------------
@@ -428,9 +429,6 @@ class Context:
         return out
 
 
-U32_LIMIT = 2 ** 32
-
-
 class PeCounter:
     """node_mat / short_mat accumulation on one device (PE_Inference.py:137-188), counters held
     in torch tensors so that torch.distributed (RCCL) can all-reduce them in place.
@@ -463,6 +461,7 @@ class PeCounter:
         self.pairs_in_buffer = 0  # pairs counted into ``mats`` since it was last empty (all ranks, after a sum)
         self.pairs_seen = 0
         self.last_all_reduce = None  # "dense" / "compact" after all_reduce()
+        self._xstate = ExchangeState()  # (what the exchanges of all_reduce keep between calls)
         # (the numbering of the index this counter counts under: kept here, so that a later build_index on the same context
         # cannot change how these matrices are read)
         self.node_order = getattr(ctx, "node_order", None)
@@ -540,79 +539,57 @@ class PeCounter:
                                                                 head.shape[0], C.c_void_p(occ.data_ptr())))
         return occ
 
-    def all_reduce(self, dst=None, predict=False):
-        """Sum over the ranks of the process group, in place, in TWO collectives (``dist.sum_counts_packed``): a MAX over
-        [occupancy of the counters' 64-cell stretches | flag bytes], then a SUM over [the occupied stretches of the union |
-        a row with the three stats and the pairs in the buffers].  The flag bytes settle, for every rank alike, whether the
-        uint32 buffers can hold the sum (a bound on the largest rank's pairs, times the ranks): if not, or if some rank
-        already holds int64 totals, every rank folds and the int64 totals are summed (a rare second exchange); a rank
-        whose environment turns the compact exchange off vetoes it for everybody (no mismatched collectives).
+    def all_reduce(self, predict=False):
+        """Sum over the ranks of the process group, in place, in TWO collectives (``dist.agree`` + ``Exchange.sum``): a MAX
+        over [occupancy of the counters' 64-cell stretches | flag bytes], then a SUM over [the occupied stretches of the
+        union | a row with the three stats and the pairs in the buffers].  The flag bytes settle, for every rank alike,
+        whether the uint32 buffers can hold the sum: if not, or if some rank already holds int64 totals, every rank folds
+        and the int64 totals are agreed on and summed (two more collectives); a rank whose environment turns the compact
+        exchange off vetoes it for everybody.  Every rank ends with the full sums.
 
-        ``dst``: only that rank needs the sums (the drop-in's writer): the SUM collectives reduce to it, the other ranks
-        keep their own counts.  ``predict``: the steady state of fixed-size steps (bench.py) -- no host wait at all; the
-        preconditions (no int64 totals, the bound, the veto) are checked statically here and again from the flag bytes when
-        ``settle()`` is called before the buffer is reused."""
-        from .dist import group_size
-
-        if group_size() <= 1:
-            return
+        ``predict``: the steady state of fixed-size steps (bench.py) -- no host wait at all; the preconditions (no int64
+        totals, the bound, the veto) are checked statically here and again from the agreed flag bytes when ``settle()`` is
+        called before the buffer is reused."""
         from . import dist as vdist
 
+        world = vdist.group_size()
+        if world <= 1:
+            return
         torch = self.torch
-        world = group_size()
         may_compact = os.environ.get("VS_COMPACT_ALLREDUCE", "1") not in ("0", "")
         p = int(self.pairs_in_buffer)
-        a_bits = p.bit_length()
-        flags = torch.zeros(vdist.FLAG_BYTES, dtype=torch.uint8)
-        flags[vdist.FLAG_NO_COMPACT] = 0 if may_compact else 1
-        flags[vdist.FLAG_WIDE] = 1 if self.wide is not None else 0
-        # the largest rank's pairs as (bit length, its top eight bits): MAX over the bytes bounds the maximum from above
-        flags[vdist.FLAG_PAIRS_LOG2] = a_bits
-        flags[vdist.FLAG_PAIRS_LOG2 + 1] = (p >> (a_bits - 8)) if a_bits > 8 else p
+        flags = vdist.flag_bytes(no_compact=not may_compact, wide=self.wide is not None, pairs=p)
         tail = torch.cat([self.stats.to(torch.int64), torch.tensor([p], dtype=torch.int64, device=self.stats.device)])
-        if not hasattr(self, "_xstate"):
-            self._xstate = vdist.ExchangeState()
         timing = {} if os.environ.get("VS_DIST_TIMING") else None
         occ_fn = self._occupied if self.mats.is_cuda else None
-        if predict and self._xstate.cap is not None:
+        xs = self._xstate
+        if predict and xs.cap is not None:
             if self.wide is not None or 2 * p * world >= U32_LIMIT or not may_compact:
                 raise OverflowError("a predicted exchange sums uint32 buffers through their occupied stretches: 2 * %d pairs * %d "
                                     "ranks must fit, without int64 totals or a veto; use all_reduce()" % (p, world))
-            how, _, out_tail = vdist.sum_counts_packed(self.mats, tail, flags, tile_map=self.tile_map, timing=timing, occupancy_fn=occ_fn,
-                                                       state=self._xstate, predict=True, dst=dst)
-            self.last_all_reduce = how
+            how, out_tail = vdist.sum_counts(self.mats, tail, flags, self.tile_map, timing, occ_fn, state=xs, predict=True)
             self.stats.copy_(out_tail[:3])
             self.pairs_in_buffer = p * world  # (a bound; the steps' blocks are of one size)
         else:
-            how, fl, out_tail = vdist.sum_counts_packed(self.mats, tail, flags, tile_map=self.tile_map, timing=timing, occupancy_fn=occ_fn,
-                                                        state=self._xstate, dst=dst, on_flags=self._fold_if_needed)
-            self.last_all_reduce = how
+            xs.collectives = xs.host_waits = 0
+            x = vdist.agree(self.mats, tail, flags, self.tile_map, timing, occ_fn, xs)
+            fl, u = x.read()
+            if vdist.must_fold(fl, world):
+                self.fold()
+                x = vdist.agree(self.wide, tail, vdist.flag_bytes(no_compact=not may_compact), None, timing, occ_fn, xs)
+                fl, u = x.read()
+            how, out_tail = x.sum(fl, u)
             out = out_tail.cpu()
             self.stats.copy_(out[:3].to(self.stats.device))
             self.pairs_in_buffer = 0 if self.wide is not None else int(out[3])
-        self.last_collectives = self._xstate.collectives
+        self.last_all_reduce = how
+        self.last_collectives = xs.collectives
         if timing is not None:
             self.exchange_timing = getattr(self, "exchange_timing", [])
             self.exchange_timing.append(timing)
 
-    def _fold_if_needed(self, fl):
-        """The flag bytes of all ranks are in: do the uint32 buffers hold the sum?  If not, every rank folds and the int64
-        totals are what is summed (returned to ``sum_counts_packed``, which starts over on them)."""
-        from . import dist as vdist
-
-        a_bits, top = int(fl[vdist.FLAG_PAIRS_LOG2]), int(fl[vdist.FLAG_PAIRS_LOG2 + 1])
-        bound = ((top + 1) << (a_bits - 8)) if a_bits > 8 else 255
-        if fl[vdist.FLAG_WIDE] or 2 * bound * vdist.group_size() >= U32_LIMIT:
-            self.fold()
-            return self.wide
-        return None
-
     def _xstate_cap(self, value=None):
         """The union size the next predicted exchange is staged for (None: not known yet); with a value: set it."""
-        from . import dist as vdist
-
-        if not hasattr(self, "_xstate"):
-            self._xstate = vdist.ExchangeState()
         if value is not None:
             self._xstate.cap = value
         return self._xstate.cap
@@ -621,25 +598,7 @@ class PeCounter:
         """The deferred half of ``all_reduce(predict=True)``; call before the buffer is counted into again."""
         from . import dist as vdist
 
-        if getattr(self, "_xstate", None) is not None:
-            vdist.settle_exchange(self._xstate)
-
-    def all_reduce_async(self):
-        """Overlapped form for fixed-size steps (bench.py): the caller keeps counting into a second
-        buffer meanwhile.  No agreement round, so the bound is checked statically."""
-        from .dist import all_reduce_counts_async, group_size
-
-        world = max(group_size(), 1)
-        if self.wide is not None or 2 * self.pairs_in_buffer * world >= U32_LIMIT:
-            raise OverflowError("all_reduce_async sums uint32 buffers: 2 * %d pairs * %d ranks does not fit; use all_reduce()"
-                                % (self.pairs_in_buffer, world))
-        work = all_reduce_counts_async(self.mats, self.stats)
-        if self.tile_map is not None:
-            import torch.distributed as dist
-
-            work.append(dist.all_reduce(self.tile_map, op=dist.ReduceOp.MAX, async_op=True))
-        self.pairs_in_buffer *= world
-        return work
+        vdist.settle(self._xstate)
 
     def user_order(self, t):
         """[2,N,N] device tensor in the index's internal numbering -> the caller's (``Context.build_index``):

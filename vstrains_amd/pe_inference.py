@@ -51,7 +51,7 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
         count_fastq(ctx, fq, counter, 0, len(fq), progress=True)
     fq.close()
     if world > 1:
-        counter.all_reduce(dst=0)  # (only rank 0 writes the files and runs the stages: the sums are reduced to it)
+        counter.all_reduce()  # (every rank ends with the full sums; only rank 0 writes the files and runs the stages)
     return ids, counter
 
 
