@@ -139,6 +139,32 @@ int vs_fastq_gather(const vs_fastq *fq, uint64_t first, uint64_t count, uint64_t
                     uint8_t *ascii);
 int vs_fastq_block(vs_ctx *ctx, vs_fastq *fq, uint64_t first, uint64_t count, vs_reads **out);
 
+/* Streamed ingest (additions to ABI 10): the same records from any file descriptor -- a FIFO, /dev/stdin, a process
+ * substitution, a regular file -- read front to back through a bounded ring of pinned chunks (one reader thread per
+ * file; gzip inflated on the fly, several members in a row are fine), the records found and packed on the device.  Peak
+ * host memory is the ring, whatever the size of the input.
+ *   vs_fastq_stream_open  : opens both files and starts their readers
+ *   vs_fastq_stream_next  : the next block of at most max_pairs pairs (0 = no limit), the layout vs_pe_count takes, ready
+ *                           when the call returns; *n_pairs = 0 and *out = NULL at the end of the input.  Before it reports
+ *                           the end both files have been read to their ends: bytes that are not valid UTF-8 anywhere in
+ *                           either file are VS_E_UTF8, a cut-off gzip stream VS_E_ARG (the first failure in file order, as
+ *                           vs_fastq_open).  After a failure every call returns it again.
+ *   vs_fastq_stream_info  : info[0] = pairs so far, [1] = text bytes read (inflated), [2] = file bytes read (compressed),
+ *                           [3] = flags: bit 0 some chunk held '\r', bit 1 a byte >= 0x80, bit 2 / 3 the forward / reverse
+ *                           file is gzip, bit 4 the end of the input was reported
+ *   vs_fastq_stream_close : stops the readers and frees everything (blocks returned earlier stay valid)
+ * VS_STREAM_CHUNK (bytes) overrides the chunk size: tests only, to put record and line boundaries across chunks. */
+typedef struct vs_fastq_stream vs_fastq_stream;
+int vs_fastq_stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, vs_fastq_stream **out);
+int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs_reads **out, uint64_t *n_pairs);
+int vs_fastq_stream_info(const vs_fastq_stream *s, uint64_t info[4]);
+void vs_fastq_stream_close(vs_fastq_stream *s);
+/* Test aid: the streamed ingest's device line scanner on n bytes of host text.  ends[i] (up to cap of them) = byte offset
+ * of newline i; info[0] = newlines, [1] = flags (bit 0 '\r', bit 1 a byte >= 0x80), [2] = one past the newline of the last
+ * line that completes a record when the text's first line has number line0 (lines 4r .. 4r+3 are record r), 0 if none. */
+int vs_fastq_scan_text(vs_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t line0, uint64_t *ends, uint64_t cap,
+                       uint64_t info[3]);
+
 /* pe_info / st_info text (PE_Inference.py:194-205): "{id_i}:{id_j}:{count}\n" for all i, j in
  * row-major order, zeros included.  ids: the n node names concatenated, id_off[n+1]; mat: HOST
  * n*n int64.  Formatted on all host cores, one write(). */

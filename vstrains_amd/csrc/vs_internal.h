@@ -224,6 +224,14 @@ extern "C" void vs_ctx_free_index(vs_ctx *ctx);
                            "%s failed: %s", #call, hipGetErrorString(e__));                \
     } while (0)
 
+// UTF-8 checks of the FASTQ ingest (vs_fastq.hip), shared with the streamed ingest (vs_stream.hip): the characters that
+// start in [lo, hi) of txt[0, size) are valid; bytes of the character at q[0] (n available), 0 if invalid
+bool vs_utf8_range_ok(const uint8_t *txt, size_t size, size_t lo, size_t hi);
+uint32_t vs_utf8_char_len(const uint8_t *q, size_t n);
+// kernels of vs_reads.hip that other translation units launch on a stream of their own
+void vs_launch_count_invalid(hipStream_t st, const uint32_t *meta, uint64_t n_ends, uint32_t *out);
+void vs_launch_inv4(hipStream_t st, const uint32_t *woff, const uint32_t *mask, uint64_t n_ends, uint32_t *meta, uint32_t *inv4);
+
 // Exclusive scan of n uint32 values on the ctx stream (in -> out, may alias); total (uint64) is
 // written to d_total if not NULL.  tmp must hold ceil(n/2048)+1 uint64.
 int vs_scan_u32(vs_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *d_tmp,

@@ -79,6 +79,13 @@ k_inv4(const uint32_t *__restrict__ woff, const uint32_t *__restrict__ mask, uin
     inv4[e] = out;
 }
 
+void vs_launch_count_invalid(hipStream_t st, const uint32_t *meta, uint64_t n_ends, uint32_t *out) {
+    if (n_ends) hipLaunchKernelGGL(k_count_invalid, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st, meta, n_ends, out);
+}
+void vs_launch_inv4(hipStream_t st, const uint32_t *woff, const uint32_t *mask, uint64_t n_ends, uint32_t *meta, uint32_t *inv4) {
+    if (n_ends) hipLaunchKernelGGL(k_inv4, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st, woff, mask, n_ends, meta, inv4);
+}
+
 __global__ void __launch_bounds__(TPB)
 k_unpack_reads(VsReadsDev rd, const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out) {
     uint64_t e = (uint64_t)blockIdx.x * TPB + threadIdx.x;

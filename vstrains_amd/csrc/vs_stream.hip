@@ -1,0 +1,927 @@
+// Streamed FASTQ ingest: both files read front to back through a bounded ring of pinned chunks, the records found and
+// packed ON THE DEVICE.  For inputs the mapped ingest (vs_fastq.hip) cannot take: a FIFO, /dev/stdin or a process
+// substitution has no size to map, and a gzip file is inflated there whole into memory before anything is counted.
+//
+// Host: one reader thread per file read(2)s any fd -- inflating with zlib in streaming mode when the file starts with
+// the gzip magic (several members in a row are fine; a cut-off stream or trailing bytes that are no member are VS_E_ARG,
+// as in map_file) -- into a ring of STREAM_RING_SLOTS pinned chunks of STREAM_CHUNK_BYTES.  Peak host memory is the
+// ring, whatever the size of the file.
+//
+// Device: every file has a window = the bytes left over from the last block (they start at a record boundary) + the
+// chunks appended since.  Per step, for each window:
+//   k_sl_count    one lane per 16-byte word: newlines per workgroup, flags for '\r' and bytes >= 0x80, the last byte;
+//   k_sl_scan     exclusive scan of the workgroup counts (one workgroup);
+//   k_sl_scatter  the lane's rank among the newlines of its wavefront from __ballot, + its wavefront's and workgroup's
+//                 base: the byte offset of every line end;
+// then, for the n = min(complete records of fwd, of rve) pairs of the block:
+//   k_sl_ends     length (line 4r+1 minus its newline) and packed words of every end, the record cuts;
+//   k_sl_scan     word offsets;
+//   k_sl_pack     one thread per packed word, straight from the window (k_pack_reads' form), the mask beside it;
+// and k_count_invalid / k_inv4 (vs_reads.hip) as vs_reads_pack runs them.  The block is the layout vs_pe_count takes.
+//
+// A window whose scan raises a flag ('\r' or a byte >= 0x80) keeps the reference's text-mode semantics on the host
+// (rare): its complete lines are copied back, universal newlines applied ("\r\n" and a lone '\r' end a line; a '\r' at
+// the end of the window waits for the next chunk, which may start with '\n'), every multi-byte UTF-8 character becomes
+// one '?' (seq_chars), the bytes are checked with utf8_range_ok, and the text goes back to the device to be scanned
+// again.  Plain ASCII with LF line ends never passes through host parsing.
+#include <errno.h>
+#include <fcntl.h>
+#include <poll.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include <zlib.h>
+
+#include <algorithm>
+#include <condition_variable>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "vs_internal.h"
+
+#define SL_TPB 256
+#define SL_SCAN_TPB 1024
+
+namespace {
+
+constexpr size_t STREAM_CHUNK_BYTES = 64u << 20;  // one pinned chunk of the ring; VS_STREAM_CHUNK overrides it (tests only)
+constexpr unsigned STREAM_RING_SLOTS = 4;         // chunks per file in the ring
+constexpr size_t STREAM_MAX_WINDOW = 0xFFFFFF00u; // line ends are 32-bit byte offsets into a window
+
+// per-window status the kernels write (one uint32 array per stream, read back in one copy)
+enum { ST_NL = 0, ST_FLAGS = 1, ST_LAST = 2, ST_PER_FILE = 4 };  // [f * ST_PER_FILE + ...]
+enum { ST_MAXLEN = 8, ST_TOO_LONG = 9, ST_WORDS = 10, ST_INVALID = 11, ST_CUT = 12 /* + f */, ST_N = 16 };
+enum { FL_CR = 1u, FL_HIGH = 2u };
+
+}  // namespace
+
+// ---- kernels -----------------------------------------------------------------------------------------------------------
+// exact mask (0x80 per byte) of the bytes of x equal to c
+__device__ __forceinline__ uint32_t sl_eq(uint32_t x, uint32_t c4) {
+    const uint32_t t = x ^ c4;
+    return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t | 0x7F7F7F7Fu);
+}
+
+// the 16 bytes of word wi (bytes at or beyond n read as 0)
+__device__ __forceinline__ uint4 sl_load16(const uint8_t *txt, uint64_t n, uint64_t wi) {
+    const uint64_t b = wi * 16u;
+    uint4 v = *(const uint4 *)(txt + b);  // (the window buffer is padded to whole words)
+    if (b + 16u > n) {
+        const uint32_t keep = (uint32_t)(n - b);  // 0..15
+        uint32_t *p = (uint32_t *)&v;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint32_t lo = 4u * k;
+            p[k] = keep >= lo + 4u ? p[k] : keep <= lo ? 0u : p[k] & ((1u << (8u * (keep - lo))) - 1u);
+        }
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint32_t sl_nl_mask(const uint4 v, uint32_t out[4]) {
+    const uint32_t *p = (const uint32_t *)&v;
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        out[k] = sl_eq(p[k], 0x0A0A0A0Au);
+        c += (uint32_t)__popc(out[k]);
+    }
+    return c;
+}
+
+// newlines per workgroup, flags of the window, its last byte
+__global__ void __launch_bounds__(SL_TPB) k_sl_count(const uint8_t *__restrict__ txt, uint64_t n, uint32_t *__restrict__ wg_cnt,
+                                                     uint32_t *__restrict__ st) {
+    __shared__ uint32_t wsum[SL_TPB / VS_WAVE];
+    const uint64_t wi = (uint64_t)blockIdx.x * SL_TPB + threadIdx.x;
+    uint32_t c = 0, fl = 0;
+    if (wi * 16u < n) {
+        const uint4 v = sl_load16(txt, n, wi);
+        uint32_t m[4];
+        c = sl_nl_mask(v, m);
+        const uint32_t *p = (const uint32_t *)&v;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            if (sl_eq(p[k], 0x0D0D0D0Du)) fl |= FL_CR;
+            if (p[k] & 0x80808080u) fl |= FL_HIGH;
+        }
+        if (wi * 16u + 16u >= n) st[ST_LAST] = txt[n - 1u];  // (the lane that holds the window's last byte)
+    }
+    const uint32_t lane = threadIdx.x & (VS_WAVE - 1u), wave = threadIdx.x / VS_WAVE;
+    uint32_t s = c;
+#pragma unroll
+    for (uint32_t o = VS_WAVE / 2u; o; o >>= 1) s += __shfl_xor(s, o);
+    const bool any_cr = __ballot(fl & FL_CR) != 0ull, any_high = __ballot(fl & FL_HIGH) != 0ull;
+    if (lane == 0) {
+        wsum[wave] = s;
+        if (any_cr || any_high) atomicOr(&st[ST_FLAGS], (any_cr ? FL_CR : 0u) | (any_high ? FL_HIGH : 0u));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < SL_TPB / VS_WAVE; w++) t += wsum[w];
+        wg_cnt[blockIdx.x] = t;
+    }
+}
+
+// exclusive scan of a[0, m) in place, one workgroup; the total to *total (uint32: the callers' totals are below 2^32)
+__global__ void __launch_bounds__(SL_SCAN_TPB) k_sl_scan(uint32_t *__restrict__ a, uint32_t m, uint32_t *__restrict__ total) {
+    __shared__ uint32_t part[SL_SCAN_TPB];
+    const uint32_t t = threadIdx.x, per = (m + SL_SCAN_TPB - 1u) / SL_SCAN_TPB;
+    const uint32_t lo = min(m, t * per), hi = min(m, lo + per);
+    uint32_t s = 0;
+    for (uint32_t i = lo; i < hi; i++) s += a[i];
+    part[t] = s;
+    __syncthreads();
+    for (uint32_t o = 1; o < SL_SCAN_TPB; o <<= 1) {  // inclusive Hillis-Steele over the thread sums
+        const uint32_t add = t >= o ? part[t - o] : 0u;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - s;
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint32_t x = a[i];
+        a[i] = run;
+        run += x;
+    }
+    if (t == SL_SCAN_TPB - 1u) *total = part[t];
+}
+
+// the byte offset of every newline, in order: workgroup base (scanned counts) + wavefront base + the lane's rank, the
+// rank from __ballot of the bits of every lane's count
+__global__ void __launch_bounds__(SL_TPB) k_sl_scatter(const uint8_t *__restrict__ txt, uint64_t n, const uint32_t *__restrict__ wg_base,
+                                                       uint32_t *__restrict__ ends) {
+    __shared__ uint32_t wsum[SL_TPB / VS_WAVE];
+    const uint64_t wi = (uint64_t)blockIdx.x * SL_TPB + threadIdx.x;
+    uint32_t c = 0, m[4] = {0u, 0u, 0u, 0u};
+    if (wi * 16u < n) c = sl_nl_mask(sl_load16(txt, n, wi), m);
+    const uint32_t lane = threadIdx.x & (VS_WAVE - 1u), wave = threadIdx.x / VS_WAVE;
+    const uint64_t below = lane ? (~0ull >> (VS_WAVE - lane)) : 0ull;
+    uint32_t rank = 0, wtotal = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 5; b++) {  // c <= 16: five bits
+        const uint64_t bal = __ballot((c >> b) & 1u);
+        rank += (uint32_t)__popcll(bal & below) << b;
+        wtotal += (uint32_t)__popcll(bal) << b;
+    }
+    if (lane == 0) wsum[wave] = wtotal;
+    __syncthreads();
+    uint32_t base = wg_base[blockIdx.x];
+    for (uint32_t w = 0; w < wave; w++) base += wsum[w];
+    if (!c) return;
+    uint32_t at = base + rank;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        uint32_t mk = m[k];
+        while (mk) {
+            const uint32_t bit = (uint32_t)__ffs((int)mk) - 1u;  // 7, 15, 23 or 31
+            ends[at++] = (uint32_t)(wi * 16u) + 4u * k + (bit >> 3);
+            mk &= mk - 1u;
+        }
+    }
+}
+
+struct SlWin {
+    const uint8_t *txt;
+    const uint32_t *ends;
+    uint32_t n_nl, size;
+};
+
+// one thread per end of the block (and one more for the closing word offset): length, packed words, the longest end, the
+// first end over the 24-bit limit; thread 0 also writes the record cuts (one past the newline of line 4n - 1)
+__global__ void __launch_bounds__(SL_TPB) k_sl_ends(SlWin f0, SlWin f1, uint32_t n_pairs, uint32_t *__restrict__ meta,
+                                                    uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
+    const uint32_t e = blockIdx.x * SL_TPB + threadIdx.x, n_ends = 2u * n_pairs;
+    if (e == 0) {
+        const uint32_t last = 4u * n_pairs - 1u;
+        st[ST_CUT + 0] = last < f0.n_nl ? f0.ends[last] + 1u : f0.size;
+        st[ST_CUT + 1] = last < f1.n_nl ? f1.ends[last] + 1u : f1.size;
+    }
+    if (e > n_ends) return;
+    if (e == n_ends) {
+        wcnt[e] = 0u;
+        return;
+    }
+    const SlWin &w = (e & 1u) ? f1 : f0;
+    const uint32_t r = e >> 1;
+    const uint32_t start = w.ends[4u * r] + 1u, len = w.ends[4u * r + 1u] - start;  // (the character dropped is the newline)
+    if (len > VS_LEN_MASK) {
+        atomicMin(&st[ST_TOO_LONG], e);
+        meta[e] = 0u;
+        wcnt[e] = 0u;
+        return;
+    }
+    meta[e] = len;
+    wcnt[e] = (len + 15u) >> 4;
+    atomicMax(&st[ST_MAXLEN], len);
+}
+
+// one thread per packed word (k_pack_reads' form), bytes straight from the window; mask beside the words
+__global__ void __launch_bounds__(SL_TPB) k_sl_pack(SlWin f0, SlWin f1, uint32_t n_ends, uint32_t total_words,
+                                                    const uint32_t *__restrict__ woff, uint32_t *__restrict__ words,
+                                                    uint32_t *__restrict__ mask, uint32_t *__restrict__ meta) {
+    const uint32_t wi = blockIdx.x * SL_TPB + threadIdx.x;
+    if (wi >= total_words) return;
+    const uint32_t e = vs_upper_idx(woff, n_ends + 1u, wi);
+    const SlWin &w = (e & 1u) ? f1 : f0;
+    const uint32_t r = e >> 1;
+    const uint32_t start = w.ends[4u * r] + 1u, len = w.ends[4u * r + 1u] - start;
+    const uint8_t *q = w.txt + start;
+    const uint32_t b0 = (wi - woff[e]) * 16u;
+    uint32_t v = 0, m = 0, fl = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 16; i++) {
+        const uint32_t p = b0 + i;
+        if (p < len) {
+            const uint8_t c = q[p];
+            const uint32_t code = vs_code(c);
+            if (code > 3u) {
+                fl |= (c == 'N') ? VS_FLAG_N : VS_FLAG_INVALID;
+                m |= 3u << (2 * i);
+            }
+            v |= (code & 3u) << (2 * i);
+        }
+    }
+    words[wi] = v;
+    mask[wi] = m;
+    if (fl) atomicOr(&meta[e], fl << 24);
+}
+
+// ---- host reader -------------------------------------------------------------------------------------------------------
+namespace {
+
+struct Slot {
+    uint8_t *p = nullptr;
+    size_t len = 0;
+    bool last = false;
+};
+
+// One file read front to back by a thread of its own into the ring.  The consumer takes filled slots in order and gives
+// them back once their bytes are on the device.
+struct Reader {
+    std::string path;
+    int fd = -1, device = 0;
+    size_t chunk = STREAM_CHUNK_BYTES;
+    Slot slots[STREAM_RING_SLOTS];
+    uint64_t filled = 0, taken = 0;  // slots published / given back (monotonic)
+    bool stop = false, finished = false;
+    int err = VS_OK;
+    std::string err_msg;
+    bool gzip = false;
+    uint64_t raw_bytes = 0, text_bytes = 0;
+    std::mutex m;
+    std::condition_variable cv;
+    std::thread th;
+
+    int fail(int code, const char *fmt, const char *a, const char *b = "") {
+        char buf[512];
+        snprintf(buf, sizeof buf, fmt, a, b);
+        err = code;
+        err_msg = buf;
+        return code;
+    }
+    // read(2) up to n bytes; 0 at the end of the file; -1 on an error or when asked to stop
+    ssize_t raw_read(uint8_t *dst, size_t n) {
+        for (;;) {
+            {
+                std::lock_guard<std::mutex> lk(m);
+                if (stop) return -1;
+            }
+            struct pollfd pfd = {fd, POLLIN, 0};
+            const int pr = poll(&pfd, 1, 200);  // (a pipe whose writer is slow: look at `stop` now and then)
+            if (pr == 0 || (pr < 0 && errno == EINTR)) continue;
+            const ssize_t got = read(fd, dst, std::min<size_t>(n, 1u << 30));
+            if (got < 0 && errno == EINTR) continue;
+            if (got < 0) {
+                fail(VS_E_ARG, "cannot read %s: %s", path.c_str(), strerror(errno));
+                return -1;
+            }
+            raw_bytes += (uint64_t)got;
+            return got;
+        }
+    }
+    void run() {
+        (void)hipSetDevice(device);
+        std::vector<uint8_t> in(1u << 20);
+        size_t in_len = 0;
+        bool in_eof = false;
+        // the first bytes say whether the file is gzip (magic 1f 8b)
+        while (in_len < 2 && !in_eof) {
+            const ssize_t got = raw_read(in.data() + in_len, in.size() - in_len);
+            if (got < 0) { publish(0, true); return; }
+            if (got == 0) in_eof = true;
+            in_len += (size_t)got;
+        }
+        gzip = in_len >= 2 && in[0] == 0x1f && in[1] == 0x8b;
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (gzip && inflateInit2(&zs, 15 + 16) != Z_OK) {
+            fail(VS_E_OOM, "%s: zlib cannot start", path.c_str());
+            publish(0, true);
+            return;
+        }
+        size_t plain_at = 0;  // (plain text: bytes of `in` not yet handed on)
+        if (gzip) {
+            zs.next_in = in.data();
+            zs.avail_in = (uInt)in_len;
+        }
+        bool at_end = false;
+        while (!at_end) {
+            Slot *slot = nullptr;
+            {
+                std::unique_lock<std::mutex> lk(m);
+                cv.wait(lk, [&] { return stop || filled - taken < STREAM_RING_SLOTS; });
+                if (stop) break;
+                slot = &slots[filled % STREAM_RING_SLOTS];  // (free: the consumer gave it back)
+            }
+            if (!slot->p && hipHostMalloc((void **)&slot->p, chunk, hipHostMallocDefault) != hipSuccess) {
+                slot->p = nullptr;
+                fail(VS_E_OOM, "%s: cannot pin a %s-byte chunk", path.c_str(), std::to_string(chunk).c_str());
+            }
+            uint8_t *dst = slot->p;
+            if (!dst) { publish(0, true); break; }
+            size_t len = 0;
+            bool bad = false;
+            if (!gzip) {
+                const size_t now = std::min(chunk, in_len - plain_at);
+                memcpy(dst, in.data() + plain_at, now);
+                plain_at += now;
+                len = now;
+                while (len < chunk && !in_eof) {
+                    const ssize_t got = raw_read(dst + len, chunk - len);
+                    if (got < 0) { bad = true; break; }
+                    if (got == 0) in_eof = true;
+                    len += (size_t)got;
+                }
+                at_end = bad || (in_eof && plain_at == in_len);
+            } else {
+                int rc = Z_OK;
+                while (len < chunk) {
+                    if (zs.avail_in == 0 && !in_eof) {
+                        const ssize_t got = raw_read(in.data(), in.size());
+                        if (got < 0) { bad = true; break; }
+                        if (got == 0) in_eof = true;
+                        zs.next_in = in.data();
+                        zs.avail_in = (uInt)got;
+                    }
+                    zs.next_out = dst + len;
+                    zs.avail_out = (uInt)(chunk - len);
+                    rc = inflate(&zs, Z_NO_FLUSH);
+                    len = chunk - zs.avail_out;
+                    if (rc == Z_STREAM_END) {
+                        if (zs.avail_in == 0 && !in_eof) {  // more members may follow: look
+                            const ssize_t got = raw_read(in.data(), in.size());
+                            if (got < 0) { bad = true; break; }
+                            if (got == 0) in_eof = true;
+                            zs.next_in = in.data();
+                            zs.avail_in = (uInt)got;
+                        }
+                        if (zs.avail_in == 0 && in_eof) { at_end = true; break; }
+                        if (inflateReset(&zs) != Z_OK) { rc = Z_DATA_ERROR; }
+                        else continue;  // next member
+                    }
+                    if (rc == Z_OK || (rc == Z_BUF_ERROR && (zs.avail_out == 0 || (zs.avail_in == 0 && !in_eof)))) {
+                        if (zs.avail_in == 0 && in_eof && zs.avail_out != 0) rc = Z_DATA_ERROR;  // truncated stream
+                        else continue;
+                    }
+                    if (rc == Z_BUF_ERROR) rc = Z_DATA_ERROR;  // (no progress with all input consumed: truncated)
+                    char code[16];
+                    snprintf(code, sizeof code, "%d", rc);
+                    fail(VS_E_ARG, "%s: not a complete gzip stream (zlib code %s)", path.c_str(), code);
+                    bad = true;
+                    break;
+                }
+                at_end = at_end || bad;
+            }
+            text_bytes += len;
+            publish(len, at_end);
+        }
+        if (gzip) inflateEnd(&zs);
+    }
+    void publish(size_t len, bool last) {
+        std::lock_guard<std::mutex> lk(m);
+        Slot &s = slots[filled % STREAM_RING_SLOTS];
+        s.len = len;
+        s.last = last;
+        filled++;
+        finished = last;
+        cv.notify_all();
+    }
+    // the next filled slot (blocks until the reader has one)
+    Slot &take() {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return filled > taken; });
+        return slots[taken % STREAM_RING_SLOTS];
+    }
+    void give_back() {
+        std::lock_guard<std::mutex> lk(m);
+        taken++;
+        cv.notify_all();
+    }
+    void shut() {
+        {
+            std::lock_guard<std::mutex> lk(m);
+            stop = true;
+        }
+        cv.notify_all();
+        if (th.joinable()) th.join();
+        for (Slot &s : slots)
+            if (s.p) (void)hipHostFree(s.p);
+        if (fd >= 0) close(fd);
+        fd = -1;
+    }
+};
+
+template <typename T>
+int grow(vs_ctx *ctx, T *&p, size_t &cap, size_t need) {
+    if (cap >= need) return VS_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t n = need + need / 4 + 64;
+    VS_HIP(ctx, hipMalloc((void **)&p, n * sizeof(T)));
+    cap = n;
+    return VS_OK;
+}
+
+// The device side of one file: the window (two buffers, the leftover copied from one to the other after a block) and
+// its line ends.
+struct DevFile {
+    uint8_t *win[2] = {nullptr, nullptr};
+    size_t win_cap[2] = {0, 0};
+    int cur = 0;
+    size_t size = 0;       // bytes in the window
+    size_t validated = 0;  // [0, validated) is known to be valid UTF-8 (ASCII, or checked on the host)
+    uint32_t *ends = nullptr, *wg = nullptr;
+    size_t ends_cap = 0, wg_cap = 0;
+    uint32_t n_nl = 0, flags = 0, last_byte = 0;
+    uint64_t records = 0;  // complete records in the window
+    uint64_t first_record = 0;  // file-wide number of the window's first record
+    bool eof = false;      // the reader's last slot is in the window
+    int err = VS_OK;       // first failure of this file (reported after the end of both, in file order)
+    std::string err_msg;
+    uint32_t pend[4] = {0, 0, 0, 0};  // (end-of-input check) bytes of a character cut by a chunk boundary
+    uint32_t n_pend = 0;
+};
+
+}  // namespace
+
+struct vs_fastq_stream {
+    int device = 0;
+    hipStream_t st = nullptr;
+    Reader rd[2];
+    DevFile df[2];
+    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // ST_N words each (h_stat pinned)
+    uint32_t *d_wcnt = nullptr;
+    size_t wcnt_cap = 0;
+    uint64_t pairs = 0;
+    uint32_t flags_seen = 0;
+    bool done = false;
+    int failed = VS_OK;
+    std::string failed_msg;
+};
+
+namespace {
+
+int stream_fail(vs_ctx *ctx, vs_fastq_stream *s, int code, const std::string &msg) {
+    s->done = true;
+    s->failed = code;
+    s->failed_msg = msg;
+    return vs_fail(ctx, code, "%s", msg.c_str());
+}
+
+// count + scan of window f: n_nl, flags, last byte into the host status (synchronises the stream)
+int scan_windows(vs_ctx *ctx, vs_fastq_stream *s) {
+    hipStream_t st = s->st;
+    VS_HIP(ctx, hipMemsetAsync(s->d_stat, 0, sizeof(uint32_t) * ST_N, st));
+    for (int f = 0; f < 2; f++) {
+        DevFile &d = s->df[f];
+        const uint64_t words = (d.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
+        if (int rc = grow(ctx, d.wg, d.wg_cap, wgs + 1u)) return rc;
+        if (wgs) {
+            hipLaunchKernelGGL(k_sl_count, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, (const uint8_t *)d.win[d.cur], (uint64_t)d.size, d.wg,
+                               s->d_stat + f * ST_PER_FILE);
+            hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, d.wg, (uint32_t)wgs, s->d_stat + f * ST_PER_FILE + ST_NL);
+        }
+    }
+    VS_HIP(ctx, hipGetLastError());
+    VS_HIP(ctx, hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_N, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
+    for (int f = 0; f < 2; f++) {
+        DevFile &d = s->df[f];
+        d.n_nl = s->h_stat[f * ST_PER_FILE + ST_NL];
+        d.flags = s->h_stat[f * ST_PER_FILE + ST_FLAGS];
+        d.last_byte = s->h_stat[f * ST_PER_FILE + ST_LAST];
+        s->flags_seen |= d.flags;
+        if (!d.flags) d.validated = d.size;
+        const uint64_t lines = (uint64_t)d.n_nl + ((d.eof && d.size && d.last_byte != '\n') ? 1u : 0u);
+        d.records = lines / 4u;
+    }
+    return VS_OK;
+}
+
+// Text mode on the host for a flagged window (see the top of the file): its bytes up to the last line end (all of them at
+// the end of the file) are translated and checked, the rest -- a partial line -- stays as it is for the next chunk.
+int translate_window(vs_ctx *ctx, vs_fastq_stream *s, int f) {
+    DevFile &d = s->df[f];
+    std::vector<uint8_t> buf(d.size);
+    if (d.size) VS_HIP(ctx, hipMemcpy(buf.data(), d.win[d.cur], d.size, hipMemcpyDeviceToHost));
+    size_t cut = d.size;
+    if (!d.eof) {
+        size_t lim = d.size;
+        if (lim && buf[lim - 1] == '\r') lim--;  // ("\r\n" may straddle the chunks)
+        cut = 0;
+        for (size_t i = lim; i-- > 0;)
+            if (buf[i] == '\n' || buf[i] == '\r') { cut = i + 1; break; }
+    }
+    if (d.validated < cut && !vs_utf8_range_ok(buf.data(), cut, d.validated, cut)) {
+        d.err = VS_E_UTF8;
+        d.err_msg = s->rd[f].path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
+        return VS_E_UTF8;
+    }
+    std::vector<uint8_t> out;
+    out.reserve(d.size);
+    for (size_t i = 0; i < cut;) {
+        const uint8_t c = buf[i];
+        if (c == '\r') {
+            out.push_back('\n');
+            i += (i + 1 < cut && buf[i + 1] == '\n') ? 2u : 1u;
+        } else if (c < 0x80u) {
+            out.push_back(c);
+            i++;
+        } else {  // one character, one byte (seq_chars); checked above
+            const uint32_t cl = vs_utf8_char_len(buf.data() + i, cut - i);
+            out.push_back('?');
+            i += cl ? cl : 1u;
+        }
+    }
+    const size_t translated = out.size();
+    out.insert(out.end(), buf.begin() + (ptrdiff_t)cut, buf.end());
+    if (!out.empty()) VS_HIP(ctx, hipMemcpy(d.win[d.cur], out.data(), out.size(), hipMemcpyHostToDevice));
+    d.size = out.size();
+    d.validated = translated;
+    return VS_OK;
+}
+
+// the end-of-input check of bytes that were never parsed (the rest of the longer file): valid UTF-8, a character cut by
+// a chunk boundary carried to the next piece
+bool check_piece(DevFile &d, const uint8_t *p, size_t n, bool last) {
+    std::vector<uint8_t> tmp;
+    if (d.n_pend) {
+        for (uint32_t i = 0; i < d.n_pend; i++) tmp.push_back((uint8_t)d.pend[i]);
+        tmp.insert(tmp.end(), p, p + n);
+        p = tmp.data();
+        n = tmp.size();
+        d.n_pend = 0;
+    }
+    size_t upto = n;
+    if (!last) {  // a lead byte in the last three whose character does not fit: wait for the next piece
+        for (size_t j = n; j-- > 0 && n - j <= 3u;) {
+            const uint8_t c = p[j];
+            if ((c & 0xC0u) == 0x80u) continue;
+            if (c >= 0xC0u) {
+                const size_t len = c >= 0xF0u ? 4u : c >= 0xE0u ? 3u : 2u;
+                if (j + len > n) upto = j;
+            }
+            break;
+        }
+    }
+    bool high = false;
+    for (size_t i = 0; i < upto && !high; i++) high = p[i] >= 0x80u;
+    if (high && !vs_utf8_range_ok(p, upto, 0, upto)) return false;
+    for (size_t i = upto; i < n; i++) d.pend[d.n_pend++] = p[i];
+    return true;
+}
+
+// Both files to their ends (the reference reads them whole): every byte not yet checked is checked, a reader's failure is
+// picked up; then the first failure in file order.
+int finish(vs_ctx *ctx, vs_fastq_stream *s) {
+    for (int f = 0; f < 2; f++) {
+        DevFile &d = s->df[f];
+        Reader &r = s->rd[f];
+        if (d.err == VS_OK && d.validated < d.size && (d.flags & FL_HIGH)) {
+            std::vector<uint8_t> buf(d.size - d.validated);
+            VS_HIP(ctx, hipMemcpy(buf.data(), d.win[d.cur] + d.validated, buf.size(), hipMemcpyDeviceToHost));
+            if (!check_piece(d, buf.data(), buf.size(), d.eof)) {
+                d.err = VS_E_UTF8;
+                d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
+            }
+        }
+        d.validated = d.size;
+        while (!d.eof) {
+            Slot &sl = r.take();
+            if (d.err == VS_OK && !check_piece(d, sl.p, sl.len, sl.last)) {
+                d.err = VS_E_UTF8;
+                d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
+            }
+            d.eof = sl.last;
+            r.give_back();
+        }
+        if (d.err == VS_OK && d.n_pend) {  // (a character cut off by the end of the file)
+            d.err = VS_E_UTF8;
+            d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
+        }
+        if (r.err != VS_OK) {  // (a read or gzip failure comes before what the bytes say: map_file fails first)
+            d.err = r.err;
+            d.err_msg = r.err_msg;
+        }
+    }
+    s->done = true;
+    for (int f = 0; f < 2; f++)
+        if (s->df[f].err != VS_OK) return stream_fail(ctx, s, s->df[f].err, s->df[f].err_msg);
+    return VS_OK;
+}
+
+// the next slot of file f appended to its window (blocks until the reader has one)
+int append_chunk(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot *&taken) {
+    DevFile &d = s->df[f];
+    Slot &sl = s->rd[f].take();
+    taken = &sl;
+    if (d.size + sl.len > STREAM_MAX_WINDOW)
+        return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete record", s->rd[f].path.c_str(),
+                       (unsigned long long)(d.size + sl.len));
+    const size_t need = ((d.size + sl.len + 15u) & ~(size_t)15u) + 16u;
+    if (d.win_cap[d.cur] < need) {  // keep the leftover: grow the other buffer, copy, switch
+        const int o = d.cur ^ 1;
+        if (int rc = grow(ctx, d.win[o], d.win_cap[o], need)) return rc;
+        if (d.size) VS_HIP(ctx, hipMemcpyAsync(d.win[o], d.win[d.cur], d.size, hipMemcpyDeviceToDevice, s->st));
+        d.cur = o;
+    }
+    if (sl.len) VS_HIP(ctx, hipMemcpyAsync(d.win[d.cur] + d.size, sl.p, sl.len, hipMemcpyHostToDevice, s->st));
+    d.size += sl.len;
+    d.eof = sl.last;
+    return VS_OK;
+}
+
+// the window after its first `cut` bytes (the records of the block) have gone: the leftover to the front of the other buffer
+int drop_front(vs_ctx *ctx, vs_fastq_stream *s, int f, size_t cut, uint64_t records) {
+    DevFile &d = s->df[f];
+    const size_t rest = d.size - cut;
+    const int o = d.cur ^ 1;
+    if (int rc = grow(ctx, d.win[o], d.win_cap[o], ((rest + 15u) & ~(size_t)15u) + 16u)) return rc;
+    if (rest) VS_HIP(ctx, hipMemcpyAsync(d.win[o], d.win[d.cur] + cut, rest, hipMemcpyDeviceToDevice, s->st));
+    d.cur = o;
+    d.size = rest;
+    d.validated = d.validated > cut ? d.validated - cut : 0;
+    d.records -= records;
+    d.first_record += records;
+    return VS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vs_fastq_stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, vs_fastq_stream **out) {
+    if (!ctx || !fwd_path || !rve_path || !out) return vs_fail(ctx, VS_E_ARG, "vs_fastq_stream_open: bad argument");
+    *out = nullptr;
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    size_t chunk = STREAM_CHUNK_BYTES;
+    if (const char *ev = getenv("VS_STREAM_CHUNK")) chunk = std::max<size_t>(1u, (size_t)atoll(ev));  // (tests: records across chunks)
+    vs_fastq_stream *s = new vs_fastq_stream();
+    s->device = ctx->device;
+    const char *paths[2] = {fwd_path, rve_path};
+    for (int f = 0; f < 2; f++) {
+        Reader &r = s->rd[f];
+        r.path = paths[f];
+        r.chunk = chunk;
+        r.device = ctx->device;
+        r.fd = open(paths[f], O_RDONLY);
+        if (r.fd < 0) {
+            const int e = errno;
+            for (int g = 0; g < f; g++) close(s->rd[g].fd);
+            delete s;
+            return vs_fail(ctx, VS_E_ARG, "cannot open %s: %s", paths[f], strerror(e));
+        }
+    }
+    hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
+    if (e1 == hipSuccess) e1 = hipMalloc((void **)&s->d_stat, sizeof(uint32_t) * ST_N);
+    if (e1 == hipSuccess) e1 = hipHostMalloc((void **)&s->h_stat, sizeof(uint32_t) * ST_N, hipHostMallocDefault);
+    if (e1 != hipSuccess) {
+        vs_fastq_stream_close(s);
+        return vs_fail(ctx, VS_E_HIP, "vs_fastq_stream_open: %s", hipGetErrorString(e1));
+    }
+    for (int f = 0; f < 2; f++) s->rd[f].th = std::thread([r = &s->rd[f]] { r->run(); });
+    *out = s;
+    return VS_OK;
+}
+
+int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs_reads **out, uint64_t *n_pairs) {
+    if (!ctx || !s || !out || !n_pairs) return vs_fail(ctx, VS_E_ARG, "vs_fastq_stream_next: bad argument");
+    *out = nullptr;
+    *n_pairs = 0;
+    if (s->failed != VS_OK) return vs_fail(ctx, s->failed, "%s", s->failed_msg.c_str());
+    if (s->done) return VS_OK;
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    if (!max_pairs || max_pairs > (1ull << 30)) max_pairs = 1ull << 30;
+    uint64_t n = 0;
+    for (int round = 0;; round++) {
+        // more text for the file that holds fewer complete records (both at the start): a window holds what is left of the
+        // last block + one chunk, so its size stays bounded whatever the two files' record lengths
+        Slot *taken[2] = {nullptr, nullptr};
+        bool appended = false;
+        for (int f = 0; f < 2; f++) {
+            DevFile &d = s->df[f], &o = s->df[f ^ 1];
+            const bool need = !d.eof && d.records < max_pairs && d.records <= o.records && !(o.eof && o.records <= d.records);
+            if (!need) continue;
+            if (int rc = append_chunk(ctx, s, f, taken[f])) {
+                const std::string msg = vs_last_error(ctx);
+                for (int g = 0; g <= f; g++)
+                    if (taken[g]) s->rd[g].give_back();
+                return stream_fail(ctx, s, rc, msg);
+            }
+            appended = true;
+        }
+        if (round > 0 && !appended) return finish(ctx, s);  // (nothing more to read and no pair: the end)
+        int rc = scan_windows(ctx, s);
+        for (int f = 0; f < 2; f++)
+            if (taken[f]) s->rd[f].give_back();  // (the stream is synchronised: the upload is done)
+        if (rc) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+        bool again = false;
+        for (int f = 0; f < 2; f++) {
+            DevFile &d = s->df[f];
+            if (taken[f] && d.flags && d.validated < d.size) {  // (text that arrived with this chunk: host text mode)
+                if (translate_window(ctx, s, f) != VS_OK) return finish(ctx, s);
+                again = true;
+            }
+        }
+        if (again && (rc = scan_windows(ctx, s))) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+        n = std::min(std::min(s->df[0].records, s->df[1].records), max_pairs);
+        if (n > 0) break;
+        if ((s->df[0].eof && s->df[0].records == 0) || (s->df[1].eof && s->df[1].records == 0)) return finish(ctx, s);
+    }
+    // ---- the block of n pairs
+    hipStream_t st = s->st;
+    const uint64_t n_ends = 2u * n;
+    for (int f = 0; f < 2; f++) {
+        DevFile &d = s->df[f];
+        if (int rc = grow(ctx, d.ends, d.ends_cap, (size_t)d.n_nl + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+        const uint64_t words = (d.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
+        if (wgs) hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, (const uint8_t *)d.win[d.cur], (uint64_t)d.size, d.wg, d.ends);
+    }
+    if (int rc = grow(ctx, s->d_wcnt, s->wcnt_cap, n_ends + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+    SlWin w0 = {s->df[0].win[s->df[0].cur], s->df[0].ends, s->df[0].n_nl, (uint32_t)s->df[0].size};
+    SlWin w1 = {s->df[1].win[s->df[1].cur], s->df[1].ends, s->df[1].n_nl, (uint32_t)s->df[1].size};
+    vs_reads *r = new vs_reads();
+    r->n_ends = n_ends;
+    r->cached = true;
+    const size_t b_woff = sizeof(uint32_t) * (n_ends + 1), b_meta = sizeof(uint32_t) * n_ends;
+    r->d_woff = vs_cache_alloc(ctx, b_woff);
+    r->d_meta = vs_cache_alloc(ctx, b_meta);
+    if (!r->d_woff || !r->d_meta) {
+        vs_reads_free(ctx, r);
+        return stream_fail(ctx, s, VS_E_OOM, "vs_fastq_stream_next: device buffers for the block");
+    }
+    hipError_t e1 = hipMemsetAsync(s->d_stat + ST_MAXLEN, 0, sizeof(uint32_t) * (ST_N - ST_MAXLEN), st);
+    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + ST_TOO_LONG, 0xFF, sizeof(uint32_t), st);
+    if (e1 == hipSuccess) {
+        hipLaunchKernelGGL(k_sl_ends, dim3((unsigned)((n_ends + 1u + SL_TPB - 1u) / SL_TPB)), dim3(SL_TPB), 0, st, w0, w1, (uint32_t)n,
+                           (uint32_t *)r->d_meta, s->d_wcnt, s->d_stat);
+        hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, s->d_wcnt, (uint32_t)(n_ends + 1u), s->d_stat + ST_WORDS);
+        e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt, b_woff, hipMemcpyDeviceToDevice, st);
+    }
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_N, hipMemcpyDeviceToHost, st);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+    if (e1 != hipSuccess) {
+        vs_reads_free(ctx, r);
+        return stream_fail(ctx, s, VS_E_HIP, std::string("vs_fastq_stream_next: ") + hipGetErrorString(e1));
+    }
+    if (s->h_stat[ST_TOO_LONG] != 0xFFFFFFFFu) {
+        const uint32_t e = s->h_stat[ST_TOO_LONG];
+        const int f = (int)(e & 1u);
+        vs_reads_free(ctx, r);
+        char msg[600];
+        snprintf(msg, sizeof msg, "%s: record %llu has a sequence line of more than %u bytes", s->rd[f].path.c_str(),
+                 (unsigned long long)(s->df[f].first_record + (e >> 1)), (unsigned)VS_LEN_MASK);
+        return stream_fail(ctx, s, VS_E_RANGE, msg);
+    }
+    const uint64_t words = s->h_stat[ST_WORDS];
+    r->n_words = words;
+    r->max_len = s->h_stat[ST_MAXLEN];
+    const size_t b_words = sizeof(uint32_t) * (words + VS_PAD_WORDS);
+    r->d_words = vs_cache_alloc(ctx, b_words);
+    void *d_mask = vs_cache_alloc(ctx, b_words);
+    r->bytes = b_woff + b_meta + b_words;
+    if (!r->d_words || !d_mask) {
+        if (d_mask) vs_cache_release(ctx, d_mask);
+        vs_reads_free(ctx, r);
+        return stream_fail(ctx, s, VS_E_OOM, "vs_fastq_stream_next: device buffers for the block");
+    }
+    e1 = hipMemsetAsync((uint32_t *)r->d_words + words, 0, sizeof(uint32_t) * VS_PAD_WORDS, st);
+    if (e1 == hipSuccess) e1 = hipMemsetAsync((uint32_t *)d_mask + words, 0, sizeof(uint32_t) * VS_PAD_WORDS, st);
+    if (e1 == hipSuccess) {
+        if (words)
+            hipLaunchKernelGGL(k_sl_pack, dim3((unsigned)((words + SL_TPB - 1u) / SL_TPB)), dim3(SL_TPB), 0, st, w0, w1, (uint32_t)n_ends,
+                               (uint32_t)words, (const uint32_t *)r->d_woff, (uint32_t *)r->d_words, (uint32_t *)d_mask, (uint32_t *)r->d_meta);
+        vs_launch_count_invalid(st, (const uint32_t *)r->d_meta, n_ends, s->d_stat + ST_INVALID);
+        e1 = hipGetLastError();
+    }
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_N, hipMemcpyDeviceToHost, st);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+    if (e1 == hipSuccess) {
+        r->n_invalid = s->h_stat[ST_INVALID];
+        if (r->n_invalid) {  // as vs_reads_pack: the mask and the position lists only when some end needs them
+            r->d_mask = d_mask;
+            d_mask = nullptr;
+            r->bytes += b_words;
+            r->d_inv4 = vs_cache_alloc(ctx, sizeof(uint32_t) * n_ends);
+            if (!r->d_inv4) e1 = hipErrorOutOfMemory;
+            else {
+                r->bytes += sizeof(uint32_t) * n_ends;
+                vs_launch_inv4(st, (const uint32_t *)r->d_woff, (const uint32_t *)r->d_mask, n_ends, (uint32_t *)r->d_meta, (uint32_t *)r->d_inv4);
+                e1 = hipGetLastError();
+            }
+        }
+    }
+    if (d_mask) vs_cache_release(ctx, d_mask);
+    size_t cut[2] = {s->h_stat[ST_CUT + 0], s->h_stat[ST_CUT + 1]};
+    for (int f = 0; f < 2 && e1 == hipSuccess; f++)
+        if (drop_front(ctx, s, f, cut[f], n) != VS_OK) e1 = hipErrorOutOfMemory;
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);  // (the block is complete when it is handed out)
+    if (e1 != hipSuccess) {
+        vs_reads_free(ctx, r);
+        return stream_fail(ctx, s, e1 == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, std::string("vs_fastq_stream_next: ") + hipGetErrorString(e1));
+    }
+    s->pairs += n;
+    *out = r;
+    *n_pairs = n;
+    return VS_OK;
+}
+
+int vs_fastq_stream_info(const vs_fastq_stream *s, uint64_t info[4]) {
+    if (!s || !info) return VS_E_ARG;
+    info[0] = s->pairs;
+    info[1] = s->rd[0].text_bytes + s->rd[1].text_bytes;
+    info[2] = s->rd[0].raw_bytes + s->rd[1].raw_bytes;
+    info[3] = (uint64_t)s->flags_seen | (s->rd[0].gzip ? 4u : 0u) | (s->rd[1].gzip ? 8u : 0u) | (s->done ? 16u : 0u);
+    return VS_OK;
+}
+
+void vs_fastq_stream_close(vs_fastq_stream *s) {
+    if (!s) return;
+    for (Reader &r : s->rd) r.shut();
+    if (s->st) (void)hipStreamSynchronize(s->st);
+    for (DevFile &d : s->df) {
+        void *ps[] = {d.win[0], d.win[1], d.ends, d.wg};
+        for (void *p : ps)
+            if (p) (void)hipFree(p);
+    }
+    if (s->d_stat) (void)hipFree(s->d_stat);
+    if (s->d_wcnt) (void)hipFree(s->d_wcnt);
+    if (s->h_stat) (void)hipHostFree(s->h_stat);
+    if (s->st) (void)hipStreamDestroy(s->st);
+    delete s;
+}
+
+// Test aid: the device line scanner on host text.  ends[i] (cap of them) = byte offset of newline i; info[0] = newlines,
+// info[1] = flags (1: '\r', 2: a byte >= 0x80), info[2] = the record cut: one past the newline that ends the last line
+// completing a record when the text's first line has number `line0` (mod 4), 0 if none.
+int vs_fastq_scan_text(vs_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t line0, uint64_t *ends, uint64_t cap, uint64_t info[3]) {
+    if (!ctx || (!text && n) || !info || n > STREAM_MAX_WINDOW) return vs_fail(ctx, VS_E_ARG, "vs_fastq_scan_text: bad argument");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t words = (n + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
+    uint8_t *d_txt = nullptr;
+    uint32_t *d_wg = nullptr, *d_ends = nullptr, *d_st = nullptr;
+    uint32_t hs[ST_N] = {0};
+    hipError_t e1 = hipMalloc((void **)&d_txt, words * 16u + 16u);
+    if (e1 == hipSuccess) e1 = hipMalloc((void **)&d_wg, sizeof(uint32_t) * (wgs + 1u));
+    if (e1 == hipSuccess) e1 = hipMalloc((void **)&d_ends, sizeof(uint32_t) * (n + 1u));
+    if (e1 == hipSuccess) e1 = hipMalloc((void **)&d_st, sizeof(uint32_t) * ST_N);
+    if (e1 == hipSuccess) e1 = hipMemsetAsync(d_st, 0, sizeof(uint32_t) * ST_N, st);
+    if (e1 == hipSuccess && n) e1 = hipMemcpyAsync(d_txt, text, n, hipMemcpyHostToDevice, st);
+    if (e1 == hipSuccess && wgs) {
+        hipLaunchKernelGGL(k_sl_count, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, (const uint8_t *)d_txt, n, d_wg, d_st);
+        hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, d_wg, (uint32_t)wgs, d_st + ST_NL);
+        hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, (const uint8_t *)d_txt, n, (const uint32_t *)d_wg, d_ends);
+        e1 = hipGetLastError();
+    }
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(hs, d_st, sizeof hs, hipMemcpyDeviceToHost, st);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+    std::vector<uint32_t> h(hs[ST_NL] ? hs[ST_NL] : 1u);
+    if (e1 == hipSuccess && hs[ST_NL]) e1 = hipMemcpy(h.data(), d_ends, sizeof(uint32_t) * hs[ST_NL], hipMemcpyDeviceToHost);
+    void *ps[] = {d_txt, d_wg, d_ends, d_st};
+    for (void *p : ps)
+        if (p) (void)hipFree(p);
+    if (e1 != hipSuccess) return vs_fail(ctx, VS_E_HIP, "vs_fastq_scan_text: %s", hipGetErrorString(e1));
+    const uint64_t nl = hs[ST_NL];
+    info[0] = nl;
+    info[1] = hs[ST_FLAGS];
+    // newline i ends line line0 + i; a record closes with a line of number 3 mod 4
+    const uint64_t first_close = (3u + 4u - (line0 & 3u)) & 3u;  // index of the first newline that closes a record
+    info[2] = 0;
+    if (nl > first_close) {
+        const uint64_t last_close = first_close + (nl - 1u - first_close) / 4u * 4u;
+        info[2] = (uint64_t)h[last_close] + 1u;
+    }
+    if (ends)
+        for (uint64_t i = 0; i < nl && i < cap; i++) ends[i] = h[i];
+    return VS_OK;
+}
+
+}  // extern "C"

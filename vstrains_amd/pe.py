@@ -216,6 +216,66 @@ class FastqPair:
         return ReadBlock(self._ctx, h)
 
 
+class FastqStream:
+    """Both FASTQ files read front to back through the library's streamed ingest (``vs_fastq_stream_*``): any file a
+    process can read once -- a FIFO, ``/dev/stdin``, ``<(zcat R1.fq.gz)``, a regular or gzip file -- with host memory
+    bounded by a ring of pinned chunks; the records are found and packed on the device.  Iterating yields ``ReadBlock``s
+    of at most ``block_pairs`` pairs until the input is exhausted; the checks of the whole input (bytes that are not valid
+    UTF-8 anywhere, a cut-off gzip stream) raise before the iteration ends, with the exceptions ``FastqPair`` raises.
+    ``close()`` as ``FastqPair``."""
+
+    def __init__(self, fwd: str, rve: str, ctx: "Context", block_pairs: int = 1 << 20):
+        self._ctx = ctx
+        self._h = None
+        self.block_pairs = block_pairs
+        h = C.c_void_p()
+        rc = nat.lib().vs_fastq_stream_open(ctx._h, fwd.encode(), rve.encode(), C.byref(h))
+        if rc != nat.VS_OK:
+            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+            if "cannot open" in msg:
+                raise FileNotFoundError(msg)
+            raise nat.NativeError(rc, msg)
+        self._h = h
+
+    @property
+    def info(self):
+        a = (C.c_uint64 * 4)()
+        nat.lib().vs_fastq_stream_info(self._h, a)
+        return dict(pairs=int(a[0]), text_bytes=int(a[1]), file_bytes=int(a[2]), flags=int(a[3]))
+
+    @property
+    def n_pairs(self) -> int:
+        """pairs delivered so far (all of them once the iteration has ended)"""
+        return self.info["pairs"]
+
+    def next_block(self) -> Optional["ReadBlock"]:
+        """The next block, or None at the end of the input."""
+        h = C.c_void_p()
+        n = C.c_uint64(0)
+        rc = nat.lib().vs_fastq_stream_next(self._ctx._h, self._h, self.block_pairs, C.byref(h), C.byref(n))
+        if rc != nat.VS_OK:
+            FastqPair._raise(self._ctx._h, rc)  # ValueError for bytes that are not valid UTF-8
+        return ReadBlock(self._ctx, h) if n.value else None
+
+    def __iter__(self):
+        while True:
+            block = self.next_block()
+            if block is None:
+                return
+            yield block
+
+    def close(self):
+        if self._h:
+            nat.lib().vs_fastq_stream_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def encode_seqs(seqs: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
     off = np.zeros(len(seqs) + 1, dtype=np.uint64)
     if len(seqs):
@@ -361,6 +421,15 @@ class Context:
         a = (C.c_uint64 * 6)()
         nat.check(self._h, nat.lib().vs_index_info(self._h, a))
         return dict(seed_len=a[0], stride=a[1], seed_positions=a[2], slots=a[3], distinct_seeds=a[4], device_bytes=a[5])
+
+    def scan_text(self, text: bytes, line0: int = 0):
+        """The streamed ingest's device line scanner on ``text`` (a test aid, ``vs_fastq_scan_text``): (byte offsets of the
+        newlines, flags: 1 a carriage return, 2 a byte >= 0x80, the record cut when the first line has number ``line0``)."""
+        buf = np.frombuffer(text or b"\0", dtype=np.uint8)
+        ends = np.zeros(max(text.count(b"\n"), 1), dtype=np.uint64)
+        info = (C.c_uint64 * 3)()
+        nat.check(self._h, nat.lib().vs_fastq_scan_text(self._h, buf.ctypes.data, len(text), line0, ends.ctypes.data, ends.size, info))
+        return ends[: int(info[0])].copy(), int(info[1]), int(info[2])
 
     def pack(self, ascii_bytes: np.ndarray, off: np.ndarray) -> ReadBlock:
         ascii_bytes = np.ascontiguousarray(ascii_bytes, dtype=np.uint8)

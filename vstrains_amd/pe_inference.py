@@ -7,6 +7,7 @@ stdout lines; reference lines cited inline), running on MI355X through libvstrai
 import argparse
 import os
 import shutil
+import stat
 import sys
 import time
 
@@ -31,6 +32,11 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     on the device.  Returns ``(node ids in file order, PeCounter)``.  ``stages_follow``: the graph stages will build their
     PE-link table from these counters in this process (the pipeline; not the stand-alone script, which writes the two text
     files) -- the table's device buffer is then set aside together with the counters."""
+    rank, world = _rank_world()
+    streamed = use_stream(fwd, rve)
+    if world > 1 and not (_regular(fwd) and _regular(rve)):  # (the sharded path maps regular files; VS_FASTQ_STREAM aside)
+        raise ValueError("the FASTQ inputs %s / %s are not both regular files: a pipe can be read by one process only, so "
+                         "the sharded (torchrun) run cannot take it; run one process, or write the reads to files" % (fwd, rve))
     ids, seqs = host.read_gfa_segments(gfa)  # :100-112
     ctx.build_index(seqs, kmer_size)  # :114-135  (KeyError on a bad node base, as :13)
     counter = host.PeCounter(ctx)
@@ -38,7 +44,6 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     print("Start aligning reads to gfa nodes")  # :146
     # one process per GPU (torchrun): this rank counts its contiguous block of the pairs and the
     # counters are summed over ranks afterwards (RCCL all-reduce); a single process takes everything
-    rank, world = _rank_world()
     if rank == 0 and stages_follow:
         counter.reserve_link_table()  # (the graph stages run on this rank: their table's buffer is taken now)
     if world > 1:
@@ -46,6 +51,12 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
         # each indexes only the bytes of its own records (:154's total follows from the counts)
         fq = host.FastqPair.open_shard(fwd, rve, ctx, rank, world)
         count_fastq(ctx, fq, counter, fq.block_offset, fq.block_offset + len(fq), progress=(rank == 0))
+    elif streamed:
+        fq = host.FastqStream(fwd, rve, ctx, block_pairs=BATCH_PAIRS)  # :146-154 from any readable file, read once
+        try:
+            count_stream(ctx, fq, counter, progress=True)
+        finally:
+            fq.close()
     else:
         fq = host.FastqPair(fwd, rve, ctx)  # :146-154, native multi-threaded ingest
         count_fastq(ctx, fq, counter, 0, len(fq), progress=True)
@@ -53,6 +64,39 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     if world > 1:
         counter.all_reduce()  # (every rank ends with the full sums; only rank 0 writes the files and runs the stages)
     return ids, counter
+
+
+def _regular(path: str) -> bool:
+    try:
+        return stat.S_ISREG(os.stat(path).st_mode)
+    except OSError:
+        return True  # (a missing file: the mapped open names it)
+
+
+def use_stream(fwd: str, rve: str) -> bool:
+    """The streamed ingest reads the pair when either input is not a regular file (a FIFO, /dev/stdin, a process
+    substitution: there is nothing to map), or when ``VS_FASTQ_STREAM=1`` asks for it; regular files are mapped."""
+    return os.environ.get("VS_FASTQ_STREAM") == "1" or not (_regular(fwd) and _regular(rve))
+
+
+def count_stream(ctx, fs, counter, progress: bool = False):
+    """Every pair of a ``FastqStream`` through the counters, block by block: the device packs block i+1 while it still
+    counts block i.  The total is known only at the end of the input, so the progress lines (:156-157) are held and
+    printed then -- and not at all when the input fails its end-of-input checks, as the mapped path prints none."""
+    import torch
+
+    with torch.cuda.device(counter.device):
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    block = fs.next_block()
+    while block is not None:
+        counter.add(block)
+        nxt = fs.next_block()
+        ctx.sync()
+        block.free()
+        block = nxt
+    if progress:
+        for mark in range(0, fs.n_pairs, 100000):
+            print("Number of processed reads: ", mark)
 
 
 def count_fastq(ctx, fq, counter, first: int, last: int, batch: int = BATCH_PAIRS, progress: bool = False):
