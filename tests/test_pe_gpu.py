@@ -607,10 +607,8 @@ def test_device_read_generator_equals_cpu_twin(host, ctx):
 @pytest.mark.parametrize("env", [
     {"VS_NO_SORT": "1"}, {"VS_NO_AGG": "1"}, {"VS_LOCUS_GLOBAL": "1"}, {"VS_EPT": "32"}, {"VS_EPT": "128"},
     {"VS_EPT": "6", "VS_GRID_PER_CU": "1"}, {"VS_ACC_FILL": "1"}, {"VS_ACC_FILL": "100"}, {"VS_NO_FAST": "1"},
-    {"VS_ACC_QUEUE": "0"}, {"VS_ACC_GRID_PER_CU": "1", "VS_ACC_QUEUE": "0"}, {"VS_NO_XCD_MAP": "1"}, {"VS_GRID_PER_CU": "8"}, {"VS_NO_STD": "1"}, {"VS_SHORTCUT": "1"}, {"VS_SHORTCUT": "0"},
-    {"VS_PHASE0": "1"}, {"VS_PHASE0": "1", "VS_NO_FAST": "1"}, {"VS_PHASE0": "1", "VS_SHORTCUT": "1"},  # (r5) the probe grid from offset 0, as before vs_seed_phase
+    {"VS_GRID_PER_CU": "8"}, {"VS_NO_STD": "1"}, {"VS_SHORTCUT": "1"}, {"VS_SHORTCUT": "0"},
     {"VS_ADAPT_GRID": "1"}, {"VS_ADAPT_GRID": "0"}, {"VS_ADAPT_GRID": "1", "VS_SHORTCUT": "1"}, {"VS_ADAPT_GRID": "1", "VS_NO_SORT": "1"},  # (r5) the adaptive step grid forced on / off
-    {"VS_ACC_ROUND": "128"},
     {"VS_EPT": "32", "VS_ACC_ROWS": "1"}, {"VS_NO_MID": "1"},
     {"VS_ACC_ROWS": "1"}, {"VS_ACC_ROWS": "1", "VS_ROWS_PER_STRIP": "1"}, {"VS_ACC_ROWS": "1", "VS_ROWS_PER_STRIP": "64", "VS_ACC_FILL": "1"},
     {"VS_ACC_ROWS": "1", "VS_NO_SORT": "1"}, {"VS_ACC_ROWS": "1", "VS_ROWS_KEYS": "100"}, {"VS_ACC_ROWS": "1", "VS_ROWS_SUB": "2048", "VS_ROWS_KEYS": "7"},
@@ -643,10 +641,11 @@ def test_every_kernel_variant_gives_the_same_counters(host, xctx, env, monkeypat
 
 
 def test_switches_do_not_exist_outside_experiment_mode(tmp_path):
-    """A production process (no VS_EXPERIMENT) never reads the tuning environment: with the timing-only
-    switches set -- VS_DEBUG_STOP stops k_pe_tiles after its first phase, VS_ACC_ABLATE=2 skips the counting,
-    both give WRONG counters in experiment mode -- the counters still equal the oracle's and the default
-    kernel runs.  With VS_EXPERIMENT=1 they stay unreachable too (that needs VS_EXPERIMENT=timing)."""
+    """A production process (no VS_EXPERIMENT, or any value other than 1 -- "timing" named a level of switches that
+    gave wrong counters by design) never reads the tuning environment: with the names of those switches set
+    (VS_DEBUG_STOP, VS_ACC_ABLATE) and VS_NO_STD, the counters equal the oracle's and the default kernel runs.  With
+    VS_EXPERIMENT=1 the removed switches do not exist either (the counters still equal the oracle's), while VS_NO_STD,
+    a test hook, takes effect."""
     script = r"""
 import sys, numpy as np
 sys.path.insert(0, %r)
@@ -665,7 +664,7 @@ assert np.array_equal(node_mat, want[0]) and np.array_equal(short_mat, want[1]),
 print("KERNEL", ctx.last_kernel)
 """ % ROOT
     kernels = []
-    for mode in (None, "1"):
+    for mode in (None, "1", "timing"):
         env = dict(os.environ, VS_DEBUG_STOP="1", VS_ACC_ABLATE="2", VS_NO_STD="1")
         env.pop("VS_EXPERIMENT", None)
         if mode:
@@ -673,8 +672,9 @@ print("KERNEL", ctx.last_kernel)
         proc = subprocess.run([sys.executable, "-c", script], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-3000:]
         kernels.append([l.split(" ", 1)[1] for l in proc.stdout.splitlines() if l.startswith("KERNEL")][0])
-    # production ignores VS_NO_STD as well; experiment mode honours it (a parity-safe switch)
+    # production ignores VS_NO_STD as well; experiment mode honours it (a test hook)
     assert kernels[0] != kernels[1], kernels
+    assert kernels[2] == kernels[0], kernels
 
 
 def test_full_size_block_properties(host, ctx, tmp_path):

@@ -4,7 +4,7 @@
 #
 #   tools/campaign.sh sweep  "<configs>" "<env 1>" "<env 2>" ...   per-kernel timing line of bench.py per config and environment
 #                                                                  (tuning switches need VS_EXPERIMENT=1, which this sets), e.g.
-#                                                                  tools/campaign.sh sweep "2 4" "X=0" "VS_GRID_PER_CU=64" "VS_NO_XCD_MAP=1"
+#                                                                  tools/campaign.sh sweep "2 4" "X=0" "VS_GRID_PER_CU=64" "VS_NO_SORT=1"
 #   tools/campaign.sh profiles "<configs>" [TAG]                   rocprofv3 kernel stats + HBM / L2 counters per config
 #                                                                  (tools/profile.sh), SQ / TCP counters for configs 2 and 3
 #                                                                  (tools/pmc.sh), summaries kept as gpurun_out/prof_<TAG>_c<i>/

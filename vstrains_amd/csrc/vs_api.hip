@@ -23,39 +23,25 @@ static bool env_on(const char *name) {
     return v && atoi(v) != 0;
 }
 
-void vs_tuning_load(VsTuning &t, int level) {
+void vs_tuning_load(VsTuning &t, bool experiment) {
     t = VsTuning();
-    if (level < 1) return;
+    if (!experiment) return;
     if (const char *v = getenv("VS_EPT")) t.ept = (uint32_t)atoi(v) & ~1u;
     if (const char *v = getenv("VS_GRID_PER_CU")) t.grid_per_cu = atoi(v) > 0 ? (uint32_t)atoi(v) : 128u;
-    if (const char *v = getenv("VS_ACC_GRID_PER_CU")) t.acc_grid_per_cu = atoi(v) > 0 ? (uint32_t)atoi(v) : 32u;
     if (const char *v = getenv("VS_ACC_FILL")) t.acc_fill_pct = atoi(v);
-    if (const char *v = getenv("VS_ACC_ROUND")) { const int r = atoi(v); t.acc_round = (r == 64 || r == 128 || r == 256 || r == 512 || r == 1024) ? (uint32_t)r : 0u; }
     if (const char *v = getenv("VS_SHORTCUT")) t.shortcut = atoi(v) != 0 ? 1 : 0;
     if (const char *v = getenv("VS_ADAPT_GRID")) t.adapt_grid = atoi(v) != 0 ? 1 : 0;
-    if (const char *v = getenv("VS_TABLE_SHIFT")) t.table_shift = atoi(v) < 1 ? 1u : atoi(v) > 8 ? 8u : (uint32_t)atoi(v);
     if (const char *v = getenv("VS_ACC_ROWS")) t.acc_rows = atoi(v) != 0 ? 1 : 0;
     if (const char *v = getenv("VS_LTAB_BITS")) t.ltab_bits = atoi(v) >= 0 && atoi(v) <= 31 ? atoi(v) : -1;
     if (const char *v = getenv("VS_ROWS_KEYS")) t.rows_keys = atoi(v) >= 2 && atoi(v) <= 65536 ? (uint32_t)atoi(v) : 0u;
     if (const char *v = getenv("VS_ROWS_SUB")) t.rows_sub = atoi(v) >= 1024 ? (uint32_t)atoi(v) : 0u;
-    if (const char *v = getenv("VS_ROWS_PER_STRIP1")) t.rows_per_strip1 = atoi(v) > 0 && atoi(v) <= 64 ? (uint32_t)atoi(v) : 0u;
     if (const char *v = getenv("VS_ROWS_PER_STRIP")) t.rows_per_strip = atoi(v) > 0 && atoi(v) <= 64 ? (uint32_t)atoi(v) : 0u;
     t.no_sort = env_on("VS_NO_SORT");
     t.locus_global = env_on("VS_LOCUS_GLOBAL");
-    t.no_xcd_map = env_on("VS_NO_XCD_MAP");
     t.no_fast = env_on("VS_NO_FAST");
     t.no_std = env_on("VS_NO_STD");
-    t.phase0 = env_on("VS_PHASE0");
     t.no_agg = env_on("VS_NO_AGG");
     t.no_mid = env_on("VS_NO_MID");
-    if (const char *v = getenv("VS_ACC_QUEUE")) t.acc_queue = atoi(v) != 0;
-    if (const char *v = getenv("VS_ACC_WGS")) t.acc_wgs = atoi(v) > 0 ? (uint32_t)atoi(v) : 0u;
-    t.debug_postings = getenv("VS_DEBUG_POSTINGS") != nullptr;
-    t.debug_occ = getenv("VS_DEBUG_OCC") != nullptr;
-    t.debug_acc = getenv("VS_DEBUG_ACC") != nullptr;
-    if (level < 2) return;
-    if (const char *v = getenv("VS_DEBUG_STOP")) t.debug_stop = (uint32_t)atoi(v);
-    if (const char *v = getenv("VS_ACC_ABLATE")) t.acc_ablate = atoi(v);
 }
 
 void *vs_cache_alloc(vs_ctx *ctx, size_t bytes) {
@@ -114,8 +100,8 @@ int vs_ctx_create(int device, vs_ctx **out) {
     if (e != hipSuccess) return vs_fail(nullptr, VS_E_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
     vs_ctx *ctx = new vs_ctx();
     ctx->device = device;
-    if (const char *ev = getenv("VS_EXPERIMENT")) ctx->experiment_level = strcmp(ev, "timing") == 0 ? 2 : strcmp(ev, "1") == 0 ? 1 : 0;
-    vs_tuning_load(ctx->tune, ctx->experiment_level);
+    if (const char *ev = getenv("VS_EXPERIMENT")) ctx->experiment = strcmp(ev, "1") == 0;
+    vs_tuning_load(ctx->tune, ctx->experiment);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->n_cu = prop.multiProcessorCount;
     for (int i = 0; i < 5; i++) {

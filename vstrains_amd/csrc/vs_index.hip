@@ -169,7 +169,6 @@ extern "C" int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint
     VS_HIP(ctx, hipMalloc(&ctx->d_fwd, 2 * b_words));  // forward text, then the reverse complements
     ctx->d_rc = nullptr;
     VS_HIP(ctx, hipMalloc(&ctx->d_post, b_post));
-    if (ctx->experiment_level) vs_tuning_load(ctx->tune, ctx->experiment_level);
     ctx->index_bytes = b_meta + 2 * b_words + b_post;  // (+ the table, sized below)
     // temporaries
     uint8_t *d_ascii = nullptr;
@@ -249,7 +248,7 @@ extern "C" int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint
                                (uint32_t *)nullptr, d_flags + 3);
             TRY(hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
             TRY(hipStreamSynchronize(st));
-            const uint64_t want = ((uint64_t)h_flags[3] << ctx->tune.table_shift) + 2u;
+            const uint64_t want = ((uint64_t)h_flags[3] << 3) + 2u;  // (at most an eighth full)
             bits_final = 4;
             while ((1ull << bits_final) < want) bits_final++;
             if (bits_final > 30u) bits_final = 30u;

@@ -97,40 +97,29 @@ struct FqStage {
     bool in_flight = false;
 };
 
-// Experiment switches of vs_pe_count (tuning sweeps, parity-test variants, timing ablations).  A production
-// context never reads the environment per call: the switches exist only when the process was started with
-// VS_EXPERIMENT=1 (parity-safe ones: every one of them is a test variant) or VS_EXPERIMENT=timing (also the
-// ones that stop kernels early / skip work and therefore produce WRONG counters); they are then re-read on
-// every call so that a test can flip them on a live context.  Defaults = the measured best.
+// Test hooks of vs_pe_count.  A production context never reads the environment: the switches exist only when the process
+// was started with VS_EXPERIMENT=1 (any other value is production), and are then re-read on every call so that a test can
+// flip them on a live context.  A switch is kept only if a test uses it and it forces a path that a production context
+// takes on some input (often one that only full-size blocks or large graphs reach), or the reference path of a test.
+// Every one of them gives the production counters.  Defaults = what a production context does.
 struct VsTuning {
     uint32_t ept = 0;               // VS_EPT (0 = automatic)
-    uint32_t grid_per_cu = 128;     // VS_GRID_PER_CU
-    uint32_t acc_grid_per_cu = 32;  // VS_ACC_GRID_PER_CU
-    int acc_fill_pct = -1;          // VS_ACC_FILL (-1 = 1/16 of the slots)
-    uint32_t acc_round = 0;         // VS_ACC_ROUND: pairs per round of the counter kernel (0 = automatic; 64 .. 1024, power of two)
+    uint32_t grid_per_cu = 128;     // VS_GRID_PER_CU: longer runs of tiles per workgroup, as a full-size block has
+    int acc_fill_pct = -1;          // VS_ACC_FILL (-1 = 1/16 of the slots): cell-table write-outs on fill
     int shortcut = -1;              // VS_SHORTCUT (-1 = by index statistics)
     int adapt_grid = -1;            // VS_ADAPT_GRID (-1 = by index statistics): the adaptive step grid of the compile-time-shape kernels
-    uint32_t table_shift = 3;       // VS_TABLE_SHIFT: seed table of >= (distinct seeds << shift) slots (3: at most an eighth full)
     int acc_rows = -1;              // VS_ACC_ROWS (-1 = by graph size): counters summed by row owners (k_rows_sum) instead of pair-major (k_pe_accumulate)
     int ltab_bits = -1;             // VS_LTAB_BITS: log2 slots of the block's list table (-1 = by block size, 0 = no table: every end stands for itself)
     uint32_t rows_keys = 0, rows_sub = 0;  // VS_ROWS_KEYS / VS_ROWS_SUB: rows per histogram pass, pairs per transposition (0 = the constants; tests shrink them)
-    uint32_t rows_per_strip1 = 0;   // VS_ROWS_PER_STRIP1: the same for short_mat alone
     uint32_t rows_per_strip = 0;    // VS_ROWS_PER_STRIP (0 = automatic): matrix rows one workgroup of k_rows_sum owns at a time
-    bool no_sort = false, locus_global = false, no_xcd_map = false, no_fast = false, no_std = false, no_agg = false;
-    bool acc_queue = true;
-    uint32_t acc_wgs = 0;           // VS_ACC_WGS: workgroups of k_pe_accumulate's chunk queue (0 = two per CU)
+    bool no_sort = false, locus_global = false, no_fast = false, no_std = false, no_agg = false;
     bool no_mid = false;            // VS_NO_MID: overflow pairs straight to k_pe_slow
-    bool phase0 = false;            // VS_PHASE0: probe grid 0, s, 2s, ... as before round 5 (vs_seed_phase); the generic kernels only (implies VS_NO_STD)
-    bool debug_postings = false, debug_occ = false, debug_acc = false;
-    // timing only (VS_EXPERIMENT=timing): wrong counters by design
-    uint32_t debug_stop = 0;        // VS_DEBUG_STOP=1..5
-    int acc_ablate = -1;            // VS_ACC_ABLATE=2|3
 };
-void vs_tuning_load(VsTuning &t, int level);  // level 0: defaults, 1: parity-safe switches, 2: + timing-only ones
+void vs_tuning_load(VsTuning &t, bool experiment);  // production (false): the defaults
 
 struct vs_ctx {
     int device = 0;
-    int experiment_level = 0;  // VS_EXPERIMENT at vs_ctx_create: 0 none, 1 "1", 2 "timing"
+    bool experiment = false;   // VS_EXPERIMENT=1 at vs_ctx_create: the test hooks of VsTuning exist
     VsTuning tune;
     hipStream_t stream = nullptr;
     std::string err;
@@ -202,12 +191,11 @@ struct vs_reads {
 // inside the read instead of flush with its first base.  phi = (r + s) / 2 is the middle of that range (and s - 1, the
 // only choice, when r = s - 1).  Measured on the configs[2] stream: 21.9 instead of 27.4 postings per end, four probes
 // instead of five (profiles/r5/phase_gate_config2.json).  Ends shorter than K are never probed (PE_Inference.py:160-163).
-__host__ __device__ inline uint32_t vs_seed_phase(uint32_t len, uint32_t w, uint32_t s, bool phase0 = false) {
-    return (phase0 || len < w) ? 0u : ((len - w) % s + s) / 2u;
+__host__ __device__ inline uint32_t vs_seed_phase(uint32_t len, uint32_t w, uint32_t s) {
+    return len < w ? 0u : ((len - w) % s + s) / 2u;
 }
-__host__ __device__ inline uint32_t vs_seed_probes(uint32_t len, uint32_t w, uint32_t s, bool phase0 = false) {
+__host__ __device__ inline uint32_t vs_seed_probes(uint32_t len, uint32_t w, uint32_t s) {
     if (len < w) return 0u;
-    if (phase0) return (len - w) / s + 1u;
     return (len - w + 1u) / s;  // (0 for an end shorter than K = w + s - 1: it has no (k+1)-window, PE_Inference.py:23, and is never probed)
 }
 

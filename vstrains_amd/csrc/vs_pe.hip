@@ -16,20 +16,28 @@
 //   Every MEM holds a seed at a read offset divisible by s; the MEM is credited by the first
 //   such seed only (left extension < s), so nothing is counted twice.
 //
-// Work split per 256-thread workgroup and tile of `ept` read ends (ept/2 pairs, taken in locus
-// order, see k_pe_locus):
-//   P0  tile header + packed reads -> LDS (one wpe-word slot per end)
-//   P1  one thread per (end, probe): seed, canonical form, open-address table probe (one 16-B
-//       load per slot visited); posting count per probe -> LDS
-//   P2  workgroup inclusive scan of the posting counts
-//   P3  one thread per posting (binary search of the scan = CSR-style frontier expansion, so a
-//       repeat seed's many postings spread over lanes): left/right extension on 64-bit windows
-//       (XOR + clz/ctz), LDS atomics into an 8-slot per-end table keyed by node
-//   P4  acceptance test per occupied slot (integer form, see oracle/pe_oracle.py)
-//   P5  one thread per node_mat / short_mat increment (global atomics; tiles are locus-sorted
-//       and taken in contiguous runs, so the same cells are hit again while still in L2)
-// Ends that touch more than 8 nodes overflow the LDS table; their pairs go to a list that a
-// second, fully general kernel (dense per-workgroup node state in HBM) works through.
+// The pipeline of one block (vs_pe_count):
+//   k_pe_locus / k_locus_*  the pairs in locus order (first node a seed of the forward read hits)
+//   k_pe_tiles              the mapping kernel, one 256-thread workgroup per run of tiles of `ept` read ends (ept/2 pairs):
+//     P0  the next tile's headers and packed reads brought into the other LDS copy (one wpe-word slot per end), the
+//         tile-wide (end, node) table emptied, pairs classified
+//     P1  one thread per (end, probe): seed, canonical form, open-address table probe (one 16-B load per slot visited);
+//         posting count per probe -> LDS.  (The compile-time shapes of graphs with many postings per seed probe two
+//         candidate grids and expand the cheaper one: the adaptive step grid)
+//     P2  workgroup inclusive scan of the posting counts
+//     P3  one thread per posting (binary search of the scan = CSR-style frontier expansion, so a repeat seed's many
+//         postings spread over lanes): left/right extension on 64-bit windows (XOR + clz/ctz), LDS atomics into the
+//         tile's (end, node) hash table
+//     P4  acceptance test per occupied slot (integer form, see oracle/pe_oracle.py); the accepted nodes of every end
+//         PACKED into lists by a wavefront prefix sum; pairs with an overflowed end to the overflow list
+//     P5  the hand-off to the counter kernels: the tile's packed lists as one coalesced stretch (or, for the row
+//         owners, rows of a fixed stride per end)
+//   k_pe_accumulate         the counters pair-major, summed in an LDS cell table (graphs of at most 46 340 nodes), or
+//   k_list_owners .. k_rows_sum   the counters by ROW OWNERS (output-major: the lists transposed, a strip of matrix rows
+//                           per workgroup)
+//   k_pe_mid, k_pe_slow     the overflow: pairs with an end of more than LCAP accepted nodes, a full tile table or many
+//                           bytes outside ACGT, one wavefront per pair with LDS state, then what that cannot hold with
+//                           dense per-workgroup node state in HBM
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -55,24 +63,9 @@ __device__ __forceinline__ const uint32_t *vs_row_quad(const uint32_t *__restric
     return q < LC / 4u ? lists + row * LC + 4u * q : hi + row * 4u;
 }
 #define EMPTY_NODE 0xFFFFFFFFu
-#ifndef PPT
 #define PPT 2u               // postings per thread and expansion chunk
-#endif
-#ifndef TILES_WAVES
-#define TILES_WAVES 5        // k_pe_tiles is compiled for 5 waves per SIMD (<= 96 VGPRs); its LDS tile fits 5 times too
-#endif
-#ifndef TTPB
 #define TTPB 256             // threads per k_pe_tiles workgroup (a tile holds TTPB / 4 read ends)
-#endif
-#ifndef TILES_WAVES_LONG
-#define TILES_WAVES_LONG 5   // the long-window instantiation (k = 127) too: 21.9 ms at configs[3] against 23.3 at 4 waves (118 VGPRs)
-#endif
-#ifndef VS_ADAPT
-#define VS_ADAPT 1           // compile-time-shape instantiations pick, per end, the cheaper of two candidate offsets per grid position (step grid)
-#endif
-#ifndef PPT_LONG
 #define PPT_LONG 1u          // the same for the long-window instantiations (MODE 2, k = 127)
-#endif
 #define CHUNK (TTPB * PPT)   // (the owner array of a tile is sized for the larger of the two)
 
 struct PeParams {
@@ -80,7 +73,7 @@ struct PeParams {
     VsReadsDev rd;
     uint32_t *node_mat, *short_mat;
     unsigned long long *stats;
-    uint32_t ept, pmax, words_cap, pool, pool_bits, debug_stop;
+    uint32_t ept, pmax, words_cap, pool, pool_bits;
     uint64_t n_tiles;
     uint32_t *slow_list, *slow_count;
     uint32_t *dbg_lists, *dbg_counts;
@@ -90,17 +83,14 @@ struct PeParams {
     uint32_t wpe;          // LDS words reserved per read end
     uint32_t tiles_per_wg; // contiguous run of tiles per workgroup
     uint32_t magic_pmax, magic_wpe;  // vs_fastdiv constants
-    uint32_t count_postings;         // VS_DEBUG_POSTINGS: sum the postings expanded (diagnostics)
     uint32_t *out_lists;             // accepted node ids, tile order: packed regions of ept * LC words / rows of LCAP words (out_rows)
     uint32_t *out_counts;            // [n_tiles * ept] list lengths (0 for ends that add nothing), packed form: | quad offset << 8
     uint32_t out_rows;               // 1: fixed rows of LC words per end + out_lists_hi (the row owners follow), 0: packed
     uint32_t *out_lists_hi;          // [n_tiles * ept * 4] nodes 17 .. LCAP of every end (row layout)
     uint64_t n_pairs;
-    uint32_t no_xcd_map;             // VS_NO_XCD_MAP=1: workgroup b takes run b (experiments)
     uint32_t shortcut;               // overlapping-seed ownership shortcut for single postings (P3 stage A)
     uint8_t *tile_map;               // vs_pe_count_tracked: one byte per 64 x 64 tile of node_mat, then of short_mat; NULL = none
     uint32_t tile_T;                 // tiles per matrix side = ceil(N / 64)
-    uint32_t phase0;                 // VS_PHASE0: probe grid 0, s, 2s, ... (generic instantiations only; see vs_seed_phase)
     uint32_t mid_fast;               // k_pe_mid: clean ends are compared straight-line (vs_agree_fast; the block has the shape of MODE 1)
 };
 
@@ -119,50 +109,23 @@ __device__ __forceinline__ void vs_mark_tile_store(uint8_t *map, uint32_t T, uin
 
 // Inclusive scans over the 64 lanes of a wavefront by DPP moves -- row_shr 1, 2, 4, 8 inside the rows of 16 lanes, then the
 // last lane of a row broadcast to the rows after it (row_bcast 15 / 31) -- six VALU instructions where the __shfl_up form
-// takes six ds_bpermute round trips through the LDS crossbar (r6; -DVS_DPP_SCAN=0: the __shfl_up form).  A lane whose source
-// lies outside its row keeps the `old` operand: the identity of the operation.
-#ifndef VS_DPP_SCAN
-#define VS_DPP_SCAN 1
-#endif
+// takes six ds_bpermute round trips through the LDS crossbar (r6).  A lane whose source lies outside its row keeps the `old`
+// operand: the identity of the operation.
 // (r6) SIX workgroups per CU for the compile-time shapes of graphs whose ends touch few nodes (the non-adaptive instantiations):
 // a tile table of 768 slots instead of 1 024 (12 per end, placed by a multiply-high range reduction instead of a power-of-two
 // mask) and a list region of 960 words make 26.8 KB of LDS per workgroup, and with the thread index laundered at the top of the
 // tile loop as well (nothing P0 .. P2 derive from it is hoisted across P3) the kernel fits 80 vector registers without
 // scratch: six wavefronts per SIMD instead of five.  configs[2]: 4.70 -> 4.45 ms; either half alone gains nothing
-// (VS_LAUNDER_TOP alone: noise; the smaller table at five workgroups: +2 %).  -DVS_POOL12=0 -DVS_LAUNDER_TOP=0: round 5's shape.
-#ifndef VS_LAUNDER_TOP
-#define VS_LAUNDER_TOP 1
-#endif
-#ifndef VS_POOL12
-#define VS_POOL12 1
-#endif
+// (the laundering alone: noise; the smaller table at five workgroups: +2 %).
 #define VS_DPP_STEP(op, ctrl, rowmask) { const uint32_t t_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rowmask, 0xf, false); v = op; }
 __device__ __forceinline__ uint32_t vs_wave_scan_add(uint32_t v) {
-#if VS_DPP_SCAN
     VS_DPP_STEP(v + t_, 0x111, 0xf) VS_DPP_STEP(v + t_, 0x112, 0xf) VS_DPP_STEP(v + t_, 0x114, 0xf) VS_DPP_STEP(v + t_, 0x118, 0xf)
     VS_DPP_STEP(v + t_, 0x142, 0xa) VS_DPP_STEP(v + t_, 0x143, 0xc)
-#else
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t2 = __shfl_up(v, d, 64);
-        if (lane >= (uint32_t)d) v += t2;
-    }
-#endif
     return v;
 }
 __device__ __forceinline__ uint32_t vs_wave_scan_max(uint32_t v) {
-#if VS_DPP_SCAN
     VS_DPP_STEP(v > t_ ? v : t_, 0x111, 0xf) VS_DPP_STEP(v > t_ ? v : t_, 0x112, 0xf) VS_DPP_STEP(v > t_ ? v : t_, 0x114, 0xf)
     VS_DPP_STEP(v > t_ ? v : t_, 0x118, 0xf) VS_DPP_STEP(v > t_ ? v : t_, 0x142, 0xa) VS_DPP_STEP(v > t_ ? v : t_, 0x143, 0xc)
-#else
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t2 = __shfl_up(v, d, 64);
-        if (lane >= (uint32_t)d && t2 > v) v = t2;
-    }
-#endif
     return v;
 }
 
@@ -432,28 +395,19 @@ __device__ __forceinline__ bool vs_accept32(uint32_t v, uint32_t coord, uint32_t
 }
 
 // Probe the table for the seed at read offset j.  Returns posting count (0 = miss) and payload.
-// -DVS_PROBE_PAIR=1 requests two neighbouring slots together (at an eighth fill one lane in ten needs the second slot,
-// so nearly every wavefront does, as a second dependent round trip): measured equal within noise at configs[2..4]
-// (5.97 / 30.2 / 11.7 ms against 5.99 / 30.6 / 11.5), like tables of 1/16 .. 1/64 fill -- the probes are not where
-// k_pe_tiles waits.  Fuller tables lose: 1/4 fill +3 %, 1/2 fill +13 % (tools/r3_table.sh).
-#ifndef VS_PROBE_PAIR
-#define VS_PROBE_PAIR 0
-#endif
+// (Requesting two neighbouring slots together -- at an eighth fill one lane in ten needs the second slot, so nearly every
+// wavefront does, as a second dependent round trip -- was measured equal within noise at configs[2..4] (5.97 / 30.2 /
+// 11.7 ms against 5.99 / 30.6 / 11.5), like tables of 1/16 .. 1/64 fill: the probes are not where k_pe_tiles waits.
+// Fuller tables lose: 1/4 fill +3 %, 1/2 fill +13 %.)
 __device__ __forceinline__ uint32_t vs_probe(const VsIndexDev &idx, uint64_t key, uint32_t sr, uint32_t *pa, uint32_t *pb) {
     uint32_t mask = (1u << idx.table_bits) - 1u;
     uint32_t sl = vs_slot_of(key, idx.table_bits);
     const uint4 *tab = (const uint4 *)idx.table;
     for (;;) {
         const uint4 r0 = tab[sl];
-#if VS_PROBE_PAIR
-        const uint4 r1 = tab[(sl + 1u) & mask];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const uint4 raw = h ? r1 : r0;
-#else
-        {
+        {   // (the slot in a scope of its own: without it the compile-time-shape k_pe_tiles schedule about ten more vector
+            // instructions and one more global load)
             const uint4 raw = r0;
-#endif
             uint64_t k = (uint64_t)raw.x | ((uint64_t)raw.y << 32);
             if (k == VS_EMPTY_KEY) return 0u;
             if ((k & ~VS_MULTI_BIT) == key) {
@@ -467,7 +421,7 @@ __device__ __forceinline__ uint32_t vs_probe(const VsIndexDev &idx, uint64_t key
                 return 1u;
             }
         }
-        sl = (sl + (VS_PROBE_PAIR ? 2u : 1u)) & mask;
+        sl = (sl + 1u) & mask;
     }
 }
 
@@ -531,10 +485,8 @@ __host__ __device__ inline TileLayout tile_layout(uint32_t ept, uint32_t pmax, u
 // (7, 2) = 2 x 97..107.  Every LDS array then sits at a constant offset (folded into the LDS
 // instructions) instead of costing a scalar register and an add, the divisions by pmax / wpe and
 // k+1 / seed length / stride become constants.  The host picks one when the block has that shape.
-#ifndef STD_EPT
 #define STD_EPT (TTPB / 4u)
-#endif
-#define STD_POOL_BITS (STD_EPT > 32u ? 10u : STD_EPT > 16u ? 9u : 8u)  // pool_for(STD_EPT)
+#define STD_POOL_BITS 10u  // pool_for(STD_EPT)
 #define STD_K 56u   // k + 1
 #define STD_W 31u   // seed length and probe stride that follow from it (seed_geometry)
 #define STD_S 26u
@@ -545,19 +497,14 @@ __host__ __device__ inline TileLayout tile_layout(uint32_t ept, uint32_t pmax, u
 #define STD2_S 66u
 // MODE 0: generic loops (masked reads through the validity mask, any stride / read length);
 //      1: straight-line comparison, stride <= 32, reads <= w + 160; 2: the same for stride <= 128, reads <= w + 256.
-// tile and pair indices inside k_pe_tiles: a block holds fewer than 2^32 ends, so 32 bits do (-DVS_TILE32=0: 64, as before --
-// six more scalar registers spilled and two more vector registers in the k = 55 shape)
-#ifndef VS_TILE32
-#define VS_TILE32 1
-#endif
-#if VS_TILE32
-typedef uint32_t tidx_t;
-#else
-typedef uint64_t tidx_t;
-#endif
+// Tile and pair indices inside k_pe_tiles are 32-bit: a block holds fewer than 2^32 ends (64-bit indices spilled six more
+// scalar registers and took two more vector registers in the k = 55 shape).
+// Compiled for 5 waves per SIMD (<= 96 VGPRs; the LDS tile fits 5 times too), the long-window instantiations (k = 127) as
+// well (21.9 ms at configs[3] against 23.3 at 4 waves, 118 VGPRs); 6 for the non-adaptive compile-time shapes (the
+// 768-slot table above).
 template <int MODE, uint32_t SW, uint32_t SP, bool AD = false>
 __global__ void __launch_bounds__(TTPB)
-__attribute__((amdgpu_waves_per_eu((VS_POOL12 && SW != 0u && !AD) ? 6 : MODE == 2 ? TILES_WAVES_LONG : TILES_WAVES, (VS_POOL12 && SW != 0u && !AD) ? 6 : MODE == 2 ? TILES_WAVES_LONG : TILES_WAVES)))
+__attribute__((amdgpu_waves_per_eu((SW != 0u && !AD) ? 6 : 5, (SW != 0u && !AD) ? 6 : 5)))
 k_pe_tiles(PeParams P) {
     constexpr bool FAST = MODE != 0;
     constexpr uint32_t AB = MODE == 2 ? 9u : 8u;  // bits of the read offset packed under the node length (credit / P4)
@@ -570,14 +517,12 @@ k_pe_tiles(PeParams P) {
     // read's start.  P1 probes both candidates of every position (8 slot loads per 150-base end instead of 4), picks the t
     // with the fewest postings, and only that grid is expanded: 57 -> 43 postings per end at configs[4], 21.9 -> 17.1
     // at configs[2] (tools/phase_gate.py).  Any grid of the family gives the same lists; the choice only changes the work.
-    constexpr bool ADAPT = STD && AD && VS_ADAPT != 0;
+    constexpr bool ADAPT = STD && AD;
     static_assert(!ADAPT || (MODE == 2 ? STD2_EPT : STD_EPT) * SP <= TTPB, "the adaptive probe phase takes one probe position per thread");
     constexpr uint32_t STD_WPE = SW, STD_PMAX = SP;
     const uint32_t tid = threadIdx.x;
-    // (the compile-time-shape instantiation is also the one without diagnostics: the host only picks
-    // it for plain counting runs)
-    const uint32_t debug_stop = STD ? 0u : P.debug_stop;
-    const bool count_postings = !STD && P.count_postings, want_dbg = !STD && P.dbg_counts != nullptr;
+    // (the compile-time-shape instantiations only count: vs_pe_map_ends takes the generic ones)
+    const bool want_dbg = !STD && P.dbg_counts != nullptr;
     const bool accumulate = STD || P.accumulate;
     // (r3) MODE 2 has one compile-time shape too: k = 127 with 2 x 241..256 bases -- 63-base seeds, stride 66, 16 words and
     // two probes per end, 60 ends per tile (what the host's LDS budget gives that shape)
@@ -590,7 +535,7 @@ k_pe_tiles(PeParams P) {
     const uint32_t wv = VS_SEED_VERIFIED(w);  // seed bases the comparison skips (0: seeds with mixed keys, vs_seed_key)
     // (the 768-slot table is for graphs whose ends touch few nodes: the adaptive instantiations -- many postings per seed, long
     // lists -- keep 1 024 slots and five wavefronts per SIMD)
-    constexpr bool P12 = VS_POOL12 != 0 && STD && !AD;
+    constexpr bool P12 = STD && !AD;
     constexpr uint32_t C_POOL = P12 ? 768u : (1u << C_POOL_BITS), C_TRIM = P12 ? (MODE == 2 ? 192u : 64u) : 0u;  // (k = 127: 16 words per end of read text leave less)
     const uint32_t pool = STD ? C_POOL : P.pool, pool_shift = 32u - (STD ? C_POOL_BITS : P.pool_bits);
     const uint32_t words_cap = STD ? C_EPT * STD_WPE : P.words_cap;
@@ -611,7 +556,6 @@ k_pe_tiles(PeParams P) {
     uint32_t *s_hminj = vs_lds + T.hminj;
     uint32_t *s_ns = vs_lds + T.ns;        // accepted nodes per end
     uint32_t *s_state = vs_lds + T.state;  // bit0: end belongs to a used pair, bit1: overflow; bits 8..: first probe offset (vs_seed_phase)
-    const bool phase0 = !STD && P.phase0;
     uint32_t *s_list = vs_lds + T.list;    // accepted node ids, LC per end
     uint32_t *s_misc = vs_lds + T.misc;
     uint32_t *s_owner = vs_lds + T.owner;
@@ -626,22 +570,22 @@ k_pe_tiles(PeParams P) {
     // works through the x-th eighth of the locus order: what a locus touches (table slots, postings,
     // node text) is then cached in one L2 instead of eight.
     uint32_t wg = blockIdx.x;
-    if ((gridDim.x & 7u) == 0u && !P.no_xcd_map) wg = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    if ((gridDim.x & 7u) == 0u) wg = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     // (pairs and tiles of a block fit 32 bits: vs_reads holds fewer than 2^32 ends)
-    const tidx_t n_pairs32 = (tidx_t)P.n_pairs, n_tiles32 = (tidx_t)P.n_tiles;
-    const tidx_t tile_lo = (tidx_t)wg * P.tiles_per_wg;
-    const tidx_t tile_hi = tile_lo + P.tiles_per_wg < n_tiles32 ? tile_lo + P.tiles_per_wg : n_tiles32;
+    const uint32_t n_pairs32 = (uint32_t)P.n_pairs, n_tiles32 = (uint32_t)P.n_tiles;
+    const uint32_t tile_lo = wg * P.tiles_per_wg;
+    const uint32_t tile_hi = tile_lo + P.tiles_per_wg < n_tiles32 ? tile_lo + P.tiles_per_wg : n_tiles32;
     // The headers of a tile (pair order -> end index -> word offset, length) are two dependent
     // global loads; they run ahead in registers, one link per tile (pair order two tiles ahead, word
     // offset and length one tile ahead; one end per thread, ept <= TTPB), so that neither waits for
     // the other and both are covered by the previous tiles' work.
     uint32_t pf_gend = 0, pf_gwoff = 0, pf_meta = 0, pf_inv = 0xFFFFFFFFu, pf_pair = 0xFFFFFFFFu;
     uint32_t cur_inv = 0xFFFFFFFFu;  // this thread's end of the CURRENT tile (goes to LDS at the top of the tile)
-    auto prefetch_pair = [&](tidx_t t) {  // pair (in input order) of this thread's end in tile t
+    auto prefetch_pair = [&](uint32_t t) {  // pair (in input order) of this thread's end in tile t
         pf_pair = 0xFFFFFFFFu;
         if (t < tile_hi && tid < ept) {
-            const tidx_t p = t * ppt + (tid >> 1);
-            if (p < n_pairs32) pf_pair = P.perm ? P.perm[p] : (uint32_t)p;
+            const uint32_t p = t * ppt + (tid >> 1);
+            if (p < n_pairs32) pf_pair = P.perm ? P.perm[p] : p;
         }
     };
     auto prefetch_headers = [&]() {  // of the tile whose pair order sits in pf_pair
@@ -680,8 +624,8 @@ k_pe_tiles(PeParams P) {
     prefetch_pair(tile_lo);
     prefetch_headers();
     {
-        const tidx_t np0 = n_pairs32 - tile_lo * ppt;
-        const uint32_t ne0 = 2u * (uint32_t)(np0 < ppt ? np0 : ppt);
+        const uint32_t np0 = n_pairs32 - tile_lo * ppt;
+        const uint32_t ne0 = 2u * (np0 < ppt ? np0 : ppt);
         if (tid < ne0) {
             s_gend[tid] = pf_gend;
             s_gwoff[tid] = pf_gwoff;
@@ -699,17 +643,13 @@ k_pe_tiles(PeParams P) {
     prefetch_pair(tile_lo + 1u);
     prefetch_headers();
     prefetch_pair(tile_lo + 2u);
-    for (tidx_t tile = tile_lo; tile < tile_hi; tile++) {
-#if VS_LAUNDER_TOP
-        uint32_t ltop = tid;  // (nothing P0 .. P2 derive from the thread index is hoisted out of the tile loop: see VS_POOL12)
+    for (uint32_t tile = tile_lo; tile < tile_hi; tile++) {
+        uint32_t ltop = tid;  // (nothing P0 .. P2 derive from the thread index is hoisted out of the tile loop: see the 768-slot table)
         asm volatile("" : "+v"(ltop));
-#else
-        const uint32_t ltop = tid;
-#endif
-        const tidx_t p0 = tile * ppt;
-        const uint32_t npair = (uint32_t)((n_pairs32 - p0) < ppt ? (n_pairs32 - p0) : ppt);
+        const uint32_t p0 = tile * ppt;
+        const uint32_t npair = (n_pairs32 - p0) < ppt ? (n_pairs32 - p0) : ppt;
         const uint32_t ne = 2u * npair;
-        const uint32_t cur = (uint32_t)(tile - tile_lo) & 1u, nxt = cur ^ 1u;
+        const uint32_t cur = (tile - tile_lo) & 1u, nxt = cur ^ 1u;
         s_gwoff = vs_lds + T.woff + cur * hw;
         s_gend = vs_lds + T.gend + cur * ept;
         s_meta = vs_lds + T.meta + cur * ept;
@@ -718,8 +658,8 @@ k_pe_tiles(PeParams P) {
         uint32_t *n_meta = vs_lds + T.meta + nxt * ept, *n_words = vs_lds + T.words + nxt * wcap;
         uint32_t ne1 = 0;  // ends of the next tile of this run
         if (tile + 1u < tile_hi) {
-            const tidx_t np1 = n_pairs32 - (tile + 1u) * ppt;
-            ne1 = 2u * (uint32_t)(np1 < ppt ? np1 : ppt);
+            const uint32_t np1 = n_pairs32 - (tile + 1u) * ppt;
+            ne1 = 2u * (np1 < ppt ? np1 : ppt);
         }
         __syncthreads();  // previous tile fully consumed; this tile's words have landed (see before P4)
         // ---- P0: the next tile's headers go to the other copy, the (end, node) table is emptied
@@ -767,7 +707,7 @@ k_pe_tiles(PeParams P) {
             // length), phi in bits 8..31.  ADAPT: base s - 1 in bits 8..15, the step point t in bits 16..19 (set by P1), the
             // shift D in bits 20..27 (0: the length leaves one phase only)
             auto grid_bits = [&](uint32_t len) {
-                if (!ADAPT || !(st & 1u)) return vs_seed_phase(len, w, s, phase0) << 8;
+                if (!ADAPT || !(st & 1u)) return vs_seed_phase(len, w, s) << 8;
                 const uint32_t r = (len - w) % s;
                 return ((s - 1u) << 8) | ((r + 2u <= s ? s - 2u - r : 0u) << 20);
             };
@@ -776,7 +716,6 @@ k_pe_tiles(PeParams P) {
             s_ns[2 * ltop] = s_ns[2 * ltop + 1] = 0;
         }
         __syncthreads();
-        if (debug_stop == 1u) continue;
         // ---- P1: probes
         if (ADAPT) {
             // one grid position per thread; both candidate offsets probed with their slot loads in flight together
@@ -860,7 +799,6 @@ k_pe_tiles(PeParams P) {
             s_pb[it] = pb;
         }
         __syncthreads();
-        if (debug_stop == 2u) continue;
         // ---- P2: inclusive scan of the postings per probe, s_pcnt[0..NI)
         {
             const uint32_t chunk = (NI + TTPB - 1u) / TTPB;
@@ -881,14 +819,12 @@ k_pe_tiles(PeParams P) {
                 }
         }
         __syncthreads();
-        if (debug_stop == 3u) continue;
         // ---- P3: one thread per posting.  Expansion of the per-probe posting counts (CSR-style
         // frontier expansion) in chunks of KCHUNK postings: every probe marks the first position it
         // owns in the chunk, a workgroup-wide running maximum fills the gaps, and each thread ends
         // up with the owners of its KPPT consecutive postings in registers.
         {
         const uint32_t total = s_pcnt[NI - 1u];
-        if (count_postings && tid == 0) atomicAdd((unsigned long long *)(P.slow_count + 2), (unsigned long long)total);
         for (uint32_t c0 = 0; c0 < total; c0 += KCHUNK) {
             for (uint32_t i = tid; i < KCHUNK; i += TTPB) s_owner[i] = 0;
             __syncthreads();
@@ -1017,7 +953,6 @@ k_pe_tiles(PeParams P) {
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wavefront's LDS-direct loads of the next tile's words are in
         __syncthreads();
-        if (debug_stop == 4u) continue;
         // ---- P4: acceptance test per table slot; an accepted node takes the next position of its end's list
         // (r6) The lists are PACKED: first every slot is judged and the ends' list lengths counted (the slot keeps its
         // position, its count is not needed any more), then ONE wavefront turns the lengths -- rounded up to whole quads -- into
@@ -1101,7 +1036,6 @@ k_pe_tiles(PeParams P) {
             }
         }
         __syncthreads();
-        if (debug_stop == 5u) continue;
         // ---- P5: hand the accepted lists to the counter kernels, tile order; length 0 for ends of dropped pairs and of
         // pairs the slow path takes
         if (accumulate) {
@@ -1153,12 +1087,8 @@ k_pe_tiles(PeParams P) {
 //     table is written out.  One wavefront expands 64 pairs at a time, one lane per run of at most four increments.
 //   * the row owners below (larger graphs): output-major.  There a round of locus-ordered pairs brings more distinct
 //     cells than the table holds, and the same cell returns from loci hundreds of rounds apart.
-#ifndef ACC_TPB
 #define ACC_TPB 1024
-#endif
-#ifndef ACC_BITS
 #define ACC_BITS 14
-#endif
 #define ACC_SLOTS (1u << ACC_BITS)
 #define ACC_LDS_BYTES ((2u * ACC_SLOTS + (ACC_TPB / 64) * 66u + (LCAP + 1u) + (LCAP + 1u) * ACC_GMAX + 4u) * 4u)
 // Work units: a list row is cut into runs of at most ACC_RUN partners, one lane per run, so that
@@ -1166,10 +1096,9 @@ k_pe_tiles(PeParams P) {
 //   node_mat : left node a against right positions [4c, 4c+4)           -> nl * ceil(nr/4) runs
 //   short_mat: list position a against positions [a+4c, a+4c+4) (b >= a) -> g(n) runs per list,
 //              g(n) = sum_{m=1..n} ceil(m/4)
-#ifndef ACC_RUN
-#define ACC_RUN 4u   // 4 or 8 (8: two 16-byte partner loads per run; measured r5, see profiles/EXPERIMENTS.md)
-#endif
-#define ACC_GMAX 60u  // g(LCAP = 20) for runs of 4 (runs of 8 need 36)
+#define ACC_RUN 4u   // (runs of 8, two 16-byte partner loads per run, were measured in r5: profiles/EXPERIMENTS.md)
+#define ACC_GMAX 60u  // g(LCAP = 20)
+#define ACC_PPW 64u   // pairs per wavefront and round: one per lane
 // The cell table: 16 k slots, 32-bit keys (k_pe_accumulate: mat * N*N + x * N + y, while 2*N*N fits 32 bits, N <= 46340;
 // the row owners: cell index relative to the strip's first row).  The 16 cells of one 64-byte stretch of a matrix row
 // sit in 16 NEIGHBOURING slots (the hash picks a group of 16 slots from the key >> 4, the low four bits pick the slot
@@ -1208,8 +1137,7 @@ __device__ __forceinline__ bool vs_cell_claim(uint32_t *s_key, uint32_t *s_cnt, 
 __global__ void __launch_bounds__(ACC_TPB)
 k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ counts, uint64_t n_slots_pairs,
                 uint32_t pairs_per_wg, uint32_t N, uint32_t use_table, uint32_t fill_limit,
-                uint32_t *__restrict__ node_mat, uint32_t *__restrict__ short_mat, uint32_t *__restrict__ queue,
-                uint32_t *__restrict__ dbg, uint32_t ppw, uint32_t ept) {  // VS_DEBUG_ACC: [0] increments past the table, [1] write-outs, [2] cells written, [3] rounds
+                uint32_t *__restrict__ node_mat, uint32_t *__restrict__ short_mat, uint32_t *__restrict__ queue, uint32_t ept) {
     uint32_t *s_key = vs_lds;                      // [ACC_SLOTS]
     uint32_t *s_cnt = vs_lds + ACC_SLOTS;          // [ACC_SLOTS]
     uint32_t(*s_pref)[66] = (uint32_t(*)[66])(vs_lds + 2u * ACC_SLOTS);  // [ACC_TPB / 64][66]
@@ -1231,8 +1159,8 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
     }
     if (tid == 0) { s_used = 0; s_lost = 0; }
     __syncthreads();
-    // chunks of pairs_per_wg pairs: chunk blockIdx.x, or (queue) whichever chunk is next when this
-    // workgroup is free -- the table then lives across chunks and is written out on fill only
+    // chunks of pairs_per_wg pairs: whichever chunk is next when this workgroup is free -- the table lives across chunks
+    // and is written out on fill only
     uint32_t &s_chunk = s_ua[(LCAP + 1u) * ACC_GMAX + 2u];
     const uint32_t ppt = ept >> 1, region_q = (ept * LC) >> 2;  // pairs per tile of the mapping kernel; quads of a tile's region
     // every cell of the table to its counter (one global atomic per cell), the table emptied
@@ -1240,8 +1168,7 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
         for (uint32_t i = tid; i < ACC_SLOTS; i += ACC_TPB) {
             const uint32_t key = s_key[i];
             if (key != Acc32::EMPTY) {
-                if (use_table != 3u)  // (3: timing experiment without the write-outs)
-                    atomicAdd(key >= NN ? short_mat + (key - NN) : node_mat + key, s_cnt[i]);
+                atomicAdd(key >= NN ? short_mat + (key - NN) : node_mat + key, s_cnt[i]);
                 s_key[i] = Acc32::EMPTY;
                 s_cnt[i] = 0;
             }
@@ -1250,19 +1177,16 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
         __syncthreads();
     };
     for (;;) {
-    uint64_t chunk = blockIdx.x;
-    if (queue) {
-        __syncthreads();
-        if (tid == 0) s_chunk = atomicAdd(queue, 1u);
-        __syncthreads();
-        chunk = s_chunk;
-    }
+    __syncthreads();
+    if (tid == 0) s_chunk = atomicAdd(queue, 1u);
+    __syncthreads();
+    const uint64_t chunk = s_chunk;
     const uint64_t lo = chunk * pairs_per_wg;
     if (lo >= n_slots_pairs) break;
     const uint64_t hi = lo + pairs_per_wg < n_slots_pairs ? lo + pairs_per_wg : n_slots_pairs;
-    // a round = ppw pairs per wavefront (64: one per lane; VS_ACC_ROUND for fewer)
-    for (uint64_t base = lo; base < hi; base += (ACC_TPB / 64u) * ppw) {
-        const uint64_t wbase = base + wv * ppw;             // wave-uniform
+    // a round = ACC_PPW pairs per wavefront
+    for (uint64_t base = lo; base < hi; base += (ACC_TPB / 64u) * ACC_PPW) {
+        const uint64_t wbase = base + wv * ACC_PPW;         // wave-uniform
         const uint32_t *wcounts = counts + 2u * wbase;
         // the lists are packed per tile of the mapping kernel (k_pe_tiles P4 / P5): where a pair's two lists start, in quads
         // from the region of the wavefront's first tile -- at most 64 pairs further on, so 11 bits each, next to the lengths
@@ -1270,7 +1194,7 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
         const uint32_t rem0 = (uint32_t)(wbase - tile0 * ppt);
         const uint32_t *wlists = lists + tile0 * ept * LC;
         uint32_t nl = 0, nr = 0, packed = 0;
-        if (lane < ppw && wbase + lane < hi) {
+        if (wbase + lane < hi) {
             const uint2 c = *(const uint2 *)(wcounts + 2u * lane);
             nl = c.x & 0xFFu; nr = c.y & 0xFFu;
             const uint32_t tq = (rem0 + lane) / ppt * region_q;
@@ -1292,9 +1216,6 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
         struct Run {
             uint32_t x, mat, bi, be;
             VsQuad yq;
-#if ACC_RUN == 8u
-            VsQuad yq2;
-#endif
             bool ok;
         };
         auto fetch = [&](uint32_t t0) {
@@ -1330,9 +1251,6 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
             // up to ACC_RUN partners, loaded together (reading a few words past `be` -- the list's padding, the next
             // list -- stays inside the lists buffer, which carries padding at its end, and is ignored)
             R.yq = *(const VsQuad *)(wlists + off + R.bi);  // one 16-byte load
-#if ACC_RUN == 8u
-            R.yq2 = *(const VsQuad *)(wlists + off + R.bi + 4u);
-#endif
             return R;
         };
         // (r6: the list loads of two and three windows ahead instead of one were measured -- 2.23 / 2.25 / 2.31 ms at configs[2]: the
@@ -1345,14 +1263,8 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
             if (t0 + 64u < U) nxt = fetch(t0 + 64u);
             if (!c.ok) continue;
             const uint32_t x = c.x, mat = c.mat, bi = c.bi, be = c.be;
-#if ACC_RUN == 8u
-            const uint32_t ys[ACC_RUN] = {c.yq.x, c.yq.y, c.yq.z, c.yq.w, c.yq2.x, c.yq2.y, c.yq2.z, c.yq2.w};
-#else
             const uint32_t ys[ACC_RUN] = {c.yq.x, c.yq.y, c.yq.z, c.yq.w};
-#endif
-            if (use_table == 2u) {
-                if ((ys[0] ^ ys[1] ^ ys[2] ^ ys[3] ^ x) == 0xDEADBEEFu) atomicAdd(&s_lost, 1u);  // (timing experiment: decode only)
-            } else if (use_table) {
+            if (use_table) {
                 // the four cells' slots are read together (independent LDS loads), then counted; a
                 // slot that does not hold the cell yet goes the slow way (claim / probe / global)
                 uint32_t key[ACC_RUN], seen[ACC_RUN], at[ACC_RUN];
@@ -1387,20 +1299,14 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
         }
         __syncthreads();
         const bool spill = s_used > fill_limit || s_lost > 4096u;
-        if (dbg && tid == 0) {
-            atomicAdd(dbg + 3, 1u);
-            if (spill) { atomicAdd(dbg + 0, s_lost); atomicAdd(dbg + 1, 1u); atomicAdd(dbg + 2, s_used); }
-        }
         __syncthreads();
         // (everything goes, also the cells of the locus still being worked on: keeping those across
         // write-outs was measured -- 3.1 -> 3.9 ms -- the table is only fast while nearly empty, when a
         // cell sits in the first slot its key hashes to)
         if (spill) write_out();
     }
-    if (!queue) break;
     }
     __syncthreads();
-    if (dbg && tid == 0) atomicAdd(dbg + 0, s_lost);
     write_out();
 }
 
@@ -1808,12 +1714,8 @@ k_rows_fill(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ lis
 
 // The strips' cell table is smaller than the pair-major kernel's (8 k slots, 64 KB) and the strips narrower for it: two
 // workgroups share a CU, and one waits in its LDS queue while the other computes (configs[4]: 14.1 -> 11.2 ms)
-#ifndef RS_BITS
 #define RS_BITS 13
-#endif
-#ifndef RS_TPB
 #define RS_TPB 1024
-#endif
 #define RS_SLOTS (1u << RS_BITS)
 typedef CellTable<RS_BITS> RsTable;
 #define RSUM_LDS_BYTES ((2u * RS_SLOTS + 64u + 8u) * 4u)
@@ -1822,8 +1724,7 @@ template <int MODE>
 __global__ void __launch_bounds__(RS_TPB)
 k_rows_sum(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ lists_hi, const uint32_t *__restrict__ counts, const uint32_t *__restrict__ mult, uint32_t N,
            const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ entries, uint32_t R, uint32_t n_strips, uint32_t fill_limit,
-           uint32_t *__restrict__ mat, uint32_t off, uint8_t *__restrict__ tile_map, uint32_t T, uint32_t *__restrict__ queue,
-           uint32_t *__restrict__ dbg) {
+           uint32_t *__restrict__ mat, uint32_t off, uint8_t *__restrict__ tile_map, uint32_t T, uint32_t *__restrict__ queue) {
     uint32_t *s_key = vs_lds, *s_cnt = vs_lds + RS_SLOTS, *s_rowend = vs_lds + 2u * RS_SLOTS;  // [RSUM_MAX_ROWS]
     uint32_t &s_used = s_rowend[64], &s_lost = s_rowend[65], &s_strip = s_rowend[66];
     const uint32_t tid = threadIdx.x, q = tid & 3u;
@@ -1857,7 +1758,6 @@ k_rows_sum(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ list
                     s_cnt[i] = 0u;
                 }
             }
-            if (dbg && tid == 0) { atomicAdd(dbg + 0, s_lost); atomicAdd(dbg + 1, 1u); atomicAdd(dbg + 2, s_used); }
             __syncthreads();
             if (tid == 0) { s_used = 0u; s_lost = 0u; }
             __syncthreads();
@@ -1985,12 +1885,8 @@ __device__ __forceinline__ uint32_t vs_locus_key_end(const VsIndexDev &idx, cons
 //   k_locus_scatter : workgroup g loads its column as LDS cursors and places its pairs
 #define LOCUS_LDS_KEYS 36864u  // 144 KB of LDS counters
 #define LOCUS_LDS_MAX_PASSES 4u  // ... per pass; graphs of up to 147 k nodes are sorted through LDS histograms
-#ifndef LOCUS_TPB
 #define LOCUS_TPB 1024     // threads per workgroup of the two LDS-histogram sort kernels
-#endif
-#ifndef LOCUS_WGS
-#define LOCUS_WGS 256u       // one per CU (measured: 1024 x 256 threads 0.70 ms, 256 x 1024 threads 0.57 ms)
-#endif
+#define LOCUS_WGS 256u     // one per CU (measured: 1024 x 256 threads 0.70 ms, 256 x 1024 threads 0.57 ms)
 // (key_lo, nk): the keys this pass counts / places -- a graph with more keys than one LDS histogram holds (54 k nodes at
 // configs[4]) takes two or three passes over the stored keys instead of the global-atomic sort; `compute`: the first
 // pass derives the keys (the expensive part: a read's seeds are probed) and stores them, the others read them back.
@@ -2083,7 +1979,7 @@ k_pe_mid(PeParams P, const uint32_t *__restrict__ in_list, const uint32_t *__res
             const uint32_t rlen = meta & VS_LEN_MASK;
             const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
             const uint32_t *mk = ((meta >> 24) & VS_FLAG_INVALID) ? P.rd.mask : nullptr;
-            const uint32_t nprobe = vs_seed_probes(rlen, w, s, P.phase0), phase = vs_seed_phase(rlen, w, s, P.phase0);
+            const uint32_t nprobe = vs_seed_probes(rlen, w, s), phase = vs_seed_phase(rlen, w, s);
             for (uint32_t i = lane; i < MID_SLOTS; i += 64u) { s_key[i] = EMPTY_NODE; s_cnt[i] = 0u; s_minp[i] = 0xFFFFFFFFu; s_minj[i] = 0xFFFFFFFFu; }
             if (nprobe > 64u) { if (lane == 0u) s_flag[0] = 1u; }
             // probes: one per lane
@@ -2262,7 +2158,7 @@ k_pe_slow(PeParams P, uint32_t *dense, uint32_t n_slow_cap, const uint32_t *__re
             const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
             const uint32_t *mk = ((meta >> 24) & VS_FLAG_INVALID) ? P.rd.mask : nullptr;
             uint32_t *surv = side ? surv1 : surv0;
-            const uint32_t nprobe = vs_seed_probes(rlen, w, s, P.phase0), phase = vs_seed_phase(rlen, w, s, P.phase0);
+            const uint32_t nprobe = vs_seed_probes(rlen, w, s), phase = vs_seed_phase(rlen, w, s);
             if (tid == 0) s_nt = 0;
             __syncthreads();
             for (uint32_t p0 = 0; p0 < nprobe; p0 += TPB) {
@@ -2453,8 +2349,7 @@ static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_
     if (fill > RS_SLOTS - 1024u) fill = RS_SLOTS - 1024u;
     // rows per strip: a strip's distinct cells should fill the table less than half.  configs[4]: 4 rows of node_mat hold
     // 1.7 k cells at the median and 6 k at most, 32 rows of short_mat 2.1 k and 6.6 k.  VS_ROWS_PER_STRIP overrides both.
-    const uint32_t R[2] = {tn.rows_per_strip ? tn.rows_per_strip : 2u, tn.rows_per_strip1 ? tn.rows_per_strip1 : tn.rows_per_strip ? tn.rows_per_strip : 2u};
-    uint32_t *dbg = tn.debug_acc ? (uint32_t *)ctx->d_slow_count + 10 : nullptr;
+    const uint32_t R = tn.rows_per_strip ? tn.rows_per_strip : 2u;
     uint32_t *queue = (uint32_t *)ctx->d_slow_count + 9, *n_owners = (uint32_t *)ctx->d_slow_count + 15;
     unsigned long long *ltab = use_ltab ? (unsigned long long *)ctx->d_ltab : nullptr;
     uint32_t *lmult = use_ltab ? (uint32_t *)((unsigned long long *)ctx->d_ltab + ltab_slots) : nullptr;
@@ -2496,18 +2391,18 @@ static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_
         for (int mode = 0; mode < 2; mode++) {
             const uint32_t *row_ptr = rows + 3u * mode * cap + 2u * cap;
             const uint32_t *entries = (const uint32_t *)ctx->d_row_entries + (mode ? np * LCAP : 0u);
-            const uint32_t n_strips = (N + R[mode] - 1u) / R[mode];
-            uint32_t grid = (uint32_t)ctx->n_cu * (RSUM_LDS_BYTES <= 40000u ? 4u : 2u) * (1024u / RS_TPB);
+            const uint32_t n_strips = (N + R - 1u) / R;
+            uint32_t grid = (uint32_t)ctx->n_cu * 2u;  // (two workgroups per CU: 64 KB of LDS each)
             if (grid > n_strips) grid = n_strips;
             uint32_t *m = mode ? d_short_mat : d_node_mat;
             const uint32_t off = (uint32_t)(((uintptr_t)m >> 2) & 15u);
             VS_HIP(ctx, hipMemsetAsync(queue, 0, sizeof(uint32_t), st));
             if (mode)
-                hipLaunchKernelGGL(k_rows_sum<1>, dim3(grid), dim3(RS_TPB), RSUM_LDS_BYTES, st, sl, sh, sc, (const uint32_t *)mult, N, row_ptr, entries, R[1], n_strips, fill, m,
-                                   off, d_tile_map, T, queue, dbg);
+                hipLaunchKernelGGL(k_rows_sum<1>, dim3(grid), dim3(RS_TPB), RSUM_LDS_BYTES, st, sl, sh, sc, (const uint32_t *)mult, N, row_ptr, entries, R, n_strips, fill, m,
+                                   off, d_tile_map, T, queue);
             else
-                hipLaunchKernelGGL(k_rows_sum<0>, dim3(grid), dim3(RS_TPB), RSUM_LDS_BYTES, st, sl, sh, sc, (const uint32_t *)mult, N, row_ptr, entries, R[0], n_strips, fill, m,
-                                   off, d_tile_map, T, queue, dbg);
+                hipLaunchKernelGGL(k_rows_sum<0>, dim3(grid), dim3(RS_TPB), RSUM_LDS_BYTES, st, sl, sh, sc, (const uint32_t *)mult, N, row_ptr, entries, R, n_strips, fill, m,
+                                   off, d_tile_map, T, queue);
         }
     }
     VS_HIP(ctx, hipGetLastError());
@@ -2527,11 +2422,11 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     const uint32_t maxlen = (uint32_t)reads->max_len;
     const uint32_t wpe = maxlen ? (maxlen + 15u) / 16u : 1u;
     if (idx.n_nodes > 0x01FFFFFEu) return vs_fail(ctx, VS_E_RANGE, "more than 2^25-2 nodes");
-    // experiment switches: fixed defaults unless the process runs with VS_EXPERIMENT (see VsTuning)
-    if (ctx->experiment_level) vs_tuning_load(ctx->tune, ctx->experiment_level);
+    // test hooks: fixed defaults unless the process runs with VS_EXPERIMENT=1 (see VsTuning)
+    if (ctx->experiment) vs_tuning_load(ctx->tune, true);
     const VsTuning &tn = ctx->tune;
     // probes of the longest end (vs_seed_probes grows with the length): the probe slots a tile reserves per end
-    uint32_t pmax = vs_seed_probes(maxlen, idx.w, idx.s, tn.phase0);
+    uint32_t pmax = vs_seed_probes(maxlen, idx.w, idx.s);
     if (!pmax) pmax = 1u;
     uint32_t ept = tn.ept ? tn.ept : STD_EPT;
     if (ept < 2 || ept > TTPB / 2u) ept = STD_EPT;
@@ -2539,7 +2434,7 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     // (LDS is handed out in 1280-byte pieces: 32 000 B per workgroup lets five share a CU, 40 000 four.  A tile of
     // at least 32 ends that fits one of these is taken over a larger one that wastes the rest.)
     if (!tn.ept) {
-        for (size_t fit : {(size_t)(TTPB >= 256 ? 32000 : TTPB == 128 ? 15360 : 7680), (size_t)(TTPB >= 256 ? 40000 : TTPB == 128 ? 17920 : 8960)}) {
+        for (size_t fit : {(size_t)32000, (size_t)40000}) {
             uint32_t e2 = ept;
             while (e2 > STD_EPT / 2u && lds_bytes(e2, pmax, e2 * wpe) > fit) e2 -= 2;
             if (lds_bytes(e2, pmax, e2 * wpe) <= fit) { ept = e2; break; }
@@ -2556,7 +2451,7 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
         VS_HIP(ctx, hipMalloc(&ctx->d_slow_list, sizeof(uint32_t) * n_pairs));
         ctx->slow_cap = n_pairs;
     }
-    if (!ctx->d_slow_count) VS_HIP(ctx, hipMalloc(&ctx->d_slow_count, 64));  // [0] pairs for k_pe_mid, [1] queue, [2..3] postings, [4..7] acc, [8] pairs for k_pe_slow, [9] strip queue, [10..14] k_rows_sum debug, [15] owning ends
+    if (!ctx->d_slow_count) VS_HIP(ctx, hipMalloc(&ctx->d_slow_count, 64));  // [0] pairs for k_pe_mid, [1] k_pe_accumulate's chunk queue, [8] pairs for k_pe_slow, [9] k_rows_sum's strip queue, [15] owning ends (the other words unused)
     if (ctx->slow2_cap < n_pairs) {
         if (ctx->d_slow_list2) VS_HIP(ctx, hipFree(ctx->d_slow_list2));
         ctx->d_slow_list2 = nullptr;
@@ -2610,11 +2505,10 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     // 32-bit keys (packed lists), by row owners above (rows of LCAP words); VS_ACC_ROWS=0 / 1 overrides (0 beyond 46 340
     // nodes: no table, every increment a global atomic).  VS_NO_AGG=1 turns the summing in LDS off
     uint32_t use_table = tn.no_agg ? 0u : 1u;
-    if (tn.acc_ablate >= 0) use_table = (uint32_t)tn.acc_ablate;  // 2: decode only, 3: no write-outs (VS_EXPERIMENT=timing only)
     const bool fits32 = 2ull * idx.n_nodes * idx.n_nodes < 0xFFFFFFFFull;
     bool use_rows = tn.acc_rows >= 0 ? tn.acc_rows != 0 : !fits32;
-    if (idx.n_nodes == 0 || use_table != 1u) use_rows = false;
-    if (!use_rows && !fits32 && use_table == 1u) use_table = 0u;
+    if (idx.n_nodes == 0 || !use_table) use_rows = false;
+    if (!use_rows && !fits32) use_table = 0u;
     // per-end lists handed from k_pe_tiles to k_pe_accumulate
     const uint64_t n_tiles_all = (n_pairs + ept / 2 - 1) / (ept / 2);
     const uint64_t list_ends = n_tiles_all * ept;
@@ -2642,11 +2536,9 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     P.pmax = pmax;
     P.words_cap = ept * wpe;
     P.pool = pool_for(ept, &P.pool_bits);
-    P.debug_stop = tn.debug_stop;  // (VS_EXPERIMENT=timing only)
     P.n_pairs = n_pairs;
     P.n_tiles = (n_pairs + ept / 2 - 1) / (ept / 2);
     P.wpe = wpe;
-    P.count_postings = tn.debug_postings ? 1u : 0u;
     P.magic_pmax = pmax > 1u ? (uint32_t)(0x100000000ull / pmax) + 1u : 0u;
     P.magic_wpe = wpe > 1u ? (uint32_t)(0x100000000ull / wpe) + 1u : 0u;
     P.perm = use_sort ? (const uint32_t *)ctx->d_perm : nullptr;
@@ -2660,8 +2552,6 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     P.out_lists_hi = (uint32_t *)ctx->d_lists + list_ends * LC;
     P.tile_map = d_node_mat ? d_tile_map : nullptr;
     P.tile_T = (idx.n_nodes + 63u) >> 6;
-    P.no_xcd_map = tn.no_xcd_map ? 1u : 0u;
-    P.phase0 = tn.phase0 ? 1u : 0u;
     // The shortcut spares a single posting its extension when the previous probe already owns the
     // match; it pays on graphs whose seeds are mostly unique.  Where seeds repeat (a compacted de
     // Bruijn graph of many strains: 3.5 postings per distinct seed at configs[2]) nearly every
@@ -2680,11 +2570,12 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     const bool fast = (!reads->d_mask || reads->d_inv4) && idx.s <= 32u && maxlen <= 128u + idx.w + 32u &&
                       ctx->max_node_len < (1u << 23) && !tn.no_fast;
     P.mid_fast = fast && VS_SEED_VERIFIED(idx.w) && ctx->max_node_len < (1u << 23) ? 1u : 0u;
-    // compile-time-shape instantiations (see k_pe_tiles): 1 = (10, 4), 2 = (8, 3), 3 = (7, 2)
+    // compile-time-shape instantiations (see k_pe_tiles): 1 = (10, 4), 2 = (8, 3), 3 = (7, 2); counting runs only (vs_pe_map_ends
+    // takes the generic kernels)
+    const bool std_ok = P.accumulate && !tn.no_std;
     int std_shape = 0;
-    if (fast && ept == STD_EPT && P.pool_bits == STD_POOL_BITS && maxlen <= 159u && idx.K == STD_K && idx.w == STD_W &&
-        idx.s == STD_S && P.accumulate && !P.debug_stop && !P.count_postings && !P.dbg_counts &&
-        !tn.no_std && !tn.phase0) {
+    if (fast && std_ok && ept == STD_EPT && P.pool_bits == STD_POOL_BITS && maxlen <= 159u && idx.K == STD_K && idx.w == STD_W &&
+        idx.s == STD_S) {
         if (wpe == 10u && pmax == 4u) std_shape = 1;       // 2 x 145..159 bases
         else if (wpe == 8u && pmax == 3u) std_shape = 2;   // 2 x 113..128
         else if (wpe == 7u && pmax == 2u) std_shape = 3;   // 2 x 97..107
@@ -2696,13 +2587,13 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     // (vs_seed_phase): reads of up to 317 bases qualify at k = 127 (r5; 256 with the grid of rounds 1-4)
     uint32_t long_reach = 0;
     for (uint32_t len = idx.K; len <= maxlen; len++) {
-        const uint32_t behind = len - vs_seed_phase(len, idx.w, idx.s, tn.phase0) - VS_SEED_VERIFIED(idx.w);
+        const uint32_t behind = len - vs_seed_phase(len, idx.w, idx.s) - VS_SEED_VERIFIED(idx.w);
         long_reach = behind > long_reach ? behind : long_reach;
     }
     const bool fast_long = !fast && (!reads->d_mask || reads->d_inv4) && idx.s <= 128u && long_reach <= 256u && maxlen < 512u &&
                            ctx->max_node_len < (1u << 23) && !tn.no_fast;
-    if (fast_long && ept == STD2_EPT && P.pool_bits == STD2_POOL_BITS && idx.K == STD2_K && idx.w == STD2_W && idx.s == STD2_S &&
-        wpe == 16u && pmax == 2u && P.accumulate && !P.debug_stop && !P.count_postings && !P.dbg_counts && !tn.no_std && !tn.phase0)
+    if (fast_long && std_ok && ept == STD2_EPT && P.pool_bits == STD2_POOL_BITS && idx.K == STD2_K && idx.w == STD2_W && idx.s == STD2_S &&
+        wpe == 16u && pmax == 2u)
         std_shape = 4;
     // (r5) the adaptive step grid (k_pe_tiles, ADAPT) probes twice as many seeds to expand fewer postings: it pays where a
     // seed has many postings -- 8.9 seed positions per distinct seed at configs[4]: 24.8 -> 22.5 ms -- and costs a little
@@ -2724,14 +2615,9 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
                        : fast_long      ? TilesFn{(const void *)k_pe_tiles<2, 0u, 0u>, "k_pe_tiles<2, 0u, 0u>"}
                                         : TilesFn{(const void *)k_pe_tiles<0, 0u, 0u>, "k_pe_tiles<0, 0u, 0u>"};
     const void *tiles_fn = tf.fn;
-    if (std_shape && VS_POOL12 && !adapt) lds = (size_t)tile_layout(ept, pmax, ept * wpe, 768u, std_shape == 4 ? 192u : 64u).total * sizeof(uint32_t);
+    if (std_shape && !adapt) lds = (size_t)tile_layout(ept, pmax, ept * wpe, 768u, std_shape == 4 ? 192u : 64u).total * sizeof(uint32_t);
     if (lds > 64u * 1024u)
         VS_HIP(ctx, hipFuncSetAttribute(tiles_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (tn.debug_occ) {
-        int nb = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, tiles_fn, TTPB, lds);
-        fprintf(stderr, "[vs] k_pe_tiles: %zu B of LDS per workgroup, %d workgroups per CU\n", lds, nb);
-    }
     uint64_t grid = P.n_tiles;
     // Many more workgroups than fit at once (4 per CU): loci differ a lot in postings per read, and
     // short runs let the dispatcher even that out (runs of ~10 tiles at configs[2]: 8.4 ms, against
@@ -2798,35 +2684,28 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
             if (rc) return rc;
             ctx->last_launched |= VS_RAN_ROW_OWNERS;
         } else {
-            // one workgroup fits per CU (the cell table); 32 per CU queued, for the same reason as above
-            // (4.9 -> 3.9 ms), each at least one round of ACC_TPB pairs
-            uint32_t acc_grid = (uint32_t)ctx->n_cu * tn.acc_grid_per_cu;
+            // chunks of pairs: 32 per CU, for the same reason as above (4.9 -> 3.9 ms), each at least one round of
+            // ACC_TPB pairs
+            uint32_t acc_grid = (uint32_t)ctx->n_cu * 32u;
             uint32_t per_wg = (uint32_t)((slots_pairs + acc_grid - 1) / acc_grid);
             per_wg = (per_wg + ACC_TPB - 1) / ACC_TPB * ACC_TPB;
             acc_grid = (uint32_t)((slots_pairs + per_wg - 1) / per_wg);
             // the chunks are not bound to workgroups: two workgroups per CU take the next chunk off a
             // counter whenever they are free, so a cell table lives across chunks and is written out on
-            // fill only (3.85 -> 3.6 ms against one workgroup per chunk; VS_ACC_QUEUE=0 for that)
-            uint32_t *acc_queue = nullptr;
-            if (tn.acc_queue) {
-                acc_queue = (uint32_t *)ctx->d_slow_count + 1;
-                uint32_t wgs = (uint32_t)ctx->n_cu * 2u;
-                if (tn.acc_wgs) wgs = tn.acc_wgs;  // VS_ACC_WGS: fewer workgroups than CUs = the kernel on a part of the chip (r5 gate)
-                if (acc_grid > wgs) acc_grid = wgs;
-            }
+            // fill only (3.85 -> 3.6 ms against one workgroup per chunk)
+            uint32_t *acc_queue = (uint32_t *)ctx->d_slow_count + 1;
+            if (acc_grid > (uint32_t)ctx->n_cu * 2u) acc_grid = (uint32_t)ctx->n_cu * 2u;
             // the table is written out once this many of its slots are taken: probing stays short at a low
             // fill, and cells of loci the run has left do not pile up (VS_ACC_FILL: percent)
             uint32_t fill_limit = ACC_SLOTS / 16u;
             if (tn.acc_fill_pct >= 0) fill_limit = (uint32_t)((uint64_t)ACC_SLOTS * (uint32_t)tn.acc_fill_pct / 100u);
-            uint32_t *acc_dbg = tn.debug_acc ? (uint32_t *)ctx->d_slow_count + 4 : nullptr;
-            const uint32_t acc_ppw = tn.acc_round ? tn.acc_round / (ACC_TPB / 64u) : 64u;  // VS_ACC_ROUND: pairs per round
             if (d_tile_map && slots_pairs)  // (timed with the counter kernel: it is part of the counting)
                 hipLaunchKernelGGL(k_mark_tiles, dim3((unsigned)((slots_pairs + 255u) / 256u)), dim3(256), 0, st, (const uint32_t *)ctx->d_lists,
                                    (const uint32_t *)ctx->d_list_counts, slots_pairs, d_tile_map, P.tile_T, ept);
             VS_HIP(ctx, hipFuncSetAttribute((const void *)k_pe_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ACC_LDS_BYTES));
             hipLaunchKernelGGL(k_pe_accumulate, dim3(acc_grid), dim3(ACC_TPB), ACC_LDS_BYTES, st, (const uint32_t *)ctx->d_lists,
                                (const uint32_t *)ctx->d_list_counts, slots_pairs, per_wg, idx.n_nodes, use_table, fill_limit, d_node_mat,
-                               d_short_mat, acc_queue, acc_dbg, acc_ppw, ept);
+                               d_short_mat, acc_queue, ept);
         }
     }
     VS_HIP(ctx, hipEventRecord(ctx->ev[1], st));
@@ -2887,27 +2766,6 @@ extern "C" int vs_pe_last_timing(vs_ctx *ctx, double ms[5]) {
     uint32_t n_slow = 0;
     VS_HIP(ctx, hipMemcpy(&n_slow, ctx->d_slow_count, sizeof n_slow, hipMemcpyDeviceToHost));
     ms[0] = a; ms[1] = b; ms[2] = (double)n_slow; ms[3] = c; ms[4] = d;
-    if (ctx->tune.debug_postings) {
-        unsigned long long np = 0;
-        VS_HIP(ctx, hipMemcpy(&np, (char *)ctx->d_slow_count + 8, sizeof np, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[vs] postings expanded by the last vs_pe_count: %llu\n", np);
-    }
-    if (ctx->tune.debug_acc) {
-        uint32_t d4[4] = {0, 0, 0, 0};
-        VS_HIP(ctx, hipMemcpy(d4, (char *)ctx->d_slow_count + 16, sizeof d4, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[vs] k_pe_accumulate: %u increments went past the cell table, %u write-outs of %u cells, %u rounds\n", d4[0], d4[1], d4[2], d4[3]);
-        if (ctx->last_launched & VS_RAN_ROW_OWNERS) {
-            uint32_t r3[3] = {0, 0, 0};
-            VS_HIP(ctx, hipMemcpy(r3, (char *)ctx->d_slow_count + 40, sizeof r3, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[vs] k_rows_sum (both matrices): %u increments went past the cell table, %u write-outs of %u cells\n", r3[0], r3[1], r3[2]);
-
-            uint32_t e2[2] = {0, 0};  // entries of the last transposition: row_ptr[N] of either mode
-            const uint32_t *rows = (const uint32_t *)ctx->d_rows;
-            VS_HIP(ctx, hipMemcpy(&e2[0], rows + 2u * ctx->rows_cap + ctx->idx.n_nodes, sizeof(uint32_t), hipMemcpyDeviceToHost));
-            VS_HIP(ctx, hipMemcpy(&e2[1], rows + 5u * ctx->rows_cap + ctx->idx.n_nodes, sizeof(uint32_t), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[vs] row entries: node_mat %u, short_mat %u\n", e2[0], e2[1]);
-        }
-    }
     ctx->last_ms[0] = a; ctx->last_ms[1] = b; ctx->last_ms[2] = n_slow;
     return VS_OK;
 }
