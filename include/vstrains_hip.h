@@ -68,6 +68,15 @@ int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint64_t *node_
  * indexed, [3]=hash slots, [4]=distinct seeds, [5]=bytes of device memory held by the index. */
 int vs_index_info(const vs_ctx *ctx, uint64_t info[6]);
 
+/* Testing aid: the index the context holds, copied to host memory as the kernels read it (no kernel runs, nothing on
+ * the counting path changes).  sizes[0]=hash slots, [1]=postings (= seed positions), [2]=packed words per strand
+ * INCLUDING the zero pad words behind the text, [3]=nodes, [4]=log2 of the slots.  Every buffer may be NULL (not copied;
+ * call once with all NULL for the sizes): slots[sizes[0]] of 16 B (key u64 | a u32 | b u32), postings[sizes[1]] of 16 B
+ * (node | pos + strand << 31 | node length | first word), fwd_words / rc_words[sizes[2]], meta[sizes[3]] of 8 B
+ * (first word | length). */
+int vs_index_export(vs_ctx *ctx, void *slots, void *postings, uint32_t *fwd_words, uint32_t *rc_words, void *meta,
+                    uint64_t sizes[5]);
+
 /* A numbering of the nodes that runs along the graph's paths (host only; depth-first over k-base overlaps, either strand).
  * order_out[n_nodes]: order_out[r] = the node (position in node_off) that should be handed to vs_index_build as number r.
  * Optional, for speed only: the matrices vs_pe_count fills are indexed by the numbering vs_index_build was given

@@ -3,6 +3,8 @@
 boundaries where vs_pe_count switches kernels (seed geometry, straight-line vs long-window vs generic
 comparison, compile-time tile shapes, dirty-byte lists vs mask, list overflow), counts on the device and
 compares node_mat / short_mat / stats with the C oracle.  Prints the parameters of every failing draw.
+FUZZ_STD=1 draws the compile-time tile shapes only; FUZZ_COLLIDE=1 draws k >= 95 only (63-base seeds, whose keys are not
+unique) and plants different seeds with one key into the nodes and the reads (plant_collisions).
 
     python tests/fuzz_pe.py [seconds=300] [seed=1]        (test infrastructure: the oracle is the checker)
 """
@@ -16,6 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import seed_index_model as sim  # noqa: E402  (constructs 63-base seeds that share a key)
 from oracle import pe_oracle_c  # noqa: E402  (the checker)
 from vstrains_amd import pe as host, synth  # noqa: E402
 
@@ -37,6 +41,9 @@ def draw(rng):
     k = int(rng.choice(K_EDGE)) if rng.random() < 0.7 else int(rng.integers(3, 128))
     w = min(31, k + 1)
     w -= 1 - (w & 1)
+    if os.environ.get("FUZZ_COLLIDE"):  # 63-base seeds only
+        k = int(rng.choice([95, 96, 100, 125, 126, 127, 128, 140, 150])) if rng.random() < 0.7 else int(rng.integers(95, 160))
+        w = 63
     edges = [k + 1, k + 2, w + 127, w + 128, w + 129, w + 159, w + 160, w + 161, w + 255, w + 256, w + 257, 97, 112, 113, 128, 129, 145, 150, 159, 160, 250]
     L = int(rng.choice(edges)) if rng.random() < 0.7 else int(rng.integers(max(k - 3, 4), k + 320))
     L = max(4, min(L, 600))
@@ -75,6 +82,40 @@ def make_reads(p, st):
     return out
 
 
+def plant_collisions(p, seqs, fwd, rve):
+    """FUZZ_COLLIDE: one random 63-base stretch in each of some nodes replaced by seeds that share a key (several groups
+    of two to four seeds), and reads that hold them: windows of the changed nodes over the stretch, as they are and with
+    another seed of the group in its place -- text that is in no node, under a key that is.  The oracle judges as before."""
+    rng = np.random.default_rng(p["seed"] + 3)
+    K, L = p["k"] + 1, p["L"]
+    seqs = list(seqs)
+    fwd, rve = list(fwd), list(rve)
+    long_enough = [i for i, q in enumerate(seqs) if len(q) >= max(K, 63)]
+    rng.shuffle(long_enough)
+    extra = []
+    while len(long_enough) >= 2:
+        group_nodes = [long_enough.pop() for _ in range(min(int(rng.integers(2, 5)), len(long_enough)))]
+        x = sim.random_seq(rng, 63)
+        group = [x] + sim.colliding_seeds(x, len(group_nodes) - 1, rng)
+        for i, q in zip(group_nodes, group):
+            at = int(rng.integers(0, len(seqs[i]) - 62))
+            if rng.random() < 0.3:
+                q = sim.rc(q)
+            seqs[i] = seqs[i][:at] + q + seqs[i][at + 63:]
+            for other in (q, group[int(rng.integers(0, len(group)))]):
+                text = seqs[i][:at] + other + seqs[i][at + 63:]
+                st = max(0, min(at - int(rng.integers(0, max(L - 62, 1))), len(text) - L))
+                win = text[st: st + L]
+                extra.append(win if rng.random() < 0.5 else sim.rc(win))
+        if len(extra) > 400:
+            break
+    for j, e in enumerate(extra):  # into the block, in place of sampled reads
+        if not fwd:
+            break
+        (fwd if j % 2 else rve)[int(rng.integers(0, len(fwd)))] = e
+    return seqs, fwd, rve
+
+
 def main():
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 300.0
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -94,7 +135,10 @@ def main():
             skipped += 1
             continue
         fwd, rve = make_reads(p, st)
-        want = pe_oracle_c.Oracle(g.seqs, p["k"]).count_pairs(fwd, rve)
+        seqs = g.seqs
+        if os.environ.get("FUZZ_COLLIDE") and p["k"] >= 95:
+            seqs, fwd, rve = plant_collisions(p, seqs, fwd, rve)
+        want = pe_oracle_c.Oracle(seqs, p["k"]).count_pairs(fwd, rve)
         env = {}
         if rng.random() < 0.3:
             env = dict([[("VS_NO_STD", "1")], [("VS_NO_FAST", "1")], [("VS_EPT", "6")], [("VS_ACC_ROWS", "1"), ("VS_ROWS_KEYS", "64")], [("VS_ACC_ROWS", "1"), ("VS_LTAB_BITS", "0")], [("VS_ACC_ROWS", "1"), ("VS_ROWS_SUB", "1024")], [("VS_ACC_ROWS", "1"), ("VS_ACC_FILL", "1")], [("VS_ACC_FILL", "100")],
@@ -116,7 +160,7 @@ def main():
             env["VS_ADAPT_GRID"] = "0"
         os.environ.update(env)
         try:
-            ctx.build_index(g.seqs, p["k"])
+            ctx.build_index(seqs, p["k"])
             counter = host.PeCounter(ctx)
             block = ctx.pack_pairs(fwd, rve)
             counter.add(block)
@@ -130,7 +174,7 @@ def main():
         n += 1
         if not ok:
             bad += 1
-            print("MISMATCH", dict(p, env=env, nodes=len(g.seqs), kernel=kern,
+            print("MISMATCH", dict(p, env=env, nodes=len(seqs), kernel=kern,
                                    node_diff=int((node_mat != want[0]).sum()), short_diff=int((short_mat != want[1]).sum()),
                                    stats=(stats, tuple(int(x) for x in want[2]))), flush=True)
     print("draws %d, mismatches %d, skipped %d, %.0f s; kernels %s" % (n, bad, skipped, time.time() - t0, kernels))

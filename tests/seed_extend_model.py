@@ -12,13 +12,17 @@ def rc(s: str) -> str:
 
 
 def geometry(K: int) -> Tuple[int, int]:
-    w = min(K, 31)
+    """seed_geometry (csrc/vs_index.hip): 31-base seeds, 63-base ones from K = k + 1 = 96 on, made odd."""
+    w = 63 if K >= 96 else min(K, 31)
     if w % 2 == 0:
         w -= 1
     return w, K - w + 1
 
 
-def build(seqs: Sequence[str], K: int):
+def build(seqs: Sequence[str], K: int, key_fn=None):
+    """``key_fn`` (canonical seed text -> key, default the text itself): what the table files a seed under.  A function
+    that is not injective -- the device's mixed key of a 63-base seed (vs_seed_key), or a lossy one a test makes up --
+    puts different seeds into one bucket, and each then nominates the postings of the others."""
     w, s = geometry(K)
     table: Dict[str, List[Tuple[int, int, int]]] = {}
     for i, seq in enumerate(seqs):
@@ -28,6 +32,8 @@ def build(seqs: Sequence[str], K: int):
             f = seq[p : p + w]
             r = rc(f)
             key, strand = (f, 0) if f < r else (r, 1)
+            if key_fn is not None:
+                key = key_fn(key)
             table.setdefault(key, []).append((i, p, strand))
     return table, w, s
 
@@ -54,8 +60,14 @@ def step_grid(rlen: int, w: int, s: int, t: int) -> List[int]:
     return [s - 1 + i * s - (D if i >= t else 0) for i in range(n)]
 
 
-def map_end(read: str, seqs: Sequence[str], rcs: Sequence[str], table, w: int, s: int, K: int, first=None, probes=None, grid=None) -> List[int]:
+def map_end(read: str, seqs: Sequence[str], rcs: Sequence[str], table, w: int, s: int, K: int, first=None, probes=None, grid=None, key_fn=None,
+            verified=None) -> List[int]:
+    """``verified``: the seed bases the comparison after a probe takes for granted, the device's VS_SEED_VERIFIED(w)
+    (csrc/vs_internal.h) -- all w (the default) where equal keys mean equal seeds, 0 where they do not: the comparison
+    then starts at the seed's first base, and a posting whose seed differs from the read's ends below K bases."""
     rlen = len(read)
+    if verified is None:
+        verified = w
     agg: Dict[int, List[int]] = {}
     if grid is not None:  # explicit probe offsets: a match is credited by the first of them inside it (left extension < gap)
         todo = [(j, (j - grid[i - 1]) if i else s) for i, j in enumerate(grid) if j + w <= rlen]
@@ -72,6 +84,8 @@ def map_end(read: str, seqs: Sequence[str], rcs: Sequence[str], table, w: int, s
         if all(valid(c) for c in f):
             r = rc(f)
             key, sr = (f, 0) if f < r else (r, 1)
+            if key_fn is not None:
+                key = key_fn(key)
             for node, p, sn in table.get(key, ()):
                 opp = sn ^ sr
                 text = rcs[node] if opp else seqs[node]
@@ -83,10 +97,10 @@ def map_end(read: str, seqs: Sequence[str], rcs: Sequence[str], table, w: int, s
                     left += 1
                 if left >= gap:
                     continue
-                ext = 0
-                while j + w + ext < rlen and q + w + ext < tlen and read[j + w + ext] == text[q + w + ext]:
+                ext = verified  # (bases from the seed's first one on that are known or found equal)
+                while j + ext < rlen and q + ext < tlen and read[j + ext] == text[q + ext]:
                     ext += 1
-                ln = left + w + ext
+                ln = left + ext
                 if ln < K:
                     continue
                 a = j - left

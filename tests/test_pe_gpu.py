@@ -1026,14 +1026,17 @@ def test_two_gpu_rccl_step_and_sharded_drop_in(tmp_path):
     assert _read(outdir / "st_info") == _read(os.path.join(d, "st_info"))
 
 
-@pytest.mark.parametrize("mode", ["boundaries", "tile_shapes"])
+@pytest.mark.parametrize("mode", ["boundaries", "tile_shapes", "collisions"])
 def test_randomized_campaign_short(mode):
     """tests/fuzz_pe.py for ten seconds per mode: random graph / read shapes around the points where
     vs_pe_count switches kernels, every draw against the C oracle (the full campaigns of the round:
-    4 510 draws, no mismatch -- DESIGN.md 8)."""
+    4 510 draws, no mismatch -- DESIGN.md 8).  "collisions": k >= 95 with different 63-base seeds under one key planted
+    into nodes and reads (FUZZ_COLLIDE)."""
     env = dict(os.environ)
     if mode == "tile_shapes":
         env["FUZZ_STD"] = "1"
+    if mode == "collisions":
+        env["FUZZ_COLLIDE"] = "1"
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz_pe.py"), "10", "7"], cwd=ROOT, env=env,
                           capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stdout[-3000:] + proc.stderr[-2000:]

@@ -339,3 +339,24 @@ extern "C" int vs_index_info(const vs_ctx *ctx, uint64_t info[6]) {
     info[5] = ctx->index_bytes;
     return VS_OK;
 }
+
+// Testing aid: the built index as the kernels read it, copied to host memory (copies only, no kernel).
+extern "C" int vs_index_export(vs_ctx *ctx, void *slots, void *postings, uint32_t *fwd_words, uint32_t *rc_words, void *meta,
+                               uint64_t sizes[5]) {
+    if (!ctx || !sizes) return VS_E_ARG;
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_index_export: build an index first (vs_index_build)");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const VsIndexDev &d = ctx->idx;
+    sizes[0] = ctx->n_slots;
+    sizes[1] = ctx->n_seed_pos;
+    sizes[2] = d.rc_delta;
+    sizes[3] = d.n_nodes;
+    sizes[4] = d.table_bits;
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (slots) VS_HIP(ctx, hipMemcpy(slots, ctx->d_table, sizeof(VsSlot) * ctx->n_slots, hipMemcpyDeviceToHost));
+    if (postings && ctx->n_seed_pos) VS_HIP(ctx, hipMemcpy(postings, ctx->d_post, sizeof(uint4) * ctx->n_seed_pos, hipMemcpyDeviceToHost));
+    if (fwd_words) VS_HIP(ctx, hipMemcpy(fwd_words, d.fwd_words, sizeof(uint32_t) * d.rc_delta, hipMemcpyDeviceToHost));
+    if (rc_words) VS_HIP(ctx, hipMemcpy(rc_words, d.rc_words, sizeof(uint32_t) * d.rc_delta, hipMemcpyDeviceToHost));
+    if (meta && d.n_nodes) VS_HIP(ctx, hipMemcpy(meta, d.meta, sizeof(VsNodeMeta) * d.n_nodes, hipMemcpyDeviceToHost));
+    return VS_OK;
+}

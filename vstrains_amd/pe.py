@@ -422,6 +422,24 @@ class Context:
         nat.check(self._h, nat.lib().vs_index_info(self._h, a))
         return dict(seed_len=a[0], stride=a[1], seed_positions=a[2], slots=a[3], distinct_seeds=a[4], device_bytes=a[5])
 
+    def index_export(self):
+        """The built index as the kernels read it, in host arrays (a test aid, ``vs_index_export``): ``slot_key`` uint64,
+        ``slot_a`` / ``slot_b`` uint32 [slots]; ``postings`` uint32 [seed positions, 4] (node, pos | strand << 31, node
+        length, first word); ``fwd`` / ``rc`` uint32 packed words of either strand with the pad words; ``meta`` uint32
+        [nodes, 2] (first word, length); ``table_bits``."""
+        sizes = (C.c_uint64 * 5)()
+        nat.check(self._h, nat.lib().vs_index_export(self._h, None, None, None, None, None, sizes))
+        n_slots, n_post, n_words, n_nodes, bits = (int(x) for x in sizes)
+        slots = np.zeros(n_slots, dtype=np.dtype([("key", "<u8"), ("a", "<u4"), ("b", "<u4")]))
+        post = np.zeros((max(n_post, 1), 4), dtype=np.uint32)
+        fwd = np.zeros(n_words, dtype=np.uint32)
+        rc = np.zeros(n_words, dtype=np.uint32)
+        meta = np.zeros((max(n_nodes, 1), 2), dtype=np.uint32)
+        nat.check(self._h, nat.lib().vs_index_export(self._h, slots.ctypes.data, post.ctypes.data, fwd.ctypes.data, rc.ctypes.data,
+                                                     meta.ctypes.data, sizes))
+        return dict(slot_key=slots["key"].copy(), slot_a=slots["a"].copy(), slot_b=slots["b"].copy(), postings=post[:n_post],
+                    fwd=fwd, rc=rc, meta=meta[:n_nodes], table_bits=bits)
+
     def scan_text(self, text: bytes, line0: int = 0):
         """The streamed ingest's device line scanner on ``text`` (a test aid, ``vs_fastq_scan_text``): (byte offsets of the
         newlines, flags: 1 a carriage return, 2 a byte >= 0x80, the record cut when the first line has number ``line0``)."""
