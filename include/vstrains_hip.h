@@ -174,6 +174,30 @@ void vs_fastq_stream_close(vs_fastq_stream *s);
 int vs_fastq_scan_text(vs_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t line0, uint64_t *ends, uint64_t cap,
                        uint64_t info[3]);
 
+/* BGZF (additions to ABI 10): the blocked gzip of bgzip / htslib / samtools.  The streamed ingest inflates the members of
+ * such a file ON THE DEVICE (one wavefront per member, vs_inflate.hip) unless VS_BGZF_DEVICE=0; any other gzip member keeps
+ * the host zlib loop, from that byte on for the rest of its file.
+ *   vs_bgzf_walk    : host only.  The whole BGZF members at the front of buf[0, n): members[4i .. 4i+3] (up to cap members)
+ *                     = payload offset, payload length, ISIZE, CRC32; info[0] = members found, [1] = the offset of the first
+ *                     byte that is not part of one, [2] = what is there: 0 nothing (the range ends after a member), 1 bytes
+ *                     that may become a member ("need more bytes"), 2 not BGZF (any other gzip member, any other bytes, other
+ *                     FLG bits, CM != 8, no BC subfield, BSIZE too small for header and trailer, ISIZE > 65536)
+ *   vs_inflate_host : host only.  One raw deflate payload through the decoder the kernel runs, lane loops serial:
+ *                     *status = 0, or the first thing wrong: 1 block type 3, 2 stored LEN/NLEN, 3 over-subscribed and
+ *                     4 incomplete code lengths, 5 invalid literal/length and 6 distance symbol, 7 distance beyond the
+ *                     member's own output, 8 payload exhausted, 9 output beyond and 10 short of ISIZE, 11 CRC32 mismatch,
+ *                     12 bad code-length section, 13 payload bytes behind the final block, 14 bad descriptor.  Nothing is
+ *                     written outside out[0, isize).
+ *   vs_inflate_bgzf : test aid.  n host bytes of whole members through the device kernel; member i's bytes at
+ *                     out[sum over j < i of (ISIZE_j + guard)], followed by `guard` bytes that keep the value 0xA5;
+ *                     status[i] as above; info[0] = members, [1] = bytes of out used (out == NULL: the sizes only)
+ *   vs_fastq_stream_inflate_info : info[2f + 0] = members of file f inflated on the device, [2f + 1] = on the host */
+int vs_bgzf_walk(const uint8_t *buf, uint64_t n, uint64_t *members, uint64_t cap, uint64_t info[3]);
+int vs_inflate_host(const uint8_t *payload, uint32_t len, uint8_t *out, uint32_t isize, uint32_t crc, uint32_t *status);
+int vs_inflate_bgzf(vs_ctx *ctx, const uint8_t *data, uint64_t n, uint8_t *out, uint64_t out_cap, uint32_t guard, uint32_t *status,
+                    uint64_t status_cap, uint64_t info[2]);
+int vs_fastq_stream_inflate_info(const vs_fastq_stream *s, uint64_t info[4]);
+
 /* pe_info / st_info text (PE_Inference.py:194-205): "{id_i}:{id_j}:{count}\n" for all i, j in
  * row-major order, zeros included.  ids: the n node names concatenated, id_off[n+1]; mat: HOST
  * n*n int64.  Formatted on all host cores, one write(). */

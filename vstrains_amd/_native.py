@@ -47,6 +47,11 @@ SYMBOLS = {
     "vs_fastq_stream_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "vs_fastq_stream_close": (None, [C.c_void_p]),
     "vs_fastq_scan_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vs_bgzf_walk": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vs_inflate_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "vs_inflate_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                  C.POINTER(C.c_uint64)]),
+    "vs_fastq_stream_inflate_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "vs_write_matrix_text": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "vs_synth_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
                                  C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,

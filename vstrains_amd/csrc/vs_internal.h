@@ -220,6 +220,21 @@ uint32_t vs_utf8_char_len(const uint8_t *q, size_t n);
 void vs_launch_count_invalid(hipStream_t st, const uint32_t *meta, uint64_t n_ends, uint32_t *out);
 void vs_launch_inv4(hipStream_t st, const uint32_t *woff, const uint32_t *mask, uint64_t n_ends, uint32_t *meta, uint32_t *inv4);
 
+// BGZF members (vs_inflate.hip), shared with the streamed ingest.  A member for the device: its raw deflate payload in a
+// buffer of compressed bytes, where its ISIZE bytes go in an output buffer, and the CRC32 of its trailer.
+struct vs_bgzf_member {
+    uint32_t in_off, in_len, out_off, isize, crc;
+};
+// p[0, avail): 0 when a whole BGZF member starts at p (*m with in_off relative to p and out_off 0, *member_size its bytes),
+// 1 when what is there may still become one with more bytes, 2 when it is not BGZF
+int vs_bgzf_parse(const uint8_t *p, size_t avail, vs_bgzf_member *m, size_t *member_size);
+// n members, one wavefront each: status[i] = 0 or an INF_E_* word; atomicMin(first_bad, base + i) for every i that failed
+// (member i is dir[i], or dir[n - 1 - i] when `reversed`)
+void vs_launch_inflate(hipStream_t st, const uint8_t *comp, uint64_t comp_size, uint8_t *out, uint64_t out_size, const vs_bgzf_member *dir,
+                       uint32_t n, uint32_t *status, uint32_t *first_bad, uint32_t base, int reversed);
+// the same decoder on the host (vs_inflate_core.h with one lane): the status word
+uint32_t vs_inflate_member_host(const uint8_t *pay, uint32_t len, uint8_t *out, uint32_t isize, uint32_t crc);
+
 // Exclusive scan of n uint32 values on the ctx stream (in -> out, may alias); total (uint64) is
 // written to d_total if not NULL.  tmp must hold ceil(n/2048)+1 uint64.
 int vs_scan_u32(vs_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *d_tmp,

@@ -7,6 +7,17 @@
 // as in map_file) -- into a ring of STREAM_RING_SLOTS pinned chunks of STREAM_CHUNK_BYTES.  Peak host memory is the
 // ring, whatever the size of the file.
 //
+// BGZF (the blocked gzip of bgzip / htslib / samtools; VS_BGZF_DEVICE=0 switches this off): when a file's first bytes
+// are a BGZF member the reader does not inflate.  It fills a slot with the raw deflate payloads of WHOLE members, their
+// directory (payload offset and length, output offset, ISIZE, CRC32) growing down from the slot's end, until the ISIZE sum
+// would pass the chunk size or the slot is full; the device inflates them into the window (k_inflate of vs_inflate.hip,
+// one wavefront per member) and checks every CRC32.  The index of the first member that failed comes back with the
+// statistics scan_windows reads anyway.  A slot holds at least one member whatever VS_STREAM_CHUNK says, so the ring's
+// pinned memory is STREAM_RING_SLOTS x max(chunk, 64 KiB) per file.  From the first byte that is no whole BGZF member
+// (another gzip member, garbage, a member cut off by the end of the file) the file goes through the zlib loop for the rest
+// of it -- which also words the failure for what is no gzip at all.  A member the device rejected is inflated again with
+// zlib on the host for the code of that message; should zlib accept it, that is VS_E_STATE, never a silent continuation.
+//
 // Device: every file has a window = the bytes left over from the last block (they start at a record boundary) + the
 // chunks appended since.  Per step, for each window:
 //   k_sl_count    one lane per 16-byte word: newlines per workgroup, flags for '\r' and bytes >= 0x80, the last byte;
@@ -55,7 +66,9 @@ constexpr size_t STREAM_MAX_WINDOW = 0xFFFFFF00u; // line ends are 32-bit byte o
 // per-window status the kernels write (one uint32 array per stream, read back in one copy)
 enum { ST_NL = 0, ST_FLAGS = 1, ST_LAST = 2, ST_PER_FILE = 4 };  // [f * ST_PER_FILE + ...]
 enum { ST_MAXLEN = 8, ST_TOO_LONG = 9, ST_WORDS = 10, ST_INVALID = 11, ST_CUT = 12 /* + f */, ST_N = 16 };
+enum { ST_BAD = ST_N /* + f: the first member of file f the device rejected (a running index), ~0u: none */, ST_ALL = ST_N + 2 };
 enum { FL_CR = 1u, FL_HIGH = 2u };
+enum { M_PLAIN = 0, M_ZLIB = 1, M_BGZF = 2 };
 
 }  // namespace
 
@@ -257,8 +270,12 @@ namespace {
 
 struct Slot {
     uint8_t *p = nullptr;
-    size_t len = 0;
+    size_t len = 0;  // bytes of text, or of deflate payloads when n_members > 0 or comp
     bool last = false;
+    bool comp = false;        // payloads of BGZF members + their directory at the slot's end (the last member first)
+    uint32_t n_members = 0;
+    size_t text = 0;          // what the members inflate to (the ISIZE sum)
+    size_t cap = 0;
 };
 
 // One file read front to back by a thread of its own into the ring.  The consumer takes filled slots in order and gives
@@ -272,8 +289,9 @@ struct Reader {
     bool stop = false, finished = false;
     int err = VS_OK;
     std::string err_msg;
-    bool gzip = false;
-    uint64_t raw_bytes = 0, text_bytes = 0;
+    bool gzip = false, bgzf = false, bgzf_device = true;
+    size_t slot_cap = STREAM_CHUNK_BYTES;
+    uint64_t raw_bytes = 0, text_bytes = 0, members_host = 0;
     std::mutex m;
     std::condition_variable cv;
     std::thread th;
@@ -311,13 +329,22 @@ struct Reader {
         size_t in_len = 0;
         bool in_eof = false;
         // the first bytes say whether the file is gzip (magic 1f 8b)
-        while (in_len < 2 && !in_eof) {
+        while (in_len < 18 && !in_eof) {  // (18: the header of a BGZF member as bgzip writes it)
             const ssize_t got = raw_read(in.data() + in_len, in.size() - in_len);
             if (got < 0) { publish(0, true); return; }
             if (got == 0) in_eof = true;
             in_len += (size_t)got;
         }
         gzip = in_len >= 2 && in[0] == 0x1f && in[1] == 0x8b;
+        int mode = gzip ? M_ZLIB : M_PLAIN;
+        if (gzip && bgzf_device) {
+            vs_bgzf_member mb;
+            size_t msize = 0;
+            if (vs_bgzf_parse(in.data(), in_len, &mb, &msize) != 2) mode = M_BGZF;
+        }
+        bgzf = mode == M_BGZF;
+        slot_cap = bgzf ? (std::max<size_t>(chunk, 65536u) + 15u) & ~(size_t)15u : chunk;
+        size_t in_at = 0;  // (BGZF: bytes of `in` already handed on)
         z_stream zs;
         memset(&zs, 0, sizeof zs);
         if (gzip && inflateInit2(&zs, 15 + 16) != Z_OK) {
@@ -326,7 +353,7 @@ struct Reader {
             return;
         }
         size_t plain_at = 0;  // (plain text: bytes of `in` not yet handed on)
-        if (gzip) {
+        if (mode == M_ZLIB) {
             zs.next_in = in.data();
             zs.avail_in = (uInt)in_len;
         }
@@ -339,15 +366,64 @@ struct Reader {
                 if (stop) break;
                 slot = &slots[filled % STREAM_RING_SLOTS];  // (free: the consumer gave it back)
             }
-            if (!slot->p && hipHostMalloc((void **)&slot->p, chunk, hipHostMallocDefault) != hipSuccess) {
+            if (!slot->p && hipHostMalloc((void **)&slot->p, slot_cap, hipHostMallocDefault) != hipSuccess) {
                 slot->p = nullptr;
-                fail(VS_E_OOM, "%s: cannot pin a %s-byte chunk", path.c_str(), std::to_string(chunk).c_str());
+                fail(VS_E_OOM, "%s: cannot pin a %s-byte chunk", path.c_str(), std::to_string(slot_cap).c_str());
             }
+            slot->cap = slot_cap;
             uint8_t *dst = slot->p;
             if (!dst) { publish(0, true); break; }
             size_t len = 0;
             bool bad = false;
-            if (!gzip) {
+            if (mode == M_BGZF) {
+                uint32_t nm = 0;
+                size_t text = 0;
+                bool to_zlib = false;
+                vs_bgzf_member *dir_end = (vs_bgzf_member *)(dst + slot_cap);
+                for (;;) {
+                    vs_bgzf_member mb;
+                    size_t msize = 0;
+                    const int st = vs_bgzf_parse(in.data() + in_at, in_len - in_at, &mb, &msize);
+                    if (st == 0) {
+                        const size_t need = ((len + mb.in_len + 3u) & ~(size_t)3u) + sizeof(vs_bgzf_member) * (nm + 1u);
+                        if (nm && (need > slot_cap || text + mb.isize > chunk || len + mb.in_len > 0xFFFF0000u)) break;  // the next slot's
+                        memcpy(dst + len, in.data() + in_at + mb.in_off, mb.in_len);
+                        mb.in_off = (uint32_t)len;
+                        mb.out_off = (uint32_t)text;
+                        dir_end[-(ptrdiff_t)(nm + 1u)] = mb;
+                        len += mb.in_len;
+                        text += mb.isize;
+                        nm++;
+                        in_at += msize;
+                        if (text >= chunk) break;
+                        continue;
+                    }
+                    if (st == 1 && !in_eof) {  // a member cut by a read boundary: more bytes
+                        memmove(in.data(), in.data() + in_at, in_len - in_at);
+                        in_len -= in_at;
+                        in_at = 0;
+                        const ssize_t got = raw_read(in.data() + in_len, in.size() - in_len);
+                        if (got < 0) { bad = true; break; }
+                        if (got == 0) in_eof = true;
+                        in_len += (size_t)got;
+                        continue;
+                    }
+                    if (in_at == in_len) at_end = true;  // the end of the file, after a whole member
+                    else to_zlib = true;                 // not BGZF, or a member the end of the file cut: zlib says what it is
+                    break;
+                }
+                if (to_zlib) {
+                    mode = M_ZLIB;
+                    zs.next_in = in.data() + in_at;
+                    zs.avail_in = (uInt)(in_len - in_at);
+                    if (!nm) continue;  // (nothing for the device in this slot: the zlib loop fills it)
+                }
+                at_end = at_end || bad || (!to_zlib && in_eof && in_at == in_len);
+                text_bytes += text;
+                publish(len, at_end, true, nm, text);
+                continue;
+            }
+            if (mode == M_PLAIN) {
                 const size_t now = std::min(chunk, in_len - plain_at);
                 memcpy(dst, in.data() + plain_at, now);
                 plain_at += now;
@@ -374,6 +450,7 @@ struct Reader {
                     rc = inflate(&zs, Z_NO_FLUSH);
                     len = chunk - zs.avail_out;
                     if (rc == Z_STREAM_END) {
+                        members_host++;
                         if (zs.avail_in == 0 && !in_eof) {  // more members may follow: look
                             const ssize_t got = raw_read(in.data(), in.size());
                             if (got < 0) { bad = true; break; }
@@ -403,11 +480,14 @@ struct Reader {
         }
         if (gzip) inflateEnd(&zs);
     }
-    void publish(size_t len, bool last) {
+    void publish(size_t len, bool last, bool comp = false, uint32_t n_members = 0, size_t text = 0) {
         std::lock_guard<std::mutex> lk(m);
         Slot &s = slots[filled % STREAM_RING_SLOTS];
         s.len = len;
         s.last = last;
+        s.comp = comp;
+        s.n_members = n_members;
+        s.text = comp ? text : len;
         filled++;
         finished = last;
         cv.notify_all();
@@ -467,6 +547,13 @@ struct DevFile {
     std::string err_msg;
     uint32_t pend[4] = {0, 0, 0, 0};  // (end-of-input check) bytes of a character cut by a chunk boundary
     uint32_t n_pend = 0;
+    // BGZF: the device copy of a slot's payloads and directory, a status word per member
+    uint8_t *comp = nullptr;
+    vs_bgzf_member *dir = nullptr;
+    uint32_t *mstat = nullptr;
+    size_t comp_cap = 0, dir_cap = 0, mstat_cap = 0;
+    uint64_t members_dev = 0;  // members the device inflated so far
+    uint32_t slot_base = 0;    // running index of the first member of the slot appended last
 };
 
 }  // namespace
@@ -476,7 +563,7 @@ struct vs_fastq_stream {
     hipStream_t st = nullptr;
     Reader rd[2];
     DevFile df[2];
-    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // ST_N words each (h_stat pinned)
+    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // ST_ALL words each (h_stat pinned)
     uint32_t *d_wcnt = nullptr;
     size_t wcnt_cap = 0;
     uint64_t pairs = 0;
@@ -496,10 +583,11 @@ int stream_fail(vs_ctx *ctx, vs_fastq_stream *s, int code, const std::string &ms
 }
 
 // count + scan of window f: n_nl, flags, last byte into the host status (synchronises the stream)
-int scan_windows(vs_ctx *ctx, vs_fastq_stream *s) {
+int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
     hipStream_t st = s->st;
     VS_HIP(ctx, hipMemsetAsync(s->d_stat, 0, sizeof(uint32_t) * ST_N, st));
     for (int f = 0; f < 2; f++) {
+        if (only >= 0 && f != only) continue;
         DevFile &d = s->df[f];
         const uint64_t words = (d.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
         if (int rc = grow(ctx, d.wg, d.wg_cap, wgs + 1u)) return rc;
@@ -510,9 +598,10 @@ int scan_windows(vs_ctx *ctx, vs_fastq_stream *s) {
         }
     }
     VS_HIP(ctx, hipGetLastError());
-    VS_HIP(ctx, hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_N, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_ALL, hipMemcpyDeviceToHost, st));
     VS_HIP(ctx, hipStreamSynchronize(st));
     for (int f = 0; f < 2; f++) {
+        if (only >= 0 && f != only) continue;
         DevFile &d = s->df[f];
         d.n_nl = s->h_stat[f * ST_PER_FILE + ST_NL];
         d.flags = s->h_stat[f * ST_PER_FILE + ST_FLAGS];
@@ -598,6 +687,9 @@ bool check_piece(DevFile &d, const uint8_t *p, size_t n, bool last) {
     return true;
 }
 
+int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot &sl);
+bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl);
+
 // Both files to their ends (the reference reads them whole): every byte not yet checked is checked, a reader's failure is
 // picked up; then the first failure in file order.
 int finish(vs_ctx *ctx, vs_fastq_stream *s) {
@@ -615,7 +707,31 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
         d.validated = d.size;
         while (!d.eof) {
             Slot &sl = r.take();
-            if (d.err == VS_OK && !check_piece(d, sl.p, sl.len, sl.last)) {
+            bool ok = true;
+            if (d.err == VS_OK && sl.comp) {
+                // no text on the host: the members are inflated (and their CRCs checked) on the device like any others, and
+                // the text comes back only when the scan saw a byte >= 0x80 (or a character is still open)
+                d.size = 0;
+                int rc = append_slot(ctx, s, f, sl);
+                if (rc == VS_OK) rc = scan_windows(ctx, s, f);
+                if (rc != VS_OK) {
+                    const std::string msg = vs_last_error(ctx);
+                    r.give_back();
+                    return stream_fail(ctx, s, rc, msg);
+                }
+                if (!member_failed(ctx, s, f, sl) && ((d.flags & FL_HIGH) || d.n_pend)) {
+                    std::vector<uint8_t> buf(d.size);
+                    if (d.size && hipMemcpy(buf.data(), d.win[d.cur], d.size, hipMemcpyDeviceToHost) != hipSuccess) {
+                        r.give_back();
+                        return stream_fail(ctx, s, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
+                    }
+                    ok = check_piece(d, buf.data(), buf.size(), sl.last);
+                }
+                d.size = d.validated = 0;
+            } else if (d.err == VS_OK) {
+                ok = check_piece(d, sl.p, sl.len, sl.last);
+            }
+            if (!ok) {
                 d.err = VS_E_UTF8;
                 d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
             }
@@ -637,25 +753,96 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
     return VS_OK;
 }
 
-// the next slot of file f appended to its window (blocks until the reader has one)
-int append_chunk(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot *&taken) {
+// a slot of file f appended to its window: its text uploaded, or its BGZF members uploaded and inflated there
+int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot &sl) {
     DevFile &d = s->df[f];
-    Slot &sl = s->rd[f].take();
-    taken = &sl;
-    if (d.size + sl.len > STREAM_MAX_WINDOW)
+    if (d.size + sl.text > STREAM_MAX_WINDOW)
         return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete record", s->rd[f].path.c_str(),
-                       (unsigned long long)(d.size + sl.len));
-    const size_t need = ((d.size + sl.len + 15u) & ~(size_t)15u) + 16u;
+                       (unsigned long long)(d.size + sl.text));
+    const size_t need = ((d.size + sl.text + 15u) & ~(size_t)15u) + 16u;
     if (d.win_cap[d.cur] < need) {  // keep the leftover: grow the other buffer, copy, switch
         const int o = d.cur ^ 1;
         if (int rc = grow(ctx, d.win[o], d.win_cap[o], need)) return rc;
         if (d.size) VS_HIP(ctx, hipMemcpyAsync(d.win[o], d.win[d.cur], d.size, hipMemcpyDeviceToDevice, s->st));
         d.cur = o;
     }
-    if (sl.len) VS_HIP(ctx, hipMemcpyAsync(d.win[d.cur] + d.size, sl.p, sl.len, hipMemcpyHostToDevice, s->st));
-    d.size += sl.len;
+    if (sl.comp) {
+        const uint32_t nm = sl.n_members;
+        d.slot_base = (uint32_t)d.members_dev;
+        if (nm) {
+            if (int rc = grow(ctx, d.comp, d.comp_cap, sl.len + 16u)) return rc;
+            if (int rc = grow(ctx, d.dir, d.dir_cap, (size_t)nm)) return rc;
+            if (int rc = grow(ctx, d.mstat, d.mstat_cap, (size_t)nm)) return rc;
+            const vs_bgzf_member *dir = (const vs_bgzf_member *)(sl.p + sl.cap) - nm;  // (member i at dir[nm - 1 - i])
+            if (sl.len) VS_HIP(ctx, hipMemcpyAsync(d.comp, sl.p, sl.len, hipMemcpyHostToDevice, s->st));
+            VS_HIP(ctx, hipMemcpyAsync(d.dir, dir, sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, s->st));
+            vs_launch_inflate(s->st, d.comp, sl.len, d.win[d.cur] + d.size, sl.text, d.dir, nm, d.mstat, s->d_stat + ST_BAD + f, d.slot_base, 1);
+            VS_HIP(ctx, hipGetLastError());
+            d.members_dev += nm;
+        }
+    } else if (sl.len) {
+        VS_HIP(ctx, hipMemcpyAsync(d.win[d.cur] + d.size, sl.p, sl.len, hipMemcpyHostToDevice, s->st));
+    }
+    d.size += sl.text;
     d.eof = sl.last;
     return VS_OK;
+}
+
+// the next slot of file f appended to its window (blocks until the reader has one)
+int append_chunk(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot *&taken) {
+    Slot &sl = s->rd[f].take();
+    taken = &sl;
+    return append_slot(ctx, s, f, sl);
+}
+
+// After scan_windows: did the device reject a member of the slot of file f appended last?  Then zlib inflates that member
+// on the host and the file fails with zlib's code, in the words of the reader's zlib loop (true: the file has failed).
+bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
+    DevFile &d = s->df[f];
+    if (!sl.comp || s->h_stat[ST_BAD + f] == 0xFFFFFFFFu) return false;
+    const uint32_t idx = s->h_stat[ST_BAD + f] - d.slot_base;
+    char msg[700];
+    if (d.err != VS_OK) return true;
+    if (idx >= sl.n_members) {
+        d.err = VS_E_STATE;
+        d.err_msg = s->rd[f].path + ": the device reported a BGZF member that is not of the slot it inflated";
+        return true;
+    }
+    const vs_bgzf_member mb = ((const vs_bgzf_member *)(sl.p + sl.cap))[-(ptrdiff_t)(idx + 1u)];
+    uint32_t dev_status = 0;
+    (void)hipMemcpy(&dev_status, d.mstat + idx, sizeof dev_status, hipMemcpyDeviceToHost);
+    // the member as a plain gzip member: a 10-byte header, the payload, the trailer
+    std::vector<uint8_t> gz = {0x1f, 0x8b, 0x08, 0, 0, 0, 0, 0, 0, 0xff};
+    gz.insert(gz.end(), sl.p + mb.in_off, sl.p + mb.in_off + mb.in_len);
+    for (uint32_t v : {mb.crc, mb.isize})
+        for (int k = 0; k < 4; k++) gz.push_back((uint8_t)(v >> (8 * k)));
+    std::vector<uint8_t> out(1u << 16);
+    z_stream zs;
+    memset(&zs, 0, sizeof zs);
+    int rc = inflateInit2(&zs, 15 + 16);
+    if (rc == Z_OK) {
+        zs.next_in = gz.data();
+        zs.avail_in = (uInt)gz.size();
+        do {
+            zs.next_out = out.data();
+            zs.avail_out = (uInt)out.size();
+            rc = inflate(&zs, Z_NO_FLUSH);
+        } while (rc == Z_OK && (zs.avail_in != 0 || zs.avail_out == 0));
+        const bool accepted = rc == Z_STREAM_END && zs.avail_in == 0;
+        inflateEnd(&zs);
+        if (accepted) {
+            snprintf(msg, sizeof msg, "%s: BGZF member %llu was rejected on the device (status %u) but zlib accepts it", s->rd[f].path.c_str(),
+                     (unsigned long long)(d.slot_base + idx), dev_status);
+            d.err = VS_E_STATE;
+            d.err_msg = msg;
+            return true;
+        }
+        if (rc >= 0 || rc == Z_BUF_ERROR) rc = Z_DATA_ERROR;  // (cut off, or bytes behind its end: as the reader's zlib loop)
+    }
+    snprintf(msg, sizeof msg, "%s: not a complete gzip stream (zlib code %d)", s->rd[f].path.c_str(), rc);
+    d.err = VS_E_ARG;
+    d.err_msg = msg;
+    return true;
 }
 
 // the window after its first `cut` bytes (the records of the block) have gone: the leftover to the front of the other buffer
@@ -691,6 +878,7 @@ int vs_fastq_stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path
         r.path = paths[f];
         r.chunk = chunk;
         r.device = ctx->device;
+        if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
         r.fd = open(paths[f], O_RDONLY);
         if (r.fd < 0) {
             const int e = errno;
@@ -700,8 +888,9 @@ int vs_fastq_stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path
         }
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
-    if (e1 == hipSuccess) e1 = hipMalloc((void **)&s->d_stat, sizeof(uint32_t) * ST_N);
-    if (e1 == hipSuccess) e1 = hipHostMalloc((void **)&s->h_stat, sizeof(uint32_t) * ST_N, hipHostMallocDefault);
+    if (e1 == hipSuccess) e1 = hipMalloc((void **)&s->d_stat, sizeof(uint32_t) * ST_ALL);
+    if (e1 == hipSuccess) e1 = hipMemset(s->d_stat + ST_BAD, 0xFF, sizeof(uint32_t) * 2);
+    if (e1 == hipSuccess) e1 = hipHostMalloc((void **)&s->h_stat, sizeof(uint32_t) * ST_ALL, hipHostMallocDefault);
     if (e1 != hipSuccess) {
         vs_fastq_stream_close(s);
         return vs_fail(ctx, VS_E_HIP, "vs_fastq_stream_open: %s", hipGetErrorString(e1));
@@ -739,9 +928,18 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
         }
         if (round > 0 && !appended) return finish(ctx, s);  // (nothing more to read and no pair: the end)
         int rc = scan_windows(ctx, s);
+        if (rc) {
+            const std::string msg = vs_last_error(ctx);
+            for (int f = 0; f < 2; f++)
+                if (taken[f]) s->rd[f].give_back();
+            return stream_fail(ctx, s, rc, msg);
+        }
+        bool rejected = false;
+        for (int f = 0; f < 2; f++)
+            if (taken[f] && member_failed(ctx, s, f, *taken[f])) rejected = true;  // (needs the slot: before it goes back)
         for (int f = 0; f < 2; f++)
             if (taken[f]) s->rd[f].give_back();  // (the stream is synchronised: the upload is done)
-        if (rc) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+        if (rejected) return finish(ctx, s);
         bool again = false;
         for (int f = 0; f < 2; f++) {
             DevFile &d = s->df[f];
@@ -867,7 +1065,7 @@ void vs_fastq_stream_close(vs_fastq_stream *s) {
     for (Reader &r : s->rd) r.shut();
     if (s->st) (void)hipStreamSynchronize(s->st);
     for (DevFile &d : s->df) {
-        void *ps[] = {d.win[0], d.win[1], d.ends, d.wg};
+        void *ps[] = {d.win[0], d.win[1], d.ends, d.wg, d.comp, d.dir, d.mstat};
         for (void *p : ps)
             if (p) (void)hipFree(p);
     }
@@ -876,6 +1074,15 @@ void vs_fastq_stream_close(vs_fastq_stream *s) {
     if (s->h_stat) (void)hipHostFree(s->h_stat);
     if (s->st) (void)hipStreamDestroy(s->st);
     delete s;
+}
+
+int vs_fastq_stream_inflate_info(const vs_fastq_stream *s, uint64_t info[4]) {
+    if (!s || !info) return VS_E_ARG;
+    for (int f = 0; f < 2; f++) {
+        info[2 * f + 0] = s->df[f].members_dev;
+        info[2 * f + 1] = s->rd[f].members_host;
+    }
+    return VS_OK;
 }
 
 // Test aid: the device line scanner on host text.  ends[i] (cap of them) = byte offset of newline i; info[0] = newlines,

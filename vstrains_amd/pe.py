@@ -219,7 +219,9 @@ class FastqPair:
 class FastqStream:
     """Both FASTQ files read front to back through the library's streamed ingest (``vs_fastq_stream_*``): any file a
     process can read once -- a FIFO, ``/dev/stdin``, ``<(zcat R1.fq.gz)``, a regular or gzip file -- with host memory
-    bounded by a ring of pinned chunks; the records are found and packed on the device.  Iterating yields ``ReadBlock``s
+    bounded by a ring of pinned chunks; the records are found and packed on the device, and the members of a BGZF file
+    (bgzip, htslib) are inflated there too (``info["members_device"]`` / ``["members_host"]`` per file say where; other
+    gzip members go through zlib in the reader thread, ``VS_BGZF_DEVICE=0`` sends all of them there).  Iterating yields ``ReadBlock``s
     of at most ``block_pairs`` pairs until the input is exhausted; the checks of the whole input (bytes that are not valid
     UTF-8 anywhere, a cut-off gzip stream) raise before the iteration ends, with the exceptions ``FastqPair`` raises.
     ``close()`` as ``FastqPair``."""
@@ -241,7 +243,10 @@ class FastqStream:
     def info(self):
         a = (C.c_uint64 * 4)()
         nat.lib().vs_fastq_stream_info(self._h, a)
-        return dict(pairs=int(a[0]), text_bytes=int(a[1]), file_bytes=int(a[2]), flags=int(a[3]))
+        m = (C.c_uint64 * 4)()
+        nat.lib().vs_fastq_stream_inflate_info(self._h, m)
+        return dict(pairs=int(a[0]), text_bytes=int(a[1]), file_bytes=int(a[2]), flags=int(a[3]),
+                    members_device=(int(m[0]), int(m[2])), members_host=(int(m[1]), int(m[3])))
 
     @property
     def n_pairs(self) -> int:
@@ -274,6 +279,56 @@ class FastqStream:
             self.close()
         except Exception:
             pass
+
+
+INFLATE_GUARD = 64  # bytes kept behind every member's output by the inflate test aids; they must stay INFLATE_GUARD_BYTE
+INFLATE_GUARD_BYTE = 0xA5
+
+
+def bgzf_walk(data: bytes):
+    """The whole BGZF members at the front of ``data`` (``vs_bgzf_walk``, host only): (list of (payload offset, payload
+    length, ISIZE, CRC32), offset of the first byte that is not part of one, what is there: 0 nothing, 1 "need more
+    bytes", 2 "not BGZF")."""
+    buf = np.frombuffer(data or b"\0", dtype=np.uint8)
+    info = (C.c_uint64 * 3)()
+    rc = nat.lib().vs_bgzf_walk(buf.ctypes.data, len(data), None, 0, info)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_bgzf_walk")
+    mem = np.zeros((max(int(info[0]), 1), 4), dtype=np.uint64)
+    nat.lib().vs_bgzf_walk(buf.ctypes.data, len(data), mem.ctypes.data, int(info[0]), info)
+    return [tuple(int(x) for x in row) for row in mem[: int(info[0])]], int(info[1]), int(info[2])
+
+
+def inflate_host(payload: bytes, isize: int, crc: int):
+    """One raw deflate payload through the host form of the device decoder (``vs_inflate_host``): (status word, the
+    ``isize`` output bytes, whether the guard bytes behind them are untouched)."""
+    src = np.frombuffer(payload or b"\0", dtype=np.uint8)
+    out = np.full(isize + INFLATE_GUARD, INFLATE_GUARD_BYTE, dtype=np.uint8)
+    status = C.c_uint32(0xFFFFFFFF)
+    rc = nat.lib().vs_inflate_host(src.ctypes.data, len(payload), out.ctypes.data, isize, crc & 0xFFFFFFFF, C.byref(status))
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_inflate_host")
+    return int(status.value), out[:isize].tobytes(), bool((out[isize:] == INFLATE_GUARD_BYTE).all())
+
+
+def inflate_bgzf(data: bytes, ctx: "Context"):
+    """Whole BGZF members through the device kernel (``vs_inflate_bgzf``): per member (status word, output bytes, whether
+    the guard bytes behind its output are untouched)."""
+    src = np.frombuffer(data or b"\0", dtype=np.uint8)
+    info = (C.c_uint64 * 2)()
+    nat.check(ctx._h, nat.lib().vs_inflate_bgzf(ctx._h, src.ctypes.data, len(data), None, 0, INFLATE_GUARD, None, 0, info))
+    n, total = int(info[0]), int(info[1])
+    out = np.zeros(max(total, 1), dtype=np.uint8)
+    status = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
+    nat.check(ctx._h, nat.lib().vs_inflate_bgzf(ctx._h, src.ctypes.data, len(data), out.ctypes.data, total, INFLATE_GUARD,
+                                                status.ctypes.data, n, info))
+    members, _, _ = bgzf_walk(data)
+    res, at = [], 0
+    for i, (_, _, isize, _) in enumerate(members):
+        guard = out[at + isize: at + isize + INFLATE_GUARD]
+        res.append((int(status[i]), out[at: at + isize].tobytes(), bool((guard == INFLATE_GUARD_BYTE).all())))
+        at += isize + INFLATE_GUARD
+    return res
 
 
 def encode_seqs(seqs: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:

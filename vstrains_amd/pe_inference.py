@@ -73,10 +73,36 @@ def _regular(path: str) -> bool:
         return True  # (a missing file: the mapped open names it)
 
 
+def _starts_bgzf(path: str) -> bool:
+    """The first bytes of a regular file are the header of a BGZF member (gzip with FEXTRA only and a ``BC`` subfield)."""
+    try:
+        if not stat.S_ISREG(os.stat(path).st_mode):
+            return False
+        with open(path, "rb") as fh:
+            head = fh.read(12)
+            if len(head) < 12 or head[:4] != b"\x1f\x8b\x08\x04":
+                return False
+            extra = fh.read(head[10] | (head[11] << 8))
+    except OSError:
+        return False  # (missing or unreadable: the mapped open names it)
+    at = 0
+    while at + 4 <= len(extra):
+        slen = extra[at + 2] | (extra[at + 3] << 8)
+        if extra[at:at + 2] == b"BC" and slen == 2:
+            return True
+        at += 4 + slen
+    return False
+
+
 def use_stream(fwd: str, rve: str) -> bool:
     """The streamed ingest reads the pair when either input is not a regular file (a FIFO, /dev/stdin, a process
-    substitution: there is nothing to map), or when ``VS_FASTQ_STREAM=1`` asks for it; regular files are mapped."""
-    return os.environ.get("VS_FASTQ_STREAM") == "1" or not (_regular(fwd) and _regular(rve))
+    substitution: there is nothing to map), when ``VS_FASTQ_STREAM=1`` asks for it, or when both are regular files and at
+    least one starts with a BGZF member (its members are inflated on the device there, where the mapped open inflates the
+    whole file on one host core) unless ``VS_FASTQ_STREAM=0``; other regular files are mapped."""
+    env = os.environ.get("VS_FASTQ_STREAM")
+    if env == "1" or not (_regular(fwd) and _regular(rve)):
+        return True
+    return env != "0" and (_starts_bgzf(fwd) or _starts_bgzf(rve))
 
 
 def count_stream(ctx, fs, counter, progress: bool = False):
