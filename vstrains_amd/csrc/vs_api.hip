@@ -3,6 +3,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <utility>
 
 #include "vs_internal.h"
 
@@ -47,30 +48,27 @@ void vs_tuning_load(VsTuning &t, bool experiment) {
 void *vs_cache_alloc(vs_ctx *ctx, size_t bytes) {
     if (!bytes) bytes = 16;
     for (auto &b : ctx->cache)
-        if (!b.used && b.cap >= bytes && b.cap <= 2 * bytes + (1u << 20)) {
+        if (!b.used && b.buf.capacity() >= bytes && b.buf.capacity() <= 2 * bytes + (1u << 20)) {
             b.used = true;
-            return b.p;
+            return b.buf.ptr();
         }
-    void *p = nullptr;
-    const size_t cap = bytes + bytes / 8;  // (blocks of one file differ a little in size)
-    if (hipMalloc(&p, cap) != hipSuccess) return nullptr;
-    ctx->cache.push_back({p, cap, true});
-    return p;
+    VsDevBuf buf;
+    if (buf.reserve(bytes, bytes + bytes / 8) != hipSuccess) return nullptr;  // (blocks of one file differ a little in size)
+    ctx->cache.push_back({std::move(buf), true});
+    return ctx->cache.back().buf.ptr();
 }
 
 void vs_cache_release(vs_ctx *ctx, void *p) {
     if (!p) return;
     size_t idle = 0;
     for (auto &b : ctx->cache)
-        if (b.p == p) b.used = false;
+        if (b.buf.ptr() == p) b.used = false;
     for (auto &b : ctx->cache)
         if (!b.used) idle++;
     if (idle > 24) {  // do not hoard: drop the idle ones
         std::vector<vs_ctx::CachedBuf> keep;
-        for (auto &b : ctx->cache) {
-            if (b.used) keep.push_back(b);
-            else (void)hipFree(b.p);
-        }
+        for (auto &b : ctx->cache)
+            if (b.used) keep.push_back(std::move(b));
         ctx->cache.swap(keep);
     }
 }
@@ -117,11 +115,10 @@ int vs_ctx_create(int device, vs_ctx **out) {
 }
 
 static void free_index(vs_ctx *ctx) {
-    void **ps[] = {&ctx->d_meta, &ctx->d_fwd, &ctx->d_rc, &ctx->d_table, &ctx->d_post};
-    for (void **p : ps) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
+    ctx->d_meta.reset();
+    ctx->d_fwd.reset();
+    ctx->d_table.reset();
+    ctx->d_post.reset();
     ctx->has_index = false;
     ctx->index_bytes = 0;
 }
@@ -132,27 +129,13 @@ void vs_ctx_destroy(vs_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    free_index(ctx);
-    if (ctx->d_slow_list) (void)hipFree(ctx->d_slow_list);
-    if (ctx->d_slow_count) (void)hipFree(ctx->d_slow_count);
-    if (ctx->links_spare) (void)hipFree(ctx->links_spare);
-    if (ctx->d_slow_list2) (void)hipFree(ctx->d_slow_list2);
-    if (ctx->d_dense) (void)hipFree(ctx->d_dense);
-    for (void *q : {ctx->d_locus_keys, ctx->d_perm, ctx->d_locus_hist, ctx->d_scan_tmp, ctx->d_lists, ctx->d_list_counts, ctx->d_rows, ctx->d_row_entries, ctx->d_mult, ctx->d_ltab})
-        if (q) (void)hipFree(q);
-    for (void *q : ctx->scratch)
-        if (q) (void)hipFree(q);
-    for (auto &b : ctx->cache) (void)hipFree(b.p);
     for (FqStage &st : ctx->fq_stage) {
         if (st.in_flight && st.done) (void)hipEventSynchronize(st.done);
-        if (st.words) (void)hipHostFree(st.words);
-        if (st.woff) (void)hipHostFree(st.woff);
-        if (st.meta) (void)hipHostFree(st.meta);
         if (st.done) (void)hipEventDestroy(st.done);
     }
     for (int i = 0; i < 5; i++)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    delete ctx;
+    delete ctx;  // (every buffer the context owns goes with it)
 }
 
 int vs_ctx_set_stream(vs_ctx *ctx, void *stream) {

@@ -726,16 +726,8 @@ int vs_fastq_block(vs_ctx *ctx, vs_fastq *fq, uint64_t first, uint64_t count, vs
     }
     const unsigned T = n_threads();
     // words per thread range -> word offset of every end
-    if (st.ends_cap < n_ends + 1) {
-        if (st.woff) VS_HIP(ctx, hipHostFree(st.woff));
-        if (st.meta) VS_HIP(ctx, hipHostFree(st.meta));
-        st.woff = st.meta = nullptr;
-        st.ends_cap = 0;
-        const size_t cap = n_ends + n_ends / 8 + 16;
-        VS_HIP(ctx, hipHostMalloc((void **)&st.woff, sizeof(uint32_t) * cap, hipHostMallocDefault));
-        VS_HIP(ctx, hipHostMalloc((void **)&st.meta, sizeof(uint32_t) * cap, hipHostMallocDefault));
-        st.ends_cap = cap;
-    }
+    VS_HIP(ctx, st.woff.reserve(sizeof(uint32_t) * (n_ends + 1), sizeof(uint32_t) * (n_ends + n_ends / 8 + 16)));
+    VS_HIP(ctx, st.meta.reserve(sizeof(uint32_t) * (n_ends + 1), sizeof(uint32_t) * (n_ends + n_ends / 8 + 16)));
     std::vector<uint64_t> part_words(T + 1, 0);
     std::vector<uint32_t> part_max(T, 0);
     parallel_for(T, [&](unsigned p) {
@@ -753,14 +745,8 @@ int vs_fastq_block(vs_ctx *ctx, vs_fastq *fq, uint64_t first, uint64_t count, vs
     for (unsigned p = 0; p < T; p++) part_words[p + 1] += part_words[p];
     const uint64_t words = part_words[T];
     if (words > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "vs_fastq_block: block exceeds 2^32 packed words");
-    if (st.words_cap < words + VS_PAD_WORDS) {
-        if (st.words) VS_HIP(ctx, hipHostFree(st.words));
-        st.words = nullptr;
-        st.words_cap = 0;
-        const size_t cap = words + words / 8 + VS_PAD_WORDS;
-        VS_HIP(ctx, hipHostMalloc((void **)&st.words, sizeof(uint32_t) * cap, hipHostMallocDefault));
-        st.words_cap = cap;
-    }
+    VS_HIP(ctx, st.words.reserve(sizeof(uint32_t) * (words + VS_PAD_WORDS), sizeof(uint32_t) * (words + words / 8 + VS_PAD_WORDS)));
+    uint32_t *const h_words = st.words.as<uint32_t>(), *const h_woff = st.woff.as<uint32_t>(), *const h_meta = st.meta.as<uint32_t>();
     std::vector<uint32_t> part_flags(T, 0);
     parallel_for(T, [&](unsigned p) {
         uint64_t lo = count * p / T, hi = count * (p + 1) / T;
@@ -770,16 +756,16 @@ int vs_fastq_block(vs_ctx *ctx, vs_fastq *fq, uint64_t first, uint64_t count, vs
             for (int w2 = 0; w2 < 2; w2++) {
                 const FqFile &f = fq->f[w2];
                 const uint32_t l = f.seq_len[first + r];
-                const uint32_t fl = pack_sequence(f.text() + f.seq_start[first + r], l, st.words + wat);
-                st.woff[2 * r + w2] = (uint32_t)wat;
-                st.meta[2 * r + w2] = l | (fl << 24);
+                const uint32_t fl = pack_sequence(f.text() + f.seq_start[first + r], l, h_words + wat);
+                h_woff[2 * r + w2] = (uint32_t)wat;
+                h_meta[2 * r + w2] = l | (fl << 24);
                 any |= fl;
                 wat += (l + 15u) >> 4;
             }
         part_flags[p] = any;
     });
-    st.woff[n_ends] = (uint32_t)words;
-    for (uint32_t i = 0; i < VS_PAD_WORDS; i++) st.words[words + i] = 0u;
+    h_woff[n_ends] = (uint32_t)words;
+    for (uint32_t i = 0; i < VS_PAD_WORDS; i++) h_words[words + i] = 0u;
     uint32_t any = 0, maxlen = 0;
     for (unsigned p = 0; p < T; p++) { any |= part_flags[p]; maxlen = part_max[p] > maxlen ? part_max[p] : maxlen; }
     if (any & (VS_FLAG_INVALID | 0x80u)) {
@@ -809,9 +795,9 @@ int vs_fastq_block(vs_ctx *ctx, vs_fastq *fq, uint64_t first, uint64_t count, vs
         vs_reads_free(ctx, r);
         return vs_fail(ctx, VS_E_OOM, "vs_fastq_block: device buffers for %llu ends", (unsigned long long)n_ends);
     }
-    hipError_t e1 = hipMemcpyAsync(r->d_woff, st.woff, b_woff, hipMemcpyHostToDevice, ctx->stream);
-    if (e1 == hipSuccess && n_ends) e1 = hipMemcpyAsync(r->d_meta, st.meta, sizeof(uint32_t) * n_ends, hipMemcpyHostToDevice, ctx->stream);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(r->d_words, st.words, b_words, hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e1 = hipMemcpyAsync(r->d_woff, h_woff, b_woff, hipMemcpyHostToDevice, ctx->stream);
+    if (e1 == hipSuccess && n_ends) e1 = hipMemcpyAsync(r->d_meta, h_meta, sizeof(uint32_t) * n_ends, hipMemcpyHostToDevice, ctx->stream);
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(r->d_words, h_words, b_words, hipMemcpyHostToDevice, ctx->stream);
     if (e1 == hipSuccess) e1 = hipEventRecord(st.done, ctx->stream);
     if (e1 != hipSuccess) {
         vs_reads_free(ctx, r);

@@ -12,18 +12,19 @@
 #include <string.h>
 #include <time.h>
 
+#include <utility>
 #include <vector>
 
 struct vs_links {
     uint32_t n = 0;
-    int64_t *d_p0 = nullptr;  // [n*n] symmetric; diagonal = node[i][i] + short[i][i]  (dense form)
+    VsDevBuf d_p0;  // int64 [n*n] symmetric; diagonal = node[i][i] + short[i][i]  (dense form)
     // sparse form (r6, graphs of 2^15 nodes and more whose counters keep a dirty-tile map): CSR rows of the non-zero cells,
     // columns ascending inside a row -- 0.4 GB instead of 23.7 GB at 54 465 nodes (1.2 % of the cells are non-zero)
-    uint32_t *d_row_ptr = nullptr;  // [n + 1]
-    uint32_t *d_col = nullptr;      // [nnz]
-    int64_t *d_val = nullptr;       // [nnz]
+    VsDevBuf d_row_ptr;  // uint32 [n + 1]
+    VsDevBuf d_col;      // uint32 [nnz]
+    VsDevBuf d_val;      // int64 [nnz]
     uint64_t nnz = 0;
-    bool sparse() const { return d_row_ptr != nullptr; }
+    bool sparse() const { return d_row_ptr.ptr() != nullptr; }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -581,40 +582,22 @@ __global__ void __launch_bounds__(256) k_edge_flow(uint32_t nv, const uint64_t *
 // host entry points
 // =============================================================================================
 namespace {
-// A view of one of the context's grow-only scratch slots: the graph stages call these entry
+// The next of the context's grow-only scratch slots, at least `bytes` large: the graph stages call these entry
 // points hundreds of times per run with similar sizes, so nothing is allocated after warm-up.
-struct DevBuf {
-    void *p = nullptr;
-    template <typename T>
-    T *as() { return (T *)p; }
-};
-
-int slot_reserve(vs_ctx *ctx, int slot, DevBuf &b, size_t bytes) {
+int dev_alloc(vs_ctx *ctx, int &slot, VsDevBuf *&b, size_t bytes) {
     if (bytes < 16) bytes = 16;
-    if (ctx->scratch_cap[slot] < bytes) {
-        VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch[slot]) VS_HIP(ctx, hipFree(ctx->scratch[slot]));
-        ctx->scratch[slot] = nullptr;
-        ctx->scratch_cap[slot] = 0;
-        size_t cap = bytes + bytes / 2;
-        VS_HIP(ctx, hipMalloc(&ctx->scratch[slot], cap));
-        ctx->scratch_cap[slot] = cap;
-    }
-    b.p = ctx->scratch[slot];
+    b = &ctx->scratch[slot++];
+    if (b->capacity() < bytes) VS_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the device may still use the old block)
+    VS_HIP(ctx, b->reserve(bytes, bytes + bytes / 2));
     return VS_OK;
 }
 
-struct SlotCounter {
-    int next = 0;
-};
-
-int dev_upload(vs_ctx *ctx, SlotCounter &sc, DevBuf &b, const void *host, size_t bytes) {
-    int rc = slot_reserve(ctx, sc.next++, b, bytes);
+int dev_upload(vs_ctx *ctx, int &slot, VsDevBuf *&b, const void *host, size_t bytes) {
+    int rc = dev_alloc(ctx, slot, b, bytes);
     if (rc) return rc;
-    if (bytes) VS_HIP(ctx, hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (bytes) VS_HIP(ctx, hipMemcpyAsync(b->ptr(), host, bytes, hipMemcpyHostToDevice, ctx->stream));
     return VS_OK;
 }
-int dev_alloc(vs_ctx *ctx, SlotCounter &sc, DevBuf &b, size_t bytes) { return slot_reserve(ctx, sc.next++, b, bytes); }
 #define VS_TRY(x)            \
     do {                     \
         int rc__ = (x);      \
@@ -634,13 +617,12 @@ int links_build(vs_ctx *ctx, const TIn *d_node, const TIn *d_short, uint32_t n, 
     if (timing) (void)hipStreamSynchronize(ctx->stream);
     const double t0 = now();
     hipError_t e = hipSuccess;
-    const bool reserved = ctx->links_spare && ctx->links_spare_n == n && n;
+    const bool reserved = ctx->links_spare.ptr() && ctx->links_spare_n == n && n;
     if (reserved) {  // vs_links_reserve set it aside
-        L->d_p0 = (int64_t *)ctx->links_spare;
-        ctx->links_spare = nullptr;
+        L->d_p0 = std::move(ctx->links_spare);
         ctx->links_spare_n = 0;
     } else {
-        e = hipMalloc((void **)&L->d_p0, (size_t)(n ? (uint64_t)n * n : 1) * sizeof(int64_t));
+        e = L->d_p0.reserve((size_t)(n ? (uint64_t)n * n : 1) * sizeof(int64_t));
     }
     const double t1 = now();
     if (e != hipSuccess) {
@@ -651,10 +633,9 @@ int links_build(vs_ctx *ctx, const TIn *d_node, const TIn *d_short, uint32_t n, 
         uint32_t tiles = (n + SYM_T - 1) / SYM_T;
         uint64_t pairs = (uint64_t)tiles * (tiles + 1) / 2;
         hipLaunchKernelGGL((k_links_symmetrize<TIn>), dim3((unsigned)pairs), dim3(256), 0, ctx->stream, d_node, d_short, n,
-                           tiles, L->d_p0);
+                           tiles, L->d_p0.as<int64_t>());
         e = hipGetLastError();
         if (e != hipSuccess) {
-            (void)hipFree(L->d_p0);
             delete L;
             return vs_fail(ctx, VS_E_HIP, "k_links_symmetrize: %s", hipGetErrorString(e));
         }
@@ -662,7 +643,7 @@ int links_build(vs_ctx *ctx, const TIn *d_node, const TIn *d_short, uint32_t n, 
     if (timing) {
         (void)hipStreamSynchronize(ctx->stream);
         fprintf(stderr, "[vs] link table of %u nodes: %.2f GB %s %.4f s, k_links_symmetrize %.4f s\n", n, (double)n * n * 8 / 1e9,
-                reserved ? "taken from vs_links_reserve" : "hipMalloc", t1 - t0, now() - t1);
+                reserved ? "taken from vs_links_reserve" : "allocation", t1 - t0, now() - t1);
     }
     *out = L;
     return VS_OK;
@@ -674,43 +655,40 @@ int links_build_sparse(vs_ctx *ctx, const TIn *d_node, const TIn *d_short, uint3
     L->n = n;
     const uint32_t T = (n + SL_T - 1u) / SL_T;
     const uint64_t pairs = (uint64_t)T * (T + 1u) / 2u;
-    uint8_t *d_cnt = nullptr;
-    uint32_t *d_piece = nullptr, *d_total = nullptr;
-    uint64_t *d_scan_tmp = nullptr, *d_sum = nullptr;
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_cnt, (void *)d_piece, (void *)d_total, (void *)d_scan_tmp, (void *)d_sum})
-            if (q) (void)hipFree(q);
+    VsDevBuf cnt_buf, piece_buf, total_buf, scan_tmp_buf, sum_buf;  // (die with the call)
+    const auto on_device = [&]() -> int {
+        VS_HIP(ctx, cnt_buf.reserve((size_t)n * T));
+        VS_HIP(ctx, piece_buf.reserve((size_t)n * T * sizeof(uint32_t)));
+        VS_HIP(ctx, total_buf.reserve(((size_t)n + 2u) * sizeof(uint32_t)));
+        VS_HIP(ctx, L->d_row_ptr.reserve(((size_t)n + 2u) * sizeof(uint32_t)));
+        VS_HIP(ctx, scan_tmp_buf.reserve(((size_t)n / 2048u + 8u) * sizeof(uint64_t)));
+        VS_HIP(ctx, sum_buf.reserve(sizeof(uint64_t)));
+        uint8_t *d_cnt = cnt_buf.as<uint8_t>();
+        uint32_t *d_piece = piece_buf.as<uint32_t>(), *d_total = total_buf.as<uint32_t>(), *d_row_ptr = L->d_row_ptr.as<uint32_t>();
+        uint64_t *d_sum = sum_buf.as<uint64_t>();
+        VS_HIP(ctx, hipMemsetAsync(d_cnt, 0, (size_t)n * T, ctx->stream));
+        VS_HIP(ctx, hipMemsetAsync(d_total, 0, ((size_t)n + 2u) * sizeof(uint32_t), ctx->stream));
+        hipLaunchKernelGGL((k_sl_count<TIn>), dim3((unsigned)pairs), dim3(256), 0, ctx->stream, d_node, d_short, d_tile_map, n, T, d_cnt);
+        hipLaunchKernelGGL(k_sl_rows, dim3((n + 3u) / 4u), dim3(256), 0, ctx->stream, (const uint8_t *)d_cnt, n, T, d_piece, d_total);
+        if (int rc = vs_scan_u32(ctx, d_total, d_row_ptr, (uint64_t)n + 1u, scan_tmp_buf.as<uint64_t>(), d_sum)) return rc;
+        uint64_t nnz = 0;
+        VS_HIP(ctx, hipMemcpyAsync(&nnz, d_sum, sizeof nnz, hipMemcpyDeviceToHost, ctx->stream));
+        VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (nnz > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "vs_links (sparse): %llu non-zero cells", (unsigned long long)nnz);
+        L->nnz = nnz;
+        VS_HIP(ctx, L->d_col.reserve((size_t)(nnz + 1u) * sizeof(uint32_t)));
+        VS_HIP(ctx, L->d_val.reserve((size_t)(nnz + 1u) * sizeof(int64_t)));
+        hipLaunchKernelGGL((k_sl_fill<TIn>), dim3((unsigned)pairs), dim3(256), 0, ctx->stream, d_node, d_short, d_tile_map, n, T, (const uint32_t *)d_piece,
+                           (const uint32_t *)d_row_ptr, L->d_col.as<uint32_t>(), L->d_val.as<int64_t>());
+        VS_HIP(ctx, hipGetLastError());
+        VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return VS_OK;
     };
-    auto fail = [&](int code, const char *what, hipError_t e) {
-        cleanup();
+    if (int rc = on_device()) {
         vs_links_free(ctx, L);
-        return vs_fail(ctx, code, "vs_links (sparse): %s: %s", what, hipGetErrorString(e));
-    };
-    hipError_t e;
-    if ((e = hipMalloc((void **)&d_cnt, (size_t)n * T)) != hipSuccess) return fail(VS_E_OOM, "piece counts", e);
-    if ((e = hipMalloc((void **)&d_piece, (size_t)n * T * sizeof(uint32_t))) != hipSuccess) return fail(VS_E_OOM, "piece offsets", e);
-    if ((e = hipMalloc((void **)&d_total, ((size_t)n + 2u) * sizeof(uint32_t))) != hipSuccess) return fail(VS_E_OOM, "row totals", e);
-    if ((e = hipMalloc((void **)&L->d_row_ptr, ((size_t)n + 2u) * sizeof(uint32_t))) != hipSuccess) return fail(VS_E_OOM, "row_ptr", e);
-    if ((e = hipMalloc((void **)&d_scan_tmp, ((size_t)n / 2048u + 8u) * sizeof(uint64_t))) != hipSuccess) return fail(VS_E_OOM, "scan", e);
-    if ((e = hipMalloc((void **)&d_sum, sizeof(uint64_t))) != hipSuccess) return fail(VS_E_OOM, "sum", e);
-    if ((e = hipMemsetAsync(d_cnt, 0, (size_t)n * T, ctx->stream)) != hipSuccess) return fail(VS_E_HIP, "memset", e);
-    if ((e = hipMemsetAsync(d_total, 0, ((size_t)n + 2u) * sizeof(uint32_t), ctx->stream)) != hipSuccess) return fail(VS_E_HIP, "memset", e);
-    hipLaunchKernelGGL((k_sl_count<TIn>), dim3((unsigned)pairs), dim3(256), 0, ctx->stream, d_node, d_short, d_tile_map, n, T, d_cnt);
-    hipLaunchKernelGGL(k_sl_rows, dim3((n + 3u) / 4u), dim3(256), 0, ctx->stream, (const uint8_t *)d_cnt, n, T, d_piece, d_total);
-    int rc = vs_scan_u32(ctx, d_total, L->d_row_ptr, (uint64_t)n + 1u, d_scan_tmp, d_sum);
-    if (rc) { cleanup(); vs_links_free(ctx, L); return rc; }
-    uint64_t nnz = 0;
-    if ((e = hipMemcpyAsync(&nnz, d_sum, sizeof nnz, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return fail(VS_E_HIP, "copy", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(VS_E_HIP, "count pass", e);
-    if (nnz > 0xFFFFFFF0ull) { cleanup(); vs_links_free(ctx, L); return vs_fail(ctx, VS_E_RANGE, "vs_links (sparse): %llu non-zero cells", (unsigned long long)nnz); }
-    L->nnz = nnz;
-    if ((e = hipMalloc((void **)&L->d_col, (size_t)(nnz + 1u) * sizeof(uint32_t))) != hipSuccess) return fail(VS_E_OOM, "columns", e);
-    if ((e = hipMalloc((void **)&L->d_val, (size_t)(nnz + 1u) * sizeof(int64_t))) != hipSuccess) return fail(VS_E_OOM, "values", e);
-    hipLaunchKernelGGL((k_sl_fill<TIn>), dim3((unsigned)pairs), dim3(256), 0, ctx->stream, d_node, d_short, d_tile_map, n, T, (const uint32_t *)d_piece,
-                       (const uint32_t *)L->d_row_ptr, L->d_col, L->d_val);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(VS_E_HIP, "k_sl_fill", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(VS_E_HIP, "fill pass", e);
-    cleanup();
+        return rc;
+    }
+    const uint64_t nnz = L->nnz;
     if (getenv("VS_LINKS_TIMING"))
         fprintf(stderr, "[vs] link table of %u nodes held as CSR rows: %llu non-zero cells, %.3f GB (dense: %.2f GB)\n", n, (unsigned long long)nnz,
                 (double)nnz * 12 / 1e9, (double)n * n * 8 / 1e9);
@@ -724,19 +702,15 @@ extern "C" {
 int vs_links_reserve(vs_ctx *ctx, uint32_t n) {
     if (!ctx) return VS_E_ARG;
     VS_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->links_spare && ctx->links_spare_n == n) return VS_OK;
-    if (ctx->links_spare) {
+    if (ctx->links_spare.ptr() && ctx->links_spare_n == n) return VS_OK;
+    if (ctx->links_spare.ptr()) {
         VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->links_spare);
-        ctx->links_spare = nullptr;
+        ctx->links_spare.reset();
         ctx->links_spare_n = 0;
     }
     if (!n) return VS_OK;
-    const hipError_t e = hipMalloc(&ctx->links_spare, (size_t)n * n * sizeof(int64_t));
-    if (e != hipSuccess) {
-        ctx->links_spare = nullptr;
-        return vs_fail(ctx, VS_E_OOM, "vs_links_reserve: %.2f GB: %s", (double)n * n * 8 / 1e9, hipGetErrorString(e));
-    }
+    const hipError_t e = ctx->links_spare.reserve((size_t)n * n * sizeof(int64_t));
+    if (e != hipSuccess) return vs_fail(ctx, VS_E_OOM, "vs_links_reserve: %.2f GB: %s", (double)n * n * 8 / 1e9, hipGetErrorString(e));
     ctx->links_spare_n = n;
     return VS_OK;
 }
@@ -753,10 +727,9 @@ int vs_links_from_counts_tracked(vs_ctx *ctx, const uint32_t *d_node_mat, const 
     VS_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t min_nodes = sparse_min_nodes ? sparse_min_nodes : VS_LINKS_SPARSE_MIN;
     if (!d_tile_map || n < min_nodes || n < SL_T) return links_build<uint32_t>(ctx, d_node_mat, d_short_mat, n, out);
-    if (ctx->links_spare) {  // (a dense buffer set aside earlier is not needed: give it back)
+    if (ctx->links_spare.ptr()) {  // (a dense buffer set aside earlier is not needed: give it back)
         VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->links_spare);
-        ctx->links_spare = nullptr;
+        ctx->links_spare.reset();
         ctx->links_spare_n = 0;
     }
     return links_build_sparse<uint32_t>(ctx, d_node_mat, d_short_mat, n, d_tile_map, out);
@@ -771,12 +744,12 @@ int vs_links_from_wide(vs_ctx *ctx, const int64_t *d_node_mat, const int64_t *d_
 int vs_links_from_host(vs_ctx *ctx, const int64_t *node_mat, const int64_t *short_mat, uint32_t n, vs_links **out) {
     if (!ctx || !out || (n && (!node_mat || !short_mat))) return vs_fail(ctx, VS_E_ARG, "vs_links_from_host: bad argument");
     VS_HIP(ctx, hipSetDevice(ctx->device));
-    SlotCounter sc;
-    DevBuf a, b;
+    int slot = 0;
+    VsDevBuf *a, *b;
     size_t bytes = (size_t)n * n * sizeof(int64_t);
-    VS_TRY(dev_upload(ctx, sc, a, node_mat, bytes));
-    VS_TRY(dev_upload(ctx, sc, b, short_mat, bytes));
-    int rc = links_build<int64_t>(ctx, a.as<int64_t>(), b.as<int64_t>(), n, out);
+    VS_TRY(dev_upload(ctx, slot, a, node_mat, bytes));
+    VS_TRY(dev_upload(ctx, slot, b, short_mat, bytes));
+    int rc = links_build<int64_t>(ctx, a->as<int64_t>(), b->as<int64_t>(), n, out);
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return rc;
 }
@@ -787,10 +760,6 @@ void vs_links_free(vs_ctx *ctx, vs_links *links) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    if (links->d_p0) (void)hipFree(links->d_p0);
-    if (links->d_row_ptr) (void)hipFree(links->d_row_ptr);
-    if (links->d_col) (void)hipFree(links->d_col);
-    if (links->d_val) (void)hipFree(links->d_val);
     delete links;
 }
 
@@ -807,10 +776,10 @@ int vs_links_to_host(vs_ctx *ctx, const vs_links *links, int64_t *out) {
         const uint32_t n = links->n;
         std::vector<uint32_t> rp((size_t)n + 1u), col((size_t)links->nnz);
         std::vector<int64_t> val((size_t)links->nnz);
-        VS_HIP(ctx, hipMemcpyAsync(rp.data(), links->d_row_ptr, rp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VS_HIP(ctx, hipMemcpyAsync(rp.data(), links->d_row_ptr.ptr(), rp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         if (links->nnz) {
-            VS_HIP(ctx, hipMemcpyAsync(col.data(), links->d_col, col.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VS_HIP(ctx, hipMemcpyAsync(val.data(), links->d_val, val.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+            VS_HIP(ctx, hipMemcpyAsync(col.data(), links->d_col.ptr(), col.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VS_HIP(ctx, hipMemcpyAsync(val.data(), links->d_val.ptr(), val.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
         }
         VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         memset(out, 0, (size_t)n * n * sizeof(int64_t));
@@ -818,7 +787,7 @@ int vs_links_to_host(vs_ctx *ctx, const vs_links *links, int64_t *out) {
             for (uint32_t i = rp[r]; i < rp[r + 1]; i++) out[(size_t)r * n + col[i]] = val[i];
         return VS_OK;
     }
-    VS_HIP(ctx, hipMemcpyAsync(out, links->d_p0, (size_t)links->n * links->n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipMemcpyAsync(out, links->d_p0.as<int64_t>(), (size_t)links->n * links->n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VS_OK;
 }
@@ -841,24 +810,24 @@ int vs_links_block_sums(vs_ctx *ctx, const vs_links *links, const uint64_t *list
     for (uint64_t q = 0; q < n_queries; q++)
         if (qa[q] >= n_lists || qb[q] >= n_lists) return vs_fail(ctx, VS_E_RANGE, "query %llu names a list out of range", (unsigned long long)q);
     VS_HIP(ctx, hipSetDevice(ctx->device));
-    SlotCounter sc;
-    DevBuf d_off, d_idx, d_qa, d_qb, d_out;
-    VS_TRY(dev_upload(ctx, sc, d_off, list_off, (size_t)(n_lists + 1) * sizeof(uint64_t)));
-    VS_TRY(dev_upload(ctx, sc, d_idx, list_idx, (size_t)list_off[n_lists] * sizeof(uint32_t)));
-    VS_TRY(dev_upload(ctx, sc, d_qa, qa, (size_t)n_queries * sizeof(uint32_t)));
-    VS_TRY(dev_upload(ctx, sc, d_qb, qb, (size_t)n_queries * sizeof(uint32_t)));
-    VS_TRY(dev_alloc(ctx, sc, d_out, (size_t)n_queries * sizeof(int64_t)));
+    int slot = 0;
+    VsDevBuf *d_off, *d_idx, *d_qa, *d_qb, *d_out;
+    VS_TRY(dev_upload(ctx, slot, d_off, list_off, (size_t)(n_lists + 1) * sizeof(uint64_t)));
+    VS_TRY(dev_upload(ctx, slot, d_idx, list_idx, (size_t)list_off[n_lists] * sizeof(uint32_t)));
+    VS_TRY(dev_upload(ctx, slot, d_qa, qa, (size_t)n_queries * sizeof(uint32_t)));
+    VS_TRY(dev_upload(ctx, slot, d_qb, qb, (size_t)n_queries * sizeof(uint32_t)));
+    VS_TRY(dev_alloc(ctx, slot, d_out, (size_t)n_queries * sizeof(int64_t)));
     const unsigned waves = 256 / VS_WAVE;
     if (links->sparse())
         hipLaunchKernelGGL(k_links_block_sums_csr, dim3((unsigned)((n_queries + waves - 1) / waves)), dim3(256), 0, ctx->stream,
-                           (const uint32_t *)links->d_row_ptr, (const uint32_t *)links->d_col, (const int64_t *)links->d_val, d_off.as<uint64_t>(),
-                           d_idx.as<uint32_t>(), d_qa.as<uint32_t>(), d_qb.as<uint32_t>(), n_queries, d_out.as<int64_t>());
+                           links->d_row_ptr.as<const uint32_t>(), links->d_col.as<const uint32_t>(), links->d_val.as<const int64_t>(), d_off->as<uint64_t>(),
+                           d_idx->as<uint32_t>(), d_qa->as<uint32_t>(), d_qb->as<uint32_t>(), n_queries, d_out->as<int64_t>());
     else
     hipLaunchKernelGGL(k_links_block_sums, dim3((unsigned)((n_queries + waves - 1) / waves)), dim3(256), 0, ctx->stream,
-                       links->d_p0, links->n, d_off.as<uint64_t>(), d_idx.as<uint32_t>(), d_qa.as<uint32_t>(),
-                       d_qb.as<uint32_t>(), n_queries, d_out.as<int64_t>());
+                       links->d_p0.as<int64_t>(), links->n, d_off->as<uint64_t>(), d_idx->as<uint32_t>(), d_qa->as<uint32_t>(),
+                       d_qb->as<uint32_t>(), n_queries, d_out->as<int64_t>());
     VS_HIP(ctx, hipGetLastError());
-    VS_HIP(ctx, hipMemcpyAsync(out, d_out.p, (size_t)n_queries * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipMemcpyAsync(out, d_out->ptr(), (size_t)n_queries * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VS_OK;
 }
@@ -877,22 +846,22 @@ int vs_links_group_matrix(vs_ctx *ctx, const vs_links *links, const uint64_t *li
         return vs_links_block_sums(ctx, links, list_off, list_idx, n_groups, qa.data(), qb.data(), qa.size(), out);
     }
     uint32_t n = links->n;
-    SlotCounter sc;
-    DevBuf d_off, d_idx, d_t, d_out;
-    VS_TRY(dev_upload(ctx, sc, d_off, list_off, (size_t)(n_groups + 1) * sizeof(uint64_t)));
-    VS_TRY(dev_upload(ctx, sc, d_idx, list_idx, (size_t)list_off[n_groups] * sizeof(uint32_t)));
-    VS_TRY(dev_alloc(ctx, sc, d_t, (size_t)n_groups * (n ? n : 1) * sizeof(int64_t)));
-    VS_TRY(dev_alloc(ctx, sc, d_out, (size_t)n_groups * n_groups * sizeof(int64_t)));
+    int slot = 0;
+    VsDevBuf *d_off, *d_idx, *d_t, *d_out;
+    VS_TRY(dev_upload(ctx, slot, d_off, list_off, (size_t)(n_groups + 1) * sizeof(uint64_t)));
+    VS_TRY(dev_upload(ctx, slot, d_idx, list_idx, (size_t)list_off[n_groups] * sizeof(uint32_t)));
+    VS_TRY(dev_alloc(ctx, slot, d_t, (size_t)n_groups * (n ? n : 1) * sizeof(int64_t)));
+    VS_TRY(dev_alloc(ctx, slot, d_out, (size_t)n_groups * n_groups * sizeof(int64_t)));
     if (n) {
-        hipLaunchKernelGGL(k_links_group_rows, dim3((n + 255) / 256, n_groups), dim3(256), 0, ctx->stream, links->d_p0, n,
-                           d_off.as<uint64_t>(), d_idx.as<uint32_t>(), d_t.as<int64_t>());
+        hipLaunchKernelGGL(k_links_group_rows, dim3((n + 255) / 256, n_groups), dim3(256), 0, ctx->stream, links->d_p0.as<int64_t>(), n,
+                           d_off->as<uint64_t>(), d_idx->as<uint32_t>(), d_t->as<int64_t>());
     }
     uint64_t pairs = (uint64_t)n_groups * n_groups;
     const unsigned waves = 256 / VS_WAVE;
     hipLaunchKernelGGL(k_links_group_cols, dim3((unsigned)((pairs + waves - 1) / waves)), dim3(256), 0, ctx->stream,
-                       d_t.as<int64_t>(), n, n_groups, d_off.as<uint64_t>(), d_idx.as<uint32_t>(), d_out.as<int64_t>());
+                       d_t->as<int64_t>(), n, n_groups, d_off->as<uint64_t>(), d_idx->as<uint32_t>(), d_out->as<int64_t>());
     VS_HIP(ctx, hipGetLastError());
-    VS_HIP(ctx, hipMemcpyAsync(out, d_out.p, (size_t)pairs * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipMemcpyAsync(out, d_out->ptr(), (size_t)pairs * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VS_OK;
 }
@@ -914,53 +883,53 @@ int vs_graph_refresh(vs_ctx *ctx, uint32_t n_vertices, uint32_t n_edge_slots, co
     for (uint64_t i = 0; i < n_adj; i++)
         if (nbr[i] >= n_vertices || eidx[i] >= n_edge_slots) return vs_fail(ctx, VS_E_RANGE, "vs_graph_refresh: adjacency entry %llu out of range", (unsigned long long)i);
     VS_HIP(ctx, hipSetDevice(ctx->device));
-    SlotCounter sc;
-    DevBuf d_row, d_no, d_nbr, d_eidx, d_dp, d_vb, d_eb, d_os, d_is, d_nt, d_fk, d_nx, d_pd, d_flow, d_bad;
-    DevBuf d_chain, d_top, d_rank, d_big;
-    VS_TRY(dev_upload(ctx, sc, d_row, row_ptr, (size_t)(n_vertices + 1) * sizeof(uint64_t)));
-    VS_TRY(dev_upload(ctx, sc, d_no, n_out, (size_t)n_vertices * sizeof(uint32_t)));
-    VS_TRY(dev_upload(ctx, sc, d_nbr, nbr, (size_t)n_adj * sizeof(uint32_t)));
-    VS_TRY(dev_upload(ctx, sc, d_eidx, eidx, (size_t)n_adj * sizeof(uint32_t)));
-    VS_TRY(dev_upload(ctx, sc, d_dp, dp, (size_t)n_vertices * sizeof(double)));
-    VS_TRY(dev_upload(ctx, sc, d_vb, vertex_black, (size_t)n_vertices));
-    VS_TRY(dev_upload(ctx, sc, d_eb, edge_black, (size_t)n_edge_slots));
-    VS_TRY(dev_alloc(ctx, sc, d_os, (size_t)n_vertices * sizeof(double)));
-    VS_TRY(dev_alloc(ctx, sc, d_is, (size_t)n_vertices * sizeof(double)));
-    VS_TRY(dev_alloc(ctx, sc, d_nt, n_vertices));
-    VS_TRY(dev_alloc(ctx, sc, d_fk, n_vertices));
-    VS_TRY(dev_alloc(ctx, sc, d_nx, (size_t)n_vertices * sizeof(int32_t)));
-    VS_TRY(dev_alloc(ctx, sc, d_pd, (size_t)n_vertices * sizeof(int32_t)));
-    VS_TRY(dev_alloc(ctx, sc, d_flow, (size_t)(n_edge_slots ? n_edge_slots : 1) * sizeof(double)));
-    VS_TRY(dev_alloc(ctx, sc, d_bad, sizeof(uint32_t)));
-    VS_TRY(dev_alloc(ctx, sc, d_big, (size_t)(n_vertices + 1) * sizeof(uint32_t)));
-    VS_HIP(ctx, hipMemsetAsync(d_big.p, 0, sizeof(uint32_t), ctx->stream));
+    int slot = 0;
+    VsDevBuf *d_row, *d_no, *d_nbr, *d_eidx, *d_dp, *d_vb, *d_eb, *d_os, *d_is, *d_nt, *d_fk, *d_nx, *d_pd, *d_flow, *d_bad;
+    VsDevBuf *d_chain, *d_top, *d_rank, *d_big;
+    VS_TRY(dev_upload(ctx, slot, d_row, row_ptr, (size_t)(n_vertices + 1) * sizeof(uint64_t)));
+    VS_TRY(dev_upload(ctx, slot, d_no, n_out, (size_t)n_vertices * sizeof(uint32_t)));
+    VS_TRY(dev_upload(ctx, slot, d_nbr, nbr, (size_t)n_adj * sizeof(uint32_t)));
+    VS_TRY(dev_upload(ctx, slot, d_eidx, eidx, (size_t)n_adj * sizeof(uint32_t)));
+    VS_TRY(dev_upload(ctx, slot, d_dp, dp, (size_t)n_vertices * sizeof(double)));
+    VS_TRY(dev_upload(ctx, slot, d_vb, vertex_black, (size_t)n_vertices));
+    VS_TRY(dev_upload(ctx, slot, d_eb, edge_black, (size_t)n_edge_slots));
+    VS_TRY(dev_alloc(ctx, slot, d_os, (size_t)n_vertices * sizeof(double)));
+    VS_TRY(dev_alloc(ctx, slot, d_is, (size_t)n_vertices * sizeof(double)));
+    VS_TRY(dev_alloc(ctx, slot, d_nt, n_vertices));
+    VS_TRY(dev_alloc(ctx, slot, d_fk, n_vertices));
+    VS_TRY(dev_alloc(ctx, slot, d_nx, (size_t)n_vertices * sizeof(int32_t)));
+    VS_TRY(dev_alloc(ctx, slot, d_pd, (size_t)n_vertices * sizeof(int32_t)));
+    VS_TRY(dev_alloc(ctx, slot, d_flow, (size_t)(n_edge_slots ? n_edge_slots : 1) * sizeof(double)));
+    VS_TRY(dev_alloc(ctx, slot, d_bad, sizeof(uint32_t)));
+    VS_TRY(dev_alloc(ctx, slot, d_big, (size_t)(n_vertices + 1) * sizeof(uint32_t)));
+    VS_HIP(ctx, hipMemsetAsync(d_big->ptr(), 0, sizeof(uint32_t), ctx->stream));
     const uint32_t chain_stride = (n_vertices + 3u) & ~3u;
-    VS_TRY(dev_alloc(ctx, sc, d_chain, (size_t)6 * chain_stride * sizeof(int32_t)));
-    VS_TRY(dev_alloc(ctx, sc, d_top, (size_t)n_vertices * sizeof(int32_t)));
-    VS_TRY(dev_alloc(ctx, sc, d_rank, (size_t)n_vertices * sizeof(int32_t)));
-    VS_HIP(ctx, hipMemsetAsync(d_bad.p, 0xFF, sizeof(uint32_t), ctx->stream));
-    VS_HIP(ctx, hipMemsetAsync(d_flow.p, 0, (size_t)(n_edge_slots ? n_edge_slots : 1) * sizeof(double), ctx->stream));
+    VS_TRY(dev_alloc(ctx, slot, d_chain, (size_t)6 * chain_stride * sizeof(int32_t)));
+    VS_TRY(dev_alloc(ctx, slot, d_top, (size_t)n_vertices * sizeof(int32_t)));
+    VS_TRY(dev_alloc(ctx, slot, d_rank, (size_t)n_vertices * sizeof(int32_t)));
+    VS_HIP(ctx, hipMemsetAsync(d_bad->ptr(), 0xFF, sizeof(uint32_t), ctx->stream));
+    VS_HIP(ctx, hipMemsetAsync(d_flow->ptr(), 0, (size_t)(n_edge_slots ? n_edge_slots : 1) * sizeof(double), ctx->stream));
     dim3 grid((n_vertices + 255) / 256), block(256);
-    hipLaunchKernelGGL(k_vertex_scan, grid, block, 0, ctx->stream, n_vertices, d_row.as<uint64_t>(), d_no.as<uint32_t>(),
-                       d_nbr.as<uint32_t>(), d_eidx.as<uint32_t>(), d_dp.as<double>(), d_vb.as<uint8_t>(), d_eb.as<uint8_t>(),
-                       d_os.as<double>(), d_is.as<double>(), d_nt.as<uint8_t>(), d_fk.as<uint8_t>(), d_nx.as<int32_t>(),
-                       d_pd.as<int32_t>(), d_big.as<uint32_t>() + 1, d_big.as<uint32_t>(), (uint32_t *)nullptr);
-    hipLaunchKernelGGL(k_vertex_sums_big, dim3(64), dim3(64), 0, ctx->stream, d_big.as<uint32_t>() + 1, d_big.as<uint32_t>(), d_row.as<uint64_t>(),
-                       d_no.as<uint32_t>(), d_nbr.as<uint32_t>(), d_dp.as<double>(), d_os.as<double>(), d_is.as<double>());
-    hipLaunchKernelGGL(k_edge_flow, grid, block, 0, ctx->stream, n_vertices, d_row.as<uint64_t>(), d_no.as<uint32_t>(),
-                       d_nbr.as<uint32_t>(), d_eidx.as<uint32_t>(), d_dp.as<double>(), d_os.as<double>(), d_is.as<double>(),
-                       d_flow.as<double>(), d_bad.as<uint32_t>());
-    hipLaunchKernelGGL(k_chain_rank, dim3(1), dim3(CHAIN_TPB), 0, ctx->stream, n_vertices, d_pd.as<int32_t>(), d_chain.as<int32_t>(),
-                       chain_stride, d_top.as<int32_t>(), d_rank.as<int32_t>());
+    hipLaunchKernelGGL(k_vertex_scan, grid, block, 0, ctx->stream, n_vertices, d_row->as<uint64_t>(), d_no->as<uint32_t>(),
+                       d_nbr->as<uint32_t>(), d_eidx->as<uint32_t>(), d_dp->as<double>(), d_vb->as<uint8_t>(), d_eb->as<uint8_t>(),
+                       d_os->as<double>(), d_is->as<double>(), d_nt->as<uint8_t>(), d_fk->as<uint8_t>(), d_nx->as<int32_t>(),
+                       d_pd->as<int32_t>(), d_big->as<uint32_t>() + 1, d_big->as<uint32_t>(), (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_vertex_sums_big, dim3(64), dim3(64), 0, ctx->stream, d_big->as<uint32_t>() + 1, d_big->as<uint32_t>(), d_row->as<uint64_t>(),
+                       d_no->as<uint32_t>(), d_nbr->as<uint32_t>(), d_dp->as<double>(), d_os->as<double>(), d_is->as<double>());
+    hipLaunchKernelGGL(k_edge_flow, grid, block, 0, ctx->stream, n_vertices, d_row->as<uint64_t>(), d_no->as<uint32_t>(),
+                       d_nbr->as<uint32_t>(), d_eidx->as<uint32_t>(), d_dp->as<double>(), d_os->as<double>(), d_is->as<double>(),
+                       d_flow->as<double>(), d_bad->as<uint32_t>());
+    hipLaunchKernelGGL(k_chain_rank, dim3(1), dim3(CHAIN_TPB), 0, ctx->stream, n_vertices, d_pd->as<int32_t>(), d_chain->as<int32_t>(),
+                       chain_stride, d_top->as<int32_t>(), d_rank->as<int32_t>());
     VS_HIP(ctx, hipGetLastError());
     uint32_t bad = 0xFFFFFFFFu;
-    if (flow && n_edge_slots) VS_HIP(ctx, hipMemcpyAsync(flow, d_flow.p, (size_t)n_edge_slots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (nontrivial) VS_HIP(ctx, hipMemcpyAsync(nontrivial, d_nt.p, n_vertices, hipMemcpyDeviceToHost, ctx->stream));
-    if (fork_kind) VS_HIP(ctx, hipMemcpyAsync(fork_kind, d_fk.p, n_vertices, hipMemcpyDeviceToHost, ctx->stream));
-    if (chain_next) VS_HIP(ctx, hipMemcpyAsync(chain_next, d_nx.p, (size_t)n_vertices * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (chain_top) VS_HIP(ctx, hipMemcpyAsync(chain_top, d_top.p, (size_t)n_vertices * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (chain_rank) VS_HIP(ctx, hipMemcpyAsync(chain_rank, d_rank.p, (size_t)n_vertices * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    VS_HIP(ctx, hipMemcpyAsync(&bad, d_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (flow && n_edge_slots) VS_HIP(ctx, hipMemcpyAsync(flow, d_flow->ptr(), (size_t)n_edge_slots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (nontrivial) VS_HIP(ctx, hipMemcpyAsync(nontrivial, d_nt->ptr(), n_vertices, hipMemcpyDeviceToHost, ctx->stream));
+    if (fork_kind) VS_HIP(ctx, hipMemcpyAsync(fork_kind, d_fk->ptr(), n_vertices, hipMemcpyDeviceToHost, ctx->stream));
+    if (chain_next) VS_HIP(ctx, hipMemcpyAsync(chain_next, d_nx->ptr(), (size_t)n_vertices * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (chain_top) VS_HIP(ctx, hipMemcpyAsync(chain_top, d_top->ptr(), (size_t)n_vertices * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (chain_rank) VS_HIP(ctx, hipMemcpyAsync(chain_rank, d_rank->ptr(), (size_t)n_vertices * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipMemcpyAsync(&bad, d_bad->ptr(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (zero_sum_edge) *zero_sum_edge = bad;
     return VS_OK;
@@ -979,8 +948,8 @@ namespace {
 struct HipStageOps : VsStageOps {
     vs_ctx *ctx;
     const vs_links *links;
-    void *h_up = nullptr, *h_down = nullptr, *d_up = nullptr, *d_down = nullptr, *d_tmp = nullptr, *d_ones = nullptr;
-    size_t cap_up = 0, cap_down = 0, cap_tmp = 0, cap_ones = 0;
+    VsPinnedBuf h_up, h_down;
+    VsDevBuf d_up, d_down, d_tmp, d_ones;
     double t_pack = 0, t_enqueue = 0, t_wait = 0, t_unpack = 0;  // where a call's host time goes (VS_STAGE_OP_TIMING=1 prints the sums)
     uint64_t n_calls = 0, n_second_waits = 0;
     static double now() {
@@ -994,27 +963,10 @@ struct HipStageOps : VsStageOps {
             fprintf(stderr, "[vs] stage flow/scan operation: %llu calls (%llu with a second wait for long chains), pack %.4f s, enqueue %.4f s, wait %.4f s, unpack %.4f s\n",
                     (unsigned long long)n_calls, (unsigned long long)n_second_waits, t_pack, t_enqueue, t_wait, t_unpack);
         (void)hipSetDevice(ctx->device);
-        (void)hipStreamSynchronize(ctx->stream);
-        if (h_up) (void)hipHostFree(h_up);
-        if (h_down) (void)hipHostFree(h_down);
-        if (d_up) (void)hipFree(d_up);
-        if (d_down) (void)hipFree(d_down);
-        if (d_tmp) (void)hipFree(d_tmp);
-        if (d_ones) (void)hipFree(d_ones);
+        (void)hipStreamSynchronize(ctx->stream);  // (then the buffers die)
     }
     static size_t up8(size_t x) { return (x + 7u) & ~(size_t)7u; }
-    int grow(void **host, void **dev, size_t *cap, size_t need) {
-        if (*cap >= need) return VS_OK;
-        VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (host && *host) { VS_HIP(ctx, hipHostFree(*host)); *host = nullptr; }
-        if (*dev) { VS_HIP(ctx, hipFree(*dev)); *dev = nullptr; }
-        *cap = 0;
-        const size_t c = need + need / 2 + 4096;
-        if (host) VS_HIP(ctx, hipHostMalloc(host, c, hipHostMallocDefault));
-        VS_HIP(ctx, hipMalloc(dev, c));
-        *cap = c;
-        return VS_OK;
-    }
+    static size_t slack(size_t need) { return need + need / 2 + 4096; }
     int run(uint32_t nv, uint32_t ne, const uint64_t *row_ptr, const uint32_t *n_out, const uint32_t *nbr, const uint32_t *eidx,
             const double *dp, double *flow, uint8_t *nontrivial, uint8_t *fork_kind, int32_t *chain_next, int32_t *chain_top,
             int32_t *chain_rank, uint32_t *zero_sum_edge) {
@@ -1032,15 +984,18 @@ struct HipStageOps : VsStageOps {
         const uint32_t chain_stride = (nv + 3u) & ~3u;
         const size_t t_os = 0, t_is = t_os + (size_t)nv * 8, t_pd = t_is + (size_t)nv * 8, t_pj = t_pd + up8((size_t)nv * 4),
                      t_ctl = t_pj + (size_t)6 * chain_stride * 4, t_big = t_ctl + 64 * 4, tmp_bytes = t_big + ((size_t)nv + 2) * 4;
-        VS_TRY(grow(&h_up, &d_up, &cap_up, up_bytes));
-        VS_TRY(grow(&h_down, &d_down, &cap_down, down_bytes));
-        VS_TRY(grow(nullptr, &d_tmp, &cap_tmp, tmp_bytes));
         const size_t need_ones = (size_t)(nv > ne ? nv : ne) + 1;
-        if (cap_ones < need_ones) {
-            VS_TRY(grow(nullptr, &d_ones, &cap_ones, need_ones));
-            VS_HIP(ctx, hipMemsetAsync(d_ones, 1, cap_ones, ctx->stream));
-        }
-        char *hu = (char *)h_up, *du = (char *)d_up, *dd = (char *)d_down, *dt = (char *)d_tmp;
+        if (h_up.capacity() < up_bytes || h_down.capacity() < down_bytes || d_tmp.capacity() < tmp_bytes || d_ones.capacity() < need_ones)
+            VS_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the device may still use a block that is about to be regrown)
+        VS_HIP(ctx, h_up.reserve(up_bytes, slack(up_bytes)));
+        VS_HIP(ctx, d_up.reserve(up_bytes, slack(up_bytes)));
+        VS_HIP(ctx, h_down.reserve(down_bytes, slack(down_bytes)));
+        VS_HIP(ctx, d_down.reserve(down_bytes, slack(down_bytes)));
+        VS_HIP(ctx, d_tmp.reserve(tmp_bytes, slack(tmp_bytes)));
+        bool ones_new = false;
+        VS_HIP(ctx, d_ones.reserve(need_ones, slack(need_ones), &ones_new));
+        if (ones_new) VS_HIP(ctx, hipMemsetAsync(d_ones.ptr(), 1, d_ones.capacity(), ctx->stream));
+        char *hu = h_up.as<char>(), *du = d_up.as<char>(), *dd = d_down.as<char>(), *dt = d_tmp.as<char>();
         const double t0 = now();
         n_calls++;
         memcpy(hu + o_row, row_ptr, (size_t)(nv + 1) * 8);
@@ -1056,7 +1011,7 @@ struct HipStageOps : VsStageOps {
             memcpy(hu + o_eidx, eidx, (size_t)n_adj * 4);
         }
         const double t1 = now();
-        VS_HIP(ctx, hipMemcpyAsync(d_up, h_up, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+        VS_HIP(ctx, hipMemcpyAsync(du, hu, up_bytes, hipMemcpyHostToDevice, ctx->stream));
         // rows of more than 128 neighbours on a side are rare: without one, neither their list's counter nor the kernel that
         // sums them is needed (the "no zero sum" word is set by the scan kernel) -- three device operations less per stage graph
         if (any_big) VS_HIP(ctx, hipMemsetAsync(dt + t_big, 0, 4, ctx->stream));
@@ -1066,8 +1021,8 @@ struct HipStageOps : VsStageOps {
         double *d_os = (double *)(dt + t_os), *d_is = (double *)(dt + t_is);
         int32_t *d_pd = (int32_t *)(dt + t_pd);
         dim3 grid((nv + 255) / 256), block(256);
-        hipLaunchKernelGGL(k_vertex_scan, grid, block, 0, ctx->stream, nv, d_row, d_no, d_nbr, d_eidx, d_dp, (const uint8_t *)d_ones,
-                           (const uint8_t *)d_ones, d_os, d_is, (uint8_t *)(dd + q_nt), (uint8_t *)(dd + q_fk), (int32_t *)(dd + q_next), d_pd,
+        hipLaunchKernelGGL(k_vertex_scan, grid, block, 0, ctx->stream, nv, d_row, d_no, d_nbr, d_eidx, d_dp, d_ones.as<const uint8_t>(),
+                           d_ones.as<const uint8_t>(), d_os, d_is, (uint8_t *)(dd + q_nt), (uint8_t *)(dd + q_fk), (int32_t *)(dd + q_next), d_pd,
                            (uint32_t *)(dt + t_big) + 1, (uint32_t *)(dt + t_big), (uint32_t *)(dd + q_bad));
         if (any_big)
             hipLaunchKernelGGL(k_vertex_sums_big, dim3(64), dim3(64), 0, ctx->stream, (const uint32_t *)(dt + t_big) + 1,
@@ -1093,10 +1048,10 @@ struct HipStageOps : VsStageOps {
                                (int32_t *)(dd + q_rank), round, (uint32_t *)(dd + q_bad) + 1);
         }
         VS_HIP(ctx, hipGetLastError());
-        VS_HIP(ctx, hipMemcpyAsync(h_down, d_down, down_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        VS_HIP(ctx, hipMemcpyAsync(h_down.ptr(), dd, down_bytes, hipMemcpyDeviceToHost, ctx->stream));
         const double t2 = now();
         VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const char *hd = (const char *)h_down;
+        const char *hd = h_down.as<const char>();
         if (rounds_done < rounds_total) {
             uint32_t live = 0;
             memcpy(&live, hd + q_bad + 4, 4);
@@ -1107,7 +1062,7 @@ struct HipStageOps : VsStageOps {
                 hipLaunchKernelGGL(k_chain_finish_wide, grid, block, 0, ctx->stream, nv, buf, chain_stride, ctl, (int32_t *)(dd + q_top),
                                    (int32_t *)(dd + q_rank), rounds_total, (uint32_t *)nullptr);
                 VS_HIP(ctx, hipGetLastError());
-                VS_HIP(ctx, hipMemcpyAsync((char *)h_down + q_top, dd + q_top, (q_bad - q_top), hipMemcpyDeviceToHost, ctx->stream));
+                VS_HIP(ctx, hipMemcpyAsync(h_down.as<char>() + q_top, dd + q_top, (q_bad - q_top), hipMemcpyDeviceToHost, ctx->stream));
                 VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
             }
         }

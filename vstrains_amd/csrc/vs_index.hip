@@ -165,59 +165,50 @@ extern "C" int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint
     size_t b_meta = sizeof(VsNodeMeta) * (n_nodes ? n_nodes : 1);
     size_t b_words = sizeof(uint32_t) * (words + VS_PAD_WORDS);
     size_t b_post = sizeof(uint4) * (npos ? npos : 1);
-    VS_HIP(ctx, hipMalloc(&ctx->d_meta, b_meta));
-    VS_HIP(ctx, hipMalloc(&ctx->d_fwd, 2 * b_words));  // forward text, then the reverse complements
-    ctx->d_rc = nullptr;
-    VS_HIP(ctx, hipMalloc(&ctx->d_post, b_post));
+    VS_HIP(ctx, ctx->d_meta.reserve(b_meta));
+    VS_HIP(ctx, ctx->d_fwd.reserve(2 * b_words));  // forward text, then the reverse complements
+    VS_HIP(ctx, ctx->d_post.reserve(b_post));
     ctx->index_bytes = b_meta + 2 * b_words + b_post;  // (+ the table, sized below)
-    // temporaries
-    uint8_t *d_ascii = nullptr;
-    uint64_t *d_aoff = nullptr, *d_seed_off = nullptr, *d_tmp = nullptr;
-    uint32_t *d_woff = nullptr, *d_cnts = nullptr, *d_offs = nullptr, *d_cursor = nullptr, *d_pos_slot = nullptr, *d_flags = nullptr;
-    unsigned long long *d_keys = nullptr;
-    int rc = VS_OK;
+    // temporaries; the steps on the device return at the first failure, and what has to happen on every way out follows them
+    VsDevBuf ascii_buf, aoff_buf, seed_off_buf, woff_buf, keys_buf, pos_slot_buf, flags_buf, cnts_buf, offs_buf, cursor_buf, tmp_buf;
     hipStream_t st = ctx->stream;
-#define TRY(call)                                                                                  \
-    do {                                                                                           \
-        hipError_t e__ = (call);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            rc = vs_fail(ctx, e__ == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, "%s failed: %s", #call, hipGetErrorString(e__)); \
-            goto done;                                                                             \
-        }                                                                                          \
-    } while (0)
-    {
-        TRY(hipMalloc((void **)&d_ascii, total_ascii + 16));
-        TRY(hipMalloc((void **)&d_aoff, sizeof(uint64_t) * (n_nodes + 1)));
-        TRY(hipMalloc((void **)&d_seed_off, sizeof(uint64_t) * (n_nodes + 1)));
-        TRY(hipMalloc((void **)&d_woff, sizeof(uint32_t) * (n_nodes + 1)));
-        TRY(hipMalloc((void **)&d_keys, sizeof(unsigned long long) * n_slots));
-        TRY(hipMalloc((void **)&d_pos_slot, sizeof(uint32_t) * (npos ? npos : 1)));
-        TRY(hipMalloc((void **)&d_flags, sizeof(uint32_t) * 4));
-        if (total_ascii) TRY(hipMemcpyAsync(d_ascii, node_ascii, total_ascii, hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(d_aoff, node_off, sizeof(uint64_t) * (n_nodes + 1), hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(d_seed_off, seed_off.data(), sizeof(uint64_t) * (n_nodes + 1), hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(d_woff, woff.data(), sizeof(uint32_t) * (n_nodes + 1), hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(ctx->d_meta, meta.data(), b_meta, hipMemcpyHostToDevice, st));
-        TRY(hipMemsetAsync(ctx->d_fwd, 0, 2 * b_words, st));
-        TRY(hipMemsetAsync(d_keys, 0xFF, sizeof(unsigned long long) * n_slots, st));
+    const auto on_device = [&]() -> int {
+        VS_HIP(ctx, ascii_buf.reserve(total_ascii + 16));
+        VS_HIP(ctx, aoff_buf.reserve(sizeof(uint64_t) * (n_nodes + 1)));
+        VS_HIP(ctx, seed_off_buf.reserve(sizeof(uint64_t) * (n_nodes + 1)));
+        VS_HIP(ctx, woff_buf.reserve(sizeof(uint32_t) * (n_nodes + 1)));
+        VS_HIP(ctx, keys_buf.reserve(sizeof(unsigned long long) * n_slots));
+        VS_HIP(ctx, pos_slot_buf.reserve(sizeof(uint32_t) * (npos ? npos : 1)));
+        VS_HIP(ctx, flags_buf.reserve(sizeof(uint32_t) * 4));
+        uint8_t *d_ascii = ascii_buf.as<uint8_t>();
+        uint64_t *d_aoff = aoff_buf.as<uint64_t>(), *d_seed_off = seed_off_buf.as<uint64_t>();
+        uint32_t *d_woff = woff_buf.as<uint32_t>(), *d_pos_slot = pos_slot_buf.as<uint32_t>(), *d_flags = flags_buf.as<uint32_t>();
+        unsigned long long *d_keys = keys_buf.as<unsigned long long>();
+        if (total_ascii) VS_HIP(ctx, hipMemcpyAsync(d_ascii, node_ascii, total_ascii, hipMemcpyHostToDevice, st));
+        VS_HIP(ctx, hipMemcpyAsync(d_aoff, node_off, sizeof(uint64_t) * (n_nodes + 1), hipMemcpyHostToDevice, st));
+        VS_HIP(ctx, hipMemcpyAsync(d_seed_off, seed_off.data(), sizeof(uint64_t) * (n_nodes + 1), hipMemcpyHostToDevice, st));
+        VS_HIP(ctx, hipMemcpyAsync(d_woff, woff.data(), sizeof(uint32_t) * (n_nodes + 1), hipMemcpyHostToDevice, st));
+        VS_HIP(ctx, hipMemcpyAsync(ctx->d_meta.ptr(), meta.data(), b_meta, hipMemcpyHostToDevice, st));
+        VS_HIP(ctx, hipMemsetAsync(ctx->d_fwd.ptr(), 0, 2 * b_words, st));
+        VS_HIP(ctx, hipMemsetAsync(d_keys, 0xFF, sizeof(unsigned long long) * n_slots, st));
         uint32_t init_flags[4] = {0xFFFFFFFFu, 0, 0, 0};
-        TRY(hipMemcpyAsync(d_flags, init_flags, sizeof init_flags, hipMemcpyHostToDevice, st));
+        VS_HIP(ctx, hipMemcpyAsync(d_flags, init_flags, sizeof init_flags, hipMemcpyHostToDevice, st));
 
         VsIndexDev d{};
         d.n_nodes = n_nodes; d.K = K; d.w = w; d.s = s; d.table_bits = bits;
-        d.meta = (const VsNodeMeta *)ctx->d_meta;
-        d.fwd_words = (const uint32_t *)ctx->d_fwd;
+        d.meta = ctx->d_meta.as<const VsNodeMeta>();
+        d.fwd_words = ctx->d_fwd.as<const uint32_t>();
         d.rc_delta = (uint32_t)(words + VS_PAD_WORDS);
         d.rc_words = d.fwd_words + d.rc_delta;
-        d.table = (const VsSlot *)ctx->d_table;
-        d.postings = (const uint4 *)ctx->d_post;
+        d.table = ctx->d_table.as<const VsSlot>();
+        d.postings = ctx->d_post.as<const uint4>();
 
         if (words)
             hipLaunchKernelGGL(k_pack_nodes, dim3((unsigned)((words + TPB - 1) / TPB)), dim3(TPB), 0, st, d_ascii, d_aoff,
-                               d_woff, n_nodes, (uint32_t)words, K, (uint32_t *)ctx->d_fwd, (uint32_t *)ctx->d_fwd + (words + VS_PAD_WORDS), d_flags);
+                               d_woff, n_nodes, (uint32_t)words, K, ctx->d_fwd.as<uint32_t>(), ctx->d_fwd.as<uint32_t>() + (words + VS_PAD_WORDS), d_flags);
         uint32_t h_flags[4];
-        TRY(hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
-        TRY(hipStreamSynchronize(st));
+        VS_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
+        VS_HIP(ctx, hipStreamSynchronize(st));
         if (h_flags[0] != 0xFFFFFFFFu) {
             // Name the byte the reference's KeyError names: last offending byte of the first
             // (k+1)-window of that node that holds one (reverse_seq scans the window from its end).
@@ -232,8 +223,7 @@ extern "C" int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint
                 if (isbad(t[q])) last = t[q];
             if (bad_node_out) *bad_node_out = nd;
             if (bad_char_out) *bad_char_out = last;
-            rc = vs_fail(ctx, VS_E_NODE_BASE, "node %u holds byte 0x%02x outside ACGT", nd, last);
-            goto done;
+            return vs_fail(ctx, VS_E_NODE_BASE, "node %u holds byte 0x%02x outside ACGT", nd, last);
         }
         // The table is sized by the DISTINCT seeds, which only an insertion pass can count: a graph whose nodes overlap
         // by k bases holds every seed of an overlap once per node that shares it (3.6 positions per distinct seed at
@@ -246,8 +236,8 @@ extern "C" int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint
             unsigned nb = (unsigned)((npos + TPB - 1) / TPB);
             hipLaunchKernelGGL(k_seed_insert, dim3(nb), dim3(TPB), 0, st, d, d_seed_off, npos, d_keys, (uint32_t *)nullptr,
                                (uint32_t *)nullptr, d_flags + 3);
-            TRY(hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
-            TRY(hipStreamSynchronize(st));
+            VS_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
+            VS_HIP(ctx, hipStreamSynchronize(st));
             const uint64_t want = ((uint64_t)h_flags[3] << 3) + 2u;  // (at most an eighth full)
             bits_final = 4;
             while ((1ull << bits_final) < want) bits_final++;
@@ -257,57 +247,54 @@ extern "C" int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint
             const uint64_t distinct = h_flags[3];
             uint32_t gave_up_bits = 0;
             if (bits_final > bits) {
-                (void)hipFree(d_keys);
-                d_keys = nullptr;
-                while (hipMalloc((void **)&d_keys, sizeof(unsigned long long) << bits_final) != hipSuccess) {
+                while (keys_buf.reserve(sizeof(unsigned long long) << bits_final) != hipSuccess) {  // (the small table goes first)
                     (void)hipGetLastError();
-                    d_keys = nullptr;
                     if (bits_final <= bits + 1u || (3ull << (bits_final - 1u)) / 4u < distinct) break;
                     bits_final--;
                 }
-                if (!d_keys) {
+                if (!keys_buf.ptr()) {
                     gave_up_bits = bits_final;  // (the smallest table that was asked for and refused)
                     bits_final = bits;
-                    TRY(hipMalloc((void **)&d_keys, sizeof(unsigned long long) << bits_final));
+                    VS_HIP(ctx, keys_buf.reserve(sizeof(unsigned long long) << bits_final));
                 }
+                d_keys = keys_buf.as<unsigned long long>();
             }
             if ((3ull << bits_final) / 4u < distinct) {
                 //  two ways to get here: the 2^30-slot cap (a graph beyond what this build supports), or a device
                 // without room for the table the graph needs -- the caller must be able to tell them apart
                 if (gave_up_bits)
-                    rc = vs_fail(ctx, VS_E_OOM, "vs_index_build: no device memory for a seed table of 2^%u slots (%llu bytes of keys) and the %llu distinct seeds do not fit 2^%u",
-                                 gave_up_bits, (unsigned long long)(sizeof(unsigned long long) << gave_up_bits), (unsigned long long)distinct, bits_final);
-                else
-                    rc = vs_fail(ctx, VS_E_RANGE, "vs_index_build: %llu distinct seeds do not fit a seed table of 2^%u slots", (unsigned long long)distinct, bits_final);
-                goto done;
+                    return vs_fail(ctx, VS_E_OOM, "vs_index_build: no device memory for a seed table of 2^%u slots (%llu bytes of keys) and the %llu distinct seeds do not fit 2^%u",
+                                   gave_up_bits, (unsigned long long)(sizeof(unsigned long long) << gave_up_bits), (unsigned long long)distinct, bits_final);
+                return vs_fail(ctx, VS_E_RANGE, "vs_index_build: %llu distinct seeds do not fit a seed table of 2^%u slots", (unsigned long long)distinct, bits_final);
             }
             n_slots_final = 1ull << bits_final;
             d.table_bits = bits_final;
-            TRY(hipMemsetAsync(d_keys, 0xFF, sizeof(unsigned long long) * n_slots_final, st));
+            VS_HIP(ctx, hipMemsetAsync(d_keys, 0xFF, sizeof(unsigned long long) * n_slots_final, st));
         }
-        TRY(hipMalloc((void **)&d_cnts, sizeof(uint32_t) * n_slots_final));
-        TRY(hipMalloc((void **)&d_offs, sizeof(uint32_t) * n_slots_final));
-        TRY(hipMalloc((void **)&d_cursor, sizeof(uint32_t) * n_slots_final));
-        TRY(hipMalloc((void **)&d_tmp, sizeof(uint64_t) * (n_slots_final / 2048 + 4)));
-        TRY(hipMemsetAsync(d_cnts, 0, sizeof(uint32_t) * n_slots_final, st));
-        TRY(hipMemsetAsync(d_cursor, 0, sizeof(uint32_t) * n_slots_final, st));
-        TRY(hipMalloc(&ctx->d_table, sizeof(VsSlot) * n_slots_final));
-        d.table = (const VsSlot *)ctx->d_table;
+        VS_HIP(ctx, cnts_buf.reserve(sizeof(uint32_t) * n_slots_final));
+        VS_HIP(ctx, offs_buf.reserve(sizeof(uint32_t) * n_slots_final));
+        VS_HIP(ctx, cursor_buf.reserve(sizeof(uint32_t) * n_slots_final));
+        VS_HIP(ctx, tmp_buf.reserve(sizeof(uint64_t) * (n_slots_final / 2048 + 4)));
+        uint32_t *d_cnts = cnts_buf.as<uint32_t>(), *d_offs = offs_buf.as<uint32_t>(), *d_cursor = cursor_buf.as<uint32_t>();
+        uint64_t *d_tmp = tmp_buf.as<uint64_t>();
+        VS_HIP(ctx, hipMemsetAsync(d_cnts, 0, sizeof(uint32_t) * n_slots_final, st));
+        VS_HIP(ctx, hipMemsetAsync(d_cursor, 0, sizeof(uint32_t) * n_slots_final, st));
+        VS_HIP(ctx, ctx->d_table.reserve(sizeof(VsSlot) * n_slots_final));
+        d.table = ctx->d_table.as<const VsSlot>();
         ctx->index_bytes += sizeof(VsSlot) * n_slots_final;
         if (npos) {
             unsigned nb = (unsigned)((npos + TPB - 1) / TPB);
             hipLaunchKernelGGL(k_seed_insert, dim3(nb), dim3(TPB), 0, st, d, d_seed_off, npos, d_keys, d_cnts, d_pos_slot,
                                (uint32_t *)nullptr);
-            rc = vs_scan_u32(ctx, d_cnts, d_offs, n_slots_final, d_tmp, nullptr);
-            if (rc) goto done;
+            if (int rc = vs_scan_u32(ctx, d_cnts, d_offs, n_slots_final, d_tmp, nullptr)) return rc;
             hipLaunchKernelGGL(k_seed_fill, dim3(nb), dim3(TPB), 0, st, d, d_seed_off, npos, d_pos_slot, d_offs, d_cursor,
-                               (uint4 *)ctx->d_post);
+                               ctx->d_post.as<uint4>());
         }
         hipLaunchKernelGGL(k_table_finalize, dim3((unsigned)((n_slots_final + TPB - 1) / TPB)), dim3(TPB), 0, st, d_keys, d_cnts,
-                           d_offs, (const uint4 *)ctx->d_post, (uint32_t)n_slots_final, (VsSlot *)ctx->d_table, d_flags + 1);
-        TRY(hipGetLastError());
-        TRY(hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
-        TRY(hipStreamSynchronize(st));
+                           d_offs, ctx->d_post.as<const uint4>(), (uint32_t)n_slots_final, ctx->d_table.as<VsSlot>(), d_flags + 1);
+        VS_HIP(ctx, hipGetLastError());
+        VS_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
+        VS_HIP(ctx, hipStreamSynchronize(st));
         ctx->idx = d;
         ctx->n_seed_pos = npos;
         ctx->max_node_len = 0;
@@ -315,17 +302,12 @@ extern "C" int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint
         ctx->n_slots = n_slots_final;
         ctx->n_distinct = h_flags[1];
         ctx->has_index = true;
-    }
-done:
-    (void)hipStreamSynchronize(st);
-    {
-        void *tmps[] = {d_ascii, d_aoff, d_seed_off, d_woff, d_keys, d_cnts, d_offs, d_cursor, d_pos_slot, d_tmp, d_flags};
-        for (void *p : tmps)
-            if (p) (void)hipFree(p);
-    }
+        return VS_OK;
+    };
+    const int rc = on_device();
+    (void)hipStreamSynchronize(st);  // (before the temporaries die)
     if (rc != VS_OK) vs_ctx_free_index(ctx);
     return rc;
-#undef TRY
 }
 
 extern "C" int vs_index_info(const vs_ctx *ctx, uint64_t info[6]) {
@@ -353,8 +335,8 @@ extern "C" int vs_index_export(vs_ctx *ctx, void *slots, void *postings, uint32_
     sizes[3] = d.n_nodes;
     sizes[4] = d.table_bits;
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (slots) VS_HIP(ctx, hipMemcpy(slots, ctx->d_table, sizeof(VsSlot) * ctx->n_slots, hipMemcpyDeviceToHost));
-    if (postings && ctx->n_seed_pos) VS_HIP(ctx, hipMemcpy(postings, ctx->d_post, sizeof(uint4) * ctx->n_seed_pos, hipMemcpyDeviceToHost));
+    if (slots) VS_HIP(ctx, hipMemcpy(slots, ctx->d_table.ptr(), sizeof(VsSlot) * ctx->n_slots, hipMemcpyDeviceToHost));
+    if (postings && ctx->n_seed_pos) VS_HIP(ctx, hipMemcpy(postings, ctx->d_post.ptr(), sizeof(uint4) * ctx->n_seed_pos, hipMemcpyDeviceToHost));
     if (fwd_words) VS_HIP(ctx, hipMemcpy(fwd_words, d.fwd_words, sizeof(uint32_t) * d.rc_delta, hipMemcpyDeviceToHost));
     if (rc_words) VS_HIP(ctx, hipMemcpy(rc_words, d.rc_words, sizeof(uint32_t) * d.rc_delta, hipMemcpyDeviceToHost));
     if (meta && d.n_nodes) VS_HIP(ctx, hipMemcpy(meta, d.meta, sizeof(VsNodeMeta) * d.n_nodes, hipMemcpyDeviceToHost));

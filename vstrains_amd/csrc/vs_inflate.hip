@@ -173,29 +173,24 @@ int vs_inflate_bgzf(vs_ctx *ctx, const uint8_t *data, uint64_t n, uint8_t *out, 
     if (dir.empty()) return VS_OK;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    uint8_t *d_comp = nullptr, *d_out = nullptr;
-    vs_bgzf_member *d_dir = nullptr;
-    uint32_t *d_status = nullptr;
     const uint32_t nm = (uint32_t)dir.size();
-    hipError_t e1 = hipMalloc((void **)&d_comp, n + 16u);
-    if (e1 == hipSuccess) e1 = hipMalloc((void **)&d_out, total + 16u);
-    if (e1 == hipSuccess) e1 = hipMalloc((void **)&d_dir, sizeof(vs_bgzf_member) * nm);
-    if (e1 == hipSuccess) e1 = hipMalloc((void **)&d_status, sizeof(uint32_t) * nm);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(d_comp, data, n, hipMemcpyHostToDevice, st);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(d_dir, dir.data(), sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(d_out, 0xA5, total + 16u, st);  // (the guard bytes behind every member keep this)
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(d_status, 0xFF, sizeof(uint32_t) * nm, st);
-    if (e1 == hipSuccess) {
-        vs_launch_inflate(st, d_comp, n, d_out, total, d_dir, nm, d_status, nullptr, 0, 0);
-        e1 = hipGetLastError();
-    }
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, st);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(status, d_status, sizeof(uint32_t) * nm, hipMemcpyDeviceToHost, st);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-    void *ps[] = {d_comp, d_out, d_dir, d_status};
-    for (void *p : ps)
-        if (p) (void)hipFree(p);
-    if (e1 != hipSuccess) return vs_fail(ctx, VS_E_HIP, "vs_inflate_bgzf: %s", hipGetErrorString(e1));
+    VsDevBuf comp_buf, out_buf, dir_buf, status_buf;
+    VS_HIP(ctx, comp_buf.reserve(n + 16u));
+    VS_HIP(ctx, out_buf.reserve(total + 16u));
+    VS_HIP(ctx, dir_buf.reserve(sizeof(vs_bgzf_member) * nm));
+    VS_HIP(ctx, status_buf.reserve(sizeof(uint32_t) * nm));
+    uint8_t *d_comp = comp_buf.as<uint8_t>(), *d_out = out_buf.as<uint8_t>();
+    vs_bgzf_member *d_dir = dir_buf.as<vs_bgzf_member>();
+    uint32_t *d_status = status_buf.as<uint32_t>();
+    VS_HIP(ctx, hipMemcpyAsync(d_comp, data, n, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemcpyAsync(d_dir, dir.data(), sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemsetAsync(d_out, 0xA5, total + 16u, st));  // (the guard bytes behind every member keep this)
+    VS_HIP(ctx, hipMemsetAsync(d_status, 0xFF, sizeof(uint32_t) * nm, st));
+    vs_launch_inflate(st, d_comp, n, d_out, total, d_dir, nm, d_status, nullptr, 0, 0);
+    VS_HIP(ctx, hipGetLastError());
+    VS_HIP(ctx, hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipMemcpyAsync(status, d_status, sizeof(uint32_t) * nm, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
     return VS_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/vstrains_hip.h"
+#include "vs_buf.h"
 
 #define VS_WAVE 64
 #define VS_PAD_WORDS 16  // zero words behind every packed text buffer (window reads may overshoot)
@@ -91,8 +92,7 @@ struct VsReadsDev {
 // pinned staging of one FASTQ block in flight (vs_fastq_block): packed words (+ pad), word offsets,
 // lengths | flags; two sets alternate, the cores fill one while the other is still being uploaded
 struct FqStage {
-    uint32_t *words = nullptr, *woff = nullptr, *meta = nullptr;
-    size_t words_cap = 0, ends_cap = 0;
+    VsPinnedBuf words, woff, meta;
     hipEvent_t done = nullptr;  // the uploads out of this set have finished
     bool in_flight = false;
 };
@@ -128,37 +128,38 @@ struct vs_ctx {
     bool has_index = false;
     VsIndexDev idx{};
     // owned device allocations of the index
-    void *d_meta = nullptr, *d_fwd = nullptr, *d_rc = nullptr, *d_table = nullptr, *d_post = nullptr;
+    VsDevBuf d_meta, d_fwd, d_table, d_post;
     uint64_t n_seed_pos = 0, n_slots = 0, n_distinct = 0, index_bytes = 0;
     uint32_t max_node_len = 0;
     // scratch for vs_pe_count
-    void *d_slow_list = nullptr;   // pair indices sent to the slow path
-    uint64_t slow_cap = 0;
-    void *d_slow_count = nullptr;  // uint32 counters (see pe_launch)
-    void *links_spare = nullptr;   // vs_links_reserve: the buffer of the next link table (links_spare_n nodes)
+    VsDevBuf d_slow_list;          // pair indices sent to the slow path
+    VsDevBuf d_slow_count;         // SC_WORDS uint32 counters, zeroed before every count
+    enum SlowCount : uint32_t {
+        SC_MID = 0,         // pairs for k_pe_mid
+        SC_ACC_QUEUE = 1,   // k_pe_accumulate's chunk queue
+        SC_SLOW = 8,        // pairs for k_pe_slow
+        SC_STRIP_QUEUE = 9, // k_rows_sum's strip queue
+        SC_OWNERS = 15,     // owning ends
+        SC_WORDS = 16       // (the other words unused)
+    };
+    VsDevBuf links_spare;          // vs_links_reserve: the buffer of the next link table (links_spare_n nodes)
     uint32_t links_spare_n = 0;
-    void *d_slow_list2 = nullptr;  // pairs k_pe_mid hands on to k_pe_slow
-    uint64_t slow2_cap = 0;
-    void *d_dense = nullptr;       // dense per-workgroup state for the slow path
-    uint64_t dense_bytes = 0;
+    VsDevBuf d_slow_list2;         // pairs k_pe_mid hands on to k_pe_slow
+    VsDevBuf d_dense;              // dense per-workgroup state for the slow path
     uint32_t dense_nodes = 0xFFFFFFFFu;  // node count the dense layout was initialised for
     // locus order scratch (k_pe_locus / k_pe_permute)
-    void *d_locus_keys = nullptr, *d_perm = nullptr, *d_locus_hist = nullptr, *d_scan_tmp = nullptr;
-    uint64_t locus_cap = 0, hist_cap = 0;
+    VsDevBuf d_locus_keys, d_perm, d_locus_hist, d_scan_tmp;
     double last_sort_ms = 0;
     // per-end accepted lists between k_pe_tiles and k_pe_accumulate
-    void *d_lists = nullptr, *d_list_counts = nullptr;
-    uint64_t lists_cap = 0, lists_words = 0;
+    VsDevBuf d_lists, d_list_counts;
     // row-owner counting (k_list_owners / k_rows_count / k_rows_fill / k_rows_sum): per matrix and row the counts, cursors
     // and offsets (6 x (N + 2) words), the items of every row (one word per listed node), the multiplicity of every end's list
-    void *d_rows = nullptr, *d_row_entries = nullptr, *d_mult = nullptr, *d_ltab = nullptr;
-    uint64_t rows_cap = 0, row_entries_cap = 0 /* pairs */, ltab_cap = 0 /* slots */;
-    // grow-only device scratch slots of the graph-stage entry points (no hipMalloc per call)
-    void *scratch[32] = {};
-    size_t scratch_cap[32] = {};
+    VsDevBuf d_rows, d_row_entries, d_mult, d_ltab;
+    // grow-only device scratch slots of the graph-stage entry points (no allocation per call)
+    VsDevBuf scratch[32];
     // device buffers of freed read blocks, kept for the next block of about the same size (the
     // FASTQ ingest makes and frees one block per million pairs)
-    struct CachedBuf { void *p; size_t cap; bool used; };
+    struct CachedBuf { VsDevBuf buf; bool used; };
     std::vector<CachedBuf> cache;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double last_ms[3] = {0, 0, 0};
@@ -169,8 +170,17 @@ struct vs_ctx {
 
 struct vs_reads {
     uint64_t n_ends = 0, n_words = 0, max_len = 0, n_invalid = 0, bytes = 0;
+    // the five arrays as the kernels see them: lent by the context's cache (cached: vs_cache_alloc) or held in own[]
     void *d_woff = nullptr, *d_meta = nullptr, *d_words = nullptr, *d_mask = nullptr, *d_inv4 = nullptr;
-    bool cached = false;  // buffers came from vs_cache_alloc
+    bool cached = false;
+    VsDevBuf own[5];
+    unsigned n_own = 0;
+    hipError_t own_alloc(void *&view, size_t bytes) {  // one more array of a block that is not cached
+        const hipError_t e = own[n_own].reserve(bytes);
+        view = own[n_own].ptr();
+        if (e == hipSuccess) n_own++;
+        return e;
+    }
     VsReadsDev dev() const {
         VsReadsDev r;
         r.n_ends = n_ends;

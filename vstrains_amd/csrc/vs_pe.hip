@@ -2306,14 +2306,9 @@ static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_
     const uint32_t N = ctx->idx.n_nodes;
     const uint64_t sub_max = tn.rows_sub ? (uint64_t)tn.rows_sub : (uint64_t)ROWS_SUB;
     const uint64_t sub_pairs = slots_pairs < sub_max ? slots_pairs : sub_max;  // pairs per transposition
-    if (ctx->rows_cap < (uint64_t)N + 2u) {
-        if (ctx->d_rows) VS_HIP(ctx, hipFree(ctx->d_rows));
-        ctx->d_rows = nullptr;
-        ctx->rows_cap = 0;
-        // per mode: counts, cursors, offsets; then the block sums of the scan (2 048 values per block, 64 bits each)
-        VS_HIP(ctx, hipMalloc(&ctx->d_rows, sizeof(uint32_t) * 6u * ((uint64_t)N + 2u) + sizeof(uint64_t) * ((uint64_t)N / 2048u + 8u)));
-        ctx->rows_cap = (uint64_t)N + 2u;
-    }
+    // per mode: counts, cursors, offsets; then the block sums of the scan (2 048 values per block, 64 bits each)
+    const uint64_t cap = (uint64_t)N + 2u;
+    VS_HIP(ctx, ctx->d_rows.reserve(sizeof(uint32_t) * 6u * cap + sizeof(uint64_t) * ((uint64_t)N / 2048u + 8u)));
     // the list table of a transposition: a power of two of slots, at least one per read end (VS_LTAB_BITS: tests crowd it)
     uint32_t ltab_bits = 10;
     while ((1ull << ltab_bits) < 2u * sub_pairs && ltab_bits < 31u) ltab_bits++;
@@ -2322,18 +2317,10 @@ static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_
     const uint64_t ltab_slots = use_ltab ? 1ull << ltab_bits : 0;
     // entries: one word per listed node -- the left lists (node_mat) and the lists of the owning ends (short_mat); the
     // multiplicity of every end, the owning ends, the table (a 64-bit word and a 32-bit sum per slot)
-    if (ctx->row_entries_cap < sub_pairs || ctx->ltab_cap < ltab_slots) {
-        for (void **q : {&ctx->d_row_entries, &ctx->d_mult, &ctx->d_ltab})
-            if (*q) { VS_HIP(ctx, hipFree(*q)); *q = nullptr; }
-        ctx->row_entries_cap = ctx->ltab_cap = 0;
-        VS_HIP(ctx, hipMalloc(&ctx->d_row_entries, sizeof(uint32_t) * (3u * sub_pairs * LCAP + 16u)));
-        VS_HIP(ctx, hipMalloc(&ctx->d_mult, sizeof(uint32_t) * (6u * sub_pairs + 4u)));  // mult[2 np], owners[2 np], gown[2 np]
-        VS_HIP(ctx, hipMalloc(&ctx->d_ltab, (sizeof(uint64_t) + sizeof(uint32_t)) * ltab_slots + 16u));
-        ctx->row_entries_cap = sub_pairs;
-        ctx->ltab_cap = ltab_slots;
-    }
-    const uint64_t cap = ctx->rows_cap;
-    uint32_t *rows = (uint32_t *)ctx->d_rows;
+    VS_HIP(ctx, ctx->d_row_entries.reserve(sizeof(uint32_t) * (3u * sub_pairs * LCAP + 16u)));
+    VS_HIP(ctx, ctx->d_mult.reserve(sizeof(uint32_t) * (6u * sub_pairs + 4u)));  // mult[2 np], owners[2 np], gown[2 np]
+    VS_HIP(ctx, ctx->d_ltab.reserve((sizeof(uint64_t) + sizeof(uint32_t)) * ltab_slots + 16u));
+    uint32_t *rows = ctx->d_rows.as<uint32_t>();
     uint64_t *scan_tmp = (uint64_t *)(rows + ((6u * cap + 1u) & ~1ull));
     const uint32_t keys_max = tn.rows_keys ? tn.rows_keys : ROWS_KEYS;
     const uint32_t n_keys = N < keys_max ? N : keys_max;
@@ -2350,19 +2337,19 @@ static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_
     // rows per strip: a strip's distinct cells should fill the table less than half.  configs[4]: 4 rows of node_mat hold
     // 1.7 k cells at the median and 6 k at most, 32 rows of short_mat 2.1 k and 6.6 k.  VS_ROWS_PER_STRIP overrides both.
     const uint32_t R = tn.rows_per_strip ? tn.rows_per_strip : 2u;
-    uint32_t *queue = (uint32_t *)ctx->d_slow_count + 9, *n_owners = (uint32_t *)ctx->d_slow_count + 15;
-    unsigned long long *ltab = use_ltab ? (unsigned long long *)ctx->d_ltab : nullptr;
-    uint32_t *lmult = use_ltab ? (uint32_t *)((unsigned long long *)ctx->d_ltab + ltab_slots) : nullptr;
+    uint32_t *queue = ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_STRIP_QUEUE, *n_owners = ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_OWNERS;
+    unsigned long long *ltab = use_ltab ? ctx->d_ltab.as<unsigned long long>() : nullptr;
+    uint32_t *lmult = use_ltab ? (uint32_t *)(ctx->d_ltab.as<unsigned long long>() + ltab_slots) : nullptr;
     for (uint64_t p0 = 0; p0 < slots_pairs; p0 += sub_pairs) {
         const uint64_t np = slots_pairs - p0 < sub_pairs ? slots_pairs - p0 : sub_pairs;
-        const uint32_t *sl = (const uint32_t *)ctx->d_lists + 2u * p0 * LC, *sh = (const uint32_t *)ctx->d_lists + 2u * slots_pairs * LC + 2u * p0 * 4u;
-        const uint32_t *sc = (const uint32_t *)ctx->d_list_counts + 2u * p0;
-        uint32_t *mult = (uint32_t *)ctx->d_mult, *owners = mult + 2u * sub_pairs, *gown = owners + 2u * sub_pairs;
+        const uint32_t *sl = ctx->d_lists.as<const uint32_t>() + 2u * p0 * LC, *sh = ctx->d_lists.as<const uint32_t>() + 2u * slots_pairs * LC + 2u * p0 * 4u;
+        const uint32_t *sc = ctx->d_list_counts.as<const uint32_t>() + 2u * p0;
+        uint32_t *mult = ctx->d_mult.as<uint32_t>(), *owners = mult + 2u * sub_pairs, *gown = owners + 2u * sub_pairs;
         const unsigned n_chunks = (unsigned)((np + ROWS_CHUNK - 1u) / ROWS_CHUNK);
         const unsigned n_chunks1 = (unsigned)((2u * np + ROWS_CHUNK1 - 1u) / ROWS_CHUNK1);  // (every end could be an owner; a chunk past the last owner returns at once)
         VS_HIP(ctx, hipMemsetAsync(rows, 0, sizeof(uint32_t) * 6u * cap, st));
         VS_HIP(ctx, hipMemsetAsync(n_owners, 0, sizeof(uint32_t), st));
-        if (use_ltab) VS_HIP(ctx, hipMemsetAsync(ctx->d_ltab, 0, (sizeof(uint64_t) + sizeof(uint32_t)) * ltab_slots, st));
+        if (use_ltab) VS_HIP(ctx, hipMemsetAsync(ctx->d_ltab.ptr(), 0, (sizeof(uint64_t) + sizeof(uint32_t)) * ltab_slots, st));
         hipLaunchKernelGGL(k_list_owners, dim3((unsigned)((2u * np + 255u) / 256u)), dim3(256), 0, st, sl, sh, sc, 2u * np, mult, gown, ltab, lmult, ltab_bits);
         if (use_ltab)
             hipLaunchKernelGGL(k_owners_mult, dim3((unsigned)((ltab_slots + 255u) / 256u)), dim3(256), 0, st, (const unsigned long long *)ltab,
@@ -2374,7 +2361,7 @@ static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_
         }
         for (int mode = 0; mode < 2; mode++) {
             uint32_t *row_count = rows + 3u * mode * cap, *row_cursor = row_count + cap, *row_ptr = row_cursor + cap;
-            uint32_t *entries = (uint32_t *)ctx->d_row_entries + (mode ? np * LCAP : 0u);
+            uint32_t *entries = ctx->d_row_entries.as<uint32_t>() + (mode ? np * LCAP : 0u);
             for (uint32_t key_lo = 0; key_lo < N; key_lo += n_keys) {
                 const uint32_t nk = N - key_lo < n_keys ? N - key_lo : n_keys;
                 if (mode) hipLaunchKernelGGL(k_rows_count<1>, dim3(n_chunks1), dim3(ROWS_TPB), rl, st, sl, sh, sc, (const uint32_t *)owners, 0ull, (const uint32_t *)n_owners, key_lo, nk, row_count);
@@ -2390,7 +2377,7 @@ static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_
         }
         for (int mode = 0; mode < 2; mode++) {
             const uint32_t *row_ptr = rows + 3u * mode * cap + 2u * cap;
-            const uint32_t *entries = (const uint32_t *)ctx->d_row_entries + (mode ? np * LCAP : 0u);
+            const uint32_t *entries = ctx->d_row_entries.as<const uint32_t>() + (mode ? np * LCAP : 0u);
             const uint32_t n_strips = (N + R - 1u) / R;
             uint32_t grid = (uint32_t)ctx->n_cu * 2u;  // (two workgroups per CU: 64 KB of LDS each)
             if (grid > n_strips) grid = n_strips;
@@ -2444,61 +2431,34 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     if (lds > 160u * 1024u)
         return vs_fail(ctx, VS_E_RANGE, "reads of %u bases with k+1=%u need %zu B of LDS per pair (limit 160 KiB)", maxlen, idx.K, lds);
 
-    // scratch: slow list (one slot per pair), counter, dense state
-    if (ctx->slow_cap < n_pairs) {
-        if (ctx->d_slow_list) VS_HIP(ctx, hipFree(ctx->d_slow_list));
-        ctx->d_slow_list = nullptr;
-        VS_HIP(ctx, hipMalloc(&ctx->d_slow_list, sizeof(uint32_t) * n_pairs));
-        ctx->slow_cap = n_pairs;
-    }
-    if (!ctx->d_slow_count) VS_HIP(ctx, hipMalloc(&ctx->d_slow_count, 64));  // [0] pairs for k_pe_mid, [1] k_pe_accumulate's chunk queue, [8] pairs for k_pe_slow, [9] k_rows_sum's strip queue, [15] owning ends (the other words unused)
-    if (ctx->slow2_cap < n_pairs) {
-        if (ctx->d_slow_list2) VS_HIP(ctx, hipFree(ctx->d_slow_list2));
-        ctx->d_slow_list2 = nullptr;
-        ctx->slow2_cap = 0;
-        VS_HIP(ctx, hipMalloc(&ctx->d_slow_list2, sizeof(uint32_t) * n_pairs));
-        ctx->slow2_cap = n_pairs;
-    }
+    // scratch: slow lists (one slot per pair), counters, dense state
+    VS_HIP(ctx, ctx->d_slow_list.reserve(sizeof(uint32_t) * n_pairs));
+    VS_HIP(ctx, ctx->d_slow_count.reserve(sizeof(uint32_t) * vs_ctx::SC_WORDS));
+    VS_HIP(ctx, ctx->d_slow_list2.reserve(sizeof(uint32_t) * n_pairs));
     const uint32_t SLOW_GRID = slow_grid_for(idx.n_nodes);
     uint64_t need_dense = sizeof(uint32_t) * (uint64_t)SLOW_WORDS_PER_NODE * (idx.n_nodes ? idx.n_nodes : 1) * SLOW_GRID;
-    if (ctx->dense_bytes < need_dense || ctx->dense_nodes != idx.n_nodes) {
-        if (ctx->d_dense) VS_HIP(ctx, hipFree(ctx->d_dense));
-        ctx->d_dense = nullptr;
-        ctx->dense_bytes = 0;
-        VS_HIP(ctx, hipMalloc(&ctx->d_dense, need_dense));
-        ctx->dense_bytes = need_dense;
+    if (ctx->dense_nodes != idx.n_nodes) ctx->d_dense.reset();  // (the layout is by node count)
+    bool dense_new = false;
+    VS_HIP(ctx, ctx->d_dense.reserve(need_dense, need_dense, &dense_new));
+    if (dense_new) {
         ctx->dense_nodes = idx.n_nodes;
         // cnt = 0, minp/minj = ~0 once; k_pe_slow restores this state after every end it sweeps
         uint64_t N = idx.n_nodes ? idx.n_nodes : 1;
-        VS_HIP(ctx, hipMemsetAsync(ctx->d_dense, 0xFF, need_dense, st));
+        VS_HIP(ctx, hipMemsetAsync(ctx->d_dense.ptr(), 0xFF, need_dense, st));
         hipLaunchKernelGGL(k_dense_zero_cnt, dim3((unsigned)((N * SLOW_GRID + TPB - 1) / TPB)), dim3(TPB), 0, st,
-                           (uint32_t *)ctx->d_dense, N, (uint64_t)SLOW_GRID);
+                           ctx->d_dense.as<uint32_t>(), N, (uint64_t)SLOW_GRID);
     }
-    VS_HIP(ctx, hipMemsetAsync(ctx->d_slow_count, 0, 64, st));
+    VS_HIP(ctx, hipMemsetAsync(ctx->d_slow_count.ptr(), 0, sizeof(uint32_t) * vs_ctx::SC_WORDS, st));
 
     // locus order of the pairs (see k_pe_locus); VS_NO_SORT=1 keeps the input order
     const bool use_sort = !tn.no_sort && n_pairs >= 4096 && n_pairs < 0xFFFFFFF0ull;
     if (use_sort) {
         const uint64_t nk = (uint64_t)idx.n_nodes + 2u;
-        if (ctx->locus_cap < n_pairs) {
-            if (ctx->d_locus_keys) VS_HIP(ctx, hipFree(ctx->d_locus_keys));
-            if (ctx->d_perm) VS_HIP(ctx, hipFree(ctx->d_perm));
-            ctx->d_locus_keys = ctx->d_perm = nullptr;
-            ctx->locus_cap = 0;
-            VS_HIP(ctx, hipMalloc(&ctx->d_locus_keys, sizeof(uint32_t) * n_pairs));
-            VS_HIP(ctx, hipMalloc(&ctx->d_perm, sizeof(uint32_t) * n_pairs));
-            ctx->locus_cap = n_pairs;
-        }
+        VS_HIP(ctx, ctx->d_locus_keys.reserve(sizeof(uint32_t) * n_pairs));
+        VS_HIP(ctx, ctx->d_perm.reserve(sizeof(uint32_t) * n_pairs));
         const uint64_t hist_words = nk <= LOCUS_LDS_MAX_PASSES * LOCUS_LDS_KEYS ? nk * LOCUS_WGS : nk;
-        if (ctx->hist_cap < hist_words) {
-            if (ctx->d_locus_hist) VS_HIP(ctx, hipFree(ctx->d_locus_hist));
-            if (ctx->d_scan_tmp) VS_HIP(ctx, hipFree(ctx->d_scan_tmp));
-            ctx->d_locus_hist = ctx->d_scan_tmp = nullptr;
-            ctx->hist_cap = 0;
-            VS_HIP(ctx, hipMalloc(&ctx->d_locus_hist, sizeof(uint32_t) * hist_words));
-            VS_HIP(ctx, hipMalloc(&ctx->d_scan_tmp, sizeof(uint64_t) * (hist_words / 2048 + 4)));
-            ctx->hist_cap = hist_words;
-        }
+        VS_HIP(ctx, ctx->d_locus_hist.reserve(sizeof(uint32_t) * hist_words));
+        VS_HIP(ctx, ctx->d_scan_tmp.reserve(sizeof(uint64_t) * (hist_words / 2048 + 4)));
     }
 
     // which counter kernels follow decides the layout of the hand-off: pair-major with one cell table while 2*N*N fits its
@@ -2513,22 +2473,16 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     const uint64_t n_tiles_all = (n_pairs + ept / 2 - 1) / (ept / 2);
     const uint64_t list_ends = n_tiles_all * ept;
     const uint64_t list_words = list_ends * (use_rows ? LC + 4u : LC) + 16u;  // (either layout of the hand-off)
-    if (d_node_mat && (ctx->lists_cap < list_ends || ctx->lists_words < list_words)) {
-        if (ctx->d_lists) VS_HIP(ctx, hipFree(ctx->d_lists));
-        if (ctx->d_list_counts) VS_HIP(ctx, hipFree(ctx->d_list_counts));
-        ctx->d_lists = ctx->d_list_counts = nullptr;
-        ctx->lists_cap = ctx->lists_words = 0;
-        VS_HIP(ctx, hipMalloc(&ctx->d_lists, sizeof(uint32_t) * list_words));
-        VS_HIP(ctx, hipMalloc(&ctx->d_list_counts, sizeof(uint32_t) * (list_ends + 2)));
-        ctx->lists_cap = list_ends;
-        ctx->lists_words = list_words;
+    if (d_node_mat) {
+        VS_HIP(ctx, ctx->d_lists.reserve(sizeof(uint32_t) * list_words));
+        VS_HIP(ctx, ctx->d_list_counts.reserve(sizeof(uint32_t) * (list_ends + 2)));
     }
 
     PeParams P;
     P.idx = idx;
     P.rd = reads->dev();
-    P.out_lists = (uint32_t *)ctx->d_lists;
-    P.out_counts = (uint32_t *)ctx->d_list_counts;
+    P.out_lists = ctx->d_lists.as<uint32_t>();
+    P.out_counts = ctx->d_list_counts.as<uint32_t>();
     P.node_mat = d_node_mat;
     P.short_mat = d_short_mat;
     P.stats = (unsigned long long *)d_stats;
@@ -2541,15 +2495,15 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     P.wpe = wpe;
     P.magic_pmax = pmax > 1u ? (uint32_t)(0x100000000ull / pmax) + 1u : 0u;
     P.magic_wpe = wpe > 1u ? (uint32_t)(0x100000000ull / wpe) + 1u : 0u;
-    P.perm = use_sort ? (const uint32_t *)ctx->d_perm : nullptr;
-    P.slow_list = (uint32_t *)ctx->d_slow_list;
-    P.slow_count = (uint32_t *)ctx->d_slow_count;
+    P.perm = use_sort ? ctx->d_perm.as<const uint32_t>() : nullptr;
+    P.slow_list = ctx->d_slow_list.as<uint32_t>();
+    P.slow_count = ctx->d_slow_count.as<uint32_t>();
     P.dbg_lists = d_dbg_lists;
     P.dbg_counts = d_dbg_counts;
     P.dbg_cap = dbg_cap;
     P.accumulate = d_node_mat ? 1u : 0u;
     P.out_rows = use_rows ? 1u : 0u;
-    P.out_lists_hi = (uint32_t *)ctx->d_lists + list_ends * LC;
+    P.out_lists_hi = ctx->d_lists.as<uint32_t>() + list_ends * LC;
     P.tile_map = d_node_mat ? d_tile_map : nullptr;
     P.tile_T = (idx.n_nodes + 63u) >> 6;
     // The shortcut spares a single posting its extension when the previous probe already owns the
@@ -2643,26 +2597,26 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
             for (uint32_t key_lo = 0; key_lo < nk; key_lo += per_pass) {
                 const uint32_t n_here = (uint32_t)(nk - key_lo < per_pass ? nk - key_lo : per_pass);
                 hipLaunchKernelGGL(k_locus_count, dim3(n_wg), dim3(LOCUS_TPB), lds_keys, st, idx, reads->dev(), n_pairs, chunk, n_wg,
-                                   (uint32_t *)ctx->d_locus_keys, (uint32_t *)ctx->d_locus_hist, key_lo, n_here, key_lo == 0u ? 1u : 0u);
+                                   ctx->d_locus_keys.as<uint32_t>(), ctx->d_locus_hist.as<uint32_t>(), key_lo, n_here, key_lo == 0u ? 1u : 0u);
             }
-            int rc = vs_scan_u32(ctx, (const uint32_t *)ctx->d_locus_hist, (uint32_t *)ctx->d_locus_hist, nk * n_wg,
-                                 (uint64_t *)ctx->d_scan_tmp, nullptr);
+            int rc = vs_scan_u32(ctx, ctx->d_locus_hist.as<const uint32_t>(), ctx->d_locus_hist.as<uint32_t>(), nk * n_wg,
+                                 ctx->d_scan_tmp.as<uint64_t>(), nullptr);
             if (rc) return rc;
             for (uint32_t key_lo = 0; key_lo < nk; key_lo += per_pass) {
                 const uint32_t n_here = (uint32_t)(nk - key_lo < per_pass ? nk - key_lo : per_pass);
                 hipLaunchKernelGGL(k_locus_scatter, dim3(n_wg), dim3(LOCUS_TPB), lds_keys, st, key_lo, n_here, n_pairs, chunk, n_wg,
-                                   (const uint32_t *)ctx->d_locus_keys, (const uint32_t *)ctx->d_locus_hist, (uint32_t *)ctx->d_perm);
+                                   ctx->d_locus_keys.as<const uint32_t>(), ctx->d_locus_hist.as<const uint32_t>(), ctx->d_perm.as<uint32_t>());
             }
         } else {
-            VS_HIP(ctx, hipMemsetAsync(ctx->d_locus_hist, 0, sizeof(uint32_t) * nk, st));
+            VS_HIP(ctx, hipMemsetAsync(ctx->d_locus_hist.ptr(), 0, sizeof(uint32_t) * nk, st));
             const unsigned pg = (unsigned)((n_pairs + TPB - 1) / TPB);
-            hipLaunchKernelGGL(k_pe_locus, dim3(pg), dim3(TPB), 0, st, idx, reads->dev(), n_pairs, (uint32_t *)ctx->d_locus_keys,
-                               (uint32_t *)ctx->d_locus_hist);
-            int rc = vs_scan_u32(ctx, (const uint32_t *)ctx->d_locus_hist, (uint32_t *)ctx->d_locus_hist, nk,
-                                 (uint64_t *)ctx->d_scan_tmp, nullptr);
+            hipLaunchKernelGGL(k_pe_locus, dim3(pg), dim3(TPB), 0, st, idx, reads->dev(), n_pairs, ctx->d_locus_keys.as<uint32_t>(),
+                               ctx->d_locus_hist.as<uint32_t>());
+            int rc = vs_scan_u32(ctx, ctx->d_locus_hist.as<const uint32_t>(), ctx->d_locus_hist.as<uint32_t>(), nk,
+                                 ctx->d_scan_tmp.as<uint64_t>(), nullptr);
             if (rc) return rc;
-            hipLaunchKernelGGL(k_pe_permute, dim3(pg), dim3(TPB), 0, st, n_pairs, (const uint32_t *)ctx->d_locus_keys,
-                               (uint32_t *)ctx->d_locus_hist, (uint32_t *)ctx->d_perm);
+            hipLaunchKernelGGL(k_pe_permute, dim3(pg), dim3(TPB), 0, st, n_pairs, ctx->d_locus_keys.as<const uint32_t>(),
+                               ctx->d_locus_hist.as<uint32_t>(), ctx->d_perm.as<uint32_t>());
         }
     }
     VS_HIP(ctx, hipEventRecord(ctx->ev[0], st));
@@ -2676,7 +2630,7 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
         // the last tile may be partly empty: its unused rows must read as length 0
         const uint64_t used_ends = 2ull * n_pairs;
         if (list_ends > used_ends)
-            VS_HIP(ctx, hipMemsetAsync((uint32_t *)ctx->d_list_counts + used_ends, 0, sizeof(uint32_t) * (list_ends - used_ends), st));
+            VS_HIP(ctx, hipMemsetAsync(ctx->d_list_counts.as<uint32_t>() + used_ends, 0, sizeof(uint32_t) * (list_ends - used_ends), st));
         const uint64_t slots_pairs = list_ends / 2;
         VS_HIP(ctx, hipEventRecord(ctx->ev[4], st));
         if (use_rows) {
@@ -2693,18 +2647,18 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
             // the chunks are not bound to workgroups: two workgroups per CU take the next chunk off a
             // counter whenever they are free, so a cell table lives across chunks and is written out on
             // fill only (3.85 -> 3.6 ms against one workgroup per chunk)
-            uint32_t *acc_queue = (uint32_t *)ctx->d_slow_count + 1;
+            uint32_t *acc_queue = ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_ACC_QUEUE;
             if (acc_grid > (uint32_t)ctx->n_cu * 2u) acc_grid = (uint32_t)ctx->n_cu * 2u;
             // the table is written out once this many of its slots are taken: probing stays short at a low
             // fill, and cells of loci the run has left do not pile up (VS_ACC_FILL: percent)
             uint32_t fill_limit = ACC_SLOTS / 16u;
             if (tn.acc_fill_pct >= 0) fill_limit = (uint32_t)((uint64_t)ACC_SLOTS * (uint32_t)tn.acc_fill_pct / 100u);
             if (d_tile_map && slots_pairs)  // (timed with the counter kernel: it is part of the counting)
-                hipLaunchKernelGGL(k_mark_tiles, dim3((unsigned)((slots_pairs + 255u) / 256u)), dim3(256), 0, st, (const uint32_t *)ctx->d_lists,
-                                   (const uint32_t *)ctx->d_list_counts, slots_pairs, d_tile_map, P.tile_T, ept);
+                hipLaunchKernelGGL(k_mark_tiles, dim3((unsigned)((slots_pairs + 255u) / 256u)), dim3(256), 0, st, ctx->d_lists.as<const uint32_t>(),
+                                   ctx->d_list_counts.as<const uint32_t>(), slots_pairs, d_tile_map, P.tile_T, ept);
             VS_HIP(ctx, hipFuncSetAttribute((const void *)k_pe_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ACC_LDS_BYTES));
-            hipLaunchKernelGGL(k_pe_accumulate, dim3(acc_grid), dim3(ACC_TPB), ACC_LDS_BYTES, st, (const uint32_t *)ctx->d_lists,
-                               (const uint32_t *)ctx->d_list_counts, slots_pairs, per_wg, idx.n_nodes, use_table, fill_limit, d_node_mat,
+            hipLaunchKernelGGL(k_pe_accumulate, dim3(acc_grid), dim3(ACC_TPB), ACC_LDS_BYTES, st, ctx->d_lists.as<const uint32_t>(),
+                               ctx->d_list_counts.as<const uint32_t>(), slots_pairs, per_wg, idx.n_nodes, use_table, fill_limit, d_node_mat,
                                d_short_mat, acc_queue, ept);
         }
     }
@@ -2712,13 +2666,13 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     // overflow pairs: one wavefront per pair with its state in LDS first, the general kernel for what that cannot hold
     ctx->last_launched |= tn.no_mid ? 0u : VS_RAN_PE_MID;
     if (!tn.no_mid) {
-        hipLaunchKernelGGL(k_pe_mid, dim3((unsigned)ctx->n_cu * 8u), dim3(TPB), 0, st, P, (const uint32_t *)ctx->d_slow_list,
-                           (const uint32_t *)ctx->d_slow_count, (uint32_t)n_pairs, (uint32_t *)ctx->d_slow_list2, (uint32_t *)ctx->d_slow_count + 8);
-        hipLaunchKernelGGL(k_pe_slow, dim3(SLOW_GRID), dim3(TPB), 0, st, P, (uint32_t *)ctx->d_dense, (uint32_t)n_pairs,
-                           (const uint32_t *)ctx->d_slow_list2, (const uint32_t *)ctx->d_slow_count + 8);
+        hipLaunchKernelGGL(k_pe_mid, dim3((unsigned)ctx->n_cu * 8u), dim3(TPB), 0, st, P, ctx->d_slow_list.as<const uint32_t>(),
+                           ctx->d_slow_count.as<const uint32_t>(), (uint32_t)n_pairs, ctx->d_slow_list2.as<uint32_t>(), ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_SLOW);
+        hipLaunchKernelGGL(k_pe_slow, dim3(SLOW_GRID), dim3(TPB), 0, st, P, ctx->d_dense.as<uint32_t>(), (uint32_t)n_pairs,
+                           ctx->d_slow_list2.as<const uint32_t>(), ctx->d_slow_count.as<const uint32_t>() + vs_ctx::SC_SLOW);
     } else {
-        hipLaunchKernelGGL(k_pe_slow, dim3(SLOW_GRID), dim3(TPB), 0, st, P, (uint32_t *)ctx->d_dense, (uint32_t)n_pairs,
-                           (const uint32_t *)ctx->d_slow_list, (const uint32_t *)ctx->d_slow_count);
+        hipLaunchKernelGGL(k_pe_slow, dim3(SLOW_GRID), dim3(TPB), 0, st, P, ctx->d_dense.as<uint32_t>(), (uint32_t)n_pairs,
+                           ctx->d_slow_list.as<const uint32_t>(), ctx->d_slow_count.as<const uint32_t>());
     }
     VS_HIP(ctx, hipEventRecord(ctx->ev[2], st));
     VS_HIP(ctx, hipGetLastError());
@@ -2764,7 +2718,7 @@ extern "C" int vs_pe_last_timing(vs_ctx *ctx, double ms[5]) {
     VS_HIP(ctx, hipEventElapsedTime(&c, ctx->ev[3], ctx->ev[0]));
     ctx->last_sort_ms = c;
     uint32_t n_slow = 0;
-    VS_HIP(ctx, hipMemcpy(&n_slow, ctx->d_slow_count, sizeof n_slow, hipMemcpyDeviceToHost));
+    VS_HIP(ctx, hipMemcpy(&n_slow, ctx->d_slow_count.ptr(), sizeof n_slow, hipMemcpyDeviceToHost));
     ms[0] = a; ms[1] = b; ms[2] = (double)n_slow; ms[3] = c; ms[4] = d;
     ctx->last_ms[0] = a; ctx->last_ms[1] = b; ctx->last_ms[2] = n_slow;
     return VS_OK;
@@ -2775,18 +2729,16 @@ extern "C" int vs_pe_map_ends(vs_ctx *ctx, const vs_reads *reads, uint32_t cap, 
     VS_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t n = reads->n_ends;
     if (!n) return VS_OK;
-    uint32_t *d_lists = nullptr, *d_counts = nullptr;
-    VS_HIP(ctx, hipMalloc((void **)&d_lists, sizeof(uint32_t) * n * cap));
-    hipError_t e1 = hipMalloc((void **)&d_counts, sizeof(uint32_t) * n);
-    int rc = VS_OK;
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * n, ctx->stream);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(d_lists, 0xFF, sizeof(uint32_t) * n * cap, ctx->stream);
-    if (e1 == hipSuccess) rc = pe_launch(ctx, reads, nullptr, nullptr, nullptr, d_lists, d_counts, cap);
-    if (e1 == hipSuccess && rc == VS_OK) e1 = hipMemcpyAsync(lists, d_lists, sizeof(uint32_t) * n * cap, hipMemcpyDeviceToHost, ctx->stream);
-    if (e1 == hipSuccess && rc == VS_OK) e1 = hipMemcpyAsync(counts, d_counts, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e1 == hipSuccess && rc == VS_OK) e1 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_lists);
-    if (d_counts) (void)hipFree(d_counts);
-    if (e1 != hipSuccess) return vs_fail(ctx, VS_E_HIP, "vs_pe_map_ends: %s", hipGetErrorString(e1));
+    VsDevBuf lists_buf, counts_buf;
+    VS_HIP(ctx, lists_buf.reserve(sizeof(uint32_t) * n * cap));
+    VS_HIP(ctx, counts_buf.reserve(sizeof(uint32_t) * n));
+    uint32_t *d_lists = lists_buf.as<uint32_t>(), *d_counts = counts_buf.as<uint32_t>();
+    VS_HIP(ctx, hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * n, ctx->stream));
+    VS_HIP(ctx, hipMemsetAsync(d_lists, 0xFF, sizeof(uint32_t) * n * cap, ctx->stream));
+    const int rc = pe_launch(ctx, reads, nullptr, nullptr, nullptr, d_lists, d_counts, cap);
+    if (rc != VS_OK) return rc;
+    VS_HIP(ctx, hipMemcpyAsync(lists, d_lists, sizeof(uint32_t) * n * cap, hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipMemcpyAsync(counts, d_counts, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return rc;
 }

@@ -100,13 +100,13 @@ static int alloc_reads(vs_ctx *ctx, vs_reads *r, bool with_mask) {
     size_t b_woff = sizeof(uint32_t) * (r->n_ends + 1);
     size_t b_meta = sizeof(uint32_t) * (r->n_ends ? r->n_ends : 1);
     size_t b_words = sizeof(uint32_t) * (r->n_words + VS_PAD_WORDS);
-    VS_HIP(ctx, hipMalloc(&r->d_woff, b_woff));
-    VS_HIP(ctx, hipMalloc(&r->d_meta, b_meta));
-    VS_HIP(ctx, hipMalloc(&r->d_words, b_words));
+    VS_HIP(ctx, r->own_alloc(r->d_woff, b_woff));
+    VS_HIP(ctx, r->own_alloc(r->d_meta, b_meta));
+    VS_HIP(ctx, r->own_alloc(r->d_words, b_words));
     VS_HIP(ctx, hipMemsetAsync((char *)r->d_words + sizeof(uint32_t) * r->n_words, 0, VS_PAD_WORDS * sizeof(uint32_t), ctx->stream));
     r->bytes = b_woff + b_meta + b_words;
     if (with_mask) {
-        VS_HIP(ctx, hipMalloc(&r->d_mask, b_words));
+        VS_HIP(ctx, r->own_alloc(r->d_mask, b_words));
         VS_HIP(ctx, hipMemsetAsync((char *)r->d_mask + sizeof(uint32_t) * r->n_words, 0, VS_PAD_WORDS * sizeof(uint32_t), ctx->stream));
         r->bytes += b_words;
     }
@@ -119,18 +119,58 @@ extern "C" void vs_reads_free(vs_ctx *ctx, vs_reads *r) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    void *ps[] = {r->d_woff, r->d_meta, r->d_words, r->d_mask, r->d_inv4};
-    for (void *p : ps) {
-        if (!p) continue;
-        if (r->cached && ctx) vs_cache_release(ctx, p);
-        else (void)hipFree(p);
-    }
-    delete r;
+    if (r->cached && ctx)
+        for (void *p : {r->d_woff, r->d_meta, r->d_words, r->d_mask, r->d_inv4}) vs_cache_release(ctx, p);
+    delete r;  // (what the block owns itself goes with it)
 }
 
 extern "C" int vs_reads_info(const vs_reads *r, uint64_t info[5]) {
     if (!r || !info) return VS_E_ARG;
     info[0] = r->n_ends; info[1] = r->n_words; info[2] = r->max_len; info[3] = r->n_invalid; info[4] = r->bytes;
+    return VS_OK;
+}
+
+// the device side of vs_reads_pack: r's arrays are allocated, woff / meta are the host's word offsets and lengths
+static int pack_block(vs_ctx *ctx, vs_reads *r, const uint8_t *ascii, const uint64_t *off, const std::vector<uint32_t> &woff, const std::vector<uint32_t> &meta) {
+    const uint64_t n_ends = r->n_ends, words = r->n_words, total = off[n_ends];
+    hipStream_t st = ctx->stream;
+    VsDevBuf ascii_buf, aoff_buf, cnt_buf;
+    VS_HIP(ctx, ascii_buf.reserve(total + 16));
+    VS_HIP(ctx, aoff_buf.reserve(sizeof(uint64_t) * (n_ends + 1)));
+    VS_HIP(ctx, cnt_buf.reserve(sizeof(uint32_t)));
+    uint8_t *d_ascii = ascii_buf.as<uint8_t>();
+    uint64_t *d_aoff = aoff_buf.as<uint64_t>();
+    uint32_t *d_cnt = cnt_buf.as<uint32_t>();
+    if (total) VS_HIP(ctx, hipMemcpyAsync(d_ascii, ascii, total, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemcpyAsync(d_aoff, off, sizeof(uint64_t) * (n_ends + 1), hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemcpyAsync(r->d_woff, woff.data(), sizeof(uint32_t) * (n_ends + 1), hipMemcpyHostToDevice, st));
+    if (n_ends) VS_HIP(ctx, hipMemcpyAsync(r->d_meta, meta.data(), sizeof(uint32_t) * n_ends, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), st));
+    unsigned nbw = (unsigned)((words + TPB - 1) / TPB);
+    if (words)
+        hipLaunchKernelGGL(k_pack_reads, dim3(nbw), dim3(TPB), 0, st, d_ascii, d_aoff, (const uint32_t *)r->d_woff, n_ends,
+                           (uint32_t)words, (uint32_t *)r->d_words, (uint32_t *)nullptr, (uint32_t *)r->d_meta);
+    if (n_ends)
+        hipLaunchKernelGGL(k_count_invalid, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st,
+                           (const uint32_t *)r->d_meta, n_ends, d_cnt);
+    uint32_t h_cnt = 0;
+    VS_HIP(ctx, hipMemcpyAsync(&h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
+    r->n_invalid = h_cnt;
+    if (h_cnt) {  // rare: some end holds a byte outside ACGTN -> build the validity mask too
+        size_t b_words = sizeof(uint32_t) * (words + VS_PAD_WORDS);
+        VS_HIP(ctx, r->own_alloc(r->d_mask, b_words));
+        VS_HIP(ctx, hipMemsetAsync(r->d_mask, 0, b_words, st));
+        r->bytes += b_words;
+        hipLaunchKernelGGL(k_pack_reads, dim3(nbw), dim3(TPB), 0, st, d_ascii, d_aoff, (const uint32_t *)r->d_woff, n_ends,
+                           (uint32_t)words, (uint32_t *)r->d_words, (uint32_t *)r->d_mask, (uint32_t *)r->d_meta);
+        VS_HIP(ctx, r->own_alloc(r->d_inv4, sizeof(uint32_t) * n_ends));
+        r->bytes += sizeof(uint32_t) * n_ends;
+        hipLaunchKernelGGL(k_inv4, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st, (const uint32_t *)r->d_woff,
+                           (const uint32_t *)r->d_mask, n_ends, (uint32_t *)r->d_meta, (uint32_t *)r->d_inv4);
+    }
+    VS_HIP(ctx, hipGetLastError());
+    VS_HIP(ctx, hipStreamSynchronize(st));  // (the temporaries die here)
     return VS_OK;
 }
 
@@ -156,54 +196,8 @@ extern "C" int vs_reads_pack(vs_ctx *ctx, const uint8_t *ascii, const uint64_t *
     woff[n_ends] = (uint32_t)words;
     r->n_words = words;
     r->max_len = maxlen;
-    uint8_t *d_ascii = nullptr;
-    uint64_t *d_aoff = nullptr;
-    uint32_t *d_cnt = nullptr;
     int rc = alloc_reads(ctx, r, false);
-    hipStream_t st = ctx->stream;
-    uint64_t total = off[n_ends];
-    hipError_t e1 = hipSuccess;
-    if (rc == VS_OK) {
-        do {
-            if ((e1 = hipMalloc((void **)&d_ascii, total + 16)) != hipSuccess) break;
-            if ((e1 = hipMalloc((void **)&d_aoff, sizeof(uint64_t) * (n_ends + 1))) != hipSuccess) break;
-            if ((e1 = hipMalloc((void **)&d_cnt, sizeof(uint32_t))) != hipSuccess) break;
-            if (total && (e1 = hipMemcpyAsync(d_ascii, ascii, total, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-            if ((e1 = hipMemcpyAsync(d_aoff, off, sizeof(uint64_t) * (n_ends + 1), hipMemcpyHostToDevice, st)) != hipSuccess) break;
-            if ((e1 = hipMemcpyAsync(r->d_woff, woff.data(), sizeof(uint32_t) * (n_ends + 1), hipMemcpyHostToDevice, st)) != hipSuccess) break;
-            if (n_ends && (e1 = hipMemcpyAsync(r->d_meta, meta.data(), sizeof(uint32_t) * n_ends, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-            if ((e1 = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), st)) != hipSuccess) break;
-            unsigned nbw = (unsigned)((words + TPB - 1) / TPB);
-            if (words)
-                hipLaunchKernelGGL(k_pack_reads, dim3(nbw), dim3(TPB), 0, st, d_ascii, d_aoff, (const uint32_t *)r->d_woff, n_ends,
-                                   (uint32_t)words, (uint32_t *)r->d_words, (uint32_t *)nullptr, (uint32_t *)r->d_meta);
-            if (n_ends)
-                hipLaunchKernelGGL(k_count_invalid, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st,
-                                   (const uint32_t *)r->d_meta, n_ends, d_cnt);
-            uint32_t h_cnt = 0;
-            if ((e1 = hipMemcpyAsync(&h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-            if ((e1 = hipStreamSynchronize(st)) != hipSuccess) break;
-            r->n_invalid = h_cnt;
-            if (h_cnt) {  // rare: some end holds a byte outside ACGTN -> build the validity mask too
-                size_t b_words = sizeof(uint32_t) * (words + VS_PAD_WORDS);
-                if ((e1 = hipMalloc(&r->d_mask, b_words)) != hipSuccess) break;
-                if ((e1 = hipMemsetAsync(r->d_mask, 0, b_words, st)) != hipSuccess) break;
-                r->bytes += b_words;
-                hipLaunchKernelGGL(k_pack_reads, dim3(nbw), dim3(TPB), 0, st, d_ascii, d_aoff, (const uint32_t *)r->d_woff, n_ends,
-                                   (uint32_t)words, (uint32_t *)r->d_words, (uint32_t *)r->d_mask, (uint32_t *)r->d_meta);
-                if ((e1 = hipMalloc(&r->d_inv4, sizeof(uint32_t) * n_ends)) != hipSuccess) break;
-                r->bytes += sizeof(uint32_t) * n_ends;
-                hipLaunchKernelGGL(k_inv4, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st, (const uint32_t *)r->d_woff,
-                                   (const uint32_t *)r->d_mask, n_ends, (uint32_t *)r->d_meta, (uint32_t *)r->d_inv4);
-            }
-            if ((e1 = hipGetLastError()) != hipSuccess) break;
-            e1 = hipStreamSynchronize(st);
-        } while (0);
-        if (e1 != hipSuccess) rc = vs_fail(ctx, e1 == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, "vs_reads_pack: %s", hipGetErrorString(e1));
-    }
-    if (d_ascii) (void)hipFree(d_ascii);
-    if (d_aoff) (void)hipFree(d_aoff);
-    if (d_cnt) (void)hipFree(d_cnt);
+    if (rc == VS_OK) rc = pack_block(ctx, r, ascii, off, woff, meta);
     if (rc != VS_OK) { vs_reads_free(ctx, r); return rc; }
     *out = r;
     return VS_OK;
@@ -225,19 +219,15 @@ extern "C" int vs_reads_unpack(vs_ctx *ctx, const vs_reads *r, uint8_t *out, uin
     }
     ooff[r->n_ends] = tot;
     if (!tot) return VS_OK;
-    uint64_t *d_ooff = nullptr;
-    uint8_t *d_out = nullptr;
-    VS_HIP(ctx, hipMalloc((void **)&d_ooff, sizeof(uint64_t) * (r->n_ends + 1)));
-    hipError_t e1 = hipMalloc((void **)&d_out, tot);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(d_ooff, ooff.data(), sizeof(uint64_t) * (r->n_ends + 1), hipMemcpyHostToDevice, ctx->stream);
-    if (e1 == hipSuccess) {
-        hipLaunchKernelGGL(k_unpack_reads, dim3((unsigned)((r->n_ends + TPB - 1) / TPB)), dim3(TPB), 0, ctx->stream, r->dev(), d_ooff, d_out);
-        e1 = hipMemcpyAsync(out, d_out, tot, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_ooff);
-    if (d_out) (void)hipFree(d_out);
-    if (e1 != hipSuccess) return vs_fail(ctx, VS_E_HIP, "vs_reads_unpack: %s", hipGetErrorString(e1));
+    VsDevBuf ooff_buf, out_buf;
+    VS_HIP(ctx, ooff_buf.reserve(sizeof(uint64_t) * (r->n_ends + 1)));
+    VS_HIP(ctx, out_buf.reserve(tot));
+    uint64_t *d_ooff = ooff_buf.as<uint64_t>();
+    uint8_t *d_out = out_buf.as<uint8_t>();
+    VS_HIP(ctx, hipMemcpyAsync(d_ooff, ooff.data(), sizeof(uint64_t) * (r->n_ends + 1), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_unpack_reads, dim3((unsigned)((r->n_ends + TPB - 1) / TPB)), dim3(TPB), 0, ctx->stream, r->dev(), d_ooff, d_out);
+    VS_HIP(ctx, hipMemcpyAsync(out, d_out, tot, hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VS_OK;
 }
 
@@ -310,6 +300,35 @@ __global__ void __launch_bounds__(TPB) k_iota_woff(uint32_t *woff, uint64_t n, u
     if (i < n) woff[i] = (uint32_t)(i * stride);
 }
 
+// the device side of vs_synth_pairs: r's arrays are allocated
+static int synth_block(vs_ctx *ctx, vs_reads *r, const std::vector<uint32_t> &gwords, const std::vector<uint64_t> &gbase, const std::vector<uint64_t> &glen,
+                       const uint32_t *cum, uint64_t seed, uint64_t first_pair, uint32_t read_len, uint32_t sub_thresh, uint32_t n_thresh) {
+    const uint32_t n_strains = (uint32_t)gbase.size(), wpe = (read_len + 15) / 16;
+    hipStream_t st = ctx->stream;
+    VsDevBuf d_gw, d_cum, d_gb, d_gl;
+    VS_HIP(ctx, d_gw.reserve(sizeof(uint32_t) * gwords.size()));
+    VS_HIP(ctx, d_cum.reserve(sizeof(uint32_t) * n_strains));
+    VS_HIP(ctx, d_gb.reserve(sizeof(uint64_t) * n_strains));
+    VS_HIP(ctx, d_gl.reserve(sizeof(uint64_t) * n_strains));
+    VS_HIP(ctx, hipMemcpyAsync(d_gw.ptr(), gwords.data(), sizeof(uint32_t) * gwords.size(), hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemcpyAsync(d_cum.ptr(), cum, sizeof(uint32_t) * n_strains, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemcpyAsync(d_gb.ptr(), gbase.data(), sizeof(uint64_t) * n_strains, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemcpyAsync(d_gl.ptr(), glen.data(), sizeof(uint64_t) * n_strains, hipMemcpyHostToDevice, st));
+    SynthParams P;
+    P.gwords = d_gw.as<uint32_t>(); P.gbase = d_gb.as<uint64_t>(); P.glen = d_gl.as<uint64_t>(); P.cum = d_cum.as<uint32_t>(); P.n_strains = n_strains;
+    P.seed = seed; P.first_pair = first_pair; P.n_pairs = r->n_ends / 2; P.read_len = read_len;
+    P.words_per_end = wpe; P.sub_thresh = sub_thresh; P.n_thresh = n_thresh;
+    uint64_t nthreads = r->n_words;
+    if (nthreads)
+        hipLaunchKernelGGL(k_synth, dim3((unsigned)((nthreads + TPB - 1) / TPB)), dim3(TPB), 0, st, P,
+                           (uint32_t *)r->d_words, (uint32_t *)r->d_meta);
+    hipLaunchKernelGGL(k_iota_woff, dim3((unsigned)((r->n_ends + 1 + TPB - 1) / TPB)), dim3(TPB), 0, st,
+                       (uint32_t *)r->d_woff, r->n_ends + 1, wpe);
+    VS_HIP(ctx, hipGetLastError());
+    VS_HIP(ctx, hipStreamSynchronize(st));  // (the temporaries die here)
+    return VS_OK;
+}
+
 extern "C" int vs_synth_pairs(vs_ctx *ctx, const uint8_t *genomes, const uint64_t *goff, const uint32_t *cum,
                               uint32_t n_strains, uint64_t seed, uint64_t first_pair, uint64_t n_pairs, uint32_t read_len,
                               uint32_t sub_thresh, uint32_t n_thresh, vs_reads **out) {
@@ -342,38 +361,7 @@ extern "C" int vs_synth_pairs(vs_ctx *ctx, const uint8_t *genomes, const uint64_
     r->n_words = 2 * n_pairs * wpe;
     r->max_len = read_len;
     int rc = alloc_reads(ctx, r, false);
-    uint32_t *d_gw = nullptr, *d_cum = nullptr;
-    uint64_t *d_gb = nullptr, *d_gl = nullptr;
-    hipStream_t st = ctx->stream;
-    hipError_t e1 = hipSuccess;
-    if (rc == VS_OK) {
-        do {
-            if ((e1 = hipMalloc((void **)&d_gw, sizeof(uint32_t) * gwords.size())) != hipSuccess) break;
-            if ((e1 = hipMalloc((void **)&d_cum, sizeof(uint32_t) * n_strains)) != hipSuccess) break;
-            if ((e1 = hipMalloc((void **)&d_gb, sizeof(uint64_t) * n_strains)) != hipSuccess) break;
-            if ((e1 = hipMalloc((void **)&d_gl, sizeof(uint64_t) * n_strains)) != hipSuccess) break;
-            if ((e1 = hipMemcpyAsync(d_gw, gwords.data(), sizeof(uint32_t) * gwords.size(), hipMemcpyHostToDevice, st)) != hipSuccess) break;
-            if ((e1 = hipMemcpyAsync(d_cum, cum, sizeof(uint32_t) * n_strains, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-            if ((e1 = hipMemcpyAsync(d_gb, gbase.data(), sizeof(uint64_t) * n_strains, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-            if ((e1 = hipMemcpyAsync(d_gl, glen.data(), sizeof(uint64_t) * n_strains, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-            SynthParams P;
-            P.gwords = d_gw; P.gbase = d_gb; P.glen = d_gl; P.cum = d_cum; P.n_strains = n_strains;
-            P.seed = seed; P.first_pair = first_pair; P.n_pairs = n_pairs; P.read_len = read_len;
-            P.words_per_end = wpe; P.sub_thresh = sub_thresh; P.n_thresh = n_thresh;
-            uint64_t nthreads = r->n_words;
-            if (nthreads)
-                hipLaunchKernelGGL(k_synth, dim3((unsigned)((nthreads + TPB - 1) / TPB)), dim3(TPB), 0, st, P,
-                                   (uint32_t *)r->d_words, (uint32_t *)r->d_meta);
-            hipLaunchKernelGGL(k_iota_woff, dim3((unsigned)((r->n_ends + 1 + TPB - 1) / TPB)), dim3(TPB), 0, st,
-                               (uint32_t *)r->d_woff, r->n_ends + 1, wpe);
-            if ((e1 = hipGetLastError()) != hipSuccess) break;
-            e1 = hipStreamSynchronize(st);
-        } while (0);
-        if (e1 != hipSuccess) rc = vs_fail(ctx, e1 == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, "vs_synth_pairs: %s", hipGetErrorString(e1));
-    }
-    void *tmps[] = {d_gw, d_cum, d_gb, d_gl};
-    for (void *p : tmps)
-        if (p) (void)hipFree(p);
+    if (rc == VS_OK) rc = synth_block(ctx, r, gwords, gbase, glen, cum, seed, first_pair, read_len, sub_thresh, n_thresh);
     if (rc != VS_OK) { vs_reads_free(ctx, r); return rc; }
     *out = r;
     return VS_OK;

@@ -269,13 +269,12 @@ __global__ void __launch_bounds__(SL_TPB) k_sl_pack(SlWin f0, SlWin f1, uint32_t
 namespace {
 
 struct Slot {
-    uint8_t *p = nullptr;
+    VsPinnedBuf buf;          // slot_cap bytes, pinned by the reader at first use
     size_t len = 0;  // bytes of text, or of deflate payloads when n_members > 0 or comp
     bool last = false;
     bool comp = false;        // payloads of BGZF members + their directory at the slot's end (the last member first)
     uint32_t n_members = 0;
     size_t text = 0;          // what the members inflate to (the ISIZE sum)
-    size_t cap = 0;
 };
 
 // One file read front to back by a thread of its own into the ring.  The consumer takes filled slots in order and gives
@@ -366,12 +365,9 @@ struct Reader {
                 if (stop) break;
                 slot = &slots[filled % STREAM_RING_SLOTS];  // (free: the consumer gave it back)
             }
-            if (!slot->p && hipHostMalloc((void **)&slot->p, slot_cap, hipHostMallocDefault) != hipSuccess) {
-                slot->p = nullptr;
+            if (slot->buf.reserve(slot_cap) != hipSuccess)
                 fail(VS_E_OOM, "%s: cannot pin a %s-byte chunk", path.c_str(), std::to_string(slot_cap).c_str());
-            }
-            slot->cap = slot_cap;
-            uint8_t *dst = slot->p;
+            uint8_t *dst = slot->buf.as<uint8_t>();
             if (!dst) { publish(0, true); break; }
             size_t len = 0;
             bool bad = false;
@@ -510,35 +506,27 @@ struct Reader {
         }
         cv.notify_all();
         if (th.joinable()) th.join();
-        for (Slot &s : slots)
-            if (s.p) (void)hipHostFree(s.p);
+        for (Slot &s : slots) s.buf.reset();
         if (fd >= 0) close(fd);
         fd = -1;
     }
 };
 
+// room for `need` elements of T, a quarter more when the buffer has to grow (what it held is not kept)
 template <typename T>
-int grow(vs_ctx *ctx, T *&p, size_t &cap, size_t need) {
-    if (cap >= need) return VS_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t n = need + need / 4 + 64;
-    VS_HIP(ctx, hipMalloc((void **)&p, n * sizeof(T)));
-    cap = n;
+int reserve_n(vs_ctx *ctx, VsDevBuf &b, size_t need) {
+    VS_HIP(ctx, b.reserve(need * sizeof(T), (need + need / 4 + 64) * sizeof(T)));
     return VS_OK;
 }
 
 // The device side of one file: the window (two buffers, the leftover copied from one to the other after a block) and
 // its line ends.
 struct DevFile {
-    uint8_t *win[2] = {nullptr, nullptr};
-    size_t win_cap[2] = {0, 0};
+    VsDevBuf win[2];       // bytes
     int cur = 0;
     size_t size = 0;       // bytes in the window
     size_t validated = 0;  // [0, validated) is known to be valid UTF-8 (ASCII, or checked on the host)
-    uint32_t *ends = nullptr, *wg = nullptr;
-    size_t ends_cap = 0, wg_cap = 0;
+    VsDevBuf ends, wg;     // uint32
     uint32_t n_nl = 0, flags = 0, last_byte = 0;
     uint64_t records = 0;  // complete records in the window
     uint64_t first_record = 0;  // file-wide number of the window's first record
@@ -548,10 +536,7 @@ struct DevFile {
     uint32_t pend[4] = {0, 0, 0, 0};  // (end-of-input check) bytes of a character cut by a chunk boundary
     uint32_t n_pend = 0;
     // BGZF: the device copy of a slot's payloads and directory, a status word per member
-    uint8_t *comp = nullptr;
-    vs_bgzf_member *dir = nullptr;
-    uint32_t *mstat = nullptr;
-    size_t comp_cap = 0, dir_cap = 0, mstat_cap = 0;
+    VsDevBuf comp, dir, mstat;  // bytes, vs_bgzf_member, uint32
     uint64_t members_dev = 0;  // members the device inflated so far
     uint32_t slot_base = 0;    // running index of the first member of the slot appended last
 };
@@ -563,9 +548,10 @@ struct vs_fastq_stream {
     hipStream_t st = nullptr;
     Reader rd[2];
     DevFile df[2];
-    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // ST_ALL words each (h_stat pinned)
-    uint32_t *d_wcnt = nullptr;
-    size_t wcnt_cap = 0;
+    VsDevBuf stat_buf;
+    VsPinnedBuf h_stat_buf;
+    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // ST_ALL words each, in the two buffers above
+    VsDevBuf d_wcnt;  // uint32
     uint64_t pairs = 0;
     uint32_t flags_seen = 0;
     bool done = false;
@@ -590,11 +576,11 @@ int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
         if (only >= 0 && f != only) continue;
         DevFile &d = s->df[f];
         const uint64_t words = (d.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
-        if (int rc = grow(ctx, d.wg, d.wg_cap, wgs + 1u)) return rc;
+        if (int rc = reserve_n<uint32_t>(ctx, d.wg, wgs + 1u)) return rc;
         if (wgs) {
-            hipLaunchKernelGGL(k_sl_count, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, (const uint8_t *)d.win[d.cur], (uint64_t)d.size, d.wg,
+            hipLaunchKernelGGL(k_sl_count, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, d.win[d.cur].as<const uint8_t>(), (uint64_t)d.size, d.wg.as<uint32_t>(),
                                s->d_stat + f * ST_PER_FILE);
-            hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, d.wg, (uint32_t)wgs, s->d_stat + f * ST_PER_FILE + ST_NL);
+            hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, d.wg.as<uint32_t>(), (uint32_t)wgs, s->d_stat + f * ST_PER_FILE + ST_NL);
         }
     }
     VS_HIP(ctx, hipGetLastError());
@@ -619,7 +605,7 @@ int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
 int translate_window(vs_ctx *ctx, vs_fastq_stream *s, int f) {
     DevFile &d = s->df[f];
     std::vector<uint8_t> buf(d.size);
-    if (d.size) VS_HIP(ctx, hipMemcpy(buf.data(), d.win[d.cur], d.size, hipMemcpyDeviceToHost));
+    if (d.size) VS_HIP(ctx, hipMemcpy(buf.data(), d.win[d.cur].as<uint8_t>(), d.size, hipMemcpyDeviceToHost));
     size_t cut = d.size;
     if (!d.eof) {
         size_t lim = d.size;
@@ -651,7 +637,7 @@ int translate_window(vs_ctx *ctx, vs_fastq_stream *s, int f) {
     }
     const size_t translated = out.size();
     out.insert(out.end(), buf.begin() + (ptrdiff_t)cut, buf.end());
-    if (!out.empty()) VS_HIP(ctx, hipMemcpy(d.win[d.cur], out.data(), out.size(), hipMemcpyHostToDevice));
+    if (!out.empty()) VS_HIP(ctx, hipMemcpy(d.win[d.cur].as<uint8_t>(), out.data(), out.size(), hipMemcpyHostToDevice));
     d.size = out.size();
     d.validated = translated;
     return VS_OK;
@@ -698,7 +684,7 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
         Reader &r = s->rd[f];
         if (d.err == VS_OK && d.validated < d.size && (d.flags & FL_HIGH)) {
             std::vector<uint8_t> buf(d.size - d.validated);
-            VS_HIP(ctx, hipMemcpy(buf.data(), d.win[d.cur] + d.validated, buf.size(), hipMemcpyDeviceToHost));
+            VS_HIP(ctx, hipMemcpy(buf.data(), d.win[d.cur].as<uint8_t>() + d.validated, buf.size(), hipMemcpyDeviceToHost));
             if (!check_piece(d, buf.data(), buf.size(), d.eof)) {
                 d.err = VS_E_UTF8;
                 d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
@@ -721,7 +707,7 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
                 }
                 if (!member_failed(ctx, s, f, sl) && ((d.flags & FL_HIGH) || d.n_pend)) {
                     std::vector<uint8_t> buf(d.size);
-                    if (d.size && hipMemcpy(buf.data(), d.win[d.cur], d.size, hipMemcpyDeviceToHost) != hipSuccess) {
+                    if (d.size && hipMemcpy(buf.data(), d.win[d.cur].as<uint8_t>(), d.size, hipMemcpyDeviceToHost) != hipSuccess) {
                         r.give_back();
                         return stream_fail(ctx, s, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
                     }
@@ -729,7 +715,7 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
                 }
                 d.size = d.validated = 0;
             } else if (d.err == VS_OK) {
-                ok = check_piece(d, sl.p, sl.len, sl.last);
+                ok = check_piece(d, sl.buf.as<uint8_t>(), sl.len, sl.last);
             }
             if (!ok) {
                 d.err = VS_E_UTF8;
@@ -760,28 +746,28 @@ int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot &sl) {
         return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete record", s->rd[f].path.c_str(),
                        (unsigned long long)(d.size + sl.text));
     const size_t need = ((d.size + sl.text + 15u) & ~(size_t)15u) + 16u;
-    if (d.win_cap[d.cur] < need) {  // keep the leftover: grow the other buffer, copy, switch
+    if (d.win[d.cur].capacity() < need) {  // keep the leftover: grow the other buffer, copy, switch
         const int o = d.cur ^ 1;
-        if (int rc = grow(ctx, d.win[o], d.win_cap[o], need)) return rc;
-        if (d.size) VS_HIP(ctx, hipMemcpyAsync(d.win[o], d.win[d.cur], d.size, hipMemcpyDeviceToDevice, s->st));
+        if (int rc = reserve_n<uint8_t>(ctx, d.win[o], need)) return rc;
+        if (d.size) VS_HIP(ctx, hipMemcpyAsync(d.win[o].as<uint8_t>(), d.win[d.cur].as<uint8_t>(), d.size, hipMemcpyDeviceToDevice, s->st));
         d.cur = o;
     }
     if (sl.comp) {
         const uint32_t nm = sl.n_members;
         d.slot_base = (uint32_t)d.members_dev;
         if (nm) {
-            if (int rc = grow(ctx, d.comp, d.comp_cap, sl.len + 16u)) return rc;
-            if (int rc = grow(ctx, d.dir, d.dir_cap, (size_t)nm)) return rc;
-            if (int rc = grow(ctx, d.mstat, d.mstat_cap, (size_t)nm)) return rc;
-            const vs_bgzf_member *dir = (const vs_bgzf_member *)(sl.p + sl.cap) - nm;  // (member i at dir[nm - 1 - i])
-            if (sl.len) VS_HIP(ctx, hipMemcpyAsync(d.comp, sl.p, sl.len, hipMemcpyHostToDevice, s->st));
-            VS_HIP(ctx, hipMemcpyAsync(d.dir, dir, sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, s->st));
-            vs_launch_inflate(s->st, d.comp, sl.len, d.win[d.cur] + d.size, sl.text, d.dir, nm, d.mstat, s->d_stat + ST_BAD + f, d.slot_base, 1);
+            if (int rc = reserve_n<uint8_t>(ctx, d.comp, sl.len + 16u)) return rc;
+            if (int rc = reserve_n<vs_bgzf_member>(ctx, d.dir, (size_t)nm)) return rc;
+            if (int rc = reserve_n<uint32_t>(ctx, d.mstat, (size_t)nm)) return rc;
+            const vs_bgzf_member *dir = (const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()) - nm;  // (member i at dir[nm - 1 - i])
+            if (sl.len) VS_HIP(ctx, hipMemcpyAsync(d.comp.as<uint8_t>(), sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st));
+            VS_HIP(ctx, hipMemcpyAsync(d.dir.as<vs_bgzf_member>(), dir, sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, s->st));
+            vs_launch_inflate(s->st, d.comp.as<uint8_t>(), sl.len, d.win[d.cur].as<uint8_t>() + d.size, sl.text, d.dir.as<vs_bgzf_member>(), nm, d.mstat.as<uint32_t>(), s->d_stat + ST_BAD + f, d.slot_base, 1);
             VS_HIP(ctx, hipGetLastError());
             d.members_dev += nm;
         }
     } else if (sl.len) {
-        VS_HIP(ctx, hipMemcpyAsync(d.win[d.cur] + d.size, sl.p, sl.len, hipMemcpyHostToDevice, s->st));
+        VS_HIP(ctx, hipMemcpyAsync(d.win[d.cur].as<uint8_t>() + d.size, sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st));
     }
     d.size += sl.text;
     d.eof = sl.last;
@@ -808,12 +794,12 @@ bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
         d.err_msg = s->rd[f].path + ": the device reported a BGZF member that is not of the slot it inflated";
         return true;
     }
-    const vs_bgzf_member mb = ((const vs_bgzf_member *)(sl.p + sl.cap))[-(ptrdiff_t)(idx + 1u)];
+    const vs_bgzf_member mb = ((const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()))[-(ptrdiff_t)(idx + 1u)];
     uint32_t dev_status = 0;
-    (void)hipMemcpy(&dev_status, d.mstat + idx, sizeof dev_status, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&dev_status, d.mstat.as<uint32_t>() + idx, sizeof dev_status, hipMemcpyDeviceToHost);
     // the member as a plain gzip member: a 10-byte header, the payload, the trailer
     std::vector<uint8_t> gz = {0x1f, 0x8b, 0x08, 0, 0, 0, 0, 0, 0, 0xff};
-    gz.insert(gz.end(), sl.p + mb.in_off, sl.p + mb.in_off + mb.in_len);
+    gz.insert(gz.end(), sl.buf.as<uint8_t>() + mb.in_off, sl.buf.as<uint8_t>() + mb.in_off + mb.in_len);
     for (uint32_t v : {mb.crc, mb.isize})
         for (int k = 0; k < 4; k++) gz.push_back((uint8_t)(v >> (8 * k)));
     std::vector<uint8_t> out(1u << 16);
@@ -850,8 +836,8 @@ int drop_front(vs_ctx *ctx, vs_fastq_stream *s, int f, size_t cut, uint64_t reco
     DevFile &d = s->df[f];
     const size_t rest = d.size - cut;
     const int o = d.cur ^ 1;
-    if (int rc = grow(ctx, d.win[o], d.win_cap[o], ((rest + 15u) & ~(size_t)15u) + 16u)) return rc;
-    if (rest) VS_HIP(ctx, hipMemcpyAsync(d.win[o], d.win[d.cur] + cut, rest, hipMemcpyDeviceToDevice, s->st));
+    if (int rc = reserve_n<uint8_t>(ctx, d.win[o], ((rest + 15u) & ~(size_t)15u) + 16u)) return rc;
+    if (rest) VS_HIP(ctx, hipMemcpyAsync(d.win[o].as<uint8_t>(), d.win[d.cur].as<uint8_t>() + cut, rest, hipMemcpyDeviceToDevice, s->st));
     d.cur = o;
     d.size = rest;
     d.validated = d.validated > cut ? d.validated - cut : 0;
@@ -888,9 +874,11 @@ int vs_fastq_stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path
         }
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
-    if (e1 == hipSuccess) e1 = hipMalloc((void **)&s->d_stat, sizeof(uint32_t) * ST_ALL);
+    if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * ST_ALL);
+    s->d_stat = s->stat_buf.as<uint32_t>();
     if (e1 == hipSuccess) e1 = hipMemset(s->d_stat + ST_BAD, 0xFF, sizeof(uint32_t) * 2);
-    if (e1 == hipSuccess) e1 = hipHostMalloc((void **)&s->h_stat, sizeof(uint32_t) * ST_ALL, hipHostMallocDefault);
+    if (e1 == hipSuccess) e1 = s->h_stat_buf.reserve(sizeof(uint32_t) * ST_ALL);
+    s->h_stat = s->h_stat_buf.as<uint32_t>();
     if (e1 != hipSuccess) {
         vs_fastq_stream_close(s);
         return vs_fail(ctx, VS_E_HIP, "vs_fastq_stream_open: %s", hipGetErrorString(e1));
@@ -958,13 +946,13 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     const uint64_t n_ends = 2u * n;
     for (int f = 0; f < 2; f++) {
         DevFile &d = s->df[f];
-        if (int rc = grow(ctx, d.ends, d.ends_cap, (size_t)d.n_nl + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
         const uint64_t words = (d.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
-        if (wgs) hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, (const uint8_t *)d.win[d.cur], (uint64_t)d.size, d.wg, d.ends);
+        if (wgs) hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, d.win[d.cur].as<const uint8_t>(), (uint64_t)d.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
     }
-    if (int rc = grow(ctx, s->d_wcnt, s->wcnt_cap, n_ends + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
-    SlWin w0 = {s->df[0].win[s->df[0].cur], s->df[0].ends, s->df[0].n_nl, (uint32_t)s->df[0].size};
-    SlWin w1 = {s->df[1].win[s->df[1].cur], s->df[1].ends, s->df[1].n_nl, (uint32_t)s->df[1].size};
+    if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+    SlWin w0 = {s->df[0].win[s->df[0].cur].as<uint8_t>(), s->df[0].ends.as<uint32_t>(), s->df[0].n_nl, (uint32_t)s->df[0].size};
+    SlWin w1 = {s->df[1].win[s->df[1].cur].as<uint8_t>(), s->df[1].ends.as<uint32_t>(), s->df[1].n_nl, (uint32_t)s->df[1].size};
     vs_reads *r = new vs_reads();
     r->n_ends = n_ends;
     r->cached = true;
@@ -979,9 +967,9 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + ST_TOO_LONG, 0xFF, sizeof(uint32_t), st);
     if (e1 == hipSuccess) {
         hipLaunchKernelGGL(k_sl_ends, dim3((unsigned)((n_ends + 1u + SL_TPB - 1u) / SL_TPB)), dim3(SL_TPB), 0, st, w0, w1, (uint32_t)n,
-                           (uint32_t *)r->d_meta, s->d_wcnt, s->d_stat);
-        hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, s->d_wcnt, (uint32_t)(n_ends + 1u), s->d_stat + ST_WORDS);
-        e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt, b_woff, hipMemcpyDeviceToDevice, st);
+                           (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
+        hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + ST_WORDS);
+        e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), b_woff, hipMemcpyDeviceToDevice, st);
     }
     if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_N, hipMemcpyDeviceToHost, st);
     if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
@@ -1064,14 +1052,6 @@ void vs_fastq_stream_close(vs_fastq_stream *s) {
     if (!s) return;
     for (Reader &r : s->rd) r.shut();
     if (s->st) (void)hipStreamSynchronize(s->st);
-    for (DevFile &d : s->df) {
-        void *ps[] = {d.win[0], d.win[1], d.ends, d.wg, d.comp, d.dir, d.mstat};
-        for (void *p : ps)
-            if (p) (void)hipFree(p);
-    }
-    if (s->d_stat) (void)hipFree(s->d_stat);
-    if (s->d_wcnt) (void)hipFree(s->d_wcnt);
-    if (s->h_stat) (void)hipHostFree(s->h_stat);
     if (s->st) (void)hipStreamDestroy(s->st);
     delete s;
 }
@@ -1093,29 +1073,26 @@ int vs_fastq_scan_text(vs_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t li
     VS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint64_t words = (n + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
-    uint8_t *d_txt = nullptr;
-    uint32_t *d_wg = nullptr, *d_ends = nullptr, *d_st = nullptr;
+    VsDevBuf txt_buf, wg_buf, ends_buf, st_buf;
     uint32_t hs[ST_N] = {0};
-    hipError_t e1 = hipMalloc((void **)&d_txt, words * 16u + 16u);
-    if (e1 == hipSuccess) e1 = hipMalloc((void **)&d_wg, sizeof(uint32_t) * (wgs + 1u));
-    if (e1 == hipSuccess) e1 = hipMalloc((void **)&d_ends, sizeof(uint32_t) * (n + 1u));
-    if (e1 == hipSuccess) e1 = hipMalloc((void **)&d_st, sizeof(uint32_t) * ST_N);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(d_st, 0, sizeof(uint32_t) * ST_N, st);
-    if (e1 == hipSuccess && n) e1 = hipMemcpyAsync(d_txt, text, n, hipMemcpyHostToDevice, st);
-    if (e1 == hipSuccess && wgs) {
+    VS_HIP(ctx, txt_buf.reserve(words * 16u + 16u));
+    VS_HIP(ctx, wg_buf.reserve(sizeof(uint32_t) * (wgs + 1u)));
+    VS_HIP(ctx, ends_buf.reserve(sizeof(uint32_t) * (n + 1u)));
+    VS_HIP(ctx, st_buf.reserve(sizeof(uint32_t) * ST_N));
+    uint8_t *d_txt = txt_buf.as<uint8_t>();
+    uint32_t *d_wg = wg_buf.as<uint32_t>(), *d_ends = ends_buf.as<uint32_t>(), *d_st = st_buf.as<uint32_t>();
+    VS_HIP(ctx, hipMemsetAsync(d_st, 0, sizeof(uint32_t) * ST_N, st));
+    if (n) VS_HIP(ctx, hipMemcpyAsync(d_txt, text, n, hipMemcpyHostToDevice, st));
+    if (wgs) {
         hipLaunchKernelGGL(k_sl_count, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, (const uint8_t *)d_txt, n, d_wg, d_st);
         hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, d_wg, (uint32_t)wgs, d_st + ST_NL);
         hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, (const uint8_t *)d_txt, n, (const uint32_t *)d_wg, d_ends);
-        e1 = hipGetLastError();
+        VS_HIP(ctx, hipGetLastError());
     }
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(hs, d_st, sizeof hs, hipMemcpyDeviceToHost, st);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+    VS_HIP(ctx, hipMemcpyAsync(hs, d_st, sizeof hs, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
     std::vector<uint32_t> h(hs[ST_NL] ? hs[ST_NL] : 1u);
-    if (e1 == hipSuccess && hs[ST_NL]) e1 = hipMemcpy(h.data(), d_ends, sizeof(uint32_t) * hs[ST_NL], hipMemcpyDeviceToHost);
-    void *ps[] = {d_txt, d_wg, d_ends, d_st};
-    for (void *p : ps)
-        if (p) (void)hipFree(p);
-    if (e1 != hipSuccess) return vs_fail(ctx, VS_E_HIP, "vs_fastq_scan_text: %s", hipGetErrorString(e1));
+    if (hs[ST_NL]) VS_HIP(ctx, hipMemcpy(h.data(), d_ends, sizeof(uint32_t) * hs[ST_NL], hipMemcpyDeviceToHost));
     const uint64_t nl = hs[ST_NL];
     info[0] = nl;
     info[1] = hs[ST_FLAGS];
