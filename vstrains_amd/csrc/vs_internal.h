@@ -9,6 +9,7 @@
 
 #include "../../include/vstrains_hip.h"
 #include "vs_buf.h"
+#include "vs_pe_plan.h"  // VsTuning, the probe grid of a read end (vs_seed_phase, vs_seed_probes, VS_SEED_VERIFIED)
 
 #define VS_WAVE 64
 #define VS_PAD_WORDS 16  // zero words behind every packed text buffer (window reads may overshoot)
@@ -97,24 +98,6 @@ struct FqStage {
     bool in_flight = false;
 };
 
-// Test hooks of vs_pe_count.  A production context never reads the environment: the switches exist only when the process
-// was started with VS_EXPERIMENT=1 (any other value is production), and are then re-read on every call so that a test can
-// flip them on a live context.  A switch is kept only if a test uses it and it forces a path that a production context
-// takes on some input (often one that only full-size blocks or large graphs reach), or the reference path of a test.
-// Every one of them gives the production counters.  Defaults = what a production context does.
-struct VsTuning {
-    uint32_t ept = 0;               // VS_EPT (0 = automatic)
-    uint32_t grid_per_cu = 128;     // VS_GRID_PER_CU: longer runs of tiles per workgroup, as a full-size block has
-    int acc_fill_pct = -1;          // VS_ACC_FILL (-1 = 1/16 of the slots): cell-table write-outs on fill
-    int shortcut = -1;              // VS_SHORTCUT (-1 = by index statistics)
-    int adapt_grid = -1;            // VS_ADAPT_GRID (-1 = by index statistics): the adaptive step grid of the compile-time-shape kernels
-    int acc_rows = -1;              // VS_ACC_ROWS (-1 = by graph size): counters summed by row owners (k_rows_sum) instead of pair-major (k_pe_accumulate)
-    int ltab_bits = -1;             // VS_LTAB_BITS: log2 slots of the block's list table (-1 = by block size, 0 = no table: every end stands for itself)
-    uint32_t rows_keys = 0, rows_sub = 0;  // VS_ROWS_KEYS / VS_ROWS_SUB: rows per histogram pass, pairs per transposition (0 = the constants; tests shrink them)
-    uint32_t rows_per_strip = 0;    // VS_ROWS_PER_STRIP (0 = automatic): matrix rows one workgroup of k_rows_sum owns at a time
-    bool no_sort = false, locus_global = false, no_fast = false, no_std = false, no_agg = false;
-    bool no_mid = false;            // VS_NO_MID: overflow pairs straight to k_pe_slow
-};
 void vs_tuning_load(VsTuning &t, bool experiment);  // production (false): the defaults
 
 struct vs_ctx {
@@ -192,22 +175,6 @@ struct vs_reads {
         return r;
     }
 };
-
-// The probe grid of a read end (round 5).  A match of K bases and more holds s = K - w + 1 consecutive seed starts, so any
-// grid phi, phi + s, phi + 2s, ... of read offsets finds it, and the first grid point inside it credits it (left extension
-// below s: vs_extend / k_pe_tiles).  phi = 0 spends a probe on the read's last, partly covered stride: floor((len - w) / s) + 1
-// probes.  With r = (len - w) mod s every phi in (r, s) needs one probe less -- floor((len - w + 1) / s), the fewest any
-// exact grid of stride s can have (the len - K + 1 windows of a read in runs of s) -- and the grid's seeds then lie
-// inside the read instead of flush with its first base.  phi = (r + s) / 2 is the middle of that range (and s - 1, the
-// only choice, when r = s - 1).  Measured on the configs[2] stream: 21.9 instead of 27.4 postings per end, four probes
-// instead of five (profiles/r5/phase_gate_config2.json).  Ends shorter than K are never probed (PE_Inference.py:160-163).
-__host__ __device__ inline uint32_t vs_seed_phase(uint32_t len, uint32_t w, uint32_t s) {
-    return len < w ? 0u : ((len - w) % s + s) / 2u;
-}
-__host__ __device__ inline uint32_t vs_seed_probes(uint32_t len, uint32_t w, uint32_t s) {
-    if (len < w) return 0u;
-    return (len - w + 1u) / s;  // (0 for an end shorter than K = w + s - 1: it has no (k+1)-window, PE_Inference.py:23, and is never probed)
-}
 
 int vs_fail(vs_ctx *ctx, int code, const char *fmt, ...);
 // grow-only cache of device buffers (see vs_ctx::cache); NULL on allocation failure
@@ -328,8 +295,6 @@ __device__ __forceinline__ bool vs_seed_dirty(const uint32_t *mask, B base, uint
     if (w <= 32u) return (vs_win(mask, base) & vs_lowmask(2u * w)) != 0ull;
     return vs_win(mask, base) != 0ull || (vs_win(mask, base + (B)32) & vs_lowmask(2u * (w - 32u))) != 0ull;
 }
-// bases of the seed the comparison may take for granted: all of them for exact keys, none for mixed ones
-#define VS_SEED_VERIFIED(w) ((w) <= 31u ? (w) : 0u)
 
 __device__ __forceinline__ uint32_t vs_slot_of(uint64_t key, uint32_t bits) {
     return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64u - bits));

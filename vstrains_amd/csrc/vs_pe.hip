@@ -55,18 +55,13 @@
 //   row owners (graphs beyond 46 340 nodes): their entries name lists by END INDEX, so the lists keep a fixed stride
 //         there -- a row of LC words per end, of which only the quads that hold nodes are written, and ONE more quad per
 //         end, in an array of its own behind the rows, for nodes 17 .. LCAP; counts[end] = n
-#define LC 16u
-#define LCAP 20u
+#define LCAP 20u  // (LC: vs_pe_plan.h)
 // (rows of LCAP words, 80 bytes apart, straddle a 64-byte stretch every other time -- the row owners took 13.0 ms instead of
 // 10.9 at configs[4] -- and rows 128 bytes apart are fetched as whole 128-byte lines: k_list_owners 2.9 -> 4.1 ms)
 __device__ __forceinline__ const uint32_t *vs_row_quad(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ hi, uint64_t row, uint32_t q) {
     return q < LC / 4u ? lists + row * LC + 4u * q : hi + row * 4u;
 }
 #define EMPTY_NODE 0xFFFFFFFFu
-#define PPT 2u               // postings per thread and expansion chunk
-#define TTPB 256             // threads per k_pe_tiles workgroup (a tile holds TTPB / 4 read ends)
-#define PPT_LONG 1u          // the same for the long-window instantiations (MODE 2, k = 127)
-#define CHUNK (TTPB * PPT)   // (the owner array of a tile is sized for the larger of the two)
 
 struct PeParams {
     VsIndexDev idx;
@@ -449,52 +444,7 @@ __device__ __forceinline__ uint32_t vs_probe_from(const VsIndexDev &idx, uint64_
 
 extern __shared__ __attribute__((aligned(16))) uint32_t vs_lds[];
 
-// LDS carve shared by the kernel and the host-side size computation
-struct TileLayout {
-    uint32_t woff, gend, meta, inv, words, pcnt, pa, pb, hkey, hcnt, hminp, hminj, ns, state, list, owner, misc, total;
-};
-__host__ __device__ inline TileLayout tile_layout(uint32_t ept, uint32_t pmax, uint32_t words_cap, uint32_t pool, uint32_t list_trim = 0u) {
-    TileLayout t;
-    uint32_t o = 0;
-    const uint32_t NI = ept * pmax;
-    // headers and packed words exist twice: the next tile's are brought in while this one is worked on
-    t.woff = o;  o += 2u * ((ept + 2u) & ~1u);  // global word offset of every end of the tile
-    t.gend = o;  o += 2u * ept;                 // global end index
-    t.meta = o;  o += 2u * ept;
-    t.inv = o;   o += ept;                      // positions of bytes outside ACGT (straight-line kernels; current tile only)
-    t.words = o; o += 2u * (words_cap + 8u);
-    t.pcnt = o;  o += NI + 1u;  // [0] stays zero: the scan is read as s_pcnt[it - 1] .. s_pcnt[it] without a test for it == 0
-    t.pa = o;    o += NI;
-    t.pb = o;    o += NI;
-    t.hkey = o;  o += pool;
-    t.hcnt = o;  o += pool;
-    t.hminp = o; o += pool;
-    t.hminj = o; o += pool;
-    t.ns = o;    o += ept;
-    t.state = o; o += ept;
-    // the posting owners of P3 and the accepted lists of P4/P5 are never live together
-    t.list = o;
-    t.owner = o; o += (ept * LC - list_trim > CHUNK ? ept * LC - list_trim : CHUNK);
-    t.misc = o;  o += 16u;
-    t.total = o;
-    return t;
-}
-
-// SW, SP != 0: the tile shape is a compile-time one for k = 55 -- 64 ends per tile, 1024-slot table,
-// SW packed words and SP probes per end (vs_seed_probes): (10, 4) = 2 x 145..159 bases, (8, 3) = 2 x 113..128, (7, 3) = 2 x 108..112,
-// (7, 2) = 2 x 97..107.  Every LDS array then sits at a constant offset (folded into the LDS
-// instructions) instead of costing a scalar register and an add, the divisions by pmax / wpe and
-// k+1 / seed length / stride become constants.  The host picks one when the block has that shape.
-#define STD_EPT (TTPB / 4u)
-#define STD_POOL_BITS 10u  // pool_for(STD_EPT)
-#define STD_K 56u   // k + 1
-#define STD_W 31u   // seed length and probe stride that follow from it (seed_geometry)
-#define STD_S 26u
-#define STD2_EPT 60u  // the k = 127 shape (MODE 2): ends per tile, pool_for(60) = 1024 slots, k + 1, seed length, stride
-#define STD2_POOL_BITS 10u
-#define STD2_K 128u
-#define STD2_W 63u
-#define STD2_S 66u
+// (TileLayout, the compile-time shapes STD_* / STD2_* and vs_std_table: vs_pe_plan.h)
 // MODE 0: generic loops (masked reads through the validity mask, any stride / read length);
 //      1: straight-line comparison, stride <= 32, reads <= w + 160; 2: the same for stride <= 128, reads <= w + 256.
 // Tile and pair indices inside k_pe_tiles are 32-bit: a block holds fewer than 2^32 ends (64-bit indices spilled six more
@@ -525,7 +475,7 @@ k_pe_tiles(PeParams P) {
     const bool want_dbg = !STD && P.dbg_counts != nullptr;
     const bool accumulate = STD || P.accumulate;
     // (r3) MODE 2 has one compile-time shape too: k = 127 with 2 x 241..256 bases -- 63-base seeds, stride 66, 16 words and
-    // two probes per end, 60 ends per tile (what the host's LDS budget gives that shape)
+    // two probes per end, 60 ends per tile (what the plan's LDS budget gives that shape)
     constexpr uint32_t C_EPT = MODE == 2 ? STD2_EPT : STD_EPT, C_K = MODE == 2 ? STD2_K : STD_K;
     constexpr uint32_t C_W = MODE == 2 ? STD2_W : STD_W, C_S = MODE == 2 ? STD2_S : STD_S;
     constexpr uint32_t C_POOL_BITS = MODE == 2 ? STD2_POOL_BITS : STD_POOL_BITS;
@@ -533,10 +483,8 @@ k_pe_tiles(PeParams P) {
     const uint32_t NI = ept * pmax;
     const uint32_t w = STD ? C_W : P.idx.w, s = STD ? C_S : P.idx.s, K = STD ? C_K : P.idx.K;
     const uint32_t wv = VS_SEED_VERIFIED(w);  // seed bases the comparison skips (0: seeds with mixed keys, vs_seed_key)
-    // (the 768-slot table is for graphs whose ends touch few nodes: the adaptive instantiations -- many postings per seed, long
-    // lists -- keep 1 024 slots and five wavefronts per SIMD)
-    constexpr bool P12 = STD && !AD;
-    constexpr uint32_t C_POOL = P12 ? 768u : (1u << C_POOL_BITS), C_TRIM = P12 ? (MODE == 2 ? 192u : 64u) : 0u;  // (k = 127: 16 words per end of read text leave less)
+    constexpr bool P12 = STD && !AD;  // the 768-slot table (vs_std_table)
+    constexpr uint32_t C_POOL = vs_std_table(MODE, STD, AD).pool, C_TRIM = vs_std_table(MODE, STD, AD).trim;
     const uint32_t pool = STD ? C_POOL : P.pool, pool_shift = 32u - (STD ? C_POOL_BITS : P.pool_bits);
     const uint32_t words_cap = STD ? C_EPT * STD_WPE : P.words_cap;
     const TileLayout T = tile_layout(ept, pmax, words_cap, pool, C_TRIM);
@@ -1087,9 +1035,6 @@ k_pe_tiles(PeParams P) {
 //     table is written out.  One wavefront expands 64 pairs at a time, one lane per run of at most four increments.
 //   * the row owners below (larger graphs): output-major.  There a round of locus-ordered pairs brings more distinct
 //     cells than the table holds, and the same cell returns from loci hundreds of rounds apart.
-#define ACC_TPB 1024
-#define ACC_BITS 14
-#define ACC_SLOTS (1u << ACC_BITS)
 #define ACC_LDS_BYTES ((2u * ACC_SLOTS + (ACC_TPB / 64) * 66u + (LCAP + 1u) + (LCAP + 1u) * ACC_GMAX + 4u) * 4u)
 // Work units: a list row is cut into runs of at most ACC_RUN partners, one lane per run, so that
 // every lane of a wavefront has about the same (small, fully unrolled) amount of work:
@@ -1443,8 +1388,6 @@ __global__ void __launch_bounds__(64) k_zero_tiles(uint32_t *__restrict__ node_m
 #define ROWS_CHUNK1 8192u  // owning ends per chunk (mode 1: few items, spread over more workgroups)
 #define ROWS_TPB 1024u
 #define ROWS_CAP 4096u     // distinct rows of a chunk that get an LDS cursor (the rest: a global atomic per entry)
-#define ROWS_KEYS 65536u   // rows per histogram pass (larger graphs take several passes over the lists)
-#define ROWS_SUB ((1u << 26) - 1024u)  // pairs per transposition (an entry names a read end in 27 bits, its list's length in five; row offsets are 32-bit)
 static inline size_t rows_lds_bytes(uint32_t n_keys) { return sizeof(uint32_t) * (((size_t)n_keys + 2u) / 2u + ROWS_CAP + ROWS_CAP / 2u + 4u); }
 
 // Which read ends stand for a list of their own, and for how many ends: short_mat takes one weighted pass per DISTINCT
@@ -1714,9 +1657,7 @@ k_rows_fill(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ lis
 
 // The strips' cell table is smaller than the pair-major kernel's (8 k slots, 64 KB) and the strips narrower for it: two
 // workgroups share a CU, and one waits in its LDS queue while the other computes (configs[4]: 14.1 -> 11.2 ms)
-#define RS_BITS 13
 #define RS_TPB 1024
-#define RS_SLOTS (1u << RS_BITS)
 typedef CellTable<RS_BITS> RsTable;
 #define RSUM_LDS_BYTES ((2u * RS_SLOTS + 64u + 8u) * 4u)
 #define RSUM_MAX_ROWS 64u
@@ -1883,10 +1824,7 @@ __device__ __forceinline__ uint32_t vs_locus_key_end(const VsIndexDev &idx, cons
 //   vs_scan_u32     : exclusive scan of cnt[] in (key, workgroup) order = first slot of every
 //                     (key, workgroup) run in the sorted order -- stable, deterministic
 //   k_locus_scatter : workgroup g loads its column as LDS cursors and places its pairs
-#define LOCUS_LDS_KEYS 36864u  // 144 KB of LDS counters
-#define LOCUS_LDS_MAX_PASSES 4u  // ... per pass; graphs of up to 147 k nodes are sorted through LDS histograms
 #define LOCUS_TPB 1024     // threads per workgroup of the two LDS-histogram sort kernels
-#define LOCUS_WGS 256u     // one per CU (measured: 1024 x 256 threads 0.70 ms, 256 x 1024 threads 0.57 ms)
 // (key_lo, nk): the keys this pass counts / places -- a graph with more keys than one LDS histogram holds (54 k nodes at
 // configs[4]) takes two or three passes over the stored keys instead of the global-atomic sort; `compute`: the first
 // pass derives the keys (the expensive part: a read's seeds are probed) and stores them, the others read them back.
@@ -2138,7 +2076,6 @@ k_pe_mid(PeParams P, const uint32_t *__restrict__ in_list, const uint32_t *__res
 // list and restores the state.  Probes go through the workgroup 256 at a time; their postings are
 // spread over the threads (prefix sum of the counts in LDS, one posting per thread and round).
 // dense layout per workgroup: cnt[N] minp[N] minj[N] touched[N] surv0[N] surv1[N].
-#define SLOW_WORDS_PER_NODE 6u
 __global__ void __launch_bounds__(TPB)
 k_pe_slow(PeParams P, uint32_t *dense, uint32_t n_slow_cap, const uint32_t *__restrict__ list, const uint32_t *__restrict__ count) {
     __shared__ uint32_t s_n[2], s_nt, s_cnt[TPB + 1], s_pa[TPB], s_pb[TPB];
@@ -2277,42 +2214,19 @@ __global__ void __launch_bounds__(TPB) k_dense_zero_cnt(uint32_t *dense, uint64_
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-#define LDS_BUDGET_BYTES (64u * 1024u)
-#define NI_CAP 4096u
-// workgroups of the overflow kernel: as many as 4 GB of dense per-workgroup node state allow, 64 .. 2048
-static uint32_t slow_grid_for(uint32_t n_nodes) {
-    const uint64_t per_wg = sizeof(uint32_t) * (uint64_t)SLOW_WORDS_PER_NODE * (n_nodes ? n_nodes : 1u);
-    uint64_t g = (4ull << 30) / per_wg;
-    return (uint32_t)(g < 64u ? 64u : g > 2048u ? 2048u : g);
-}
-
-static uint32_t pool_for(uint32_t ept, uint32_t *bits) {
-    uint32_t b = 6;
-    while ((1u << b) < 16u * ept) b++;
-    *bits = b;
-    return 1u << b;
-}
-
-static size_t lds_bytes(uint32_t ept, uint32_t pmax, uint32_t words_cap) {
-    uint32_t bits;
-    uint32_t pool = pool_for(ept, &bits);
-    return (size_t)tile_layout(ept, pmax, words_cap, pool).total * sizeof(uint32_t);
-}
+// Every decision of a call -- tile shape, instantiation, locus order, counter path, grids, scratch sizes -- is taken by
+// vs_pe_plan (vs_pe_plan.h); what follows reserves, fills PeParams and launches from the plan.
 
 // The row-owner path: both counters of one block from the per-end lists (see "both matrices by ROW OWNERS").
-static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_mat, uint32_t *d_short_mat, uint8_t *d_tile_map, uint32_t T) {
+static int pe_count_by_rows(vs_ctx *ctx, const PePlan &pl, uint32_t *d_node_mat, uint32_t *d_short_mat, uint8_t *d_tile_map, uint32_t T) {
     hipStream_t st = ctx->stream;
-    const VsTuning &tn = ctx->tune;
     const uint32_t N = ctx->idx.n_nodes;
-    const uint64_t sub_max = tn.rows_sub ? (uint64_t)tn.rows_sub : (uint64_t)ROWS_SUB;
-    const uint64_t sub_pairs = slots_pairs < sub_max ? slots_pairs : sub_max;  // pairs per transposition
+    const uint64_t slots_pairs = pl.list_ends / 2, sub_pairs = pl.rows_sub_pairs;  // pairs per transposition
     // per mode: counts, cursors, offsets; then the block sums of the scan (2 048 values per block, 64 bits each)
     const uint64_t cap = (uint64_t)N + 2u;
     VS_HIP(ctx, ctx->d_rows.reserve(sizeof(uint32_t) * 6u * cap + sizeof(uint64_t) * ((uint64_t)N / 2048u + 8u)));
-    // the list table of a transposition: a power of two of slots, at least one per read end (VS_LTAB_BITS: tests crowd it)
-    uint32_t ltab_bits = 10;
-    while ((1ull << ltab_bits) < 2u * sub_pairs && ltab_bits < 31u) ltab_bits++;
-    if (tn.ltab_bits >= 0) ltab_bits = (uint32_t)tn.ltab_bits;
+    // the list table of a transposition (0 bits: no table, every end stands for itself)
+    const uint32_t ltab_bits = pl.rows_ltab_bits;
     const bool use_ltab = ltab_bits > 0;
     const uint64_t ltab_slots = use_ltab ? 1ull << ltab_bits : 0;
     // entries: one word per listed node -- the left lists (node_mat) and the lists of the owning ends (short_mat); the
@@ -2322,21 +2236,12 @@ static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_
     VS_HIP(ctx, ctx->d_ltab.reserve((sizeof(uint64_t) + sizeof(uint32_t)) * ltab_slots + 16u));
     uint32_t *rows = ctx->d_rows.as<uint32_t>();
     uint64_t *scan_tmp = (uint64_t *)(rows + ((6u * cap + 1u) & ~1ull));
-    const uint32_t keys_max = tn.rows_keys ? tn.rows_keys : ROWS_KEYS;
-    const uint32_t n_keys = N < keys_max ? N : keys_max;
+    const uint32_t n_keys = pl.rows_keys, fill = pl.rows_fill, R = pl.rows_per_strip;
     const size_t rl = rows_lds_bytes(n_keys);
     for (const void *fn : {(const void *)k_rows_count<0>, (const void *)k_rows_count<1>, (const void *)k_rows_fill<0>, (const void *)k_rows_fill<1>})
         VS_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl));
     for (const void *fn : {(const void *)k_rows_sum<0>, (const void *)k_rows_sum<1>})
         VS_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RSUM_LDS_BYTES));
-    // the table is written out once this share of its slots is taken (a strip that holds more cells than that is written
-    // in pieces: still one atomic per cell and piece); VS_ACC_FILL: percent
-    uint32_t fill = RS_SLOTS / 2u;
-    if (tn.acc_fill_pct >= 0) fill = (uint32_t)((uint64_t)RS_SLOTS * (uint32_t)tn.acc_fill_pct / 100u);
-    if (fill > RS_SLOTS - 1024u) fill = RS_SLOTS - 1024u;
-    // rows per strip: a strip's distinct cells should fill the table less than half.  configs[4]: 4 rows of node_mat hold
-    // 1.7 k cells at the median and 6 k at most, 32 rows of short_mat 2.1 k and 6.6 k.  VS_ROWS_PER_STRIP overrides both.
-    const uint32_t R = tn.rows_per_strip ? tn.rows_per_strip : 2u;
     uint32_t *queue = ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_STRIP_QUEUE, *n_owners = ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_OWNERS;
     unsigned long long *ltab = use_ltab ? ctx->d_ltab.as<unsigned long long>() : nullptr;
     uint32_t *lmult = use_ltab ? (uint32_t *)(ctx->d_ltab.as<unsigned long long>() + ltab_slots) : nullptr;
@@ -2396,86 +2301,71 @@ static int pe_count_by_rows(vs_ctx *ctx, uint64_t slots_pairs, uint32_t *d_node_
     return VS_OK;
 }
 
+// The instantiations of k_pe_tiles by (MODE, SW, SP, AD), each with the name vs_pe_last_kernel returns for it; every
+// compile-time shape (VS_STD_SHAPES) exists with and without the adaptive step grid.
+struct TilesFn {
+    uint32_t mode, sw, sp, ad;
+    const void *fn;
+    const char *name;
+};
+#define TILES(M, SW, SP) {M, SW, SP, 0u, (const void *)k_pe_tiles<M, SW, SP>, "k_pe_tiles<" #M ", " #SW ", " #SP ">"}
+#define TILES_AD(M, SW, SP) {M, SW, SP, 1u, (const void *)k_pe_tiles<M, SW, SP, true>, "k_pe_tiles<" #M ", " #SW ", " #SP ", true>"}, TILES(M, SW, SP)
+static const TilesFn TILES_TABLE[] = {TILES_AD(1, 10u, 4u), TILES_AD(1, 8u, 3u), TILES_AD(1, 7u, 2u), TILES_AD(1, 7u, 3u), TILES(1, 0u, 0u),
+                                      TILES_AD(2, 16u, 2u), TILES(2, 0u, 0u),    TILES(0, 0u, 0u)};
+
 static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, uint32_t *d_short_mat, uint64_t *d_stats,
                      uint32_t *d_dbg_lists, uint32_t *d_dbg_counts, uint32_t dbg_cap, uint8_t *d_tile_map = nullptr) {
     if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_pe_count: build an index first (vs_index_build)");
     VS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const VsIndexDev &idx = ctx->idx;
-    const uint64_t n_ends = reads->n_ends, n_pairs = n_ends / 2;
+    const uint64_t n_pairs = reads->n_ends / 2;
     ctx->last_ms[0] = ctx->last_ms[1] = ctx->last_ms[2] = 0;
     ctx->last_launched = 0;
-    if (n_ends == 0) return VS_OK;
-    const uint32_t maxlen = (uint32_t)reads->max_len;
-    const uint32_t wpe = maxlen ? (maxlen + 15u) / 16u : 1u;
-    if (idx.n_nodes > 0x01FFFFFEu) return vs_fail(ctx, VS_E_RANGE, "more than 2^25-2 nodes");
     // test hooks: fixed defaults unless the process runs with VS_EXPERIMENT=1 (see VsTuning)
     if (ctx->experiment) vs_tuning_load(ctx->tune, true);
-    const VsTuning &tn = ctx->tune;
-    // probes of the longest end (vs_seed_probes grows with the length): the probe slots a tile reserves per end
-    uint32_t pmax = vs_seed_probes(maxlen, idx.w, idx.s);
-    if (!pmax) pmax = 1u;
-    uint32_t ept = tn.ept ? tn.ept : STD_EPT;
-    if (ept < 2 || ept > TTPB / 2u) ept = STD_EPT;
-    while (ept > 2 && (ept * pmax > NI_CAP || lds_bytes(ept, pmax, ept * wpe) > LDS_BUDGET_BYTES)) ept -= 2;
-    // (LDS is handed out in 1280-byte pieces: 32 000 B per workgroup lets five share a CU, 40 000 four.  A tile of
-    // at least 32 ends that fits one of these is taken over a larger one that wastes the rest.)
-    if (!tn.ept) {
-        for (size_t fit : {(size_t)32000, (size_t)40000}) {
-            uint32_t e2 = ept;
-            while (e2 > STD_EPT / 2u && lds_bytes(e2, pmax, e2 * wpe) > fit) e2 -= 2;
-            if (lds_bytes(e2, pmax, e2 * wpe) <= fit) { ept = e2; break; }
-        }
-    }
-    size_t lds = lds_bytes(ept, pmax, ept * wpe);
-    if (lds > 160u * 1024u)
-        return vs_fail(ctx, VS_E_RANGE, "reads of %u bases with k+1=%u need %zu B of LDS per pair (limit 160 KiB)", maxlen, idx.K, lds);
+    PePlanIn in;
+    in.n_nodes = idx.n_nodes; in.K = idx.K; in.w = idx.w; in.s = idx.s;
+    in.n_seed_pos = ctx->n_seed_pos; in.n_distinct = ctx->n_distinct; in.max_node_len = ctx->max_node_len; in.n_cu = (uint32_t)ctx->n_cu;
+    in.n_ends = reads->n_ends; in.max_len = (uint32_t)reads->max_len;
+    in.has_mask = reads->d_mask != nullptr; in.has_inv4 = reads->d_inv4 != nullptr;
+    in.count = d_node_mat != nullptr; in.tile_map = d_tile_map != nullptr;
+    in.tune = ctx->tune;
+    const PePlan pl = vs_pe_plan(in);
+    if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "%s", pl.msg);
+    if (!pl.n_tiles) return VS_OK;  // an empty block
+    const TilesFn *tf = nullptr;
+    for (const TilesFn &t : TILES_TABLE)
+        if (t.mode == pl.mode && t.sw == pl.sw && t.sp == pl.sp && t.ad == pl.ad) tf = &t;
+    if (!tf) return vs_fail(ctx, VS_E_STATE, "vs_pe_count: the plan names k_pe_tiles<%u, %uu, %uu, %u>, which this build does not hold", pl.mode, pl.sw, pl.sp, pl.ad);
 
     // scratch: slow lists (one slot per pair), counters, dense state
     VS_HIP(ctx, ctx->d_slow_list.reserve(sizeof(uint32_t) * n_pairs));
     VS_HIP(ctx, ctx->d_slow_count.reserve(sizeof(uint32_t) * vs_ctx::SC_WORDS));
     VS_HIP(ctx, ctx->d_slow_list2.reserve(sizeof(uint32_t) * n_pairs));
-    const uint32_t SLOW_GRID = slow_grid_for(idx.n_nodes);
-    uint64_t need_dense = sizeof(uint32_t) * (uint64_t)SLOW_WORDS_PER_NODE * (idx.n_nodes ? idx.n_nodes : 1) * SLOW_GRID;
     if (ctx->dense_nodes != idx.n_nodes) ctx->d_dense.reset();  // (the layout is by node count)
     bool dense_new = false;
-    VS_HIP(ctx, ctx->d_dense.reserve(need_dense, need_dense, &dense_new));
+    VS_HIP(ctx, ctx->d_dense.reserve(pl.dense_bytes, pl.dense_bytes, &dense_new));
     if (dense_new) {
         ctx->dense_nodes = idx.n_nodes;
         // cnt = 0, minp/minj = ~0 once; k_pe_slow restores this state after every end it sweeps
         uint64_t N = idx.n_nodes ? idx.n_nodes : 1;
-        VS_HIP(ctx, hipMemsetAsync(ctx->d_dense.ptr(), 0xFF, need_dense, st));
-        hipLaunchKernelGGL(k_dense_zero_cnt, dim3((unsigned)((N * SLOW_GRID + TPB - 1) / TPB)), dim3(TPB), 0, st,
-                           ctx->d_dense.as<uint32_t>(), N, (uint64_t)SLOW_GRID);
+        VS_HIP(ctx, hipMemsetAsync(ctx->d_dense.ptr(), 0xFF, pl.dense_bytes, st));
+        hipLaunchKernelGGL(k_dense_zero_cnt, dim3((unsigned)((N * pl.slow_grid + TPB - 1) / TPB)), dim3(TPB), 0, st,
+                           ctx->d_dense.as<uint32_t>(), N, (uint64_t)pl.slow_grid);
     }
     VS_HIP(ctx, hipMemsetAsync(ctx->d_slow_count.ptr(), 0, sizeof(uint32_t) * vs_ctx::SC_WORDS, st));
-
-    // locus order of the pairs (see k_pe_locus); VS_NO_SORT=1 keeps the input order
-    const bool use_sort = !tn.no_sort && n_pairs >= 4096 && n_pairs < 0xFFFFFFF0ull;
-    if (use_sort) {
-        const uint64_t nk = (uint64_t)idx.n_nodes + 2u;
+    // locus order of the pairs (see k_pe_locus)
+    if (pl.use_sort) {
         VS_HIP(ctx, ctx->d_locus_keys.reserve(sizeof(uint32_t) * n_pairs));
         VS_HIP(ctx, ctx->d_perm.reserve(sizeof(uint32_t) * n_pairs));
-        const uint64_t hist_words = nk <= LOCUS_LDS_MAX_PASSES * LOCUS_LDS_KEYS ? nk * LOCUS_WGS : nk;
-        VS_HIP(ctx, ctx->d_locus_hist.reserve(sizeof(uint32_t) * hist_words));
-        VS_HIP(ctx, ctx->d_scan_tmp.reserve(sizeof(uint64_t) * (hist_words / 2048 + 4)));
+        VS_HIP(ctx, ctx->d_locus_hist.reserve(sizeof(uint32_t) * pl.locus_hist_words));
+        VS_HIP(ctx, ctx->d_scan_tmp.reserve(sizeof(uint64_t) * (pl.locus_hist_words / 2048 + 4)));
     }
-
-    // which counter kernels follow decides the layout of the hand-off: pair-major with one cell table while 2*N*N fits its
-    // 32-bit keys (packed lists), by row owners above (rows of LCAP words); VS_ACC_ROWS=0 / 1 overrides (0 beyond 46 340
-    // nodes: no table, every increment a global atomic).  VS_NO_AGG=1 turns the summing in LDS off
-    uint32_t use_table = tn.no_agg ? 0u : 1u;
-    const bool fits32 = 2ull * idx.n_nodes * idx.n_nodes < 0xFFFFFFFFull;
-    bool use_rows = tn.acc_rows >= 0 ? tn.acc_rows != 0 : !fits32;
-    if (idx.n_nodes == 0 || !use_table) use_rows = false;
-    if (!use_rows && !fits32) use_table = 0u;
-    // per-end lists handed from k_pe_tiles to k_pe_accumulate
-    const uint64_t n_tiles_all = (n_pairs + ept / 2 - 1) / (ept / 2);
-    const uint64_t list_ends = n_tiles_all * ept;
-    const uint64_t list_words = list_ends * (use_rows ? LC + 4u : LC) + 16u;  // (either layout of the hand-off)
+    // per-end lists handed from k_pe_tiles to the counter kernels
     if (d_node_mat) {
-        VS_HIP(ctx, ctx->d_lists.reserve(sizeof(uint32_t) * list_words));
-        VS_HIP(ctx, ctx->d_list_counts.reserve(sizeof(uint32_t) * (list_ends + 2)));
+        VS_HIP(ctx, ctx->d_lists.reserve(sizeof(uint32_t) * pl.list_words));
+        VS_HIP(ctx, ctx->d_list_counts.reserve(sizeof(uint32_t) * (pl.list_ends + 2)));
     }
 
     PeParams P;
@@ -2486,109 +2376,40 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     P.node_mat = d_node_mat;
     P.short_mat = d_short_mat;
     P.stats = (unsigned long long *)d_stats;
-    P.ept = ept;
-    P.pmax = pmax;
-    P.words_cap = ept * wpe;
-    P.pool = pool_for(ept, &P.pool_bits);
+    P.ept = pl.ept;
+    P.pmax = pl.pmax;
+    P.words_cap = pl.words_cap;
+    P.pool = pl.pool;
+    P.pool_bits = pl.pool_bits;
     P.n_pairs = n_pairs;
-    P.n_tiles = (n_pairs + ept / 2 - 1) / (ept / 2);
-    P.wpe = wpe;
-    P.magic_pmax = pmax > 1u ? (uint32_t)(0x100000000ull / pmax) + 1u : 0u;
-    P.magic_wpe = wpe > 1u ? (uint32_t)(0x100000000ull / wpe) + 1u : 0u;
-    P.perm = use_sort ? ctx->d_perm.as<const uint32_t>() : nullptr;
+    P.n_tiles = pl.n_tiles;
+    P.tiles_per_wg = pl.tiles_per_wg;
+    P.wpe = pl.wpe;
+    P.magic_pmax = pl.magic_pmax;
+    P.magic_wpe = pl.magic_wpe;
+    P.perm = pl.use_sort ? ctx->d_perm.as<const uint32_t>() : nullptr;
     P.slow_list = ctx->d_slow_list.as<uint32_t>();
     P.slow_count = ctx->d_slow_count.as<uint32_t>();
     P.dbg_lists = d_dbg_lists;
     P.dbg_counts = d_dbg_counts;
     P.dbg_cap = dbg_cap;
     P.accumulate = d_node_mat ? 1u : 0u;
-    P.out_rows = use_rows ? 1u : 0u;
-    P.out_lists_hi = ctx->d_lists.as<uint32_t>() + list_ends * LC;
+    P.out_rows = pl.use_rows;
+    P.out_lists_hi = ctx->d_lists.as<uint32_t>() + pl.list_ends * LC;
     P.tile_map = d_node_mat ? d_tile_map : nullptr;
     P.tile_T = (idx.n_nodes + 63u) >> 6;
-    // The shortcut spares a single posting its extension when the previous probe already owns the
-    // match; it pays on graphs whose seeds are mostly unique.  Where seeds repeat (a compacted de
-    // Bruijn graph of many strains: 3.5 postings per distinct seed at configs[2]) nearly every
-    // wavefront holds some single posting and all 64 lanes walk through the test for it: 6.0 ms with,
-    // 5.8 ms without.  VS_SHORTCUT=0/1 overrides.
-    P.shortcut = ctx->n_distinct && ctx->n_seed_pos < 2 * ctx->n_distinct ? 1u : 0u;
-    if (tn.shortcut >= 0) P.shortcut = (uint32_t)tn.shortcut;
-    // (63-base seeds have MIXED keys: equal keys do not prove equal seeds, so "the bases in between match too" does not
-    // follow from two key hits on one diagonal -- the shortcut is for exact keys only, whatever the switch says)
-    if (VS_SEED_VERIFIED(idx.w) == 0u) P.shortcut = 0u;
+    P.shortcut = pl.shortcut;
+    P.mid_fast = pl.mid_fast;
 
-    // straight-line extension when the whole block qualifies (see vs_extend_fast)
-    // (reads with bytes outside ACGT qualify through their position lists, see k_inv4 / vs_seed_limits)
-    // (and nodes below 2^23 bases: the straight-line kernels carry a node's length above the read offset in one table word -- a
-    // longer node takes the generic kernel; r6: the guard was missing for MODE 1)
-    const bool fast = (!reads->d_mask || reads->d_inv4) && idx.s <= 32u && maxlen <= 128u + idx.w + 32u &&
-                      ctx->max_node_len < (1u << 23) && !tn.no_fast;
-    P.mid_fast = fast && VS_SEED_VERIFIED(idx.w) && ctx->max_node_len < (1u << 23) ? 1u : 0u;
-    // compile-time-shape instantiations (see k_pe_tiles): 1 = (10, 4), 2 = (8, 3), 3 = (7, 2); counting runs only (vs_pe_map_ends
-    // takes the generic kernels)
-    const bool std_ok = P.accumulate && !tn.no_std;
-    int std_shape = 0;
-    if (fast && std_ok && ept == STD_EPT && P.pool_bits == STD_POOL_BITS && maxlen <= 159u && idx.K == STD_K && idx.w == STD_W &&
-        idx.s == STD_S) {
-        if (wpe == 10u && pmax == 4u) std_shape = 1;       // 2 x 145..159 bases
-        else if (wpe == 8u && pmax == 3u) std_shape = 2;   // 2 x 113..128
-        else if (wpe == 7u && pmax == 2u) std_shape = 3;   // 2 x 97..107
-        else if (wpe == 7u && pmax == 3u) std_shape = 5;   // 2 x 108..112 (r6, ADVICE r5: these took the generic kernel)
-    }
-    // longer strides and reads (k = 127 with 2 x 250 bases): the straight-line kernel with more windows
-    // Its eight right windows compare 256 bases from where the comparison starts (behind a verified seed, at the first base
-    // of a 63-base one); what has to fit is the read's part behind its FIRST probe, and the grid does not start at offset 0
-    // (vs_seed_phase): reads of up to 317 bases qualify at k = 127 (r5; 256 with the grid of rounds 1-4)
-    uint32_t long_reach = 0;
-    for (uint32_t len = idx.K; len <= maxlen; len++) {
-        const uint32_t behind = len - vs_seed_phase(len, idx.w, idx.s) - VS_SEED_VERIFIED(idx.w);
-        long_reach = behind > long_reach ? behind : long_reach;
-    }
-    const bool fast_long = !fast && (!reads->d_mask || reads->d_inv4) && idx.s <= 128u && long_reach <= 256u && maxlen < 512u &&
-                           ctx->max_node_len < (1u << 23) && !tn.no_fast;
-    if (fast_long && std_ok && ept == STD2_EPT && P.pool_bits == STD2_POOL_BITS && idx.K == STD2_K && idx.w == STD2_W && idx.s == STD2_S &&
-        wpe == 16u && pmax == 2u)
-        std_shape = 4;
-    // (r5) the adaptive step grid (k_pe_tiles, ADAPT) probes twice as many seeds to expand fewer postings: it pays where a
-    // seed has many postings -- 8.9 seed positions per distinct seed at configs[4]: 24.8 -> 22.5 ms -- and costs a little
-    // where it has few (3.6 at configs[2]: 4.80 -> 4.87 ms).  VS_ADAPT_GRID=0 / 1 overrides.
-    bool adapt = std_shape != 0 && ctx->n_distinct && ctx->n_seed_pos >= 6u * ctx->n_distinct;
-    if (tn.adapt_grid >= 0) adapt = std_shape != 0 && tn.adapt_grid != 0;
-    struct TilesFn { const void *fn; const char *name; };
-    const TilesFn tf = std_shape == 1   ? (adapt ? TilesFn{(const void *)k_pe_tiles<1, 10u, 4u, true>, "k_pe_tiles<1, 10u, 4u, true>"}
-                                                 : TilesFn{(const void *)k_pe_tiles<1, 10u, 4u>, "k_pe_tiles<1, 10u, 4u>"})
-                       : std_shape == 2 ? (adapt ? TilesFn{(const void *)k_pe_tiles<1, 8u, 3u, true>, "k_pe_tiles<1, 8u, 3u, true>"}
-                                                 : TilesFn{(const void *)k_pe_tiles<1, 8u, 3u>, "k_pe_tiles<1, 8u, 3u>"})
-                       : std_shape == 3 ? (adapt ? TilesFn{(const void *)k_pe_tiles<1, 7u, 2u, true>, "k_pe_tiles<1, 7u, 2u, true>"}
-                                                 : TilesFn{(const void *)k_pe_tiles<1, 7u, 2u>, "k_pe_tiles<1, 7u, 2u>"})
-                       : std_shape == 5 ? (adapt ? TilesFn{(const void *)k_pe_tiles<1, 7u, 3u, true>, "k_pe_tiles<1, 7u, 3u, true>"}
-                                                 : TilesFn{(const void *)k_pe_tiles<1, 7u, 3u>, "k_pe_tiles<1, 7u, 3u>"})
-                       : fast           ? TilesFn{(const void *)k_pe_tiles<1, 0u, 0u>, "k_pe_tiles<1, 0u, 0u>"}
-                       : std_shape == 4 ? (adapt ? TilesFn{(const void *)k_pe_tiles<2, 16u, 2u, true>, "k_pe_tiles<2, 16u, 2u, true>"}
-                                                 : TilesFn{(const void *)k_pe_tiles<2, 16u, 2u>, "k_pe_tiles<2, 16u, 2u>"})
-                       : fast_long      ? TilesFn{(const void *)k_pe_tiles<2, 0u, 0u>, "k_pe_tiles<2, 0u, 0u>"}
-                                        : TilesFn{(const void *)k_pe_tiles<0, 0u, 0u>, "k_pe_tiles<0, 0u, 0u>"};
-    const void *tiles_fn = tf.fn;
-    if (std_shape && !adapt) lds = (size_t)tile_layout(ept, pmax, ept * wpe, 768u, std_shape == 4 ? 192u : 64u).total * sizeof(uint32_t);
+    const size_t lds = pl.lds_bytes;
     if (lds > 64u * 1024u)
-        VS_HIP(ctx, hipFuncSetAttribute(tiles_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    uint64_t grid = P.n_tiles;
-    // Many more workgroups than fit at once (4 per CU): loci differ a lot in postings per read, and
-    // short runs let the dispatcher even that out (runs of ~10 tiles at configs[2]: 8.4 ms, against
-    // 10.0 ms with 8 workgroups per CU and 9.0 ms with one tile per workgroup)
-    const uint64_t max_grid = (uint64_t)ctx->n_cu * tn.grid_per_cu;
-    if (grid > max_grid) grid = max_grid;
-    P.tiles_per_wg = (uint32_t)((P.n_tiles + grid - 1) / grid);
-    grid = (P.n_tiles + P.tiles_per_wg - 1) / P.tiles_per_wg;
+        VS_HIP(ctx, hipFuncSetAttribute(tf->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     VS_HIP(ctx, hipEventRecord(ctx->ev[3], st));
-    if (use_sort) {
-        const uint64_t nk = (uint64_t)idx.n_nodes + 2u;
-        const bool lds_sort = nk <= LOCUS_LDS_MAX_PASSES * LOCUS_LDS_KEYS && !tn.locus_global;
-        ctx->last_launched |= lds_sort ? VS_RAN_LOCUS_LDS_SORT : VS_RAN_LOCUS_GLOBAL_SORT;
-        if (lds_sort) {
-            const uint32_t n_wg = LOCUS_WGS;
-            const uint32_t chunk = (uint32_t)((n_pairs + n_wg - 1) / n_wg);
-            const uint32_t per_pass = (uint32_t)(nk < LOCUS_LDS_KEYS ? nk : LOCUS_LDS_KEYS);
+    if (pl.use_sort) {
+        const uint64_t nk = pl.locus_keys;
+        ctx->last_launched |= pl.lds_sort ? VS_RAN_LOCUS_LDS_SORT : VS_RAN_LOCUS_GLOBAL_SORT;
+        if (pl.lds_sort) {
+            const uint32_t n_wg = LOCUS_WGS, chunk = pl.locus_chunk, per_pass = pl.locus_per_pass;
             const size_t lds_keys = sizeof(uint32_t) * per_pass;
             if (lds_keys > 64u * 1024u) {
                 VS_HIP(ctx, hipFuncSetAttribute((const void *)k_locus_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_keys));
@@ -2621,57 +2442,45 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     }
     VS_HIP(ctx, hipEventRecord(ctx->ev[0], st));
     if (!d_node_mat) VS_HIP(ctx, hipEventRecord(ctx->ev[4], st));
-    ctx->last_kernel = tf.name;
+    ctx->last_kernel = tf->name;
     {
         void *kargs[] = {(void *)&P};
-        VS_HIP(ctx, hipLaunchKernel(tiles_fn, dim3((unsigned)grid), dim3(TTPB), kargs, lds, st));
+        VS_HIP(ctx, hipLaunchKernel(tf->fn, dim3((unsigned)pl.grid), dim3(TTPB), kargs, lds, st));
     }
     if (d_node_mat) {
         // the last tile may be partly empty: its unused rows must read as length 0
         const uint64_t used_ends = 2ull * n_pairs;
-        if (list_ends > used_ends)
-            VS_HIP(ctx, hipMemsetAsync(ctx->d_list_counts.as<uint32_t>() + used_ends, 0, sizeof(uint32_t) * (list_ends - used_ends), st));
-        const uint64_t slots_pairs = list_ends / 2;
+        if (pl.list_ends > used_ends)
+            VS_HIP(ctx, hipMemsetAsync(ctx->d_list_counts.as<uint32_t>() + used_ends, 0, sizeof(uint32_t) * (pl.list_ends - used_ends), st));
+        const uint64_t slots_pairs = pl.list_ends / 2;
         VS_HIP(ctx, hipEventRecord(ctx->ev[4], st));
-        if (use_rows) {
-            const int rc = pe_count_by_rows(ctx, slots_pairs, d_node_mat, d_short_mat, d_tile_map, P.tile_T);
+        if (pl.use_rows) {
+            const int rc = pe_count_by_rows(ctx, pl, d_node_mat, d_short_mat, d_tile_map, P.tile_T);
             if (rc) return rc;
             ctx->last_launched |= VS_RAN_ROW_OWNERS;
         } else {
-            // chunks of pairs: 32 per CU, for the same reason as above (4.9 -> 3.9 ms), each at least one round of
-            // ACC_TPB pairs
-            uint32_t acc_grid = (uint32_t)ctx->n_cu * 32u;
-            uint32_t per_wg = (uint32_t)((slots_pairs + acc_grid - 1) / acc_grid);
-            per_wg = (per_wg + ACC_TPB - 1) / ACC_TPB * ACC_TPB;
-            acc_grid = (uint32_t)((slots_pairs + per_wg - 1) / per_wg);
-            // the chunks are not bound to workgroups: two workgroups per CU take the next chunk off a
-            // counter whenever they are free, so a cell table lives across chunks and is written out on
-            // fill only (3.85 -> 3.6 ms against one workgroup per chunk)
+            // (the chunks of pairs are not bound to workgroups: they are taken off a counter, see vs_pe_plan)
             uint32_t *acc_queue = ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_ACC_QUEUE;
-            if (acc_grid > (uint32_t)ctx->n_cu * 2u) acc_grid = (uint32_t)ctx->n_cu * 2u;
-            // the table is written out once this many of its slots are taken: probing stays short at a low
-            // fill, and cells of loci the run has left do not pile up (VS_ACC_FILL: percent)
-            uint32_t fill_limit = ACC_SLOTS / 16u;
-            if (tn.acc_fill_pct >= 0) fill_limit = (uint32_t)((uint64_t)ACC_SLOTS * (uint32_t)tn.acc_fill_pct / 100u);
-            if (d_tile_map && slots_pairs)  // (timed with the counter kernel: it is part of the counting)
+            if (pl.mark_tiles)  // (timed with the counter kernel: it is part of the counting)
                 hipLaunchKernelGGL(k_mark_tiles, dim3((unsigned)((slots_pairs + 255u) / 256u)), dim3(256), 0, st, ctx->d_lists.as<const uint32_t>(),
-                                   ctx->d_list_counts.as<const uint32_t>(), slots_pairs, d_tile_map, P.tile_T, ept);
+                                   ctx->d_list_counts.as<const uint32_t>(), slots_pairs, d_tile_map, P.tile_T, pl.ept);
             VS_HIP(ctx, hipFuncSetAttribute((const void *)k_pe_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ACC_LDS_BYTES));
-            hipLaunchKernelGGL(k_pe_accumulate, dim3(acc_grid), dim3(ACC_TPB), ACC_LDS_BYTES, st, ctx->d_lists.as<const uint32_t>(),
-                               ctx->d_list_counts.as<const uint32_t>(), slots_pairs, per_wg, idx.n_nodes, use_table, fill_limit, d_node_mat,
-                               d_short_mat, acc_queue, ept);
+            hipLaunchKernelGGL(k_pe_accumulate, dim3(pl.acc_grid), dim3(ACC_TPB), ACC_LDS_BYTES, st, ctx->d_lists.as<const uint32_t>(),
+                               ctx->d_list_counts.as<const uint32_t>(), slots_pairs, pl.acc_per_wg, idx.n_nodes, pl.use_table, pl.acc_fill, d_node_mat,
+                               d_short_mat, acc_queue, pl.ept);
         }
     }
     VS_HIP(ctx, hipEventRecord(ctx->ev[1], st));
     // overflow pairs: one wavefront per pair with its state in LDS first, the general kernel for what that cannot hold
-    ctx->last_launched |= tn.no_mid ? 0u : VS_RAN_PE_MID;
-    if (!tn.no_mid) {
+    const bool no_mid = ctx->tune.no_mid;
+    ctx->last_launched |= no_mid ? 0u : VS_RAN_PE_MID;
+    if (!no_mid) {
         hipLaunchKernelGGL(k_pe_mid, dim3((unsigned)ctx->n_cu * 8u), dim3(TPB), 0, st, P, ctx->d_slow_list.as<const uint32_t>(),
                            ctx->d_slow_count.as<const uint32_t>(), (uint32_t)n_pairs, ctx->d_slow_list2.as<uint32_t>(), ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_SLOW);
-        hipLaunchKernelGGL(k_pe_slow, dim3(SLOW_GRID), dim3(TPB), 0, st, P, ctx->d_dense.as<uint32_t>(), (uint32_t)n_pairs,
+        hipLaunchKernelGGL(k_pe_slow, dim3(pl.slow_grid), dim3(TPB), 0, st, P, ctx->d_dense.as<uint32_t>(), (uint32_t)n_pairs,
                            ctx->d_slow_list2.as<const uint32_t>(), ctx->d_slow_count.as<const uint32_t>() + vs_ctx::SC_SLOW);
     } else {
-        hipLaunchKernelGGL(k_pe_slow, dim3(SLOW_GRID), dim3(TPB), 0, st, P, ctx->d_dense.as<uint32_t>(), (uint32_t)n_pairs,
+        hipLaunchKernelGGL(k_pe_slow, dim3(pl.slow_grid), dim3(TPB), 0, st, P, ctx->d_dense.as<uint32_t>(), (uint32_t)n_pairs,
                            ctx->d_slow_list.as<const uint32_t>(), ctx->d_slow_count.as<const uint32_t>());
     }
     VS_HIP(ctx, hipEventRecord(ctx->ev[2], st));
