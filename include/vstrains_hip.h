@@ -131,7 +131,9 @@ void vs_fastq_close(vs_fastq *fq);
  *      not end in a newline); the ranks exchange these (an all-gather of three integers per file);
  *   2. from the totals every rank derives its record range and calls vs_fastq_open_records with everybody's counts:
  *      only the bytes of records [first, last) are indexed; the handle numbers them from 0.
- * Files with '\r' or gzip files are opened whole (vs_fastq_open) by every rank instead. */
+ * Files with '\r' or gzip files are opened whole (vs_fastq_open) by every rank instead -- except a pair of whole BGZF files
+ * of plain ASCII with LF line ends, which the ranks share by MEMBER and inflate on their devices (the member-sharded open
+ * further down: vs_bgzf_walk_file .. vs_fastq_stream_open_range). */
 int vs_fastq_count_part(const char *path, uint32_t part, uint32_t n_parts, uint64_t out[3]);
 int vs_fastq_open_records(vs_ctx *ctx, const char *fwd_path, const char *rve_path, uint32_t n_parts,
                           const uint64_t *counts_f, const uint64_t *counts_r, uint64_t first, uint64_t last,
@@ -197,6 +199,45 @@ int vs_inflate_host(const uint8_t *payload, uint32_t len, uint8_t *out, uint32_t
 int vs_inflate_bgzf(vs_ctx *ctx, const uint8_t *data, uint64_t n, uint8_t *out, uint64_t out_cap, uint32_t guard, uint32_t *status,
                     uint64_t status_cap, uint64_t info[2]);
 int vs_fastq_stream_inflate_info(const vs_fastq_stream *s, uint64_t info[4]);
+
+/* Member-sharded open of a BGZF pair for one process per GPU (additions to ABI 10): no rank inflates a whole file, nothing
+ * is inflated on a host, and every rank streams exactly its own records.  Both files must be regular files made of whole
+ * BGZF members from the first byte to the last.  Two passes with one exchange between them (pe.FastqStream.open_shard):
+ *   1. every rank walks the member headers of both files (vs_bgzf_walk_file), takes the members [M r / W, M (r + 1) / W) of
+ *      each and has the device count their lines (vs_bgzf_count_lines); the ranks all-gather the per-member counts, the OR
+ *      of the flags and the last byte of the last non-empty member;
+ *   2. from everybody's counts every rank derives the pair total min(lines_f // 4, lines_r // 4) (PE_Inference.py:154), its
+ *      record range and, per file, where to start (vs_bgzf_shard_plan), and opens the streamed ingest on that member range
+ *      (vs_fastq_stream_open_range).
+ * A rank inflates its share twice (the text of pass 1 is not kept: its device memory does not grow with the file); a '\r' or
+ * a byte >= 0x80 anywhere, or a file that is not whole BGZF, sends all ranks to the cooperative open above instead.
+ *   vs_bgzf_walk_file   : host only, reads headers and trailers, no payload.  offsets[i] (up to cap entries) = file offset of
+ *                         member i, and one more entry = one past the last member; info[0] = members, [1] = the offset of the
+ *                         first byte that is not part of one, [2] = what is there (0 / 1 / 2 as vs_bgzf_walk: the file
+ *                         qualifies only with 0), [3] = the file's size
+ *   vs_bgzf_count_lines : members [0, n) at offsets[0 .. n] (n + 1 entries, a slice of the walk's) read -- those bytes only --
+ *                         and inflated on the device, `grid` wavefronts looping over them with one 64 KiB region each
+ *                         (k_inflate_count); counts[i] = newlines of member i; info[0] = flags (bit 0 a '\r', bit 1 a byte
+ *                         >= 0x80), [1] = the last byte of the last non-empty member (256: all are empty), [2] = members
+ *                         inflated, [3] = file bytes read.  CRC32 and every check of the streamed inflate hold; a member the
+ *                         device rejects is VS_E_ARG, worded by zlib on the host as the streamed ingest words it
+ *   vs_inflate_count_host : host only.  The count of the kernel through the same decoder text, one lane: res[0] = status (as
+ *                         vs_inflate_host), [1] = newlines, [2] = flags, [3] = last byte (0 for an empty member)
+ *   vs_bgzf_shard_plan  : host only, a pure function.  counts[n_members] of ONE file, no_final_newline = its last byte is no
+ *                         '\n'; for the records [first, last) (record r = lines 4r .. 4r+3): plan[0] = the first member to
+ *                         open, [1] = the lines to skip in front of it, [2] = one past the last member needed.  The first
+ *                         member is the one that holds the newline in front of line 4 * first, so neighbouring ranks share
+ *                         that one member and no other; an empty range opens nothing ({0, 0, 0})
+ *   vs_fastq_stream_open_range : the streamed ingest on range[3f .. 3f+2] = {offset of the first member, offset one past the
+ *                         last, lines to skip} of file f; it delivers n_pairs pairs and then reports the end.  The readers
+ *                         seek to the first offset and never read at or beyond the second; a final line without a newline
+ *                         counts only where the range ends at the end of the file */
+int vs_bgzf_walk_file(const char *path, uint64_t *offsets, uint64_t cap, uint64_t info[4]);
+int vs_bgzf_count_lines(vs_ctx *ctx, const char *path, const uint64_t *offsets, uint64_t n, uint32_t *counts, uint64_t info[4]);
+int vs_inflate_count_host(const uint8_t *payload, uint32_t len, uint32_t isize, uint32_t crc, uint32_t res[4]);
+int vs_bgzf_shard_plan(const uint32_t *counts, uint64_t n_members, int no_final_newline, uint64_t first, uint64_t last, uint64_t plan[3]);
+int vs_fastq_stream_open_range(vs_ctx *ctx, const char *fwd_path, const char *rve_path, const uint64_t range[6], uint64_t n_pairs,
+                               vs_fastq_stream **out);
 
 /* pe_info / st_info text (PE_Inference.py:194-205): "{id_i}:{id_j}:{count}\n" for all i, j in
  * row-major order, zeros included.  ids: the n node names concatenated, id_off[n+1]; mat: HOST

@@ -12,6 +12,13 @@ that fails ends the run.  All legs must give the same counters.
     c  streamed BGZF, inflated on the device
     d  mapped BGZF                               (VS_FASTQ_STREAM=0: inflated whole at open)
     p  leg b on another build of the library (--parent-lib, e.g. tools/_ab/parent.so of tools/ab_build.sh)
+    q  leg c on that other build (needs --parent-lib; a build that has the device inflate)
+    s  sharded BGZF: --ranks processes under torchrun on ONE device over gloo, the files shared by member and inflated
+       on the device (FastqStream.open_shard); seconds = the slowest rank's wall time from the FASTQ paths to the summed
+       counters, rss_mb = the ranks' peak RSS added up.  Ranks sharing one GPU say nothing about scaling.  (Not measured yet:
+       profiles/stream_ingest.md, "Sharded BGZF", says what is to be reported.)
+    t  the same run on the other build (needs --parent-lib): what a sharded run did before, every rank inflating both
+       whole files with zlib at the open (VS_BGZF_DEVICE=0 keeps the new open out of the way)
 
     python tools/bgzf_legs.py [--out legs.json]
     python tools/bgzf_legs.py --only c --rounds 1 --keep DIR     (one leg, e.g. under rocprofv3 ... -- python ...)
@@ -36,7 +43,13 @@ LEGS = {
     "c": ("streamed BGZF, inflated on the device", "fq.gz", {}),
     "d": ("mapped BGZF (VS_FASTQ_STREAM=0)", "fq.gz", {"VS_FASTQ_STREAM": "0"}),
     "p": ("streamed BGZF on the other build of the library", "fq.gz", {"VS_FASTQ_STREAM": "1"}),
+    "q": ("streamed BGZF, inflated on the device, on the other build of the library", "fq.gz", {}),
+    "s": ("sharded BGZF by member, device inflate, ranks on one GPU over gloo", "fq.gz", {}),
+    "t": ("sharded BGZF on the other build: whole-file zlib open on every rank", "fq.gz", {"VS_BGZF_DEVICE": "0"}),
 }
+OTHER_BUILD = "pqt"  # legs that run on --parent-lib
+SHARDED = "st"       # legs that run under torchrun
+NEW_ENTRIES = ("vs_bgzf_walk_file", "vs_bgzf_count_lines", "vs_inflate_count_host", "vs_bgzf_shard_plan", "vs_fastq_stream_open_range")
 K = 55
 
 
@@ -67,17 +80,29 @@ def run_leg(d, lib):
 
     if lib:  # another build of the library: without the entries it does not have
         nat.LIB_PATH = lib
-        for name in ("vs_bgzf_walk", "vs_inflate_host", "vs_inflate_bgzf", "vs_fastq_stream_inflate_info"):
-            nat.SYMBOLS.pop(name, None)
+        import ctypes
+
+        import torch  # noqa: F401  (first, as _native.lib() does: the build must bind to the HIP runtime torch brings)
+
+        have = ctypes.CDLL(lib)
+        for name in ("vs_bgzf_walk", "vs_inflate_host", "vs_inflate_bgzf", "vs_fastq_stream_inflate_info") + NEW_ENTRIES:
+            if not hasattr(have, name):
+                nat.SYMBOLS.pop(name, None)
     import numpy as np
 
     from vstrains_amd import pe as host
     from vstrains_amd import pe_inference
 
     ext = os.environ["BGZF_LEG_EXT"]
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:  # (a sharded leg: the ranks share device 0, the counters are summed over gloo)
+        import torch.distributed as dist
+
+        os.environ.setdefault("VS_DIST_BACKEND", "gloo")
+        dist.init_process_group("gloo")
     ctx = host.Context(0)
     info = {}
-    if lib:  # (that build has no member counts to report)
+    if lib and "vs_fastq_stream_inflate_info" not in nat.SYMBOLS:  # (that build has no member counts to report)
         import ctypes as C
 
         def plain_info(self):
@@ -102,10 +127,20 @@ def run_leg(d, lib):
     ctx.sync()
     dt = time.perf_counter() - t0
     sys.stdout = stdout
+    rss = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
+    if world > 1:
+        every = [None] * world
+        dist.all_gather_object(every, (dt, rss))
+        dt, rss = max(e[0] for e in every), sum(e[1] for e in every)
+        info = dict(ranks=world, rss_mb_per_rank=[round(e[1]) for e in every])
+        if dist.get_rank() != 0:
+            dist.barrier()
+            return
     node, short, stats = counter.result()
     h = hashlib.sha256(np.ascontiguousarray(node).tobytes() + np.ascontiguousarray(short).tobytes() + repr(stats).encode()).hexdigest()
-    print("LEG " + json.dumps(dict(seconds=dt, rss_mb=resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0, digest=h,
-                                   node_sum=int(node.sum()), info={k: v for k, v in info.items()})))
+    print("LEG " + json.dumps(dict(seconds=dt, rss_mb=rss, digest=h, node_sum=int(node.sum()), info={k: v for k, v in info.items()})))
+    if world > 1:
+        dist.barrier()
 
 
 def main():
@@ -116,6 +151,7 @@ def main():
     ap.add_argument("--seed", type=int, default=31)
     ap.add_argument("--only", default="abcd")
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--ranks", type=int, default=2, help="processes of the sharded legs s and t (at most 8: they share one GPU)")
     ap.add_argument("--limit", type=int, default=240, help="seconds per leg")
     ap.add_argument("--keep", default=None, help="make (or reuse) the inputs in this directory")
     ap.add_argument("--out", default=None)
@@ -136,17 +172,31 @@ def main():
         with open(os.path.join(d, "sizes.json"), "w") as fh:
             json.dump(sizes, fh)
     sizes = json.load(open(os.path.join(d, "sizes.json")))
-    legs = [l for l in args.only if l in LEGS] + (["p"] if args.parent_lib else [])
+    legs = [l for l in args.only if l in LEGS and (l not in OTHER_BUILD or args.parent_lib)]
+    if args.parent_lib and args.only == "abcd":
+        legs.append("p")
+    if not 1 < args.ranks <= 8 and any(l in SHARDED for l in legs):
+        sys.exit("--ranks must be 2 .. 8")
     runs = {l: [] for l in legs}
     base = {k: v for k, v in os.environ.items() if k not in ("VS_FASTQ_STREAM", "VS_BGZF_DEVICE", "VS_STREAM_CHUNK")}
     failed = None
     for rnd in range(args.rounds):
         for l in legs:
             env = dict(base, BGZF_LEG_EXT=LEGS[l][1], **LEGS[l][2])
-            if l == "p":
+            if l in OTHER_BUILD:
                 env["BGZF_LEG_LIB"] = os.path.abspath(args.parent_lib)
+            cmd = [sys.executable]
+            if l in SHARDED:
+                import socket
+
+                with socket.socket() as sk:
+                    sk.bind(("127.0.0.1", 0))
+                    port = sk.getsockname()[1]
+                cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.ranks), "--master-addr", "127.0.0.1",
+                        "--master-port", str(port)]
+                env.update(VS_DIST_BACKEND="gloo", VS_DIST_DEVICE="0")
             try:
-                proc = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", d], env=env, capture_output=True, text=True,
+                proc = subprocess.run(cmd + [os.path.abspath(__file__), "--leg", d], env=env, capture_output=True, text=True,
                                       timeout=args.limit, cwd=ROOT)
             except subprocess.TimeoutExpired:
                 failed = "leg %s round %d: over %d s" % (l, rnd, args.limit)

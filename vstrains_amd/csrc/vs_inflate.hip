@@ -32,8 +32,10 @@
 
 // ---- the walker (host) -------------------------------------------------------------------------------------------------
 // p[0, avail): 0 and *m (in_off relative to p, out_off 0), *member_size when a whole BGZF member starts at p; 1 when what
-// is there could still become one ("need more bytes"); 2 when it cannot ("not BGZF")
-int vs_bgzf_parse(const uint8_t *p, size_t avail, vs_bgzf_member *m, size_t *member_size) {
+// is there could still become one ("need more bytes"); 2 when it cannot ("not BGZF").  vs_bgzf_header is its first half:
+// the same verdict from the header alone (*header_size up to the payload, *member_size = BSIZE + 1), for a walk that hops
+// from header to header without reading a payload.
+int vs_bgzf_header(const uint8_t *p, size_t avail, size_t *header_size, size_t *member_size) {
     static const uint8_t magic[4] = {0x1f, 0x8b, 0x08, 0x04};
     for (size_t i = 0; i < 4 && i < avail; i++)
         if (p[i] != magic[i]) return 2;
@@ -54,13 +56,21 @@ int vs_bgzf_parse(const uint8_t *p, size_t avail, vs_bgzf_member *m, size_t *mem
         at += 4 + slen;
     }
     if (!found || bsize < 12 + xlen + 8) return 2;
+    *header_size = 12 + xlen;
+    *member_size = bsize;
+    return 0;
+}
+
+int vs_bgzf_parse(const uint8_t *p, size_t avail, vs_bgzf_member *m, size_t *member_size) {
+    size_t head = 0, bsize = 0;
+    if (const int st = vs_bgzf_header(p, avail, &head, &bsize)) return st;
     if (avail < bsize) return 1;
     const uint8_t *t = p + bsize - 8;
     const uint32_t crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
     const uint32_t isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
     if (isize > INF_MAX_ISIZE) return 2;
-    m->in_off = (uint32_t)(12 + xlen);
-    m->in_len = (uint32_t)(bsize - 12 - xlen - 8);  // < 65536
+    m->in_off = (uint32_t)head;
+    m->in_len = (uint32_t)(bsize - head - 8);  // < 65536
     m->out_off = 0;
     m->isize = isize;
     m->crc = crc;
@@ -117,6 +127,58 @@ uint32_t vs_inflate_member_host(const uint8_t *pay, uint32_t len, uint8_t *out, 
     return st;
 }
 
+// the count of k_inflate_count with one lane: res[0 .. 3] as the kernel writes them
+void vs_inflate_count_member_host(const uint8_t *pay, uint32_t len, uint32_t isize, uint32_t crc, uint32_t res[4]) {
+    res[0] = INF_E_ARG;
+    res[1] = res[2] = res[3] = 0;
+    if (isize > INF_MAX_ISIZE || len >= 65536u) return;
+    InfState *S = new InfState();
+    std::vector<uint8_t> out(isize ? isize : 1u);
+    inf_crc_table(S, 0, 1);
+    uint32_t st = inf_member(S, pay, len, out.data(), isize, 0, 1);
+    if (st == INF_OK) {
+        uint32_t c = 0, nl = 0, fl = 0;
+        for (uint32_t part = 0; part < INF_CRC_PARTS; part++) c ^= inf_crc_count_part(S, out.data(), isize, part, nl, fl);
+        if (c != crc) st = INF_E_CRC;
+        else {
+            res[1] = nl;
+            res[2] = fl;
+            res[3] = isize ? out[isize - 1u] : 0u;
+        }
+    }
+    res[0] = st;
+    delete S;
+}
+
+// ---- the record range of a rank in per-member line counts (host) --------------------------------------------------------------
+// counts[0, n): newlines per member of ONE file, in file order; no_final_newline: the file's last byte is no '\n' (its last
+// line then counts although no newline ends it, as PE_Inference.py:154 counts it).  Record r is lines 4r .. 4r+3.  For the
+// records [first, last): plan[0] = the first member to open, plan[1] = the lines to skip in front of it, plan[2] = one past
+// the last member needed.  The first member is the one that holds the newline in front of line 4 * first (member 0, nothing
+// skipped, for first == 0): what lies behind that newline cannot be told from counts alone, so a range that starts exactly
+// on a member boundary still opens the member before it, only to skip all of it; neighbours share that one member and no
+// other.  An empty range opens nothing: {0, 0, 0}.  Returns 1 when the file has fewer than 4 * last lines, else 0.
+static int shard_plan(const uint32_t *counts, uint64_t n, int no_final_newline, uint64_t first, uint64_t last, uint64_t plan[3]) {
+    plan[0] = plan[1] = plan[2] = 0;
+    if (last <= first) return 0;
+    const uint64_t line0 = 4u * first, line1 = 4u * last;  // newline number line0 (counted from 1) ends the line in front
+    uint64_t before = 0, m = 0;
+    if (line0) {
+        while (m < n && before + counts[m] < line0) before += counts[m++];
+        if (m == n) return 1;
+        plan[0] = m;
+        plan[1] = line0 - before;
+    }
+    while (m < n && before + counts[m] < line1) before += counts[m++];
+    if (m < n) {
+        plan[2] = m + 1u;
+        return 0;
+    }
+    plan[2] = n;  // the last line has no newline: it runs to the end of the file
+    return (no_final_newline && before + 1u == line1) ? 0 : 1;
+}
+
+
 extern "C" {
 
 int vs_bgzf_walk(const uint8_t *buf, uint64_t n, uint64_t *members, uint64_t cap, uint64_t info[3]) {
@@ -146,6 +208,21 @@ int vs_bgzf_walk(const uint8_t *buf, uint64_t n, uint64_t *members, uint64_t cap
 int vs_inflate_host(const uint8_t *payload, uint32_t len, uint8_t *out, uint32_t isize, uint32_t crc, uint32_t *status) {
     if ((!payload && len) || (!out && isize) || !status) return vs_fail(nullptr, VS_E_ARG, "vs_inflate_host: bad argument");
     *status = vs_inflate_member_host(payload, len, out, isize, crc);
+    return VS_OK;
+}
+
+int vs_inflate_count_host(const uint8_t *payload, uint32_t len, uint32_t isize, uint32_t crc, uint32_t res[4]) {
+    if ((!payload && len) || !res) return vs_fail(nullptr, VS_E_ARG, "vs_inflate_count_host: bad argument");
+    vs_inflate_count_member_host(payload, len, isize, crc, res);
+    return VS_OK;
+}
+
+int vs_bgzf_shard_plan(const uint32_t *counts, uint64_t n_members, int no_final_newline, uint64_t first, uint64_t last, uint64_t plan[3]) {
+    if ((!counts && n_members) || !plan || first > last || last > (1ull << 60))
+        return vs_fail(nullptr, VS_E_ARG, "vs_bgzf_shard_plan: bad argument");
+    if (shard_plan(counts, n_members, no_final_newline, first, last, plan))
+        return vs_fail(nullptr, VS_E_RANGE, "vs_bgzf_shard_plan: records [%llu, %llu) lie beyond the lines counted", (unsigned long long)first,
+                       (unsigned long long)last);
     return VS_OK;
 }
 

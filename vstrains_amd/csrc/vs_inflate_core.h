@@ -397,4 +397,25 @@ INF_FN uint32_t inf_crc_part(const InfState *S, const uint8_t *out, uint32_t isi
     return hi < isize ? inf_multmodp(inf_x8n(isize - hi), c) : c;
 }
 
+// ---- line count beside the CRC (the member-sharded open counts lines per member and throws the text away) ---------------
+enum { INF_FL_CR = 1u, INF_FL_HIGH = 2u };  // a '\r' seen, a byte >= 0x80 seen (FL_CR / FL_HIGH of the streamed ingest)
+
+// inf_crc_part of slice `part` that also adds the slice's '\n' bytes to nl and ORs INF_FL_* into flags: the one walk over
+// the output serves both.  The slice bounds are inf_crc_part's, so the loop is bounded by isize.
+INF_FN uint32_t inf_crc_count_part(const InfState *S, const uint8_t *out, uint32_t isize, uint32_t part, uint32_t &nl, uint32_t &flags) {
+    const uint32_t slice = (isize + INF_CRC_PARTS - 1u) / INF_CRC_PARTS;
+    const uint32_t lo = part * slice < isize ? part * slice : isize;
+    const uint32_t hi = lo + slice < isize ? lo + slice : isize;
+    if (hi == lo) return 0;
+    uint32_t c = 0xFFFFFFFFu;
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint32_t b = out[i];
+        c = S->crc_tab[(c ^ b) & 255u] ^ (c >> 8);
+        nl += b == 0x0Au ? 1u : 0u;
+        flags |= (b == 0x0Du ? (uint32_t)INF_FL_CR : 0u) | (b >= 0x80u ? (uint32_t)INF_FL_HIGH : 0u);
+    }
+    c = ~c;
+    return hi < isize ? inf_multmodp(inf_x8n(isize - hi), c) : c;
+}
+
 #endif  // VS_INFLATE_CORE_H

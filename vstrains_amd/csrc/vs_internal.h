@@ -205,10 +205,16 @@ struct vs_bgzf_member {
 // p[0, avail): 0 when a whole BGZF member starts at p (*m with in_off relative to p and out_off 0, *member_size its bytes),
 // 1 when what is there may still become one with more bytes, 2 when it is not BGZF
 int vs_bgzf_parse(const uint8_t *p, size_t avail, vs_bgzf_member *m, size_t *member_size);
+// the same verdict from the header alone: *header_size = the bytes in front of the payload, *member_size = all of the member
+int vs_bgzf_header(const uint8_t *p, size_t avail, size_t *header_size, size_t *member_size);
 // n members, one wavefront each: status[i] = 0 or an INF_E_* word; atomicMin(first_bad, base + i) for every i that failed
 // (member i is dir[i], or dir[n - 1 - i] when `reversed`)
 void vs_launch_inflate(hipStream_t st, const uint8_t *comp, uint64_t comp_size, uint8_t *out, uint64_t out_size, const vs_bgzf_member *dir,
                        uint32_t n, uint32_t *status, uint32_t *first_bad, uint32_t base, int reversed);
+// n members counted and thrown away (k_inflate_count): `grid` wavefronts, each with 64 KiB of `scratch` of its own, loop
+// over the members; res[4 i ..] = status, newlines, flags (bit 0 '\r', bit 1 a byte >= 0x80), last byte of member dir[i]
+void vs_launch_inflate_count(hipStream_t st, const uint8_t *comp, uint64_t comp_size, uint8_t *scratch, uint32_t grid, const vs_bgzf_member *dir,
+                             uint32_t n, uint32_t *res);
 // the same decoder on the host (vs_inflate_core.h with one lane): the status word
 uint32_t vs_inflate_member_host(const uint8_t *pay, uint32_t len, uint8_t *out, uint32_t isize, uint32_t crc);
 

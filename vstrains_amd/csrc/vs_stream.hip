@@ -35,6 +35,13 @@
 // the end of the window waits for the next chunk, which may start with '\n'), every multi-byte UTF-8 character becomes
 // one '?' (seq_chars), the bytes are checked with utf8_range_ok, and the text goes back to the device to be scanned
 // again.  Plain ASCII with LF line ends never passes through host parsing.
+//
+// A MEMBER RANGE (vs_fastq_stream_open_range; one process per GPU on two whole-BGZF files): the same stream on the bytes
+// [first member, one past the last member) of each file.  The reader seeks to the first and never reads at or beyond the
+// second; the device drops the lines in front that belong to the neighbour's record (skip_lines) and the stream ends
+// after the rank's pairs.  Which range that is follows from per-member line counts that the ranks made on their devices
+// and exchanged before (vs_bgzf_walk_file, vs_bgzf_count_lines, further down; the plan is vs_bgzf_shard_plan of
+// vs_inflate.hip).  A final line without a newline counts only where the range ends with the file.
 #include <errno.h>
 #include <fcntl.h>
 #include <poll.h>
@@ -291,6 +298,7 @@ struct Reader {
     bool gzip = false, bgzf = false, bgzf_device = true;
     size_t slot_cap = STREAM_CHUNK_BYTES;
     uint64_t raw_bytes = 0, text_bytes = 0, members_host = 0;
+    uint64_t begin = 0, end = ~0ull;  // the bytes of the file this reader may read (a member range of a sharded open)
     std::mutex m;
     std::condition_variable cv;
     std::thread th;
@@ -312,7 +320,9 @@ struct Reader {
             struct pollfd pfd = {fd, POLLIN, 0};
             const int pr = poll(&pfd, 1, 200);  // (a pipe whose writer is slow: look at `stop` now and then)
             if (pr == 0 || (pr < 0 && errno == EINTR)) continue;
-            const ssize_t got = read(fd, dst, std::min<size_t>(n, 1u << 30));
+            const uint64_t left = end - (begin + raw_bytes);  // (never a byte beyond the range, not even into a buffer)
+            if (left == 0) return 0;
+            const ssize_t got = read(fd, dst, (size_t)std::min<uint64_t>(std::min<size_t>(n, 1u << 30), left));
             if (got < 0 && errno == EINTR) continue;
             if (got < 0) {
                 fail(VS_E_ARG, "cannot read %s: %s", path.c_str(), strerror(errno));
@@ -324,6 +334,11 @@ struct Reader {
     }
     void run() {
         (void)hipSetDevice(device);
+        if (begin && lseek(fd, (off_t)begin, SEEK_SET) < 0) {
+            fail(VS_E_ARG, "cannot seek in %s: %s", path.c_str(), strerror(errno));
+            publish(0, true);
+            return;
+        }
         std::vector<uint8_t> in(1u << 20);
         size_t in_len = 0;
         bool in_eof = false;
@@ -539,6 +554,9 @@ struct DevFile {
     VsDevBuf comp, dir, mstat;  // bytes, vs_bgzf_member, uint32
     uint64_t members_dev = 0;  // members the device inflated so far
     uint32_t slot_base = 0;    // running index of the first member of the slot appended last
+    // a member range (vs_fastq_stream_open_range): lines still to drop from the front; whether the range ends where the file does
+    uint64_t skip = 0;
+    bool to_file_end = true;
 };
 
 }  // namespace
@@ -553,6 +571,8 @@ struct vs_fastq_stream {
     uint32_t *d_stat = nullptr, *h_stat = nullptr;  // ST_ALL words each, in the two buffers above
     VsDevBuf d_wcnt;  // uint32
     uint64_t pairs = 0;
+    uint64_t limit = ~0ull;  // pairs to deliver (a member range: the rank's own)
+    bool ranged = false;
     uint32_t flags_seen = 0;
     bool done = false;
     int failed = VS_OK;
@@ -594,7 +614,9 @@ int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
         d.last_byte = s->h_stat[f * ST_PER_FILE + ST_LAST];
         s->flags_seen |= d.flags;
         if (!d.flags) d.validated = d.size;
-        const uint64_t lines = (uint64_t)d.n_nl + ((d.eof && d.size && d.last_byte != '\n') ? 1u : 0u);
+        // (a final line without a newline counts -- at the end of the FILE: where a member range ends earlier, the bytes behind
+        // its last newline are the front of a line of the next rank)
+        const uint64_t lines = (uint64_t)d.n_nl + ((d.eof && d.to_file_end && d.size && d.last_byte != '\n') ? 1u : 0u);
         d.records = lines / 4u;
     }
     return VS_OK;
@@ -674,6 +696,7 @@ bool check_piece(DevFile &d, const uint8_t *p, size_t n, bool last) {
 }
 
 int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot &sl);
+bool zlib_accepts(const uint8_t *pay, const vs_bgzf_member &mb, int *code);
 bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl);
 
 // Both files to their ends (the reference reads them whole): every byte not yet checked is checked, a reader's failure is
@@ -781,25 +804,11 @@ int append_chunk(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot *&taken) {
     return append_slot(ctx, s, f, sl);
 }
 
-// After scan_windows: did the device reject a member of the slot of file f appended last?  Then zlib inflates that member
-// on the host and the file fails with zlib's code, in the words of the reader's zlib loop (true: the file has failed).
-bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
-    DevFile &d = s->df[f];
-    if (!sl.comp || s->h_stat[ST_BAD + f] == 0xFFFFFFFFu) return false;
-    const uint32_t idx = s->h_stat[ST_BAD + f] - d.slot_base;
-    char msg[700];
-    if (d.err != VS_OK) return true;
-    if (idx >= sl.n_members) {
-        d.err = VS_E_STATE;
-        d.err_msg = s->rd[f].path + ": the device reported a BGZF member that is not of the slot it inflated";
-        return true;
-    }
-    const vs_bgzf_member mb = ((const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()))[-(ptrdiff_t)(idx + 1u)];
-    uint32_t dev_status = 0;
-    (void)hipMemcpy(&dev_status, d.mstat.as<uint32_t>() + idx, sizeof dev_status, hipMemcpyDeviceToHost);
-    // the member as a plain gzip member: a 10-byte header, the payload, the trailer
-    std::vector<uint8_t> gz = {0x1f, 0x8b, 0x08, 0, 0, 0, 0, 0, 0, 0xff};
-    gz.insert(gz.end(), sl.buf.as<uint8_t>() + mb.in_off, sl.buf.as<uint8_t>() + mb.in_off + mb.in_len);
+// One BGZF member (its payload at pay) as a plain gzip member through zlib: true when zlib accepts it; else *code = what
+// the reader's zlib loop reports for such a stream (cut off, or bytes behind its end: Z_DATA_ERROR).
+bool zlib_accepts(const uint8_t *pay, const vs_bgzf_member &mb, int *code) {
+    std::vector<uint8_t> gz = {0x1f, 0x8b, 0x08, 0, 0, 0, 0, 0, 0, 0xff};  // a 10-byte header, the payload, the trailer
+    gz.insert(gz.end(), pay, pay + mb.in_len);
     for (uint32_t v : {mb.crc, mb.isize})
         for (int k = 0; k < 4; k++) gz.push_back((uint8_t)(v >> (8 * k)));
     std::vector<uint8_t> out(1u << 16);
@@ -816,14 +825,36 @@ bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
         } while (rc == Z_OK && (zs.avail_in != 0 || zs.avail_out == 0));
         const bool accepted = rc == Z_STREAM_END && zs.avail_in == 0;
         inflateEnd(&zs);
-        if (accepted) {
-            snprintf(msg, sizeof msg, "%s: BGZF member %llu was rejected on the device (status %u) but zlib accepts it", s->rd[f].path.c_str(),
-                     (unsigned long long)(d.slot_base + idx), dev_status);
-            d.err = VS_E_STATE;
-            d.err_msg = msg;
-            return true;
-        }
-        if (rc >= 0 || rc == Z_BUF_ERROR) rc = Z_DATA_ERROR;  // (cut off, or bytes behind its end: as the reader's zlib loop)
+        if (accepted) return true;
+        if (rc >= 0 || rc == Z_BUF_ERROR) rc = Z_DATA_ERROR;
+    }
+    *code = rc;
+    return false;
+}
+
+// After scan_windows: did the device reject a member of the slot of file f appended last?  Then zlib inflates that member
+// on the host and the file fails with zlib's code, in the words of the reader's zlib loop (true: the file has failed).
+bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
+    DevFile &d = s->df[f];
+    if (!sl.comp || s->h_stat[ST_BAD + f] == 0xFFFFFFFFu) return false;
+    const uint32_t idx = s->h_stat[ST_BAD + f] - d.slot_base;
+    char msg[700];
+    if (d.err != VS_OK) return true;
+    if (idx >= sl.n_members) {
+        d.err = VS_E_STATE;
+        d.err_msg = s->rd[f].path + ": the device reported a BGZF member that is not of the slot it inflated";
+        return true;
+    }
+    const vs_bgzf_member mb = ((const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()))[-(ptrdiff_t)(idx + 1u)];
+    uint32_t dev_status = 0;
+    (void)hipMemcpy(&dev_status, d.mstat.as<uint32_t>() + idx, sizeof dev_status, hipMemcpyDeviceToHost);
+    int rc = Z_DATA_ERROR;
+    if (zlib_accepts(sl.buf.as<uint8_t>() + mb.in_off, mb, &rc)) {
+        snprintf(msg, sizeof msg, "%s: BGZF member %llu was rejected on the device (status %u) but zlib accepts it", s->rd[f].path.c_str(),
+                 (unsigned long long)(d.slot_base + idx), dev_status);
+        d.err = VS_E_STATE;
+        d.err_msg = msg;
+        return true;
     }
     snprintf(msg, sizeof msg, "%s: not a complete gzip stream (zlib code %d)", s->rd[f].path.c_str(), rc);
     d.err = VS_E_ARG;
@@ -846,12 +877,26 @@ int drop_front(vs_ctx *ctx, vs_fastq_stream *s, int f, size_t cut, uint64_t reco
     return VS_OK;
 }
 
-}  // namespace
+// A member range starts inside a record of the rank before: after scan_windows, the first d.skip lines of the window of
+// file f go (its line ends scattered once, the offset of the last one to drop read back).  They all end in the range's
+// first member -- that is how the plan picks it -- and a slot holds whole members, so the first window has them.
+int skip_lines(vs_ctx *ctx, vs_fastq_stream *s, int f) {
+    DevFile &d = s->df[f];
+    if (d.n_nl < d.skip) return vs_fail(ctx, VS_E_STATE, "%s: fewer lines at the front of its member range than were counted", s->rd[f].path.c_str());
+    if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return rc;
+    const uint64_t words = (d.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
+    hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, s->st, d.win[d.cur].as<const uint8_t>(), (uint64_t)d.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
+    VS_HIP(ctx, hipGetLastError());
+    uint32_t at = 0;
+    VS_HIP(ctx, hipMemcpyAsync(&at, d.ends.as<uint32_t>() + (d.skip - 1u), sizeof at, hipMemcpyDeviceToHost, s->st));
+    VS_HIP(ctx, hipStreamSynchronize(s->st));
+    if ((size_t)at + 1u > d.size) return vs_fail(ctx, VS_E_STATE, "%s: a line end beyond the window", s->rd[f].path.c_str());
+    d.skip = 0;
+    return drop_front(ctx, s, f, (size_t)at + 1u, 0);
+}
 
-extern "C" {
-
-int vs_fastq_stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, vs_fastq_stream **out) {
-    if (!ctx || !fwd_path || !rve_path || !out) return vs_fail(ctx, VS_E_ARG, "vs_fastq_stream_open: bad argument");
+// both files opened and their readers started; range (may be NULL) = per file {first byte, one past the last byte, lines to skip}
+int stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, const uint64_t *range, uint64_t n_pairs, vs_fastq_stream **out) {
     *out = nullptr;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     size_t chunk = STREAM_CHUNK_BYTES;
@@ -866,12 +911,29 @@ int vs_fastq_stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path
         r.device = ctx->device;
         if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
         r.fd = open(paths[f], O_RDONLY);
+        int e = errno;
+        struct stat sb;
+        if (r.fd >= 0 && range && (fstat(r.fd, &sb) != 0 || !S_ISREG(sb.st_mode) || range[3 * f] > range[3 * f + 1] || range[3 * f + 1] > (uint64_t)sb.st_size)) {
+            close(r.fd);
+            r.fd = -1;
+            e = EINVAL;  // (a member range is a range of a regular file that holds it)
+        }
         if (r.fd < 0) {
-            const int e = errno;
             for (int g = 0; g < f; g++) close(s->rd[g].fd);
+            for (int g = 0; g < 2; g++) s->rd[g].fd = -1;
             delete s;
             return vs_fail(ctx, VS_E_ARG, "cannot open %s: %s", paths[f], strerror(e));
         }
+        if (range) {
+            r.begin = range[3 * f];
+            r.end = range[3 * f + 1];
+            s->df[f].skip = range[3 * f + 2];
+            s->df[f].to_file_end = r.end == (uint64_t)sb.st_size;
+        }
+    }
+    if (range) {
+        s->ranged = true;
+        s->limit = n_pairs;
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
     if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * ST_ALL);
@@ -888,6 +950,21 @@ int vs_fastq_stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path
     return VS_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int vs_fastq_stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, vs_fastq_stream **out) {
+    if (!ctx || !fwd_path || !rve_path || !out) return vs_fail(ctx, VS_E_ARG, "vs_fastq_stream_open: bad argument");
+    return stream_open(ctx, fwd_path, rve_path, nullptr, 0, out);
+}
+
+int vs_fastq_stream_open_range(vs_ctx *ctx, const char *fwd_path, const char *rve_path, const uint64_t range[6], uint64_t n_pairs,
+                               vs_fastq_stream **out) {
+    if (!ctx || !fwd_path || !rve_path || !range || !out) return vs_fail(ctx, VS_E_ARG, "vs_fastq_stream_open_range: bad argument");
+    return stream_open(ctx, fwd_path, rve_path, range, n_pairs, out);
+}
+
 int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs_reads **out, uint64_t *n_pairs) {
     if (!ctx || !s || !out || !n_pairs) return vs_fail(ctx, VS_E_ARG, "vs_fastq_stream_next: bad argument");
     *out = nullptr;
@@ -896,6 +973,8 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     if (s->done) return VS_OK;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     if (!max_pairs || max_pairs > (1ull << 30)) max_pairs = 1ull << 30;
+    if (s->pairs >= s->limit) return finish(ctx, s);  // (a member range: the rank's pairs are out)
+    max_pairs = std::min<uint64_t>(max_pairs, s->limit - s->pairs);
     uint64_t n = 0;
     for (int round = 0;; round++) {
         // more text for the file that holds fewer complete records (both at the start): a window holds what is left of the
@@ -928,6 +1007,18 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
         for (int f = 0; f < 2; f++)
             if (taken[f]) s->rd[f].give_back();  // (the stream is synchronised: the upload is done)
         if (rejected) return finish(ctx, s);
+        if (s->ranged) {
+            // (pass 1 of the sharded open saw neither a '\r' nor a byte >= 0x80 in the whole file, and the plan rests on that)
+            if (s->df[0].flags | s->df[1].flags)
+                return stream_fail(ctx, s, VS_E_STATE, s->rd[s->df[0].flags ? 0 : 1].path + " changed after its lines were counted");
+            bool skipped = false;
+            for (int f = 0; f < 2; f++) {
+                if (!s->df[f].skip || !taken[f]) continue;  // (the first window of the file; it may arrive a round after the other's)
+                if ((rc = skip_lines(ctx, s, f))) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+                skipped = true;
+            }
+            if (skipped && (rc = scan_windows(ctx, s))) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+        }
         bool again = false;
         for (int f = 0; f < 2; f++) {
             DevFile &d = s->df[f];
@@ -1061,6 +1152,161 @@ int vs_fastq_stream_inflate_info(const vs_fastq_stream *s, uint64_t info[4]) {
     for (int f = 0; f < 2; f++) {
         info[2 * f + 0] = s->df[f].members_dev;
         info[2 * f + 1] = s->rd[f].members_host;
+    }
+    return VS_OK;
+}
+
+// ---- the member-sharded open of a BGZF pair (one process per GPU), pass 1 ------------------------------------------------
+// The header hop: only the header (and the 8-byte trailer, for ISIZE) of every member is read, never a payload.
+int vs_bgzf_walk_file(const char *path, uint64_t *offsets, uint64_t cap, uint64_t info[4]) {
+    if (!path || !info || (!offsets && cap)) return vs_fail(nullptr, VS_E_ARG, "vs_bgzf_walk_file: bad argument");
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return vs_fail(nullptr, VS_E_ARG, "cannot open %s: %s", path, strerror(errno));
+    struct stat sb;
+    if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        close(fd);
+        return vs_fail(nullptr, VS_E_ARG, "%s is not a regular file", path);
+    }
+    const uint64_t size = (uint64_t)sb.st_size;
+    std::vector<uint8_t> head(12u + 65535u);
+    uint64_t at = 0, count = 0;
+    int state = 0;
+    while (at < size) {
+        size_t have = 0, hsize = 0, msize = 0;
+        for (size_t want = 64;;) {  // (bgzip's header is 18 bytes; a longer extra field is read to its end, 12 + XLEN, and no further)
+            want = (size_t)std::min<uint64_t>(want, size - at);
+            while (have < want) {
+                const ssize_t got = pread(fd, head.data() + have, want - have, (off_t)(at + have));
+                if (got < 0 && errno == EINTR) continue;
+                if (got <= 0) {
+                    const int e = errno;
+                    close(fd);
+                    return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, got < 0 ? strerror(e) : "it shrank while it was read");
+                }
+                have += (size_t)got;
+            }
+            state = vs_bgzf_header(head.data(), have, &hsize, &msize);
+            const size_t whole = have >= 12 ? 12u + ((size_t)head[10] | ((size_t)head[11] << 8)) : 12u;
+            if (state != 1 || whole <= have || at + have == size) break;
+            want = whole;
+        }
+        if (state == 0 && at + msize > size) state = 1;  // cut off by the end of the file
+        if (state == 0) {
+            uint8_t t[4];
+            ssize_t got;
+            do got = pread(fd, t, 4, (off_t)(at + msize - 4));
+            while (got < 0 && errno == EINTR);
+            if (got != 4) {
+                const int e = errno;
+                close(fd);
+                return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, got < 0 ? strerror(e) : "it shrank while it was read");
+            }
+            const uint32_t isize = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+            if (isize > 65536u) state = 2;
+        }
+        if (state) break;
+        if (count < cap) offsets[count] = at;
+        count++;
+        at += msize;
+    }
+    close(fd);
+    if (count < cap) offsets[count] = at;  // (one past the last member)
+    info[0] = count;
+    info[1] = at;
+    info[2] = (uint64_t)state;
+    info[3] = size;
+    return VS_OK;
+}
+
+int vs_bgzf_count_lines(vs_ctx *ctx, const char *path, const uint64_t *offsets, uint64_t n, uint32_t *counts, uint64_t info[4]) {
+    if (!ctx || !path || !info || (n && (!offsets || !counts))) return vs_fail(ctx, VS_E_ARG, "vs_bgzf_count_lines: bad argument");
+    info[0] = info[2] = info[3] = 0;
+    info[1] = 256;
+    if (!n) return VS_OK;
+    for (uint64_t i = 0; i < n; i++)
+        if (offsets[i + 1] <= offsets[i] || offsets[i + 1] - offsets[i] > 65536u) return vs_fail(ctx, VS_E_ARG, "vs_bgzf_count_lines: member %llu is no BGZF member's size", (unsigned long long)i);
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    constexpr size_t BATCH = 32u << 20;  // compressed bytes per launch; two pinned buffers of it, one device copy
+    struct FdGuard {
+        int fd;
+        ~FdGuard() { if (fd >= 0) close(fd); }
+    } file = {open(path, O_RDONLY)};
+    if (file.fd < 0) return vs_fail(ctx, VS_E_ARG, "cannot open %s: %s", path, strerror(errno));
+    hipStream_t st = ctx->stream;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max(ctx->n_cu, 1) * 8u);
+    VsPinnedBuf pin[2];
+    VsDevBuf d_comp, d_dir, d_res, d_scratch;
+    VS_HIP(ctx, d_comp.reserve(BATCH + 16u));
+    VS_HIP(ctx, d_scratch.reserve((size_t)grid * 65536u));
+    std::vector<vs_bgzf_member> dir[2];
+    VsPinnedBuf pin_dir[2], pin_res[2];  // (pinned, so that neither copy makes the host wait for the kernel before it)
+    uint64_t first[2] = {0, 0}, next = 0;
+    struct SyncGuard {  // (no return while the device may still read or write this call's buffers)
+        hipStream_t st;
+        ~SyncGuard() { (void)hipStreamSynchronize(st); }
+    } drain = {st};
+    for (int k = 0; next < n || !dir[k ^ 1].empty(); k ^= 1) {
+        dir[k].clear();
+        size_t bytes = 0;
+        if (next < n) {  // read and parse batch k while the device still works on the one before
+            uint64_t upto = next;
+            while (upto < n && offsets[upto + 1] - offsets[next] <= BATCH) upto++;
+            bytes = (size_t)(offsets[upto] - offsets[next]);
+            VS_HIP(ctx, pin[k].reserve(BATCH));
+            uint8_t *buf = pin[k].as<uint8_t>();
+            for (size_t have = 0; have < bytes;) {
+                const ssize_t got = pread(file.fd, buf + have, bytes - have, (off_t)(offsets[next] + have));
+                if (got < 0 && errno == EINTR) continue;
+                if (got <= 0) return vs_fail(ctx, VS_E_ARG, "cannot read %s: %s", path, got < 0 ? strerror(errno) : "it shrank while it was read");
+                have += (size_t)got;
+            }
+            for (uint64_t i = next; i < upto; i++) {
+                vs_bgzf_member mb;
+                size_t msize = 0;
+                const size_t rel = (size_t)(offsets[i] - offsets[next]);
+                if (vs_bgzf_parse(buf + rel, (size_t)(offsets[i + 1] - offsets[i]), &mb, &msize) != 0 || msize != offsets[i + 1] - offsets[i])
+                    return vs_fail(ctx, VS_E_STATE, "%s: no BGZF member of %llu bytes at byte %llu (the file changed after it was walked?)", path,
+                                   (unsigned long long)(offsets[i + 1] - offsets[i]), (unsigned long long)offsets[i]);
+                mb.in_off += (uint32_t)rel;
+                dir[k].push_back(mb);
+            }
+            first[k] = next;
+            next = upto;
+            info[3] += bytes;
+        }
+        const int o = k ^ 1;
+        if (!dir[o].empty()) {  // the batch before: its results
+            VS_HIP(ctx, hipStreamSynchronize(st));
+            for (size_t i = 0; i < dir[o].size(); i++) {
+                const uint32_t *r = pin_res[o].as<uint32_t>() + 4u * i;
+                if (r[0] != 0) {  // worded as the streamed ingest words a member its device rejected (member_failed)
+                    int rc = Z_DATA_ERROR;
+                    if (zlib_accepts(pin[o].as<uint8_t>() + dir[o][i].in_off, dir[o][i], &rc))
+                        return vs_fail(ctx, VS_E_STATE, "%s: BGZF member %llu was rejected on the device (status %u) but zlib accepts it", path,
+                                       (unsigned long long)(first[o] + i), r[0]);
+                    return vs_fail(ctx, VS_E_ARG, "%s: not a complete gzip stream (zlib code %d)", path, rc);
+                }
+                counts[first[o] + i] = r[1];
+                info[0] |= r[2];
+                if (dir[o][i].isize) info[1] = r[3] & 255u;
+            }
+            info[2] += dir[o].size();
+            dir[o].clear();
+        }
+        if (!dir[k].empty()) {
+            const size_t nm = dir[k].size();
+            VS_HIP(ctx, pin_dir[k].reserve(sizeof(vs_bgzf_member) * nm, sizeof(vs_bgzf_member) * (nm + nm / 4 + 64)));
+            VS_HIP(ctx, pin_res[k].reserve(sizeof(uint32_t) * 4u * nm, sizeof(uint32_t) * 4u * (nm + nm / 4 + 64)));
+            memcpy(pin_dir[k].ptr(), dir[k].data(), sizeof(vs_bgzf_member) * nm);
+            if (int rc = reserve_n<vs_bgzf_member>(ctx, d_dir, nm)) return rc;
+            if (int rc = reserve_n<uint32_t>(ctx, d_res, 4u * nm)) return rc;
+            VS_HIP(ctx, hipMemcpyAsync(d_comp.as<uint8_t>(), pin[k].as<uint8_t>(), bytes, hipMemcpyHostToDevice, st));
+            VS_HIP(ctx, hipMemcpyAsync(d_dir.as<vs_bgzf_member>(), pin_dir[k].ptr(), sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, st));
+            VS_HIP(ctx, hipMemsetAsync(d_res.as<uint32_t>(), 0xFF, sizeof(uint32_t) * 4u * nm, st));
+            vs_launch_inflate_count(st, d_comp.as<uint8_t>(), bytes, d_scratch.as<uint8_t>(), grid, d_dir.as<vs_bgzf_member>(), (uint32_t)nm, d_res.as<uint32_t>());
+            VS_HIP(ctx, hipGetLastError());
+            VS_HIP(ctx, hipMemcpyAsync(pin_res[k].ptr(), d_res.as<uint32_t>(), sizeof(uint32_t) * 4u * nm, hipMemcpyDeviceToHost, st));
+        }
     }
     return VS_OK;
 }

@@ -239,6 +239,139 @@ class FastqStream:
             raise nat.NativeError(rc, msg)
         self._h = h
 
+    # ---- the member-sharded open of a BGZF pair (one process per GPU) ------------------------------------------------------
+    @classmethod
+    def open_shard(cls, fwd: str, rve: str, ctx: "Context", rank: int, world: int, all_gather=None, block_pairs: int = 1 << 20):
+        """This rank's contiguous block of the pairs of two whole-BGZF files, shared with the other ranks by MEMBER and
+        inflated on the devices only: pass 1 (``shard_count``) walks the member headers of both files and counts, on the
+        device, the lines of this rank's share of the members; one exchange (``all_gather``: a callable that takes this
+        rank's list of integers and returns every rank's, rank order -- the lists may differ in length; default
+        ``torch.distributed.all_gather_object``); pass 2 (``shard_open``) opens the stream on the member range of this
+        rank's records and exchanges one more integer, the status of that open.  A rank inflates its share twice -- the
+        text of pass 1 is not kept, which is what keeps its device memory independent of the file.
+
+        Returns ``(stream, None)``, or ``(None, reason)`` when the ranks -- all of them, the decision is a function of the
+        gathered values alone -- must take ``FastqPair.open_shard`` instead: a file that is not whole BGZF, or a ``\\r`` or a
+        byte >= 0x80 anywhere (universal newlines and the UTF-8 check of the whole file are the host ingest's).  The
+        stream has ``first`` / ``total_pairs`` / ``shard_pairs`` (where its block lies), ``members`` (per file),
+        ``members_pass1`` and ``plan`` (per file: first member, lines skipped, one past the last member)."""
+        if all_gather is None:
+            import torch.distributed as dist
+
+            def all_gather(vals):
+                got = [None] * world
+                dist.all_gather_object(got, [int(v) for v in vals])
+                return got
+
+        mine = cls.shard_count(fwd, rve, ctx, rank, world)
+        everyone = all_gather(mine.message)
+        return cls.shard_open(mine, everyone, all_gather, block_pairs)
+
+    class ShardCount:
+        """What pass 1 leaves on a rank: ``message`` for the exchange, its own failure (raised after the exchange), the
+        members' file offsets of both walks, how many members it inflated per file."""
+
+        def __init__(self, fwd, rve, ctx, rank, world):
+            self.paths, self.ctx, self.rank, self.world = (fwd, rve), ctx, rank, world
+            self.failure, self.offsets, self.states, self.members_pass1 = None, [None, None], [2, 2], [0, 0]
+            self.message = [1]
+
+    @classmethod
+    def shard_count(cls, fwd: str, rve: str, ctx: "Context", rank: int, world: int) -> "FastqStream.ShardCount":
+        """Pass 1 on this rank.  ``message`` = [failed] + per file [whole BGZF, members M, flags of my share (1: a
+        ``\\r``, 2: a byte >= 0x80), last byte of the last non-empty member of my share (256: none), members in my share,
+        their newline counts padded with zeros to ceil(M / world)].  No share is counted when either file is not whole
+        BGZF (every rank sees that in its own walk, and says so in the message)."""
+        L = nat.lib()
+        sc = cls.ShardCount(fwd, rve, ctx, rank, world)
+        try:
+            for i, path in enumerate(sc.paths):
+                sc.offsets[i], sc.states[i], _ = bgzf_walk_file(path)
+            whole = all(st == 0 for st in sc.states)
+            msg = [0]
+            for i, path in enumerate(sc.paths):
+                m = len(sc.offsets[i]) - 1
+                lo, hi = (m * rank) // world, (m * (rank + 1)) // world
+                counts = np.zeros(max(hi - lo, 1), dtype=np.uint32)
+                info = (C.c_uint64 * 4)(0, 256, 0, 0)
+                if whole and hi > lo:
+                    off = np.ascontiguousarray(sc.offsets[i][lo:hi + 1])
+                    rc = L.vs_bgzf_count_lines(ctx._h, path.encode(), off.ctypes.data, hi - lo, counts.ctypes.data, info)
+                    if rc != nat.VS_OK:
+                        FastqPair._raise(ctx._h, rc)
+                    sc.members_pass1[i] = int(info[2])
+                share = [int(x) for x in counts[: hi - lo]] if whole else []
+                msg += [1 if sc.states[i] == 0 else 0, m, int(info[0]), int(info[1]), len(share)]
+                msg += share + [0] * (-(-m // world) - len(share))
+            sc.message = msg
+        except Exception as e:  # noqa: BLE001 (the peers hear of it through the message, then this rank raises it)
+            sc.failure = e
+            sc.message = [1]
+        return sc
+
+    @classmethod
+    def shard_open(cls, mine: "FastqStream.ShardCount", everyone, all_gather, block_pairs: int = 1 << 20):
+        """Pass 2 on this rank from every rank's pass-1 message; see ``open_shard`` for what comes back."""
+        from .dist import shard_range
+
+        rank, world, ctx = mine.rank, mine.world, mine.ctx
+        if mine.failure is not None:
+            raise mine.failure
+        failed = [r for r, vals in enumerate(everyone) if vals[0]]
+        if failed:
+            raise RuntimeError("FASTQ open failed on rank(s) %s" % failed)
+        # every rank's shares, file by file (all that follows is a function of `everyone`: no rank can take another branch)
+        whole, members, flags, last_byte, counts = [], [], 0, [256, 256], [[], []]
+        at = [1] * len(everyone)
+        for i in range(2):
+            heads = {(vals[at[r]], vals[at[r] + 1]) for r, vals in enumerate(everyone)}
+            if len(heads) != 1:
+                raise RuntimeError("the ranks do not see the same file %s: (whole BGZF, members) = %s" % (mine.paths[i], sorted(heads)))
+            (w, m), = heads
+            whole.append(bool(w))
+            members.append(m)
+            for r, vals in enumerate(everyone):
+                fl, lb, n = vals[at[r] + 2: at[r] + 5]
+                flags |= fl
+                if lb != 256:
+                    last_byte[i] = lb
+                counts[i] += vals[at[r] + 5: at[r] + 5 + n]
+                at[r] += 5 + -(-m // world)
+        if not all(whole):
+            return None, "not whole BGZF"
+        if flags & 3:
+            return None, "a carriage return or a byte >= 0x80"
+        if [len(c) for c in counts] != members:
+            raise RuntimeError("the ranks' shares do not add up to the members of %s / %s" % mine.paths)
+        counts = [np.asarray(c, dtype=np.uint32) for c in counts]
+        open_end = [lb not in (256, 10) for lb in last_byte]
+        lines = [int(counts[i].sum(dtype=np.uint64)) + (1 if open_end[i] else 0) for i in range(2)]
+        total = min(lines[0] // 4, lines[1] // 4)  # PE_Inference.py:154
+        first, last = shard_range(total, rank, world)
+        plan = [bgzf_shard_plan(counts[i], open_end[i], first, last) for i in range(2)]
+        rng = (C.c_uint64 * 6)()
+        for i, (a, skip, e) in enumerate(plan):
+            rng[3 * i], rng[3 * i + 1], rng[3 * i + 2] = int(mine.offsets[i][a]), int(mine.offsets[i][e]), skip
+        self = cls.__new__(cls)
+        self._ctx, self._h, self.block_pairs = ctx, None, block_pairs
+        h = C.c_void_p()
+        rc = nat.lib().vs_fastq_stream_open_range(ctx._h, mine.paths[0].encode(), mine.paths[1].encode(), rng, last - first, C.byref(h))
+        err = None
+        if rc != nat.VS_OK:
+            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+            err = FileNotFoundError(msg) if "cannot open" in msg else nat.NativeError(rc, msg)
+        status = all_gather([0 if err is None else 1])
+        if err is not None:
+            raise err
+        failed = [r for r, vals in enumerate(status) if vals[0]]
+        if failed:
+            nat.lib().vs_fastq_stream_close(h)
+            raise RuntimeError("FASTQ open failed on rank(s) %s" % failed)
+        self._h = h
+        self.first, self.total_pairs, self.shard_pairs, self.lines = first, total, last - first, tuple(lines)
+        self.members, self.members_pass1, self.plan = tuple(members), tuple(mine.members_pass1), plan
+        return self, None
+
     @property
     def info(self):
         a = (C.c_uint64 * 4)()
@@ -297,6 +430,58 @@ def bgzf_walk(data: bytes):
     mem = np.zeros((max(int(info[0]), 1), 4), dtype=np.uint64)
     nat.lib().vs_bgzf_walk(buf.ctypes.data, len(data), mem.ctypes.data, int(info[0]), info)
     return [tuple(int(x) for x in row) for row in mem[: int(info[0])]], int(info[1]), int(info[2])
+
+
+def bgzf_walk_file(path: str):
+    """The header hop over a regular file (``vs_bgzf_walk_file``, host only, no payload read): (the members' file offsets
+    and one past the last as uint64[M + 1], what follows the last member: 0 nothing, 1 a cut-off member, 2 not BGZF, the
+    file's size)."""
+    info = (C.c_uint64 * 4)()
+    cap = os.path.getsize(path) // 4096 + 1024 if os.path.isfile(path) else 1
+    while True:
+        off = np.zeros(cap + 1, dtype=np.uint64)
+        rc = nat.lib().vs_bgzf_walk_file(path.encode(), off.ctypes.data, cap + 1, info)
+        if rc != nat.VS_OK:
+            msg = nat.lib().vs_last_error(None).decode("utf-8", "replace")
+            raise FileNotFoundError(msg) if "cannot open" in msg else nat.NativeError(rc, msg)
+        if int(info[0]) <= cap:
+            return off[: int(info[0]) + 1].copy(), int(info[2]), int(info[3])
+        cap = int(info[0])
+
+
+def inflate_count_host(payload: bytes, isize: int, crc: int):
+    """One raw deflate payload through the host form of the counting kernel (``vs_inflate_count_host``): (status word,
+    newlines, flags -- 1: a ``\\r``, 2: a byte >= 0x80 --, last byte)."""
+    src = np.frombuffer(payload or b"\0", dtype=np.uint8)
+    res = (C.c_uint32 * 4)()
+    rc = nat.lib().vs_inflate_count_host(src.ctypes.data, len(payload), isize, crc & 0xFFFFFFFF, res)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_inflate_count_host")
+    return tuple(int(x) for x in res)
+
+
+def bgzf_count_lines(path: str, offsets, ctx: "Context"):
+    """The members at ``offsets`` (M + 1 file offsets) counted on the device (``vs_bgzf_count_lines``): (newlines per
+    member, flags, last byte of the last non-empty member or 256, members inflated, file bytes read)."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(off) - 1
+    counts = np.zeros(max(n, 1), dtype=np.uint32)
+    info = (C.c_uint64 * 4)()
+    rc = nat.lib().vs_bgzf_count_lines(ctx._h, path.encode(), off.ctypes.data, n, counts.ctypes.data, info)
+    if rc != nat.VS_OK:
+        FastqPair._raise(ctx._h, rc)
+    return counts[:n], int(info[0]), int(info[1]), int(info[2]), int(info[3])
+
+
+def bgzf_shard_plan(counts, no_final_newline: bool, first: int, last: int):
+    """``vs_bgzf_shard_plan`` (a pure function of the host): for the records [first, last) of a file with these newline
+    counts per member, (the first member to open, the lines to skip in front of it, one past the last member needed)."""
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    plan = (C.c_uint64 * 3)()
+    rc = nat.lib().vs_bgzf_shard_plan(c.ctypes.data if c.size else None, c.size, 1 if no_final_newline else 0, first, last, plan)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    return int(plan[0]), int(plan[1]), int(plan[2])
 
 
 def inflate_host(payload: bytes, isize: int, crc: int):

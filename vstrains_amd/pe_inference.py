@@ -47,10 +47,28 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     if rank == 0 and stages_follow:
         counter.reserve_link_table()  # (the graph stages run on this rank: their table's buffer is taken now)
     if world > 1:
-        # nobody reads a whole file: every rank counts the lines of its byte range, the ranks exchange the counts and
-        # each indexes only the bytes of its own records (:154's total follows from the counts)
-        fq = host.FastqPair.open_shard(fwd, rve, ctx, rank, world)
-        count_fastq(ctx, fq, counter, fq.block_offset, fq.block_offset + len(fq), progress=(rank == 0))
+        # two whole-BGZF files: the ranks share them by member, count lines and inflate on their devices only, and each
+        # streams its own records (FastqStream.open_shard); why == the reason when that is not what happens
+        fq, why = None, member_shard_refusal(fwd, rve)
+        if why is None:
+            fq, why = host.FastqStream.open_shard(fwd, rve, ctx, rank, world, block_pairs=BATCH_PAIRS)
+        if fq is not None:
+            try:
+                count_stream(ctx, fq, counter, progress=(rank == 0))  # (:156-157 for rank 0's own block, as below)
+                info = fq.info
+            finally:
+                fq.close()
+            if info["pairs"] != fq.shard_pairs:
+                raise RuntimeError("%s / %s: %d pairs in the member range of rank %d where %d were counted (did a file change?)"
+                                   % (fwd, rve, info["pairs"], rank, fq.shard_pairs))
+            ingest_report(rank, world, "bgzf_members", None, fq.first, info["pairs"], fq.members, fq.members_pass1, info["members_device"])
+        else:
+            # nobody reads a whole plain file: every rank counts the lines of its byte range, the ranks exchange the counts
+            # and each indexes only the bytes of its own records (:154's total follows from the counts); gzip files and
+            # files with carriage returns are opened whole by every rank
+            fq = host.FastqPair.open_shard(fwd, rve, ctx, rank, world)
+            count_fastq(ctx, fq, counter, fq.block_offset, fq.block_offset + len(fq), progress=(rank == 0))
+            ingest_report(rank, world, "whole_files" if fq.whole else "byte_ranges", why, fq.first, len(fq), None, (0, 0), (0, 0))
     elif streamed:
         fq = host.FastqStream(fwd, rve, ctx, block_pairs=BATCH_PAIRS)  # :146-154 from any readable file, read once
         try:
@@ -92,6 +110,34 @@ def _starts_bgzf(path: str) -> bool:
             return True
         at += 4 + slen
     return False
+
+
+def member_shard_refusal(fwd: str, rve: str):
+    """None when a sharded run tries the member-sharded open (both inputs regular files that start with a BGZF member, and
+    neither ``VS_FASTQ_STREAM=0`` nor ``VS_BGZF_DEVICE=0`` -- the switches that give the mapped open and host zlib in
+    one process), else the reason it does not; the same on every rank, which all see the same files and environment."""
+    if os.environ.get("VS_FASTQ_STREAM") == "0":
+        return "VS_FASTQ_STREAM=0"
+    if os.environ.get("VS_BGZF_DEVICE") == "0":
+        return "VS_BGZF_DEVICE=0"
+    if not (_starts_bgzf(fwd) and _starts_bgzf(rve)):
+        return "the inputs are not both BGZF"
+    return None
+
+
+def ingest_report(rank, world, path, reason, first_pair, pairs, members, members_pass1, members_pass2):
+    """Which ingest a rank of a sharded run took, for whoever asks with ``VS_INGEST_REPORT=DIR`` (stdout stays the
+    reference's): ``DIR/ingest_rank<r>.json``."""
+    d = os.environ.get("VS_INGEST_REPORT")
+    if not d:
+        return
+    import json
+
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, "ingest_rank%d.json" % rank), "w") as fh:
+        json.dump(dict(rank=rank, world=world, path=path, reason=reason, first_pair=int(first_pair), pairs=int(pairs),
+                       members=None if members is None else [int(x) for x in members],
+                       members_pass1=[int(x) for x in members_pass1], members_pass2=[int(x) for x in members_pass2]), fh)
 
 
 def use_stream(fwd: str, rve: str) -> bool:
