@@ -245,6 +245,47 @@ int vs_fastq_stream_open_range(vs_ctx *ctx, const char *fwd_path, const char *rv
 int vs_write_matrix_text(vs_ctx *ctx, const char *path, const uint8_t *ids, const uint64_t *id_off,
                          uint32_t n, const int64_t *mat);
 
+/* Sparse pe_info / st_info (additions to ABI 10): the dense file above with every line removed whose count is 0, the other
+ * lines in their order (row-major in the caller's node order, ids written as the dense writer writes them).  A matrix of
+ * zeros gives a file of 0 bytes; no empty line is ever written (the reference stops reading at one).  The reference reads
+ * such a file to the same dict as the dense one: process_pe_info (utils/VStrains_IO.py:598-623) sets every key to 0 before
+ * it adds the lines.
+ *   vs_write_info_sparse      : formatted ON THE DEVICE from the counters where they lie -- no permuted copy, no download of
+ *                               a matrix, no sort.  d_counts: DEVICE n*n uint32 cells in the index's internal numbering (may
+ *                               be NULL); d_wide: DEVICE n*n int64 totals (vs_counts_fold; may be NULL; one of the two must
+ *                               be given); a cell's total is the sum of both.  d_tile_map: DEVICE T*T bytes, T = ceil(n / 64),
+ *                               THIS matrix's half of the dirty-tile map of vs_pe_count_tracked, or NULL: a cell of d_counts
+ *                               in an unmarked tile is taken as 0 without being read (d_wide is always read).  rank: HOST,
+ *                               rank[i] = internal number of the caller's node i (NULL = the same numbering).  The value of
+ *                               the caller's cell (i, j), with a = rank[i], b = rank[j]:
+ *                                 upper == 0 (node_mat)  M[a][b]
+ *                                 upper == 1 (short_mat) 0 for i > j, S[a][a] for i == j, S[a][b] + S[b][a] otherwise
+ *                               A negative total is VS_E_ARG.  Two passes (k_info_row_sizes: lines and bytes per row;
+ *                               k_info_format: the text of a block of whole rows of at most 256 MB, VS_TEXT_BLOCK as in
+ *                               vs_write_matrix_text), two device / pinned buffer pairs: block k + 1 is formatted while
+ *                               block k is written.  info (may be NULL): [0] lines, [1] bytes, [2] blocks written,
+ *                               [3] counter cells read (a cell skipped through the tile map is not).
+ *   vs_write_info_sparse_host : the host twin.  The same arguments as HOST pointers, ctx may be NULL, one thread; it runs the
+ *                               text the kernels run (csrc/vs_info_core.h) and writes the same bytes. */
+int vs_write_info_sparse(vs_ctx *ctx, const char *path, const uint8_t *ids, const uint64_t *id_off, uint32_t n,
+                         const uint32_t *d_counts, const int64_t *d_wide, const uint8_t *d_tile_map, const uint32_t *rank,
+                         int upper, uint64_t info[4]);
+int vs_write_info_sparse_host(vs_ctx *ctx, const char *path, const uint8_t *ids, const uint64_t *id_off, uint32_t n,
+                              const uint32_t *counts, const int64_t *wide, const uint8_t *tile_map, const uint32_t *rank,
+                              int upper, uint64_t info[4]);
+
+/* (addition to ABI 10) A pe_info / st_info file, dense or sparse, parsed on the host threads into cells against a name list:
+ * the lines up to the first empty one; each line minus its LAST CHARACTER (the newline, or a real character on a final line
+ * without one) split at ':', the first three fields taken (IO.py:603-612); a line naming an id that is not among the n names
+ * (concatenated in `names`, name_off[n + 1]) is skipped.  Fewer than three fields, or a count that is not an optionally
+ * signed decimal integer that fits int64, is VS_E_ARG (vs_last_error(NULL) quotes the line).  rows / cols / vals receive
+ * up to cap cells in file order; with cap == 0 nothing is parsed and info[0] is the number of lines, an upper bound on the
+ * cells.  info[0] = cells, [1] = flags: bit 0 the file holds a '\r', bit 1 a byte >= 0x80 -- such a file is NOT parsed here
+ * (universal newlines and the text decoding belong to Python: the caller keeps its own loop), [2] = lines read,
+ * [3] = lines skipped for an unknown id. */
+int vs_info_parse(const char *path, const uint8_t *names, const uint64_t *name_off, uint32_t n, uint32_t *rows, uint32_t *cols,
+                  int64_t *vals, uint64_t cap, uint64_t info[4]);
+
 /* Synthetic pairs generated on the device from a seed (bench workload; the CPU twin is
  * oracle/pe_oracle.c:peo_synth_pairs).  genomes: concatenated ACGT ASCII (host), goff
  * [n_strains+1]; cum[s]: inclusive upper bound of strain s in a uniform u32 draw (last =
@@ -358,6 +399,14 @@ int vs_links_from_wide(vs_ctx *ctx, const int64_t *d_node_mat, const int64_t *d_
 /* Same from HOST int64 matrices (e.g. parsed back from pe_info / st_info text). */
 int vs_links_from_host(vs_ctx *ctx, const int64_t *node_mat, const int64_t *short_mat, uint32_t n,
                        vs_links **out);
+/* (addition to ABI 10) The same table from cells (HOST arrays; vs_info_parse of both files, one after the other): what
+ * vs_links_from_host gives for dense matrices built by m[r][c] += v -- a cell with r != c adds v to P0[r][c] and to P0[c][r],
+ * one with r == c adds v to P0[r][r]; duplicates add.  Below `sparse_min_nodes` nodes (0 = 32 768, as above) the table is
+ * dense: the cells are uploaded and scattered into a zeroed table by a kernel; from there on it is the CSR form (row_ptr u32,
+ * col u32 ascending, val i64, non-zero sums only), mirrored, sorted and merged on the host threads and uploaded.  A cell
+ * outside n x n is VS_E_RANGE. */
+int vs_links_from_cells(vs_ctx *ctx, const uint32_t *rows, const uint32_t *cols, const int64_t *vals, uint64_t n_cells, uint32_t n,
+                        uint32_t sparse_min_nodes, vs_links **out);
 /* Optional, ABI 9: set aside the device buffer of the next table of n nodes (n*n int64) now -- typically when the counters
  * are allocated, before any read is counted -- so that vs_links_from_counts / _from_wide / _from_host does not have to ask the
  * driver for it later (a hipMalloc of tens of gigabytes takes 0.3 ms or half a second depending on what the process freed

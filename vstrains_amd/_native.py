@@ -58,6 +58,12 @@ SYMBOLS = {
     "vs_bgzf_shard_plan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vs_fastq_stream_open_range": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_void_p)]),
     "vs_write_matrix_text": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "vs_write_info_sparse": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "vs_write_info_sparse_host": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "vs_info_parse": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                C.POINTER(C.c_uint64)]),
     "vs_synth_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
                                  C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                  C.POINTER(C.c_void_p)]),
@@ -78,6 +84,7 @@ SYMBOLS = {
     "vs_links_from_counts_tracked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "vs_links_from_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "vs_links_from_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "vs_links_from_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "vs_links_reserve": (C.c_int, [C.c_void_p, C.c_uint32]),
     "vs_links_free": (None, [C.c_void_p, C.c_void_p]),
     "vs_links_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -45,6 +45,9 @@ def build_parser():
     p.add_argument("--no-pe-text", dest="no_pe_text", action="store_true", default=False,
                    help="extension: do not write the N^2-line aln/pe_info and aln/st_info (the graph stages read "
                         "the counters from device memory either way)")
+    p.add_argument("--sparse-pe-text", dest="sparse_pe_text", action="store_true", default=False,
+                   help="extension: write aln/pe_info and aln/st_info with the lines of non-zero count only, formatted on "
+                        "the device (not together with --no-pe-text)")
     return p
 
 
@@ -56,7 +59,10 @@ def _bail(*lines):
 
 
 def main(argv=None, backend=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.no_pe_text and args.sparse_pe_text:
+        parser.error("--no-pe-text and --sparse-pe-text are mutually exclusive")
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
         _bail("\nPath to the assembly graph is required, (.gfa format)", "Please ensure the path is correct")
     args.assembler = args.assembler.lower()
@@ -127,10 +133,12 @@ def main(argv=None, backend=None):
 
     from .graph import pipeline
 
-    if backend is None and args.no_pe_text:
+    if backend is None and (args.no_pe_text or args.sparse_pe_text):
         from .graph.hip_ops import HipBackend
 
-        backend = HipBackend(args.device, write_info_text=False)
+        backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text)
+    elif backend is not None and args.sparse_pe_text:
+        backend.sparse_info_text = True
 
     old_err = numpy.seterr(all="raise")  # vstrains:25
     try:

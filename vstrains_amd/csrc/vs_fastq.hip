@@ -813,6 +813,7 @@ int vs_fastq_block(vs_ctx *ctx, vs_fastq *fq, uint64_t first, uint64_t count, vs
 // (the streamed ingest, vs_stream.hip, checks and translates its chunks with the same routines)
 bool vs_utf8_range_ok(const uint8_t *txt, size_t size, size_t lo, size_t hi) { return utf8_range_ok(txt, size, lo, hi); }
 uint32_t vs_utf8_char_len(const uint8_t *q, size_t n) { return utf8_char_len(q, n); }
+unsigned vs_host_threads() { return n_threads(); }
 
 // ---- pe_info / st_info text -------------------------------------------------------------------
 // utils/VStrains_PE_Inference.py:194-205 writes "{id_i}:{id_j}:{count}\n" for all i, j in

@@ -12,6 +12,8 @@
 #include <string.h>
 #include <time.h>
 
+#include <algorithm>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -697,6 +699,23 @@ int links_build_sparse(vs_ctx *ctx, const TIn *d_node, const TIn *d_short, uint3
 }
 }  // namespace
 
+// K5c  the table from (row, column, value) cells parsed out of pe_info / st_info text (vs_info_parse): what vs_links_from_host
+// gives for dense matrices built by m[r][c] += v -- every cell adds to P0[r][c] and, off the diagonal, to P0[c][r] as well
+// (process_pe_info, IO.py:614-623: every line is added under the key (min, max)).  Duplicates add; int64 adds commute, so the
+// order the atomics land in does not matter.
+namespace {
+__global__ void __launch_bounds__(256) k_links_scatter(const uint32_t *__restrict__ rows, const uint32_t *__restrict__ cols,
+                                                      const int64_t *__restrict__ vals, uint64_t n_cells, uint32_t n, int64_t *__restrict__ p0) {
+    for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n_cells; x += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = rows[x], c = cols[x];
+        if (r >= n || c >= n) continue;  // (refused on the host before the launch)
+        const unsigned long long v = (unsigned long long)vals[x];
+        atomicAdd((unsigned long long *)&p0[(uint64_t)r * n + c], v);
+        if (r != c) atomicAdd((unsigned long long *)&p0[(uint64_t)c * n + r], v);
+    }
+}
+}  // namespace
+
 extern "C" {
 
 int vs_links_reserve(vs_ctx *ctx, uint32_t n) {
@@ -752,6 +771,120 @@ int vs_links_from_host(vs_ctx *ctx, const int64_t *node_mat, const int64_t *shor
     int rc = links_build<int64_t>(ctx, a->as<int64_t>(), b->as<int64_t>(), n, out);
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return rc;
+}
+
+int vs_links_from_cells(vs_ctx *ctx, const uint32_t *rows, const uint32_t *cols, const int64_t *vals, uint64_t n_cells, uint32_t n,
+                        uint32_t sparse_min_nodes, vs_links **out) {
+    if (!ctx || !out || (n_cells && (!rows || !cols || !vals))) return vs_fail(ctx, VS_E_ARG, "vs_links_from_cells: bad argument");
+    for (uint64_t x = 0; x < n_cells; x++)
+        if (rows[x] >= n || cols[x] >= n) return vs_fail(ctx, VS_E_RANGE, "vs_links_from_cells: cell %llu (%u, %u) outside %u nodes", (unsigned long long)x, rows[x], cols[x], n);
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t min_nodes = sparse_min_nodes ? sparse_min_nodes : VS_LINKS_SPARSE_MIN;
+    vs_links *L = new vs_links();
+    L->n = n;
+    const auto fail = [&](int rc) {
+        vs_links_free(ctx, L);
+        return rc;
+    };
+    if (n < min_nodes) {  // dense: the cells uploaded and scattered into a zeroed table
+        const size_t bytes = (size_t)(n ? (uint64_t)n * n : 1) * sizeof(int64_t);
+        if (ctx->links_spare.ptr() && ctx->links_spare_n == n && n) {  // vs_links_reserve set it aside
+            L->d_p0 = std::move(ctx->links_spare);
+            ctx->links_spare_n = 0;
+        } else if (L->d_p0.reserve(bytes) != hipSuccess) {
+            return fail(vs_fail(ctx, VS_E_OOM, "vs_links_from_cells: %.2f GB", (double)bytes / 1e9));
+        }
+        VsDevBuf d_rows, d_cols, d_vals;  // (die with the call)
+        const auto on_device = [&]() -> int {
+            VS_HIP(ctx, hipMemsetAsync(L->d_p0.ptr(), 0, bytes, ctx->stream));
+            if (!n_cells) return VS_OK;
+            VS_HIP(ctx, d_rows.reserve((size_t)n_cells * sizeof(uint32_t)));
+            VS_HIP(ctx, d_cols.reserve((size_t)n_cells * sizeof(uint32_t)));
+            VS_HIP(ctx, d_vals.reserve((size_t)n_cells * sizeof(int64_t)));
+            VS_HIP(ctx, hipMemcpyAsync(d_rows.ptr(), rows, (size_t)n_cells * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VS_HIP(ctx, hipMemcpyAsync(d_cols.ptr(), cols, (size_t)n_cells * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VS_HIP(ctx, hipMemcpyAsync(d_vals.ptr(), vals, (size_t)n_cells * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+            const unsigned grid = (unsigned)std::min<uint64_t>((n_cells + 255u) / 256u, 2048u);
+            hipLaunchKernelGGL(k_links_scatter, dim3(grid), dim3(256), 0, ctx->stream, d_rows.as<const uint32_t>(), d_cols.as<const uint32_t>(),
+                               d_vals.as<const int64_t>(), n_cells, n, L->d_p0.as<int64_t>());
+            VS_HIP(ctx, hipGetLastError());
+            return VS_OK;
+        };
+        int rc = on_device();
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = vs_fail(ctx, VS_E_HIP, "vs_links_from_cells: the scatter failed");
+        if (rc) return fail(rc);
+        *out = L;
+        return VS_OK;
+    }
+    // CSR rows (the form vs_links_from_counts_tracked gives from 2^15 nodes on), built on the host -- a one-off over the
+    // cells of two files: every cell and its mirror dealt to its row (a counting sort over the rows), every row sorted by
+    // column on the host threads, equal columns merged, sums of zero dropped (the table holds non-zero cells)
+    std::vector<uint64_t> start((size_t)n + 2u, 0);
+    for (uint64_t x = 0; x < n_cells; x++) {
+        start[(size_t)rows[x] + 1u]++;
+        if (rows[x] != cols[x]) start[(size_t)cols[x] + 1u]++;
+    }
+    for (uint32_t r = 0; r < n; r++) start[(size_t)r + 1u] += start[r];
+    std::vector<std::pair<uint32_t, int64_t>> ent((size_t)start[n]);
+    {
+        std::vector<uint64_t> cur(start.begin(), start.begin() + n + 1);
+        for (uint64_t x = 0; x < n_cells; x++) {
+            ent[(size_t)cur[rows[x]]++] = {cols[x], vals[x]};
+            if (rows[x] != cols[x]) ent[(size_t)cur[cols[x]]++] = {rows[x], vals[x]};
+        }
+    }
+    std::vector<uint32_t> kept((size_t)n + 1u, 0);  // entries row r keeps, packed at the front of its stretch
+    const unsigned T = (unsigned)std::max<uint64_t>(1u, std::min<uint64_t>(vs_host_threads(), ent.size() >> 16));
+    {
+        std::vector<std::thread> th;
+        const auto work = [&](unsigned p) {
+            // (rows dealt so that every thread gets about the same number of entries)
+            const uint64_t lo_e = ent.size() * p / T, hi_e = ent.size() * (p + 1) / T;
+            const uint32_t r0 = p ? (uint32_t)(std::lower_bound(start.begin(), start.begin() + n + 1, lo_e) - start.begin()) : 0u;
+            const uint32_t r1 = p + 1 < T ? (uint32_t)(std::lower_bound(start.begin(), start.begin() + n + 1, hi_e) - start.begin()) : n;
+            for (uint32_t r = r0; r < r1; r++) {
+                auto *b = ent.data() + start[r], *e = ent.data() + start[(size_t)r + 1u];
+                std::sort(b, e, [](const auto &x, const auto &y) { return x.first < y.first; });
+                auto *w = b;
+                for (auto *q = b; q < e;) {
+                    uint32_t c = q->first;
+                    uint64_t sum = 0;  // (unsigned: a sum that wraps wraps as the device's adds do)
+                    for (; q < e && q->first == c; q++) sum += (uint64_t)q->second;
+                    if (sum) *w++ = {c, (int64_t)sum};
+                }
+                kept[r] = (uint32_t)(w - b);
+            }
+        };
+        for (unsigned p = 1; p < T; p++) th.emplace_back(work, p);
+        work(0u);
+        for (auto &t : th) t.join();
+    }
+    uint64_t nnz = 0;
+    for (uint32_t r = 0; r < n; r++) nnz += kept[r];
+    if (nnz > 0xFFFFFFF0ull) return fail(vs_fail(ctx, VS_E_RANGE, "vs_links (sparse): %llu non-zero cells", (unsigned long long)nnz));
+    std::vector<uint32_t> row_ptr((size_t)n + 2u, 0), col((size_t)nnz + 1u, 0);
+    std::vector<int64_t> val((size_t)nnz + 1u, 0);
+    for (uint32_t r = 0; r < n; r++) {
+        const auto *b = ent.data() + start[r];
+        uint32_t at = row_ptr[r];
+        for (uint32_t x = 0; x < kept[r]; x++, at++) col[at] = b[x].first, val[at] = b[x].second;
+        row_ptr[(size_t)r + 1u] = at;
+    }
+    row_ptr[(size_t)n + 1u] = row_ptr[n];
+    L->nnz = nnz;
+    const auto upload = [&]() -> int {
+        VS_HIP(ctx, L->d_row_ptr.reserve(row_ptr.size() * sizeof(uint32_t)));
+        VS_HIP(ctx, L->d_col.reserve(col.size() * sizeof(uint32_t)));
+        VS_HIP(ctx, L->d_val.reserve(val.size() * sizeof(int64_t)));
+        VS_HIP(ctx, hipMemcpyAsync(L->d_row_ptr.ptr(), row_ptr.data(), row_ptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        VS_HIP(ctx, hipMemcpyAsync(L->d_col.ptr(), col.data(), col.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        VS_HIP(ctx, hipMemcpyAsync(L->d_val.ptr(), val.data(), val.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return VS_OK;
+    };
+    if (int rc = upload()) return fail(rc);
+    *out = L;
+    return VS_OK;
 }
 
 void vs_links_free(vs_ctx *ctx, vs_links *links) {

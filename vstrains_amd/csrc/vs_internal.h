@@ -193,6 +193,8 @@ extern "C" void vs_ctx_free_index(vs_ctx *ctx);
 // start in [lo, hi) of txt[0, size) are valid; bytes of the character at q[0] (n available), 0 if invalid
 bool vs_utf8_range_ok(const uint8_t *txt, size_t size, size_t lo, size_t hi);
 uint32_t vs_utf8_char_len(const uint8_t *q, size_t n);
+// host threads a parallel host loop may use (the affinity mask cut by the cgroup quota, or VS_HOST_THREADS): vs_fastq.hip
+unsigned vs_host_threads();
 // kernels of vs_reads.hip that other translation units launch on a stream of their own
 void vs_launch_count_invalid(hipStream_t st, const uint32_t *meta, uint64_t n_ends, uint32_t *out);
 void vs_launch_inv4(hipStream_t st, const uint32_t *woff, const uint32_t *mask, uint64_t n_ends, uint32_t *meta, uint32_t *inv4);
@@ -322,6 +324,22 @@ __device__ __forceinline__ uint32_t vs_upper_idx(const T *a, uint32_t n, T x) {
         if (a[mid] <= x) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// Inclusive scans over the 64 lanes of a wavefront by DPP moves -- row_shr 1, 2, 4, 8 inside the rows of 16 lanes, then the
+// last lane of a row broadcast to the rows after it (row_bcast 15 / 31) -- six VALU instructions where the __shfl_up form
+// takes six ds_bpermute round trips through the LDS crossbar (r6).  A lane whose source lies outside its row keeps the `old`
+// operand: the identity of the operation.
+#define VS_DPP_STEP(op, ctrl, rowmask) { const uint32_t t_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rowmask, 0xf, false); v = op; }
+__device__ __forceinline__ uint32_t vs_wave_scan_add(uint32_t v) {
+    VS_DPP_STEP(v + t_, 0x111, 0xf) VS_DPP_STEP(v + t_, 0x112, 0xf) VS_DPP_STEP(v + t_, 0x114, 0xf) VS_DPP_STEP(v + t_, 0x118, 0xf)
+    VS_DPP_STEP(v + t_, 0x142, 0xa) VS_DPP_STEP(v + t_, 0x143, 0xc)
+    return v;
+}
+__device__ __forceinline__ uint32_t vs_wave_scan_max(uint32_t v) {
+    VS_DPP_STEP(v > t_ ? v : t_, 0x111, 0xf) VS_DPP_STEP(v > t_ ? v : t_, 0x112, 0xf) VS_DPP_STEP(v > t_ ? v : t_, 0x114, 0xf)
+    VS_DPP_STEP(v > t_ ? v : t_, 0x118, 0xf) VS_DPP_STEP(v > t_ ? v : t_, 0x142, 0xa) VS_DPP_STEP(v > t_ ? v : t_, 0x143, 0xc)
+    return v;
 }
 
 #endif  // __HIPCC__

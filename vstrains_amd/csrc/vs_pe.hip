@@ -102,28 +102,13 @@ __device__ __forceinline__ void vs_mark_tile_store(uint8_t *map, uint32_t T, uin
     if (map) map[((uint64_t)mat * T + (x >> 6)) * T + (y >> 6)] = 1;
 }
 
-// Inclusive scans over the 64 lanes of a wavefront by DPP moves -- row_shr 1, 2, 4, 8 inside the rows of 16 lanes, then the
-// last lane of a row broadcast to the rows after it (row_bcast 15 / 31) -- six VALU instructions where the __shfl_up form
-// takes six ds_bpermute round trips through the LDS crossbar (r6).  A lane whose source lies outside its row keeps the `old`
-// operand: the identity of the operation.
+// (the wavefront scans by DPP moves, vs_wave_scan_add / vs_wave_scan_max, are in vs_internal.h)
 // (r6) SIX workgroups per CU for the compile-time shapes of graphs whose ends touch few nodes (the non-adaptive instantiations):
 // a tile table of 768 slots instead of 1 024 (12 per end, placed by a multiply-high range reduction instead of a power-of-two
 // mask) and a list region of 960 words make 26.8 KB of LDS per workgroup, and with the thread index laundered at the top of the
 // tile loop as well (nothing P0 .. P2 derive from it is hoisted across P3) the kernel fits 80 vector registers without
 // scratch: six wavefronts per SIMD instead of five.  configs[2]: 4.70 -> 4.45 ms; either half alone gains nothing
 // (the laundering alone: noise; the smaller table at five workgroups: +2 %).
-#define VS_DPP_STEP(op, ctrl, rowmask) { const uint32_t t_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rowmask, 0xf, false); v = op; }
-__device__ __forceinline__ uint32_t vs_wave_scan_add(uint32_t v) {
-    VS_DPP_STEP(v + t_, 0x111, 0xf) VS_DPP_STEP(v + t_, 0x112, 0xf) VS_DPP_STEP(v + t_, 0x114, 0xf) VS_DPP_STEP(v + t_, 0x118, 0xf)
-    VS_DPP_STEP(v + t_, 0x142, 0xa) VS_DPP_STEP(v + t_, 0x143, 0xc)
-    return v;
-}
-__device__ __forceinline__ uint32_t vs_wave_scan_max(uint32_t v) {
-    VS_DPP_STEP(v > t_ ? v : t_, 0x111, 0xf) VS_DPP_STEP(v > t_ ? v : t_, 0x112, 0xf) VS_DPP_STEP(v > t_ ? v : t_, 0x114, 0xf)
-    VS_DPP_STEP(v > t_ ? v : t_, 0x118, 0xf) VS_DPP_STEP(v > t_ ? v : t_, 0x142, 0xa) VS_DPP_STEP(v > t_ ? v : t_, 0x143, 0xc)
-    return v;
-}
-
 struct Mem {  // one credited maximal exact match
     uint32_t cnt, minp, minj;
 };

@@ -135,8 +135,63 @@ class HipPeLinks(PeLinks):
         return cls(ctx, h, names)
 
     @classmethod
-    def from_files(cls, ctx, names: Sequence[str], pe_file: str, st_file: str):
-        """The reference's own hand-off (IO.py:603-623): parse the two N^2-line text files."""
+    def from_files(cls, ctx, names: Sequence[str], pe_file: str, st_file: str, sparse_min_nodes: int = 0):
+        """The reference's own hand-off (IO.py:603-623): the two text files, dense (N^2 lines) or sparse (the lines of
+        non-zero count only).  The library parses them on the host threads (``vs_info_parse``) and builds the table from
+        the cells (``vs_links_from_cells``: dense below ``sparse_min_nodes`` nodes -- 0: the library's 32 768 --, CSR rows
+        from there on); a file that holds a carriage return or a byte outside ASCII is left to Python's text mode, the
+        loop over ``formats.read_pe_text``."""
+        names = list(names)
+        cells = []
+        for path in (pe_file, st_file):
+            got = cls._parse_cells(names, path)
+            if got is None:
+                return cls._from_files_python(ctx, names, pe_file, st_file)
+            cells.append(got)
+        rows = np.concatenate([c[0] for c in cells])
+        cols = np.concatenate([c[1] for c in cells])
+        vals = np.concatenate([c[2] for c in cells])
+        h = C.c_void_p()
+        nat.check(ctx._h, nat.lib().vs_links_from_cells(ctx._h, _ptr(rows), _ptr(cols), _ptr(vals), rows.size, len(names),
+                                                        sparse_min_nodes, C.byref(h)))
+        return cls(ctx, h, names)
+
+    @staticmethod
+    def _parse_cells(names: Sequence[str], path: str):
+        """``vs_info_parse`` of one file: (rows uint32, cols uint32, vals int64), or None when the file is Python's to read
+        (a carriage return, a byte outside ASCII, a name the library cannot be handed as bytes)."""
+        try:
+            enc = [s.encode("ascii") for s in names]
+        except UnicodeEncodeError:
+            return None
+        off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        if enc:
+            off[1:] = np.cumsum([len(b) for b in enc], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8)
+        info = (C.c_uint64 * 4)()
+
+        def call(rows, cols, vals, cap):
+            rc = nat.lib().vs_info_parse(path.encode(), blob.ctypes.data, off.ctypes.data, len(enc), rows, cols, vals, cap, info)
+            if rc != nat.VS_OK:
+                msg = (nat.lib().vs_last_error(None) or b"?").decode("utf-8", "replace")
+                if "cannot open" in msg:
+                    raise FileNotFoundError(msg)
+                raise ValueError(msg)  # (a malformed line: what the unpacking / int() of the Python loop raises)
+
+        call(None, None, None, 0)
+        if int(info[1]):
+            return None
+        cap = int(info[0])
+        rows = np.zeros(max(cap, 1), dtype=np.uint32)
+        cols = np.zeros(max(cap, 1), dtype=np.uint32)
+        vals = np.zeros(max(cap, 1), dtype=np.int64)
+        if cap:
+            call(rows.ctypes.data, cols.ctypes.data, vals.ctypes.data, cap)
+            cap = int(info[0])
+        return rows[:cap], cols[:cap], vals[:cap]
+
+    @classmethod
+    def _from_files_python(cls, ctx, names: Sequence[str], pe_file: str, st_file: str):
         from .formats import read_pe_text
 
         index = {n: i for i, n in enumerate(names)}
@@ -226,12 +281,13 @@ class HipPeLinks(PeLinks):
 class HipBackend:
     """What ``pipeline.run`` needs from the device: PE-link inference + the graph kernels."""
 
-    def __init__(self, device: int = 0, write_info_text: bool = True, ctx=None):
+    def __init__(self, device: int = 0, write_info_text: bool = True, ctx=None, sparse_info_text: bool = False):
         from .. import pe as host
 
         self.ctx = ctx if ctx is not None else host.Context(device)  # raises NativeError without a HIP device
         self.graph_ops = HipGraphOps(self.ctx)
         self.write_info_text = write_info_text
+        self.sparse_info_text = sparse_info_text  # pe_info / st_info with the lines of non-zero count only
         self.pe_stats = None
 
     def pe_links(self, gfa: str, aln_dir: str, fwd: str, rve: str, ksize: int, names: List[str]) -> HipPeLinks:
@@ -242,7 +298,8 @@ class HipBackend:
 
         print("----------------------Paired-End Information Alignment----------------------")
         if self.write_info_text:
-            self.pe_stats = pe_inference.run(gfa, aln_dir, fwd, rve, ksize, ctx=self.ctx, stages_follow=True)
+            self.pe_stats = pe_inference.run(gfa, aln_dir, fwd, rve, ksize, ctx=self.ctx, stages_follow=True,
+                                              sparse_info=self.sparse_info_text)
             ids, counter = pe_inference.run.last
         else:
             os.makedirs(aln_dir, exist_ok=True)

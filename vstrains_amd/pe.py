@@ -927,6 +927,44 @@ class PeCounter:
 
         vdist.settle(self._xstate)
 
+    def write_sparse_text(self, pe_path: str, st_path: str, ids: Sequence[str]):
+        """``pe_info`` / ``st_info`` without the lines whose count is 0 -- the other lines byte for byte those
+        ``write_matrix_text`` writes from ``result()``, in the same order -- formatted from the counters where they lie
+        (``vs_write_info_sparse``: on the device for device counters; counters held in CPU tensors go through the library's
+        host twin).  No permuted copy of a matrix is made and none is downloaded.  Returns per file
+        ``dict(lines, bytes, blocks, cells_read)``."""
+        torch = self.torch
+        n = self.n
+        if len(ids) != n:
+            raise ValueError("%d ids for counters of %d nodes" % (len(ids), n))
+        blob, off = _encode_ids(ids)
+        rank = None if self.node_rank is None else np.ascontiguousarray(self.node_rank, dtype=np.uint32)
+        tiles = (max(n, 1) + 63) // 64
+        on_device = self.mats.is_cuda
+        if on_device:
+            torch.cuda.synchronize(self.device)
+        out = []
+        for m, path in enumerate((pe_path, st_path)):
+            info = (C.c_uint64 * 4)()
+            args = (path.encode(), blob.ctypes.data, off.ctypes.data, n,
+                    C.c_void_p(self.mats[m].data_ptr()) if n else None,
+                    C.c_void_p(self.wide[m].data_ptr()) if (self.wide is not None and n) else None,
+                    C.c_void_p(self.tile_map[m * tiles * tiles:].data_ptr()) if (self.tile_map is not None and n) else None,
+                    rank.ctypes.data if rank is not None else None, m, info)
+            if on_device:
+                with torch.cuda.device(self.device):
+                    self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+                    rc = nat.lib().vs_write_info_sparse(self.ctx._h, *args)
+                err = self.ctx._h
+            else:
+                rc = nat.lib().vs_write_info_sparse_host(None, *args)
+                err = None
+            if rc != nat.VS_OK:
+                msg = (nat.lib().vs_last_error(err) or b"?").decode("utf-8", "replace")
+                raise (OSError if "cannot open" in msg or "write to" in msg else ValueError)(msg)
+            out.append(dict(lines=int(info[0]), bytes=int(info[1]), blocks=int(info[2]), cells_read=int(info[3])))
+        return out
+
     def user_order(self, t):
         """[2,N,N] device tensor in the index's internal numbering -> the caller's (``Context.build_index``):
         node_mat rows and columns permuted; short_mat, which holds a pair of nodes at (smaller, larger) number
@@ -964,16 +1002,21 @@ class PeCounter:
 
 
 # ---- outputs -------------------------------------------------------------------------------------
-def write_matrix_text(path: str, ids: Sequence[str], mat: np.ndarray):
-    """``{id_i}:{id_j}:{count}`` for all i, j in row-major order, zeros included
-    (PE_Inference.py:194-205) -- N^2 lines, formatted by the library on all host cores."""
+def _encode_ids(ids: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+    """The node names as the text writers take them: concatenated latin-1 bytes and their n + 1 offsets."""
     names = [s.encode("latin-1") for s in ids]
     off = np.zeros(len(names) + 1, dtype=np.uint64)
     if names:
         off[1:] = np.cumsum([len(b) for b in names], dtype=np.uint64)
-    blob = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
+    return np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8), off
+
+
+def write_matrix_text(path: str, ids: Sequence[str], mat: np.ndarray):
+    """``{id_i}:{id_j}:{count}`` for all i, j in row-major order, zeros included
+    (PE_Inference.py:194-205) -- N^2 lines, formatted by the library on all host cores."""
+    blob, off = _encode_ids(ids)
     m = np.ascontiguousarray(mat, dtype=np.int64)
-    rc = nat.lib().vs_write_matrix_text(None, path.encode(), blob.ctypes.data, off.ctypes.data, len(names),
+    rc = nat.lib().vs_write_matrix_text(None, path.encode(), blob.ctypes.data, off.ctypes.data, len(ids),
                                         m.ctypes.data if m.size else None)
     if rc != nat.VS_OK:
         raise OSError(nat.lib().vs_last_error(None).decode("utf-8", "replace"))
