@@ -3,7 +3,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <utility>
 
 #include "vs_internal.h"
 
@@ -43,34 +42,6 @@ void vs_tuning_load(VsTuning &t, bool experiment) {
     t.no_std = env_on("VS_NO_STD");
     t.no_agg = env_on("VS_NO_AGG");
     t.no_mid = env_on("VS_NO_MID");
-}
-
-void *vs_cache_alloc(vs_ctx *ctx, size_t bytes) {
-    if (!bytes) bytes = 16;
-    for (auto &b : ctx->cache)
-        if (!b.used && b.buf.capacity() >= bytes && b.buf.capacity() <= 2 * bytes + (1u << 20)) {
-            b.used = true;
-            return b.buf.ptr();
-        }
-    VsDevBuf buf;
-    if (buf.reserve(bytes, bytes + bytes / 8) != hipSuccess) return nullptr;  // (blocks of one file differ a little in size)
-    ctx->cache.push_back({std::move(buf), true});
-    return ctx->cache.back().buf.ptr();
-}
-
-void vs_cache_release(vs_ctx *ctx, void *p) {
-    if (!p) return;
-    size_t idle = 0;
-    for (auto &b : ctx->cache)
-        if (b.buf.ptr() == p) b.used = false;
-    for (auto &b : ctx->cache)
-        if (!b.used) idle++;
-    if (idle > 24) {  // do not hoard: drop the idle ones
-        std::vector<vs_ctx::CachedBuf> keep;
-        for (auto &b : ctx->cache)
-            if (b.used) keep.push_back(std::move(b));
-        ctx->cache.swap(keep);
-    }
 }
 
 extern "C" {

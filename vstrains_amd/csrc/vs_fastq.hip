@@ -765,7 +765,6 @@ int vs_fastq_block(vs_ctx *ctx, vs_fastq *fq, uint64_t first, uint64_t count, vs
         part_flags[p] = any;
     });
     h_woff[n_ends] = (uint32_t)words;
-    for (uint32_t i = 0; i < VS_PAD_WORDS; i++) h_words[words + i] = 0u;
     uint32_t any = 0, maxlen = 0;
     for (unsigned p = 0; p < T; p++) { any |= part_flags[p]; maxlen = part_max[p] > maxlen ? part_max[p] : maxlen; }
     if (any & (VS_FLAG_INVALID | 0x80u)) {
@@ -781,23 +780,16 @@ int vs_fastq_block(vs_ctx *ctx, vs_fastq *fq, uint64_t first, uint64_t count, vs
         return vs_reads_pack(ctx, bytes.data(), off.data(), n_ends, out);
     }
     vs_reads *r = new vs_reads();
-    r->n_ends = n_ends;
-    r->n_words = words;
     r->max_len = maxlen;
     r->cached = true;
-    const size_t b_woff = sizeof(uint32_t) * (n_ends + 1), b_meta = sizeof(uint32_t) * (n_ends ? n_ends : 1);
-    const size_t b_words = sizeof(uint32_t) * (words + VS_PAD_WORDS);
-    r->d_woff = vs_cache_alloc(ctx, b_woff);
-    r->d_meta = vs_cache_alloc(ctx, b_meta);
-    r->d_words = vs_cache_alloc(ctx, b_words);
-    r->bytes = b_woff + b_meta + b_words;
-    if (!r->d_woff || !r->d_meta || !r->d_words) {
+    hipError_t e1 = vs_reads_alloc(ctx, ctx->stream, r, n_ends, &words, false);
+    if (e1 == hipErrorOutOfMemory) {
         vs_reads_free(ctx, r);
         return vs_fail(ctx, VS_E_OOM, "vs_fastq_block: device buffers for %llu ends", (unsigned long long)n_ends);
     }
-    hipError_t e1 = hipMemcpyAsync(r->d_woff, h_woff, b_woff, hipMemcpyHostToDevice, ctx->stream);
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(r->d_woff, h_woff, sizeof(uint32_t) * (n_ends + 1), hipMemcpyHostToDevice, ctx->stream);
     if (e1 == hipSuccess && n_ends) e1 = hipMemcpyAsync(r->d_meta, h_meta, sizeof(uint32_t) * n_ends, hipMemcpyHostToDevice, ctx->stream);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(r->d_words, h_words, b_words, hipMemcpyHostToDevice, ctx->stream);
+    if (e1 == hipSuccess && words) e1 = hipMemcpyAsync(r->d_words, h_words, sizeof(uint32_t) * words, hipMemcpyHostToDevice, ctx->stream);
     if (e1 == hipSuccess) e1 = hipEventRecord(st.done, ctx->stream);
     if (e1 != hipSuccess) {
         vs_reads_free(ctx, r);

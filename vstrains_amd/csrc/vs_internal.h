@@ -153,17 +153,13 @@ struct vs_ctx {
 
 struct vs_reads {
     uint64_t n_ends = 0, n_words = 0, max_len = 0, n_invalid = 0, bytes = 0;
-    // the five arrays as the kernels see them: lent by the context's cache (cached: vs_cache_alloc) or held in own[]
+    // the five arrays as the kernels see them, all from one place: lent by the context's cache (cached: the blocks of the
+    // FASTQ ingests, one after another of about the same size) or held by the block itself in own[]
     void *d_woff = nullptr, *d_meta = nullptr, *d_words = nullptr, *d_mask = nullptr, *d_inv4 = nullptr;
     bool cached = false;
     VsDevBuf own[5];
-    unsigned n_own = 0;
-    hipError_t own_alloc(void *&view, size_t bytes) {  // one more array of a block that is not cached
-        const hipError_t e = own[n_own].reserve(bytes);
-        view = own[n_own].ptr();
-        if (e == hipSuccess) n_own++;
-        return e;
-    }
+    hipError_t alloc(vs_ctx *ctx, void *&view, size_t bytes);  // one more array (vs_reads.hip)
+    void release(vs_ctx *ctx, void *&view);                    // ... given back; view = NULL
     VsReadsDev dev() const {
         VsReadsDev r;
         r.n_ends = n_ends;
@@ -177,9 +173,6 @@ struct vs_reads {
 };
 
 int vs_fail(vs_ctx *ctx, int code, const char *fmt, ...);
-// grow-only cache of device buffers (see vs_ctx::cache); NULL on allocation failure
-void *vs_cache_alloc(vs_ctx *ctx, size_t bytes);
-void vs_cache_release(vs_ctx *ctx, void *p);
 extern "C" void vs_ctx_free_index(vs_ctx *ctx);
 #define VS_HIP(ctx, call)                                                                  \
     do {                                                                                   \
@@ -195,9 +188,23 @@ bool vs_utf8_range_ok(const uint8_t *txt, size_t size, size_t lo, size_t hi);
 uint32_t vs_utf8_char_len(const uint8_t *q, size_t n);
 // host threads a parallel host loop may use (the affinity mask cut by the cgroup quota, or VS_HOST_THREADS): vs_fastq.hip
 unsigned vs_host_threads();
-// kernels of vs_reads.hip that other translation units launch on a stream of their own
-void vs_launch_count_invalid(hipStream_t st, const uint32_t *meta, uint64_t n_ends, uint32_t *out);
-void vs_launch_inv4(hipStream_t st, const uint32_t *woff, const uint32_t *mask, uint64_t n_ends, uint32_t *meta, uint32_t *inv4);
+// How a read block comes to be (vs_reads.hip), for every builder, on the stream the builder works on.
+// The arrays of block r, from where r->cached says: woff and meta for n_ends ends at the first call; words (and the mask
+// beside them, where asked) once n_words is known -- in the same call or a later one -- with their pad tails zeroed.
+// Sets n_ends, n_words and bytes.
+hipError_t vs_reads_alloc(vs_ctx *ctx, hipStream_t st, vs_reads *r, uint64_t n_ends, const uint64_t *n_words, bool with_mask);
+// The last step of a block packed on the device, its mask written: the ends flagged VS_FLAG_INVALID counted into *d_cnt
+// (zero before) and read back through *h_cnt (synchronises st) = n_invalid; none: the mask goes back; else it stays, inv4 is
+// built from it and bytes grows by both.
+hipError_t vs_reads_finish(vs_ctx *ctx, hipStream_t st, vs_reads *r, uint32_t *d_cnt, uint32_t *h_cnt);
+// A window of the streamed ingest (vs_stream.hip): its text and the byte offsets of its n_nl line ends
+struct SlWin {
+    const uint8_t *txt;
+    const uint32_t *ends;
+    uint32_t n_nl, size;
+};
+// k_pack_reads for the first r->n_ends / 2 records of two windows (r's woff and lengths are on the device, r->d_mask too)
+void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, const vs_reads *r);
 
 // BGZF members (vs_inflate.hip), shared with the streamed ingest.  A member for the device: its raw deflate payload in a
 // buffer of compressed bytes, where its ISIZE bytes go in an output buffer, and the CRC32 of its trailer.

@@ -3,30 +3,54 @@
 //
 // Layout (see vs_internal.h): ends interleaved (2r = forward, 2r+1 = reverse), every end starts
 // on a uint32 word, 16 bases per word, LSB first; meta[e] = length | flags << 24.
+#include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "vs_internal.h"
+#include "vs_pack_host.h"
 
 #define TPB 256
 
-// one thread per packed word
+// Where the bytes of a block's ends lie: end(e, &len) = the first byte of end e and how many there are.
+struct PackText {  // the caller's text: end e is ascii[aoff[e], aoff[e + 1])
+    const uint8_t *ascii;
+    const uint64_t *aoff;
+    __device__ const uint8_t *end(uint32_t e, uint32_t *len) const {
+        const uint64_t a = aoff[e];
+        *len = (uint32_t)(aoff[e + 1] - a);
+        return ascii + a;
+    }
+};
+struct PackLines {  // the windows of the streamed ingest: end e is line 4 (e / 2) + 1 of file e & 1, without its newline
+    SlWin f0, f1;
+    __device__ const uint8_t *end(uint32_t e, uint32_t *len) const {
+        const SlWin &w = (e & 1u) ? f1 : f0;
+        const uint32_t r = e >> 1;
+        const uint32_t start = w.ends[4u * r] + 1u;
+        *len = w.ends[4u * r + 1u] - start;
+        return w.txt + start;
+    }
+};
+
+// one thread per packed word; mask (may be NULL) beside the words
+template <class Src>
 __global__ void __launch_bounds__(TPB)
-k_pack_reads(const uint8_t *__restrict__ ascii, const uint64_t *__restrict__ aoff,
-             const uint32_t *__restrict__ woff, uint64_t n_ends, uint32_t total_words,
+k_pack_reads(Src src, const uint32_t *__restrict__ woff, uint32_t n_ends, uint32_t total_words,
              uint32_t *__restrict__ words, uint32_t *__restrict__ mask, uint32_t *__restrict__ meta) {
-    uint32_t wi = blockIdx.x * TPB + threadIdx.x;
+    const uint32_t wi = blockIdx.x * TPB + threadIdx.x;
     if (wi >= total_words) return;
-    uint32_t e = vs_upper_idx(woff, (uint32_t)n_ends + 1u, wi);
-    uint64_t a = aoff[e];
-    uint32_t len = (uint32_t)(aoff[e + 1] - a);
-    uint32_t b0 = (wi - woff[e]) * 16u;
+    const uint32_t e = vs_upper_idx(woff, n_ends + 1u, wi);
+    uint32_t len;
+    const uint8_t *q = src.end(e, &len);
+    const uint32_t b0 = (wi - woff[e]) * 16u;
     uint32_t v = 0, m = 0, fl = 0;
 #pragma unroll
     for (uint32_t i = 0; i < 16; i++) {
-        uint32_t p = b0 + i;
+        const uint32_t p = b0 + i;
         if (p < len) {
-            uint8_t c = ascii[a + p];
-            uint32_t code = vs_code(c);
+            const uint8_t c = q[p];
+            const uint32_t code = vs_code(c);
             if (code > 3u) {
                 fl |= (c == 'N') ? VS_FLAG_N : VS_FLAG_INVALID;
                 m |= 3u << (2 * i);
@@ -38,6 +62,15 @@ k_pack_reads(const uint8_t *__restrict__ ascii, const uint64_t *__restrict__ aof
     if (mask) mask[wi] = m;
     if (fl) atomicOr(&meta[e], fl << 24);
 }
+
+// r's woff and meta (lengths) are on the device: its words, and the mask beside them, from the bytes at src
+template <class Src>
+static void launch_pack(hipStream_t st, const Src &src, const vs_reads *r) {
+    if (r->n_words)
+        hipLaunchKernelGGL(k_pack_reads<Src>, dim3((unsigned)((r->n_words + TPB - 1) / TPB)), dim3(TPB), 0, st, src, (const uint32_t *)r->d_woff,
+                           (uint32_t)r->n_ends, (uint32_t)r->n_words, (uint32_t *)r->d_words, (uint32_t *)r->d_mask, (uint32_t *)r->d_meta);
+}
+void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, const vs_reads *r) { launch_pack(st, PackLines{f0, f1}, r); }
 
 __global__ void __launch_bounds__(TPB)
 k_count_invalid(const uint32_t *__restrict__ meta, uint64_t n_ends, uint32_t *__restrict__ out) {
@@ -79,13 +112,6 @@ k_inv4(const uint32_t *__restrict__ woff, const uint32_t *__restrict__ mask, uin
     inv4[e] = out;
 }
 
-void vs_launch_count_invalid(hipStream_t st, const uint32_t *meta, uint64_t n_ends, uint32_t *out) {
-    if (n_ends) hipLaunchKernelGGL(k_count_invalid, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st, meta, n_ends, out);
-}
-void vs_launch_inv4(hipStream_t st, const uint32_t *woff, const uint32_t *mask, uint64_t n_ends, uint32_t *meta, uint32_t *inv4) {
-    if (n_ends) hipLaunchKernelGGL(k_inv4, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st, woff, mask, n_ends, meta, inv4);
-}
-
 __global__ void __launch_bounds__(TPB)
 k_unpack_reads(VsReadsDev rd, const uint64_t *__restrict__ out_off, uint8_t *__restrict__ out) {
     uint64_t e = (uint64_t)blockIdx.x * TPB + threadIdx.x;
@@ -96,21 +122,92 @@ k_unpack_reads(VsReadsDev rd, const uint64_t *__restrict__ out_off, uint8_t *__r
     for (uint32_t i = 0; i < len; i++) o[i] = "ACGT"[(w[i >> 4] >> ((i & 15u) * 2u)) & 3u];
 }
 
-static int alloc_reads(vs_ctx *ctx, vs_reads *r, bool with_mask) {
-    size_t b_woff = sizeof(uint32_t) * (r->n_ends + 1);
-    size_t b_meta = sizeof(uint32_t) * (r->n_ends ? r->n_ends : 1);
-    size_t b_words = sizeof(uint32_t) * (r->n_words + VS_PAD_WORDS);
-    VS_HIP(ctx, r->own_alloc(r->d_woff, b_woff));
-    VS_HIP(ctx, r->own_alloc(r->d_meta, b_meta));
-    VS_HIP(ctx, r->own_alloc(r->d_words, b_words));
-    VS_HIP(ctx, hipMemsetAsync((char *)r->d_words + sizeof(uint32_t) * r->n_words, 0, VS_PAD_WORDS * sizeof(uint32_t), ctx->stream));
-    r->bytes = b_woff + b_meta + b_words;
-    if (with_mask) {
-        VS_HIP(ctx, r->own_alloc(r->d_mask, b_words));
-        VS_HIP(ctx, hipMemsetAsync((char *)r->d_mask + sizeof(uint32_t) * r->n_words, 0, VS_PAD_WORDS * sizeof(uint32_t), ctx->stream));
-        r->bytes += b_words;
+// ---- a block's memory ----------------------------------------------------------------------------
+// Grow-only cache of device buffers (vs_ctx::cache) that lends the blocks of the FASTQ ingests their arrays; NULL on
+// allocation failure.
+static void *cache_alloc(vs_ctx *ctx, size_t bytes) {
+    if (!bytes) bytes = 16;
+    for (auto &b : ctx->cache)
+        if (!b.used && b.buf.capacity() >= bytes && b.buf.capacity() <= 2 * bytes + (1u << 20)) {
+            b.used = true;
+            return b.buf.ptr();
+        }
+    VsDevBuf buf;
+    if (buf.reserve(bytes, bytes + bytes / 8) != hipSuccess) return nullptr;  // (blocks of one file differ a little in size)
+    ctx->cache.push_back({std::move(buf), true});
+    return ctx->cache.back().buf.ptr();
+}
+
+static void cache_release(vs_ctx *ctx, void *p) {
+    if (!p) return;
+    size_t idle = 0;
+    for (auto &b : ctx->cache)
+        if (b.buf.ptr() == p) b.used = false;
+    for (auto &b : ctx->cache)
+        if (!b.used) idle++;
+    if (idle > 24) {  // do not hoard: drop the idle ones
+        std::vector<vs_ctx::CachedBuf> keep;
+        for (auto &b : ctx->cache)
+            if (b.used) keep.push_back(std::move(b));
+        ctx->cache.swap(keep);
     }
-    return VS_OK;
+}
+
+hipError_t vs_reads::alloc(vs_ctx *ctx, void *&view, size_t bytes) {
+    if (cached) return (view = cache_alloc(ctx, bytes)) ? hipSuccess : hipErrorOutOfMemory;
+    VsDevBuf *b = own;
+    while (b->ptr()) b++;  // (five arrays, five slots)
+    const hipError_t e = b->reserve(bytes);
+    view = b->ptr();
+    return e;
+}
+
+void vs_reads::release(vs_ctx *ctx, void *&view) {
+    if (cached) cache_release(ctx, view);
+    else
+        for (VsDevBuf &b : own)
+            if (view && b.ptr() == view) b.reset();
+    view = nullptr;
+}
+
+hipError_t vs_reads_alloc(vs_ctx *ctx, hipStream_t st, vs_reads *r, uint64_t n_ends, const uint64_t *n_words, bool with_mask) {
+    hipError_t e = hipSuccess;
+    if (!r->d_woff) {
+        const size_t b_woff = sizeof(uint32_t) * (n_ends + 1), b_meta = sizeof(uint32_t) * (n_ends ? n_ends : 1);
+        r->n_ends = n_ends;
+        if ((e = r->alloc(ctx, r->d_woff, b_woff)) != hipSuccess || (e = r->alloc(ctx, r->d_meta, b_meta)) != hipSuccess) return e;
+        r->bytes = b_woff + b_meta;
+    }
+    if (!n_words) return e;
+    const size_t b_words = sizeof(uint32_t) * (*n_words + VS_PAD_WORDS);
+    r->n_words = *n_words;
+    r->bytes += b_words;
+    auto padded = [&](void *&a) {  // n_words words and the zero tail behind them
+        const hipError_t e1 = r->alloc(ctx, a, b_words);
+        return e1 != hipSuccess ? e1 : hipMemsetAsync((uint32_t *)a + r->n_words, 0, sizeof(uint32_t) * VS_PAD_WORDS, st);
+    };
+    if ((e = padded(r->d_words)) == hipSuccess && with_mask) e = padded(r->d_mask);
+    return e;
+}
+
+hipError_t vs_reads_finish(vs_ctx *ctx, hipStream_t st, vs_reads *r, uint32_t *d_cnt, uint32_t *h_cnt) {
+    const unsigned nbe = (unsigned)((r->n_ends + TPB - 1) / TPB);
+    if (nbe) hipLaunchKernelGGL(k_count_invalid, dim3(nbe), dim3(TPB), 0, st, (const uint32_t *)r->d_meta, r->n_ends, d_cnt);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, sizeof *h_cnt, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    r->n_invalid = *h_cnt;
+    if (!r->n_invalid) {
+        r->release(ctx, r->d_mask);
+        return hipSuccess;
+    }
+    // rare: some end holds a byte outside ACGTN -> the mask stays, and the position lists are read off it
+    if ((e = r->alloc(ctx, r->d_inv4, sizeof(uint32_t) * r->n_ends)) != hipSuccess) return e;
+    r->bytes += sizeof(uint32_t) * (r->n_words + VS_PAD_WORDS) + sizeof(uint32_t) * r->n_ends;
+    hipLaunchKernelGGL(k_inv4, dim3(nbe), dim3(TPB), 0, st, (const uint32_t *)r->d_woff, (const uint32_t *)r->d_mask, r->n_ends,
+                       (uint32_t *)r->d_meta, (uint32_t *)r->d_inv4);
+    return hipGetLastError();
 }
 
 extern "C" void vs_reads_free(vs_ctx *ctx, vs_reads *r) {
@@ -118,10 +215,9 @@ extern "C" void vs_reads_free(vs_ctx *ctx, vs_reads *r) {
     if (ctx) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
+        for (void **a : {&r->d_woff, &r->d_meta, &r->d_words, &r->d_mask, &r->d_inv4}) r->release(ctx, *a);
     }
-    if (r->cached && ctx)
-        for (void *p : {r->d_woff, r->d_meta, r->d_words, r->d_mask, r->d_inv4}) vs_cache_release(ctx, p);
-    delete r;  // (what the block owns itself goes with it)
+    delete r;  // (what the block still owns goes with it)
 }
 
 extern "C" int vs_reads_info(const vs_reads *r, uint64_t info[5]) {
@@ -130,46 +226,23 @@ extern "C" int vs_reads_info(const vs_reads *r, uint64_t info[5]) {
     return VS_OK;
 }
 
-// the device side of vs_reads_pack: r's arrays are allocated, woff / meta are the host's word offsets and lengths
+// the device side of vs_reads_pack: woff / meta are the host's word offsets and lengths
 static int pack_block(vs_ctx *ctx, vs_reads *r, const uint8_t *ascii, const uint64_t *off, const std::vector<uint32_t> &woff, const std::vector<uint32_t> &meta) {
-    const uint64_t n_ends = r->n_ends, words = r->n_words, total = off[n_ends];
+    const uint64_t n_ends = woff.size() - 1, words = woff[n_ends], total = off[n_ends];
     hipStream_t st = ctx->stream;
+    VS_HIP(ctx, vs_reads_alloc(ctx, st, r, n_ends, &words, true));
     VsDevBuf ascii_buf, aoff_buf, cnt_buf;
     VS_HIP(ctx, ascii_buf.reserve(total + 16));
     VS_HIP(ctx, aoff_buf.reserve(sizeof(uint64_t) * (n_ends + 1)));
     VS_HIP(ctx, cnt_buf.reserve(sizeof(uint32_t)));
-    uint8_t *d_ascii = ascii_buf.as<uint8_t>();
-    uint64_t *d_aoff = aoff_buf.as<uint64_t>();
-    uint32_t *d_cnt = cnt_buf.as<uint32_t>();
-    if (total) VS_HIP(ctx, hipMemcpyAsync(d_ascii, ascii, total, hipMemcpyHostToDevice, st));
-    VS_HIP(ctx, hipMemcpyAsync(d_aoff, off, sizeof(uint64_t) * (n_ends + 1), hipMemcpyHostToDevice, st));
+    if (total) VS_HIP(ctx, hipMemcpyAsync(ascii_buf.ptr(), ascii, total, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemcpyAsync(aoff_buf.ptr(), off, sizeof(uint64_t) * (n_ends + 1), hipMemcpyHostToDevice, st));
     VS_HIP(ctx, hipMemcpyAsync(r->d_woff, woff.data(), sizeof(uint32_t) * (n_ends + 1), hipMemcpyHostToDevice, st));
     if (n_ends) VS_HIP(ctx, hipMemcpyAsync(r->d_meta, meta.data(), sizeof(uint32_t) * n_ends, hipMemcpyHostToDevice, st));
-    VS_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), st));
-    unsigned nbw = (unsigned)((words + TPB - 1) / TPB);
-    if (words)
-        hipLaunchKernelGGL(k_pack_reads, dim3(nbw), dim3(TPB), 0, st, d_ascii, d_aoff, (const uint32_t *)r->d_woff, n_ends,
-                           (uint32_t)words, (uint32_t *)r->d_words, (uint32_t *)nullptr, (uint32_t *)r->d_meta);
-    if (n_ends)
-        hipLaunchKernelGGL(k_count_invalid, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st,
-                           (const uint32_t *)r->d_meta, n_ends, d_cnt);
+    VS_HIP(ctx, hipMemsetAsync(cnt_buf.ptr(), 0, sizeof(uint32_t), st));
+    launch_pack(st, PackText{ascii_buf.as<uint8_t>(), aoff_buf.as<uint64_t>()}, r);
     uint32_t h_cnt = 0;
-    VS_HIP(ctx, hipMemcpyAsync(&h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
-    VS_HIP(ctx, hipStreamSynchronize(st));
-    r->n_invalid = h_cnt;
-    if (h_cnt) {  // rare: some end holds a byte outside ACGTN -> build the validity mask too
-        size_t b_words = sizeof(uint32_t) * (words + VS_PAD_WORDS);
-        VS_HIP(ctx, r->own_alloc(r->d_mask, b_words));
-        VS_HIP(ctx, hipMemsetAsync(r->d_mask, 0, b_words, st));
-        r->bytes += b_words;
-        hipLaunchKernelGGL(k_pack_reads, dim3(nbw), dim3(TPB), 0, st, d_ascii, d_aoff, (const uint32_t *)r->d_woff, n_ends,
-                           (uint32_t)words, (uint32_t *)r->d_words, (uint32_t *)r->d_mask, (uint32_t *)r->d_meta);
-        VS_HIP(ctx, r->own_alloc(r->d_inv4, sizeof(uint32_t) * n_ends));
-        r->bytes += sizeof(uint32_t) * n_ends;
-        hipLaunchKernelGGL(k_inv4, dim3((unsigned)((n_ends + TPB - 1) / TPB)), dim3(TPB), 0, st, (const uint32_t *)r->d_woff,
-                           (const uint32_t *)r->d_mask, n_ends, (uint32_t *)r->d_meta, (uint32_t *)r->d_inv4);
-    }
-    VS_HIP(ctx, hipGetLastError());
+    VS_HIP(ctx, vs_reads_finish(ctx, st, r, cnt_buf.as<uint32_t>(), &h_cnt));
     VS_HIP(ctx, hipStreamSynchronize(st));  // (the temporaries die here)
     return VS_OK;
 }
@@ -180,24 +253,21 @@ extern "C" int vs_reads_pack(vs_ctx *ctx, const uint8_t *ascii, const uint64_t *
     if (n_ends & 1ull) return vs_fail(ctx, VS_E_ARG, "vs_reads_pack: ends come in pairs (got %llu)", (unsigned long long)n_ends);
     if (n_ends > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "vs_reads_pack: split the input into blocks of < 2^32 ends");
     VS_HIP(ctx, hipSetDevice(ctx->device));
-    vs_reads *r = new vs_reads();
-    r->n_ends = n_ends;
     std::vector<uint32_t> woff(n_ends + 1), meta(n_ends ? n_ends : 1);
     uint64_t words = 0, maxlen = 0;
     for (uint64_t e = 0; e < n_ends; e++) {
         uint64_t len = off[e + 1] - off[e];
-        if (len > VS_LEN_MASK) { delete r; return vs_fail(ctx, VS_E_RANGE, "read end %llu is %llu bytes long", (unsigned long long)e, (unsigned long long)len); }
+        if (len > VS_LEN_MASK) return vs_fail(ctx, VS_E_RANGE, "read end %llu is %llu bytes long", (unsigned long long)e, (unsigned long long)len);
         woff[e] = (uint32_t)words;
         meta[e] = (uint32_t)len;
         words += (len + 15) / 16;
         if (len > maxlen) maxlen = len;
-        if (words > 0xFFFFFFF0ull) { delete r; return vs_fail(ctx, VS_E_RANGE, "vs_reads_pack: block exceeds 2^32 packed words"); }
+        if (words > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "vs_reads_pack: block exceeds 2^32 packed words");
     }
     woff[n_ends] = (uint32_t)words;
-    r->n_words = words;
+    vs_reads *r = new vs_reads();
     r->max_len = maxlen;
-    int rc = alloc_reads(ctx, r, false);
-    if (rc == VS_OK) rc = pack_block(ctx, r, ascii, off, woff, meta);
+    int rc = pack_block(ctx, r, ascii, off, woff, meta);
     if (rc != VS_OK) { vs_reads_free(ctx, r); return rc; }
     *out = r;
     return VS_OK;
@@ -300,11 +370,13 @@ __global__ void __launch_bounds__(TPB) k_iota_woff(uint32_t *woff, uint64_t n, u
     if (i < n) woff[i] = (uint32_t)(i * stride);
 }
 
-// the device side of vs_synth_pairs: r's arrays are allocated
-static int synth_block(vs_ctx *ctx, vs_reads *r, const std::vector<uint32_t> &gwords, const std::vector<uint64_t> &gbase, const std::vector<uint64_t> &glen,
+// the device side of vs_synth_pairs
+static int synth_block(vs_ctx *ctx, vs_reads *r, uint64_t n_ends, const std::vector<uint32_t> &gwords, const std::vector<uint64_t> &gbase, const std::vector<uint64_t> &glen,
                        const uint32_t *cum, uint64_t seed, uint64_t first_pair, uint32_t read_len, uint32_t sub_thresh, uint32_t n_thresh) {
     const uint32_t n_strains = (uint32_t)gbase.size(), wpe = (read_len + 15) / 16;
     hipStream_t st = ctx->stream;
+    const uint64_t n_words = n_ends * wpe;
+    VS_HIP(ctx, vs_reads_alloc(ctx, st, r, n_ends, &n_words, false));
     VsDevBuf d_gw, d_cum, d_gb, d_gl;
     VS_HIP(ctx, d_gw.reserve(sizeof(uint32_t) * gwords.size()));
     VS_HIP(ctx, d_cum.reserve(sizeof(uint32_t) * n_strains));
@@ -349,19 +421,12 @@ extern "C" int vs_synth_pairs(vs_ctx *ctx, const uint8_t *genomes, const uint64_
     }
     std::vector<uint32_t> gwords(gw + 4, 0u);
     for (uint32_t s = 0; s < n_strains; s++)
-        for (uint64_t i = 0; i < glen[s]; i++) {
-            uint8_t c = genomes[goff[s] + i];
-            uint32_t code = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
-            if (code > 3u) return vs_fail(ctx, VS_E_ARG, "vs_synth_pairs: genome %u holds a byte outside ACGT", s);
-            uint64_t b = gbase[s] + i;
-            gwords[b >> 4] |= code << ((b & 15u) * 2u);
-        }
+        for (uint64_t i = 0; i < glen[s]; i += 1u << 30)  // (the packer takes a 32-bit length)
+            if (vs_pack_sequence_host_plain(genomes + goff[s] + i, (uint32_t)std::min<uint64_t>(glen[s] - i, 1u << 30), &gwords[(gbase[s] + i) >> 4]))
+                return vs_fail(ctx, VS_E_ARG, "vs_synth_pairs: genome %u holds a byte outside ACGT", s);
     vs_reads *r = new vs_reads();
-    r->n_ends = 2 * n_pairs;
-    r->n_words = 2 * n_pairs * wpe;
     r->max_len = read_len;
-    int rc = alloc_reads(ctx, r, false);
-    if (rc == VS_OK) rc = synth_block(ctx, r, gwords, gbase, glen, cum, seed, first_pair, read_len, sub_thresh, n_thresh);
+    int rc = synth_block(ctx, r, 2 * n_pairs, gwords, gbase, glen, cum, seed, first_pair, read_len, sub_thresh, n_thresh);
     if (rc != VS_OK) { vs_reads_free(ctx, r); return rc; }
     *out = r;
     return VS_OK;

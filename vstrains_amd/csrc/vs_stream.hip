@@ -27,8 +27,9 @@
 // then, for the n = min(complete records of fwd, of rve) pairs of the block:
 //   k_sl_ends     length (line 4r+1 minus its newline) and packed words of every end, the record cuts;
 //   k_sl_scan     word offsets;
-//   k_sl_pack     one thread per packed word, straight from the window (k_pack_reads' form), the mask beside it;
-// and k_count_invalid / k_inv4 (vs_reads.hip) as vs_reads_pack runs them.  The block is the layout vs_pe_count takes.
+// and from there on as every read block is built (vs_reads.hip): k_pack_reads, one thread per packed word, straight from
+// the windows, the mask beside the words; k_count_invalid, and k_inv4 when some end needs it.  The block is the layout
+// vs_pe_count takes.
 //
 // A window whose scan raises a flag ('\r' or a byte >= 0x80) keeps the reference's text-mode semantics on the host
 // (rare): its complete lines are copied back, universal newlines applied ("\r\n" and a lone '\r' end a line; a '\r' at
@@ -206,12 +207,6 @@ __global__ void __launch_bounds__(SL_TPB) k_sl_scatter(const uint8_t *__restrict
     }
 }
 
-struct SlWin {
-    const uint8_t *txt;
-    const uint32_t *ends;
-    uint32_t n_nl, size;
-};
-
 // one thread per end of the block (and one more for the closing word offset): length, packed words, the longest end, the
 // first end over the 24-bit limit; thread 0 also writes the record cuts (one past the newline of line 4n - 1)
 __global__ void __launch_bounds__(SL_TPB) k_sl_ends(SlWin f0, SlWin f1, uint32_t n_pairs, uint32_t *__restrict__ meta,
@@ -239,37 +234,6 @@ __global__ void __launch_bounds__(SL_TPB) k_sl_ends(SlWin f0, SlWin f1, uint32_t
     meta[e] = len;
     wcnt[e] = (len + 15u) >> 4;
     atomicMax(&st[ST_MAXLEN], len);
-}
-
-// one thread per packed word (k_pack_reads' form), bytes straight from the window; mask beside the words
-__global__ void __launch_bounds__(SL_TPB) k_sl_pack(SlWin f0, SlWin f1, uint32_t n_ends, uint32_t total_words,
-                                                    const uint32_t *__restrict__ woff, uint32_t *__restrict__ words,
-                                                    uint32_t *__restrict__ mask, uint32_t *__restrict__ meta) {
-    const uint32_t wi = blockIdx.x * SL_TPB + threadIdx.x;
-    if (wi >= total_words) return;
-    const uint32_t e = vs_upper_idx(woff, n_ends + 1u, wi);
-    const SlWin &w = (e & 1u) ? f1 : f0;
-    const uint32_t r = e >> 1;
-    const uint32_t start = w.ends[4u * r] + 1u, len = w.ends[4u * r + 1u] - start;
-    const uint8_t *q = w.txt + start;
-    const uint32_t b0 = (wi - woff[e]) * 16u;
-    uint32_t v = 0, m = 0, fl = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 16; i++) {
-        const uint32_t p = b0 + i;
-        if (p < len) {
-            const uint8_t c = q[p];
-            const uint32_t code = vs_code(c);
-            if (code > 3u) {
-                fl |= (c == 'N') ? VS_FLAG_N : VS_FLAG_INVALID;
-                m |= 3u << (2 * i);
-            }
-            v |= (code & 3u) << (2 * i);
-        }
-    }
-    words[wi] = v;
-    mask[wi] = m;
-    if (fl) atomicOr(&meta[e], fl << 24);
 }
 
 // ---- host reader -------------------------------------------------------------------------------------------------------
@@ -1045,29 +1009,26 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     SlWin w0 = {s->df[0].win[s->df[0].cur].as<uint8_t>(), s->df[0].ends.as<uint32_t>(), s->df[0].n_nl, (uint32_t)s->df[0].size};
     SlWin w1 = {s->df[1].win[s->df[1].cur].as<uint8_t>(), s->df[1].ends.as<uint32_t>(), s->df[1].n_nl, (uint32_t)s->df[1].size};
     vs_reads *r = new vs_reads();
-    r->n_ends = n_ends;
     r->cached = true;
-    const size_t b_woff = sizeof(uint32_t) * (n_ends + 1), b_meta = sizeof(uint32_t) * n_ends;
-    r->d_woff = vs_cache_alloc(ctx, b_woff);
-    r->d_meta = vs_cache_alloc(ctx, b_meta);
-    if (!r->d_woff || !r->d_meta) {
+    // (a failure of the block: it goes back, and the stream has failed)
+    auto fail = [&](hipError_t e, const char *oom_msg = nullptr) {
         vs_reads_free(ctx, r);
-        return stream_fail(ctx, s, VS_E_OOM, "vs_fastq_stream_next: device buffers for the block");
-    }
-    hipError_t e1 = hipMemsetAsync(s->d_stat + ST_MAXLEN, 0, sizeof(uint32_t) * (ST_N - ST_MAXLEN), st);
+        if (e == hipErrorOutOfMemory && oom_msg) return stream_fail(ctx, s, VS_E_OOM, oom_msg);
+        return stream_fail(ctx, s, e == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, std::string("vs_fastq_stream_next: ") + hipGetErrorString(e));
+    };
+    const char *no_buffers = "vs_fastq_stream_next: device buffers for the block";
+    hipError_t e1 = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true);
+    if (e1 != hipSuccess) return fail(e1, no_buffers);
+    e1 = hipMemsetAsync(s->d_stat + ST_MAXLEN, 0, sizeof(uint32_t) * (ST_N - ST_MAXLEN), st);
     if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + ST_TOO_LONG, 0xFF, sizeof(uint32_t), st);
-    if (e1 == hipSuccess) {
-        hipLaunchKernelGGL(k_sl_ends, dim3((unsigned)((n_ends + 1u + SL_TPB - 1u) / SL_TPB)), dim3(SL_TPB), 0, st, w0, w1, (uint32_t)n,
-                           (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
-        hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + ST_WORDS);
-        e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), b_woff, hipMemcpyDeviceToDevice, st);
-    }
+    if (e1 != hipSuccess) return fail(e1);
+    hipLaunchKernelGGL(k_sl_ends, dim3((unsigned)((n_ends + 1u + SL_TPB - 1u) / SL_TPB)), dim3(SL_TPB), 0, st, w0, w1, (uint32_t)n,
+                       (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
+    hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + ST_WORDS);
+    e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
     if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_N, hipMemcpyDeviceToHost, st);
     if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-    if (e1 != hipSuccess) {
-        vs_reads_free(ctx, r);
-        return stream_fail(ctx, s, VS_E_HIP, std::string("vs_fastq_stream_next: ") + hipGetErrorString(e1));
-    }
+    if (e1 != hipSuccess) return fail(e1);
     if (s->h_stat[ST_TOO_LONG] != 0xFFFFFFFFu) {
         const uint32_t e = s->h_stat[ST_TOO_LONG];
         const int f = (int)(e & 1u);
@@ -1078,52 +1039,14 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
         return stream_fail(ctx, s, VS_E_RANGE, msg);
     }
     const uint64_t words = s->h_stat[ST_WORDS];
-    r->n_words = words;
+    const size_t cut[2] = {s->h_stat[ST_CUT + 0], s->h_stat[ST_CUT + 1]};
     r->max_len = s->h_stat[ST_MAXLEN];
-    const size_t b_words = sizeof(uint32_t) * (words + VS_PAD_WORDS);
-    r->d_words = vs_cache_alloc(ctx, b_words);
-    void *d_mask = vs_cache_alloc(ctx, b_words);
-    r->bytes = b_woff + b_meta + b_words;
-    if (!r->d_words || !d_mask) {
-        if (d_mask) vs_cache_release(ctx, d_mask);
-        vs_reads_free(ctx, r);
-        return stream_fail(ctx, s, VS_E_OOM, "vs_fastq_stream_next: device buffers for the block");
-    }
-    e1 = hipMemsetAsync((uint32_t *)r->d_words + words, 0, sizeof(uint32_t) * VS_PAD_WORDS, st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync((uint32_t *)d_mask + words, 0, sizeof(uint32_t) * VS_PAD_WORDS, st);
-    if (e1 == hipSuccess) {
-        if (words)
-            hipLaunchKernelGGL(k_sl_pack, dim3((unsigned)((words + SL_TPB - 1u) / SL_TPB)), dim3(SL_TPB), 0, st, w0, w1, (uint32_t)n_ends,
-                               (uint32_t)words, (const uint32_t *)r->d_woff, (uint32_t *)r->d_words, (uint32_t *)d_mask, (uint32_t *)r->d_meta);
-        vs_launch_count_invalid(st, (const uint32_t *)r->d_meta, n_ends, s->d_stat + ST_INVALID);
-        e1 = hipGetLastError();
-    }
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_N, hipMemcpyDeviceToHost, st);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-    if (e1 == hipSuccess) {
-        r->n_invalid = s->h_stat[ST_INVALID];
-        if (r->n_invalid) {  // as vs_reads_pack: the mask and the position lists only when some end needs them
-            r->d_mask = d_mask;
-            d_mask = nullptr;
-            r->bytes += b_words;
-            r->d_inv4 = vs_cache_alloc(ctx, sizeof(uint32_t) * n_ends);
-            if (!r->d_inv4) e1 = hipErrorOutOfMemory;
-            else {
-                r->bytes += sizeof(uint32_t) * n_ends;
-                vs_launch_inv4(st, (const uint32_t *)r->d_woff, (const uint32_t *)r->d_mask, n_ends, (uint32_t *)r->d_meta, (uint32_t *)r->d_inv4);
-                e1 = hipGetLastError();
-            }
-        }
-    }
-    if (d_mask) vs_cache_release(ctx, d_mask);
-    size_t cut[2] = {s->h_stat[ST_CUT + 0], s->h_stat[ST_CUT + 1]};
-    for (int f = 0; f < 2 && e1 == hipSuccess; f++)
-        if (drop_front(ctx, s, f, cut[f], n) != VS_OK) e1 = hipErrorOutOfMemory;
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);  // (the block is complete when it is handed out)
-    if (e1 != hipSuccess) {
-        vs_reads_free(ctx, r);
-        return stream_fail(ctx, s, e1 == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, std::string("vs_fastq_stream_next: ") + hipGetErrorString(e1));
-    }
+    if ((e1 = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e1, no_buffers);
+    vs_launch_pack_lines(st, w0, w1, r);
+    if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + ST_INVALID, s->h_stat + ST_INVALID)) != hipSuccess) return fail(e1);
+    for (int f = 0; f < 2; f++)
+        if (drop_front(ctx, s, f, cut[f], n) != VS_OK) return fail(hipErrorOutOfMemory);
+    if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
     s->pairs += n;
     *out = r;
     *n_pairs = n;
