@@ -373,6 +373,29 @@ enum {
 };
 uint32_t vs_pe_last_launched(const vs_ctx *ctx);
 
+/* Testing aids (additions to ABI 10, like vs_index_export): the counter stage of a PE count alone, and the locus order of
+ * the most recent count, observed.
+ *   vs_pe_count_lists : the kernels between the mapping kernel and the matrices (k_mark_tiles, k_pe_accumulate, or the row
+ *       owners k_list_owners .. k_rows_sum) on a block of per-end node lists the caller made up.  No index, no reads: the
+ *       launch plan is the one vs_pe_count would make for n_nodes nodes and 2 * n_pairs ends of 150 bases at k = 55, with
+ *       the context's switches; the lists are written into the hand-off layout that plan names and the host code a real
+ *       count runs behind its mapping kernel is launched.  HOST pointers: lists = 2 * n_pairs rows of 20 words (left end,
+ *       right end of pair 0, of pair 1, ...), counts[2 * n_pairs] = nodes per row, 0 .. 20, handed over in the order
+ *       given.  DEVICE pointers: the matrices (n_nodes * n_nodes uint32 each, ADDED to) and d_tile_map (may be NULL; as
+ *       vs_pe_count_tracked).  VS_E_RANGE, nothing launched: a count above 20, a node >= n_nodes, a node twice in one
+ *       list, a tile of the plan (vs_pe_lists_ept ends) whose lists need more than ends * 4 quads of four nodes.
+ *       vs_pe_last_launched says VS_RAN_ROW_OWNERS as after a count.
+ *   vs_pe_lists_ept   : the read ends per tile of that plan on this context now (64 unless an experiment context says
+ *       otherwise): a caller keeps a tile's lists inside its region by closing it early with empty pairs.
+ *   vs_pe_last_order  : keys[i] = locus key of pair i, perm[j] = the pair the mapping kernel took j-th, of the most recent
+ *       vs_pe_count / vs_pe_map_ends, copied to HOST memory (at most cap of each; either may be NULL); changes nothing.
+ *       info[0] = pairs of that call, info[1] = the sort that ran: 0 none (input order; keys and perm are not written),
+ *       VS_RAN_LOCUS_LDS_SORT or VS_RAN_LOCUS_GLOBAL_SORT. */
+int vs_pe_count_lists(vs_ctx *ctx, uint32_t n_nodes, uint64_t n_pairs, const uint32_t *lists, const uint32_t *counts,
+                      uint32_t *d_node_mat, uint32_t *d_short_mat, uint8_t *d_tile_map);
+uint32_t vs_pe_lists_ept(vs_ctx *ctx);
+int vs_pe_last_order(vs_ctx *ctx, uint32_t *keys, uint32_t *perm, uint64_t cap, uint64_t info[2]);
+
 /* ---- graph stages: K5 PE-link table ---------------------------------------------------------
  * Replaces process_pe_info (utils/VStrains_IO.py:598-627) and every later read or rewrite of the
  * pe_info dict (utils/VStrains_Decomposition.py:141-143,178,273,492-503,608-617,672-684;

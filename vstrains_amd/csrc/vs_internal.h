@@ -148,6 +148,7 @@ struct vs_ctx {
     double last_ms[3] = {0, 0, 0};
     const char *last_kernel = "";  // mapping-kernel instantiation of the last vs_pe_count
     uint32_t last_launched = 0;    // VS_RAN_* bits: which optional kernels that call launched
+    uint64_t last_order_pairs = 0; // pairs of that call (vs_pe_last_order: d_locus_keys / d_perm hold their order if a sort ran)
     int n_cu = 256;
 };
 

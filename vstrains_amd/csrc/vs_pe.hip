@@ -42,7 +42,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <vector>
+
 #include "vs_internal.h"
+#include "vs_pe_pack.h"
 
 #define TPB 256
 // The hand-off between the mapping kernel and the counter kernels (r6): the accepted nodes of a tile's ends are PACKED --
@@ -2203,9 +2206,8 @@ __global__ void __launch_bounds__(TPB) k_dense_zero_cnt(uint32_t *dense, uint64_
 // vs_pe_plan (vs_pe_plan.h); what follows reserves, fills PeParams and launches from the plan.
 
 // The row-owner path: both counters of one block from the per-end lists (see "both matrices by ROW OWNERS").
-static int pe_count_by_rows(vs_ctx *ctx, const PePlan &pl, uint32_t *d_node_mat, uint32_t *d_short_mat, uint8_t *d_tile_map, uint32_t T) {
+static int pe_count_by_rows(vs_ctx *ctx, const PePlan &pl, uint32_t N, uint32_t *d_node_mat, uint32_t *d_short_mat, uint8_t *d_tile_map, uint32_t T) {
     hipStream_t st = ctx->stream;
-    const uint32_t N = ctx->idx.n_nodes;
     const uint64_t slots_pairs = pl.list_ends / 2, sub_pairs = pl.rows_sub_pairs;  // pairs per transposition
     // per mode: counts, cursors, offsets; then the block sums of the scan (2 048 values per block, 64 bits each)
     const uint64_t cap = (uint64_t)N + 2u;
@@ -2286,6 +2288,37 @@ static int pe_count_by_rows(vs_ctx *ctx, const PePlan &pl, uint32_t *d_node_mat,
     return VS_OK;
 }
 
+// Everything a count launches between the mapping kernel and the overflow kernels: both matrices of N nodes from the
+// hand-off in d_lists / d_list_counts (the layout the plan names, used_ends end slots written), by whichever counter
+// path the plan picked.  vs_pe_count runs this behind k_pe_tiles, vs_pe_count_lists behind lists the host wrote.
+static int pe_count_from_lists(vs_ctx *ctx, const PePlan &pl, uint32_t N, uint64_t used_ends, uint32_t *d_node_mat, uint32_t *d_short_mat,
+                               uint8_t *d_tile_map) {
+    hipStream_t st = ctx->stream;
+    const uint32_t T = (N + 63u) >> 6;
+    // the last tile may be partly empty: its unused rows must read as length 0
+    if (pl.list_ends > used_ends)
+        VS_HIP(ctx, hipMemsetAsync(ctx->d_list_counts.as<uint32_t>() + used_ends, 0, sizeof(uint32_t) * (pl.list_ends - used_ends), st));
+    const uint64_t slots_pairs = pl.list_ends / 2;
+    VS_HIP(ctx, hipEventRecord(ctx->ev[4], st));
+    if (pl.use_rows) {
+        const int rc = pe_count_by_rows(ctx, pl, N, d_node_mat, d_short_mat, d_tile_map, T);  // (zeroes its own queue words)
+        if (rc) return rc;
+        ctx->last_launched |= VS_RAN_ROW_OWNERS;
+    } else {
+        // (the chunks of pairs are not bound to workgroups: they are taken off a counter, see vs_pe_plan; the counter is a
+        // word of d_slow_count, which either caller zeroes whole before its count)
+        uint32_t *acc_queue = ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_ACC_QUEUE;
+        if (pl.mark_tiles)  // (timed with the counter kernel: it is part of the counting)
+            hipLaunchKernelGGL(k_mark_tiles, dim3((unsigned)((slots_pairs + 255u) / 256u)), dim3(256), 0, st, ctx->d_lists.as<const uint32_t>(),
+                               ctx->d_list_counts.as<const uint32_t>(), slots_pairs, d_tile_map, T, pl.ept);
+        VS_HIP(ctx, hipFuncSetAttribute((const void *)k_pe_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ACC_LDS_BYTES));
+        hipLaunchKernelGGL(k_pe_accumulate, dim3(pl.acc_grid), dim3(ACC_TPB), ACC_LDS_BYTES, st, ctx->d_lists.as<const uint32_t>(),
+                           ctx->d_list_counts.as<const uint32_t>(), slots_pairs, pl.acc_per_wg, N, pl.use_table, pl.acc_fill, d_node_mat,
+                           d_short_mat, acc_queue, pl.ept);
+    }
+    return VS_OK;
+}
+
 // The instantiations of k_pe_tiles by (MODE, SW, SP, AD), each with the name vs_pe_last_kernel returns for it; every
 // compile-time shape (VS_STD_SHAPES) exists with and without the adaptive step grid.
 struct TilesFn {
@@ -2307,6 +2340,7 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     const uint64_t n_pairs = reads->n_ends / 2;
     ctx->last_ms[0] = ctx->last_ms[1] = ctx->last_ms[2] = 0;
     ctx->last_launched = 0;
+    ctx->last_order_pairs = 0;
     // test hooks: fixed defaults unless the process runs with VS_EXPERIMENT=1 (see VsTuning)
     if (ctx->experiment) vs_tuning_load(ctx->tune, true);
     PePlanIn in;
@@ -2390,6 +2424,7 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     if (lds > 64u * 1024u)
         VS_HIP(ctx, hipFuncSetAttribute(tf->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     VS_HIP(ctx, hipEventRecord(ctx->ev[3], st));
+    ctx->last_order_pairs = n_pairs;
     if (pl.use_sort) {
         const uint64_t nk = pl.locus_keys;
         ctx->last_launched |= pl.lds_sort ? VS_RAN_LOCUS_LDS_SORT : VS_RAN_LOCUS_GLOBAL_SORT;
@@ -2433,27 +2468,8 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
         VS_HIP(ctx, hipLaunchKernel(tf->fn, dim3((unsigned)pl.grid), dim3(TTPB), kargs, lds, st));
     }
     if (d_node_mat) {
-        // the last tile may be partly empty: its unused rows must read as length 0
-        const uint64_t used_ends = 2ull * n_pairs;
-        if (pl.list_ends > used_ends)
-            VS_HIP(ctx, hipMemsetAsync(ctx->d_list_counts.as<uint32_t>() + used_ends, 0, sizeof(uint32_t) * (pl.list_ends - used_ends), st));
-        const uint64_t slots_pairs = pl.list_ends / 2;
-        VS_HIP(ctx, hipEventRecord(ctx->ev[4], st));
-        if (pl.use_rows) {
-            const int rc = pe_count_by_rows(ctx, pl, d_node_mat, d_short_mat, d_tile_map, P.tile_T);
-            if (rc) return rc;
-            ctx->last_launched |= VS_RAN_ROW_OWNERS;
-        } else {
-            // (the chunks of pairs are not bound to workgroups: they are taken off a counter, see vs_pe_plan)
-            uint32_t *acc_queue = ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_ACC_QUEUE;
-            if (pl.mark_tiles)  // (timed with the counter kernel: it is part of the counting)
-                hipLaunchKernelGGL(k_mark_tiles, dim3((unsigned)((slots_pairs + 255u) / 256u)), dim3(256), 0, st, ctx->d_lists.as<const uint32_t>(),
-                                   ctx->d_list_counts.as<const uint32_t>(), slots_pairs, d_tile_map, P.tile_T, pl.ept);
-            VS_HIP(ctx, hipFuncSetAttribute((const void *)k_pe_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ACC_LDS_BYTES));
-            hipLaunchKernelGGL(k_pe_accumulate, dim3(pl.acc_grid), dim3(ACC_TPB), ACC_LDS_BYTES, st, ctx->d_lists.as<const uint32_t>(),
-                               ctx->d_list_counts.as<const uint32_t>(), slots_pairs, pl.acc_per_wg, idx.n_nodes, pl.use_table, pl.acc_fill, d_node_mat,
-                               d_short_mat, acc_queue, pl.ept);
-        }
+        const int rc = pe_count_from_lists(ctx, pl, idx.n_nodes, 2ull * n_pairs, d_node_mat, d_short_mat, d_tile_map);
+        if (rc) return rc;
     }
     VS_HIP(ctx, hipEventRecord(ctx->ev[1], st));
     // overflow pairs: one wavefront per pair with its state in LDS first, the general kernel for what that cannot hold
@@ -2493,6 +2509,78 @@ extern "C" int vs_counts_zero_tracked(vs_ctx *ctx, uint32_t *d_node_mat, uint32_
     if (tiles > 0x7FFFFFFFull) return vs_fail(ctx, VS_E_RANGE, "vs_counts_zero_tracked: %u nodes make more tiles than one launch takes", n);
     hipLaunchKernelGGL(k_zero_tiles, dim3((unsigned)((tiles + 63u) / 64u)), dim3(64), 0, ctx->stream, d_node_mat, d_short_mat, n, T, d_tile_map, tiles);
     VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}
+
+// ---- testing aids: the counter stage alone, the locus order observed ---------------------------------------------------
+// The plan vs_pe_count would make for a block of n_ends ends of 150 bases at k = 55 on a graph of n_nodes nodes.
+static PePlan pe_lists_plan(vs_ctx *ctx, uint32_t n_nodes, uint64_t n_ends, bool tile_map) {
+    if (ctx->experiment) vs_tuning_load(ctx->tune, true);
+    PePlanIn in;
+    in.n_nodes = n_nodes; in.K = STD_K; in.w = STD_W; in.s = STD_S;
+    in.n_cu = (uint32_t)ctx->n_cu;
+    in.n_ends = n_ends; in.max_len = 150u;
+    in.count = true; in.tile_map = tile_map;
+    in.tune = ctx->tune;
+    return vs_pe_plan(in);
+}
+
+extern "C" uint32_t vs_pe_lists_ept(vs_ctx *ctx) { return ctx ? pe_lists_plan(ctx, 1u, 2u, false).ept : 0u; }
+
+extern "C" int vs_pe_count_lists(vs_ctx *ctx, uint32_t n_nodes, uint64_t n_pairs, const uint32_t *lists, const uint32_t *counts,
+                                 uint32_t *d_node_mat, uint32_t *d_short_mat, uint8_t *d_tile_map) {
+    if (!ctx) return VS_E_ARG;
+    if (n_pairs && (!lists || !counts || !d_node_mat || !d_short_mat)) return vs_fail(ctx, VS_E_ARG, "vs_pe_count_lists: bad argument");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    ctx->last_ms[0] = ctx->last_ms[1] = ctx->last_ms[2] = 0;
+    ctx->last_launched = 0;
+    ctx->last_order_pairs = 0;
+    ctx->last_kernel = "";
+    const PePlan pl = pe_lists_plan(ctx, n_nodes, 2u * n_pairs, d_tile_map != nullptr);
+    if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "%s", pl.msg);
+    if (!pl.n_tiles) return VS_OK;  // an empty block
+    std::vector<uint32_t> h_lists(pl.list_words), h_counts(pl.list_ends);
+    char msg[128];
+    const int prc = vs_pe_pack_lists(n_nodes, n_pairs, lists, counts, pl.ept, pl.list_ends, pl.use_rows != 0u, h_lists.data(), h_counts.data(), msg, sizeof msg);
+    if (prc != VS_OK) return vs_fail(ctx, prc, "vs_pe_count_lists: %s", msg);
+    VS_HIP(ctx, ctx->d_slow_count.reserve(sizeof(uint32_t) * vs_ctx::SC_WORDS));
+    VS_HIP(ctx, ctx->d_lists.reserve(sizeof(uint32_t) * pl.list_words));
+    VS_HIP(ctx, ctx->d_list_counts.reserve(sizeof(uint32_t) * (pl.list_ends + 2)));
+    // (as pe_launch does before every count: the queue word of k_pe_accumulate, the overflow count vs_pe_last_timing reads)
+    VS_HIP(ctx, hipMemsetAsync(ctx->d_slow_count.ptr(), 0, sizeof(uint32_t) * vs_ctx::SC_WORDS, st));
+    VS_HIP(ctx, hipEventRecord(ctx->ev[3], st));
+    VS_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    // (the host writes what k_pe_tiles writes: the used end slots; the rest of the last tile is the shared code's)
+    // The copies are waited for before anything can return: h_lists / h_counts are pageable and die with this frame.
+    const hipError_t e_lists = hipMemcpyAsync(ctx->d_lists.ptr(), h_lists.data(), sizeof(uint32_t) * pl.list_words, hipMemcpyHostToDevice, st);
+    const hipError_t e_counts = hipMemcpyAsync(ctx->d_list_counts.ptr(), h_counts.data(), sizeof(uint32_t) * 2u * n_pairs, hipMemcpyHostToDevice, st);
+    const hipError_t e_sync = hipStreamSynchronize(st);
+    VS_HIP(ctx, e_lists);
+    VS_HIP(ctx, e_counts);
+    VS_HIP(ctx, e_sync);
+    int rc = pe_count_from_lists(ctx, pl, n_nodes, 2ull * n_pairs, d_node_mat, d_short_mat, d_tile_map);
+    if (rc == VS_OK) {
+        VS_HIP(ctx, hipEventRecord(ctx->ev[1], st));
+        VS_HIP(ctx, hipEventRecord(ctx->ev[2], st));
+        VS_HIP(ctx, hipGetLastError());
+    }
+    VS_HIP(ctx, hipStreamSynchronize(st));  // (the aid returns with the counters written)
+    return rc;
+}
+
+extern "C" int vs_pe_last_order(vs_ctx *ctx, uint32_t *keys, uint32_t *perm, uint64_t cap, uint64_t info[2]) {
+    if (!ctx || !info) return VS_E_ARG;
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = ctx->last_order_pairs;
+    const uint32_t sort = ctx->last_launched & (VS_RAN_LOCUS_LDS_SORT | VS_RAN_LOCUS_GLOBAL_SORT);
+    info[0] = n;
+    info[1] = sort;
+    const uint64_t m = n < cap ? n : cap;
+    if (!sort || !m) return VS_OK;
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (keys) VS_HIP(ctx, hipMemcpy(keys, ctx->d_locus_keys.ptr(), sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    if (perm) VS_HIP(ctx, hipMemcpy(perm, ctx->d_perm.ptr(), sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
     return VS_OK;
 }
 

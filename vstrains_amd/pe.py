@@ -539,6 +539,34 @@ def node_order(seqs: Sequence[str], ksize: int, _encoded=None) -> np.ndarray:
     return order[: len(seqs)].astype(np.int64)
 
 
+LIST_CAP = 20  # nodes a read end may list on the main path of a count (LCAP of the kernels)
+
+
+def list_block(pairs, ept: int = 64) -> Tuple[np.ndarray, np.ndarray]:
+    """``pairs`` (sequences of (left list, right list), node numbers in any order) as the arrays ``pe_count_lists``
+    takes: uint32 [2 P, 20] and [2 P].  A tile of ``ept`` ends holds ``ept * 4`` quads of four nodes; where the next
+    pair would not fit, the tile is closed with empty pairs (both counts 0) -- they are part of the block that comes
+    back, so that every layout and every model see the same one."""
+    ppt, cap_q = ept // 2, ept * 4
+    rows, used_p, used_q = [], 0, 0
+    for left, right in pairs:
+        q = (len(left) + 3) // 4 + (len(right) + 3) // 4
+        if used_p == ppt or used_q + q > cap_q:
+            rows += [()] * (2 * (ppt - used_p) if used_p < ppt else 0)
+            used_p = used_q = 0
+        rows += [left, right]
+        used_p += 1
+        used_q += q
+    lists = np.full((max(len(rows), 1), LIST_CAP), 0xFFFFFFFF, dtype=np.uint32)
+    counts = np.zeros(max(len(rows), 1), dtype=np.uint32)
+    for e, row in enumerate(rows):
+        if len(row) > LIST_CAP:
+            raise ValueError("end %d lists %d nodes, at most %d" % (e, len(row), LIST_CAP))
+        counts[e] = len(row)
+        lists[e, : len(row)] = row
+    return lists[: len(rows)], counts[: len(rows)]
+
+
 # ---- device objects ------------------------------------------------------------------------------
 class ReadBlock:
     def __init__(self, ctx: "Context", handle):
@@ -740,6 +768,42 @@ class Context:
     def last_launched(self) -> int:
         """VS_RAN_* bits: which optional kernels the most recent ``pe_count`` launched."""
         return int(nat.lib().vs_pe_last_launched(self._h))
+
+    @property
+    def lists_ept(self) -> int:
+        """Read ends per tile of the plan ``pe_count_lists`` makes on this context now (``vs_pe_lists_ept``)."""
+        return int(nat.lib().vs_pe_lists_ept(self._h))
+
+    def list_block(self, pairs) -> Tuple[np.ndarray, np.ndarray]:
+        """``list_block`` with this context's tile size."""
+        return list_block(pairs, self.lists_ept)
+
+    def pe_count_lists(self, n_nodes: int, lists: np.ndarray, counts: np.ndarray, node_mat_ptr: int, short_mat_ptr: int,
+                       tile_map_ptr: Optional[int] = None):
+        """The counter stage alone (a test aid, ``vs_pe_count_lists``): the per-end node lists ``lists`` uint32 [2 P, 20] /
+        ``counts`` uint32 [2 P], in the order given, added to the device matrices of ``n_nodes`` nodes by the kernels a real
+        count runs behind its mapping kernel.  Refused (``NativeError``, VS_E_RANGE): what ``list_block`` would not make."""
+        lists = np.ascontiguousarray(lists, dtype=np.uint32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        if lists.ndim != 2 or lists.shape[1] != LIST_CAP or lists.shape[0] != counts.size or counts.size % 2:
+            raise ValueError("lists [2 P, %d] and counts [2 P]" % LIST_CAP)
+        nat.check(self._h, nat.lib().vs_pe_count_lists(self._h, n_nodes, counts.size // 2, lists.ctypes.data, counts.ctypes.data,
+                                                       C.c_void_p(node_mat_ptr), C.c_void_p(short_mat_ptr),
+                                                       C.c_void_p(tile_map_ptr) if tile_map_ptr is not None else None))
+
+    def last_order(self):
+        """The locus order of the most recent count (a test aid, ``vs_pe_last_order``): (keys uint32 [P] by pair, perm uint32
+        [P] = the pairs in the order the mapping kernel took them, which sort ran: 0 none -- then both arrays are empty --
+        ``RAN_LOCUS_LDS_SORT`` or ``RAN_LOCUS_GLOBAL_SORT``, pairs of that count)."""
+        info = (C.c_uint64 * 2)()
+        nat.check(self._h, nat.lib().vs_pe_last_order(self._h, None, None, 0, info))
+        n, sort = int(info[0]), int(info[1])
+        m = n if sort else 0
+        keys = np.zeros(max(m, 1), dtype=np.uint32)
+        perm = np.zeros(max(m, 1), dtype=np.uint32)
+        if m:
+            nat.check(self._h, nat.lib().vs_pe_last_order(self._h, keys.ctypes.data, perm.ctypes.data, m, info))
+        return keys[:m], perm[:m], sort, n
 
     def map_ends(self, reads: ReadBlock, cap: int = 64) -> List[List[int]]:
         n = reads.info["ends"]
