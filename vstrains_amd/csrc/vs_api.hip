@@ -29,6 +29,7 @@ void vs_tuning_load(VsTuning &t, bool experiment) {
     if (const char *v = getenv("VS_EPT")) t.ept = (uint32_t)atoi(v) & ~1u;
     if (const char *v = getenv("VS_GRID_PER_CU")) t.grid_per_cu = atoi(v) > 0 ? (uint32_t)atoi(v) : 128u;
     if (const char *v = getenv("VS_ACC_FILL")) t.acc_fill_pct = atoi(v);
+    if (const char *v = getenv("VS_ACC_TASKS")) t.acc_tasks = atoi(v) > 0 ? (uint32_t)atoi(v) : 0u;
     if (const char *v = getenv("VS_SHORTCUT")) t.shortcut = atoi(v) != 0 ? 1 : 0;
     if (const char *v = getenv("VS_ADAPT_GRID")) t.adapt_grid = atoi(v) != 0 ? 1 : 0;
     if (const char *v = getenv("VS_ACC_ROWS")) t.acc_rows = atoi(v) != 0 ? 1 : 0;

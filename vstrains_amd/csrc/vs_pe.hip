@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "vs_internal.h"
+#include "vs_acc_tasks.h"
 #include "vs_pe_pack.h"
 
 #define TPB 256
@@ -1020,18 +1021,13 @@ k_pe_tiles(PeParams P) {
 // at configs[2]), so increments are summed per cell in LDS before they reach memory.  Two loop orders:
 //   * k_pe_accumulate (graphs of at most 46 340 nodes): pair-major.  A workgroup (1024 threads, one per CU, a
 //     contiguous run of pairs = a few loci) sums in a 16k-slot cell table and issues ONE global atomic per cell when the
-//     table is written out.  One wavefront expands 64 pairs at a time, one lane per run of at most four increments.
+//     table is written out.  One wavefront takes 64 pairs at a time and counts them as TASKS, one per matrix row
+//     (vs_acc_tasks.h), one lane per task, the tasks of a batch of pairs ordered by length.
 //   * the row owners below (larger graphs): output-major.  There a round of locus-ordered pairs brings more distinct
 //     cells than the table holds, and the same cell returns from loci hundreds of rounds apart.
-#define ACC_LDS_BYTES ((2u * ACC_SLOTS + (ACC_TPB / 64) * 66u + (LCAP + 1u) + (LCAP + 1u) * ACC_GMAX + 4u) * 4u)
-// Work units: a list row is cut into runs of at most ACC_RUN partners, one lane per run, so that
-// every lane of a wavefront has about the same (small, fully unrolled) amount of work:
-//   node_mat : left node a against right positions [4c, 4c+4)           -> nl * ceil(nr/4) runs
-//   short_mat: list position a against positions [a+4c, a+4c+4) (b >= a) -> g(n) runs per list,
-//              g(n) = sum_{m=1..n} ceil(m/4)
-#define ACC_RUN 4u   // (runs of 8, two 16-byte partner loads per run, were measured in r5: profiles/EXPERIMENTS.md)
-#define ACC_GMAX 60u  // g(LCAP = 20)
-#define ACC_PPW 64u   // pairs per wavefront and round: one per lane
+// LDS of k_pe_accumulate: the cell table, per wavefront a region of task entries and the counters of their sort, four words
+#define ACC_LDS_BYTES ((2u * ACC_SLOTS + (ACC_TPB / 64) * (ACC_TASK_WORDS + ACC_BINS) + 4u) * 4u)
+static_assert(ACC_LDS_BYTES <= 160u * 1024u, "k_pe_accumulate: one workgroup per CU");
 // The cell table: 16 k slots, 32-bit keys (k_pe_accumulate: mat * N*N + x * N + y, while 2*N*N fits 32 bits, N <= 46340;
 // the row owners: cell index relative to the strip's first row).  The 16 cells of one 64-byte stretch of a matrix row
 // sit in 16 NEIGHBOURING slots (the hash picks a group of 16 slots from the key >> 4, the low four bits pick the slot
@@ -1067,34 +1063,46 @@ __device__ __forceinline__ bool vs_cell_claim(uint32_t *s_key, uint32_t *s_cnt, 
     return false;
 }
 
+// (the same wavefront writes and reads its own task region: no workgroup barrier, only the LDS wait)
+__device__ __forceinline__ void vs_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// k_pe_accumulate, per round of 64 pairs of a wavefront (lane = pair):
+//   batch  the longest run of the round's next pairs whose tasks fit the wavefront's task region (task_cap entries; a pair
+//          has at most 40 tasks, so a batch holds at least one pair): a wavefront scan of the pairs' task counts
+//   sort   every lane writes its pair's tasks, 16 bits each (vs_acc_task_entry), placed by a counting sort on their turns,
+//          longest first: per pair at most eleven LDS atomics into the wavefront's counters (the node rows of a pair have
+//          one length, the folded short rows of a list four -- vs_acc_fold_class -- its middle row one), a scan over the
+//          counters, then plain stores
+//   count  windows of 64 consecutive tasks, one per lane.  A lane decodes its entry ONCE (pair -> the lengths and places of
+//          its lists by one cross-lane read, kind and position -> x, partner list, partner stretches) and walks its
+//          partners in blocks of four list words -- one 16-byte load at the word the block starts at, issued one block
+//          ahead; the decode, x and first block of the NEXT window are issued before this window is counted, so no global
+//          load is waited on.  A turn is one key, one slot read, one add or claim; the four turns of a block read their
+//          slots together, as the runs of four did.  A window ends with its longest task, which the order makes nearly
+//          every lane's end.
+// gfx950 (hipcc -O3, -Rpass-analysis=kernel-resource-usage): 122 VGPRs, 0 B of scratch, ACC_LDS_BYTES = 163 344 B of the CU's 163 840 B
+// of LDS: one workgroup of sixteen wavefronts per CU, four per SIMD (which 128 VGPRs allow).
 __global__ void __launch_bounds__(ACC_TPB)
 k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ counts, uint64_t n_slots_pairs,
-                uint32_t pairs_per_wg, uint32_t N, uint32_t use_table, uint32_t fill_limit,
+                uint32_t pairs_per_wg, uint32_t N, uint32_t use_table, uint32_t fill_limit, uint32_t task_cap,
                 uint32_t *__restrict__ node_mat, uint32_t *__restrict__ short_mat, uint32_t *__restrict__ queue, uint32_t ept) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
     uint32_t *s_key = vs_lds;                      // [ACC_SLOTS]
     uint32_t *s_cnt = vs_lds + ACC_SLOTS;          // [ACC_SLOTS]
-    uint32_t(*s_pref)[66] = (uint32_t(*)[66])(vs_lds + 2u * ACC_SLOTS);  // [ACC_TPB / 64][66]
-    uint32_t *s_g = vs_lds + 2u * ACC_SLOTS + (ACC_TPB / 64) * 66u;      // [LCAP + 1]: g(n)
-    uint32_t *s_ua = s_g + (LCAP + 1u);                                   // [LCAP + 1][ACC_GMAX]: run -> position a
-    uint32_t &s_used = s_ua[(LCAP + 1u) * ACC_GMAX];
-    uint32_t &s_lost = s_ua[(LCAP + 1u) * ACC_GMAX + 1u];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    uint32_t *s_bin = vs_lds + 2u * ACC_SLOTS + wv * (ACC_TASK_WORDS + ACC_BINS);  // [ACC_BINS] of this wavefront
+    uint16_t *s_task = (uint16_t *)(s_bin + ACC_BINS);                             // [ACC_TASK_CAP]
+    uint32_t *s_misc = vs_lds + 2u * ACC_SLOTS + (ACC_TPB / 64) * (ACC_TASK_WORDS + ACC_BINS);
+    uint32_t &s_used = s_misc[0], &s_lost = s_misc[1], &s_chunk = s_misc[2];
     const uint32_t NN = N * N;  // (use_table: 2 * N * N fits 32 bits)
     for (uint32_t i = tid; i < ACC_SLOTS; i += ACC_TPB) { s_key[i] = Acc32::EMPTY; s_cnt[i] = 0; }
-    if (tid <= LCAP) {
-        uint32_t gsum = 0;
-        for (uint32_t m = 1; m <= tid; m++) gsum += (m + ACC_RUN - 1u) / ACC_RUN;
-        s_g[tid] = gsum;
-        // runs of an n-list in order: position a = 0 first (n - a partners), then a = 1, ...
-        uint32_t r = 0;
-        for (uint32_t a2 = 0; a2 < tid; a2++)
-            for (uint32_t c = 0; c < (tid - a2 + ACC_RUN - 1u) / ACC_RUN; c++) s_ua[tid * ACC_GMAX + r++] = a2;
-    }
     if (tid == 0) { s_used = 0; s_lost = 0; }
     __syncthreads();
     // chunks of pairs_per_wg pairs: whichever chunk is next when this workgroup is free -- the table lives across chunks
     // and is written out on fill only
-    uint32_t &s_chunk = s_ua[(LCAP + 1u) * ACC_GMAX + 2u];
     const uint32_t ppt = ept >> 1, region_q = (ept * LC) >> 2;  // pairs per tile of the mapping kernel; quads of a tile's region
     // every cell of the table to its counter (one global atomic per cell), the table emptied
     auto write_out = [&]() {
@@ -1133,100 +1141,139 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
             const uint32_t tq = (rem0 + lane) / ppt * region_q;
             packed = nl | nr << 5 | (tq + (c.x >> 8)) << 10 | (tq + (c.y >> 8)) << 21;
         }
-        const uint32_t u = nl * ((nr + ACC_RUN - 1u) / ACC_RUN) + s_g[nl] + s_g[nr];
-        const uint32_t incl = vs_wave_scan_add(u);
-        s_pref[wv][lane + 1u] = incl;
-        if (lane == 0) s_pref[wv][0] = 0;
-        if (lane == 63u) s_pref[wv][65] = 0xFFFFFFFFu;  // sentinel: the look-ahead below never runs off
-        const uint32_t U = __shfl(incl, 63, 64);
-        // (the same wavefront wrote and reads s_pref: no workgroup barrier, only the LDS wait)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        uint32_t cur = 0;  // wave-uniform: first pair whose runs reach into the current window
-        // One window of 64 runs: which pair and which of its runs a lane takes, the run's first node and
-        // its (up to) four partners.  The two list loads of window i+1 are issued before window i is
-        // counted, so their round trip (L2) is covered by the cell-table work instead of preceding it.
-        struct Run {
-            uint32_t x, mat, bi, be;
-            VsQuad yq;
-            bool ok;
-        };
-        auto fetch = [&](uint32_t t0) {
-            Run R;
-            while (s_pref[wv][cur + 1u] <= t0) cur++;
-            const uint32_t t_raw = t0 + lane;
-            const uint32_t t = t_raw < U ? t_raw : U - 1u;  // (lanes past the end ride along, their result is dropped)
-            uint32_t a0 = cur;  // last pair of this wavefront with pref <= t
-            a0 += s_pref[wv][a0 + 1u] <= t ? 1u : 0u;
-            a0 += s_pref[wv][a0 + 1u] <= t ? 1u : 0u;
-            a0 += s_pref[wv][a0 + 1u] <= t ? 1u : 0u;
-            while (s_pref[wv][a0 + 1u] <= t) a0++;
-            uint32_t r = t - s_pref[wv][a0];
-            // list lengths and places of pair a0: lane a0 holds them (ONE cross-lane read, no memory round trip)
-            const uint32_t pk = __shfl(packed, (int)a0, 64);
-            const uint32_t ql = pk & 31u, qr = (pk >> 5) & 31u, rowl = ((pk >> 10) & 0x7FFu) << 2, rowr = (pk >> 21) << 2;
-            R.ok = t_raw < U;
-            const uint32_t cq = (qr + ACC_RUN - 1u) / ACC_RUN;
-            uint32_t off;
-            if (r < ql * cq) {  // node_mat: left node a, right positions of run c
-                const uint32_t a = cq == 1u ? r : cq == 2u ? r >> 1 : cq == 4u ? r >> 2 : cq == 3u ? (r * 43691u) >> 17 : (r * 52429u) >> 18;
-                R.x = wlists[rowl + a]; R.mat = 0u; off = rowr; R.bi = ACC_RUN * (r - a * cq); R.be = qr;
-            } else {
-                r -= ql * cq;
-                uint32_t n = ql;
-                off = rowl;
-                const uint32_t gl = s_g[ql];
-                if (r >= gl) { r -= gl; n = qr; off = rowr; }
-                const uint32_t a = s_ua[n * ACC_GMAX + r];
-                const uint32_t crun = r - (s_g[n] - s_g[n - a]);  // runs of positions before a: g(n) - g(n-a)
-                R.x = wlists[off + a]; R.mat = 1u; R.bi = a + ACC_RUN * crun; R.be = n;
-            }
-            // up to ACC_RUN partners, loaded together (reading a few words past `be` -- the list's padding, the next
-            // list -- stays inside the lists buffer, which carries padding at its end, and is ignored)
-            R.yq = *(const VsQuad *)(wlists + off + R.bi);  // one 16-byte load
-            return R;
-        };
-        // (r6: the list loads of two and three windows ahead instead of one were measured -- 2.23 / 2.25 / 2.31 ms at configs[2]: the
-        // kernel does not wait on these loads; profiles/EXPERIMENTS.md)
-        Run nxt;
-        nxt.ok = false;
-        if (U) nxt = fetch(0u);
-        for (uint32_t t0 = 0; t0 < U; t0 += 64u) {
-            const Run c = nxt;
-            if (t0 + 64u < U) nxt = fetch(t0 + 64u);
-            if (!c.ok) continue;
-            const uint32_t x = c.x, mat = c.mat, bi = c.bi, be = c.be;
-            const uint32_t ys[ACC_RUN] = {c.yq.x, c.yq.y, c.yq.z, c.yq.w};
-            if (use_table) {
-                // the four cells' slots are read together (independent LDS loads), then counted; a
-                // slot that does not hold the cell yet goes the slow way (claim / probe / global)
-                uint32_t key[ACC_RUN], seen[ACC_RUN], at[ACC_RUN];
+        const uint32_t my_tasks = vs_acc_pair_tasks(nl, nr);
+        for (uint32_t first = 0; first < ACC_PPW;) {  // the batches of the round (wave-uniform)
+            const uint32_t incl = vs_wave_scan_add(lane >= first ? my_tasks : 0u);
+            const uint32_t last = (uint32_t)__popcll(__ballot(vs_acc_batch_fits(incl, task_cap)));  // (the lanes that fit are a prefix)
+            const uint32_t U = (uint32_t)__builtin_amdgcn_readlane((int)incl, (int)last - 1);  // tasks of the batch
+            const bool mine = lane >= first && lane < last;
+            first = last;
+            if (!U) continue;
+            // ---- sort: counters per partner count, then the places, longest first
+            if (lane < ACC_BINS) s_bin[lane] = 0u;
+            vs_wave_lds_sync();
+            uint32_t o_n = 0, o_lm = 0, o_rm = 0, o_l[4], o_r[4];  // this pair's places among the tasks of one length
+            if (mine) {
+                if (nl && nr) o_n = atomicAdd(&s_bin[nr], nl);
+                if (nl & 1u) o_lm = atomicAdd(&s_bin[(nl + 1u) >> 1], 1u);
+                if (nr & 1u) o_rm = atomicAdd(&s_bin[(nr + 1u) >> 1], 1u);
 #pragma unroll
-                for (uint32_t j = 0; j < ACC_RUN; j++) {
-                    const uint32_t yv = ys[j];
-                    const uint32_t cx = (mat && yv < x) ? yv : x, cy = (mat && yv < x) ? x : yv;
-                    key[j] = Acc32::key(mat, cx, cy, N);
-                    at[j] = Acc32::slot(key[j]);
-                    seen[j] = s_key[at[j]];
+                for (uint32_t r = 0; r < 4u; r++) {
+                    const VsAccClass cl = vs_acc_fold_class(nl, r), cr = vs_acc_fold_class(nr, r);
+                    o_l[r] = cl.cnt ? atomicAdd(&s_bin[cl.turns], cl.cnt) : 0u;
+                    o_r[r] = cr.cnt ? atomicAdd(&s_bin[cr.turns], cr.cnt) : 0u;
                 }
+            }
+            vs_wave_lds_sync();
+            {
+                const uint32_t v = lane < ACC_BINS ? s_bin[ACC_BINS - 1u - lane] : 0u;
+                const uint32_t before = vs_wave_scan_add(v) - v;
+                if (lane < ACC_BINS) s_bin[ACC_BINS - 1u - lane] = before;  // (every lane rewrites the counter it read)
+            }
+            vs_wave_lds_sync();
+            if (mine) {
+                if (nl && nr) {
+                    const uint32_t at = s_bin[nr] + o_n;
+                    for (uint32_t a = 0; a < nl; a++) s_task[at + a] = vs_acc_task_entry(lane, VS_ACC_NODE, a);
+                }
+                if (nl & 1u) s_task[s_bin[(nl + 1u) >> 1] + o_lm] = vs_acc_task_entry(lane, VS_ACC_LEFT, nl >> 1);
+                if (nr & 1u) s_task[s_bin[(nr + 1u) >> 1] + o_rm] = vs_acc_task_entry(lane, VS_ACC_RIGHT, nr >> 1);
+                // (the classes are worked out again from laundered lengths: kept from above they cost 24 registers and scratch)
+                uint32_t nl2 = nl, nr2 = nr;
+                asm volatile("" : "+v"(nl2), "+v"(nr2));
 #pragma unroll
-                for (uint32_t j = 0; j < ACC_RUN; j++) {
-                    if (bi + j >= be) continue;  // (j = 0 always counts)
-                    if (seen[j] == key[j]) {
-                        atomicAdd(&s_cnt[at[j]], 1u);
-                    } else if (!vs_cell_claim<Acc32>(s_key, s_cnt, &s_used, key[j], at[j], 1u)) {
-                        atomicAdd(&s_lost, 1u);
-                        atomicAdd(key[j] >= NN ? short_mat + (key[j] - NN) : node_mat + key[j], 1u);
+                for (uint32_t r = 0; r < 4u; r++) {
+                    const VsAccClass cl = vs_acc_fold_class(nl2, r), cr = vs_acc_fold_class(nr2, r);
+                    if (cl.cnt) {
+                        const uint32_t at = s_bin[cl.turns] + o_l[r];
+                        for (uint32_t i = 0; i < cl.cnt; i++) s_task[at + i] = vs_acc_task_entry(lane, VS_ACC_LEFT, cl.a0 + 4u * i);
+                    }
+                    if (cr.cnt) {
+                        const uint32_t at = s_bin[cr.turns] + o_r[r];
+                        for (uint32_t i = 0; i < cr.cnt; i++) s_task[at + i] = vs_acc_task_entry(lane, VS_ACC_RIGHT, cr.a0 + 4u * i);
                     }
                 }
-            } else {
-                // (VS_NO_AGG=1: every increment a global atomic)
+            }
+            vs_wave_lds_sync();
+            // ---- count.  A lane's task, decoded: x (a node row's; a short row takes the first word of either stretch),
+            // the partner list, the position the next block starts at, the stretches (vs_acc_tasks.h), the first block.
+            struct Task {
+                uint32_t x, mat, off, p, p2, e, turns;
+                VsQuad q;
+            };
+            auto decode = [&](uint32_t t0) {
+                Task T;
+                const uint32_t w = t0 + lane < U ? s_task[t0 + lane] : 0u;  // (0: no task, no turns, every load at the region's first word)
+                const uint32_t kind = vs_acc_entry_kind(w), a = vs_acc_entry_a(w);
+                // list lengths and places of the task's pair: the lane of that pair holds them (ONE cross-lane read, no memory round trip)
+                const uint32_t pk = __shfl(packed, (int)vs_acc_entry_pair(w), 64);
+                const uint32_t ql = pk & 31u, qr = (pk >> 5) & 31u, rowl = ((pk >> 10) & 0x7FFu) << 2, rowr = (pk >> 21) << 2;
+                const VsAccSegs s = w ? vs_acc_task_segs(kind, a, ql, qr) : VsAccSegs{0u, 0u, 0u};
+                T.turns = vs_acc_turns(s);
+                T.mat = kind != VS_ACC_NODE ? 1u : 0u;
+                T.off = !w ? 0u : kind == VS_ACC_LEFT ? rowl : rowr;
+                T.p = s.p1; T.p2 = s.p2; T.e = s.e;
+                T.x = 0u;
+                if (w && kind == VS_ACC_NODE) T.x = wlists[rowl + a];
+                // (reading a few words past `e` -- the list's padding, the next list -- stays inside the lists buffer, which
+                // carries padding at its end, and is ignored)
+                T.q = *(const VsQuad *)(wlists + T.off + T.p);  // one 16-byte load
+                return T;
+            };
+            Task nxt = decode(0u);
+            for (uint32_t t0 = 0; t0 < U; t0 += 64u) {
+                const Task c = nxt;
+                if (t0 + 64u < U) nxt = decode(t0 + 64u);
+                const uint32_t tmax = (uint32_t)__builtin_amdgcn_readlane((int)vs_wave_scan_max(c.turns), 63);  // the window's longest task (wave-uniform)
+                const uint32_t mat = c.mat, e = c.e;
+                const uint32_t *plist = wlists + c.off;
+                uint32_t x = c.x, p = c.p, p2 = c.p2;
+                bool fresh = true;  // the block begins a stretch
+                VsQuad q = c.q;
+                for (uint32_t t = 0; t < tmax; t += 4u) {
+                    const uint32_t ys[4] = {q.x, q.y, q.z, q.w};
+                    if (mat && fresh) x = ys[0];
+                    const uint32_t pb = p;
+                    // the next block: on in this stretch, or the first of the second one, or none (p = e)
+                    p += 4u;
+                    fresh = p >= e;
+                    if (fresh) { p = p2; p2 = e; }
+                    if (t + 4u < tmax) q = *(const VsQuad *)(plist + p);
+                    const uint32_t left = tmax - t;  // turns of the window still to come (wave-uniform)
+                    if (use_table) {
+                        // the block's cells' slots are read together (independent LDS loads), then counted; a
+                        // slot that does not hold the cell yet goes the slow way (claim / probe / global)
+                        uint32_t key[4], seen[4], at[4];
 #pragma unroll
-                for (uint32_t j = 0; j < ACC_RUN; j++) {
-                    if (bi + j >= be) continue;
-                    const uint32_t yv = ys[j];
-                    const uint32_t cx = (mat && yv < x) ? yv : x, cy = (mat && yv < x) ? x : yv;
-                    atomicAdd((mat ? short_mat : node_mat) + (uint64_t)cx * N + cy, 1u);
+                        for (uint32_t j = 0; j < 4u; j++) {
+                            if (j >= left) break;
+                            const uint32_t yv = ys[j];
+                            const uint32_t cx = (mat && yv < x) ? yv : x, cy = (mat && yv < x) ? x : yv;
+                            key[j] = Acc32::key(mat, cx, cy, N);
+                            at[j] = Acc32::slot(key[j]);
+                            seen[j] = s_key[at[j]];
+                        }
+#pragma unroll
+                        for (uint32_t j = 0; j < 4u; j++) {
+                            if (j >= left) break;
+                            if (pb + j >= e) continue;
+                            if (seen[j] == key[j]) {
+                                atomicAdd(&s_cnt[at[j]], 1u);
+                            } else if (!vs_cell_claim<Acc32>(s_key, s_cnt, &s_used, key[j], at[j], 1u)) {
+                                atomicAdd(&s_lost, 1u);
+                                atomicAdd(key[j] >= NN ? short_mat + (key[j] - NN) : node_mat + key[j], 1u);
+                            }
+                        }
+                    } else {
+                        // (VS_NO_AGG=1: every increment a global atomic)
+#pragma unroll
+                        for (uint32_t j = 0; j < 4u; j++) {
+                            if (pb + j >= e) continue;
+                            const uint32_t yv = ys[j];
+                            const uint32_t cx = (mat && yv < x) ? yv : x, cy = (mat && yv < x) ? x : yv;
+                            atomicAdd((mat ? short_mat : node_mat) + (uint64_t)cx * N + cy, 1u);
+                        }
+                    }
                 }
             }
         }
@@ -2313,7 +2360,7 @@ static int pe_count_from_lists(vs_ctx *ctx, const PePlan &pl, uint32_t N, uint64
                                ctx->d_list_counts.as<const uint32_t>(), slots_pairs, d_tile_map, T, pl.ept);
         VS_HIP(ctx, hipFuncSetAttribute((const void *)k_pe_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ACC_LDS_BYTES));
         hipLaunchKernelGGL(k_pe_accumulate, dim3(pl.acc_grid), dim3(ACC_TPB), ACC_LDS_BYTES, st, ctx->d_lists.as<const uint32_t>(),
-                           ctx->d_list_counts.as<const uint32_t>(), slots_pairs, pl.acc_per_wg, N, pl.use_table, pl.acc_fill, d_node_mat,
+                           ctx->d_list_counts.as<const uint32_t>(), slots_pairs, pl.acc_per_wg, N, pl.use_table, pl.acc_fill, pl.acc_task_cap, d_node_mat,
                            d_short_mat, acc_queue, pl.ept);
     }
     return VS_OK;
