@@ -1,7 +1,9 @@
 """String-level model of the device algorithm (seeds at stride s from the end's phase, canonical w-mer table, exact
 extension, first-seed-owns-the-match rule).  It exists to pin the *algorithm* of
 vstrains_amd/csrc/vs_pe.hip against the oracle on the CPU, where no GPU is available; the HIP
-kernels themselves are checked against the oracle in the -m gpu tests."""
+kernels themselves are checked against the oracle on the device: on random reads in tests/test_pe_gpu.py, and on matches
+cut at every length -- the cases of tests/pe_extension_cases.py, whose coverage is read off this model's trace -- in
+tests/test_pe_extension_gpu.py."""
 from typing import Dict, List, Sequence, Tuple
 
 _C = {"A": "T", "C": "G", "G": "C", "T": "A"}
@@ -60,11 +62,25 @@ def step_grid(rlen: int, w: int, s: int, t: int) -> List[int]:
     return [s - 1 + i * s - (D if i >= t else 0) for i in range(n)]
 
 
+def seed_verified(w: int) -> int:
+    """VS_SEED_VERIFIED(w) (csrc/vs_pe_plan.h): exact keys up to 31 bases, mixed ones above."""
+    return w if w <= 31 else 0
+
+
 def map_end(read: str, seqs: Sequence[str], rcs: Sequence[str], table, w: int, s: int, K: int, first=None, probes=None, grid=None, key_fn=None,
-            verified=None) -> List[int]:
+            verified=None, trace=None, hook=None) -> List[int]:
     """``verified``: the seed bases the comparison after a probe takes for granted, the device's VS_SEED_VERIFIED(w)
-    (csrc/vs_internal.h) -- all w (the default) where equal keys mean equal seeds, 0 where they do not: the comparison
-    then starts at the seed's first base, and a posting whose seed differs from the read's ends below K bases."""
+    (csrc/vs_pe_plan.h) -- all w (the default) where equal keys mean equal seeds, 0 where they do not: the comparison
+    then starts at the seed's first base, and a posting whose seed differs from the read's ends below K bases.
+
+    ``trace``: a list that gets one dict per posting looked at, in the device's terms (k_pe_tiles, vs_agree_fast /
+    vs_agree_long) -- ``j`` the read offset, ``q`` the seed's offset in the text compared, ``node``, ``strand`` (1: the
+    read runs against the node), ``left``, ``c`` the left limit min(gap, j, q), ``ext`` the equal bases from where the
+    comparison starts (j + verified), ``rem`` = min(rlen - j, tlen - q) - verified, what is left of read and text from
+    there (behind the seed, min(rlen - j - w, tlen - q - w), when verified = w), ``credited`` -- and then one dict per
+    touched node with what the acceptance test used: ``node``, ``v``, ``coord``, ``kidx``, ``saturate``, ``T`` (the
+    smallest v the second clause takes) and ``kept``.
+    ``hook`` (left, ext) -> (left, ext): a test's mutation of what the comparison found.  Neither changes the result."""
     rlen = len(read)
     if verified is None:
         verified = w
@@ -95,13 +111,16 @@ def map_end(read: str, seqs: Sequence[str], rcs: Sequence[str], table, w: int, s
                 left = 0
                 while left < c and read[j - 1 - left] == text[q - 1 - left]:
                     left += 1
-                if left >= gap:
-                    continue
-                ext = verified  # (bases from the seed's first one on that are known or found equal)
-                while j + ext < rlen and q + ext < tlen and read[j + ext] == text[q + ext]:
+                ext = 0  # (bases found equal behind the ``verified`` ones that are known to be)
+                while j + verified + ext < rlen and q + verified + ext < tlen and read[j + verified + ext] == text[q + verified + ext]:
                     ext += 1
-                ln = left + ext
-                if ln < K:
+                if hook is not None:
+                    left, ext = hook(left, ext)
+                ln = left + verified + ext
+                credited = left < gap and ln >= K
+                if trace is not None:
+                    trace.append(dict(j=j, q=q, node=node, strand=opp, left=left, c=c, ext=ext, rem=min(rlen - j, tlen - q) - verified, credited=credited))
+                if not credited:
                     continue
                 a = j - left
                 qa = q - left
@@ -116,7 +135,11 @@ def map_end(read: str, seqs: Sequence[str], rcs: Sequence[str], table, w: int, s
         nlen = len(seqs[node])
         right = min(c + nlen - 1, c - ki + rlen - 1)
         saturate = right - c - K + 2
-        if v >= saturate or v * rlen >= (min(rlen, nlen) - K + 1) * (rlen - K):
+        span = min(rlen, nlen) - K + 1
+        kept = v >= saturate or v * rlen >= span * (rlen - K)
+        if trace is not None:
+            trace.append(dict(node=node, v=v, coord=c, kidx=ki, saturate=saturate, T=-(-span * (rlen - K) // rlen), kept=kept))
+        if kept:
             keep.append(node)
     return keep
 
