@@ -200,6 +200,23 @@ int vs_inflate_bgzf(vs_ctx *ctx, const uint8_t *data, uint64_t n, uint8_t *out, 
                     uint64_t status_cap, uint64_t info[2]);
 int vs_fastq_stream_inflate_info(const vs_fastq_stream *s, uint64_t info[4]);
 
+/* BGZF written on the device (additions to ABI 10): the other half of the above.  A text is cut into members of at most
+ * 0xFF00 bytes (bgzip's cut) and every member is made by ONE wavefront (k_deflate, vs_deflate.hip) through the encoder of
+ * csrc/vs_deflate_core.h, which the host runs from the same text with one lane: the bytes are the same, for every text.
+ * A member is the 18-byte BGZF header, ONE final deflate block -- the smallest of stored, fixed Huffman and dynamic Huffman,
+ * sized before anything is emitted -- CRC32 and ISIZE.  LZ77 with matches of 3 .. 258 bytes at most 32768 back, greedy; no
+ * member is larger than its text + 31 bytes (the stored form), so BSIZE never passes 65536.
+ *   vs_deflate_host : host only.  text[0, n), n <= 0xFF00, as ONE member into out[0, cap): *size its bytes, *kind = 0 stored,
+ *                     1 fixed, 2 dynamic.  VS_E_ARG for a longer text, VS_E_RANGE when the member does not fit (nothing is
+ *                     written then); cap = n + 31 always suffices.
+ *   vs_deflate_bgzf : test aid.  n host bytes cut into members of 0xFF00 through the device kernel, every member in a device
+ *                     slot of its own followed by `guard` bytes that must keep the value 0xA5 (checked, as is the rest of the
+ *                     slot behind the member: VS_E_STATE), then packed back to back on the device; out receives the members
+ *                     and the 28-byte EOF member.  info[0] = members without the EOF member, [1] = bytes of out used,
+ *                     [2] / [3] / [4] = members that came out stored / fixed / dynamic */
+int vs_deflate_host(const uint8_t *text, uint32_t n, uint8_t *out, uint32_t cap, uint32_t *size, uint32_t *kind);
+int vs_deflate_bgzf(vs_ctx *ctx, const uint8_t *text, uint64_t n, uint8_t *out, uint64_t out_cap, uint32_t guard, uint64_t info[5]);
+
 /* Member-sharded open of a BGZF pair for one process per GPU (additions to ABI 10): no rank inflates a whole file, nothing
  * is inflated on a host, and every rank streams exactly its own records.  Both files must be regular files made of whole
  * BGZF members from the first byte to the last.  Two passes with one exchange between them (pe.FastqStream.open_shard):
@@ -274,6 +291,25 @@ int vs_write_info_sparse_host(vs_ctx *ctx, const char *path, const uint8_t *ids,
                               const uint32_t *counts, const int64_t *wide, const uint8_t *tile_map, const uint32_t *rank,
                               int upper, uint64_t info[4]);
 
+/* pe_info / st_info as BGZF, deflated on the device (additions to ABI 10): `gzip -dc`, `zcat` and Python's gzip give back
+ * the text, bgzip-aware tools can seek in it.  Arguments as vs_write_info_sparse.  dense == 0: the sparse text above;
+ * dense == 1: EVERY line of the reference's file in row-major order, zeros included (for upper == 1 the lines below the
+ * diagonal too, with the count 0) -- the file utils/VStrains_PE_Inference.py writes, byte for byte, once inflated.  Per block
+ * of text (whole rows, at most 256 MB, VS_TEXT_BLOCK): k_info_format writes the text into a device buffer, k_deflate makes
+ * the block's members (members never span blocks: a block's last member is short), they are packed back to back on the device
+ * from the scan of their sizes, and ONLY those bytes are copied to a pinned buffer and written; two buffer pairs alternate.
+ * No text and no matrix leaves the device.  The 28-byte EOF member ends the file: a matrix of zeros, sparse, is that member
+ * alone.  Errors as vs_write_info_sparse; a member that ends with a status other than 0 is VS_E_STATE and names the member.
+ * info (may be NULL): [0] lines, [1] text bytes, [2] blocks, [3] counter cells read, [4] members without the EOF member,
+ * [5] file bytes.
+ *   vs_write_info_bgzf_host : the host twin.  The same arguments as HOST pointers, ctx may be NULL, one thread, the same bytes. */
+int vs_write_info_bgzf(vs_ctx *ctx, const char *path, const uint8_t *ids, const uint64_t *id_off, uint32_t n,
+                       const uint32_t *d_counts, const int64_t *d_wide, const uint8_t *d_tile_map, const uint32_t *rank,
+                       int upper, int dense, uint64_t info[6]);
+int vs_write_info_bgzf_host(vs_ctx *ctx, const char *path, const uint8_t *ids, const uint64_t *id_off, uint32_t n,
+                            const uint32_t *counts, const int64_t *wide, const uint8_t *tile_map, const uint32_t *rank,
+                            int upper, int dense, uint64_t info[6]);
+
 /* (addition to ABI 10) A pe_info / st_info file, dense or sparse, parsed on the host threads into cells against a name list:
  * the lines up to the first empty one; each line minus its LAST CHARACTER (the newline, or a real character on a final line
  * without one) split at ':', the first three fields taken (IO.py:603-612); a line naming an id that is not among the n names
@@ -282,7 +318,9 @@ int vs_write_info_sparse_host(vs_ctx *ctx, const char *path, const uint8_t *ids,
  * up to cap cells in file order; with cap == 0 nothing is parsed and info[0] is the number of lines, an upper bound on the
  * cells.  info[0] = cells, [1] = flags: bit 0 the file holds a '\r', bit 1 a byte >= 0x80 -- such a file is NOT parsed here
  * (universal newlines and the text decoding belong to Python: the caller keeps its own loop), [2] = lines read,
- * [3] = lines skipped for an unknown id. */
+ * [3] = lines skipped for an unknown id.  A file that starts with the gzip magic 1f 8b (what vs_write_info_bgzf writes, or
+ * any gzip) is first inflated on the host with zlib, all members of it, and then read exactly as the plain file is; a cut-off
+ * or corrupt stream is VS_E_ARG with zlib's words. */
 int vs_info_parse(const char *path, const uint8_t *names, const uint64_t *name_off, uint32_t n, uint32_t *rows, uint32_t *cols,
                   int64_t *vals, uint64_t cap, uint64_t info[4]);
 

@@ -48,6 +48,10 @@ def build_parser():
     p.add_argument("--sparse-pe-text", dest="sparse_pe_text", action="store_true", default=False,
                    help="extension: write aln/pe_info and aln/st_info with the lines of non-zero count only, formatted on "
                         "the device (not together with --no-pe-text)")
+    p.add_argument("--bgzf-pe-text", dest="bgzf_pe_text", action="store_true", default=False,
+                   help="extension: write aln/pe_info.gz and aln/st_info.gz, BGZF deflated on the device; `gzip -dc` gives the "
+                        "reference's files byte for byte, or with --sparse-pe-text the sparse ones (not together with "
+                        "--no-pe-text)")
     return p
 
 
@@ -63,6 +67,8 @@ def main(argv=None, backend=None):
     args = parser.parse_args(argv)
     if args.no_pe_text and args.sparse_pe_text:
         parser.error("--no-pe-text and --sparse-pe-text are mutually exclusive")
+    if args.no_pe_text and args.bgzf_pe_text:
+        parser.error("--no-pe-text and --bgzf-pe-text are mutually exclusive")
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
         _bail("\nPath to the assembly graph is required, (.gfa format)", "Please ensure the path is correct")
     args.assembler = args.assembler.lower()
@@ -133,12 +139,16 @@ def main(argv=None, backend=None):
 
     from .graph import pipeline
 
-    if backend is None and (args.no_pe_text or args.sparse_pe_text):
+    if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text):
         from .graph.hip_ops import HipBackend
 
-        backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text)
-    elif backend is not None and args.sparse_pe_text:
-        backend.sparse_info_text = True
+        backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text,
+                             bgzf_info_text=args.bgzf_pe_text)
+    elif backend is not None:
+        if args.sparse_pe_text:
+            backend.sparse_info_text = True
+        if args.bgzf_pe_text:
+            backend.bgzf_info_text = True
 
     old_err = numpy.seterr(all="raise")  # vstrains:25
     try:

@@ -1,7 +1,8 @@
 // The text of a sparse pe_info / st_info file, one source for the device kernels and their host twin (vs_info.hip): which
 // value a cell of the caller's matrix has, how many bytes its line takes, and the line itself.  The dense file is
 // "{id_i}:{id_j}:{count}\n" for all i, j in row-major order (utils/VStrains_PE_Inference.py:194-205); the sparse file is
-// that file without the lines whose count is 0.
+// that file without the lines whose count is 0.  VsInfoSrc::dense keeps the zero lines, and with them the lines below the
+// diagonal of st_info: the dense file itself, for the writer that compresses it on the device (vs_write_info_bgzf).
 //
 // Compiled twice from this text: by the kernels of vs_info.hip, and by vs_write_info_sparse_host, which walks the same
 // cells with one thread -- so that a CPU test drives every branch of it before anything is launched.
@@ -26,7 +27,12 @@ struct VsInfoSrc {
     const uint32_t *rank;    // rank[i] = internal number of the caller's node i, or NULL (the same numbering)
     uint32_t n, T;           // T = ceil(n / 64)
     int upper;               // 0: node_mat rule, 1: short_mat rule
+    int dense = 0;           // 0: only the lines with a count above 0, 1: every line of the reference's file
 };
+
+// the first column of the caller's row i that can have a line, and whether the value v has one
+VS_INFO_HD uint32_t vs_info_first_col(const VsInfoSrc &s, uint32_t i) { return s.upper && !s.dense ? i : 0u; }
+VS_INFO_HD bool vs_info_has_line(const VsInfoSrc &s, int64_t v) { return v > 0 || (s.dense && v == 0); }
 
 // total of the internal cell (r, c): uint32 cell + int64 total; *reads counts the cells whose counters were loaded
 VS_INFO_HD int64_t vs_info_total(const VsInfoSrc &s, uint32_t r, uint32_t c, uint32_t *reads) {
@@ -74,7 +80,7 @@ VS_INFO_HD uint32_t vs_info_digits(uint64_t v) {
     return d;
 }
 
-// bytes of the line of a non-zero value v between ids of li and lj bytes: id_i ':' id_j ':' digits '\n'
+// bytes of the line of a value v between ids of li and lj bytes: id_i ':' id_j ':' digits '\n'
 VS_INFO_HD uint32_t vs_info_line_len(uint32_t li, uint32_t lj, uint64_t v) { return li + lj + vs_info_digits(v) + 3u; }
 
 // the line, vs_info_line_len bytes at q

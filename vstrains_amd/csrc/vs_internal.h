@@ -228,6 +228,19 @@ void vs_launch_inflate_count(hipStream_t st, const uint8_t *comp, uint64_t comp_
 // the same decoder on the host (vs_inflate_core.h with one lane): the status word
 uint32_t vs_inflate_member_host(const uint8_t *pay, uint32_t len, uint8_t *out, uint32_t isize, uint32_t crc);
 
+// BGZF members made on the device (vs_deflate.hip).  text[0, text_bytes) is cut into n = ceil(text_bytes / 0xFF00) members,
+// one wavefront each: member i lies at slots[i * stride, + sizes[i]) and may use `cap` <= stride bytes of its slot
+// (cap >= 0xFF00 + 31 always suffices); res[2 i] = 0 or a DEF_E_* word (sizes[i] is then 0), res[2 i + 1] = 0 stored /
+// 1 fixed / 2 dynamic
+void vs_launch_deflate(hipStream_t st, const uint8_t *text, uint64_t text_bytes, uint32_t n, uint8_t *slots, uint64_t slots_bytes, uint32_t stride,
+                       uint32_t cap, uint32_t *sizes, uint32_t *res);
+// member i's sizes[i] bytes from its slot to packed[offs[i] ...) (offs: the exclusive scan of sizes); nothing beyond packed_bytes
+void vs_launch_deflate_pack(hipStream_t st, const uint8_t *slots, uint32_t stride, const uint32_t *sizes, const uint32_t *offs, uint32_t n,
+                            uint8_t *packed, uint64_t packed_bytes);
+// the same encoder on the host (vs_deflate_core.h with one lane): the DEF_* status word
+uint32_t vs_deflate_member_host(const uint8_t *text, uint32_t n, uint8_t *out, uint32_t cap, uint32_t *size, uint32_t *kind);
+extern const uint8_t vs_bgzf_eof[28];  // the empty member that ends a BGZF file
+
 // Exclusive scan of n uint32 values on the ctx stream (in -> out, may alias); total (uint64) is
 // written to d_total if not NULL.  tmp must hold ceil(n/2048)+1 uint64.
 int vs_scan_u32(vs_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *d_tmp,

@@ -7,6 +7,7 @@ tab split that keeps file order (its segment / edge views are file-ordered).
 """
 from __future__ import annotations
 
+import gzip
 from typing import Dict, Iterable, List, Optional, Tuple
 
 from .asm_graph import BLACK, AsmGraph, EdgeMap, NodeMap
@@ -214,8 +215,12 @@ def write_contig_paths(contigs: ContigDict, filename: str, id_mapping: Optional[
 
 
 def read_pe_text(path: str) -> Iterable[Tuple[str, str, int]]:
-    """Lines ``u:v:count`` up to the first empty line (``process_pe_info`` IO.py:603-612)."""
-    with open(path, "r") as fh:
+    """Lines ``u:v:count`` up to the first empty line (``process_pe_info`` IO.py:603-612).  A file that starts with the
+    gzip magic (``pe_info.gz`` as ``--bgzf-info`` writes it, or any gzip) is read through ``gzip`` in text mode, with the
+    newline handling of ``open``."""
+    with open(path, "rb") as probe:
+        zipped = probe.read(2) == b"\x1f\x8b"
+    with (gzip.open(path, "rt", newline=None) if zipped else open(path, "r")) as fh:
         for line in fh:
             if line == "\n":
                 break

@@ -137,7 +137,7 @@ class HipPeLinks(PeLinks):
     @classmethod
     def from_files(cls, ctx, names: Sequence[str], pe_file: str, st_file: str, sparse_min_nodes: int = 0):
         """The reference's own hand-off (IO.py:603-623): the two text files, dense (N^2 lines) or sparse (the lines of
-        non-zero count only).  The library parses them on the host threads (``vs_info_parse``) and builds the table from
+        non-zero count only), plain or gzip / BGZF (``pe_info.gz``: inflated on the host by the library).  The library parses them on the host threads (``vs_info_parse``) and builds the table from
         the cells (``vs_links_from_cells``: dense below ``sparse_min_nodes`` nodes -- 0: the library's 32 768 --, CSR rows
         from there on); a file that holds a carriage return or a byte outside ASCII is left to Python's text mode, the
         loop over ``formats.read_pe_text``."""
@@ -281,13 +281,15 @@ class HipPeLinks(PeLinks):
 class HipBackend:
     """What ``pipeline.run`` needs from the device: PE-link inference + the graph kernels."""
 
-    def __init__(self, device: int = 0, write_info_text: bool = True, ctx=None, sparse_info_text: bool = False):
+    def __init__(self, device: int = 0, write_info_text: bool = True, ctx=None, sparse_info_text: bool = False,
+                 bgzf_info_text: bool = False):
         from .. import pe as host
 
         self.ctx = ctx if ctx is not None else host.Context(device)  # raises NativeError without a HIP device
         self.graph_ops = HipGraphOps(self.ctx)
         self.write_info_text = write_info_text
         self.sparse_info_text = sparse_info_text  # pe_info / st_info with the lines of non-zero count only
+        self.bgzf_info_text = bgzf_info_text  # pe_info.gz / st_info.gz: BGZF deflated on the device
         self.pe_stats = None
 
     def pe_links(self, gfa: str, aln_dir: str, fwd: str, rve: str, ksize: int, names: List[str]) -> HipPeLinks:
@@ -299,7 +301,7 @@ class HipBackend:
         print("----------------------Paired-End Information Alignment----------------------")
         if self.write_info_text:
             self.pe_stats = pe_inference.run(gfa, aln_dir, fwd, rve, ksize, ctx=self.ctx, stages_follow=True,
-                                              sparse_info=self.sparse_info_text)
+                                              sparse_info=self.sparse_info_text, bgzf_info=self.bgzf_info_text)
             ids, counter = pe_inference.run.last
         else:
             os.makedirs(aln_dir, exist_ok=True)

@@ -997,6 +997,19 @@ class PeCounter:
         (``vs_write_info_sparse``: on the device for device counters; counters held in CPU tensors go through the library's
         host twin).  No permuted copy of a matrix is made and none is downloaded.  Returns per file
         ``dict(lines, bytes, blocks, cells_read)``."""
+        return self._write_info_text("vs_write_info_sparse", pe_path, st_path, ids, (), ("lines", "bytes", "blocks", "cells_read"))
+
+    def write_bgzf_text(self, pe_path: str, st_path: str, ids: Sequence[str], dense: bool = False):
+        """``pe_info`` / ``st_info`` as BGZF, formatted AND deflated where the counters lie (``vs_write_info_bgzf``: on the
+        device for device counters, the library's host twin for CPU tensors -- the same bytes).  ``dense``: every line of
+        the reference's file, zeros included, so that ``gzip -dc`` gives back that file byte for byte; otherwise the
+        sparse text of ``write_sparse_text``.  Only compressed bytes leave the device.  Returns per file
+        ``dict(lines, bytes, blocks, cells_read, members, file_bytes)`` (``bytes``: of text; ``members``: without the
+        28-byte EOF member that ends the file)."""
+        return self._write_info_text("vs_write_info_bgzf", pe_path, st_path, ids, (1 if dense else 0,),
+                                     ("lines", "bytes", "blocks", "cells_read", "members", "file_bytes"))
+
+    def _write_info_text(self, entry: str, pe_path: str, st_path: str, ids: Sequence[str], extra, keys):
         torch = self.torch
         n = self.n
         if len(ids) != n:
@@ -1009,24 +1022,24 @@ class PeCounter:
             torch.cuda.synchronize(self.device)
         out = []
         for m, path in enumerate((pe_path, st_path)):
-            info = (C.c_uint64 * 4)()
+            info = (C.c_uint64 * len(keys))()
             args = (path.encode(), blob.ctypes.data, off.ctypes.data, n,
                     C.c_void_p(self.mats[m].data_ptr()) if n else None,
                     C.c_void_p(self.wide[m].data_ptr()) if (self.wide is not None and n) else None,
                     C.c_void_p(self.tile_map[m * tiles * tiles:].data_ptr()) if (self.tile_map is not None and n) else None,
-                    rank.ctypes.data if rank is not None else None, m, info)
+                    rank.ctypes.data if rank is not None else None, m) + tuple(extra) + (info,)
             if on_device:
                 with torch.cuda.device(self.device):
                     self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
-                    rc = nat.lib().vs_write_info_sparse(self.ctx._h, *args)
+                    rc = getattr(nat.lib(), entry)(self.ctx._h, *args)
                 err = self.ctx._h
             else:
-                rc = nat.lib().vs_write_info_sparse_host(None, *args)
+                rc = getattr(nat.lib(), entry + "_host")(None, *args)
                 err = None
             if rc != nat.VS_OK:
                 msg = (nat.lib().vs_last_error(err) or b"?").decode("utf-8", "replace")
                 raise (OSError if "cannot open" in msg or "write to" in msg else ValueError)(msg)
-            out.append(dict(lines=int(info[0]), bytes=int(info[1]), blocks=int(info[2]), cells_read=int(info[3])))
+            out.append({key: int(info[i]) for i, key in enumerate(keys)})
         return out
 
     def user_order(self, t):

@@ -194,12 +194,19 @@ def count_fastq(ctx, fq, counter, first: int, last: int, batch: int = BATCH_PAIR
         block.free()
 
 
-def write_info_files(out_dir: str, ids, counter, sparse: bool = False):
+def write_info_files(out_dir: str, ids, counter, sparse: bool = False, bgzf: bool = False):
     """pe_info / st_info text, PE_Inference.py:190-207.  Returns the first file's name and the stats.  ``sparse``: only the
     lines with a non-zero count, written from the counters on the device (``PeCounter.write_sparse_text``) -- the
-    reference reads them to the same dict (``process_pe_info`` zeroes every key first, IO.py:598-623)."""
+    reference reads them to the same dict (``process_pe_info`` zeroes every key first, IO.py:598-623).  ``bgzf``: the
+    files are ``pe_info.gz`` / ``st_info.gz``, BGZF made on the device (``PeCounter.write_bgzf_text``); they inflate to
+    the dense text, or with ``sparse`` to the sparse one."""
     out_file = "{0}/pe_info".format(out_dir)
     out_file2 = "{0}/st_info".format(out_dir)
+    if bgzf:
+        out_file, out_file2 = out_file + ".gz", out_file2 + ".gz"
+        counter.write_bgzf_text(out_file, out_file2, ids, dense=not sparse)
+        s = counter.stats.cpu().numpy()
+        return out_file, (int(s[0]), int(s[1]), int(s[2]))
     if sparse:
         counter.write_sparse_text(out_file, out_file2, ids)
         s = counter.stats.cpu().numpy()
@@ -211,7 +218,7 @@ def write_info_files(out_dir: str, ids, counter, sparse: bool = False):
 
 
 def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int = 0, ctx=None, stages_follow: bool = False,
-        sparse_info: bool = False):
+        sparse_info: bool = False, bgzf_info: bool = False):
     # PE_Inference.py:93-96: the output directory is wiped and recreated
     if out_dir[-1] == "/":
         out_dir = out_dir[:-1]
@@ -231,7 +238,7 @@ def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int 
     run.last = (ids, counter)
     if rank != 0:
         return None  # the counters were reduced to rank 0, which writes the files
-    out_file, stats = write_info_files(out_dir, ids, counter, sparse=sparse_info)
+    out_file, stats = write_info_files(out_dir, ids, counter, sparse=sparse_info, bgzf=bgzf_info)
     glb_elapsed = time.time() - glb_start
     print("Global time elapsed: ", glb_elapsed)  # :209-211
     print("result stored in: ", out_file)
@@ -251,6 +258,9 @@ def main(argv=None):
     parser.add_argument("--sparse-info", dest="sparse_info", action="store_true", default=False,
                         help="extension: write only the lines of pe_info / st_info whose count is not 0, formatted on the "
                              "device (the reference reads such files to the same result)")
+    parser.add_argument("--bgzf-info", dest="bgzf_info", action="store_true", default=False,
+                        help="extension: write pe_info.gz / st_info.gz, BGZF deflated on the device; `gzip -dc` gives the "
+                             "reference's file byte for byte (with --sparse-info: the sparse file)")
     args = parser.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:  # launched by torchrun: one rank per GPU, counters all-reduced over RCCL
@@ -272,7 +282,7 @@ def main(argv=None):
         # every rank indexes both FASTQ files on the host: share the cores between the local ranks
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
         os.environ.setdefault("VS_HOST_THREADS", str(max(1, (os.cpu_count() or 1) // max(local_world, 1))))
-    run(args.gfa, args.dir, args.fwd, args.rve, args.kmer_size, args.device, sparse_info=args.sparse_info)
+    run(args.gfa, args.dir, args.fwd, args.rve, args.kmer_size, args.device, sparse_info=args.sparse_info, bgzf_info=args.bgzf_info)
     if world > 1:
         import torch.distributed as dist
 
