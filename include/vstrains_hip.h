@@ -323,6 +323,14 @@ int vs_write_info_bgzf_host(vs_ctx *ctx, const char *path, const uint8_t *ids, c
  * or corrupt stream is VS_E_ARG with zlib's words. */
 int vs_info_parse(const char *path, const uint8_t *names, const uint64_t *name_off, uint32_t n, uint32_t *rows, uint32_t *cols,
                   int64_t *vals, uint64_t cap, uint64_t info[4]);
+/* (addition to ABI 10) The host twin of the device reader below (vs_links_from_info): text[0, size) held by the caller, read
+ * by the rules of vs_info_parse through the code the kernels run (csrc/vs_info_read_core.h), one thread, in windows of
+ * window_bytes (0 = 256 MB, at least 16) whose buffer always begins at a line start.  rows / cols / vals receive up to cap cells
+ * in text order (more is VS_E_RANGE).  info[0] = outcome: 0 read, 1 the text holds a '\r' or a byte >= 0x80 (Python's to read),
+ * 2 a malformed line, 3 a line does not fit a window (the file is vs_info_parse's); [1] lines, [2] lines skipped for an unknown
+ * id, [3] cells, [4] text offset of the first malformed line, [5] windows, [6] flags as vs_info_parse's info[1], [7] text bytes. */
+int vs_info_read_host(const uint8_t *text, uint64_t size, const uint8_t *names, const uint64_t *name_off, uint32_t n,
+                      uint64_t window_bytes, uint32_t *rows, uint32_t *cols, int64_t *vals, uint64_t cap, uint64_t info[8]);
 
 /* Synthetic pairs generated on the device from a seed (bench workload; the CPU twin is
  * oracle/pe_oracle.c:peo_synth_pairs).  genomes: concatenated ACGT ASCII (host), goff
@@ -468,6 +476,20 @@ int vs_links_from_host(vs_ctx *ctx, const int64_t *node_mat, const int64_t *shor
  * outside n x n is VS_E_RANGE. */
 int vs_links_from_cells(vs_ctx *ctx, const uint32_t *rows, const uint32_t *cols, const int64_t *vals, uint64_t n_cells, uint32_t n,
                         uint32_t sparse_min_nodes, vs_links **out);
+/* (addition to ABI 10) The same table straight from the two files, read where the table lives.  A file that is BGZF from its
+ * first byte to its last (what vs_write_info_bgzf writes) is uploaded compressed, window by window, and inflated on the device
+ * (one wavefront per member, CRC checked); a plain file is uploaded window by window from the mapped file; the text of a window
+ * (window_bytes, 0 = 256 MB; a buffer always begins at a line start, the cut line is carried) is scanned and parsed by kernels
+ * and every non-zero count is added into ONE zeroed table (the buffer of vs_links_reserve when there is one) by 64-bit atomic
+ * adds -- or, from `sparse_min_nodes` nodes on, appended to a cell list that the CSR build of vs_links_from_cells takes.  No
+ * text exists on the host.  Any other gzip file, a file with a line longer than a window, and a file with an error go through
+ * vs_info_parse on the host, which words the error (VS_E_ARG, the same text in vs_last_error(ctx)).  When either file holds a
+ * '\r' or a byte >= 0x80 the call returns 0 with *out = NULL and the flags set: the caller keeps its own loop, as after
+ * vs_info_parse.  info, 8 words per file (pe_info first): [0] route -- 1 BGZF inflated on the device, 2 plain text parsed on the
+ * device, 3 vs_info_parse --, [1] lines, [2] lines skipped for an unknown id, [3] lines that named two known ids, [4] members
+ * inflated on the device, [5] text bytes, [6] windows, [7] flags as vs_info_parse's info[1]. */
+int vs_links_from_info(vs_ctx *ctx, const char *pe_path, const char *st_path, const uint8_t *names, const uint64_t *name_off,
+                       uint32_t n, uint32_t sparse_min_nodes, uint64_t window_bytes, vs_links **out, uint64_t info[16]);
 /* Optional, ABI 9: set aside the device buffer of the next table of n nodes (n*n int64) now -- typically when the counters
  * are allocated, before any read is counted -- so that vs_links_from_counts / _from_wide / _from_host does not have to ask the
  * driver for it later (a hipMalloc of tens of gigabytes takes 0.3 ms or half a second depending on what the process freed

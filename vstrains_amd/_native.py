@@ -70,6 +70,8 @@ SYMBOLS = {
                                           C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "vs_info_parse": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                 C.POINTER(C.c_uint64)]),
+    "vs_info_read_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_uint64, C.POINTER(C.c_uint64)]),
     "vs_synth_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
                                  C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                  C.POINTER(C.c_void_p)]),
@@ -94,6 +96,8 @@ SYMBOLS = {
     "vs_links_from_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "vs_links_from_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "vs_links_from_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "vs_links_from_info": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64,
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "vs_links_reserve": (C.c_int, [C.c_void_p, C.c_uint32]),
     "vs_links_free": (None, [C.c_void_p, C.c_void_p]),
     "vs_links_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -52,7 +52,21 @@ def build_parser():
                    help="extension: write aln/pe_info.gz and aln/st_info.gz, BGZF deflated on the device; `gzip -dc` gives the "
                         "reference's files byte for byte, or with --sparse-pe-text the sparse ones (not together with "
                         "--no-pe-text)")
+    p.add_argument("--pe-text-from", dest="pe_text_from", default=None, type=str, metavar="ALN_DIR",
+                   help="extension: do not count the reads again; read ALN_DIR/pe_info.gz + st_info.gz (or pe_info + st_info) "
+                        "that an earlier run or vstrains_amd.pe_inference wrote, on the device (not together with --no-pe-text, "
+                        "--sparse-pe-text or --bgzf-pe-text; -fwd / -rve are still required and are not opened)")
     return p
+
+
+def pe_text_pair(aln_dir):
+    """The pe_info / st_info pair of ``aln_dir`` that --pe-text-from reads: the .gz pair if both are there, else the plain
+    pair, else None."""
+    for suffix in (".gz", ""):
+        pair = (os.path.join(aln_dir, "pe_info" + suffix), os.path.join(aln_dir, "st_info" + suffix))
+        if all(os.path.isfile(f) for f in pair):
+            return pair
+    return None
 
 
 def _bail(*lines):
@@ -69,8 +83,18 @@ def main(argv=None, backend=None):
         parser.error("--no-pe-text and --sparse-pe-text are mutually exclusive")
     if args.no_pe_text and args.bgzf_pe_text:
         parser.error("--no-pe-text and --bgzf-pe-text are mutually exclusive")
+    if args.pe_text_from is not None:
+        for flag, name in ((args.no_pe_text, "--no-pe-text"), (args.sparse_pe_text, "--sparse-pe-text"), (args.bgzf_pe_text, "--bgzf-pe-text")):
+            if flag:
+                parser.error("--pe-text-from and %s are mutually exclusive" % name)
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
         _bail("\nPath to the assembly graph is required, (.gfa format)", "Please ensure the path is correct")
+    args.pe_text_files = None
+    if args.pe_text_from is not None:
+        args.pe_text_files = pe_text_pair(args.pe_text_from)
+        if args.pe_text_files is None:
+            _bail("\nPath to the paired-end information (--pe-text-from) must hold pe_info.gz and st_info.gz, or pe_info and st_info",
+                  "Please ensure the path is correct")
     args.assembler = args.assembler.lower()
     if (not args.path_file) or (not os.path.exists(args.path_file)):
         _bail("\nPath to Contig file from SPAdes (.paths format) is required for SPAdes assmbler option. e.g., contigs.paths")

@@ -650,7 +650,6 @@ int links_build(vs_ctx *ctx, const TIn *d_node, const TIn *d_short, uint32_t n, 
     *out = L;
     return VS_OK;
 }
-#define VS_LINKS_SPARSE_MIN 32768u  // nodes from which a table with a dirty-tile map is held as CSR rows (4 GiB of counters)
 template <typename TIn>
 int links_build_sparse(vs_ctx *ctx, const TIn *d_node, const TIn *d_short, uint32_t n, const uint8_t *d_tile_map, vs_links **out) {
     vs_links *L = new vs_links();
@@ -780,45 +779,91 @@ int vs_links_from_cells(vs_ctx *ctx, const uint32_t *rows, const uint32_t *cols,
         if (rows[x] >= n || cols[x] >= n) return vs_fail(ctx, VS_E_RANGE, "vs_links_from_cells: cell %llu (%u, %u) outside %u nodes", (unsigned long long)x, rows[x], cols[x], n);
     VS_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t min_nodes = sparse_min_nodes ? sparse_min_nodes : VS_LINKS_SPARSE_MIN;
+    if (n >= min_nodes) return vs_links_csr_from_cells(ctx, rows, cols, vals, n_cells, n, out);
+    // dense: the cells uploaded and scattered into a zeroed table
+    vs_links *L = nullptr;
+    int64_t *d_p0 = nullptr;
+    if (int rc = vs_links_dense_zeroed(ctx, "vs_links_from_cells", n, &L, &d_p0)) return rc;
+    int rc = vs_links_scatter_cells(ctx, d_p0, n, rows, cols, vals, n_cells);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = vs_fail(ctx, VS_E_HIP, "vs_links_from_cells: the scatter failed");
+    if (rc) {
+        vs_links_free(ctx, L);
+        return rc;
+    }
+    *out = L;
+    return VS_OK;
+}
+
+}  // extern "C"
+
+// ---- the pieces of vs_links_from_cells, shared with vs_links_from_info (vs_info_read.hip) --------------------------------
+// a table of n nodes, dense, its cells zeroed on the ctx stream: the buffer vs_links_reserve set aside, or a new one
+int vs_links_dense_zeroed(vs_ctx *ctx, const char *who, uint32_t n, vs_links **out, int64_t **d_p0) {
+    vs_links *L = new vs_links();
+    L->n = n;
+    const size_t bytes = (size_t)(n ? (uint64_t)n * n : 1) * sizeof(int64_t);
+    if (ctx->links_spare.ptr() && ctx->links_spare_n == n && n) {  // vs_links_reserve set it aside
+        L->d_p0 = std::move(ctx->links_spare);
+        ctx->links_spare_n = 0;
+    } else if (L->d_p0.reserve(bytes) != hipSuccess) {
+        vs_links_free(ctx, L);
+        return vs_fail(ctx, VS_E_OOM, "%s: %.2f GB", who, (double)bytes / 1e9);
+    }
+    if (hipMemsetAsync(L->d_p0.ptr(), 0, bytes, ctx->stream) != hipSuccess) {
+        vs_links_free(ctx, L);
+        return vs_fail(ctx, VS_E_HIP, "%s: the table could not be zeroed", who);
+    }
+    *out = L;
+    *d_p0 = L->d_p0.as<int64_t>();
+    return VS_OK;
+}
+
+// host cells uploaded and added to a dense table (k_links_scatter); the upload buffers die with the call, which therefore
+// synchronises the stream
+int vs_links_scatter_cells(vs_ctx *ctx, int64_t *d_p0, uint32_t n, const uint32_t *rows, const uint32_t *cols, const int64_t *vals, uint64_t n_cells) {
+    if (!n_cells) return VS_OK;
+    VsDevBuf d_rows, d_cols, d_vals;
+    const auto on_device = [&]() -> int {
+        VS_HIP(ctx, d_rows.reserve((size_t)n_cells * sizeof(uint32_t)));
+        VS_HIP(ctx, d_cols.reserve((size_t)n_cells * sizeof(uint32_t)));
+        VS_HIP(ctx, d_vals.reserve((size_t)n_cells * sizeof(int64_t)));
+        VS_HIP(ctx, hipMemcpyAsync(d_rows.ptr(), rows, (size_t)n_cells * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        VS_HIP(ctx, hipMemcpyAsync(d_cols.ptr(), cols, (size_t)n_cells * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        VS_HIP(ctx, hipMemcpyAsync(d_vals.ptr(), vals, (size_t)n_cells * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        const unsigned grid = (unsigned)std::min<uint64_t>((n_cells + 255u) / 256u, 2048u);
+        hipLaunchKernelGGL(k_links_scatter, dim3(grid), dim3(256), 0, ctx->stream, d_rows.as<const uint32_t>(), d_cols.as<const uint32_t>(),
+                           d_vals.as<const int64_t>(), n_cells, n, d_p0);
+        VS_HIP(ctx, hipGetLastError());
+        return VS_OK;
+    };
+    int rc = on_device();
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = vs_fail(ctx, VS_E_HIP, "the scatter of %llu cells failed", (unsigned long long)n_cells);
+    return rc;
+}
+
+// a table that is not handed out after all: a dense buffer goes back to where vs_links_reserve keeps it
+void vs_links_abandon(vs_ctx *ctx, vs_links *L) {
+    if (!L) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    if (!L->sparse() && L->n && L->d_p0.ptr() && !ctx->links_spare.ptr()) {
+        ctx->links_spare = std::move(L->d_p0);
+        ctx->links_spare_n = L->n;
+    }
+    delete L;
+}
+
+// CSR rows (the form vs_links_from_counts_tracked gives from 2^15 nodes on), built on the host -- a one-off over the cells of
+// two files: every cell and its mirror dealt to its row (a counting sort over the rows), every row sorted by column on the
+// host threads, equal columns merged, sums of zero dropped (the table holds non-zero cells).  Every cell lies inside n nodes.
+int vs_links_csr_from_cells(vs_ctx *ctx, const uint32_t *rows, const uint32_t *cols, const int64_t *vals, uint64_t n_cells, uint32_t n, vs_links **out) {
+    for (uint64_t x = 0; x < n_cells; x++)
+        if (rows[x] >= n || cols[x] >= n) return vs_fail(ctx, VS_E_RANGE, "vs_links (sparse): cell %llu (%u, %u) outside %u nodes", (unsigned long long)x, rows[x], cols[x], n);
     vs_links *L = new vs_links();
     L->n = n;
     const auto fail = [&](int rc) {
         vs_links_free(ctx, L);
         return rc;
     };
-    if (n < min_nodes) {  // dense: the cells uploaded and scattered into a zeroed table
-        const size_t bytes = (size_t)(n ? (uint64_t)n * n : 1) * sizeof(int64_t);
-        if (ctx->links_spare.ptr() && ctx->links_spare_n == n && n) {  // vs_links_reserve set it aside
-            L->d_p0 = std::move(ctx->links_spare);
-            ctx->links_spare_n = 0;
-        } else if (L->d_p0.reserve(bytes) != hipSuccess) {
-            return fail(vs_fail(ctx, VS_E_OOM, "vs_links_from_cells: %.2f GB", (double)bytes / 1e9));
-        }
-        VsDevBuf d_rows, d_cols, d_vals;  // (die with the call)
-        const auto on_device = [&]() -> int {
-            VS_HIP(ctx, hipMemsetAsync(L->d_p0.ptr(), 0, bytes, ctx->stream));
-            if (!n_cells) return VS_OK;
-            VS_HIP(ctx, d_rows.reserve((size_t)n_cells * sizeof(uint32_t)));
-            VS_HIP(ctx, d_cols.reserve((size_t)n_cells * sizeof(uint32_t)));
-            VS_HIP(ctx, d_vals.reserve((size_t)n_cells * sizeof(int64_t)));
-            VS_HIP(ctx, hipMemcpyAsync(d_rows.ptr(), rows, (size_t)n_cells * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            VS_HIP(ctx, hipMemcpyAsync(d_cols.ptr(), cols, (size_t)n_cells * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            VS_HIP(ctx, hipMemcpyAsync(d_vals.ptr(), vals, (size_t)n_cells * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-            const unsigned grid = (unsigned)std::min<uint64_t>((n_cells + 255u) / 256u, 2048u);
-            hipLaunchKernelGGL(k_links_scatter, dim3(grid), dim3(256), 0, ctx->stream, d_rows.as<const uint32_t>(), d_cols.as<const uint32_t>(),
-                               d_vals.as<const int64_t>(), n_cells, n, L->d_p0.as<int64_t>());
-            VS_HIP(ctx, hipGetLastError());
-            return VS_OK;
-        };
-        int rc = on_device();
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = vs_fail(ctx, VS_E_HIP, "vs_links_from_cells: the scatter failed");
-        if (rc) return fail(rc);
-        *out = L;
-        return VS_OK;
-    }
-    // CSR rows (the form vs_links_from_counts_tracked gives from 2^15 nodes on), built on the host -- a one-off over the
-    // cells of two files: every cell and its mirror dealt to its row (a counting sort over the rows), every row sorted by
-    // column on the host threads, equal columns merged, sums of zero dropped (the table holds non-zero cells)
     std::vector<uint64_t> start((size_t)n + 2u, 0);
     for (uint64_t x = 0; x < n_cells; x++) {
         start[(size_t)rows[x] + 1u]++;
@@ -886,6 +931,8 @@ int vs_links_from_cells(vs_ctx *ctx, const uint32_t *rows, const uint32_t *cols,
     *out = L;
     return VS_OK;
 }
+
+extern "C" {
 
 void vs_links_free(vs_ctx *ctx, vs_links *links) {
     if (!links) return;

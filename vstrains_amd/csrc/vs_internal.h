@@ -241,6 +241,17 @@ void vs_launch_deflate_pack(hipStream_t st, const uint8_t *slots, uint32_t strid
 uint32_t vs_deflate_member_host(const uint8_t *text, uint32_t n, uint8_t *out, uint32_t cap, uint32_t *size, uint32_t *kind);
 extern const uint8_t vs_bgzf_eof[28];  // the empty member that ends a BGZF file
 
+#define VS_LINKS_SPARSE_MIN 32768u  // nodes from which a table with a dirty-tile map is held as CSR rows (4 GiB of counters)
+// The pieces of vs_links_from_cells (vs_graph.hip), shared with vs_links_from_info (vs_info_read.hip).
+// A dense table of n nodes, its cells zeroed on the ctx stream: the buffer vs_links_reserve set aside, or a new one.
+int vs_links_dense_zeroed(vs_ctx *ctx, const char *who, uint32_t n, vs_links **out, int64_t **d_p0);
+// host cells uploaded and added to a dense table: P0[r][c] += v and, off the diagonal, P0[c][r] += v; synchronises the stream
+int vs_links_scatter_cells(vs_ctx *ctx, int64_t *d_p0, uint32_t n, const uint32_t *rows, const uint32_t *cols, const int64_t *vals, uint64_t n_cells);
+// the CSR table of host cells (every cell and its mirror, equal cells merged, sums of zero dropped)
+int vs_links_csr_from_cells(vs_ctx *ctx, const uint32_t *rows, const uint32_t *cols, const int64_t *vals, uint64_t n_cells, uint32_t n, vs_links **out);
+// a table that is not handed out after all: a dense buffer goes back to where vs_links_reserve keeps it
+void vs_links_abandon(vs_ctx *ctx, vs_links *L);
+
 // Exclusive scan of n uint32 values on the ctx stream (in -> out, may alias); total (uint64) is
 // written to d_total if not NULL.  tmp must hold ceil(n/2048)+1 uint64.
 int vs_scan_u32(vs_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *d_tmp,

@@ -134,18 +134,42 @@ class HipPeLinks(PeLinks):
         nat.check(ctx._h, nat.lib().vs_links_from_host(ctx._h, _ptr(a), _ptr(b), n, C.byref(h)))
         return cls(ctx, h, names)
 
+    #: what the last ``from_files`` read: {"pe": {...}, "st": {...}} with the route ("bgzf_device", "plain_device", "host";
+    #: "python" when the files went to the Python loop), lines, skipped, cells, members_device, text_bytes, windows, flags
+    last_read: Optional[Dict[str, Dict[str, object]]] = None
+    _ROUTES = {0: "none", 1: "bgzf_device", 2: "plain_device", 3: "host"}
+
     @classmethod
-    def from_files(cls, ctx, names: Sequence[str], pe_file: str, st_file: str, sparse_min_nodes: int = 0):
+    def from_files(cls, ctx, names: Sequence[str], pe_file: str, st_file: str, sparse_min_nodes: int = 0,
+                   device_parse: bool = True, window_bytes: int = 0):
         """The reference's own hand-off (IO.py:603-623): the two text files, dense (N^2 lines) or sparse (the lines of
-        non-zero count only), plain or gzip / BGZF (``pe_info.gz``: inflated on the host by the library).  The library parses them on the host threads (``vs_info_parse``) and builds the table from
-        the cells (``vs_links_from_cells``: dense below ``sparse_min_nodes`` nodes -- 0: the library's 32 768 --, CSR rows
-        from there on); a file that holds a carriage return or a byte outside ASCII is left to Python's text mode, the
-        loop over ``formats.read_pe_text``."""
+        non-zero count only), plain or gzip / BGZF (``pe_info.gz``).
+
+        ``device_parse=True`` (``vs_links_from_info``): the files are read where the table lives.  A file that is BGZF from
+        end to end is uploaded compressed and inflated on the device, a plain file is uploaded as it is; windows of
+        ``window_bytes`` of text (0: 256 MB) are scanned and parsed by kernels and the counts are added straight into the
+        table (dense below ``sparse_min_nodes`` nodes -- 0: the library's 32 768 --, CSR rows from there on).  Any other gzip
+        file, a line longer than a window and every error take the host reader.  It is the default for every file kind;
+        the legs of ``tools/info_read_legs.py`` that are to confirm it have NOT been measured yet (profiles/info_read.md):
+        a file kind whose device leg does not beat its host leg there is to go back to the host route by default.
+
+        ``device_parse=False``: the library parses on the host threads (``vs_info_parse``, gzip inflated by zlib on one
+        thread) and builds the table from the cells (``vs_links_from_cells``).
+
+        Either way a file that holds a carriage return or a byte outside ASCII is left to Python's text mode, the loop over
+        ``formats.read_pe_text``.  ``HipPeLinks.last_read`` says which route each file took."""
         names = list(names)
+        if device_parse:
+            got = cls._from_files_device(ctx, names, pe_file, st_file, sparse_min_nodes, window_bytes)
+            if got is None:
+                HipPeLinks.last_read = {"pe": {"route": "python"}, "st": {"route": "python"}}
+                return cls._from_files_python(ctx, names, pe_file, st_file)
+            return got
         cells = []
         for path in (pe_file, st_file):
             got = cls._parse_cells(names, path)
             if got is None:
+                HipPeLinks.last_read = {"pe": {"route": "python"}, "st": {"route": "python"}}
                 return cls._from_files_python(ctx, names, pe_file, st_file)
             cells.append(got)
         rows = np.concatenate([c[0] for c in cells])
@@ -154,7 +178,45 @@ class HipPeLinks(PeLinks):
         h = C.c_void_p()
         nat.check(ctx._h, nat.lib().vs_links_from_cells(ctx._h, _ptr(rows), _ptr(cols), _ptr(vals), rows.size, len(names),
                                                         sparse_min_nodes, C.byref(h)))
+        HipPeLinks.last_read = {"pe": {"route": "host", "cells": int(cells[0][0].size)},
+                                "st": {"route": "host", "cells": int(cells[1][0].size)}}
         return cls(ctx, h, names)
+
+    @classmethod
+    def _from_files_device(cls, ctx, names: Sequence[str], pe_file: str, st_file: str, sparse_min_nodes: int, window_bytes: int):
+        """``vs_links_from_info``: the table, or None when the files are Python's to read (a carriage return, a byte outside
+        ASCII, a name the library cannot be handed as bytes)."""
+        try:
+            enc = [s.encode("ascii") for s in names]
+        except UnicodeEncodeError:
+            return None
+        off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        if enc:
+            off[1:] = np.cumsum([len(b) for b in enc], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8)
+        info = (C.c_uint64 * 16)()
+        h = C.c_void_p()
+        rc = nat.lib().vs_links_from_info(ctx._h, pe_file.encode(), st_file.encode(), blob.ctypes.data, off.ctypes.data, len(enc),
+                                          sparse_min_nodes, window_bytes, C.byref(h), info)
+        if rc != nat.VS_OK:
+            msg = (nat.lib().vs_last_error(ctx._h) or b"?").decode("utf-8", "replace")
+            if rc == nat.VS_E_ARG and "cannot open" in msg:
+                raise FileNotFoundError(msg)
+            if rc == nat.VS_E_ARG:
+                raise ValueError(msg)  # (a malformed line, a corrupt gzip stream: what the host route raises)
+            raise nat.NativeError(rc, msg)
+        keys = ("route", "lines", "skipped", "cells", "members_device", "text_bytes", "windows", "flags")
+        read = {}
+        for f, tag in enumerate(("pe", "st")):
+            rec = {k: int(info[8 * f + i]) for i, k in enumerate(keys)}
+            rec["route"] = cls._ROUTES.get(rec["route"], "none")
+            read[tag] = rec
+        if not h.value:
+            return None
+        HipPeLinks.last_read = read
+        table = cls(ctx, h, names)
+        table.read_info = read
+        return table
 
     @staticmethod
     def _parse_cells(names: Sequence[str], path: str):

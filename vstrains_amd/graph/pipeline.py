@@ -10,6 +10,7 @@ checker from ``oracle/``.
 from __future__ import annotations
 
 import gc
+import os
 import sys
 import time
 from typing import Dict
@@ -183,8 +184,21 @@ def _run(args, logger, backend=None):
     pre = prepare(args, logger)
 
     t0 = time.time()
-    table = backend.pe_links("{0}/gfa/s_graph_L1.gfa".format(out), "{0}/aln".format(out), args.fwd, args.rve,
-                             pre.ksize, list(pre.nodes1.keys()))
+    files = getattr(args, "pe_text_files", None)
+    if files:
+        # (extension, --pe-text-from) the hand-off of VStrains_SPAdes.py:119-138 taken from an earlier count: nothing is
+        # counted, OUT/aln stays empty
+        os.makedirs("{0}/aln".format(out), exist_ok=True)
+        logger.info("paired end information is read from {0} and {1}; {2} and {3} are not opened".format(
+            files[0], files[1], args.fwd, args.rve))
+        table = backend.links_from_files(list(pre.nodes1.keys()), files[0], files[1])
+        unknown = sum(int(rec.get("skipped", 0)) for rec in (getattr(table, "read_info", None) or {}).values())
+        if unknown:
+            logger.warning("{0} lines of the paired end information name a node that s_graph_L1 does not have "
+                           "(counted under another -mc?); they are ignored".format(unknown))
+    else:
+        table = backend.pe_links("{0}/gfa/s_graph_L1.gfa".format(out), "{0}/aln".format(out), args.fwd, args.rve,
+                                 pre.ksize, list(pre.nodes1.keys()))
     timings["pe_inference_s"] = time.time() - t0
     logger.info("paired end information stored")
 
