@@ -256,6 +256,43 @@ int vs_bgzf_shard_plan(const uint32_t *counts, uint64_t n_members, int no_final_
 int vs_fastq_stream_open_range(vs_ctx *ctx, const char *fwd_path, const char *rve_path, const uint64_t range[6], uint64_t n_pairs,
                                vs_fastq_stream **out);
 
+/* Read pairs from ONE collated BAM file (additions to ABI 10): the BGZF members inflated on the device as for FASTQ, the
+ * records found there by following the chain of block_size fields from the end of the header, the 4-bit bases packed by
+ * the one packer.  The file stands for the FASTQ pair `samtools fastq -1 -2` would write: records with flag 0x100 or 0x800
+ * are dropped, records that are not 0x1 with exactly one of 0x40 / 0x80 are dropped ("other"), the rest are taken two at
+ * a time, each couple one 0x40 (the forward end) and one 0x80 record in either order; an end with 0x10 is reversed and
+ * complemented.  Two firsts or two seconds in a couple, or an odd record at the end, are VS_E_ARG ("not collated").
+ *   vs_bam_stream_open  : a regular file whose first BGZF member inflates to "BAM\1" (a FIFO or anything else: VS_E_ARG);
+ *                         the header (text and references) is inflated on the host with zlib and skipped on the device
+ *   vs_bam_stream_next  : as vs_fastq_stream_next; a record cut by the end of the file ("truncated record") and a record
+ *                         whose block_size is below 32 or smaller than its own fields need (named by its number from 0 in
+ *                         the file) are VS_E_ARG
+ *   vs_bam_stream_info  : info[0] = pairs delivered, [1] = records seen, [2] = dropped for 0x100 / 0x800, [3] = dropped as
+ *                         other, [4] = members inflated on the device, [5] = text bytes (inflated), [6] = file bytes read,
+ *                         [7] = 1 once the end of the input has been reached
+ *   vs_bam_stream_close : as vs_fastq_stream_close
+ * VS_BAM_SEG (tests only, like VS_STREAM_CHUNK) sets the segment of the chain passes, 64 .. 12288 bytes.
+ *
+ * Test aids, the chain alone.  bytes[0, n) are inflated BAM bytes, a record starts at `skip`; seg = 0 is the default.
+ * recs[4 i ..] for the i-th whole record on the chain (at most cap_recs are written): its offset, flag | class << 16
+ * (class 0 first, 1 second, 2 dropped for 0x900, 3 other, 4 malformed), l_seq, the offset of its bases; ends[2 c], [2 c + 1]
+ * (at most cap_ends entries) = the record indices of the forward and the reverse end of couple c.  info[0] = records,
+ * [1] = records that take part, [2] = how the chain ended (0 at byte n, 1 in front of a record the window cuts, 2 at a
+ * block_size < 32), [3] = where, [4] = index of the first malformed record, [5] = the first couple that is not one first
+ * and one second (~0: none).  vs_bam_scan_host: the same text with one host thread; vs_bam_scan_text: the kernels. */
+typedef struct vs_bam_stream vs_bam_stream;
+int vs_bam_stream_open(vs_ctx *ctx, const char *path, vs_bam_stream **out);
+int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_reads **out, uint64_t *n_pairs);
+int vs_bam_stream_info(const vs_bam_stream *s, uint64_t info[8]);
+void vs_bam_stream_close(vs_bam_stream *s);
+int vs_bam_scan_host(const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t *recs, uint64_t cap_recs, uint32_t *ends,
+                     uint64_t cap_ends, uint64_t info[6]);
+int vs_bam_scan_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t *recs, uint64_t cap_recs,
+                     uint32_t *ends, uint64_t cap_ends, uint64_t info[6]);
+/* The header of a BAM at the front of a file (host: zlib on its leading BGZF members): *header_bytes = inflated bytes in
+ * front of the first record.  VS_E_ARG with a message when the file is no BAM. */
+int vs_bam_header(const char *path, uint64_t *header_bytes);
+
 /* pe_info / st_info text (PE_Inference.py:194-205): "{id_i}:{id_j}:{count}\n" for all i, j in
  * row-major order, zeros included.  ids: the n node names concatenated, id_off[n+1]; mat: HOST
  * n*n int64.  Formatted on all host cores, one write(). */

@@ -1,0 +1,709 @@
+// Read pairs from one collated BAM file: the streamed ingest of vs_stream.hip with a different way to find the records.
+//
+// Host: the Reader of vs_stream_reader.h fills its ring with whole BGZF members and k_inflate (vs_inflate.hip) inflates them
+// into the window, CRC32 checked, exactly as for BGZF FASTQ.  Only the header is looked at on the host: vs_bam_header
+// inflates the leading members with zlib until magic, text and references are consumed and hands the device the number of
+// inflated bytes to skip (it may be larger than a window).
+//
+// Device: the window starts at a record boundary.  A record is block_size = le32(p) and block_size bytes, so the record
+// starts are a serial chain; they are found exactly, from the known start, in three passes (vs_bam_core.h):
+//   k_bam_exits    a workgroup per segment of `seg` bytes: next(p) of every byte into LDS, pointer doubling until every
+//                  entry has left the segment (next is strictly forward, so any value read while another lane writes it is
+//                  still a point of the same chain), then 2 bytes per window byte to memory;
+//   k_bam_walk     one lane: from the start through the tables, one lookup per segment the chain touches; the entry
+//                  offset of each such segment, how and where the chain ends;
+//   k_bam_count    one thread per segment with an entry walks its records (tens of them): records, and records that take part;
+//   (k_sl_scan)    both counts to offsets;
+//   k_bam_scatter  the same walk: offset, flag and class, l_seq and sequence offset of every record at its index, the
+//                  index of every record that takes part at its compacted index; the first malformed record by atomicMin;
+// and per block of n couples
+//   k_bam_ends     couple c = compacted records 2c, 2c + 1: one first and one second or the first bad couple by atomicMin;
+//                  the forward and the reverse record of every couple, the lengths and packed words of the ends, the cut;
+//   k_bam_tally    records seen and dropped, by class, among those the block passes;
+// then k_sl_scan for the word offsets, k_pack_reads<PackBam> and vs_reads_finish as every block is built.
+// No kernel waits for another workgroup; every window read and LDS index is tested against its range.
+//
+// The window is scanned once per appended chunk; blocks are cut from the scanned records with a cursor.  The carry is
+// everything from the first record not delivered: an odd record, or the record the window's end cuts.
+#include "vs_stream_reader.h"
+#include "vs_bam_core.h"
+
+#define BAM_TPB 256
+
+namespace {
+
+enum {
+    B_END = 0,      // BAM_END_* of the walk
+    B_STOP = 1,     // where
+    B_NREC = 2,
+    B_NPART = 3,
+    B_MALFORMED = 4,  // index of the first malformed record, ~0u: none
+    B_BADCOUPLE = 5,  // first couple of the block that is not one first and one second, ~0u: none
+    B_CUT = 6,        // offset of the first record behind the block
+    B_CUTREC = 7,     // ... and its index
+    B_MAXLEN = 8,
+    B_TOO_LONG = 9,
+    B_WORDS = 10,
+    B_INVALID = 11,
+    B_BAD_MEMBER = 12,  // first BGZF member the device rejected (a running index), ~0u: none
+    B_TALLY = 16,       // + class: records passed so far (cumulative)
+    B_ALL = 24
+};
+
+}  // namespace
+
+// ---- kernels -----------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(BAM_TPB) k_bam_exits(const uint8_t *__restrict__ win, uint64_t n, uint32_t seg, uint16_t *__restrict__ tab) {
+    extern __shared__ uint32_t e[];  // seg words: below 2^31 the offset in the segment the chain goes to next, else 2^31 | exit code
+    __shared__ uint32_t changed;
+    constexpr uint32_t T = 0x80000000u;
+    const uint64_t lo = (uint64_t)blockIdx.x * seg;
+    if (lo >= n) return;
+    const uint64_t hi = lo + seg < n ? lo + seg : n;
+    const uint32_t len = (uint32_t)(hi - lo);
+    for (uint32_t i = threadIdx.x; i < len; i += BAM_TPB) {
+        uint64_t nx = 0;
+        const int st = bam_step(win, n, lo + i, &nx);
+        e[i] = st == BAM_STEP_NEED ? T | (uint32_t)BAM_X_NEED : st == BAM_STEP_DEAD ? T | (uint32_t)BAM_X_DEAD
+               : nx >= hi ? T | bam_exit_encode(nx, hi) : (uint32_t)(nx - lo);
+    }
+    __syncthreads();
+    for (;;) {
+        if (threadIdx.x == 0) changed = 0u;
+        __syncthreads();
+        bool mine = false;
+        for (uint32_t i = threadIdx.x; i < len; i += BAM_TPB) {
+            const uint32_t v = e[i];
+            if (v & T) continue;
+            const uint32_t w = v < len ? e[v] : T | (uint32_t)BAM_X_DEAD;  // (v < len always: it came from nx < hi)
+            e[i] = w;
+            mine = mine || !(w & T);
+        }
+        if (mine) changed = 1u;
+        __syncthreads();
+        const bool again = changed != 0u;
+        __syncthreads();
+        if (!again) break;
+    }
+    for (uint32_t i = threadIdx.x; i < len; i += BAM_TPB) tab[lo + i] = (uint16_t)(e[i] & 0xFFFFu);
+}
+
+__global__ void __launch_bounds__(VS_WAVE) k_bam_walk(const uint8_t *__restrict__ win, uint64_t n, const uint16_t *__restrict__ tab, uint32_t seg,
+                                                      uint64_t start, uint32_t *__restrict__ entry, uint32_t *__restrict__ st) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    uint64_t stop = 0;
+    st[B_END] = (uint32_t)bam_walk(win, n, tab, seg, start, entry, &stop);
+    st[B_STOP] = (uint32_t)stop;
+}
+
+__global__ void __launch_bounds__(BAM_TPB) k_bam_count(const uint8_t *__restrict__ win, uint64_t n, uint32_t seg, uint32_t n_seg,
+                                                       const uint32_t *__restrict__ entry, uint32_t *__restrict__ cnt_rec, uint32_t *__restrict__ cnt_part) {
+    const uint32_t s = blockIdx.x * BAM_TPB + threadIdx.x;
+    if (s >= n_seg) return;
+    uint32_t nr = 0, np = 0;
+    if (entry[s] != BAM_NONE) {
+        const uint64_t lo = (uint64_t)s * seg, hi = lo + seg < n ? lo + seg : n;
+        uint64_t p = entry[s], at = 0;
+        while (bam_seg_next(win, n, hi, &p, &at)) {
+            nr++;
+            if ((bam_classify(win, at).flag_cls >> 16) <= (uint32_t)BAM_C_SECOND) np++;
+        }
+    }
+    cnt_rec[s] = nr;
+    cnt_part[s] = np;
+}
+
+__global__ void __launch_bounds__(BAM_TPB) k_bam_scatter(const uint8_t *__restrict__ win, uint64_t n, uint32_t seg, uint32_t n_seg,
+                                                         const uint32_t *__restrict__ entry, const uint32_t *__restrict__ base_rec,
+                                                         const uint32_t *__restrict__ base_part, uint32_t n_rec, uint32_t n_part,
+                                                         uint4 *__restrict__ recs, uint32_t *__restrict__ part, uint32_t *__restrict__ st) {
+    const uint32_t s = blockIdx.x * BAM_TPB + threadIdx.x;
+    if (s >= n_seg || entry[s] == BAM_NONE) return;
+    const uint64_t lo = (uint64_t)s * seg, hi = lo + seg < n ? lo + seg : n;
+    uint64_t p = entry[s], at = 0;
+    uint32_t ri = base_rec[s], pi = base_part[s];
+    while (bam_seg_next(win, n, hi, &p, &at)) {
+        const BamRec r = bam_classify(win, at);
+        const uint32_t cls = r.flag_cls >> 16;
+        if (ri < n_rec) recs[ri] = make_uint4(r.off, r.flag_cls, r.l_seq, r.seq_off);
+        if (cls == (uint32_t)BAM_C_MALFORMED) atomicMin(&st[B_MALFORMED], ri);
+        if (cls <= (uint32_t)BAM_C_SECOND) {
+            if (pi < n_part) part[pi] = ri;
+            pi++;
+        }
+        ri++;
+    }
+}
+
+// one thread per end of the block (and one more for the closing word offset)
+__global__ void __launch_bounds__(BAM_TPB) k_bam_ends(const uint4 *__restrict__ recs, const uint32_t *__restrict__ part, uint32_t part0, uint32_t n_pairs,
+                                                      uint32_t n_rec, uint32_t stop, uint32_t *__restrict__ ends, uint32_t *__restrict__ meta,
+                                                      uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
+    const uint32_t e = blockIdx.x * BAM_TPB + threadIdx.x, n_ends = 2u * n_pairs;
+    if (e == 0 && n_pairs) {
+        const uint32_t after = part[part0 + n_ends - 1u] + 1u;
+        st[B_CUTREC] = after;
+        st[B_CUT] = after < n_rec ? recs[after].x : stop;
+    }
+    if (e > n_ends) return;
+    if (e == n_ends) {
+        wcnt[e] = 0u;
+        return;
+    }
+    const uint32_t c = e >> 1, a = part[part0 + 2u * c], b = part[part0 + 2u * c + 1u];
+    const uint32_t fa = recs[a].y, fb = recs[b].y;
+    if (!bam_couple_ok(fa, fb) && !(e & 1u)) atomicMin(&st[B_BADCOUPLE], c);
+    const bool a_first = (fa >> 16) == (uint32_t)BAM_C_FIRST;
+    const uint32_t r = ((e & 1u) != 0u) == a_first ? b : a;  // (the first is the forward end)
+    ends[e] = r;
+    const uint32_t len = recs[r].z;
+    if (len > VS_LEN_MASK) {
+        atomicMin(&st[B_TOO_LONG], e);
+        meta[e] = 0u;
+        wcnt[e] = 0u;
+        return;
+    }
+    meta[e] = len;
+    wcnt[e] = (len + 15u) >> 4;
+    atomicMax(&st[B_MAXLEN], len);
+}
+
+__global__ void __launch_bounds__(BAM_TPB) k_bam_tally(const uint4 *__restrict__ recs, uint32_t from, uint32_t to, uint32_t *__restrict__ tally) {
+    const uint32_t i = from + blockIdx.x * BAM_TPB + threadIdx.x;
+    const uint32_t cls = i < to ? recs[i].y >> 16 : 0xFFu;
+#pragma unroll
+    for (uint32_t k = 0; k <= (uint32_t)BAM_C_MALFORMED; k++) {
+        const unsigned long long b = __ballot(cls == k);
+        if ((threadIdx.x & (VS_WAVE - 1u)) == 0 && b) atomicAdd(&tally[k], (uint32_t)__popcll(b));
+    }
+}
+
+// ---- the chain on a device window ---------------------------------------------------------------------------------------
+namespace {
+
+uint32_t seg_checked(uint32_t seg) { return seg == 0 ? BAM_SEG_DEFAULT : std::min<uint32_t>(std::max<uint32_t>(seg, BAM_SEG_MIN), BAM_SEG_MAX); }
+
+struct BamScan {
+    VsDevBuf tab, entry, cnt_rec, cnt_part, recs, part;
+    uint32_t n_rec = 0, n_part = 0, end = BAM_END_CLEAN, stop = 0, malformed = BAM_NONE;
+};
+
+// the records of win[0, n) on the chain from `start`, on stream st; d_stat / h_stat: B_ALL words each (synchronises st)
+int bam_scan_device(vs_ctx *ctx, hipStream_t st, const uint8_t *win, uint64_t n, uint64_t start, uint32_t seg, BamScan &sc, uint32_t *d_stat,
+                    uint32_t *h_stat) {
+    const uint64_t n_seg64 = (n + seg - 1u) / seg;
+    if (n > STREAM_MAX_WINDOW || n_seg64 > 0x7FFFFFFFu) return vs_fail(ctx, VS_E_RANGE, "a BAM window of %llu bytes", (unsigned long long)n);
+    const uint32_t n_seg = (uint32_t)n_seg64;
+    sc.n_rec = sc.n_part = 0;
+    sc.end = BAM_END_CLEAN;
+    sc.stop = (uint32_t)n;
+    sc.malformed = BAM_NONE;
+    VS_HIP(ctx, hipMemsetAsync(d_stat, 0, sizeof(uint32_t) * B_BAD_MEMBER, st));
+    VS_HIP(ctx, hipMemsetAsync(d_stat + B_MALFORMED, 0xFF, sizeof(uint32_t) * 2, st));
+    if (n_seg) {
+        if (int rc = reserve_n<uint16_t>(ctx, sc.tab, n)) return rc;
+        if (int rc = reserve_n<uint32_t>(ctx, sc.entry, n_seg)) return rc;
+        if (int rc = reserve_n<uint32_t>(ctx, sc.cnt_rec, (size_t)n_seg + 1u)) return rc;
+        if (int rc = reserve_n<uint32_t>(ctx, sc.cnt_part, (size_t)n_seg + 1u)) return rc;
+        VS_HIP(ctx, hipMemsetAsync(sc.entry.ptr(), 0xFF, sizeof(uint32_t) * n_seg, st));
+        const unsigned grid = (n_seg + BAM_TPB - 1u) / BAM_TPB;
+        hipLaunchKernelGGL(k_bam_exits, dim3(n_seg), dim3(BAM_TPB), sizeof(uint32_t) * seg, st, win, n, seg, sc.tab.as<uint16_t>());
+        VS_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_bam_walk, dim3(1), dim3(VS_WAVE), 0, st, win, n, sc.tab.as<const uint16_t>(), seg, start, sc.entry.as<uint32_t>(), d_stat);
+        VS_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_bam_count, dim3(grid), dim3(BAM_TPB), 0, st, win, n, seg, n_seg, sc.entry.as<const uint32_t>(), sc.cnt_rec.as<uint32_t>(),
+                           sc.cnt_part.as<uint32_t>());
+        VS_HIP(ctx, hipGetLastError());
+        vs_launch_scan_u32(st, sc.cnt_rec.as<uint32_t>(), n_seg, d_stat + B_NREC);
+        VS_HIP(ctx, hipGetLastError());
+        vs_launch_scan_u32(st, sc.cnt_part.as<uint32_t>(), n_seg, d_stat + B_NPART);
+        VS_HIP(ctx, hipGetLastError());
+    }
+    VS_HIP(ctx, hipMemcpyAsync(h_stat, d_stat, sizeof(uint32_t) * B_ALL, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
+    if (!n_seg) return VS_OK;
+    sc.n_rec = h_stat[B_NREC];
+    sc.n_part = h_stat[B_NPART];
+    sc.end = h_stat[B_END];
+    sc.stop = h_stat[B_STOP];
+    if (int rc = reserve_n<uint4>(ctx, sc.recs, (size_t)sc.n_rec + 1u)) return rc;
+    if (int rc = reserve_n<uint32_t>(ctx, sc.part, (size_t)sc.n_part + 1u)) return rc;
+    if (sc.n_rec) {
+        hipLaunchKernelGGL(k_bam_scatter, dim3((n_seg + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, st, win, n, seg, n_seg, sc.entry.as<const uint32_t>(),
+                           sc.cnt_rec.as<const uint32_t>(), sc.cnt_part.as<const uint32_t>(), sc.n_rec, sc.n_part, sc.recs.as<uint4>(), sc.part.as<uint32_t>(),
+                           d_stat);
+        VS_HIP(ctx, hipGetLastError());
+        VS_HIP(ctx, hipMemcpyAsync(h_stat + B_MALFORMED, d_stat + B_MALFORMED, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VS_HIP(ctx, hipStreamSynchronize(st));
+        sc.malformed = h_stat[B_MALFORMED];
+    }
+    return VS_OK;
+}
+
+// the ends of couples [part0 / 2, part0 / 2 + n_pairs) of a scanned window: ends, lengths (meta), words per end (wcnt)
+void launch_ends(hipStream_t st, const BamScan &sc, uint32_t part0, uint32_t n_pairs, uint32_t *ends, uint32_t *meta, uint32_t *wcnt, uint32_t *d_stat) {
+    hipLaunchKernelGGL(k_bam_ends, dim3((2u * n_pairs + 1u + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, st, sc.recs.as<const uint4>(),
+                       sc.part.as<const uint32_t>(), part0, n_pairs, sc.n_rec, sc.stop, ends, meta, wcnt, d_stat);
+}
+
+void fill_info(uint64_t info[6], uint64_t n_rec, uint64_t n_part, uint32_t end, uint64_t stop, uint32_t malformed, uint32_t bad_couple) {
+    info[0] = n_rec;
+    info[1] = n_part;
+    info[2] = end;
+    info[3] = stop;
+    info[4] = malformed == BAM_NONE ? ~0ull : malformed;
+    info[5] = bad_couple == BAM_NONE ? ~0ull : bad_couple;
+}
+
+}  // namespace
+
+// ---- the stream ------------------------------------------------------------------------------------------------------------
+struct vs_bam_stream {
+    int device = 0;
+    hipStream_t st = nullptr;
+    Reader rd;
+    VsDevBuf win[2];
+    int cur = 0;
+    size_t size = 0;
+    bool eof = false;
+    VsDevBuf comp, dir, mstat;
+    uint64_t members_dev = 0;
+    uint64_t skip = 0;  // header bytes still to drop from the front
+    uint32_t seg = BAM_SEG_DEFAULT;
+    BamScan sc;
+    bool scanned = false;
+    uint32_t rec_cur = 0, part_cur = 0;  // the first record / compacted record of the scanned window not yet delivered
+    uint64_t first_record = 0;           // file-wide number of the window's record 0
+    VsDevBuf stat_buf, d_wcnt, d_ends;
+    VsPinnedBuf h_stat_buf;
+    uint32_t *d_stat = nullptr, *h_stat = nullptr;
+    uint64_t pairs = 0;
+    bool done = false;
+    int failed = VS_OK;
+    std::string failed_msg;
+};
+
+namespace {
+
+int bam_fail(vs_ctx *ctx, vs_bam_stream *s, int code, const std::string &msg) {
+    s->done = true;
+    s->failed = code;
+    s->failed_msg = msg;
+    return vs_fail(ctx, code, "%s", msg.c_str());
+}
+
+std::string rec_msg(const vs_bam_stream *s, uint64_t rec, const char *what) {
+    return s->rd.path + ": record " + std::to_string(rec) + what;
+}
+
+const char *NOT_COLLATED = ": the file is not collated (mates do not follow each other); run `samtools collate` on it first";
+
+// the window after its first `cut` bytes have gone: the leftover to the front of the other buffer
+int bam_drop_front(vs_ctx *ctx, vs_bam_stream *s, size_t cut) {
+    const size_t rest = s->size - cut;
+    const int o = s->cur ^ 1;
+    if (int rc = reserve_n<uint8_t>(ctx, s->win[o], ((rest + 15u) & ~(size_t)15u) + 16u)) return rc;
+    if (rest) VS_HIP(ctx, hipMemcpyAsync(s->win[o].as<uint8_t>(), s->win[s->cur].as<uint8_t>() + cut, rest, hipMemcpyDeviceToDevice, s->st));
+    s->cur = o;
+    s->size = rest;
+    return VS_OK;
+}
+
+// the reader's next slot appended to the window: its bytes uploaded, or its BGZF members uploaded and inflated there
+int bam_append(vs_ctx *ctx, vs_bam_stream *s) {
+    Slot &sl = s->rd.take();
+    struct Back {
+        Reader &r;
+        ~Back() { r.give_back(); }
+    } back = {s->rd};
+    if (s->size + sl.text > STREAM_MAX_WINDOW)
+        return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete pair", s->rd.path.c_str(), (unsigned long long)(s->size + sl.text));
+    const size_t need = ((s->size + sl.text + 15u) & ~(size_t)15u) + 16u;
+    if (s->win[s->cur].capacity() < need) {
+        const int o = s->cur ^ 1;
+        if (int rc = reserve_n<uint8_t>(ctx, s->win[o], need)) return rc;
+        if (s->size) VS_HIP(ctx, hipMemcpyAsync(s->win[o].as<uint8_t>(), s->win[s->cur].as<uint8_t>(), s->size, hipMemcpyDeviceToDevice, s->st));
+        s->cur = o;
+    }
+    uint8_t *dst = s->win[s->cur].as<uint8_t>() + s->size;
+    if (sl.comp) {
+        const uint32_t nm = sl.n_members;
+        if (nm) {
+            if (int rc = reserve_n<uint8_t>(ctx, s->comp, sl.len + 16u)) return rc;
+            if (int rc = reserve_n<vs_bgzf_member>(ctx, s->dir, (size_t)nm)) return rc;
+            if (int rc = reserve_n<uint32_t>(ctx, s->mstat, (size_t)nm)) return rc;
+            const vs_bgzf_member *dir = (const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()) - nm;  // (member i at dir[nm - 1 - i])
+            if (sl.len) VS_HIP(ctx, hipMemcpyAsync(s->comp.as<uint8_t>(), sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st));
+            VS_HIP(ctx, hipMemcpyAsync(s->dir.as<vs_bgzf_member>(), dir, sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, s->st));
+            vs_launch_inflate(s->st, s->comp.as<uint8_t>(), sl.len, dst, sl.text, s->dir.as<vs_bgzf_member>(), nm, s->mstat.as<uint32_t>(),
+                              s->d_stat + B_BAD_MEMBER, (uint32_t)s->members_dev, 1);
+            VS_HIP(ctx, hipGetLastError());
+            s->members_dev += nm;
+        }
+    } else if (sl.len) {
+        VS_HIP(ctx, hipMemcpyAsync(dst, sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st));
+    }
+    s->size += sl.text;
+    s->eof = sl.last;
+    VS_HIP(ctx, hipStreamSynchronize(s->st));  // (the slot goes back: its bytes are on the device)
+    return VS_OK;
+}
+
+// records [rec_cur, upto) of the scanned window have been passed: counted by class, the sums copied to the host (the copy is
+// complete once the stream has been synchronised)
+int bam_pass(vs_ctx *ctx, vs_bam_stream *s, uint32_t upto) {
+    if (upto > s->rec_cur) {
+        hipLaunchKernelGGL(k_bam_tally, dim3((upto - s->rec_cur + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, s->st, s->sc.recs.as<const uint4>(),
+                           s->rec_cur, upto, s->d_stat + B_TALLY);
+        VS_HIP(ctx, hipGetLastError());
+        VS_HIP(ctx, hipMemcpyAsync(s->h_stat + B_TALLY, s->d_stat + B_TALLY, sizeof(uint32_t) * (B_ALL - B_TALLY), hipMemcpyDeviceToHost, s->st));
+    }
+    s->rec_cur = upto;
+    return VS_OK;
+}
+
+// the end of the input: what is left in the window is passed, and said if it is no whole couple
+int bam_finish(vs_ctx *ctx, vs_bam_stream *s) {
+    if (s->rd.err != VS_OK) return bam_fail(ctx, s, s->rd.err, s->rd.err_msg);
+    uint32_t odd = BAM_NONE;
+    if (s->scanned) {
+        if (s->sc.n_part - s->part_cur == 1u)
+            VS_HIP(ctx, hipMemcpyAsync(&odd, s->sc.part.as<uint32_t>() + s->part_cur, sizeof odd, hipMemcpyDeviceToHost, s->st));
+        if (int rc = bam_pass(ctx, s, s->sc.n_rec)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+        VS_HIP(ctx, hipStreamSynchronize(s->st));
+        if (s->sc.end == BAM_END_CUT)
+            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + s->sc.n_rec, ": truncated record (the file ends inside it)"));
+        if (odd != BAM_NONE)
+            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + odd, " has no mate behind it") + NOT_COLLATED);
+    } else if (s->skip) {
+        return bam_fail(ctx, s, VS_E_STATE, s->rd.path + " ends inside its header (did it change after it was opened?)");
+    }
+    s->done = true;
+    return VS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vs_bam_header(const char *path, uint64_t *header_bytes) {
+    if (!path || !header_bytes) return vs_fail(nullptr, VS_E_ARG, "vs_bam_header: bad argument");
+    *header_bytes = 0;
+    struct stat sb;
+    if (stat(path, &sb) != 0) return vs_fail(nullptr, VS_E_ARG, "cannot open %s: %s", path, strerror(errno));
+    if (!S_ISREG(sb.st_mode))  // (before it is opened: opening a FIFO would wait for its writer)
+        return vs_fail(nullptr, VS_E_ARG, "%s is not a regular file: BAM is read from a regular file only (a FIFO is out of scope)", path);
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return vs_fail(nullptr, VS_E_ARG, "cannot open %s: %s", path, strerror(errno));
+    struct FdGuard {
+        int fd;
+        ~FdGuard() { close(fd); }
+    } guard = {fd};
+    std::vector<uint8_t> in, text;
+    size_t in_at = 0;
+    bool in_eof = false;
+    // header bytes needed so far, as far as the bytes at hand say: magic, l_text, text, n_ref, then per reference l_name, name, l_ref
+    auto needed = [&](uint64_t *need) -> int {  // 0: *need bytes are the whole header; 1: *need bytes are needed to say more; 2: no BAM
+        auto u32 = [&](uint64_t at) { return (uint64_t)bam_le32(text.data() + at); };
+        if (text.size() >= 4 && memcmp(text.data(), "BAM\1", 4) != 0) return 2;
+        uint64_t at = 8;
+        if (text.size() < at) { *need = at; return 1; }
+        at += u32(4) + 4u;
+        if (text.size() < at) { *need = at; return 1; }
+        const uint64_t n_ref = u32(at - 4u);
+        for (uint64_t i = 0; i < n_ref; i++) {
+            if (text.size() < at + 4u) { *need = at + 4u; return 1; }
+            at += 4u + u32(at) + 4u;
+            if (text.size() < at) { *need = at; return 1; }
+        }
+        *need = at;
+        return 0;
+    };
+    for (;;) {
+        uint64_t need = 0;
+        const int st = needed(&need);
+        if (st == 2) return vs_fail(nullptr, VS_E_ARG, "%s is not a BAM file (its first bytes do not inflate to \"BAM\\1\")", path);
+        if (st == 0) {
+            *header_bytes = need;
+            return VS_OK;
+        }
+        // one more member
+        vs_bgzf_member mb;
+        size_t msize = 0;
+        int pst;
+        while ((pst = vs_bgzf_parse(in.data() + in_at, in.size() - in_at, &mb, &msize)) == 1 && !in_eof) {
+            const size_t have = in.size();
+            in.resize(have + (1u << 16));
+            ssize_t got;
+            do got = read(fd, in.data() + have, 1u << 16);
+            while (got < 0 && errno == EINTR);
+            if (got < 0) return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, strerror(errno));
+            in.resize(have + (size_t)got);
+            if (got == 0) in_eof = true;
+        }
+        if (pst != 0) return vs_fail(nullptr, VS_E_ARG, "%s is not a BAM file (no whole BGZF member where its header goes on)", path);
+        const size_t have = text.size();
+        text.resize(have + mb.isize);
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (inflateInit2(&zs, -15) != Z_OK) return vs_fail(nullptr, VS_E_OOM, "%s: zlib cannot start", path);
+        zs.next_in = in.data() + in_at + mb.in_off;
+        zs.avail_in = mb.in_len;
+        zs.next_out = text.data() + have;
+        zs.avail_out = mb.isize;
+        const int rc = mb.isize ? inflate(&zs, Z_FINISH) : Z_STREAM_END;
+        const bool whole = (rc == Z_STREAM_END || (rc == Z_OK && mb.isize == 0)) && zs.avail_out == 0;
+        inflateEnd(&zs);
+        if (!whole) return vs_fail(nullptr, VS_E_ARG, "%s: not a complete gzip stream (zlib code %d)", path, rc);
+        in_at += msize;
+        if (in_at == in.size() && in_eof && text.size() == have && needed(&need) != 0)
+            return vs_fail(nullptr, VS_E_ARG, "%s is not a BAM file (it ends inside its header)", path);
+    }
+}
+
+int vs_bam_stream_open(vs_ctx *ctx, const char *path, vs_bam_stream **out) {
+    if (!ctx || !path || !out) return vs_fail(ctx, VS_E_ARG, "vs_bam_stream_open: bad argument");
+    *out = nullptr;
+    uint64_t header = 0;
+    if (int rc = vs_bam_header(path, &header)) return vs_fail(ctx, rc, "%s", vs_last_error(nullptr));
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    vs_bam_stream *s = new vs_bam_stream();
+    s->device = ctx->device;
+    s->skip = header;
+    if (const char *ev = getenv("VS_BAM_SEG")) s->seg = seg_checked((uint32_t)atoll(ev));  // (tests: records across segments)
+    Reader &r = s->rd;
+    r.path = path;
+    r.device = ctx->device;
+    if (const char *ev = getenv("VS_STREAM_CHUNK")) r.chunk = std::max<size_t>(1u, (size_t)atoll(ev));
+    r.fd = open(path, O_RDONLY);
+    if (r.fd < 0) {
+        const int e = errno;
+        delete s;
+        return vs_fail(ctx, VS_E_ARG, "cannot open %s: %s", path, strerror(e));
+    }
+    hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
+    if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * B_ALL);
+    s->d_stat = s->stat_buf.as<uint32_t>();
+    if (e1 == hipSuccess) e1 = hipMemset(s->d_stat, 0, sizeof(uint32_t) * B_ALL);
+    if (e1 == hipSuccess) e1 = hipMemset(s->d_stat + B_BAD_MEMBER, 0xFF, sizeof(uint32_t));
+    if (e1 == hipSuccess) e1 = s->h_stat_buf.reserve(sizeof(uint32_t) * B_ALL);
+    s->h_stat = s->h_stat_buf.as<uint32_t>();
+    if (e1 != hipSuccess) {
+        vs_bam_stream_close(s);
+        return vs_fail(ctx, VS_E_HIP, "vs_bam_stream_open: %s", hipGetErrorString(e1));
+    }
+    memset(s->h_stat, 0, sizeof(uint32_t) * B_ALL);
+    r.th = std::thread([rp = &s->rd] { rp->run(); });
+    *out = s;
+    return VS_OK;
+}
+
+int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_reads **out, uint64_t *n_pairs) {
+    if (!ctx || !s || !out || !n_pairs) return vs_fail(ctx, VS_E_ARG, "vs_bam_stream_next: bad argument");
+    *out = nullptr;
+    *n_pairs = 0;
+    if (s->failed != VS_OK) return vs_fail(ctx, s->failed, "%s", s->failed_msg.c_str());
+    if (s->done) return VS_OK;
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    if (!max_pairs || max_pairs > (1ull << 30)) max_pairs = 1ull << 30;
+    hipStream_t st = s->st;
+    BamScan &sc = s->sc;
+    for (;;) {
+        if (s->scanned) {
+            if ((sc.n_part - s->part_cur) / 2u > 0u) break;
+            if (s->eof) return bam_finish(ctx, s);
+            // the carry: everything from the first record not delivered
+            uint32_t cut = sc.stop;
+            if (s->rec_cur < sc.n_rec) {
+                VS_HIP(ctx, hipMemcpyAsync(&cut, (const uint32_t *)(sc.recs.as<uint4>() + s->rec_cur), sizeof cut, hipMemcpyDeviceToHost, st));
+                VS_HIP(ctx, hipStreamSynchronize(st));
+            }
+            if (cut > s->size) return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": a record start beyond the window");
+            if (int rc = bam_drop_front(ctx, s, cut)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            s->first_record += s->rec_cur;
+            s->rec_cur = s->part_cur = 0;
+            s->scanned = false;
+        }
+        if (!s->eof) {
+            if (int rc = bam_append(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            if (s->skip) {  // the header goes, whole windows of it if need be
+                const size_t now = (size_t)std::min<uint64_t>(s->skip, s->size);
+                if (int rc = bam_drop_front(ctx, s, now)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+                s->skip -= now;
+                if (s->skip) {
+                    if (s->eof) return bam_finish(ctx, s);
+                    continue;
+                }
+            }
+        }
+        if (int rc = bam_scan_device(ctx, st, s->win[s->cur].as<const uint8_t>(), s->size, 0, s->seg, sc, s->d_stat, s->h_stat))
+            return bam_fail(ctx, s, rc, vs_last_error(ctx));
+        s->scanned = true;
+        if (s->h_stat[B_BAD_MEMBER] != BAM_NONE)
+            return bam_fail(ctx, s, VS_E_ARG, s->rd.path + ": not a complete gzip stream (BGZF member " + std::to_string(s->h_stat[B_BAD_MEMBER]) +
+                                                  " does not inflate to its CRC32 and size)");
+        if (sc.malformed != BAM_NONE)
+            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + sc.malformed, " is malformed: its name, cigar, sequence and quality need more than its block_size"));
+        if (sc.end == BAM_END_DEAD)
+            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + sc.n_rec, " is malformed: its block_size is below the 32 bytes of the fixed part"));
+    }
+    // ---- the block of n couples from the cursor
+    const uint64_t n = std::min<uint64_t>((sc.n_part - s->part_cur) / 2u, max_pairs), n_ends = 2u * n;
+    if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+    if (int rc = reserve_n<uint32_t>(ctx, s->d_ends, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+    vs_reads *r = new vs_reads();
+    r->cached = true;
+    auto fail = [&](hipError_t e, const char *oom_msg = nullptr) {
+        vs_reads_free(ctx, r);
+        if (e == hipErrorOutOfMemory && oom_msg) return bam_fail(ctx, s, VS_E_OOM, oom_msg);
+        return bam_fail(ctx, s, e == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, std::string("vs_bam_stream_next: ") + hipGetErrorString(e));
+    };
+    const char *no_buffers = "vs_bam_stream_next: device buffers for the block";
+    hipError_t e1 = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true);
+    if (e1 != hipSuccess) return fail(e1, no_buffers);
+    e1 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0, sizeof(uint32_t) * (B_BAD_MEMBER - B_BADCOUPLE), st);
+    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0xFF, sizeof(uint32_t), st);
+    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_TOO_LONG, 0xFF, sizeof(uint32_t), st);
+    if (e1 != hipSuccess) return fail(e1);
+    launch_ends(st, sc, s->part_cur, (uint32_t)n, s->d_ends.as<uint32_t>(), (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
+    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
+    vs_launch_scan_u32(st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + B_WORDS);
+    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
+    e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * B_BAD_MEMBER, hipMemcpyDeviceToHost, st);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+    if (e1 != hipSuccess) return fail(e1);
+    if (s->h_stat[B_BADCOUPLE] != BAM_NONE) {
+        uint32_t second = 0;
+        e1 = hipMemcpy(&second, sc.part.as<uint32_t>() + s->part_cur + 2u * s->h_stat[B_BADCOUPLE] + 1u, sizeof second, hipMemcpyDeviceToHost);
+        if (e1 != hipSuccess) return fail(e1);
+        vs_reads_free(ctx, r);
+        return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + second, " is the same end (first or second) of a pair as the record it is coupled with") + NOT_COLLATED);
+    }
+    if (s->h_stat[B_TOO_LONG] != BAM_NONE) {
+        vs_reads_free(ctx, r);
+        return bam_fail(ctx, s, VS_E_RANGE, s->rd.path + ": pair " + std::to_string(s->pairs + (s->h_stat[B_TOO_LONG] >> 1)) + " has a sequence of more than " +
+                                                std::to_string((unsigned)VS_LEN_MASK) + " bases");
+    }
+    const uint64_t words = s->h_stat[B_WORDS];
+    r->max_len = s->h_stat[B_MAXLEN];
+    if ((e1 = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e1, no_buffers);
+    vs_launch_pack_bam(st, BamEnds{s->win[s->cur].as<const uint8_t>(), (const uint32_t *)sc.recs.as<uint4>(), s->d_ends.as<const uint32_t>()}, r);
+    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
+    if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + B_INVALID, s->h_stat + B_INVALID)) != hipSuccess) return fail(e1);
+    if (bam_pass(ctx, s, s->h_stat[B_CUTREC]) != VS_OK) return fail(hipErrorUnknown);
+    if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
+    s->part_cur += (uint32_t)n_ends;
+    s->pairs += n;
+    *out = r;
+    *n_pairs = n;
+    return VS_OK;
+}
+
+int vs_bam_stream_info(const vs_bam_stream *s, uint64_t info[8]) {
+    if (!s || !info) return VS_E_ARG;
+    const uint32_t *t = s->h_stat + B_TALLY;
+    info[0] = s->pairs;
+    info[1] = (uint64_t)t[0] + t[1] + t[2] + t[3] + t[4];
+    info[2] = t[BAM_C_DROP900];
+    info[3] = t[BAM_C_OTHER];
+    info[4] = s->members_dev;
+    info[5] = s->rd.text_bytes;
+    info[6] = s->rd.raw_bytes;
+    info[7] = s->done ? 1u : 0u;
+    return VS_OK;
+}
+
+void vs_bam_stream_close(vs_bam_stream *s) {
+    if (!s) return;
+    s->rd.shut();
+    if (s->st) (void)hipStreamSynchronize(s->st);
+    if (s->st) (void)hipStreamDestroy(s->st);
+    delete s;
+}
+
+// ---- test aids: the chain alone -------------------------------------------------------------------------------------------
+int vs_bam_scan_host(const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t *recs, uint64_t cap_recs, uint32_t *ends,
+                     uint64_t cap_ends, uint64_t info[6]) {
+    if ((!bytes && n) || !info || (!recs && cap_recs) || (!ends && cap_ends) || n > STREAM_MAX_WINDOW || skip > n)
+        return vs_fail(nullptr, VS_E_ARG, "vs_bam_scan_host: bad argument");
+    seg = seg_checked(seg);
+    const uint64_t n_seg = (n + seg - 1u) / seg;
+    std::vector<uint16_t> tab(n);
+    std::vector<uint32_t> entry(n_seg, BAM_NONE);
+    for (uint64_t s = 0; s < n_seg; s++) bam_seg_exits_serial(bytes, n, s * seg, std::min<uint64_t>(n, (s + 1u) * seg), tab.data());
+    uint64_t stop = n;
+    const int end = n ? bam_walk(bytes, n, tab.data(), seg, skip, entry.data(), &stop) : BAM_END_CLEAN;
+    uint64_t n_rec = 0;
+    uint32_t malformed = BAM_NONE, bad_couple = BAM_NONE;
+    std::vector<BamRec> part;
+    std::vector<uint32_t> part_idx;
+    for (uint64_t s = 0; s < n_seg; s++) {
+        if (entry[s] == BAM_NONE) continue;
+        uint64_t p = entry[s], at = 0;
+        while (bam_seg_next(bytes, n, std::min<uint64_t>(n, (s + 1u) * seg), &p, &at)) {
+            const BamRec r = bam_classify(bytes, at);
+            const uint32_t cls = r.flag_cls >> 16;
+            if (n_rec < cap_recs) {
+                uint32_t *o = recs + 4u * n_rec;
+                o[0] = r.off; o[1] = r.flag_cls; o[2] = r.l_seq; o[3] = r.seq_off;
+            }
+            if (cls == (uint32_t)BAM_C_MALFORMED && malformed == BAM_NONE) malformed = (uint32_t)n_rec;
+            if (cls <= (uint32_t)BAM_C_SECOND) {
+                part.push_back(r);
+                part_idx.push_back((uint32_t)n_rec);
+            }
+            n_rec++;
+        }
+    }
+    for (uint64_t c = 0; 2u * c + 1u < part.size(); c++) {
+        const BamRec &a = part[2u * c], &b = part[2u * c + 1u];
+        if (!bam_couple_ok(a.flag_cls, b.flag_cls) && bad_couple == BAM_NONE) bad_couple = (uint32_t)c;
+        const bool a_first = (a.flag_cls >> 16) == (uint32_t)BAM_C_FIRST;
+        if (2u * c < cap_ends) ends[2u * c] = part_idx[2u * c + (a_first ? 0u : 1u)];
+        if (2u * c + 1u < cap_ends) ends[2u * c + 1u] = part_idx[2u * c + (a_first ? 1u : 0u)];
+    }
+    fill_info(info, n_rec, part.size(), (uint32_t)end, stop, malformed, bad_couple);
+    return VS_OK;
+}
+
+int vs_bam_scan_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t *recs, uint64_t cap_recs,
+                     uint32_t *ends, uint64_t cap_ends, uint64_t info[6]) {
+    if (!ctx || (!bytes && n) || !info || (!recs && cap_recs) || (!ends && cap_ends) || n > STREAM_MAX_WINDOW || skip > n)
+        return vs_fail(ctx, VS_E_ARG, "vs_bam_scan_text: bad argument");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    seg = seg_checked(seg);
+    hipStream_t st = ctx->stream;
+    VsDevBuf win, stat, d_ends, d_meta, d_wcnt;
+    BamScan sc;
+    uint32_t hs[B_ALL] = {0};
+    VS_HIP(ctx, win.reserve(((n + 15u) & ~(uint64_t)15u) + 16u));
+    VS_HIP(ctx, stat.reserve(sizeof(uint32_t) * B_ALL));
+    if (n) VS_HIP(ctx, hipMemcpyAsync(win.ptr(), bytes, n, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemsetAsync(stat.ptr(), 0, sizeof(uint32_t) * B_ALL, st));
+    if (int rc = bam_scan_device(ctx, st, win.as<const uint8_t>(), n, skip, seg, sc, stat.as<uint32_t>(), hs)) return rc;
+    const uint32_t n_pairs = sc.n_part / 2u;
+    uint32_t bad_couple = BAM_NONE;
+    if (sc.n_rec && cap_recs) {
+        const uint64_t m = std::min<uint64_t>(cap_recs, sc.n_rec);
+        VS_HIP(ctx, hipMemcpy(recs, sc.recs.ptr(), sizeof(uint32_t) * 4u * m, hipMemcpyDeviceToHost));
+    }
+    if (n_pairs) {
+        VS_HIP(ctx, d_ends.reserve(sizeof(uint32_t) * (2u * (size_t)n_pairs + 1u)));
+        VS_HIP(ctx, d_meta.reserve(sizeof(uint32_t) * (2u * (size_t)n_pairs + 1u)));
+        VS_HIP(ctx, d_wcnt.reserve(sizeof(uint32_t) * (2u * (size_t)n_pairs + 1u)));
+        VS_HIP(ctx, hipMemsetAsync(stat.as<uint32_t>() + B_BADCOUPLE, 0xFF, sizeof(uint32_t), st));
+        VS_HIP(ctx, hipMemsetAsync(stat.as<uint32_t>() + B_TOO_LONG, 0xFF, sizeof(uint32_t), st));
+        launch_ends(st, sc, 0, n_pairs, d_ends.as<uint32_t>(), d_meta.as<uint32_t>(), d_wcnt.as<uint32_t>(), stat.as<uint32_t>());
+        VS_HIP(ctx, hipGetLastError());
+        VS_HIP(ctx, hipMemcpyAsync(hs, stat.ptr(), sizeof(uint32_t) * B_ALL, hipMemcpyDeviceToHost, st));
+        VS_HIP(ctx, hipStreamSynchronize(st));
+        bad_couple = hs[B_BADCOUPLE];
+        const uint64_t m = std::min<uint64_t>(cap_ends, 2u * (uint64_t)n_pairs);
+        if (m) VS_HIP(ctx, hipMemcpy(ends, d_ends.ptr(), sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    }
+    fill_info(info, sc.n_rec, sc.n_part, sc.end, sc.stop, sc.malformed, bad_couple);
+    return VS_OK;
+}
+
+}  // extern "C"

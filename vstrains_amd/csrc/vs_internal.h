@@ -206,6 +206,17 @@ struct SlWin {
 };
 // k_pack_reads for the first r->n_ends / 2 records of two windows (r's woff and lengths are on the device, r->d_mask too)
 void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, const vs_reads *r);
+// exclusive scan of a[0, m) in place by one workgroup (k_sl_scan of vs_stream.hip); the total, below 2^32, to *total
+void vs_launch_scan_u32(hipStream_t st, uint32_t *a, uint32_t m, uint32_t *total);
+// The ends of a block of the BAM ingest (vs_bam.hip): end e is record ends[e] of recs (BamRec of vs_bam_core.h: four words,
+// the flag in the low 16 bits of the second, l_seq the third, the offset of the 4-bit bases in win the fourth)
+struct BamEnds {
+    const uint8_t *win;
+    const uint32_t *recs;
+    const uint32_t *ends;
+};
+// k_pack_reads for them (r's woff and lengths are on the device, r->d_mask too)
+void vs_launch_pack_bam(hipStream_t st, const BamEnds &b, const vs_reads *r);
 
 // BGZF members (vs_inflate.hip), shared with the streamed ingest.  A member for the device: its raw deflate payload in a
 // buffer of compressed bytes, where its ISIZE bytes go in an output buffer, and the CRC32 of its trailer.

@@ -8,28 +8,45 @@
 #include <vector>
 
 #include "vs_internal.h"
+#include "vs_bam_core.h"
 #include "vs_pack_host.h"
 
 #define TPB 256
 
-// Where the bytes of a block's ends lie: end(e, &len) = the first byte of end e and how many there are.
+// Where the characters of a block's ends come from: open(e) = end e, with its length `len` and its character at(p), p < len.
+struct PackBytes {  // an end that lies in memory as it reads
+    const uint8_t *q;
+    uint32_t len;
+    __device__ uint8_t at(uint32_t p) const { return q[p]; }
+};
 struct PackText {  // the caller's text: end e is ascii[aoff[e], aoff[e + 1])
     const uint8_t *ascii;
     const uint64_t *aoff;
-    __device__ const uint8_t *end(uint32_t e, uint32_t *len) const {
+    __device__ PackBytes open(uint32_t e) const {
         const uint64_t a = aoff[e];
-        *len = (uint32_t)(aoff[e + 1] - a);
-        return ascii + a;
+        return PackBytes{ascii + a, (uint32_t)(aoff[e + 1] - a)};
     }
 };
 struct PackLines {  // the windows of the streamed ingest: end e is line 4 (e / 2) + 1 of file e & 1, without its newline
     SlWin f0, f1;
-    __device__ const uint8_t *end(uint32_t e, uint32_t *len) const {
+    __device__ PackBytes open(uint32_t e) const {
         const SlWin &w = (e & 1u) ? f1 : f0;
         const uint32_t r = e >> 1;
         const uint32_t start = w.ends[4u * r] + 1u;
-        *len = w.ends[4u * r + 1u] - start;
-        return w.txt + start;
+        return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
+    }
+};
+struct PackBamEnd {  // 4-bit bases, read backwards and complemented where the record's flag has 0x10
+    const uint8_t *seq;
+    uint32_t len;
+    bool rev;
+    __device__ uint8_t at(uint32_t p) const { return bam_base(seq, len, rev, p); }
+};
+struct PackBam {  // the records of a window of the BAM ingest
+    BamEnds b;
+    __device__ PackBamEnd open(uint32_t e) const {
+        const uint32_t *r = b.recs + 4u * (size_t)b.ends[e];
+        return PackBamEnd{b.win + r[3], r[2], (r[1] & 0x10u) != 0u};
     }
 };
 
@@ -41,15 +58,15 @@ k_pack_reads(Src src, const uint32_t *__restrict__ woff, uint32_t n_ends, uint32
     const uint32_t wi = blockIdx.x * TPB + threadIdx.x;
     if (wi >= total_words) return;
     const uint32_t e = vs_upper_idx(woff, n_ends + 1u, wi);
-    uint32_t len;
-    const uint8_t *q = src.end(e, &len);
+    const auto end = src.open(e);
+    const uint32_t len = end.len;
     const uint32_t b0 = (wi - woff[e]) * 16u;
     uint32_t v = 0, m = 0, fl = 0;
 #pragma unroll
     for (uint32_t i = 0; i < 16; i++) {
         const uint32_t p = b0 + i;
         if (p < len) {
-            const uint8_t c = q[p];
+            const uint8_t c = end.at(p);
             const uint32_t code = vs_code(c);
             if (code > 3u) {
                 fl |= (c == 'N') ? VS_FLAG_N : VS_FLAG_INVALID;
@@ -71,6 +88,7 @@ static void launch_pack(hipStream_t st, const Src &src, const vs_reads *r) {
                            (uint32_t)r->n_ends, (uint32_t)r->n_words, (uint32_t *)r->d_words, (uint32_t *)r->d_mask, (uint32_t *)r->d_meta);
 }
 void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, const vs_reads *r) { launch_pack(st, PackLines{f0, f1}, r); }
+void vs_launch_pack_bam(hipStream_t st, const BamEnds &b, const vs_reads *r) { launch_pack(st, PackBam{b}, r); }
 
 __global__ void __launch_bounds__(TPB)
 k_count_invalid(const uint32_t *__restrict__ meta, uint64_t n_ends, uint32_t *__restrict__ out) {

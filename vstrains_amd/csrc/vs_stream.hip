@@ -2,7 +2,7 @@
 // packed ON THE DEVICE.  For inputs the mapped ingest (vs_fastq.hip) cannot take: a FIFO, /dev/stdin or a process
 // substitution has no size to map, and a gzip file is inflated there whole into memory before anything is counted.
 //
-// Host: one reader thread per file read(2)s any fd -- inflating with zlib in streaming mode when the file starts with
+// Host: one reader thread per file (the Reader of vs_stream_reader.h, which the BAM ingest shares) read(2)s any fd -- inflating with zlib in streaming mode when the file starts with
 // the gzip magic (several members in a row are fine; a cut-off stream or trailing bytes that are no member are VS_E_ARG,
 // as in map_file) -- into a ring of STREAM_RING_SLOTS pinned chunks of STREAM_CHUNK_BYTES.  Peak host memory is the
 // ring, whatever the size of the file.
@@ -61,22 +61,18 @@
 #include <vector>
 
 #include "vs_internal.h"
+#include "vs_stream_reader.h"
 
 #define SL_TPB 256
 #define SL_SCAN_TPB 1024
 
 namespace {
 
-constexpr size_t STREAM_CHUNK_BYTES = 64u << 20;  // one pinned chunk of the ring; VS_STREAM_CHUNK overrides it (tests only)
-constexpr unsigned STREAM_RING_SLOTS = 4;         // chunks per file in the ring
-constexpr size_t STREAM_MAX_WINDOW = 0xFFFFFF00u; // line ends are 32-bit byte offsets into a window
-
 // per-window status the kernels write (one uint32 array per stream, read back in one copy)
 enum { ST_NL = 0, ST_FLAGS = 1, ST_LAST = 2, ST_PER_FILE = 4 };  // [f * ST_PER_FILE + ...]
 enum { ST_MAXLEN = 8, ST_TOO_LONG = 9, ST_WORDS = 10, ST_INVALID = 11, ST_CUT = 12 /* + f */, ST_N = 16 };
 enum { ST_BAD = ST_N /* + f: the first member of file f the device rejected (a running index), ~0u: none */, ST_ALL = ST_N + 2 };
 enum { FL_CR = 1u, FL_HIGH = 2u };
-enum { M_PLAIN = 0, M_ZLIB = 1, M_BGZF = 2 };
 
 }  // namespace
 
@@ -172,6 +168,9 @@ __global__ void __launch_bounds__(SL_SCAN_TPB) k_sl_scan(uint32_t *__restrict__ 
     }
     if (t == SL_SCAN_TPB - 1u) *total = part[t];
 }
+void vs_launch_scan_u32(hipStream_t st, uint32_t *a, uint32_t m, uint32_t *total) {
+    hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, a, m, total);
+}
 
 // the byte offset of every newline, in order: workgroup base (scanned counts) + wavefront base + the lane's rank, the
 // rank from __ballot of the bits of every lane's count
@@ -236,267 +235,8 @@ __global__ void __launch_bounds__(SL_TPB) k_sl_ends(SlWin f0, SlWin f1, uint32_t
     atomicMax(&st[ST_MAXLEN], len);
 }
 
-// ---- host reader -------------------------------------------------------------------------------------------------------
+// ---- host side (the reader: vs_stream_reader.h) ---------------------------------------------------------------------------
 namespace {
-
-struct Slot {
-    VsPinnedBuf buf;          // slot_cap bytes, pinned by the reader at first use
-    size_t len = 0;  // bytes of text, or of deflate payloads when n_members > 0 or comp
-    bool last = false;
-    bool comp = false;        // payloads of BGZF members + their directory at the slot's end (the last member first)
-    uint32_t n_members = 0;
-    size_t text = 0;          // what the members inflate to (the ISIZE sum)
-};
-
-// One file read front to back by a thread of its own into the ring.  The consumer takes filled slots in order and gives
-// them back once their bytes are on the device.
-struct Reader {
-    std::string path;
-    int fd = -1, device = 0;
-    size_t chunk = STREAM_CHUNK_BYTES;
-    Slot slots[STREAM_RING_SLOTS];
-    uint64_t filled = 0, taken = 0;  // slots published / given back (monotonic)
-    bool stop = false, finished = false;
-    int err = VS_OK;
-    std::string err_msg;
-    bool gzip = false, bgzf = false, bgzf_device = true;
-    size_t slot_cap = STREAM_CHUNK_BYTES;
-    uint64_t raw_bytes = 0, text_bytes = 0, members_host = 0;
-    uint64_t begin = 0, end = ~0ull;  // the bytes of the file this reader may read (a member range of a sharded open)
-    std::mutex m;
-    std::condition_variable cv;
-    std::thread th;
-
-    int fail(int code, const char *fmt, const char *a, const char *b = "") {
-        char buf[512];
-        snprintf(buf, sizeof buf, fmt, a, b);
-        err = code;
-        err_msg = buf;
-        return code;
-    }
-    // read(2) up to n bytes; 0 at the end of the file; -1 on an error or when asked to stop
-    ssize_t raw_read(uint8_t *dst, size_t n) {
-        for (;;) {
-            {
-                std::lock_guard<std::mutex> lk(m);
-                if (stop) return -1;
-            }
-            struct pollfd pfd = {fd, POLLIN, 0};
-            const int pr = poll(&pfd, 1, 200);  // (a pipe whose writer is slow: look at `stop` now and then)
-            if (pr == 0 || (pr < 0 && errno == EINTR)) continue;
-            const uint64_t left = end - (begin + raw_bytes);  // (never a byte beyond the range, not even into a buffer)
-            if (left == 0) return 0;
-            const ssize_t got = read(fd, dst, (size_t)std::min<uint64_t>(std::min<size_t>(n, 1u << 30), left));
-            if (got < 0 && errno == EINTR) continue;
-            if (got < 0) {
-                fail(VS_E_ARG, "cannot read %s: %s", path.c_str(), strerror(errno));
-                return -1;
-            }
-            raw_bytes += (uint64_t)got;
-            return got;
-        }
-    }
-    void run() {
-        (void)hipSetDevice(device);
-        if (begin && lseek(fd, (off_t)begin, SEEK_SET) < 0) {
-            fail(VS_E_ARG, "cannot seek in %s: %s", path.c_str(), strerror(errno));
-            publish(0, true);
-            return;
-        }
-        std::vector<uint8_t> in(1u << 20);
-        size_t in_len = 0;
-        bool in_eof = false;
-        // the first bytes say whether the file is gzip (magic 1f 8b)
-        while (in_len < 18 && !in_eof) {  // (18: the header of a BGZF member as bgzip writes it)
-            const ssize_t got = raw_read(in.data() + in_len, in.size() - in_len);
-            if (got < 0) { publish(0, true); return; }
-            if (got == 0) in_eof = true;
-            in_len += (size_t)got;
-        }
-        gzip = in_len >= 2 && in[0] == 0x1f && in[1] == 0x8b;
-        int mode = gzip ? M_ZLIB : M_PLAIN;
-        if (gzip && bgzf_device) {
-            vs_bgzf_member mb;
-            size_t msize = 0;
-            if (vs_bgzf_parse(in.data(), in_len, &mb, &msize) != 2) mode = M_BGZF;
-        }
-        bgzf = mode == M_BGZF;
-        slot_cap = bgzf ? (std::max<size_t>(chunk, 65536u) + 15u) & ~(size_t)15u : chunk;
-        size_t in_at = 0;  // (BGZF: bytes of `in` already handed on)
-        z_stream zs;
-        memset(&zs, 0, sizeof zs);
-        if (gzip && inflateInit2(&zs, 15 + 16) != Z_OK) {
-            fail(VS_E_OOM, "%s: zlib cannot start", path.c_str());
-            publish(0, true);
-            return;
-        }
-        size_t plain_at = 0;  // (plain text: bytes of `in` not yet handed on)
-        if (mode == M_ZLIB) {
-            zs.next_in = in.data();
-            zs.avail_in = (uInt)in_len;
-        }
-        bool at_end = false;
-        while (!at_end) {
-            Slot *slot = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv.wait(lk, [&] { return stop || filled - taken < STREAM_RING_SLOTS; });
-                if (stop) break;
-                slot = &slots[filled % STREAM_RING_SLOTS];  // (free: the consumer gave it back)
-            }
-            if (slot->buf.reserve(slot_cap) != hipSuccess)
-                fail(VS_E_OOM, "%s: cannot pin a %s-byte chunk", path.c_str(), std::to_string(slot_cap).c_str());
-            uint8_t *dst = slot->buf.as<uint8_t>();
-            if (!dst) { publish(0, true); break; }
-            size_t len = 0;
-            bool bad = false;
-            if (mode == M_BGZF) {
-                uint32_t nm = 0;
-                size_t text = 0;
-                bool to_zlib = false;
-                vs_bgzf_member *dir_end = (vs_bgzf_member *)(dst + slot_cap);
-                for (;;) {
-                    vs_bgzf_member mb;
-                    size_t msize = 0;
-                    const int st = vs_bgzf_parse(in.data() + in_at, in_len - in_at, &mb, &msize);
-                    if (st == 0) {
-                        const size_t need = ((len + mb.in_len + 3u) & ~(size_t)3u) + sizeof(vs_bgzf_member) * (nm + 1u);
-                        if (nm && (need > slot_cap || text + mb.isize > chunk || len + mb.in_len > 0xFFFF0000u)) break;  // the next slot's
-                        memcpy(dst + len, in.data() + in_at + mb.in_off, mb.in_len);
-                        mb.in_off = (uint32_t)len;
-                        mb.out_off = (uint32_t)text;
-                        dir_end[-(ptrdiff_t)(nm + 1u)] = mb;
-                        len += mb.in_len;
-                        text += mb.isize;
-                        nm++;
-                        in_at += msize;
-                        if (text >= chunk) break;
-                        continue;
-                    }
-                    if (st == 1 && !in_eof) {  // a member cut by a read boundary: more bytes
-                        memmove(in.data(), in.data() + in_at, in_len - in_at);
-                        in_len -= in_at;
-                        in_at = 0;
-                        const ssize_t got = raw_read(in.data() + in_len, in.size() - in_len);
-                        if (got < 0) { bad = true; break; }
-                        if (got == 0) in_eof = true;
-                        in_len += (size_t)got;
-                        continue;
-                    }
-                    if (in_at == in_len) at_end = true;  // the end of the file, after a whole member
-                    else to_zlib = true;                 // not BGZF, or a member the end of the file cut: zlib says what it is
-                    break;
-                }
-                if (to_zlib) {
-                    mode = M_ZLIB;
-                    zs.next_in = in.data() + in_at;
-                    zs.avail_in = (uInt)(in_len - in_at);
-                    if (!nm) continue;  // (nothing for the device in this slot: the zlib loop fills it)
-                }
-                at_end = at_end || bad || (!to_zlib && in_eof && in_at == in_len);
-                text_bytes += text;
-                publish(len, at_end, true, nm, text);
-                continue;
-            }
-            if (mode == M_PLAIN) {
-                const size_t now = std::min(chunk, in_len - plain_at);
-                memcpy(dst, in.data() + plain_at, now);
-                plain_at += now;
-                len = now;
-                while (len < chunk && !in_eof) {
-                    const ssize_t got = raw_read(dst + len, chunk - len);
-                    if (got < 0) { bad = true; break; }
-                    if (got == 0) in_eof = true;
-                    len += (size_t)got;
-                }
-                at_end = bad || (in_eof && plain_at == in_len);
-            } else {
-                int rc = Z_OK;
-                while (len < chunk) {
-                    if (zs.avail_in == 0 && !in_eof) {
-                        const ssize_t got = raw_read(in.data(), in.size());
-                        if (got < 0) { bad = true; break; }
-                        if (got == 0) in_eof = true;
-                        zs.next_in = in.data();
-                        zs.avail_in = (uInt)got;
-                    }
-                    zs.next_out = dst + len;
-                    zs.avail_out = (uInt)(chunk - len);
-                    rc = inflate(&zs, Z_NO_FLUSH);
-                    len = chunk - zs.avail_out;
-                    if (rc == Z_STREAM_END) {
-                        members_host++;
-                        if (zs.avail_in == 0 && !in_eof) {  // more members may follow: look
-                            const ssize_t got = raw_read(in.data(), in.size());
-                            if (got < 0) { bad = true; break; }
-                            if (got == 0) in_eof = true;
-                            zs.next_in = in.data();
-                            zs.avail_in = (uInt)got;
-                        }
-                        if (zs.avail_in == 0 && in_eof) { at_end = true; break; }
-                        if (inflateReset(&zs) != Z_OK) { rc = Z_DATA_ERROR; }
-                        else continue;  // next member
-                    }
-                    if (rc == Z_OK || (rc == Z_BUF_ERROR && (zs.avail_out == 0 || (zs.avail_in == 0 && !in_eof)))) {
-                        if (zs.avail_in == 0 && in_eof && zs.avail_out != 0) rc = Z_DATA_ERROR;  // truncated stream
-                        else continue;
-                    }
-                    if (rc == Z_BUF_ERROR) rc = Z_DATA_ERROR;  // (no progress with all input consumed: truncated)
-                    char code[16];
-                    snprintf(code, sizeof code, "%d", rc);
-                    fail(VS_E_ARG, "%s: not a complete gzip stream (zlib code %s)", path.c_str(), code);
-                    bad = true;
-                    break;
-                }
-                at_end = at_end || bad;
-            }
-            text_bytes += len;
-            publish(len, at_end);
-        }
-        if (gzip) inflateEnd(&zs);
-    }
-    void publish(size_t len, bool last, bool comp = false, uint32_t n_members = 0, size_t text = 0) {
-        std::lock_guard<std::mutex> lk(m);
-        Slot &s = slots[filled % STREAM_RING_SLOTS];
-        s.len = len;
-        s.last = last;
-        s.comp = comp;
-        s.n_members = n_members;
-        s.text = comp ? text : len;
-        filled++;
-        finished = last;
-        cv.notify_all();
-    }
-    // the next filled slot (blocks until the reader has one)
-    Slot &take() {
-        std::unique_lock<std::mutex> lk(m);
-        cv.wait(lk, [&] { return filled > taken; });
-        return slots[taken % STREAM_RING_SLOTS];
-    }
-    void give_back() {
-        std::lock_guard<std::mutex> lk(m);
-        taken++;
-        cv.notify_all();
-    }
-    void shut() {
-        {
-            std::lock_guard<std::mutex> lk(m);
-            stop = true;
-        }
-        cv.notify_all();
-        if (th.joinable()) th.join();
-        for (Slot &s : slots) s.buf.reset();
-        if (fd >= 0) close(fd);
-        fd = -1;
-    }
-};
-
-// room for `need` elements of T, a quarter more when the buffer has to grow (what it held is not kept)
-template <typename T>
-int reserve_n(vs_ctx *ctx, VsDevBuf &b, size_t need) {
-    VS_HIP(ctx, b.reserve(need * sizeof(T), (need + need / 4 + 64) * sizeof(T)));
-    return VS_OK;
-}
 
 // The device side of one file: the window (two buffers, the leftover copied from one to the other after a block) and
 // its line ends.

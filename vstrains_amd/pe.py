@@ -414,6 +414,106 @@ class FastqStream:
             pass
 
 
+class BamStream:
+    """The read pairs of ONE collated BAM file (unaligned BAM from the sequencer, or the unmapped pairs of a host
+    alignment after ``samtools collate``) through ``vs_bam_stream_*``: the BGZF members inflated on the device, the records
+    found there by following their ``block_size`` chain from the end of the header, the 4-bit bases packed by the packer of
+    every block.  The file stands for the FASTQ pair ``samtools fastq -1 -2`` writes: secondary and supplementary records
+    are dropped, so is every record that is not paired with exactly one of first / second; the rest are taken two at a
+    time, one first (the forward end) and one second in either order, an end with flag 0x10 reversed and complemented.
+    Anything else -- two firsts in a row, an odd record at the end, a truncated or malformed record -- raises
+    ``ValueError`` naming the record (numbered from 0 in file order).  Interface of ``FastqStream``; ``info`` has
+    ``pairs``, ``records``, ``dropped_0x900``, ``dropped_other``, ``members_device``, ``text_bytes``, ``file_bytes``."""
+
+    def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20):
+        self._ctx = ctx
+        self._h = None
+        self.block_pairs = block_pairs
+        h = C.c_void_p()
+        rc = nat.lib().vs_bam_stream_open(ctx._h, path.encode(), C.byref(h))
+        if rc != nat.VS_OK:
+            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+            if "cannot open" in msg:
+                raise FileNotFoundError(msg)
+            if rc == nat.VS_E_ARG:
+                raise ValueError(msg)
+            raise nat.NativeError(rc, msg)
+        self._h = h
+
+    @property
+    def info(self):
+        a = (C.c_uint64 * 8)()
+        nat.lib().vs_bam_stream_info(self._h, a)
+        return dict(pairs=int(a[0]), records=int(a[1]), dropped_0x900=int(a[2]), dropped_other=int(a[3]), members_device=int(a[4]),
+                    text_bytes=int(a[5]), file_bytes=int(a[6]), done=bool(a[7]))
+
+    @property
+    def n_pairs(self) -> int:
+        """pairs delivered so far (all of them once the iteration has ended)"""
+        return self.info["pairs"]
+
+    def next_block(self) -> Optional["ReadBlock"]:
+        """The next block, or None at the end of the input."""
+        h = C.c_void_p()
+        n = C.c_uint64(0)
+        rc = nat.lib().vs_bam_stream_next(self._ctx._h, self._h, self.block_pairs, C.byref(h), C.byref(n))
+        if rc == nat.VS_E_ARG:
+            raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
+        nat.check(self._ctx._h, rc)
+        return ReadBlock(self._ctx, h) if n.value else None
+
+    def __iter__(self):
+        while True:
+            block = self.next_block()
+            if block is None:
+                return
+            yield block
+
+    def close(self):
+        if self._h:
+            nat.lib().vs_bam_stream_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bam_header_bytes(path: str) -> int:
+    """Inflated bytes in front of the first record of the BAM at ``path`` (``vs_bam_header``, host only); ``ValueError``
+    when the file is no BAM."""
+    n = C.c_uint64(0)
+    rc = nat.lib().vs_bam_header(path.encode(), C.byref(n))
+    if rc != nat.VS_OK:
+        raise ValueError(nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    return int(n.value)
+
+
+def bam_scan(data: bytes, skip: int = 0, seg: int = 0, ctx: "Context" = None):
+    """The record chain of inflated BAM bytes from ``skip`` (test aid): ``vs_bam_scan_host`` (one host thread), or with
+    ``ctx`` the kernels (``vs_bam_scan_text``).  Returns (recs uint32 [n, 4]: offset, flag | class << 16, l_seq, sequence
+    offset; ends uint32 [couples, 2]: record index of the forward and the reverse end; info dict)."""
+    buf = np.frombuffer(data or b"\0", dtype=np.uint8)
+    cap = len(data) // 36 + 1
+    recs = np.zeros((cap, 4), dtype=np.uint32)
+    ends = np.zeros(cap + 1, dtype=np.uint32)
+    info = (C.c_uint64 * 6)()
+    if ctx is None:
+        rc = nat.lib().vs_bam_scan_host(buf.ctypes.data, len(data), skip, seg, recs.ctypes.data, cap, ends.ctypes.data, cap, info)
+        if rc != nat.VS_OK:
+            raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    else:
+        nat.check(ctx._h, nat.lib().vs_bam_scan_text(ctx._h, buf.ctypes.data, len(data), skip, seg, recs.ctypes.data, cap, ends.ctypes.data,
+                                                    cap, info))
+    none = (1 << 64) - 1
+    n_rec, n_part = int(info[0]), int(info[1])
+    return recs[:n_rec], ends[:2 * (n_part // 2)].reshape(-1, 2), dict(
+        records=n_rec, taking_part=n_part, end=int(info[2]), stop=int(info[3]),
+        malformed=None if info[4] == none else int(info[4]), bad_couple=None if info[5] == none else int(info[5]))
+
+
 INFLATE_GUARD = 64  # bytes kept behind every member's output by the inflate test aids; they must stay INFLATE_GUARD_BYTE
 INFLATE_GUARD_BYTE = 0xA5
 

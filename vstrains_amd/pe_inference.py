@@ -33,7 +33,8 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     PE-link table from these counters in this process (the pipeline; not the stand-alone script, which writes the two text
     files) -- the table's device buffer is then set aside together with the counters."""
     rank, world = _rank_world()
-    streamed = use_stream(fwd, rve)
+    bam = bam_input(fwd, rve, world)
+    streamed = bam is None and use_stream(fwd, rve)
     if world > 1 and not (_regular(fwd) and _regular(rve)):  # (the sharded path maps regular files; VS_FASTQ_STREAM aside)
         raise ValueError("the FASTQ inputs %s / %s are not both regular files: a pipe can be read by one process only, so "
                          "the sharded (torchrun) run cannot take it; run one process, or write the reads to files" % (fwd, rve))
@@ -46,7 +47,13 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     # counters are summed over ranks afterwards (RCCL all-reduce); a single process takes everything
     if rank == 0 and stages_follow:
         counter.reserve_link_table()  # (the graph stages run on this rank: their table's buffer is taken now)
-    if world > 1:
+    if bam is not None:
+        fq = host.BamStream(bam, ctx, block_pairs=BATCH_PAIRS)  # one collated BAM stands for the pair (-f and -r both name it)
+        try:
+            count_stream(ctx, fq, counter, progress=True)
+        finally:
+            fq.close()
+    elif world > 1:
         # two whole-BGZF files: the ranks share them by member, count lines and inflate on their devices only, and each
         # streams its own records (FastqStream.open_shard); why == the reason when that is not what happens
         fq, why = None, member_shard_refusal(fwd, rve)
@@ -110,6 +117,39 @@ def _starts_bgzf(path: str) -> bool:
             return True
         at += 4 + slen
     return False
+
+
+def _starts_bam(path: str) -> bool:
+    """The first BGZF member of a regular file inflates to bytes that start with the BAM magic."""
+    if not _starts_bgzf(path):
+        return False
+    import zlib
+
+    try:
+        with open(path, "rb") as fh:
+            head = fh.read(65536)
+        xlen = head[10] | (head[11] << 8)
+        return zlib.decompressobj(-15).decompress(head[12 + xlen:], 4) == b"BAM\1"
+    except (OSError, zlib.error, IndexError):
+        return False
+
+
+def bam_input(fwd: str, rve: str, world: int = 1):
+    """The path when ``-f`` and ``-r`` name the same regular file and it is a BAM: the pair is read from it
+    (``BamStream``).  None when neither input is a BAM.  ``ValueError`` for what is out of scope: BAM on one side only, two
+    different BAM files, a BAM under a process group of more than one rank."""
+    is_bam = (_starts_bam(fwd), _starts_bam(rve))
+    if not any(is_bam):
+        return None
+    if not all(is_bam):
+        raise ValueError("%s is a BAM file and %s is not: BAM on one side only is not supported; name the same collated BAM "
+                         "for both reads, or convert it with `samtools fastq`" % ((fwd, rve) if is_bam[0] else (rve, fwd)))
+    if not os.path.samefile(fwd, rve):
+        raise ValueError("%s and %s are two different BAM files: a pair is read from ONE collated BAM (both mates in it); "
+                         "name the same file for both reads" % (fwd, rve))
+    if world > 1:
+        raise ValueError("%s: a BAM file is read by one process only (no member-sharded BAM yet); run without torchrun" % fwd)
+    return fwd
 
 
 def member_shard_refusal(fwd: str, rve: str):
