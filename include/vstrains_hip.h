@@ -289,6 +289,36 @@ int vs_bam_scan_host(const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t s
                      uint64_t cap_ends, uint64_t info[6]);
 int vs_bam_scan_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t *recs, uint64_t cap_recs,
                      uint32_t *ends, uint64_t cap_ends, uint64_t info[6]);
+/* Mates matched by name (additions to ABI 10): the participating records of ONE regular BAM in ANY record order -- a
+ * coordinate-sorted alignment, `samtools view -f 12` of one, a file that lost one mate of some pairs.  The file stands for
+ * the pair `samtools collate | samtools fastq -1 R1 -2 R2 -s /dev/null -0 /dev/null` writes, up to the order of the pairs
+ * (no result depends on it).  The rule: records are walked in file order, classified as above, and only first and second
+ * records take part.  The name of a record is its l_read_name bytes as they lie in it, terminator included; two names are
+ * the same when lengths and bytes are (never because a hash is).  A record of class c pairs with the OLDEST waiting record
+ * of its name and the other class, or waits when there is none: the j-th first of a name pairs with its j-th second, the
+ * first is the forward end.  Pairs are delivered in the order of the record that completed them, whatever the window,
+ * chunk, segment or block size.  What still waits at the end of the input are singletons: dropped and counted.
+ *   vs_bam_stream_open_mode : mode VS_BAM_COLLATED is vs_bam_stream_open; VS_BAM_BY_NAME selects the above.  next, info
+ *                             (info[0..7] keep their meaning) and close serve both.  Truncated and malformed records and
+ *                             damaged members fail as in the collated mode.  VS_E_RANGE, with advice to run `samtools
+ *                             collate`: more than 64 records of one name and one class in one window (the waiting ones
+ *                             included; the newest record of the name is named -- this bounds every list walk), and
+ *                             waiting records plus the next chunk beyond the largest window.
+ *   vs_bam_stream_mate_info : info[0] = singletons dropped, [1] = most records carried between two windows, [2] = most
+ *                             bytes carried, [3] = windows scanned
+ * VS_BAM_NAME_BITS=<0..64> (tests only) keeps that many low bits of the name hash: long probe chains without constructed
+ * collisions.
+ * Test aids, the match of one window: bytes, n, skip, seg as vs_bam_scan_*; hash_bits as VS_BAM_NAME_BITS.  pairs[2 p],
+ * [2 p + 1] = record index of the first and the second of pair p in delivery order (at most cap_pairs pairs), waiting[] = the
+ * records left waiting in window order (at most cap_waiting); info[0] = pairs, [1] = waiting, [2] = the newest record of a
+ * name with more than 64 records of one class (then no pairs and no waiting records are given), ~0: none. */
+enum { VS_BAM_COLLATED = 0, VS_BAM_BY_NAME = 1 };
+int vs_bam_stream_open_mode(vs_ctx *ctx, const char *path, int mode, vs_bam_stream **out);
+int vs_bam_stream_mate_info(const vs_bam_stream *s, uint64_t info[4]);
+int vs_bam_mates_host(const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t hash_bits, uint32_t *pairs, uint64_t cap_pairs,
+                      uint32_t *waiting, uint64_t cap_waiting, uint64_t info[3]);
+int vs_bam_mates_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t hash_bits, uint32_t *pairs,
+                      uint64_t cap_pairs, uint32_t *waiting, uint64_t cap_waiting, uint64_t info[3]);
 /* The header of a BAM at the front of a file (host: zlib on its leading BGZF members): *header_bytes = inflated bytes in
  * front of the first record.  VS_E_ARG with a message when the file is no BAM. */
 int vs_bam_header(const char *path, uint64_t *header_bytes);

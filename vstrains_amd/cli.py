@@ -56,6 +56,10 @@ def build_parser():
                    help="extension: do not count the reads again; read ALN_DIR/pe_info.gz + st_info.gz (or pe_info + st_info) "
                         "that an earlier run or vstrains_amd.pe_inference wrote, on the device (not together with --no-pe-text, "
                         "--sparse-pe-text or --bgzf-pe-text; -fwd / -rve are still required and are not opened)")
+    p.add_argument("--bam-by-name", dest="bam_by_name", action="store_true", default=False,
+                   help="extension: -fwd and -rve name ONE BAM in any record order (coordinate-sorted, `samtools view -f 12` of a "
+                        "sorted alignment, ...); the mates are matched by read name on the device and records without a mate are "
+                        "dropped, no `samtools collate` first (not together with --pe-text-from)")
     return p
 
 
@@ -84,7 +88,8 @@ def main(argv=None, backend=None):
     if args.no_pe_text and args.bgzf_pe_text:
         parser.error("--no-pe-text and --bgzf-pe-text are mutually exclusive")
     if args.pe_text_from is not None:
-        for flag, name in ((args.no_pe_text, "--no-pe-text"), (args.sparse_pe_text, "--sparse-pe-text"), (args.bgzf_pe_text, "--bgzf-pe-text")):
+        for flag, name in ((args.no_pe_text, "--no-pe-text"), (args.sparse_pe_text, "--sparse-pe-text"), (args.bgzf_pe_text, "--bgzf-pe-text"),
+                           (args.bam_by_name, "--bam-by-name")):
             if flag:
                 parser.error("--pe-text-from and %s are mutually exclusive" % name)
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
@@ -163,12 +168,14 @@ def main(argv=None, backend=None):
 
     from .graph import pipeline
 
-    if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text):
+    if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text or args.bam_by_name):
         from .graph.hip_ops import HipBackend
 
         backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text,
-                             bgzf_info_text=args.bgzf_pe_text)
+                             bgzf_info_text=args.bgzf_pe_text, bam_by_name=args.bam_by_name)
     elif backend is not None:
+        if args.bam_by_name:
+            backend.bam_by_name = True
         if args.sparse_pe_text:
             backend.sparse_info_text = True
         if args.bgzf_pe_text:

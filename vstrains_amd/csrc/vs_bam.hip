@@ -25,6 +25,22 @@
 //
 // The window is scanned once per appended chunk; blocks are cut from the scanned records with a cursor.  The carry is
 // everything from the first record not delivered: an odd record, or the record the window's end cuts.
+//
+// By name (VS_BAM_BY_NAME): the mates of a pair may lie anywhere in the file.  A window is then [the records still waiting
+// for their mates, whole, in file order][new bytes]; the chain passes run over it as above (carried records are ordinary
+// records) and the participating records are joined on their names (the rule and every step: vs_bam_core.h):
+//   k_mate_hash     a lane per participating record: 64-bit hash of its name;
+//   k_mate_claim    open-address table of participating indices in device memory, claimed by atomicCAS, names compared
+//                   byte for byte out of the window; the record pushes itself on its name's list (atomicExch);
+//   k_mate_rank     a bounded walk of the name's list: rank within the own class, paired or waiting, bytes to carry;
+//   k_mate_partner  the same walk for the partner; the later record of a pair emits it;
+//   (k_sl_scan)     per workgroup: emitters, waiting records and their bytes to bases (a word per 256 records);
+//   k_mate_emit     the place inside the workgroup by a prefix over its lanes: the pair list (first, second) in the order of
+//                   the emitting record, the waiting list, the offset of every waiting record among the carried bytes;
+//   k_bam_ends_list a block of pairs from that list with a cursor (k_bam_ends takes neighbours instead);
+//   k_mate_carry    a wavefront per waiting record copies it to the front of the other window buffer, 16 bytes a lane
+//                   where source and destination are aligned alike; the bytes from `stop` on follow.
+// No lane waits for another lane's progress: a lost compare-and-swap reads the winner and goes on.
 #include "vs_stream_reader.h"
 #include "vs_bam_core.h"
 
@@ -178,6 +194,174 @@ __global__ void __launch_bounds__(BAM_TPB) k_bam_tally(const uint4 *__restrict__
     }
 }
 
+
+// ---- mates by name ----------------------------------------------------------------------------------------------------------
+namespace {
+enum { M_NPAIRS = 0, M_NWAIT = 1, M_WBYTES = 2, M_CROWDED = 3 /* ~record, 0xFFFFFFFF: none (atomicMin) */, M_BAD = 4, M_ALL = 8 };
+}
+
+__global__ void __launch_bounds__(BAM_TPB) k_mate_hash(BamMates m, uint64_t n, uint32_t bits, uint32_t *__restrict__ st) {
+    const uint32_t i = blockIdx.x * BAM_TPB + threadIdx.x;
+    if (i >= m.n_part) return;
+    uint64_t h = 0;
+    const uint32_t r = bam_mate_rec(m, i);
+    const uint64_t off = r == BAM_NONE ? n : (uint64_t)m.recs[4u * r];
+    if (off + 36u > n || off + 36u + m.win[off + 12u] > n) atomicOr(&st[M_BAD], 1u);  // (never: the scan found the record whole)
+    else h = bam_name_hash(m.win, (uint32_t)off, bits);
+    m.hash[i] = h;
+}
+
+__global__ void __launch_bounds__(BAM_TPB) k_mate_claim(BamMates m, uint32_t *__restrict__ st) {
+    const uint32_t i = blockIdx.x * BAM_TPB + threadIdx.x;
+    if (i >= m.n_part || st[M_BAD]) return;  // (M_BAD: a record index out of range, nothing is followed)
+    const uint32_t s = bam_mate_claim(m, i);
+    if (s == BAM_NONE) atomicOr(&st[M_BAD], 2u);
+    bam_mate_push(m, i, s);
+}
+
+// exclusive prefix of v over the workgroup's BAM_TPB threads, every thread calls; *total: the workgroup's sum
+__device__ inline uint32_t bam_block_excl(uint32_t v, uint32_t *wsum, uint32_t *total) {
+    const uint32_t lane = threadIdx.x & (VS_WAVE - 1u), wave = threadIdx.x / VS_WAVE;
+    uint32_t inc = v;
+#pragma unroll
+    for (uint32_t o = 1; o < VS_WAVE; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    if (lane == VS_WAVE - 1u) wsum[wave] = inc;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < BAM_TPB / VS_WAVE; w++) {
+        if (w < wave) base += wsum[w];
+        tot += wsum[w];
+    }
+    __syncthreads();  // (wsum is free for the next call)
+    *total = tot;
+    return base + inc - v;
+}
+
+// wbytes: 4 + block_size for a record that goes on waiting, else 0
+__global__ void __launch_bounds__(BAM_TPB) k_mate_rank(BamMates m, uint32_t *__restrict__ wbytes, uint32_t *__restrict__ st) {
+    const uint32_t i = blockIdx.x * BAM_TPB + threadIdx.x;
+    if (i >= m.n_part || st[M_BAD]) return;  // (M_BAD: a record index out of range, nothing is followed)
+    bool crowded = false;
+    const uint32_t rk = bam_mate_rank(m, i, &crowded);
+    if (crowded) atomicMin(&st[M_CROWDED], ~m.part[i]);  // (the complement: the newest record of a crowded name wins)
+    m.rank[i] = rk;
+    wbytes[i] = (rk & BAM_MATE_PAIRED) ? 0u : 4u + bam_le32(m.win + bam_mate_off(m, i));
+}
+
+// partner[i]: the earlier record of the pair i completes, BAM_NONE when i completes none.  Per workgroup: the pairs its
+// records complete, its waiting records and their bytes (sums[0 / 1 / 2][blockIdx.x]; scanned, they are the bases of k_mate_emit)
+__global__ void __launch_bounds__(BAM_TPB) k_mate_partner(BamMates m, uint32_t *__restrict__ partner, const uint32_t *__restrict__ wbytes,
+                                                          uint32_t *__restrict__ sum_e, uint32_t *__restrict__ sum_w, uint32_t *__restrict__ sum_b,
+                                                          const uint32_t *__restrict__ st) {
+    __shared__ uint32_t wsum[BAM_TPB / VS_WAVE];
+    const uint32_t i = blockIdx.x * BAM_TPB + threadIdx.x;
+    if (st[M_BAD]) return;  // (the same for every thread)
+    uint32_t e = 0, w = 0, b = 0;
+    if (i < m.n_part) {
+        uint32_t j = BAM_NONE;
+        const bool paired = (m.rank[i] & BAM_MATE_PAIRED) != 0u;
+        if (paired) j = bam_mate_partner(m, i);
+        const bool emits = j < i;  // (BAM_NONE is above every index)
+        partner[i] = emits ? j : BAM_NONE;
+        e = emits ? 1u : 0u;
+        w = paired ? 0u : 1u;
+        b = wbytes[i];
+    }
+    uint32_t te, tw, tb;
+    bam_block_excl(e, wsum, &te);
+    bam_block_excl(w, wsum, &tw);
+    bam_block_excl(b, wsum, &tb);
+    if (threadIdx.x == 0) {
+        sum_e[blockIdx.x] = te;
+        sum_w[blockIdx.x] = tw;
+        sum_b[blockIdx.x] = tb;
+    }
+}
+
+// sum_e / sum_w / sum_b scanned: the workgroup's bases; the place inside the workgroup by the same prefix.  pairs[2 p] = the
+// first, [2 p + 1] = the second of the pair emitter i completes; wlist[w] = record, wpart[w] = participating index of the
+// w-th waiting record; woff[i]: 4 + block_size of a waiting record in, its offset among the carried bytes out
+__global__ void __launch_bounds__(BAM_TPB) k_mate_emit(BamMates m, const uint32_t *__restrict__ partner, const uint32_t *__restrict__ sum_e,
+                                                       const uint32_t *__restrict__ sum_w, const uint32_t *__restrict__ sum_b, uint32_t n_pairs, uint32_t n_wait,
+                                                       uint32_t *__restrict__ pairs, uint32_t *__restrict__ wlist, uint32_t *__restrict__ wpart,
+                                                       uint32_t *__restrict__ woff) {
+    __shared__ uint32_t wsum[BAM_TPB / VS_WAVE];
+    const uint32_t i = blockIdx.x * BAM_TPB + threadIdx.x;  // (launched only when the status words are clean)
+    const bool in = i < m.n_part;
+    const uint32_t j = in ? partner[i] : BAM_NONE;
+    const bool emits = in && j < i, waits = in && !(m.rank[i] & BAM_MATE_PAIRED);
+    const uint32_t bytes = waits ? woff[i] : 0u;
+    uint32_t t;
+    const uint32_t p = sum_e[blockIdx.x] + bam_block_excl(emits ? 1u : 0u, wsum, &t);
+    const uint32_t w = sum_w[blockIdx.x] + bam_block_excl(waits ? 1u : 0u, wsum, &t);
+    const uint32_t o = sum_b[blockIdx.x] + bam_block_excl(bytes, wsum, &t);
+    if (emits && p < n_pairs) {
+        const bool i_first = bam_mate_cls(m, i) == (uint32_t)BAM_C_FIRST;
+        pairs[2u * p] = m.part[i_first ? i : j];
+        pairs[2u * p + 1u] = m.part[i_first ? j : i];
+    }
+    if (waits && w < n_wait) {
+        wlist[w] = m.part[i];
+        wpart[w] = i;
+        woff[i] = o;
+    }
+}
+
+// a wavefront per waiting record: its 4 + block_size bytes to dst + woff[its participating index]
+__global__ void __launch_bounds__(BAM_TPB) k_mate_carry(BamMates m, uint64_t n, const uint32_t *__restrict__ wpart, uint32_t n_wait,
+                                                        const uint32_t *__restrict__ woff, uint8_t *__restrict__ dst, uint64_t dst_size) {
+    const uint32_t w = (blockIdx.x * BAM_TPB + threadIdx.x) / VS_WAVE, lane = threadIdx.x & (VS_WAVE - 1u);
+    if (w >= n_wait) return;
+    const uint32_t i = wpart[w];
+    if (i >= m.n_part) return;
+    const uint64_t off = bam_mate_off(m, i), to = woff[i];
+    if (off + 4u > n) return;
+    const uint64_t len = 4ull + bam_le32(m.win + off);
+    if (off + len > n || to + len > dst_size) return;
+    const uint8_t *s = m.win + off;
+    uint8_t *t = dst + to;
+    uint64_t head = len, body = 0;
+    if ((((uintptr_t)s ^ (uintptr_t)t) & 15u) == 0u) {  // aligned alike: bytes up to a 16-byte boundary, 16 bytes a lane, the rest
+        head = (16u - ((uintptr_t)t & 15u)) & 15u;
+        if (head > len) head = len;
+        body = (len - head) >> 4;
+    }
+    for (uint64_t k = lane; k < head; k += VS_WAVE) t[k] = s[k];
+    const uint4 *s16 = (const uint4 *)(s + head);
+    uint4 *t16 = (uint4 *)(t + head);
+    for (uint64_t k = lane; k < body; k += VS_WAVE) t16[k] = s16[k];
+    for (uint64_t k = head + 16u * body + lane; k < len; k += VS_WAVE) t[k] = s[k];
+}
+
+// the ends of pairs [pair0, pair0 + n_pairs) of the pair list: as k_bam_ends, the two records taken from the list
+__global__ void __launch_bounds__(BAM_TPB) k_bam_ends_list(const uint4 *__restrict__ recs, const uint32_t *__restrict__ pairs, uint32_t pair0, uint32_t n_pairs,
+                                                           uint32_t n_rec, uint32_t *__restrict__ ends, uint32_t *__restrict__ meta,
+                                                           uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
+    const uint32_t e = blockIdx.x * BAM_TPB + threadIdx.x, n_ends = 2u * n_pairs;
+    if (e > n_ends) return;
+    if (e == n_ends) {
+        wcnt[e] = 0u;
+        return;
+    }
+    const uint32_t r = pairs[2u * pair0 + e];
+    const uint32_t len = r < n_rec ? recs[r].z : 0u;
+    ends[e] = r < n_rec ? r : 0u;
+    if (r >= n_rec) atomicMin(&st[B_BADCOUPLE], e >> 1);  // (never: the list holds records of this window)
+    if (len > VS_LEN_MASK) {
+        atomicMin(&st[B_TOO_LONG], e);
+        meta[e] = 0u;
+        wcnt[e] = 0u;
+        return;
+    }
+    meta[e] = len;
+    wcnt[e] = (len + 15u) >> 4;
+    atomicMax(&st[B_MAXLEN], len);
+}
+
 // ---- the chain on a device window ---------------------------------------------------------------------------------------
 namespace {
 
@@ -246,6 +430,92 @@ void launch_ends(hipStream_t st, const BamScan &sc, uint32_t part0, uint32_t n_p
                        sc.part.as<const uint32_t>(), part0, n_pairs, sc.n_rec, sc.stop, ends, meta, wcnt, d_stat);
 }
 
+// the match of a scanned window
+struct BamMatch {
+    VsDevBuf hash, table, slot, next, rank, partner, woff, sums, pairs, wlist, wpart, stat;
+    uint32_t n_pairs = 0, n_wait = 0, wait_bytes = 0, crowded = BAM_NONE;
+    BamMates view = {};
+};
+
+// the pairs and the waiting records of the scanned window win[0, n) on stream st (synchronises it).  mt.crowded: the newest
+// record of a name with more than BAM_MATE_CAP records of one class (then there are no lists), else BAM_NONE.
+int bam_match_device(vs_ctx *ctx, hipStream_t st, const uint8_t *win, uint64_t n, const BamScan &sc, uint32_t bits, BamMatch &mt) {
+    mt.n_pairs = mt.n_wait = mt.wait_bytes = 0;
+    mt.crowded = BAM_NONE;
+    const uint32_t np = sc.n_part;
+    if (!np) return VS_OK;
+    if (np > 0x3FFFFFFFu) return vs_fail(ctx, VS_E_RANGE, "%u records to match by name in one window", np);
+    const uint32_t size = bam_table_size(np);
+    if (int rc = reserve_n<uint64_t>(ctx, mt.hash, np)) return rc;
+    if (int rc = reserve_n<uint32_t>(ctx, mt.table, 2u * (size_t)size)) return rc;
+    for (VsDevBuf *b : {&mt.slot, &mt.next, &mt.rank, &mt.partner, &mt.woff})
+        if (int rc = reserve_n<uint32_t>(ctx, *b, (size_t)np + 1u)) return rc;
+    const uint32_t n_wg = (np + BAM_TPB - 1u) / BAM_TPB;
+    if (int rc = reserve_n<uint32_t>(ctx, mt.sums, 3u * (size_t)n_wg)) return rc;
+    uint32_t *sum_e = mt.sums.as<uint32_t>(), *sum_w = sum_e + n_wg, *sum_b = sum_w + n_wg;
+    if (int rc = reserve_n<uint32_t>(ctx, mt.stat, M_ALL)) return rc;
+    uint32_t *d_ms = mt.stat.as<uint32_t>(), h_ms[M_ALL];
+    BamMates &m = mt.view;
+    m.win = win;
+    m.recs = (const uint32_t *)sc.recs.as<uint4>();
+    m.part = sc.part.as<const uint32_t>();
+    m.n_rec = sc.n_rec;
+    m.n_part = np;
+    m.hash = mt.hash.as<uint64_t>();
+    m.table = mt.table.as<uint32_t>();
+    m.head = m.table + size;
+    m.size = size;
+    m.slot = mt.slot.as<uint32_t>();
+    m.next = mt.next.as<uint32_t>();
+    m.rank = mt.rank.as<uint32_t>();
+    VS_HIP(ctx, hipMemsetAsync(d_ms, 0, sizeof(uint32_t) * M_ALL, st));
+    VS_HIP(ctx, hipMemsetAsync(d_ms + M_CROWDED, 0xFF, sizeof(uint32_t), st));
+    VS_HIP(ctx, hipMemsetAsync(m.table, 0xFF, sizeof(uint32_t) * 2u * (size_t)size, st));
+    const dim3 grid(n_wg), tpb(BAM_TPB);
+    hipLaunchKernelGGL(k_mate_hash, grid, tpb, 0, st, m, n, bits, d_ms);
+    VS_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_mate_claim, grid, tpb, 0, st, m, d_ms);
+    VS_HIP(ctx, hipGetLastError());
+    VS_HIP(ctx, hipMemsetAsync(sum_e, 0, sizeof(uint32_t) * 3u * (size_t)n_wg, st));
+    hipLaunchKernelGGL(k_mate_rank, grid, tpb, 0, st, m, mt.woff.as<uint32_t>(), d_ms);
+    VS_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_mate_partner, grid, tpb, 0, st, m, mt.partner.as<uint32_t>(), mt.woff.as<const uint32_t>(), sum_e, sum_w, sum_b, d_ms);
+    VS_HIP(ctx, hipGetLastError());
+    vs_launch_scan_u32(st, sum_e, n_wg, d_ms + M_NPAIRS);  // (a word per workgroup: the places inside one are found in k_mate_emit)
+    VS_HIP(ctx, hipGetLastError());
+    vs_launch_scan_u32(st, sum_w, n_wg, d_ms + M_NWAIT);
+    VS_HIP(ctx, hipGetLastError());
+    vs_launch_scan_u32(st, sum_b, n_wg, d_ms + M_WBYTES);
+    VS_HIP(ctx, hipGetLastError());
+    VS_HIP(ctx, hipMemcpyAsync(h_ms, d_ms, sizeof(uint32_t) * M_ALL, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
+    if (h_ms[M_BAD]) return vs_fail(ctx, VS_E_STATE, "matching by name: %s", (h_ms[M_BAD] & 1u) ? "a record index beyond the window's records" : "the name table is full");
+    if (h_ms[M_CROWDED] != BAM_NONE) {
+        mt.crowded = ~h_ms[M_CROWDED];
+        return VS_OK;
+    }
+    mt.n_pairs = h_ms[M_NPAIRS];
+    mt.n_wait = h_ms[M_NWAIT];
+    mt.wait_bytes = h_ms[M_WBYTES];
+    if (int rc = reserve_n<uint32_t>(ctx, mt.pairs, 2u * (size_t)mt.n_pairs + 1u)) return rc;
+    if (int rc = reserve_n<uint32_t>(ctx, mt.wlist, (size_t)mt.n_wait + 1u)) return rc;
+    if (int rc = reserve_n<uint32_t>(ctx, mt.wpart, (size_t)mt.n_wait + 1u)) return rc;
+    hipLaunchKernelGGL(k_mate_emit, grid, tpb, 0, st, m, mt.partner.as<const uint32_t>(), sum_e, sum_w, sum_b, mt.n_pairs, mt.n_wait, mt.pairs.as<uint32_t>(),
+                       mt.wlist.as<uint32_t>(), mt.wpart.as<uint32_t>(), mt.woff.as<uint32_t>());
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}
+
+// the waiting records of a matched window win[0, n) to dst[0, wait_bytes), in window order
+int bam_carry_device(vs_ctx *ctx, hipStream_t st, uint64_t n, const BamMatch &mt, uint8_t *dst, uint64_t dst_size) {
+    if (!mt.n_wait) return VS_OK;
+    const uint64_t threads = (uint64_t)mt.n_wait * VS_WAVE;
+    hipLaunchKernelGGL(k_mate_carry, dim3((unsigned)((threads + BAM_TPB - 1u) / BAM_TPB)), dim3(BAM_TPB), 0, st, mt.view, n, mt.wpart.as<const uint32_t>(), mt.n_wait,
+                       mt.woff.as<const uint32_t>(), dst, dst_size);
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}
+
 void fill_info(uint64_t info[6], uint64_t n_rec, uint64_t n_part, uint32_t end, uint64_t stop, uint32_t malformed, uint32_t bad_couple) {
     info[0] = n_rec;
     info[1] = n_part;
@@ -281,6 +551,13 @@ struct vs_bam_stream {
     bool done = false;
     int failed = VS_OK;
     std::string failed_msg;
+    // by name
+    bool by_name = false;
+    uint32_t name_bits = 64;
+    BamMatch mt;
+    uint32_t pair_cur = 0;   // the first pair of the matched window not yet delivered
+    uint32_t n_carried = 0;  // the window's first records are the ones carried from earlier windows (first_record: its first NEW one)
+    uint64_t singletons = 0, waiting_max = 0, carried_bytes_max = 0, windows = 0;
 };
 
 namespace {
@@ -292,11 +569,12 @@ int bam_fail(vs_ctx *ctx, vs_bam_stream *s, int code, const std::string &msg) {
     return vs_fail(ctx, code, "%s", msg.c_str());
 }
 
+// (rec: index in the window; the records carried in front of the new ones have been numbered before)
 std::string rec_msg(const vs_bam_stream *s, uint64_t rec, const char *what) {
-    return s->rd.path + ": record " + std::to_string(rec) + what;
+    return s->rd.path + ": record " + std::to_string(s->first_record + rec - std::min<uint64_t>(rec, s->n_carried)) + what;
 }
 
-const char *NOT_COLLATED = ": the file is not collated (mates do not follow each other); run `samtools collate` on it first";
+const char *NOT_COLLATED = ": the file is not collated (mates do not follow each other); run `samtools collate` on it first, or match the mates by name (--bam-by-name)";
 
 // the window after its first `cut` bytes have gone: the leftover to the front of the other buffer
 int bam_drop_front(vs_ctx *ctx, vs_bam_stream *s, size_t cut) {
@@ -317,7 +595,10 @@ int bam_append(vs_ctx *ctx, vs_bam_stream *s) {
         ~Back() { r.give_back(); }
     } back = {s->rd};
     if (s->size + sl.text > STREAM_MAX_WINDOW)
-        return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete pair", s->rd.path.c_str(), (unsigned long long)(s->size + sl.text));
+        return s->by_name ? vs_fail(ctx, VS_E_RANGE, "%s: the records that wait for their mates and the next chunk make a window of %llu bytes (the limit is %llu): "
+                                                     "the mates lie too far apart to be matched by name; run `samtools collate` on the file first",
+                                    s->rd.path.c_str(), (unsigned long long)(s->size + sl.text), (unsigned long long)STREAM_MAX_WINDOW)
+                          : vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete pair", s->rd.path.c_str(), (unsigned long long)(s->size + sl.text));
     const size_t need = ((s->size + sl.text + 15u) & ~(size_t)15u) + 16u;
     if (s->win[s->cur].capacity() < need) {
         const int o = s->cur ^ 1;
@@ -362,19 +643,43 @@ int bam_pass(vs_ctx *ctx, vs_bam_stream *s, uint32_t upto) {
     return VS_OK;
 }
 
+// by name: the window is done.  The next one starts with its waiting records, whole and in file order, then the bytes from
+// `stop` on (the record the window's end cut, or nothing)
+int bam_carry_waiting(vs_ctx *ctx, vs_bam_stream *s) {
+    const BamMatch &mt = s->mt;
+    if (s->sc.stop > s->size) return vs_fail(ctx, VS_E_STATE, "%s: a record start beyond the window", s->rd.path.c_str());
+    const size_t rest = s->size - s->sc.stop, total = (size_t)mt.wait_bytes + rest;
+    const int o = s->cur ^ 1;
+    if (int rc = reserve_n<uint8_t>(ctx, s->win[o], ((total + 15u) & ~(size_t)15u) + 16u)) return rc;
+    if (int rc = bam_carry_device(ctx, s->st, s->size, mt, s->win[o].as<uint8_t>(), mt.wait_bytes)) return rc;
+    if (rest)
+        VS_HIP(ctx, hipMemcpyAsync(s->win[o].as<uint8_t>() + mt.wait_bytes, s->win[s->cur].as<uint8_t>() + s->sc.stop, rest, hipMemcpyDeviceToDevice, s->st));
+    s->first_record += s->sc.n_rec - s->n_carried;
+    s->n_carried = mt.n_wait;
+    s->waiting_max = std::max<uint64_t>(s->waiting_max, mt.n_wait);
+    s->carried_bytes_max = std::max<uint64_t>(s->carried_bytes_max, mt.wait_bytes);
+    s->cur = o;
+    s->size = total;
+    return VS_OK;
+}
+
 // the end of the input: what is left in the window is passed, and said if it is no whole couple
 int bam_finish(vs_ctx *ctx, vs_bam_stream *s) {
     if (s->rd.err != VS_OK) return bam_fail(ctx, s, s->rd.err, s->rd.err_msg);
     uint32_t odd = BAM_NONE;
-    if (s->scanned) {
+    if (s->scanned && s->by_name) {  // (its records are counted already; what still waits has no mate in the file)
+        VS_HIP(ctx, hipStreamSynchronize(s->st));
+        if (s->sc.end == BAM_END_CUT) return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->sc.n_rec, ": truncated record (the file ends inside it)"));
+        s->singletons += s->mt.n_wait;
+    } else if (s->scanned) {
         if (s->sc.n_part - s->part_cur == 1u)
             VS_HIP(ctx, hipMemcpyAsync(&odd, s->sc.part.as<uint32_t>() + s->part_cur, sizeof odd, hipMemcpyDeviceToHost, s->st));
         if (int rc = bam_pass(ctx, s, s->sc.n_rec)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
         VS_HIP(ctx, hipStreamSynchronize(s->st));
         if (s->sc.end == BAM_END_CUT)
-            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + s->sc.n_rec, ": truncated record (the file ends inside it)"));
+            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->sc.n_rec, ": truncated record (the file ends inside it)"));
         if (odd != BAM_NONE)
-            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + odd, " has no mate behind it") + NOT_COLLATED);
+            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, odd, " has no mate behind it") + NOT_COLLATED);
     } else if (s->skip) {
         return bam_fail(ctx, s, VS_E_STATE, s->rd.path + " ends inside its header (did it change after it was opened?)");
     }
@@ -461,8 +766,10 @@ int vs_bam_header(const char *path, uint64_t *header_bytes) {
     }
 }
 
-int vs_bam_stream_open(vs_ctx *ctx, const char *path, vs_bam_stream **out) {
-    if (!ctx || !path || !out) return vs_fail(ctx, VS_E_ARG, "vs_bam_stream_open: bad argument");
+int vs_bam_stream_open(vs_ctx *ctx, const char *path, vs_bam_stream **out) { return vs_bam_stream_open_mode(ctx, path, VS_BAM_COLLATED, out); }
+
+int vs_bam_stream_open_mode(vs_ctx *ctx, const char *path, int mode, vs_bam_stream **out) {
+    if (!ctx || !path || !out || (mode != VS_BAM_COLLATED && mode != VS_BAM_BY_NAME)) return vs_fail(ctx, VS_E_ARG, "vs_bam_stream_open: bad argument");
     *out = nullptr;
     uint64_t header = 0;
     if (int rc = vs_bam_header(path, &header)) return vs_fail(ctx, rc, "%s", vs_last_error(nullptr));
@@ -470,6 +777,8 @@ int vs_bam_stream_open(vs_ctx *ctx, const char *path, vs_bam_stream **out) {
     vs_bam_stream *s = new vs_bam_stream();
     s->device = ctx->device;
     s->skip = header;
+    s->by_name = mode == VS_BAM_BY_NAME;
+    if (const char *ev = getenv("VS_BAM_NAME_BITS")) s->name_bits = (uint32_t)std::min<long long>(std::max<long long>(atoll(ev), 0), 64);  // (tests: long probe chains)
     if (const char *ev = getenv("VS_BAM_SEG")) s->seg = seg_checked((uint32_t)atoll(ev));  // (tests: records across segments)
     Reader &r = s->rd;
     r.path = path;
@@ -510,18 +819,22 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
     BamScan &sc = s->sc;
     for (;;) {
         if (s->scanned) {
-            if ((sc.n_part - s->part_cur) / 2u > 0u) break;
+            if (s->by_name ? s->pair_cur < s->mt.n_pairs : (sc.n_part - s->part_cur) / 2u > 0u) break;
             if (s->eof) return bam_finish(ctx, s);
-            // the carry: everything from the first record not delivered
-            uint32_t cut = sc.stop;
-            if (s->rec_cur < sc.n_rec) {
-                VS_HIP(ctx, hipMemcpyAsync(&cut, (const uint32_t *)(sc.recs.as<uint4>() + s->rec_cur), sizeof cut, hipMemcpyDeviceToHost, st));
-                VS_HIP(ctx, hipStreamSynchronize(st));
+            if (s->by_name) {
+                if (int rc = bam_carry_waiting(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            } else {
+                // the carry: everything from the first record not delivered
+                uint32_t cut = sc.stop;
+                if (s->rec_cur < sc.n_rec) {
+                    VS_HIP(ctx, hipMemcpyAsync(&cut, (const uint32_t *)(sc.recs.as<uint4>() + s->rec_cur), sizeof cut, hipMemcpyDeviceToHost, st));
+                    VS_HIP(ctx, hipStreamSynchronize(st));
+                }
+                if (cut > s->size) return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": a record start beyond the window");
+                if (int rc = bam_drop_front(ctx, s, cut)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+                s->first_record += s->rec_cur;
             }
-            if (cut > s->size) return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": a record start beyond the window");
-            if (int rc = bam_drop_front(ctx, s, cut)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
-            s->first_record += s->rec_cur;
-            s->rec_cur = s->part_cur = 0;
+            s->rec_cur = s->part_cur = s->pair_cur = 0;
             s->scanned = false;
         }
         if (!s->eof) {
@@ -543,12 +856,22 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
             return bam_fail(ctx, s, VS_E_ARG, s->rd.path + ": not a complete gzip stream (BGZF member " + std::to_string(s->h_stat[B_BAD_MEMBER]) +
                                                   " does not inflate to its CRC32 and size)");
         if (sc.malformed != BAM_NONE)
-            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + sc.malformed, " is malformed: its name, cigar, sequence and quality need more than its block_size"));
+            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, sc.malformed, " is malformed: its name, cigar, sequence and quality need more than its block_size"));
         if (sc.end == BAM_END_DEAD)
-            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + sc.n_rec, " is malformed: its block_size is below the 32 bytes of the fixed part"));
+            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, sc.n_rec, " is malformed: its block_size is below the 32 bytes of the fixed part"));
+        if (s->by_name) {
+            s->windows++;
+            s->pair_cur = 0;
+            if (int rc = bam_match_device(ctx, st, s->win[s->cur].as<const uint8_t>(), s->size, sc, s->name_bits, s->mt)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            if (s->mt.crowded != BAM_NONE)
+                return bam_fail(ctx, s, VS_E_RANGE, rec_msg(s, s->mt.crowded, " is one of more than 64 records of one name and one end (first or second) in a window: mates "
+                                                                              "are matched by name among at most 64 such records; run `samtools collate` on the file first"));
+            s->rec_cur = std::min(s->n_carried, sc.n_rec);  // (the carried records were counted in their own windows)
+            if (int rc = bam_pass(ctx, s, sc.n_rec)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+        }
     }
     // ---- the block of n couples from the cursor
-    const uint64_t n = std::min<uint64_t>((sc.n_part - s->part_cur) / 2u, max_pairs), n_ends = 2u * n;
+    const uint64_t n = std::min<uint64_t>(s->by_name ? s->mt.n_pairs - s->pair_cur : (sc.n_part - s->part_cur) / 2u, max_pairs), n_ends = 2u * n;
     if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
     if (int rc = reserve_n<uint32_t>(ctx, s->d_ends, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
     vs_reads *r = new vs_reads();
@@ -565,7 +888,11 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
     if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0xFF, sizeof(uint32_t), st);
     if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_TOO_LONG, 0xFF, sizeof(uint32_t), st);
     if (e1 != hipSuccess) return fail(e1);
-    launch_ends(st, sc, s->part_cur, (uint32_t)n, s->d_ends.as<uint32_t>(), (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
+    if (s->by_name)
+        hipLaunchKernelGGL(k_bam_ends_list, dim3((unsigned)((n_ends + 1u + BAM_TPB - 1u) / BAM_TPB)), dim3(BAM_TPB), 0, st, sc.recs.as<const uint4>(),
+                           s->mt.pairs.as<const uint32_t>(), s->pair_cur, (uint32_t)n, sc.n_rec, s->d_ends.as<uint32_t>(), (uint32_t *)r->d_meta,
+                           s->d_wcnt.as<uint32_t>(), s->d_stat);
+    else launch_ends(st, sc, s->part_cur, (uint32_t)n, s->d_ends.as<uint32_t>(), (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
     if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
     vs_launch_scan_u32(st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + B_WORDS);
     if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
@@ -573,12 +900,16 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
     if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * B_BAD_MEMBER, hipMemcpyDeviceToHost, st);
     if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
     if (e1 != hipSuccess) return fail(e1);
+    if (s->h_stat[B_BADCOUPLE] != BAM_NONE && s->by_name) {
+        vs_reads_free(ctx, r);
+        return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": a pair of the name match names a record beyond the window's");
+    }
     if (s->h_stat[B_BADCOUPLE] != BAM_NONE) {
         uint32_t second = 0;
         e1 = hipMemcpy(&second, sc.part.as<uint32_t>() + s->part_cur + 2u * s->h_stat[B_BADCOUPLE] + 1u, sizeof second, hipMemcpyDeviceToHost);
         if (e1 != hipSuccess) return fail(e1);
         vs_reads_free(ctx, r);
-        return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->first_record + second, " is the same end (first or second) of a pair as the record it is coupled with") + NOT_COLLATED);
+        return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, second, " is the same end (first or second) of a pair as the record it is coupled with") + NOT_COLLATED);
     }
     if (s->h_stat[B_TOO_LONG] != BAM_NONE) {
         vs_reads_free(ctx, r);
@@ -591,9 +922,10 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
     vs_launch_pack_bam(st, BamEnds{s->win[s->cur].as<const uint8_t>(), (const uint32_t *)sc.recs.as<uint4>(), s->d_ends.as<const uint32_t>()}, r);
     if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
     if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + B_INVALID, s->h_stat + B_INVALID)) != hipSuccess) return fail(e1);
-    if (bam_pass(ctx, s, s->h_stat[B_CUTREC]) != VS_OK) return fail(hipErrorUnknown);
+    if (!s->by_name && bam_pass(ctx, s, s->h_stat[B_CUTREC]) != VS_OK) return fail(hipErrorUnknown);
     if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
-    s->part_cur += (uint32_t)n_ends;
+    if (s->by_name) s->pair_cur += (uint32_t)n;
+    else s->part_cur += (uint32_t)n_ends;
     s->pairs += n;
     *out = r;
     *n_pairs = n;
@@ -611,6 +943,15 @@ int vs_bam_stream_info(const vs_bam_stream *s, uint64_t info[8]) {
     info[5] = s->rd.text_bytes;
     info[6] = s->rd.raw_bytes;
     info[7] = s->done ? 1u : 0u;
+    return VS_OK;
+}
+
+int vs_bam_stream_mate_info(const vs_bam_stream *s, uint64_t info[4]) {
+    if (!s || !info) return VS_E_ARG;
+    info[0] = s->singletons;
+    info[1] = s->waiting_max;
+    info[2] = s->carried_bytes_max;
+    info[3] = s->windows;
     return VS_OK;
 }
 
@@ -703,6 +1044,60 @@ int vs_bam_scan_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t ski
         if (m) VS_HIP(ctx, hipMemcpy(ends, d_ends.ptr(), sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
     }
     fill_info(info, sc.n_rec, sc.n_part, sc.end, sc.stop, sc.malformed, bad_couple);
+    return VS_OK;
+}
+
+// ---- test aids: the match of one window -----------------------------------------------------------------------------------
+static void mates_info(uint64_t info[3], uint64_t pairs, uint64_t waiting, uint64_t crowded) {
+    info[0] = pairs;
+    info[1] = waiting;
+    info[2] = crowded;
+}
+
+int vs_bam_mates_host(const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t hash_bits, uint32_t *pairs, uint64_t cap_pairs,
+                      uint32_t *waiting, uint64_t cap_waiting, uint64_t info[3]) {
+    if ((!bytes && n) || !info || (!pairs && cap_pairs) || (!waiting && cap_waiting) || n > STREAM_MAX_WINDOW || skip > n || hash_bits > 64u)
+        return vs_fail(nullptr, VS_E_ARG, "vs_bam_mates_host: bad argument");
+    const uint64_t cap = n / 36u + 1u;
+    std::vector<uint32_t> recs(4u * cap), ends(1);
+    uint64_t sinfo[6];
+    if (int rc = vs_bam_scan_host(bytes, n, skip, seg, recs.data(), cap, ends.data(), 0, sinfo)) return rc;
+    std::vector<uint32_t> part;
+    for (uint64_t r = 0; r < sinfo[0]; r++)
+        if ((recs[4u * r + 1u] >> 16) <= (uint32_t)BAM_C_SECOND) part.push_back((uint32_t)r);
+    const uint32_t np = (uint32_t)part.size(), size = bam_table_size(np);
+    std::vector<uint64_t> hash(np);
+    std::vector<uint32_t> table(size), head(size), slot(np), next(np), rank(np);
+    BamMates m = {bytes, recs.data(), part.data(), (uint32_t)sinfo[0], np, hash.data(), table.data(), head.data(), size, slot.data(), next.data(), rank.data()};
+    uint64_t minfo[4];
+    bam_mates_serial(m, hash_bits, pairs, cap_pairs, waiting, cap_waiting, minfo);
+    if (minfo[3]) return vs_fail(nullptr, VS_E_STATE, "vs_bam_mates_host: the name table is full");
+    mates_info(info, minfo[0], minfo[1], minfo[2]);
+    return VS_OK;
+}
+
+int vs_bam_mates_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t hash_bits, uint32_t *pairs, uint64_t cap_pairs,
+                      uint32_t *waiting, uint64_t cap_waiting, uint64_t info[3]) {
+    if (!ctx || (!bytes && n) || !info || (!pairs && cap_pairs) || (!waiting && cap_waiting) || n > STREAM_MAX_WINDOW || skip > n || hash_bits > 64u)
+        return vs_fail(ctx, VS_E_ARG, "vs_bam_mates_text: bad argument");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    seg = seg_checked(seg);
+    hipStream_t st = ctx->stream;
+    VsDevBuf win, stat;
+    BamScan sc;
+    BamMatch mt;
+    uint32_t hs[B_ALL] = {0};
+    VS_HIP(ctx, win.reserve(((n + 15u) & ~(uint64_t)15u) + 16u));
+    VS_HIP(ctx, stat.reserve(sizeof(uint32_t) * B_ALL));
+    if (n) VS_HIP(ctx, hipMemcpyAsync(win.ptr(), bytes, n, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipMemsetAsync(stat.ptr(), 0, sizeof(uint32_t) * B_ALL, st));
+    if (int rc = bam_scan_device(ctx, st, win.as<const uint8_t>(), n, skip, seg, sc, stat.as<uint32_t>(), hs)) return rc;
+    if (int rc = bam_match_device(ctx, st, win.as<const uint8_t>(), n, sc, hash_bits, mt)) return rc;
+    VS_HIP(ctx, hipStreamSynchronize(st));
+    const uint64_t np = std::min<uint64_t>(cap_pairs, mt.n_pairs), nw = std::min<uint64_t>(cap_waiting, mt.n_wait);
+    if (np) VS_HIP(ctx, hipMemcpy(pairs, mt.pairs.ptr(), sizeof(uint32_t) * 2u * np, hipMemcpyDeviceToHost));
+    if (nw) VS_HIP(ctx, hipMemcpy(waiting, mt.wlist.ptr(), sizeof(uint32_t) * nw, hipMemcpyDeviceToHost));
+    mates_info(info, mt.n_pairs, mt.n_wait, mt.crowded == BAM_NONE ? ~0ull : mt.crowded);
     return VS_OK;
 }
 

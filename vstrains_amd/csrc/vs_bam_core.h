@@ -158,3 +158,184 @@ BAM_HD uint8_t bam_base(const uint8_t *seq, uint32_t len, bool rev, uint32_t p) 
 
 // a couple of participating records: one first and one second, in either order
 BAM_HD bool bam_couple_ok(uint32_t flag_cls_a, uint32_t flag_cls_b) { return ((flag_cls_a >> 16) ^ (flag_cls_b >> 16)) == 1u; }
+
+// ---- mates by name ---------------------------------------------------------------------------------------------------------
+// The rule, once: the participating records (classes first and second) are walked in file order and a set of waiting
+// records is kept.  A record of class c looks for waiting records of the same name and the OTHER class; it forms a pair
+// with the OLDEST of them (which stops waiting), or waits itself when there is none.  So the j-th first of a name pairs
+// with the j-th second of that name, pairs are delivered in the order of the record that completed them, and what waits
+// at the end of the input are singletons.  The name of a record is its l_read_name bytes as they lie in the record,
+// terminator included; names are equal when lengths and bytes are, never because a hash is.
+//
+// Window-wise, which is what the kernels and the host twin run: in a window [waiting records of earlier windows, in file
+// order][new records] the members of a name are ranked within their own class in window order; member i is paired exactly
+// when its rank is below the number of members of the other class, with the other class's member of the same rank, and the
+// LATER of the two emits the pair.  The waiting records of one name are all of one class (two of different classes would
+// have paired), they are the oldest unpaired of it and keep their order, so ranks in the window continue the ranks in the
+// file and the two forms give the same pairs, the same order and the same waiting set wherever the windows are cut.
+//
+//   hash     bam_name_hash of every participating record (VS_BAM_NAME_BITS / hash_bits keep the low bits only: tests)
+//   claim    bam_mate_claim: an open-address table of participating indices, a power of two and at most half full; a
+//            record probes linearly from its hash, claims an empty slot by compare-and-swap or finds its name's
+//            representative there (hash first, then the bytes); then it pushes itself on the slot's list (exchange)
+//   rank     bam_mate_rank: a walk of the name's list, at most 2 * BAM_MATE_CAP + 1 steps: rank in the own class, paired or
+//            not; more than BAM_MATE_CAP records of one name and class in a window are refused ("crowded"), which bounds
+//            every walk
+//   partner  bam_mate_partner: the same walk for the other class's member of the same rank
+#define BAM_MATE_CAP 64u
+#define BAM_MATE_PAIRED 0x80000000u  // in rank[]: the member is paired in this window
+
+struct BamMates {
+    const uint8_t *win;
+    const uint32_t *recs;  // 4 words per record: BamRec
+    const uint32_t *part;  // record index of every participating record, in window order
+    uint32_t n_rec, n_part;
+    uint64_t *hash;         // [n_part]
+    uint32_t *table, *head; // [size]: participating index of the name's representative / of the newest pushed member
+    uint32_t size;          // a power of two >= 2 * n_part
+    uint32_t *slot, *next, *rank;  // [n_part]
+};
+
+BAM_HD uint32_t bam_table_size(uint32_t n_part) {
+    uint32_t s = 2u;
+    while (s < 2u * n_part && s < 0x80000000u) s <<= 1;
+    return s;
+}
+
+BAM_HD uint32_t bam_cas(uint32_t *p, uint32_t expect, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return atomicCAS(p, expect, v);
+#else
+    const uint32_t old = *p;
+    if (old == expect) *p = v;
+    return old;
+#endif
+}
+BAM_HD uint32_t bam_exch(uint32_t *p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return atomicExch(p, v);
+#else
+    const uint32_t old = *p;
+    *p = v;
+    return old;
+#endif
+}
+
+// the name of the (well-formed, whole) record at off: l_read_name bytes behind the fixed part
+BAM_HD uint64_t bam_name_hash(const uint8_t *win, uint32_t off, uint32_t bits) {
+    const uint8_t *p = win + off;
+    const uint32_t l = p[12];
+    uint64_t h = 0xCBF29CE484222325ull;  // FNV-1a, then the finaliser of MurmurHash3 so that the low bits depend on every byte
+    for (uint32_t i = 0; i < l; i++) h = (h ^ p[36u + i]) * 0x100000001B3ull;
+    h ^= h >> 33;
+    h *= 0xFF51AFD7ED558CCDull;
+    h ^= h >> 33;
+    h *= 0xC4CEB9FE1A85EC53ull;
+    h ^= h >> 33;
+    return bits >= 64u ? h : bits == 0u ? 0ull : h & ((1ull << bits) - 1ull);
+}
+BAM_HD bool bam_name_eq(const uint8_t *win, uint32_t off_a, uint32_t off_b) {
+    const uint8_t *a = win + off_a, *b = win + off_b;
+    const uint32_t l = a[12];
+    if (l != b[12]) return false;
+    for (uint32_t i = 0; i < l; i++)
+        if (a[36u + i] != b[36u + i]) return false;
+    return true;
+}
+
+// participating record i < n_part: its record (BAM_NONE: an index out of range), offset and class
+BAM_HD uint32_t bam_mate_rec(const BamMates &m, uint32_t i) {
+    const uint32_t r = m.part[i];
+    return r < m.n_rec ? r : BAM_NONE;
+}
+BAM_HD uint32_t bam_mate_off(const BamMates &m, uint32_t i) { return m.recs[4u * m.part[i]]; }
+BAM_HD uint32_t bam_mate_cls(const BamMates &m, uint32_t i) { return m.recs[4u * m.part[i] + 1u] >> 16; }
+
+// the slot of i's name (table[] and head[] are BAM_NONE before the first claim); BAM_NONE: no slot within `size` probes
+BAM_HD uint32_t bam_mate_claim(const BamMates &m, uint32_t i) {
+    const uint32_t mask = m.size - 1u, off = bam_mate_off(m, i);
+    const uint64_t h = m.hash[i];
+    uint32_t s = (uint32_t)h & mask;
+    for (uint32_t probe = 0; probe < m.size; probe++, s = (s + 1u) & mask) {
+        const uint32_t v = bam_cas(&m.table[s], BAM_NONE, i);  // (what the slot held: a lost race reads the winner here)
+        if (v == BAM_NONE || v == i) return s;
+        if (v < m.n_part && m.hash[v] == h && bam_name_eq(m.win, bam_mate_off(m, v), off)) return s;
+    }
+    return BAM_NONE;
+}
+BAM_HD void bam_mate_push(const BamMates &m, uint32_t i, uint32_t s) {
+    m.slot[i] = s;
+    m.next[i] = s < m.size ? bam_exch(&m.head[s], i) : BAM_NONE;
+}
+
+// rank of i among the members of its name and class in window order | BAM_MATE_PAIRED; *crowded: the name has more than
+// BAM_MATE_CAP members of one class in the window (the rank then means nothing)
+BAM_HD uint32_t bam_mate_rank(const BamMates &m, uint32_t i, bool *crowded) {
+    const uint32_t cls = bam_mate_cls(m, i), s = m.slot[i];
+    uint32_t lower = 0, own = 0, other = 0, steps = 0;
+    uint32_t j = s < m.size ? m.head[s] : BAM_NONE;
+    while (j < m.n_part && steps <= 2u * BAM_MATE_CAP) {  // (BAM_NONE ends a list)
+        if (bam_mate_cls(m, j) == cls) {
+            own++;
+            lower += j < i ? 1u : 0u;
+        } else other++;
+        j = m.next[j];
+        steps++;
+    }
+    *crowded = j < m.n_part || own > BAM_MATE_CAP || other > BAM_MATE_CAP;
+    return lower | (lower < other ? BAM_MATE_PAIRED : 0u);
+}
+
+// the member of the other class with i's rank (rank[] complete), BAM_NONE: there is none
+BAM_HD uint32_t bam_mate_partner(const BamMates &m, uint32_t i) {
+    const uint32_t cls = bam_mate_cls(m, i), s = m.slot[i], r = m.rank[i] & ~BAM_MATE_PAIRED;
+    uint32_t steps = 0;
+    uint32_t j = s < m.size ? m.head[s] : BAM_NONE;
+    while (j < m.n_part && steps <= 2u * BAM_MATE_CAP) {
+        if (bam_mate_cls(m, j) != cls && (m.rank[j] & ~BAM_MATE_PAIRED) == r) return j;
+        j = m.next[j];
+        steps++;
+    }
+    return BAM_NONE;
+}
+
+// All passes with one thread.  pairs[2 p], [2 p + 1]: record index of the first and the second of pair p, in delivery order
+// (at most cap_pairs pairs written); waiting[]: record index of every record left waiting, in window order (at most
+// cap_waiting); info[0] = pairs, [1] = waiting, [2] = the newest record of a crowded name (then no pair and no waiting
+// record is reported) or ~0, [3] = 1 when a record found no slot (the table was not half empty).
+inline void bam_mates_serial(const BamMates &m, uint32_t bits, uint32_t *pairs, uint64_t cap_pairs, uint32_t *waiting, uint64_t cap_waiting,
+                             uint64_t info[4]) {
+    for (uint32_t s = 0; s < m.size; s++) m.table[s] = m.head[s] = BAM_NONE;
+    uint64_t full = 0, crowded = ~0ull, n_pairs = 0, n_wait = 0;
+    for (uint32_t i = 0; i < m.n_part; i++) m.hash[i] = bam_name_hash(m.win, bam_mate_off(m, i), bits);
+    for (uint32_t i = 0; i < m.n_part; i++) {
+        const uint32_t s = bam_mate_claim(m, i);
+        if (s == BAM_NONE) full = 1;
+        bam_mate_push(m, i, s);
+    }
+    for (uint32_t i = 0; i < m.n_part; i++) {
+        bool c = false;
+        m.rank[i] = bam_mate_rank(m, i, &c);
+        if (c) crowded = m.part[i];  // (i rises: the newest stays)
+    }
+    if (crowded == ~0ull && !full)
+        for (uint32_t i = 0; i < m.n_part; i++) {
+            if (!(m.rank[i] & BAM_MATE_PAIRED)) {
+                if (n_wait < cap_waiting) waiting[n_wait] = m.part[i];
+                n_wait++;
+                continue;
+            }
+            const uint32_t j = bam_mate_partner(m, i);
+            if (j >= i) continue;  // (the later of the two emits)
+            const bool i_first = bam_mate_cls(m, i) == (uint32_t)BAM_C_FIRST;
+            if (n_pairs < cap_pairs) {
+                pairs[2u * n_pairs] = m.part[i_first ? i : j];
+                pairs[2u * n_pairs + 1u] = m.part[i_first ? j : i];
+            }
+            n_pairs++;
+        }
+    info[0] = n_pairs;
+    info[1] = n_wait;
+    info[2] = crowded;
+    info[3] = full;
+}

@@ -200,6 +200,9 @@ def _run(args, logger, backend=None):
         table = backend.pe_links("{0}/gfa/s_graph_L1.gfa".format(out), "{0}/aln".format(out), args.fwd, args.rve,
                                  pre.ksize, list(pre.nodes1.keys()))
     timings["pe_inference_s"] = time.time() - t0
+    singletons = (getattr(backend, "bam_info", None) or {}).get("singletons", 0)
+    if singletons:
+        logger.info("{0} records of the BAM have no mate in it and were dropped".format(singletons))
     logger.info("paired end information stored")
 
     t0 = time.time()

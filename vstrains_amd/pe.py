@@ -423,14 +423,24 @@ class BamStream:
     time, one first (the forward end) and one second in either order, an end with flag 0x10 reversed and complemented.
     Anything else -- two firsts in a row, an odd record at the end, a truncated or malformed record -- raises
     ``ValueError`` naming the record (numbered from 0 in file order).  Interface of ``FastqStream``; ``info`` has
-    ``pairs``, ``records``, ``dropped_0x900``, ``dropped_other``, ``members_device``, ``text_bytes``, ``file_bytes``."""
+    ``pairs``, ``records``, ``dropped_0x900``, ``dropped_other``, ``members_device``, ``text_bytes``, ``file_bytes``.
 
-    def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20):
+    ``by_name=True``: the records may lie in any order (a coordinate-sorted alignment, ``samtools view -f 12`` of one, a
+    file that lost one mate of some pairs).  The mates are matched on the device by their names, byte for byte: the j-th
+    first of a name pairs with its j-th second, pairs come in the order of the record that completed them, and a record
+    whose mate never comes is a singleton, dropped and counted -- the pair ``samtools collate | samtools fastq -1 -2 -s
+    /dev/null -0 /dev/null`` writes, up to the order of the pairs.  ``info`` also has ``singletons``, ``waiting_max`` (most
+    records carried from one window to the next), ``carried_bytes_max`` and ``windows``.  More than 64 records of one name
+    and one end in a window, or waiting records beyond the largest window, raise ``ValueError`` advising ``samtools
+    collate``."""
+
+    def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20, by_name: bool = False):
         self._ctx = ctx
         self._h = None
         self.block_pairs = block_pairs
+        self.by_name = bool(by_name)
         h = C.c_void_p()
-        rc = nat.lib().vs_bam_stream_open(ctx._h, path.encode(), C.byref(h))
+        rc = nat.lib().vs_bam_stream_open_mode(ctx._h, path.encode(), 1 if by_name else 0, C.byref(h))
         if rc != nat.VS_OK:
             msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
             if "cannot open" in msg:
@@ -444,8 +454,11 @@ class BamStream:
     def info(self):
         a = (C.c_uint64 * 8)()
         nat.lib().vs_bam_stream_info(self._h, a)
+        m = (C.c_uint64 * 4)()
+        nat.lib().vs_bam_stream_mate_info(self._h, m)
         return dict(pairs=int(a[0]), records=int(a[1]), dropped_0x900=int(a[2]), dropped_other=int(a[3]), members_device=int(a[4]),
-                    text_bytes=int(a[5]), file_bytes=int(a[6]), done=bool(a[7]))
+                    text_bytes=int(a[5]), file_bytes=int(a[6]), done=bool(a[7]), singletons=int(m[0]), waiting_max=int(m[1]),
+                    carried_bytes_max=int(m[2]), windows=int(m[3]))
 
     @property
     def n_pairs(self) -> int:
@@ -457,7 +470,7 @@ class BamStream:
         h = C.c_void_p()
         n = C.c_uint64(0)
         rc = nat.lib().vs_bam_stream_next(self._ctx._h, self._h, self.block_pairs, C.byref(h), C.byref(n))
-        if rc == nat.VS_E_ARG:
+        if rc == nat.VS_E_ARG or (rc == nat.VS_E_RANGE and self.by_name):  # (by name: a file the match refuses)
             raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
         nat.check(self._ctx._h, rc)
         return ReadBlock(self._ctx, h) if n.value else None
@@ -512,6 +525,28 @@ def bam_scan(data: bytes, skip: int = 0, seg: int = 0, ctx: "Context" = None):
     return recs[:n_rec], ends[:2 * (n_part // 2)].reshape(-1, 2), dict(
         records=n_rec, taking_part=n_part, end=int(info[2]), stop=int(info[3]),
         malformed=None if info[4] == none else int(info[4]), bad_couple=None if info[5] == none else int(info[5]))
+
+
+def bam_mates(data: bytes, skip: int = 0, seg: int = 0, ctx: "Context" = None, hash_bits: int = 64):
+    """The mates of ONE window of inflated BAM bytes matched by name (test aid): ``vs_bam_mates_host`` (one host thread),
+    or with ``ctx`` the kernels (``vs_bam_mates_text``).  Returns (pairs uint32 [n, 2]: record index of the first and the
+    second in delivery order; waiting uint32 [m]: the records left waiting, in file order; info dict: ``pairs``,
+    ``waiting``, ``crowded`` = the newest record of a name with more than 64 records of one end, or None)."""
+    buf = np.frombuffer(data or b"\0", dtype=np.uint8)
+    cap = len(data) // 36 + 1
+    pairs = np.zeros((cap, 2), dtype=np.uint32)
+    waiting = np.zeros(cap, dtype=np.uint32)
+    info = (C.c_uint64 * 3)()
+    if ctx is None:
+        rc = nat.lib().vs_bam_mates_host(buf.ctypes.data, len(data), skip, seg, hash_bits, pairs.ctypes.data, cap, waiting.ctypes.data, cap, info)
+        if rc != nat.VS_OK:
+            raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    else:
+        nat.check(ctx._h, nat.lib().vs_bam_mates_text(ctx._h, buf.ctypes.data, len(data), skip, seg, hash_bits, pairs.ctypes.data, cap,
+                                                     waiting.ctypes.data, cap, info))
+    none = (1 << 64) - 1
+    return pairs[:int(info[0])], waiting[:int(info[1])], dict(pairs=int(info[0]), waiting=int(info[1]),
+                                                              crowded=None if info[2] == none else int(info[2]))
 
 
 INFLATE_GUARD = 64  # bytes kept behind every member's output by the inflate test aids; they must stay INFLATE_GUARD_BYTE

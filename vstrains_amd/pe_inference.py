@@ -27,13 +27,16 @@ def _rank_world():
     return 0, 1
 
 
-def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow: bool = False):
+def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow: bool = False, bam_by_name: bool = False):
     """Index the nodes of ``gfa`` and count every pair of the two FASTQ files; the counters stay
     on the device.  Returns ``(node ids in file order, PeCounter)``.  ``stages_follow``: the graph stages will build their
     PE-link table from these counters in this process (the pipeline; not the stand-alone script, which writes the two text
-    files) -- the table's device buffer is then set aside together with the counters."""
+    files) -- the table's device buffer is then set aside together with the counters.  ``bam_by_name``: the inputs are ONE
+    BAM in any record order, its mates matched by name (``BamStream(by_name=True)``); ``count_links.bam_info`` is then the
+    stream's ``info`` (``singletons`` among it), else None."""
     rank, world = _rank_world()
-    bam = bam_input(fwd, rve, world)
+    count_links.bam_info = None
+    bam = bam_input(fwd, rve, world, by_name=bam_by_name)
     streamed = bam is None and use_stream(fwd, rve)
     if world > 1 and not (_regular(fwd) and _regular(rve)):  # (the sharded path maps regular files; VS_FASTQ_STREAM aside)
         raise ValueError("the FASTQ inputs %s / %s are not both regular files: a pipe can be read by one process only, so "
@@ -48,9 +51,11 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     if rank == 0 and stages_follow:
         counter.reserve_link_table()  # (the graph stages run on this rank: their table's buffer is taken now)
     if bam is not None:
-        fq = host.BamStream(bam, ctx, block_pairs=BATCH_PAIRS)  # one collated BAM stands for the pair (-f and -r both name it)
+        fq = host.BamStream(bam, ctx, block_pairs=BATCH_PAIRS, by_name=bam_by_name)  # one BAM stands for the pair (-f and -r both name it)
         try:
             count_stream(ctx, fq, counter, progress=True)
+            if bam_by_name:
+                count_links.bam_info = fq.info
         finally:
             fq.close()
     elif world > 1:
@@ -134,12 +139,16 @@ def _starts_bam(path: str) -> bool:
         return False
 
 
-def bam_input(fwd: str, rve: str, world: int = 1):
+def bam_input(fwd: str, rve: str, world: int = 1, by_name: bool = False):
     """The path when ``-f`` and ``-r`` name the same regular file and it is a BAM: the pair is read from it
     (``BamStream``).  None when neither input is a BAM.  ``ValueError`` for what is out of scope: BAM on one side only, two
-    different BAM files, a BAM under a process group of more than one rank."""
+    different BAM files, a BAM under a process group of more than one rank -- and, with ``by_name`` (``--bam-by-name``),
+    inputs that are not a BAM at all."""
     is_bam = (_starts_bam(fwd), _starts_bam(rve))
     if not any(is_bam):
+        if by_name:
+            raise ValueError("--bam-by-name matches the mates of ONE BAM file by their names, and %s / %s are not a BAM; name the "
+                             "same BAM for both reads, or leave the flag out" % (fwd, rve))
         return None
     if not all(is_bam):
         raise ValueError("%s is a BAM file and %s is not: BAM on one side only is not supported; name the same collated BAM "
@@ -258,7 +267,7 @@ def write_info_files(out_dir: str, ids, counter, sparse: bool = False, bgzf: boo
 
 
 def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int = 0, ctx=None, stages_follow: bool = False,
-        sparse_info: bool = False, bgzf_info: bool = False):
+        sparse_info: bool = False, bgzf_info: bool = False, bam_by_name: bool = False):
     # PE_Inference.py:93-96: the output directory is wiped and recreated
     if out_dir[-1] == "/":
         out_dir = out_dir[:-1]
@@ -272,9 +281,11 @@ def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int 
         dist.barrier()  # nobody counts (or could fail half-way) before the directory is in its final state
 
     glb_start = time.time()
+    if bam_by_name:
+        bam_input(fwd, rve, world, by_name=True)  # (what the flag cannot apply to is said before a device is opened)
     if ctx is None:
         ctx = host.Context(device)
-    ids, counter = count_links(ctx, gfa, fwd, rve, kmer_size, stages_follow=stages_follow)
+    ids, counter = count_links(ctx, gfa, fwd, rve, kmer_size, stages_follow=stages_follow, bam_by_name=bam_by_name)
     run.last = (ids, counter)
     if rank != 0:
         return None  # the counters were reduced to rank 0, which writes the files
@@ -301,6 +312,10 @@ def main(argv=None):
     parser.add_argument("--bgzf-info", dest="bgzf_info", action="store_true", default=False,
                         help="extension: write pe_info.gz / st_info.gz, BGZF deflated on the device; `gzip -dc` gives the "
                              "reference's file byte for byte (with --sparse-info: the sparse file)")
+    parser.add_argument("--bam-by-name", dest="bam_by_name", action="store_true", default=False,
+                        help="extension: -f and -r name ONE BAM in any record order (coordinate-sorted, `samtools view -f 12` of "
+                             "a sorted alignment, ...); the mates are matched by read name on the device, records without a mate "
+                             "are dropped -- no `samtools collate` first")
     args = parser.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:  # launched by torchrun: one rank per GPU, counters all-reduced over RCCL
@@ -322,7 +337,8 @@ def main(argv=None):
         # every rank indexes both FASTQ files on the host: share the cores between the local ranks
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
         os.environ.setdefault("VS_HOST_THREADS", str(max(1, (os.cpu_count() or 1) // max(local_world, 1))))
-    run(args.gfa, args.dir, args.fwd, args.rve, args.kmer_size, args.device, sparse_info=args.sparse_info, bgzf_info=args.bgzf_info)
+    run(args.gfa, args.dir, args.fwd, args.rve, args.kmer_size, args.device, sparse_info=args.sparse_info, bgzf_info=args.bgzf_info,
+        bam_by_name=args.bam_by_name)
     if world > 1:
         import torch.distributed as dist
 
