@@ -319,6 +319,46 @@ int vs_bam_mates_host(const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t 
                       uint32_t *waiting, uint64_t cap_waiting, uint64_t info[3]);
 int vs_bam_mates_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t hash_bits, uint32_t *pairs,
                       uint64_t cap_pairs, uint32_t *waiting, uint64_t cap_waiting, uint64_t info[3]);
+/* Member-sharded open of ONE collated BAM for one process per GPU (additions to ABI 10): no rank inflates the whole file and
+ * nothing is inflated on a host.  Rank r of W takes the BGZF members [M r / W, M (r + 1) / W) of vs_bgzf_walk_file, its
+ * "share": the inflated bytes [S_r, S_r + E_r).  A share cannot be entered at a guessed record start, so pass 1 follows the
+ * chain from EVERY candidate start and the ranks exchange what each found (pe.BamStream.open_shard):
+ *   vs_bam_share_summary : members [first, last) of the walk (offsets[n_members + 1], all of them: the whole members behind
+ *                         the share that hold 64 inflated bytes, or the rest of the file, are read too and belong to no
+ *                         count) inflated window by window on the device.  start = ~0: candidates c = 0 .. C - 1 with
+ *                         C = min(seg, E) (positions relative to S_r); else the one candidate `start` (rank 0: vs_bam_header).
+ *                         x[c] = the first position >= E the chain from c reaches, minus E; ~0 when it meets a block_size
+ *                         < 32 first; ~0 - 1 when the end of the file cuts a size field or a record's fixed part.
+ *                         cnt[c] = the participating records (first / second) that start on that chain inside the share.
+ *                         seg = 0: VS_BAM_SEG, else 12288.  info[0] = C, [1] = E, [2] = members inflated, [3] = file bytes
+ *                         read, [4] = windows.  A member the device rejects is VS_E_ARG in the stream's words
+ *   vs_bam_share_summary_host / _text : test aids over inflated bytes share[0, n), n >= share_size + 64 unless the file ends
+ *                         at n; windows of `chunk` new bytes (0: one window).  _host: the same text with one host thread,
+ *                         _text: the kernels.  info[0] = C, [1] = windows
+ *   vs_bam_shard_plan   : host only, a pure function of the gathered values.  head[6 r ..] = failed, whole BGZF, M, header
+ *                         bytes H, E_r, C_r; xn + xn_off[r] = x_r[0 .. C_r) then cnt_r[0 .. C_r).  plan[5 r ..] = bytes in
+ *                         front of rank r's first record (e_r - S_r), where its ownership ends relative to S_r (~0: the end
+ *                         of the file), participating records in front of e_r, S_r, participating records in front of
+ *                         e_{r+1}.  *reason = 0, or why every rank leaves the file to rank 0: 1 a rank failed, 2 the ranks
+ *                         see different files, 3 not whole BGZF, 4 the header reaches beyond rank 0's share, 5 a record
+ *                         longer than a segment across a share boundary or a share without bytes, 6 a block_size < 32 on
+ *                         the chain, 7 the file ends inside a record, 8 the chain does not end at the end of the file, 9 an
+ *                         odd number of participating records
+ *   vs_bam_stream_open_range : the collated stream on range = {file offset of the share's first member, e_r - S_r, where
+ *                         ownership ends relative to S_r (~0: none), 1 when the first participating record is the second
+ *                         of the previous rank's last couple and is passed over, S_r}.  Couple c belongs to the rank whose
+ *                         [e_r, e_{r+1}) holds the start of its first record; the second may start beyond, and the members
+ *                         behind the range are inflated one by one for it and for nothing else.  next, info and close as
+ *                         for the other modes; info counts the records that start in [e_r, e_{r+1}).  A message names a
+ *                         record by its byte offset in the inflated file and says so. */
+int vs_bam_share_summary(vs_ctx *ctx, const char *path, const uint64_t *offsets, uint64_t n_members, uint64_t first, uint64_t last, uint64_t start,
+                         uint32_t seg, uint64_t *x, uint64_t *cnt, uint64_t cap, uint64_t info[5]);
+int vs_bam_share_summary_host(const uint8_t *share, uint64_t n, uint64_t share_size, uint64_t start, uint32_t seg, uint64_t chunk, uint64_t *x,
+                              uint64_t *cnt, uint64_t cap, uint64_t info[2]);
+int vs_bam_share_summary_text(vs_ctx *ctx, const uint8_t *share, uint64_t n, uint64_t share_size, uint64_t start, uint32_t seg, uint64_t chunk,
+                              uint64_t *x, uint64_t *cnt, uint64_t cap, uint64_t info[2]);
+int vs_bam_shard_plan(uint32_t world, const uint64_t *head, const uint64_t *xn, const uint64_t *xn_off, uint64_t *plan, int *reason);
+int vs_bam_stream_open_range(vs_ctx *ctx, const char *path, const uint64_t range[5], vs_bam_stream **out);
 /* The header of a BAM at the front of a file (host: zlib on its leading BGZF members): *header_bytes = inflated bytes in
  * front of the first record.  VS_E_ARG with a message when the file is no BAM. */
 int vs_bam_header(const char *path, uint64_t *header_bytes);

@@ -68,6 +68,14 @@ SYMBOLS = {
     "vs_bam_scan_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                    C.POINTER(C.c_uint64)]),
     "vs_bam_header": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
+    "vs_bam_share_summary": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vs_bam_share_summary_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                            C.POINTER(C.c_uint64)]),
+    "vs_bam_share_summary_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                            C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vs_bam_shard_plan": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "vs_bam_stream_open_range": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]),
     "vs_bam_stream_open_mode": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "vs_bam_stream_mate_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "vs_bam_mates_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,

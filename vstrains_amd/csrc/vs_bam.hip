@@ -41,6 +41,20 @@
 //   k_mate_carry    a wavefront per waiting record copies it to the front of the other window buffer, 16 bytes a lane
 //                   where source and destination are aligned alike; the bytes from `stop` on follow.
 // No lane waits for another lane's progress: a lost compare-and-swap reads the winner and goes on.
+//
+// A member range (vs_bam_stream_open_range; one process per GPU on one collated whole-BGZF file).  A range cannot be entered
+// at a guessed record start, so the open has two passes with one exchange between them (pe.BamStream.open_shard):
+//   vs_bam_share_summary  the rank's members and the few behind them that hold 64 inflated bytes, window by window through
+//                         the reader, k_inflate, k_bam_exits_cnt (exits with the count of participating records) and
+//                         k_bam_lanes (a lane per candidate start, position and count carried across windows): per candidate
+//                         where the chain leaves the share and what it counted (the rule: vs_bam_core.h); the text is not kept;
+//   vs_bam_shard_plan     from every rank's summary each rank's true entry, the participating records in front of it, where
+//                         its ownership ends -- or why rank 0 reads the whole file instead;
+//   the ranged stream     this stream from the range's first member: the bytes in front of the entry dropped as the header is,
+//                         the previous rank's second record passed over when the count in front is odd, k_bam_owned for the
+//                         records that start below the end of the ownership (couples whose first record does are delivered,
+//                         those records are counted), members behind that end inflated one at a time until the last second
+//                         record is whole.  Messages name a record by its byte offset in the inflated file.
 #include "vs_stream_reader.h"
 #include "vs_bam_core.h"
 
@@ -62,6 +76,8 @@ enum {
     B_WORDS = 10,
     B_INVALID = 11,
     B_BAD_MEMBER = 12,  // first BGZF member the device rejected (a running index), ~0u: none
+    B_OWN_REC = 13,     // a ranged stream: records / participating records of the window that this rank owns
+    B_OWN_PART = 14,
     B_TALLY = 16,       // + class: records passed so far (cumulative)
     B_ALL = 24
 };
@@ -194,6 +210,79 @@ __global__ void __launch_bounds__(BAM_TPB) k_bam_tally(const uint4 *__restrict__
     }
 }
 
+
+// ---- the summary of a share (vs_bam_core.h) ---------------------------------------------------------------------------------
+// k_bam_exits with a count: a sibling, so that the kernel of the whole-file stream stays as it is.  The word of byte i is
+// 2^31 (terminal) | participating records << 16 | the offset in the segment the chain goes to next, or the exit code.  The
+// invariant of a word: "the chain from i reaches that point after that many participating records that start in front of
+// it".  A lane's update is ONE 32-bit store computed from two 32-bit loads, its own word (i -> o after a) and the word of
+// o (o -> t after b), and gives i -> t after a + b: any two words that hold the invariant compose to one that holds it, so
+// whatever another lane has made of the word of o by the time it is read -- every store is a whole consistent word -- the
+// result is a point of the same chain with its own count, as in k_bam_exits.  A segment holds at most seg / 36 < 2^15
+// records, so the sum never reaches bit 31.  Tables for [0, lim), lim <= n: segments are clipped to lim.
+__global__ void __launch_bounds__(BAM_TPB) k_bam_exits_cnt(const uint8_t *__restrict__ win, uint64_t n, uint64_t lim, uint32_t seg,
+                                                           uint16_t *__restrict__ tab, uint16_t *__restrict__ cnt) {
+    extern __shared__ uint32_t e[];
+    __shared__ uint32_t changed;
+    constexpr uint32_t T = 0x80000000u, CNT = 0x7FFF0000u;
+    const uint64_t lo = (uint64_t)blockIdx.x * seg;
+    if (lo >= lim || lim > n) return;
+    const uint64_t hi = lo + seg < lim ? lo + seg : lim;
+    const uint32_t len = (uint32_t)(hi - lo);
+    for (uint32_t i = threadIdx.x; i < len; i += BAM_TPB) {
+        uint64_t nx = 0;
+        uint32_t part = 0;
+        const int st = bam_step_cnt(win, n, lo + i, &nx, &part);
+        e[i] = st == BAM_STEP_NEED ? T | (uint32_t)BAM_X_NEED : st == BAM_STEP_DEAD ? T | (uint32_t)BAM_X_DEAD
+               : nx >= hi ? T | (part << 16) | bam_exit_encode(nx, hi) : (part << 16) | (uint32_t)(nx - lo);
+    }
+    __syncthreads();
+    for (;;) {
+        if (threadIdx.x == 0) changed = 0u;
+        __syncthreads();
+        bool mine = false;
+        for (uint32_t i = threadIdx.x; i < len; i += BAM_TPB) {
+            const uint32_t v = e[i];
+            if (v & T) continue;
+            const uint32_t o = v & 0xFFFFu;
+            const uint32_t w = o < len ? e[o] : T | (uint32_t)BAM_X_DEAD;  // (o < len always: it came from nx < hi)
+            e[i] = (w & ~CNT) | (((v & CNT) + (w & CNT)) & CNT);
+            mine = mine || !(w & T);
+        }
+        if (mine) changed = 1u;
+        __syncthreads();
+        const bool again = changed != 0u;
+        __syncthreads();
+        if (!again) break;
+    }
+    for (uint32_t i = threadIdx.x; i < len; i += BAM_TPB) {
+        tab[lo + i] = (uint16_t)(e[i] & 0xFFFFu);
+        cnt[lo + i] = (uint16_t)((e[i] & CNT) >> 16);
+    }
+}
+
+// a lane per candidate through the window's tables (bam_lane_walk: bounded by the window's segments, no lane waits for another)
+__global__ void __launch_bounds__(BAM_TPB) k_bam_lanes(const uint8_t *__restrict__ win, uint64_t n, uint64_t lim, const uint16_t *__restrict__ tab,
+                                                       const uint16_t *__restrict__ cnt, uint32_t seg, uint64_t base, BamLane *__restrict__ lanes,
+                                                       uint32_t n_lanes) {
+    const uint32_t i = blockIdx.x * BAM_TPB + threadIdx.x;
+    if (i >= n_lanes || lim > n) return;
+    BamLane l = lanes[i];
+    bam_lane_walk(win, n, lim, tab, cnt, seg, base, &l);
+    lanes[i] = l;
+}
+
+// ownership of a ranged stream: st[B_OWN_REC] / st[B_OWN_PART] = the records / participating records of the scanned window
+// that start below `lim` (records lie in the order of their offsets; both words are 0 before)
+__global__ void __launch_bounds__(BAM_TPB) k_bam_owned(const uint4 *__restrict__ recs, const uint32_t *__restrict__ part, uint32_t n_rec, uint32_t n_part,
+                                                       uint32_t lim, uint32_t *__restrict__ st) {
+    const uint32_t i = blockIdx.x * BAM_TPB + threadIdx.x;
+    if (i < n_rec && recs[i].x < lim && (i + 1u == n_rec || recs[i + 1u].x >= lim)) st[B_OWN_REC] = i + 1u;
+    if (i < n_part) {
+        const uint32_t r = part[i], nx = i + 1u < n_part ? part[i + 1u] : n_rec;
+        if (r < n_rec && recs[r].x < lim && (nx >= n_rec || recs[nx].x >= lim)) st[B_OWN_PART] = i + 1u;
+    }
+}
 
 // ---- mates by name ----------------------------------------------------------------------------------------------------------
 namespace {
@@ -558,6 +647,16 @@ struct vs_bam_stream {
     uint32_t pair_cur = 0;   // the first pair of the matched window not yet delivered
     uint32_t n_carried = 0;  // the window's first records are the ones carried from earlier windows (first_record: its first NEW one)
     uint64_t singletons = 0, waiting_max = 0, carried_bytes_max = 0, windows = 0;
+    // a member range (vs_bam_stream_open_range): positions are relative to S, the inflated offset of the range's first member
+    bool ranged = false;
+    uint64_t share_start = 0;      // S, for messages
+    uint64_t own_end = ~0ull;      // records that start at or behind it are the next rank's (~0: the end of the file)
+    bool skip_part = false;        // the first participating record is the second of the previous rank's last couple
+    uint64_t win_base = 0;         // position of the window's byte 0
+    uint64_t read_pos = 0;         // position of the next member to inflate
+    uint32_t own_rec = 0, own_part = 0;  // of the scanned window: its records / participating records below own_end
+    Slot *held = nullptr;          // the slot whose members are being inflated, the next one is held_at
+    uint32_t held_at = 0;
 };
 
 namespace {
@@ -571,6 +670,11 @@ int bam_fail(vs_ctx *ctx, vs_bam_stream *s, int code, const std::string &msg) {
 
 // (rec: index in the window; the records carried in front of the new ones have been numbered before)
 std::string rec_msg(const vs_bam_stream *s, uint64_t rec, const char *what) {
+    if (s->ranged) {  // (no file-wide number: the record's offset in the inflated file, fetched from the scanned window)
+        uint32_t off = s->sc.stop;
+        if (rec < s->sc.n_rec) (void)hipMemcpy(&off, (const uint32_t *)(s->sc.recs.as<uint4>() + rec), sizeof off, hipMemcpyDeviceToHost);
+        return s->rd.path + ": the record at byte " + std::to_string(s->share_start + s->win_base + off) + " of the inflated file (a member range: records are named by offset)" + what;
+    }
     return s->rd.path + ": record " + std::to_string(s->first_record + rec - std::min<uint64_t>(rec, s->n_carried)) + what;
 }
 
@@ -584,6 +688,7 @@ int bam_drop_front(vs_ctx *ctx, vs_bam_stream *s, size_t cut) {
     if (rest) VS_HIP(ctx, hipMemcpyAsync(s->win[o].as<uint8_t>(), s->win[s->cur].as<uint8_t>() + cut, rest, hipMemcpyDeviceToDevice, s->st));
     s->cur = o;
     s->size = rest;
+    s->win_base += cut;
     return VS_OK;
 }
 
@@ -630,12 +735,118 @@ int bam_append(vs_ctx *ctx, vs_bam_stream *s) {
     return VS_OK;
 }
 
+// A member range: the members of the reader's slots inflated a few at a time.  Every member that starts below own_end goes
+// into the window at once; behind own_end only the second record of the last owned couple is still wanted, and the members
+// come one by one until it is whole.
+int bam_append_ranged(vs_ctx *ctx, vs_bam_stream *s) {
+    if (!s->held) {
+        Slot &sl = s->rd.take();
+        if (!sl.comp || !sl.n_members) {  // (the end of the file, or bytes that are no BGZF member: pass 1 saw a whole-BGZF file)
+            const bool empty = sl.len == 0;
+            s->eof = sl.last;
+            s->rd.give_back();
+            if (!empty) return vs_fail(ctx, VS_E_STATE, "%s changed after its members were walked (it is not whole BGZF any more)", s->rd.path.c_str());
+            return VS_OK;
+        }
+        if (int rc = reserve_n<uint8_t>(ctx, s->comp, sl.len + 16u)) { s->rd.give_back(); return rc; }
+        if (hipMemcpyAsync(s->comp.as<uint8_t>(), sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st) != hipSuccess) {
+            s->rd.give_back();
+            return vs_fail(ctx, VS_E_HIP, "vs_bam_stream_next: upload of a chunk");
+        }
+        s->held = &sl;
+        s->held_at = 0;
+    }
+    Slot &sl = *s->held;
+    const uint32_t nm = sl.n_members, a = s->held_at;
+    const vs_bgzf_member *dir_end = (const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity());  // (member i at dir_end[-(i + 1)])
+    std::vector<vs_bgzf_member> dir;
+    uint64_t text = 0;
+    for (uint32_t b = a; b < nm; b++) {
+        if (b > a && s->own_end != ~0ull && s->read_pos + text >= s->own_end) break;
+        vs_bgzf_member m = dir_end[-(ptrdiff_t)(b + 1u)];
+        m.out_off = (uint32_t)text;
+        text += m.isize;
+        dir.push_back(m);
+    }
+    const uint32_t k = (uint32_t)dir.size();
+    struct Back {
+        vs_bam_stream *s;
+        bool whole;
+        ~Back() {
+            if (!whole) return;
+            s->eof = s->held->last;
+            s->held = nullptr;
+            s->rd.give_back();
+        }
+    } back = {s, a + k == nm};
+    if (s->size + text > STREAM_MAX_WINDOW)
+        return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete pair", s->rd.path.c_str(), (unsigned long long)(s->size + text));
+    const size_t need = ((s->size + text + 15u) & ~(size_t)15u) + 16u;
+    if (s->win[s->cur].capacity() < need) {
+        const int o = s->cur ^ 1;
+        if (int rc = reserve_n<uint8_t>(ctx, s->win[o], need)) return rc;
+        if (s->size) VS_HIP(ctx, hipMemcpyAsync(s->win[o].as<uint8_t>(), s->win[s->cur].as<uint8_t>(), s->size, hipMemcpyDeviceToDevice, s->st));
+        s->cur = o;
+    }
+    if (int rc = reserve_n<vs_bgzf_member>(ctx, s->dir, (size_t)k)) return rc;
+    if (int rc = reserve_n<uint32_t>(ctx, s->mstat, (size_t)k)) return rc;
+    VS_HIP(ctx, hipMemcpyAsync(s->dir.as<vs_bgzf_member>(), dir.data(), sizeof(vs_bgzf_member) * k, hipMemcpyHostToDevice, s->st));
+    vs_launch_inflate(s->st, s->comp.as<uint8_t>(), sl.len, s->win[s->cur].as<uint8_t>() + s->size, text, s->dir.as<vs_bgzf_member>(), k, s->mstat.as<uint32_t>(),
+                      s->d_stat + B_BAD_MEMBER, (uint32_t)s->members_dev, 0);
+    VS_HIP(ctx, hipGetLastError());
+    VS_HIP(ctx, hipStreamSynchronize(s->st));  // (dir is read by the copy; the slot may go back)
+    s->members_dev += k;
+    s->held_at = a + k;
+    s->size += text;
+    s->read_pos += text;
+    return VS_OK;
+}
+
+int bam_pass(vs_ctx *ctx, vs_bam_stream *s, uint32_t upto);
+
+// a member range, after a scan: which of the window's records this rank owns, and the previous rank's record passed over
+int bam_owned(vs_ctx *ctx, vs_bam_stream *s) {
+    BamScan &sc = s->sc;
+    s->own_rec = sc.n_rec;
+    s->own_part = sc.n_part;
+    const uint64_t lim = s->own_end == ~0ull ? ~0ull : (s->own_end > s->win_base ? s->own_end - s->win_base : 0u);
+    if (lim < s->size && sc.n_rec) {
+        VS_HIP(ctx, hipMemsetAsync(s->d_stat + B_OWN_REC, 0, sizeof(uint32_t) * 2, s->st));
+        hipLaunchKernelGGL(k_bam_owned, dim3((sc.n_rec + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, s->st, sc.recs.as<const uint4>(), sc.part.as<const uint32_t>(),
+                           sc.n_rec, sc.n_part, (uint32_t)lim, s->d_stat);
+        VS_HIP(ctx, hipGetLastError());
+        VS_HIP(ctx, hipMemcpyAsync(s->h_stat + B_OWN_REC, s->d_stat + B_OWN_REC, sizeof(uint32_t) * 2, hipMemcpyDeviceToHost, s->st));
+        VS_HIP(ctx, hipStreamSynchronize(s->st));
+        s->own_rec = std::min(s->h_stat[B_OWN_REC], sc.n_rec);
+        s->own_part = std::min(s->h_stat[B_OWN_PART], sc.n_part);
+    }
+    if (s->skip_part && sc.n_part) {
+        uint32_t first = 0;
+        VS_HIP(ctx, hipMemcpyAsync(&first, sc.part.as<uint32_t>(), sizeof first, hipMemcpyDeviceToHost, s->st));
+        VS_HIP(ctx, hipStreamSynchronize(s->st));
+        if (first >= sc.n_rec) return vs_fail(ctx, VS_E_STATE, "%s: a record index beyond the window's records", s->rd.path.c_str());
+        if (int rc = bam_pass(ctx, s, first + 1u)) return rc;
+        s->part_cur = 1;
+        s->skip_part = false;
+    }
+    return VS_OK;
+}
+
+// couples of the scanned window that can be delivered: all whole ones, or for a member range those whose first record is owned
+uint64_t bam_ready(const vs_bam_stream *s) {
+    const uint64_t whole = (s->sc.n_part - s->part_cur) / 2u;
+    if (!s->ranged) return whole;
+    const uint64_t owned = s->own_part > s->part_cur ? (s->own_part - s->part_cur + 1u) / 2u : 0u;
+    return std::min(whole, owned);
+}
+
 // records [rec_cur, upto) of the scanned window have been passed: counted by class, the sums copied to the host (the copy is
 // complete once the stream has been synchronised)
 int bam_pass(vs_ctx *ctx, vs_bam_stream *s, uint32_t upto) {
-    if (upto > s->rec_cur) {
-        hipLaunchKernelGGL(k_bam_tally, dim3((upto - s->rec_cur + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, s->st, s->sc.recs.as<const uint4>(),
-                           s->rec_cur, upto, s->d_stat + B_TALLY);
+    const uint32_t counted = s->ranged ? std::min(upto, s->own_rec) : upto;  // (a member range counts the records it owns)
+    if (counted > s->rec_cur) {
+        hipLaunchKernelGGL(k_bam_tally, dim3((counted - s->rec_cur + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, s->st, s->sc.recs.as<const uint4>(),
+                           s->rec_cur, counted, s->d_stat + B_TALLY);
         VS_HIP(ctx, hipGetLastError());
         VS_HIP(ctx, hipMemcpyAsync(s->h_stat + B_TALLY, s->d_stat + B_TALLY, sizeof(uint32_t) * (B_ALL - B_TALLY), hipMemcpyDeviceToHost, s->st));
     }
@@ -768,16 +979,37 @@ int vs_bam_header(const char *path, uint64_t *header_bytes) {
 
 int vs_bam_stream_open(vs_ctx *ctx, const char *path, vs_bam_stream **out) { return vs_bam_stream_open_mode(ctx, path, VS_BAM_COLLATED, out); }
 
+static int bam_open(vs_ctx *ctx, const char *path, int mode, const uint64_t *range, vs_bam_stream **out);
+
 int vs_bam_stream_open_mode(vs_ctx *ctx, const char *path, int mode, vs_bam_stream **out) {
     if (!ctx || !path || !out || (mode != VS_BAM_COLLATED && mode != VS_BAM_BY_NAME)) return vs_fail(ctx, VS_E_ARG, "vs_bam_stream_open: bad argument");
+    return bam_open(ctx, path, mode, nullptr, out);
+}
+
+int vs_bam_stream_open_range(vs_ctx *ctx, const char *path, const uint64_t range[5], vs_bam_stream **out) {
+    if (!ctx || !path || !range || !out || range[3] > 1u || range[1] > range[2]) return vs_fail(ctx, VS_E_ARG, "vs_bam_stream_open_range: bad argument");
+    return bam_open(ctx, path, VS_BAM_COLLATED, range, out);
+}
+
+// range: nullptr, or {file offset of the first member, bytes in front of the first record, where ownership ends (both relative
+// to the first member's inflated offset; ~0: the end of the file), 1 to pass over the first participating record, that offset}
+static int bam_open(vs_ctx *ctx, const char *path, int mode, const uint64_t *range, vs_bam_stream **out) {
     *out = nullptr;
     uint64_t header = 0;
-    if (int rc = vs_bam_header(path, &header)) return vs_fail(ctx, rc, "%s", vs_last_error(nullptr));
+    if (!range)
+        if (int rc = vs_bam_header(path, &header)) return vs_fail(ctx, rc, "%s", vs_last_error(nullptr));
     VS_HIP(ctx, hipSetDevice(ctx->device));
     vs_bam_stream *s = new vs_bam_stream();
     s->device = ctx->device;
-    s->skip = header;
+    s->skip = range ? range[1] : header;
     s->by_name = mode == VS_BAM_BY_NAME;
+    if (range) {
+        s->ranged = true;
+        s->rd.begin = range[0];
+        s->own_end = range[2];
+        s->skip_part = range[3] != 0u;
+        s->share_start = range[4];
+    }
     if (const char *ev = getenv("VS_BAM_NAME_BITS")) s->name_bits = (uint32_t)std::min<long long>(std::max<long long>(atoll(ev), 0), 64);  // (tests: long probe chains)
     if (const char *ev = getenv("VS_BAM_SEG")) s->seg = seg_checked((uint32_t)atoll(ev));  // (tests: records across segments)
     Reader &r = s->rd;
@@ -819,7 +1051,15 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
     BamScan &sc = s->sc;
     for (;;) {
         if (s->scanned) {
-            if (s->by_name ? s->pair_cur < s->mt.n_pairs : (sc.n_part - s->part_cur) / 2u > 0u) break;
+            if (s->by_name ? s->pair_cur < s->mt.n_pairs : bam_ready(s) > 0u) break;
+            if (s->ranged && s->own_end != ~0ull && s->own_part <= s->part_cur &&
+                (s->own_end > s->win_base ? s->own_end - s->win_base : 0u) <= (uint64_t)sc.stop) {
+                // a member range: the next record starts at or behind own_end, so every owned couple is out
+                if (int rc = bam_pass(ctx, s, sc.n_rec)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+                VS_HIP(ctx, hipStreamSynchronize(st));
+                s->done = true;
+                return VS_OK;
+            }
             if (s->eof) return bam_finish(ctx, s);
             if (s->by_name) {
                 if (int rc = bam_carry_waiting(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
@@ -838,7 +1078,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
             s->scanned = false;
         }
         if (!s->eof) {
-            if (int rc = bam_append(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = s->ranged ? bam_append_ranged(ctx, s) : bam_append(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
             if (s->skip) {  // the header goes, whole windows of it if need be
                 const size_t now = (size_t)std::min<uint64_t>(s->skip, s->size);
                 if (int rc = bam_drop_front(ctx, s, now)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
@@ -859,6 +1099,8 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
             return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, sc.malformed, " is malformed: its name, cigar, sequence and quality need more than its block_size"));
         if (sc.end == BAM_END_DEAD)
             return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, sc.n_rec, " is malformed: its block_size is below the 32 bytes of the fixed part"));
+        if (s->ranged)
+            if (int rc = bam_owned(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
         if (s->by_name) {
             s->windows++;
             s->pair_cur = 0;
@@ -871,7 +1113,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
         }
     }
     // ---- the block of n couples from the cursor
-    const uint64_t n = std::min<uint64_t>(s->by_name ? s->mt.n_pairs - s->pair_cur : (sc.n_part - s->part_cur) / 2u, max_pairs), n_ends = 2u * n;
+    const uint64_t n = std::min<uint64_t>(s->by_name ? s->mt.n_pairs - s->pair_cur : bam_ready(s), max_pairs), n_ends = 2u * n;
     if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
     if (int rc = reserve_n<uint32_t>(ctx, s->d_ends, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
     vs_reads *r = new vs_reads();
@@ -1098,6 +1340,236 @@ int vs_bam_mates_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t sk
     if (np) VS_HIP(ctx, hipMemcpy(pairs, mt.pairs.ptr(), sizeof(uint32_t) * 2u * np, hipMemcpyDeviceToHost));
     if (nw) VS_HIP(ctx, hipMemcpy(waiting, mt.wlist.ptr(), sizeof(uint32_t) * nw, hipMemcpyDeviceToHost));
     mates_info(info, mt.n_pairs, mt.n_wait, mt.crowded == BAM_NONE ? ~0ull : mt.crowded);
+    return VS_OK;
+}
+
+// ---- the member-sharded open, pass 1: the summary of a share ----------------------------------------------------------------
+namespace {
+
+// the tables and the lanes of one summary window
+struct BamSum {
+    VsDevBuf tab, cnt, lanes;
+    uint32_t n_lanes = 0, seg = BAM_SEG_DEFAULT;
+    uint64_t share = 0, base = 0, windows = 0;  // the share's inflated size; the position of the next window's byte 0
+};
+
+uint32_t seg_of(uint32_t seg) {
+    if (seg == 0)
+        if (const char *ev = getenv("VS_BAM_SEG")) seg = (uint32_t)atoll(ev);
+    return seg_checked(seg);
+}
+
+// lanes: `start` alone (rank 0: the end of the header), or every candidate [0, min(seg, share)) for start = ~0
+int sum_begin(vs_ctx *ctx, hipStream_t st, BamSum &sm, uint64_t share, uint64_t start, uint32_t seg, uint64_t cap) {
+    sm.seg = seg;
+    sm.share = share;
+    sm.base = sm.windows = 0;
+    sm.n_lanes = start == ~0ull ? (uint32_t)std::min<uint64_t>(seg, share) : 1u;
+    if (sm.n_lanes > cap) return vs_fail(ctx, VS_E_ARG, "the summary of a share: room for %llu entries, %u needed", (unsigned long long)cap, sm.n_lanes);
+    std::vector<BamLane> lanes(sm.n_lanes);
+    for (uint32_t i = 0; i < sm.n_lanes; i++) lanes[i] = BamLane{start == ~0ull ? (uint64_t)i : start, 0, BAM_LANE_LIVE, 0};
+    if (int rc = reserve_n<BamLane>(ctx, sm.lanes, (size_t)sm.n_lanes + 1u)) return rc;
+    if (sm.n_lanes) VS_HIP(ctx, hipMemcpyAsync(sm.lanes.ptr(), lanes.data(), sizeof(BamLane) * sm.n_lanes, hipMemcpyHostToDevice, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
+    return VS_OK;
+}
+
+// the window win[0, n) at position sm.base; *lim: the bytes of it that are done (the rest is the front of the next window)
+int sum_window(vs_ctx *ctx, hipStream_t st, BamSum &sm, const uint8_t *win, uint64_t n, int last, uint64_t *lim) {
+    *lim = bam_sum_limit(n, sm.base, sm.share, last);
+    const uint64_t n_seg = (*lim + sm.seg - 1u) / sm.seg;
+    if (n > STREAM_MAX_WINDOW || n_seg > 0x7FFFFFFFu) return vs_fail(ctx, VS_E_RANGE, "a BAM window of %llu bytes", (unsigned long long)n);
+    if (n_seg && sm.n_lanes) {
+        if (int rc = reserve_n<uint16_t>(ctx, sm.tab, *lim)) return rc;
+        if (int rc = reserve_n<uint16_t>(ctx, sm.cnt, *lim)) return rc;
+        hipLaunchKernelGGL(k_bam_exits_cnt, dim3((unsigned)n_seg), dim3(BAM_TPB), sizeof(uint32_t) * sm.seg, st, win, n, *lim, sm.seg, sm.tab.as<uint16_t>(),
+                           sm.cnt.as<uint16_t>());
+        VS_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_bam_lanes, dim3((sm.n_lanes + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, st, win, n, *lim, sm.tab.as<const uint16_t>(),
+                           sm.cnt.as<const uint16_t>(), sm.seg, sm.base, sm.lanes.as<BamLane>(), sm.n_lanes);
+        VS_HIP(ctx, hipGetLastError());
+    }
+    sm.base += *lim;
+    sm.windows++;
+    return VS_OK;
+}
+
+int sum_end(vs_ctx *ctx, hipStream_t st, BamSum &sm, uint64_t *x, uint64_t *cnt) {
+    std::vector<BamLane> lanes(sm.n_lanes);
+    if (sm.n_lanes) VS_HIP(ctx, hipMemcpyAsync(lanes.data(), sm.lanes.ptr(), sizeof(BamLane) * sm.n_lanes, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < sm.n_lanes; i++) {
+        x[i] = bam_lane_exit(lanes[i], sm.share);
+        cnt[i] = lanes[i].count;
+    }
+    return VS_OK;
+}
+
+// ISIZE of the member that ends at file offset `end`
+int member_isize(int fd, const char *path, uint64_t end, uint32_t *isize) {
+    uint8_t t[4];
+    ssize_t got;
+    do got = end >= 4u ? pread(fd, t, 4, (off_t)(end - 4u)) : 0;
+    while (got < 0 && errno == EINTR);
+    if (got != 4) return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, got < 0 ? strerror(errno) : "it shrank while it was read");
+    *isize = bam_le32(t);
+    return VS_OK;
+}
+
+}  // namespace
+
+int vs_bam_share_summary_host(const uint8_t *share, uint64_t n, uint64_t share_size, uint64_t start, uint32_t seg, uint64_t chunk, uint64_t *x,
+                              uint64_t *cnt, uint64_t cap, uint64_t info[2]) {
+    if ((!share && n) || !info || share_size > n || n > STREAM_MAX_WINDOW || (cap && (!x || !cnt)))
+        return vs_fail(nullptr, VS_E_ARG, "vs_bam_share_summary_host: bad argument");
+    seg = seg_checked(seg);
+    const uint32_t n_lanes = start == ~0ull ? (uint32_t)std::min<uint64_t>(seg, share_size) : 1u;
+    if (n_lanes > cap) return vs_fail(nullptr, VS_E_ARG, "vs_bam_share_summary_host: room for %llu entries, %u needed", (unsigned long long)cap, n_lanes);
+    const uint64_t windows = bam_share_summary_serial(share, n, share_size, start, seg, chunk, n_lanes, x, cnt);
+    info[0] = n_lanes;
+    info[1] = windows;
+    return VS_OK;
+}
+
+int vs_bam_share_summary_text(vs_ctx *ctx, const uint8_t *share, uint64_t n, uint64_t share_size, uint64_t start, uint32_t seg, uint64_t chunk,
+                              uint64_t *x, uint64_t *cnt, uint64_t cap, uint64_t info[2]) {
+    if (!ctx || (!share && n) || !info || share_size > n || n > STREAM_MAX_WINDOW || (cap && (!x || !cnt)))
+        return vs_fail(ctx, VS_E_ARG, "vs_bam_share_summary_text: bad argument");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    VsDevBuf dev;
+    BamSum sm;
+    VS_HIP(ctx, dev.reserve(((n + 15u) & ~(uint64_t)15u) + 16u));
+    if (n) VS_HIP(ctx, hipMemcpyAsync(dev.ptr(), share, n, hipMemcpyHostToDevice, st));
+    if (int rc = sum_begin(ctx, st, sm, share_size, start, seg_checked(seg), cap)) return rc;
+    if (!chunk) chunk = n ? n : 1u;
+    for (uint64_t have = std::min(n, chunk);; have = std::min(n, have + chunk)) {
+        uint64_t lim = 0;
+        const uint64_t base = sm.base;
+        if (int rc = sum_window(ctx, st, sm, dev.as<const uint8_t>() + base, have - base, have == n, &lim)) return rc;
+        if (have == n) break;
+    }
+    if (int rc = sum_end(ctx, st, sm, x, cnt)) return rc;
+    info[0] = sm.n_lanes;
+    info[1] = sm.windows;
+    return VS_OK;
+}
+
+int vs_bam_share_summary(vs_ctx *ctx, const char *path, const uint64_t *offsets, uint64_t n_members, uint64_t first, uint64_t last, uint64_t start,
+                         uint32_t seg, uint64_t *x, uint64_t *cnt, uint64_t cap, uint64_t info[5]) {
+    if (!ctx || !path || !offsets || !info || first > last || last > n_members || (cap && (!x || !cnt)))
+        return vs_fail(ctx, VS_E_ARG, "vs_bam_share_summary: bad argument");
+    for (uint64_t i = first; i < n_members; i++)
+        if (offsets[i + 1] <= offsets[i] || offsets[i + 1] - offsets[i] > 65536u)
+            return vs_fail(ctx, VS_E_ARG, "vs_bam_share_summary: member %llu is no BGZF member's size", (unsigned long long)i);
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    seg = seg_of(seg);
+    struct Run {
+        Reader rd;
+        hipStream_t st = nullptr;
+        ~Run() {
+            if (st) (void)hipStreamSynchronize(st);  // (before the reader's pinned chunks go)
+            rd.shut();
+            if (st) (void)hipStreamDestroy(st);
+        }
+    } run;
+    Reader &r = run.rd;
+    r.path = path;
+    r.device = ctx->device;
+    if (const char *ev = getenv("VS_STREAM_CHUNK")) r.chunk = std::max<size_t>(1u, (size_t)atoll(ev));
+    r.fd = open(path, O_RDONLY);
+    if (r.fd < 0) return vs_fail(ctx, VS_E_ARG, "cannot open %s: %s", path, strerror(errno));
+    // the share's inflated size, and the whole members behind it that hold BAM_SUM_TAIL bytes (or the rest of the file)
+    uint64_t share = 0, tail = 0, until = last;
+    for (uint64_t i = first; i < last; i++) {
+        uint32_t isize = 0;
+        if (int rc = member_isize(r.fd, path, offsets[i + 1], &isize)) return vs_fail(ctx, rc, "%s", vs_last_error(nullptr));
+        share += isize;
+    }
+    while (tail < (uint64_t)BAM_SUM_TAIL && until < n_members) {
+        uint32_t isize = 0;
+        if (int rc = member_isize(r.fd, path, offsets[until + 1], &isize)) return vs_fail(ctx, rc, "%s", vs_last_error(nullptr));
+        tail += isize;
+        until++;
+    }
+    r.begin = offsets[first];
+    r.end = offsets[until];
+    VS_HIP(ctx, hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking));
+    hipStream_t st = run.st;
+    BamSum sm;
+    if (int rc = sum_begin(ctx, st, sm, share, start, seg, cap)) return rc;
+    VsDevBuf win[2], comp, dir, mstat, bad;
+    VS_HIP(ctx, bad.reserve(sizeof(uint32_t)));
+    VS_HIP(ctx, hipMemsetAsync(bad.ptr(), 0xFF, sizeof(uint32_t), st));
+    int cur = 0;
+    size_t size = 0;
+    uint64_t members = 0, inflated = 0;
+    r.th = std::thread([rp = &r] { rp->run(); });
+    for (bool eof = false; !eof;) {
+        Slot &sl = r.take();
+        struct Back {
+            Reader &r;
+            ~Back() { r.give_back(); }
+        } back = {r};
+        eof = sl.last;
+        if (!sl.comp && sl.len) return vs_fail(ctx, VS_E_STATE, "%s changed after its members were walked (it is not whole BGZF any more)", path);
+        const uint32_t nm = sl.comp ? sl.n_members : 0u;
+        const size_t text = nm ? sl.text : 0u;
+        if (size + text > STREAM_MAX_WINDOW) return vs_fail(ctx, VS_E_RANGE, "a BAM window of %llu bytes", (unsigned long long)(size + text));
+        const size_t need = ((size + text + 15u) & ~(size_t)15u) + 16u;
+        if (win[cur].capacity() < need) {
+            const int o = cur ^ 1;
+            if (int rc = reserve_n<uint8_t>(ctx, win[o], need)) return rc;
+            if (size) VS_HIP(ctx, hipMemcpyAsync(win[o].as<uint8_t>(), win[cur].as<uint8_t>(), size, hipMemcpyDeviceToDevice, st));
+            cur = o;
+        }
+        if (nm) {
+            if (int rc = reserve_n<uint8_t>(ctx, comp, sl.len + 16u)) return rc;
+            if (int rc = reserve_n<vs_bgzf_member>(ctx, dir, (size_t)nm)) return rc;
+            if (int rc = reserve_n<uint32_t>(ctx, mstat, (size_t)nm)) return rc;
+            const vs_bgzf_member *d = (const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()) - nm;  // (member i at d[nm - 1 - i])
+            if (sl.len) VS_HIP(ctx, hipMemcpyAsync(comp.as<uint8_t>(), sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, st));
+            VS_HIP(ctx, hipMemcpyAsync(dir.as<vs_bgzf_member>(), d, sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, st));
+            vs_launch_inflate(st, comp.as<uint8_t>(), sl.len, win[cur].as<uint8_t>() + size, text, dir.as<vs_bgzf_member>(), nm, mstat.as<uint32_t>(),
+                              bad.as<uint32_t>(), (uint32_t)(first + members), 1);
+            VS_HIP(ctx, hipGetLastError());
+            members += nm;
+            inflated += text;
+        }
+        size += text;
+        uint64_t lim = 0;
+        if (int rc = sum_window(ctx, st, sm, win[cur].as<const uint8_t>(), size, eof ? 1 : 0, &lim)) return rc;
+        uint32_t first_bad = BAM_NONE;
+        VS_HIP(ctx, hipMemcpyAsync(&first_bad, bad.ptr(), sizeof first_bad, hipMemcpyDeviceToHost, st));
+        VS_HIP(ctx, hipStreamSynchronize(st));
+        if (first_bad != BAM_NONE)
+            return vs_fail(ctx, VS_E_ARG, "%s: not a complete gzip stream (BGZF member %u does not inflate to its CRC32 and size)", path, first_bad);
+        // what is not done is the front of the next window
+        const size_t rest = size - (size_t)lim;
+        if (!eof && lim) {
+            const int o = cur ^ 1;
+            if (int rc = reserve_n<uint8_t>(ctx, win[o], ((rest + 15u) & ~(size_t)15u) + 16u)) return rc;
+            if (rest) VS_HIP(ctx, hipMemcpyAsync(win[o].as<uint8_t>(), win[cur].as<uint8_t>() + lim, rest, hipMemcpyDeviceToDevice, st));
+            VS_HIP(ctx, hipStreamSynchronize(st));
+            cur = o;
+        }
+        size = rest;
+    }
+    if (r.err != VS_OK) return vs_fail(ctx, r.err, "%s", r.err_msg.c_str());
+    if (inflated != share + tail) return vs_fail(ctx, VS_E_STATE, "%s changed after its members were walked (%llu inflated bytes where its trailers say %llu)", path,
+                                                 (unsigned long long)inflated, (unsigned long long)(share + tail));
+    if (int rc = sum_end(ctx, st, sm, x, cnt)) return rc;
+    info[0] = sm.n_lanes;
+    info[1] = share;
+    info[2] = members;
+    info[3] = r.raw_bytes;
+    info[4] = sm.windows;
+    return VS_OK;
+}
+
+int vs_bam_shard_plan(uint32_t world, const uint64_t *head, const uint64_t *xn, const uint64_t *xn_off, uint64_t *plan, int *reason) {
+    if (!world || !head || !xn || !xn_off || !plan || !reason) return vs_fail(nullptr, VS_E_ARG, "vs_bam_shard_plan: bad argument");
+    *reason = bam_shard_plan(world, head, xn, xn_off, plan);
     return VS_OK;
 }
 

@@ -16,6 +16,8 @@
 #pragma once
 #include <stdint.h>
 
+#include <vector>
+
 #if defined(__HIPCC__)
 #define BAM_HD __host__ __device__ inline __attribute__((always_inline))
 #else
@@ -338,4 +340,199 @@ inline void bam_mates_serial(const BamMates &m, uint32_t bits, uint32_t *pairs, 
     info[1] = n_wait;
     info[2] = crowded;
     info[3] = full;
+}
+
+// ---- the summary of a share (member-sharded BAM) ---------------------------------------------------------------------------
+// A rank of a sharded run holds the inflated bytes [S, S + E) of its members ("the share") and at least BAM_SUM_TAIL bytes
+// behind them, or everything up to the end of the file.  It does not know where the true chain enters the share, so it
+// follows the chain from every candidate start c (positions are relative to S) and keeps, per candidate,
+//   X[c]  the first position >= E the chain from c reaches, minus E; BAM_SUM_DEAD when it meets a block_size < 32 first;
+//         BAM_SUM_CUT when the end of the file cuts a size field or the fixed part of a record that starts in the share
+//         (a record whose variable part runs beyond the end of the file shows as an X beyond it: bam_shard_plan sees that);
+//   N[c]  the participating records (classes first and second) that start on that chain inside the share; its parity is
+//         the Q of the plan, the count itself places the rank's couples among the file's.
+// Nothing guesses which candidate is a record start: every candidate is followed, and the one the previous share's chain
+// hands over is picked after the exchange (bam_shard_plan).
+//
+//   tables   per segment [lo, hi) of a window, hi clipped to the window's limit `lim`: exit(p) as above and cnt(p) = the
+//            participating records on the chain from p that start in [p, hi) (bam_seg_exits_cnt_serial / k_bam_exits_cnt);
+//            every p < lim has its size field and its fixed part inside the window's n bytes, unless the file ends there
+//   lanes    bam_lane_walk: a lane per live candidate, one lookup per segment it touches; position and count are carried
+//            from window to window.  Chains go strictly forward: a lane's loop is bounded by the segments of the window.
+#define BAM_SUM_TAIL 64u
+#define BAM_SUM_DEAD 0xFFFFFFFFFFFFFFFFull
+#define BAM_SUM_CUT 0xFFFFFFFFFFFFFFFEull
+enum { BAM_LANE_LIVE = 0, BAM_LANE_DEAD = 1, BAM_LANE_CUT = 2 };
+
+// the record at p (its size field read, block_size >= 32) counts when its fixed part lies in win[0, n) and it takes part
+BAM_HD uint32_t bam_takes_part(const uint8_t *win, uint64_t n, uint64_t p) {
+    return p + 4u + BAM_FIXED <= n && (bam_classify(win, p).flag_cls >> 16) <= (uint32_t)BAM_C_SECOND ? 1u : 0u;
+}
+
+// one step of a summary chain from p < n: BAM_STEP_NEED also when the window's end cuts the fixed part (with the limits of
+// the summary windows that is the end of the file); *part = 1 when the record takes part
+BAM_HD int bam_step_cnt(const uint8_t *win, uint64_t n, uint64_t p, uint64_t *next, uint32_t *part) {
+    const int st = bam_step(win, n, p, next);
+    if (st != BAM_STEP_OK) return st;
+    if (p + 4u + BAM_FIXED > n) return BAM_STEP_NEED;
+    *part = bam_takes_part(win, n, p);
+    return BAM_STEP_OK;
+}
+
+// the tables of segment [lo, hi), hi <= lim <= n, with one thread (from the last byte to the first)
+inline void bam_seg_exits_cnt_serial(const uint8_t *win, uint64_t n, uint64_t lo, uint64_t hi, uint16_t *tab, uint16_t *cnt) {
+    for (uint64_t p = hi; p-- > lo;) {
+        uint64_t nx = 0;
+        uint32_t part = 0;
+        const int st = bam_step_cnt(win, n, p, &nx, &part);
+        if (st != BAM_STEP_OK) {
+            tab[p] = (uint16_t)(st == BAM_STEP_NEED ? BAM_X_NEED : BAM_X_DEAD);
+            cnt[p] = 0;
+        } else if (nx >= hi) {
+            tab[p] = (uint16_t)bam_exit_encode(nx, hi);
+            cnt[p] = (uint16_t)part;
+        } else {
+            tab[p] = tab[nx];
+            cnt[p] = (uint16_t)(cnt[nx] + part);
+        }
+    }
+}
+
+struct BamLane {
+    uint64_t pos;    // relative to S: where the chain stands (live), or where it met what ended it
+    uint64_t count;  // participating records passed so far
+    uint32_t state;  // BAM_LANE_*
+    uint32_t pad;
+};
+
+// A live lane through the window win[0, n) that starts at position `base` (relative to S), tables for [0, lim): it moves
+// while base <= pos < base + lim.  At most one table lookup or one walk of a segment's records per segment of the window.
+BAM_HD void bam_lane_walk(const uint8_t *win, uint64_t n, uint64_t lim, const uint16_t *tab, const uint16_t *cnt, uint32_t seg, uint64_t base,
+                          BamLane *lane) {
+    if (lane->state != (uint32_t)BAM_LANE_LIVE || lane->pos < base) return;
+    uint64_t p = lane->pos - base, count = lane->count;
+    uint32_t state = BAM_LANE_LIVE;
+    while (p < lim) {
+        const uint64_t lo = p / seg * seg, hi = lo + seg < lim ? lo + seg : lim;
+        const uint32_t code = tab[p];
+        if (code < (uint32_t)BAM_X_FAR) {
+            count += cnt[p];
+            p = hi + code;
+            continue;
+        }
+        for (;;) {  // from the bytes: the records of this segment (a far exit, a dead or a cut chain)
+            uint64_t nx = 0;
+            uint32_t part = 0;
+            const int st = bam_step_cnt(win, n, p, &nx, &part);
+            if (st != BAM_STEP_OK) {
+                state = st == BAM_STEP_NEED ? BAM_LANE_CUT : BAM_LANE_DEAD;
+                break;
+            }
+            count += part;
+            p = nx;
+            if (p >= hi) break;
+        }
+        if (state != (uint32_t)BAM_LANE_LIVE) break;
+    }
+    lane->pos = base + p;
+    lane->count = count;
+    lane->state = state;
+}
+
+// what a lane says once the share's last window is done: X (BAM_SUM_*), N
+BAM_HD uint64_t bam_lane_exit(const BamLane &lane, uint64_t share) {
+    if (lane.state == (uint32_t)BAM_LANE_DEAD) return BAM_SUM_DEAD;
+    if (lane.state == (uint32_t)BAM_LANE_CUT || lane.pos < share) return BAM_SUM_CUT;  // (pos < share: the bytes ended before the share did)
+    return lane.pos - share;
+}
+
+// the limit of a summary window of n bytes at `base`: positions below it are walked in this window.  More bytes follow
+// (`last` = 0): the final BAM_FIXED + 3 bytes wait for them, so that every walked record has its fixed part in the window.
+BAM_HD uint64_t bam_sum_limit(uint64_t n, uint64_t base, uint64_t share, int last) {
+    const uint64_t keep = (uint64_t)BAM_FIXED + 3u, here = last ? n : (n > keep ? n - keep : 0u);
+    const uint64_t left = share > base ? share - base : 0u;
+    return here < left ? here : left;
+}
+
+// The summary with one thread: share[0, n) are the inflated bytes from S on (share_size of them the share, then
+// BAM_SUM_TAIL or more, or everything up to the end of the file), taken in windows of `chunk` new bytes (0: one window).
+// n_lanes = 1 and the candidate `start`, or the candidates 0 .. n_lanes - 1 when start = ~0.  Returns the windows.
+inline uint64_t bam_share_summary_serial(const uint8_t *share, uint64_t n, uint64_t share_size, uint64_t start, uint32_t seg, uint64_t chunk,
+                                         uint32_t n_lanes, uint64_t *x, uint64_t *cnt) {
+    std::vector<BamLane> lanes(n_lanes);
+    for (uint32_t i = 0; i < n_lanes; i++) lanes[i] = BamLane{start == ~0ull ? (uint64_t)i : start, 0, BAM_LANE_LIVE, 0};
+    if (!chunk) chunk = n ? n : 1u;
+    uint64_t base = 0, windows = 0;
+    for (uint64_t have = n < chunk ? n : chunk;; have = n - have < chunk ? n : have + chunk) {  // the window: share[base, have)
+        const uint64_t wn = have - base, lim = bam_sum_limit(wn, base, share_size, have == n);
+        std::vector<uint16_t> tab(lim), tcnt(lim);  // (exactly sized: an index beyond the limit is an error a sanitizer sees)
+        for (uint64_t lo = 0; lo < lim; lo += seg) bam_seg_exits_cnt_serial(share + base, wn, lo, lo + seg < lim ? lo + seg : lim, tab.data(), tcnt.data());
+        for (BamLane &l : lanes) bam_lane_walk(share + base, wn, lim, tab.data(), tcnt.data(), seg, base, &l);
+        base += lim;
+        windows++;
+        if (have == n) break;
+    }
+    for (uint32_t i = 0; i < n_lanes; i++) {
+        x[i] = bam_lane_exit(lanes[i], share_size);
+        cnt[i] = lanes[i].count;
+    }
+    return windows;
+}
+
+// ---- the plan of a sharded open: a pure function of what the ranks gathered ----------------------------------------------------
+// head[6 r ..] = failed, whole BGZF, members M, header bytes H, the share's inflated size, candidates C_r; xn + xn_off[r]:
+// X_r[0 .. C_r) then N_r[0 .. C_r).  Rank 0's one candidate is H.  plan[5 r ..] = bytes in front of the rank's first record
+// (e_r - S_r), where its ownership ends relative to S_r (~0: at the end of the file), participating records in front of e_r,
+// S_r, participating records in front of e_{r+1}.  Returns BAM_PLAN_*: 0, or why every rank leaves the file to rank 0.
+enum {
+    BAM_PLAN_OK = 0,
+    BAM_PLAN_FAILED = 1,      // a rank failed in pass 1
+    BAM_PLAN_DIFFER = 2,      // the ranks do not see the same file
+    BAM_PLAN_NOT_BGZF = 3,
+    BAM_PLAN_HEADER = 4,      // H >= S_1
+    BAM_PLAN_ACROSS = 5,      // some x >= C_r
+    BAM_PLAN_DEAD = 6,
+    BAM_PLAN_CUT = 7,
+    BAM_PLAN_NOT_AT_END = 8,
+    BAM_PLAN_ODD = 9
+};
+
+inline int bam_shard_plan(uint32_t world, const uint64_t *head, const uint64_t *xn, const uint64_t *xn_off, uint64_t *plan) {
+    if (!world) return BAM_PLAN_FAILED;
+    for (uint32_t r = 0; r < world; r++)
+        if (head[6u * r]) return BAM_PLAN_FAILED;
+    for (uint32_t r = 1; r < world; r++)
+        if (head[6u * r + 1u] != head[1] || head[6u * r + 2u] != head[2] || head[6u * r + 3u] != head[3]) return BAM_PLAN_DIFFER;
+    if (!head[1]) return BAM_PLAN_NOT_BGZF;
+    uint64_t total = 0;
+    for (uint32_t r = 0; r < world; r++) total += head[6u * r + 4u];
+    if (world > 1u && head[3] >= head[4]) return BAM_PLAN_HEADER;
+    if (head[5] != 1u) return BAM_PLAN_FAILED;
+    uint64_t S = 0, x = xn[xn_off[0]], count = xn[xn_off[0] + 1u];
+    plan[0] = head[3];
+    plan[2] = 0;
+    plan[3] = 0;
+    for (uint32_t r = 0;; r++) {
+        // x: the exit of share r on the true chain, relative to S_{r+1}
+        S += head[6u * r + 4u];
+        if (x == BAM_SUM_DEAD) return BAM_PLAN_DEAD;
+        if (x == BAM_SUM_CUT || (r + 1u < world && x > total - S)) return BAM_PLAN_CUT;  // (beyond the file from an inner share)
+        plan[5u * r + 4u] = count;
+        if (r + 1u == world) {
+            plan[5u * r + 1u] = ~0ull;
+            break;
+        }
+        const uint64_t C = head[6u * (r + 1u) + 5u];
+        if (x >= C) return BAM_PLAN_ACROSS;
+        plan[5u * r + 1u] = S + x - plan[5u * r + 3u];
+        plan[5u * (r + 1u)] = x;
+        plan[5u * (r + 1u) + 2u] = count;
+        plan[5u * (r + 1u) + 3u] = S;
+        const uint64_t *mine = xn + xn_off[r + 1u];
+        count += mine[C + x];
+        x = mine[x];
+    }
+    if (x != 0u) return BAM_PLAN_NOT_AT_END;
+    if (count & 1u) return BAM_PLAN_ODD;
+    return BAM_PLAN_OK;
 }

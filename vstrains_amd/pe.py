@@ -450,6 +450,110 @@ class BamStream:
             raise nat.NativeError(rc, msg)
         self._h = h
 
+    # ---- the member-sharded open of a collated BAM (one process per GPU) ---------------------------------------------------
+    @classmethod
+    def open_shard(cls, path: str, ctx: "Context", rank: int, world: int, all_gather=None, block_pairs: int = 1 << 20):
+        """This rank's couples of ONE collated whole-BGZF BAM, shared with the other ranks by MEMBER and inflated on the
+        devices only.  A member range cannot be entered at a guessed record start, so pass 1 (``shard_summary``) follows
+        the record chain from EVERY candidate start of this rank's share on the device and keeps, per candidate, where the
+        chain leaves the share and how many participating records it passed; one exchange (``all_gather`` as
+        ``FastqStream.open_shard`` takes it, default ``torch.distributed.all_gather_object``; at most 2 * 12 288 entries a
+        rank); ``bam_shard_plan`` chains the summaries into every rank's true entry, and pass 2 (``shard_open``) opens the
+        stream on that range and exchanges one more integer, the status of that open.  A rank inflates its share twice.
+
+        Returns ``(stream, None)``, or ``(None, reason)`` -- one of ``BAM_SHARD_REASONS``, the same on every rank, a
+        function of the gathered values alone -- when rank 0 must read the whole file as the single process does.  The
+        stream has ``first_pair`` / ``pairs`` (where its couples lie among the file's), ``members``, ``members_pass1`` and
+        ``plan`` (bytes in front of its first record, where its ownership ends, participating records in front of its
+        entry, the inflated offset of its share, participating records in front of the next rank's entry)."""
+        if all_gather is None:
+            import torch.distributed as dist
+
+            def all_gather(vals):
+                got = [None] * world
+                dist.all_gather_object(got, [int(v) for v in vals])
+                return got
+
+        mine = cls.shard_summary(path, ctx, rank, world)
+        everyone = all_gather(mine.message)
+        return cls.shard_open(mine, everyone, all_gather, block_pairs)
+
+    class ShardSummary:
+        """What pass 1 leaves on a rank: ``message`` for the exchange, its own failure (raised after the exchange), the
+        members' file offsets, how many members it inflated."""
+
+        def __init__(self, path, ctx, rank, world):
+            self.path, self.ctx, self.rank, self.world = path, ctx, rank, world
+            self.failure, self.offsets, self.members_pass1 = None, None, 0
+            self.message = [1, 0, 0, 0, 0, 0]
+
+    @classmethod
+    def shard_summary(cls, path: str, ctx: "Context", rank: int, world: int) -> "BamStream.ShardSummary":
+        """Pass 1 on this rank.  ``message`` = [failed, whole BGZF, members M, header bytes H, my share's inflated size,
+        candidates C, X[0 .. C), N[0 .. C)] (``vs_bam_share_summary``); no share is summarised when the file is not whole
+        BGZF (every rank sees that in its own walk)."""
+        sm = cls.ShardSummary(path, ctx, rank, world)
+        try:
+            sm.offsets, state, _ = bgzf_walk_file(path)
+            m = len(sm.offsets) - 1
+            header = bam_header_bytes(path)
+            if state != 0:
+                sm.message = [0, 0, m, header, 0, 0]
+                return sm
+            lo, hi = (m * rank) // world, (m * (rank + 1)) // world
+            cap = 1 if rank == 0 else BAM_SEG_MAX
+            x = np.zeros(cap, dtype=np.uint64)
+            n = np.zeros(cap, dtype=np.uint64)
+            info = (C.c_uint64 * 5)()
+            off = np.ascontiguousarray(sm.offsets, dtype=np.uint64)
+            rc = nat.lib().vs_bam_share_summary(ctx._h, path.encode(), off.ctypes.data, m, lo, hi, header if rank == 0 else (1 << 64) - 1, 0,
+                                                x.ctypes.data, n.ctypes.data, cap, info)
+            if rc != nat.VS_OK:
+                msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+                raise ValueError(msg) if rc == nat.VS_E_ARG else nat.NativeError(rc, msg)
+            c = int(info[0])
+            sm.members_pass1 = int(info[2])
+            sm.message = [0, 1, m, header, int(info[1]), c] + [int(v) for v in x[:c]] + [int(v) for v in n[:c]]
+        except Exception as e:  # noqa: BLE001 (the peers hear of it through the message, then this rank raises it)
+            sm.failure = e
+            sm.message = [1, 0, 0, 0, 0, 0]
+        return sm
+
+    @classmethod
+    def shard_open(cls, mine: "BamStream.ShardSummary", everyone, all_gather, block_pairs: int = 1 << 20):
+        """Pass 2 on this rank from every rank's pass-1 message; see ``open_shard`` for what comes back."""
+        rank, ctx = mine.rank, mine.ctx
+        if mine.failure is not None:
+            raise mine.failure
+        failed = [r for r, vals in enumerate(everyone) if vals[0]]
+        if failed:
+            raise RuntimeError("BAM open failed on rank(s) %s" % failed)
+        plan, reason = bam_shard_plan(everyone)  # (a function of `everyone`: no rank can take another branch)
+        if reason is not None:
+            return None, reason
+        drop, own_end, before, start, after = plan[rank]
+        rng = (C.c_uint64 * 5)(int(mine.offsets[(everyone[rank][2] * rank) // mine.world]), drop, (1 << 64) - 1 if own_end is None else own_end,
+                               before & 1, start)
+        self = cls.__new__(cls)
+        self._ctx, self._h, self.block_pairs, self.by_name = ctx, None, block_pairs, False
+        h = C.c_void_p()
+        rc = nat.lib().vs_bam_stream_open_range(ctx._h, mine.path.encode(), rng, C.byref(h))
+        err = None
+        if rc != nat.VS_OK:
+            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+            err = FileNotFoundError(msg) if "cannot open" in msg else nat.NativeError(rc, msg)
+        status = all_gather([0 if err is None else 1])
+        if err is not None:
+            raise err
+        failed = [r for r, vals in enumerate(status) if vals[0]]
+        if failed:
+            nat.lib().vs_bam_stream_close(h)
+            raise RuntimeError("BAM open failed on rank(s) %s" % failed)
+        self._h = h
+        self.first_pair, self.pairs = (before + 1) // 2, (after + 1) // 2 - (before + 1) // 2
+        self.members, self.members_pass1, self.plan = everyone[rank][2], mine.members_pass1, plan[rank]
+        return self, None
+
     @property
     def info(self):
         a = (C.c_uint64 * 8)()
@@ -502,6 +606,74 @@ def bam_header_bytes(path: str) -> int:
     if rc != nat.VS_OK:
         raise ValueError(nat.lib().vs_last_error(None).decode("utf-8", "replace"))
     return int(n.value)
+
+
+BAM_SEG_MAX = 12288  # the largest segment of the chain passes, and so the most candidates of a share's summary
+BAM_SUM_DEAD, BAM_SUM_CUT = (1 << 64) - 1, (1 << 64) - 2
+# why the ranks of a sharded run leave a BAM to rank 0 (vs_bam_shard_plan's codes 3 ..; pe_inference adds "VS_BGZF_DEVICE=0")
+BAM_SHARD_REASONS = {
+    3: "not whole BGZF",
+    4: "the header reaches beyond the share of rank 0",
+    5: "a record longer than a segment across a share boundary, or a share without bytes",
+    6: "a block_size below 32 on the chain",
+    7: "the file ends inside a record",
+    8: "the chain does not end at the end of the file",
+    9: "an odd number of records that take part",
+}
+
+
+def bam_share_summary(share: bytes, share_size: int, start: Optional[int] = None, seg: int = 0, chunk: int = 0, ctx: "Context" = None):
+    """The summary of a share from its inflated bytes (test aid): ``share[:share_size]`` is the share, what follows are the
+    bytes behind it (64 at least, unless the file ends).  ``start``: the one candidate (rank 0: the header's size), None:
+    every candidate below min(seg, share_size).  ``chunk``: new bytes per window (0: one window).  ``vs_bam_share_summary_host``
+    (one host thread), or with ``ctx`` the kernels (``_text``).  Returns (X list, N list, windows)."""
+    buf = np.frombuffer(share or b"\0", dtype=np.uint8)
+    cap = 1 if start is not None else BAM_SEG_MAX
+    x = np.zeros(cap, dtype=np.uint64)
+    n = np.zeros(cap, dtype=np.uint64)
+    info = (C.c_uint64 * 2)()
+    st = (1 << 64) - 1 if start is None else start
+    if ctx is None:
+        rc = nat.lib().vs_bam_share_summary_host(buf.ctypes.data, len(share), share_size, st, seg, chunk, x.ctypes.data, n.ctypes.data, cap, info)
+        if rc != nat.VS_OK:
+            raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    else:
+        nat.check(ctx._h, nat.lib().vs_bam_share_summary_text(ctx._h, buf.ctypes.data, len(share), share_size, st, seg, chunk, x.ctypes.data,
+                                                             n.ctypes.data, cap, info))
+    c = int(info[0])
+    return [int(v) for v in x[:c]], [int(v) for v in n[:c]], int(info[1])
+
+
+def bam_shard_plan(everyone):
+    """``vs_bam_shard_plan`` (a pure function of the host) of every rank's pass-1 message [failed, whole BGZF, M, H, share
+    size, C, X[C], N[C]]: (per rank (bytes in front of its first record, where its ownership ends relative to its share or
+    None, participating records in front of its entry, inflated offset of its share, participating records in front of
+    the next rank's entry), None) or (None, reason of ``BAM_SHARD_REASONS``).  ``RuntimeError`` when a rank failed or the
+    ranks do not see the same file."""
+    world = len(everyone)
+    head = np.zeros(6 * world, dtype=np.uint64)
+    xn, off = [], np.zeros(world, dtype=np.uint64)
+    for r, vals in enumerate(everyone):
+        head[6 * r: 6 * r + 6] = [int(v) for v in vals[:6]]
+        c = int(vals[5])
+        if len(vals) != 6 + 2 * c:
+            raise RuntimeError("the message of rank %d has %d entries where its head says %d" % (r, len(vals), 6 + 2 * c))
+        off[r] = len(xn)
+        xn += [int(v) for v in vals[6:]]
+    xn = np.asarray(xn + [0], dtype=np.uint64)
+    plan = np.zeros(5 * world, dtype=np.uint64)
+    reason = C.c_int(0)
+    rc = nat.lib().vs_bam_shard_plan(world, head.ctypes.data, xn.ctypes.data, off.ctypes.data, plan.ctypes.data, C.byref(reason))
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    if reason.value == 1:
+        raise RuntimeError("BAM open failed on rank(s) %s" % [r for r, vals in enumerate(everyone) if vals[0]])
+    if reason.value == 2:
+        raise RuntimeError("the ranks do not see the same BAM file: (whole BGZF, members, header bytes) = %s" % sorted({tuple(v[1:4]) for v in everyone}))
+    if reason.value:
+        return None, BAM_SHARD_REASONS[reason.value]
+    none = (1 << 64) - 1
+    return [(int(p[0]), None if int(p[1]) == none else int(p[1]), int(p[2]), int(p[3]), int(p[4])) for p in plan.reshape(world, 5)], None
 
 
 def bam_scan(data: bytes, skip: int = 0, seg: int = 0, ctx: "Context" = None):

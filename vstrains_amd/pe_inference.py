@@ -36,7 +36,7 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     stream's ``info`` (``singletons`` among it), else None."""
     rank, world = _rank_world()
     count_links.bam_info = None
-    bam = bam_input(fwd, rve, world, by_name=bam_by_name)
+    bam = bam_input(fwd, rve, world, by_name=bam_by_name, sharded=not bam_by_name)  # (a collated BAM is shared by member)
     streamed = bam is None and use_stream(fwd, rve)
     if world > 1 and not (_regular(fwd) and _regular(rve)):  # (the sharded path maps regular files; VS_FASTQ_STREAM aside)
         raise ValueError("the FASTQ inputs %s / %s are not both regular files: a pipe can be read by one process only, so "
@@ -50,7 +50,35 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     # counters are summed over ranks afterwards (RCCL all-reduce); a single process takes everything
     if rank == 0 and stages_follow:
         counter.reserve_link_table()  # (the graph stages run on this rank: their table's buffer is taken now)
-    if bam is not None:
+    if bam is not None and world > 1:
+        # one collated whole-BGZF BAM: the ranks share it by member, summarise their shares for every entry the previous share
+        # could hand them, and each streams its own couples (BamStream.open_shard); why == the reason when rank 0 reads the
+        # whole file instead, as the single process does and in its words, and the others only join the sum
+        why = "VS_BGZF_DEVICE=0" if os.environ.get("VS_BGZF_DEVICE") == "0" else None
+        fq = None
+        if why is None:
+            fq, why = host.BamStream.open_shard(bam, ctx, rank, world, block_pairs=BATCH_PAIRS)
+        if fq is not None:
+            try:
+                count_stream(ctx, fq, counter, progress=(rank == 0))
+                info = fq.info
+            finally:
+                fq.close()
+            if info["pairs"] != fq.pairs:
+                raise RuntimeError("%s: %d pairs in the member range of rank %d where its plan says %d (did the file change?)"
+                                   % (bam, info["pairs"], rank, fq.pairs))
+            ingest_report(rank, world, "bam_members", None, fq.first_pair, info["pairs"], [fq.members], (fq.members_pass1,), (info["members_device"],))
+        elif rank == 0:
+            fq = host.BamStream(bam, ctx, block_pairs=BATCH_PAIRS)
+            try:
+                count_stream(ctx, fq, counter, progress=True)
+                info = fq.info
+            finally:
+                fq.close()
+            ingest_report(rank, world, "bam_whole_file_rank0", why, 0, info["pairs"], None, (0,), (info["members_device"],))
+        else:
+            ingest_report(rank, world, "bam_whole_file_rank0", why, 0, 0, None, (0,), (0,))
+    elif bam is not None:
         fq = host.BamStream(bam, ctx, block_pairs=BATCH_PAIRS, by_name=bam_by_name)  # one BAM stands for the pair (-f and -r both name it)
         try:
             count_stream(ctx, fq, counter, progress=True)
@@ -90,7 +118,8 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     else:
         fq = host.FastqPair(fwd, rve, ctx)  # :146-154, native multi-threaded ingest
         count_fastq(ctx, fq, counter, 0, len(fq), progress=True)
-    fq.close()
+    if fq is not None:
+        fq.close()
     if world > 1:
         counter.all_reduce()  # (every rank ends with the full sums; only rank 0 writes the files and runs the stages)
     return ids, counter
@@ -139,11 +168,13 @@ def _starts_bam(path: str) -> bool:
         return False
 
 
-def bam_input(fwd: str, rve: str, world: int = 1, by_name: bool = False):
+def bam_input(fwd: str, rve: str, world: int = 1, by_name: bool = False, sharded: bool = False):
     """The path when ``-f`` and ``-r`` name the same regular file and it is a BAM: the pair is read from it
     (``BamStream``).  None when neither input is a BAM.  ``ValueError`` for what is out of scope: BAM on one side only, two
     different BAM files, a BAM under a process group of more than one rank -- and, with ``by_name`` (``--bam-by-name``),
-    inputs that are not a BAM at all."""
+    inputs that are not a BAM at all.  ``sharded``: the caller shares a collated BAM among the ranks by member
+    (``BamStream.open_shard``; ``count_links`` does), so a process group is no refusal -- except with ``by_name``, whose
+    mates may lie in different ranks' shares."""
     is_bam = (_starts_bam(fwd), _starts_bam(rve))
     if not any(is_bam):
         if by_name:
@@ -156,8 +187,12 @@ def bam_input(fwd: str, rve: str, world: int = 1, by_name: bool = False):
     if not os.path.samefile(fwd, rve):
         raise ValueError("%s and %s are two different BAM files: a pair is read from ONE collated BAM (both mates in it); "
                          "name the same file for both reads" % (fwd, rve))
-    if world > 1:
-        raise ValueError("%s: a BAM file is read by one process only (no member-sharded BAM yet); run without torchrun" % fwd)
+    if world > 1 and by_name:
+        raise ValueError("%s: --bam-by-name reads the file in one process only: the mates of a pair may lie in different ranks' shares of "
+                         "a member-sharded run; run without torchrun, or `samtools collate` the file and leave the flag out" % fwd)
+    if world > 1 and not sharded:
+        raise ValueError("%s: a BAM file is read by one process only by this caller (count_links shares a collated BAM among the "
+                         "ranks by member); run without torchrun" % fwd)
     return fwd
 
 
