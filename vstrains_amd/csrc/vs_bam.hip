@@ -56,6 +56,7 @@
 //                         those records are counted), members behind that end inflated one at a time until the last second
 //                         record is whole.  Messages name a record by its byte offset in the inflated file.
 #include "vs_stream_reader.h"
+#include "vs_stream_window.h"
 #include "vs_bam_core.h"
 
 #define BAM_TPB 256
@@ -454,7 +455,13 @@ __global__ void __launch_bounds__(BAM_TPB) k_bam_ends_list(const uint4 *__restri
 // ---- the chain on a device window ---------------------------------------------------------------------------------------
 namespace {
 
-uint32_t seg_checked(uint32_t seg) { return seg == 0 ? BAM_SEG_DEFAULT : std::min<uint32_t>(std::max<uint32_t>(seg, BAM_SEG_MIN), BAM_SEG_MAX); }
+// the segment length to use: `seg` clamped, the default for 0 -- or, where 0 means the environment, what VS_BAM_SEG says (tests:
+// records across segments)
+uint32_t seg_checked(uint32_t seg, bool zero_is_env = false) {
+    if (seg == 0 && zero_is_env)
+        if (const char *ev = getenv("VS_BAM_SEG")) seg = (uint32_t)atoll(ev);
+    return seg == 0 ? BAM_SEG_DEFAULT : std::min<uint32_t>(std::max<uint32_t>(seg, BAM_SEG_MIN), BAM_SEG_MAX);
+}
 
 struct BamScan {
     VsDevBuf tab, entry, cnt_rec, cnt_part, recs, part;
@@ -621,12 +628,8 @@ struct vs_bam_stream {
     int device = 0;
     hipStream_t st = nullptr;
     Reader rd;
-    VsDevBuf win[2];
-    int cur = 0;
-    size_t size = 0;
+    DevWindow w;  // inflated BAM bytes that start at a record boundary
     bool eof = false;
-    VsDevBuf comp, dir, mstat;
-    uint64_t members_dev = 0;
     uint64_t skip = 0;  // header bytes still to drop from the front
     uint32_t seg = BAM_SEG_DEFAULT;
     BamScan sc;
@@ -655,7 +658,7 @@ struct vs_bam_stream {
     uint64_t win_base = 0;         // position of the window's byte 0
     uint64_t read_pos = 0;         // position of the next member to inflate
     uint32_t own_rec = 0, own_part = 0;  // of the scanned window: its records / participating records below own_end
-    Slot *held = nullptr;          // the slot whose members are being inflated, the next one is held_at
+    SlotLease held;                // the slot whose members are being inflated, the next one is held_at
     uint32_t held_at = 0;
 };
 
@@ -680,56 +683,27 @@ std::string rec_msg(const vs_bam_stream *s, uint64_t rec, const char *what) {
 
 const char *NOT_COLLATED = ": the file is not collated (mates do not follow each other); run `samtools collate` on it first, or match the mates by name (--bam-by-name)";
 
-// the window after its first `cut` bytes have gone: the leftover to the front of the other buffer
+// the window after its first `cut` bytes have gone
 int bam_drop_front(vs_ctx *ctx, vs_bam_stream *s, size_t cut) {
-    const size_t rest = s->size - cut;
-    const int o = s->cur ^ 1;
-    if (int rc = reserve_n<uint8_t>(ctx, s->win[o], ((rest + 15u) & ~(size_t)15u) + 16u)) return rc;
-    if (rest) VS_HIP(ctx, hipMemcpyAsync(s->win[o].as<uint8_t>(), s->win[s->cur].as<uint8_t>() + cut, rest, hipMemcpyDeviceToDevice, s->st));
-    s->cur = o;
-    s->size = rest;
+    if (int rc = s->w.keep_from(ctx, s->st, cut)) return rc;
     s->win_base += cut;
     return VS_OK;
 }
 
+int bam_too_large(vs_ctx *ctx, const vs_bam_stream *s, uint64_t bytes) {
+    return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete pair", s->rd.path.c_str(), (unsigned long long)bytes);
+}
+
 // the reader's next slot appended to the window: its bytes uploaded, or its BGZF members uploaded and inflated there
 int bam_append(vs_ctx *ctx, vs_bam_stream *s) {
-    Slot &sl = s->rd.take();
-    struct Back {
-        Reader &r;
-        ~Back() { r.give_back(); }
-    } back = {s->rd};
-    if (s->size + sl.text > STREAM_MAX_WINDOW)
+    const SlotLease lease(s->rd);
+    const Slot &sl = *lease;
+    if (s->w.size + sl.text > STREAM_MAX_WINDOW)
         return s->by_name ? vs_fail(ctx, VS_E_RANGE, "%s: the records that wait for their mates and the next chunk make a window of %llu bytes (the limit is %llu): "
                                                      "the mates lie too far apart to be matched by name; run `samtools collate` on the file first",
-                                    s->rd.path.c_str(), (unsigned long long)(s->size + sl.text), (unsigned long long)STREAM_MAX_WINDOW)
-                          : vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete pair", s->rd.path.c_str(), (unsigned long long)(s->size + sl.text));
-    const size_t need = ((s->size + sl.text + 15u) & ~(size_t)15u) + 16u;
-    if (s->win[s->cur].capacity() < need) {
-        const int o = s->cur ^ 1;
-        if (int rc = reserve_n<uint8_t>(ctx, s->win[o], need)) return rc;
-        if (s->size) VS_HIP(ctx, hipMemcpyAsync(s->win[o].as<uint8_t>(), s->win[s->cur].as<uint8_t>(), s->size, hipMemcpyDeviceToDevice, s->st));
-        s->cur = o;
-    }
-    uint8_t *dst = s->win[s->cur].as<uint8_t>() + s->size;
-    if (sl.comp) {
-        const uint32_t nm = sl.n_members;
-        if (nm) {
-            if (int rc = reserve_n<uint8_t>(ctx, s->comp, sl.len + 16u)) return rc;
-            if (int rc = reserve_n<vs_bgzf_member>(ctx, s->dir, (size_t)nm)) return rc;
-            if (int rc = reserve_n<uint32_t>(ctx, s->mstat, (size_t)nm)) return rc;
-            const vs_bgzf_member *dir = (const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()) - nm;  // (member i at dir[nm - 1 - i])
-            if (sl.len) VS_HIP(ctx, hipMemcpyAsync(s->comp.as<uint8_t>(), sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st));
-            VS_HIP(ctx, hipMemcpyAsync(s->dir.as<vs_bgzf_member>(), dir, sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, s->st));
-            vs_launch_inflate(s->st, s->comp.as<uint8_t>(), sl.len, dst, sl.text, s->dir.as<vs_bgzf_member>(), nm, s->mstat.as<uint32_t>(),
-                              s->d_stat + B_BAD_MEMBER, (uint32_t)s->members_dev, 1);
-            VS_HIP(ctx, hipGetLastError());
-            s->members_dev += nm;
-        }
-    } else if (sl.len) {
-        VS_HIP(ctx, hipMemcpyAsync(dst, sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st));
-    }
-    s->size += sl.text;
+                                    s->rd.path.c_str(), (unsigned long long)(s->w.size + sl.text), (unsigned long long)STREAM_MAX_WINDOW)
+                          : bam_too_large(ctx, s, s->w.size + sl.text);
+    if (int rc = s->w.append(ctx, s->st, sl, s->d_stat + B_BAD_MEMBER, (uint32_t)s->w.members)) return rc;
     s->eof = sl.last;
     VS_HIP(ctx, hipStreamSynchronize(s->st));  // (the slot goes back: its bytes are on the device)
     return VS_OK;
@@ -740,66 +714,36 @@ int bam_append(vs_ctx *ctx, vs_bam_stream *s) {
 // come one by one until it is whole.
 int bam_append_ranged(vs_ctx *ctx, vs_bam_stream *s) {
     if (!s->held) {
-        Slot &sl = s->rd.take();
+        SlotLease lease(s->rd);
+        const Slot &sl = *lease;
         if (!sl.comp || !sl.n_members) {  // (the end of the file, or bytes that are no BGZF member: pass 1 saw a whole-BGZF file)
-            const bool empty = sl.len == 0;
             s->eof = sl.last;
-            s->rd.give_back();
-            if (!empty) return vs_fail(ctx, VS_E_STATE, "%s changed after its members were walked (it is not whole BGZF any more)", s->rd.path.c_str());
+            if (sl.len) return vs_fail(ctx, VS_E_STATE, "%s changed after its members were walked (it is not whole BGZF any more)", s->rd.path.c_str());
             return VS_OK;
         }
-        if (int rc = reserve_n<uint8_t>(ctx, s->comp, sl.len + 16u)) { s->rd.give_back(); return rc; }
-        if (hipMemcpyAsync(s->comp.as<uint8_t>(), sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st) != hipSuccess) {
-            s->rd.give_back();
-            return vs_fail(ctx, VS_E_HIP, "vs_bam_stream_next: upload of a chunk");
-        }
-        s->held = &sl;
+        if (int rc = s->w.upload_payloads(ctx, s->st, sl)) return rc == VS_E_OOM ? rc : vs_fail(ctx, VS_E_HIP, "vs_bam_stream_next: upload of a chunk");
+        s->held = std::move(lease);
         s->held_at = 0;
     }
-    Slot &sl = *s->held;
-    const uint32_t nm = sl.n_members, a = s->held_at;
-    const vs_bgzf_member *dir_end = (const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity());  // (member i at dir_end[-(i + 1)])
-    std::vector<vs_bgzf_member> dir;
+    const Slot &sl = *s->held;
+    const uint32_t a = s->held_at;
+    uint32_t b = a;
     uint64_t text = 0;
-    for (uint32_t b = a; b < nm; b++) {
+    for (; b < sl.n_members; b++) {
         if (b > a && s->own_end != ~0ull && s->read_pos + text >= s->own_end) break;
-        vs_bgzf_member m = dir_end[-(ptrdiff_t)(b + 1u)];
-        m.out_off = (uint32_t)text;
-        text += m.isize;
-        dir.push_back(m);
+        text += slot_member(sl, b).isize;
     }
-    const uint32_t k = (uint32_t)dir.size();
-    struct Back {
-        vs_bam_stream *s;
-        bool whole;
-        ~Back() {
-            if (!whole) return;
-            s->eof = s->held->last;
-            s->held = nullptr;
-            s->rd.give_back();
-        }
-    } back = {s, a + k == nm};
-    if (s->size + text > STREAM_MAX_WINDOW)
-        return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete pair", s->rd.path.c_str(), (unsigned long long)(s->size + text));
-    const size_t need = ((s->size + text + 15u) & ~(size_t)15u) + 16u;
-    if (s->win[s->cur].capacity() < need) {
-        const int o = s->cur ^ 1;
-        if (int rc = reserve_n<uint8_t>(ctx, s->win[o], need)) return rc;
-        if (s->size) VS_HIP(ctx, hipMemcpyAsync(s->win[o].as<uint8_t>(), s->win[s->cur].as<uint8_t>(), s->size, hipMemcpyDeviceToDevice, s->st));
-        s->cur = o;
+    int rc = s->w.size + text > STREAM_MAX_WINDOW ? bam_too_large(ctx, s, s->w.size + text)
+                                                  : s->w.append_members(ctx, s->st, sl, a, b, s->d_stat + B_BAD_MEMBER, (uint32_t)s->w.members);
+    if (rc == VS_OK) {
+        s->held_at = b;
+        s->read_pos += text;
     }
-    if (int rc = reserve_n<vs_bgzf_member>(ctx, s->dir, (size_t)k)) return rc;
-    if (int rc = reserve_n<uint32_t>(ctx, s->mstat, (size_t)k)) return rc;
-    VS_HIP(ctx, hipMemcpyAsync(s->dir.as<vs_bgzf_member>(), dir.data(), sizeof(vs_bgzf_member) * k, hipMemcpyHostToDevice, s->st));
-    vs_launch_inflate(s->st, s->comp.as<uint8_t>(), sl.len, s->win[s->cur].as<uint8_t>() + s->size, text, s->dir.as<vs_bgzf_member>(), k, s->mstat.as<uint32_t>(),
-                      s->d_stat + B_BAD_MEMBER, (uint32_t)s->members_dev, 0);
-    VS_HIP(ctx, hipGetLastError());
-    VS_HIP(ctx, hipStreamSynchronize(s->st));  // (dir is read by the copy; the slot may go back)
-    s->members_dev += k;
-    s->held_at = a + k;
-    s->size += text;
-    s->read_pos += text;
-    return VS_OK;
+    if (b == sl.n_members) {  // (the slot is done with, whatever came of its last members)
+        s->eof = sl.last;
+        s->held.give_back();
+    }
+    return rc;
 }
 
 int bam_pass(vs_ctx *ctx, vs_bam_stream *s, uint32_t upto);
@@ -810,7 +754,7 @@ int bam_owned(vs_ctx *ctx, vs_bam_stream *s) {
     s->own_rec = sc.n_rec;
     s->own_part = sc.n_part;
     const uint64_t lim = s->own_end == ~0ull ? ~0ull : (s->own_end > s->win_base ? s->own_end - s->win_base : 0u);
-    if (lim < s->size && sc.n_rec) {
+    if (lim < s->w.size && sc.n_rec) {
         VS_HIP(ctx, hipMemsetAsync(s->d_stat + B_OWN_REC, 0, sizeof(uint32_t) * 2, s->st));
         hipLaunchKernelGGL(k_bam_owned, dim3((sc.n_rec + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, s->st, sc.recs.as<const uint4>(), sc.part.as<const uint32_t>(),
                            sc.n_rec, sc.n_part, (uint32_t)lim, s->d_stat);
@@ -858,19 +802,17 @@ int bam_pass(vs_ctx *ctx, vs_bam_stream *s, uint32_t upto) {
 // `stop` on (the record the window's end cut, or nothing)
 int bam_carry_waiting(vs_ctx *ctx, vs_bam_stream *s) {
     const BamMatch &mt = s->mt;
-    if (s->sc.stop > s->size) return vs_fail(ctx, VS_E_STATE, "%s: a record start beyond the window", s->rd.path.c_str());
-    const size_t rest = s->size - s->sc.stop, total = (size_t)mt.wait_bytes + rest;
-    const int o = s->cur ^ 1;
-    if (int rc = reserve_n<uint8_t>(ctx, s->win[o], ((total + 15u) & ~(size_t)15u) + 16u)) return rc;
-    if (int rc = bam_carry_device(ctx, s->st, s->size, mt, s->win[o].as<uint8_t>(), mt.wait_bytes)) return rc;
-    if (rest)
-        VS_HIP(ctx, hipMemcpyAsync(s->win[o].as<uint8_t>() + mt.wait_bytes, s->win[s->cur].as<uint8_t>() + s->sc.stop, rest, hipMemcpyDeviceToDevice, s->st));
+    if (s->sc.stop > s->w.size) return vs_fail(ctx, VS_E_STATE, "%s: a record start beyond the window", s->rd.path.c_str());
+    const size_t rest = s->w.size - s->sc.stop, total = (size_t)mt.wait_bytes + rest;
+    uint8_t *next = nullptr;
+    if (int rc = s->w.other(ctx, total, &next)) return rc;
+    if (int rc = bam_carry_device(ctx, s->st, s->w.size, mt, next, mt.wait_bytes)) return rc;
+    if (rest) VS_HIP(ctx, hipMemcpyAsync(next + mt.wait_bytes, s->w.data() + s->sc.stop, rest, hipMemcpyDeviceToDevice, s->st));
     s->first_record += s->sc.n_rec - s->n_carried;
     s->n_carried = mt.n_wait;
     s->waiting_max = std::max<uint64_t>(s->waiting_max, mt.n_wait);
     s->carried_bytes_max = std::max<uint64_t>(s->carried_bytes_max, mt.wait_bytes);
-    s->cur = o;
-    s->size = total;
+    s->w.flip(total);
     return VS_OK;
 }
 
@@ -1011,16 +953,11 @@ static int bam_open(vs_ctx *ctx, const char *path, int mode, const uint64_t *ran
         s->share_start = range[4];
     }
     if (const char *ev = getenv("VS_BAM_NAME_BITS")) s->name_bits = (uint32_t)std::min<long long>(std::max<long long>(atoll(ev), 0), 64);  // (tests: long probe chains)
-    if (const char *ev = getenv("VS_BAM_SEG")) s->seg = seg_checked((uint32_t)atoll(ev));  // (tests: records across segments)
+    s->seg = seg_checked(0, true);
     Reader &r = s->rd;
-    r.path = path;
-    r.device = ctx->device;
-    if (const char *ev = getenv("VS_STREAM_CHUNK")) r.chunk = std::max<size_t>(1u, (size_t)atoll(ev));
-    r.fd = open(path, O_RDONLY);
-    if (r.fd < 0) {
-        const int e = errno;
+    if (int rc = r.open_file(ctx, path)) {
         delete s;
-        return vs_fail(ctx, VS_E_ARG, "cannot open %s: %s", path, strerror(e));
+        return rc;
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
     if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * B_ALL);
@@ -1070,7 +1007,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
                     VS_HIP(ctx, hipMemcpyAsync(&cut, (const uint32_t *)(sc.recs.as<uint4>() + s->rec_cur), sizeof cut, hipMemcpyDeviceToHost, st));
                     VS_HIP(ctx, hipStreamSynchronize(st));
                 }
-                if (cut > s->size) return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": a record start beyond the window");
+                if (cut > s->w.size) return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": a record start beyond the window");
                 if (int rc = bam_drop_front(ctx, s, cut)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
                 s->first_record += s->rec_cur;
             }
@@ -1080,7 +1017,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
         if (!s->eof) {
             if (int rc = s->ranged ? bam_append_ranged(ctx, s) : bam_append(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
             if (s->skip) {  // the header goes, whole windows of it if need be
-                const size_t now = (size_t)std::min<uint64_t>(s->skip, s->size);
+                const size_t now = (size_t)std::min<uint64_t>(s->skip, s->w.size);
                 if (int rc = bam_drop_front(ctx, s, now)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
                 s->skip -= now;
                 if (s->skip) {
@@ -1089,7 +1026,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
                 }
             }
         }
-        if (int rc = bam_scan_device(ctx, st, s->win[s->cur].as<const uint8_t>(), s->size, 0, s->seg, sc, s->d_stat, s->h_stat))
+        if (int rc = bam_scan_device(ctx, st, s->w.data(), s->w.size, 0, s->seg, sc, s->d_stat, s->h_stat))
             return bam_fail(ctx, s, rc, vs_last_error(ctx));
         s->scanned = true;
         if (s->h_stat[B_BAD_MEMBER] != BAM_NONE)
@@ -1104,7 +1041,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
         if (s->by_name) {
             s->windows++;
             s->pair_cur = 0;
-            if (int rc = bam_match_device(ctx, st, s->win[s->cur].as<const uint8_t>(), s->size, sc, s->name_bits, s->mt)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = bam_match_device(ctx, st, s->w.data(), s->w.size, sc, s->name_bits, s->mt)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
             if (s->mt.crowded != BAM_NONE)
                 return bam_fail(ctx, s, VS_E_RANGE, rec_msg(s, s->mt.crowded, " is one of more than 64 records of one name and one end (first or second) in a window: mates "
                                                                               "are matched by name among at most 64 such records; run `samtools collate` on the file first"));
@@ -1161,7 +1098,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
     const uint64_t words = s->h_stat[B_WORDS];
     r->max_len = s->h_stat[B_MAXLEN];
     if ((e1 = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e1, no_buffers);
-    vs_launch_pack_bam(st, BamEnds{s->win[s->cur].as<const uint8_t>(), (const uint32_t *)sc.recs.as<uint4>(), s->d_ends.as<const uint32_t>()}, r);
+    vs_launch_pack_bam(st, BamEnds{s->w.data(), (const uint32_t *)sc.recs.as<uint4>(), s->d_ends.as<const uint32_t>()}, r);
     if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
     if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + B_INVALID, s->h_stat + B_INVALID)) != hipSuccess) return fail(e1);
     if (!s->by_name && bam_pass(ctx, s, s->h_stat[B_CUTREC]) != VS_OK) return fail(hipErrorUnknown);
@@ -1181,7 +1118,7 @@ int vs_bam_stream_info(const vs_bam_stream *s, uint64_t info[8]) {
     info[1] = (uint64_t)t[0] + t[1] + t[2] + t[3] + t[4];
     info[2] = t[BAM_C_DROP900];
     info[3] = t[BAM_C_OTHER];
-    info[4] = s->members_dev;
+    info[4] = s->w.members;
     info[5] = s->rd.text_bytes;
     info[6] = s->rd.raw_bytes;
     info[7] = s->done ? 1u : 0u;
@@ -1353,12 +1290,6 @@ struct BamSum {
     uint64_t share = 0, base = 0, windows = 0;  // the share's inflated size; the position of the next window's byte 0
 };
 
-uint32_t seg_of(uint32_t seg) {
-    if (seg == 0)
-        if (const char *ev = getenv("VS_BAM_SEG")) seg = (uint32_t)atoll(ev);
-    return seg_checked(seg);
-}
-
 // lanes: `start` alone (rank 0: the end of the header), or every candidate [0, min(seg, share)) for start = ~0
 int sum_begin(vs_ctx *ctx, hipStream_t st, BamSum &sm, uint64_t share, uint64_t start, uint32_t seg, uint64_t cap) {
     sm.seg = seg;
@@ -1408,10 +1339,8 @@ int sum_end(vs_ctx *ctx, hipStream_t st, BamSum &sm, uint64_t *x, uint64_t *cnt)
 // ISIZE of the member that ends at file offset `end`
 int member_isize(int fd, const char *path, uint64_t end, uint32_t *isize) {
     uint8_t t[4];
-    ssize_t got;
-    do got = end >= 4u ? pread(fd, t, 4, (off_t)(end - 4u)) : 0;
-    while (got < 0 && errno == EINTR);
-    if (got != 4) return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, got < 0 ? strerror(errno) : "it shrank while it was read");
+    if (const char *why = end >= 4u ? pread_all(fd, t, 4, end - 4u) : "it shrank while it was read")
+        return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, why);
     *isize = bam_le32(t);
     return VS_OK;
 }
@@ -1463,7 +1392,7 @@ int vs_bam_share_summary(vs_ctx *ctx, const char *path, const uint64_t *offsets,
         if (offsets[i + 1] <= offsets[i] || offsets[i + 1] - offsets[i] > 65536u)
             return vs_fail(ctx, VS_E_ARG, "vs_bam_share_summary: member %llu is no BGZF member's size", (unsigned long long)i);
     VS_HIP(ctx, hipSetDevice(ctx->device));
-    seg = seg_of(seg);
+    seg = seg_checked(seg, true);
     struct Run {
         Reader rd;
         hipStream_t st = nullptr;
@@ -1474,11 +1403,7 @@ int vs_bam_share_summary(vs_ctx *ctx, const char *path, const uint64_t *offsets,
         }
     } run;
     Reader &r = run.rd;
-    r.path = path;
-    r.device = ctx->device;
-    if (const char *ev = getenv("VS_STREAM_CHUNK")) r.chunk = std::max<size_t>(1u, (size_t)atoll(ev));
-    r.fd = open(path, O_RDONLY);
-    if (r.fd < 0) return vs_fail(ctx, VS_E_ARG, "cannot open %s: %s", path, strerror(errno));
+    if (int rc = r.open_file(ctx, path)) return rc;
     // the share's inflated size, and the whole members behind it that hold BAM_SUM_TAIL bytes (or the rest of the file)
     uint64_t share = 0, tail = 0, until = last;
     for (uint64_t i = first; i < last; i++) {
@@ -1498,62 +1423,31 @@ int vs_bam_share_summary(vs_ctx *ctx, const char *path, const uint64_t *offsets,
     hipStream_t st = run.st;
     BamSum sm;
     if (int rc = sum_begin(ctx, st, sm, share, start, seg, cap)) return rc;
-    VsDevBuf win[2], comp, dir, mstat, bad;
+    DevWindow w;  // one slot + what the window before left undone
+    VsDevBuf bad;
     VS_HIP(ctx, bad.reserve(sizeof(uint32_t)));
     VS_HIP(ctx, hipMemsetAsync(bad.ptr(), 0xFF, sizeof(uint32_t), st));
-    int cur = 0;
-    size_t size = 0;
-    uint64_t members = 0, inflated = 0;
+    uint64_t inflated = 0;
     r.th = std::thread([rp = &r] { rp->run(); });
     for (bool eof = false; !eof;) {
-        Slot &sl = r.take();
-        struct Back {
-            Reader &r;
-            ~Back() { r.give_back(); }
-        } back = {r};
+        const SlotLease lease(r);  // (every round ends synchronised: the slot's bytes are on the device)
+        const Slot &sl = *lease;
         eof = sl.last;
         if (!sl.comp && sl.len) return vs_fail(ctx, VS_E_STATE, "%s changed after its members were walked (it is not whole BGZF any more)", path);
-        const uint32_t nm = sl.comp ? sl.n_members : 0u;
-        const size_t text = nm ? sl.text : 0u;
-        if (size + text > STREAM_MAX_WINDOW) return vs_fail(ctx, VS_E_RANGE, "a BAM window of %llu bytes", (unsigned long long)(size + text));
-        const size_t need = ((size + text + 15u) & ~(size_t)15u) + 16u;
-        if (win[cur].capacity() < need) {
-            const int o = cur ^ 1;
-            if (int rc = reserve_n<uint8_t>(ctx, win[o], need)) return rc;
-            if (size) VS_HIP(ctx, hipMemcpyAsync(win[o].as<uint8_t>(), win[cur].as<uint8_t>(), size, hipMemcpyDeviceToDevice, st));
-            cur = o;
-        }
-        if (nm) {
-            if (int rc = reserve_n<uint8_t>(ctx, comp, sl.len + 16u)) return rc;
-            if (int rc = reserve_n<vs_bgzf_member>(ctx, dir, (size_t)nm)) return rc;
-            if (int rc = reserve_n<uint32_t>(ctx, mstat, (size_t)nm)) return rc;
-            const vs_bgzf_member *d = (const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()) - nm;  // (member i at d[nm - 1 - i])
-            if (sl.len) VS_HIP(ctx, hipMemcpyAsync(comp.as<uint8_t>(), sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, st));
-            VS_HIP(ctx, hipMemcpyAsync(dir.as<vs_bgzf_member>(), d, sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, st));
-            vs_launch_inflate(st, comp.as<uint8_t>(), sl.len, win[cur].as<uint8_t>() + size, text, dir.as<vs_bgzf_member>(), nm, mstat.as<uint32_t>(),
-                              bad.as<uint32_t>(), (uint32_t)(first + members), 1);
-            VS_HIP(ctx, hipGetLastError());
-            members += nm;
-            inflated += text;
-        }
-        size += text;
+        if (w.size + sl.text > STREAM_MAX_WINDOW) return vs_fail(ctx, VS_E_RANGE, "a BAM window of %llu bytes", (unsigned long long)(w.size + sl.text));
+        if (int rc = w.append(ctx, st, sl, bad.as<uint32_t>(), (uint32_t)(first + w.members))) return rc;
+        inflated += sl.text;
         uint64_t lim = 0;
-        if (int rc = sum_window(ctx, st, sm, win[cur].as<const uint8_t>(), size, eof ? 1 : 0, &lim)) return rc;
+        if (int rc = sum_window(ctx, st, sm, w.data(), w.size, eof ? 1 : 0, &lim)) return rc;
         uint32_t first_bad = BAM_NONE;
         VS_HIP(ctx, hipMemcpyAsync(&first_bad, bad.ptr(), sizeof first_bad, hipMemcpyDeviceToHost, st));
         VS_HIP(ctx, hipStreamSynchronize(st));
         if (first_bad != BAM_NONE)
             return vs_fail(ctx, VS_E_ARG, "%s: not a complete gzip stream (BGZF member %u does not inflate to its CRC32 and size)", path, first_bad);
-        // what is not done is the front of the next window
-        const size_t rest = size - (size_t)lim;
-        if (!eof && lim) {
-            const int o = cur ^ 1;
-            if (int rc = reserve_n<uint8_t>(ctx, win[o], ((rest + 15u) & ~(size_t)15u) + 16u)) return rc;
-            if (rest) VS_HIP(ctx, hipMemcpyAsync(win[o].as<uint8_t>(), win[cur].as<uint8_t>() + lim, rest, hipMemcpyDeviceToDevice, st));
+        if (!eof && lim) {  // what is not done is the front of the next window
+            if (int rc = w.keep_from(ctx, st, (size_t)lim)) return rc;
             VS_HIP(ctx, hipStreamSynchronize(st));
-            cur = o;
         }
-        size = rest;
     }
     if (r.err != VS_OK) return vs_fail(ctx, r.err, "%s", r.err_msg.c_str());
     if (inflated != share + tail) return vs_fail(ctx, VS_E_STATE, "%s changed after its members were walked (%llu inflated bytes where its trailers say %llu)", path,
@@ -1561,7 +1455,7 @@ int vs_bam_share_summary(vs_ctx *ctx, const char *path, const uint64_t *offsets,
     if (int rc = sum_end(ctx, st, sm, x, cnt)) return rc;
     info[0] = sm.n_lanes;
     info[1] = share;
-    info[2] = members;
+    info[2] = w.members;
     info[3] = r.raw_bytes;
     info[4] = sm.windows;
     return VS_OK;

@@ -62,6 +62,7 @@
 
 #include "vs_internal.h"
 #include "vs_stream_reader.h"
+#include "vs_stream_window.h"
 
 #define SL_TPB 256
 #define SL_SCAN_TPB 1024
@@ -238,12 +239,9 @@ __global__ void __launch_bounds__(SL_TPB) k_sl_ends(SlWin f0, SlWin f1, uint32_t
 // ---- host side (the reader: vs_stream_reader.h) ---------------------------------------------------------------------------
 namespace {
 
-// The device side of one file: the window (two buffers, the leftover copied from one to the other after a block) and
-// its line ends.
+// The device side of one file: the window (vs_stream_window.h) and its line ends.
 struct DevFile {
-    VsDevBuf win[2];       // bytes
-    int cur = 0;
-    size_t size = 0;       // bytes in the window
+    DevWindow w;
     size_t validated = 0;  // [0, validated) is known to be valid UTF-8 (ASCII, or checked on the host)
     VsDevBuf ends, wg;     // uint32
     uint32_t n_nl = 0, flags = 0, last_byte = 0;
@@ -254,10 +252,7 @@ struct DevFile {
     std::string err_msg;
     uint32_t pend[4] = {0, 0, 0, 0};  // (end-of-input check) bytes of a character cut by a chunk boundary
     uint32_t n_pend = 0;
-    // BGZF: the device copy of a slot's payloads and directory, a status word per member
-    VsDevBuf comp, dir, mstat;  // bytes, vs_bgzf_member, uint32
-    uint64_t members_dev = 0;  // members the device inflated so far
-    uint32_t slot_base = 0;    // running index of the first member of the slot appended last
+    uint32_t slot_base = 0;  // BGZF: running index of the first member of the slot appended last
     // a member range (vs_fastq_stream_open_range): lines still to drop from the front; whether the range ends where the file does
     uint64_t skip = 0;
     bool to_file_end = true;
@@ -299,10 +294,10 @@ int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
     for (int f = 0; f < 2; f++) {
         if (only >= 0 && f != only) continue;
         DevFile &d = s->df[f];
-        const uint64_t words = (d.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
+        const uint64_t words = (d.w.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
         if (int rc = reserve_n<uint32_t>(ctx, d.wg, wgs + 1u)) return rc;
         if (wgs) {
-            hipLaunchKernelGGL(k_sl_count, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, d.win[d.cur].as<const uint8_t>(), (uint64_t)d.size, d.wg.as<uint32_t>(),
+            hipLaunchKernelGGL(k_sl_count, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(),
                                s->d_stat + f * ST_PER_FILE);
             hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, d.wg.as<uint32_t>(), (uint32_t)wgs, s->d_stat + f * ST_PER_FILE + ST_NL);
         }
@@ -317,10 +312,10 @@ int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
         d.flags = s->h_stat[f * ST_PER_FILE + ST_FLAGS];
         d.last_byte = s->h_stat[f * ST_PER_FILE + ST_LAST];
         s->flags_seen |= d.flags;
-        if (!d.flags) d.validated = d.size;
+        if (!d.flags) d.validated = d.w.size;
         // (a final line without a newline counts -- at the end of the FILE: where a member range ends earlier, the bytes behind
         // its last newline are the front of a line of the next rank)
-        const uint64_t lines = (uint64_t)d.n_nl + ((d.eof && d.to_file_end && d.size && d.last_byte != '\n') ? 1u : 0u);
+        const uint64_t lines = (uint64_t)d.n_nl + ((d.eof && d.to_file_end && d.w.size && d.last_byte != '\n') ? 1u : 0u);
         d.records = lines / 4u;
     }
     return VS_OK;
@@ -330,11 +325,11 @@ int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
 // the end of the file) are translated and checked, the rest -- a partial line -- stays as it is for the next chunk.
 int translate_window(vs_ctx *ctx, vs_fastq_stream *s, int f) {
     DevFile &d = s->df[f];
-    std::vector<uint8_t> buf(d.size);
-    if (d.size) VS_HIP(ctx, hipMemcpy(buf.data(), d.win[d.cur].as<uint8_t>(), d.size, hipMemcpyDeviceToHost));
-    size_t cut = d.size;
+    std::vector<uint8_t> buf(d.w.size);
+    if (d.w.size) VS_HIP(ctx, hipMemcpy(buf.data(), d.w.data(), d.w.size, hipMemcpyDeviceToHost));
+    size_t cut = d.w.size;
     if (!d.eof) {
-        size_t lim = d.size;
+        size_t lim = d.w.size;
         if (lim && buf[lim - 1] == '\r') lim--;  // ("\r\n" may straddle the chunks)
         cut = 0;
         for (size_t i = lim; i-- > 0;)
@@ -346,7 +341,7 @@ int translate_window(vs_ctx *ctx, vs_fastq_stream *s, int f) {
         return VS_E_UTF8;
     }
     std::vector<uint8_t> out;
-    out.reserve(d.size);
+    out.reserve(d.w.size);
     for (size_t i = 0; i < cut;) {
         const uint8_t c = buf[i];
         if (c == '\r') {
@@ -363,8 +358,8 @@ int translate_window(vs_ctx *ctx, vs_fastq_stream *s, int f) {
     }
     const size_t translated = out.size();
     out.insert(out.end(), buf.begin() + (ptrdiff_t)cut, buf.end());
-    if (!out.empty()) VS_HIP(ctx, hipMemcpy(d.win[d.cur].as<uint8_t>(), out.data(), out.size(), hipMemcpyHostToDevice));
-    d.size = out.size();
+    if (!out.empty()) VS_HIP(ctx, hipMemcpy(d.w.data(), out.data(), out.size(), hipMemcpyHostToDevice));
+    d.w.size = out.size();
     d.validated = translated;
     return VS_OK;
 }
@@ -399,7 +394,7 @@ bool check_piece(DevFile &d, const uint8_t *p, size_t n, bool last) {
     return true;
 }
 
-int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot &sl);
+int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl);
 bool zlib_accepts(const uint8_t *pay, const vs_bgzf_member &mb, int *code);
 bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl);
 
@@ -409,38 +404,35 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
     for (int f = 0; f < 2; f++) {
         DevFile &d = s->df[f];
         Reader &r = s->rd[f];
-        if (d.err == VS_OK && d.validated < d.size && (d.flags & FL_HIGH)) {
-            std::vector<uint8_t> buf(d.size - d.validated);
-            VS_HIP(ctx, hipMemcpy(buf.data(), d.win[d.cur].as<uint8_t>() + d.validated, buf.size(), hipMemcpyDeviceToHost));
+        if (d.err == VS_OK && d.validated < d.w.size && (d.flags & FL_HIGH)) {
+            std::vector<uint8_t> buf(d.w.size - d.validated);
+            VS_HIP(ctx, hipMemcpy(buf.data(), d.w.data() + d.validated, buf.size(), hipMemcpyDeviceToHost));
             if (!check_piece(d, buf.data(), buf.size(), d.eof)) {
                 d.err = VS_E_UTF8;
                 d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
             }
         }
-        d.validated = d.size;
+        d.validated = d.w.size;
         while (!d.eof) {
-            Slot &sl = r.take();
+            const SlotLease lease(r);  // (goes back at the end of the round, or with a failure)
+            const Slot &sl = *lease;
             bool ok = true;
             if (d.err == VS_OK && sl.comp) {
                 // no text on the host: the members are inflated (and their CRCs checked) on the device like any others, and
                 // the text comes back only when the scan saw a byte >= 0x80 (or a character is still open)
-                d.size = 0;
+                d.w.size = 0;
                 int rc = append_slot(ctx, s, f, sl);
                 if (rc == VS_OK) rc = scan_windows(ctx, s, f);
                 if (rc != VS_OK) {
-                    const std::string msg = vs_last_error(ctx);
-                    r.give_back();
-                    return stream_fail(ctx, s, rc, msg);
+                    return stream_fail(ctx, s, rc, vs_last_error(ctx));
                 }
                 if (!member_failed(ctx, s, f, sl) && ((d.flags & FL_HIGH) || d.n_pend)) {
-                    std::vector<uint8_t> buf(d.size);
-                    if (d.size && hipMemcpy(buf.data(), d.win[d.cur].as<uint8_t>(), d.size, hipMemcpyDeviceToHost) != hipSuccess) {
-                        r.give_back();
+                    std::vector<uint8_t> buf(d.w.size);
+                    if (d.w.size && hipMemcpy(buf.data(), d.w.data(), d.w.size, hipMemcpyDeviceToHost) != hipSuccess)
                         return stream_fail(ctx, s, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
-                    }
                     ok = check_piece(d, buf.data(), buf.size(), sl.last);
                 }
-                d.size = d.validated = 0;
+                d.w.size = d.validated = 0;
             } else if (d.err == VS_OK) {
                 ok = check_piece(d, sl.buf.as<uint8_t>(), sl.len, sl.last);
             }
@@ -449,7 +441,6 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
                 d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
             }
             d.eof = sl.last;
-            r.give_back();
         }
         if (d.err == VS_OK && d.n_pend) {  // (a character cut off by the end of the file)
             d.err = VS_E_UTF8;
@@ -467,45 +458,21 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
 }
 
 // a slot of file f appended to its window: its text uploaded, or its BGZF members uploaded and inflated there
-int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot &sl) {
+int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
     DevFile &d = s->df[f];
-    if (d.size + sl.text > STREAM_MAX_WINDOW)
+    if (d.w.size + sl.text > STREAM_MAX_WINDOW)
         return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete record", s->rd[f].path.c_str(),
-                       (unsigned long long)(d.size + sl.text));
-    const size_t need = ((d.size + sl.text + 15u) & ~(size_t)15u) + 16u;
-    if (d.win[d.cur].capacity() < need) {  // keep the leftover: grow the other buffer, copy, switch
-        const int o = d.cur ^ 1;
-        if (int rc = reserve_n<uint8_t>(ctx, d.win[o], need)) return rc;
-        if (d.size) VS_HIP(ctx, hipMemcpyAsync(d.win[o].as<uint8_t>(), d.win[d.cur].as<uint8_t>(), d.size, hipMemcpyDeviceToDevice, s->st));
-        d.cur = o;
-    }
-    if (sl.comp) {
-        const uint32_t nm = sl.n_members;
-        d.slot_base = (uint32_t)d.members_dev;
-        if (nm) {
-            if (int rc = reserve_n<uint8_t>(ctx, d.comp, sl.len + 16u)) return rc;
-            if (int rc = reserve_n<vs_bgzf_member>(ctx, d.dir, (size_t)nm)) return rc;
-            if (int rc = reserve_n<uint32_t>(ctx, d.mstat, (size_t)nm)) return rc;
-            const vs_bgzf_member *dir = (const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()) - nm;  // (member i at dir[nm - 1 - i])
-            if (sl.len) VS_HIP(ctx, hipMemcpyAsync(d.comp.as<uint8_t>(), sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st));
-            VS_HIP(ctx, hipMemcpyAsync(d.dir.as<vs_bgzf_member>(), dir, sizeof(vs_bgzf_member) * nm, hipMemcpyHostToDevice, s->st));
-            vs_launch_inflate(s->st, d.comp.as<uint8_t>(), sl.len, d.win[d.cur].as<uint8_t>() + d.size, sl.text, d.dir.as<vs_bgzf_member>(), nm, d.mstat.as<uint32_t>(), s->d_stat + ST_BAD + f, d.slot_base, 1);
-            VS_HIP(ctx, hipGetLastError());
-            d.members_dev += nm;
-        }
-    } else if (sl.len) {
-        VS_HIP(ctx, hipMemcpyAsync(d.win[d.cur].as<uint8_t>() + d.size, sl.buf.as<uint8_t>(), sl.len, hipMemcpyHostToDevice, s->st));
-    }
-    d.size += sl.text;
+                       (unsigned long long)(d.w.size + sl.text));
+    if (sl.comp) d.slot_base = (uint32_t)d.w.members;
+    if (int rc = d.w.append(ctx, s->st, sl, s->d_stat + ST_BAD + f, d.slot_base)) return rc;
     d.eof = sl.last;
     return VS_OK;
 }
 
 // the next slot of file f appended to its window (blocks until the reader has one)
-int append_chunk(vs_ctx *ctx, vs_fastq_stream *s, int f, Slot *&taken) {
-    Slot &sl = s->rd[f].take();
-    taken = &sl;
-    return append_slot(ctx, s, f, sl);
+int append_chunk(vs_ctx *ctx, vs_fastq_stream *s, int f, SlotLease &taken) {
+    taken = SlotLease(s->rd[f]);
+    return append_slot(ctx, s, f, *taken);
 }
 
 // One BGZF member (its payload at pay) as a plain gzip member through zlib: true when zlib accepts it; else *code = what
@@ -549,9 +516,9 @@ bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
         d.err_msg = s->rd[f].path + ": the device reported a BGZF member that is not of the slot it inflated";
         return true;
     }
-    const vs_bgzf_member mb = ((const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()))[-(ptrdiff_t)(idx + 1u)];
+    const vs_bgzf_member mb = slot_member(sl, idx);
     uint32_t dev_status = 0;
-    (void)hipMemcpy(&dev_status, d.mstat.as<uint32_t>() + idx, sizeof dev_status, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&dev_status, d.w.mstat.as<uint32_t>() + idx, sizeof dev_status, hipMemcpyDeviceToHost);
     int rc = Z_DATA_ERROR;
     if (zlib_accepts(sl.buf.as<uint8_t>() + mb.in_off, mb, &rc)) {
         snprintf(msg, sizeof msg, "%s: BGZF member %llu was rejected on the device (status %u) but zlib accepts it", s->rd[f].path.c_str(),
@@ -569,12 +536,7 @@ bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
 // the window after its first `cut` bytes (the records of the block) have gone: the leftover to the front of the other buffer
 int drop_front(vs_ctx *ctx, vs_fastq_stream *s, int f, size_t cut, uint64_t records) {
     DevFile &d = s->df[f];
-    const size_t rest = d.size - cut;
-    const int o = d.cur ^ 1;
-    if (int rc = reserve_n<uint8_t>(ctx, d.win[o], ((rest + 15u) & ~(size_t)15u) + 16u)) return rc;
-    if (rest) VS_HIP(ctx, hipMemcpyAsync(d.win[o].as<uint8_t>(), d.win[d.cur].as<uint8_t>() + cut, rest, hipMemcpyDeviceToDevice, s->st));
-    d.cur = o;
-    d.size = rest;
+    if (int rc = d.w.keep_from(ctx, s->st, cut)) return rc;
     d.validated = d.validated > cut ? d.validated - cut : 0;
     d.records -= records;
     d.first_record += records;
@@ -588,13 +550,13 @@ int skip_lines(vs_ctx *ctx, vs_fastq_stream *s, int f) {
     DevFile &d = s->df[f];
     if (d.n_nl < d.skip) return vs_fail(ctx, VS_E_STATE, "%s: fewer lines at the front of its member range than were counted", s->rd[f].path.c_str());
     if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return rc;
-    const uint64_t words = (d.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
-    hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, s->st, d.win[d.cur].as<const uint8_t>(), (uint64_t)d.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
+    const uint64_t words = (d.w.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
+    hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, s->st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
     VS_HIP(ctx, hipGetLastError());
     uint32_t at = 0;
     VS_HIP(ctx, hipMemcpyAsync(&at, d.ends.as<uint32_t>() + (d.skip - 1u), sizeof at, hipMemcpyDeviceToHost, s->st));
     VS_HIP(ctx, hipStreamSynchronize(s->st));
-    if ((size_t)at + 1u > d.size) return vs_fail(ctx, VS_E_STATE, "%s: a line end beyond the window", s->rd[f].path.c_str());
+    if ((size_t)at + 1u > d.w.size) return vs_fail(ctx, VS_E_STATE, "%s: a line end beyond the window", s->rd[f].path.c_str());
     d.skip = 0;
     return drop_front(ctx, s, f, (size_t)at + 1u, 0);
 }
@@ -603,30 +565,21 @@ int skip_lines(vs_ctx *ctx, vs_fastq_stream *s, int f) {
 int stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, const uint64_t *range, uint64_t n_pairs, vs_fastq_stream **out) {
     *out = nullptr;
     VS_HIP(ctx, hipSetDevice(ctx->device));
-    size_t chunk = STREAM_CHUNK_BYTES;
-    if (const char *ev = getenv("VS_STREAM_CHUNK")) chunk = std::max<size_t>(1u, (size_t)atoll(ev));  // (tests: records across chunks)
     vs_fastq_stream *s = new vs_fastq_stream();
     s->device = ctx->device;
     const char *paths[2] = {fwd_path, rve_path};
     for (int f = 0; f < 2; f++) {
         Reader &r = s->rd[f];
-        r.path = paths[f];
-        r.chunk = chunk;
-        r.device = ctx->device;
         if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
-        r.fd = open(paths[f], O_RDONLY);
-        int e = errno;
+        int rc = r.open_file(ctx, paths[f]);
         struct stat sb;
-        if (r.fd >= 0 && range && (fstat(r.fd, &sb) != 0 || !S_ISREG(sb.st_mode) || range[3 * f] > range[3 * f + 1] || range[3 * f + 1] > (uint64_t)sb.st_size)) {
-            close(r.fd);
-            r.fd = -1;
-            e = EINVAL;  // (a member range is a range of a regular file that holds it)
-        }
-        if (r.fd < 0) {
+        if (rc == VS_OK && range && (fstat(r.fd, &sb) != 0 || !S_ISREG(sb.st_mode) || range[3 * f] > range[3 * f + 1] || range[3 * f + 1] > (uint64_t)sb.st_size))
+            rc = r.cannot_open(ctx, EINVAL);  // (a member range is a range of a regular file that holds it)
+        if (rc != VS_OK) {
             for (int g = 0; g < f; g++) close(s->rd[g].fd);
             for (int g = 0; g < 2; g++) s->rd[g].fd = -1;
             delete s;
-            return vs_fail(ctx, VS_E_ARG, "cannot open %s: %s", paths[f], strerror(e));
+            return rc;
         }
         if (range) {
             r.begin = range[3 * f];
@@ -683,33 +636,22 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     for (int round = 0;; round++) {
         // more text for the file that holds fewer complete records (both at the start): a window holds what is left of the
         // last block + one chunk, so its size stays bounded whatever the two files' record lengths
-        Slot *taken[2] = {nullptr, nullptr};
-        bool appended = false;
+        SlotLease taken[2];  // (a failure gives them back)
+        bool fresh[2] = {false, false};
         for (int f = 0; f < 2; f++) {
             DevFile &d = s->df[f], &o = s->df[f ^ 1];
             const bool need = !d.eof && d.records < max_pairs && d.records <= o.records && !(o.eof && o.records <= d.records);
             if (!need) continue;
-            if (int rc = append_chunk(ctx, s, f, taken[f])) {
-                const std::string msg = vs_last_error(ctx);
-                for (int g = 0; g <= f; g++)
-                    if (taken[g]) s->rd[g].give_back();
-                return stream_fail(ctx, s, rc, msg);
-            }
-            appended = true;
+            if (int rc = append_chunk(ctx, s, f, taken[f])) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+            fresh[f] = true;
         }
-        if (round > 0 && !appended) return finish(ctx, s);  // (nothing more to read and no pair: the end)
+        if (round > 0 && !fresh[0] && !fresh[1]) return finish(ctx, s);  // (nothing more to read and no pair: the end)
         int rc = scan_windows(ctx, s);
-        if (rc) {
-            const std::string msg = vs_last_error(ctx);
-            for (int f = 0; f < 2; f++)
-                if (taken[f]) s->rd[f].give_back();
-            return stream_fail(ctx, s, rc, msg);
-        }
+        if (rc) return stream_fail(ctx, s, rc, vs_last_error(ctx));
         bool rejected = false;
         for (int f = 0; f < 2; f++)
-            if (taken[f] && member_failed(ctx, s, f, *taken[f])) rejected = true;  // (needs the slot: before it goes back)
-        for (int f = 0; f < 2; f++)
-            if (taken[f]) s->rd[f].give_back();  // (the stream is synchronised: the upload is done)
+            if (fresh[f] && member_failed(ctx, s, f, *taken[f])) rejected = true;  // (needs the slot: before it goes back)
+        for (int f = 0; f < 2; f++) taken[f].give_back();  // (the stream is synchronised: the upload is done)
         if (rejected) return finish(ctx, s);
         if (s->ranged) {
             // (pass 1 of the sharded open saw neither a '\r' nor a byte >= 0x80 in the whole file, and the plan rests on that)
@@ -717,7 +659,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
                 return stream_fail(ctx, s, VS_E_STATE, s->rd[s->df[0].flags ? 0 : 1].path + " changed after its lines were counted");
             bool skipped = false;
             for (int f = 0; f < 2; f++) {
-                if (!s->df[f].skip || !taken[f]) continue;  // (the first window of the file; it may arrive a round after the other's)
+                if (!s->df[f].skip || !fresh[f]) continue;  // (the first window of the file; it may arrive a round after the other's)
                 if ((rc = skip_lines(ctx, s, f))) return stream_fail(ctx, s, rc, vs_last_error(ctx));
                 skipped = true;
             }
@@ -726,7 +668,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
         bool again = false;
         for (int f = 0; f < 2; f++) {
             DevFile &d = s->df[f];
-            if (taken[f] && d.flags && d.validated < d.size) {  // (text that arrived with this chunk: host text mode)
+            if (fresh[f] && d.flags && d.validated < d.w.size) {  // (text that arrived with this chunk: host text mode)
                 if (translate_window(ctx, s, f) != VS_OK) return finish(ctx, s);
                 again = true;
             }
@@ -742,12 +684,12 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     for (int f = 0; f < 2; f++) {
         DevFile &d = s->df[f];
         if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
-        const uint64_t words = (d.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
-        if (wgs) hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, d.win[d.cur].as<const uint8_t>(), (uint64_t)d.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
+        const uint64_t words = (d.w.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
+        if (wgs) hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
     }
     if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
-    SlWin w0 = {s->df[0].win[s->df[0].cur].as<uint8_t>(), s->df[0].ends.as<uint32_t>(), s->df[0].n_nl, (uint32_t)s->df[0].size};
-    SlWin w1 = {s->df[1].win[s->df[1].cur].as<uint8_t>(), s->df[1].ends.as<uint32_t>(), s->df[1].n_nl, (uint32_t)s->df[1].size};
+    SlWin w0 = {s->df[0].w.data(), s->df[0].ends.as<uint32_t>(), s->df[0].n_nl, (uint32_t)s->df[0].w.size};
+    SlWin w1 = {s->df[1].w.data(), s->df[1].ends.as<uint32_t>(), s->df[1].n_nl, (uint32_t)s->df[1].w.size};
     vs_reads *r = new vs_reads();
     r->cached = true;
     // (a failure of the block: it goes back, and the stream has failed)
@@ -813,7 +755,7 @@ void vs_fastq_stream_close(vs_fastq_stream *s) {
 int vs_fastq_stream_inflate_info(const vs_fastq_stream *s, uint64_t info[4]) {
     if (!s || !info) return VS_E_ARG;
     for (int f = 0; f < 2; f++) {
-        info[2 * f + 0] = s->df[f].members_dev;
+        info[2 * f + 0] = s->df[f].w.members;
         info[2 * f + 1] = s->rd[f].members_host;
     }
     return VS_OK;
@@ -838,16 +780,11 @@ int vs_bgzf_walk_file(const char *path, uint64_t *offsets, uint64_t cap, uint64_
         size_t have = 0, hsize = 0, msize = 0;
         for (size_t want = 64;;) {  // (bgzip's header is 18 bytes; a longer extra field is read to its end, 12 + XLEN, and no further)
             want = (size_t)std::min<uint64_t>(want, size - at);
-            while (have < want) {
-                const ssize_t got = pread(fd, head.data() + have, want - have, (off_t)(at + have));
-                if (got < 0 && errno == EINTR) continue;
-                if (got <= 0) {
-                    const int e = errno;
-                    close(fd);
-                    return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, got < 0 ? strerror(e) : "it shrank while it was read");
-                }
-                have += (size_t)got;
+            if (const char *why = pread_all(fd, head.data() + have, want - have, at + have)) {
+                close(fd);
+                return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, why);
             }
+            have = want;
             state = vs_bgzf_header(head.data(), have, &hsize, &msize);
             const size_t whole = have >= 12 ? 12u + ((size_t)head[10] | ((size_t)head[11] << 8)) : 12u;
             if (state != 1 || whole <= have || at + have == size) break;
@@ -856,13 +793,9 @@ int vs_bgzf_walk_file(const char *path, uint64_t *offsets, uint64_t cap, uint64_
         if (state == 0 && at + msize > size) state = 1;  // cut off by the end of the file
         if (state == 0) {
             uint8_t t[4];
-            ssize_t got;
-            do got = pread(fd, t, 4, (off_t)(at + msize - 4));
-            while (got < 0 && errno == EINTR);
-            if (got != 4) {
-                const int e = errno;
+            if (const char *why = pread_all(fd, t, 4, at + msize - 4)) {
                 close(fd);
-                return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, got < 0 ? strerror(e) : "it shrank while it was read");
+                return vs_fail(nullptr, VS_E_ARG, "cannot read %s: %s", path, why);
             }
             const uint32_t isize = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
             if (isize > 65536u) state = 2;
@@ -917,12 +850,7 @@ int vs_bgzf_count_lines(vs_ctx *ctx, const char *path, const uint64_t *offsets, 
             bytes = (size_t)(offsets[upto] - offsets[next]);
             VS_HIP(ctx, pin[k].reserve(BATCH));
             uint8_t *buf = pin[k].as<uint8_t>();
-            for (size_t have = 0; have < bytes;) {
-                const ssize_t got = pread(file.fd, buf + have, bytes - have, (off_t)(offsets[next] + have));
-                if (got < 0 && errno == EINTR) continue;
-                if (got <= 0) return vs_fail(ctx, VS_E_ARG, "cannot read %s: %s", path, got < 0 ? strerror(errno) : "it shrank while it was read");
-                have += (size_t)got;
-            }
+            if (const char *why = pread_all(file.fd, buf, bytes, offsets[next])) return vs_fail(ctx, VS_E_ARG, "cannot read %s: %s", path, why);
             for (uint64_t i = next; i < upto; i++) {
                 vs_bgzf_member mb;
                 size_t msize = 0;

@@ -36,6 +36,21 @@ struct Slot {
     uint32_t n_members = 0;
     size_t text = 0;          // what the members inflate to (the ISIZE sum)
 };
+// member i of a BGZF slot (its directory grows down from the slot's end)
+inline const vs_bgzf_member &slot_member(const Slot &sl, uint32_t i) {
+    return ((const vs_bgzf_member *)(sl.buf.as<uint8_t>() + sl.buf.capacity()))[-(ptrdiff_t)(i + 1u)];
+}
+
+// n bytes of fd from offset off (EINTR retried): nullptr, or why not -- for "cannot read %s: %s"
+inline const char *pread_all(int fd, void *dst, size_t n, uint64_t off) {
+    for (size_t have = 0; have < n;) {
+        const ssize_t got = pread(fd, (uint8_t *)dst + have, n - have, (off_t)(off + have));
+        if (got < 0 && errno == EINTR) continue;
+        if (got <= 0) return got < 0 ? strerror(errno) : "it shrank while it was read";
+        have += (size_t)got;
+    }
+    return nullptr;
+}
 
 // One file read front to back by a thread of its own into the ring.  The consumer takes filled slots in order and gives
 // them back once their bytes are on the device.
@@ -56,6 +71,19 @@ struct Reader {
     std::condition_variable cv;
     std::thread th;
 
+    // the file opened for a reader on the context's device (VS_STREAM_CHUNK: tests, records across chunks)
+    int open_file(vs_ctx *ctx, const char *p) {
+        path = p;
+        device = ctx->device;
+        if (const char *ev = getenv("VS_STREAM_CHUNK")) chunk = std::max<size_t>(1u, (size_t)atoll(ev));
+        fd = open(p, O_RDONLY);
+        return fd < 0 ? cannot_open(ctx, errno) : VS_OK;
+    }
+    int cannot_open(vs_ctx *ctx, int e) {
+        if (fd >= 0) close(fd);
+        fd = -1;
+        return vs_fail(ctx, VS_E_ARG, "cannot open %s: %s", path.c_str(), strerror(e));
+    }
     int fail(int code, const char *fmt, const char *a, const char *b = "") {
         char buf[512];
         snprintf(buf, sizeof buf, fmt, a, b);
@@ -278,6 +306,34 @@ struct Reader {
         if (fd >= 0) close(fd);
         fd = -1;
     }
+};
+
+// A taken slot: the reader's next filled slot (the constructor blocks until there is one), given back when the lease ends or
+// is moved over -- by then the holder has seen to it that the slot's bytes are on the device.
+struct SlotLease {
+    SlotLease() = default;
+    explicit SlotLease(Reader &r) : rd(&r), slot(&r.take()) {}
+    SlotLease(SlotLease &&o) noexcept : rd(o.rd), slot(o.slot) { o.rd = nullptr, o.slot = nullptr; }
+    SlotLease &operator=(SlotLease &&o) noexcept {
+        if (this != &o) {
+            give_back();
+            rd = o.rd, slot = o.slot;
+            o.rd = nullptr, o.slot = nullptr;
+        }
+        return *this;
+    }
+    ~SlotLease() { give_back(); }
+    void give_back() {
+        if (rd) rd->give_back();
+        rd = nullptr, slot = nullptr;
+    }
+    explicit operator bool() const { return slot != nullptr; }
+    const Slot &operator*() const { return *slot; }
+    const Slot *operator->() const { return slot; }
+
+private:
+    Reader *rd = nullptr;
+    Slot *slot = nullptr;
 };
 
 // room for `need` elements of T, a quarter more when the buffer has to grow (what it held is not kept)
