@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define VS_ABI_VERSION 10
+#define VS_ABI_VERSION 11
 
 enum {
     VS_OK = 0,
@@ -548,6 +548,23 @@ int vs_pe_count_lists(vs_ctx *ctx, uint32_t n_nodes, uint64_t n_pairs, const uin
                       uint32_t *d_node_mat, uint32_t *d_short_mat, uint8_t *d_tile_map);
 uint32_t vs_pe_lists_ept(vs_ctx *ctx);
 int vs_pe_last_order(vs_ctx *ctx, uint32_t *keys, uint32_t *perm, uint64_t cap, uint64_t info[2]);
+
+/* Testing aid (ABI 11): the two exclusive scans under the index build, the locus sort, every row_ptr and every member,
+ * record and word offset, run alone on values the caller made up, launched exactly as their callers launch them (no kernel
+ * of its own).  HOST pointers: in[n + guard] = the n values and behind them `guard` words of a sentinel the caller chose;
+ * out[n + guard] = the device buffer the scan wrote, whole: out[i] = in[0] + .. + in[i - 1] mod 2^32 for i < n, and the
+ * sentinel words as they were handed in unless the scan wrote past its end.
+ *   which = 0 : the three-launch scan of any length (2 048 values per workgroup, the block sums walked 256 at a time), its
+ *               scratch sized ceil(n / 2048) + 1 words as its callers size it.  flags bit 0: in place (out == in on the
+ *               device); otherwise the first n words of the device's out hold 0xA5A5A5A5 before the scan.  flags bit 1:
+ *               the scan gets no place for its total, and *total (may be NULL then) is left as it was; otherwise *total =
+ *               the exact 64-bit sum, 0 for n = 0.
+ *   which = 1 : the one-workgroup scan of the streamed ingests (1 024 threads, a slice of ceil(n / 1024) values each):
+ *               always in place, n < 2^32, flags bit 1 is VS_E_ARG; *total = the sum mod 2^32 (its callers' totals stay
+ *               below 2^32).
+ * The device's word for the total holds all ones before either scan. */
+int vs_scan_check(vs_ctx *ctx, int which, const uint32_t *in, uint64_t n, int flags, uint32_t *out, uint64_t guard,
+                  uint64_t *total);
 
 /* ---- graph stages: K5 PE-link table ---------------------------------------------------------
  * Replaces process_pe_info (utils/VStrains_IO.py:598-627) and every later read or rewrite of the

@@ -246,3 +246,43 @@ int vs_scan_u32(vs_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint
     VS_HIP(ctx, hipGetLastError());
     return VS_OK;
 }
+
+// Test aid: either exclusive scan on host values, launched as its callers launch it.  in / out: n + guard words each; the
+// guard words of `in` come back behind the scanned ones unless a scan wrote past its end.
+extern "C" int vs_scan_check(vs_ctx *ctx, int which, const uint32_t *in, uint64_t n, int flags, uint32_t *out, uint64_t guard, uint64_t *total) {
+    if (!ctx || (which != 0 && which != 1) || (flags & ~3) || (!in && n + guard) || (!out && n + guard) || (!total && !(flags & 2)) ||
+        (which == 1 && ((n >> 32) || (flags & 2))) || n + guard > (1ull << 34))
+        return vs_fail(ctx, VS_E_ARG, "vs_scan_check: bad argument");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t bytes = sizeof(uint32_t) * (n + guard);
+    const bool in_place = which == 1 || (flags & 1);
+    VsDevBuf in_buf, out_buf, tmp_buf, total_buf;
+    VS_HIP(ctx, in_buf.reserve(bytes + 16u));
+    VS_HIP(ctx, total_buf.reserve(sizeof(uint64_t)));
+    uint32_t *d_in = in_buf.as<uint32_t>(), *d_out = d_in;
+    uint64_t *d_total = total_buf.as<uint64_t>();
+    if (bytes) VS_HIP(ctx, hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, st));
+    if (!in_place) {  // (a cell the scan leaves out keeps 0xA5A5A5A5)
+        VS_HIP(ctx, out_buf.reserve(bytes + 16u));
+        d_out = out_buf.as<uint32_t>();
+        if (n) VS_HIP(ctx, hipMemsetAsync(d_out, 0xA5, sizeof(uint32_t) * n, st));
+        if (guard) VS_HIP(ctx, hipMemcpyAsync(d_out + n, in + n, sizeof(uint32_t) * guard, hipMemcpyHostToDevice, st));
+    }
+    VS_HIP(ctx, hipMemsetAsync(d_total, 0xFF, sizeof(uint64_t), st));  // (a total nobody writes reads back as all ones)
+    if (which == 0) {
+        const uint64_t nb = (n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;
+        VS_HIP(ctx, tmp_buf.reserve(sizeof(uint64_t) * (nb + 1u)));
+        if (int rc = vs_scan_u32(ctx, d_in, d_out, n, tmp_buf.as<uint64_t>(), (flags & 2) ? nullptr : d_total)) return rc;
+    } else {
+        vs_launch_scan_u32(st, d_in, (uint32_t)n, (uint32_t *)d_total);
+        VS_HIP(ctx, hipGetLastError());
+    }
+    uint64_t h_total = 0;
+    if (bytes) VS_HIP(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipMemcpyAsync(&h_total, d_total, sizeof h_total, hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
+    if (which == 1) *total = (uint32_t)h_total;
+    else if (!(flags & 2)) *total = h_total;
+    return VS_OK;
+}

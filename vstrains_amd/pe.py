@@ -1024,6 +1024,19 @@ class Context:
         nat.check(self._h, nat.lib().vs_fastq_scan_text(self._h, buf.ctypes.data, len(text), line0, ends.ctypes.data, ends.size, info))
         return ends[: int(info[0])].copy(), int(info[1]), int(info[2])
 
+    def scan_check(self, which: int, values, sentinel, flags: int = 0, total_before: int = 0):
+        """One of the library's exclusive scans on ``values`` (a test aid, ``vs_scan_check``): ``which`` 0 the three-launch
+        scan (``flags`` 1 in place, 2 without a place for its total), 1 the one-workgroup scan of the streamed ingests.
+        ``sentinel``: the words behind the values on the device.  -> (the scanned words, the words behind them afterwards,
+        the total; ``total_before`` where the scan was given no place for one)."""
+        values = np.asarray(values, dtype=np.uint32)
+        buf = np.concatenate([values, np.asarray(sentinel, dtype=np.uint32)])
+        out = np.zeros(max(buf.size, 1), dtype=np.uint32)
+        total = C.c_uint64(total_before)
+        nat.check(self._h, nat.lib().vs_scan_check(self._h, which, buf.ctypes.data if buf.size else None, values.size, flags,
+                                                   out.ctypes.data if buf.size else None, buf.size - values.size, C.byref(total)))
+        return out[: values.size], out[values.size: buf.size], int(total.value)
+
     def pack(self, ascii_bytes: np.ndarray, off: np.ndarray) -> ReadBlock:
         ascii_bytes = np.ascontiguousarray(ascii_bytes, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
