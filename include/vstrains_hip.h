@@ -200,6 +200,36 @@ int vs_inflate_bgzf(vs_ctx *ctx, const uint8_t *data, uint64_t n, uint8_t *out, 
                     uint64_t status_cap, uint64_t info[2]);
 int vs_fastq_stream_inflate_info(const vs_fastq_stream *s, uint64_t info[4]);
 
+/* ---- plain gzip on the device: one deflate stream decoded by many wavefronts (vs_gzip.hip, vs_gzip_core.h) -------
+ * A gzip file that is not BGZF has no member directory.  Its blocks are found speculatively (every bit offset is tested for
+ * the header of a non-final dynamic block), runs are decoded from the selected starts into 16-bit symbols that name bytes
+ * of the unknown 32 KiB in front of a run, the runs that the known first block's run reaches ("the chain") hand their
+ * histories down, and the symbols are resolved into bytes; CRC32 and ISIZE of every member are checked.
+ *   vs_gzip_inflate      : test aid.  data[0, n) (n <= 256 MiB), a whole gzip file of one or more members, through the
+ *                          kernels.  gran = compressed bytes per selected start (>= 16), 0 = every candidate.  The text to
+ *                          out[0, info[7]), followed by `guard` bytes that keep the value 0xA5 (out == NULL: the sizes
+ *                          only); nothing is written when the status is not 0.  info[0] = candidates (offsets that passed
+ *                          the full header check, of those the search looked at), [1] = selected starts, [2] = chain runs,
+ *                          [3] = runs dropped, [4] = members, [5] = status, 0 or the first thing wrong: the words of
+ *                          vs_inflate_host, 15 no gzip member header, 16 ISIZE mismatch, [6] = the failing run's place
+ *                          in the chain, [7] = bytes of text, [8] = chain runs counted a second time: a counted run other than the
+ *                          first may read 64 finder spans of input (64 KiB at least) and is then given up (17); if the chain
+ *                          reaches such a run it is counted again without the bound
+ *   vs_gzip_inflate_host : host only.  The same routines with one lane, step for step; out and info as above, no guard
+ *   vs_fastq_stream_gzip_info : with VS_GZIP_DEVICE=1 in the environment at vs_fastq_stream_open, a file that starts with
+ *                          the gzip magic and whose first member is not BGZF is not inflated by zlib: its bytes go to the
+ *                          device slot by slot and through the kernels above, one start per 16 KiB of compressed bytes; what
+ *                          cannot finish inside a slot (the compressed bytes of the open run, its bit offset, the last
+ *                          32 KiB of text, the open member's CRC32 and length) is carried to the next.  info[4f + 0] =
+ *                          windows of file f decoded so, [4f + 1] = chain runs, [4f + 2] = runs dropped, [4f + 3] = members.
+ *                          Such members count neither in members_device nor in members_host of
+ *                          vs_fastq_stream_inflate_info.  A stream the device refuses fails as the zlib loop fails: VS_E_ARG,
+ *                          "<path>: not a complete gzip stream (zlib code <c>)" for a regular file, which zlib reads again
+ *                          for the code; a pipe gets "(device status <NAME>)" in its place */
+int vs_gzip_inflate(vs_ctx *ctx, const uint8_t *data, uint64_t n, uint32_t gran, uint8_t *out, uint64_t out_cap, uint32_t guard, uint64_t info[9]);
+int vs_gzip_inflate_host(const uint8_t *data, uint64_t n, uint32_t gran, uint8_t *out, uint64_t out_cap, uint64_t info[9]);
+int vs_fastq_stream_gzip_info(const vs_fastq_stream *s, uint64_t info[8]);
+
 /* BGZF written on the device (additions to ABI 10): the other half of the above.  A text is cut into members of at most
  * 0xFF00 bytes (bgzip's cut) and every member is made by ONE wavefront (k_deflate, vs_deflate.hip) through the encoder of
  * csrc/vs_deflate_core.h, which the host runs from the same text with one lane: the bytes are the same, for every text.

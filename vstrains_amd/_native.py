@@ -52,6 +52,9 @@ SYMBOLS = {
     "vs_inflate_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
                                   C.POINTER(C.c_uint64)]),
     "vs_fastq_stream_inflate_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "vs_gzip_inflate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "vs_gzip_inflate_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vs_fastq_stream_gzip_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "vs_deflate_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "vs_deflate_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     "vs_bgzf_walk_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -60,6 +60,9 @@ def build_parser():
                    help="extension: -fwd and -rve name ONE BAM in any record order (coordinate-sorted, `samtools view -f 12` of a "
                         "sorted alignment, ...); the mates are matched by read name on the device and records without a mate are "
                         "dropped, no `samtools collate` first (not together with --pe-text-from)")
+    p.add_argument("--gzip-device", dest="gzip_device", action="store_true", default=False,
+                   help="extension: decode plain .fastq.gz (one deflate stream, as gzip and pigz write it) on the device, in parallel "
+                        "from speculative block starts, instead of with zlib on one host core (sets VS_GZIP_DEVICE=1; one process only)")
     return p
 
 
@@ -83,6 +86,8 @@ def _bail(*lines):
 def main(argv=None, backend=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.gzip_device:
+        os.environ["VS_GZIP_DEVICE"] = "1"  # (the library reads the switch where it reads VS_BGZF_DEVICE)
     if args.no_pe_text and args.sparse_pe_text:
         parser.error("--no-pe-text and --sparse-pe-text are mutually exclusive")
     if args.no_pe_text and args.bgzf_pe_text:

@@ -18,6 +18,15 @@
 // of it -- which also words the failure for what is no gzip at all.  A member the device rejected is inflated again with
 // zlib on the host for the code of that message; should zlib accept it, that is VS_E_STATE, never a silent continuation.
 //
+// PLAIN GZIP ON THE DEVICE (VS_GZIP_DEVICE=1, off by default): a file that starts with the gzip magic and whose first member
+// is not BGZF is one deflate stream, or a few, without a directory.  The reader then makes no zlib call: its slots carry the
+// file's bytes as they are (Slot::gz), and DevWindow::append_gzip decodes them behind the window in parallel -- block starts
+// found speculatively, runs counted, chained and decoded into symbols, histories handed down, symbols resolved, every
+// member's CRC32 and ISIZE checked (vs_gzip.hip, vs_gzip_core.h); what cannot finish inside a slot is carried to the next.
+// A slot may add no text at all (it ended inside the first run): the round loop then simply takes the next one.  A stream
+// the device refuses fails the file in the words of the zlib loop: gzip_failed reads a regular file again with zlib for the
+// code; a pipe's message names the device's status instead.
+//
 // Device: every file has a window = the bytes left over from the last block (they start at a record boundary) + the
 // chunks appended since.  Per step, for each window:
 //   k_sl_count    one lane per 16-byte word: newlines per workgroup, flags for '\r' and bytes >= 0x80, the last byte;
@@ -395,6 +404,8 @@ bool check_piece(DevFile &d, const uint8_t *p, size_t n, bool last) {
 }
 
 int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl);
+void gzip_failed(vs_fastq_stream *s, int f);
+int append_gzip(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot *sl);
 bool zlib_accepts(const uint8_t *pay, const vs_bgzf_member &mb, int *code);
 bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl);
 
@@ -414,10 +425,27 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
         }
         d.validated = d.w.size;
         while (!d.eof) {
+            if (d.err == VS_OK && d.w.gz.more) {  // held-back gzip runs: a round on them, no slot
+                d.w.size = 0;
+                int rc = append_gzip(ctx, s, f, nullptr);
+                if (rc == VS_OK) rc = scan_windows(ctx, s, f);
+                if (rc != VS_OK) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+                if (d.err == VS_OK && ((d.flags & FL_HIGH) || d.n_pend)) {
+                    std::vector<uint8_t> buf(d.w.size);
+                    if (d.w.size && hipMemcpy(buf.data(), d.w.data(), d.w.size, hipMemcpyDeviceToHost) != hipSuccess)
+                        return stream_fail(ctx, s, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
+                    if (!check_piece(d, buf.data(), buf.size(), d.eof)) {
+                        d.err = VS_E_UTF8;
+                        d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
+                    }
+                }
+                d.w.size = d.validated = 0;
+                continue;
+            }
             const SlotLease lease(r);  // (goes back at the end of the round, or with a failure)
             const Slot &sl = *lease;
             bool ok = true;
-            if (d.err == VS_OK && sl.comp) {
+            if (d.err == VS_OK && (sl.comp || sl.gz)) {
                 // no text on the host: the members are inflated (and their CRCs checked) on the device like any others, and
                 // the text comes back only when the scan saw a byte >= 0x80 (or a character is still open)
                 d.w.size = 0;
@@ -426,11 +454,11 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
                 if (rc != VS_OK) {
                     return stream_fail(ctx, s, rc, vs_last_error(ctx));
                 }
-                if (!member_failed(ctx, s, f, sl) && ((d.flags & FL_HIGH) || d.n_pend)) {
+                if (!member_failed(ctx, s, f, sl) && d.err == VS_OK && ((d.flags & FL_HIGH) || d.n_pend)) {
                     std::vector<uint8_t> buf(d.w.size);
                     if (d.w.size && hipMemcpy(buf.data(), d.w.data(), d.w.size, hipMemcpyDeviceToHost) != hipSuccess)
                         return stream_fail(ctx, s, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
-                    ok = check_piece(d, buf.data(), buf.size(), sl.last);
+                    ok = check_piece(d, buf.data(), buf.size(), sl.gz ? d.eof : sl.last);
                 }
                 d.w.size = d.validated = 0;
             } else if (d.err == VS_OK) {
@@ -440,7 +468,7 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
                 d.err = VS_E_UTF8;
                 d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
             }
-            d.eof = sl.last;
+            d.eof = sl.last && !(d.err == VS_OK && d.w.gz.more);
         }
         if (d.err == VS_OK && d.n_pend) {  // (a character cut off by the end of the file)
             d.err = VS_E_UTF8;
@@ -457,6 +485,62 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
     return VS_OK;
 }
 
+// The device refused the plain gzip stream of file f (DevWindow::gz_status).  A regular file is read again through zlib, for
+// the code in the words of the reader's zlib loop; a pipe cannot be read twice, its message names the device's status.
+void gzip_failed(vs_fastq_stream *s, int f) {
+    DevFile &d = s->df[f];
+    const std::string &path = s->rd[f].path;
+    char msg[700];
+    struct stat sb;
+    d.err = VS_E_ARG;
+    if (fstat(s->rd[f].fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        snprintf(msg, sizeof msg, "%s: not a complete gzip stream (device status %s)", path.c_str(), vs_gz_status_name(d.w.gz_status));
+        d.err_msg = msg;
+        return;
+    }
+    int code = Z_OK;  // zlib over the whole file, as the reader's loop runs it
+    {
+        std::vector<uint8_t> in(1u << 20), out(1u << 20);
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        uint64_t at = 0;
+        bool eof = false, done = false;
+        if (inflateInit2(&zs, 15 + 16) != Z_OK) code = Z_MEM_ERROR;
+        while (code == Z_OK && !done) {
+            if (zs.avail_in == 0 && !eof) {
+                const ssize_t got = pread(s->rd[f].fd, in.data(), in.size(), (off_t)at);
+                if (got <= 0) eof = true;
+                else at += (uint64_t)got;
+                zs.next_in = in.data();
+                zs.avail_in = got > 0 ? (uInt)got : 0u;
+            }
+            zs.next_out = out.data();
+            zs.avail_out = (uInt)out.size();
+            int rc = inflate(&zs, Z_NO_FLUSH);
+            if (rc == Z_STREAM_END) {
+                if (zs.avail_in == 0 && !eof) continue;  // (look whether more members follow)
+                if (zs.avail_in == 0 && eof) done = true;
+                else if (inflateReset(&zs) != Z_OK) code = Z_DATA_ERROR;
+                continue;
+            }
+            if (rc == Z_OK || (rc == Z_BUF_ERROR && (zs.avail_out == 0 || (zs.avail_in == 0 && !eof)))) {
+                if (zs.avail_in == 0 && eof && zs.avail_out != 0) code = Z_DATA_ERROR;  // truncated stream
+                continue;
+            }
+            code = rc == Z_BUF_ERROR ? Z_DATA_ERROR : rc;
+        }
+        inflateEnd(&zs);
+    }
+    if (code == Z_OK) {
+        snprintf(msg, sizeof msg, "%s: the gzip stream was rejected on the device (status %s) but zlib accepts it", path.c_str(),
+                 vs_gz_status_name(d.w.gz_status));
+        d.err = VS_E_STATE;
+    } else {
+        snprintf(msg, sizeof msg, "%s: not a complete gzip stream (zlib code %d)", path.c_str(), code);
+    }
+    d.err_msg = msg;
+}
+
 // a slot of file f appended to its window: its text uploaded, or its BGZF members uploaded and inflated there
 int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
     DevFile &d = s->df[f];
@@ -464,13 +548,26 @@ int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
         return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete record", s->rd[f].path.c_str(),
                        (unsigned long long)(d.w.size + sl.text));
     if (sl.comp) d.slot_base = (uint32_t)d.w.members;
+    if (sl.gz) return append_gzip(ctx, s, f, &sl);
     if (int rc = d.w.append(ctx, s->st, sl, s->d_stat + ST_BAD + f, d.slot_base)) return rc;
     d.eof = sl.last;
     return VS_OK;
 }
 
-// the next slot of file f appended to its window (blocks until the reader has one)
+// A slot of a plain gzip file decoded behind the window of file f, or (sl == nullptr, while DevWindow::gz.more) one more
+// round on the compressed bytes that the text cap of the round before held back: no slot is taken for it.
+int append_gzip(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot *sl) {
+    DevFile &d = s->df[f];
+    if (int rc = d.w.append_gzip(ctx, s->st, sl, s->rd[f].path.c_str())) return rc;
+    if (d.w.gz_status && d.err == VS_OK) gzip_failed(s, f);
+    d.eof = d.w.gzip_at_end();
+    return VS_OK;
+}
+
+// the next slot of file f appended to its window (blocks until the reader has one); while held-back gzip runs are pending,
+// those instead, and `taken` stays empty
 int append_chunk(vs_ctx *ctx, vs_fastq_stream *s, int f, SlotLease &taken) {
+    if (s->df[f].w.gz.more) return append_gzip(ctx, s, f, nullptr);
     taken = SlotLease(s->rd[f]);
     return append_slot(ctx, s, f, *taken);
 }
@@ -571,6 +668,8 @@ int stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, const u
     for (int f = 0; f < 2; f++) {
         Reader &r = s->rd[f];
         if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
+        if (const char *ev = getenv("VS_GZIP_DEVICE")) r.gzip_device = !range && strcmp(ev, "1") == 0;  // (a member range is BGZF's)
+        if (const char *ev = getenv("VS_GZIP_TEXT")) s->df[f].w.gz.text_cap = (uint32_t)std::max<long long>(1, atoll(ev));  // (tests only, as VS_STREAM_CHUNK)
         int rc = r.open_file(ctx, paths[f]);
         struct stat sb;
         if (rc == VS_OK && range && (fstat(r.fd, &sb) != 0 || !S_ISREG(sb.st_mode) || range[3 * f] > range[3 * f + 1] || range[3 * f + 1] > (uint64_t)sb.st_size))
@@ -650,7 +749,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
         if (rc) return stream_fail(ctx, s, rc, vs_last_error(ctx));
         bool rejected = false;
         for (int f = 0; f < 2; f++)
-            if (fresh[f] && member_failed(ctx, s, f, *taken[f])) rejected = true;  // (needs the slot: before it goes back)
+            if (fresh[f] && ((taken[f] && member_failed(ctx, s, f, *taken[f])) || s->df[f].err != VS_OK)) rejected = true;  // (needs the slot: before it goes back)
         for (int f = 0; f < 2; f++) taken[f].give_back();  // (the stream is synchronised: the upload is done)
         if (rejected) return finish(ctx, s);
         if (s->ranged) {
@@ -738,7 +837,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
 int vs_fastq_stream_info(const vs_fastq_stream *s, uint64_t info[4]) {
     if (!s || !info) return VS_E_ARG;
     info[0] = s->pairs;
-    info[1] = s->rd[0].text_bytes + s->rd[1].text_bytes;
+    info[1] = s->rd[0].text_bytes + s->rd[1].text_bytes + s->df[0].w.gz.text + s->df[1].w.gz.text;
     info[2] = s->rd[0].raw_bytes + s->rd[1].raw_bytes;
     info[3] = (uint64_t)s->flags_seen | (s->rd[0].gzip ? 4u : 0u) | (s->rd[1].gzip ? 8u : 0u) | (s->done ? 16u : 0u);
     return VS_OK;
@@ -757,6 +856,18 @@ int vs_fastq_stream_inflate_info(const vs_fastq_stream *s, uint64_t info[4]) {
     for (int f = 0; f < 2; f++) {
         info[2 * f + 0] = s->df[f].w.members;
         info[2 * f + 1] = s->rd[f].members_host;
+    }
+    return VS_OK;
+}
+
+int vs_fastq_stream_gzip_info(const vs_fastq_stream *s, uint64_t info[8]) {
+    if (!s || !info) return VS_E_ARG;
+    for (int f = 0; f < 2; f++) {
+        const GzStream &g = s->df[f].w.gz;
+        info[4 * f + 0] = g.windows;
+        info[4 * f + 1] = g.runs;
+        info[4 * f + 2] = g.dropped;
+        info[4 * f + 3] = g.members;
     }
     return VS_OK;
 }

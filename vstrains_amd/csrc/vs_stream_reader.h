@@ -1,6 +1,7 @@
 // The host reader of the streamed ingests (vs_stream.hip: FASTQ; vs_bam.hip: BAM): one file read front to back by a thread of
-// its own into a bounded ring of pinned chunks -- plain bytes, zlib-inflated gzip, or the raw deflate payloads of whole BGZF
-// members with their directory, for the device to inflate (see the top of vs_stream.hip).
+// its own into a bounded ring of pinned chunks -- plain bytes, zlib-inflated gzip, the raw deflate payloads of whole BGZF
+// members with their directory, or (VS_GZIP_DEVICE=1) the bytes of a plain gzip file as they are, for the device to inflate
+// (see the top of vs_stream.hip).
 #pragma once
 #include <errno.h>
 #include <fcntl.h>
@@ -26,13 +27,14 @@ namespace {
 constexpr size_t STREAM_CHUNK_BYTES = 64u << 20;  // one pinned chunk of the ring; VS_STREAM_CHUNK overrides it (tests only)
 constexpr unsigned STREAM_RING_SLOTS = 4;         // chunks per file in the ring
 constexpr size_t STREAM_MAX_WINDOW = 0xFFFFFF00u; // line ends and record starts are 32-bit byte offsets into a window
-enum { M_PLAIN = 0, M_ZLIB = 1, M_BGZF = 2 };
+enum { M_PLAIN = 0, M_ZLIB = 1, M_BGZF = 2, M_GZRAW = 3 };
 
 struct Slot {
     VsPinnedBuf buf;          // slot_cap bytes, pinned by the reader at first use
     size_t len = 0;  // bytes of text, or of deflate payloads when n_members > 0 or comp
     bool last = false;
     bool comp = false;        // payloads of BGZF members + their directory at the slot's end (the last member first)
+    bool gz = false;          // the next bytes of a plain gzip file, not inflated (text = 0: the device finds out)
     uint32_t n_members = 0;
     size_t text = 0;          // what the members inflate to (the ISIZE sum)
 };
@@ -63,7 +65,7 @@ struct Reader {
     bool stop = false, finished = false;
     int err = VS_OK;
     std::string err_msg;
-    bool gzip = false, bgzf = false, bgzf_device = true;
+    bool gzip = false, bgzf = false, bgzf_device = true, gzip_device = false, gz_raw = false;
     size_t slot_cap = STREAM_CHUNK_BYTES;
     uint64_t raw_bytes = 0, text_bytes = 0, members_host = 0;
     uint64_t begin = 0, end = ~0ull;  // the bytes of the file this reader may read (a member range of a sharded open)
@@ -137,12 +139,15 @@ struct Reader {
             size_t msize = 0;
             if (vs_bgzf_parse(in.data(), in_len, &mb, &msize) != 2) mode = M_BGZF;
         }
+        if (mode == M_ZLIB && gzip_device) mode = M_GZRAW;  // (a file whose first member is BGZF keeps the BGZF path)
         bgzf = mode == M_BGZF;
+        gz_raw = mode == M_GZRAW;
         slot_cap = bgzf ? (std::max<size_t>(chunk, 65536u) + 15u) & ~(size_t)15u : chunk;
         size_t in_at = 0;  // (BGZF: bytes of `in` already handed on)
         z_stream zs;
         memset(&zs, 0, sizeof zs);
-        if (gzip && inflateInit2(&zs, 15 + 16) != Z_OK) {
+        const bool zs_open = gzip && mode != M_GZRAW;  // (M_GZRAW makes no zlib call)
+        if (zs_open && inflateInit2(&zs, 15 + 16) != Z_OK) {
             fail(VS_E_OOM, "%s: zlib cannot start", path.c_str());
             publish(0, true);
             return;
@@ -215,7 +220,7 @@ struct Reader {
                 publish(len, at_end, true, nm, text);
                 continue;
             }
-            if (mode == M_PLAIN) {
+            if (mode == M_PLAIN || mode == M_GZRAW) {
                 const size_t now = std::min(chunk, in_len - plain_at);
                 memcpy(dst, in.data() + plain_at, now);
                 plain_at += now;
@@ -267,19 +272,20 @@ struct Reader {
                 }
                 at_end = at_end || bad;
             }
-            text_bytes += len;
-            publish(len, at_end);
+            if (mode != M_GZRAW) text_bytes += len;
+            publish(len, at_end, false, 0, 0, mode == M_GZRAW);
         }
-        if (gzip) inflateEnd(&zs);
+        if (zs_open) inflateEnd(&zs);
     }
-    void publish(size_t len, bool last, bool comp = false, uint32_t n_members = 0, size_t text = 0) {
+    void publish(size_t len, bool last, bool comp = false, uint32_t n_members = 0, size_t text = 0, bool gz = false) {
         std::lock_guard<std::mutex> lk(m);
         Slot &s = slots[filled % STREAM_RING_SLOTS];
         s.len = len;
         s.last = last;
         s.comp = comp;
         s.n_members = n_members;
-        s.text = comp ? text : len;
+        s.gz = gz;
+        s.text = comp ? text : gz ? 0 : len;
         filled++;
         finished = last;
         cv.notify_all();

@@ -16,6 +16,7 @@
 //  * The limit.  size never passes STREAM_MAX_WINDOW (offsets into a window are 32-bit).  The callers check that before they
 //    append and word it for their input; an append beyond it is a programming error here (VS_E_STATE).
 #pragma once
+#include "vs_gzip_stream.h"
 #include "vs_stream_reader.h"
 
 namespace {
@@ -27,6 +28,9 @@ struct DevWindow {
     // BGZF: the device copy of a slot's payloads and directory, a status word per member; members inflated so far
     VsDevBuf comp, dir, mstat;  // bytes, vs_bgzf_member, uint32
     uint64_t members = 0;
+    // plain gzip inflated on the device (VS_GZIP_DEVICE=1): what goes from one window of the file to the next
+    GzStream gz;
+    uint32_t gz_status = 0;  // the status word with which the file's gzip stream failed, 0: it has not
 
     static size_t padded(size_t n) { return ((n + 15u) & ~(size_t)15u) + 16u; }
     uint8_t *data() { return buf[cur].as<uint8_t>(); }
@@ -81,6 +85,29 @@ struct DevWindow {
         size += sl.text;
         return VS_OK;
     }
+    // A slot of a plain gzip file (sl.gz) appended: uploaded, its block starts found, the runs counted and chained, decoded to
+    // symbols, the histories handed down, the symbols resolved to text behind `size` (vs_gz_window); what could not finish
+    // inside the slot is carried.  Synchronises the stream.  A stream that fails leaves its status word in gz_status and the
+    // window as it was; the caller words it.  limit_msg: the path for the message of a window beyond STREAM_MAX_WINDOW.
+    int append_gzip(vs_ctx *ctx, hipStream_t st, const Slot *sl, const char *limit_msg) {
+        const std::function<int(size_t, uint8_t **)> room = [&](size_t text, uint8_t **dst) -> int {
+            if (size + text > STREAM_MAX_WINDOW)
+                return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete record", limit_msg, (unsigned long long)(size + text));
+            if (int rc = make_room(ctx, st, text)) return rc;
+            *dst = data() + size;
+            return VS_OK;
+        };
+        // sl == nullptr: a round on what is pending (gz.more: the cap of the round before held whole runs back)
+        size_t text = 0;
+        if (int rc = vs_gz_window(ctx, st, gz, sl ? sl->buf.as<uint8_t>() : nullptr, sl ? sl->len : 0, sl ? sl->last : gz.last_seen, room, &text, &gz_status))
+            return rc;
+        size += text;
+        if (gz_status) gz.more = false;
+        if (!gz_status && gz.last_seen && !gz.more && !(gz.at_member && gz.pend.empty())) gz_status = 8u;  // INF_E_INPUT: the file ends inside a member
+        return VS_OK;
+    }
+    // the file's end is reached: its last slot has been appended and nothing decodable is pending
+    bool gzip_at_end() const { return gz.last_seen && !gz.more; }
     // Members [a, b) of a BGZF slot whose payloads are uploaded, inflated behind `size` (a forward directory, out_off from 0).
     // Synchronises the stream: the directory of the sub-range is made here and read by the upload.
     int append_members(vs_ctx *ctx, hipStream_t st, const Slot &sl, uint32_t a, uint32_t b, uint32_t *first_bad, uint32_t base) {

@@ -221,7 +221,10 @@ class FastqStream:
     process can read once -- a FIFO, ``/dev/stdin``, ``<(zcat R1.fq.gz)``, a regular or gzip file -- with host memory
     bounded by a ring of pinned chunks; the records are found and packed on the device, and the members of a BGZF file
     (bgzip, htslib) are inflated there too (``info["members_device"]`` / ``["members_host"]`` per file say where; other
-    gzip members go through zlib in the reader thread, ``VS_BGZF_DEVICE=0`` sends all of them there).  Iterating yields ``ReadBlock``s
+    gzip members go through zlib in the reader thread, ``VS_BGZF_DEVICE=0`` sends all of them there; with
+    ``VS_GZIP_DEVICE=1`` a plain gzip file -- one deflate stream, no member directory -- is decoded on the device too, in
+    parallel from speculative block starts: ``info["gzip_device"]`` per file says in how many windows, chain runs, dropped
+    runs and members, and such members count in neither of the other two).  Iterating yields ``ReadBlock``s
     of at most ``block_pairs`` pairs until the input is exhausted; the checks of the whole input (bytes that are not valid
     UTF-8 anywhere, a cut-off gzip stream) raise before the iteration ends, with the exceptions ``FastqPair`` raises.
     ``close()`` as ``FastqPair``."""
@@ -378,8 +381,11 @@ class FastqStream:
         nat.lib().vs_fastq_stream_info(self._h, a)
         m = (C.c_uint64 * 4)()
         nat.lib().vs_fastq_stream_inflate_info(self._h, m)
+        g = (C.c_uint64 * 8)()
+        nat.lib().vs_fastq_stream_gzip_info(self._h, g)
+        gz = tuple(dict(windows=int(g[4 * f]), runs=int(g[4 * f + 1]), dropped=int(g[4 * f + 2]), members=int(g[4 * f + 3])) for f in (0, 1))
         return dict(pairs=int(a[0]), text_bytes=int(a[1]), file_bytes=int(a[2]), flags=int(a[3]),
-                    members_device=(int(m[0]), int(m[2])), members_host=(int(m[1]), int(m[3])))
+                    members_device=(int(m[0]), int(m[2])), members_host=(int(m[1]), int(m[3])), gzip_device=gz)
 
     @property
     def n_pairs(self) -> int:
@@ -821,6 +827,35 @@ def inflate_bgzf(data: bytes, ctx: "Context"):
         res.append((int(status[i]), out[at: at + isize].tobytes(), bool((guard == INFLATE_GUARD_BYTE).all())))
         at += isize + INFLATE_GUARD
     return res
+
+
+GZIP_INFO = ("candidates", "selected", "chain_runs", "dropped", "members", "status", "bad_run", "text", "recounted")
+
+
+def gzip_inflate_host(data: bytes, gran: int = 0):
+    """A whole plain gzip file through the one-lane host form of the parallel decoder (``vs_gzip_inflate_host``):
+    (info as a dict of ``GZIP_INFO``, the text -- empty unless the status is 0).  ``gran``: compressed bytes per selected
+    run start, 0 = every candidate."""
+    src = np.frombuffer(data or b"\0", dtype=np.uint8)
+    info = (C.c_uint64 * 9)()
+    nat.check(None, nat.lib().vs_gzip_inflate_host(src.ctypes.data, len(data), gran, None, 0, info))
+    out = np.zeros(max(int(info[7]), 1), dtype=np.uint8)
+    nat.check(None, nat.lib().vs_gzip_inflate_host(src.ctypes.data, len(data), gran, out.ctypes.data, out.size, info))
+    return dict(zip(GZIP_INFO, (int(x) for x in info))), out[:int(info[7])].tobytes()
+
+
+def gzip_inflate(data: bytes, ctx: "Context", gran: int = 0):
+    """The same through the kernels (``vs_gzip_inflate``): (info, text, whether the guard bytes behind the text are
+    untouched)."""
+    src = np.frombuffer(data or b"\0", dtype=np.uint8)
+    info = (C.c_uint64 * 9)()
+    nat.check(ctx._h, nat.lib().vs_gzip_inflate(ctx._h, src.ctypes.data, len(data), gran, None, 0, INFLATE_GUARD, info))
+    n = int(info[7])
+    out = np.full(n + INFLATE_GUARD, INFLATE_GUARD_BYTE, dtype=np.uint8)
+    nat.check(ctx._h, nat.lib().vs_gzip_inflate(ctx._h, src.ctypes.data, len(data), gran, out.ctypes.data, out.size, INFLATE_GUARD, info))
+    got = int(info[7])
+    assert got <= n
+    return dict(zip(GZIP_INFO, (int(x) for x in info))), out[:got].tobytes(), bool((out[n:] == INFLATE_GUARD_BYTE).all())
 
 
 def encode_seqs(seqs: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:

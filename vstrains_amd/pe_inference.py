@@ -36,6 +36,9 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     stream's ``info`` (``singletons`` among it), else None."""
     rank, world = _rank_world()
     count_links.bam_info = None
+    why = gzip_device_refusal(world)  # (reads the environment only; None with the switch unset)
+    if why is not None:
+        raise ValueError(why)
     bam = bam_input(fwd, rve, world, by_name=bam_by_name, sharded=not bam_by_name)  # (a collated BAM is shared by member)
     streamed = bam is None and use_stream(fwd, rve)
     if world > 1 and not (_regular(fwd) and _regular(rve)):  # (the sharded path maps regular files; VS_FASTQ_STREAM aside)
@@ -224,13 +227,49 @@ def ingest_report(rank, world, path, reason, first_pair, pairs, members, members
                        members_pass1=[int(x) for x in members_pass1], members_pass2=[int(x) for x in members_pass2]), fh)
 
 
+def _starts_gzip(path: str) -> bool:
+    """The first two bytes of a regular file are the gzip magic (a pipe is not read here: it streams whatever it holds)."""
+    try:
+        if not stat.S_ISREG(os.stat(path).st_mode):
+            return False
+        with open(path, "rb") as fh:
+            return fh.read(2) == b"\x1f\x8b"
+    except OSError:
+        return False
+
+
+def gzip_device_refusal(world: int):
+    """None, or why ``VS_GZIP_DEVICE=1`` (``--gzip-device``: plain gzip decoded in parallel on the device, in the streamed
+    ingest) cannot hold: under a process group of more than one rank -- one deflate stream shared among ranks is not built --
+    and together with ``VS_FASTQ_STREAM=0``, which asks for the mapped open."""
+    if os.environ.get("VS_GZIP_DEVICE") != "1":
+        return None
+    if world > 1:
+        return ("VS_GZIP_DEVICE=1 (--gzip-device) decodes a plain gzip file as one stream in one process; sharing one stream among the "
+                "%d ranks of this process group is not built: leave the switch out, or write the reads as BGZF (bgzip), which the "
+                "ranks share by member" % world)
+    if os.environ.get("VS_FASTQ_STREAM") == "0":
+        return ("VS_GZIP_DEVICE=1 (--gzip-device) decodes gzip in the streamed ingest, and VS_FASTQ_STREAM=0 asks for the mapped "
+                "open: set one of the two")
+    return None
+
+
 def use_stream(fwd: str, rve: str) -> bool:
     """The streamed ingest reads the pair when either input is not a regular file (a FIFO, /dev/stdin, a process
     substitution: there is nothing to map), when ``VS_FASTQ_STREAM=1`` asks for it, or when both are regular files and at
     least one starts with a BGZF member (its members are inflated on the device there, where the mapped open inflates the
-    whole file on one host core) unless ``VS_FASTQ_STREAM=0``; other regular files are mapped."""
+    whole file on one host core) unless ``VS_FASTQ_STREAM=0``; other regular files are mapped.  With ``VS_GZIP_DEVICE=1``
+    a regular file that starts with the gzip magic streams too (ValueError where the switch cannot hold:
+    ``gzip_device_refusal``)."""
     env = os.environ.get("VS_FASTQ_STREAM")
+    gzip_device = os.environ.get("VS_GZIP_DEVICE") == "1"
+    if gzip_device:  # (the world size is asked for only with the switch on)
+        why = gzip_device_refusal(_rank_world()[1])
+        if why is not None:
+            raise ValueError(why)
     if env == "1" or not (_regular(fwd) and _regular(rve)):
+        return True
+    if gzip_device and (_starts_gzip(fwd) or _starts_gzip(rve)):
         return True
     return env != "0" and (_starts_bgzf(fwd) or _starts_bgzf(rve))
 
@@ -351,7 +390,13 @@ def main(argv=None):
                         help="extension: -f and -r name ONE BAM in any record order (coordinate-sorted, `samtools view -f 12` of "
                              "a sorted alignment, ...); the mates are matched by read name on the device, records without a mate "
                              "are dropped -- no `samtools collate` first")
+    parser.add_argument("--gzip-device", dest="gzip_device", action="store_true", default=False,
+                        help="extension: decode plain .fastq.gz (one deflate stream, as gzip and pigz write it) on the device, in "
+                             "parallel from speculative block starts, instead of with zlib on one host core (sets VS_GZIP_DEVICE=1; "
+                             "one process only)")
     args = parser.parse_args(argv)
+    if args.gzip_device:
+        os.environ["VS_GZIP_DEVICE"] = "1"  # (the library reads the switch where it reads VS_BGZF_DEVICE)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:  # launched by torchrun: one rank per GPU, counters all-reduced over RCCL
         import torch
