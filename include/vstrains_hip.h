@@ -663,6 +663,14 @@ int vs_links_block_sums(vs_ctx *ctx, const vs_links *links, const uint64_t *list
  * Extension.py:766-799).  Host pointers. */
 int vs_links_group_matrix(vs_ctx *ctx, const vs_links *links, const uint64_t *list_off,
                           const uint32_t *list_idx, uint32_t n_groups, int64_t *out);
+/* Testing aid (addition to ABI 11, like vs_index_export / vs_scan_check): the CSR rows of a table exactly as the device holds
+ * them, so that a test sees what vs_links_to_host's dense answer hides -- the order of the columns inside a row, a column
+ * stored twice, a stored zero, a row_ptr that does not end at nnz.  Copies only, no kernel.  HOST pointers: *nnz (may be NULL)
+ * = the number of stored cells the table records; row_ptr (may be NULL) receives the n + 1 row offsets; col and val (both or
+ * neither NULL) receive the first *nnz stored columns and values when cap >= *nnz -- a smaller cap is VS_E_RANGE, with *nnz
+ * set, nothing else written.  A dense table is VS_E_ARG. */
+int vs_links_export_csr(vs_ctx *ctx, const vs_links *links, uint32_t *row_ptr, uint32_t *col, int64_t *val, uint64_t cap,
+                        uint64_t *nnz);
 
 /* ---- graph stages: K6 vertex scan + chain ranking, K7 edge flow -------------------------------
  * One call per re-initialised stage graph (store_reinit_graph, VStrains_IO.py:630-642).

@@ -972,6 +972,23 @@ int vs_links_to_host(vs_ctx *ctx, const vs_links *links, int64_t *out) {
     return VS_OK;
 }
 
+int vs_links_export_csr(vs_ctx *ctx, const vs_links *links, uint32_t *row_ptr, uint32_t *col, int64_t *val, uint64_t cap, uint64_t *nnz) {
+    if (!ctx || !links || (col == nullptr) != (val == nullptr)) return vs_fail(ctx, VS_E_ARG, "vs_links_export_csr: bad argument");
+    if (!links->sparse()) return vs_fail(ctx, VS_E_ARG, "vs_links_export_csr: the table of %u nodes is dense", links->n);
+    if (nnz) *nnz = links->nnz;
+    if (col && cap < links->nnz)
+        return vs_fail(ctx, VS_E_RANGE, "vs_links_export_csr: %llu stored cells, room for %llu", (unsigned long long)links->nnz, (unsigned long long)cap);
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    if (row_ptr)
+        VS_HIP(ctx, hipMemcpyAsync(row_ptr, links->d_row_ptr.ptr(), ((size_t)links->n + 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (col && links->nnz) {
+        VS_HIP(ctx, hipMemcpyAsync(col, links->d_col.ptr(), (size_t)links->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VS_HIP(ctx, hipMemcpyAsync(val, links->d_val.ptr(), (size_t)links->nnz * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VS_OK;
+}
+
 static int check_lists(vs_ctx *ctx, const vs_links *links, const uint64_t *list_off, const uint32_t *list_idx, uint32_t n_lists) {
     for (uint32_t l = 0; l < n_lists; l++)
         if (list_off[l + 1] < list_off[l]) return vs_fail(ctx, VS_E_ARG, "list offsets must not decrease");

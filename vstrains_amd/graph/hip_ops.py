@@ -290,6 +290,19 @@ class HipPeLinks(PeLinks):
             out = out[np.ix_(self._caller_rows, self._caller_rows)]
         return out
 
+    def csr(self):
+        """(testing aid, ``vs_links_export_csr``) The rows of a CSR table as the device holds them, in the table's own
+        numbering: (row_ptr uint32 [n + 1], col uint32 [nnz], val int64 [nnz], nnz as the table records it).  A dense table
+        raises ``NativeError`` (VS_E_ARG)."""
+        L, h = nat.lib(), self.ctx._h
+        nnz = C.c_uint64(0)
+        row_ptr = np.zeros(len(self.names) + 1, dtype=np.uint32)
+        nat.check(h, L.vs_links_export_csr(h, self._h, row_ptr.ctypes.data, None, None, 0, C.byref(nnz)))
+        col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
+        val = np.zeros(max(nnz.value, 1), dtype=np.int64)
+        nat.check(h, L.vs_links_export_csr(h, self._h, None, col.ctypes.data, val.ctypes.data, nnz.value, C.byref(nnz)))
+        return row_ptr, col[:nnz.value], val[:nnz.value], int(nnz.value)
+
     @staticmethod
     def _pool(lists: Sequence[Sequence[int]]):
         ids: Dict[Tuple[int, ...], int] = {}
