@@ -349,6 +349,40 @@ int vs_bam_mates_host(const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t 
                       uint32_t *waiting, uint64_t cap_waiting, uint64_t info[3]);
 int vs_bam_mates_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t hash_bits, uint32_t *pairs,
                       uint64_t cap_pairs, uint32_t *waiting, uint64_t cap_waiting, uint64_t info[3]);
+/* Interleaved FASTQ (additions to ABI 11): ONE file or pipe in which each pair's two records follow each other (`samtools
+ * fastq x.bam` to stdout, `seqtk mergepe`, `fastp --stdout`; what `bwa mem -p` reads), streamed as vs_fastq_stream_* streams
+ * two files, in every form that stream reads.  Mates are found by NAME on the device, as `bwa mem -p` finds them.
+ * A record is four lines: complete records = lines / 4, a final line without a newline counts at the end of the file, a
+ * trailing group of fewer than four lines is ignored; '\r' and bytes >= 0x80 as in the two-file stream (names are compared
+ * after that translation).  The name token of a record is its first line from its first byte up to (not including) the first
+ * space (0x20), tab (0x09) or the line's end.  mates(a, b): take both tokens; if a's ends in "/1" AND b's in "/2" drop those
+ * two bytes from both; true iff both are non-empty, of equal length and equal byte for byte ("a/2" then "a/1": no;
+ * "a 1:N:0:x" then "a 2:N:0:x": yes; "a/1" then "a/1": yes; an empty token never matches).  Pairing is greedy from the front:
+ *     i = 0;  while i < R:  if i + 1 < R and mates(i, i + 1): pair (i, i + 1), i += 2;  else: single i, i += 1
+ * The result is by definition what vs_fastq_stream_* gives for the two files (first records of the pairs, second records of
+ * the pairs).
+ *   vs_fastq_il_open  : mode VS_IL_STRICT: the first single record fails the stream with VS_E_ARG -- the message names the
+ *                       path, the file-wide 0-based record number and both header lines (the single's and its successor's,
+ *                       or "end of file"); VS_IL_SINGLES: single records are dropped and counted
+ *   vs_fastq_il_next  : as vs_fastq_stream_next
+ *   vs_fastq_il_info  : info[0] = pairs delivered, [1] = singles dropped, [2] = records decided, [3] = text bytes read
+ *                       (inflated), [4] = file bytes read (compressed), [5] = flags as vs_fastq_stream_info (bit 2: gzip)
+ *   vs_fastq_il_close : as vs_fastq_stream_close
+ * Test aids, the match of ONE window of n text bytes as they are (no text-mode translation); eof: the file ends with the
+ * window -- otherwise the last complete record is held back, unclassified, unless it is the second of a pair (its successor
+ * has not been seen).  pairs[2 p], [2 p + 1] = record index of the first and the second of pair p (at most cap_pairs pairs);
+ * info[0] = pairs, [1] = singles, [2] = records decided, [3] = the record held back (~0: none), [4] = the first single (~0:
+ * none), [5] = complete records.  _host is the one-thread twin (vs_mates_core.h); _text runs the kernels and keeps `guard`
+ * sentinel words on either side of the device pair list, VS_E_STATE if one changed or a word of the list stayed unwritten. */
+enum { VS_IL_STRICT = 0, VS_IL_SINGLES = 1 };
+typedef struct vs_fastq_il vs_fastq_il;
+int vs_fastq_il_open(vs_ctx *ctx, const char *path, int mode, vs_fastq_il **out);
+int vs_fastq_il_next(vs_ctx *ctx, vs_fastq_il *s, uint64_t max_pairs, vs_reads **out, uint64_t *n_pairs);
+int vs_fastq_il_info(const vs_fastq_il *s, uint64_t info[6]);
+void vs_fastq_il_close(vs_fastq_il *s);
+int vs_fastq_mates_host(const uint8_t *text, uint64_t n, int eof, uint32_t *pairs, uint64_t cap_pairs, uint64_t info[6]);
+int vs_fastq_mates_text(vs_ctx *ctx, const uint8_t *text, uint64_t n, int eof, uint32_t *pairs, uint64_t cap_pairs, uint32_t guard,
+                        uint64_t info[6]);
 /* Member-sharded open of ONE collated BAM for one process per GPU (additions to ABI 10): no rank inflates the whole file and
  * nothing is inflated on a host.  Rank r of W takes the BGZF members [M r / W, M (r + 1) / W) of vs_bgzf_walk_file, its
  * "share": the inflated bytes [S_r, S_r + E_r).  A share cannot be entered at a guessed record start, so pass 1 follows the

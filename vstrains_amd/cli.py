@@ -60,6 +60,14 @@ def build_parser():
                    help="extension: -fwd and -rve name ONE BAM in any record order (coordinate-sorted, `samtools view -f 12` of a "
                         "sorted alignment, ...); the mates are matched by read name on the device and records without a mate are "
                         "dropped, no `samtools collate` first (not together with --pe-text-from)")
+    p.add_argument("--interleaved", dest="interleaved", action="store_true", default=False,
+                   help="extension: -fwd and -rve name ONE interleaved FASTQ (a file, a pipe, /dev/stdin; any compression the two-file "
+                        "input takes), each pair's two records one behind the other as `samtools fastq`, `seqtk mergepe` and `fastp "
+                        "--stdout` write them; the mates are checked by name on the device and a record without its mate beside it "
+                        "stops the run (not together with --pe-text-from)")
+    p.add_argument("--interleaved-singles", dest="interleaved_singles", action="store_true", default=False,
+                   help="extension: with --interleaved, records without their mate beside them (the single reads `samtools fastq "
+                        "x.bam` writes among the pairs) are dropped and counted instead")
     p.add_argument("--gzip-device", dest="gzip_device", action="store_true", default=False,
                    help="extension: decode plain .fastq.gz (one deflate stream, as gzip and pigz write it) on the device, in parallel "
                         "from speculative block starts, instead of with zlib on one host core (sets VS_GZIP_DEVICE=1; one process only)")
@@ -94,9 +102,14 @@ def main(argv=None, backend=None):
         parser.error("--no-pe-text and --bgzf-pe-text are mutually exclusive")
     if args.pe_text_from is not None:
         for flag, name in ((args.no_pe_text, "--no-pe-text"), (args.sparse_pe_text, "--sparse-pe-text"), (args.bgzf_pe_text, "--bgzf-pe-text"),
-                           (args.bam_by_name, "--bam-by-name")):
+                           (args.bam_by_name, "--bam-by-name"), (args.interleaved or args.interleaved_singles, "--interleaved")):
             if flag:
                 parser.error("--pe-text-from and %s are mutually exclusive" % name)
+    from . import pe_inference
+
+    # (what the flags cannot apply to is a ValueError that says why, before anything is written or a device opened)
+    args.interleaved = pe_inference.interleaved_mode(args.interleaved, args.interleaved_singles)
+    pe_inference.interleaved_input(args.fwd, args.rve, pe_inference._rank_world()[1], args.interleaved)
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
         _bail("\nPath to the assembly graph is required, (.gfa format)", "Please ensure the path is correct")
     args.pe_text_files = None
@@ -173,12 +186,14 @@ def main(argv=None, backend=None):
 
     from .graph import pipeline
 
-    if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text or args.bam_by_name):
+    if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text or args.bam_by_name or args.interleaved):
         from .graph.hip_ops import HipBackend
 
         backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text,
-                             bgzf_info_text=args.bgzf_pe_text, bam_by_name=args.bam_by_name)
+                             bgzf_info_text=args.bgzf_pe_text, bam_by_name=args.bam_by_name, interleaved=args.interleaved)
     elif backend is not None:
+        if args.interleaved:
+            backend.interleaved = args.interleaved
         if args.bam_by_name:
             backend.bam_by_name = True
         if args.sparse_pe_text:

@@ -36,6 +36,15 @@ struct PackLines {  // the windows of the streamed ingest: end e is line 4 (e / 
         return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
     }
 };
+struct PackRecords {  // ONE window of the interleaved ingest: end e is line 4 rec[e] + 1 of it, without its newline
+    SlWin w;
+    const uint32_t *rec;
+    __device__ PackBytes open(uint32_t e) const {
+        const uint32_t r = rec[e];
+        const uint32_t start = w.ends[4u * r] + 1u;
+        return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
+    }
+};
 struct PackBamEnd {  // 4-bit bases, read backwards and complemented where the record's flag has 0x10
     const uint8_t *seq;
     uint32_t len;
@@ -88,6 +97,7 @@ static void launch_pack(hipStream_t st, const Src &src, const vs_reads *r) {
                            (uint32_t)r->n_ends, (uint32_t)r->n_words, (uint32_t *)r->d_words, (uint32_t *)r->d_mask, (uint32_t *)r->d_meta);
 }
 void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, const vs_reads *r) { launch_pack(st, PackLines{f0, f1}, r); }
+void vs_launch_pack_records(hipStream_t st, const SlWin &w, const uint32_t *rec, const vs_reads *r) { launch_pack(st, PackRecords{w, rec}, r); }
 void vs_launch_pack_bam(hipStream_t st, const BamEnds &b, const vs_reads *r) { launch_pack(st, PackBam{b}, r); }
 
 __global__ void __launch_bounds__(TPB)

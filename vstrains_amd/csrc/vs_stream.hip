@@ -52,6 +52,9 @@
 // after the rank's pairs.  Which range that is follows from per-member line counts that the ranks made on their devices
 // and exchanged before (vs_bgzf_walk_file, vs_bgzf_count_lines, further down; the plan is vs_bgzf_shard_plan of
 // vs_inflate.hip).  A final line without a newline counts only where the range ends with the file.
+//
+// What ONE file needs of all this -- its window and line ends (DevFile), a slot appended in each form, host text mode, the
+// wording of a rejected stream or member -- is in vs_stream_lines.h, which the interleaved ingest (vs_interleaved.hip) shares.
 #include <errno.h>
 #include <fcntl.h>
 #include <poll.h>
@@ -70,19 +73,16 @@
 #include <vector>
 
 #include "vs_internal.h"
-#include "vs_stream_reader.h"
-#include "vs_stream_window.h"
+#include "vs_stream_lines.h"
 
-#define SL_TPB 256
 #define SL_SCAN_TPB 1024
 
 namespace {
 
 // per-window status the kernels write (one uint32 array per stream, read back in one copy)
-enum { ST_NL = 0, ST_FLAGS = 1, ST_LAST = 2, ST_PER_FILE = 4 };  // [f * ST_PER_FILE + ...]
+// ([f * ST_PER_FILE + ST_NL / ST_FLAGS / ST_LAST]: vs_stream_lines.h)
 enum { ST_MAXLEN = 8, ST_TOO_LONG = 9, ST_WORDS = 10, ST_INVALID = 11, ST_CUT = 12 /* + f */, ST_N = 16 };
 enum { ST_BAD = ST_N /* + f: the first member of file f the device rejected (a running index), ~0u: none */, ST_ALL = ST_N + 2 };
-enum { FL_CR = 1u, FL_HIGH = 2u };
 
 }  // namespace
 
@@ -216,6 +216,17 @@ __global__ void __launch_bounds__(SL_TPB) k_sl_scatter(const uint8_t *__restrict
     }
 }
 
+void vs_launch_sl_count(hipStream_t st, const uint8_t *txt, uint64_t n, uint32_t *wg, uint32_t *stat) {
+    const uint64_t wgs = sl_workgroups(n);
+    if (!wgs) return;
+    hipLaunchKernelGGL(k_sl_count, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, txt, n, wg, stat);
+    hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, wg, (uint32_t)wgs, stat + ST_NL);
+}
+void vs_launch_sl_scatter(hipStream_t st, const uint8_t *txt, uint64_t n, const uint32_t *wg, uint32_t *ends) {
+    const uint64_t wgs = sl_workgroups(n);
+    if (wgs) hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, txt, n, wg, ends);
+}
+
 // one thread per end of the block (and one more for the closing word offset): length, packed words, the longest end, the
 // first end over the 24-bit limit; thread 0 also writes the record cuts (one past the newline of line 4n - 1)
 __global__ void __launch_bounds__(SL_TPB) k_sl_ends(SlWin f0, SlWin f1, uint32_t n_pairs, uint32_t *__restrict__ meta,
@@ -245,30 +256,7 @@ __global__ void __launch_bounds__(SL_TPB) k_sl_ends(SlWin f0, SlWin f1, uint32_t
     atomicMax(&st[ST_MAXLEN], len);
 }
 
-// ---- host side (the reader: vs_stream_reader.h) ---------------------------------------------------------------------------
-namespace {
-
-// The device side of one file: the window (vs_stream_window.h) and its line ends.
-struct DevFile {
-    DevWindow w;
-    size_t validated = 0;  // [0, validated) is known to be valid UTF-8 (ASCII, or checked on the host)
-    VsDevBuf ends, wg;     // uint32
-    uint32_t n_nl = 0, flags = 0, last_byte = 0;
-    uint64_t records = 0;  // complete records in the window
-    uint64_t first_record = 0;  // file-wide number of the window's first record
-    bool eof = false;      // the reader's last slot is in the window
-    int err = VS_OK;       // first failure of this file (reported after the end of both, in file order)
-    std::string err_msg;
-    uint32_t pend[4] = {0, 0, 0, 0};  // (end-of-input check) bytes of a character cut by a chunk boundary
-    uint32_t n_pend = 0;
-    uint32_t slot_base = 0;  // BGZF: running index of the first member of the slot appended last
-    // a member range (vs_fastq_stream_open_range): lines still to drop from the front; whether the range ends where the file does
-    uint64_t skip = 0;
-    bool to_file_end = true;
-};
-
-}  // namespace
-
+// ---- host side (the reader: vs_stream_reader.h; one file's window and line ends: DevFile of vs_stream_lines.h) -------------
 struct vs_fastq_stream {
     int device = 0;
     hipStream_t st = nullptr;
@@ -303,13 +291,8 @@ int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
     for (int f = 0; f < 2; f++) {
         if (only >= 0 && f != only) continue;
         DevFile &d = s->df[f];
-        const uint64_t words = (d.w.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
-        if (int rc = reserve_n<uint32_t>(ctx, d.wg, wgs + 1u)) return rc;
-        if (wgs) {
-            hipLaunchKernelGGL(k_sl_count, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(),
-                               s->d_stat + f * ST_PER_FILE);
-            hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, d.wg.as<uint32_t>(), (uint32_t)wgs, s->d_stat + f * ST_PER_FILE + ST_NL);
-        }
+        if (int rc = reserve_n<uint32_t>(ctx, d.wg, sl_workgroups(d.w.size) + 1u)) return rc;
+        vs_launch_sl_count(st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), s->d_stat + f * ST_PER_FILE);
     }
     VS_HIP(ctx, hipGetLastError());
     VS_HIP(ctx, hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_ALL, hipMemcpyDeviceToHost, st));
@@ -317,59 +300,9 @@ int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
     for (int f = 0; f < 2; f++) {
         if (only >= 0 && f != only) continue;
         DevFile &d = s->df[f];
-        d.n_nl = s->h_stat[f * ST_PER_FILE + ST_NL];
-        d.flags = s->h_stat[f * ST_PER_FILE + ST_FLAGS];
-        d.last_byte = s->h_stat[f * ST_PER_FILE + ST_LAST];
+        d.take_status(s->h_stat + f * ST_PER_FILE);
         s->flags_seen |= d.flags;
-        if (!d.flags) d.validated = d.w.size;
-        // (a final line without a newline counts -- at the end of the FILE: where a member range ends earlier, the bytes behind
-        // its last newline are the front of a line of the next rank)
-        const uint64_t lines = (uint64_t)d.n_nl + ((d.eof && d.to_file_end && d.w.size && d.last_byte != '\n') ? 1u : 0u);
-        d.records = lines / 4u;
     }
-    return VS_OK;
-}
-
-// Text mode on the host for a flagged window (see the top of the file): its bytes up to the last line end (all of them at
-// the end of the file) are translated and checked, the rest -- a partial line -- stays as it is for the next chunk.
-int translate_window(vs_ctx *ctx, vs_fastq_stream *s, int f) {
-    DevFile &d = s->df[f];
-    std::vector<uint8_t> buf(d.w.size);
-    if (d.w.size) VS_HIP(ctx, hipMemcpy(buf.data(), d.w.data(), d.w.size, hipMemcpyDeviceToHost));
-    size_t cut = d.w.size;
-    if (!d.eof) {
-        size_t lim = d.w.size;
-        if (lim && buf[lim - 1] == '\r') lim--;  // ("\r\n" may straddle the chunks)
-        cut = 0;
-        for (size_t i = lim; i-- > 0;)
-            if (buf[i] == '\n' || buf[i] == '\r') { cut = i + 1; break; }
-    }
-    if (d.validated < cut && !vs_utf8_range_ok(buf.data(), cut, d.validated, cut)) {
-        d.err = VS_E_UTF8;
-        d.err_msg = s->rd[f].path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
-        return VS_E_UTF8;
-    }
-    std::vector<uint8_t> out;
-    out.reserve(d.w.size);
-    for (size_t i = 0; i < cut;) {
-        const uint8_t c = buf[i];
-        if (c == '\r') {
-            out.push_back('\n');
-            i += (i + 1 < cut && buf[i + 1] == '\n') ? 2u : 1u;
-        } else if (c < 0x80u) {
-            out.push_back(c);
-            i++;
-        } else {  // one character, one byte (seq_chars); checked above
-            const uint32_t cl = vs_utf8_char_len(buf.data() + i, cut - i);
-            out.push_back('?');
-            i += cl ? cl : 1u;
-        }
-    }
-    const size_t translated = out.size();
-    out.insert(out.end(), buf.begin() + (ptrdiff_t)cut, buf.end());
-    if (!out.empty()) VS_HIP(ctx, hipMemcpy(d.w.data(), out.data(), out.size(), hipMemcpyHostToDevice));
-    d.w.size = out.size();
-    d.validated = translated;
     return VS_OK;
 }
 
@@ -403,12 +336,6 @@ bool check_piece(DevFile &d, const uint8_t *p, size_t n, bool last) {
     return true;
 }
 
-int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl);
-void gzip_failed(vs_fastq_stream *s, int f);
-int append_gzip(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot *sl);
-bool zlib_accepts(const uint8_t *pay, const vs_bgzf_member &mb, int *code);
-bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl);
-
 // Both files to their ends (the reference reads them whole): every byte not yet checked is checked, a reader's failure is
 // picked up; then the first failure in file order.
 int finish(vs_ctx *ctx, vs_fastq_stream *s) {
@@ -427,7 +354,7 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
         while (!d.eof) {
             if (d.err == VS_OK && d.w.gz.more) {  // held-back gzip runs: a round on them, no slot
                 d.w.size = 0;
-                int rc = append_gzip(ctx, s, f, nullptr);
+                int rc = append_gzip(ctx, s->st, d, r, nullptr);
                 if (rc == VS_OK) rc = scan_windows(ctx, s, f);
                 if (rc != VS_OK) return stream_fail(ctx, s, rc, vs_last_error(ctx));
                 if (d.err == VS_OK && ((d.flags & FL_HIGH) || d.n_pend)) {
@@ -449,12 +376,12 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
                 // no text on the host: the members are inflated (and their CRCs checked) on the device like any others, and
                 // the text comes back only when the scan saw a byte >= 0x80 (or a character is still open)
                 d.w.size = 0;
-                int rc = append_slot(ctx, s, f, sl);
+                int rc = append_slot(ctx, s->st, d, r, sl, s->d_stat + ST_BAD + f);
                 if (rc == VS_OK) rc = scan_windows(ctx, s, f);
                 if (rc != VS_OK) {
                     return stream_fail(ctx, s, rc, vs_last_error(ctx));
                 }
-                if (!member_failed(ctx, s, f, sl) && d.err == VS_OK && ((d.flags & FL_HIGH) || d.n_pend)) {
+                if (!member_failed(d, r, sl, s->h_stat[ST_BAD + f]) && d.err == VS_OK && ((d.flags & FL_HIGH) || d.n_pend)) {
                     std::vector<uint8_t> buf(d.w.size);
                     if (d.w.size && hipMemcpy(buf.data(), d.w.data(), d.w.size, hipMemcpyDeviceToHost) != hipSuccess)
                         return stream_fail(ctx, s, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
@@ -485,161 +412,6 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
     return VS_OK;
 }
 
-// The device refused the plain gzip stream of file f (DevWindow::gz_status).  A regular file is read again through zlib, for
-// the code in the words of the reader's zlib loop; a pipe cannot be read twice, its message names the device's status.
-void gzip_failed(vs_fastq_stream *s, int f) {
-    DevFile &d = s->df[f];
-    const std::string &path = s->rd[f].path;
-    char msg[700];
-    struct stat sb;
-    d.err = VS_E_ARG;
-    if (fstat(s->rd[f].fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
-        snprintf(msg, sizeof msg, "%s: not a complete gzip stream (device status %s)", path.c_str(), vs_gz_status_name(d.w.gz_status));
-        d.err_msg = msg;
-        return;
-    }
-    int code = Z_OK;  // zlib over the whole file, as the reader's loop runs it
-    {
-        std::vector<uint8_t> in(1u << 20), out(1u << 20);
-        z_stream zs;
-        memset(&zs, 0, sizeof zs);
-        uint64_t at = 0;
-        bool eof = false, done = false;
-        if (inflateInit2(&zs, 15 + 16) != Z_OK) code = Z_MEM_ERROR;
-        while (code == Z_OK && !done) {
-            if (zs.avail_in == 0 && !eof) {
-                const ssize_t got = pread(s->rd[f].fd, in.data(), in.size(), (off_t)at);
-                if (got <= 0) eof = true;
-                else at += (uint64_t)got;
-                zs.next_in = in.data();
-                zs.avail_in = got > 0 ? (uInt)got : 0u;
-            }
-            zs.next_out = out.data();
-            zs.avail_out = (uInt)out.size();
-            int rc = inflate(&zs, Z_NO_FLUSH);
-            if (rc == Z_STREAM_END) {
-                if (zs.avail_in == 0 && !eof) continue;  // (look whether more members follow)
-                if (zs.avail_in == 0 && eof) done = true;
-                else if (inflateReset(&zs) != Z_OK) code = Z_DATA_ERROR;
-                continue;
-            }
-            if (rc == Z_OK || (rc == Z_BUF_ERROR && (zs.avail_out == 0 || (zs.avail_in == 0 && !eof)))) {
-                if (zs.avail_in == 0 && eof && zs.avail_out != 0) code = Z_DATA_ERROR;  // truncated stream
-                continue;
-            }
-            code = rc == Z_BUF_ERROR ? Z_DATA_ERROR : rc;
-        }
-        inflateEnd(&zs);
-    }
-    if (code == Z_OK) {
-        snprintf(msg, sizeof msg, "%s: the gzip stream was rejected on the device (status %s) but zlib accepts it", path.c_str(),
-                 vs_gz_status_name(d.w.gz_status));
-        d.err = VS_E_STATE;
-    } else {
-        snprintf(msg, sizeof msg, "%s: not a complete gzip stream (zlib code %d)", path.c_str(), code);
-    }
-    d.err_msg = msg;
-}
-
-// a slot of file f appended to its window: its text uploaded, or its BGZF members uploaded and inflated there
-int append_slot(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
-    DevFile &d = s->df[f];
-    if (d.w.size + sl.text > STREAM_MAX_WINDOW)
-        return vs_fail(ctx, VS_E_RANGE, "%s: a window of %llu bytes without a complete record", s->rd[f].path.c_str(),
-                       (unsigned long long)(d.w.size + sl.text));
-    if (sl.comp) d.slot_base = (uint32_t)d.w.members;
-    if (sl.gz) return append_gzip(ctx, s, f, &sl);
-    if (int rc = d.w.append(ctx, s->st, sl, s->d_stat + ST_BAD + f, d.slot_base)) return rc;
-    d.eof = sl.last;
-    return VS_OK;
-}
-
-// A slot of a plain gzip file decoded behind the window of file f, or (sl == nullptr, while DevWindow::gz.more) one more
-// round on the compressed bytes that the text cap of the round before held back: no slot is taken for it.
-int append_gzip(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot *sl) {
-    DevFile &d = s->df[f];
-    if (int rc = d.w.append_gzip(ctx, s->st, sl, s->rd[f].path.c_str())) return rc;
-    if (d.w.gz_status && d.err == VS_OK) gzip_failed(s, f);
-    d.eof = d.w.gzip_at_end();
-    return VS_OK;
-}
-
-// the next slot of file f appended to its window (blocks until the reader has one); while held-back gzip runs are pending,
-// those instead, and `taken` stays empty
-int append_chunk(vs_ctx *ctx, vs_fastq_stream *s, int f, SlotLease &taken) {
-    if (s->df[f].w.gz.more) return append_gzip(ctx, s, f, nullptr);
-    taken = SlotLease(s->rd[f]);
-    return append_slot(ctx, s, f, *taken);
-}
-
-// One BGZF member (its payload at pay) as a plain gzip member through zlib: true when zlib accepts it; else *code = what
-// the reader's zlib loop reports for such a stream (cut off, or bytes behind its end: Z_DATA_ERROR).
-bool zlib_accepts(const uint8_t *pay, const vs_bgzf_member &mb, int *code) {
-    std::vector<uint8_t> gz = {0x1f, 0x8b, 0x08, 0, 0, 0, 0, 0, 0, 0xff};  // a 10-byte header, the payload, the trailer
-    gz.insert(gz.end(), pay, pay + mb.in_len);
-    for (uint32_t v : {mb.crc, mb.isize})
-        for (int k = 0; k < 4; k++) gz.push_back((uint8_t)(v >> (8 * k)));
-    std::vector<uint8_t> out(1u << 16);
-    z_stream zs;
-    memset(&zs, 0, sizeof zs);
-    int rc = inflateInit2(&zs, 15 + 16);
-    if (rc == Z_OK) {
-        zs.next_in = gz.data();
-        zs.avail_in = (uInt)gz.size();
-        do {
-            zs.next_out = out.data();
-            zs.avail_out = (uInt)out.size();
-            rc = inflate(&zs, Z_NO_FLUSH);
-        } while (rc == Z_OK && (zs.avail_in != 0 || zs.avail_out == 0));
-        const bool accepted = rc == Z_STREAM_END && zs.avail_in == 0;
-        inflateEnd(&zs);
-        if (accepted) return true;
-        if (rc >= 0 || rc == Z_BUF_ERROR) rc = Z_DATA_ERROR;
-    }
-    *code = rc;
-    return false;
-}
-
-// After scan_windows: did the device reject a member of the slot of file f appended last?  Then zlib inflates that member
-// on the host and the file fails with zlib's code, in the words of the reader's zlib loop (true: the file has failed).
-bool member_failed(vs_ctx *ctx, vs_fastq_stream *s, int f, const Slot &sl) {
-    DevFile &d = s->df[f];
-    if (!sl.comp || s->h_stat[ST_BAD + f] == 0xFFFFFFFFu) return false;
-    const uint32_t idx = s->h_stat[ST_BAD + f] - d.slot_base;
-    char msg[700];
-    if (d.err != VS_OK) return true;
-    if (idx >= sl.n_members) {
-        d.err = VS_E_STATE;
-        d.err_msg = s->rd[f].path + ": the device reported a BGZF member that is not of the slot it inflated";
-        return true;
-    }
-    const vs_bgzf_member mb = slot_member(sl, idx);
-    uint32_t dev_status = 0;
-    (void)hipMemcpy(&dev_status, d.w.mstat.as<uint32_t>() + idx, sizeof dev_status, hipMemcpyDeviceToHost);
-    int rc = Z_DATA_ERROR;
-    if (zlib_accepts(sl.buf.as<uint8_t>() + mb.in_off, mb, &rc)) {
-        snprintf(msg, sizeof msg, "%s: BGZF member %llu was rejected on the device (status %u) but zlib accepts it", s->rd[f].path.c_str(),
-                 (unsigned long long)(d.slot_base + idx), dev_status);
-        d.err = VS_E_STATE;
-        d.err_msg = msg;
-        return true;
-    }
-    snprintf(msg, sizeof msg, "%s: not a complete gzip stream (zlib code %d)", s->rd[f].path.c_str(), rc);
-    d.err = VS_E_ARG;
-    d.err_msg = msg;
-    return true;
-}
-
-// the window after its first `cut` bytes (the records of the block) have gone: the leftover to the front of the other buffer
-int drop_front(vs_ctx *ctx, vs_fastq_stream *s, int f, size_t cut, uint64_t records) {
-    DevFile &d = s->df[f];
-    if (int rc = d.w.keep_from(ctx, s->st, cut)) return rc;
-    d.validated = d.validated > cut ? d.validated - cut : 0;
-    d.records -= records;
-    d.first_record += records;
-    return VS_OK;
-}
-
 // A member range starts inside a record of the rank before: after scan_windows, the first d.skip lines of the window of
 // file f go (its line ends scattered once, the offset of the last one to drop read back).  They all end in the range's
 // first member -- that is how the plan picks it -- and a slot holds whole members, so the first window has them.
@@ -647,15 +419,14 @@ int skip_lines(vs_ctx *ctx, vs_fastq_stream *s, int f) {
     DevFile &d = s->df[f];
     if (d.n_nl < d.skip) return vs_fail(ctx, VS_E_STATE, "%s: fewer lines at the front of its member range than were counted", s->rd[f].path.c_str());
     if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return rc;
-    const uint64_t words = (d.w.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
-    hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, s->st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
+    vs_launch_sl_scatter(s->st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
     VS_HIP(ctx, hipGetLastError());
     uint32_t at = 0;
     VS_HIP(ctx, hipMemcpyAsync(&at, d.ends.as<uint32_t>() + (d.skip - 1u), sizeof at, hipMemcpyDeviceToHost, s->st));
     VS_HIP(ctx, hipStreamSynchronize(s->st));
     if ((size_t)at + 1u > d.w.size) return vs_fail(ctx, VS_E_STATE, "%s: a line end beyond the window", s->rd[f].path.c_str());
     d.skip = 0;
-    return drop_front(ctx, s, f, (size_t)at + 1u, 0);
+    return drop_front(ctx, s->st, d, (size_t)at + 1u, 0);
 }
 
 // both files opened and their readers started; range (may be NULL) = per file {first byte, one past the last byte, lines to skip}
@@ -741,7 +512,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
             DevFile &d = s->df[f], &o = s->df[f ^ 1];
             const bool need = !d.eof && d.records < max_pairs && d.records <= o.records && !(o.eof && o.records <= d.records);
             if (!need) continue;
-            if (int rc = append_chunk(ctx, s, f, taken[f])) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = append_chunk(ctx, s->st, d, s->rd[f], taken[f], s->d_stat + ST_BAD + f)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
             fresh[f] = true;
         }
         if (round > 0 && !fresh[0] && !fresh[1]) return finish(ctx, s);  // (nothing more to read and no pair: the end)
@@ -749,7 +520,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
         if (rc) return stream_fail(ctx, s, rc, vs_last_error(ctx));
         bool rejected = false;
         for (int f = 0; f < 2; f++)
-            if (fresh[f] && ((taken[f] && member_failed(ctx, s, f, *taken[f])) || s->df[f].err != VS_OK)) rejected = true;  // (needs the slot: before it goes back)
+            if (fresh[f] && ((taken[f] && member_failed(s->df[f], s->rd[f], *taken[f], s->h_stat[ST_BAD + f])) || s->df[f].err != VS_OK)) rejected = true;  // (needs the slot: before it goes back)
         for (int f = 0; f < 2; f++) taken[f].give_back();  // (the stream is synchronised: the upload is done)
         if (rejected) return finish(ctx, s);
         if (s->ranged) {
@@ -768,7 +539,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
         for (int f = 0; f < 2; f++) {
             DevFile &d = s->df[f];
             if (fresh[f] && d.flags && d.validated < d.w.size) {  // (text that arrived with this chunk: host text mode)
-                if (translate_window(ctx, s, f) != VS_OK) return finish(ctx, s);
+                if (translate_window(ctx, d, s->rd[f].path) != VS_OK) return finish(ctx, s);
                 again = true;
             }
         }
@@ -783,8 +554,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     for (int f = 0; f < 2; f++) {
         DevFile &d = s->df[f];
         if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
-        const uint64_t words = (d.w.size + 15u) / 16u, wgs = (words + SL_TPB - 1u) / SL_TPB;
-        if (wgs) hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
+        vs_launch_sl_scatter(st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
     }
     if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
     SlWin w0 = {s->df[0].w.data(), s->df[0].ends.as<uint32_t>(), s->df[0].n_nl, (uint32_t)s->df[0].w.size};
@@ -826,7 +596,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     vs_launch_pack_lines(st, w0, w1, r);
     if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + ST_INVALID, s->h_stat + ST_INVALID)) != hipSuccess) return fail(e1);
     for (int f = 0; f < 2; f++)
-        if (drop_front(ctx, s, f, cut[f], n) != VS_OK) return fail(hipErrorOutOfMemory);
+        if (drop_front(ctx, st, s->df[f], cut[f], n) != VS_OK) return fail(hipErrorOutOfMemory);
     if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
     s->pairs += n;
     *out = r;

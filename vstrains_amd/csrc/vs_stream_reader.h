@@ -1,4 +1,4 @@
-// The host reader of the streamed ingests (vs_stream.hip: FASTQ; vs_bam.hip: BAM): one file read front to back by a thread of
+// The host reader of the streamed ingests (vs_stream.hip: two FASTQ files; vs_interleaved.hip: one interleaved FASTQ; vs_bam.hip: BAM): one file read front to back by a thread of
 // its own into a bounded ring of pinned chunks -- plain bytes, zlib-inflated gzip, the raw deflate payloads of whole BGZF
 // members with their directory, or (VS_GZIP_DEVICE=1) the bytes of a plain gzip file as they are, for the device to inflate
 // (see the top of vs_stream.hip).

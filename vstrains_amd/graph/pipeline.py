@@ -203,6 +203,9 @@ def _run(args, logger, backend=None):
     singletons = (getattr(backend, "bam_info", None) or {}).get("singletons", 0)
     if singletons:
         logger.info("{0} records of the BAM have no mate in it and were dropped".format(singletons))
+    singles = (getattr(backend, "interleaved_info", None) or {}).get("singles", 0)
+    if singles:
+        logger.info("{0} records of the interleaved FASTQ have no mate beside them and were dropped".format(singles))
     logger.info("paired end information stored")
 
     t0 = time.time()

@@ -420,6 +420,94 @@ class FastqStream:
             pass
 
 
+class InterleavedStream:
+    """The read pairs of ONE interleaved FASTQ -- a file or pipe in which each pair's two records follow each other
+    (``samtools fastq x.bam`` to stdout, ``seqtk mergepe``, ``fastp --stdout``; what ``bwa mem -p`` reads) -- through
+    ``vs_fastq_il_*``: read front to back like ``FastqStream`` reads two files, in every form that stream reads, the mates
+    found by NAME on the device.  Two adjacent records are a pair when their name tokens (the header line up to the first
+    space or tab; a ``/1`` on the first and ``/2`` on the second dropped) are non-empty and equal byte for byte, greedily
+    from the front as ``bwa mem -p`` pairs; any other record is a single.  The stream stands for the two files (first
+    records of the pairs, second records of the pairs).  ``singles=False`` (strict): the first single raises ``ValueError``
+    naming the path, the record (numbered from 0 in file order) and both header lines; ``singles=True``: singles are dropped
+    and counted.  Interface of ``FastqStream``; ``info`` has ``pairs``, ``singles``, ``records``, ``text_bytes``,
+    ``file_bytes``, ``flags``."""
+
+    def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20, singles: bool = False):
+        self._ctx = ctx
+        self._h = None
+        self.block_pairs = block_pairs
+        self.singles = bool(singles)
+        h = C.c_void_p()
+        rc = nat.lib().vs_fastq_il_open(ctx._h, os.fspath(path).encode(), 1 if singles else 0, C.byref(h))
+        if rc != nat.VS_OK:
+            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+            if "cannot open" in msg:
+                raise FileNotFoundError(msg)
+            raise nat.NativeError(rc, msg)
+        self._h = h
+
+    @property
+    def info(self):
+        a = (C.c_uint64 * 6)()
+        nat.lib().vs_fastq_il_info(self._h, a)
+        return dict(pairs=int(a[0]), singles=int(a[1]), records=int(a[2]), text_bytes=int(a[3]), file_bytes=int(a[4]), flags=int(a[5]))
+
+    @property
+    def n_pairs(self) -> int:
+        """pairs delivered so far (all of them once the iteration has ended)"""
+        return self.info["pairs"]
+
+    def next_block(self) -> Optional["ReadBlock"]:
+        """The next block, or None at the end of the input."""
+        h = C.c_void_p()
+        n = C.c_uint64(0)
+        rc = nat.lib().vs_fastq_il_next(self._ctx._h, self._h, self.block_pairs, C.byref(h), C.byref(n))
+        if rc == nat.VS_E_ARG:  # (a single record in the strict mode; a stream that is no complete gzip)
+            raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
+        if rc != nat.VS_OK:
+            FastqPair._raise(self._ctx._h, rc)  # ValueError for bytes that are not valid UTF-8
+        return ReadBlock(self._ctx, h) if n.value else None
+
+    def __iter__(self):
+        while True:
+            block = self.next_block()
+            if block is None:
+                return
+            yield block
+
+    def close(self):
+        if self._h:
+            nat.lib().vs_fastq_il_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fastq_mates(text: bytes, eof: bool = True, ctx: "Context" = None, guard: int = 64):
+    """The mates of ONE window of interleaved FASTQ text, bytes as they are (test aid): ``vs_fastq_mates_host`` (one host
+    thread), or with ``ctx`` the kernels (``vs_fastq_mates_text``, ``guard`` sentinel words around the device pair list).
+    ``eof``: the file ends with the window; otherwise its last complete record is held back unless it is the second of a
+    pair.  Returns (pairs uint32 [n, 2]: record index of the first and the second; info dict: ``pairs``, ``singles``,
+    ``decided``, ``held`` and ``first_single`` = a record index or None, ``records``)."""
+    buf = np.frombuffer(text or b"\0", dtype=np.uint8)
+    cap = len(text) // 8 + 1
+    pairs = np.zeros((cap, 2), dtype=np.uint32)
+    info = (C.c_uint64 * 6)()
+    if ctx is None:
+        rc = nat.lib().vs_fastq_mates_host(buf.ctypes.data, len(text), 1 if eof else 0, pairs.ctypes.data, cap, info)
+        if rc != nat.VS_OK:
+            raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    else:
+        nat.check(ctx._h, nat.lib().vs_fastq_mates_text(ctx._h, buf.ctypes.data, len(text), 1 if eof else 0, pairs.ctypes.data, cap, guard, info))
+    none = (1 << 64) - 1
+    return pairs[:int(info[0])], dict(pairs=int(info[0]), singles=int(info[1]), decided=int(info[2]), held=None if info[3] == none else int(info[3]),
+                                      first_single=None if info[4] == none else int(info[4]), records=int(info[5]))
+
+
 class BamStream:
     """The read pairs of ONE collated BAM file (unaligned BAM from the sequencer, or the unmapped pairs of a host
     alignment after ``samtools collate``) through ``vs_bam_stream_*``: the BGZF members inflated on the device, the records

@@ -27,20 +27,25 @@ def _rank_world():
     return 0, 1
 
 
-def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow: bool = False, bam_by_name: bool = False):
+def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow: bool = False, bam_by_name: bool = False, interleaved=None):
     """Index the nodes of ``gfa`` and count every pair of the two FASTQ files; the counters stay
     on the device.  Returns ``(node ids in file order, PeCounter)``.  ``stages_follow``: the graph stages will build their
     PE-link table from these counters in this process (the pipeline; not the stand-alone script, which writes the two text
     files) -- the table's device buffer is then set aside together with the counters.  ``bam_by_name``: the inputs are ONE
     BAM in any record order, its mates matched by name (``BamStream(by_name=True)``); ``count_links.bam_info`` is then the
-    stream's ``info`` (``singletons`` among it), else None."""
+    stream's ``info`` (``singletons`` among it), else None.  ``interleaved`` (None, ``"strict"`` or ``"singles"``): the inputs
+    are ONE interleaved FASTQ, each pair's two records one behind the other, the mates checked by name on the device
+    (``InterleavedStream``; ``"singles"`` drops and counts the records without a mate, ``"strict"`` refuses the first);
+    ``count_links.interleaved_info`` is then the stream's ``info``, else None."""
     rank, world = _rank_world()
     count_links.bam_info = None
+    count_links.interleaved_info = None
+    il_path = interleaved_input(fwd, rve, world, interleaved)  # (None without the flag; what it cannot apply to is a ValueError)
     why = gzip_device_refusal(world)  # (reads the environment only; None with the switch unset)
     if why is not None:
         raise ValueError(why)
-    bam = bam_input(fwd, rve, world, by_name=bam_by_name, sharded=not bam_by_name)  # (a collated BAM is shared by member)
-    streamed = bam is None and use_stream(fwd, rve)
+    bam = None if il_path else bam_input(fwd, rve, world, by_name=bam_by_name, sharded=not bam_by_name)  # (a collated BAM is shared by member)
+    streamed = bam is None and not il_path and use_stream(fwd, rve)
     if world > 1 and not (_regular(fwd) and _regular(rve)):  # (the sharded path maps regular files; VS_FASTQ_STREAM aside)
         raise ValueError("the FASTQ inputs %s / %s are not both regular files: a pipe can be read by one process only, so "
                          "the sharded (torchrun) run cannot take it; run one process, or write the reads to files" % (fwd, rve))
@@ -53,7 +58,14 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     # counters are summed over ranks afterwards (RCCL all-reduce); a single process takes everything
     if rank == 0 and stages_follow:
         counter.reserve_link_table()  # (the graph stages run on this rank: their table's buffer is taken now)
-    if bam is not None and world > 1:
+    if il_path:
+        fq = host.InterleavedStream(il_path, ctx, block_pairs=BATCH_PAIRS, singles=(interleaved == "singles"))  # one file, opened once
+        try:
+            count_stream(ctx, fq, counter, progress=True)
+            count_links.interleaved_info = fq.info
+        finally:
+            fq.close()
+    elif bam is not None and world > 1:
         # one collated whole-BGZF BAM: the ranks share it by member, summarise their shares for every entry the previous share
         # could hand them, and each streams its own couples (BamStream.open_shard); why == the reason when rank 0 reads the
         # whole file instead, as the single process does and in its words, and the others only join the sum
@@ -199,6 +211,45 @@ def bam_input(fwd: str, rve: str, world: int = 1, by_name: bool = False, sharded
     return fwd
 
 
+def interleaved_mode(interleaved: bool, singles: bool):
+    """The two flags of the commands as ``count_links`` takes them: None, ``"strict"`` or ``"singles"``."""
+    if singles and not interleaved:
+        raise ValueError("--interleaved-singles says what to do with the single records of an interleaved FASTQ and needs "
+                         "--interleaved, which says that -f and -r name one")
+    return ("singles" if singles else "strict") if interleaved else None
+
+
+def interleaved_input(fwd: str, rve: str, world: int = 1, interleaved=None):
+    """The path when ``interleaved`` (``--interleaved``) asks for ONE interleaved FASTQ and ``-f`` and ``-r`` name it (the same
+    string -- ``/dev/stdin`` twice, a FIFO -- or the same file), None without the flag.  ``ValueError`` for what the flag
+    cannot apply to, before a device is opened: two different files, a BAM, ``VS_FASTQ_STREAM=0``, a process group of more
+    than one rank."""
+    if interleaved is None:
+        return None
+    if interleaved not in ("strict", "singles"):
+        raise ValueError("interleaved is None, 'strict' or 'singles', not %r" % (interleaved,))
+    same = fwd == rve
+    if not same:
+        try:
+            same = os.path.samefile(fwd, rve)
+        except OSError:
+            same = False
+    if not same:
+        raise ValueError("--interleaved reads the pairs from ONE file in which each pair's two records follow each other, and %s / %s "
+                         "are two different files; name the same file for both reads, or leave the flag out" % (fwd, rve))
+    if _starts_bam(fwd):
+        raise ValueError("%s is a BAM file, and --interleaved reads an interleaved FASTQ; leave the flag out (a collated BAM is read "
+                         "as it is, one in any record order with --bam-by-name)" % fwd)
+    if os.environ.get("VS_FASTQ_STREAM") == "0":
+        raise ValueError("--interleaved reads its file in the streamed ingest, and VS_FASTQ_STREAM=0 asks for the mapped open of two "
+                         "files: set one of the two")
+    if world > 1:
+        raise ValueError("%s: --interleaved reads the file in one process only; sharing an interleaved file among the %d ranks of this "
+                         "process group is not built: run without torchrun -- what the ranks share by member are BGZF pairs (two "
+                         "bgzip files) and collated BAMs" % (fwd, world))
+    return fwd
+
+
 def member_shard_refusal(fwd: str, rve: str):
     """None when a sharded run tries the member-sharded open (both inputs regular files that start with a BGZF member, and
     neither ``VS_FASTQ_STREAM=0`` nor ``VS_BGZF_DEVICE=0`` -- the switches that give the mapped open and host zlib in
@@ -341,7 +392,7 @@ def write_info_files(out_dir: str, ids, counter, sparse: bool = False, bgzf: boo
 
 
 def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int = 0, ctx=None, stages_follow: bool = False,
-        sparse_info: bool = False, bgzf_info: bool = False, bam_by_name: bool = False):
+        sparse_info: bool = False, bgzf_info: bool = False, bam_by_name: bool = False, interleaved=None):
     # PE_Inference.py:93-96: the output directory is wiped and recreated
     if out_dir[-1] == "/":
         out_dir = out_dir[:-1]
@@ -357,9 +408,10 @@ def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int 
     glb_start = time.time()
     if bam_by_name:
         bam_input(fwd, rve, world, by_name=True)  # (what the flag cannot apply to is said before a device is opened)
+    interleaved_input(fwd, rve, world, interleaved)  # (the same)
     if ctx is None:
         ctx = host.Context(device)
-    ids, counter = count_links(ctx, gfa, fwd, rve, kmer_size, stages_follow=stages_follow, bam_by_name=bam_by_name)
+    ids, counter = count_links(ctx, gfa, fwd, rve, kmer_size, stages_follow=stages_follow, bam_by_name=bam_by_name, interleaved=interleaved)
     run.last = (ids, counter)
     if rank != 0:
         return None  # the counters were reduced to rank 0, which writes the files
@@ -394,10 +446,20 @@ def main(argv=None):
                         help="extension: decode plain .fastq.gz (one deflate stream, as gzip and pigz write it) on the device, in "
                              "parallel from speculative block starts, instead of with zlib on one host core (sets VS_GZIP_DEVICE=1; "
                              "one process only)")
+    parser.add_argument("--interleaved", dest="interleaved", action="store_true", default=False,
+                        help="extension: -f and -r name ONE interleaved FASTQ (a file, a pipe, /dev/stdin; any compression the "
+                             "two-file input takes), each pair's two records one behind the other as `samtools fastq`, `seqtk "
+                             "mergepe` and `fastp --stdout` write them; the mates are checked by name on the device and a record "
+                             "without its mate beside it stops the run")
+    parser.add_argument("--interleaved-singles", dest="interleaved_singles", action="store_true", default=False,
+                        help="extension: with --interleaved, records without their mate beside them (the single reads `samtools "
+                             "fastq x.bam` writes among the pairs) are dropped and counted instead")
     args = parser.parse_args(argv)
+    interleaved = interleaved_mode(args.interleaved, args.interleaved_singles)
     if args.gzip_device:
         os.environ["VS_GZIP_DEVICE"] = "1"  # (the library reads the switch where it reads VS_BGZF_DEVICE)
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    interleaved_input(args.fwd, args.rve, world, interleaved)  # (refused before a device is opened or a process group made)
     if world > 1:  # launched by torchrun: one rank per GPU, counters all-reduced over RCCL
         import torch
         import torch.distributed as dist
@@ -418,7 +480,7 @@ def main(argv=None):
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
         os.environ.setdefault("VS_HOST_THREADS", str(max(1, (os.cpu_count() or 1) // max(local_world, 1))))
     run(args.gfa, args.dir, args.fwd, args.rve, args.kmer_size, args.device, sparse_info=args.sparse_info, bgzf_info=args.bgzf_info,
-        bam_by_name=args.bam_by_name)
+        bam_by_name=args.bam_by_name, interleaved=interleaved)
     if world > 1:
         import torch.distributed as dist
 
