@@ -383,6 +383,48 @@ void vs_fastq_il_close(vs_fastq_il *s);
 int vs_fastq_mates_host(const uint8_t *text, uint64_t n, int eof, uint32_t *pairs, uint64_t cap_pairs, uint64_t info[6]);
 int vs_fastq_mates_text(vs_ctx *ctx, const uint8_t *text, uint64_t n, int eof, uint32_t *pairs, uint64_t cap_pairs, uint32_t guard,
                         uint64_t info[6]);
+/* Two FASTQ files paired by READ NAME (additions to ABI 11): the two files of vs_fastq_stream_*, in every form that stream
+ * reads, but a pair is a pair of mates by name, decided on the device.  Records, the name token and mates(a, b) as for the
+ * interleaved FASTQ above; a = the header line of the file-1 record, b = that of the file-2 record.
+ * KEY of a record: its token, without a trailing "/1" on a file-1 record and without a trailing "/2" on a file-2 record.  The
+ * key only nominates: two records are a pair iff they are of different files, their keys are non-empty and equal byte for
+ * byte, and mates(a, b) ("x/1" against "x": two singles).
+ *   VS_PN_STRICT  : pair p is record p of either file and must be a pair of mates (mates(a_p, b_p), nothing else): the first
+ *                   that is not fails the stream with VS_E_ARG -- the message names both paths, the file-wide 0-based pair
+ *                   number and both header lines (at most 200 bytes each) -- and so does a complete record left over in the
+ *                   longer file.
+ *   VS_PN_SINGLES : the files are in the same order, either may lack records the other has.  An input is VALID when (V1)
+ *                   within one file no non-empty key occurs twice and (V2) the file-1 records that have a mate, in file order,
+ *                   have their mates in increasing file-2 order.  For a valid input the pairs are exactly the records whose
+ *                   key is in both files (and mates), in file-1 order; every other complete record is a single of its file,
+ *                   dropped and counted -- whatever the chunk size.  A V1 or V2 violation inside one pair of windows fails the
+ *                   stream with VS_E_ARG ("name X occurs twice in FILE", "... are mates but lie behind ..."); one that spans
+ *                   windows leaves its records among the singles.  A window beyond VS_PAIR_WINDOW bytes (environment; default
+ *                   the largest window) none of whose records a round decided is VS_E_RANGE.  VS_PAIR_NAME_BITS (environment, tests)
+ *                   keeps the low bits of the name hash only.
+ *   vs_fastq_pn_next  : as vs_fastq_stream_next
+ *   vs_fastq_pn_info  : info[0] = pairs delivered, [1] / [2] = singles dropped of file 1 / file 2, [3] / [4] = records decided
+ *                       of file 1 / file 2, [5] = rounds (pairs of windows joined), [6] = the largest window in bytes, [7] =
+ *                       text bytes read, [8] = file bytes read, [9] = flags as vs_fastq_stream_info
+ * Test aids, the join of ONE pair of windows (n0 / n1 text bytes as they are; eof0 / eof1: the file ends with its window; table:
+ * slots of the open-address table, a power of two >= 2, 0: the stream's choice (>= 2 (R1 + R2)); name_bits: low bits of the
+ * name hash kept, 0: all 64).  pairs[2 p], [2 p + 1] = file-1 and file-2 record of pair p (at most cap_pairs pairs); info[0] =
+ * pairs, [1] / [2] = complete records of window 1 / 2, [3] / [4] = records of window 1 / 2 the round decides, [5] = a key
+ * twice in one window: file << 32 | the smallest record involved (~0: none), [6] = the first pair whose file-2 record does not
+ * lie behind that of the pair before (~0: none, also with [5] set), [7] = VS_PN_STRICT: the first pair that is no pair of mates (~0: none).  With
+ * [5] or [6] set no pairs are given and nothing is decided.  _host is the one-thread twin (vs_pair_names_core.h), VS_E_STATE
+ * when the table is full; _text runs the kernels and keeps `guard` sentinel words on either side of the device pair list
+ * (room for min(R1, R2) pairs), VS_E_STATE if one changed, a word of the list stayed unwritten or one behind it was written. */
+enum { VS_PN_STRICT = 0, VS_PN_SINGLES = 1 };
+typedef struct vs_fastq_pn vs_fastq_pn;
+int vs_fastq_pn_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, int mode, vs_fastq_pn **out);
+int vs_fastq_pn_next(vs_ctx *ctx, vs_fastq_pn *s, uint64_t max_pairs, vs_reads **out, uint64_t *n_pairs);
+int vs_fastq_pn_info(const vs_fastq_pn *s, uint64_t info[10]);
+void vs_fastq_pn_close(vs_fastq_pn *s);
+int vs_fastq_join_host(const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
+                       uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint64_t info[8]);
+int vs_fastq_join_text(vs_ctx *ctx, const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
+                       uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint32_t guard, uint64_t info[8]);
 /* Member-sharded open of ONE collated BAM for one process per GPU (additions to ABI 10): no rank inflates the whole file and
  * nothing is inflated on a host.  Rank r of W takes the BGZF members [M r / W, M (r + 1) / W) of vs_bgzf_walk_file, its
  * "share": the inflated bytes [S_r, S_r + E_r).  A share cannot be entered at a guessed record start, so pass 1 follows the

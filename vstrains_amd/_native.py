@@ -91,6 +91,14 @@ SYMBOLS = {
     "vs_fastq_il_close": (None, [C.c_void_p]),
     "vs_fastq_mates_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vs_fastq_mates_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "vs_fastq_pn_open": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "vs_fastq_pn_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "vs_fastq_pn_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "vs_fastq_pn_close": (None, [C.c_void_p]),
+    "vs_fastq_join_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                     C.POINTER(C.c_uint64)]),
+    "vs_fastq_join_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
+                                     C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     "vs_write_matrix_text": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "vs_write_info_sparse": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),

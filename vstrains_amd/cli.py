@@ -68,6 +68,14 @@ def build_parser():
     p.add_argument("--interleaved-singles", dest="interleaved_singles", action="store_true", default=False,
                    help="extension: with --interleaved, records without their mate beside them (the single reads `samtools fastq "
                         "x.bam` writes among the pairs) are dropped and counted instead")
+    p.add_argument("--check-names", dest="check_names", action="store_true", default=False,
+                   help="extension: pair the two FASTQ files by read name on the device instead of by position: record i of -fwd and "
+                        "record i of -rve must be mates by name (as `bwa mem` demands), and the first pair that is not stops the run -- "
+                        "what two files trimmed or filtered separately would otherwise turn into wrong links unnoticed (not together "
+                        "with --pe-text-from)")
+    p.add_argument("--check-names-singles", dest="check_names_singles", action="store_true", default=False,
+                   help="extension: with --check-names, the two files are in the same order but either may lack records the other has; "
+                        "mates are found by a hash join on the names, records without a mate are dropped and counted per file")
     p.add_argument("--gzip-device", dest="gzip_device", action="store_true", default=False,
                    help="extension: decode plain .fastq.gz (one deflate stream, as gzip and pigz write it) on the device, in parallel "
                         "from speculative block starts, instead of with zlib on one host core (sets VS_GZIP_DEVICE=1; one process only)")
@@ -102,7 +110,8 @@ def main(argv=None, backend=None):
         parser.error("--no-pe-text and --bgzf-pe-text are mutually exclusive")
     if args.pe_text_from is not None:
         for flag, name in ((args.no_pe_text, "--no-pe-text"), (args.sparse_pe_text, "--sparse-pe-text"), (args.bgzf_pe_text, "--bgzf-pe-text"),
-                           (args.bam_by_name, "--bam-by-name"), (args.interleaved or args.interleaved_singles, "--interleaved")):
+                           (args.bam_by_name, "--bam-by-name"), (args.interleaved or args.interleaved_singles, "--interleaved"),
+                           (args.check_names or args.check_names_singles, "--check-names")):
             if flag:
                 parser.error("--pe-text-from and %s are mutually exclusive" % name)
     from . import pe_inference
@@ -110,6 +119,9 @@ def main(argv=None, backend=None):
     # (what the flags cannot apply to is a ValueError that says why, before anything is written or a device opened)
     args.interleaved = pe_inference.interleaved_mode(args.interleaved, args.interleaved_singles)
     pe_inference.interleaved_input(args.fwd, args.rve, pe_inference._rank_world()[1], args.interleaved)
+    args.check_names = pe_inference.check_names_mode(args.check_names, args.check_names_singles)
+    pe_inference.check_names_input(args.fwd, args.rve, pe_inference._rank_world()[1], args.check_names, bam_by_name=args.bam_by_name,
+                                   interleaved=args.interleaved)
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
         _bail("\nPath to the assembly graph is required, (.gfa format)", "Please ensure the path is correct")
     args.pe_text_files = None
@@ -186,12 +198,16 @@ def main(argv=None, backend=None):
 
     from .graph import pipeline
 
-    if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text or args.bam_by_name or args.interleaved):
+    if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text or args.bam_by_name or args.interleaved or
+                            args.check_names):
         from .graph.hip_ops import HipBackend
 
         backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text,
-                             bgzf_info_text=args.bgzf_pe_text, bam_by_name=args.bam_by_name, interleaved=args.interleaved)
+                             bgzf_info_text=args.bgzf_pe_text, bam_by_name=args.bam_by_name, interleaved=args.interleaved,
+                             check_names=args.check_names)
     elif backend is not None:
+        if args.check_names:
+            backend.check_names = args.check_names
         if args.interleaved:
             backend.interleaved = args.interleaved
         if args.bam_by_name:

@@ -209,6 +209,9 @@ void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, cons
 // k_pack_reads for the records rec[0, r->n_ends) of ONE window (the interleaved ingest, vs_interleaved.hip): end e is the
 // sequence line of record rec[e]
 void vs_launch_pack_records(hipStream_t st, const SlWin &w, const uint32_t *rec, const vs_reads *r);
+// k_pack_reads for the records of TWO windows joined by name (vs_pair_names.hip): end e is the sequence line of record
+// rec[e] of window e & 1 (k_pn_ends has range-tested every rec[e] before)
+void vs_launch_pack_pairs(hipStream_t st, const SlWin &f0, const SlWin &f1, const uint32_t *rec, const vs_reads *r);
 // exclusive scan of a[0, m) in place by one workgroup (k_sl_scan of vs_stream.hip); the total, below 2^32, to *total
 void vs_launch_scan_u32(hipStream_t st, uint32_t *a, uint32_t m, uint32_t *total);
 // The ends of a block of the BAM ingest (vs_bam.hip): end e is record ends[e] of recs (BamRec of vs_bam_core.h: four words,

@@ -45,6 +45,16 @@ struct PackRecords {  // ONE window of the interleaved ingest: end e is line 4 r
         return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
     }
 };
+struct PackPairs {  // TWO windows joined by name (vs_pair_names.hip): end e is line 4 rec[e] + 1 of file e & 1, without its newline
+    SlWin f0, f1;
+    const uint32_t *rec;
+    __device__ PackBytes open(uint32_t e) const {
+        const SlWin &w = (e & 1u) ? f1 : f0;
+        const uint32_t r = rec[e];
+        const uint32_t start = w.ends[4u * r] + 1u;
+        return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
+    }
+};
 struct PackBamEnd {  // 4-bit bases, read backwards and complemented where the record's flag has 0x10
     const uint8_t *seq;
     uint32_t len;
@@ -98,6 +108,7 @@ static void launch_pack(hipStream_t st, const Src &src, const vs_reads *r) {
 }
 void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, const vs_reads *r) { launch_pack(st, PackLines{f0, f1}, r); }
 void vs_launch_pack_records(hipStream_t st, const SlWin &w, const uint32_t *rec, const vs_reads *r) { launch_pack(st, PackRecords{w, rec}, r); }
+void vs_launch_pack_pairs(hipStream_t st, const SlWin &f0, const SlWin &f1, const uint32_t *rec, const vs_reads *r) { launch_pack(st, PackPairs{f0, f1, rec}, r); }
 void vs_launch_pack_bam(hipStream_t st, const BamEnds &b, const vs_reads *r) { launch_pack(st, PackBam{b}, r); }
 
 __global__ void __launch_bounds__(TPB)

@@ -206,6 +206,10 @@ def _run(args, logger, backend=None):
     singles = (getattr(backend, "interleaved_info", None) or {}).get("singles", 0)
     if singles:
         logger.info("{0} records of the interleaved FASTQ have no mate beside them and were dropped".format(singles))
+    by_names = getattr(backend, "pair_names_info", None) or {}
+    if by_names.get("singles_fwd", 0) or by_names.get("singles_rve", 0):
+        logger.info("{0} records of {1} and {2} records of {3} have no mate by name in the other file and were dropped".format(
+            by_names["singles_fwd"], args.fwd, by_names["singles_rve"], args.rve))
     logger.info("paired end information stored")
 
     t0 = time.time()

@@ -508,6 +508,103 @@ def fastq_mates(text: bytes, eof: bool = True, ctx: "Context" = None, guard: int
                                       first_single=None if info[4] == none else int(info[4]), records=int(info[5]))
 
 
+class PairedNameStream:
+    """The read pairs of TWO FASTQ files paired by read NAME on the device, through ``vs_fastq_pn_*``: the two files of
+    ``FastqStream``, read front to back in every form that stream reads, but a pair is a pair of mates by name (the rule of
+    ``InterleavedStream``: name tokens equal byte for byte, a ``/1`` on the file-1 record and ``/2`` on the file-2 record
+    dropped).  ``singles=False`` (strict): pair p is record p of either file; the first that is no pair of mates, or a
+    complete record left over in the longer file, raises ``ValueError`` naming both paths, the pair (numbered from 0 in file
+    order) and both header lines.  ``singles=True``: the files are in the same order but either may lack records the other
+    has (trimmed or filtered separately); mates are found by a hash join on the names, records without a mate are dropped and
+    counted per file, and the result is that of the two files filtered to their shared names, whatever the chunk size.  A name
+    twice in one file's window, mates out of order inside a pair of windows, and a window beyond ``VS_PAIR_WINDOW`` bytes
+    without a decision raise ``ValueError``.  Interface of ``FastqStream``; ``info`` has ``pairs``, ``singles_fwd``,
+    ``singles_rve``, ``records_fwd``, ``records_rve``, ``windows``, ``max_window_bytes``, ``text_bytes``, ``file_bytes``,
+    ``flags``."""
+
+    def __init__(self, fwd: str, rve: str, ctx: "Context", block_pairs: int = 1 << 20, singles: bool = False):
+        self._ctx = ctx
+        self._h = None
+        self.block_pairs = block_pairs
+        self.singles = bool(singles)
+        h = C.c_void_p()
+        rc = nat.lib().vs_fastq_pn_open(ctx._h, os.fspath(fwd).encode(), os.fspath(rve).encode(), 1 if singles else 0, C.byref(h))
+        if rc != nat.VS_OK:
+            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+            if "cannot open" in msg:
+                raise FileNotFoundError(msg)
+            raise nat.NativeError(rc, msg)
+        self._h = h
+
+    @property
+    def info(self):
+        a = (C.c_uint64 * 10)()
+        nat.lib().vs_fastq_pn_info(self._h, a)
+        return dict(pairs=int(a[0]), singles_fwd=int(a[1]), singles_rve=int(a[2]), records_fwd=int(a[3]), records_rve=int(a[4]), windows=int(a[5]),
+                    max_window_bytes=int(a[6]), text_bytes=int(a[7]), file_bytes=int(a[8]), flags=int(a[9]))
+
+    @property
+    def n_pairs(self) -> int:
+        """pairs delivered so far (all of them once the iteration has ended)"""
+        return self.info["pairs"]
+
+    def next_block(self) -> Optional["ReadBlock"]:
+        """The next block, or None at the end of the input."""
+        h = C.c_void_p()
+        n = C.c_uint64(0)
+        rc = nat.lib().vs_fastq_pn_next(self._ctx._h, self._h, self.block_pairs, C.byref(h), C.byref(n))
+        if rc in (nat.VS_E_ARG, nat.VS_E_RANGE):  # (names that do not pair, a name twice, mates out of order, a window without a decision)
+            raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
+        if rc != nat.VS_OK:
+            FastqPair._raise(self._ctx._h, rc)  # ValueError for bytes that are not valid UTF-8
+        return ReadBlock(self._ctx, h) if n.value else None
+
+    def __iter__(self):
+        while True:
+            block = self.next_block()
+            if block is None:
+                return
+            yield block
+
+    def close(self):
+        if self._h:
+            nat.lib().vs_fastq_pn_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fastq_join(text0: bytes, text1: bytes, eof0: bool = True, eof1: bool = True, ctx: "Context" = None, singles: bool = True, table: int = 0,
+               name_bits: int = 0, guard: int = 64):
+    """The join by name of ONE pair of FASTQ windows, bytes as they are (test aid): ``vs_fastq_join_host`` (one host thread),
+    or with ``ctx`` the kernels (``vs_fastq_join_text``, ``guard`` sentinel words around the device pair list).  ``eof0`` /
+    ``eof1``: the file ends with its window.  ``table``: slots of the open-address table (0: the stream's choice);
+    ``name_bits``: low bits of the name hash kept (0: all).  Returns (pairs uint32 [n, 2]: record of window 1, record of
+    window 2; info dict: ``pairs``, ``records`` and ``decided`` (a pair of counts each), ``duplicate`` = (file, record) or
+    None, ``order`` = the first pair out of order or None, ``first_bad`` = strict: the first pair that is no pair of mates,
+    or None)."""
+    b0, b1 = (np.frombuffer(t or b"\0", dtype=np.uint8) for t in (text0, text1))
+    cap = min(len(text0), len(text1)) // 8 + 1
+    pairs = np.zeros((cap, 2), dtype=np.uint32)
+    info = (C.c_uint64 * 8)()
+    args = (b0.ctypes.data, len(text0), b1.ctypes.data, len(text1), 1 if eof0 else 0, 1 if eof1 else 0, 1 if singles else 0, table, name_bits, pairs.ctypes.data, cap)
+    if ctx is None:
+        rc = nat.lib().vs_fastq_join_host(*args, info)
+        if rc != nat.VS_OK:
+            raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    else:
+        nat.check(ctx._h, nat.lib().vs_fastq_join_text(ctx._h, *args, guard, info))
+    none = (1 << 64) - 1
+    opt = lambda v: None if v == none else int(v)
+    return pairs[:int(info[0])], dict(pairs=int(info[0]), records=(int(info[1]), int(info[2])), decided=(int(info[3]), int(info[4])),
+                                      duplicate=None if info[5] == none else (int(info[5] >> 32), int(info[5] & 0xFFFFFFFF)), order=opt(info[6]),
+                                      first_bad=opt(info[7]))
+
+
 class BamStream:
     """The read pairs of ONE collated BAM file (unaligned BAM from the sequencer, or the unmapped pairs of a host
     alignment after ``samtools collate``) through ``vs_bam_stream_*``: the BGZF members inflated on the device, the records

@@ -27,7 +27,8 @@ def _rank_world():
     return 0, 1
 
 
-def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow: bool = False, bam_by_name: bool = False, interleaved=None):
+def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow: bool = False, bam_by_name: bool = False, interleaved=None,
+                check_names=None):
     """Index the nodes of ``gfa`` and count every pair of the two FASTQ files; the counters stay
     on the device.  Returns ``(node ids in file order, PeCounter)``.  ``stages_follow``: the graph stages will build their
     PE-link table from these counters in this process (the pipeline; not the stand-alone script, which writes the two text
@@ -36,16 +37,21 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     stream's ``info`` (``singletons`` among it), else None.  ``interleaved`` (None, ``"strict"`` or ``"singles"``): the inputs
     are ONE interleaved FASTQ, each pair's two records one behind the other, the mates checked by name on the device
     (``InterleavedStream``; ``"singles"`` drops and counts the records without a mate, ``"strict"`` refuses the first);
-    ``count_links.interleaved_info`` is then the stream's ``info``, else None."""
+    ``count_links.interleaved_info`` is then the stream's ``info``, else None.  ``check_names`` (None, ``"strict"`` or
+    ``"singles"``): the two FASTQ files are paired by read name on the device (``PairedNameStream``, whatever ``use_stream``
+    says; ``"strict"`` refuses the first pair that is no pair of mates, ``"singles"`` joins the files by name and drops and
+    counts the records without a mate); ``count_links.pair_names_info`` is then the stream's ``info``, else None."""
     rank, world = _rank_world()
     count_links.bam_info = None
     count_links.interleaved_info = None
+    count_links.pair_names_info = None
+    by_names = check_names_input(fwd, rve, world, check_names, bam_by_name=bam_by_name, interleaved=interleaved)  # (False without the flag)
     il_path = interleaved_input(fwd, rve, world, interleaved)  # (None without the flag; what it cannot apply to is a ValueError)
     why = gzip_device_refusal(world)  # (reads the environment only; None with the switch unset)
     if why is not None:
         raise ValueError(why)
-    bam = None if il_path else bam_input(fwd, rve, world, by_name=bam_by_name, sharded=not bam_by_name)  # (a collated BAM is shared by member)
-    streamed = bam is None and not il_path and use_stream(fwd, rve)
+    bam = None if il_path or by_names else bam_input(fwd, rve, world, by_name=bam_by_name, sharded=not bam_by_name)  # (a collated BAM is shared by member)
+    streamed = bam is None and not il_path and not by_names and use_stream(fwd, rve)
     if world > 1 and not (_regular(fwd) and _regular(rve)):  # (the sharded path maps regular files; VS_FASTQ_STREAM aside)
         raise ValueError("the FASTQ inputs %s / %s are not both regular files: a pipe can be read by one process only, so "
                          "the sharded (torchrun) run cannot take it; run one process, or write the reads to files" % (fwd, rve))
@@ -65,6 +71,16 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
             count_links.interleaved_info = fq.info
         finally:
             fq.close()
+    elif by_names:
+        fq = host.PairedNameStream(fwd, rve, ctx, block_pairs=BATCH_PAIRS, singles=(check_names == "singles"))  # both files, each read once
+        try:
+            count_stream(ctx, fq, counter, progress=True)
+            count_links.pair_names_info = info = fq.info
+        finally:
+            fq.close()
+        if check_names == "singles":
+            print("Pairs joined by read name: %d; records without a mate dropped: %d of %s, %d of %s"
+                  % (info["pairs"], info["singles_fwd"], fwd, info["singles_rve"], rve))
     elif bam is not None and world > 1:
         # one collated whole-BGZF BAM: the ranks share it by member, summarise their shares for every entry the previous share
         # could hand them, and each streams its own couples (BamStream.open_shard); why == the reason when rank 0 reads the
@@ -250,6 +266,42 @@ def interleaved_input(fwd: str, rve: str, world: int = 1, interleaved=None):
     return fwd
 
 
+def check_names_mode(check_names: bool, singles: bool):
+    """The two flags of the commands as ``count_links`` takes them: None, ``"strict"`` or ``"singles"``."""
+    if singles and not check_names:
+        raise ValueError("--check-names-singles says what to do with the records of two FASTQ files that have no mate in the other "
+                         "file and needs --check-names, which says that the two files are paired by read name")
+    return ("singles" if singles else "strict") if check_names else None
+
+
+def check_names_input(fwd: str, rve: str, world: int = 1, check_names=None, bam_by_name: bool = False, interleaved=None) -> bool:
+    """True when ``check_names`` (``--check-names``) asks for the two FASTQ files to be paired by read name
+    (``PairedNameStream``), False without the flag.  ``ValueError`` for what the flag cannot apply to, before a device is
+    opened: together with ``--interleaved`` or ``--bam-by-name`` (those inputs are checked or joined by name already), a BAM
+    input, ``VS_FASTQ_STREAM=0``, a process group of more than one rank."""
+    if check_names is None:
+        return False
+    if check_names not in ("strict", "singles"):
+        raise ValueError("check_names is None, 'strict' or 'singles', not %r" % (check_names,))
+    if interleaved is not None:
+        raise ValueError("--check-names pairs TWO FASTQ files by read name, and --interleaved reads one file whose mates are checked by "
+                         "name already: set one of the two")
+    if bam_by_name:
+        raise ValueError("--check-names pairs two FASTQ files by read name, and --bam-by-name joins the records of one BAM by name "
+                         "already: set one of the two")
+    for path in (fwd, rve):
+        if _starts_bam(path):
+            raise ValueError("%s is a BAM file, and --check-names pairs two FASTQ files by read name; leave the flag out (a collated BAM "
+                             "is checked by its first / second flags, one in any record order is joined with --bam-by-name)" % path)
+    if os.environ.get("VS_FASTQ_STREAM") == "0":
+        raise ValueError("--check-names reads its files in the streamed ingest, and VS_FASTQ_STREAM=0 asks for the mapped open: set one "
+                         "of the two")
+    if world > 1:
+        raise ValueError("%s / %s: --check-names reads the two files in one process only; pairing by name among the %d ranks of this "
+                         "process group is not built: run without torchrun" % (fwd, rve, world))
+    return True
+
+
 def member_shard_refusal(fwd: str, rve: str):
     """None when a sharded run tries the member-sharded open (both inputs regular files that start with a BGZF member, and
     neither ``VS_FASTQ_STREAM=0`` nor ``VS_BGZF_DEVICE=0`` -- the switches that give the mapped open and host zlib in
@@ -392,7 +444,7 @@ def write_info_files(out_dir: str, ids, counter, sparse: bool = False, bgzf: boo
 
 
 def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int = 0, ctx=None, stages_follow: bool = False,
-        sparse_info: bool = False, bgzf_info: bool = False, bam_by_name: bool = False, interleaved=None):
+        sparse_info: bool = False, bgzf_info: bool = False, bam_by_name: bool = False, interleaved=None, check_names=None):
     # PE_Inference.py:93-96: the output directory is wiped and recreated
     if out_dir[-1] == "/":
         out_dir = out_dir[:-1]
@@ -409,9 +461,11 @@ def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int 
     if bam_by_name:
         bam_input(fwd, rve, world, by_name=True)  # (what the flag cannot apply to is said before a device is opened)
     interleaved_input(fwd, rve, world, interleaved)  # (the same)
+    check_names_input(fwd, rve, world, check_names, bam_by_name=bam_by_name, interleaved=interleaved)  # (the same)
     if ctx is None:
         ctx = host.Context(device)
-    ids, counter = count_links(ctx, gfa, fwd, rve, kmer_size, stages_follow=stages_follow, bam_by_name=bam_by_name, interleaved=interleaved)
+    ids, counter = count_links(ctx, gfa, fwd, rve, kmer_size, stages_follow=stages_follow, bam_by_name=bam_by_name, interleaved=interleaved,
+                               check_names=check_names)
     run.last = (ids, counter)
     if rank != 0:
         return None  # the counters were reduced to rank 0, which writes the files
@@ -454,12 +508,21 @@ def main(argv=None):
     parser.add_argument("--interleaved-singles", dest="interleaved_singles", action="store_true", default=False,
                         help="extension: with --interleaved, records without their mate beside them (the single reads `samtools "
                              "fastq x.bam` writes among the pairs) are dropped and counted instead")
+    parser.add_argument("--check-names", dest="check_names", action="store_true", default=False,
+                        help="extension: pair the two FASTQ files by read name on the device instead of by position: record i of -f and "
+                             "record i of -r must be mates by name (as `bwa mem` demands), and the first pair that is not stops the run "
+                             "-- what two files trimmed or filtered separately would otherwise turn into wrong links unnoticed")
+    parser.add_argument("--check-names-singles", dest="check_names_singles", action="store_true", default=False,
+                        help="extension: with --check-names, the two files are in the same order but either may lack records the other "
+                             "has; mates are found by a hash join on the names, records without a mate are dropped and counted per file")
     args = parser.parse_args(argv)
     interleaved = interleaved_mode(args.interleaved, args.interleaved_singles)
+    check_names = check_names_mode(args.check_names, args.check_names_singles)
     if args.gzip_device:
         os.environ["VS_GZIP_DEVICE"] = "1"  # (the library reads the switch where it reads VS_BGZF_DEVICE)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     interleaved_input(args.fwd, args.rve, world, interleaved)  # (refused before a device is opened or a process group made)
+    check_names_input(args.fwd, args.rve, world, check_names, bam_by_name=args.bam_by_name, interleaved=interleaved)  # (the same)
     if world > 1:  # launched by torchrun: one rank per GPU, counters all-reduced over RCCL
         import torch
         import torch.distributed as dist
@@ -480,7 +543,7 @@ def main(argv=None):
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
         os.environ.setdefault("VS_HOST_THREADS", str(max(1, (os.cpu_count() or 1) // max(local_world, 1))))
     run(args.gfa, args.dir, args.fwd, args.rve, args.kmer_size, args.device, sparse_info=args.sparse_info, bgzf_info=args.bgzf_info,
-        bam_by_name=args.bam_by_name, interleaved=interleaved)
+        bam_by_name=args.bam_by_name, interleaved=interleaved, check_names=check_names)
     if world > 1:
         import torch.distributed as dist
 
