@@ -27,30 +27,46 @@ class HipGraphOps(GraphOps):
         self.ctx = ctx
         self.calls = 0
 
-    def _refresh(self, g: AsmGraph):
-        nv = g.num_vertices()
-        row_ptr, n_out, nbr, eidx = g.csr_arrays()
-        a_row = np.asarray(row_ptr, dtype=np.uint64)
-        a_no = np.asarray(n_out, dtype=np.uint32)
-        a_nbr = np.asarray(nbr, dtype=np.uint32)
-        a_eidx = np.asarray(eidx, dtype=np.uint32)
-        a_dp = np.asarray(g.vdp, dtype=np.float64)
-        a_vb = np.asarray(g.vblack, dtype=np.uint8)
-        n_slots = len(g.esrc)
-        a_eb = np.asarray(g.eblack, dtype=np.uint8) if n_slots else np.zeros(1, dtype=np.uint8)
-        flow = np.zeros(max(n_slots, 1), dtype=np.float64)
-        nt = np.zeros(max(nv, 1), dtype=np.uint8)
-        fk = np.zeros(max(nv, 1), dtype=np.uint8)
-        nxt = np.full(max(nv, 1), -1, dtype=np.int32)
-        top = np.zeros(max(nv, 1), dtype=np.int32)
-        rank = np.zeros(max(nv, 1), dtype=np.int32)
+    #: the outputs of ``vs_graph_refresh``, in the order of its arguments
+    OUTPUTS = ("flow", "nontrivial", "fork_kind", "chain_next", "chain_top", "chain_rank", "zero_sum_edge")
+
+    def refresh_csr(self, row_ptr, n_out, nbr, eidx, dp, vertex_black, edge_black, n_edge_slots, outputs=OUTPUTS):
+        """(testing aid) ``vs_graph_refresh`` on raw arrays, as the header describes them: the adjacency rows, dp, the
+        colours and the number of edge slots are handed over as they are (an array given as ``None`` or empty goes as
+        NULL), nothing is checked here.  Only the ``outputs`` asked for get a buffer, the others are passed as NULL.
+        -> {name: array, or the int ``zero_sum_edge``}; raises ``NativeError`` with the library's code."""
+        nv = len(n_out) if n_out is not None else len(row_ptr) - 1
+        unknown = set(outputs) - set(self.OUTPUTS)
+        if unknown:
+            raise ValueError("unknown outputs %s" % sorted(unknown))
+
+        def given(a, dtype):
+            return None if a is None else np.ascontiguousarray(a, dtype=dtype)
+
+        ins = [given(row_ptr, np.uint64), given(n_out, np.uint32), given(nbr, np.uint32), given(eidx, np.uint32),
+               given(dp, np.float64), given(vertex_black, np.uint8), given(edge_black, np.uint8)]
+        got = {}
+        if "flow" in outputs:
+            got["flow"] = np.zeros(max(n_edge_slots, 1), dtype=np.float64)
+        for name, dtype, fill in (("nontrivial", np.uint8, 0), ("fork_kind", np.uint8, 0), ("chain_next", np.int32, -1),
+                                  ("chain_top", np.int32, 0), ("chain_rank", np.int32, 0)):
+            if name in outputs:
+                got[name] = np.full(max(nv, 1), fill, dtype=dtype)
         bad = C.c_uint32(0xFFFFFFFF)
+        outs = [got[name].ctypes.data if name in got else None for name in self.OUTPUTS[:-1]]
         nat.check(self.ctx._h, nat.lib().vs_graph_refresh(
-            self.ctx._h, nv, n_slots, _ptr(a_row), _ptr(a_no), _ptr(a_nbr), _ptr(a_eidx), _ptr(a_dp), _ptr(a_vb),
-            a_eb.ctypes.data, flow.ctypes.data, nt.ctypes.data, fk.ctypes.data, nxt.ctypes.data, top.ctypes.data,
-            rank.ctypes.data, C.byref(bad)))
+            self.ctx._h, nv, n_edge_slots, *[None if a is None else _ptr(a) for a in ins], *outs,
+            C.byref(bad) if "zero_sum_edge" in outputs else None))
         self.calls += 1
-        return flow, nt, fk, nxt, top, rank, bad.value
+        if "zero_sum_edge" in outputs:
+            got["zero_sum_edge"] = bad.value
+        return got
+
+    def _refresh(self, g: AsmGraph):
+        row_ptr, n_out, nbr, eidx = g.csr_arrays()
+        n_slots = len(g.esrc)
+        got = self.refresh_csr(row_ptr, n_out, nbr, eidx, g.vdp, g.vblack, g.eblack if n_slots else [0], n_slots)
+        return tuple(got[name] for name in self.OUTPUTS)
 
     @staticmethod
     def _apply_flows(g: AsmGraph, flow, bad) -> None:
