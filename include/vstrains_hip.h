@@ -104,6 +104,18 @@ int vs_reads_info(const vs_reads *reads, uint64_t info[5]);
  * non-ACGT) may be NULL. */
 int vs_reads_unpack(vs_ctx *ctx, const vs_reads *reads, uint8_t *out, uint32_t *lens,
                     uint8_t *flags);
+/* Unpaired reads (additions to ABI 11 without a new number: nothing that exists changes): a SINGLES BLOCK of n reads is a block of 2n ends in which
+ * end 2r is read r and end 2r+1 is absent (length 0, no words, flag bit 3).  The counting kernels treat read r as the
+ * reference treats ONE end of a pair (PE_Inference.py:160-184 restricted to one end): a read with an 'N' is counted as an
+ * N read and nothing else; otherwise one shorter than k+1 as a short read and nothing else; otherwise it is used:
+ * short_mat[L[a]][L[b]] += 1 for a <= b over its accepted nodes L.  node_mat is never touched.  The three words vs_pe_count
+ * adds to `stats` are then tallies of READS (with N, short, used): hand it a stats array of its own to keep them apart
+ * from the pairs'.  A block spends one empty end slot per read (8 bytes).
+ *   vs_reads_pack_single : as vs_reads_pack from host text, off[n_reads + 1], one read per slot; vs_reads_info says
+ *                          ends = 2 n_reads, vs_reads_unpack returns the absent ends with length 0 (flags bit 3 set)
+ *   vs_reads_unpaired    : 1 for a singles block, 0 for a block of pairs (all slots of a block are one or the other) */
+int vs_reads_pack_single(vs_ctx *ctx, const uint8_t *ascii, const uint64_t *off, uint64_t n_reads, vs_reads **out);
+int vs_reads_unpaired(const vs_reads *reads);
 
 /* ---- FASTQ ingest (host, multi-threaded) -----------------------------------------------------
  * Replaces PE_Inference.py:146-159: both files read in text mode (universal newlines), record r
@@ -363,9 +375,14 @@ int vs_bam_mates_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t sk
  * the pairs).
  *   vs_fastq_il_open  : mode VS_IL_STRICT: the first single record fails the stream with VS_E_ARG -- the message names the
  *                       path, the file-wide 0-based record number and both header lines (the single's and its successor's,
- *                       or "end of file"); VS_IL_SINGLES: single records are dropped and counted
- *   vs_fastq_il_next  : as vs_fastq_stream_next
- *   vs_fastq_il_info  : info[0] = pairs delivered, [1] = singles dropped, [2] = records decided, [3] = text bytes read
+ *                       or "end of file"); VS_IL_SINGLES: single records are dropped and counted; VS_IL_KEEP (an addition to
+ *                       ABI 11, the other modes unchanged): classified as VS_IL_SINGLES, but the single records are KEPT -- when
+ *                       the pairs of a window are out, its single records are handed out in file order as singles blocks
+ *                       (vs_reads_pack_single above has the layout).  A record held back stays held; at the end of the file it
+ *                       is a single and is handed out.  No mixed block is ever made
+ *   vs_fastq_il_next  : as vs_fastq_stream_next; under VS_IL_KEEP *n_pairs is the number of SLOTS of the block and
+ *                       vs_reads_unpaired tells its kind
+ *   vs_fastq_il_info  : info[0] = pairs delivered, [1] = single records (dropped, or kept under VS_IL_KEEP), [2] = records decided, [3] = text bytes read
  *                       (inflated), [4] = file bytes read (compressed), [5] = flags as vs_fastq_stream_info (bit 2: gzip)
  *   vs_fastq_il_close : as vs_fastq_stream_close
  * Test aids, the match of ONE window of n text bytes as they are (no text-mode translation); eof: the file ends with the
@@ -374,7 +391,7 @@ int vs_bam_mates_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t sk
  * info[0] = pairs, [1] = singles, [2] = records decided, [3] = the record held back (~0: none), [4] = the first single (~0:
  * none), [5] = complete records.  _host is the one-thread twin (vs_mates_core.h); _text runs the kernels and keeps `guard`
  * sentinel words on either side of the device pair list, VS_E_STATE if one changed or a word of the list stayed unwritten. */
-enum { VS_IL_STRICT = 0, VS_IL_SINGLES = 1 };
+enum { VS_IL_STRICT = 0, VS_IL_SINGLES = 1, VS_IL_KEEP = 2 };
 typedef struct vs_fastq_il vs_fastq_il;
 int vs_fastq_il_open(vs_ctx *ctx, const char *path, int mode, vs_fastq_il **out);
 int vs_fastq_il_next(vs_ctx *ctx, vs_fastq_il *s, uint64_t max_pairs, vs_reads **out, uint64_t *n_pairs);
@@ -383,6 +400,24 @@ void vs_fastq_il_close(vs_fastq_il *s);
 int vs_fastq_mates_host(const uint8_t *text, uint64_t n, int eof, uint32_t *pairs, uint64_t cap_pairs, uint64_t info[6]);
 int vs_fastq_mates_text(vs_ctx *ctx, const uint8_t *text, uint64_t n, int eof, uint32_t *pairs, uint64_t cap_pairs, uint32_t guard,
                         uint64_t info[6]);
+/* ONE file of unpaired reads (additions to ABI 11 without a new number: nothing that exists changes): the unpaired survivors of
+ * a trimmer, the merged reads of an overlapping library.  Streamed as vs_fastq_il_* streams one file, in every form that
+ * stream reads (plain, FIFO, gzip through zlib, BGZF inflated on the device, plain gzip on the device with VS_GZIP_DEVICE=1),
+ * without the matching: every complete record is one read.  Records, '\r', bytes >= 0x80, a final line without a newline and
+ * a trailing group of fewer than four lines as there.  The blocks are singles blocks (vs_reads_pack_single above), built on
+ * the device; no record text comes back to the host.
+ *   vs_fastq_se_open  : opens the file and starts its reader
+ *   vs_fastq_se_next  : the next block of up to max_reads reads (0 = 2^30), *n_reads = its reads = its slots; *out == NULL
+ *                       at the end.  A sequence line of more than 2^24 - 1 bytes is VS_E_RANGE, the message names the path
+ *                       and the file-wide 0-based record number
+ *   vs_fastq_se_info  : info[0] = reads delivered, [1] = complete records seen, [2] = text bytes read (inflated), [3] = file
+ *                       bytes read (compressed), [4] = flags as vs_fastq_il_info's info[5], [5] = 0
+ *   vs_fastq_se_close : as vs_fastq_stream_close */
+typedef struct vs_fastq_se vs_fastq_se;
+int vs_fastq_se_open(vs_ctx *ctx, const char *path, vs_fastq_se **out);
+int vs_fastq_se_next(vs_ctx *ctx, vs_fastq_se *s, uint64_t max_reads, vs_reads **out, uint64_t *n_reads);
+int vs_fastq_se_info(const vs_fastq_se *s, uint64_t info[6]);
+void vs_fastq_se_close(vs_fastq_se *s);
 /* Two FASTQ files paired by READ NAME (additions to ABI 11): the two files of vs_fastq_stream_*, in every form that stream
  * reads, but a pair is a pair of mates by name, decided on the device.  Records, the name token and mates(a, b) as for the
  * interleaved FASTQ above; a = the header line of the file-1 record, b = that of the file-2 record.

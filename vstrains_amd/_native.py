@@ -28,6 +28,8 @@ SYMBOLS = {
     "vs_index_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "vs_node_order_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "vs_reads_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "vs_reads_pack_single": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "vs_reads_unpaired": (C.c_int, [C.c_void_p]),
     "vs_reads_free": (None, [C.c_void_p, C.c_void_p]),
     "vs_reads_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "vs_reads_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -89,6 +91,10 @@ SYMBOLS = {
     "vs_fastq_il_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "vs_fastq_il_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "vs_fastq_il_close": (None, [C.c_void_p]),
+    "vs_fastq_se_open": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "vs_fastq_se_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "vs_fastq_se_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "vs_fastq_se_close": (None, [C.c_void_p]),
     "vs_fastq_mates_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vs_fastq_mates_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     "vs_fastq_pn_open": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),

@@ -79,6 +79,14 @@ def build_parser():
     p.add_argument("--gzip-device", dest="gzip_device", action="store_true", default=False,
                    help="extension: decode plain .fastq.gz (one deflate stream, as gzip and pigz write it) on the device, in parallel "
                         "from speculative block starts, instead of with zlib on one host core (sets VS_GZIP_DEVICE=1; one process only)")
+    p.add_argument("--single", dest="single", action="append", default=[], metavar="FILE",
+                   help="extension (repeatable): a FASTQ of UNPAIRED reads -- the unpaired survivors of a trimmer, the merged reads of an "
+                        "overlapping library -- in any form the paired input takes; each read is counted into aln/st_info as the "
+                        "reference counts one end of a pair, aln/pe_info does not change (one process only; not together with "
+                        "--pe-text-from)")
+    p.add_argument("--count-singles", dest="count_singles", action="store_true", default=False,
+                   help="extension: with --interleaved --interleaved-singles, the records without their mate beside them are counted "
+                        "into aln/st_info as unpaired reads instead of dropped")
     return p
 
 
@@ -122,6 +130,8 @@ def main(argv=None, backend=None):
     args.check_names = pe_inference.check_names_mode(args.check_names, args.check_names_singles)
     pe_inference.check_names_input(args.fwd, args.rve, pe_inference._rank_world()[1], args.check_names, bam_by_name=args.bam_by_name,
                                    interleaved=args.interleaved)
+    args.single = pe_inference.unpaired_input(args.single, args.count_singles, pe_inference._rank_world()[1], args.interleaved,
+                                              pe_text_from=args.pe_text_from)
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
         _bail("\nPath to the assembly graph is required, (.gfa format)", "Please ensure the path is correct")
     args.pe_text_files = None
@@ -199,13 +209,17 @@ def main(argv=None, backend=None):
     from .graph import pipeline
 
     if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text or args.bam_by_name or args.interleaved or
-                            args.check_names):
+                            args.check_names or args.single):
         from .graph.hip_ops import HipBackend
 
         backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text,
                              bgzf_info_text=args.bgzf_pe_text, bam_by_name=args.bam_by_name, interleaved=args.interleaved,
-                             check_names=args.check_names)
+                             check_names=args.check_names, single=args.single, count_singles=args.count_singles)
     elif backend is not None:
+        if args.single:
+            backend.single = list(args.single)
+        if args.count_singles:
+            backend.count_singles = True
         if args.check_names:
             backend.check_names = args.check_names
         if args.interleaved:

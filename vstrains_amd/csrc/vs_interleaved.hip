@@ -22,6 +22,10 @@
 // the greedy rule afresh; no parity crosses a cut.
 // A block of n pairs from the cursor: k_il_ends (lengths and word counts of the ends rec[2 cursor ...]), k_sl_scan (word
 // offsets), k_pack_reads<PackRecords>, vs_reads_finish -- the layout vs_pe_count takes.
+// Mode VS_IL_KEEP keeps the single records instead of dropping them: after the window's pairs are listed, k_il_singles_count /
+// k_sl_scan / k_il_singles_emit compact the records of class single, in file order, into srec[]; when the pairs of the window
+// are out they are handed out as SINGLES blocks (vs_reads_singles_block, vs_reads.hip), before the window is cut.  The held-back
+// record stays held; at the end of the file it is a single like any other.
 // The host reads back counts, the cut and status words; no record text, except the two header lines of the message with
 // which the strict mode refuses a single record.
 #include <algorithm>
@@ -139,6 +143,36 @@ __global__ void __launch_bounds__(IL_TPB) k_il_emit(const uint8_t *__restrict__ 
     rec[2u * p + 1u] = i + 1u;
 }
 
+// VS_IL_KEEP: the single records of each workgroup counted (wg_cnt, scanned afterwards), then srec[q] = i for the q-th single
+// record i of the window -- a ballot and the counts of the wavefronts in front, as k_il_emit places the pair starts
+__global__ void __launch_bounds__(IL_TPB) k_il_singles_count(const uint8_t *__restrict__ cls, uint32_t n_rec, uint32_t *__restrict__ wg_cnt) {
+    __shared__ uint32_t wcnt[IL_TPB / VS_WAVE];
+    const uint32_t i = blockIdx.x * IL_TPB + threadIdx.x;
+    const uint64_t b = __ballot(i < n_rec && cls[i] == (uint8_t)IL_SINGLE);
+    if ((threadIdx.x & (VS_WAVE - 1u)) == 0u) wcnt[threadIdx.x / VS_WAVE] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < IL_TPB / VS_WAVE; w++) t += wcnt[w];
+        wg_cnt[blockIdx.x] = t;
+    }
+}
+
+__global__ void __launch_bounds__(IL_TPB) k_il_singles_emit(const uint8_t *__restrict__ cls, const uint32_t *__restrict__ wg_base, uint32_t n_rec,
+                                                            uint32_t n_singles, uint32_t *__restrict__ srec) {
+    __shared__ uint32_t wcnt[IL_TPB / VS_WAVE];
+    const uint32_t i = blockIdx.x * IL_TPB + threadIdx.x, lane = threadIdx.x & (VS_WAVE - 1u), wave = threadIdx.x / VS_WAVE;
+    const bool single = i < n_rec && cls[i] == (uint8_t)IL_SINGLE;
+    const uint64_t b = __ballot(single);
+    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (!single) return;
+    uint32_t q = wg_base[blockIdx.x] + (uint32_t)__popcll(b & (lane ? (~0ull >> (VS_WAVE - lane)) : 0ull));
+    for (uint32_t w = 0; w < wave; w++) q += wcnt[w];
+    if (q >= n_singles) return;  // (cannot be: the total of the scan is n_singles)
+    srec[q] = i;
+}
+
 // one thread per end of the block (and one more for the closing word offset): end e is the sequence line of record rec[e];
 // length, packed words, the longest end, the first end over the 24-bit limit
 __global__ void __launch_bounds__(IL_TPB) k_il_ends(SlWin w, const uint32_t *__restrict__ rec, uint32_t n_ends, uint32_t *__restrict__ meta,
@@ -169,6 +203,7 @@ struct IlMatch {
     VsDevBuf m, cls;          // uint8 per record: the match flag with the record behind it, the class
     VsDevBuf wgfn, wg_first;  // uint32 per workgroup: parity function -> parity at its start; pair starts -> those in front
     VsDevBuf rec;             // uint32: rec[2p], rec[2p + 1] = the records of the window's p-th pair
+    VsDevBuf srec, wg_single; // VS_IL_KEEP: srec[q] = the window's q-th single record; singles per workgroup -> those in front
     uint32_t n_rec = 0, n_pairs = 0, singles = 0, first_single = IL_NONE, decided = 0;
     bool held = false;
 };
@@ -216,6 +251,21 @@ int il_emit_device(vs_ctx *ctx, hipStream_t st, const IlMatch &mt, uint32_t *rec
     return VS_OK;
 }
 
+// VS_IL_KEEP: the single records of a classified window listed in srec (mt.singles words), in file order.  d_total: a status
+// word for the scan's total (synchronises nothing)
+int il_emit_singles_device(vs_ctx *ctx, hipStream_t st, IlMatch &mt, uint32_t *d_total) {
+    if (!mt.singles) return VS_OK;
+    const uint32_t wgs = (mt.n_rec + IL_TPB - 1u) / IL_TPB;
+    if (int rc = reserve_n<uint32_t>(ctx, mt.wg_single, (size_t)wgs + 1u)) return rc;
+    if (int rc = reserve_n<uint32_t>(ctx, mt.srec, (size_t)mt.singles)) return rc;
+    hipLaunchKernelGGL(k_il_singles_count, dim3(wgs), dim3(IL_TPB), 0, st, mt.cls.as<const uint8_t>(), mt.n_rec, mt.wg_single.as<uint32_t>());
+    vs_launch_scan_u32(st, mt.wg_single.as<uint32_t>(), wgs, d_total);
+    hipLaunchKernelGGL(k_il_singles_emit, dim3(wgs), dim3(IL_TPB), 0, st, mt.cls.as<const uint8_t>(), mt.wg_single.as<const uint32_t>(), mt.n_rec, mt.singles,
+                       mt.srec.as<uint32_t>());
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}
+
 void il_mates_info(uint64_t info[6], uint64_t pairs, uint64_t singles, uint64_t decided, bool held, uint32_t first_single, uint64_t records) {
     info[0] = pairs;
     info[1] = singles;
@@ -236,7 +286,9 @@ struct vs_fastq_il {
     IlMatch mt;
     bool matched = false;   // mt describes the window
     uint32_t pair_cur = 0;  // the first pair of the matched window not yet delivered
+    uint32_t single_cur = 0;  // VS_IL_KEEP: the first single record of the matched window not yet delivered
     bool singles_ok = false;
+    bool keep = false;  // VS_IL_KEEP: the single records are handed out as singles blocks
     VsDevBuf stat_buf, d_wcnt;
     VsPinnedBuf h_stat_buf;
     uint32_t *d_stat = nullptr, *h_stat = nullptr;  // IS_ALL words each
@@ -309,6 +361,7 @@ int il_next_window(vs_ctx *ctx, vs_fastq_il *s, bool *end) {
         if (int rc = drop_front(ctx, st, d, cut, s->mt.decided)) return il_fail(ctx, s, rc, vs_last_error(ctx));
         s->matched = false;
         s->pair_cur = 0;
+        s->single_cur = 0;
     }
     {
         SlotLease taken;  // (goes back once the stream is synchronised: the upload is done)
@@ -336,6 +389,8 @@ int il_next_window(vs_ctx *ctx, vs_fastq_il *s, bool *end) {
     }
     if (int rc = reserve_n<uint32_t>(ctx, s->mt.rec, 2u * (size_t)s->mt.n_pairs + 1u)) return il_fail(ctx, s, rc, vs_last_error(ctx));
     if (int rc = il_emit_device(ctx, st, s->mt, s->mt.rec.as<uint32_t>())) return il_fail(ctx, s, rc, vs_last_error(ctx));
+    if (s->keep)
+        if (int rc = il_emit_singles_device(ctx, st, s->mt, s->d_stat + IS_WORDS)) return il_fail(ctx, s, rc, vs_last_error(ctx));
     s->records += s->mt.decided;
     s->singles += s->mt.singles;
     *end = false;
@@ -347,12 +402,13 @@ int il_next_window(vs_ctx *ctx, vs_fastq_il *s, bool *end) {
 extern "C" {
 
 int vs_fastq_il_open(vs_ctx *ctx, const char *path, int mode, vs_fastq_il **out) {
-    if (!ctx || !path || !out || (mode != VS_IL_STRICT && mode != VS_IL_SINGLES)) return vs_fail(ctx, VS_E_ARG, "vs_fastq_il_open: bad argument");
+    if (!ctx || !path || !out || (mode != VS_IL_STRICT && mode != VS_IL_SINGLES && mode != VS_IL_KEEP)) return vs_fail(ctx, VS_E_ARG, "vs_fastq_il_open: bad argument");
     *out = nullptr;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     vs_fastq_il *s = new vs_fastq_il();
     s->device = ctx->device;
-    s->singles_ok = mode == VS_IL_SINGLES;
+    s->singles_ok = mode != VS_IL_STRICT;
+    s->keep = mode == VS_IL_KEEP;
     Reader &r = s->rd;
     if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
     if (const char *ev = getenv("VS_GZIP_DEVICE")) r.gzip_device = strcmp(ev, "1") == 0;
@@ -386,13 +442,35 @@ int vs_fastq_il_next(vs_ctx *ctx, vs_fastq_il *s, uint64_t max_pairs, vs_reads *
     VS_HIP(ctx, hipSetDevice(ctx->device));
     if (!max_pairs || max_pairs > (1ull << 30)) max_pairs = 1ull << 30;
     hipStream_t st = s->st;
-    while (!s->matched || s->pair_cur >= s->mt.n_pairs) {
+    while (!s->matched || (s->pair_cur >= s->mt.n_pairs && !(s->keep && s->single_cur < s->mt.singles))) {
         bool end = false;
         const int rc = il_next_window(ctx, s, &end);
         if (end) return rc;
     }
-    // ---- the block of n pairs from the cursor
     DevFile &d = s->df;
+    if (s->pair_cur >= s->mt.n_pairs) {
+        // ---- VS_IL_KEEP, the window's pairs are out: a singles block of n of its single records from the cursor
+        const uint64_t n = std::min<uint64_t>(s->mt.singles - s->single_cur, max_pairs);
+        const uint32_t *srec = s->mt.srec.as<const uint32_t>() + s->single_cur;
+        const SlWin win = {d.w.data(), d.ends.as<const uint32_t>(), d.n_nl, (uint32_t)d.w.size};
+        vs_reads *r = nullptr;
+        hipError_t e1 = vs_reads_singles_block(ctx, st, win, srec, 0u, n, s->d_wcnt, s->d_stat + IS_MAXLEN, s->h_stat + IS_MAXLEN, &r);
+        if (e1 == hipErrorOutOfMemory) return il_fail(ctx, s, VS_E_OOM, "vs_fastq_il_next: device buffers for the block");
+        if (e1 != hipSuccess) return il_fail(ctx, s, VS_E_HIP, std::string("vs_fastq_il_next: ") + hipGetErrorString(e1));
+        if (!r) {
+            uint32_t at = 0;
+            e1 = hipMemcpy(&at, srec + (s->h_stat[IS_TOO_LONG] >> 1), sizeof at, hipMemcpyDeviceToHost);
+            char msg[600];
+            snprintf(msg, sizeof msg, "%s: record %llu has a sequence line of more than %u bytes", s->rd.path.c_str(),
+                     (unsigned long long)(d.first_record + (e1 == hipSuccess ? at : 0u)), (unsigned)VS_LEN_MASK);
+            return il_fail(ctx, s, VS_E_RANGE, msg);
+        }
+        s->single_cur += (uint32_t)n;
+        *out = r;
+        *n_pairs = n;
+        return VS_OK;
+    }
+    // ---- the block of n pairs from the cursor
     const uint64_t n = std::min<uint64_t>(s->mt.n_pairs - s->pair_cur, max_pairs), n_ends = 2u * n;
     const uint32_t *rec = s->mt.rec.as<const uint32_t>() + 2u * (size_t)s->pair_cur;
     const SlWin win = {d.w.data(), d.ends.as<const uint32_t>(), d.n_nl, (uint32_t)d.w.size};

@@ -87,7 +87,15 @@ struct VsReadsDev {
 #define VS_FLAG_N 1u        // read holds an upper-case 'N'
 #define VS_FLAG_INVALID 2u  // read holds some other byte outside ACGT
 #define VS_FLAG_MANY 4u     // ... more of them than inv4 holds (or one beyond position 254): overflow path
+// the slot has no second end (a singles block, vs_reads_pack_single): on an odd end only, with length 0 and no words; the slot is
+// classified and counted from its even end alone.  (0x80 is taken on the host: vs_pack_host.h)
+#define VS_FLAG_ABSENT 8u
 #define VS_LEN_MASK 0x00FFFFFFu
+// The length the pair filter (PE_Inference.py:162-165) sees of a SECOND end: an absent one counts as longer than any k+1, so the
+// slot is short only if its first end is -- the same compare as for a pair, its mask one bit wider.  (An absent end has no
+// other flag, so the N test and the VS_FLAG_MANY test over both ends are the first end's alone as they stand; past the
+// filter it is an end of length 0: no seed fits it, so it is never probed, owns no list words and lists 0 nodes.)
+#define VS_FILTER_LEN_MASK (VS_LEN_MASK | (VS_FLAG_ABSENT << 24))
 
 // ---- host-side objects -----------------------------------------------------------------------
 // pinned staging of one FASTQ block in flight (vs_fastq_block): packed words (+ pad), word offsets,
@@ -158,6 +166,7 @@ struct vs_reads {
     // FASTQ ingests, one after another of about the same size) or held by the block itself in own[]
     void *d_woff = nullptr, *d_meta = nullptr, *d_words = nullptr, *d_mask = nullptr, *d_inv4 = nullptr;
     bool cached = false;
+    bool unpaired = false;  // a singles block: every odd end is VS_FLAG_ABSENT (all slots are singles, or none are)
     VsDevBuf own[5];
     hipError_t alloc(vs_ctx *ctx, void *&view, size_t bytes);  // one more array (vs_reads.hip)
     void release(vs_ctx *ctx, void *&view);                    // ... given back; view = NULL
@@ -212,6 +221,14 @@ void vs_launch_pack_records(hipStream_t st, const SlWin &w, const uint32_t *rec,
 // k_pack_reads for the records of TWO windows joined by name (vs_pair_names.hip): end e is the sequence line of record
 // rec[e] of window e & 1 (k_pn_ends has range-tested every rec[e] before)
 void vs_launch_pack_pairs(hipStream_t st, const SlWin &f0, const SlWin &f1, const uint32_t *rec, const vs_reads *r);
+// A singles block (vs_reads::unpaired) of n_reads records of ONE window, built on the device on stream st (vs_single.hip, the
+// kept singles of vs_interleaved.hip): read i is the sequence line of record rec[i], or of record first + i when rec is NULL;
+// every odd end is absent.  k_single_ends (lengths, word counts), the scan, k_pack_reads<PackSingles>, vs_reads_finish.
+// wcnt: scratch of the caller, grown here.  d4 / h4: four status words on the device / pinned, rewritten: the longest read,
+// the first END over the 24-bit limit (~0u: none), the packed words, the ends with bytes outside ACGTN.  Synchronises st.
+// hipSuccess with *out == NULL: h4[1] names an end over the limit (read h4[1] / 2 of the block).
+hipError_t vs_reads_singles_block(vs_ctx *ctx, hipStream_t st, const SlWin &win, const uint32_t *rec, uint32_t first, uint64_t n_reads, VsDevBuf &wcnt,
+                                  uint32_t *d4, uint32_t *h4, vs_reads **out);
 // exclusive scan of a[0, m) in place by one workgroup (k_sl_scan of vs_stream.hip); the total, below 2^32, to *total
 void vs_launch_scan_u32(hipStream_t st, uint32_t *a, uint32_t m, uint32_t *total);
 // The ends of a block of the BAM ingest (vs_bam.hip): end e is record ends[e] of recs (BamRec of vs_bam_core.h: four words,

@@ -632,9 +632,10 @@ k_pe_tiles(PeParams P) {
         // pair classification (PE_Inference.py:160-165): one thread per pair
         if (ltop < npair) {
             uint32_t mf = s_meta[2 * ltop], mr = s_meta[2 * ltop + 1];
+            // (a slot without a second end, VS_FLAG_ABSENT, is classified from its first end alone: VS_FILTER_LEN_MASK)
             uint32_t cls;
             if (((mf | mr) >> 24) & VS_FLAG_N) cls = 0;
-            else if ((mf & VS_LEN_MASK) < K || (mr & VS_LEN_MASK) < K) cls = 1;
+            else if ((mf & VS_LEN_MASK) < K || (mr & VS_FILTER_LEN_MASK) < K) cls = 1;
             else cls = 2;
             atomicAdd(&s_misc[12 + cls], 1u);
             uint32_t st = (cls == 2) ? 1u : 0u;
@@ -1823,7 +1824,8 @@ k_rows_sum(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ list
 __device__ __forceinline__ uint32_t vs_locus_key(const VsIndexDev &idx, const VsReadsDev &rd, uint64_t p) {
     const uint32_t mf = rd.meta[2 * p], mr = rd.meta[2 * p + 1];
     const uint32_t N = idx.n_nodes, w = idx.w, s = idx.s, K = idx.K;
-    if ((((mf | mr) >> 24) & VS_FLAG_N) || (mf & VS_LEN_MASK) < K || (mr & VS_LEN_MASK) < K) return N + 1u;
+    // (no second end, VS_FLAG_ABSENT: the filters of the first alone -- VS_FILTER_LEN_MASK)
+    if ((((mf | mr) >> 24) & VS_FLAG_N) || (mf & VS_LEN_MASK) < K || (mr & VS_FILTER_LEN_MASK) < K) return N + 1u;
     const uint32_t rlen = mf & VS_LEN_MASK;
     const uint64_t base = (uint64_t)rd.woff[2 * p] * 16u;
     const bool inv = (mf >> 24) & VS_FLAG_INVALID;

@@ -45,6 +45,17 @@ struct PackRecords {  // ONE window of the interleaved ingest: end e is line 4 r
         return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
     }
 };
+struct PackSingles {  // ONE window, unpaired reads: even end e is line 4 r + 1 of it, r = rec[e / 2] (rec == NULL: first + e / 2); odd ends are empty
+    SlWin w;
+    const uint32_t *rec;
+    uint32_t first;
+    __device__ PackBytes open(uint32_t e) const {
+        if (e & 1u) return PackBytes{w.txt, 0u};
+        const uint32_t r = rec ? rec[e >> 1] : first + (e >> 1);
+        const uint32_t start = w.ends[4u * r] + 1u;
+        return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
+    }
+};
 struct PackPairs {  // TWO windows joined by name (vs_pair_names.hip): end e is line 4 rec[e] + 1 of file e & 1, without its newline
     SlWin f0, f1;
     const uint32_t *rec;
@@ -110,6 +121,34 @@ void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, cons
 void vs_launch_pack_records(hipStream_t st, const SlWin &w, const uint32_t *rec, const vs_reads *r) { launch_pack(st, PackRecords{w, rec}, r); }
 void vs_launch_pack_pairs(hipStream_t st, const SlWin &f0, const SlWin &f1, const uint32_t *rec, const vs_reads *r) { launch_pack(st, PackPairs{f0, f1, rec}, r); }
 void vs_launch_pack_bam(hipStream_t st, const BamEnds &b, const vs_reads *r) { launch_pack(st, PackBam{b}, r); }
+
+// The lengths of a singles block: one thread per end (and one more for the closing word offset).  Even end e is the sequence
+// line of its record (as PackSingles reads it): meta = its length, wcnt = its packed words; odd ends are absent: no length,
+// no words, VS_FLAG_ABSENT.  st4[0] = the longest read (atomicMax), st4[1] = the first even end over the 24-bit limit (atomicMin).
+__global__ void __launch_bounds__(TPB)
+k_single_ends(PackSingles src, uint32_t n_ends, uint32_t *__restrict__ meta, uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st4) {
+    const uint32_t e = blockIdx.x * TPB + threadIdx.x;
+    if (e > n_ends) return;
+    if (e == n_ends) {
+        wcnt[e] = 0u;
+        return;
+    }
+    if (e & 1u) {
+        meta[e] = VS_FLAG_ABSENT << 24;
+        wcnt[e] = 0u;
+        return;
+    }
+    const uint32_t len = src.open(e).len;  // (the character dropped is the newline)
+    if (len > VS_LEN_MASK) {
+        atomicMin(&st4[1], e);
+        meta[e] = 0u;
+        wcnt[e] = 0u;
+        return;
+    }
+    meta[e] = len;
+    wcnt[e] = (len + 15u) >> 4;
+    atomicMax(&st4[0], len);
+}
 
 __global__ void __launch_bounds__(TPB)
 k_count_invalid(const uint32_t *__restrict__ meta, uint64_t n_ends, uint32_t *__restrict__ out) {
@@ -249,6 +288,44 @@ hipError_t vs_reads_finish(vs_ctx *ctx, hipStream_t st, vs_reads *r, uint32_t *d
     return hipGetLastError();
 }
 
+hipError_t vs_reads_singles_block(vs_ctx *ctx, hipStream_t st, const SlWin &win, const uint32_t *rec, uint32_t first, uint64_t n_reads, VsDevBuf &wcnt,
+                                  uint32_t *d4, uint32_t *h4, vs_reads **out) {
+    *out = nullptr;
+    const uint64_t n_ends = 2u * n_reads;
+    hipError_t e = wcnt.reserve(sizeof(uint32_t) * (n_ends + 1u));
+    if (e != hipSuccess) return e;
+    vs_reads *r = new vs_reads();
+    r->cached = true;
+    r->unpaired = true;
+    auto fail = [&](hipError_t e1) {  // (the block goes back)
+        vs_reads_free(ctx, r);
+        return e1;
+    };
+    if ((e = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true)) != hipSuccess) return fail(e);
+    e = hipMemsetAsync(d4, 0, sizeof(uint32_t) * 4u, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d4 + 1, 0xFF, sizeof(uint32_t), st);
+    if (e != hipSuccess) return fail(e);
+    const PackSingles src{win, rec, first};
+    hipLaunchKernelGGL(k_single_ends, dim3((unsigned)((n_ends + 1u + TPB - 1u) / TPB)), dim3(TPB), 0, st, src, (uint32_t)n_ends, (uint32_t *)r->d_meta,
+                       wcnt.as<uint32_t>(), d4);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(e);
+    vs_launch_scan_u32(st, wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), d4 + 2);
+    e = hipMemcpyAsync(r->d_woff, wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h4, d4, sizeof(uint32_t) * 4u, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(e);
+    if (h4[1] != 0xFFFFFFFFu) return fail(hipSuccess);  // a read over the limit: no block, the caller names the record
+    const uint64_t words = h4[2];
+    r->max_len = h4[0];
+    if ((e = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e);
+    launch_pack(st, src, r);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(e);
+    if ((e = vs_reads_finish(ctx, st, r, d4 + 3, h4 + 3)) != hipSuccess) return fail(e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e);  // (the block is complete when it is handed out)
+    *out = r;
+    return hipSuccess;
+}
+
 extern "C" void vs_reads_free(vs_ctx *ctx, vs_reads *r) {
     if (!r) return;
     if (ctx) {
@@ -286,11 +363,9 @@ static int pack_block(vs_ctx *ctx, vs_reads *r, const uint8_t *ascii, const uint
     return VS_OK;
 }
 
-extern "C" int vs_reads_pack(vs_ctx *ctx, const uint8_t *ascii, const uint64_t *off, uint64_t n_ends, vs_reads **out) {
-    if (!ctx || !off || !out) return VS_E_ARG;
-    *out = nullptr;
-    if (n_ends & 1ull) return vs_fail(ctx, VS_E_ARG, "vs_reads_pack: ends come in pairs (got %llu)", (unsigned long long)n_ends);
-    if (n_ends > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "vs_reads_pack: split the input into blocks of < 2^32 ends");
+// vs_reads_pack / vs_reads_pack_single: the host's word offsets and lengths of n_ends ends of ascii/off, then the device side
+static int pack_text(vs_ctx *ctx, const char *who, const uint8_t *ascii, const uint64_t *off, uint64_t n_ends, bool unpaired, vs_reads **out) {
+    if (n_ends > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "%s: split the input into blocks of < 2^32 ends", who);
     VS_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint32_t> woff(n_ends + 1), meta(n_ends ? n_ends : 1);
     uint64_t words = 0, maxlen = 0;
@@ -298,19 +373,43 @@ extern "C" int vs_reads_pack(vs_ctx *ctx, const uint8_t *ascii, const uint64_t *
         uint64_t len = off[e + 1] - off[e];
         if (len > VS_LEN_MASK) return vs_fail(ctx, VS_E_RANGE, "read end %llu is %llu bytes long", (unsigned long long)e, (unsigned long long)len);
         woff[e] = (uint32_t)words;
-        meta[e] = (uint32_t)len;
+        meta[e] = (uint32_t)len | ((unpaired && (e & 1ull)) ? VS_FLAG_ABSENT << 24 : 0u);
         words += (len + 15) / 16;
         if (len > maxlen) maxlen = len;
-        if (words > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "vs_reads_pack: block exceeds 2^32 packed words");
+        if (words > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "%s: block exceeds 2^32 packed words", who);
     }
     woff[n_ends] = (uint32_t)words;
     vs_reads *r = new vs_reads();
     r->max_len = maxlen;
+    r->unpaired = unpaired;
     int rc = pack_block(ctx, r, ascii, off, woff, meta);
     if (rc != VS_OK) { vs_reads_free(ctx, r); return rc; }
     *out = r;
     return VS_OK;
 }
+
+extern "C" int vs_reads_pack(vs_ctx *ctx, const uint8_t *ascii, const uint64_t *off, uint64_t n_ends, vs_reads **out) {
+    if (!ctx || !off || !out) return VS_E_ARG;
+    *out = nullptr;
+    if (n_ends & 1ull) return vs_fail(ctx, VS_E_ARG, "vs_reads_pack: ends come in pairs (got %llu)", (unsigned long long)n_ends);
+    return pack_text(ctx, "vs_reads_pack", ascii, off, n_ends, false, out);
+}
+
+// A singles block: read r is end 2r, end 2r + 1 is the empty range behind it, flagged absent
+extern "C" int vs_reads_pack_single(vs_ctx *ctx, const uint8_t *ascii, const uint64_t *off, uint64_t n_reads, vs_reads **out) {
+    if (!ctx || !off || !out) return VS_E_ARG;
+    *out = nullptr;
+    if (n_reads > 0x7FFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "vs_reads_pack_single: split the input into blocks of < 2^31 reads");
+    std::vector<uint64_t> off2(2 * n_reads + 1);
+    for (uint64_t r = 0; r < n_reads; r++) {
+        off2[2 * r] = off[r];
+        off2[2 * r + 1] = off[r + 1];
+    }
+    off2[2 * n_reads] = off[n_reads];
+    return pack_text(ctx, "vs_reads_pack_single", ascii, off2.data(), 2 * n_reads, true, out);
+}
+
+extern "C" int vs_reads_unpaired(const vs_reads *r) { return r && r->unpaired ? 1 : 0; }
 
 extern "C" int vs_reads_unpack(vs_ctx *ctx, const vs_reads *r, uint8_t *out, uint32_t *lens, uint8_t *flags) {
     if (!ctx || !r || !out) return VS_E_ARG;

@@ -373,7 +373,8 @@ class HipBackend:
     """What ``pipeline.run`` needs from the device: PE-link inference + the graph kernels."""
 
     def __init__(self, device: int = 0, write_info_text: bool = True, ctx=None, sparse_info_text: bool = False,
-                 bgzf_info_text: bool = False, bam_by_name: bool = False, interleaved=None, check_names=None):
+                 bgzf_info_text: bool = False, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
+                 count_singles: bool = False):
         from .. import pe as host
 
         self.ctx = ctx if ctx is not None else host.Context(device)  # raises NativeError without a HIP device
@@ -387,6 +388,9 @@ class HipBackend:
         self.interleaved_info = None  # that stream's info (singles dropped, ...) after pe_links
         self.check_names = check_names  # "strict" / "singles": the two FASTQ files are paired by read name on the device
         self.pair_names_info = None  # that stream's info (singles dropped per file, ...) after pe_links
+        self.single = list(single)  # files of unpaired reads, counted into the same counters after the pairs
+        self.count_singles = count_singles  # the single records of the interleaved FASTQ are counted instead of dropped
+        self.single_info = []  # per file of unpaired reads: what it added (pe_inference.count_links.single_info) after pe_links
         self.pe_stats = None
 
     def pe_links(self, gfa: str, aln_dir: str, fwd: str, rve: str, ksize: int, names: List[str]) -> HipPeLinks:
@@ -399,12 +403,15 @@ class HipBackend:
         if self.write_info_text:
             self.pe_stats = pe_inference.run(gfa, aln_dir, fwd, rve, ksize, ctx=self.ctx, stages_follow=True,
                                               sparse_info=self.sparse_info_text, bgzf_info=self.bgzf_info_text, bam_by_name=self.bam_by_name,
-                                              interleaved=self.interleaved, check_names=self.check_names)
+                                              interleaved=self.interleaved, check_names=self.check_names, single=self.single,
+                                              count_singles=self.count_singles)
             ids, counter = pe_inference.run.last
         else:
             os.makedirs(aln_dir, exist_ok=True)
             ids, counter = pe_inference.count_links(self.ctx, gfa, fwd, rve, ksize, stages_follow=True, bam_by_name=self.bam_by_name,
-                                                    interleaved=self.interleaved, check_names=self.check_names)
+                                                    interleaved=self.interleaved, check_names=self.check_names, single=self.single,
+                                                    count_singles=self.count_singles)
+        self.single_info = pe_inference.count_links.single_info
         self.bam_info = pe_inference.count_links.bam_info
         self.interleaved_info = pe_inference.count_links.interleaved_info
         self.pair_names_info = pe_inference.count_links.pair_names_info

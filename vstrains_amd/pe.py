@@ -429,16 +429,21 @@ class InterleavedStream:
     from the front as ``bwa mem -p`` pairs; any other record is a single.  The stream stands for the two files (first
     records of the pairs, second records of the pairs).  ``singles=False`` (strict): the first single raises ``ValueError``
     naming the path, the record (numbered from 0 in file order) and both header lines; ``singles=True``: singles are dropped
-    and counted.  Interface of ``FastqStream``; ``info`` has ``pairs``, ``singles``, ``records``, ``text_bytes``,
-    ``file_bytes``, ``flags``."""
+    and counted; ``singles="keep"``: classified alike, but the singles are KEPT -- when the pairs of a window are out its
+    single records follow as singles blocks (``ReadBlock.unpaired``), which a ``PeCounter`` counts as unpaired reads.
+    Interface of ``FastqStream``; ``info`` has ``pairs``, ``singles``, ``records``, ``text_bytes``, ``file_bytes``,
+    ``flags``."""
 
-    def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20, singles: bool = False):
+    def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20, singles=False):
         self._ctx = ctx
         self._h = None
         self.block_pairs = block_pairs
+        if isinstance(singles, str) and singles != "keep":
+            raise ValueError('singles is False, True or "keep" (got %r)' % (singles,))
+        self.keep = singles == "keep"
         self.singles = bool(singles)
         h = C.c_void_p()
-        rc = nat.lib().vs_fastq_il_open(ctx._h, os.fspath(path).encode(), 1 if singles else 0, C.byref(h))
+        rc = nat.lib().vs_fastq_il_open(ctx._h, os.fspath(path).encode(), 2 if self.keep else 1 if singles else 0, C.byref(h))
         if rc != nat.VS_OK:
             msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
             if "cannot open" in msg:
@@ -478,6 +483,67 @@ class InterleavedStream:
     def close(self):
         if self._h:
             nat.lib().vs_fastq_il_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SingleEndStream:
+    """The UNPAIRED reads of one FASTQ file or pipe -- the unpaired survivors of a trimmer, the merged reads of an overlapping
+    library -- through ``vs_fastq_se_*``: read front to back like ``InterleavedStream`` reads its file, in every form that
+    stream reads, every complete record one read.  The blocks are singles blocks (``ReadBlock.unpaired``) of up to
+    ``block_reads`` reads, built on the device.  ``info`` has ``reads``, ``records``, ``text_bytes``, ``file_bytes``,
+    ``flags``."""
+
+    def __init__(self, path: str, ctx: "Context", block_reads: int = 1 << 20):
+        self._ctx = ctx
+        self._h = None
+        self.block_reads = block_reads
+        h = C.c_void_p()
+        rc = nat.lib().vs_fastq_se_open(ctx._h, os.fspath(path).encode(), C.byref(h))
+        if rc != nat.VS_OK:
+            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+            if "cannot open" in msg:
+                raise FileNotFoundError(msg)
+            raise nat.NativeError(rc, msg)
+        self._h = h
+
+    @property
+    def info(self):
+        a = (C.c_uint64 * 6)()
+        nat.lib().vs_fastq_se_info(self._h, a)
+        return dict(reads=int(a[0]), records=int(a[1]), text_bytes=int(a[2]), file_bytes=int(a[3]), flags=int(a[4]))
+
+    @property
+    def n_reads(self) -> int:
+        """reads delivered so far (all of them once the iteration has ended)"""
+        return self.info["reads"]
+
+    def next_block(self) -> Optional["ReadBlock"]:
+        """The next block, or None at the end of the input."""
+        h = C.c_void_p()
+        n = C.c_uint64(0)
+        rc = nat.lib().vs_fastq_se_next(self._ctx._h, self._h, self.block_reads, C.byref(h), C.byref(n))
+        if rc == nat.VS_E_ARG:  # (a stream that is no complete gzip)
+            raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
+        if rc != nat.VS_OK:
+            FastqPair._raise(self._ctx._h, rc)  # ValueError for bytes that are not valid UTF-8
+        return ReadBlock(self._ctx, h) if n.value else None
+
+    def __iter__(self):
+        while True:
+            block = self.next_block()
+            if block is None:
+                return
+            yield block
+
+    def close(self):
+        if self._h:
+            nat.lib().vs_fastq_se_close(self._h)
             self._h = None
 
     def __del__(self):
@@ -1106,6 +1172,11 @@ class ReadBlock:
         nat.check(self._ctx._h, nat.lib().vs_reads_info(self._h, a))
         return dict(ends=a[0], words=a[1], max_len=a[2], invalid_ends=a[3], device_bytes=a[4])
 
+    @property
+    def unpaired(self) -> bool:
+        """A singles block (``Context.pack_singles``): end 2r is read r, every odd end is absent."""
+        return bool(nat.lib().vs_reads_unpaired(self._h))
+
     def unpack(self):
         inf = self.info
         n = inf["ends"]
@@ -1274,6 +1345,14 @@ class Context:
         data, off = encode_seqs(seqs)
         return self.pack(data, off)
 
+    def pack_singles(self, reads: Sequence[str]) -> ReadBlock:
+        """A singles block of unpaired reads (``vs_reads_pack_single``): one read per slot, no second end.  Counted, a read
+        is worth what the reference gives ONE end of a pair: its own short_mat triangle, nothing in node_mat."""
+        data, off = encode_seqs(list(reads))
+        h = C.c_void_p()
+        nat.check(self._h, nat.lib().vs_reads_pack_single(self._h, data.ctypes.data, off.ctypes.data, off.size - 1, C.byref(h)))
+        return ReadBlock(self, h)
+
     def synth_pairs(self, genomes: Sequence[str], cum: np.ndarray, seed: int, first_pair: int, n_pairs: int,
                     read_len: int, sub_thresh: int = 0, n_thresh: int = 0) -> ReadBlock:
         gd, go = encode_seqs(genomes)
@@ -1388,6 +1467,8 @@ class PeCounter:
         tiles = (max(n, 1) + 63) // 64
         self.tile_map = torch.zeros(2 * tiles * tiles, dtype=torch.uint8, device=self.device) if track_tiles else None
         self.stats = torch.zeros(3, dtype=torch.int64, device=self.device)
+        # unpaired reads (singles blocks) with N / shorter than k+1 / used: kept apart from the pairs' ``stats``
+        self.single_stats = torch.zeros(3, dtype=torch.int64, device=self.device)
         self.wide = None          # int64 totals, allocated by the first fold
         self.pairs_in_buffer = 0  # pairs counted into ``mats`` since it was last empty (all ranks, after a sum)
         self.pairs_seen = 0
@@ -1427,6 +1508,7 @@ class PeCounter:
         else:
             self.mats.zero_()
         self.stats.zero_()
+        self.single_stats.zero_()
         if self.wide is not None:
             self.wide.zero_()
         self.pairs_in_buffer = 0
@@ -1446,8 +1528,11 @@ class PeCounter:
         self.pairs_in_buffer = 0
 
     def add(self, reads: ReadBlock):
+        """Count one block.  A singles block (``reads.unpaired``) adds to ``short_mat`` and ``single_stats`` only; a slot
+        of it counts as one pair toward the uint32 bound (a cell grows by at most 1 per unpaired read)."""
         torch = self.torch
         n_pairs = reads.info["ends"] // 2
+        stats = self.single_stats if reads.unpaired else self.stats
         if 2 * (self.pairs_in_buffer + n_pairs) >= U32_LIMIT:
             self.fold()
         if 2 * n_pairs >= U32_LIMIT:
@@ -1456,7 +1541,7 @@ class PeCounter:
         self.pairs_seen += n_pairs
         with torch.cuda.device(self.device):
             self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
-            self.ctx.pe_count(reads, self.mats[0].data_ptr(), self.mats[1].data_ptr(), self.stats.data_ptr(),
+            self.ctx.pe_count(reads, self.mats[0].data_ptr(), self.mats[1].data_ptr(), stats.data_ptr(),
                               tile_map_ptr=self.tile_map.data_ptr() if self.tile_map is not None else None)
 
     def _occupied(self, head):

@@ -28,7 +28,7 @@ def _rank_world():
 
 
 def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow: bool = False, bam_by_name: bool = False, interleaved=None,
-                check_names=None):
+                check_names=None, single=(), count_singles: bool = False):
     """Index the nodes of ``gfa`` and count every pair of the two FASTQ files; the counters stay
     on the device.  Returns ``(node ids in file order, PeCounter)``.  ``stages_follow``: the graph stages will build their
     PE-link table from these counters in this process (the pipeline; not the stand-alone script, which writes the two text
@@ -40,11 +40,19 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     ``count_links.interleaved_info`` is then the stream's ``info``, else None.  ``check_names`` (None, ``"strict"`` or
     ``"singles"``): the two FASTQ files are paired by read name on the device (``PairedNameStream``, whatever ``use_stream``
     says; ``"strict"`` refuses the first pair that is no pair of mates, ``"singles"`` joins the files by name and drops and
-    counts the records without a mate); ``count_links.pair_names_info`` is then the stream's ``info``, else None."""
+    counts the records without a mate); ``count_links.pair_names_info`` is then the stream's ``info``, else None.
+    ``single``: files of UNPAIRED reads (the unpaired survivors of a trimmer, merged reads), each streamed into the same
+    counter after the pairs (``SingleEndStream``); ``count_singles``: the single records of the interleaved FASTQ
+    (``interleaved="singles"``) are kept and counted instead of dropped.  An unpaired read is worth what the reference gives
+    one end of a pair: its own triangle of ``short_mat``, nothing in ``node_mat``; its tallies go to
+    ``PeCounter.single_stats``, apart from the pairs'.  ``count_links.single_info`` is the list of per-file dicts (``path``,
+    ``reads``, ``with_n``, ``short``, ``used``), the interleaved file's first under ``count_singles``."""
     rank, world = _rank_world()
     count_links.bam_info = None
     count_links.interleaved_info = None
     count_links.pair_names_info = None
+    count_links.single_info = []
+    single = unpaired_input(single, count_singles, world, interleaved)  # (what the flags cannot apply to is a ValueError)
     by_names = check_names_input(fwd, rve, world, check_names, bam_by_name=bam_by_name, interleaved=interleaved)  # (False without the flag)
     il_path = interleaved_input(fwd, rve, world, interleaved)  # (None without the flag; what it cannot apply to is a ValueError)
     why = gzip_device_refusal(world)  # (reads the environment only; None with the switch unset)
@@ -65,12 +73,15 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     if rank == 0 and stages_follow:
         counter.reserve_link_table()  # (the graph stages run on this rank: their table's buffer is taken now)
     if il_path:
-        fq = host.InterleavedStream(il_path, ctx, block_pairs=BATCH_PAIRS, singles=(interleaved == "singles"))  # one file, opened once
+        fq = host.InterleavedStream(il_path, ctx, block_pairs=BATCH_PAIRS,
+                                    singles="keep" if count_singles else (interleaved == "singles"))  # one file, opened once
         try:
             count_stream(ctx, fq, counter, progress=True)
             count_links.interleaved_info = fq.info
         finally:
             fq.close()
+        if count_singles:
+            count_links.single_info.append(_single_tally(il_path, counter, (0, 0, 0)))
     elif by_names:
         fq = host.PairedNameStream(fwd, rve, ctx, block_pairs=BATCH_PAIRS, singles=(check_names == "singles"))  # both files, each read once
         try:
@@ -151,9 +162,52 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
         count_fastq(ctx, fq, counter, 0, len(fq), progress=True)
     if fq is not None:
         fq.close()
+    for path in single:  # (one process only: unpaired_input)
+        before = tuple(int(x) for x in counter.single_stats.cpu().numpy())
+        fs = host.SingleEndStream(path, ctx, block_reads=BATCH_PAIRS)
+        try:
+            count_stream(ctx, fs, counter)
+        finally:
+            fs.close()
+        count_links.single_info.append(_single_tally(path, counter, before))
+    for rec in count_links.single_info:
+        print("Unpaired reads of %s: %d used, %d with N, %d shorter than k+1" % (rec["path"], rec["used"], rec["with_n"], rec["short"]))
     if world > 1:
         counter.all_reduce()  # (every rank ends with the full sums; only rank 0 writes the files and runs the stages)
     return ids, counter
+
+
+def _single_tally(path: str, counter, before):
+    """What one file added to ``PeCounter.single_stats`` (with N, shorter than k+1, used) since ``before``."""
+    now = tuple(int(x) for x in counter.single_stats.cpu().numpy())
+    with_n, short, used = (a - b for a, b in zip(now, before))
+    return dict(path=path, reads=with_n + short + used, with_n=with_n, short=short, used=used)
+
+
+def unpaired_input(single=(), count_singles: bool = False, world: int = 1, interleaved=None, pe_text_from=None):
+    """The ``--single`` files as a list, after ``--single`` / ``--count-singles`` are checked against what they cannot apply
+    to -- a ``ValueError`` that says why and what to do instead, before a device is opened: ``--count-singles`` without
+    ``--interleaved-singles``, a BAM named by ``--single``, either flag with ``--pe-text-from`` (nothing is counted then)
+    or under a process group of more than one rank."""
+    single = [os.fspath(p) for p in (single or ())]
+    if not single and not count_singles:
+        return single
+    what = " and ".join(f for f, on in (("--single", bool(single)), ("--count-singles", count_singles)) if on)
+    if pe_text_from is not None:
+        raise ValueError("%s counts unpaired reads, and --pe-text-from reads the counts of an earlier run instead of counting: add the "
+                         "unpaired reads to the run that wrote %s, or leave one of the flags out" % (what, pe_text_from))
+    if count_singles and interleaved != "singles":
+        raise ValueError("--count-singles counts the single records of an interleaved FASTQ instead of dropping them and needs "
+                         "--interleaved --interleaved-singles, which say that -f and -r name one and that it may hold such records; "
+                         "unpaired reads in a file of their own are given with --single FILE")
+    for path in single:
+        if _starts_bam(path):
+            raise ValueError("%s is a BAM file, and --single reads a FASTQ of unpaired reads; convert it first, e.g. `samtools fastq "
+                             "-0 unpaired.fq -s unpaired.fq %s`" % (path, path))
+    if world > 1:
+        raise ValueError("%s: unpaired reads are counted in one process only; sharing them among the %d ranks of this process group is "
+                         "not built: run without torchrun" % (what, world))
+    return single
 
 
 def _regular(path: str) -> bool:
@@ -444,7 +498,8 @@ def write_info_files(out_dir: str, ids, counter, sparse: bool = False, bgzf: boo
 
 
 def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int = 0, ctx=None, stages_follow: bool = False,
-        sparse_info: bool = False, bgzf_info: bool = False, bam_by_name: bool = False, interleaved=None, check_names=None):
+        sparse_info: bool = False, bgzf_info: bool = False, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
+        count_singles: bool = False):
     # PE_Inference.py:93-96: the output directory is wiped and recreated
     if out_dir[-1] == "/":
         out_dir = out_dir[:-1]
@@ -462,10 +517,11 @@ def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int 
         bam_input(fwd, rve, world, by_name=True)  # (what the flag cannot apply to is said before a device is opened)
     interleaved_input(fwd, rve, world, interleaved)  # (the same)
     check_names_input(fwd, rve, world, check_names, bam_by_name=bam_by_name, interleaved=interleaved)  # (the same)
+    unpaired_input(single, count_singles, world, interleaved)  # (the same)
     if ctx is None:
         ctx = host.Context(device)
     ids, counter = count_links(ctx, gfa, fwd, rve, kmer_size, stages_follow=stages_follow, bam_by_name=bam_by_name, interleaved=interleaved,
-                               check_names=check_names)
+                               check_names=check_names, single=single, count_singles=count_singles)
     run.last = (ids, counter)
     if rank != 0:
         return None  # the counters were reduced to rank 0, which writes the files
@@ -515,6 +571,13 @@ def main(argv=None):
     parser.add_argument("--check-names-singles", dest="check_names_singles", action="store_true", default=False,
                         help="extension: with --check-names, the two files are in the same order but either may lack records the other "
                              "has; mates are found by a hash join on the names, records without a mate are dropped and counted per file")
+    parser.add_argument("--single", dest="single", action="append", default=[], metavar="FILE",
+                        help="extension (repeatable): a FASTQ of UNPAIRED reads -- the unpaired survivors of a trimmer, the merged reads "
+                             "of an overlapping library -- in any form the paired input takes; each read is counted into st_info as the "
+                             "reference counts one end of a pair, pe_info does not change (one process only)")
+    parser.add_argument("--count-singles", dest="count_singles", action="store_true", default=False,
+                        help="extension: with --interleaved --interleaved-singles, the records without their mate beside them are counted "
+                             "into st_info as unpaired reads instead of dropped")
     args = parser.parse_args(argv)
     interleaved = interleaved_mode(args.interleaved, args.interleaved_singles)
     check_names = check_names_mode(args.check_names, args.check_names_singles)
@@ -523,6 +586,7 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     interleaved_input(args.fwd, args.rve, world, interleaved)  # (refused before a device is opened or a process group made)
     check_names_input(args.fwd, args.rve, world, check_names, bam_by_name=args.bam_by_name, interleaved=interleaved)  # (the same)
+    unpaired_input(args.single, args.count_singles, world, interleaved)  # (the same)
     if world > 1:  # launched by torchrun: one rank per GPU, counters all-reduced over RCCL
         import torch
         import torch.distributed as dist
@@ -543,7 +607,7 @@ def main(argv=None):
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
         os.environ.setdefault("VS_HOST_THREADS", str(max(1, (os.cpu_count() or 1) // max(local_world, 1))))
     run(args.gfa, args.dir, args.fwd, args.rve, args.kmer_size, args.device, sparse_info=args.sparse_info, bgzf_info=args.bgzf_info,
-        bam_by_name=args.bam_by_name, interleaved=interleaved, check_names=check_names)
+        bam_by_name=args.bam_by_name, interleaved=interleaved, check_names=check_names, single=args.single, count_singles=args.count_singles)
     if world > 1:
         import torch.distributed as dist
 
