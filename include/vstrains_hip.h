@@ -346,7 +346,15 @@ int vs_bam_scan_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t ski
  *                             collate`: more than 64 records of one name and one class in one window (the waiting ones
  *                             included; the newest record of the name is named -- this bounds every list walk), and
  *                             waiting records plus the next chunk beyond the largest window.
- *   vs_bam_stream_mate_info : info[0] = singletons dropped, [1] = most records carried between two windows, [2] = most
+ *                             VS_BAM_BY_NAME_KEEP (an addition to ABI 11; the other modes unchanged, a member range takes
+ *                             the collated mode only): matching, carrying, the cap of 64 per name and every refusal are those
+ *                             of VS_BAM_BY_NAME, but the singletons are KEPT: at the end of the input the records that still
+ *                             wait are handed out, in file order, as singles blocks (vs_reads_pack_single above has the
+ *                             layout) of at most max_pairs slots.  End 2 r of such a block is the bases of waiting record r as
+ *                             `samtools fastq -s` writes them (reversed and complemented under 0x10), end 2 r + 1 is absent;
+ *                             a record with l_seq == 0 is a read of length 0, present and short.  *n_pairs of next is then
+ *                             the number of SLOTS of the block and vs_reads_unpaired tells its kind.  No mixed block is made
+ *   vs_bam_stream_mate_info : info[0] = singletons (dropped, or kept under VS_BAM_BY_NAME_KEEP), [1] = most records carried between two windows, [2] = most
  *                             bytes carried, [3] = windows scanned
  * VS_BAM_NAME_BITS=<0..64> (tests only) keeps that many low bits of the name hash: long probe chains without constructed
  * collisions.
@@ -354,7 +362,7 @@ int vs_bam_scan_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t ski
  * [2 p + 1] = record index of the first and the second of pair p in delivery order (at most cap_pairs pairs), waiting[] = the
  * records left waiting in window order (at most cap_waiting); info[0] = pairs, [1] = waiting, [2] = the newest record of a
  * name with more than 64 records of one class (then no pairs and no waiting records are given), ~0: none. */
-enum { VS_BAM_COLLATED = 0, VS_BAM_BY_NAME = 1 };
+enum { VS_BAM_COLLATED = 0, VS_BAM_BY_NAME = 1, VS_BAM_BY_NAME_KEEP = 2 };
 int vs_bam_stream_open_mode(vs_ctx *ctx, const char *path, int mode, vs_bam_stream **out);
 int vs_bam_stream_mate_info(const vs_bam_stream *s, uint64_t info[4]);
 int vs_bam_mates_host(const uint8_t *bytes, uint64_t n, uint64_t skip, uint32_t seg, uint32_t hash_bits, uint32_t *pairs, uint64_t cap_pairs,
@@ -437,8 +445,19 @@ void vs_fastq_se_close(vs_fastq_se *s);
  *                   windows leaves its records among the singles.  A window beyond VS_PAIR_WINDOW bytes (environment; default
  *                   the largest window) none of whose records a round decided is VS_E_RANGE.  VS_PAIR_NAME_BITS (environment, tests)
  *                   keeps the low bits of the name hash only.
- *   vs_fastq_pn_next  : as vs_fastq_stream_next
- *   vs_fastq_pn_info  : info[0] = pairs delivered, [1] / [2] = singles dropped of file 1 / file 2, [3] / [4] = records decided
+ *   VS_PN_KEEP    : (an addition to ABI 11, the other modes unchanged) the join, V1, V2, the refusals and what a round decides are
+ *                   those of VS_PN_SINGLES, but the singles are KEPT.  A kept single of a round is a record the round decided
+ *                   that is in none of its pairs; when the pairs of a round are out its kept singles are handed out as singles
+ *                   blocks (vs_reads_pack_single above has the layout) of at most max_pairs slots, file 1's first in file
+ *                   order, then file 2's in file order, and only then are the windows cut.  A record the round did not decide
+ *                   is not handed out: it is in the next round's windows and is handed out exactly once, as half of a pair
+ *                   or as a single.  For a valid input the kept reads of file f are exactly the complete records of file f
+ *                   whose key is not in both files, in file order, whatever the chunk, window or block size.  No mixed block
+ *                   is ever made.  As under VS_PN_SINGLES a V1 or V2 violation that spans windows leaves its records among
+ *                   the singles: they are then counted as unpaired reads.
+ *   vs_fastq_pn_next  : as vs_fastq_stream_next; under VS_PN_KEEP as vs_fastq_il_next under VS_IL_KEEP: *n_pairs is the number
+ *                       of SLOTS of the block and vs_reads_unpaired tells its kind
+ *   vs_fastq_pn_info  : info[0] = pairs delivered, [1] / [2] = singles of file 1 / file 2 (dropped, or kept under VS_PN_KEEP), [3] / [4] = records decided
  *                       of file 1 / file 2, [5] = rounds (pairs of windows joined), [6] = the largest window in bytes, [7] =
  *                       text bytes read, [8] = file bytes read, [9] = flags as vs_fastq_stream_info
  * Test aids, the join of ONE pair of windows (n0 / n1 text bytes as they are; eof0 / eof1: the file ends with its window; table:
@@ -449,8 +468,13 @@ void vs_fastq_se_close(vs_fastq_se *s);
  * lie behind that of the pair before (~0: none, also with [5] set), [7] = VS_PN_STRICT: the first pair that is no pair of mates (~0: none).  With
  * [5] or [6] set no pairs are given and nothing is decided.  _host is the one-thread twin (vs_pair_names_core.h), VS_E_STATE
  * when the table is full; _text runs the kernels and keeps `guard` sentinel words on either side of the device pair list
- * (room for min(R1, R2) pairs), VS_E_STATE if one changed, a word of the list stayed unwritten or one behind it was written. */
-enum { VS_PN_STRICT = 0, VS_PN_SINGLES = 1 };
+ * (room for min(R1, R2) pairs), VS_E_STATE if one changed, a word of the list stayed unwritten or one behind it was written.
+ * vs_fastq_join_singles_host / _text: the same join (mode VS_PN_SINGLES or VS_PN_KEEP, the same result for both) and the kept
+ * singles of the round as well: singles0[] / singles1[] = the decided records of window 1 / 2 that are in no pair, in order
+ * (at most cap_singles0 / cap_singles1 of them), info[8] / [9] = how many there are; info[0..7] as above.  _host is the
+ * one-thread twin; _text runs the compaction kernels with `guard` sentinel words on either side of both device lists,
+ * VS_E_STATE if one changed or a word of a list stayed unwritten. */
+enum { VS_PN_STRICT = 0, VS_PN_SINGLES = 1, VS_PN_KEEP = 2 };
 typedef struct vs_fastq_pn vs_fastq_pn;
 int vs_fastq_pn_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, int mode, vs_fastq_pn **out);
 int vs_fastq_pn_next(vs_ctx *ctx, vs_fastq_pn *s, uint64_t max_pairs, vs_reads **out, uint64_t *n_pairs);
@@ -460,6 +484,12 @@ int vs_fastq_join_host(const uint8_t *text0, uint64_t n0, const uint8_t *text1, 
                        uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint64_t info[8]);
 int vs_fastq_join_text(vs_ctx *ctx, const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
                        uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint32_t guard, uint64_t info[8]);
+int vs_fastq_join_singles_host(const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
+                               uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint32_t *singles0, uint64_t cap_singles0, uint32_t *singles1,
+                               uint64_t cap_singles1, uint64_t info[10]);
+int vs_fastq_join_singles_text(vs_ctx *ctx, const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
+                               uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint32_t *singles0, uint64_t cap_singles0, uint32_t *singles1,
+                               uint64_t cap_singles1, uint32_t guard, uint64_t info[10]);
 /* Member-sharded open of ONE collated BAM for one process per GPU (additions to ABI 10): no rank inflates the whole file and
  * nothing is inflated on a host.  Rank r of W takes the BGZF members [M r / W, M (r + 1) / W) of vs_bgzf_walk_file, its
  * "share": the inflated bytes [S_r, S_r + E_r).  A share cannot be entered at a guessed record start, so pass 1 follows the

@@ -85,8 +85,8 @@ def build_parser():
                         "reference counts one end of a pair, aln/pe_info does not change (one process only; not together with "
                         "--pe-text-from)")
     p.add_argument("--count-singles", dest="count_singles", action="store_true", default=False,
-                   help="extension: with --interleaved --interleaved-singles, the records without their mate beside them are counted "
-                        "into aln/st_info as unpaired reads instead of dropped")
+                   help="extension: with --interleaved --interleaved-singles, with --check-names --check-names-singles or with "
+                        "--bam-by-name, the records without a mate are counted into aln/st_info as unpaired reads instead of dropped")
     return p
 
 
@@ -131,7 +131,8 @@ def main(argv=None, backend=None):
     pe_inference.check_names_input(args.fwd, args.rve, pe_inference._rank_world()[1], args.check_names, bam_by_name=args.bam_by_name,
                                    interleaved=args.interleaved)
     args.single = pe_inference.unpaired_input(args.single, args.count_singles, pe_inference._rank_world()[1], args.interleaved,
-                                              pe_text_from=args.pe_text_from)
+                                              pe_text_from=args.pe_text_from, check_names=args.check_names, bam_by_name=args.bam_by_name,
+                                              fwd=args.fwd, rve=args.rve)
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
         _bail("\nPath to the assembly graph is required, (.gfa format)", "Please ensure the path is correct")
     args.pe_text_files = None

@@ -41,6 +41,9 @@
 //   k_mate_carry    a wavefront per waiting record copies it to the front of the other window buffer, 16 bytes a lane
 //                   where source and destination are aligned alike; the bytes from `stop` on follow.
 // No lane waits for another lane's progress: a lost compare-and-swap reads the winner and goes on.
+// What still waits at the end of the input are singletons: counted, and under VS_BAM_BY_NAME_KEEP handed out from the last
+// window's waiting list (window order = file order) as singles blocks: k_bam_single_ends, k_sl_scan,
+// k_pack_reads<PackBamSingles> (even end e = waiting record e / 2, reversed and complemented under 0x10; odd ends absent).
 //
 // A member range (vs_bam_stream_open_range; one process per GPU on one collated whole-BGZF file).  A range cannot be entered
 // at a guessed record start, so the open has two passes with one exchange between them (pe.BamStream.open_shard):
@@ -452,6 +455,36 @@ __global__ void __launch_bounds__(BAM_TPB) k_bam_ends_list(const uint4 *__restri
     atomicMax(&st[B_MAXLEN], len);
 }
 
+// VS_BAM_BY_NAME_KEEP: the ends of a singles block of waiting records [w0, w0 + n_reads) of the waiting list, the analogue of
+// k_single_ends (vs_reads.hip).  One thread per end (and one more for the closing word offset): even end e is record
+// wlist[w0 + e / 2] -- its length is l_seq, 0 included; odd ends are absent: no length, no words, VS_FLAG_ABSENT.
+__global__ void __launch_bounds__(BAM_TPB) k_bam_single_ends(const uint4 *__restrict__ recs, const uint32_t *__restrict__ wlist, uint32_t w0, uint32_t n_reads,
+                                                             uint32_t n_rec, uint32_t *__restrict__ meta, uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
+    const uint32_t e = blockIdx.x * BAM_TPB + threadIdx.x, n_ends = 2u * n_reads;
+    if (e > n_ends) return;
+    if (e == n_ends) {
+        wcnt[e] = 0u;
+        return;
+    }
+    if (e & 1u) {
+        meta[e] = VS_FLAG_ABSENT << 24;
+        wcnt[e] = 0u;
+        return;
+    }
+    const uint32_t r = wlist[w0 + (e >> 1)];
+    const uint32_t len = r < n_rec ? recs[r].z : 0u;
+    if (r >= n_rec) atomicMin(&st[B_BADCOUPLE], e >> 1);  // (never: the list holds records of this window)
+    if (len > VS_LEN_MASK) {
+        atomicMin(&st[B_TOO_LONG], e);
+        meta[e] = 0u;
+        wcnt[e] = 0u;
+        return;
+    }
+    meta[e] = len;
+    wcnt[e] = (len + 15u) >> 4;
+    atomicMax(&st[B_MAXLEN], len);
+}
+
 // ---- the chain on a device window ---------------------------------------------------------------------------------------
 namespace {
 
@@ -648,6 +681,8 @@ struct vs_bam_stream {
     uint32_t name_bits = 64;
     BamMatch mt;
     uint32_t pair_cur = 0;   // the first pair of the matched window not yet delivered
+    bool keep = false;       // VS_BAM_BY_NAME_KEEP: what still waits at the end of the input is handed out as singles blocks
+    uint32_t single_cur = 0; // ... the first waiting record of the last window not yet delivered
     uint32_t n_carried = 0;  // the window's first records are the ones carried from earlier windows (first_record: its first NEW one)
     uint64_t singletons = 0, waiting_max = 0, carried_bytes_max = 0, windows = 0;
     // a member range (vs_bam_stream_open_range): positions are relative to S, the inflated offset of the range's first member
@@ -840,6 +875,60 @@ int bam_finish(vs_ctx *ctx, vs_bam_stream *s) {
     return VS_OK;
 }
 
+// VS_BAM_BY_NAME_KEEP, the input is at its end and its pairs are out: a singles block of up to max_reads of the records that
+// still wait (mt.wlist of the last window, window order = file order), from the cursor
+int bam_singles_block(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_reads, vs_reads **out, uint64_t *n_slots) {
+    hipStream_t st = s->st;
+    const BamScan &sc = s->sc;
+    const uint64_t n = std::min<uint64_t>(s->mt.n_wait - s->single_cur, max_reads), n_ends = 2u * n;
+    if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+    vs_reads *r = new vs_reads();
+    r->cached = true;
+    r->unpaired = true;
+    auto fail = [&](hipError_t e) {
+        vs_reads_free(ctx, r);
+        if (e == hipErrorOutOfMemory) return bam_fail(ctx, s, VS_E_OOM, "vs_bam_stream_next: device buffers for the block");
+        return bam_fail(ctx, s, VS_E_HIP, std::string("vs_bam_stream_next: ") + hipGetErrorString(e));
+    };
+    hipError_t e1 = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true);
+    if (e1 != hipSuccess) return fail(e1);
+    e1 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0, sizeof(uint32_t) * (B_BAD_MEMBER - B_BADCOUPLE), st);
+    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0xFF, sizeof(uint32_t), st);
+    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_TOO_LONG, 0xFF, sizeof(uint32_t), st);
+    if (e1 != hipSuccess) return fail(e1);
+    hipLaunchKernelGGL(k_bam_single_ends, dim3((unsigned)((n_ends + 1u + BAM_TPB - 1u) / BAM_TPB)), dim3(BAM_TPB), 0, st, sc.recs.as<const uint4>(),
+                       s->mt.wlist.as<const uint32_t>(), s->single_cur, (uint32_t)n, sc.n_rec, (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
+    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
+    vs_launch_scan_u32(st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + B_WORDS);
+    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
+    e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat + B_BADCOUPLE, s->d_stat + B_BADCOUPLE, sizeof(uint32_t) * (B_BAD_MEMBER - B_BADCOUPLE), hipMemcpyDeviceToHost, st);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+    if (e1 != hipSuccess) return fail(e1);
+    if (s->h_stat[B_BADCOUPLE] != BAM_NONE) {
+        vs_reads_free(ctx, r);
+        return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": the waiting list of the name match names a record beyond the window's");
+    }
+    if (s->h_stat[B_TOO_LONG] != BAM_NONE) {
+        uint32_t rec = 0;
+        e1 = hipMemcpy(&rec, s->mt.wlist.as<uint32_t>() + s->single_cur + (s->h_stat[B_TOO_LONG] >> 1), sizeof rec, hipMemcpyDeviceToHost);
+        if (e1 != hipSuccess) return fail(e1);
+        vs_reads_free(ctx, r);
+        return bam_fail(ctx, s, VS_E_RANGE, rec_msg(s, rec, " has a sequence of more than ") + std::to_string((unsigned)VS_LEN_MASK) + " bases");
+    }
+    const uint64_t words = s->h_stat[B_WORDS];
+    r->max_len = s->h_stat[B_MAXLEN];
+    if ((e1 = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e1);
+    vs_launch_pack_bam_singles(st, BamSingles{s->w.data(), (const uint32_t *)sc.recs.as<uint4>(), s->mt.wlist.as<const uint32_t>() + s->single_cur, sc.n_rec}, r);
+    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
+    if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + B_INVALID, s->h_stat + B_INVALID)) != hipSuccess) return fail(e1);
+    if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
+    s->single_cur += (uint32_t)n;
+    *out = r;
+    *n_slots = n;
+    return VS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -924,7 +1013,7 @@ int vs_bam_stream_open(vs_ctx *ctx, const char *path, vs_bam_stream **out) { ret
 static int bam_open(vs_ctx *ctx, const char *path, int mode, const uint64_t *range, vs_bam_stream **out);
 
 int vs_bam_stream_open_mode(vs_ctx *ctx, const char *path, int mode, vs_bam_stream **out) {
-    if (!ctx || !path || !out || (mode != VS_BAM_COLLATED && mode != VS_BAM_BY_NAME)) return vs_fail(ctx, VS_E_ARG, "vs_bam_stream_open: bad argument");
+    if (!ctx || !path || !out || (mode != VS_BAM_COLLATED && mode != VS_BAM_BY_NAME && mode != VS_BAM_BY_NAME_KEEP)) return vs_fail(ctx, VS_E_ARG, "vs_bam_stream_open: bad argument");
     return bam_open(ctx, path, mode, nullptr, out);
 }
 
@@ -944,7 +1033,8 @@ static int bam_open(vs_ctx *ctx, const char *path, int mode, const uint64_t *ran
     vs_bam_stream *s = new vs_bam_stream();
     s->device = ctx->device;
     s->skip = range ? range[1] : header;
-    s->by_name = mode == VS_BAM_BY_NAME;
+    s->by_name = mode != VS_BAM_COLLATED;
+    s->keep = mode == VS_BAM_BY_NAME_KEEP;
     if (range) {
         s->ranged = true;
         s->rd.begin = range[0];
@@ -997,6 +1087,8 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
                 s->done = true;
                 return VS_OK;
             }
+            if (s->keep && s->eof && s->rd.err == VS_OK && sc.end != BAM_END_CUT && s->single_cur < s->mt.n_wait)
+                return bam_singles_block(ctx, s, max_pairs, out, n_pairs);  // (what bam_finish would refuse comes first, there)
             if (s->eof) return bam_finish(ctx, s);
             if (s->by_name) {
                 if (int rc = bam_carry_waiting(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
@@ -1011,7 +1103,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
                 if (int rc = bam_drop_front(ctx, s, cut)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
                 s->first_record += s->rec_cur;
             }
-            s->rec_cur = s->part_cur = s->pair_cur = 0;
+            s->rec_cur = s->part_cur = s->pair_cur = s->single_cur = 0;
             s->scanned = false;
         }
         if (!s->eof) {

@@ -240,6 +240,15 @@ struct BamEnds {
 };
 // k_pack_reads for them (r's woff and lengths are on the device, r->d_mask too)
 void vs_launch_pack_bam(hipStream_t st, const BamEnds &b, const vs_reads *r);
+// The kept singletons of the BAM ingest (VS_BAM_BY_NAME_KEEP): a singles block whose even end e is record list[e / 2] of recs
+// (n_rec of them, as BamEnds), every odd end absent; k_bam_single_ends (vs_bam.hip) has written r's lengths
+struct BamSingles {
+    const uint8_t *win;
+    const uint32_t *recs;
+    const uint32_t *list;
+    uint32_t n_rec;
+};
+void vs_launch_pack_bam_singles(hipStream_t st, const BamSingles &b, const vs_reads *r);
 
 // BGZF members (vs_inflate.hip), shared with the streamed ingest.  A member for the device: its raw deflate payload in a
 // buffer of compressed bytes, where its ISIZE bytes go in an output buffer, and the CRC32 of its trailer.

@@ -30,6 +30,13 @@
 // whose window is the smaller one (to both while both are small, to the other when one is at its end), so in-step files keep
 // windows of carry + one slot.  A window beyond VS_PAIR_WINDOW bytes (default: the largest window) in a round that decided
 // none of its records is refused: the files are probably not in the same order.
+// Mode VS_PN_KEEP keeps the records without a mate instead of dropping them: joined and decided as singles; then, per round,
+//     k_pn_mated    one thread per file-1 record: mated[mate[i]] = 1 (one byte per file-2 record, zeroed before);
+//     k_pn_singles_count<Pred> / k_sl_scan / k_pn_singles_emit<Pred>   once per file, bound dec[f]: the DECIDED records in no
+//                   pair compacted in file order into srec[f] (Pred: mate[i] is none / mated[j] is 0);
+//   and when the round's pairs are out they are handed out as SINGLES blocks (vs_reads_singles_block, vs_reads.hip), file 1's
+//   first, then file 2's, before the windows are cut.  A record behind dec[f] waits, as it does for the pairs: it is handed
+//   out once, by the round that decides it.  The other modes launch none of this.
 // Inputs that are wrong end in status words and messages, never in a fault.
 #include <algorithm>
 #include <string>
@@ -110,6 +117,47 @@ __global__ void __launch_bounds__(PN_TPB) k_pn_order(const uint32_t *__restrict_
     if (rec[2u * p + 1u] <= rec[2u * p - 1u]) atomicMin(&st[PS_ORDER], p);
 }
 
+// VS_PN_KEEP: mated[j] = 1 for every file-2 record j that a file-1 record names (mated zeroed before; one byte per record)
+__global__ void __launch_bounds__(PN_TPB) k_pn_mated(const uint32_t *__restrict__ mate, uint32_t n0, uint8_t *__restrict__ mated, uint32_t n1) {
+    const uint32_t i = blockIdx.x * PN_TPB + threadIdx.x;
+    if (i >= n0) return;
+    const uint32_t j = mate[i];
+    if (j < n1) mated[j] = 1u;
+}
+
+// VS_PN_KEEP: the records r < n (n = what the round decided of the file) with pred(r) counted per workgroup (wg_cnt, scanned
+// afterwards), then srec[q] = r for the q-th of them -- a ballot, the popcount below the lane and the counts of the wavefronts
+// in front, as k_pn_emit places the pairs.  One pair of kernels for both files: Pred is PnUnmated0 or PnUnmated1.
+template <class Pred>
+__global__ void __launch_bounds__(PN_TPB) k_pn_singles_count(Pred pred, uint32_t n, uint32_t *__restrict__ wg_cnt) {
+    __shared__ uint32_t wcnt[PN_TPB / VS_WAVE];
+    const uint32_t r = blockIdx.x * PN_TPB + threadIdx.x;
+    const uint64_t b = __ballot(r < n && pred(r));
+    if ((threadIdx.x & (VS_WAVE - 1u)) == 0u) wcnt[threadIdx.x / VS_WAVE] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < PN_TPB / VS_WAVE; w++) t += wcnt[w];
+        wg_cnt[blockIdx.x] = t;
+    }
+}
+
+template <class Pred>
+__global__ void __launch_bounds__(PN_TPB) k_pn_singles_emit(Pred pred, const uint32_t *__restrict__ wg_base, uint32_t n, uint32_t n_singles,
+                                                            uint32_t *__restrict__ srec) {
+    __shared__ uint32_t wcnt[PN_TPB / VS_WAVE];
+    const uint32_t r = blockIdx.x * PN_TPB + threadIdx.x, lane = threadIdx.x & (VS_WAVE - 1u), wave = threadIdx.x / VS_WAVE;
+    const bool single = r < n && pred(r);
+    const uint64_t b = __ballot(single);
+    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (!single) return;
+    uint32_t q = wg_base[blockIdx.x] + (uint32_t)__popcll(b & (lane ? (~0ull >> (VS_WAVE - lane)) : 0ull));
+    for (uint32_t w = 0; w < wave; w++) q += wcnt[w];
+    if (q >= n_singles) return;  // (cannot be: the decided records that are in no pair are dec - pairs)
+    srec[q] = r;
+}
+
 // strict: pair p = record p of either window (p < n); the first that is no pair of mates
 __global__ void __launch_bounds__(PN_TPB) k_pn_index(PnWin f0, PnWin f1, uint32_t n, uint32_t *__restrict__ rec, uint32_t *__restrict__ st) {
     const uint32_t p = blockIdx.x * PN_TPB + threadIdx.x;
@@ -161,8 +209,45 @@ namespace {
 
 struct PnDev {
     VsDevBuf hash, klen_slot, table, mate, wg;  // uint64 per record; uint32 x 2 per record; 3 T words; per file-1 record; per workgroup
+    VsDevBuf mated, wg_single;                  // VS_PN_KEEP: uint8 per file-2 record; singles per workgroup -> those in front
     uint32_t n_pairs = 0, li = 0, lj = 0, dup[2] = {PN_NONE, PN_NONE}, order = PN_NONE, first_bad = PN_NONE;
 };
+
+// VS_PN_KEEP, one file of a joined round: the n_singles records r < dec with pred(r) listed in srec, in file order
+template <class Pred>
+int pn_compact_device(vs_ctx *ctx, hipStream_t st, const Pred &pred, uint32_t dec, uint32_t n_singles, PnDev &jd, uint32_t *srec, uint32_t *d_total) {
+    if (!n_singles) return VS_OK;
+    const uint32_t wgs = (dec + PN_TPB - 1u) / PN_TPB;
+    if (int rc = reserve_n<uint32_t>(ctx, jd.wg_single, (size_t)wgs + 1u)) return rc;
+    hipLaunchKernelGGL(k_pn_singles_count<Pred>, dim3(wgs), dim3(PN_TPB), 0, st, pred, dec, jd.wg_single.as<uint32_t>());
+    VS_HIP(ctx, hipGetLastError());
+    vs_launch_scan_u32(st, jd.wg_single.as<uint32_t>(), wgs, d_total);
+    VS_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_pn_singles_emit<Pred>, dim3(wgs), dim3(PN_TPB), 0, st, pred, jd.wg_single.as<const uint32_t>(), dec, n_singles, srec);
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}
+
+// VS_PN_KEEP: the kept singles of a round that pn_join_device joined (no key twice, the pairs in order) and pn_decide decided:
+// srec0 (dec[0] - n_pairs words) and srec1 (dec[1] - n_pairs words), either file's in file order.  r0 / r1: the complete
+// records of the windows.  d_total: a status word for the scans' totals.  Synchronises nothing.
+int pn_singles_device(vs_ctx *ctx, hipStream_t st, uint32_t r0, uint32_t r1, const uint32_t dec[2], PnDev &jd, uint32_t *srec0, uint32_t *srec1,
+                      uint32_t *d_total) {
+    if (dec[0] > r0 || dec[1] > r1 || jd.n_pairs > std::min(dec[0], dec[1])) return vs_fail(ctx, VS_E_STATE, "the decided records of a round do not hold its pairs");
+    if (dec[0] == jd.n_pairs && dec[1] == jd.n_pairs) return VS_OK;
+    if (int rc = reserve_n<uint32_t>(ctx, jd.mate, r0)) return rc;
+    if (int rc = reserve_n<uint8_t>(ctx, jd.mated, r1)) return rc;
+    if (int rc = reserve_n<uint32_t>(ctx, jd.wg_single, (size_t)(std::max(dec[0], dec[1]) + PN_TPB - 1u) / PN_TPB + 1u)) return rc;  // (once, for both files)
+    if (r1) VS_HIP(ctx, hipMemsetAsync(jd.mated.ptr(), 0, r1, st));
+    if (!std::min(r0, r1)) {  // (a window without a record: nothing was joined, mate[] was not written)
+        if (r0) VS_HIP(ctx, hipMemsetAsync(jd.mate.ptr(), 0xFF, sizeof(uint32_t) * (size_t)r0, st));
+    } else {
+        hipLaunchKernelGGL(k_pn_mated, dim3((r0 + PN_TPB - 1u) / PN_TPB), dim3(PN_TPB), 0, st, jd.mate.as<const uint32_t>(), r0, jd.mated.as<uint8_t>(), r1);
+        VS_HIP(ctx, hipGetLastError());
+    }
+    if (int rc = pn_compact_device(ctx, st, PnUnmated0{jd.mate.as<const uint32_t>()}, dec[0], dec[0] - jd.n_pairs, jd, srec0, d_total)) return rc;
+    return pn_compact_device(ctx, st, PnUnmated1{jd.mated.as<const uint8_t>()}, dec[1], dec[1] - jd.n_pairs, jd, srec1, d_total);
+}
 
 // The pairs of the windows f0, f1 into rec (room for 2 * min(R1, R2) words): joined by name (singles), or record by record
 // (strict).  table: slots (0: pn_table_size), bits: hash bits kept.  d_stat / h_stat: PS_ALL status words, [PS_PAIRS, PS_MAXLEN)
@@ -260,6 +345,9 @@ struct vs_fastq_pn {
     uint32_t pair_cur = 0;   // the first pair of the round not yet delivered
     uint32_t dec[2] = {0, 0};  // records of either window the round decided
     bool singles_mode = false;
+    bool keep = false;             // VS_PN_KEEP: the decided records without a mate are handed out as singles blocks
+    VsDevBuf srec[2];              // VS_PN_KEEP: srec[f][q] = the q-th kept single of file f's window, in file order
+    uint32_t n_single[2] = {0, 0}, single_cur[2] = {0, 0};  // ... how many the round has, the first not yet delivered
     size_t window_limit = STREAM_MAX_WINDOW;
     uint32_t name_bits = 64;  // bits of the name hash kept (VS_PAIR_NAME_BITS: tests)
     VsDevBuf stat_buf, d_wcnt;
@@ -353,6 +441,7 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
         s->joined = false;
         s->pair_cur = 0;
         s->dec[0] = s->dec[1] = 0;
+        s->n_single[0] = s->n_single[1] = s->single_cur[0] = s->single_cur[1] = 0;
     }
     {
         // more text: for the smaller window, for both while both are below half a chunk, for the other when one is at its end
@@ -445,6 +534,13 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
         s->records[f] += s->dec[f];
         s->singles[f] += s->dec[f] - j.n_pairs;
     }
+    if (s->keep) {
+        for (int f = 0; f < 2; f++)
+            if (int rc = reserve_n<uint32_t>(ctx, s->srec[f], (size_t)(s->dec[f] - j.n_pairs) + 1u)) return pn_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = pn_singles_device(ctx, st, f0.n_rec, f1.n_rec, s->dec, s->jd, s->srec[0].as<uint32_t>(), s->srec[1].as<uint32_t>(), s->d_stat + PS_WORDS))
+            return pn_fail(ctx, s, rc, vs_last_error(ctx));
+        for (int f = 0; f < 2; f++) s->n_single[f] = s->dec[f] - j.n_pairs;
+    }
     *end = false;
     return VS_OK;
 }
@@ -454,12 +550,13 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
 extern "C" {
 
 int vs_fastq_pn_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, int mode, vs_fastq_pn **out) {
-    if (!ctx || !fwd_path || !rve_path || !out || (mode != VS_PN_STRICT && mode != VS_PN_SINGLES)) return vs_fail(ctx, VS_E_ARG, "vs_fastq_pn_open: bad argument");
+    if (!ctx || !fwd_path || !rve_path || !out || (mode != VS_PN_STRICT && mode != VS_PN_SINGLES && mode != VS_PN_KEEP)) return vs_fail(ctx, VS_E_ARG, "vs_fastq_pn_open: bad argument");
     *out = nullptr;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     vs_fastq_pn *s = new vs_fastq_pn();
     s->device = ctx->device;
-    s->singles_mode = mode == VS_PN_SINGLES;
+    s->singles_mode = mode != VS_PN_STRICT;
+    s->keep = mode == VS_PN_KEEP;
     if (const char *ev = getenv("VS_PAIR_WINDOW")) s->window_limit = (size_t)std::min<long long>(std::max<long long>(1, atoll(ev)), (long long)STREAM_MAX_WINDOW);  // (tests)
     if (const char *ev = getenv("VS_PAIR_NAME_BITS")) s->name_bits = (uint32_t)std::min<long long>(std::max<long long>(1, atoll(ev)), 64);  // (tests: shared probe chains)
     const char *paths[2] = {fwd_path, rve_path};
@@ -503,10 +600,35 @@ int vs_fastq_pn_next(vs_ctx *ctx, vs_fastq_pn *s, uint64_t max_pairs, vs_reads *
     VS_HIP(ctx, hipSetDevice(ctx->device));
     if (!max_pairs || max_pairs > (1ull << 30)) max_pairs = 1ull << 30;
     hipStream_t st = s->st;
-    while (!s->joined || s->pair_cur >= s->jd.n_pairs) {
+    while (!s->joined || (s->pair_cur >= s->jd.n_pairs && s->single_cur[0] >= s->n_single[0] && s->single_cur[1] >= s->n_single[1])) {
         bool end = false;
         const int rc = pn_next_round(ctx, s, &end);
         if (end) return rc;
+    }
+    if (s->pair_cur >= s->jd.n_pairs) {
+        // ---- VS_PN_KEEP, the round's pairs are out: a singles block of n kept records of file 1 -- or, once those are out, of
+        // file 2 -- from the cursor
+        const int f = s->single_cur[0] < s->n_single[0] ? 0 : 1;
+        const DevFile &d = s->df[f];
+        const uint64_t n = std::min<uint64_t>(s->n_single[f] - s->single_cur[f], max_pairs);
+        const uint32_t *srec = s->srec[f].as<const uint32_t>() + s->single_cur[f];
+        const SlWin win = {d.w.data(), d.ends.as<const uint32_t>(), d.n_nl, (uint32_t)d.w.size};
+        vs_reads *r = nullptr;
+        hipError_t e1 = vs_reads_singles_block(ctx, st, win, srec, 0u, n, s->d_wcnt, s->d_stat + PS_MAXLEN, s->h_stat + PS_MAXLEN, &r);
+        if (e1 == hipErrorOutOfMemory) return pn_fail(ctx, s, VS_E_OOM, "vs_fastq_pn_next: device buffers for the block");
+        if (e1 != hipSuccess) return pn_fail(ctx, s, VS_E_HIP, std::string("vs_fastq_pn_next: ") + hipGetErrorString(e1));
+        if (!r) {
+            uint32_t at = 0;
+            e1 = hipMemcpy(&at, srec + (s->h_stat[PS_TOO_LONG] >> 1), sizeof at, hipMemcpyDeviceToHost);
+            char msg[600];
+            snprintf(msg, sizeof msg, "%s: record %llu has a sequence line of more than %u bytes", s->rd[f].path.c_str(),
+                     (unsigned long long)(d.first_record + (e1 == hipSuccess ? at : 0u)), (unsigned)VS_LEN_MASK);
+            return pn_fail(ctx, s, VS_E_RANGE, msg);
+        }
+        s->single_cur[f] += (uint32_t)n;
+        *out = r;
+        *n_pairs = n;
+        return VS_OK;
     }
     // ---- the block of n pairs from the cursor
     const uint64_t n = std::min<uint64_t>(s->jd.n_pairs - s->pair_cur, max_pairs), n_ends = 2u * n;
@@ -605,11 +727,18 @@ static bool pn_table_ok(uint32_t table) { return table == 0u || (table >= 2u && 
 
 }  // namespace
 
-int vs_fastq_join_host(const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table, uint32_t name_bits,
-                       uint32_t *pairs, uint64_t cap_pairs, uint64_t info[8]) {
+// vs_fastq_join_host, and with `sing` vs_fastq_join_singles_host: the kept singles of either window too (info has 10 words then)
+struct PnSinglesOut {
+    uint32_t *list[2];
+    uint64_t cap[2];
+};
+
+static int pn_join_host_entry(const char *who, const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
+                              uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, const PnSinglesOut *sing, uint64_t *info) {
     if ((!text0 && n0) || (!text1 && n1) || !info || (!pairs && cap_pairs) || n0 > STREAM_MAX_WINDOW || n1 > STREAM_MAX_WINDOW || !pn_table_ok(table) ||
-        (mode != VS_PN_STRICT && mode != VS_PN_SINGLES))
-        return vs_fail(nullptr, VS_E_ARG, "vs_fastq_join_host: bad argument");
+        (sing ? (mode != VS_PN_SINGLES && mode != VS_PN_KEEP) || (!sing->list[0] && sing->cap[0]) || (!sing->list[1] && sing->cap[1])
+              : (mode != VS_PN_STRICT && mode != VS_PN_SINGLES)))
+        return vs_fail(nullptr, VS_E_ARG, "%s: bad argument", who);
     std::vector<uint32_t> e0, e1;
     uint32_t r0 = 0, r1 = 0;
     pn_host_lines(text0, n0, eof0, e0, &r0);
@@ -618,6 +747,7 @@ int vs_fastq_join_host(const uint8_t *text0, uint64_t n0, const uint8_t *text1, 
     const uint32_t cap = std::min(r0, r1), n_all = r0 + r1;
     std::vector<uint32_t> rec(2u * (size_t)cap + 1u);
     uint32_t res[5] = {0u, PN_NONE, PN_NONE, PN_NONE, 0u}, first_bad = PN_NONE;
+    std::vector<uint32_t> mate(r0 ? r0 : 1u, PN_NONE);
     if (mode == VS_PN_STRICT) {
         for (uint32_t p = 0; p < cap; p++) {
             if (first_bad == PN_NONE && !pn_mates_at(f0, p, f1, p)) first_bad = p;
@@ -631,19 +761,41 @@ int vs_fastq_join_host(const uint8_t *text0, uint64_t n0, const uint8_t *text1, 
         const PnJoin J = {f0, f1, n_all, hash.data(), klen_slot.data(), klen_slot.data() + n_all, T, tb.data(), tb.data() + T, tb.data() + 2u * (size_t)T};
         pn_join_host(J, name_bits ? name_bits : 64u, rec.data(), res);
         if (res[4]) return vs_fail(nullptr, VS_E_STATE, "the table of a join by name (%u slots for %u records) is full", T, n_all);
+        if (sing)
+            for (uint32_t i = 0; i < r0; i++) mate[i] = pn_partner_at(J, i);  // (as k_pn_partner leaves it)
     }
     const uint32_t P = std::min(res[0], cap);
-    pn_join_info(info, mode == VS_PN_SINGLES, P, P ? rec[2u * P - 2u] : 0u, P ? rec[2u * P - 1u] : 0u, &res[1], res[3], first_bad, r0, r1, eof0 != 0, eof1 != 0);
+    pn_join_info(info, mode != VS_PN_STRICT, P, P ? rec[2u * P - 2u] : 0u, P ? rec[2u * P - 1u] : 0u, &res[1], res[3], first_bad, r0, r1, eof0 != 0, eof1 != 0);
     const uint64_t np = std::min<uint64_t>(cap_pairs, info[0]);
     if (np) memcpy(pairs, rec.data(), sizeof(uint32_t) * 2u * np);
+    if (sing) {  // (a refused round decides nothing: info[3] = info[4] = 0, no singles)
+        std::vector<uint8_t> mated(r1 ? r1 : 1u);
+        pn_mated_host(mate.data(), r0, mated.data(), r1);
+        info[8] = pn_singles_host(PnUnmated0{mate.data()}, (uint32_t)info[3], sing->list[0], sing->cap[0]);
+        info[9] = pn_singles_host(PnUnmated1{mated.data()}, (uint32_t)info[4], sing->list[1], sing->cap[1]);
+    }
     return VS_OK;
 }
 
-int vs_fastq_join_text(vs_ctx *ctx, const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
-                       uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint32_t guard, uint64_t info[8]) {
+int vs_fastq_join_host(const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table, uint32_t name_bits,
+                       uint32_t *pairs, uint64_t cap_pairs, uint64_t info[8]) {
+    return pn_join_host_entry("vs_fastq_join_host", text0, n0, text1, n1, eof0, eof1, mode, table, name_bits, pairs, cap_pairs, nullptr, info);
+}
+
+int vs_fastq_join_singles_host(const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
+                               uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint32_t *singles0, uint64_t cap_singles0, uint32_t *singles1,
+                               uint64_t cap_singles1, uint64_t info[10]) {
+    const PnSinglesOut sing = {{singles0, singles1}, {cap_singles0, cap_singles1}};
+    return pn_join_host_entry("vs_fastq_join_singles_host", text0, n0, text1, n1, eof0, eof1, mode, table, name_bits, pairs, cap_pairs, &sing, info);
+}
+
+static int pn_join_text_entry(const char *who, vs_ctx *ctx, const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode,
+                              uint32_t table, uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, const PnSinglesOut *sing, uint32_t guard, uint64_t *info) {
     if (!ctx || (!text0 && n0) || (!text1 && n1) || !info || (!pairs && cap_pairs) || n0 > STREAM_MAX_WINDOW || n1 > STREAM_MAX_WINDOW || !pn_table_ok(table) ||
-        (mode != VS_PN_STRICT && mode != VS_PN_SINGLES) || guard > (1u << 20))
-        return vs_fail(ctx, VS_E_ARG, "vs_fastq_join_text: bad argument");
+        (sing ? (mode != VS_PN_SINGLES && mode != VS_PN_KEEP) || (!sing->list[0] && sing->cap[0]) || (!sing->list[1] && sing->cap[1])
+              : (mode != VS_PN_STRICT && mode != VS_PN_SINGLES)) ||
+        guard > (1u << 20))
+        return vs_fail(ctx, VS_E_ARG, "%s: bad argument", who);
     VS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint32_t SENTINEL = 0xA5C3F00Du;
@@ -680,7 +832,7 @@ int vs_fastq_join_text(vs_ctx *ctx, const uint8_t *text0, uint64_t n0, const uin
     std::vector<uint32_t> h(all ? all : 1u, SENTINEL);
     VS_HIP(ctx, rec.reserve(sizeof(uint32_t) * (all ? all : 1u)));
     if (all) VS_HIP(ctx, hipMemcpyAsync(rec.ptr(), h.data(), sizeof(uint32_t) * all, hipMemcpyHostToDevice, st));
-    if (int rc = pn_join_device(ctx, st, w[0], w[1], mode == VS_PN_SINGLES, table, name_bits ? name_bits : 64u, jd, rec.as<uint32_t>() + guard, stat.as<uint32_t>(), hs)) return rc;
+    if (int rc = pn_join_device(ctx, st, w[0], w[1], mode != VS_PN_STRICT, table, name_bits ? name_bits : 64u, jd, rec.as<uint32_t>() + guard, stat.as<uint32_t>(), hs)) return rc;
     if (all) VS_HIP(ctx, hipMemcpyAsync(h.data(), rec.ptr(), sizeof(uint32_t) * all, hipMemcpyDeviceToHost, st));
     VS_HIP(ctx, hipStreamSynchronize(st));
     for (uint32_t g = 0; g < guard; g++)
@@ -690,10 +842,50 @@ int vs_fastq_join_text(vs_ctx *ctx, const uint8_t *text0, uint64_t n0, const uin
         if (h[guard + k] == SENTINEL) return vs_fail(ctx, VS_E_STATE, "vs_fastq_join_text: a word of the pair list was not written");
     for (size_t k = 2u * (size_t)jd.n_pairs; !twice && k < body; k++)
         if (h[guard + k] != SENTINEL) return vs_fail(ctx, VS_E_STATE, "vs_fastq_join_text: a word behind the pair list was written");
-    pn_join_info(info, mode == VS_PN_SINGLES, jd.n_pairs, jd.li, jd.lj, jd.dup, jd.order, jd.first_bad, w[0].n_rec, w[1].n_rec, eof0 != 0, eof1 != 0);
+    pn_join_info(info, mode != VS_PN_STRICT, jd.n_pairs, jd.li, jd.lj, jd.dup, jd.order, jd.first_bad, w[0].n_rec, w[1].n_rec, eof0 != 0, eof1 != 0);
     const uint64_t np = std::min<uint64_t>(cap_pairs, info[0]);
     if (np) memcpy(pairs, h.data() + guard, sizeof(uint32_t) * 2u * np);
+    if (!sing) return VS_OK;
+    // the kept singles of what the round decides: either list at its exact size between two rows of `guard` sentinel words
+    const uint32_t dec[2] = {(uint32_t)info[3], (uint32_t)info[4]};
+    const uint32_t P = (uint32_t)info[0];  // (0 where the round is refused: then nothing is decided either)
+    if (dec[0] < P || dec[1] < P) return vs_fail(ctx, VS_E_STATE, "%s: the decided records of the round do not hold its pairs", who);
+    const size_t ns[2] = {(size_t)(dec[0] - P), (size_t)(dec[1] - P)};
+    VsDevBuf srec[2];
+    std::vector<uint32_t> hl[2];
+    for (int f = 0; f < 2; f++) {
+        hl[f].assign(ns[f] + 2u * (size_t)guard + 1u, SENTINEL);
+        VS_HIP(ctx, srec[f].reserve(sizeof(uint32_t) * hl[f].size()));
+        VS_HIP(ctx, hipMemcpyAsync(srec[f].ptr(), hl[f].data(), sizeof(uint32_t) * hl[f].size(), hipMemcpyHostToDevice, st));
+    }
+    jd.n_pairs = P;
+    if (int rc = pn_singles_device(ctx, st, w[0].n_rec, w[1].n_rec, dec, jd, srec[0].as<uint32_t>() + guard, srec[1].as<uint32_t>() + guard, stat.as<uint32_t>() + PS_WORDS))
+        return rc;
+    for (int f = 0; f < 2; f++) VS_HIP(ctx, hipMemcpyAsync(hl[f].data(), srec[f].ptr(), sizeof(uint32_t) * hl[f].size(), hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipStreamSynchronize(st));
+    for (int f = 0; f < 2; f++) {
+        for (uint32_t g = 0; g < guard; g++)
+            if (hl[f][g] != SENTINEL || hl[f][guard + ns[f] + g] != SENTINEL) return vs_fail(ctx, VS_E_STATE, "%s: a kernel wrote outside the singles list of file %d", who, f + 1);
+        if (hl[f][2u * (size_t)guard + ns[f]] != SENTINEL) return vs_fail(ctx, VS_E_STATE, "%s: a kernel wrote outside the singles list of file %d", who, f + 1);
+        for (size_t k = 0; k < ns[f]; k++)
+            if (hl[f][guard + k] == SENTINEL) return vs_fail(ctx, VS_E_STATE, "%s: a word of the singles list of file %d was not written", who, f + 1);
+        const uint64_t take = std::min<uint64_t>(sing->cap[f], ns[f]);
+        if (take) memcpy(sing->list[f], hl[f].data() + guard, sizeof(uint32_t) * take);
+        info[8 + f] = ns[f];
+    }
     return VS_OK;
+}
+
+int vs_fastq_join_text(vs_ctx *ctx, const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
+                       uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint32_t guard, uint64_t info[8]) {
+    return pn_join_text_entry("vs_fastq_join_text", ctx, text0, n0, text1, n1, eof0, eof1, mode, table, name_bits, pairs, cap_pairs, nullptr, guard, info);
+}
+
+int vs_fastq_join_singles_text(vs_ctx *ctx, const uint8_t *text0, uint64_t n0, const uint8_t *text1, uint64_t n1, int eof0, int eof1, int mode, uint32_t table,
+                               uint32_t name_bits, uint32_t *pairs, uint64_t cap_pairs, uint32_t *singles0, uint64_t cap_singles0, uint32_t *singles1,
+                               uint64_t cap_singles1, uint32_t guard, uint64_t info[10]) {
+    const PnSinglesOut sing = {{singles0, singles1}, {cap_singles0, cap_singles1}};
+    return pn_join_text_entry("vs_fastq_join_singles_text", ctx, text0, n0, text1, n1, eof0, eof1, mode, table, name_bits, pairs, cap_pairs, &sing, guard, info);
 }
 
 }  // extern "C"

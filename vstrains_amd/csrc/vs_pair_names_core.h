@@ -184,6 +184,39 @@ IL_HD void pn_decide(uint32_t n_pairs, uint32_t li, uint32_t lj, uint32_t r0, ui
     if (eof0) dec[1] = r1;
 }
 
+// KEPT SINGLES (VS_PN_KEEP).  A kept single of a round is a DECIDED record that is in no pair: file-1 record i < dec[0] with
+// mate[i] none; file-2 record j < dec[1] that no pair names (mated[j], one byte per file-2 record, scattered from mate[]).
+// A record behind dec[f] is not a single of this round: it is in the next windows and is judged there, once.  With the cut
+// independence above, the kept singles of file f over all rounds are, for a valid input, exactly the complete records of file
+// f whose key is not in both files, in file order.  The two predicates, for the compaction kernels and the host twin:
+struct PnUnmated0 {
+    const uint32_t *mate;
+    IL_HD bool operator()(uint32_t i) const { return mate[i] == PN_NONE; }
+};
+struct PnUnmated1 {
+    const uint8_t *mated;
+    IL_HD bool operator()(uint32_t j) const { return mated[j] == 0u; }
+};
+
+// mated[] of the n1 file-2 records from mate[] of the n0 file-1 records, on one host thread
+inline void pn_mated_host(const uint32_t *mate, uint32_t n0, uint8_t *mated, uint32_t n1) {
+    for (uint32_t j = 0; j < n1; j++) mated[j] = 0u;
+    for (uint32_t i = 0; i < n0; i++)
+        if (mate[i] < n1) mated[mate[i]] = 1u;
+}
+
+// the records r < dec with pred(r), in order, into out (at most cap of them); returns how many there are
+template <class Pred>
+inline uint32_t pn_singles_host(const Pred &pred, uint32_t dec, uint32_t *out, uint64_t cap) {
+    uint32_t q = 0;
+    for (uint32_t r = 0; r < dec; r++)
+        if (pred(r)) {
+            if (q < cap) out[q] = r;
+            q++;
+        }
+    return q;
+}
+
 // The join on one host thread.  rec (2 * min(R0, R1) words): rec[2p], rec[2p + 1] = the file-1 and the file-2 record of pair p.
 // res: [0] pairs (beyond min(R0, R1) only with res[1] set), [1] the smallest file-1 record whose key occurs twice, [2] the same of file 2, [3] the first pair whose
 // file-2 record does not lie behind the one before it, [4] table full (PN_NONE / 0: none).

@@ -79,6 +79,15 @@ struct PackBam {  // the records of a window of the BAM ingest
         return PackBamEnd{b.win + r[3], r[2], (r[1] & 0x10u) != 0u};
     }
 };
+struct PackBamSingles {  // the kept singletons of the BAM ingest: even end e is record list[e / 2] of the window, odd ends are empty
+    BamSingles b;
+    __device__ PackBamEnd open(uint32_t e) const {
+        const uint32_t i = (e & 1u) ? b.n_rec : b.list[e >> 1];
+        if (i >= b.n_rec) return PackBamEnd{b.win, 0u, false};  // (an odd end; never a list entry: the list holds records of the window)
+        const uint32_t *r = b.recs + 4u * (size_t)i;
+        return PackBamEnd{b.win + r[3], r[2], (r[1] & 0x10u) != 0u};
+    }
+};
 
 // one thread per packed word; mask (may be NULL) beside the words
 template <class Src>
@@ -121,6 +130,7 @@ void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, cons
 void vs_launch_pack_records(hipStream_t st, const SlWin &w, const uint32_t *rec, const vs_reads *r) { launch_pack(st, PackRecords{w, rec}, r); }
 void vs_launch_pack_pairs(hipStream_t st, const SlWin &f0, const SlWin &f1, const uint32_t *rec, const vs_reads *r) { launch_pack(st, PackPairs{f0, f1, rec}, r); }
 void vs_launch_pack_bam(hipStream_t st, const BamEnds &b, const vs_reads *r) { launch_pack(st, PackBam{b}, r); }
+void vs_launch_pack_bam_singles(hipStream_t st, const BamSingles &b, const vs_reads *r) { launch_pack(st, PackBamSingles{b}, r); }
 
 // The lengths of a singles block: one thread per end (and one more for the closing word offset).  Even end e is the sequence
 // line of its record (as PackSingles reads it): meta = its length, wcnt = its packed words; odd ends are absent: no length,

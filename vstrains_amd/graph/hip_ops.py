@@ -389,7 +389,7 @@ class HipBackend:
         self.check_names = check_names  # "strict" / "singles": the two FASTQ files are paired by read name on the device
         self.pair_names_info = None  # that stream's info (singles dropped per file, ...) after pe_links
         self.single = list(single)  # files of unpaired reads, counted into the same counters after the pairs
-        self.count_singles = count_singles  # the single records of the interleaved FASTQ are counted instead of dropped
+        self.count_singles = count_singles  # --count-singles: the records without a mate are counted instead of dropped
         self.single_info = []  # per file of unpaired reads: what it added (pe_inference.count_links.single_info) after pe_links
         self.pe_stats = None
 

@@ -201,7 +201,7 @@ def _run(args, logger, backend=None):
                                  pre.ksize, list(pre.nodes1.keys()))
     timings["pe_inference_s"] = time.time() - t0
     singletons = (getattr(backend, "bam_info", None) or {}).get("singletons", 0)
-    if singletons:
+    if singletons and not getattr(backend, "count_singles", False):
         logger.info("{0} records of the BAM have no mate in it and were dropped".format(singletons))
     singles = (getattr(backend, "interleaved_info", None) or {}).get("singles", 0)
     if singles and not getattr(backend, "count_singles", False):
@@ -209,7 +209,7 @@ def _run(args, logger, backend=None):
     for rec in getattr(backend, "single_info", None) or ():
         logger.info("{0} unpaired reads of {1} were counted into the paired end information".format(rec["used"], rec["path"]))
     by_names = getattr(backend, "pair_names_info", None) or {}
-    if by_names.get("singles_fwd", 0) or by_names.get("singles_rve", 0):
+    if (by_names.get("singles_fwd", 0) or by_names.get("singles_rve", 0)) and not getattr(backend, "count_singles", False):
         logger.info("{0} records of {1} and {2} records of {3} have no mate by name in the other file and were dropped".format(
             by_names["singles_fwd"], args.fwd, by_names["singles_rve"], args.rve))
     logger.info("paired end information stored")

@@ -584,17 +584,22 @@ class PairedNameStream:
     has (trimmed or filtered separately); mates are found by a hash join on the names, records without a mate are dropped and
     counted per file, and the result is that of the two files filtered to their shared names, whatever the chunk size.  A name
     twice in one file's window, mates out of order inside a pair of windows, and a window beyond ``VS_PAIR_WINDOW`` bytes
-    without a decision raise ``ValueError``.  Interface of ``FastqStream``; ``info`` has ``pairs``, ``singles_fwd``,
-    ``singles_rve``, ``records_fwd``, ``records_rve``, ``windows``, ``max_window_bytes``, ``text_bytes``, ``file_bytes``,
-    ``flags``."""
+    without a decision raise ``ValueError``.  ``singles="keep"``: joined alike, but the records without a mate are KEPT: when
+    the pairs of a round are out, its decided records that are in no pair come as singles blocks (``ReadBlock.unpaired``) of
+    up to ``block_pairs`` reads, file 1's first, then file 2's, each in file order.  Interface of ``FastqStream``; ``info``
+    has ``pairs``, ``singles_fwd``, ``singles_rve`` (dropped, or kept), ``records_fwd``, ``records_rve``, ``windows``,
+    ``max_window_bytes``, ``text_bytes``, ``file_bytes``, ``flags``."""
 
-    def __init__(self, fwd: str, rve: str, ctx: "Context", block_pairs: int = 1 << 20, singles: bool = False):
+    def __init__(self, fwd: str, rve: str, ctx: "Context", block_pairs: int = 1 << 20, singles=False):
         self._ctx = ctx
         self._h = None
         self.block_pairs = block_pairs
+        if isinstance(singles, str) and singles != "keep":
+            raise ValueError('singles is False, True or "keep" (got %r)' % (singles,))
+        self.keep = singles == "keep"
         self.singles = bool(singles)
         h = C.c_void_p()
-        rc = nat.lib().vs_fastq_pn_open(ctx._h, os.fspath(fwd).encode(), os.fspath(rve).encode(), 1 if singles else 0, C.byref(h))
+        rc = nat.lib().vs_fastq_pn_open(ctx._h, os.fspath(fwd).encode(), os.fspath(rve).encode(), 2 if self.keep else 1 if singles else 0, C.byref(h))
         if rc != nat.VS_OK:
             msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
             if "cannot open" in msg:
@@ -671,6 +676,33 @@ def fastq_join(text0: bytes, text1: bytes, eof0: bool = True, eof1: bool = True,
                                       first_bad=opt(info[7]))
 
 
+def fastq_join_singles(text0: bytes, text1: bytes, eof0: bool = True, eof1: bool = True, ctx: "Context" = None, table: int = 0, name_bits: int = 0,
+                       guard: int = 64):
+    """``fastq_join`` (``singles=True``) and the KEPT singles of the round as well (test aid): ``vs_fastq_join_singles_host``, or
+    with ``ctx`` the kernels (``vs_fastq_join_singles_text``, ``guard`` sentinel words around both device lists).  Returns
+    (pairs, singles of window 1, singles of window 2 -- uint32 record indices in order: the decided records in no pair --,
+    info as ``fastq_join`` gives it)."""
+    b0, b1 = (np.frombuffer(t or b"\0", dtype=np.uint8) for t in (text0, text1))
+    cap = min(len(text0), len(text1)) // 8 + 1
+    caps = (len(text0) // 4 + 1, len(text1) // 4 + 1)
+    pairs = np.zeros((cap, 2), dtype=np.uint32)
+    lists = [np.zeros(c, dtype=np.uint32) for c in caps]
+    info = (C.c_uint64 * 10)()
+    args = (b0.ctypes.data, len(text0), b1.ctypes.data, len(text1), 1 if eof0 else 0, 1 if eof1 else 0, 2, table, name_bits, pairs.ctypes.data, cap,
+            lists[0].ctypes.data, caps[0], lists[1].ctypes.data, caps[1])
+    if ctx is None:
+        rc = nat.lib().vs_fastq_join_singles_host(*args, info)
+        if rc != nat.VS_OK:
+            raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    else:
+        nat.check(ctx._h, nat.lib().vs_fastq_join_singles_text(ctx._h, *args, guard, info))
+    none = (1 << 64) - 1
+    opt = lambda v: None if v == none else int(v)
+    return (pairs[:int(info[0])], lists[0][:int(info[8])], lists[1][:int(info[9])],
+            dict(pairs=int(info[0]), records=(int(info[1]), int(info[2])), decided=(int(info[3]), int(info[4])),
+                 duplicate=None if info[5] == none else (int(info[5] >> 32), int(info[5] & 0xFFFFFFFF)), order=opt(info[6]), first_bad=opt(info[7])))
+
+
 class BamStream:
     """The read pairs of ONE collated BAM file (unaligned BAM from the sequencer, or the unmapped pairs of a host
     alignment after ``samtools collate``) through ``vs_bam_stream_*``: the BGZF members inflated on the device, the records
@@ -689,15 +721,22 @@ class BamStream:
     /dev/null -0 /dev/null`` writes, up to the order of the pairs.  ``info`` also has ``singletons``, ``waiting_max`` (most
     records carried from one window to the next), ``carried_bytes_max`` and ``windows``.  More than 64 records of one name
     and one end in a window, or waiting records beyond the largest window, raise ``ValueError`` advising ``samtools
-    collate``."""
+    collate``.  ``by_name=True, singles="keep"``: matched alike, but the singletons are KEPT: at the end of the input they come
+    in file order as singles blocks (``ReadBlock.unpaired``) of up to ``block_pairs`` reads, each read as ``samtools fastq
+    -s`` writes it (reversed and complemented under 0x10; no bases: a read of length 0)."""
 
-    def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20, by_name: bool = False):
+    def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20, by_name: bool = False, singles=None):
         self._ctx = ctx
         self._h = None
         self.block_pairs = block_pairs
         self.by_name = bool(by_name)
+        if singles not in (None, "keep"):
+            raise ValueError('singles is None or "keep" (got %r)' % (singles,))
+        self.keep = singles == "keep"
+        if self.keep and not by_name:
+            raise ValueError('singles="keep" keeps the singletons of a BAM whose mates are matched by name and needs by_name=True: a collated BAM has none')
         h = C.c_void_p()
-        rc = nat.lib().vs_bam_stream_open_mode(ctx._h, path.encode(), 1 if by_name else 0, C.byref(h))
+        rc = nat.lib().vs_bam_stream_open_mode(ctx._h, path.encode(), 2 if self.keep else 1 if by_name else 0, C.byref(h))
         if rc != nat.VS_OK:
             msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
             if "cannot open" in msg:
@@ -792,7 +831,7 @@ class BamStream:
         rng = (C.c_uint64 * 5)(int(mine.offsets[(everyone[rank][2] * rank) // mine.world]), drop, (1 << 64) - 1 if own_end is None else own_end,
                                before & 1, start)
         self = cls.__new__(cls)
-        self._ctx, self._h, self.block_pairs, self.by_name = ctx, None, block_pairs, False
+        self._ctx, self._h, self.block_pairs, self.by_name, self.keep = ctx, None, block_pairs, False, False
         h = C.c_void_p()
         rc = nat.lib().vs_bam_stream_open_range(ctx._h, mine.path.encode(), rng, C.byref(h))
         err = None

@@ -43,16 +43,20 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     counts the records without a mate); ``count_links.pair_names_info`` is then the stream's ``info``, else None.
     ``single``: files of UNPAIRED reads (the unpaired survivors of a trimmer, merged reads), each streamed into the same
     counter after the pairs (``SingleEndStream``); ``count_singles``: the single records of the interleaved FASTQ
-    (``interleaved="singles"``) are kept and counted instead of dropped.  An unpaired read is worth what the reference gives
+    (``interleaved="singles"``), the records without a mate of the two files joined by name (``check_names="singles"``) or the
+    singletons of the BAM (``bam_by_name``) are kept and counted instead of dropped.  An unpaired read is worth what the reference gives
     one end of a pair: its own triangle of ``short_mat``, nothing in ``node_mat``; its tallies go to
     ``PeCounter.single_stats``, apart from the pairs'.  ``count_links.single_info`` is the list of per-file dicts (``path``,
-    ``reads``, ``with_n``, ``short``, ``used``), the interleaved file's first under ``count_singles``."""
+    ``reads``, ``with_n``, ``short``, ``used``), the kept records' first under ``count_singles``: one entry for the interleaved
+    file or the BAM, one entry with ``path = "FWD + RVE"`` for the two files joined by name (their blocks alternate per round;
+    the per-file kept counts are ``pair_names_info``'s ``singles_fwd`` / ``singles_rve``)."""
     rank, world = _rank_world()
     count_links.bam_info = None
     count_links.interleaved_info = None
     count_links.pair_names_info = None
     count_links.single_info = []
-    single = unpaired_input(single, count_singles, world, interleaved)  # (what the flags cannot apply to is a ValueError)
+    single = unpaired_input(single, count_singles, world, interleaved, check_names=check_names, bam_by_name=bam_by_name, fwd=fwd,
+                            rve=rve)  # (what the flags cannot apply to is a ValueError)
     by_names = check_names_input(fwd, rve, world, check_names, bam_by_name=bam_by_name, interleaved=interleaved)  # (False without the flag)
     il_path = interleaved_input(fwd, rve, world, interleaved)  # (None without the flag; what it cannot apply to is a ValueError)
     why = gzip_device_refusal(world)  # (reads the environment only; None with the switch unset)
@@ -83,15 +87,18 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
         if count_singles:
             count_links.single_info.append(_single_tally(il_path, counter, (0, 0, 0)))
     elif by_names:
-        fq = host.PairedNameStream(fwd, rve, ctx, block_pairs=BATCH_PAIRS, singles=(check_names == "singles"))  # both files, each read once
+        fq = host.PairedNameStream(fwd, rve, ctx, block_pairs=BATCH_PAIRS,
+                                   singles="keep" if count_singles else (check_names == "singles"))  # both files, each read once
         try:
             count_stream(ctx, fq, counter, progress=True)
             count_links.pair_names_info = info = fq.info
         finally:
             fq.close()
         if check_names == "singles":
-            print("Pairs joined by read name: %d; records without a mate dropped: %d of %s, %d of %s"
-                  % (info["pairs"], info["singles_fwd"], fwd, info["singles_rve"], rve))
+            print("Pairs joined by read name: %d; records without a mate %s: %d of %s, %d of %s"
+                  % (info["pairs"], "counted as unpaired reads" if count_singles else "dropped", info["singles_fwd"], fwd, info["singles_rve"], rve))
+        if count_singles:
+            count_links.single_info.append(_single_tally("%s + %s" % (fwd, rve), counter, (0, 0, 0)))
     elif bam is not None and world > 1:
         # one collated whole-BGZF BAM: the ranks share it by member, summarise their shares for every entry the previous share
         # could hand them, and each streams its own couples (BamStream.open_shard); why == the reason when rank 0 reads the
@@ -121,13 +128,16 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
         else:
             ingest_report(rank, world, "bam_whole_file_rank0", why, 0, 0, None, (0,), (0,))
     elif bam is not None:
-        fq = host.BamStream(bam, ctx, block_pairs=BATCH_PAIRS, by_name=bam_by_name)  # one BAM stands for the pair (-f and -r both name it)
+        fq = host.BamStream(bam, ctx, block_pairs=BATCH_PAIRS, by_name=bam_by_name,
+                            singles="keep" if count_singles else None)  # one BAM stands for the pair (-f and -r both name it)
         try:
             count_stream(ctx, fq, counter, progress=True)
             if bam_by_name:
                 count_links.bam_info = fq.info
         finally:
             fq.close()
+        if count_singles:
+            count_links.single_info.append(_single_tally(bam, counter, (0, 0, 0)))
     elif world > 1:
         # two whole-BGZF files: the ranks share them by member, count lines and inflate on their devices only, and each
         # streams its own records (FastqStream.open_shard); why == the reason when that is not what happens
@@ -184,11 +194,14 @@ def _single_tally(path: str, counter, before):
     return dict(path=path, reads=with_n + short + used, with_n=with_n, short=short, used=used)
 
 
-def unpaired_input(single=(), count_singles: bool = False, world: int = 1, interleaved=None, pe_text_from=None):
+def unpaired_input(single=(), count_singles: bool = False, world: int = 1, interleaved=None, pe_text_from=None, check_names=None,
+                   bam_by_name: bool = False, fwd=None, rve=None):
     """The ``--single`` files as a list, after ``--single`` / ``--count-singles`` are checked against what they cannot apply
-    to -- a ``ValueError`` that says why and what to do instead, before a device is opened: ``--count-singles`` without
-    ``--interleaved-singles``, a BAM named by ``--single``, either flag with ``--pe-text-from`` (nothing is counted then)
-    or under a process group of more than one rank."""
+    to -- a ``ValueError`` that says why and what to do instead, before a device is opened: ``--count-singles`` without one of
+    its three homes (``--interleaved --interleaved-singles``, ``--check-names --check-names-singles``, ``--bam-by-name``;
+    ``check_names`` / ``bam_by_name`` say which pairing mode is on, ``fwd`` / ``rve`` are the paired inputs, looked at only to
+    say that a collated BAM has no singletons), a BAM named by ``--single``, either flag with ``--pe-text-from`` (nothing is
+    counted then) or under a process group of more than one rank."""
     single = [os.fspath(p) for p in (single or ())]
     if not single and not count_singles:
         return single
@@ -196,9 +209,19 @@ def unpaired_input(single=(), count_singles: bool = False, world: int = 1, inter
     if pe_text_from is not None:
         raise ValueError("%s counts unpaired reads, and --pe-text-from reads the counts of an earlier run instead of counting: add the "
                          "unpaired reads to the run that wrote %s, or leave one of the flags out" % (what, pe_text_from))
-    if count_singles and interleaved != "singles":
+    if count_singles and interleaved != "singles" and check_names != "singles" and not bam_by_name:
+        if check_names == "strict":
+            raise ValueError("--count-singles counts the records without a mate instead of dropping them, and --check-names alone stops "
+                             "at the first record without a mate: no singles can exist there; add --check-names-singles, which joins "
+                             "the two files by name and lets either lack records, or leave --count-singles out")
+        if interleaved is None and fwd is not None and rve is not None and _starts_bam(fwd) and _starts_bam(rve):
+            raise ValueError("--count-singles counts the records without a mate instead of dropping them, and %s is read as a collated "
+                             "BAM, whose records come two by two: such a file has no singletons; for a BAM in any record order, or one "
+                             "that lost some mates, add --bam-by-name, or leave --count-singles out" % fwd)
         raise ValueError("--count-singles counts the single records of an interleaved FASTQ instead of dropping them and needs "
-                         "--interleaved --interleaved-singles, which say that -f and -r name one and that it may hold such records; "
+                         "--interleaved --interleaved-singles, which say that -f and -r name one and that it may hold such records "
+                         "(or --check-names --check-names-singles for two FASTQ files joined by read name, or --bam-by-name for one "
+                         "BAM: their records without a mate are counted alike); "
                          "unpaired reads in a file of their own are given with --single FILE")
     for path in single:
         if _starts_bam(path):
@@ -517,7 +540,7 @@ def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int 
         bam_input(fwd, rve, world, by_name=True)  # (what the flag cannot apply to is said before a device is opened)
     interleaved_input(fwd, rve, world, interleaved)  # (the same)
     check_names_input(fwd, rve, world, check_names, bam_by_name=bam_by_name, interleaved=interleaved)  # (the same)
-    unpaired_input(single, count_singles, world, interleaved)  # (the same)
+    unpaired_input(single, count_singles, world, interleaved, check_names=check_names, bam_by_name=bam_by_name, fwd=fwd, rve=rve)  # (the same)
     if ctx is None:
         ctx = host.Context(device)
     ids, counter = count_links(ctx, gfa, fwd, rve, kmer_size, stages_follow=stages_follow, bam_by_name=bam_by_name, interleaved=interleaved,
@@ -551,7 +574,7 @@ def main(argv=None):
     parser.add_argument("--bam-by-name", dest="bam_by_name", action="store_true", default=False,
                         help="extension: -f and -r name ONE BAM in any record order (coordinate-sorted, `samtools view -f 12` of "
                              "a sorted alignment, ...); the mates are matched by read name on the device, records without a mate "
-                             "are dropped -- no `samtools collate` first")
+                             "are dropped (counted as unpaired reads with --count-singles) -- no `samtools collate` first")
     parser.add_argument("--gzip-device", dest="gzip_device", action="store_true", default=False,
                         help="extension: decode plain .fastq.gz (one deflate stream, as gzip and pigz write it) on the device, in "
                              "parallel from speculative block starts, instead of with zlib on one host core (sets VS_GZIP_DEVICE=1; "
@@ -576,8 +599,8 @@ def main(argv=None):
                              "of an overlapping library -- in any form the paired input takes; each read is counted into st_info as the "
                              "reference counts one end of a pair, pe_info does not change (one process only)")
     parser.add_argument("--count-singles", dest="count_singles", action="store_true", default=False,
-                        help="extension: with --interleaved --interleaved-singles, the records without their mate beside them are counted "
-                             "into st_info as unpaired reads instead of dropped")
+                        help="extension: with --interleaved --interleaved-singles, with --check-names --check-names-singles or with "
+                             "--bam-by-name, the records without a mate are counted into st_info as unpaired reads instead of dropped")
     args = parser.parse_args(argv)
     interleaved = interleaved_mode(args.interleaved, args.interleaved_singles)
     check_names = check_names_mode(args.check_names, args.check_names_singles)
@@ -586,7 +609,8 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     interleaved_input(args.fwd, args.rve, world, interleaved)  # (refused before a device is opened or a process group made)
     check_names_input(args.fwd, args.rve, world, check_names, bam_by_name=args.bam_by_name, interleaved=interleaved)  # (the same)
-    unpaired_input(args.single, args.count_singles, world, interleaved)  # (the same)
+    unpaired_input(args.single, args.count_singles, world, interleaved, check_names=check_names, bam_by_name=args.bam_by_name, fwd=args.fwd,
+                   rve=args.rve)  # (the same)
     if world > 1:  # launched by torchrun: one rank per GPU, counters all-reduced over RCCL
         import torch
         import torch.distributed as dist
