@@ -37,6 +37,7 @@ void vs_tuning_load(VsTuning &t, bool experiment) {
     if (const char *v = getenv("VS_ROWS_KEYS")) t.rows_keys = atoi(v) >= 2 && atoi(v) <= 65536 ? (uint32_t)atoi(v) : 0u;
     if (const char *v = getenv("VS_ROWS_SUB")) t.rows_sub = atoi(v) >= 1024 ? (uint32_t)atoi(v) : 0u;
     if (const char *v = getenv("VS_ROWS_PER_STRIP")) t.rows_per_strip = atoi(v) > 0 && atoi(v) <= 64 ? (uint32_t)atoi(v) : 0u;
+    if (const char *v = getenv("VS_LOCUS_STAGE")) t.locus_stage = atoi(v) >= 0 ? atoi(v) : -1;
     t.no_sort = env_on("VS_NO_SORT");
     t.locus_global = env_on("VS_LOCUS_GLOBAL");
     t.no_fast = env_on("VS_NO_FAST");
@@ -91,6 +92,7 @@ static void free_index(vs_ctx *ctx) {
     ctx->d_fwd.reset();
     ctx->d_table.reset();
     ctx->d_post.reset();
+    ctx->d_slot_node.reset();
     ctx->has_index = false;
     ctx->index_bytes = 0;
 }

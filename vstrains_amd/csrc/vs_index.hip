@@ -93,17 +93,20 @@ k_seed_fill(VsIndexDev idx, const uint64_t *__restrict__ seed_off, uint64_t n_po
 __global__ void __launch_bounds__(TPB)
 k_table_finalize(const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ cnts,
                  const uint32_t *__restrict__ offs, const uint4 *__restrict__ postings,
-                 uint32_t n_slots, VsSlot *__restrict__ table, uint32_t *__restrict__ n_distinct) {
+                 uint32_t n_slots, VsSlot *__restrict__ table, uint32_t *__restrict__ slot_node, uint32_t *__restrict__ n_distinct) {
     uint32_t sl = blockIdx.x * TPB + threadIdx.x;
     if (sl >= n_slots) return;
     VsSlot out;
+    uint32_t node = 0;  // the locus key a read gets whose first seed that hits is this slot's (vs_locus_probe): the node of
+                        // the slot's first posting, in the order THIS build's k_seed_fill stored them
     uint64_t key = keys[sl];
     if (key == VS_EMPTY_KEY) {
         out.key = VS_EMPTY_KEY; out.a = 0; out.b = 0;
     } else {
         uint32_t c = cnts[sl];
+        const uint4 p = postings[offs[sl]];
+        node = p.x & 0x01FFFFFFu;
         if (c == 1u) {
-            const uint4 p = postings[offs[sl]];
             out.key = key; out.a = p.x; out.b = p.y;
         } else {
             out.key = key | VS_MULTI_BIT; out.a = offs[sl]; out.b = c;
@@ -111,6 +114,7 @@ k_table_finalize(const unsigned long long *__restrict__ keys, const uint32_t *__
         atomicAdd(n_distinct, 1u);
     }
     table[sl] = out;
+    slot_node[sl] = node;
 }
 
 static void seed_geometry(uint32_t K, uint32_t *w, uint32_t *s) {
@@ -281,7 +285,9 @@ extern "C" int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint
         VS_HIP(ctx, hipMemsetAsync(d_cursor, 0, sizeof(uint32_t) * n_slots_final, st));
         VS_HIP(ctx, ctx->d_table.reserve(sizeof(VsSlot) * n_slots_final));
         d.table = ctx->d_table.as<const VsSlot>();
-        ctx->index_bytes += sizeof(VsSlot) * n_slots_final;
+        VS_HIP(ctx, ctx->d_slot_node.reserve(sizeof(uint32_t) * n_slots_final));
+        d.slot_node = ctx->d_slot_node.as<const uint32_t>();
+        ctx->index_bytes += (sizeof(VsSlot) + sizeof(uint32_t)) * n_slots_final;
         if (npos) {
             unsigned nb = (unsigned)((npos + TPB - 1) / TPB);
             hipLaunchKernelGGL(k_seed_insert, dim3(nb), dim3(TPB), 0, st, d, d_seed_off, npos, d_keys, d_cnts, d_pos_slot,
@@ -291,7 +297,7 @@ extern "C" int vs_index_build(vs_ctx *ctx, const uint8_t *node_ascii, const uint
                                ctx->d_post.as<uint4>());
         }
         hipLaunchKernelGGL(k_table_finalize, dim3((unsigned)((n_slots_final + TPB - 1) / TPB)), dim3(TPB), 0, st, d_keys, d_cnts,
-                           d_offs, ctx->d_post.as<const uint4>(), (uint32_t)n_slots_final, ctx->d_table.as<VsSlot>(), d_flags + 1);
+                           d_offs, ctx->d_post.as<const uint4>(), (uint32_t)n_slots_final, ctx->d_table.as<VsSlot>(), ctx->d_slot_node.as<uint32_t>(), d_flags + 1);
         VS_HIP(ctx, hipGetLastError());
         VS_HIP(ctx, hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
         VS_HIP(ctx, hipStreamSynchronize(st));

@@ -74,6 +74,7 @@ struct VsIndexDev {
     uint32_t rc_delta;          // so that a kernel can address either strand off one uniform base)
     const VsSlot *table;        // [1 << table_bits]
     const uint4 *postings;      // VsPosting records, the postings of one seed contiguous
+    const uint32_t *slot_node;  // [1 << table_bits] the locus node of a slot: the node of its first posting as this build stored them (empty slot: anything)
 };
 
 struct VsReadsDev {
@@ -119,7 +120,7 @@ struct vs_ctx {
     bool has_index = false;
     VsIndexDev idx{};
     // owned device allocations of the index
-    VsDevBuf d_meta, d_fwd, d_table, d_post;
+    VsDevBuf d_meta, d_fwd, d_table, d_post, d_slot_node;
     uint64_t n_seed_pos = 0, n_slots = 0, n_distinct = 0, index_bytes = 0;
     uint32_t max_node_len = 0;
     // scratch for vs_pe_count

@@ -432,6 +432,11 @@ __device__ __forceinline__ uint32_t vs_probe_from(const VsIndexDev &idx, uint64_
 }
 
 extern __shared__ __attribute__((aligned(16))) uint32_t vs_lds[];
+__device__ __forceinline__ void vs_wave_sync() {  // LDS written by this wavefront is visible to all of its lanes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
 
 // (TileLayout, the compile-time shapes STD_* / STD2_* and vs_std_table: vs_pe_plan.h)
 // MODE 0: generic loops (masked reads through the validity mask, any stride / read length);
@@ -1821,6 +1826,24 @@ k_rows_sum(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ list
 // counters (integer addition commutes); this one only changes how many global atomics it takes.
 // key: node index, N = no seed of the forward read hits, N+1 = pair dropped by the N / length
 // filters (still counted in the stats by k_pe_tiles).
+// The locus node of the seed `key`, or ~0u when no slot holds it.  A slot's node stands beside the table (slot_node, written
+// by the index build from the finished postings), so the slot and its node are requested together -- the slot index is
+// known before the slot arrives -- and no posting is loaded; the one probe in ten that moves on requests again.
+#define VS_LOCUS_MISS 0xFFFFFFFFu
+__device__ __forceinline__ uint32_t vs_locus_probe(const VsIndexDev &idx, uint64_t key) {
+    const uint32_t mask = (1u << idx.table_bits) - 1u;
+    uint32_t sl = vs_slot_of(key, idx.table_bits);
+    const uint4 *tab = (const uint4 *)idx.table;
+    for (;;) {
+        const uint4 raw = tab[sl];
+        const uint32_t node = idx.slot_node[sl];
+        const uint64_t k = (uint64_t)raw.x | ((uint64_t)raw.y << 32);
+        if (k == VS_EMPTY_KEY) return VS_LOCUS_MISS;
+        if ((k & ~VS_MULTI_BIT) == key) return node;
+        sl = (sl + 1u) & mask;
+    }
+}
+
 __device__ __forceinline__ uint32_t vs_locus_key(const VsIndexDev &idx, const VsReadsDev &rd, uint64_t p) {
     const uint32_t mf = rd.meta[2 * p], mr = rd.meta[2 * p + 1];
     const uint32_t N = idx.n_nodes, w = idx.w, s = idx.s, K = idx.K;
@@ -1831,10 +1854,10 @@ __device__ __forceinline__ uint32_t vs_locus_key(const VsIndexDev &idx, const Vs
     const bool inv = (mf >> 24) & VS_FLAG_INVALID;
     for (uint32_t j = vs_seed_phase(rlen, w, s); j + w <= rlen; j += s) {
         if (inv && vs_seed_dirty(rd.mask, base + j, w)) continue;
-        uint32_t pa, pb, sr;
+        uint32_t sr;
         const uint64_t key = vs_seed_key(rd.words, base + j, w, &sr);
-        const uint32_t c = vs_probe(idx, key, sr, &pa, &pb);
-        if (c) return c == 1u ? pa : (idx.postings[pa].x & 0x01FFFFFFu);
+        const uint32_t node = vs_locus_probe(idx, key);
+        if (node != VS_LOCUS_MISS) return node;
     }
     return N;
 }
@@ -1847,10 +1870,10 @@ __device__ __forceinline__ uint32_t vs_locus_key_end(const VsIndexDev &idx, cons
     const bool inv = (m >> 24) & VS_FLAG_INVALID;
     for (uint32_t j = vs_seed_phase(rlen, w, s); j + w <= rlen; j += s) {
         if (inv && vs_seed_dirty(rd.mask, base + j, w)) continue;
-        uint32_t pa, pb, sr;
+        uint32_t sr;
         const uint64_t key = vs_seed_key(rd.words, base + j, w, &sr);
-        const uint32_t c = vs_probe(idx, key, sr, &pa, &pb);
-        if (c) return c == 1u ? pa : (idx.postings[pa].x & 0x01FFFFFFu);
+        const uint32_t node = vs_locus_probe(idx, key);
+        if (node != VS_LOCUS_MISS) return node;
     }
     return N;
 }
@@ -1884,6 +1907,205 @@ k_locus_count(VsIndexDev idx, VsReadsDev rd, uint64_t n_pairs, uint32_t chunk, u
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < nk; i += LOCUS_TPB) cnt[(uint64_t)(key_lo + i) * n_wg + blockIdx.x] = vs_lds[i];
+}
+
+// The computing pass of a one-pass sort with the read words STREAMED THROUGH LDS (the plan says when: vs_pe_plan,
+// locus_stage_words).  k_locus_count above pays three dependent round trips per pair -- header, read words, slot -- with
+// 64 lanes on 64 lines in the last two.  A workgroup's chunk is one contiguous stretch of `words` (woff is a prefix array),
+// and so is the sixteenth of it that each WAVEFRONT takes here and walks in batches (vs_locus_batch: the longest run of
+// pairs whose words fit a buffer, one pair per lane at most).  A wavefront has two LDS buffers of its own: while batch i is
+// keyed out of one and its slots are probed, the words of batch i + 1 are on their way into the other with coalesced 16-byte
+// loads, and the headers of batch i + 2 behind them.  What is left per pair is one dependent global load, the slot with its
+// node beside it (vs_locus_probe).  The keys are vs_locus_key's, bit for bit: the same words, the same seeds in the same
+// order.  A pair whose own words exceed a buffer is a batch of its own, keyed by vs_locus_key; an end flagged
+// VS_FLAG_INVALID reads its mask from memory as there.
+// No workgroup barrier between the zeroing of the histogram and its write-out: the wavefronts run apart, as those of
+// k_locus_count do (batches of the whole workgroup behind a barrier were measured first: every batch then waits for the
+// longest probe chain among 818 pairs, and the pass took what it took before -- profiles/EXPERIMENTS.md).  Every loop is
+// bounded by the chunk, nothing waits for another workgroup.
+// (The loads of a batch are issued by every lane, with or without work, at clamped indices: straight-line code, so that
+// the wait for a slot is not also a wait for the stream requested behind it.)
+struct LocusHdr {
+    uint32_t mf, mr, ws, we, w0;  // lengths | flags of the lane's pair, its first word and the word behind its last, the first word of the batch
+    bool live;                    // the lane's pair exists
+};
+typedef uint32_t LocusQuad __attribute__((ext_vector_type(4)));  // (a plain vector: as uint4 structs the quads were copied through private memory)
+struct LocusQuads {
+    LocusQuad q0, q1, q2, q3, q4;
+};
+struct LocusProbe {  // one pair's walk over its seeds and their slots
+    uint32_t res, j, sl, node, rlen, lbase;  // lbase: the pair's first base, counted from the first of the wavefront's two buffers
+    uint64_t key, gbase;
+    uint4 raw;
+    bool have, active, inv;
+};
+__global__ void __launch_bounds__(LOCUS_TPB)
+k_locus_count_staged(VsIndexDev idx, VsReadsDev rd, uint64_t n_pairs, uint32_t chunk, uint32_t n_wg, uint32_t *__restrict__ keys,
+                     uint32_t *__restrict__ cnt, uint32_t nk, uint32_t cap) {
+    static_assert(LOCUS_STAGE_PAIRS == 64u && LOCUS_TPB / 64u == LOCUS_STAGE_WAVES, "a batch holds one pair per lane of a wavefront");
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t hist_words = (nk + 3u) & ~3u, buf_words = vs_locus_buf_words(cap);
+    uint32_t *s_hist = vs_lds;
+    uint32_t *s_buf = vs_lds + hist_words + wv * 2u * buf_words;  // [2][buf_words] of this wavefront
+    for (uint32_t i = tid; i < nk; i += LOCUS_TPB) s_hist[i] = 0;
+    __syncthreads();
+    // the wavefront's part [lo, hi) of the workgroup's chunk (empty where the chunk is: 4 097 pairs leave workgroups 241 .. 255 nothing)
+    const uint64_t c_lo = (uint64_t)blockIdx.x * chunk, c_hi = c_lo + chunk < n_pairs ? c_lo + chunk : n_pairs;
+    const uint32_t sub = (chunk + LOCUS_STAGE_WAVES - 1u) / LOCUS_STAGE_WAVES;
+    const uint64_t hi = c_lo + (uint64_t)(wv + 1u) * sub < c_hi ? c_lo + (uint64_t)(wv + 1u) * sub : c_hi;
+    const uint64_t lo = c_lo + (uint64_t)wv * sub < hi ? c_lo + (uint64_t)wv * sub : hi;
+    const bool any = lo < hi;
+    const uint32_t N = idx.n_nodes, w = idx.w, s = idx.s, K = idx.K, tmask = (1u << idx.table_bits) - 1u;
+    const uint4 *tab = (const uint4 *)idx.table;
+
+    // the headers of the batch that starts at pair P: lane t has those of pair P + t (indices clamped to the part's last pair)
+    auto load_hdr = [&](uint64_t P) -> LocusHdr {
+        LocusHdr h = {0u, 0u, 0u, 0u, 0u, false};
+        if (!any) return h;  // (uniform over the wavefront)
+        const uint64_t Pc = P < hi ? P : hi - 1u, q = P + lane < hi ? P + lane : hi - 1u;
+        const uint2 m = *(const uint2 *)(rd.meta + 2u * q);
+        h.mf = m.x;
+        h.mr = m.y;
+        h.ws = rd.woff[2u * q];
+        h.we = rd.woff[2u * q + 2u];
+        h.w0 = rd.woff[2u * Pc];
+        h.live = P + lane < hi;
+        return h;
+    };
+    // the batch cut (vs_locus_in_batch, counted): pairs in the batch (0: the first does not fit, or none is left), the word
+    // behind the last of them
+    auto cut = [&](const LocusHdr &h, uint32_t &w_end) -> uint32_t {
+        const uint64_t m = __ballot(vs_locus_in_batch(h.live, h.w0, h.we, cap));
+        const uint32_t n = (uint32_t)__popcll(m);  // (the lanes in the batch are a prefix: lane n - 1 is the last)
+        w_end = n ? (uint32_t)__shfl((int)h.we, (int)(n - 1u)) : 0u;
+        return n;
+    };
+    // the words of a staged batch on their way: whole quads from the aligned word at or below w_first (vs_locus_span)
+    // (quad k of a lane in a variable of its own, r.q<k>, not in an array: the array went to private memory)
+#define LOCUS_EACH_QUAD(X) X(0) X(1) X(2) X(3) X(4)
+    static_assert(LOCUS_STAGE_QUADS == 5u, "LOCUS_EACH_QUAD names the quads");
+    auto stage_load = [&](bool on, uint32_t w_first, uint32_t w_end, LocusQuads &r) {
+        LocusSpan sp = vs_locus_span(on ? w_first : 0u, on ? w_end : 0u);  // (off: the block's first quads, loaded and dropped)
+        if (sp.quads > buf_words / 4u) sp.quads = buf_words / 4u;          // (never: the cut keeps w_end - w_first <= cap)
+        const LocusQuad *src = (const LocusQuad *)(rd.words + sp.first);
+#define LOCUS_LOAD(k) r.q##k = src[lane + k * 64u < sp.quads ? lane + k * 64u : sp.quads - 1u];
+        LOCUS_EACH_QUAD(LOCUS_LOAD)
+#undef LOCUS_LOAD
+    };
+    auto stage_store = [&](bool on, uint32_t w_first, uint32_t w_end, const LocusQuads &r, uint32_t *buf) {
+        LocusSpan sp = vs_locus_span(w_first, w_end);
+        if (sp.quads > buf_words / 4u) sp.quads = buf_words / 4u;
+#define LOCUS_STORE(k) if (on && lane + k * 64u < sp.quads) ((LocusQuad *)buf)[lane + k * 64u] = r.q##k;
+        LOCUS_EACH_QUAD(LOCUS_STORE)
+#undef LOCUS_STORE
+#undef LOCUS_EACH_QUAD
+        vs_wave_sync();  // (written by some lanes, read by others of this wavefront)
+    };
+    // the next clean seed of a pair at or behind its j: key and slot; false: the read has none left
+    auto seek = [&](LocusProbe &q) -> bool {
+        for (; q.j + w <= q.rlen; q.j += s) {
+            if (q.inv && vs_seed_dirty(rd.mask, q.gbase + q.j, w)) continue;
+            uint32_t sr;
+            q.key = vs_seed_key((const uint32_t *)s_buf, q.lbase + q.j, w, &sr);
+            q.sl = vs_slot_of(q.key, idx.table_bits);
+            return true;
+        }
+        return false;
+    };
+    // one slot looked at, as vs_locus_probe does; a seed in no node moves on to the read's next seed
+    auto look = [&](LocusProbe &q) {
+        if (!q.active) return;
+        const uint64_t k = (uint64_t)q.raw.x | ((uint64_t)q.raw.y << 32);
+        if (k != VS_EMPTY_KEY && (k & ~VS_MULTI_BIT) == q.key) {
+            q.res = q.node;
+            q.active = false;
+            return;
+        }
+        if (k == VS_EMPTY_KEY) {
+            q.j += s;
+            q.active = seek(q);
+        } else {
+            q.sl = (q.sl + 1u) & tmask;
+        }
+        if (q.active) {
+            q.raw = tab[q.sl];
+            q.node = idx.slot_node[q.sl];
+        }
+    };
+    auto finish = [&](const LocusProbe &q, uint64_t p_first) {
+        if (q.have) {
+            keys[p_first + lane] = q.res;
+            if (q.res < nk) atomicAdd(&s_hist[q.res], 1u);
+        }
+    };
+
+    // cur: the batch whose pairs are started (buffer it & 1); nxt: the one whose words are requested while that happens;
+    // old: the batch before cur, whose pairs that are still looking go on beside cur's first looks -- their buffer is the
+    // one nxt's words go to, so they are through before those are stored.  A batch's longest chain of slots (a read error
+    // in each of the first seeds, slots passed over) is thus walked beside the next batch's shortest.
+    LocusQuads r;
+    uint64_t pc = lo, po = lo;
+    LocusHdr hc = load_hdr(pc);
+    uint32_t wec, wen;
+    uint32_t nc = cut(hc, wec);
+    bool stc = nc != 0u;
+    if (!nc && pc < hi) nc = 1u;  // (an oversize pair, alone)
+    stage_load(stc, hc.w0, wec, r);
+    stage_store(stc, hc.w0, wec, r, s_buf);
+    uint64_t pn = pc + nc;
+    LocusHdr hn = load_hdr(pn);
+    uint32_t nn = cut(hn, wen);
+    bool stn = nn != 0u;
+    if (!nn && pn < hi) nn = 1u;
+    LocusProbe qo = {};  // (nothing: have = active = false)
+    for (uint32_t it = 0; pc < hi; it++) {
+        // 1. the lane's pair of the current batch: filters, its first clean seed, the slot of that seed requested
+        LocusProbe qc = {};
+        qc.have = lane < nc;
+        qc.res = N + 1u;
+        qc.rlen = hc.mf & VS_LEN_MASK;
+        qc.inv = (hc.mf >> 24) & VS_FLAG_INVALID;
+        qc.lbase = ((it & 1u) * buf_words + hc.ws - (hc.w0 & ~3u)) * 16u;  // the pair's first base in the two buffers (vs_locus_span)
+        qc.gbase = (uint64_t)hc.ws * 16u;
+        if (qc.have && !stc) {
+            qc.res = vs_locus_key(idx, rd, pc);  // (lane 0 alone)
+        } else if (qc.have && !((((hc.mf | hc.mr) >> 24) & VS_FLAG_N) || qc.rlen < K || (hc.mr & VS_FILTER_LEN_MASK) < K)) {
+            qc.res = N;
+            qc.j = vs_seed_phase(qc.rlen, w, s);
+            qc.active = seek(qc);
+        }
+        if (!qc.active) qc.sl = 0;
+        qc.raw = tab[qc.sl];
+        qc.node = idx.slot_node[qc.sl];
+        // 2. the next batch's words, 3. the headers of the one behind it
+        stage_load(stn, hn.w0, wen, r);
+        const uint64_t p2 = pn + nn;
+        const LocusHdr h2 = load_hdr(p2);
+        // 4. the slots: the old batch to its end, the current one beside it (the first looks outside the loop: they wait
+        // for the slots alone, the stream stays in flight)
+        look(qo);
+        look(qc);
+        while (qo.active) {
+            look(qo);
+            look(qc);
+        }
+        finish(qo, po);
+        // 5. the next batch's words into the old batch's buffer, the cut behind it
+        stage_store(stn, hn.w0, wen, r, s_buf + ((it + 1u) & 1u) * buf_words);
+        uint32_t we2;
+        uint32_t n2 = cut(h2, we2);
+        const bool st2 = n2 != 0u;
+        if (!n2 && p2 < hi) n2 = 1u;
+        qo.res = qc.res; qo.j = qc.j; qo.sl = qc.sl; qo.node = qc.node; qo.rlen = qc.rlen; qo.lbase = qc.lbase; qo.key = qc.key;
+        qo.gbase = qc.gbase; qo.raw = qc.raw; qo.have = qc.have; qo.active = qc.active; qo.inv = qc.inv;
+        po = pc;
+        pc = pn; hc = hn; nc = nn; stc = stn; wec = wen;
+        pn = p2; hn = h2; nn = n2; stn = st2; wen = we2;
+    }
+    while (qo.active) look(qo);
+    finish(qo, po);
+    __syncthreads();
+    for (uint32_t i = tid; i < nk; i += LOCUS_TPB) cnt[(uint64_t)i * n_wg + blockIdx.x] = s_hist[i];
 }
 
 __global__ void __launch_bounds__(LOCUS_TPB)
@@ -1926,11 +2148,6 @@ k_pe_permute(uint64_t n_pairs, const uint32_t *__restrict__ keys, uint32_t *__re
 #define MID_SLOTS 256u
 #define MID_LIST 64u
 #define MID_WORDS (4u * MID_SLOTS + 3u * 64u + 65u + 2u * MID_LIST + 4u)
-__device__ __forceinline__ void vs_wave_sync() {  // LDS written by this wavefront is visible to all of its lanes
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 __global__ void __launch_bounds__(TPB)
 k_pe_mid(PeParams P, const uint32_t *__restrict__ in_list, const uint32_t *__restrict__ in_count, uint32_t in_cap,
          uint32_t *__restrict__ out_list, uint32_t *__restrict__ out_count) {
@@ -2484,10 +2701,18 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
                 VS_HIP(ctx, hipFuncSetAttribute((const void *)k_locus_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_keys));
                 VS_HIP(ctx, hipFuncSetAttribute((const void *)k_locus_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_keys));
             }
-            for (uint32_t key_lo = 0; key_lo < nk; key_lo += per_pass) {
-                const uint32_t n_here = (uint32_t)(nk - key_lo < per_pass ? nk - key_lo : per_pass);
-                hipLaunchKernelGGL(k_locus_count, dim3(n_wg), dim3(LOCUS_TPB), lds_keys, st, idx, reads->dev(), n_pairs, chunk, n_wg,
-                                   ctx->d_locus_keys.as<uint32_t>(), ctx->d_locus_hist.as<uint32_t>(), key_lo, n_here, key_lo == 0u ? 1u : 0u);
+            // (the staged key pass copies `words` in 16-byte quads: every block allocates them so; one that did not keeps the per-pair loads)
+            if (pl.locus_stage_words && ((uintptr_t)reads->d_words & 15u) == 0u) {
+                VS_HIP(ctx, hipFuncSetAttribute((const void *)k_locus_count_staged, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.locus_lds_bytes));
+                hipLaunchKernelGGL(k_locus_count_staged, dim3(n_wg), dim3(LOCUS_TPB), pl.locus_lds_bytes, st, idx, reads->dev(), n_pairs, chunk, n_wg,
+                                   ctx->d_locus_keys.as<uint32_t>(), ctx->d_locus_hist.as<uint32_t>(), (uint32_t)nk, pl.locus_stage_words);
+                ctx->last_launched |= VS_RAN_LOCUS_STAGED;
+            } else {
+                for (uint32_t key_lo = 0; key_lo < nk; key_lo += per_pass) {
+                    const uint32_t n_here = (uint32_t)(nk - key_lo < per_pass ? nk - key_lo : per_pass);
+                    hipLaunchKernelGGL(k_locus_count, dim3(n_wg), dim3(LOCUS_TPB), lds_keys, st, idx, reads->dev(), n_pairs, chunk, n_wg,
+                                       ctx->d_locus_keys.as<uint32_t>(), ctx->d_locus_hist.as<uint32_t>(), key_lo, n_here, key_lo == 0u ? 1u : 0u);
+                }
             }
             int rc = vs_scan_u32(ctx, ctx->d_locus_hist.as<const uint32_t>(), ctx->d_locus_hist.as<uint32_t>(), nk * n_wg,
                                  ctx->d_scan_tmp.as<uint64_t>(), nullptr);

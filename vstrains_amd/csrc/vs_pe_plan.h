@@ -37,6 +37,7 @@ struct VsTuning {
     uint32_t rows_per_strip = 0;    // VS_ROWS_PER_STRIP (0 = automatic): matrix rows one workgroup of k_rows_sum owns at a time
     bool no_sort = false, locus_global = false, no_fast = false, no_std = false, no_agg = false;
     bool no_mid = false;            // VS_NO_MID: overflow pairs straight to k_pe_slow
+    int locus_stage = -1;           // VS_LOCUS_STAGE (-1 = by the room the histogram leaves): 0 = the key pass of the locus sort with per-pair loads, N = staged through buffers of N words per wavefront, so that small blocks reach batch cuts and oversize pairs
 };
 
 // The probe grid of a read end (round 5).  A match of K bases and more holds s = K - w + 1 consecutive seed starts, so any
@@ -78,9 +79,52 @@ VS_PLAN_FN uint32_t vs_seed_probes(uint32_t len, uint32_t w, uint32_t s) {
 #define LOCUS_LDS_KEYS 36864u  // 144 KB of LDS counters
 #define LOCUS_LDS_MAX_PASSES 4u  // ... per pass; graphs of up to 147 k nodes are sorted through LDS histograms
 #define LOCUS_WGS 256u     // one per CU (measured: 1024 x 256 threads 0.70 ms, 256 x 1024 threads 0.57 ms)
+// The staged key pass (k_locus_count_staged): a wavefront copies the packed words of a batch of pairs into one of its two LDS buffers
+#define LOCUS_STAGE_WAVES 16u     // wavefronts of the workgroup, each with buffers of its own
+#define LOCUS_STAGE_PAIRS 64u     // pairs a batch holds at most: one per lane
+#define LOCUS_STAGE_QUADS 5u      // 16-byte loads a lane has in flight for the next batch
+#define LOCUS_STAGE_SLACK 16u     // words of a buffer beyond its capacity: up to 3 in front (the copy starts 16-byte aligned), 4 behind (window reads overshoot an end by up to two words), rounding
+#define LOCUS_STAGE_MAX (LOCUS_STAGE_QUADS * 4u * LOCUS_STAGE_PAIRS - LOCUS_STAGE_SLACK)  // what the lanes' loads cover
+#define LOCUS_STAGE_MIN_PAIRS 48u  // production stages only where a buffer holds this many pairs of the block's longest reads: three lanes in four with a pair (measured: 55 pairs a batch, 2 x 150 bases, win; 34 pairs, 2 x 250 bases, lose to the per-pair loads -- profiles/EXPERIMENTS.md)
+#define LOCUS_LDS_WORDS 40960u    // 160 KB, one workgroup per CU
 #define SLOW_WORDS_PER_NODE 6u
 #define LDS_BUDGET_BYTES (64u * 1024u)
 #define NI_CAP 4096u
+
+// ---- the batch cut of the staged key pass ------------------------------------------------------------------------------
+// woff is the block's prefix array of word offsets (two ends per pair, n_ends + 1 entries), so the words of pairs
+// [p0, p0 + n) are the stretch woff[2 p0] .. woff[2 (p0 + n)].  A batch that starts at pair p0 of a chunk that ends at hi
+// is the longest prefix of [p0, hi) whose stretch fits `cap` words, at most LOCUS_STAGE_PAIRS pairs.  woff is monotone, so
+// "pair p0 + i is in the batch" is a prefix property of i and every lane of the wavefront decides it for its own pair:
+// the kernel counts the lanes that say yes, vs_locus_batch below is the same count taken in turn.
+VS_PLAN_FN bool vs_locus_in_batch(bool exists, uint32_t w_first, uint32_t w_pair_end, uint32_t cap) {
+    return exists && w_pair_end - w_first <= cap;  // (exists: i < LOCUS_STAGE_PAIRS and p0 + i < hi)
+}
+struct LocusBatch {
+    uint32_t n;       // pairs: at least one while p0 < hi
+    uint32_t staged;  // 0: one pair whose own two ends do not fit the buffer -- keyed by per-pair loads, alone
+};
+VS_PLAN_FN LocusBatch vs_locus_batch(const uint32_t *woff, uint64_t p0, uint64_t hi, uint32_t cap) {
+    LocusBatch b = {0u, 1u};
+    if (p0 >= hi) return b;  // (an empty chunk, or its end)
+    const uint32_t w_first = woff[2u * p0];
+    while (b.n < LOCUS_STAGE_PAIRS && vs_locus_in_batch(p0 + b.n < hi, w_first, p0 + b.n < hi ? woff[2u * (p0 + b.n) + 2u] : 0u, cap)) b.n++;
+    if (!b.n) { b.n = 1u; b.staged = 0u; }
+    return b;
+}
+// What of `words` a staged batch copies: whole 16-byte quads from the aligned word at or below its first word to four
+// words behind its last (a window read at a seed overshoots its end by up to two words; the words behind the block's last
+// are the zero pad, VS_PAD_WORDS).  Word x of the block is word x - first of the buffer.
+struct LocusSpan {
+    uint32_t first, quads;
+};
+VS_PLAN_FN LocusSpan vs_locus_span(uint32_t w_first, uint32_t w_end) {
+    LocusSpan sp;
+    sp.first = w_first & ~3u;
+    sp.quads = (w_end + 4u - sp.first + 3u) / 4u;  // <= (cap + 10) / 4 <= (buffer words) / 4
+    return sp;
+}
+VS_PLAN_FN uint32_t vs_locus_buf_words(uint32_t cap) { return ((cap + 3u) & ~3u) + LOCUS_STAGE_SLACK; }
 
 // LDS carve shared by the kernel and the host-side size computation
 struct TileLayout {
@@ -186,6 +230,8 @@ struct PePlan {
     // locus order: through LDS histograms (keys per pass, pairs per workgroup) or global atomics
     uint32_t use_sort, lds_sort, locus_chunk, locus_per_pass;
     uint64_t locus_keys, locus_hist_words;
+    uint32_t locus_stage_words;  // capacity of each of a wavefront's two LDS buffers in the staged key pass (0: per-pair loads)
+    uint64_t locus_lds_bytes;    // dynamic LDS of k_locus_count / k_locus_count_staged
     // the counters: pair-major (k_pe_accumulate) or by row owners (pe_count_by_rows)
     uint32_t use_rows, use_table, mark_tiles;
     uint32_t acc_grid, acc_per_wg, acc_fill, acc_task_cap;
@@ -250,6 +296,20 @@ inline PePlan vs_pe_plan(const PePlanIn &in) {
         if (p.lds_sort) {
             p.locus_chunk = (uint32_t)((n_pairs + LOCUS_WGS - 1) / LOCUS_WGS);
             p.locus_per_pass = (uint32_t)(nk < LOCUS_LDS_KEYS ? nk : LOCUS_LDS_KEYS);
+            p.locus_lds_bytes = sizeof(uint32_t) * (uint64_t)p.locus_per_pass;
+            // the key pass streams the read words through two LDS buffers per wavefront (k_locus_count_staged) where one pass's
+            // histogram leaves room for them beside it: not beside a full pass of LOCUS_LDS_KEYS keys, so not in a multi-pass sort
+            if (nk < LOCUS_LDS_KEYS && tn.locus_stage != 0) {
+                const uint32_t hist = ((uint32_t)nk + 3u) & ~3u;
+                uint32_t room = ((LOCUS_LDS_WORDS - hist) / (2u * LOCUS_STAGE_WAVES) - LOCUS_STAGE_SLACK) & ~3u;
+                if (room > LOCUS_STAGE_MAX) room = LOCUS_STAGE_MAX;
+                uint32_t cap = room / (2u * wpe) >= LOCUS_STAGE_MIN_PAIRS ? room : 0u;
+                if (tn.locus_stage > 0) cap = (uint32_t)tn.locus_stage < room ? (uint32_t)tn.locus_stage : room;
+                if (cap) {
+                    p.locus_stage_words = cap;
+                    p.locus_lds_bytes = sizeof(uint32_t) * (uint64_t)(hist + 2u * LOCUS_STAGE_WAVES * vs_locus_buf_words(cap));
+                }
+            }
         }
     }
 

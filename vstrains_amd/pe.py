@@ -1421,6 +1421,7 @@ class Context:
         return (nat.lib().vs_pe_last_kernel(self._h) or b"").decode()
 
     RAN_LOCUS_LDS_SORT, RAN_LOCUS_GLOBAL_SORT, RAN_PE_MID, RAN_ROW_OWNERS = 1, 2, 8, 16
+    RAN_LOCUS_STAGED = 4
 
     @property
     def last_launched(self) -> int:
