@@ -408,6 +408,36 @@ void vs_fastq_il_close(vs_fastq_il *s);
 int vs_fastq_mates_host(const uint8_t *text, uint64_t n, int eof, uint32_t *pairs, uint64_t cap_pairs, uint64_t info[6]);
 int vs_fastq_mates_text(vs_ctx *ctx, const uint8_t *text, uint64_t n, int eof, uint32_t *pairs, uint64_t cap_pairs, uint32_t guard,
                         uint64_t info[6]);
+/* An interleaved whole-BGZF file shared among ranks by member (additions to ABI 11 without a new number: nothing that exists
+ * changes).  With m[j] = mates(j, j + 1) and p(0) = 0, p(j + 1) = m[j] ? !p(j) : 0, record j is the SECOND of a pair iff p(j) = 1.
+ * A rank owns the records [a, b) = its share of the T complete records, every pair whose FIRST record it owns and every single
+ * it owns.  A function of one bit is two bits, f(0) | f(1) << 1: const-0 = 0, flip = 1, identity = 2, const-1 = 3.  The
+ * function of a share is the composition, in order, of flip (m true) or const-0 (m false) over m[a .. b - 1]; it takes p(a) to
+ * p(b).
+ *   vs_fastq_il_range_fn   : range = {file offset of the first member, offset one past the last, lines to skip in front} as
+ *                            vs_fastq_stream_open_range takes it for one file.  *fn = the composition of m[0 .. n_rec - 2] of
+ *                            the first n_rec records of the range (identity for n_rec < 2, nothing is read then): the range is
+ *                            streamed window by window, the line ends scanned, the records matched and the windows' functions
+ *                            composed on the device; nothing is packed or classified and no text returns to the host.  info[0]
+ *                            = members inflated, [1] = file bytes read, [2] = windows, [3] = records seen.  A range with fewer
+ *                            than n_rec records, or with a '\r' or a byte >= 0x80, is VS_E_STATE
+ *   vs_il_shard_plan       : host only, pure.  fn[r] = the function of rank r's share (identity for an empty one; the last
+ *                            rank's is not used); entry[r] = p of rank r's first record: entry[0] = 0, entry[r + 1] =
+ *                            fn[r](entry[r])
+ *   vs_fastq_il_open_range : the interleaved stream on a member range, mode VS_IL_STRICT or VS_IL_SINGLES (VS_IL_KEEP: VS_E_ARG).
+ *                            The stream sees exactly n_owned + lookahead records behind the skipped lines.  entry = 1: the first
+ *                            record is the second of the previous rank's last pair, neither handed out nor counted.  lookahead =
+ *                            1: the last record is the next rank's first and the range does not end the file; classed second it
+ *                            completes this rank's last pair and is packed here, otherwise it is discarded -- never a single,
+ *                            never the start of a pair.  lookahead = 0: the range's end is the file's.  The record numbers of
+ *                            the strict mode's message are file-wide: first_record + the number within the range.
+ *                            vs_fastq_il_next / _info / _close serve the handle; pairs, singles and records count the rank's
+ *                            own decisions, so their sums over the ranks are the whole file's.  The reader never reads at or
+ *                            beyond range[1] */
+int vs_fastq_il_range_fn(vs_ctx *ctx, const char *path, const uint64_t range[3], uint64_t n_rec, uint32_t *fn, uint64_t info[4]);
+int vs_il_shard_plan(const uint32_t *fn, uint32_t world, uint32_t *entry);
+int vs_fastq_il_open_range(vs_ctx *ctx, const char *path, int mode, const uint64_t range[3], uint64_t n_owned, int lookahead, uint32_t entry,
+                           uint64_t first_record, vs_fastq_il **out);
 /* ONE file of unpaired reads (additions to ABI 11 without a new number: nothing that exists changes): the unpaired survivors of
  * a trimmer, the merged reads of an overlapping library.  Streamed as vs_fastq_il_* streams one file, in every form that
  * stream reads (plain, FIFO, gzip through zlib, BGZF inflated on the device, plain gzip on the device with VS_GZIP_DEVICE=1),

@@ -91,6 +91,10 @@ SYMBOLS = {
     "vs_fastq_il_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "vs_fastq_il_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "vs_fastq_il_close": (None, [C.c_void_p]),
+    "vs_fastq_il_range_fn": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "vs_il_shard_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "vs_fastq_il_open_range": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.c_int, C.c_uint32, C.c_uint64,
+                                         C.POINTER(C.c_void_p)]),
     "vs_fastq_se_open": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "vs_fastq_se_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "vs_fastq_se_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

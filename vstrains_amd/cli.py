@@ -68,6 +68,10 @@ def build_parser():
     p.add_argument("--interleaved-singles", dest="interleaved_singles", action="store_true", default=False,
                    help="extension: with --interleaved, records without their mate beside them (the single reads `samtools fastq "
                         "x.bam` writes among the pairs) are dropped and counted instead")
+    p.add_argument("--interleaved-shard", dest="interleaved_shard", action="store_true", default=False,
+                   help="extension, off by default: with --interleaved under torchrun, the ranks share ONE whole-BGZF interleaved file "
+                        "(`... | bgzip`) by member, each counting the pairs whose first record lies in its share; any other regular "
+                        "file is read whole by rank 0 (without the flag --interleaved is one process's)")
     p.add_argument("--check-names", dest="check_names", action="store_true", default=False,
                    help="extension: pair the two FASTQ files by read name on the device instead of by position: record i of -fwd and "
                         "record i of -rve must be mates by name (as `bwa mem` demands), and the first pair that is not stops the run -- "
@@ -118,15 +122,15 @@ def main(argv=None, backend=None):
         parser.error("--no-pe-text and --bgzf-pe-text are mutually exclusive")
     if args.pe_text_from is not None:
         for flag, name in ((args.no_pe_text, "--no-pe-text"), (args.sparse_pe_text, "--sparse-pe-text"), (args.bgzf_pe_text, "--bgzf-pe-text"),
-                           (args.bam_by_name, "--bam-by-name"), (args.interleaved or args.interleaved_singles, "--interleaved"),
+                           (args.bam_by_name, "--bam-by-name"), (args.interleaved or args.interleaved_singles or args.interleaved_shard, "--interleaved"),
                            (args.check_names or args.check_names_singles, "--check-names")):
             if flag:
                 parser.error("--pe-text-from and %s are mutually exclusive" % name)
     from . import pe_inference
 
     # (what the flags cannot apply to is a ValueError that says why, before anything is written or a device opened)
-    args.interleaved = pe_inference.interleaved_mode(args.interleaved, args.interleaved_singles)
-    pe_inference.interleaved_input(args.fwd, args.rve, pe_inference._rank_world()[1], args.interleaved)
+    args.interleaved = pe_inference.interleaved_mode(args.interleaved, args.interleaved_singles, args.interleaved_shard)
+    pe_inference.interleaved_input(args.fwd, args.rve, pe_inference._rank_world()[1], args.interleaved, shard=args.interleaved_shard)
     args.check_names = pe_inference.check_names_mode(args.check_names, args.check_names_singles)
     pe_inference.check_names_input(args.fwd, args.rve, pe_inference._rank_world()[1], args.check_names, bam_by_name=args.bam_by_name,
                                    interleaved=args.interleaved)
@@ -215,7 +219,8 @@ def main(argv=None, backend=None):
 
         backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text,
                              bgzf_info_text=args.bgzf_pe_text, bam_by_name=args.bam_by_name, interleaved=args.interleaved,
-                             check_names=args.check_names, single=args.single, count_singles=args.count_singles)
+                             check_names=args.check_names, single=args.single, count_singles=args.count_singles,
+                             interleaved_shard=args.interleaved_shard)
     elif backend is not None:
         if args.single:
             backend.single = list(args.single)
@@ -225,6 +230,7 @@ def main(argv=None, backend=None):
             backend.check_names = args.check_names
         if args.interleaved:
             backend.interleaved = args.interleaved
+            backend.interleaved_shard = args.interleaved_shard
         if args.bam_by_name:
             backend.bam_by_name = True
         if args.sparse_pe_text:

@@ -28,6 +28,18 @@
 // record stays held; at the end of the file it is a single like any other.
 // The host reads back counts, the cut and status words; no record text, except the two header lines of the message with
 // which the strict mode refuses a single record.
+//
+// A MEMBER RANGE (vs_fastq_il_open_range; one process per GPU on one whole-BGZF file): the same stream on the members that
+// hold a rank's records [a, b) and one look-ahead record, as the two-file stream has it (vs_stream.hip).  Whether record a
+// is the second of a pair follows from the parity functions of the shares in front (vs_il_shard_plan chains them); a share's
+// function is composed on the device by vs_fastq_il_range_fn: the range streamed through the same reader and window,
+// k_il_match per window, then
+//   k_il_total      one workgroup: the m of the window's records composed from their ballots, in order, into a running word
+//                   on the device -- the TOTAL where k_il_carry gives the prefixes, over exactly the records asked for.
+// The window's last record is always carried to lead the next, so every m is computed once from text that is present.
+// With entry 1 the range's first record goes unseen, and the record behind it starts with parity 0 like a file's first: no
+// parity is handed to a kernel.  The stream sees n_owned + lookahead records and no more; the look-ahead record is held
+// back like a window's last record, so it is packed only as the second of the rank's last pair.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -92,6 +104,25 @@ __global__ void __launch_bounds__(IL_CARRY_TPB) k_il_carry(uint32_t *__restrict_
         f[i] = p;
         p = il_apply(g, p);
     }
+}
+
+// m[0, n): the match flags of n records in a row.  *acc = their composed function after *acc -- the TOTAL where k_il_carry
+// gives the prefixes, and over exactly n flags: the lanes that k_il_match pads its last wavefront with are no records here.
+// One workgroup; every wavefront composes a contiguous run of 64-record groups from their ballots, thread 0 the wavefronts.
+__global__ void __launch_bounds__(IL_CARRY_TPB) k_il_total(const uint8_t *__restrict__ m, uint32_t n, uint32_t *__restrict__ acc) {
+    __shared__ uint32_t wfn[IL_CARRY_TPB / VS_WAVE];
+    const uint32_t lane = threadIdx.x & (VS_WAVE - 1u), wave = threadIdx.x / VS_WAVE;
+    const uint32_t groups = (n + VS_WAVE - 1u) / VS_WAVE, per = (groups + IL_CARRY_TPB / VS_WAVE - 1u) / (IL_CARRY_TPB / VS_WAVE);
+    const uint32_t g0 = min(groups, wave * per), g1 = min(groups, g0 + per);
+    uint32_t f = IL_F_ID;
+    for (uint32_t g = g0; g < g1; g++) {  // (g0, g1 are the wavefront's: every lane takes part in the ballot)
+        const uint32_t i = g * VS_WAVE + lane;
+        const uint64_t b = __ballot(i < n && m[i] != 0u);
+        f = il_compose(f, il_run_fn(b, min((uint32_t)VS_WAVE, n - g * VS_WAVE)));
+    }
+    if (lane == 0) wfn[wave] = f;
+    __syncthreads();
+    if (threadIdx.x == 0) *acc = il_compose(*acc, il_compose_waves(wfn, IL_CARRY_TPB / VS_WAVE));
 }
 
 __global__ void __launch_bounds__(IL_TPB) k_il_classify(const uint8_t *__restrict__ m, const uint32_t *__restrict__ wg_parity, uint32_t n_rec,
@@ -294,6 +325,11 @@ struct vs_fastq_il {
     uint32_t *d_stat = nullptr, *h_stat = nullptr;  // IS_ALL words each
     uint64_t pairs = 0, singles = 0, records = 0;
     uint32_t flags_seen = 0;
+    // a member range (vs_fastq_il_open_range): records of the range not yet decided; the last of them is the next rank's
+    // first (look-ahead); the range's first record is the second of the previous rank's last pair and goes unseen; the
+    // window that holds the range's last record has been matched
+    bool ranged = false, lookahead = false, entry_pending = false, range_done = false;
+    uint64_t remain = 0;
     bool done = false;
     int failed = VS_OK;
     std::string failed_msg;
@@ -342,6 +378,41 @@ int il_finish(vs_ctx *ctx, vs_fastq_il *s) {
     return VS_OK;
 }
 
+// the first n_lines lines of the scanned window (`records` complete records) dropped: its line ends scattered once, the
+// offset of the last one to drop read back (synchronises the stream)
+int il_drop_lines(vs_ctx *ctx, vs_fastq_il *s, uint64_t n_lines, uint64_t records) {
+    DevFile &d = s->df;
+    if (d.n_nl < n_lines) return vs_fail(ctx, VS_E_STATE, "%s: fewer lines at the front of its member range than were counted", s->rd.path.c_str());
+    if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return rc;
+    vs_launch_sl_scatter(s->st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
+    VS_HIP(ctx, hipGetLastError());
+    uint32_t at = 0;
+    VS_HIP(ctx, hipMemcpyAsync(&at, d.ends.as<uint32_t>() + (n_lines - 1u), sizeof at, hipMemcpyDeviceToHost, s->st));
+    VS_HIP(ctx, hipStreamSynchronize(s->st));
+    if ((size_t)at + 1u > d.w.size) return vs_fail(ctx, VS_E_STATE, "%s: a line end beyond the window", s->rd.path.c_str());
+    return drop_front(ctx, s->st, d, (size_t)at + 1u, records);
+}
+
+// One more slot appended to the window and the window scanned.  A member range starts inside a record of the rank before:
+// the lines in front that belong to it go (they all end in the range's first member -- that is how the plan picks it -- and
+// a slot holds whole members, so the first window has them).
+int il_append(vs_ctx *ctx, vs_fastq_il *s) {
+    DevFile &d = s->df;
+    {
+        SlotLease taken;  // (goes back once the stream is synchronised: the upload is done)
+        if (int rc = append_chunk(ctx, s->st, d, s->rd, taken, s->d_stat + IS_BAD)) return rc;
+        if (int rc = il_scan(ctx, s)) return rc;
+        if (taken) (void)member_failed(d, s->rd, *taken, s->h_stat[IS_BAD]);
+    }
+    if (!s->ranged || d.err != VS_OK) return VS_OK;
+    // (pass 1 of the sharded open saw neither a '\r' nor a byte >= 0x80 in the whole file, and the plan rests on that)
+    if (d.flags) return vs_fail(ctx, VS_E_STATE, "%s changed after its lines were counted", s->rd.path.c_str());
+    if (!d.skip) return VS_OK;
+    if (int rc = il_drop_lines(ctx, s, d.skip, 0)) return rc;
+    d.skip = 0;
+    return il_scan(ctx, s);
+}
+
 // The next window: the decided records of the last one cut off, a slot appended, the line ends found, the records matched.
 // *end: nothing more comes (the stream is done or has failed; the code is returned).
 int il_next_window(vs_ctx *ctx, vs_fastq_il *s, bool *end) {
@@ -349,7 +420,7 @@ int il_next_window(vs_ctx *ctx, vs_fastq_il *s, bool *end) {
     hipStream_t st = s->st;
     *end = true;
     if (s->matched) {
-        if (d.eof) return il_finish(ctx, s);
+        if (d.eof || s->range_done) return il_finish(ctx, s);
         size_t cut = 0;
         if (s->mt.decided) {  // one past the line end that closes the last decided record
             uint32_t at = 0;
@@ -363,20 +434,40 @@ int il_next_window(vs_ctx *ctx, vs_fastq_il *s, bool *end) {
         s->pair_cur = 0;
         s->single_cur = 0;
     }
-    {
-        SlotLease taken;  // (goes back once the stream is synchronised: the upload is done)
-        if (int rc = append_chunk(ctx, st, d, s->rd, taken, s->d_stat + IS_BAD)) return il_fail(ctx, s, rc, vs_last_error(ctx));
-        if (int rc = il_scan(ctx, s)) return il_fail(ctx, s, rc, vs_last_error(ctx));
-        if (taken) (void)member_failed(d, s->rd, *taken, s->h_stat[IS_BAD]);
+    for (;;) {
+        if (int rc = il_append(ctx, s)) return il_fail(ctx, s, rc, vs_last_error(ctx));
+        if (d.err == VS_OK && d.flags && d.validated < d.w.size) {  // (text that arrived with this slot: host text mode)
+            if (translate_window(ctx, d, s->rd.path) == VS_OK)
+                if (int rc = il_scan(ctx, s)) return il_fail(ctx, s, rc, vs_last_error(ctx));
+        }
+        if (d.err != VS_OK) return il_fail(ctx, s, s->rd.err != VS_OK ? s->rd.err : d.err, s->rd.err != VS_OK ? s->rd.err_msg : d.err_msg);
+        if (!s->entry_pending) break;
+        // the range's first record is the SECOND of the previous rank's last pair: it goes as soon as it is whole, uncounted,
+        // and the record behind the second of a pair starts with parity 0 like a file's first
+        if (d.records) {
+            int rc = il_drop_lines(ctx, s, 4u, 1u);
+            if (rc == VS_OK) rc = il_scan(ctx, s);
+            if (rc) return il_fail(ctx, s, rc, vs_last_error(ctx));
+            s->entry_pending = false;
+            s->remain--;
+            break;
+        }
+        if (d.eof) return il_fail(ctx, s, VS_E_STATE, s->rd.path + ": fewer records in its member range than were counted");
     }
-    if (d.err == VS_OK && d.flags && d.validated < d.w.size) {  // (text that arrived with this slot: host text mode)
-        if (translate_window(ctx, d, s->rd.path) == VS_OK)
-            if (int rc = il_scan(ctx, s)) return il_fail(ctx, s, rc, vs_last_error(ctx));
+    uint32_t n_rec = (uint32_t)d.records;
+    bool eof = d.eof;
+    if (s->ranged) {  // (the stream sees the range's records and no more: behind the last one the file may go on)
+        if (d.records >= s->remain) {
+            n_rec = (uint32_t)s->remain;
+            eof = !s->lookahead;  // (a look-ahead record is held back unless it completes this rank's last pair)
+            s->range_done = true;
+        } else if (d.eof) {
+            return il_fail(ctx, s, VS_E_STATE, s->rd.path + ": fewer records in its member range than were counted");
+        }
     }
-    if (d.err != VS_OK) return il_fail(ctx, s, s->rd.err != VS_OK ? s->rd.err : d.err, s->rd.err != VS_OK ? s->rd.err_msg : d.err_msg);
     if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return il_fail(ctx, s, rc, vs_last_error(ctx));
     vs_launch_sl_scatter(st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
-    if (int rc = il_classify_device(ctx, st, d.w.data(), d.ends.as<const uint32_t>(), (uint32_t)d.records, d.eof, s->mt, s->d_stat, s->h_stat))
+    if (int rc = il_classify_device(ctx, st, d.w.data(), d.ends.as<const uint32_t>(), n_rec, eof, s->mt, s->d_stat, s->h_stat))
         return il_fail(ctx, s, rc, vs_last_error(ctx));
     s->matched = true;
     if (!s->singles_ok && s->mt.first_single != IL_NONE) {
@@ -393,16 +484,14 @@ int il_next_window(vs_ctx *ctx, vs_fastq_il *s, bool *end) {
         if (int rc = il_emit_singles_device(ctx, st, s->mt, s->d_stat + IS_WORDS)) return il_fail(ctx, s, rc, vs_last_error(ctx));
     s->records += s->mt.decided;
     s->singles += s->mt.singles;
+    if (s->ranged) s->remain -= s->mt.decided;
     *end = false;
     return VS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vs_fastq_il_open(vs_ctx *ctx, const char *path, int mode, vs_fastq_il **out) {
-    if (!ctx || !path || !out || (mode != VS_IL_STRICT && mode != VS_IL_SINGLES && mode != VS_IL_KEEP)) return vs_fail(ctx, VS_E_ARG, "vs_fastq_il_open: bad argument");
+// the file opened and its reader started; range (may be NULL) = {first byte, one past the last byte, lines to skip}.  start =
+// false: no reader is started (a range without a record of this rank's)
+int il_open(vs_ctx *ctx, const char *path, int mode, const uint64_t *range, bool start, vs_fastq_il **out) {
     *out = nullptr;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     vs_fastq_il *s = new vs_fastq_il();
@@ -411,11 +500,25 @@ int vs_fastq_il_open(vs_ctx *ctx, const char *path, int mode, vs_fastq_il **out)
     s->keep = mode == VS_IL_KEEP;
     Reader &r = s->rd;
     if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
-    if (const char *ev = getenv("VS_GZIP_DEVICE")) r.gzip_device = strcmp(ev, "1") == 0;
+    if (const char *ev = getenv("VS_GZIP_DEVICE")) r.gzip_device = !range && strcmp(ev, "1") == 0;  // (a member range is BGZF's)
     if (const char *ev = getenv("VS_GZIP_TEXT")) s->df.w.gz.text_cap = (uint32_t)std::max<long long>(1, atoll(ev));  // (tests only, as VS_STREAM_CHUNK)
-    if (int rc = r.open_file(ctx, path)) {
+    int rc = r.open_file(ctx, path);
+    struct stat sb;
+    if (rc == VS_OK && range && (fstat(r.fd, &sb) != 0 || !S_ISREG(sb.st_mode) || range[0] > range[1] || range[1] > (uint64_t)sb.st_size))
+        rc = r.cannot_open(ctx, EINVAL);  // (a member range is a range of a regular file that holds it)
+    if (rc != VS_OK) {
         delete s;
         return rc;
+    }
+    if (range) {
+        s->ranged = true;
+        // (a short range -- the few members of a tail pass -- pins no slots of the full chunk size: deflate rarely packs text
+        // eightfold, and a slot holds at least one member whatever its size)
+        r.chunk = (size_t)std::min<uint64_t>(r.chunk, std::max<uint64_t>(1u << 20, 8u * (range[1] - range[0])));
+        r.begin = range[0];
+        r.end = range[1];
+        s->df.skip = range[2];
+        s->df.to_file_end = r.end == (uint64_t)sb.st_size;
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
     if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * IS_ALL);
@@ -428,8 +531,109 @@ int vs_fastq_il_open(vs_ctx *ctx, const char *path, int mode, vs_fastq_il **out)
         vs_fastq_il_close(s);
         return vs_fail(ctx, VS_E_HIP, "vs_fastq_il_open: %s", hipGetErrorString(e1));
     }
-    r.th = std::thread([rp = &s->rd] { rp->run(); });
+    if (start) r.th = std::thread([rp = &s->rd] { rp->run(); });
+    else s->done = true;
     *out = s;
+    return VS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vs_fastq_il_open(vs_ctx *ctx, const char *path, int mode, vs_fastq_il **out) {
+    if (!ctx || !path || !out || (mode != VS_IL_STRICT && mode != VS_IL_SINGLES && mode != VS_IL_KEEP)) return vs_fail(ctx, VS_E_ARG, "vs_fastq_il_open: bad argument");
+    return il_open(ctx, path, mode, nullptr, true, out);
+}
+
+int vs_fastq_il_open_range(vs_ctx *ctx, const char *path, int mode, const uint64_t range[3], uint64_t n_owned, int lookahead, uint32_t entry,
+                           uint64_t first_record, vs_fastq_il **out) {
+    if (!ctx || !path || !range || !out || (mode != VS_IL_STRICT && mode != VS_IL_SINGLES) || (lookahead != 0 && lookahead != 1) || entry > 1u ||
+        n_owned > (1ull << 60))
+        return vs_fail(ctx, VS_E_ARG, "vs_fastq_il_open_range: bad argument");
+    const bool any = n_owned > entry;  // (a share that is empty, or only the second of the previous rank's last pair: nothing is read)
+    if (int rc = il_open(ctx, path, mode, range, any, out)) return rc;
+    vs_fastq_il *s = *out;
+    s->lookahead = lookahead != 0;
+    s->entry_pending = any && entry != 0u;
+    s->remain = any ? n_owned + (uint64_t)lookahead : 0u;
+    s->df.first_record = first_record;
+    return VS_OK;
+}
+
+int vs_fastq_il_range_fn(vs_ctx *ctx, const char *path, const uint64_t range[3], uint64_t n_rec, uint32_t *fn, uint64_t info[4]) {
+    if (!ctx || !path || !range || !fn || !info || n_rec > (1ull << 60)) return vs_fail(ctx, VS_E_ARG, "vs_fastq_il_range_fn: bad argument");
+    *fn = IL_F_ID;
+    info[0] = info[1] = info[2] = info[3] = 0;
+    if (n_rec < 2u) return VS_OK;  // (no two records in a row: nothing to compose, nothing is read)
+    vs_fastq_il *s = nullptr;
+    if (int rc = il_open(ctx, path, VS_IL_SINGLES, range, true, &s)) return rc;
+    // the function so far between two sentinel words: d_acc[1], composed on the device window by window
+    const uint32_t SENTINEL = 0xA5C3F00Du, start[3] = {SENTINEL, IL_F_ID, SENTINEL};
+    uint32_t got[3] = {0, 0, 0};
+    VsDevBuf acc, m, wgfn;
+    DevFile &d = s->df;
+    hipStream_t st = s->st;
+    uint64_t seen = 0, windows = 0;  // records in front of the window; windows matched
+    auto done = [&](int rc) {
+        s->rd.shut();  // (the reader has stopped: its byte count stands)
+        info[0] = d.w.members;
+        info[1] = s->rd.raw_bytes;
+        info[2] = windows;
+        info[3] = seen;
+        vs_fastq_il_close(s);
+        return rc;
+    };
+    hipError_t e1 = acc.reserve(sizeof start);
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(acc.ptr(), start, sizeof start, hipMemcpyHostToDevice, st);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+    if (e1 != hipSuccess) return done(vs_fail(ctx, VS_E_HIP, "vs_fastq_il_range_fn: %s", hipGetErrorString(e1)));
+    for (;;) {
+        if (int rc = il_append(ctx, s)) return done(rc);
+        if (d.err != VS_OK) return done(vs_fail(ctx, s->rd.err != VS_OK ? s->rd.err : d.err, "%s", (s->rd.err != VS_OK ? s->rd.err_msg : d.err_msg).c_str()));
+        // records [seen, seen + n) of the range are whole in the window; the last of them only lends its header line to the
+        // m of the one before and leads the next window
+        const uint64_t n = std::min<uint64_t>(d.records, n_rec - seen);
+        if (n < 2u) {
+            if (d.eof) return done(vs_fail(ctx, VS_E_STATE, "%s: fewer records in its member range than were counted", path));
+            continue;  // (the window grows)
+        }
+        const uint32_t wgs = (uint32_t)((n + IL_TPB - 1u) / IL_TPB);
+        if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return done(rc);
+        if (int rc = reserve_n<uint8_t>(ctx, m, (size_t)n)) return done(rc);
+        if (int rc = reserve_n<uint32_t>(ctx, wgfn, wgs)) return done(rc);
+        vs_launch_sl_scatter(st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
+        hipLaunchKernelGGL(k_il_match, dim3(wgs), dim3(IL_TPB), 0, st, IlWin{d.w.data(), d.ends.as<const uint32_t>(), (uint32_t)n}, m.as<uint8_t>(),
+                           wgfn.as<uint32_t>());
+        hipLaunchKernelGGL(k_il_total, dim3(1), dim3(IL_CARRY_TPB), 0, st, m.as<const uint8_t>(), (uint32_t)(n - 1u), acc.as<uint32_t>() + 1);
+        if ((e1 = hipGetLastError()) != hipSuccess) return done(vs_fail(ctx, VS_E_HIP, "vs_fastq_il_range_fn: %s", hipGetErrorString(e1)));
+        windows++;
+        seen += n - 1u;
+        if (seen + 1u == n_rec) break;
+        uint32_t at = 0;  // one past the line end that closes record n - 2 of the window (the stream's own wait per window)
+        e1 = hipMemcpyAsync(&at, d.ends.as<uint32_t>() + (4u * (size_t)(n - 1u) - 1u), sizeof at, hipMemcpyDeviceToHost, st);
+        if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+        if (e1 != hipSuccess) return done(vs_fail(ctx, VS_E_HIP, "vs_fastq_il_range_fn: %s", hipGetErrorString(e1)));
+        if ((size_t)at + 1u > d.w.size) return done(vs_fail(ctx, VS_E_STATE, "%s: a line end beyond the window", path));
+        if (int rc = drop_front(ctx, st, d, (size_t)at + 1u, n - 1u)) return done(rc);
+    }
+    seen++;  // (the last record, whose header line was read)
+    e1 = hipMemcpyAsync(got, acc.ptr(), sizeof got, hipMemcpyDeviceToHost, st);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
+    if (e1 != hipSuccess) return done(vs_fail(ctx, VS_E_HIP, "vs_fastq_il_range_fn: %s", hipGetErrorString(e1)));
+    if (got[0] != SENTINEL || got[2] != SENTINEL || got[1] > 3u) return done(vs_fail(ctx, VS_E_STATE, "vs_fastq_il_range_fn: a kernel wrote outside the function word"));
+    *fn = got[1];
+    return done(VS_OK);
+}
+
+int vs_il_shard_plan(const uint32_t *fn, uint32_t world, uint32_t *entry) {
+    if (!fn || !entry || !world) return vs_fail(nullptr, VS_E_ARG, "vs_il_shard_plan: bad argument");
+    uint32_t e = 0;  // (the file's first record starts with parity 0)
+    for (uint32_t r = 0; r < world; r++) {
+        if (fn[r] > 3u) return vs_fail(nullptr, VS_E_ARG, "vs_il_shard_plan: the function of rank %u is none of the four", r);
+        entry[r] = e;
+        e = il_apply(fn[r], e);
+    }
     return VS_OK;
 }
 

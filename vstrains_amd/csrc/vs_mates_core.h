@@ -71,6 +71,12 @@ IL_HD uint32_t il_wave_fn(uint64_t b) {
     const uint32_t c = il_ones_below(b, 64u);
     return c < 64u ? ((c & 1u) ? (uint32_t)IL_F_CONST1 : (uint32_t)IL_F_CONST0) : (uint32_t)IL_F_ID;
 }
+// the same for the first n (1..64) of those records alone: a run of n true m flips n times
+IL_HD uint32_t il_run_fn(uint64_t b, uint32_t n) {
+    const uint32_t c = il_ones_below(b, n);
+    if (c < n) return (c & 1u) ? (uint32_t)IL_F_CONST1 : (uint32_t)IL_F_CONST0;
+    return (n & 1u) ? (uint32_t)IL_F_FLIP : (uint32_t)IL_F_ID;
+}
 
 // The records of one window: its text, the byte offsets of its line ends (n_nl of them), R complete records.  Header line
 // of record i = [start, end): it has a line end of its own whenever the record is complete.

@@ -374,7 +374,7 @@ class HipBackend:
 
     def __init__(self, device: int = 0, write_info_text: bool = True, ctx=None, sparse_info_text: bool = False,
                  bgzf_info_text: bool = False, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
-                 count_singles: bool = False):
+                 count_singles: bool = False, interleaved_shard: bool = False):
         from .. import pe as host
 
         self.ctx = ctx if ctx is not None else host.Context(device)  # raises NativeError without a HIP device
@@ -385,6 +385,7 @@ class HipBackend:
         self.bam_by_name = bam_by_name  # -fwd / -rve name ONE BAM in any record order: mates matched by name
         self.bam_info = None  # the by-name stream's info (singletons dropped, ...) after pe_links
         self.interleaved = interleaved  # "strict" / "singles": -fwd / -rve name ONE interleaved FASTQ, mates checked by name
+        self.interleaved_shard = interleaved_shard  # --interleaved-shard: under a process group the ranks share that file by member
         self.interleaved_info = None  # that stream's info (singles dropped, ...) after pe_links
         self.check_names = check_names  # "strict" / "singles": the two FASTQ files are paired by read name on the device
         self.pair_names_info = None  # that stream's info (singles dropped per file, ...) after pe_links
@@ -404,13 +405,13 @@ class HipBackend:
             self.pe_stats = pe_inference.run(gfa, aln_dir, fwd, rve, ksize, ctx=self.ctx, stages_follow=True,
                                               sparse_info=self.sparse_info_text, bgzf_info=self.bgzf_info_text, bam_by_name=self.bam_by_name,
                                               interleaved=self.interleaved, check_names=self.check_names, single=self.single,
-                                              count_singles=self.count_singles)
+                                              count_singles=self.count_singles, interleaved_shard=self.interleaved_shard)
             ids, counter = pe_inference.run.last
         else:
             os.makedirs(aln_dir, exist_ok=True)
             ids, counter = pe_inference.count_links(self.ctx, gfa, fwd, rve, ksize, stages_follow=True, bam_by_name=self.bam_by_name,
                                                     interleaved=self.interleaved, check_names=self.check_names, single=self.single,
-                                                    count_singles=self.count_singles)
+                                                    count_singles=self.count_singles, interleaved_shard=self.interleaved_shard)
         self.single_info = pe_inference.count_links.single_info
         self.bam_info = pe_inference.count_links.bam_info
         self.interleaved_info = pe_inference.count_links.interleaved_info

@@ -451,6 +451,173 @@ class InterleavedStream:
             raise nat.NativeError(rc, msg)
         self._h = h
 
+    # ---- the member-sharded open of one whole-BGZF interleaved file (one process per GPU) -----------------------------------
+    TAIL_RECORDS = 64  # the records at the end of a share whose mates the tail pass looks at first
+    FN_CONST0, FN_FLIP, FN_ID, FN_CONST1 = 0, 1, 2, 3  # a function of one bit: f(0) | f(1) << 1 (vs_mates_core.h)
+
+    @classmethod
+    def open_shard(cls, path: str, ctx: "Context", rank: int, world: int, all_gather=None, block_pairs: int = 1 << 20, singles=False):
+        """This rank's share of ONE whole-BGZF interleaved file, shared with the other ranks by MEMBER.  The T complete records
+        are cut as ``dist.shard_range`` cuts pairs; rank r owns the records [a_r, b_r), every pair whose FIRST record it owns
+        and every single it owns.  Whether a_r is the second record of a pair -- its entry parity -- is exact: pass 1
+        (``shard_count``) counts lines per member as ``FastqStream.shard_count`` does for one file; pass 2 (``shard_tail``)
+        composes, on the device, the parity function of the share from its tail (``vs_fastq_il_range_fn``); pass 3
+        (``shard_open``) chains the functions into every rank's entry (``vs_il_shard_plan``), opens the stream on the member
+        range of the share plus one look-ahead record (``vs_fastq_il_open_range``) and exchanges the status of that open.
+        Three exchanges through ``all_gather`` (as ``FastqStream.open_shard`` takes it), the same on every rank whatever
+        the data.  ``singles``: False (strict) or True; keep mode is not shared.
+
+        Returns ``(stream, None)``, or ``(None, reason)`` when the ranks -- all of them, from gathered values alone -- must
+        leave the file to one process: "not whole BGZF", "VS_BGZF_DEVICE=0", "a carriage return or a byte >= 0x80".  The
+        stream has ``first_record`` / ``records`` / ``total_records`` (where its share lies), ``entry``, ``members``,
+        ``members_pass1``, ``members_tail`` and ``plan`` (first member, lines skipped, one past the last member)."""
+        if all_gather is None:
+            import torch.distributed as dist
+
+            def all_gather(vals):
+                got = [None] * world
+                dist.all_gather_object(got, [int(v) for v in vals])
+                return got
+
+        mine = cls.shard_count(path, ctx, rank, world)
+        why = cls.shard_tail(mine, all_gather(mine.message))
+        if why is not None:
+            return None, why
+        return cls.shard_open(mine, all_gather(mine.tail_message), all_gather, block_pairs, singles)
+
+    class ShardCount:
+        """What the passes leave on a rank: ``message`` / ``tail_message`` for the exchanges, its own failure (raised after
+        the exchange that tells the peers), the members' file offsets, the members inflated per pass, and from ``shard_tail``
+        on the line counts of every member, T and the rank's records."""
+
+        def __init__(self, path, ctx, rank, world):
+            self.path, self.ctx, self.rank, self.world = path, ctx, rank, world
+            self.failure, self.offsets, self.state, self.members_pass1, self.members_tail = None, None, 2, 0, 0
+            self.message, self.tail_message = [1], [1, InterleavedStream.FN_ID]
+
+    @classmethod
+    def shard_count(cls, path: str, ctx: "Context", rank: int, world: int) -> "InterleavedStream.ShardCount":
+        """Pass 1 on this rank.  ``message`` = [failed, whole BGZF, members M, flags of my share (1: a ``\\r``, 2: a byte >=
+        0x80; 4: ``VS_BGZF_DEVICE=0``, nothing was counted), last byte of the last non-empty member of my share (256: none),
+        members in my share, their newline counts padded with zeros to ceil(M / world)]."""
+        path = os.fspath(path)
+        sc = cls.ShardCount(path, ctx, rank, world)
+        try:
+            sc.offsets, sc.state, _ = bgzf_walk_file(path)
+            host_zlib = os.environ.get("VS_BGZF_DEVICE") == "0"
+            m = len(sc.offsets) - 1
+            lo, hi = (m * rank) // world, (m * (rank + 1)) // world
+            counts, flags, last = [], 4 if host_zlib else 0, 256
+            if sc.state == 0 and not host_zlib and hi > lo:
+                counts, flags, last, sc.members_pass1, _ = bgzf_count_lines(path, sc.offsets[lo:hi + 1], ctx)
+            share = [int(x) for x in counts]
+            sc.message = [0, 1 if sc.state == 0 else 0, m, flags, last, len(share)] + share + [0] * (-(-m // world) - len(share))
+        except Exception as e:  # noqa: BLE001 (the peers hear of it through the message, then this rank raises it)
+            sc.failure = e
+            sc.message = [1]
+        return sc
+
+    @classmethod
+    def shard_tail(cls, mine: "InterleavedStream.ShardCount", everyone):
+        """Pass 2 on this rank from every rank's pass-1 message: the reason when the ranks leave the file to one process,
+        else None with ``mine.tail_message`` = [failed, the parity function of my share].  A rank in front of the last one with
+        a share of its own composes the m of its last ``TAIL_RECORDS`` records (the look-ahead record behind them lends its
+        header line); a constant function is the share's whatever lies in front, identity or flip says that every record
+        of the window is its successor's mate, and the window is widened 16-fold until it is constant or holds the share."""
+        from .dist import shard_range
+
+        rank, world, ctx = mine.rank, mine.world, mine.ctx
+        if mine.failure is not None:
+            raise mine.failure
+        failed = [r for r, vals in enumerate(everyone) if vals[0]]
+        if failed:
+            raise RuntimeError("FASTQ open failed on rank(s) %s" % failed)
+        # (all that follows up to the tail pass is a function of `everyone`: no rank can take another branch)
+        heads = {(vals[1], vals[2]) for vals in everyone}
+        if len(heads) != 1:
+            raise RuntimeError("the ranks do not see the same file %s: (whole BGZF, members) = %s" % (mine.path, sorted(heads)))
+        (whole, members), = heads
+        flags, last_byte, counts = 0, 256, []
+        for vals in everyone:
+            flags |= vals[3]
+            if vals[4] != 256:
+                last_byte = vals[4]
+            counts += vals[6: 6 + vals[5]]
+        if not whole:
+            return "not whole BGZF"
+        if flags & 4:
+            return "VS_BGZF_DEVICE=0"
+        if flags & 3:
+            return "a carriage return or a byte >= 0x80"
+        if len(counts) != members:
+            raise RuntimeError("the ranks' shares do not add up to the members of %s" % mine.path)
+        mine.counts = np.asarray(counts, dtype=np.uint32)
+        mine.open_end = last_byte not in (256, 10)
+        mine.members = members
+        mine.total = (int(mine.counts.sum(dtype=np.uint64)) + (1 if mine.open_end else 0)) // 4
+        a, b = mine.span = shard_range(mine.total, rank, world)
+        fn = cls.FN_ID  # (the last rank, an empty share, a share that ends with the file: nobody's entry follows from it)
+        try:
+            reach = cls.TAIL_RECORDS
+            while rank < world - 1 and a < b < mine.total:
+                lo = max(a, b - reach)
+                fn, info = cls._range_fn(mine, lo, b + 1)
+                mine.members_tail += info[0]
+                if fn in (cls.FN_CONST0, cls.FN_CONST1) or lo == a:
+                    break
+                reach *= 16
+            mine.tail_message = [0, fn]
+        except Exception as e:  # noqa: BLE001 (as in pass 1)
+            mine.failure = e
+            mine.tail_message = [1, cls.FN_ID]
+        return None
+
+    @staticmethod
+    def _range_fn(mine, first: int, last: int):
+        """``vs_fastq_il_range_fn`` on the members that hold the records [first, last): (the composition of m[first .. last -
+        2], (members inflated, file bytes read, windows, records seen))."""
+        a, skip, e = bgzf_shard_plan(mine.counts, mine.open_end, first, last)
+        return il_range_fn(mine.path, (mine.offsets[a], mine.offsets[e]), skip, last - first, mine.ctx)
+
+    @classmethod
+    def shard_open(cls, mine: "InterleavedStream.ShardCount", everyone, all_gather, block_pairs: int = 1 << 20, singles=False):
+        """Pass 3 on this rank from every rank's tail message; see ``open_shard`` for what comes back."""
+        rank, world, ctx = mine.rank, mine.world, mine.ctx
+        if singles not in (False, True):
+            raise ValueError("a shared interleaved file drops its single records (True) or refuses them (False); singles=%r is one "
+                             "process's" % (singles,))
+        if mine.failure is not None:
+            raise mine.failure
+        failed = [r for r, vals in enumerate(everyone) if vals[0]]
+        if failed:
+            raise RuntimeError("FASTQ open failed on rank(s) %s" % failed)
+        entries = il_shard_plan([vals[1] for vals in everyone])
+        (a, b), entry = mine.span, entries[rank]
+        lookahead = 1 if b < mine.total else 0
+        plan = (0, 0, 0)
+        if b - a > entry:  # (else nothing of the share is this rank's to decide: nothing is read)
+            plan = bgzf_shard_plan(mine.counts, mine.open_end, a, min(b + 1, mine.total))
+        rng = (C.c_uint64 * 3)(int(mine.offsets[plan[0]]), int(mine.offsets[plan[2]]), plan[1])
+        self = cls.__new__(cls)
+        self._ctx, self._h, self.block_pairs, self.keep, self.singles = ctx, None, block_pairs, False, bool(singles)
+        h = C.c_void_p()
+        rc = nat.lib().vs_fastq_il_open_range(ctx._h, mine.path.encode(), 1 if singles else 0, rng, b - a, lookahead, entry, a, C.byref(h))
+        err = None
+        if rc != nat.VS_OK:
+            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+            err = FileNotFoundError(msg) if "cannot open" in msg else nat.NativeError(rc, msg)
+        status = all_gather([0 if err is None else 1])
+        if err is not None:
+            raise err
+        failed = [r for r, vals in enumerate(status) if vals[0]]
+        if failed:
+            nat.lib().vs_fastq_il_close(h)
+            raise RuntimeError("FASTQ open failed on rank(s) %s" % failed)
+        self._h = h
+        self.first_record, self.records, self.total_records, self.entry = a, b - a, mine.total, entry
+        self.members, self.members_pass1, self.members_tail, self.plan = mine.members, mine.members_pass1, mine.members_tail, plan
+        return self, None
+
     @property
     def info(self):
         a = (C.c_uint64 * 6)()
@@ -1085,6 +1252,29 @@ def bgzf_shard_plan(counts, no_final_newline: bool, first: int, last: int):
     if rc != nat.VS_OK:
         raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
     return int(plan[0]), int(plan[1]), int(plan[2])
+
+
+def il_shard_plan(fns):
+    """``vs_il_shard_plan`` (a pure function of the host): from the parity function of every rank's share of an interleaved
+    file (two bits each: const-0 = 0, flip = 1, identity = 2, const-1 = 3), the parity with which every rank's first record
+    starts: 0 for rank 0, ``fns[r]`` applied to rank r's for rank r + 1."""
+    f = np.ascontiguousarray(fns, dtype=np.uint32)
+    entry = np.zeros(max(f.size, 1), dtype=np.uint32)
+    rc = nat.lib().vs_il_shard_plan(f.ctypes.data if f.size else None, f.size, entry.ctypes.data)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, nat.lib().vs_last_error(None).decode("utf-8", "replace"))
+    return [int(x) for x in entry[: f.size]]
+
+
+def il_range_fn(path: str, offsets, skip: int, n_rec: int, ctx: "Context"):
+    """``vs_fastq_il_range_fn`` on the bytes [offsets[0], offsets[1]) of a BGZF file behind ``skip`` lines: (the composition of
+    m[0 .. n_rec - 2], (members inflated, file bytes read, windows, records seen))."""
+    rng = (C.c_uint64 * 3)(int(offsets[0]), int(offsets[1]), skip)
+    fn, info = C.c_uint32(0), (C.c_uint64 * 4)()
+    rc = nat.lib().vs_fastq_il_range_fn(ctx._h, os.fspath(path).encode(), rng, n_rec, C.byref(fn), info)
+    if rc != nat.VS_OK:
+        FastqPair._raise(ctx._h, rc)
+    return int(fn.value), tuple(int(x) for x in info)
 
 
 def inflate_host(payload: bytes, isize: int, crc: int):

@@ -28,7 +28,7 @@ def _rank_world():
 
 
 def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow: bool = False, bam_by_name: bool = False, interleaved=None,
-                check_names=None, single=(), count_singles: bool = False):
+                check_names=None, single=(), count_singles: bool = False, interleaved_shard: bool = False):
     """Index the nodes of ``gfa`` and count every pair of the two FASTQ files; the counters stay
     on the device.  Returns ``(node ids in file order, PeCounter)``.  ``stages_follow``: the graph stages will build their
     PE-link table from these counters in this process (the pipeline; not the stand-alone script, which writes the two text
@@ -37,7 +37,10 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     stream's ``info`` (``singletons`` among it), else None.  ``interleaved`` (None, ``"strict"`` or ``"singles"``): the inputs
     are ONE interleaved FASTQ, each pair's two records one behind the other, the mates checked by name on the device
     (``InterleavedStream``; ``"singles"`` drops and counts the records without a mate, ``"strict"`` refuses the first);
-    ``count_links.interleaved_info`` is then the stream's ``info``, else None.  ``check_names`` (None, ``"strict"`` or
+    ``count_links.interleaved_info`` is then the stream's ``info``, else None.  ``interleaved_shard``: under a process group
+    the ranks share that file by member (``InterleavedStream.open_shard``), each counting the pairs whose first record lies
+    in its share of the records; ``interleaved_info`` then holds the ranks' SUMS of ``pairs``, ``singles`` and ``records`` on
+    every rank.  ``check_names`` (None, ``"strict"`` or
     ``"singles"``): the two FASTQ files are paired by read name on the device (``PairedNameStream``, whatever ``use_stream``
     says; ``"strict"`` refuses the first pair that is no pair of mates, ``"singles"`` joins the files by name and drops and
     counts the records without a mate); ``count_links.pair_names_info`` is then the stream's ``info``, else None.
@@ -58,7 +61,7 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     single = unpaired_input(single, count_singles, world, interleaved, check_names=check_names, bam_by_name=bam_by_name, fwd=fwd,
                             rve=rve)  # (what the flags cannot apply to is a ValueError)
     by_names = check_names_input(fwd, rve, world, check_names, bam_by_name=bam_by_name, interleaved=interleaved)  # (False without the flag)
-    il_path = interleaved_input(fwd, rve, world, interleaved)  # (None without the flag; what it cannot apply to is a ValueError)
+    il_path = interleaved_input(fwd, rve, world, interleaved, shard=interleaved_shard)  # (None without the flag; what it cannot apply to is a ValueError)
     why = gzip_device_refusal(world)  # (reads the environment only; None with the switch unset)
     if why is not None:
         raise ValueError(why)
@@ -76,7 +79,10 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     # counters are summed over ranks afterwards (RCCL all-reduce); a single process takes everything
     if rank == 0 and stages_follow:
         counter.reserve_link_table()  # (the graph stages run on this rank: their table's buffer is taken now)
-    if il_path:
+    if il_path and world > 1:
+        count_interleaved_shard(ctx, il_path, counter, rank, world, interleaved == "singles")
+        fq = None
+    elif il_path:
         fq = host.InterleavedStream(il_path, ctx, block_pairs=BATCH_PAIRS,
                                     singles="keep" if count_singles else (interleaved == "singles"))  # one file, opened once
         try:
@@ -185,6 +191,58 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     if world > 1:
         counter.all_reduce()  # (every rank ends with the full sums; only rank 0 writes the files and runs the stages)
     return ids, counter
+
+
+def count_interleaved_shard(ctx, il_path: str, counter, rank: int, world: int, singles: bool, all_gather=None):
+    """One interleaved FASTQ shared among the ranks by member (``--interleaved --interleaved-shard`` under a process group):
+    this rank's share through ``counter``.  When the ranks cannot share the file (``open_shard`` says why: the same on every
+    rank) rank 0 reads it whole as the single process does, in its words, and the others only join the sum.  After a rank's
+    stream has ended or failed every rank joins one exchange of [status, the first single's file-wide record or -1, pairs,
+    singles, records]: if any rank failed every rank raises, before any collective of the counters.  The entries are exact,
+    so in the strict mode every rank's first single is a single of the whole file, and the rank with the smallest record
+    raises the single process's own message; the others name that rank.  On success ``count_links.interleaved_info`` holds
+    the sums on every rank, and rank 0 prints the progress lines of its own pairs."""
+    if all_gather is None:
+        import torch.distributed as dist
+
+        def all_gather(vals):
+            got = [None] * world
+            dist.all_gather_object(got, [int(v) for v in vals])
+            return got
+
+    fq, why = host.InterleavedStream.open_shard(il_path, ctx, rank, world, all_gather=all_gather, block_pairs=BATCH_PAIRS, singles=singles)
+    if fq is None and rank == 0:
+        fq = host.InterleavedStream(il_path, ctx, block_pairs=BATCH_PAIRS, singles=singles)
+    err, first_single = None, -1
+    info = dict(pairs=0, singles=0, records=0)
+    if fq is not None:
+        try:
+            count_stream(ctx, fq, counter)
+        except Exception as e:  # noqa: BLE001 (the peers hear of it through the exchange, then this rank raises)
+            err = e
+            head = il_path + ": record "
+            if isinstance(e, ValueError) and str(e).startswith(head) and "has no mate beside it" in str(e):
+                first_single = int(str(e)[len(head):].split(" ", 1)[0])
+        info = fq.info
+        fq.close()
+    status = all_gather([0 if err is None else 2 if first_single >= 0 else 1, first_single, info["pairs"], info["singles"], info["records"]])
+    lone = sorted((vals[1], r) for r, vals in enumerate(status) if vals[0] == 2)
+    if err is not None and (first_single < 0 or lone[0][1] == rank):
+        raise err
+    if lone:
+        raise RuntimeError("%s: rank %d found record %d without its mate beside it" % (il_path, lone[0][1], lone[0][0]))
+    failed = [r for r, vals in enumerate(status) if vals[0]]
+    if failed:
+        raise RuntimeError("interleaved FASTQ ingest failed on rank(s) %s" % failed)
+    if why is None:
+        ingest_report(rank, world, "il_members", None, fq.first_record, info["pairs"], [fq.members], (fq.members_pass1,), (fq.plan[2] - fq.plan[0],),
+                      first_record=fq.first_record, records=fq.records, total_records=fq.total_records, entry=fq.entry, members_tail=fq.members_tail)
+    else:
+        ingest_report(rank, world, "il_whole_file_rank0", why, 0, info["pairs"], None, (0,), (0,))
+    if rank == 0:
+        for mark in range(0, info["pairs"], 100000):
+            print("Number of processed reads: ", mark)
+    count_links.interleaved_info = dict(info, pairs=sum(v[2] for v in status), singles=sum(v[3] for v in status), records=sum(v[4] for v in status))
 
 
 def _single_tally(path: str, counter, before):
@@ -304,19 +362,24 @@ def bam_input(fwd: str, rve: str, world: int = 1, by_name: bool = False, sharded
     return fwd
 
 
-def interleaved_mode(interleaved: bool, singles: bool):
-    """The two flags of the commands as ``count_links`` takes them: None, ``"strict"`` or ``"singles"``."""
+def interleaved_mode(interleaved: bool, singles: bool, shard: bool = False):
+    """The flags of the commands as ``count_links`` takes them: None, ``"strict"`` or ``"singles"`` (``shard``,
+    ``--interleaved-shard``, is only checked here: it goes on as it is)."""
+    if shard and not interleaved:
+        raise ValueError("--interleaved-shard says that the ranks of a process group share an interleaved FASTQ by member and needs "
+                         "--interleaved, which says that -f and -r name one")
     if singles and not interleaved:
         raise ValueError("--interleaved-singles says what to do with the single records of an interleaved FASTQ and needs "
                          "--interleaved, which says that -f and -r name one")
     return ("singles" if singles else "strict") if interleaved else None
 
 
-def interleaved_input(fwd: str, rve: str, world: int = 1, interleaved=None):
+def interleaved_input(fwd: str, rve: str, world: int = 1, interleaved=None, shard: bool = False):
     """The path when ``interleaved`` (``--interleaved``) asks for ONE interleaved FASTQ and ``-f`` and ``-r`` name it (the same
     string -- ``/dev/stdin`` twice, a FIFO -- or the same file), None without the flag.  ``ValueError`` for what the flag
     cannot apply to, before a device is opened: two different files, a BAM, ``VS_FASTQ_STREAM=0``, a process group of more
-    than one rank."""
+    than one rank -- unless ``shard`` (``--interleaved-shard``) says that the ranks share the file by member
+    (``InterleavedStream.open_shard``), which a regular file allows and a pipe does not."""
     if interleaved is None:
         return None
     if interleaved not in ("strict", "singles"):
@@ -336,6 +399,11 @@ def interleaved_input(fwd: str, rve: str, world: int = 1, interleaved=None):
     if os.environ.get("VS_FASTQ_STREAM") == "0":
         raise ValueError("--interleaved reads its file in the streamed ingest, and VS_FASTQ_STREAM=0 asks for the mapped open of two "
                          "files: set one of the two")
+    if world > 1 and shard:
+        if not _regular(fwd):  # (a pipe keeps the refusal count_links has for it, said here before a device is opened)
+            raise ValueError("the FASTQ inputs %s / %s are not both regular files: a pipe can be read by one process only, so "
+                             "the sharded (torchrun) run cannot take it; run one process, or write the reads to files" % (fwd, rve))
+        return fwd
     if world > 1:
         raise ValueError("%s: --interleaved reads the file in one process only; sharing an interleaved file among the %d ranks of this "
                          "process group is not built: run without torchrun -- what the ranks share by member are BGZF pairs (two "
@@ -392,9 +460,9 @@ def member_shard_refusal(fwd: str, rve: str):
     return None
 
 
-def ingest_report(rank, world, path, reason, first_pair, pairs, members, members_pass1, members_pass2):
+def ingest_report(rank, world, path, reason, first_pair, pairs, members, members_pass1, members_pass2, **more):
     """Which ingest a rank of a sharded run took, for whoever asks with ``VS_INGEST_REPORT=DIR`` (stdout stays the
-    reference's): ``DIR/ingest_rank<r>.json``."""
+    reference's): ``DIR/ingest_rank<r>.json``.  ``more``: further integers of that ingest, under their names."""
     d = os.environ.get("VS_INGEST_REPORT")
     if not d:
         return
@@ -404,7 +472,8 @@ def ingest_report(rank, world, path, reason, first_pair, pairs, members, members
     with open(os.path.join(d, "ingest_rank%d.json" % rank), "w") as fh:
         json.dump(dict(rank=rank, world=world, path=path, reason=reason, first_pair=int(first_pair), pairs=int(pairs),
                        members=None if members is None else [int(x) for x in members],
-                       members_pass1=[int(x) for x in members_pass1], members_pass2=[int(x) for x in members_pass2]), fh)
+                       members_pass1=[int(x) for x in members_pass1], members_pass2=[int(x) for x in members_pass2],
+                       **{k: int(v) for k, v in more.items()}), fh)
 
 
 def _starts_gzip(path: str) -> bool:
@@ -522,7 +591,7 @@ def write_info_files(out_dir: str, ids, counter, sparse: bool = False, bgzf: boo
 
 def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int = 0, ctx=None, stages_follow: bool = False,
         sparse_info: bool = False, bgzf_info: bool = False, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
-        count_singles: bool = False):
+        count_singles: bool = False, interleaved_shard: bool = False):
     # PE_Inference.py:93-96: the output directory is wiped and recreated
     if out_dir[-1] == "/":
         out_dir = out_dir[:-1]
@@ -538,13 +607,13 @@ def run(gfa: str, out_dir: str, fwd: str, rve: str, kmer_size: int, device: int 
     glb_start = time.time()
     if bam_by_name:
         bam_input(fwd, rve, world, by_name=True)  # (what the flag cannot apply to is said before a device is opened)
-    interleaved_input(fwd, rve, world, interleaved)  # (the same)
+    interleaved_input(fwd, rve, world, interleaved, shard=interleaved_shard)  # (the same)
     check_names_input(fwd, rve, world, check_names, bam_by_name=bam_by_name, interleaved=interleaved)  # (the same)
     unpaired_input(single, count_singles, world, interleaved, check_names=check_names, bam_by_name=bam_by_name, fwd=fwd, rve=rve)  # (the same)
     if ctx is None:
         ctx = host.Context(device)
     ids, counter = count_links(ctx, gfa, fwd, rve, kmer_size, stages_follow=stages_follow, bam_by_name=bam_by_name, interleaved=interleaved,
-                               check_names=check_names, single=single, count_singles=count_singles)
+                               check_names=check_names, single=single, count_singles=count_singles, interleaved_shard=interleaved_shard)
     run.last = (ids, counter)
     if rank != 0:
         return None  # the counters were reduced to rank 0, which writes the files
@@ -587,6 +656,10 @@ def main(argv=None):
     parser.add_argument("--interleaved-singles", dest="interleaved_singles", action="store_true", default=False,
                         help="extension: with --interleaved, records without their mate beside them (the single reads `samtools "
                              "fastq x.bam` writes among the pairs) are dropped and counted instead")
+    parser.add_argument("--interleaved-shard", dest="interleaved_shard", action="store_true", default=False,
+                        help="extension, off by default: with --interleaved under torchrun, the ranks share ONE whole-BGZF interleaved "
+                             "file (`... | bgzip`) by member, each counting the pairs whose first record lies in its share; any other "
+                             "regular file is read whole by rank 0 (without the flag --interleaved is one process's)")
     parser.add_argument("--check-names", dest="check_names", action="store_true", default=False,
                         help="extension: pair the two FASTQ files by read name on the device instead of by position: record i of -f and "
                              "record i of -r must be mates by name (as `bwa mem` demands), and the first pair that is not stops the run "
@@ -602,12 +675,12 @@ def main(argv=None):
                         help="extension: with --interleaved --interleaved-singles, with --check-names --check-names-singles or with "
                              "--bam-by-name, the records without a mate are counted into st_info as unpaired reads instead of dropped")
     args = parser.parse_args(argv)
-    interleaved = interleaved_mode(args.interleaved, args.interleaved_singles)
+    interleaved = interleaved_mode(args.interleaved, args.interleaved_singles, args.interleaved_shard)
     check_names = check_names_mode(args.check_names, args.check_names_singles)
     if args.gzip_device:
         os.environ["VS_GZIP_DEVICE"] = "1"  # (the library reads the switch where it reads VS_BGZF_DEVICE)
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    interleaved_input(args.fwd, args.rve, world, interleaved)  # (refused before a device is opened or a process group made)
+    interleaved_input(args.fwd, args.rve, world, interleaved, shard=args.interleaved_shard)  # (refused before a device is opened or a process group made)
     check_names_input(args.fwd, args.rve, world, check_names, bam_by_name=args.bam_by_name, interleaved=interleaved)  # (the same)
     unpaired_input(args.single, args.count_singles, world, interleaved, check_names=check_names, bam_by_name=args.bam_by_name, fwd=args.fwd,
                    rve=args.rve)  # (the same)
@@ -631,7 +704,8 @@ def main(argv=None):
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
         os.environ.setdefault("VS_HOST_THREADS", str(max(1, (os.cpu_count() or 1) // max(local_world, 1))))
     run(args.gfa, args.dir, args.fwd, args.rve, args.kmer_size, args.device, sparse_info=args.sparse_info, bgzf_info=args.bgzf_info,
-        bam_by_name=args.bam_by_name, interleaved=interleaved, check_names=check_names, single=args.single, count_singles=args.count_singles)
+        bam_by_name=args.bam_by_name, interleaved=interleaved, check_names=check_names, single=args.single, count_singles=args.count_singles,
+        interleaved_shard=args.interleaved_shard)
     if world > 1:
         import torch.distributed as dist
 
