@@ -750,6 +750,22 @@ int vs_pe_count_lists(vs_ctx *ctx, uint32_t n_nodes, uint64_t n_pairs, const uin
                       uint32_t *d_node_mat, uint32_t *d_short_mat, uint8_t *d_tile_map);
 uint32_t vs_pe_lists_ept(vs_ctx *ctx);
 int vs_pe_last_order(vs_ctx *ctx, uint32_t *keys, uint32_t *perm, uint64_t cap, uint64_t info[2]);
+/* Testing aid (addition to ABI 11 without a new number, like vs_pe_last_order): the hand-off between the mapping kernel and
+ * the counter kernels exactly as k_pe_tiles left it in the context's scratch at the most recent vs_pe_count /
+ * vs_pe_count_tracked, copied to HOST memory.  Launches nothing and changes nothing; synchronises the stream.
+ *   info[0] = 1 if that call made a hand-off, 0 if not (vs_pe_map_ends, vs_pe_count_lists, an empty block, no call yet):
+ *             every other word is 0 then and nothing is copied
+ *   info[1] = pairs of the call, info[2] = read ends per tile, info[3] = end slots (tiles * ends per tile)
+ *   info[4] = layout: 0 packed (counts = n | quad offset inside the tile's region << 8), 1 rows (counts = n)
+ *   info[5], info[6] = slots of the tile's (end, node) table and list trim of the k_pe_tiles instantiation that ran: a
+ *             tile's packed lists take at most (ends per tile * 16 - trim) / 4 quads
+ *   info[7] = pairs on the first overflow list (what k_pe_tiles sent on, not what k_pe_mid then left for k_pe_slow)
+ *   info[8] = words of the list buffer in that layout
+ *   lists[info[8]], counts[info[3]], overflow[info[7]]: at most cap_* words of each are written; any may be NULL.  The end
+ *   slots of the last tile past 2 * pairs are not the mapping kernel's: the host zeroes their counts before the counter
+ *   kernels run.  In the row layout only the quads that hold nodes are written by the kernel. */
+int vs_pe_last_handoff(vs_ctx *ctx, uint32_t *lists, uint64_t cap_words, uint32_t *counts, uint64_t cap_ends, uint32_t *overflow,
+                       uint64_t cap_overflow, uint64_t info[9]);
 
 /* Testing aid (ABI 11): the two exclusive scans under the index build, the locus sort, every row_ptr and every member,
  * record and word offset, run alone on values the caller made up, launched exactly as their callers launch them (no kernel

@@ -4,6 +4,14 @@
 
 enum { N_IN = 30, N_OUT = 40, MSG = 128 };
 
+// Table slots and list trim of the k_pe_tiles instantiation <mode, sw, sp, ad> (vs_std_table); `pool` = the plan's run-time pool,
+// which the instantiations without a compile-time shape (sw = 0) take.  out[0] = slots, out[1] = trim.
+extern "C" void vs_std_table_check(int mode, uint32_t sw, int ad, uint32_t pool, uint32_t *out) {
+    const StdTable t = sw ? vs_std_table(mode, true, ad != 0) : StdTable{pool, 0u};
+    out[0] = t.pool;
+    out[1] = t.trim;
+}
+
 // in: n rows of N_IN values, out: n rows of N_OUT, msgs: n texts of MSG bytes.  Returns N_OUT.
 extern "C" int vs_pe_plan_check(uint64_t n, const int64_t *in, uint64_t *out, char *msgs) {
     for (uint64_t i = 0; i < n; i++, in += N_IN, out += N_OUT, msgs += MSG) {

@@ -211,8 +211,8 @@ def _dense_case(k, n_pairs, read_len, seed, snp, n_strains=6, glen=1500, sub=0.0
 @pytest.mark.parametrize("no_mid", ["0", "1"])
 def test_overflow_pairs_take_slow_path_and_stay_exact(host, xctx, no_mid, monkeypatch):
     ctx = xctx  # (the switches below exist only on a context made in experiment mode)
-    # dense variation at k=11: a 100-base read is accepted by more than 16 short nodes in ~30 % of
-    # the ends, which overflows the per-end list kept in LDS: those pairs go to k_pe_mid (one wavefront per
+    # dense variation at k=11: a 100-base read is accepted by more than LCAP = 20 short nodes in a good part of
+    # the ends, more than an end may list on the main path: those pairs go to k_pe_mid (one wavefront per
     # pair, state in LDS), or with VS_NO_MID=1 straight to the general kernel k_pe_slow
     monkeypatch.setenv("VS_NO_MID", no_mid)
     g, f, r = _dense_case(11, 1500, 100, seed=301, snp=0.2)
@@ -294,7 +294,7 @@ def test_tracked_counting_marks_every_touched_tile_and_zeroes_only_those(host, c
 
 @pytest.mark.parametrize("case", ["dense_k11", "chain_k20"])
 def test_row_owners_next_to_the_overflow_kernels(host, xctx, case, monkeypatch):
-    """Row owners (VS_ACC_ROWS=1) on blocks where a third of the ends are accepted by more than 16 nodes: those pairs have
+    """Row owners (VS_ACC_ROWS=1) on blocks where many ends are accepted by more than LCAP = 20 nodes: those pairs have
     empty list rows and are counted by k_pe_mid / k_pe_slow, the rest by the row owners, into the same counters.  Against the
     C oracle."""
     from vstrains_amd import synth
@@ -310,7 +310,7 @@ def test_row_owners_next_to_the_overflow_kernels(host, xctx, case, monkeypatch):
         seqs = [genome[i: i + k + 1] for i in range(len(genome) - k)]
         f, r = [], []
         for i in range(900):
-            L = (120, 50, 62, 37, 30)[i % 5]  # 100 nodes (beyond k_pe_mid), 30, 42, 17 and 10 (a list row holds 16)
+            L = (120, 50, 62, 37, 30)[i % 5]  # 100 nodes (beyond k_pe_mid), 30, 42, 17 and 10 (an end lists LCAP = 20 at most: 17 has one node in the second array)
             a = int(rng.integers(0, len(genome) - 300))
             f.append(genome[a: a + L])
             r.append(synth.revcomp(genome[a + 150: a + 150 + (L if i % 3 else 25)]))
@@ -325,7 +325,7 @@ def test_row_owners_next_to_the_overflow_kernels(host, xctx, case, monkeypatch):
 
 def test_ends_with_a_hundred_nodes_pass_through_both_overflow_kernels(host, ctx):
     """A chain of nodes that advance ONE base each (every node k + 1 bases long): a 120-base read is accepted by 100 nodes
-    -- beyond a list row (16) and beyond k_pe_mid's per-end list (64), so the pairs end in the general kernel; shorter reads
+    -- beyond what an end may list (LCAP = 20) and beyond k_pe_mid's per-end list (64), so the pairs end in the general kernel; shorter reads
     of the same block (50 bases: 30 nodes) stop at k_pe_mid; reads with many dirty bytes take the mask path in either."""
     rng = np.random.default_rng(17)
     k = 20

@@ -158,6 +158,9 @@ struct vs_ctx {
     const char *last_kernel = "";  // mapping-kernel instantiation of the last vs_pe_count
     uint32_t last_launched = 0;    // VS_RAN_* bits: which optional kernels that call launched
     uint64_t last_order_pairs = 0; // pairs of that call (vs_pe_last_order: d_locus_keys / d_perm hold their order if a sort ran)
+    // the hand-off of that call, if it made one (vs_pe_last_handoff: d_lists / d_list_counts / d_slow_list hold it): pairs (0 = none),
+    // end slots, ends per tile, layout, table slots and list trim of the k_pe_tiles instantiation that ran
+    struct LastHandoff { uint64_t pairs = 0, list_ends = 0; uint32_t ept = 0, rows = 0, pool = 0, trim = 0; } last_handoff;
     int n_cu = 256;
 };
 

@@ -2607,6 +2607,7 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     ctx->last_ms[0] = ctx->last_ms[1] = ctx->last_ms[2] = 0;
     ctx->last_launched = 0;
     ctx->last_order_pairs = 0;
+    ctx->last_handoff = {};
     // test hooks: fixed defaults unless the process runs with VS_EXPERIMENT=1 (see VsTuning)
     if (ctx->experiment) vs_tuning_load(ctx->tune, true);
     PePlanIn in;
@@ -2742,6 +2743,13 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
         VS_HIP(ctx, hipLaunchKernel(tf->fn, dim3((unsigned)pl.grid), dim3(TTPB), kargs, lds, st));
     }
     if (d_node_mat) {
+        const StdTable tab = pl.sw ? vs_std_table((int)pl.mode, true, pl.ad != 0u) : StdTable{pl.pool, 0u};  // (as k_pe_tiles takes them)
+        ctx->last_handoff.pairs = n_pairs;
+        ctx->last_handoff.list_ends = pl.list_ends;
+        ctx->last_handoff.ept = pl.ept;
+        ctx->last_handoff.rows = pl.use_rows;
+        ctx->last_handoff.pool = tab.pool;
+        ctx->last_handoff.trim = tab.trim;
         const int rc = pe_count_from_lists(ctx, pl, idx.n_nodes, 2ull * n_pairs, d_node_mat, d_short_mat, d_tile_map);
         if (rc) return rc;
     }
@@ -2810,6 +2818,7 @@ extern "C" int vs_pe_count_lists(vs_ctx *ctx, uint32_t n_nodes, uint64_t n_pairs
     ctx->last_ms[0] = ctx->last_ms[1] = ctx->last_ms[2] = 0;
     ctx->last_launched = 0;
     ctx->last_order_pairs = 0;
+    ctx->last_handoff = {};  // (the lists here are the host's: nothing a mapping kernel left)
     ctx->last_kernel = "";
     const PePlan pl = pe_lists_plan(ctx, n_nodes, 2u * n_pairs, d_tile_map != nullptr);
     if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "%s", pl.msg);
@@ -2855,6 +2864,28 @@ extern "C" int vs_pe_last_order(vs_ctx *ctx, uint32_t *keys, uint32_t *perm, uin
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (keys) VS_HIP(ctx, hipMemcpy(keys, ctx->d_locus_keys.ptr(), sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
     if (perm) VS_HIP(ctx, hipMemcpy(perm, ctx->d_perm.ptr(), sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    return VS_OK;
+}
+
+extern "C" int vs_pe_last_handoff(vs_ctx *ctx, uint32_t *lists, uint64_t cap_words, uint32_t *counts, uint64_t cap_ends, uint32_t *overflow,
+                                  uint64_t cap_overflow, uint64_t info[9]) {
+    if (!ctx || !info) return VS_E_ARG;
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const vs_ctx::LastHandoff &h = ctx->last_handoff;
+    for (int i = 0; i < 9; i++) info[i] = 0;
+    if (!h.pairs) return VS_OK;  // no hand-off: vs_pe_map_ends, an empty block, vs_pe_count_lists, a call that failed before its launch
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t n_over = 0;  // (word SC_MID: k_pe_tiles counts into it, k_pe_mid only reads it and counts its own list in SC_SLOW)
+    VS_HIP(ctx, hipMemcpy(&n_over, ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_MID, sizeof n_over, hipMemcpyDeviceToHost));
+    const uint64_t words = vs_pe_pack_words(h.list_ends, h.rows != 0u);
+    info[0] = 1; info[1] = h.pairs; info[2] = h.ept; info[3] = h.list_ends; info[4] = h.rows;
+    info[5] = h.pool; info[6] = h.trim; info[7] = n_over; info[8] = words;
+    const uint64_t over = n_over < h.pairs ? n_over : h.pairs;  // (the list has a slot per pair)
+    const uint64_t mw = words < cap_words ? words : cap_words, me = h.list_ends < cap_ends ? h.list_ends : cap_ends;
+    const uint64_t mo = over < cap_overflow ? over : cap_overflow;
+    if (lists && mw) VS_HIP(ctx, hipMemcpy(lists, ctx->d_lists.ptr(), sizeof(uint32_t) * mw, hipMemcpyDeviceToHost));
+    if (counts && me) VS_HIP(ctx, hipMemcpy(counts, ctx->d_list_counts.ptr(), sizeof(uint32_t) * me, hipMemcpyDeviceToHost));
+    if (overflow && mo) VS_HIP(ctx, hipMemcpy(overflow, ctx->d_slow_list.ptr(), sizeof(uint32_t) * mo, hipMemcpyDeviceToHost));
     return VS_OK;
 }
 

@@ -1654,6 +1654,24 @@ class Context:
             nat.check(self._h, nat.lib().vs_pe_last_order(self._h, keys.ctypes.data, perm.ctypes.data, m, info))
         return keys[:m], perm[:m], sort, n
 
+    def last_handoff(self):
+        """What the mapping kernel of the most recent ``pe_count`` left for the counter kernels (a test aid,
+        ``vs_pe_last_handoff``), or None after a call that made no hand-off (``map_ends``, ``pe_count_lists``, an empty block).
+        A dict: ``pairs``, ``ept``, ``list_ends``, ``rows`` (0 packed, 1 rows), ``pool`` and ``trim`` of the instantiation that
+        ran, ``lists`` uint32 [words of that layout], ``counts`` uint32 [list_ends], ``overflow`` uint32 = the pairs k_pe_tiles
+        put on the first overflow list, in the order its atomics took.  Node numbers are the index's internal ones."""
+        info = (C.c_uint64 * 9)()
+        nat.check(self._h, nat.lib().vs_pe_last_handoff(self._h, None, 0, None, 0, None, 0, info))
+        if not info[0]:
+            return None
+        lists = np.zeros(max(int(info[8]), 1), dtype=np.uint32)
+        counts = np.zeros(max(int(info[3]), 1), dtype=np.uint32)
+        over = np.zeros(max(int(info[7]), 1), dtype=np.uint32)
+        nat.check(self._h, nat.lib().vs_pe_last_handoff(self._h, lists.ctypes.data, lists.size, counts.ctypes.data, counts.size,
+                                                        over.ctypes.data, over.size, info))
+        return dict(pairs=int(info[1]), ept=int(info[2]), list_ends=int(info[3]), rows=int(info[4]), pool=int(info[5]), trim=int(info[6]),
+                    lists=lists[: int(info[8])], counts=counts[: int(info[3])], overflow=over[: int(info[7])])
+
     def map_ends(self, reads: ReadBlock, cap: int = 64) -> List[List[int]]:
         n = reads.info["ends"]
         lists = np.zeros((max(n, 1), cap), dtype=np.uint32)
