@@ -767,6 +767,39 @@ int vs_pe_last_order(vs_ctx *ctx, uint32_t *keys, uint32_t *perm, uint64_t cap, 
 int vs_pe_last_handoff(vs_ctx *ctx, uint32_t *lists, uint64_t cap_words, uint32_t *counts, uint64_t cap_ends, uint32_t *overflow,
                        uint64_t cap_overflow, uint64_t info[9]);
 
+/* ---- segment depth from the reads (additions to ABI 11 without a new number: nothing that exists changes) ------------
+ * No counterpart in the reference, which takes a segment's depth from the assembler's DP:f or KC:i / LN:i tag
+ * (utils/VStrains_IO.py:49-77).  SPAdes' KC:i is the number of (k+1)-mer occurrences of the segment in the reads, and the
+ * reference's PE table (PE_Inference.py:117-135) is the table of the nodes' (k+1)-mers, so with K = k + 1:
+ *   KC[n] = the number of triples (read end e, read offset i, table entry of node n) for which end_e[i : i + K] is a key
+ *           of that table holding the entry
+ * -- the sum, over all read ends, of the `v` single_end_read_mapping computes per node (PE_Inference.py:29) BEFORE its
+ * acceptance test.  Deliberately: a palindromic window counts twice (the table holds it twice); a (k+1)-mer at several
+ * node positions counts at each; a window over a byte outside ACGT counts nowhere; an end shorter than K, of length 0 or
+ * absent (a singles block) counts nothing; EVERY end of the block counts, also the ends of pairs the PE filter drops
+ * ('N' in the mate, short mate): depth is a property of k-mers, not of pairs.  tests/node_depth_model.py states it.
+ *   vs_node_depth     : one block through k_node_depth on the context's CURRENT index (a later vs_index_build replaces it,
+ *                       as above); d_kc: DEVICE pointer to n_nodes uint64 totals in the numbering vs_index_build was
+ *                       given, ADDED to (atomically), so blocks accumulate.  Enqueued on the ctx stream.  The lists, the
+ *                       locus sort and the PE counters are not involved, and vs_pe_last_* are left as they were.
+ *   vs_ctx_keep_masks : on != 0: every read block built on this context from now on keeps its validity mask.  The PE count
+ *                       never maps an end with an 'N', so a block whose only bytes outside ACGT are 'N's gives its mask
+ *                       back (and the mapped ingest packs such a block on the host without one); the depth pass counts
+ *                       those ends and needs their 'N's.  Call it before the blocks of a depth pass are built: in a block
+ *                       without a mask an 'N' is read as the base it was packed as.  A PE count of a block that kept its
+ *                       mask gives the same counters, by the generic mapping kernel where the block has no position lists.
+ *   vs_depth_plan     : host only, a pure function (csrc/vs_depth_plan.h): the launch vs_node_depth makes for a graph of
+ *                       n_nodes nodes at ksize and a block of n_ends ends of at most max_len bases on a device of n_cu
+ *                       compute units.  plan[0] = route: 0 nothing launched (no end holds a window), 1 dense uint32
+ *                       counters per node in LDS, 2 global (graphs of more than plan[6] nodes: credits combined per
+ *                       wavefront, then added to the totals); [1] = workgroups; [2] = ends per workgroup; [3] = the most
+ *                       ends per workgroup for which ends * (max_len - K + 1) < 2^32, the bound under which no LDS counter
+ *                       wraps ([2] <= [3]); [4] = LDS counters; [5] = LDS bytes per workgroup; [6] = the node limit of
+ *                       route 1; [7] = threads per workgroup.  VS_E_RANGE: more than 2^25 - 2 nodes, 2^32 ends. */
+int vs_node_depth(vs_ctx *ctx, const vs_reads *reads, uint64_t *d_kc);
+int vs_ctx_keep_masks(vs_ctx *ctx, int on);
+int vs_depth_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t plan[8]);
+
 /* Testing aid (ABI 11): the two exclusive scans under the index build, the locus sort, every row_ptr and every member,
  * record and word offset, run alone on values the caller made up, launched exactly as their callers launch them (no kernel
  * of its own).  HOST pointers: in[n + guard] = the n values and behind them `guard` words of a sentinel the caller chose;

@@ -91,7 +91,57 @@ def build_parser():
     p.add_argument("--count-singles", dest="count_singles", action="store_true", default=False,
                    help="extension: with --interleaved --interleaved-singles, with --check-names --check-names-singles or with "
                         "--bam-by-name, the records without a mate are counted into aln/st_info as unpaired reads instead of dropped")
+    p.add_argument("--depth-from-reads", dest="depth_from_reads", action="store_true", default=False,
+                   help="extension: take every segment's depth from THESE reads instead of from the assembler's tags: the (k+1)-mer "
+                        "occurrences of each segment in the reads are counted on the device first (vstrains_amd.node_depth) and "
+                        "the graph goes on as gfa/graph_depth.gfa with LN:i / KC:i tags -- for one assembly graph run against many "
+                        "samples, subsampled or depleted reads, or a GFA that lost its tags; a segment no read touches stops the run; "
+                        "the reads are read twice, so they must be regular files (one process only)")
     return p
+
+
+def depth_from_reads_refusal(args, world: int):
+    """None, or why ``--depth-from-reads`` cannot hold, said before anything is written: under a process group, or -- the
+    reads are read twice, once for the depth and once for the PE links -- with an input that is not a regular file (with
+    ``--pe-text-from`` the PE links are not counted and the reads are read once: a pipe is fine)."""
+    if world > 1:
+        return ("--depth-from-reads counts in one process only; sharing the depth pass among the %d ranks of this process group is not "
+                "built: run without torchrun" % world)
+    if args.pe_text_from is None:
+        from .pe_inference import _regular
+
+        for path in [args.fwd, args.rve] + list(args.single or ()):
+            if not _regular(path):
+                return ("--depth-from-reads reads the reads twice (the depth pass, then the PE links), and %s is not a regular file: a "
+                        "pipe can be read once; write the reads to a file, or run vstrains_amd.node_depth on its own and give its GFA "
+                        "with -g" % path)
+    return None
+
+
+def depth_from_reads(args, logger, ctx):
+    """The depth pass on ``-g``: OUT/gfa/graph_depth.gfa, which the pipeline then takes as its graph.  Exit 1 when a segment
+    has KC = 0 (the reference stops on such a tag itself, IO.py:49-77)."""
+    from . import node_depth
+
+    with open(args.gfa_file, "rb") as fh:
+        raw = fh.read()
+    try:
+        k = node_depth.infer_k(raw)
+    except ValueError as e:
+        logger.error("--depth-from-reads: %s" % e)
+        sys.exit(1)
+    ids, kc, ends = node_depth.depth_pass(ctx, args.gfa_file, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=args.interleaved,
+                                          check_names=args.check_names, single=args.single, count_singles=args.count_singles, quiet=True)
+    out = args.output_dir + "/gfa/graph_depth.gfa"
+    with open(out, "wb") as fh:
+        fh.write(node_depth.rewrite_gfa(raw, kc.tolist()))
+    logger.info("segment depth counted from the reads: k = {0}, {1} read ends, KC sum {2}; the graph goes on as {3}".format(k, ends, int(kc.sum()), out))
+    empty = [ids[i] for i in range(len(ids)) if kc[i] == 0]
+    if empty:
+        logger.error("--depth-from-reads: {0} of {1} segments are touched by no read (KC = 0), e.g. {2}; take them out of the graph, or use "
+                     "the assembler's depth".format(len(empty), len(ids), ", ".join(empty[:5])))
+        sys.exit(1)
+    args.gfa_file = out
 
 
 def pe_text_pair(aln_dir):
@@ -137,6 +187,10 @@ def main(argv=None, backend=None):
     args.single = pe_inference.unpaired_input(args.single, args.count_singles, pe_inference._rank_world()[1], args.interleaved,
                                               pe_text_from=args.pe_text_from, check_names=args.check_names, bam_by_name=args.bam_by_name,
                                               fwd=args.fwd, rve=args.rve)
+    if args.depth_from_reads:
+        why = depth_from_reads_refusal(args, pe_inference._rank_world()[1])
+        if why is not None:
+            raise ValueError(why)
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
         _bail("\nPath to the assembly graph is required, (.gfa format)", "Please ensure the path is correct")
     args.pe_text_files = None
@@ -214,7 +268,7 @@ def main(argv=None, backend=None):
     from .graph import pipeline
 
     if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text or args.bam_by_name or args.interleaved or
-                            args.check_names or args.single):
+                            args.check_names or args.single or args.depth_from_reads):
         from .graph.hip_ops import HipBackend
 
         backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text,
@@ -240,6 +294,8 @@ def main(argv=None, backend=None):
 
     old_err = numpy.seterr(all="raise")  # vstrains:25
     try:
+        if args.depth_from_reads:
+            depth_from_reads(args, logger, backend.ctx)
         timings = pipeline.run(args, logger, backend)
     except BaseException:
         logger.removeHandler(to_file)

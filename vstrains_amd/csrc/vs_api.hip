@@ -118,6 +118,12 @@ int vs_ctx_set_stream(vs_ctx *ctx, void *stream) {
     return VS_OK;
 }
 
+int vs_ctx_keep_masks(vs_ctx *ctx, int on) {
+    if (!ctx) return VS_E_ARG;
+    ctx->keep_masks = on != 0;
+    return VS_OK;
+}
+
 int vs_ctx_sync(vs_ctx *ctx) {
     if (!ctx) return VS_E_ARG;
     VS_HIP(ctx, hipSetDevice(ctx->device));

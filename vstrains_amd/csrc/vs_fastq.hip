@@ -767,7 +767,7 @@ int vs_fastq_block(vs_ctx *ctx, vs_fastq *fq, uint64_t first, uint64_t count, vs
     h_woff[n_ends] = (uint32_t)words;
     uint32_t any = 0, maxlen = 0;
     for (unsigned p = 0; p < T; p++) { any |= part_flags[p]; maxlen = part_max[p] > maxlen ? part_max[p] : maxlen; }
-    if (any & (VS_FLAG_INVALID | 0x80u)) {
+    if ((any & (VS_FLAG_INVALID | 0x80u)) || (ctx->keep_masks && (any & VS_FLAG_N))) {  // (vs_ctx_keep_masks: a block with an 'N' takes that path for its mask)
         // some read holds a byte outside ACGTN (rare): the device packer also builds the validity
         // mask and the position lists -- take that path with the plain bytes of this block (one byte
         // per CHARACTER: a multi-byte UTF-8 character arrives as one '?', see seq_chars)

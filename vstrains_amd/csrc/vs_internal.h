@@ -113,6 +113,10 @@ struct vs_ctx {
     int device = 0;
     bool experiment = false;   // VS_EXPERIMENT=1 at vs_ctx_create: the test hooks of VsTuning exist
     VsTuning tune;
+    // vs_ctx_keep_masks: every read block built from now on keeps its validity mask, so that the depth pass (vs_node_depth),
+    // which counts the ends the PE filter drops too, sees where their 'N's are (without it a block whose only bytes outside
+    // ACGT are 'N's gives its mask back, vs_reads_finish, and the mapped ingest packs on the host without one)
+    bool keep_masks = false;
     hipStream_t stream = nullptr;
     std::string err;
     FqStage fq_stage[2];

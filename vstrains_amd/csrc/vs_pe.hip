@@ -2929,3 +2929,183 @@ extern "C" int vs_pe_map_ends(vs_ctx *ctx, const vs_reads *reads, uint32_t cap, 
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return rc;
 }
+
+// ---- segment depth from the reads (vs_node_depth) -------------------------------------------------------------------
+// KC[n] = the number of (read end, read offset, table entry of node n) coincidences over all ends of a block: the sum of
+// the `v` above over the ends, before any acceptance test and without the pair filter (the definition: vs_depth_plan.h,
+// tests/node_depth_model.py).  The lists, the locus sort and the counter kernels are not involved.
+//   A workgroup of sixteen wavefronts takes a contiguous share of the block's ends; its wavefronts draw batches of 64 ends
+//   off an LDS counter and work alone (no workgroup barrier inside the loop):
+//     the ends' probe counts scanned over the lanes -> one lane per (end, probe), 64 at a time: seed key, table probe;
+//     the probes' posting counts scanned -> one lane per posting, 64 at a time (a seed with a hundred postings fills
+//     two rounds of lanes instead of holding one lane a hundred turns): vs_extend under the mask for ends that hold bytes
+//     outside ACGT ('N' included: every end is counted here, so the block must have kept its mask, vs_ctx_keep_masks);
+//     a match credits len - K + 1, once, by the first grid point inside it (as k_pe_slow).
+//   Credits are summed on chip before they reach memory:
+//     graphs of up to DEPTH_LDS_NODES nodes: a dense uint32 counter per node in LDS, added to the uint64 totals with one
+//       atomic per non-zero counter when the workgroup is done (a counter that wraps carries 2^32 into the total at once);
+//     larger graphs: the 64 credits of a round meet in 64 combining slots of the wavefront (slot by a hash of the node, the
+//       last writer's node owns it), one atomic per slot; credits of nodes that lost their slot go to the totals directly.
+#include "vs_depth_plan.h"
+
+struct DepthParams {
+    VsIndexDev idx;
+    VsReadsDev rd;
+    unsigned long long *kc;  // [n_nodes] totals, ADDED to
+    uint64_t ends_per_wg;
+    uint32_t lds_nodes;      // dense counters in LDS; 0: the global route
+};
+
+__device__ __forceinline__ const uint32_t *vs_depth_mask(const VsReadsDev &rd, uint32_t meta) {
+    return ((meta >> 24) & (VS_FLAG_N | VS_FLAG_INVALID)) ? rd.mask : nullptr;
+}
+
+__global__ void __launch_bounds__(DEPTH_TPB)
+k_node_depth(DepthParams P) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t N = P.idx.n_nodes, w = P.idx.w, s = P.idx.s, K = P.idx.K;
+    const bool dense = P.lds_nodes != 0u;
+    uint32_t *s_kc = vs_lds;  // [lds_nodes]
+    uint32_t *s_head = vs_lds + ((P.lds_nodes + 3u) & ~3u);
+    uint32_t *sw = s_head + DEPTH_HEAD_WORDS + wave * DEPTH_WAVE_WORDS;
+    uint32_t *s_np = sw, *s_cnt = sw + 65u, *s_pa = sw + 130u, *s_pb = sw + 194u, *s_pj = sw + 258u, *s_hk = sw + 322u, *s_hv = sw + 386u;
+    const uint64_t e_lo = (uint64_t)blockIdx.x * P.ends_per_wg;
+    const uint64_t e_hi = e_lo + P.ends_per_wg < P.rd.n_ends ? e_lo + P.ends_per_wg : P.rd.n_ends;
+    for (uint32_t i = tid; i < P.lds_nodes; i += DEPTH_TPB) s_kc[i] = 0u;
+    if (tid == 0u) s_head[0] = 0u;
+    s_hk[lane] = EMPTY_NODE;
+    s_hv[lane] = 0u;
+    __syncthreads();
+    for (;;) {
+        uint32_t b = 0u;
+        if (lane == 0u) b = atomicAdd(&s_head[0], 64u);
+        b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+        if (e_lo + b >= e_hi) break;
+        const uint64_t e0 = e_lo + b;
+        const uint32_t n_here = e_hi - e0 < 64u ? (uint32_t)(e_hi - e0) : 64u;
+        uint32_t np = 0u;
+        if (lane < n_here) {
+            const uint32_t meta = P.rd.meta[e0 + lane];
+            if (!((meta >> 24) & VS_FLAG_ABSENT)) np = vs_seed_probes(meta & VS_LEN_MASK, w, s);  // (0 for an end shorter than K)
+        }
+        s_np[lane + 1u] = vs_wave_scan_add(np);
+        if (lane == 0u) s_np[0] = 0u;
+        vs_wave_sync();
+        const uint32_t tp = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_np[64]);
+        for (uint32_t p0 = 0u; p0 < tp; p0 += 64u) {
+            // probes p0 .. p0 + 63 of the batch: one per lane
+            const uint32_t t = p0 + lane;
+            uint32_t c = 0u, pa = 0u, pb = 0u, pj = 0u;
+            if (t < tp) {
+                const uint32_t el = vs_upper_idx(s_np, 65u, t);  // the end that owns probe t: s_np[el] <= t < s_np[el + 1]
+                const uint64_t e = e0 + el;
+                const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                const uint32_t j = vs_seed_phase(rlen, w, s) + (t - s_np[el]) * s;
+                const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                if (!(mk && vs_seed_dirty(mk, rbase + j, w))) {
+                    uint32_t sr;
+                    const uint64_t key = vs_seed_key(P.rd.words, rbase + j, w, &sr);
+                    c = vs_probe(P.idx, key, sr, &pa, &pb);
+                }
+                pj = (el << 24) | j;  // (a read offset fits 24 bits: VS_LEN_MASK)
+            }
+            s_pa[lane] = pa;
+            s_pb[lane] = pb;
+            s_pj[lane] = pj;
+            s_cnt[lane + 1u] = vs_wave_scan_add(c);
+            if (lane == 0u) s_cnt[0] = 0u;
+            vs_wave_sync();
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[64]);
+            for (uint32_t q0 = 0u; q0 < total; q0 += 64u) {
+                // postings q0 .. q0 + 63 of these probes: one per lane
+                const uint32_t t2 = q0 + lane;
+                uint32_t node = EMPTY_NODE, credit = 0u;
+                if (t2 < total) {
+                    const uint32_t pr = vs_upper_idx(s_cnt, 65u, t2);
+                    const uint32_t k2 = t2 - s_cnt[pr];
+                    const uint32_t qa0 = s_pa[pr], qb0 = s_pb[pr], ej = s_pj[pr];
+                    const uint32_t j = ej & VS_LEN_MASK;
+                    const uint64_t e = e0 + (ej >> 24);
+                    const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                    const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                    const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                    uint32_t nd, pos, opp;
+                    VsNodeMeta nm;
+                    if (s_cnt[pr + 1u] - s_cnt[pr] == 1u) {
+                        nd = qa0; pos = qb0 & 0x7FFFFFFFu; opp = qb0 >> 31;
+                        nm = P.idx.meta[nd];
+                    } else {
+                        const VsPosting po = vs_posting_unpack(P.idx.postings[qa0 + k2]);
+                        nd = po.node; pos = po.pos; opp = po.strand ^ (qb0 >> 31);
+                        nm.woff = po.woff; nm.len = po.len;
+                    }
+                    const uint32_t *tw = opp ? P.idx.rc_words : P.idx.fwd_words;
+                    const uint32_t q = opp ? nm.len - pos - w : pos;
+                    uint32_t a, qa, len;
+                    if (nd < N && vs_extend(P.rd.words, rbase, rlen, tw, nm.woff * 16u, nm.len, j, q, VS_SEED_VERIFIED(w), s, K, mk, rbase, &a, &qa, &len)) {
+                        node = nd;
+                        credit = len - K + 1u;
+                    }
+                }
+                if (dense) {
+                    if (credit) {
+                        const uint32_t old = atomicAdd(&s_kc[node], credit);
+                        if (old + credit < old) atomicAdd(&P.kc[node], 1ull << 32);  // the counter wrapped: its carry
+                    }
+                } else {
+                    const uint32_t slot = (node * 0x9E3779B1u) >> 26;
+                    if (credit) s_hk[slot] = node;  // (racing plain stores: one node owns the slot this round)
+                    vs_wave_sync();
+                    if (credit) {
+                        if (s_hk[slot] == node) atomicAdd(&s_hv[slot], credit);  // (at most 64 x 2^24)
+                        else atomicAdd(&P.kc[node], (unsigned long long)credit);
+                    }
+                    vs_wave_sync();
+                    const uint32_t v = s_hv[lane];
+                    if (v) {
+                        atomicAdd(&P.kc[s_hk[lane]], (unsigned long long)v);
+                        s_hv[lane] = 0u;
+                    }
+                    vs_wave_sync();
+                }
+            }
+            vs_wave_sync();  // s_cnt / s_pa / s_pb / s_pj are rewritten by the next 64 probes
+        }
+        vs_wave_sync();  // s_np is rewritten by the next batch
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < P.lds_nodes; i += DEPTH_TPB) {
+        const uint32_t v = s_kc[i];
+        if (v) atomicAdd(&P.kc[i], (unsigned long long)v);
+    }
+}
+
+extern "C" int vs_depth_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t plan[8]) {
+    if (!plan) return VS_E_ARG;
+    const DepthPlan p = vs_depth_plan_for(n_nodes, ksize + 1u, n_ends, max_len, n_cu);
+    plan[0] = p.route; plan[1] = p.grid; plan[2] = p.ends_per_wg; plan[3] = p.wrap_ends;
+    plan[4] = p.lds_nodes; plan[5] = p.lds_bytes; plan[6] = DEPTH_LDS_NODES; plan[7] = DEPTH_TPB;
+    return p.status;
+}
+
+extern "C" int vs_node_depth(vs_ctx *ctx, const vs_reads *reads, uint64_t *d_kc) {
+    if (!ctx || !reads || !d_kc) return VS_E_ARG;
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_node_depth: build an index first (vs_index_build)");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const VsIndexDev &idx = ctx->idx;
+    const DepthPlan pl = vs_depth_plan_for(idx.n_nodes, idx.K, reads->n_ends, (uint32_t)reads->max_len, (uint32_t)ctx->n_cu);
+    if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "vs_node_depth: %s", pl.msg);
+    if (pl.route == VS_DEPTH_NONE) return VS_OK;  // no end of the block holds a window
+    DepthParams P;
+    P.idx = idx;
+    P.rd = reads->dev();
+    P.kc = (unsigned long long *)d_kc;
+    P.ends_per_wg = pl.ends_per_wg;
+    P.lds_nodes = pl.lds_nodes;
+    if (pl.lds_bytes > 64u * 1024u)
+        VS_HIP(ctx, hipFuncSetAttribute((const void *)k_node_depth, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
+    hipLaunchKernelGGL(k_node_depth, dim3(pl.grid), dim3(DEPTH_TPB), pl.lds_bytes, ctx->stream, P);
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}

@@ -287,7 +287,8 @@ hipError_t vs_reads_finish(vs_ctx *ctx, hipStream_t st, vs_reads *r, uint32_t *d
     if (e != hipSuccess) return e;
     r->n_invalid = *h_cnt;
     if (!r->n_invalid) {
-        r->release(ctx, r->d_mask);
+        if (ctx->keep_masks && r->d_mask) r->bytes += sizeof(uint32_t) * (r->n_words + VS_PAD_WORDS);  // (vs_ctx_keep_masks: the 'N's stay visible)
+        else r->release(ctx, r->d_mask);
         return hipSuccess;
     }
     // rare: some end holds a byte outside ACGTN -> the mask stays, and the position lists are read off it

@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""Segment depth from the reads, counted on the device: write a GFA again with ``LN:i`` / ``KC:i`` tags made from a read set.
+
+    python -m vstrains_amd.node_depth -g IN.gfa -o OUT.gfa -f R1 -r R2 [-k K] [--device D] [the input flags of pe_inference]
+
+The reference takes a segment's depth from the assembler's ``DP:f`` or ``KC:i / LN:i`` tag (utils/VStrains_IO.py:49-77) and
+has no counterpart of this.  ``KC`` is SPAdes' number: the (k+1)-mer occurrences of the segment in the reads.  With K = k + 1,
+``KC[n]`` is the number of triples (read end, read offset i, entry of segment n in the table of the segments' (k+1)-mers,
+PE_Inference.py:117-135) whose read window ``end[i : i + K]`` is a key holding that entry (``tests/node_depth_model.py``);
+every end of the input counts, whatever its mate is like.  No ``DP:f`` is written: the reference's own rule ``kc / ln`` then
+applies, exactly as for a SPAdes GFA.
+"""
+import argparse
+import contextlib
+import io
+import os
+import sys
+
+DEPTH_TAGS = ("dp", "DP", "kc", "KC", "ln", "LN")
+
+
+def _is_depth_tag(field: bytes) -> bool:
+    return field[:2].decode("latin-1") in DEPTH_TAGS and field[2:3] == b":"
+
+
+def rewrite_gfa(raw: bytes, kc) -> bytes:
+    """``raw`` again, every ``S`` line carrying ``LN:i:<sequence length>`` and ``KC:i:<count>`` right behind its sequence in
+    place of any ``dp / DP / kc / KC / ln / LN`` tag it had; its other tags stay, in their order; every other line, and every
+    line end (``\\n``, ``\\r\\n``, none at the end of the file), stays byte for byte.  ``kc``: one count per ``S`` line, in file
+    order."""
+    out = []
+    n = 0
+    for line in raw.splitlines(keepends=True):
+        body = line.rstrip(b"\r\n")
+        if not body.startswith(b"S\t"):
+            out.append(line)
+            continue
+        cols = body.split(b"\t")
+        if len(cols) < 3:
+            raise ValueError("S line %d has no sequence: %r" % (n + 1, body[:60]))
+        if n >= len(kc):
+            raise ValueError("the GFA holds more S lines than the %d counts given" % len(kc))
+        tags = [b"LN:i:%d" % len(cols[2]), b"KC:i:%d" % int(kc[n])] + [t for t in cols[3:] if not _is_depth_tag(t)]
+        out.append(b"\t".join(cols[:3] + tags) + line[len(body):])
+        n += 1
+    if n != len(kc):
+        raise ValueError("the GFA holds %d S lines and %d counts were given" % (n, len(kc)))
+    return b"".join(out)
+
+
+def strip_depth_tags(raw: bytes) -> bytes:
+    """``raw`` with the depth tags of every ``S`` line taken out (what Bandage, gfatools or awk subsets leave behind)."""
+    out = []
+    for line in raw.splitlines(keepends=True):
+        body = line.rstrip(b"\r\n")
+        if body.startswith(b"S\t"):
+            cols = body.split(b"\t")
+            body = b"\t".join(cols[:3] + [t for t in cols[3:] if not _is_depth_tag(t)])
+        out.append(body + line[len(line.rstrip(b"\r\n")):])
+    return b"".join(out)
+
+
+def infer_k(raw: bytes) -> int:
+    """The overlap of the ``L`` lines (``<k>M``).  ``ValueError`` when there are none or they disagree."""
+    seen = set()
+    for line in raw.splitlines():
+        if line.startswith(b"L\t"):
+            cols = line.split(b"\t")
+            ovl = [t for t in cols[5:] if t[-1:] in (b"M", b"m")]
+            if not ovl or not ovl[0][:-1].isdigit():
+                raise ValueError("an L line has no <k>M overlap: %r" % line[:80])
+            seen.add(int(ovl[0][:-1]))
+    if not seen:
+        raise ValueError("the GFA has no L lines to take k from: give -k")
+    if len(seen) > 1:
+        raise ValueError("the L lines of the GFA disagree on the overlap (%s): give -k" % ", ".join(str(v) for v in sorted(seen)))
+    return seen.pop()
+
+
+def refuse_ranks(world: int) -> None:
+    if world > 1:
+        raise ValueError("the depth pass counts in one process only; sharing it among the %d ranks of this process group is not built "
+                         "(the sums are additive, so it can follow): run without torchrun" % world)
+
+
+def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
+               count_singles: bool = False, quiet: bool = False):
+    """Index the segments of ``gfa`` and count every end the chosen input delivers (the input dispatch of
+    ``pe_inference.count_links``, one process only).  -> (segment ids in file order, KC int64 in file order, ends counted).
+    Replaces the context's index; the context stops keeping masks when the pass is over, so a PE count may follow on it.
+    ``quiet``: the dispatch's progress lines are not printed."""
+    from . import pe as host
+    from . import pe_inference
+
+    rank, world = pe_inference._rank_world()
+    refuse_ranks(world)
+    inp = pe_inference._resolve_inputs(fwd, rve, world, bam_by_name, interleaved, check_names, single, count_singles, False)
+    ids, seqs = host.read_gfa_segments(gfa)
+    ctx.build_index(seqs, kmer_size)
+    counter = host.DepthCounter(ctx)  # (the blocks built from here on keep their masks)
+    try:
+        with contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext():
+            pe_inference.feed_counter(ctx, counter, inp, 0, 1, stages_follow=False, tally_singles=False)
+        ctx.sync()
+    finally:
+        ctx.keep_masks(False)
+    return ids, counter.result(), counter.ends_seen
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="node_depth", description="Write a GFA again with LN:i / KC:i tags counted from a read set on the device")
+    p.add_argument("-g", "--gfa", dest="gfa", type=str, required=True, help="graph, .gfa format (its depth tags, if any, are replaced)")
+    p.add_argument("-o", "--output", dest="out", type=str, required=True, help="the GFA to write")
+    p.add_argument("-f", "--forward", dest="fwd", required=True, help="forward read, .fastq")
+    p.add_argument("-r", "--reverse", dest="rve", required=True, help="reverse read, .fastq")
+    p.add_argument("-k", "--kmer_size", dest="kmer_size", type=int, default=None, help="kmer size [default: the overlap of the L lines]")
+    p.add_argument("--device", dest="device", type=int, default=0, help="HIP device ordinal")
+    p.add_argument("--bam-by-name", dest="bam_by_name", action="store_true", default=False, help="as pe_inference")
+    p.add_argument("--gzip-device", dest="gzip_device", action="store_true", default=False, help="as pe_inference")
+    p.add_argument("--interleaved", dest="interleaved", action="store_true", default=False, help="as pe_inference")
+    p.add_argument("--interleaved-singles", dest="interleaved_singles", action="store_true", default=False, help="as pe_inference")
+    p.add_argument("--check-names", dest="check_names", action="store_true", default=False, help="as pe_inference")
+    p.add_argument("--check-names-singles", dest="check_names_singles", action="store_true", default=False, help="as pe_inference")
+    p.add_argument("--single", dest="single", action="append", default=[], metavar="FILE", help="as pe_inference (repeatable)")
+    p.add_argument("--count-singles", dest="count_singles", action="store_true", default=False, help="as pe_inference")
+    return p
+
+
+def main(argv=None) -> int:
+    from . import pe_inference
+
+    args = build_parser().parse_args(argv)
+    with open(args.gfa, "rb") as fh:
+        raw = fh.read()
+    k = args.kmer_size
+    if k is None:
+        try:
+            k = infer_k(raw)
+        except ValueError as e:
+            print("node_depth: %s" % e, file=sys.stderr)
+            return 1
+    interleaved = pe_inference.interleaved_mode(args.interleaved, args.interleaved_singles)
+    check_names = pe_inference.check_names_mode(args.check_names, args.check_names_singles)
+    if args.gzip_device:
+        os.environ["VS_GZIP_DEVICE"] = "1"
+    refuse_ranks(int(os.environ.get("WORLD_SIZE", "1")))  # (before a device is opened)
+    world = 1
+    pe_inference.interleaved_input(args.fwd, args.rve, world, interleaved)
+    pe_inference.check_names_input(args.fwd, args.rve, world, check_names, bam_by_name=args.bam_by_name, interleaved=interleaved)
+    pe_inference.unpaired_input(args.single, args.count_singles, world, interleaved, check_names=check_names, bam_by_name=args.bam_by_name,
+                                fwd=args.fwd, rve=args.rve)
+    from . import pe as host
+
+    ctx = host.Context(args.device)
+    ids, kc, ends = depth_pass(ctx, args.gfa, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=interleaved,
+                               check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True)
+    text = rewrite_gfa(raw, kc.tolist())
+    with open(args.out, "wb") as fh:
+        fh.write(text)
+    print("node_depth: k = %d, %d read ends counted, %d window-entry coincidences (sum of KC), %d of %d segments with KC = 0; result stored in: %s"
+          % (k, ends, int(kc.sum()), int((kc == 0).sum()), len(ids), args.out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

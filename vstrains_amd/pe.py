@@ -1600,6 +1600,16 @@ class Context:
         nat.check(self._h, nat.lib().vs_pe_count(self._h, reads._h, C.c_void_p(node_mat_ptr),
                                                  C.c_void_p(short_mat_ptr), C.c_void_p(stats_ptr)))
 
+    def node_depth(self, reads: ReadBlock, kc_ptr: int):
+        """One block through the depth pass (``vs_node_depth``): ``kc_ptr`` is a device pointer to ``n_nodes`` 64-bit totals
+        in the index's own numbering, added to.  Blocks must have been built after ``keep_masks(True)``."""
+        nat.check(self._h, nat.lib().vs_node_depth(self._h, reads._h, C.c_void_p(kc_ptr)))
+
+    def keep_masks(self, on: bool = True):
+        """Read blocks built from now on keep their validity mask (``vs_ctx_keep_masks``): the depth pass counts the ends
+        with an 'N' too and has to see where it is."""
+        nat.check(self._h, nat.lib().vs_ctx_keep_masks(self._h, 1 if on else 0))
+
     def last_timing(self):
         a = (C.c_double * 5)()
         nat.check(self._h, nat.lib().vs_pe_last_timing(self._h, a))
@@ -1949,6 +1959,51 @@ class PeCounter:
             m += self.user_order(self.wide[:, :n, :n]).cpu().numpy()
         s = self.stats.cpu().numpy()
         return m[0], m[1], (int(s[0]), int(s[1]), int(s[2]))
+
+
+def depth_plan(n_nodes: int, ksize: int, n_ends: int, max_len: int, n_cu: int = 256) -> dict:
+    """The launch ``vs_node_depth`` makes (``vs_depth_plan``, a pure host function: no device is needed)."""
+    a = (C.c_uint64 * 8)()
+    rc = nat.lib().vs_depth_plan(n_nodes, ksize, n_ends, max_len, n_cu, a)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_depth_plan refuses %d nodes / %d ends" % (n_nodes, n_ends))
+    return dict(route=("none", "lds", "global")[int(a[0])], grid=int(a[1]), ends_per_wg=int(a[2]), wrap_ends=int(a[3]), lds_nodes=int(a[4]),
+                lds_bytes=int(a[5]), node_limit=int(a[6]), threads=int(a[7]))
+
+
+class DepthCounter:
+    """KC per segment, counted from the reads on one device (``vs_node_depth``): the number of (k+1)-mer occurrences of the
+    segment in the read ends, what SPAdes writes as ``KC:i``.  Takes the place of a ``PeCounter`` in the input dispatch of
+    ``pe_inference`` (``add``, ``device``, ``single_stats``); every end of every block counts, mates and filters aside.
+    The context keeps the masks of the blocks built after this (``Context.keep_masks``)."""
+
+    def __init__(self, ctx: Context, device: Optional[str] = None):
+        import torch
+
+        self.torch = torch
+        self.ctx = ctx
+        self.device = torch.device(device or ("cuda:%d" % ctx.device))
+        self.n = ctx.n_nodes
+        self.kc = torch.zeros(max(self.n, 1), dtype=torch.int64, device=self.device)
+        self.single_stats = torch.zeros(3, dtype=torch.int64, device=self.device)  # (what the dispatch tallies of a PeCounter: stays zero)
+        self.ends_seen = 0  # ends the blocks delivered (the absent second ends of singles blocks aside)
+        self.node_rank = getattr(ctx, "node_rank", None)  # (kept here, as PeCounter does: a later build_index cannot change how kc is read)
+        ctx.keep_masks(True)
+
+    def add(self, reads: ReadBlock):
+        torch = self.torch
+        n_ends = reads.info["ends"]
+        self.ends_seen += n_ends // 2 if reads.unpaired else n_ends
+        with torch.cuda.device(self.device):
+            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.ctx.node_depth(reads, self.kc.data_ptr())
+
+    def result(self) -> np.ndarray:
+        """int64 [N] in the numbering of the node list ``Context.build_index`` was given (the GFA's order)."""
+        kc = self.kc[: self.n]
+        if self.node_rank is not None:
+            kc = kc.index_select(0, self.torch.from_numpy(self.node_rank).to(kc.device))
+        return kc.cpu().numpy().astype(np.int64)
 
 
 # ---- outputs -------------------------------------------------------------------------------------

@@ -54,6 +54,20 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     file or the BAM, one entry with ``path = "FWD + RVE"`` for the two files joined by name (their blocks alternate per round;
     the per-file kept counts are ``pair_names_info``'s ``singles_fwd`` / ``singles_rve``)."""
     rank, world = _rank_world()
+    inp = _resolve_inputs(fwd, rve, world, bam_by_name, interleaved, check_names, single, count_singles, interleaved_shard)
+    ids, seqs = host.read_gfa_segments(gfa)  # :100-112
+    ctx.build_index(seqs, kmer_size)  # :114-135  (KeyError on a bad node base, as :13)
+    counter = host.PeCounter(ctx)
+
+    feed_counter(ctx, counter, inp, rank, world, stages_follow=stages_follow)
+    if world > 1:
+        counter.all_reduce()  # (every rank ends with the full sums; only rank 0 writes the files and runs the stages)
+    return ids, counter
+
+
+def _resolve_inputs(fwd, rve, world, bam_by_name, interleaved, check_names, single, count_singles, interleaved_shard):
+    """Which ingest reads the inputs of ``count_links``, decided (and what the flags cannot apply to refused with a
+    ``ValueError``) before a device is opened or the graph is read."""
     count_links.bam_info = None
     count_links.interleaved_info = None
     count_links.pair_names_info = None
@@ -70,10 +84,16 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     if world > 1 and not (_regular(fwd) and _regular(rve)):  # (the sharded path maps regular files; VS_FASTQ_STREAM aside)
         raise ValueError("the FASTQ inputs %s / %s are not both regular files: a pipe can be read by one process only, so "
                          "the sharded (torchrun) run cannot take it; run one process, or write the reads to files" % (fwd, rve))
-    ids, seqs = host.read_gfa_segments(gfa)  # :100-112
-    ctx.build_index(seqs, kmer_size)  # :114-135  (KeyError on a bad node base, as :13)
-    counter = host.PeCounter(ctx)
+    return dict(fwd=fwd, rve=rve, single=single, by_names=by_names, il_path=il_path, bam=bam, streamed=streamed, bam_by_name=bam_by_name,
+                interleaved=interleaved, check_names=check_names, count_singles=count_singles)
 
+
+def feed_counter(ctx, counter, inp, rank: int = 0, world: int = 1, stages_follow: bool = False, tally_singles: bool = True):
+    """Every block the chosen input delivers through ``counter.add`` -- a ``PeCounter`` (``count_links``) or a
+    ``DepthCounter`` (``node_depth.depth_pass``, one process, ``tally_singles=False``: it keeps no tallies of unpaired reads).
+    ``inp``: what ``_resolve_inputs`` decided."""
+    fwd, rve, single, by_names, il_path, bam, streamed = (inp[k] for k in ("fwd", "rve", "single", "by_names", "il_path", "bam", "streamed"))
+    bam_by_name, interleaved, check_names, count_singles = (inp[k] for k in ("bam_by_name", "interleaved", "check_names", "count_singles"))
     print("Start aligning reads to gfa nodes")  # :146
     # one process per GPU (torchrun): this rank counts its contiguous block of the pairs and the
     # counters are summed over ranks afterwards (RCCL all-reduce); a single process takes everything
@@ -90,7 +110,7 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
             count_links.interleaved_info = fq.info
         finally:
             fq.close()
-        if count_singles:
+        if count_singles and tally_singles:
             count_links.single_info.append(_single_tally(il_path, counter, (0, 0, 0)))
     elif by_names:
         fq = host.PairedNameStream(fwd, rve, ctx, block_pairs=BATCH_PAIRS,
@@ -103,7 +123,7 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
         if check_names == "singles":
             print("Pairs joined by read name: %d; records without a mate %s: %d of %s, %d of %s"
                   % (info["pairs"], "counted as unpaired reads" if count_singles else "dropped", info["singles_fwd"], fwd, info["singles_rve"], rve))
-        if count_singles:
+        if count_singles and tally_singles:
             count_links.single_info.append(_single_tally("%s + %s" % (fwd, rve), counter, (0, 0, 0)))
     elif bam is not None and world > 1:
         # one collated whole-BGZF BAM: the ranks share it by member, summarise their shares for every entry the previous share
@@ -142,7 +162,7 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
                 count_links.bam_info = fq.info
         finally:
             fq.close()
-        if count_singles:
+        if count_singles and tally_singles:
             count_links.single_info.append(_single_tally(bam, counter, (0, 0, 0)))
     elif world > 1:
         # two whole-BGZF files: the ranks share them by member, count lines and inflate on their devices only, and each
@@ -179,18 +199,16 @@ def count_links(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, stages_follow
     if fq is not None:
         fq.close()
     for path in single:  # (one process only: unpaired_input)
-        before = tuple(int(x) for x in counter.single_stats.cpu().numpy())
+        before = tuple(int(x) for x in counter.single_stats.cpu().numpy()) if tally_singles else None
         fs = host.SingleEndStream(path, ctx, block_reads=BATCH_PAIRS)
         try:
             count_stream(ctx, fs, counter)
         finally:
             fs.close()
-        count_links.single_info.append(_single_tally(path, counter, before))
+        if tally_singles:
+            count_links.single_info.append(_single_tally(path, counter, before))
     for rec in count_links.single_info:
         print("Unpaired reads of %s: %d used, %d with N, %d shorter than k+1" % (rec["path"], rec["used"], rec["with_n"], rec["short"]))
-    if world > 1:
-        counter.all_reduce()  # (every rank ends with the full sums; only rank 0 writes the files and runs the stages)
-    return ids, counter
 
 
 def count_interleaved_shard(ctx, il_path: str, counter, rank: int, world: int, singles: bool, all_gather=None):
