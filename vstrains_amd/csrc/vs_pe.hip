@@ -1069,6 +1069,28 @@ __device__ __forceinline__ bool vs_cell_claim(uint32_t *s_key, uint32_t *s_cnt, 
     return false;
 }
 
+// The same for a caller that has read the slot already and found `seen` there, not the key: the first probe takes that
+// word instead of reading the slot again -- one LDS round trip less on a path that nearly every turn of a wavefront takes
+// for some lane.  (A slot that held another cell holds it until the next write-out, and an empty one goes through the
+// compare-and-swap, which tells what it holds now.)
+template <typename TB>
+__device__ __forceinline__ bool vs_cell_claim_seen(uint32_t *s_key, uint32_t *s_cnt, uint32_t *s_used, uint32_t key, uint32_t at, uint32_t wgt, uint32_t seen) {
+    uint32_t kx = seen;
+    for (uint32_t pr = 0; pr < 8u; pr++) {
+        if (pr) kx = s_key[at];
+        if (kx == TB::EMPTY) {
+            kx = atomicCAS(&s_key[at], TB::EMPTY, key);
+            if (kx == TB::EMPTY) { atomicAdd(s_used, 1u); kx = key; }
+        }
+        if (kx == key) {
+            atomicAdd(&s_cnt[at], wgt);
+            return true;
+        }
+        at = TB::next(at);
+    }
+    return false;
+}
+
 // (the same wavefront writes and reads its own task region: no workgroup barrier, only the LDS wait)
 __device__ __forceinline__ void vs_wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1087,10 +1109,13 @@ __device__ __forceinline__ void vs_wave_lds_sync() {
 //          its lists by one cross-lane read, kind and position -> x, partner list, partner stretches) and walks its
 //          partners in blocks of four list words -- one 16-byte load at the word the block starts at, issued one block
 //          ahead; the decode, x and first block of the NEXT window are issued before this window is counted, so no global
-//          load is waited on.  A turn is one key, one slot read, one add or claim; the four turns of a block read their
-//          slots together, as the runs of four did.  A window ends with its longest task, which the order makes nearly
-//          every lane's end.
-// gfx950 (hipcc -O3, -Rpass-analysis=kernel-resource-usage): 122 VGPRs, 0 B of scratch, ACC_LDS_BYTES = 163 344 B of the CU's 163 840 B
+//          load is waited on.  A turn is one key, one slot read, one add or claim.  The block's slot reads are written
+//          side by side, but as compiled the first is waited on before the second key is formed; issuing all four ahead
+//          of one wait was measured and gains nothing (profiles/EXPERIMENTS.md, 2026-10-20b).  What a turn costs is its
+//          claims: with 64 lanes nearly every turn has a lane whose cell is not in its slot yet, so the whole wavefront
+//          walks the claim -- which therefore starts from the word the turn has read (vs_cell_claim_seen), not from a
+//          second read of the slot.  A window ends with its longest task, which the order makes nearly every lane's end.
+// gfx950 (hipcc -O3, -Rpass-analysis=kernel-resource-usage): 123 VGPRs, 0 B of scratch, ACC_LDS_BYTES = 163 344 B of the CU's 163 840 B
 // of LDS: one workgroup of sixteen wavefronts per CU, four per SIMD (which 128 VGPRs allow).
 __global__ void __launch_bounds__(ACC_TPB)
 k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__ counts, uint64_t n_slots_pairs,
@@ -1247,8 +1272,8 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
                     if (t + 4u < tmax) q = *(const VsQuad *)(plist + p);
                     const uint32_t left = tmax - t;  // turns of the window still to come (wave-uniform)
                     if (use_table) {
-                        // the block's cells' slots are read together (independent LDS loads), then counted; a
-                        // slot that does not hold the cell yet goes the slow way (claim / probe / global)
+                        // the block's cells' slots are read (independent LDS loads), then counted; a slot that does
+                        // not hold the cell yet goes the slow way (claim from the word read / probe / global)
                         uint32_t key[4], seen[4], at[4];
 #pragma unroll
                         for (uint32_t j = 0; j < 4u; j++) {
@@ -1265,7 +1290,7 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
                             if (pb + j >= e) continue;
                             if (seen[j] == key[j]) {
                                 atomicAdd(&s_cnt[at[j]], 1u);
-                            } else if (!vs_cell_claim<Acc32>(s_key, s_cnt, &s_used, key[j], at[j], 1u)) {
+                            } else if (!vs_cell_claim_seen<Acc32>(s_key, s_cnt, &s_used, key[j], at[j], 1u, seen[j])) {
                                 atomicAdd(&s_lost, 1u);
                                 atomicAdd(key[j] >= NN ? short_mat + (key[j] - NN) : node_mat + key[j], 1u);
                             }
