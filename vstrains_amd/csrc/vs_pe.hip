@@ -1031,7 +1031,8 @@ k_pe_tiles(PeParams P) {
 //     (vs_acc_tasks.h), one lane per task, the tasks of a batch of pairs ordered by length.
 //   * the row owners below (larger graphs): output-major.  There a round of locus-ordered pairs brings more distinct
 //     cells than the table holds, and the same cell returns from loci hundreds of rounds apart.
-// LDS of k_pe_accumulate: the cell table, per wavefront a region of task entries and the counters of their sort, four words
+// LDS of k_pe_accumulate: the cell table, per wavefront a region of task entries (its last words the queue of missed keys)
+// and the counters of their sort, four words
 #define ACC_LDS_BYTES ((2u * ACC_SLOTS + (ACC_TPB / 64) * (ACC_TASK_WORDS + ACC_BINS) + 4u) * 4u)
 static_assert(ACC_LDS_BYTES <= 160u * 1024u, "k_pe_accumulate: one workgroup per CU");
 // The cell table: 16 k slots, 32-bit keys (k_pe_accumulate: mat * N*N + x * N + y, while 2*N*N fits 32 bits, N <= 46340;
@@ -1061,29 +1062,9 @@ __device__ __forceinline__ bool vs_cell_claim(uint32_t *s_key, uint32_t *s_cnt, 
             if (kx == TB::EMPTY) { atomicAdd(s_used, 1u); kx = key; }
         }
         if (kx == key) {
-            atomicAdd(&s_cnt[at], wgt);
-            return true;
-        }
-        at = TB::next(at);
-    }
-    return false;
-}
-
-// The same for a caller that has read the slot already and found `seen` there, not the key: the first probe takes that
-// word instead of reading the slot again -- one LDS round trip less on a path that nearly every turn of a wavefront takes
-// for some lane.  (A slot that held another cell holds it until the next write-out, and an empty one goes through the
-// compare-and-swap, which tells what it holds now.)
-template <typename TB>
-__device__ __forceinline__ bool vs_cell_claim_seen(uint32_t *s_key, uint32_t *s_cnt, uint32_t *s_used, uint32_t key, uint32_t at, uint32_t wgt, uint32_t seen) {
-    uint32_t kx = seen;
-    for (uint32_t pr = 0; pr < 8u; pr++) {
-        if (pr) kx = s_key[at];
-        if (kx == TB::EMPTY) {
-            kx = atomicCAS(&s_key[at], TB::EMPTY, key);
-            if (kx == TB::EMPTY) { atomicAdd(s_used, 1u); kx = key; }
-        }
-        if (kx == key) {
-            atomicAdd(&s_cnt[at], wgt);
+            // (workgroup scope: with the scope of a caller's add to memory for the cell that found no place, the compiler
+            // makes ONE flat atomic on a selected address of the two)
+            __hip_atomic_fetch_add(&s_cnt[at], wgt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             return true;
         }
         at = TB::next(at);
@@ -1109,12 +1090,20 @@ __device__ __forceinline__ void vs_wave_lds_sync() {
 //          its lists by one cross-lane read, kind and position -> x, partner list, partner stretches) and walks its
 //          partners in blocks of four list words -- one 16-byte load at the word the block starts at, issued one block
 //          ahead; the decode, x and first block of the NEXT window are issued before this window is counted, so no global
-//          load is waited on.  A turn is one key, one slot read, one add or claim.  The block's slot reads are written
-//          side by side, but as compiled the first is waited on before the second key is formed; issuing all four ahead
-//          of one wait was measured and gains nothing (profiles/EXPERIMENTS.md, 2026-10-20b).  What a turn costs is its
-//          claims: with 64 lanes nearly every turn has a lane whose cell is not in its slot yet, so the whole wavefront
-//          walks the claim -- which therefore starts from the word the turn has read (vs_cell_claim_seen), not from a
-//          second read of the slot.  A window ends with its longest task, which the order makes nearly every lane's end.
+//          load is waited on.  A turn is one key, one slot read, and an add where the slot holds the cell.  The block's
+//          slot reads are written side by side, but as compiled the first is waited on before the second key is formed;
+//          issuing all four ahead of one wait was measured and gains nothing (profiles/EXPERIMENTS.md, 2026-10-20b).  A
+//          window ends with its longest task, which the order makes nearly every lane's end.
+//   claim  a turn claims nothing.  With 64 lanes seven turns in eight have a lane whose cell is not in its slot (measured:
+//          7.6 such lanes a turn, four in ten of them at a slot that holds another cell), and a claim is LDS round trips
+//          one behind the other -- compare-and-swap, fill counter, add -- which the whole wavefront would walk for those
+//          few lanes.  So the lanes that miss append their keys to the wavefront's QUEUE, the last ACC_QUEUE words of its
+//          task region (which is why the plan hands out ACC_TASK_PLAN_CAP entries at most): the place from the ballot of
+//          the misses and the lane's count of set bits below it, the length wave-uniform, from the ballot's popcount -- one
+//          store, no wait, no divergent path.  When a turn's misses do not fit, and at the end of the round in front of the
+//          barrier (so the fill and lost counters are complete when they are read and nothing waits across a write-out), the
+//          wavefront drains the queue: lane i claims key i (vs_cell_claim, which reads the slot: what the turn saw is stale).
+//          A key may wait there more than once, from several lanes and turns: every entry is worth one increment.
 // gfx950 (hipcc -O3, -Rpass-analysis=kernel-resource-usage): 123 VGPRs, 0 B of scratch, ACC_LDS_BYTES = 163 344 B of the CU's 163 840 B
 // of LDS: one workgroup of sixteen wavefronts per CU, four per SIMD (which 128 VGPRs allow).
 __global__ void __launch_bounds__(ACC_TPB)
@@ -1125,7 +1114,8 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
     uint32_t *s_key = vs_lds;                      // [ACC_SLOTS]
     uint32_t *s_cnt = vs_lds + ACC_SLOTS;          // [ACC_SLOTS]
     uint32_t *s_bin = vs_lds + 2u * ACC_SLOTS + wv * (ACC_TASK_WORDS + ACC_BINS);  // [ACC_BINS] of this wavefront
-    uint16_t *s_task = (uint16_t *)(s_bin + ACC_BINS);                             // [ACC_TASK_CAP]
+    uint16_t *s_task = (uint16_t *)(s_bin + ACC_BINS);                             // [task_cap <= ACC_TASK_PLAN_CAP]
+    uint32_t *s_q = s_bin + ACC_BINS + (ACC_TASK_WORDS - ACC_QUEUE);               // [ACC_QUEUE], the last words of the task region
     uint32_t *s_misc = vs_lds + 2u * ACC_SLOTS + (ACC_TPB / 64) * (ACC_TASK_WORDS + ACC_BINS);
     uint32_t &s_used = s_misc[0], &s_lost = s_misc[1], &s_chunk = s_misc[2];
     const uint32_t NN = N * N;  // (use_table: 2 * N * N fits 32 bits)
@@ -1147,6 +1137,21 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
         }
         if (tid == 0) { s_used = 0; s_lost = 0; }
         __syncthreads();
+    };
+    // the keys this wavefront has found no cell for yet: claimed ACC_QUEUE at a time, lane i takes key i -- the slot is read
+    // again, what the turn saw there is stale -- and none waits beyond the round
+    uint32_t qn = 0;  // keys waiting (wave-uniform)
+    auto drain = [&]() {
+        vs_wave_lds_sync();
+        if (lane < qn) {
+            const uint32_t key = s_q[lane];
+            if (!vs_cell_claim<Acc32>(s_key, s_cnt, &s_used, key, Acc32::slot(key), 1u)) {
+                atomicAdd(&s_lost, 1u);
+                atomicAdd(key >= NN ? short_mat + (key - NN) : node_mat + key, 1u);
+            }
+        }
+        vs_wave_lds_sync();
+        qn = 0;
     };
     for (;;) {
     __syncthreads();
@@ -1272,8 +1277,8 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
                     if (t + 4u < tmax) q = *(const VsQuad *)(plist + p);
                     const uint32_t left = tmax - t;  // turns of the window still to come (wave-uniform)
                     if (use_table) {
-                        // the block's cells' slots are read (independent LDS loads), then counted; a slot that does
-                        // not hold the cell yet goes the slow way (claim from the word read / probe / global)
+                        // the block's cells' slots are read (independent LDS loads), then counted; the key of a slot that
+                        // does not hold the cell yet waits in the queue for the slow way (claim / probe / global)
                         uint32_t key[4], seen[4], at[4];
 #pragma unroll
                         for (uint32_t j = 0; j < 4u; j++) {
@@ -1287,12 +1292,17 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
 #pragma unroll
                         for (uint32_t j = 0; j < 4u; j++) {
                             if (j >= left) break;
-                            if (pb + j >= e) continue;
-                            if (seen[j] == key[j]) {
-                                atomicAdd(&s_cnt[at[j]], 1u);
-                            } else if (!vs_cell_claim_seen<Acc32>(s_key, s_cnt, &s_used, key[j], at[j], 1u, seen[j])) {
-                                atomicAdd(&s_lost, 1u);
-                                atomicAdd(key[j] >= NN ? short_mat + (key[j] - NN) : node_mat + key[j], 1u);
+                            const bool on = pb + j < e;
+                            if (on && seen[j] == key[j]) atomicAdd(&s_cnt[at[j]], 1u);
+                            // the lanes that missed queue their keys: places from the ballot, the length wave-uniform
+                            const bool miss = on && seen[j] != key[j];
+                            const uint64_t mm = __ballot(miss);
+                            if (mm) {
+                                const uint32_t n_miss = (uint32_t)__popcll(mm);
+                                if (qn + n_miss > ACC_QUEUE) drain();
+                                const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
+                                if (miss) s_q[qn + before] = key[j];
+                                qn += n_miss;
                             }
                         }
                     } else {
@@ -1308,6 +1318,7 @@ k_pe_accumulate(const uint32_t *__restrict__ lists, const uint32_t *__restrict__
                 }
             }
         }
+        if (qn) drain();  // (s_used and s_lost are complete when they are read, nothing waits across a write-out)
         __syncthreads();
         const bool spill = s_used > fill_limit || s_lost > 4096u;
         __syncthreads();

@@ -28,7 +28,7 @@ struct VsTuning {
     uint32_t ept = 0;               // VS_EPT (0 = automatic)
     uint32_t grid_per_cu = 128;     // VS_GRID_PER_CU: longer runs of tiles per workgroup, as a full-size block has
     int acc_fill_pct = -1;          // VS_ACC_FILL (-1 = 1/16 of the slots): cell-table write-outs on fill
-    uint32_t acc_tasks = 0;         // VS_ACC_TASKS (0 = ACC_TASK_CAP): task entries per wavefront of k_pe_accumulate, so that small blocks reach the batch cut
+    uint32_t acc_tasks = 0;         // VS_ACC_TASKS (0 = ACC_TASK_PLAN_CAP): task entries per wavefront of k_pe_accumulate, so that small blocks reach the batch cut
     int shortcut = -1;              // VS_SHORTCUT (-1 = by index statistics)
     int adapt_grid = -1;            // VS_ADAPT_GRID (-1 = by index statistics): the adaptive step grid of the compile-time-shape kernels
     int acc_rows = -1;              // VS_ACC_ROWS (-1 = by graph size): counters summed by row owners (k_rows_sum) instead of pair-major (k_pe_accumulate)
@@ -71,6 +71,8 @@ VS_PLAN_FN uint32_t vs_seed_probes(uint32_t len, uint32_t w, uint32_t s) {
 #define ACC_TASK_WORDS 480u  // LDS words of a wavefront's task region (vs_acc_tasks.h): what the cell table leaves of 160 KB of LDS
 #define ACC_TASK_CAP (2u * ACC_TASK_WORDS)  // ... and the 16-bit task entries they hold
 #define ACC_TASK_MIN 40u     // tasks of the largest pair (two lists of 20 nodes): the smallest task region there may be
+#define ACC_QUEUE 64u        // keys a wavefront collects before it claims their cells, one per lane: the last words of its task region
+#define ACC_TASK_PLAN_CAP (ACC_TASK_CAP - 2u * ACC_QUEUE)  // ... so 832 task entries are the most the plan hands the kernel
 #define ACC_BINS 24u         // counters per wavefront of the counting sort of a batch's tasks (turns 1 .. 22)
 #define ROWS_KEYS 65536u   // rows per histogram pass (larger graphs take several passes over the lists)
 #define ROWS_SUB ((1u << 26) - 1024u)  // pairs per transposition (an entry names a read end in 27 bits, its list's length in five; row offsets are 32-bit)
@@ -399,7 +401,8 @@ inline PePlan vs_pe_plan(const PePlanIn &in) {
         p.acc_fill = ACC_SLOTS / 16u;
         if (tn.acc_fill_pct >= 0) p.acc_fill = (uint32_t)((uint64_t)ACC_SLOTS * (uint32_t)tn.acc_fill_pct / 100u);
         // task entries a wavefront sorts per batch of pairs (VS_ACC_TASKS shrinks the region: batches of a few pairs)
-        p.acc_task_cap = tn.acc_tasks >= ACC_TASK_MIN && tn.acc_tasks < ACC_TASK_CAP ? tn.acc_tasks : ACC_TASK_CAP;
+        // (the region's last ACC_QUEUE words are the wavefront's queue of missed keys)
+        p.acc_task_cap = tn.acc_tasks >= ACC_TASK_MIN && tn.acc_tasks < ACC_TASK_PLAN_CAP ? tn.acc_tasks : ACC_TASK_PLAN_CAP;
         return p;
     }
     // the row owners (pe_count_by_rows)
