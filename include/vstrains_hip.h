@@ -766,6 +766,16 @@ int vs_pe_last_order(vs_ctx *ctx, uint32_t *keys, uint32_t *perm, uint64_t cap, 
  *   kernels run.  In the row layout only the quads that hold nodes are written by the kernel. */
 int vs_pe_last_handoff(vs_ctx *ctx, uint32_t *lists, uint64_t cap_words, uint32_t *counts, uint64_t cap_ends, uint32_t *overflow,
                        uint64_t cap_overflow, uint64_t info[9]);
+/* Testing aid (addition to ABI 11 without a new number, like vs_pe_last_handoff): where the overflow pairs of the most recent
+ * vs_pe_count / vs_pe_count_tracked / vs_pe_map_ends went, copied to HOST memory.  Launches nothing and changes nothing;
+ * synchronises the stream.
+ *   info[0] = 1 if that call launched the overflow kernels, 0 if not (an empty block, vs_pe_count_lists, a call that failed
+ *             before its launch, no call yet): every other word is 0 then and nothing is copied
+ *   info[1] = pairs on the first overflow list (what k_pe_tiles gave up)
+ *   info[2] = pairs k_pe_mid passed on to k_pe_slow (beyond its 64 probes, 256 touched or 64 accepted nodes per end)
+ *   info[3] = 1 if k_pe_mid was skipped (VS_NO_MID on an experiment context: k_pe_slow took the first list; info[2] = 0)
+ *   second[info[2]]: those pairs, in the order k_pe_mid's atomics took; at most cap are written; may be NULL. */
+int vs_pe_last_overflow(vs_ctx *ctx, uint32_t *second, uint64_t cap, uint64_t info[4]);
 
 /* ---- segment depth from the reads (additions to ABI 11 without a new number: nothing that exists changes) ------------
  * No counterpart in the reference, which takes a segment's depth from the assembler's DP:f or KC:i / LN:i tag

@@ -146,6 +146,7 @@ SYMBOLS = {
     "vs_pe_lists_ept": (C.c_uint32, [C.c_void_p]),
     "vs_pe_last_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vs_pe_last_handoff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vs_pe_last_overflow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vs_node_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "vs_ctx_keep_masks": (C.c_int, [C.c_void_p, C.c_int]),
     "vs_depth_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

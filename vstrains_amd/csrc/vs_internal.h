@@ -165,6 +165,9 @@ struct vs_ctx {
     // the hand-off of that call, if it made one (vs_pe_last_handoff: d_lists / d_list_counts / d_slow_list hold it): pairs (0 = none),
     // end slots, ends per tile, layout, table slots and list trim of the k_pe_tiles instantiation that ran
     struct LastHandoff { uint64_t pairs = 0, list_ends = 0; uint32_t ept = 0, rows = 0, pool = 0, trim = 0; } last_handoff;
+    // the overflow kernels of that call, if it launched them (vs_pe_last_overflow: d_slow_count / d_slow_list2 hold what they left):
+    // pairs (0 = none), whether k_pe_mid was skipped
+    struct LastOverflow { uint64_t pairs = 0; uint32_t no_mid = 0; } last_overflow;
     int n_cu = 256;
 };
 

@@ -2644,6 +2644,7 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
     ctx->last_launched = 0;
     ctx->last_order_pairs = 0;
     ctx->last_handoff = {};
+    ctx->last_overflow = {};
     // test hooks: fixed defaults unless the process runs with VS_EXPERIMENT=1 (see VsTuning)
     if (ctx->experiment) vs_tuning_load(ctx->tune, true);
     PePlanIn in;
@@ -2802,6 +2803,8 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
         hipLaunchKernelGGL(k_pe_slow, dim3(pl.slow_grid), dim3(TPB), 0, st, P, ctx->d_dense.as<uint32_t>(), (uint32_t)n_pairs,
                            ctx->d_slow_list.as<const uint32_t>(), ctx->d_slow_count.as<const uint32_t>());
     }
+    ctx->last_overflow.pairs = n_pairs;
+    ctx->last_overflow.no_mid = no_mid ? 1u : 0u;
     VS_HIP(ctx, hipEventRecord(ctx->ev[2], st));
     VS_HIP(ctx, hipGetLastError());
     return VS_OK;
@@ -2855,6 +2858,7 @@ extern "C" int vs_pe_count_lists(vs_ctx *ctx, uint32_t n_nodes, uint64_t n_pairs
     ctx->last_launched = 0;
     ctx->last_order_pairs = 0;
     ctx->last_handoff = {};  // (the lists here are the host's: nothing a mapping kernel left)
+    ctx->last_overflow = {};
     ctx->last_kernel = "";
     const PePlan pl = pe_lists_plan(ctx, n_nodes, 2u * n_pairs, d_tile_map != nullptr);
     if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "%s", pl.msg);
@@ -2922,6 +2926,23 @@ extern "C" int vs_pe_last_handoff(vs_ctx *ctx, uint32_t *lists, uint64_t cap_wor
     if (lists && mw) VS_HIP(ctx, hipMemcpy(lists, ctx->d_lists.ptr(), sizeof(uint32_t) * mw, hipMemcpyDeviceToHost));
     if (counts && me) VS_HIP(ctx, hipMemcpy(counts, ctx->d_list_counts.ptr(), sizeof(uint32_t) * me, hipMemcpyDeviceToHost));
     if (overflow && mo) VS_HIP(ctx, hipMemcpy(overflow, ctx->d_slow_list.ptr(), sizeof(uint32_t) * mo, hipMemcpyDeviceToHost));
+    return VS_OK;
+}
+
+extern "C" int vs_pe_last_overflow(vs_ctx *ctx, uint32_t *second, uint64_t cap, uint64_t info[4]) {
+    if (!ctx || !info) return VS_E_ARG;
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const vs_ctx::LastOverflow &o = ctx->last_overflow;
+    for (int i = 0; i < 4; i++) info[i] = 0;
+    if (!o.pairs) return VS_OK;  // the overflow kernels did not run: an empty block, vs_pe_count_lists, a call that failed before its launch
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t n_first = 0, n_second = 0;  // (SC_MID: k_pe_tiles counts into it; SC_SLOW: k_pe_mid does, and stays 0 without it)
+    VS_HIP(ctx, hipMemcpy(&n_first, ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_MID, sizeof n_first, hipMemcpyDeviceToHost));
+    VS_HIP(ctx, hipMemcpy(&n_second, ctx->d_slow_count.as<uint32_t>() + vs_ctx::SC_SLOW, sizeof n_second, hipMemcpyDeviceToHost));
+    info[0] = 1; info[1] = n_first; info[2] = n_second; info[3] = o.no_mid;
+    const uint64_t held = n_second < o.pairs ? n_second : o.pairs;  // (the list has a slot per pair)
+    const uint64_t m = held < cap ? held : cap;
+    if (second && m) VS_HIP(ctx, hipMemcpy(second, ctx->d_slow_list2.ptr(), sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
     return VS_OK;
 }
 

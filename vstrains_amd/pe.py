@@ -1682,6 +1682,19 @@ class Context:
         return dict(pairs=int(info[1]), ept=int(info[2]), list_ends=int(info[3]), rows=int(info[4]), pool=int(info[5]), trim=int(info[6]),
                     lists=lists[: int(info[8])], counts=counts[: int(info[3])], overflow=over[: int(info[7])])
 
+    def last_overflow(self):
+        """Where the overflow pairs of the most recent ``pe_count`` / ``map_ends`` went (a test aid, ``vs_pe_last_overflow``),
+        or None after a call that did not launch the overflow kernels (``pe_count_lists``, an empty block).  A dict:
+        ``first_n`` = pairs k_pe_tiles gave up, ``second_n`` = pairs k_pe_mid passed on to k_pe_slow, ``second`` uint32 = those
+        pairs (indices into the block), in the order its atomics took, ``no_mid`` = 1 where k_pe_mid was skipped."""
+        info = (C.c_uint64 * 4)()
+        nat.check(self._h, nat.lib().vs_pe_last_overflow(self._h, None, 0, info))
+        if not info[0]:
+            return None
+        second = np.zeros(max(int(info[2]), 1), dtype=np.uint32)
+        nat.check(self._h, nat.lib().vs_pe_last_overflow(self._h, second.ctypes.data, second.size, info))
+        return dict(first_n=int(info[1]), second_n=int(info[2]), second=second[: int(info[2])], no_mid=int(info[3]))
+
     def map_ends(self, reads: ReadBlock, cap: int = 64) -> List[List[int]]:
         n = reads.info["ends"]
         lists = np.zeros((max(n, 1), cap), dtype=np.uint32)
