@@ -479,6 +479,13 @@ k_pe_tiles(PeParams P) {
     const uint32_t wv = VS_SEED_VERIFIED(w);  // seed bases the comparison skips (0: seeds with mixed keys, vs_seed_key)
     constexpr bool P12 = STD && !AD;  // the 768-slot table (vs_std_table)
     constexpr uint32_t C_POOL = vs_std_table(MODE, STD, AD).pool, C_TRIM = vs_std_table(MODE, STD, AD).trim;
+    // PRE: a thread's probe of the NEXT tile is begun in front of P4 -- key, home slot, the slot's load -- and finished in that
+    // tile's P1 from the carried key and slot (one probe per thread; nothing of it is live across P3).  Measured and not kept
+    // (profiles/EXPERIMENTS.md): walking the chain on at places between the two, and issuing the loads of the tile after it
+    // behind P1 instead of in front of it.
+    constexpr bool PRE = MODE == 1 && STD && !AD;
+    static_assert(!PRE || STD_EPT * SP <= TTPB, "the pre-probe takes one probe of the next tile per thread");
+    static_assert(!PRE || (STD_W <= 31u && VS_MULTI_BIT == (1ull << 62)), "the carried key keeps the strand in bit 63: exact keys of at most 62 bits");
     const uint32_t pool = STD ? C_POOL : P.pool, pool_shift = 32u - (STD ? C_POOL_BITS : P.pool_bits);
     const uint32_t words_cap = STD ? C_EPT * STD_WPE : P.words_cap;
     const TileLayout T = tile_layout(ept, pmax, words_cap, pool, C_TRIM);
@@ -585,6 +592,10 @@ k_pe_tiles(PeParams P) {
     prefetch_pair(tile_lo + 1u);
     prefetch_headers();
     prefetch_pair(tile_lo + 2u);
+    // (PRE) this thread's probe of the tile, begun a tile early: key (strand in bit 63), home slot and that slot's words
+    uint64_t pre_key = 0;
+    uint32_t pre_sl = 0;
+    uint4 pre_raw = make_uint4(0u, 0u, 0u, 0u);
     for (uint32_t tile = tile_lo; tile < tile_hi; tile++) {
         uint32_t ltop = tid;  // (nothing P0 .. P2 derive from the thread index is hoisted out of the tile loop: see the 768-slot table)
         asm volatile("" : "+v"(ltop));
@@ -722,7 +733,12 @@ k_pe_tiles(PeParams P) {
                 uint32_t meta = s_meta[e];
                 uint32_t rlen = meta & VS_LEN_MASK;
                 uint32_t j = (est >> 8) + pi * s;
-                if (j + w <= rlen) {
+                // (PRE) a clean end of a tile behind the run's first: the test the previous tile made when it began this probe
+                // (same header, same grid), so the probe is finished from its home slot, which has arrived; a dirty end, whose
+                // limits need inv4, and the first tile of a run take the plain probe
+                if (PRE && tile != tile_lo && j + w <= rlen && !((meta >> 24) & VS_FLAG_INVALID)) {
+                    cnt = vs_probe_from(P.idx, pre_key & ~(1ull << 63), (uint32_t)(pre_key >> 63), pre_sl, pre_raw, &pa, &pb);
+                } else if (j + w <= rlen) {
                     uint32_t sr;
                     const uint64_t key = vs_seed_key(s_words, e * wpe * 16u + j, w, &sr);
                     bool ok = true;
@@ -906,6 +922,28 @@ k_pe_tiles(PeParams P) {
         // across P3, the phase the kernel's 96-register budget is made for)
         uint32_t lt = tid;
         asm volatile("" : "+v"(lt));
+        // (PRE) the next tile's words are all in (the barrier above): begin this thread's probe of that tile.  Its offset
+        // follows from the end's length alone; whether the pair is used is decided in the next P0 -- a probe begun for
+        // nothing is dropped (the table is read-only).
+        if (PRE) {  // (set on every path: the old probe is dead behind its P1, not kept across P3)
+            pre_sl = 0;
+            pre_key = 0;
+            pre_raw = make_uint4(0u, 0u, 0u, 0u);
+        }
+        if (PRE && lt < NI) {
+            const uint32_t e = lt / STD_PMAX, pi = lt - e * pmax;
+            if (e < ne1) {  // (0 in the last tile of the run)
+                const uint32_t meta = n_meta[e], rlen = meta & VS_LEN_MASK;
+                const uint32_t j = vs_seed_phase(rlen, w, s) + pi * s;
+                if (j + w <= rlen && !((meta >> 24) & VS_FLAG_INVALID)) {
+                    uint32_t sr;
+                    const uint64_t key = vs_seed_key(n_words, e * wpe * 16u + j, w, &sr);
+                    pre_key = key | ((uint64_t)sr << 63);
+                    pre_sl = vs_slot_of(key, P.idx.table_bits);
+                    pre_raw = ((const uint4 *)P.idx.table)[pre_sl];
+                }
+            }
+        }
         // (compile-time shapes: a thread's four slots -- key and position -- stay in registers across the prefix sum)
         constexpr uint32_t SPT = STD ? C_POOL / TTPB : 1u;
         uint32_t r_key[SPT], r_at[SPT];
