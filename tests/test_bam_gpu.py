@@ -282,3 +282,25 @@ def test_what_is_out_of_scope_is_refused_in_words(host, ctx, tmp_path):
     bad.write_bytes(bytes(raw))
     with pytest.raises(ValueError, match="not a complete gzip stream"):
         _drain(host, ctx, bad)
+
+
+# ---- the block builder (block_builder_cases.py): what every streamed ingest checks alike ------------------------------------------
+def test_over_long_sequence_is_refused_by_its_pair(host, ctx, tmp_path):
+    """l_seq = 2^24 in the second record of pair 1: the builder's refusal, worded with the pair"""
+    import block_builder_cases as bb
+    from vstrains_amd import _native as nat
+
+    good = [bu.rec("g0", bu.PAIRED | bu.FIRST, "ACGTACGTAC"), bu.rec("g0", bu.PAIRED | bu.SECOND, "TTGCA"), bu.rec("g1", bu.PAIRED | bu.FIRST, "GATTACA")]
+    path = tmp_path / "long.bam"
+    path.write_bytes(bz.bgzf(bu.inflated(good) + bb.long_bam_record(b"g1", bu.PAIRED | bu.SECOND), 1))
+    bb.refused(host.BamStream(str(path), ctx), nat.NativeError, "%s: pair 1 has a sequence of more than %d bases" % (path, bb.LONG - 1))
+
+
+def test_blocks_are_the_host_packers_at_the_edges_of_the_ends_kernel(host, ctx, tmp_path):
+    import block_builder_cases as bb
+
+    fwd, rve = bb.edge_pairs(other="M")  # (a base that is neither ACGT nor N has a 4-bit code of its own)
+    records = [r for i, (a, b) in enumerate(zip(fwd, rve)) for r in (bu.rec("p%d" % i, bu.PAIRED | bu.FIRST, a), bu.rec("p%d" % i, bu.PAIRED | bu.SECOND, b))]
+    path = tmp_path / "edges.bam"
+    path.write_bytes(bu.write(records))
+    bb.same_at_every_block_size(lambda n: host.BamStream(str(path), ctx, block_pairs=n), ctx.pack_pairs(fwd, rve), unpaired=False)

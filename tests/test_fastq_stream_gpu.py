@@ -336,3 +336,28 @@ def test_torchrun_refuses_fifo_input(tmp_path):
             cwd=ROOT, capture_output=True, text=True, env=env, timeout=600)
     assert proc.returncode != 0
     assert "a pipe can be read by one process only" in proc.stderr
+
+
+# ---- the block builder (block_builder_cases.py): what every streamed ingest checks alike ------------------------------------------
+def test_over_long_sequence_line_of_file_2_is_refused(host, ctx, tmp_path):
+    """a sequence line of 2^24 bytes in file 2: the builder's refusal, worded with that file and the record's number"""
+    import block_builder_cases as bb
+    from vstrains_amd import _native as nat
+
+    fwd, rve = bb.edge_pairs(3)
+    names = [b"p%d" % i for i in range(3)]
+    (tmp_path / "f.fq").write_bytes(bb.fastq(fwd, names))
+    (tmp_path / "r.fq").write_bytes(bb.fastq(rve[:1], names[:1]) + bb.long_record(names[1]) + bb.fastq(rve[2:], names[2:]))
+    fs = host.FastqStream(str(tmp_path / "f.fq"), str(tmp_path / "r.fq"), ctx)
+    bb.refused(fs, nat.NativeError, "%s: record 1 has a sequence line of more than %d bytes" % (tmp_path / "r.fq", bb.LONG - 1))
+
+
+def test_blocks_are_the_host_packers_at_the_edges_of_the_ends_kernel(host, ctx, tmp_path):
+    import block_builder_cases as bb
+
+    fwd, rve = bb.edge_pairs()
+    names = [b"p%d" % i for i in range(len(fwd))]
+    (tmp_path / "f.fq").write_bytes(bb.fastq(fwd, names))
+    (tmp_path / "r.fq").write_bytes(bb.fastq(rve, names))
+    bb.same_at_every_block_size(lambda n: host.FastqStream(str(tmp_path / "f.fq"), str(tmp_path / "r.fq"), ctx, block_pairs=n),
+                                ctx.pack_pairs(fwd, rve), unpaired=False)

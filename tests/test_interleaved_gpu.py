@@ -273,3 +273,25 @@ def test_cli_on_the_interleaved_file_writes_every_file_of_the_pair(tmp_path):
         if rel != "vstrains.log":  # (time stamps and paths)
             assert (tmp_path / "out_il" / rel).read_bytes() == (tmp_path / "out_pair" / rel).read_bytes(), rel
     assert "records of the interleaved FASTQ have no mate" in (tmp_path / "out_il" / "vstrains.log").read_text()
+
+
+# ---- the block builder (block_builder_cases.py): what every streamed ingest checks alike ------------------------------------------
+def test_over_long_sequence_line_of_a_second_record_is_refused(host, ctx, tmp_path):
+    """a sequence line of 2^24 bytes in the second record of a pair: the builder's refusal names the record in file order"""
+    import block_builder_cases as bb
+    from vstrains_amd import _native as nat
+
+    fwd, rve = bb.edge_pairs(3)
+    path = tmp_path / "il.fq"
+    path.write_bytes(bb.fastq([fwd[0], rve[0], fwd[1]], [b"p0", b"p0", b"p1"]) + bb.long_record(b"p1") + bb.fastq([fwd[2], rve[2]], [b"p2", b"p2"]))
+    bb.refused(host.InterleavedStream(str(path), ctx), nat.NativeError,
+               "%s: record 3 has a sequence line of more than %d bytes" % (path, bb.LONG - 1))
+
+
+def test_blocks_are_the_host_packers_at_the_edges_of_the_ends_kernel(host, ctx, tmp_path):
+    import block_builder_cases as bb
+
+    fwd, rve = bb.edge_pairs()
+    path = tmp_path / "il.fq"
+    path.write_bytes(bb.fastq([s for pair in zip(fwd, rve) for s in pair], [b"p%d" % (i // 2) for i in range(2 * len(fwd))]))
+    bb.same_at_every_block_size(lambda n: host.InterleavedStream(str(path), ctx, block_pairs=n), ctx.pack_pairs(fwd, rve), unpaired=False)

@@ -537,3 +537,26 @@ def test_cli_counts_the_kept_records(tmp_path, source):
     assert len(counted) == 1 and counted[0].endswith("unpaired reads of %s were counted into the paired end information" % single_path)
     assert _log(tmp_path / "out_drop", "unpaired reads of") == []
     assert "Unpaired reads of %s: " % single_path in got.stdout and "Unpaired reads of" not in drop.stdout
+
+
+# ---- the block builder (block_builder_cases.py): the refusal of an over-long end in the singles blocks of the three keep modes ------
+def test_over_long_kept_single_is_refused(host, ctx, tmp_path):
+    import block_builder_cases as bb
+    from vstrains_amd import _native as nat
+
+    fwd, rve = bb.edge_pairs(3)
+    limit = bb.LONG - 1
+    # interleaved: a single record between two pairs
+    il = tmp_path / "il.fq"
+    il.write_bytes(bb.fastq([fwd[0], rve[0]], [b"p0", b"p0"]) + bb.long_record(b"s") + bb.fastq([fwd[1], rve[1]], [b"p1", b"p1"]))
+    bb.refused(host.InterleavedStream(str(il), ctx, singles="keep"), nat.NativeError, "%s: record 2 has a sequence line of more than %d bytes" % (il, limit))
+    # two files by name: a record of file 2 without a mate
+    (tmp_path / "f.fq").write_bytes(bb.fastq(fwd[:2], [b"a", b"b"]))
+    (tmp_path / "r.fq").write_bytes(bb.fastq(rve[:1], [b"a"]) + bb.long_record(b"s") + bb.fastq(rve[1:2], [b"b"]))
+    bb.refused(host.PairedNameStream(str(tmp_path / "f.fq"), str(tmp_path / "r.fq"), ctx, singles="keep"), ValueError,
+               "%s: record 1 has a sequence line of more than %d bytes" % (tmp_path / "r.fq", limit))
+    # BAM by name: a record still waiting at the end of the file
+    bam = tmp_path / "w.bam"
+    good = [bu.rec("g0", bu.PAIRED | bu.FIRST, "ACGTACGTAC"), bu.rec("g0", bu.PAIRED | bu.SECOND, "TTGCA")]
+    bam.write_bytes(bz.bgzf(bu.inflated(good) + bb.long_bam_record(b"w", bu.PAIRED | bu.FIRST), 1))
+    bb.refused(host.BamStream(str(bam), ctx, by_name=True, singles="keep"), ValueError, "%s: record 2 has a sequence of more than %d bases" % (bam, limit))

@@ -390,3 +390,27 @@ def test_cli_on_the_damaged_pair_writes_every_file_of_the_filtered_pair(tmp_path
             assert _sha(tmp_path / "out_names" / rel) == _sha(tmp_path / "out_filtered" / rel), rel
     log = (tmp_path / "out_names" / "vstrains.log").read_text()
     assert "%d records of %s and %d records of %s have no mate by name" % (s1, tmp_path / "df.fq.gz", s2, tmp_path / "dr.fq") in log
+
+
+# ---- the block builder (block_builder_cases.py): what every streamed ingest checks alike ------------------------------------------
+def test_over_long_sequence_line_of_file_2_is_refused(host, ctx, tmp_path):
+    """a sequence line of 2^24 bytes in file 2, in a record whose number is not its pair's: file 2 has a record without a mate
+    in front of it, so the builder's refusal has to go through the pair list for the record's number"""
+    import block_builder_cases as bb
+
+    fwd, rve = bb.edge_pairs(4)
+    (tmp_path / "f.fq").write_bytes(bb.fastq(fwd[:3], [b"a", b"b", b"c"]))
+    (tmp_path / "r.fq").write_bytes(bb.fastq([rve[3], rve[0]], [b"x", b"a"]) + bb.long_record(b"b") + bb.fastq([rve[2]], [b"c"]))
+    fs = host.PairedNameStream(str(tmp_path / "f.fq"), str(tmp_path / "r.fq"), ctx, singles=True)
+    bb.refused(fs, ValueError, "%s: record 2 has a sequence line of more than %d bytes" % (tmp_path / "r.fq", bb.LONG - 1))
+
+
+def test_blocks_are_the_host_packers_at_the_edges_of_the_ends_kernel(host, ctx, tmp_path):
+    import block_builder_cases as bb
+
+    fwd, rve = bb.edge_pairs()
+    names = [b"p%d" % i for i in range(len(fwd))]
+    (tmp_path / "f.fq").write_bytes(bb.fastq(fwd, names))
+    (tmp_path / "r.fq").write_bytes(bb.fastq(rve, names))
+    bb.same_at_every_block_size(lambda n: host.PairedNameStream(str(tmp_path / "f.fq"), str(tmp_path / "r.fq"), ctx, block_pairs=n),
+                                ctx.pack_pairs(fwd, rve), unpaired=False)

@@ -351,3 +351,14 @@ def test_cli_single(tmp_path):
     assert (tmp_path / "out_single" / "aln" / "st_info").read_bytes() != (tmp_path / "out_pair" / "aln" / "st_info").read_bytes()
     assert "Unpaired reads of %s: " % (tmp_path / "single.fq") in got.stdout
     assert "Unpaired reads of %s: 0 used, 0 with N, 0 shorter than k+1" % (tmp_path / "empty.fq") in empty.stdout
+
+
+# ---- the block builder (block_builder_cases.py): what every streamed ingest checks alike ------------------------------------------
+def test_blocks_are_the_host_packers_at_the_edges_of_the_ends_kernel(host, workload, tmp_path):
+    import block_builder_cases as bb
+
+    reads = [s for pair in zip(*bb.edge_pairs()) for s in pair]
+    path = tmp_path / "se.fq"
+    path.write_bytes(_fastq(reads))
+    ctx = workload["ctx"]
+    bb.same_at_every_block_size(lambda n: host.SingleEndStream(str(path), ctx, block_reads=n), ctx.pack_singles(reads), unpaired=True)

@@ -11,7 +11,7 @@ order of --only, --rounds rounds, a warm page cache, a host clock from the open 
 in which every block is downloaded -- both legs must deliver the same ends:
 
     f  pe.FastqStream on the pair      (k_inflate, k_sl_*, k_pack_reads<PackLines>)
-    b  pe.BamStream on the BAM         (k_inflate, k_bam_exits / k_bam_walk / k_bam_count / k_bam_scatter, k_bam_ends,
+    b  pe.BamStream on the BAM         (k_inflate, k_bam_exits / k_bam_walk / k_bam_count / k_bam_scatter, k_bam_couples,
                                         k_pack_reads<PackBam>)
 
 No counting: the legs end where vs_pe_count would begin.  Prints one JSON line; --out writes it to a file as well.
@@ -24,7 +24,7 @@ moved back by a random 0..2 000 records, as the proper pairs of a sorted alignme
 records -- and four legs alternate inside ONE process:
 
     c  pe.BamStream on the collated file                  (the collated mode, the yardstick)
-    n  pe.BamStream(by_name=True) on the collated file    (k_mate_hash / _claim / _rank / _partner / _emit, k_bam_ends_list, k_mate_carry)
+    n  pe.BamStream(by_name=True) on the collated file    (k_mate_hash / _claim / _rank / _partner / _emit, k_mate_carry)
     m  ... on "near"
     x  ... on "far"
 

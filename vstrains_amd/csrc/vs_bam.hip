@@ -17,10 +17,10 @@
 //   k_bam_scatter  the same walk: offset, flag and class, l_seq and sequence offset of every record at its index, the
 //                  index of every record that takes part at its compacted index; the first malformed record by atomicMin;
 // and per block of n couples
-//   k_bam_ends     couple c = compacted records 2c, 2c + 1: one first and one second or the first bad couple by atomicMin;
-//                  the forward and the reverse record of every couple, the lengths and packed words of the ends, the cut;
-//   k_bam_tally    records seen and dropped, by class, among those the block passes;
-// then k_sl_scan for the word offsets, k_pack_reads<PackBam> and vs_reads_finish as every block is built.
+//   k_bam_couples  couple c = compacted records 2c, 2c + 1: one first and one second or the first bad couple by atomicMin;
+//                  the forward and the reverse record of every couple, the cut;
+//   the block builder (vs_block_bam, vs_reads.hip), as every block of a streamed ingest is built: lengths, word offsets, packing;
+//   k_bam_tally    records seen and dropped, by class, among those the block passes.
 // No kernel waits for another workgroup; every window read and LDS index is tested against its range.
 //
 // The window is scanned once per appended chunk; blocks are cut from the scanned records with a cursor.  The carry is
@@ -37,13 +37,13 @@
 //   (k_sl_scan)     per workgroup: emitters, waiting records and their bytes to bases (a word per 256 records);
 //   k_mate_emit     the place inside the workgroup by a prefix over its lanes: the pair list (first, second) in the order of
 //                   the emitting record, the waiting list, the offset of every waiting record among the carried bytes;
-//   k_bam_ends_list a block of pairs from that list with a cursor (k_bam_ends takes neighbours instead);
+//   the block builder on a block of pairs from that list with a cursor: the list is the ends (k_bam_couples takes neighbours);
 //   k_mate_carry    a wavefront per waiting record copies it to the front of the other window buffer, 16 bytes a lane
 //                   where source and destination are aligned alike; the bytes from `stop` on follow.
 // No lane waits for another lane's progress: a lost compare-and-swap reads the winner and goes on.
 // What still waits at the end of the input are singletons: counted, and under VS_BAM_BY_NAME_KEEP handed out from the last
-// window's waiting list (window order = file order) as singles blocks: k_bam_single_ends, k_sl_scan,
-// k_pack_reads<PackBamSingles> (even end e = waiting record e / 2, reversed and complemented under 0x10; odd ends absent).
+// window's waiting list (window order = file order) as singles blocks by the same builder (vs_block_bam_singles: even end e =
+// waiting record e / 2, reversed and complemented under 0x10; odd ends absent).
 //
 // A member range (vs_bam_stream_open_range; one process per GPU on one collated whole-BGZF file).  A range cannot be entered
 // at a guessed record start, so the open has two passes with one exchange between them (pe.BamStream.open_shard):
@@ -71,14 +71,11 @@ enum {
     B_STOP = 1,     // where
     B_NREC = 2,
     B_NPART = 3,
-    B_MALFORMED = 4,  // index of the first malformed record, ~0u: none
-    B_BADCOUPLE = 5,  // first couple of the block that is not one first and one second, ~0u: none
-    B_CUT = 6,        // offset of the first record behind the block
-    B_CUTREC = 7,     // ... and its index
-    B_MAXLEN = 8,
-    B_TOO_LONG = 9,
-    B_WORDS = 10,
-    B_INVALID = 11,
+    B_BLOCK = 4,      // the VS_BLK_ST words of the block builder; behind them, read back with them, k_bam_couples' three:
+    B_BADCOUPLE = 8,  // first couple of the block that is not one first and one second, ~0u: none
+    B_CUT = 9,        // offset of the first record behind the block
+    B_CUTREC = 10,    // ... and its index
+    B_MALFORMED = 11, // index of the first malformed record, ~0u: none
     B_BAD_MEMBER = 12,  // first BGZF member the device rejected (a running index), ~0u: none
     B_OWN_REC = 13,     // a ranged stream: records / participating records of the window that this rank owns
     B_OWN_PART = 14,
@@ -171,37 +168,22 @@ __global__ void __launch_bounds__(BAM_TPB) k_bam_scatter(const uint8_t *__restri
     }
 }
 
-// one thread per end of the block (and one more for the closing word offset)
-__global__ void __launch_bounds__(BAM_TPB) k_bam_ends(const uint4 *__restrict__ recs, const uint32_t *__restrict__ part, uint32_t part0, uint32_t n_pairs,
-                                                      uint32_t n_rec, uint32_t stop, uint32_t *__restrict__ ends, uint32_t *__restrict__ meta,
-                                                      uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
-    const uint32_t e = blockIdx.x * BAM_TPB + threadIdx.x, n_ends = 2u * n_pairs;
-    if (e == 0 && n_pairs) {
-        const uint32_t after = part[part0 + n_ends - 1u] + 1u;
+// one thread per couple of the block: the check, which record is which end, and (thread 0) the cut behind the block
+__global__ void __launch_bounds__(BAM_TPB) k_bam_couples(const uint4 *__restrict__ recs, const uint32_t *__restrict__ part, uint32_t part0, uint32_t n_pairs,
+                                                         uint32_t n_rec, uint32_t stop, uint32_t *__restrict__ ends, uint32_t *__restrict__ st) {
+    const uint32_t c = blockIdx.x * BAM_TPB + threadIdx.x;
+    if (c == 0 && n_pairs) {
+        const uint32_t after = part[part0 + 2u * n_pairs - 1u] + 1u;
         st[B_CUTREC] = after;
         st[B_CUT] = after < n_rec ? recs[after].x : stop;
     }
-    if (e > n_ends) return;
-    if (e == n_ends) {
-        wcnt[e] = 0u;
-        return;
-    }
-    const uint32_t c = e >> 1, a = part[part0 + 2u * c], b = part[part0 + 2u * c + 1u];
+    if (c >= n_pairs) return;
+    const uint32_t a = part[part0 + 2u * c], b = part[part0 + 2u * c + 1u];
     const uint32_t fa = recs[a].y, fb = recs[b].y;
-    if (!bam_couple_ok(fa, fb) && !(e & 1u)) atomicMin(&st[B_BADCOUPLE], c);
-    const bool a_first = (fa >> 16) == (uint32_t)BAM_C_FIRST;
-    const uint32_t r = ((e & 1u) != 0u) == a_first ? b : a;  // (the first is the forward end)
-    ends[e] = r;
-    const uint32_t len = recs[r].z;
-    if (len > VS_LEN_MASK) {
-        atomicMin(&st[B_TOO_LONG], e);
-        meta[e] = 0u;
-        wcnt[e] = 0u;
-        return;
-    }
-    meta[e] = len;
-    wcnt[e] = (len + 15u) >> 4;
-    atomicMax(&st[B_MAXLEN], len);
+    if (!bam_couple_ok(fa, fb)) atomicMin(&st[B_BADCOUPLE], c);
+    const bool a_first = (fa >> 16) == (uint32_t)BAM_C_FIRST;  // (the first is the forward end)
+    ends[2u * c] = a_first ? a : b;
+    ends[2u * c + 1u] = a_first ? b : a;
 }
 
 __global__ void __launch_bounds__(BAM_TPB) k_bam_tally(const uint4 *__restrict__ recs, uint32_t from, uint32_t to, uint32_t *__restrict__ tally) {
@@ -430,61 +412,6 @@ __global__ void __launch_bounds__(BAM_TPB) k_mate_carry(BamMates m, uint64_t n, 
     for (uint64_t k = head + 16u * body + lane; k < len; k += VS_WAVE) t[k] = s[k];
 }
 
-// the ends of pairs [pair0, pair0 + n_pairs) of the pair list: as k_bam_ends, the two records taken from the list
-__global__ void __launch_bounds__(BAM_TPB) k_bam_ends_list(const uint4 *__restrict__ recs, const uint32_t *__restrict__ pairs, uint32_t pair0, uint32_t n_pairs,
-                                                           uint32_t n_rec, uint32_t *__restrict__ ends, uint32_t *__restrict__ meta,
-                                                           uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
-    const uint32_t e = blockIdx.x * BAM_TPB + threadIdx.x, n_ends = 2u * n_pairs;
-    if (e > n_ends) return;
-    if (e == n_ends) {
-        wcnt[e] = 0u;
-        return;
-    }
-    const uint32_t r = pairs[2u * pair0 + e];
-    const uint32_t len = r < n_rec ? recs[r].z : 0u;
-    ends[e] = r < n_rec ? r : 0u;
-    if (r >= n_rec) atomicMin(&st[B_BADCOUPLE], e >> 1);  // (never: the list holds records of this window)
-    if (len > VS_LEN_MASK) {
-        atomicMin(&st[B_TOO_LONG], e);
-        meta[e] = 0u;
-        wcnt[e] = 0u;
-        return;
-    }
-    meta[e] = len;
-    wcnt[e] = (len + 15u) >> 4;
-    atomicMax(&st[B_MAXLEN], len);
-}
-
-// VS_BAM_BY_NAME_KEEP: the ends of a singles block of waiting records [w0, w0 + n_reads) of the waiting list, the analogue of
-// k_single_ends (vs_reads.hip).  One thread per end (and one more for the closing word offset): even end e is record
-// wlist[w0 + e / 2] -- its length is l_seq, 0 included; odd ends are absent: no length, no words, VS_FLAG_ABSENT.
-__global__ void __launch_bounds__(BAM_TPB) k_bam_single_ends(const uint4 *__restrict__ recs, const uint32_t *__restrict__ wlist, uint32_t w0, uint32_t n_reads,
-                                                             uint32_t n_rec, uint32_t *__restrict__ meta, uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
-    const uint32_t e = blockIdx.x * BAM_TPB + threadIdx.x, n_ends = 2u * n_reads;
-    if (e > n_ends) return;
-    if (e == n_ends) {
-        wcnt[e] = 0u;
-        return;
-    }
-    if (e & 1u) {
-        meta[e] = VS_FLAG_ABSENT << 24;
-        wcnt[e] = 0u;
-        return;
-    }
-    const uint32_t r = wlist[w0 + (e >> 1)];
-    const uint32_t len = r < n_rec ? recs[r].z : 0u;
-    if (r >= n_rec) atomicMin(&st[B_BADCOUPLE], e >> 1);  // (never: the list holds records of this window)
-    if (len > VS_LEN_MASK) {
-        atomicMin(&st[B_TOO_LONG], e);
-        meta[e] = 0u;
-        wcnt[e] = 0u;
-        return;
-    }
-    meta[e] = len;
-    wcnt[e] = (len + 15u) >> 4;
-    atomicMax(&st[B_MAXLEN], len);
-}
-
 // ---- the chain on a device window ---------------------------------------------------------------------------------------
 namespace {
 
@@ -512,7 +439,7 @@ int bam_scan_device(vs_ctx *ctx, hipStream_t st, const uint8_t *win, uint64_t n,
     sc.stop = (uint32_t)n;
     sc.malformed = BAM_NONE;
     VS_HIP(ctx, hipMemsetAsync(d_stat, 0, sizeof(uint32_t) * B_BAD_MEMBER, st));
-    VS_HIP(ctx, hipMemsetAsync(d_stat + B_MALFORMED, 0xFF, sizeof(uint32_t) * 2, st));
+    VS_HIP(ctx, hipMemsetAsync(d_stat + B_MALFORMED, 0xFF, sizeof(uint32_t), st));
     if (n_seg) {
         if (int rc = reserve_n<uint16_t>(ctx, sc.tab, n)) return rc;
         if (int rc = reserve_n<uint32_t>(ctx, sc.entry, n_seg)) return rc;
@@ -553,10 +480,11 @@ int bam_scan_device(vs_ctx *ctx, hipStream_t st, const uint8_t *win, uint64_t n,
     return VS_OK;
 }
 
-// the ends of couples [part0 / 2, part0 / 2 + n_pairs) of a scanned window: ends, lengths (meta), words per end (wcnt)
-void launch_ends(hipStream_t st, const BamScan &sc, uint32_t part0, uint32_t n_pairs, uint32_t *ends, uint32_t *meta, uint32_t *wcnt, uint32_t *d_stat) {
-    hipLaunchKernelGGL(k_bam_ends, dim3((2u * n_pairs + 1u + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, st, sc.recs.as<const uint4>(),
-                       sc.part.as<const uint32_t>(), part0, n_pairs, sc.n_rec, sc.stop, ends, meta, wcnt, d_stat);
+// couples [part0 / 2, part0 / 2 + n_pairs) of a scanned window: the record of every end (ends), d_stat[B_BADCOUPLE] (~0u before),
+// d_stat[B_CUT] and [B_CUTREC]
+void launch_ends(hipStream_t st, const BamScan &sc, uint32_t part0, uint32_t n_pairs, uint32_t *ends, uint32_t *d_stat) {
+    hipLaunchKernelGGL(k_bam_couples, dim3((n_pairs + BAM_TPB - 1u) / BAM_TPB), dim3(BAM_TPB), 0, st, sc.recs.as<const uint4>(), sc.part.as<const uint32_t>(),
+                       part0, n_pairs, sc.n_rec, sc.stop, ends, d_stat);
 }
 
 // the match of a scanned window
@@ -657,7 +585,7 @@ void fill_info(uint64_t info[6], uint64_t n_rec, uint64_t n_part, uint32_t end, 
 }  // namespace
 
 // ---- the stream ------------------------------------------------------------------------------------------------------------
-struct vs_bam_stream {
+struct vs_bam_stream : StreamState {  // (B_ALL status words)
     int device = 0;
     hipStream_t st = nullptr;
     Reader rd;
@@ -669,13 +597,8 @@ struct vs_bam_stream {
     bool scanned = false;
     uint32_t rec_cur = 0, part_cur = 0;  // the first record / compacted record of the scanned window not yet delivered
     uint64_t first_record = 0;           // file-wide number of the window's record 0
-    VsDevBuf stat_buf, d_wcnt, d_ends;
-    VsPinnedBuf h_stat_buf;
-    uint32_t *d_stat = nullptr, *h_stat = nullptr;
+    VsDevBuf d_wcnt, d_ends;
     uint64_t pairs = 0;
-    bool done = false;
-    int failed = VS_OK;
-    std::string failed_msg;
     // by name
     bool by_name = false;
     uint32_t name_bits = 64;
@@ -698,13 +621,6 @@ struct vs_bam_stream {
 };
 
 namespace {
-
-int bam_fail(vs_ctx *ctx, vs_bam_stream *s, int code, const std::string &msg) {
-    s->done = true;
-    s->failed = code;
-    s->failed_msg = msg;
-    return vs_fail(ctx, code, "%s", msg.c_str());
-}
 
 // (rec: index in the window; the records carried in front of the new ones have been numbered before)
 std::string rec_msg(const vs_bam_stream *s, uint64_t rec, const char *what) {
@@ -853,23 +769,23 @@ int bam_carry_waiting(vs_ctx *ctx, vs_bam_stream *s) {
 
 // the end of the input: what is left in the window is passed, and said if it is no whole couple
 int bam_finish(vs_ctx *ctx, vs_bam_stream *s) {
-    if (s->rd.err != VS_OK) return bam_fail(ctx, s, s->rd.err, s->rd.err_msg);
+    if (s->rd.err != VS_OK) return s->fail(ctx, s->rd.err, s->rd.err_msg);
     uint32_t odd = BAM_NONE;
     if (s->scanned && s->by_name) {  // (its records are counted already; what still waits has no mate in the file)
         VS_HIP(ctx, hipStreamSynchronize(s->st));
-        if (s->sc.end == BAM_END_CUT) return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->sc.n_rec, ": truncated record (the file ends inside it)"));
+        if (s->sc.end == BAM_END_CUT) return s->fail(ctx, VS_E_ARG, rec_msg(s, s->sc.n_rec, ": truncated record (the file ends inside it)"));
         s->singletons += s->mt.n_wait;
     } else if (s->scanned) {
         if (s->sc.n_part - s->part_cur == 1u)
             VS_HIP(ctx, hipMemcpyAsync(&odd, s->sc.part.as<uint32_t>() + s->part_cur, sizeof odd, hipMemcpyDeviceToHost, s->st));
-        if (int rc = bam_pass(ctx, s, s->sc.n_rec)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = bam_pass(ctx, s, s->sc.n_rec)) return s->fail(ctx, rc, vs_last_error(ctx));
         VS_HIP(ctx, hipStreamSynchronize(s->st));
         if (s->sc.end == BAM_END_CUT)
-            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, s->sc.n_rec, ": truncated record (the file ends inside it)"));
+            return s->fail(ctx, VS_E_ARG, rec_msg(s, s->sc.n_rec, ": truncated record (the file ends inside it)"));
         if (odd != BAM_NONE)
-            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, odd, " has no mate behind it") + NOT_COLLATED);
+            return s->fail(ctx, VS_E_ARG, rec_msg(s, odd, " has no mate behind it") + NOT_COLLATED);
     } else if (s->skip) {
-        return bam_fail(ctx, s, VS_E_STATE, s->rd.path + " ends inside its header (did it change after it was opened?)");
+        return s->fail(ctx, VS_E_STATE, s->rd.path + " ends inside its header (did it change after it was opened?)");
     }
     s->done = true;
     return VS_OK;
@@ -878,51 +794,17 @@ int bam_finish(vs_ctx *ctx, vs_bam_stream *s) {
 // VS_BAM_BY_NAME_KEEP, the input is at its end and its pairs are out: a singles block of up to max_reads of the records that
 // still wait (mt.wlist of the last window, window order = file order), from the cursor
 int bam_singles_block(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_reads, vs_reads **out, uint64_t *n_slots) {
-    hipStream_t st = s->st;
-    const BamScan &sc = s->sc;
-    const uint64_t n = std::min<uint64_t>(s->mt.n_wait - s->single_cur, max_reads), n_ends = 2u * n;
-    if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
-    vs_reads *r = new vs_reads();
-    r->cached = true;
-    r->unpaired = true;
-    auto fail = [&](hipError_t e) {
-        vs_reads_free(ctx, r);
-        if (e == hipErrorOutOfMemory) return bam_fail(ctx, s, VS_E_OOM, "vs_bam_stream_next: device buffers for the block");
-        return bam_fail(ctx, s, VS_E_HIP, std::string("vs_bam_stream_next: ") + hipGetErrorString(e));
-    };
-    hipError_t e1 = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true);
-    if (e1 != hipSuccess) return fail(e1);
-    e1 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0, sizeof(uint32_t) * (B_BAD_MEMBER - B_BADCOUPLE), st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0xFF, sizeof(uint32_t), st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_TOO_LONG, 0xFF, sizeof(uint32_t), st);
-    if (e1 != hipSuccess) return fail(e1);
-    hipLaunchKernelGGL(k_bam_single_ends, dim3((unsigned)((n_ends + 1u + BAM_TPB - 1u) / BAM_TPB)), dim3(BAM_TPB), 0, st, sc.recs.as<const uint4>(),
-                       s->mt.wlist.as<const uint32_t>(), s->single_cur, (uint32_t)n, sc.n_rec, (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    vs_launch_scan_u32(st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + B_WORDS);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat + B_BADCOUPLE, s->d_stat + B_BADCOUPLE, sizeof(uint32_t) * (B_BAD_MEMBER - B_BADCOUPLE), hipMemcpyDeviceToHost, st);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-    if (e1 != hipSuccess) return fail(e1);
-    if (s->h_stat[B_BADCOUPLE] != BAM_NONE) {
-        vs_reads_free(ctx, r);
-        return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": the waiting list of the name match names a record beyond the window's");
+    const uint64_t n = std::min<uint64_t>(s->mt.n_wait - s->single_cur, max_reads);
+    const uint32_t *list = s->mt.wlist.as<const uint32_t>() + s->single_cur;
+    const VsBlockJob job = {ctx, s->st, 2u * n, &s->d_wcnt, s->d_stat + B_BLOCK, s->h_stat + B_BLOCK, VS_BLK_ST, false};
+    vs_reads *r = nullptr;
+    const hipError_t e1 = vs_block_bam_singles(job, BamSingles{s->w.data(), (const uint32_t *)s->sc.recs.as<uint4>(), list, s->sc.n_rec}, &r);
+    if (e1 != hipSuccess) return s->fail_hip(ctx, "vs_bam_stream_next", e1);
+    if (!r) {
+        const uint32_t bad = s->h_stat[B_BLOCK + VS_BLK_BAD];
+        if (!(bad & VS_BLK_OVER)) return s->fail(ctx, VS_E_STATE, s->rd.path + ": the waiting list of the name match names a record beyond the window's");
+        return s->fail(ctx, VS_E_RANGE, rec_msg(s, fetch_u32(list + ((bad & ~VS_BLK_OVER) >> 1)), " has a sequence of more than ") + std::to_string((unsigned)VS_LEN_MASK) + " bases");
     }
-    if (s->h_stat[B_TOO_LONG] != BAM_NONE) {
-        uint32_t rec = 0;
-        e1 = hipMemcpy(&rec, s->mt.wlist.as<uint32_t>() + s->single_cur + (s->h_stat[B_TOO_LONG] >> 1), sizeof rec, hipMemcpyDeviceToHost);
-        if (e1 != hipSuccess) return fail(e1);
-        vs_reads_free(ctx, r);
-        return bam_fail(ctx, s, VS_E_RANGE, rec_msg(s, rec, " has a sequence of more than ") + std::to_string((unsigned)VS_LEN_MASK) + " bases");
-    }
-    const uint64_t words = s->h_stat[B_WORDS];
-    r->max_len = s->h_stat[B_MAXLEN];
-    if ((e1 = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e1);
-    vs_launch_pack_bam_singles(st, BamSingles{s->w.data(), (const uint32_t *)sc.recs.as<uint4>(), s->mt.wlist.as<const uint32_t>() + s->single_cur, sc.n_rec}, r);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + B_INVALID, s->h_stat + B_INVALID)) != hipSuccess) return fail(e1);
-    if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
     s->single_cur += (uint32_t)n;
     *out = r;
     *n_slots = n;
@@ -1050,17 +932,12 @@ static int bam_open(vs_ctx *ctx, const char *path, int mode, const uint64_t *ran
         return rc;
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
-    if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * B_ALL);
-    s->d_stat = s->stat_buf.as<uint32_t>();
-    if (e1 == hipSuccess) e1 = hipMemset(s->d_stat, 0, sizeof(uint32_t) * B_ALL);
+    if (e1 == hipSuccess) e1 = s->reserve_stat(B_ALL);
     if (e1 == hipSuccess) e1 = hipMemset(s->d_stat + B_BAD_MEMBER, 0xFF, sizeof(uint32_t));
-    if (e1 == hipSuccess) e1 = s->h_stat_buf.reserve(sizeof(uint32_t) * B_ALL);
-    s->h_stat = s->h_stat_buf.as<uint32_t>();
     if (e1 != hipSuccess) {
         vs_bam_stream_close(s);
         return vs_fail(ctx, VS_E_HIP, "vs_bam_stream_open: %s", hipGetErrorString(e1));
     }
-    memset(s->h_stat, 0, sizeof(uint32_t) * B_ALL);
     r.th = std::thread([rp = &s->rd] { rp->run(); });
     *out = s;
     return VS_OK;
@@ -1070,7 +947,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
     if (!ctx || !s || !out || !n_pairs) return vs_fail(ctx, VS_E_ARG, "vs_bam_stream_next: bad argument");
     *out = nullptr;
     *n_pairs = 0;
-    if (s->failed != VS_OK) return vs_fail(ctx, s->failed, "%s", s->failed_msg.c_str());
+    if (s->failed != VS_OK) return s->again(ctx);
     if (s->done) return VS_OK;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     if (!max_pairs || max_pairs > (1ull << 30)) max_pairs = 1ull << 30;
@@ -1082,7 +959,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
             if (s->ranged && s->own_end != ~0ull && s->own_part <= s->part_cur &&
                 (s->own_end > s->win_base ? s->own_end - s->win_base : 0u) <= (uint64_t)sc.stop) {
                 // a member range: the next record starts at or behind own_end, so every owned couple is out
-                if (int rc = bam_pass(ctx, s, sc.n_rec)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+                if (int rc = bam_pass(ctx, s, sc.n_rec)) return s->fail(ctx, rc, vs_last_error(ctx));
                 VS_HIP(ctx, hipStreamSynchronize(st));
                 s->done = true;
                 return VS_OK;
@@ -1091,7 +968,7 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
                 return bam_singles_block(ctx, s, max_pairs, out, n_pairs);  // (what bam_finish would refuse comes first, there)
             if (s->eof) return bam_finish(ctx, s);
             if (s->by_name) {
-                if (int rc = bam_carry_waiting(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+                if (int rc = bam_carry_waiting(ctx, s)) return s->fail(ctx, rc, vs_last_error(ctx));
             } else {
                 // the carry: everything from the first record not delivered
                 uint32_t cut = sc.stop;
@@ -1099,18 +976,18 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
                     VS_HIP(ctx, hipMemcpyAsync(&cut, (const uint32_t *)(sc.recs.as<uint4>() + s->rec_cur), sizeof cut, hipMemcpyDeviceToHost, st));
                     VS_HIP(ctx, hipStreamSynchronize(st));
                 }
-                if (cut > s->w.size) return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": a record start beyond the window");
-                if (int rc = bam_drop_front(ctx, s, cut)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+                if (cut > s->w.size) return s->fail(ctx, VS_E_STATE, s->rd.path + ": a record start beyond the window");
+                if (int rc = bam_drop_front(ctx, s, cut)) return s->fail(ctx, rc, vs_last_error(ctx));
                 s->first_record += s->rec_cur;
             }
             s->rec_cur = s->part_cur = s->pair_cur = s->single_cur = 0;
             s->scanned = false;
         }
         if (!s->eof) {
-            if (int rc = s->ranged ? bam_append_ranged(ctx, s) : bam_append(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = s->ranged ? bam_append_ranged(ctx, s) : bam_append(ctx, s)) return s->fail(ctx, rc, vs_last_error(ctx));
             if (s->skip) {  // the header goes, whole windows of it if need be
                 const size_t now = (size_t)std::min<uint64_t>(s->skip, s->w.size);
-                if (int rc = bam_drop_front(ctx, s, now)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+                if (int rc = bam_drop_front(ctx, s, now)) return s->fail(ctx, rc, vs_last_error(ctx));
                 s->skip -= now;
                 if (s->skip) {
                     if (s->eof) return bam_finish(ctx, s);
@@ -1119,82 +996,63 @@ int vs_bam_stream_next(vs_ctx *ctx, vs_bam_stream *s, uint64_t max_pairs, vs_rea
             }
         }
         if (int rc = bam_scan_device(ctx, st, s->w.data(), s->w.size, 0, s->seg, sc, s->d_stat, s->h_stat))
-            return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            return s->fail(ctx, rc, vs_last_error(ctx));
         s->scanned = true;
         if (s->h_stat[B_BAD_MEMBER] != BAM_NONE)
-            return bam_fail(ctx, s, VS_E_ARG, s->rd.path + ": not a complete gzip stream (BGZF member " + std::to_string(s->h_stat[B_BAD_MEMBER]) +
+            return s->fail(ctx, VS_E_ARG, s->rd.path + ": not a complete gzip stream (BGZF member " + std::to_string(s->h_stat[B_BAD_MEMBER]) +
                                                   " does not inflate to its CRC32 and size)");
         if (sc.malformed != BAM_NONE)
-            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, sc.malformed, " is malformed: its name, cigar, sequence and quality need more than its block_size"));
+            return s->fail(ctx, VS_E_ARG, rec_msg(s, sc.malformed, " is malformed: its name, cigar, sequence and quality need more than its block_size"));
         if (sc.end == BAM_END_DEAD)
-            return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, sc.n_rec, " is malformed: its block_size is below the 32 bytes of the fixed part"));
+            return s->fail(ctx, VS_E_ARG, rec_msg(s, sc.n_rec, " is malformed: its block_size is below the 32 bytes of the fixed part"));
         if (s->ranged)
-            if (int rc = bam_owned(ctx, s)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = bam_owned(ctx, s)) return s->fail(ctx, rc, vs_last_error(ctx));
         if (s->by_name) {
             s->windows++;
             s->pair_cur = 0;
-            if (int rc = bam_match_device(ctx, st, s->w.data(), s->w.size, sc, s->name_bits, s->mt)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = bam_match_device(ctx, st, s->w.data(), s->w.size, sc, s->name_bits, s->mt)) return s->fail(ctx, rc, vs_last_error(ctx));
             if (s->mt.crowded != BAM_NONE)
-                return bam_fail(ctx, s, VS_E_RANGE, rec_msg(s, s->mt.crowded, " is one of more than 64 records of one name and one end (first or second) in a window: mates "
+                return s->fail(ctx, VS_E_RANGE, rec_msg(s, s->mt.crowded, " is one of more than 64 records of one name and one end (first or second) in a window: mates "
                                                                               "are matched by name among at most 64 such records; run `samtools collate` on the file first"));
             s->rec_cur = std::min(s->n_carried, sc.n_rec);  // (the carried records were counted in their own windows)
-            if (int rc = bam_pass(ctx, s, sc.n_rec)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = bam_pass(ctx, s, sc.n_rec)) return s->fail(ctx, rc, vs_last_error(ctx));
         }
     }
     // ---- the block of n couples from the cursor
     const uint64_t n = std::min<uint64_t>(s->by_name ? s->mt.n_pairs - s->pair_cur : bam_ready(s), max_pairs), n_ends = 2u * n;
-    if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
-    if (int rc = reserve_n<uint32_t>(ctx, s->d_ends, n_ends + 1u)) return bam_fail(ctx, s, rc, vs_last_error(ctx));
-    vs_reads *r = new vs_reads();
-    r->cached = true;
-    auto fail = [&](hipError_t e, const char *oom_msg = nullptr) {
-        vs_reads_free(ctx, r);
-        if (e == hipErrorOutOfMemory && oom_msg) return bam_fail(ctx, s, VS_E_OOM, oom_msg);
-        return bam_fail(ctx, s, e == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, std::string("vs_bam_stream_next: ") + hipGetErrorString(e));
-    };
-    const char *no_buffers = "vs_bam_stream_next: device buffers for the block";
-    hipError_t e1 = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true);
-    if (e1 != hipSuccess) return fail(e1, no_buffers);
-    e1 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0, sizeof(uint32_t) * (B_BAD_MEMBER - B_BADCOUPLE), st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0xFF, sizeof(uint32_t), st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + B_TOO_LONG, 0xFF, sizeof(uint32_t), st);
-    if (e1 != hipSuccess) return fail(e1);
-    if (s->by_name)
-        hipLaunchKernelGGL(k_bam_ends_list, dim3((unsigned)((n_ends + 1u + BAM_TPB - 1u) / BAM_TPB)), dim3(BAM_TPB), 0, st, sc.recs.as<const uint4>(),
-                           s->mt.pairs.as<const uint32_t>(), s->pair_cur, (uint32_t)n, sc.n_rec, s->d_ends.as<uint32_t>(), (uint32_t *)r->d_meta,
-                           s->d_wcnt.as<uint32_t>(), s->d_stat);
-    else launch_ends(st, sc, s->part_cur, (uint32_t)n, s->d_ends.as<uint32_t>(), (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    vs_launch_scan_u32(st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + B_WORDS);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * B_BAD_MEMBER, hipMemcpyDeviceToHost, st);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-    if (e1 != hipSuccess) return fail(e1);
-    if (s->h_stat[B_BADCOUPLE] != BAM_NONE && s->by_name) {
-        vs_reads_free(ctx, r);
-        return bam_fail(ctx, s, VS_E_STATE, s->rd.path + ": a pair of the name match names a record beyond the window's");
+    const uint32_t *ends = s->mt.pairs.as<const uint32_t>() + 2u * (size_t)s->pair_cur;  // by name: the pair list is (first, second), the ends as they come
+    if (!s->by_name) {
+        // collated: the couples checked, which record of each is which end, the cut -- three words that ride back with the builder's
+        if (int rc = reserve_n<uint32_t>(ctx, s->d_ends, n_ends + 1u)) return s->fail(ctx, rc, vs_last_error(ctx));
+        const hipError_t e0 = hipMemsetAsync(s->d_stat + B_BADCOUPLE, 0xFF, sizeof(uint32_t), st);
+        if (e0 != hipSuccess) return s->fail_hip(ctx, "vs_bam_stream_next", e0);
+        launch_ends(st, sc, s->part_cur, (uint32_t)n, s->d_ends.as<uint32_t>(), s->d_stat);
+        ends = s->d_ends.as<const uint32_t>();
     }
-    if (s->h_stat[B_BADCOUPLE] != BAM_NONE) {
-        uint32_t second = 0;
-        e1 = hipMemcpy(&second, sc.part.as<uint32_t>() + s->part_cur + 2u * s->h_stat[B_BADCOUPLE] + 1u, sizeof second, hipMemcpyDeviceToHost);
-        if (e1 != hipSuccess) return fail(e1);
+    // (collated: the records the block passes are tallied behind it, so the last wait is here)
+    const VsBlockJob job = {ctx, st, n_ends, &s->d_wcnt, s->d_stat + B_BLOCK, s->h_stat + B_BLOCK, (uint32_t)(s->by_name ? VS_BLK_ST : B_MALFORMED - B_BLOCK), !s->by_name};
+    vs_reads *r = nullptr;
+    hipError_t e1 = vs_block_bam(job, BamEnds{s->w.data(), (const uint32_t *)sc.recs.as<uint4>(), ends, sc.n_rec}, &r);
+    if (e1 != hipSuccess) return s->fail_hip(ctx, "vs_bam_stream_next", e1);
+    if (!s->by_name && s->h_stat[B_BADCOUPLE] != BAM_NONE) {
+        (void)hipStreamSynchronize(st);
         vs_reads_free(ctx, r);
-        return bam_fail(ctx, s, VS_E_ARG, rec_msg(s, second, " is the same end (first or second) of a pair as the record it is coupled with") + NOT_COLLATED);
+        const uint32_t second = fetch_u32(sc.part.as<uint32_t>() + s->part_cur + 2u * s->h_stat[B_BADCOUPLE] + 1u);
+        return s->fail(ctx, VS_E_ARG, rec_msg(s, second, " is the same end (first or second) of a pair as the record it is coupled with") + NOT_COLLATED);
     }
-    if (s->h_stat[B_TOO_LONG] != BAM_NONE) {
-        vs_reads_free(ctx, r);
-        return bam_fail(ctx, s, VS_E_RANGE, s->rd.path + ": pair " + std::to_string(s->pairs + (s->h_stat[B_TOO_LONG] >> 1)) + " has a sequence of more than " +
-                                                std::to_string((unsigned)VS_LEN_MASK) + " bases");
+    if (!r) {
+        const uint32_t bad = s->h_stat[B_BLOCK + VS_BLK_BAD];
+        if (!(bad & VS_BLK_OVER)) return s->fail(ctx, VS_E_STATE, s->rd.path + ": a pair of the name match names a record beyond the window's");
+        return s->fail(ctx, VS_E_RANGE, s->rd.path + ": pair " + std::to_string(s->pairs + ((bad & ~VS_BLK_OVER) >> 1)) + " has a sequence of more than " +
+                                            std::to_string((unsigned)VS_LEN_MASK) + " bases");
     }
-    const uint64_t words = s->h_stat[B_WORDS];
-    r->max_len = s->h_stat[B_MAXLEN];
-    if ((e1 = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e1, no_buffers);
-    vs_launch_pack_bam(st, BamEnds{s->w.data(), (const uint32_t *)sc.recs.as<uint4>(), s->d_ends.as<const uint32_t>()}, r);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + B_INVALID, s->h_stat + B_INVALID)) != hipSuccess) return fail(e1);
-    if (!s->by_name && bam_pass(ctx, s, s->h_stat[B_CUTREC]) != VS_OK) return fail(hipErrorUnknown);
-    if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
+    if (!s->by_name) {
+        e1 = bam_pass(ctx, s, s->h_stat[B_CUTREC]) == VS_OK ? hipStreamSynchronize(st) : hipErrorUnknown;  // (the block is complete when it is handed out)
+        if (e1 != hipSuccess) {
+            vs_reads_free(ctx, r);
+            return s->fail_hip(ctx, "vs_bam_stream_next", e1);
+        }
+    }
     if (s->by_name) s->pair_cur += (uint32_t)n;
     else s->part_cur += (uint32_t)n_ends;
     s->pairs += n;
@@ -1286,7 +1144,7 @@ int vs_bam_scan_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t ski
     VS_HIP(ctx, hipSetDevice(ctx->device));
     seg = seg_checked(seg);
     hipStream_t st = ctx->stream;
-    VsDevBuf win, stat, d_ends, d_meta, d_wcnt;
+    VsDevBuf win, stat, d_ends;
     BamScan sc;
     uint32_t hs[B_ALL] = {0};
     VS_HIP(ctx, win.reserve(((n + 15u) & ~(uint64_t)15u) + 16u));
@@ -1302,11 +1160,8 @@ int vs_bam_scan_text(vs_ctx *ctx, const uint8_t *bytes, uint64_t n, uint64_t ski
     }
     if (n_pairs) {
         VS_HIP(ctx, d_ends.reserve(sizeof(uint32_t) * (2u * (size_t)n_pairs + 1u)));
-        VS_HIP(ctx, d_meta.reserve(sizeof(uint32_t) * (2u * (size_t)n_pairs + 1u)));
-        VS_HIP(ctx, d_wcnt.reserve(sizeof(uint32_t) * (2u * (size_t)n_pairs + 1u)));
         VS_HIP(ctx, hipMemsetAsync(stat.as<uint32_t>() + B_BADCOUPLE, 0xFF, sizeof(uint32_t), st));
-        VS_HIP(ctx, hipMemsetAsync(stat.as<uint32_t>() + B_TOO_LONG, 0xFF, sizeof(uint32_t), st));
-        launch_ends(st, sc, 0, n_pairs, d_ends.as<uint32_t>(), d_meta.as<uint32_t>(), d_wcnt.as<uint32_t>(), stat.as<uint32_t>());
+        launch_ends(st, sc, 0, n_pairs, d_ends.as<uint32_t>(), stat.as<uint32_t>());
         VS_HIP(ctx, hipGetLastError());
         VS_HIP(ctx, hipMemcpyAsync(hs, stat.ptr(), sizeof(uint32_t) * B_ALL, hipMemcpyDeviceToHost, st));
         VS_HIP(ctx, hipStreamSynchronize(st));

@@ -20,11 +20,11 @@
 // The last complete record of a window that is not the second of a pair waits for its successor (or the end of the file): it
 // is held back, unclassified, and leads the next window.  The cut falls behind a consumed record, so the next window starts
 // the greedy rule afresh; no parity crosses a cut.
-// A block of n pairs from the cursor: k_il_ends (lengths and word counts of the ends rec[2 cursor ...]), k_sl_scan (word
-// offsets), k_pack_reads<PackRecords>, vs_reads_finish -- the layout vs_pe_count takes.
+// A block of n pairs from the cursor is cut by the block builder (vs_block_records, vs_reads.hip) from the ends rec[2 cursor ...]
+// -- the layout vs_pe_count takes.
 // Mode VS_IL_KEEP keeps the single records instead of dropping them: after the window's pairs are listed, k_il_singles_count /
 // k_sl_scan / k_il_singles_emit compact the records of class single, in file order, into srec[]; when the pairs of the window
-// are out they are handed out as SINGLES blocks (vs_reads_singles_block, vs_reads.hip), before the window is cut.  The held-back
+// are out they are handed out as SINGLES blocks (vs_block_singles, the same builder), before the window is cut.  The held-back
 // record stays held; at the end of the file it is a single like any other.
 // The host reads back counts, the cut and status words; no record text, except the two header lines of the message with
 // which the strict mode refuses a single record.
@@ -56,7 +56,7 @@ namespace {
 // status words of a stream (the first ST_PER_FILE are the line scanner's)
 enum {
     IS_PAIRS = 4, IS_SINGLES = 5, IS_FIRST_SINGLE = 6 /* IL_NONE: none (atomicMin) */, IS_HELD = 7,
-    IS_MAXLEN = 8, IS_TOO_LONG = 9, IS_WORDS = 10, IS_INVALID = 11,
+    IS_BLOCK = 8,    // the VS_BLK_ST words of the block builder
     IS_WINDOW = 12,  // (words below it are rewritten for every window or block)
     IS_BAD = 12,     // the first BGZF member the device rejected (a running index), ~0u: none
     IS_ALL = 16
@@ -204,29 +204,6 @@ __global__ void __launch_bounds__(IL_TPB) k_il_singles_emit(const uint8_t *__res
     srec[q] = i;
 }
 
-// one thread per end of the block (and one more for the closing word offset): end e is the sequence line of record rec[e];
-// length, packed words, the longest end, the first end over the 24-bit limit
-__global__ void __launch_bounds__(IL_TPB) k_il_ends(SlWin w, const uint32_t *__restrict__ rec, uint32_t n_ends, uint32_t *__restrict__ meta,
-                                                    uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
-    const uint32_t e = blockIdx.x * IL_TPB + threadIdx.x;
-    if (e > n_ends) return;
-    if (e == n_ends) {
-        wcnt[e] = 0u;
-        return;
-    }
-    const uint32_t r = rec[e];
-    const uint32_t start = w.ends[4u * r] + 1u, len = w.ends[4u * r + 1u] - start;  // (the character dropped is the newline)
-    if (len > VS_LEN_MASK) {
-        atomicMin(&st[IS_TOO_LONG], e);
-        meta[e] = 0u;
-        wcnt[e] = 0u;
-        return;
-    }
-    meta[e] = len;
-    wcnt[e] = (len + 15u) >> 4;
-    atomicMax(&st[IS_MAXLEN], len);
-}
-
 // ---- the match of one window ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -240,7 +217,7 @@ struct IlMatch {
 };
 
 // Records [0, n_rec) of the window (txt, its line ends scattered) classified: counts into mt (synchronises the stream).
-// d_stat / h_stat: IS_ALL status words, [IS_PAIRS, IS_MAXLEN) rewritten.
+// d_stat / h_stat: IS_ALL status words, [IS_PAIRS, IS_BLOCK) rewritten.
 int il_classify_device(vs_ctx *ctx, hipStream_t st, const uint8_t *txt, const uint32_t *ends, uint32_t n_rec, bool eof, IlMatch &mt, uint32_t *d_stat,
                        uint32_t *h_stat) {
     const uint32_t wgs = (n_rec + IL_TPB - 1u) / IL_TPB;
@@ -253,7 +230,7 @@ int il_classify_device(vs_ctx *ctx, hipStream_t st, const uint8_t *txt, const ui
     if (int rc = reserve_n<uint8_t>(ctx, mt.cls, n_rec)) return rc;
     if (int rc = reserve_n<uint32_t>(ctx, mt.wgfn, wgs)) return rc;
     if (int rc = reserve_n<uint32_t>(ctx, mt.wg_first, (size_t)wgs + 1u)) return rc;
-    VS_HIP(ctx, hipMemsetAsync(d_stat + IS_PAIRS, 0, sizeof(uint32_t) * (IS_MAXLEN - IS_PAIRS), st));
+    VS_HIP(ctx, hipMemsetAsync(d_stat + IS_PAIRS, 0, sizeof(uint32_t) * (IS_BLOCK - IS_PAIRS), st));
     VS_HIP(ctx, hipMemsetAsync(d_stat + IS_FIRST_SINGLE, 0xFF, sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_il_match, dim3(wgs), dim3(IL_TPB), 0, st, IlWin{txt, ends, n_rec}, mt.m.as<uint8_t>(), mt.wgfn.as<uint32_t>());
     hipLaunchKernelGGL(k_il_carry, dim3(1), dim3(IL_CARRY_TPB), 0, st, mt.wgfn.as<uint32_t>(), wgs);
@@ -262,7 +239,7 @@ int il_classify_device(vs_ctx *ctx, hipStream_t st, const uint8_t *txt, const ui
     VS_HIP(ctx, hipGetLastError());
     vs_launch_scan_u32(st, mt.wg_first.as<uint32_t>(), wgs, d_stat + IS_PAIRS);
     VS_HIP(ctx, hipGetLastError());
-    VS_HIP(ctx, hipMemcpyAsync(h_stat + IS_PAIRS, d_stat + IS_PAIRS, sizeof(uint32_t) * (IS_MAXLEN - IS_PAIRS), hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipMemcpyAsync(h_stat + IS_PAIRS, d_stat + IS_PAIRS, sizeof(uint32_t) * (IS_BLOCK - IS_PAIRS), hipMemcpyDeviceToHost, st));
     VS_HIP(ctx, hipStreamSynchronize(st));
     mt.n_pairs = h_stat[IS_PAIRS];
     mt.singles = h_stat[IS_SINGLES];
@@ -309,7 +286,7 @@ void il_mates_info(uint64_t info[6], uint64_t pairs, uint64_t singles, uint64_t 
 }  // namespace
 
 // ---- the stream ------------------------------------------------------------------------------------------------------------
-struct vs_fastq_il {
+struct vs_fastq_il : StreamState {  // (IS_ALL status words)
     int device = 0;
     hipStream_t st = nullptr;
     Reader rd;
@@ -320,9 +297,7 @@ struct vs_fastq_il {
     uint32_t single_cur = 0;  // VS_IL_KEEP: the first single record of the matched window not yet delivered
     bool singles_ok = false;
     bool keep = false;  // VS_IL_KEEP: the single records are handed out as singles blocks
-    VsDevBuf stat_buf, d_wcnt;
-    VsPinnedBuf h_stat_buf;
-    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // IS_ALL words each
+    VsDevBuf d_wcnt;
     uint64_t pairs = 0, singles = 0, records = 0;
     uint32_t flags_seen = 0;
     // a member range (vs_fastq_il_open_range): records of the range not yet decided; the last of them is the next rank's
@@ -330,19 +305,9 @@ struct vs_fastq_il {
     // window that holds the range's last record has been matched
     bool ranged = false, lookahead = false, entry_pending = false, range_done = false;
     uint64_t remain = 0;
-    bool done = false;
-    int failed = VS_OK;
-    std::string failed_msg;
 };
 
 namespace {
-
-int il_fail(vs_ctx *ctx, vs_fastq_il *s, int code, const std::string &msg) {
-    s->done = true;
-    s->failed = code;
-    s->failed_msg = msg;
-    return vs_fail(ctx, code, "%s", msg.c_str());
-}
 
 // count + scan of the window: its line ends counted, flags, records (synchronises the stream)
 int il_scan(vs_ctx *ctx, vs_fastq_il *s) {
@@ -373,7 +338,7 @@ std::string il_header_line(vs_fastq_il *s, uint32_t r) {
 
 // the end of the input: the reader's failure, if it had one
 int il_finish(vs_ctx *ctx, vs_fastq_il *s) {
-    if (s->rd.err != VS_OK) return il_fail(ctx, s, s->rd.err, s->rd.err_msg);
+    if (s->rd.err != VS_OK) return s->fail(ctx, s->rd.err, s->rd.err_msg);
     s->done = true;
     return VS_OK;
 }
@@ -427,32 +392,32 @@ int il_next_window(vs_ctx *ctx, vs_fastq_il *s, bool *end) {
             VS_HIP(ctx, hipMemcpyAsync(&at, d.ends.as<uint32_t>() + (4u * (size_t)s->mt.decided - 1u), sizeof at, hipMemcpyDeviceToHost, st));
             VS_HIP(ctx, hipStreamSynchronize(st));
             cut = (size_t)at + 1u;
-            if (cut > d.w.size) return il_fail(ctx, s, VS_E_STATE, s->rd.path + ": a line end beyond the window");
+            if (cut > d.w.size) return s->fail(ctx, VS_E_STATE, s->rd.path + ": a line end beyond the window");
         }
-        if (int rc = drop_front(ctx, st, d, cut, s->mt.decided)) return il_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = drop_front(ctx, st, d, cut, s->mt.decided)) return s->fail(ctx, rc, vs_last_error(ctx));
         s->matched = false;
         s->pair_cur = 0;
         s->single_cur = 0;
     }
     for (;;) {
-        if (int rc = il_append(ctx, s)) return il_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = il_append(ctx, s)) return s->fail(ctx, rc, vs_last_error(ctx));
         if (d.err == VS_OK && d.flags && d.validated < d.w.size) {  // (text that arrived with this slot: host text mode)
             if (translate_window(ctx, d, s->rd.path) == VS_OK)
-                if (int rc = il_scan(ctx, s)) return il_fail(ctx, s, rc, vs_last_error(ctx));
+                if (int rc = il_scan(ctx, s)) return s->fail(ctx, rc, vs_last_error(ctx));
         }
-        if (d.err != VS_OK) return il_fail(ctx, s, s->rd.err != VS_OK ? s->rd.err : d.err, s->rd.err != VS_OK ? s->rd.err_msg : d.err_msg);
+        if (d.err != VS_OK) return s->fail(ctx, s->rd.err != VS_OK ? s->rd.err : d.err, s->rd.err != VS_OK ? s->rd.err_msg : d.err_msg);
         if (!s->entry_pending) break;
         // the range's first record is the SECOND of the previous rank's last pair: it goes as soon as it is whole, uncounted,
         // and the record behind the second of a pair starts with parity 0 like a file's first
         if (d.records) {
             int rc = il_drop_lines(ctx, s, 4u, 1u);
             if (rc == VS_OK) rc = il_scan(ctx, s);
-            if (rc) return il_fail(ctx, s, rc, vs_last_error(ctx));
+            if (rc) return s->fail(ctx, rc, vs_last_error(ctx));
             s->entry_pending = false;
             s->remain--;
             break;
         }
-        if (d.eof) return il_fail(ctx, s, VS_E_STATE, s->rd.path + ": fewer records in its member range than were counted");
+        if (d.eof) return s->fail(ctx, VS_E_STATE, s->rd.path + ": fewer records in its member range than were counted");
     }
     uint32_t n_rec = (uint32_t)d.records;
     bool eof = d.eof;
@@ -462,26 +427,26 @@ int il_next_window(vs_ctx *ctx, vs_fastq_il *s, bool *end) {
             eof = !s->lookahead;  // (a look-ahead record is held back unless it completes this rank's last pair)
             s->range_done = true;
         } else if (d.eof) {
-            return il_fail(ctx, s, VS_E_STATE, s->rd.path + ": fewer records in its member range than were counted");
+            return s->fail(ctx, VS_E_STATE, s->rd.path + ": fewer records in its member range than were counted");
         }
     }
-    if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return il_fail(ctx, s, rc, vs_last_error(ctx));
+    if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return s->fail(ctx, rc, vs_last_error(ctx));
     vs_launch_sl_scatter(st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
     if (int rc = il_classify_device(ctx, st, d.w.data(), d.ends.as<const uint32_t>(), n_rec, eof, s->mt, s->d_stat, s->h_stat))
-        return il_fail(ctx, s, rc, vs_last_error(ctx));
+        return s->fail(ctx, rc, vs_last_error(ctx));
     s->matched = true;
     if (!s->singles_ok && s->mt.first_single != IL_NONE) {
         const uint32_t r = s->mt.first_single;
         const std::string next = r + 1u < s->mt.n_rec ? "\"" + il_header_line(s, r + 1u) + "\"" : std::string("end of file");
-        return il_fail(ctx, s, VS_E_ARG,
+        return s->fail(ctx, VS_E_ARG,
                        s->rd.path + ": record " + std::to_string(d.first_record + r) + " (\"" + il_header_line(s, r) + "\") has no mate beside it: what follows it is " +
                            next + ".  An interleaved FASTQ holds the two records of a pair one behind the other under one name; to drop and count "
                                   "single records, add --interleaved-singles");
     }
-    if (int rc = reserve_n<uint32_t>(ctx, s->mt.rec, 2u * (size_t)s->mt.n_pairs + 1u)) return il_fail(ctx, s, rc, vs_last_error(ctx));
-    if (int rc = il_emit_device(ctx, st, s->mt, s->mt.rec.as<uint32_t>())) return il_fail(ctx, s, rc, vs_last_error(ctx));
+    if (int rc = reserve_n<uint32_t>(ctx, s->mt.rec, 2u * (size_t)s->mt.n_pairs + 1u)) return s->fail(ctx, rc, vs_last_error(ctx));
+    if (int rc = il_emit_device(ctx, st, s->mt, s->mt.rec.as<uint32_t>())) return s->fail(ctx, rc, vs_last_error(ctx));
     if (s->keep)
-        if (int rc = il_emit_singles_device(ctx, st, s->mt, s->d_stat + IS_WORDS)) return il_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = il_emit_singles_device(ctx, st, s->mt, s->d_stat + IS_BLOCK + VS_BLK_WORDS)) return s->fail(ctx, rc, vs_last_error(ctx));
     s->records += s->mt.decided;
     s->singles += s->mt.singles;
     if (s->ranged) s->remain -= s->mt.decided;
@@ -499,9 +464,7 @@ int il_open(vs_ctx *ctx, const char *path, int mode, const uint64_t *range, bool
     s->singles_ok = mode != VS_IL_STRICT;
     s->keep = mode == VS_IL_KEEP;
     Reader &r = s->rd;
-    if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
-    if (const char *ev = getenv("VS_GZIP_DEVICE")) r.gzip_device = !range && strcmp(ev, "1") == 0;  // (a member range is BGZF's)
-    if (const char *ev = getenv("VS_GZIP_TEXT")) s->df.w.gz.text_cap = (uint32_t)std::max<long long>(1, atoll(ev));  // (tests only, as VS_STREAM_CHUNK)
+    fastq_switches(r, range != nullptr, s->df.w.gz.text_cap);
     int rc = r.open_file(ctx, path);
     struct stat sb;
     if (rc == VS_OK && range && (fstat(r.fd, &sb) != 0 || !S_ISREG(sb.st_mode) || range[0] > range[1] || range[1] > (uint64_t)sb.st_size))
@@ -521,12 +484,8 @@ int il_open(vs_ctx *ctx, const char *path, int mode, const uint64_t *range, bool
         s->df.to_file_end = r.end == (uint64_t)sb.st_size;
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
-    if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * IS_ALL);
-    s->d_stat = s->stat_buf.as<uint32_t>();
-    if (e1 == hipSuccess) e1 = hipMemset(s->d_stat, 0, sizeof(uint32_t) * IS_ALL);
+    if (e1 == hipSuccess) e1 = s->reserve_stat(IS_ALL);
     if (e1 == hipSuccess) e1 = hipMemset(s->d_stat + IS_BAD, 0xFF, sizeof(uint32_t));
-    if (e1 == hipSuccess) e1 = s->h_stat_buf.reserve(sizeof(uint32_t) * IS_ALL);
-    s->h_stat = s->h_stat_buf.as<uint32_t>();
     if (e1 != hipSuccess) {
         vs_fastq_il_close(s);
         return vs_fail(ctx, VS_E_HIP, "vs_fastq_il_open: %s", hipGetErrorString(e1));
@@ -641,84 +600,32 @@ int vs_fastq_il_next(vs_ctx *ctx, vs_fastq_il *s, uint64_t max_pairs, vs_reads *
     if (!ctx || !s || !out || !n_pairs) return vs_fail(ctx, VS_E_ARG, "vs_fastq_il_next: bad argument");
     *out = nullptr;
     *n_pairs = 0;
-    if (s->failed != VS_OK) return vs_fail(ctx, s->failed, "%s", s->failed_msg.c_str());
+    if (s->failed != VS_OK) return s->again(ctx);
     if (s->done) return VS_OK;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     if (!max_pairs || max_pairs > (1ull << 30)) max_pairs = 1ull << 30;
-    hipStream_t st = s->st;
     while (!s->matched || (s->pair_cur >= s->mt.n_pairs && !(s->keep && s->single_cur < s->mt.singles))) {
         bool end = false;
         const int rc = il_next_window(ctx, s, &end);
         if (end) return rc;
     }
     DevFile &d = s->df;
-    if (s->pair_cur >= s->mt.n_pairs) {
-        // ---- VS_IL_KEEP, the window's pairs are out: a singles block of n of its single records from the cursor
-        const uint64_t n = std::min<uint64_t>(s->mt.singles - s->single_cur, max_pairs);
-        const uint32_t *srec = s->mt.srec.as<const uint32_t>() + s->single_cur;
-        const SlWin win = {d.w.data(), d.ends.as<const uint32_t>(), d.n_nl, (uint32_t)d.w.size};
-        vs_reads *r = nullptr;
-        hipError_t e1 = vs_reads_singles_block(ctx, st, win, srec, 0u, n, s->d_wcnt, s->d_stat + IS_MAXLEN, s->h_stat + IS_MAXLEN, &r);
-        if (e1 == hipErrorOutOfMemory) return il_fail(ctx, s, VS_E_OOM, "vs_fastq_il_next: device buffers for the block");
-        if (e1 != hipSuccess) return il_fail(ctx, s, VS_E_HIP, std::string("vs_fastq_il_next: ") + hipGetErrorString(e1));
-        if (!r) {
-            uint32_t at = 0;
-            e1 = hipMemcpy(&at, srec + (s->h_stat[IS_TOO_LONG] >> 1), sizeof at, hipMemcpyDeviceToHost);
-            char msg[600];
-            snprintf(msg, sizeof msg, "%s: record %llu has a sequence line of more than %u bytes", s->rd.path.c_str(),
-                     (unsigned long long)(d.first_record + (e1 == hipSuccess ? at : 0u)), (unsigned)VS_LEN_MASK);
-            return il_fail(ctx, s, VS_E_RANGE, msg);
-        }
-        s->single_cur += (uint32_t)n;
-        *out = r;
-        *n_pairs = n;
-        return VS_OK;
-    }
-    // ---- the block of n pairs from the cursor
-    const uint64_t n = std::min<uint64_t>(s->mt.n_pairs - s->pair_cur, max_pairs), n_ends = 2u * n;
-    const uint32_t *rec = s->mt.rec.as<const uint32_t>() + 2u * (size_t)s->pair_cur;
+    // ---- the block of n pairs from the cursor -- or, VS_IL_KEEP and the window's pairs out, a singles block of n of its single
+    // records: rec[i] = the record of the block's i-th end / read
+    const bool single = s->pair_cur >= s->mt.n_pairs;
+    const uint64_t n = std::min<uint64_t>(single ? s->mt.singles - s->single_cur : s->mt.n_pairs - s->pair_cur, max_pairs);
+    const uint32_t *rec = single ? s->mt.srec.as<const uint32_t>() + s->single_cur : s->mt.rec.as<const uint32_t>() + 2u * (size_t)s->pair_cur;
     const SlWin win = {d.w.data(), d.ends.as<const uint32_t>(), d.n_nl, (uint32_t)d.w.size};
-    if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return il_fail(ctx, s, rc, vs_last_error(ctx));
-    vs_reads *r = new vs_reads();
-    r->cached = true;
-    // (a failure of the block: it goes back, and the stream has failed)
-    auto fail = [&](hipError_t e, const char *oom_msg = nullptr) {
-        vs_reads_free(ctx, r);
-        if (e == hipErrorOutOfMemory && oom_msg) return il_fail(ctx, s, VS_E_OOM, oom_msg);
-        return il_fail(ctx, s, e == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, std::string("vs_fastq_il_next: ") + hipGetErrorString(e));
-    };
-    const char *no_buffers = "vs_fastq_il_next: device buffers for the block";
-    hipError_t e1 = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true);
-    if (e1 != hipSuccess) return fail(e1, no_buffers);
-    e1 = hipMemsetAsync(s->d_stat + IS_MAXLEN, 0, sizeof(uint32_t) * (IS_WINDOW - IS_MAXLEN), st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + IS_TOO_LONG, 0xFF, sizeof(uint32_t), st);
-    if (e1 != hipSuccess) return fail(e1);
-    hipLaunchKernelGGL(k_il_ends, dim3((unsigned)((n_ends + 1u + IL_TPB - 1u) / IL_TPB)), dim3(IL_TPB), 0, st, win, rec, (uint32_t)n_ends, (uint32_t *)r->d_meta,
-                       s->d_wcnt.as<uint32_t>(), s->d_stat);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    vs_launch_scan_u32(st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + IS_WORDS);
-    e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat + IS_MAXLEN, s->d_stat + IS_MAXLEN, sizeof(uint32_t) * (IS_WINDOW - IS_MAXLEN), hipMemcpyDeviceToHost, st);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-    if (e1 != hipSuccess) return fail(e1);
-    if (s->h_stat[IS_TOO_LONG] != 0xFFFFFFFFu) {
-        uint32_t at = 0;
-        e1 = hipMemcpy(&at, rec + s->h_stat[IS_TOO_LONG], sizeof at, hipMemcpyDeviceToHost);
-        vs_reads_free(ctx, r);
-        char msg[600];
-        snprintf(msg, sizeof msg, "%s: record %llu has a sequence line of more than %u bytes", s->rd.path.c_str(),
-                 (unsigned long long)(d.first_record + (e1 == hipSuccess ? at : 0u)), (unsigned)VS_LEN_MASK);
-        return il_fail(ctx, s, VS_E_RANGE, msg);
+    const VsBlockJob job = {ctx, s->st, 2u * n, &s->d_wcnt, s->d_stat + IS_BLOCK, s->h_stat + IS_BLOCK, VS_BLK_ST, false};
+    vs_reads *r = nullptr;
+    const hipError_t e1 = single ? vs_block_singles(job, win, rec, 0u, &r) : vs_block_records(job, win, rec, &r);
+    if (e1 != hipSuccess) return s->fail_hip(ctx, "vs_fastq_il_next", e1);
+    if (!r) {  // (neither source faults an end: the end is over the limit)
+        const uint32_t e = s->h_stat[IS_BLOCK + VS_BLK_BAD] & ~VS_BLK_OVER;
+        return s->fail(ctx, VS_E_RANGE, too_long_line(s->rd.path, d.first_record + fetch_u32(rec + (single ? e >> 1 : e))));
     }
-    const uint64_t words = s->h_stat[IS_WORDS];
-    r->max_len = s->h_stat[IS_MAXLEN];
-    if ((e1 = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e1, no_buffers);
-    vs_launch_pack_records(st, win, rec, r);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + IS_INVALID, s->h_stat + IS_INVALID)) != hipSuccess) return fail(e1);
-    if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
-    s->pair_cur += (uint32_t)n;
-    s->pairs += n;
+    if (single) s->single_cur += (uint32_t)n;
+    else s->pair_cur += (uint32_t)n, s->pairs += n;
     *out = r;
     *n_pairs = n;
     return VS_OK;

@@ -224,42 +224,47 @@ struct SlWin {
     const uint32_t *ends;
     uint32_t n_nl, size;
 };
-// k_pack_reads for the first r->n_ends / 2 records of two windows (r's woff and lengths are on the device, r->d_mask too)
-void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, const vs_reads *r);
-// k_pack_reads for the records rec[0, r->n_ends) of ONE window (the interleaved ingest, vs_interleaved.hip): end e is the
-// sequence line of record rec[e]
-void vs_launch_pack_records(hipStream_t st, const SlWin &w, const uint32_t *rec, const vs_reads *r);
-// k_pack_reads for the records of TWO windows joined by name (vs_pair_names.hip): end e is the sequence line of record
-// rec[e] of window e & 1 (k_pn_ends has range-tested every rec[e] before)
-void vs_launch_pack_pairs(hipStream_t st, const SlWin &f0, const SlWin &f1, const uint32_t *rec, const vs_reads *r);
-// A singles block (vs_reads::unpaired) of n_reads records of ONE window, built on the device on stream st (vs_single.hip, the
-// kept singles of vs_interleaved.hip): read i is the sequence line of record rec[i], or of record first + i when rec is NULL;
-// every odd end is absent.  k_single_ends (lengths, word counts), the scan, k_pack_reads<PackSingles>, vs_reads_finish.
-// wcnt: scratch of the caller, grown here.  d4 / h4: four status words on the device / pinned, rewritten: the longest read,
-// the first END over the 24-bit limit (~0u: none), the packed words, the ends with bytes outside ACGTN.  Synchronises st.
-// hipSuccess with *out == NULL: h4[1] names an end over the limit (read h4[1] / 2 of the block).
-hipError_t vs_reads_singles_block(vs_ctx *ctx, hipStream_t st, const SlWin &win, const uint32_t *rec, uint32_t first, uint64_t n_reads, VsDevBuf &wcnt,
-                                  uint32_t *d4, uint32_t *h4, vs_reads **out);
 // exclusive scan of a[0, m) in place by one workgroup (k_sl_scan of vs_stream.hip); the total, below 2^32, to *total
 void vs_launch_scan_u32(hipStream_t st, uint32_t *a, uint32_t m, uint32_t *total);
-// The ends of a block of the BAM ingest (vs_bam.hip): end e is record ends[e] of recs (BamRec of vs_bam_core.h: four words,
-// the flag in the low 16 bits of the second, l_seq the third, the offset of the 4-bit bases in win the fourth)
+// The ends of a block of the BAM ingest (vs_bam.hip): end e is record ends[e] of recs (n_rec of them; BamRec of vs_bam_core.h:
+// four words, the flag in the low 16 bits of the second, l_seq the third, the offset of the 4-bit bases in win the fourth)
 struct BamEnds {
     const uint8_t *win;
     const uint32_t *recs;
     const uint32_t *ends;
+    uint32_t n_rec;
 };
-// k_pack_reads for them (r's woff and lengths are on the device, r->d_mask too)
-void vs_launch_pack_bam(hipStream_t st, const BamEnds &b, const vs_reads *r);
 // The kept singletons of the BAM ingest (VS_BAM_BY_NAME_KEEP): a singles block whose even end e is record list[e / 2] of recs
-// (n_rec of them, as BamEnds), every odd end absent; k_bam_single_ends (vs_bam.hip) has written r's lengths
+// (as BamEnds), every odd end absent
 struct BamSingles {
     const uint8_t *win;
     const uint32_t *recs;
     const uint32_t *list;
     uint32_t n_rec;
 };
-void vs_launch_pack_bam_singles(hipStream_t st, const BamSingles &b, const vs_reads *r);
+// THE way a streamed ingest cuts a block of n_ends ends out of its device window (vs_reads.hip, one entry per source of ends;
+// a singles source gives a block with vs_reads::unpaired): wcnt reserved, the block's woff and meta, k_block_ends<Src> (lengths,
+// word counts), the scan, woff copied, ONE read-back and wait, words and mask, k_pack_reads<Src>, vs_reads_finish, the last wait.
+// d_st / h_st: n_st >= VS_BLK_ST status words on the device / pinned.  The first VS_BLK_ST are rewritten here; the words behind
+// them are the caller's, set by a kernel of its own on st before the call, and come back in the same read-back.
+// hipSuccess with *out == NULL: h_st[VS_BLK_BAD] names the first end that stops the block -- e | VS_BLK_OVER: longer than
+// VS_LEN_MASK; e alone: its source has no such record (PackPairs, PackBam, PackBamSingles test their lists) -- the caller words it.
+enum { VS_BLK_MAXLEN = 0, VS_BLK_BAD = 1 /* ~0u: none */, VS_BLK_WORDS = 2, VS_BLK_INVALID = 3, VS_BLK_ST = 4 };
+#define VS_BLK_OVER 0x80000000u
+struct VsBlockJob {
+    vs_ctx *ctx;
+    hipStream_t st;
+    uint64_t n_ends;  // <= 2^31
+    VsDevBuf *wcnt;   // scratch of the caller, grown here
+    uint32_t *d_st, *h_st, n_st;
+    bool more;        // the caller has work for st behind the block and waits for both itself: no last wait here
+};
+hipError_t vs_block_lines(const VsBlockJob &j, const SlWin &f0, const SlWin &f1, vs_reads **out);  // end e: record e / 2 of window e & 1
+hipError_t vs_block_records(const VsBlockJob &j, const SlWin &w, const uint32_t *rec, vs_reads **out);  // record rec[e] of ONE window
+hipError_t vs_block_singles(const VsBlockJob &j, const SlWin &w, const uint32_t *rec, uint32_t first, vs_reads **out);  // even e: rec[e / 2], or first + e / 2 (rec NULL)
+hipError_t vs_block_pairs(const VsBlockJob &j, const SlWin &f0, uint32_t n_rec0, const SlWin &f1, uint32_t n_rec1, const uint32_t *rec, vs_reads **out);  // rec[e] of window e & 1
+hipError_t vs_block_bam(const VsBlockJob &j, const BamEnds &b, vs_reads **out);
+hipError_t vs_block_bam_singles(const VsBlockJob &j, const BamSingles &b, vs_reads **out);
 
 // BGZF members (vs_inflate.hip), shared with the streamed ingest.  A member for the device: its raw deflate payload in a
 // buffer of compressed bytes, where its ISIZE bytes go in an output buffer, and the CRC32 of its trailer.

@@ -24,8 +24,8 @@
 //   strict: k_pn_index   m[p] = il_mates(a_p, b_p) for p < min(R1, R2), the first failing p a minimum; rec is the identity.
 //   ONE read-back: the pair count, the last pair, the status words.  What is decided follows on the host (pn_decide); single
 //   counts are arithmetic.
-// Blocks of at most max_pairs pairs are cut from rec with a cursor: k_pn_ends (lengths, word counts, every rec index range-
-// tested), k_sl_scan, k_pack_reads<PackPairs>, vs_reads_finish -- the layout vs_pe_count takes.  When the pairs are out each
+// Blocks of at most max_pairs pairs are cut from rec with a cursor by the block builder (vs_block_pairs, vs_reads.hip; its source
+// range-tests every rec index) -- the layout vs_pe_count takes.  When the pairs are out each
 // window is cut behind its last decided record; nothing is dropped where nothing is decided.  More text goes to the file
 // whose window is the smaller one (to both while both are small, to the other when one is at its end), so in-step files keep
 // windows of carry + one slot.  A window beyond VS_PAIR_WINDOW bytes (default: the largest window) in a round that decided
@@ -34,7 +34,7 @@
 //     k_pn_mated    one thread per file-1 record: mated[mate[i]] = 1 (one byte per file-2 record, zeroed before);
 //     k_pn_singles_count<Pred> / k_sl_scan / k_pn_singles_emit<Pred>   once per file, bound dec[f]: the DECIDED records in no
 //                   pair compacted in file order into srec[f] (Pred: mate[i] is none / mated[j] is 0);
-//   and when the round's pairs are out they are handed out as SINGLES blocks (vs_reads_singles_block, vs_reads.hip), file 1's
+//   and when the round's pairs are out they are handed out as SINGLES blocks (vs_block_singles, the same builder), file 1's
 //   first, then file 2's, before the windows are cut.  A record behind dec[f] waits, as it does for the pairs: it is handed
 //   out once, by the round that decides it.  The other modes launch none of this.
 // Inputs that are wrong end in status words and messages, never in a fault.
@@ -53,7 +53,7 @@ namespace {
 // status words of a stream (file f's line scanner words at f * ST_PER_FILE)
 enum {
     PS_PAIRS = 8, PS_DUP0 = 9, PS_DUP1 = 10, PS_ORDER = 11, PS_FULL = 12, PS_LAST_I = 13, PS_LAST_J = 14, PS_FIRST_BAD = 15,
-    PS_MAXLEN = 16, PS_TOO_LONG = 17, PS_WORDS = 18, PS_INVALID = 19, PS_BAD_REC = 20,
+    PS_BLOCK = 16,  // the VS_BLK_ST words of the block builder
     PS_ROUND = 24,  // (words below it are rewritten for every round or block)
     PS_BADM = 24,   // + f: the first BGZF member of file f the device rejected (a running index), ~0u: none
     PS_ALL = 26
@@ -167,43 +167,6 @@ __global__ void __launch_bounds__(PN_TPB) k_pn_index(PnWin f0, PnWin f1, uint32_
     rec[2u * p + 1u] = p;
 }
 
-// one thread per end of the block (and one more for the closing word offset): end e is the sequence line of record rec[e] of
-// window e & 1; length, packed words, the longest end, the first end over the 24-bit limit, a rec index outside its window
-__global__ void __launch_bounds__(PN_TPB) k_pn_ends(PnWin f0, PnWin f1, const uint32_t *__restrict__ rec, uint32_t n_ends, uint32_t *__restrict__ meta,
-                                                    uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
-    const uint32_t e = blockIdx.x * PN_TPB + threadIdx.x;
-    if (e > n_ends) return;
-    if (e == n_ends) {
-        wcnt[e] = 0u;
-        return;
-    }
-    const PnWin &w = (e & 1u) ? f1 : f0;
-    const uint32_t r = rec[e];
-    uint32_t start = 0u, stop = 0u;
-    bool ok = r < w.n_rec && 4ull * r + 1u < w.n_nl;
-    if (ok) {
-        start = w.ends[4u * r] + 1u;
-        stop = w.ends[4u * r + 1u];  // (the character dropped is the newline)
-        ok = start <= stop && stop <= w.size;
-    }
-    if (!ok) {
-        atomicMin(&st[PS_BAD_REC], e);
-        meta[e] = 0u;
-        wcnt[e] = 0u;
-        return;
-    }
-    const uint32_t len = stop - start;
-    if (len > VS_LEN_MASK) {
-        atomicMin(&st[PS_TOO_LONG], e);
-        meta[e] = 0u;
-        wcnt[e] = 0u;
-        return;
-    }
-    meta[e] = len;
-    wcnt[e] = (len + 15u) >> 4;
-    atomicMax(&st[PS_MAXLEN], len);
-}
-
 // ---- the join of one pair of windows -----------------------------------------------------------------------------------------
 namespace {
 
@@ -250,7 +213,7 @@ int pn_singles_device(vs_ctx *ctx, hipStream_t st, uint32_t r0, uint32_t r1, con
 }
 
 // The pairs of the windows f0, f1 into rec (room for 2 * min(R1, R2) words): joined by name (singles), or record by record
-// (strict).  table: slots (0: pn_table_size), bits: hash bits kept.  d_stat / h_stat: PS_ALL status words, [PS_PAIRS, PS_MAXLEN)
+// (strict).  table: slots (0: pn_table_size), bits: hash bits kept.  d_stat / h_stat: PS_ALL status words, [PS_PAIRS, PS_BLOCK)
 // rewritten.  Synchronises the stream.
 int pn_join_device(vs_ctx *ctx, hipStream_t st, const PnWin &f0, const PnWin &f1, bool singles, uint32_t table, uint32_t bits, PnDev &jd, uint32_t *rec,
                    uint32_t *d_stat, uint32_t *h_stat) {
@@ -258,14 +221,14 @@ int pn_join_device(vs_ctx *ctx, hipStream_t st, const PnWin &f0, const PnWin &f1
     jd.n_pairs = jd.li = jd.lj = 0;
     jd.dup[0] = jd.dup[1] = jd.order = jd.first_bad = PN_NONE;
     if (!cap) return VS_OK;
-    VS_HIP(ctx, hipMemsetAsync(d_stat + PS_PAIRS, 0, sizeof(uint32_t) * (PS_MAXLEN - PS_PAIRS), st));
+    VS_HIP(ctx, hipMemsetAsync(d_stat + PS_PAIRS, 0, sizeof(uint32_t) * (PS_BLOCK - PS_PAIRS), st));
     VS_HIP(ctx, hipMemsetAsync(d_stat + PS_DUP0, 0xFF, sizeof(uint32_t) * 3, st));  // (both duplicates, the order)
     VS_HIP(ctx, hipMemsetAsync(d_stat + PS_FIRST_BAD, 0xFF, sizeof(uint32_t), st));
     const uint32_t cap_wgs = (cap + PN_TPB - 1u) / PN_TPB;
     if (!singles) {
         hipLaunchKernelGGL(k_pn_index, dim3(cap_wgs), dim3(PN_TPB), 0, st, f0, f1, cap, rec, d_stat);
         VS_HIP(ctx, hipGetLastError());
-        VS_HIP(ctx, hipMemcpyAsync(h_stat + PS_PAIRS, d_stat + PS_PAIRS, sizeof(uint32_t) * (PS_MAXLEN - PS_PAIRS), hipMemcpyDeviceToHost, st));
+        VS_HIP(ctx, hipMemcpyAsync(h_stat + PS_PAIRS, d_stat + PS_PAIRS, sizeof(uint32_t) * (PS_BLOCK - PS_PAIRS), hipMemcpyDeviceToHost, st));
         VS_HIP(ctx, hipStreamSynchronize(st));
         jd.first_bad = h_stat[PS_FIRST_BAD];
         jd.n_pairs = cap;
@@ -297,7 +260,7 @@ int pn_join_device(vs_ctx *ctx, hipStream_t st, const PnWin &f0, const PnWin &f1
     VS_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_pn_order, dim3(cap_wgs), dim3(PN_TPB), 0, st, (const uint32_t *)rec, (const uint32_t *)(d_stat + PS_PAIRS), cap, d_stat);
     VS_HIP(ctx, hipGetLastError());
-    VS_HIP(ctx, hipMemcpyAsync(h_stat + PS_PAIRS, d_stat + PS_PAIRS, sizeof(uint32_t) * (PS_MAXLEN - PS_PAIRS), hipMemcpyDeviceToHost, st));
+    VS_HIP(ctx, hipMemcpyAsync(h_stat + PS_PAIRS, d_stat + PS_PAIRS, sizeof(uint32_t) * (PS_BLOCK - PS_PAIRS), hipMemcpyDeviceToHost, st));
     VS_HIP(ctx, hipStreamSynchronize(st));
     if (h_stat[PS_FULL]) return vs_fail(ctx, VS_E_STATE, "the table of a join by name (%u slots for %u records) is full", T, n_all);
     jd.dup[0] = h_stat[PS_DUP0];
@@ -334,7 +297,7 @@ void pn_join_info(uint64_t info[8], bool singles, uint32_t n_pairs, uint32_t li,
 }  // namespace
 
 // ---- the stream ------------------------------------------------------------------------------------------------------------
-struct vs_fastq_pn {
+struct vs_fastq_pn : StreamState {  // (PS_ALL status words)
     int device = 0;
     hipStream_t st = nullptr;
     Reader rd[2];
@@ -350,26 +313,12 @@ struct vs_fastq_pn {
     uint32_t n_single[2] = {0, 0}, single_cur[2] = {0, 0};  // ... how many the round has, the first not yet delivered
     size_t window_limit = STREAM_MAX_WINDOW;
     uint32_t name_bits = 64;  // bits of the name hash kept (VS_PAIR_NAME_BITS: tests)
-    VsDevBuf stat_buf, d_wcnt;
-    VsPinnedBuf h_stat_buf;
-    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // PS_ALL words each
+    VsDevBuf d_wcnt;
     uint64_t pairs = 0, singles[2] = {0, 0}, records[2] = {0, 0}, windows = 0, max_window = 0;
     uint32_t flags_seen = 0;
-    bool done = false;
-    int failed = VS_OK;
-    std::string failed_msg;
 };
 
 namespace {
-
-int pn_fail(vs_ctx *ctx, vs_fastq_pn *s, int code, const std::string &msg) {
-    s->done = true;
-    s->failed = code;
-    s->failed_msg = msg;
-    if (!ctx) return code;
-    ctx->err = msg;  // (whole: two paths and two header lines of 200 bytes do not fit the formatting buffer of vs_fail)
-    return code;
-}
 
 PnWin pn_win(const DevFile &d) { return PnWin{d.w.data(), d.ends.as<const uint32_t>(), d.n_nl, (uint32_t)d.w.size, (uint32_t)d.records}; }
 
@@ -412,7 +361,7 @@ std::string pn_key_of(const std::string &line, int f) { return line.substr(0, pn
 // the end of the input: a reader's failure, if it had one (in file order)
 int pn_finish(vs_ctx *ctx, vs_fastq_pn *s) {
     for (int f = 0; f < 2; f++)
-        if (s->rd[f].err != VS_OK) return pn_fail(ctx, s, s->rd[f].err, s->rd[f].err_msg);
+        if (s->rd[f].err != VS_OK) return s->fail(ctx, s->rd[f].err, s->rd[f].err_msg);
     s->done = true;
     return VS_OK;
 }
@@ -435,8 +384,8 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
                 VS_HIP(ctx, hipStreamSynchronize(st));
                 cut = (size_t)at + 1u;
             }
-            if (cut > d.w.size) return pn_fail(ctx, s, VS_E_STATE, s->rd[f].path + ": a line end beyond the window");
-            if (int rc = drop_front(ctx, st, d, cut, s->dec[f])) return pn_fail(ctx, s, rc, vs_last_error(ctx));
+            if (cut > d.w.size) return s->fail(ctx, VS_E_STATE, s->rd[f].path + ": a line end beyond the window");
+            if (int rc = drop_front(ctx, st, d, cut, s->dec[f])) return s->fail(ctx, rc, vs_last_error(ctx));
         }
         s->joined = false;
         s->pair_cur = 0;
@@ -450,10 +399,10 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
         for (int f = 0; f < 2; f++) {
             DevFile &d = s->df[f], &o = s->df[f ^ 1];
             if (d.eof || !(o.eof || d.w.size <= o.w.size || d.w.size < s->rd[f].chunk / 2u)) continue;
-            if (int rc = append_chunk(ctx, st, d, s->rd[f], taken[f], s->d_stat + PS_BADM + f)) return pn_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = append_chunk(ctx, st, d, s->rd[f], taken[f], s->d_stat + PS_BADM + f)) return s->fail(ctx, rc, vs_last_error(ctx));
             fresh[f] = true;
         }
-        if (int rc = pn_scan(ctx, s)) return pn_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = pn_scan(ctx, s)) return s->fail(ctx, rc, vs_last_error(ctx));
         for (int f = 0; f < 2; f++)
             if (fresh[f] && taken[f]) (void)member_failed(s->df[f], s->rd[f], *taken[f], s->h_stat[PS_BADM + f]);
         for (int f = 0; f < 2; f++) taken[f].give_back();
@@ -464,14 +413,14 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
                 if (translate_window(ctx, d, s->rd[f].path) == VS_OK) again = true;
         }
         if (again)
-            if (int rc = pn_scan(ctx, s)) return pn_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = pn_scan(ctx, s)) return s->fail(ctx, rc, vs_last_error(ctx));
     }
     for (int f = 0; f < 2; f++) {
         DevFile &d = s->df[f];
         Reader &r = s->rd[f];
-        if (d.err != VS_OK) return pn_fail(ctx, s, r.err != VS_OK ? r.err : d.err, r.err != VS_OK ? r.err_msg : d.err_msg);
-        if (d.records > 0x3FFFFFFFull) return pn_fail(ctx, s, VS_E_RANGE, r.path + ": more than 2^30 records in one window");
-        if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return pn_fail(ctx, s, rc, vs_last_error(ctx));
+        if (d.err != VS_OK) return s->fail(ctx, r.err != VS_OK ? r.err : d.err, r.err != VS_OK ? r.err_msg : d.err_msg);
+        if (d.records > 0x3FFFFFFFull) return s->fail(ctx, VS_E_RANGE, r.path + ": more than 2^30 records in one window");
+        if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return s->fail(ctx, rc, vs_last_error(ctx));
         vs_launch_sl_scatter(st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
         s->max_window = std::max<uint64_t>(s->max_window, d.w.size);
     }
@@ -479,15 +428,15 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
     s->windows++;
     const PnWin f0 = pn_win(s->df[0]), f1 = pn_win(s->df[1]);
     const bool eof[2] = {s->df[0].eof, s->df[1].eof};
-    if (int rc = reserve_n<uint32_t>(ctx, s->rec, 2u * (size_t)std::min(f0.n_rec, f1.n_rec) + 1u)) return pn_fail(ctx, s, rc, vs_last_error(ctx));
-    if (int rc = pn_join_device(ctx, st, f0, f1, s->singles_mode, 0u, s->name_bits, s->jd, s->rec.as<uint32_t>(), s->d_stat, s->h_stat)) return pn_fail(ctx, s, rc, vs_last_error(ctx));
+    if (int rc = reserve_n<uint32_t>(ctx, s->rec, 2u * (size_t)std::min(f0.n_rec, f1.n_rec) + 1u)) return s->fail(ctx, rc, vs_last_error(ctx));
+    if (int rc = pn_join_device(ctx, st, f0, f1, s->singles_mode, 0u, s->name_bits, s->jd, s->rec.as<uint32_t>(), s->d_stat, s->h_stat)) return s->fail(ctx, rc, vs_last_error(ctx));
     s->joined = true;
     const PnDev &j = s->jd;
     const std::string &p0 = s->rd[0].path, &p1 = s->rd[1].path;
     if (!s->singles_mode) {
         if (j.first_bad != PN_NONE) {
             const uint32_t p = j.first_bad;
-            return pn_fail(ctx, s, VS_E_ARG,
+            return s->fail(ctx, VS_E_ARG,
                            p0 + " / " + p1 + ": pair " + std::to_string(s->df[0].first_record + p) + " is no pair of mates by name: \"" + pn_header_line(s, 0, p) + "\" against \"" +
                                pn_header_line(s, 1, p) + "\".  --check-names takes record i of either file as pair i and stops where their names differ (a record "
                                                          "lost from one file?); to drop and count the records without a mate, add --check-names-singles");
@@ -497,7 +446,7 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
         if (longer >= 0) {
             const int f = longer;
             const uint32_t r = std::min(f0.n_rec, f1.n_rec);
-            return pn_fail(ctx, s, VS_E_ARG,
+            return s->fail(ctx, VS_E_ARG,
                            p0 + " / " + p1 + ": pair " + std::to_string(s->df[f].first_record + r) + " has no record in " + s->rd[f ^ 1].path + ", which ends there: \"" +
                                pn_header_line(s, f, r) + "\" of " + s->rd[f].path + " against end of file.  --check-names stops at a record left over in the longer "
                                                                                    "file; to drop and count the records without a mate, add --check-names-singles");
@@ -506,14 +455,14 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
         for (int f = 0; f < 2; f++)
             if (j.dup[f] != PN_NONE) {
                 const std::string line = pn_header_line(s, f, j.dup[f]);
-                return pn_fail(ctx, s, VS_E_ARG,
+                return s->fail(ctx, VS_E_ARG,
                                "name " + pn_key_of(line, f) + " occurs twice in " + s->rd[f].path + " (record " + std::to_string(s->df[f].first_record + j.dup[f]) + ", \"" + line +
                                    "\", is the first of them): --check-names-singles joins the two files by read name, and within a file a name stands for one record");
             }
         if (j.order != PN_NONE) {
             uint32_t q[4] = {0, 0, 0, 0};  // the pair before it and the pair itself
             VS_HIP(ctx, hipMemcpy(q, s->rec.as<uint32_t>() + 2u * (size_t)j.order - 2u, sizeof q, hipMemcpyDeviceToHost));
-            return pn_fail(ctx, s, VS_E_ARG,
+            return s->fail(ctx, VS_E_ARG,
                            p0 + " record " + std::to_string(s->df[0].first_record + q[2]) + " and " + p1 + " record " + std::to_string(s->df[1].first_record + q[3]) + " (\"" +
                                pn_header_line(s, 0, q[2]) + "\") are mates but lie behind " + p0 + " record " + std::to_string(s->df[0].first_record + q[0]) + " and in front of its mate, " +
                                p1 + " record " + std::to_string(s->df[1].first_record + q[1]) + ": --check-names-singles needs both files in the same order");
@@ -522,23 +471,23 @@ int pn_next_round(vs_ctx *ctx, vs_fastq_pn *s, bool *end) {
         for (int f = 0; f < 2; f++) {
             const DevFile &d = s->df[f];
             if (!s->dec[f] && d.w.size > s->window_limit && !(eof[0] && eof[1]))
-                return pn_fail(ctx, s, VS_E_RANGE,
+                return s->fail(ctx, VS_E_RANGE,
                                s->rd[f].path + ": " + std::to_string(d.records) + " records of this file wait without a mate in a window of " + std::to_string(d.w.size) +
                                    " bytes (limit " + std::to_string(s->window_limit) + "; " + std::to_string(s->df[f ^ 1].records) + " records of " + s->rd[f ^ 1].path +
                                    " wait too): the two files are probably not in the same order");
         }
     }
     if (s->dec[0] > f0.n_rec || s->dec[1] > f1.n_rec || j.n_pairs > std::min(s->dec[0], s->dec[1]))
-        return pn_fail(ctx, s, VS_E_STATE, "the decided records of a round do not hold its pairs");
+        return s->fail(ctx, VS_E_STATE, "the decided records of a round do not hold its pairs");
     for (int f = 0; f < 2; f++) {
         s->records[f] += s->dec[f];
         s->singles[f] += s->dec[f] - j.n_pairs;
     }
     if (s->keep) {
         for (int f = 0; f < 2; f++)
-            if (int rc = reserve_n<uint32_t>(ctx, s->srec[f], (size_t)(s->dec[f] - j.n_pairs) + 1u)) return pn_fail(ctx, s, rc, vs_last_error(ctx));
-        if (int rc = pn_singles_device(ctx, st, f0.n_rec, f1.n_rec, s->dec, s->jd, s->srec[0].as<uint32_t>(), s->srec[1].as<uint32_t>(), s->d_stat + PS_WORDS))
-            return pn_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = reserve_n<uint32_t>(ctx, s->srec[f], (size_t)(s->dec[f] - j.n_pairs) + 1u)) return s->fail(ctx, rc, vs_last_error(ctx));
+        if (int rc = pn_singles_device(ctx, st, f0.n_rec, f1.n_rec, s->dec, s->jd, s->srec[0].as<uint32_t>(), s->srec[1].as<uint32_t>(), s->d_stat + PS_BLOCK + VS_BLK_WORDS))
+            return s->fail(ctx, rc, vs_last_error(ctx));
         for (int f = 0; f < 2; f++) s->n_single[f] = s->dec[f] - j.n_pairs;
     }
     *end = false;
@@ -562,9 +511,7 @@ int vs_fastq_pn_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, in
     const char *paths[2] = {fwd_path, rve_path};
     for (int f = 0; f < 2; f++) {
         Reader &r = s->rd[f];
-        if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
-        if (const char *ev = getenv("VS_GZIP_DEVICE")) r.gzip_device = strcmp(ev, "1") == 0;
-        if (const char *ev = getenv("VS_GZIP_TEXT")) s->df[f].w.gz.text_cap = (uint32_t)std::max<long long>(1, atoll(ev));  // (tests only, as VS_STREAM_CHUNK)
+        fastq_switches(r, false, s->df[f].w.gz.text_cap);
         if (int rc = r.open_file(ctx, paths[f])) {
             for (int g = 0; g < f; g++) close(s->rd[g].fd);
             for (int g = 0; g < 2; g++) s->rd[g].fd = -1;
@@ -573,12 +520,8 @@ int vs_fastq_pn_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, in
         }
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
-    if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * PS_ALL);
-    s->d_stat = s->stat_buf.as<uint32_t>();
-    if (e1 == hipSuccess) e1 = hipMemset(s->d_stat, 0, sizeof(uint32_t) * PS_ALL);
+    if (e1 == hipSuccess) e1 = s->reserve_stat(PS_ALL);
     if (e1 == hipSuccess) e1 = hipMemset(s->d_stat + PS_BADM, 0xFF, sizeof(uint32_t) * 2);
-    if (e1 == hipSuccess) e1 = s->h_stat_buf.reserve(sizeof(uint32_t) * PS_ALL);
-    s->h_stat = s->h_stat_buf.as<uint32_t>();
     if (e1 != hipSuccess) {
         vs_fastq_pn_close(s);
         return vs_fail(ctx, VS_E_HIP, "vs_fastq_pn_open: %s", hipGetErrorString(e1));
@@ -592,98 +535,35 @@ int vs_fastq_pn_next(vs_ctx *ctx, vs_fastq_pn *s, uint64_t max_pairs, vs_reads *
     if (!ctx || !s || !out || !n_pairs) return vs_fail(ctx, VS_E_ARG, "vs_fastq_pn_next: bad argument");
     *out = nullptr;
     *n_pairs = 0;
-    if (s->failed != VS_OK) {
-        ctx->err = s->failed_msg;
-        return s->failed;
-    }
+    if (s->failed != VS_OK) return s->again(ctx);
     if (s->done) return VS_OK;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     if (!max_pairs || max_pairs > (1ull << 30)) max_pairs = 1ull << 30;
-    hipStream_t st = s->st;
     while (!s->joined || (s->pair_cur >= s->jd.n_pairs && s->single_cur[0] >= s->n_single[0] && s->single_cur[1] >= s->n_single[1])) {
         bool end = false;
         const int rc = pn_next_round(ctx, s, &end);
         if (end) return rc;
     }
-    if (s->pair_cur >= s->jd.n_pairs) {
-        // ---- VS_PN_KEEP, the round's pairs are out: a singles block of n kept records of file 1 -- or, once those are out, of
-        // file 2 -- from the cursor
-        const int f = s->single_cur[0] < s->n_single[0] ? 0 : 1;
-        const DevFile &d = s->df[f];
-        const uint64_t n = std::min<uint64_t>(s->n_single[f] - s->single_cur[f], max_pairs);
-        const uint32_t *srec = s->srec[f].as<const uint32_t>() + s->single_cur[f];
-        const SlWin win = {d.w.data(), d.ends.as<const uint32_t>(), d.n_nl, (uint32_t)d.w.size};
-        vs_reads *r = nullptr;
-        hipError_t e1 = vs_reads_singles_block(ctx, st, win, srec, 0u, n, s->d_wcnt, s->d_stat + PS_MAXLEN, s->h_stat + PS_MAXLEN, &r);
-        if (e1 == hipErrorOutOfMemory) return pn_fail(ctx, s, VS_E_OOM, "vs_fastq_pn_next: device buffers for the block");
-        if (e1 != hipSuccess) return pn_fail(ctx, s, VS_E_HIP, std::string("vs_fastq_pn_next: ") + hipGetErrorString(e1));
-        if (!r) {
-            uint32_t at = 0;
-            e1 = hipMemcpy(&at, srec + (s->h_stat[PS_TOO_LONG] >> 1), sizeof at, hipMemcpyDeviceToHost);
-            char msg[600];
-            snprintf(msg, sizeof msg, "%s: record %llu has a sequence line of more than %u bytes", s->rd[f].path.c_str(),
-                     (unsigned long long)(d.first_record + (e1 == hipSuccess ? at : 0u)), (unsigned)VS_LEN_MASK);
-            return pn_fail(ctx, s, VS_E_RANGE, msg);
-        }
-        s->single_cur[f] += (uint32_t)n;
-        *out = r;
-        *n_pairs = n;
-        return VS_OK;
-    }
-    // ---- the block of n pairs from the cursor
-    const uint64_t n = std::min<uint64_t>(s->jd.n_pairs - s->pair_cur, max_pairs), n_ends = 2u * n;
-    const uint32_t *rec = s->rec.as<const uint32_t>() + 2u * (size_t)s->pair_cur;
+    // ---- the block of n pairs from the cursor -- or, VS_PN_KEEP and the round's pairs out, a singles block of n kept records of
+    // file 1 or, once those are out, of file 2 (file f): rec[i] = the record of the block's i-th end / read
+    const bool single = s->pair_cur >= s->jd.n_pairs;
+    const int f = s->single_cur[0] < s->n_single[0] ? 0 : 1;
+    const uint64_t n = std::min<uint64_t>(single ? s->n_single[f] - s->single_cur[f] : s->jd.n_pairs - s->pair_cur, max_pairs);
+    const uint32_t *rec = single ? s->srec[f].as<const uint32_t>() + s->single_cur[f] : s->rec.as<const uint32_t>() + 2u * (size_t)s->pair_cur;
     const PnWin f0 = pn_win(s->df[0]), f1 = pn_win(s->df[1]);
-    const SlWin w0 = {f0.txt, f0.ends, f0.n_nl, f0.size}, w1 = {f1.txt, f1.ends, f1.n_nl, f1.size};
-    if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return pn_fail(ctx, s, rc, vs_last_error(ctx));
-    vs_reads *r = new vs_reads();
-    r->cached = true;
-    // (a failure of the block: it goes back, and the stream has failed)
-    auto fail = [&](hipError_t e, const char *oom_msg = nullptr) {
-        vs_reads_free(ctx, r);
-        if (e == hipErrorOutOfMemory && oom_msg) return pn_fail(ctx, s, VS_E_OOM, oom_msg);
-        return pn_fail(ctx, s, e == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, std::string("vs_fastq_pn_next: ") + hipGetErrorString(e));
-    };
-    const char *no_buffers = "vs_fastq_pn_next: device buffers for the block";
-    hipError_t e1 = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true);
-    if (e1 != hipSuccess) return fail(e1, no_buffers);
-    e1 = hipMemsetAsync(s->d_stat + PS_MAXLEN, 0, sizeof(uint32_t) * (PS_ROUND - PS_MAXLEN), st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + PS_TOO_LONG, 0xFF, sizeof(uint32_t), st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + PS_BAD_REC, 0xFF, sizeof(uint32_t), st);
-    if (e1 != hipSuccess) return fail(e1);
-    hipLaunchKernelGGL(k_pn_ends, dim3((unsigned)((n_ends + 1u + PN_TPB - 1u) / PN_TPB)), dim3(PN_TPB), 0, st, f0, f1, rec, (uint32_t)n_ends, (uint32_t *)r->d_meta,
-                       s->d_wcnt.as<uint32_t>(), s->d_stat);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    vs_launch_scan_u32(st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + PS_WORDS);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat + PS_MAXLEN, s->d_stat + PS_MAXLEN, sizeof(uint32_t) * (PS_ROUND - PS_MAXLEN), hipMemcpyDeviceToHost, st);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-    if (e1 != hipSuccess) return fail(e1);
-    if (s->h_stat[PS_BAD_REC] != 0xFFFFFFFFu) {
-        vs_reads_free(ctx, r);
-        return pn_fail(ctx, s, VS_E_STATE, "vs_fastq_pn_next: a pair names a record outside its window");
+    const SlWin w[2] = {{f0.txt, f0.ends, f0.n_nl, f0.size}, {f1.txt, f1.ends, f1.n_nl, f1.size}};
+    const VsBlockJob job = {ctx, s->st, 2u * n, &s->d_wcnt, s->d_stat + PS_BLOCK, s->h_stat + PS_BLOCK, VS_BLK_ST, false};
+    vs_reads *r = nullptr;
+    const hipError_t e1 = single ? vs_block_singles(job, w[f], rec, 0u, &r) : vs_block_pairs(job, w[0], f0.n_rec, w[1], f1.n_rec, rec, &r);
+    if (e1 != hipSuccess) return s->fail_hip(ctx, "vs_fastq_pn_next", e1);
+    if (!r) {
+        const uint32_t bad = s->h_stat[PS_BLOCK + VS_BLK_BAD], e = bad & ~VS_BLK_OVER;
+        if (!(bad & VS_BLK_OVER)) return s->fail(ctx, VS_E_STATE, "vs_fastq_pn_next: a pair names a record outside its window");
+        const int g = single ? f : (int)(e & 1u);
+        return s->fail(ctx, VS_E_RANGE, too_long_line(s->rd[g].path, s->df[g].first_record + fetch_u32(rec + (single ? e >> 1 : e))));
     }
-    if (s->h_stat[PS_TOO_LONG] != 0xFFFFFFFFu) {
-        const uint32_t e = s->h_stat[PS_TOO_LONG];
-        const int f = (int)(e & 1u);
-        uint32_t at = 0;
-        e1 = hipMemcpy(&at, rec + e, sizeof at, hipMemcpyDeviceToHost);
-        vs_reads_free(ctx, r);
-        char msg[600];
-        snprintf(msg, sizeof msg, "%s: record %llu has a sequence line of more than %u bytes", s->rd[f].path.c_str(),
-                 (unsigned long long)(s->df[f].first_record + (e1 == hipSuccess ? at : 0u)), (unsigned)VS_LEN_MASK);
-        return pn_fail(ctx, s, VS_E_RANGE, msg);
-    }
-    const uint64_t words = s->h_stat[PS_WORDS];
-    r->max_len = s->h_stat[PS_MAXLEN];
-    if ((e1 = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e1, no_buffers);
-    vs_launch_pack_pairs(st, w0, w1, rec, r);
-    if ((e1 = hipGetLastError()) != hipSuccess) return fail(e1);
-    if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + PS_INVALID, s->h_stat + PS_INVALID)) != hipSuccess) return fail(e1);
-    if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
-    s->pair_cur += (uint32_t)n;
-    s->pairs += n;
+    if (single) s->single_cur[f] += (uint32_t)n;
+    else s->pair_cur += (uint32_t)n, s->pairs += n;
     *out = r;
     *n_pairs = n;
     return VS_OK;
@@ -859,7 +739,7 @@ static int pn_join_text_entry(const char *who, vs_ctx *ctx, const uint8_t *text0
         VS_HIP(ctx, hipMemcpyAsync(srec[f].ptr(), hl[f].data(), sizeof(uint32_t) * hl[f].size(), hipMemcpyHostToDevice, st));
     }
     jd.n_pairs = P;
-    if (int rc = pn_singles_device(ctx, st, w[0].n_rec, w[1].n_rec, dec, jd, srec[0].as<uint32_t>() + guard, srec[1].as<uint32_t>() + guard, stat.as<uint32_t>() + PS_WORDS))
+    if (int rc = pn_singles_device(ctx, st, w[0].n_rec, w[1].n_rec, dec, jd, srec[0].as<uint32_t>() + guard, srec[1].as<uint32_t>() + guard, stat.as<uint32_t>() + PS_BLOCK + VS_BLK_WORDS))
         return rc;
     for (int f = 0; f < 2; f++) VS_HIP(ctx, hipMemcpyAsync(hl[f].data(), srec[f].ptr(), sizeof(uint32_t) * hl[f].size(), hipMemcpyDeviceToHost, st));
     VS_HIP(ctx, hipStreamSynchronize(st));

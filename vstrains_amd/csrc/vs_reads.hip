@@ -14,11 +14,19 @@
 #define TPB 256
 
 // Where the characters of a block's ends come from: open(e) = end e, with its length `len` and its character at(p), p < len.
+// For the ends kernel of a block built on the device, length(e, bad) = that length alone -- or `bad` set where the source cannot
+// give one (its list names a record outside the window): the pack kernel then never runs, so open() need not test again.
+// `singles`: the source yields singles blocks, its odd ends are absent and neither method is asked for them.
 struct PackBytes {  // an end that lies in memory as it reads
     const uint8_t *q;
     uint32_t len;
     __device__ uint8_t at(uint32_t p) const { return q[p]; }
 };
+// the sequence line of record r of a window, without its newline
+__device__ __forceinline__ PackBytes pack_line(const SlWin &w, uint32_t r) {
+    const uint32_t start = w.ends[4u * r] + 1u;
+    return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
+}
 struct PackText {  // the caller's text: end e is ascii[aoff[e], aoff[e + 1])
     const uint8_t *ascii;
     const uint64_t *aoff;
@@ -27,43 +35,42 @@ struct PackText {  // the caller's text: end e is ascii[aoff[e], aoff[e + 1])
         return PackBytes{ascii + a, (uint32_t)(aoff[e + 1] - a)};
     }
 };
-struct PackLines {  // the windows of the streamed ingest: end e is line 4 (e / 2) + 1 of file e & 1, without its newline
+struct PackLines {  // the windows of the streamed ingest: end e is line 4 (e / 2) + 1 of file e & 1
+    static constexpr bool singles = false;
     SlWin f0, f1;
-    __device__ PackBytes open(uint32_t e) const {
-        const SlWin &w = (e & 1u) ? f1 : f0;
-        const uint32_t r = e >> 1;
-        const uint32_t start = w.ends[4u * r] + 1u;
-        return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
-    }
+    __device__ PackBytes open(uint32_t e) const { return pack_line((e & 1u) ? f1 : f0, e >> 1); }
+    __device__ uint32_t length(uint32_t e, bool &) const { return open(e).len; }
 };
-struct PackRecords {  // ONE window of the interleaved ingest: end e is line 4 rec[e] + 1 of it, without its newline
+struct PackRecords {  // ONE window of the interleaved ingest: end e is line 4 rec[e] + 1 of it
+    static constexpr bool singles = false;
     SlWin w;
     const uint32_t *rec;
-    __device__ PackBytes open(uint32_t e) const {
-        const uint32_t r = rec[e];
-        const uint32_t start = w.ends[4u * r] + 1u;
-        return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
-    }
+    __device__ PackBytes open(uint32_t e) const { return pack_line(w, rec[e]); }
+    __device__ uint32_t length(uint32_t e, bool &) const { return open(e).len; }
 };
-struct PackSingles {  // ONE window, unpaired reads: even end e is line 4 r + 1 of it, r = rec[e / 2] (rec == NULL: first + e / 2); odd ends are empty
+struct PackSingles {  // ONE window, unpaired reads: even end e is line 4 r + 1 of it, r = rec[e / 2] (rec == NULL: first + e / 2)
+    static constexpr bool singles = true;
     SlWin w;
     const uint32_t *rec;
     uint32_t first;
-    __device__ PackBytes open(uint32_t e) const {
-        if (e & 1u) return PackBytes{w.txt, 0u};
-        const uint32_t r = rec ? rec[e >> 1] : first + (e >> 1);
-        const uint32_t start = w.ends[4u * r] + 1u;
-        return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
-    }
+    __device__ PackBytes open(uint32_t e) const { return pack_line(w, rec ? rec[e >> 1] : first + (e >> 1)); }
+    __device__ uint32_t length(uint32_t e, bool &) const { return open(e).len; }
 };
-struct PackPairs {  // TWO windows joined by name (vs_pair_names.hip): end e is line 4 rec[e] + 1 of file e & 1, without its newline
+struct PackPairs {  // TWO windows joined by name (vs_pair_names.hip): end e is line 4 rec[e] + 1 of file e & 1, n_rec[e & 1] records
+    static constexpr bool singles = false;
     SlWin f0, f1;
+    uint32_t n_rec[2];
     const uint32_t *rec;
-    __device__ PackBytes open(uint32_t e) const {
+    __device__ PackBytes open(uint32_t e) const { return pack_line((e & 1u) ? f1 : f0, rec[e]); }
+    __device__ uint32_t length(uint32_t e, bool &bad) const {  // (every rec index range-tested: the join is new each round)
         const SlWin &w = (e & 1u) ? f1 : f0;
         const uint32_t r = rec[e];
-        const uint32_t start = w.ends[4u * r] + 1u;
-        return PackBytes{w.txt + start, w.ends[4u * r + 1u] - start};
+        if (r < n_rec[e & 1u] && 4ull * r + 1u < w.n_nl) {
+            const uint32_t start = w.ends[4u * r] + 1u, stop = w.ends[4u * r + 1u];
+            if (start <= stop && stop <= w.size) return stop - start;
+        }
+        bad = true;
+        return 0u;
     }
 };
 struct PackBamEnd {  // 4-bit bases, read backwards and complemented where the record's flag has 0x10
@@ -72,21 +79,27 @@ struct PackBamEnd {  // 4-bit bases, read backwards and complemented where the r
     bool rev;
     __device__ uint8_t at(uint32_t p) const { return bam_base(seq, len, rev, p); }
 };
-struct PackBam {  // the records of a window of the BAM ingest
+// record r of the scanned window of the BAM ingest; its l_seq, or `bad` where the window has no record r
+__device__ __forceinline__ PackBamEnd pack_bam_rec(const uint8_t *win, const uint32_t *recs, uint32_t r) {
+    const uint32_t *q = recs + 4u * (size_t)r;
+    return PackBamEnd{win + q[3], q[2], (q[1] & 0x10u) != 0u};
+}
+__device__ __forceinline__ uint32_t pack_bam_len(const uint32_t *recs, uint32_t n_rec, uint32_t r, bool &bad) {
+    if (r < n_rec) return recs[4u * (size_t)r + 2u];
+    bad = true;  // (never: the lists hold records of this window)
+    return 0u;
+}
+struct PackBam {  // the records of a window of the BAM ingest: end e is record ends[e]
+    static constexpr bool singles = false;
     BamEnds b;
-    __device__ PackBamEnd open(uint32_t e) const {
-        const uint32_t *r = b.recs + 4u * (size_t)b.ends[e];
-        return PackBamEnd{b.win + r[3], r[2], (r[1] & 0x10u) != 0u};
-    }
+    __device__ PackBamEnd open(uint32_t e) const { return pack_bam_rec(b.win, b.recs, b.ends[e]); }
+    __device__ uint32_t length(uint32_t e, bool &bad) const { return pack_bam_len(b.recs, b.n_rec, b.ends[e], bad); }
 };
-struct PackBamSingles {  // the kept singletons of the BAM ingest: even end e is record list[e / 2] of the window, odd ends are empty
+struct PackBamSingles {  // the kept singletons of the BAM ingest: even end e is record list[e / 2] of the window
+    static constexpr bool singles = true;
     BamSingles b;
-    __device__ PackBamEnd open(uint32_t e) const {
-        const uint32_t i = (e & 1u) ? b.n_rec : b.list[e >> 1];
-        if (i >= b.n_rec) return PackBamEnd{b.win, 0u, false};  // (an odd end; never a list entry: the list holds records of the window)
-        const uint32_t *r = b.recs + 4u * (size_t)i;
-        return PackBamEnd{b.win + r[3], r[2], (r[1] & 0x10u) != 0u};
-    }
+    __device__ PackBamEnd open(uint32_t e) const { return pack_bam_rec(b.win, b.recs, b.list[e >> 1]); }
+    __device__ uint32_t length(uint32_t e, bool &bad) const { return pack_bam_len(b.recs, b.n_rec, b.list[e >> 1], bad); }
 };
 
 // one thread per packed word; mask (may be NULL) beside the words
@@ -126,38 +139,36 @@ static void launch_pack(hipStream_t st, const Src &src, const vs_reads *r) {
         hipLaunchKernelGGL(k_pack_reads<Src>, dim3((unsigned)((r->n_words + TPB - 1) / TPB)), dim3(TPB), 0, st, src, (const uint32_t *)r->d_woff,
                            (uint32_t)r->n_ends, (uint32_t)r->n_words, (uint32_t *)r->d_words, (uint32_t *)r->d_mask, (uint32_t *)r->d_meta);
 }
-void vs_launch_pack_lines(hipStream_t st, const SlWin &f0, const SlWin &f1, const vs_reads *r) { launch_pack(st, PackLines{f0, f1}, r); }
-void vs_launch_pack_records(hipStream_t st, const SlWin &w, const uint32_t *rec, const vs_reads *r) { launch_pack(st, PackRecords{w, rec}, r); }
-void vs_launch_pack_pairs(hipStream_t st, const SlWin &f0, const SlWin &f1, const uint32_t *rec, const vs_reads *r) { launch_pack(st, PackPairs{f0, f1, rec}, r); }
-void vs_launch_pack_bam(hipStream_t st, const BamEnds &b, const vs_reads *r) { launch_pack(st, PackBam{b}, r); }
-void vs_launch_pack_bam_singles(hipStream_t st, const BamSingles &b, const vs_reads *r) { launch_pack(st, PackBamSingles{b}, r); }
 
-// The lengths of a singles block: one thread per end (and one more for the closing word offset).  Even end e is the sequence
-// line of its record (as PackSingles reads it): meta = its length, wcnt = its packed words; odd ends are absent: no length,
-// no words, VS_FLAG_ABSENT.  st4[0] = the longest read (atomicMax), st4[1] = the first even end over the 24-bit limit (atomicMin).
+// The lengths of a block built on the device: one thread per end (and one more for the closing word offset).  meta = the
+// length of end e as its source gives it, wcnt = its packed words; the odd ends of a singles source are absent: no length, no
+// words, VS_FLAG_ABSENT.  st: the builder's status words -- the longest end (atomicMax), the first end that stops the block
+// (atomicMin; an end its source faults comes before any that is merely over the 24-bit limit: VS_BLK_OVER, e < 2^31).
+template <class Src>
 __global__ void __launch_bounds__(TPB)
-k_single_ends(PackSingles src, uint32_t n_ends, uint32_t *__restrict__ meta, uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st4) {
+k_block_ends(Src src, uint32_t n_ends, uint32_t *__restrict__ meta, uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
     const uint32_t e = blockIdx.x * TPB + threadIdx.x;
     if (e > n_ends) return;
     if (e == n_ends) {
         wcnt[e] = 0u;
         return;
     }
-    if (e & 1u) {
+    if (Src::singles && (e & 1u)) {
         meta[e] = VS_FLAG_ABSENT << 24;
         wcnt[e] = 0u;
         return;
     }
-    const uint32_t len = src.open(e).len;  // (the character dropped is the newline)
-    if (len > VS_LEN_MASK) {
-        atomicMin(&st4[1], e);
+    bool bad = false;
+    const uint32_t len = src.length(e, bad);
+    if (bad || len > VS_LEN_MASK) {
+        atomicMin(&st[VS_BLK_BAD], bad ? e : e | VS_BLK_OVER);
         meta[e] = 0u;
         wcnt[e] = 0u;
         return;
     }
     meta[e] = len;
     wcnt[e] = (len + 15u) >> 4;
-    atomicMax(&st4[0], len);
+    atomicMax(&st[VS_BLK_MAXLEN], len);
 }
 
 __global__ void __launch_bounds__(TPB)
@@ -299,43 +310,56 @@ hipError_t vs_reads_finish(vs_ctx *ctx, hipStream_t st, vs_reads *r, uint32_t *d
     return hipGetLastError();
 }
 
-hipError_t vs_reads_singles_block(vs_ctx *ctx, hipStream_t st, const SlWin &win, const uint32_t *rec, uint32_t first, uint64_t n_reads, VsDevBuf &wcnt,
-                                  uint32_t *d4, uint32_t *h4, vs_reads **out) {
+// THE builder of a block cut on the device (VsBlockJob, vs_internal.h): every streamed ingest ends here.
+template <class Src>
+static hipError_t build_block(const VsBlockJob &j, const Src &src, vs_reads **out) {
     *out = nullptr;
-    const uint64_t n_ends = 2u * n_reads;
-    hipError_t e = wcnt.reserve(sizeof(uint32_t) * (n_ends + 1u));
+    vs_ctx *ctx = j.ctx;
+    hipStream_t st = j.st;
+    const uint64_t n_ends = j.n_ends;
+    const size_t b_wcnt = sizeof(uint32_t) * (n_ends + 1u);
+    hipError_t e = j.wcnt->reserve(b_wcnt, b_wcnt + b_wcnt / 4u);  // (the stream is idle between blocks: nothing still reads it)
     if (e != hipSuccess) return e;
+    uint32_t *wcnt = j.wcnt->as<uint32_t>();
     vs_reads *r = new vs_reads();
     r->cached = true;
-    r->unpaired = true;
+    r->unpaired = Src::singles;
     auto fail = [&](hipError_t e1) {  // (the block goes back)
         vs_reads_free(ctx, r);
         return e1;
     };
     if ((e = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true)) != hipSuccess) return fail(e);
-    e = hipMemsetAsync(d4, 0, sizeof(uint32_t) * 4u, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d4 + 1, 0xFF, sizeof(uint32_t), st);
+    e = hipMemsetAsync(j.d_st, 0, sizeof(uint32_t) * VS_BLK_ST, st);
+    if (e == hipSuccess) e = hipMemsetAsync(j.d_st + VS_BLK_BAD, 0xFF, sizeof(uint32_t), st);
     if (e != hipSuccess) return fail(e);
-    const PackSingles src{win, rec, first};
-    hipLaunchKernelGGL(k_single_ends, dim3((unsigned)((n_ends + 1u + TPB - 1u) / TPB)), dim3(TPB), 0, st, src, (uint32_t)n_ends, (uint32_t *)r->d_meta,
-                       wcnt.as<uint32_t>(), d4);
+    hipLaunchKernelGGL(k_block_ends<Src>, dim3((unsigned)((n_ends + 1u + TPB - 1u) / TPB)), dim3(TPB), 0, st, src, (uint32_t)n_ends, (uint32_t *)r->d_meta, wcnt,
+                       j.d_st);
     if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    vs_launch_scan_u32(st, wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), d4 + 2);
-    e = hipMemcpyAsync(r->d_woff, wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h4, d4, sizeof(uint32_t) * 4u, hipMemcpyDeviceToHost, st);
+    vs_launch_scan_u32(st, wcnt, (uint32_t)(n_ends + 1u), j.d_st + VS_BLK_WORDS);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(e);
+    e = hipMemcpyAsync(r->d_woff, wcnt, sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(j.h_st, j.d_st, sizeof(uint32_t) * j.n_st, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(e);
-    if (h4[1] != 0xFFFFFFFFu) return fail(hipSuccess);  // a read over the limit: no block, the caller names the record
-    const uint64_t words = h4[2];
-    r->max_len = h4[0];
+    if (j.h_st[VS_BLK_BAD] != 0xFFFFFFFFu) return fail(hipSuccess);  // no block: the caller words what VS_BLK_BAD says
+    const uint64_t words = j.h_st[VS_BLK_WORDS];
+    r->max_len = j.h_st[VS_BLK_MAXLEN];
     if ((e = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e);
     launch_pack(st, src, r);
     if ((e = hipGetLastError()) != hipSuccess) return fail(e);
-    if ((e = vs_reads_finish(ctx, st, r, d4 + 3, h4 + 3)) != hipSuccess) return fail(e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e);  // (the block is complete when it is handed out)
+    if ((e = vs_reads_finish(ctx, st, r, j.d_st + VS_BLK_INVALID, j.h_st + VS_BLK_INVALID)) != hipSuccess) return fail(e);
+    if (!j.more && (e = hipStreamSynchronize(st)) != hipSuccess) return fail(e);  // (the block is complete when it is handed out)
     *out = r;
     return hipSuccess;
 }
+hipError_t vs_block_lines(const VsBlockJob &j, const SlWin &f0, const SlWin &f1, vs_reads **out) { return build_block(j, PackLines{f0, f1}, out); }
+hipError_t vs_block_records(const VsBlockJob &j, const SlWin &w, const uint32_t *rec, vs_reads **out) { return build_block(j, PackRecords{w, rec}, out); }
+hipError_t vs_block_singles(const VsBlockJob &j, const SlWin &w, const uint32_t *rec, uint32_t first, vs_reads **out) { return build_block(j, PackSingles{w, rec, first}, out); }
+hipError_t vs_block_pairs(const VsBlockJob &j, const SlWin &f0, uint32_t n_rec0, const SlWin &f1, uint32_t n_rec1, const uint32_t *rec, vs_reads **out) {
+    return build_block(j, PackPairs{f0, f1, {n_rec0, n_rec1}, rec}, out);
+}
+hipError_t vs_block_bam(const VsBlockJob &j, const BamEnds &b, vs_reads **out) { return build_block(j, PackBam{b}, out); }
+hipError_t vs_block_bam_singles(const VsBlockJob &j, const BamSingles &b, vs_reads **out) { return build_block(j, PackBamSingles{b}, out); }
 
 extern "C" void vs_reads_free(vs_ctx *ctx, vs_reads *r) {
     if (!r) return;

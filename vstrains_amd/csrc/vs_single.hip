@@ -5,9 +5,8 @@
 // Per window (the leftover of the one before + the slot appended):
 //   k_sl_count / k_sl_scan / k_sl_scatter   the line ends, as for the two-file stream (vs_stream_lines.h); a flagged window
 //                                           ('\r', a byte >= 0x80) goes through host text mode first.
-// A block of n reads from the cursor is a SINGLES block (vs_reads_singles_block, vs_reads.hip): k_single_ends (lengths and word
-// counts of the records cursor ..., every second end absent), k_sl_scan (word offsets), k_pack_reads<PackSingles>,
-// vs_reads_finish -- the layout vs_pe_count takes.  When the window's records are out it is cut behind the last of them; the
+// A block of n reads from the cursor is a SINGLES block, cut by the block builder (vs_block_singles, vs_reads.hip) from the
+// records cursor ..., every second end absent -- the layout vs_pe_count takes.  When the window's records are out it is cut behind the last of them; the
 // partial record leads the next window.  A trailing partial record at the end of the file is dropped, as the reference drops
 // it from either of its files (len(lines) // 4).
 // The host reads back counts, the cut and status words; no record text.
@@ -21,38 +20,26 @@ namespace {
 
 // status words of a stream (the first ST_PER_FILE are the line scanner's)
 enum {
-    SS_BLOCK = 4,  // four words of vs_reads_singles_block: longest read, first end over the limit, words, invalid ends
+    SS_BLOCK = 4,  // the VS_BLK_ST words of the block builder
     SS_BAD = 8,    // the first BGZF member the device rejected (a running index), ~0u: none
     SS_ALL = 12
 };
 
 }  // namespace
 
-struct vs_fastq_se {
+struct vs_fastq_se : StreamState {  // (SS_ALL status words)
     int device = 0;
     hipStream_t st = nullptr;
     Reader rd;
     DevFile df;  // the one window, its line ends
     bool scanned = false;  // df describes the window: line ends scattered, records counted
     uint32_t rec_cur = 0;  // the first record of the scanned window not yet delivered
-    VsDevBuf stat_buf, d_wcnt;
-    VsPinnedBuf h_stat_buf;
-    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // SS_ALL words each
+    VsDevBuf d_wcnt;
     uint64_t reads = 0, records = 0;
     uint32_t flags_seen = 0;
-    bool done = false;
-    int failed = VS_OK;
-    std::string failed_msg;
 };
 
 namespace {
-
-int se_fail(vs_ctx *ctx, vs_fastq_se *s, int code, const std::string &msg) {
-    s->done = true;
-    s->failed = code;
-    s->failed_msg = msg;
-    return vs_fail(ctx, code, "%s", msg.c_str());
-}
 
 // count + scan of the window: its line ends counted, flags, records (synchronises the stream)
 int se_scan(vs_ctx *ctx, vs_fastq_se *s) {
@@ -76,7 +63,7 @@ int se_next_window(vs_ctx *ctx, vs_fastq_se *s, bool *end) {
     *end = true;
     if (s->scanned) {
         if (d.eof) {  // the end of the input: the reader's failure, if it had one
-            if (s->rd.err != VS_OK) return se_fail(ctx, s, s->rd.err, s->rd.err_msg);
+            if (s->rd.err != VS_OK) return s->fail(ctx, s->rd.err, s->rd.err_msg);
             s->done = true;
             return VS_OK;
         }
@@ -87,25 +74,25 @@ int se_next_window(vs_ctx *ctx, vs_fastq_se *s, bool *end) {
             VS_HIP(ctx, hipMemcpyAsync(&at, d.ends.as<uint32_t>() + (4u * (size_t)out - 1u), sizeof at, hipMemcpyDeviceToHost, st));
             VS_HIP(ctx, hipStreamSynchronize(st));
             cut = (size_t)at + 1u;
-            if (cut > d.w.size) return se_fail(ctx, s, VS_E_STATE, s->rd.path + ": a line end beyond the window");
+            if (cut > d.w.size) return s->fail(ctx, VS_E_STATE, s->rd.path + ": a line end beyond the window");
         }
-        if (int rc = drop_front(ctx, st, d, cut, out)) return se_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = drop_front(ctx, st, d, cut, out)) return s->fail(ctx, rc, vs_last_error(ctx));
         s->scanned = false;
         s->rec_cur = 0;
     }
     {
         SlotLease taken;  // (goes back once the stream is synchronised: the upload is done)
-        if (int rc = append_chunk(ctx, st, d, s->rd, taken, s->d_stat + SS_BAD)) return se_fail(ctx, s, rc, vs_last_error(ctx));
-        if (int rc = se_scan(ctx, s)) return se_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = append_chunk(ctx, st, d, s->rd, taken, s->d_stat + SS_BAD)) return s->fail(ctx, rc, vs_last_error(ctx));
+        if (int rc = se_scan(ctx, s)) return s->fail(ctx, rc, vs_last_error(ctx));
         if (taken) (void)member_failed(d, s->rd, *taken, s->h_stat[SS_BAD]);
     }
     if (d.err == VS_OK && d.flags && d.validated < d.w.size) {  // (text that arrived with this slot: host text mode)
         if (translate_window(ctx, d, s->rd.path) == VS_OK)
-            if (int rc = se_scan(ctx, s)) return se_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = se_scan(ctx, s)) return s->fail(ctx, rc, vs_last_error(ctx));
     }
-    if (d.err != VS_OK) return se_fail(ctx, s, s->rd.err != VS_OK ? s->rd.err : d.err, s->rd.err != VS_OK ? s->rd.err_msg : d.err_msg);
-    if (d.records > (1ull << 30)) return se_fail(ctx, s, VS_E_RANGE, s->rd.path + ": more than 2^30 records in one window");
-    if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return se_fail(ctx, s, rc, vs_last_error(ctx));
+    if (d.err != VS_OK) return s->fail(ctx, s->rd.err != VS_OK ? s->rd.err : d.err, s->rd.err != VS_OK ? s->rd.err_msg : d.err_msg);
+    if (d.records > (1ull << 30)) return s->fail(ctx, VS_E_RANGE, s->rd.path + ": more than 2^30 records in one window");
+    if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return s->fail(ctx, rc, vs_last_error(ctx));
     vs_launch_sl_scatter(st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
     VS_HIP(ctx, hipGetLastError());
     s->scanned = true;
@@ -125,20 +112,14 @@ int vs_fastq_se_open(vs_ctx *ctx, const char *path, vs_fastq_se **out) {
     vs_fastq_se *s = new vs_fastq_se();
     s->device = ctx->device;
     Reader &r = s->rd;
-    if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
-    if (const char *ev = getenv("VS_GZIP_DEVICE")) r.gzip_device = strcmp(ev, "1") == 0;
-    if (const char *ev = getenv("VS_GZIP_TEXT")) s->df.w.gz.text_cap = (uint32_t)std::max<long long>(1, atoll(ev));  // (tests only, as VS_STREAM_CHUNK)
+    fastq_switches(r, false, s->df.w.gz.text_cap);
     if (int rc = r.open_file(ctx, path)) {
         delete s;
         return rc;
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
-    if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * SS_ALL);
-    s->d_stat = s->stat_buf.as<uint32_t>();
-    if (e1 == hipSuccess) e1 = hipMemset(s->d_stat, 0, sizeof(uint32_t) * SS_ALL);
+    if (e1 == hipSuccess) e1 = s->reserve_stat(SS_ALL);
     if (e1 == hipSuccess) e1 = hipMemset(s->d_stat + SS_BAD, 0xFF, sizeof(uint32_t));
-    if (e1 == hipSuccess) e1 = s->h_stat_buf.reserve(sizeof(uint32_t) * SS_ALL);
-    s->h_stat = s->h_stat_buf.as<uint32_t>();
     if (e1 != hipSuccess) {
         vs_fastq_se_close(s);
         return vs_fail(ctx, VS_E_HIP, "vs_fastq_se_open: %s", hipGetErrorString(e1));
@@ -152,7 +133,7 @@ int vs_fastq_se_next(vs_ctx *ctx, vs_fastq_se *s, uint64_t max_reads, vs_reads *
     if (!ctx || !s || !out || !n_reads) return vs_fail(ctx, VS_E_ARG, "vs_fastq_se_next: bad argument");
     *out = nullptr;
     *n_reads = 0;
-    if (s->failed != VS_OK) return vs_fail(ctx, s->failed, "%s", s->failed_msg.c_str());
+    if (s->failed != VS_OK) return s->again(ctx);
     if (s->done) return VS_OK;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     if (!max_reads || max_reads > (1ull << 30)) max_reads = 1ull << 30;
@@ -166,15 +147,11 @@ int vs_fastq_se_next(vs_ctx *ctx, vs_fastq_se *s, uint64_t max_reads, vs_reads *
     const uint64_t n = std::min<uint64_t>(d.records - s->rec_cur, max_reads);
     const SlWin win = {d.w.data(), d.ends.as<const uint32_t>(), d.n_nl, (uint32_t)d.w.size};
     vs_reads *r = nullptr;
-    const hipError_t e1 = vs_reads_singles_block(ctx, s->st, win, nullptr, s->rec_cur, n, s->d_wcnt, s->d_stat + SS_BLOCK, s->h_stat + SS_BLOCK, &r);
-    if (e1 == hipErrorOutOfMemory) return se_fail(ctx, s, VS_E_OOM, "vs_fastq_se_next: device buffers for the block");
-    if (e1 != hipSuccess) return se_fail(ctx, s, VS_E_HIP, std::string("vs_fastq_se_next: ") + hipGetErrorString(e1));
-    if (!r) {
-        char msg[600];
-        snprintf(msg, sizeof msg, "%s: record %llu has a sequence line of more than %u bytes", s->rd.path.c_str(),
-                 (unsigned long long)(d.first_record + s->rec_cur + (s->h_stat[SS_BLOCK + 1] >> 1)), (unsigned)VS_LEN_MASK);
-        return se_fail(ctx, s, VS_E_RANGE, msg);
-    }
+    const VsBlockJob job = {ctx, s->st, 2u * n, &s->d_wcnt, s->d_stat + SS_BLOCK, s->h_stat + SS_BLOCK, VS_BLK_ST, false};
+    const hipError_t e1 = vs_block_singles(job, win, nullptr, s->rec_cur, &r);
+    if (e1 != hipSuccess) return s->fail_hip(ctx, "vs_fastq_se_next", e1);
+    if (!r)  // (a singles source faults no end: the end is over the limit)
+        return s->fail(ctx, VS_E_RANGE, too_long_line(s->rd.path, d.first_record + s->rec_cur + ((s->h_stat[SS_BLOCK + VS_BLK_BAD] & ~VS_BLK_OVER) >> 1)));
     s->rec_cur += (uint32_t)n;
     s->reads += n;
     *out = r;

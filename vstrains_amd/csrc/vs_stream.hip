@@ -34,11 +34,11 @@
 //   k_sl_scatter  the lane's rank among the newlines of its wavefront from __ballot, + its wavefront's and workgroup's
 //                 base: the byte offset of every line end;
 // then, for the n = min(complete records of fwd, of rve) pairs of the block:
-//   k_sl_ends     length (line 4r+1 minus its newline) and packed words of every end, the record cuts;
-//   k_sl_scan     word offsets;
-// and from there on as every read block is built (vs_reads.hip): k_pack_reads, one thread per packed word, straight from
-// the windows, the mask beside the words; k_count_invalid, and k_inv4 when some end needs it.  The block is the layout
-// vs_pe_count takes.
+//   k_sl_cut      the record cuts behind the block, one thread per file;
+// and from there on as every block of a streamed ingest is built, by the block builder (build_block of vs_reads.hip, here
+// vs_block_lines): k_block_ends, length (line 4r+1 minus its newline) and packed words of every end; k_sl_scan, word offsets;
+// k_pack_reads, one thread per packed word, straight from the windows, the mask beside the words; k_count_invalid, and k_inv4
+// when some end needs it.  The block is the layout vs_pe_count takes.
 //
 // A window whose scan raises a flag ('\r' or a byte >= 0x80) keeps the reference's text-mode semantics on the host
 // (rare): its complete lines are copied back, universal newlines applied ("\r\n" and a lone '\r' end a line; a '\r' at
@@ -81,7 +81,7 @@ namespace {
 
 // per-window status the kernels write (one uint32 array per stream, read back in one copy)
 // ([f * ST_PER_FILE + ST_NL / ST_FLAGS / ST_LAST]: vs_stream_lines.h)
-enum { ST_MAXLEN = 8, ST_TOO_LONG = 9, ST_WORDS = 10, ST_INVALID = 11, ST_CUT = 12 /* + f */, ST_N = 16 };
+enum { ST_BLOCK = 8 /* the VS_BLK_ST words of the block builder */, ST_CUT = 12 /* + f: behind them, read back with them */, ST_N = 16 };
 enum { ST_BAD = ST_N /* + f: the first member of file f the device rejected (a running index), ~0u: none */, ST_ALL = ST_N + 2 };
 
 }  // namespace
@@ -227,62 +227,28 @@ void vs_launch_sl_scatter(hipStream_t st, const uint8_t *txt, uint64_t n, const 
     if (wgs) hipLaunchKernelGGL(k_sl_scatter, dim3((unsigned)wgs), dim3(SL_TPB), 0, st, txt, n, wg, ends);
 }
 
-// one thread per end of the block (and one more for the closing word offset): length, packed words, the longest end, the
-// first end over the 24-bit limit; thread 0 also writes the record cuts (one past the newline of line 4n - 1)
-__global__ void __launch_bounds__(SL_TPB) k_sl_ends(SlWin f0, SlWin f1, uint32_t n_pairs, uint32_t *__restrict__ meta,
-                                                    uint32_t *__restrict__ wcnt, uint32_t *__restrict__ st) {
-    const uint32_t e = blockIdx.x * SL_TPB + threadIdx.x, n_ends = 2u * n_pairs;
-    if (e == 0) {
-        const uint32_t last = 4u * n_pairs - 1u;
-        st[ST_CUT + 0] = last < f0.n_nl ? f0.ends[last] + 1u : f0.size;
-        st[ST_CUT + 1] = last < f1.n_nl ? f1.ends[last] + 1u : f1.size;
-    }
-    if (e > n_ends) return;
-    if (e == n_ends) {
-        wcnt[e] = 0u;
-        return;
-    }
-    const SlWin &w = (e & 1u) ? f1 : f0;
-    const uint32_t r = e >> 1;
-    const uint32_t start = w.ends[4u * r] + 1u, len = w.ends[4u * r + 1u] - start;  // (the character dropped is the newline)
-    if (len > VS_LEN_MASK) {
-        atomicMin(&st[ST_TOO_LONG], e);
-        meta[e] = 0u;
-        wcnt[e] = 0u;
-        return;
-    }
-    meta[e] = len;
-    wcnt[e] = (len + 15u) >> 4;
-    atomicMax(&st[ST_MAXLEN], len);
+// two threads, one per file: the record cut behind a block of n_pairs pairs (one past the newline of line 4 n_pairs - 1)
+__global__ void __launch_bounds__(VS_WAVE) k_sl_cut(SlWin f0, SlWin f1, uint32_t n_pairs, uint32_t *__restrict__ cut) {
+    if (threadIdx.x >= 2u) return;
+    const SlWin &w = threadIdx.x ? f1 : f0;
+    const uint32_t last = 4u * n_pairs - 1u;
+    cut[threadIdx.x] = last < w.n_nl ? w.ends[last] + 1u : w.size;
 }
 
 // ---- host side (the reader: vs_stream_reader.h; one file's window and line ends: DevFile of vs_stream_lines.h) -------------
-struct vs_fastq_stream {
+struct vs_fastq_stream : StreamState {  // (ST_ALL status words)
     int device = 0;
     hipStream_t st = nullptr;
     Reader rd[2];
     DevFile df[2];
-    VsDevBuf stat_buf;
-    VsPinnedBuf h_stat_buf;
-    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // ST_ALL words each, in the two buffers above
     VsDevBuf d_wcnt;  // uint32
     uint64_t pairs = 0;
     uint64_t limit = ~0ull;  // pairs to deliver (a member range: the rank's own)
     bool ranged = false;
     uint32_t flags_seen = 0;
-    bool done = false;
-    int failed = VS_OK;
-    std::string failed_msg;
 };
 
 namespace {
-
-int stream_fail(vs_ctx *ctx, vs_fastq_stream *s, int code, const std::string &msg) {
-    s->done = true;
-    s->failed = code;
-    s->failed_msg = msg;
-    return vs_fail(ctx, code, "%s", msg.c_str());
-}
 
 // count + scan of window f: n_nl, flags, last byte into the host status (synchronises the stream)
 int scan_windows(vs_ctx *ctx, vs_fastq_stream *s, int only = -1) {
@@ -356,11 +322,11 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
                 d.w.size = 0;
                 int rc = append_gzip(ctx, s->st, d, r, nullptr);
                 if (rc == VS_OK) rc = scan_windows(ctx, s, f);
-                if (rc != VS_OK) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+                if (rc != VS_OK) return s->fail(ctx, rc, vs_last_error(ctx));
                 if (d.err == VS_OK && ((d.flags & FL_HIGH) || d.n_pend)) {
                     std::vector<uint8_t> buf(d.w.size);
                     if (d.w.size && hipMemcpy(buf.data(), d.w.data(), d.w.size, hipMemcpyDeviceToHost) != hipSuccess)
-                        return stream_fail(ctx, s, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
+                        return s->fail(ctx, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
                     if (!check_piece(d, buf.data(), buf.size(), d.eof)) {
                         d.err = VS_E_UTF8;
                         d.err_msg = r.path + " holds bytes that are not valid UTF-8 (the reference's text-mode read raises UnicodeDecodeError)";
@@ -379,12 +345,12 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
                 int rc = append_slot(ctx, s->st, d, r, sl, s->d_stat + ST_BAD + f);
                 if (rc == VS_OK) rc = scan_windows(ctx, s, f);
                 if (rc != VS_OK) {
-                    return stream_fail(ctx, s, rc, vs_last_error(ctx));
+                    return s->fail(ctx, rc, vs_last_error(ctx));
                 }
                 if (!member_failed(d, r, sl, s->h_stat[ST_BAD + f]) && d.err == VS_OK && ((d.flags & FL_HIGH) || d.n_pend)) {
                     std::vector<uint8_t> buf(d.w.size);
                     if (d.w.size && hipMemcpy(buf.data(), d.w.data(), d.w.size, hipMemcpyDeviceToHost) != hipSuccess)
-                        return stream_fail(ctx, s, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
+                        return s->fail(ctx, VS_E_HIP, "vs_fastq_stream_next: copying a window back failed");
                     ok = check_piece(d, buf.data(), buf.size(), sl.gz ? d.eof : sl.last);
                 }
                 d.w.size = d.validated = 0;
@@ -408,7 +374,7 @@ int finish(vs_ctx *ctx, vs_fastq_stream *s) {
     }
     s->done = true;
     for (int f = 0; f < 2; f++)
-        if (s->df[f].err != VS_OK) return stream_fail(ctx, s, s->df[f].err, s->df[f].err_msg);
+        if (s->df[f].err != VS_OK) return s->fail(ctx, s->df[f].err, s->df[f].err_msg);
     return VS_OK;
 }
 
@@ -438,9 +404,7 @@ int stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, const u
     const char *paths[2] = {fwd_path, rve_path};
     for (int f = 0; f < 2; f++) {
         Reader &r = s->rd[f];
-        if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
-        if (const char *ev = getenv("VS_GZIP_DEVICE")) r.gzip_device = !range && strcmp(ev, "1") == 0;  // (a member range is BGZF's)
-        if (const char *ev = getenv("VS_GZIP_TEXT")) s->df[f].w.gz.text_cap = (uint32_t)std::max<long long>(1, atoll(ev));  // (tests only, as VS_STREAM_CHUNK)
+        fastq_switches(r, range != nullptr, s->df[f].w.gz.text_cap);
         int rc = r.open_file(ctx, paths[f]);
         struct stat sb;
         if (rc == VS_OK && range && (fstat(r.fd, &sb) != 0 || !S_ISREG(sb.st_mode) || range[3 * f] > range[3 * f + 1] || range[3 * f + 1] > (uint64_t)sb.st_size))
@@ -463,11 +427,8 @@ int stream_open(vs_ctx *ctx, const char *fwd_path, const char *rve_path, const u
         s->limit = n_pairs;
     }
     hipError_t e1 = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
-    if (e1 == hipSuccess) e1 = s->stat_buf.reserve(sizeof(uint32_t) * ST_ALL);
-    s->d_stat = s->stat_buf.as<uint32_t>();
+    if (e1 == hipSuccess) e1 = s->reserve_stat(ST_ALL);
     if (e1 == hipSuccess) e1 = hipMemset(s->d_stat + ST_BAD, 0xFF, sizeof(uint32_t) * 2);
-    if (e1 == hipSuccess) e1 = s->h_stat_buf.reserve(sizeof(uint32_t) * ST_ALL);
-    s->h_stat = s->h_stat_buf.as<uint32_t>();
     if (e1 != hipSuccess) {
         vs_fastq_stream_close(s);
         return vs_fail(ctx, VS_E_HIP, "vs_fastq_stream_open: %s", hipGetErrorString(e1));
@@ -496,7 +457,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     if (!ctx || !s || !out || !n_pairs) return vs_fail(ctx, VS_E_ARG, "vs_fastq_stream_next: bad argument");
     *out = nullptr;
     *n_pairs = 0;
-    if (s->failed != VS_OK) return vs_fail(ctx, s->failed, "%s", s->failed_msg.c_str());
+    if (s->failed != VS_OK) return s->again(ctx);
     if (s->done) return VS_OK;
     VS_HIP(ctx, hipSetDevice(ctx->device));
     if (!max_pairs || max_pairs > (1ull << 30)) max_pairs = 1ull << 30;
@@ -512,12 +473,12 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
             DevFile &d = s->df[f], &o = s->df[f ^ 1];
             const bool need = !d.eof && d.records < max_pairs && d.records <= o.records && !(o.eof && o.records <= d.records);
             if (!need) continue;
-            if (int rc = append_chunk(ctx, s->st, d, s->rd[f], taken[f], s->d_stat + ST_BAD + f)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+            if (int rc = append_chunk(ctx, s->st, d, s->rd[f], taken[f], s->d_stat + ST_BAD + f)) return s->fail(ctx, rc, vs_last_error(ctx));
             fresh[f] = true;
         }
         if (round > 0 && !fresh[0] && !fresh[1]) return finish(ctx, s);  // (nothing more to read and no pair: the end)
         int rc = scan_windows(ctx, s);
-        if (rc) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+        if (rc) return s->fail(ctx, rc, vs_last_error(ctx));
         bool rejected = false;
         for (int f = 0; f < 2; f++)
             if (fresh[f] && ((taken[f] && member_failed(s->df[f], s->rd[f], *taken[f], s->h_stat[ST_BAD + f])) || s->df[f].err != VS_OK)) rejected = true;  // (needs the slot: before it goes back)
@@ -526,14 +487,14 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
         if (s->ranged) {
             // (pass 1 of the sharded open saw neither a '\r' nor a byte >= 0x80 in the whole file, and the plan rests on that)
             if (s->df[0].flags | s->df[1].flags)
-                return stream_fail(ctx, s, VS_E_STATE, s->rd[s->df[0].flags ? 0 : 1].path + " changed after its lines were counted");
+                return s->fail(ctx, VS_E_STATE, s->rd[s->df[0].flags ? 0 : 1].path + " changed after its lines were counted");
             bool skipped = false;
             for (int f = 0; f < 2; f++) {
                 if (!s->df[f].skip || !fresh[f]) continue;  // (the first window of the file; it may arrive a round after the other's)
-                if ((rc = skip_lines(ctx, s, f))) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+                if ((rc = skip_lines(ctx, s, f))) return s->fail(ctx, rc, vs_last_error(ctx));
                 skipped = true;
             }
-            if (skipped && (rc = scan_windows(ctx, s))) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+            if (skipped && (rc = scan_windows(ctx, s))) return s->fail(ctx, rc, vs_last_error(ctx));
         }
         bool again = false;
         for (int f = 0; f < 2; f++) {
@@ -543,7 +504,7 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
                 again = true;
             }
         }
-        if (again && (rc = scan_windows(ctx, s))) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+        if (again && (rc = scan_windows(ctx, s))) return s->fail(ctx, rc, vs_last_error(ctx));
         n = std::min(std::min(s->df[0].records, s->df[1].records), max_pairs);
         if (n > 0) break;
         if ((s->df[0].eof && s->df[0].records == 0) || (s->df[1].eof && s->df[1].records == 0)) return finish(ctx, s);
@@ -553,51 +514,28 @@ int vs_fastq_stream_next(vs_ctx *ctx, vs_fastq_stream *s, uint64_t max_pairs, vs
     const uint64_t n_ends = 2u * n;
     for (int f = 0; f < 2; f++) {
         DevFile &d = s->df[f];
-        if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
+        if (int rc = reserve_n<uint32_t>(ctx, d.ends, (size_t)d.n_nl + 1u)) return s->fail(ctx, rc, vs_last_error(ctx));
         vs_launch_sl_scatter(st, d.w.data(), (uint64_t)d.w.size, d.wg.as<uint32_t>(), d.ends.as<uint32_t>());
     }
-    if (int rc = reserve_n<uint32_t>(ctx, s->d_wcnt, n_ends + 1u)) return stream_fail(ctx, s, rc, vs_last_error(ctx));
     SlWin w0 = {s->df[0].w.data(), s->df[0].ends.as<uint32_t>(), s->df[0].n_nl, (uint32_t)s->df[0].w.size};
     SlWin w1 = {s->df[1].w.data(), s->df[1].ends.as<uint32_t>(), s->df[1].n_nl, (uint32_t)s->df[1].w.size};
-    vs_reads *r = new vs_reads();
-    r->cached = true;
-    // (a failure of the block: it goes back, and the stream has failed)
-    auto fail = [&](hipError_t e, const char *oom_msg = nullptr) {
-        vs_reads_free(ctx, r);
-        if (e == hipErrorOutOfMemory && oom_msg) return stream_fail(ctx, s, VS_E_OOM, oom_msg);
-        return stream_fail(ctx, s, e == hipErrorOutOfMemory ? VS_E_OOM : VS_E_HIP, std::string("vs_fastq_stream_next: ") + hipGetErrorString(e));
-    };
-    const char *no_buffers = "vs_fastq_stream_next: device buffers for the block";
-    hipError_t e1 = vs_reads_alloc(ctx, st, r, n_ends, nullptr, true);
-    if (e1 != hipSuccess) return fail(e1, no_buffers);
-    e1 = hipMemsetAsync(s->d_stat + ST_MAXLEN, 0, sizeof(uint32_t) * (ST_N - ST_MAXLEN), st);
-    if (e1 == hipSuccess) e1 = hipMemsetAsync(s->d_stat + ST_TOO_LONG, 0xFF, sizeof(uint32_t), st);
-    if (e1 != hipSuccess) return fail(e1);
-    hipLaunchKernelGGL(k_sl_ends, dim3((unsigned)((n_ends + 1u + SL_TPB - 1u) / SL_TPB)), dim3(SL_TPB), 0, st, w0, w1, (uint32_t)n,
-                       (uint32_t *)r->d_meta, s->d_wcnt.as<uint32_t>(), s->d_stat);
-    hipLaunchKernelGGL(k_sl_scan, dim3(1), dim3(SL_SCAN_TPB), 0, st, s->d_wcnt.as<uint32_t>(), (uint32_t)(n_ends + 1u), s->d_stat + ST_WORDS);
-    e1 = hipMemcpyAsync(r->d_woff, s->d_wcnt.as<uint32_t>(), sizeof(uint32_t) * (n_ends + 1u), hipMemcpyDeviceToDevice, st);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(s->h_stat, s->d_stat, sizeof(uint32_t) * ST_N, hipMemcpyDeviceToHost, st);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-    if (e1 != hipSuccess) return fail(e1);
-    if (s->h_stat[ST_TOO_LONG] != 0xFFFFFFFFu) {
-        const uint32_t e = s->h_stat[ST_TOO_LONG];
-        const int f = (int)(e & 1u);
-        vs_reads_free(ctx, r);
-        char msg[600];
-        snprintf(msg, sizeof msg, "%s: record %llu has a sequence line of more than %u bytes", s->rd[f].path.c_str(),
-                 (unsigned long long)(s->df[f].first_record + (e >> 1)), (unsigned)VS_LEN_MASK);
-        return stream_fail(ctx, s, VS_E_RANGE, msg);
+    // the record cuts ride back with the builder's words; the windows are cut behind the block, so the last wait is here
+    hipLaunchKernelGGL(k_sl_cut, dim3(1), dim3(VS_WAVE), 0, st, w0, w1, (uint32_t)n, s->d_stat + ST_CUT);
+    const VsBlockJob job = {ctx, st, n_ends, &s->d_wcnt, s->d_stat + ST_BLOCK, s->h_stat + ST_BLOCK, VS_BLK_ST + 2u, true};
+    vs_reads *r = nullptr;
+    hipError_t e1 = vs_block_lines(job, w0, w1, &r);
+    if (e1 != hipSuccess) return s->fail_hip(ctx, "vs_fastq_stream_next", e1);
+    if (!r) {  // (the source faults no end: the end is over the limit)
+        const uint32_t e = s->h_stat[ST_BLOCK + VS_BLK_BAD] & ~VS_BLK_OVER;
+        return s->fail(ctx, VS_E_RANGE, too_long_line(s->rd[e & 1u].path, s->df[e & 1u].first_record + (e >> 1)));
     }
-    const uint64_t words = s->h_stat[ST_WORDS];
-    const size_t cut[2] = {s->h_stat[ST_CUT + 0], s->h_stat[ST_CUT + 1]};
-    r->max_len = s->h_stat[ST_MAXLEN];
-    if ((e1 = vs_reads_alloc(ctx, st, r, n_ends, &words, true)) != hipSuccess) return fail(e1, no_buffers);
-    vs_launch_pack_lines(st, w0, w1, r);
-    if ((e1 = vs_reads_finish(ctx, st, r, s->d_stat + ST_INVALID, s->h_stat + ST_INVALID)) != hipSuccess) return fail(e1);
-    for (int f = 0; f < 2; f++)
-        if (drop_front(ctx, st, s->df[f], cut[f], n) != VS_OK) return fail(hipErrorOutOfMemory);
-    if ((e1 = hipStreamSynchronize(st)) != hipSuccess) return fail(e1);  // (the block is complete when it is handed out)
+    for (int f = 0; f < 2 && e1 == hipSuccess; f++)
+        if (drop_front(ctx, st, s->df[f], s->h_stat[ST_CUT + f], n) != VS_OK) e1 = hipErrorOutOfMemory;
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);  // (the block is complete when it is handed out)
+    if (e1 != hipSuccess) {
+        vs_reads_free(ctx, r);
+        return s->fail_hip(ctx, "vs_fastq_stream_next", e1);
+    }
     s->pairs += n;
     *out = r;
     *n_pairs = n;

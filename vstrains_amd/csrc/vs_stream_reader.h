@@ -314,6 +314,61 @@ struct Reader {
     }
 };
 
+// The open-time switches of a FASTQ stream, for the reader of one of its files: VS_BGZF_DEVICE=0 (BGZF through zlib too),
+// VS_GZIP_DEVICE=1 (plain gzip decoded on the device; never for a member range, which is BGZF's) and VS_GZIP_TEXT (tests only, as
+// VS_STREAM_CHUNK: the text a gzip round may add, for the window's GzStream::text_cap)
+inline void fastq_switches(Reader &r, bool ranged, uint32_t &gz_text_cap) {
+    if (const char *ev = getenv("VS_BGZF_DEVICE")) r.bgzf_device = strcmp(ev, "0") != 0;
+    if (const char *ev = getenv("VS_GZIP_DEVICE")) r.gzip_device = !ranged && strcmp(ev, "1") == 0;
+    if (const char *ev = getenv("VS_GZIP_TEXT")) gz_text_cap = (uint32_t)std::max<long long>(1, atoll(ev));
+}
+
+// What every stream keeps beside its readers: the status words its kernels write and the pinned copy the host reads, and how
+// the stream ended.  A stream that has failed stays failed: every later call reports the stored failure again.
+struct StreamState {
+    VsDevBuf stat_buf;
+    VsPinnedBuf h_stat_buf;
+    uint32_t *d_stat = nullptr, *h_stat = nullptr;  // `words` words each, in the two buffers above
+    bool done = false;
+    int failed = VS_OK;
+    std::string failed_msg;
+
+    hipError_t reserve_stat(uint32_t words) {  // both zeroed
+        hipError_t e = stat_buf.reserve(sizeof(uint32_t) * words);
+        if (e == hipSuccess) e = h_stat_buf.reserve(sizeof(uint32_t) * words);
+        if (e != hipSuccess) return e;
+        d_stat = stat_buf.as<uint32_t>();
+        h_stat = h_stat_buf.as<uint32_t>();
+        memset(h_stat, 0, sizeof(uint32_t) * words);
+        return hipMemset(d_stat, 0, sizeof(uint32_t) * words);
+    }
+    int fail(vs_ctx *ctx, int code, const std::string &msg) {
+        done = true;
+        failed = code;
+        failed_msg = msg;
+        return again(ctx);
+    }
+    int again(vs_ctx *ctx) const {
+        if (ctx) ctx->err = failed_msg;  // (whole: two paths and two header lines of 200 bytes do not fit the formatting buffer of vs_fail)
+        return failed;
+    }
+    // a block that could not be built in entry `who`
+    int fail_hip(vs_ctx *ctx, const char *who, hipError_t e) {
+        if (e == hipErrorOutOfMemory) return fail(ctx, VS_E_OOM, std::string(who) + ": device buffers for the block");
+        return fail(ctx, VS_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+};
+
+// the refusal of a FASTQ record (numbered in file order) whose end the block builder found over the limit (VS_BLK_OVER)
+inline std::string too_long_line(const std::string &path, uint64_t record) {
+    return path + ": record " + std::to_string(record) + " has a sequence line of more than " + std::to_string((unsigned)VS_LEN_MASK) + " bytes";
+}
+// ... where the record's index in the window is on the device, in a list (0 if it cannot be fetched)
+inline uint32_t fetch_u32(const uint32_t *d) {
+    uint32_t v = 0;
+    return hipMemcpy(&v, d, sizeof v, hipMemcpyDeviceToHost) == hipSuccess ? v : 0u;
+}
+
 // A taken slot: the reader's next filled slot (the constructor blocks until there is one), given back when the lease ends or
 // is moved over -- by then the holder has seen to it that the slot's bytes are on the device.
 struct SlotLease {

@@ -216,7 +216,59 @@ class FastqPair:
         return ReadBlock(self._ctx, h)
 
 
-class FastqStream:
+class _NativeStream:
+    """What the streamed ingests share: a native handle opened, read block by block and closed through the three entries
+    ``_entries`` names (open, next, close).  ``_count`` names the attribute with the block size; a return code of next in
+    ``_value_codes`` is an input the stream refuses (``ValueError``), as bytes that are not valid UTF-8 always are."""
+
+    _entries = (None, None, None)
+    _count = "block_pairs"
+    _value_codes = ()
+
+    @staticmethod
+    def _open_error(ctx, rc, value_codes=()):
+        msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
+        return FileNotFoundError(msg) if "cannot open" in msg else ValueError(msg) if rc in value_codes else nat.NativeError(rc, msg)
+
+    def _open(self, ctx, *args, value_codes=()):
+        self._ctx, self._h = ctx, None
+        h = C.c_void_p()
+        rc = getattr(nat.lib(), self._entries[0])(ctx._h, *args, C.byref(h))
+        if rc != nat.VS_OK:
+            raise self._open_error(ctx, rc, value_codes)
+        self._h = h
+
+    def next_block(self) -> Optional["ReadBlock"]:
+        """The next block, or None at the end of the input."""
+        h = C.c_void_p()
+        n = C.c_uint64(0)
+        rc = getattr(nat.lib(), self._entries[1])(self._ctx._h, self._h, getattr(self, self._count), C.byref(h), C.byref(n))
+        if rc in self._value_codes:
+            raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
+        if rc != nat.VS_OK:
+            FastqPair._raise(self._ctx._h, rc)  # ValueError for bytes that are not valid UTF-8
+        return ReadBlock(self._ctx, h) if n.value else None
+
+    def __iter__(self):
+        while True:
+            block = self.next_block()
+            if block is None:
+                return
+            yield block
+
+    def close(self):
+        if self._h:
+            getattr(nat.lib(), self._entries[2])(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FastqStream(_NativeStream):
     """Both FASTQ files read front to back through the library's streamed ingest (``vs_fastq_stream_*``): any file a
     process can read once -- a FIFO, ``/dev/stdin``, ``<(zcat R1.fq.gz)``, a regular or gzip file -- with host memory
     bounded by a ring of pinned chunks; the records are found and packed on the device, and the members of a BGZF file
@@ -229,18 +281,11 @@ class FastqStream:
     UTF-8 anywhere, a cut-off gzip stream) raise before the iteration ends, with the exceptions ``FastqPair`` raises.
     ``close()`` as ``FastqPair``."""
 
+    _entries = ("vs_fastq_stream_open", "vs_fastq_stream_next", "vs_fastq_stream_close")
+
     def __init__(self, fwd: str, rve: str, ctx: "Context", block_pairs: int = 1 << 20):
-        self._ctx = ctx
-        self._h = None
         self.block_pairs = block_pairs
-        h = C.c_void_p()
-        rc = nat.lib().vs_fastq_stream_open(ctx._h, fwd.encode(), rve.encode(), C.byref(h))
-        if rc != nat.VS_OK:
-            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
-            if "cannot open" in msg:
-                raise FileNotFoundError(msg)
-            raise nat.NativeError(rc, msg)
-        self._h = h
+        self._open(ctx, fwd.encode(), rve.encode())
 
     # ---- the member-sharded open of a BGZF pair (one process per GPU) ------------------------------------------------------
     @classmethod
@@ -359,10 +404,7 @@ class FastqStream:
         self._ctx, self._h, self.block_pairs = ctx, None, block_pairs
         h = C.c_void_p()
         rc = nat.lib().vs_fastq_stream_open_range(ctx._h, mine.paths[0].encode(), mine.paths[1].encode(), rng, last - first, C.byref(h))
-        err = None
-        if rc != nat.VS_OK:
-            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
-            err = FileNotFoundError(msg) if "cannot open" in msg else nat.NativeError(rc, msg)
+        err = None if rc == nat.VS_OK else cls._open_error(ctx, rc)
         status = all_gather([0 if err is None else 1])
         if err is not None:
             raise err
@@ -392,35 +434,8 @@ class FastqStream:
         """pairs delivered so far (all of them once the iteration has ended)"""
         return self.info["pairs"]
 
-    def next_block(self) -> Optional["ReadBlock"]:
-        """The next block, or None at the end of the input."""
-        h = C.c_void_p()
-        n = C.c_uint64(0)
-        rc = nat.lib().vs_fastq_stream_next(self._ctx._h, self._h, self.block_pairs, C.byref(h), C.byref(n))
-        if rc != nat.VS_OK:
-            FastqPair._raise(self._ctx._h, rc)  # ValueError for bytes that are not valid UTF-8
-        return ReadBlock(self._ctx, h) if n.value else None
 
-    def __iter__(self):
-        while True:
-            block = self.next_block()
-            if block is None:
-                return
-            yield block
-
-    def close(self):
-        if self._h:
-            nat.lib().vs_fastq_stream_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class InterleavedStream:
+class InterleavedStream(_NativeStream):
     """The read pairs of ONE interleaved FASTQ -- a file or pipe in which each pair's two records follow each other
     (``samtools fastq x.bam`` to stdout, ``seqtk mergepe``, ``fastp --stdout``; what ``bwa mem -p`` reads) -- through
     ``vs_fastq_il_*``: read front to back like ``FastqStream`` reads two files, in every form that stream reads, the mates
@@ -434,22 +449,17 @@ class InterleavedStream:
     Interface of ``FastqStream``; ``info`` has ``pairs``, ``singles``, ``records``, ``text_bytes``, ``file_bytes``,
     ``flags``."""
 
+    _entries = ("vs_fastq_il_open", "vs_fastq_il_next", "vs_fastq_il_close")
+    _value_codes = (nat.VS_E_ARG,)  # (a single record in the strict mode; a stream that is no complete gzip)
+
     def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20, singles=False):
-        self._ctx = ctx
         self._h = None
         self.block_pairs = block_pairs
         if isinstance(singles, str) and singles != "keep":
             raise ValueError('singles is False, True or "keep" (got %r)' % (singles,))
         self.keep = singles == "keep"
         self.singles = bool(singles)
-        h = C.c_void_p()
-        rc = nat.lib().vs_fastq_il_open(ctx._h, os.fspath(path).encode(), 2 if self.keep else 1 if singles else 0, C.byref(h))
-        if rc != nat.VS_OK:
-            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
-            if "cannot open" in msg:
-                raise FileNotFoundError(msg)
-            raise nat.NativeError(rc, msg)
-        self._h = h
+        self._open(ctx, os.fspath(path).encode(), 2 if self.keep else 1 if singles else 0)
 
     # ---- the member-sharded open of one whole-BGZF interleaved file (one process per GPU) -----------------------------------
     TAIL_RECORDS = 64  # the records at the end of a share whose mates the tail pass looks at first
@@ -602,10 +612,7 @@ class InterleavedStream:
         self._ctx, self._h, self.block_pairs, self.keep, self.singles = ctx, None, block_pairs, False, bool(singles)
         h = C.c_void_p()
         rc = nat.lib().vs_fastq_il_open_range(ctx._h, mine.path.encode(), 1 if singles else 0, rng, b - a, lookahead, entry, a, C.byref(h))
-        err = None
-        if rc != nat.VS_OK:
-            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
-            err = FileNotFoundError(msg) if "cannot open" in msg else nat.NativeError(rc, msg)
+        err = None if rc == nat.VS_OK else cls._open_error(ctx, rc)
         status = all_gather([0 if err is None else 1])
         if err is not None:
             raise err
@@ -629,55 +636,21 @@ class InterleavedStream:
         """pairs delivered so far (all of them once the iteration has ended)"""
         return self.info["pairs"]
 
-    def next_block(self) -> Optional["ReadBlock"]:
-        """The next block, or None at the end of the input."""
-        h = C.c_void_p()
-        n = C.c_uint64(0)
-        rc = nat.lib().vs_fastq_il_next(self._ctx._h, self._h, self.block_pairs, C.byref(h), C.byref(n))
-        if rc == nat.VS_E_ARG:  # (a single record in the strict mode; a stream that is no complete gzip)
-            raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
-        if rc != nat.VS_OK:
-            FastqPair._raise(self._ctx._h, rc)  # ValueError for bytes that are not valid UTF-8
-        return ReadBlock(self._ctx, h) if n.value else None
 
-    def __iter__(self):
-        while True:
-            block = self.next_block()
-            if block is None:
-                return
-            yield block
-
-    def close(self):
-        if self._h:
-            nat.lib().vs_fastq_il_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SingleEndStream:
+class SingleEndStream(_NativeStream):
     """The UNPAIRED reads of one FASTQ file or pipe -- the unpaired survivors of a trimmer, the merged reads of an overlapping
     library -- through ``vs_fastq_se_*``: read front to back like ``InterleavedStream`` reads its file, in every form that
     stream reads, every complete record one read.  The blocks are singles blocks (``ReadBlock.unpaired``) of up to
     ``block_reads`` reads, built on the device.  ``info`` has ``reads``, ``records``, ``text_bytes``, ``file_bytes``,
     ``flags``."""
 
+    _entries = ("vs_fastq_se_open", "vs_fastq_se_next", "vs_fastq_se_close")
+    _count = "block_reads"
+    _value_codes = (nat.VS_E_ARG,)  # (a stream that is no complete gzip)
+
     def __init__(self, path: str, ctx: "Context", block_reads: int = 1 << 20):
-        self._ctx = ctx
-        self._h = None
         self.block_reads = block_reads
-        h = C.c_void_p()
-        rc = nat.lib().vs_fastq_se_open(ctx._h, os.fspath(path).encode(), C.byref(h))
-        if rc != nat.VS_OK:
-            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
-            if "cannot open" in msg:
-                raise FileNotFoundError(msg)
-            raise nat.NativeError(rc, msg)
-        self._h = h
+        self._open(ctx, os.fspath(path).encode())
 
     @property
     def info(self):
@@ -689,35 +662,6 @@ class SingleEndStream:
     def n_reads(self) -> int:
         """reads delivered so far (all of them once the iteration has ended)"""
         return self.info["reads"]
-
-    def next_block(self) -> Optional["ReadBlock"]:
-        """The next block, or None at the end of the input."""
-        h = C.c_void_p()
-        n = C.c_uint64(0)
-        rc = nat.lib().vs_fastq_se_next(self._ctx._h, self._h, self.block_reads, C.byref(h), C.byref(n))
-        if rc == nat.VS_E_ARG:  # (a stream that is no complete gzip)
-            raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
-        if rc != nat.VS_OK:
-            FastqPair._raise(self._ctx._h, rc)  # ValueError for bytes that are not valid UTF-8
-        return ReadBlock(self._ctx, h) if n.value else None
-
-    def __iter__(self):
-        while True:
-            block = self.next_block()
-            if block is None:
-                return
-            yield block
-
-    def close(self):
-        if self._h:
-            nat.lib().vs_fastq_se_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def fastq_mates(text: bytes, eof: bool = True, ctx: "Context" = None, guard: int = 64):
@@ -741,7 +685,7 @@ def fastq_mates(text: bytes, eof: bool = True, ctx: "Context" = None, guard: int
                                       first_single=None if info[4] == none else int(info[4]), records=int(info[5]))
 
 
-class PairedNameStream:
+class PairedNameStream(_NativeStream):
     """The read pairs of TWO FASTQ files paired by read NAME on the device, through ``vs_fastq_pn_*``: the two files of
     ``FastqStream``, read front to back in every form that stream reads, but a pair is a pair of mates by name (the rule of
     ``InterleavedStream``: name tokens equal byte for byte, a ``/1`` on the file-1 record and ``/2`` on the file-2 record
@@ -757,22 +701,17 @@ class PairedNameStream:
     has ``pairs``, ``singles_fwd``, ``singles_rve`` (dropped, or kept), ``records_fwd``, ``records_rve``, ``windows``,
     ``max_window_bytes``, ``text_bytes``, ``file_bytes``, ``flags``."""
 
+    _entries = ("vs_fastq_pn_open", "vs_fastq_pn_next", "vs_fastq_pn_close")
+    _value_codes = (nat.VS_E_ARG, nat.VS_E_RANGE)  # (names that do not pair, a name twice, mates out of order, a window without a decision)
+
     def __init__(self, fwd: str, rve: str, ctx: "Context", block_pairs: int = 1 << 20, singles=False):
-        self._ctx = ctx
         self._h = None
         self.block_pairs = block_pairs
         if isinstance(singles, str) and singles != "keep":
             raise ValueError('singles is False, True or "keep" (got %r)' % (singles,))
         self.keep = singles == "keep"
         self.singles = bool(singles)
-        h = C.c_void_p()
-        rc = nat.lib().vs_fastq_pn_open(ctx._h, os.fspath(fwd).encode(), os.fspath(rve).encode(), 2 if self.keep else 1 if singles else 0, C.byref(h))
-        if rc != nat.VS_OK:
-            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
-            if "cannot open" in msg:
-                raise FileNotFoundError(msg)
-            raise nat.NativeError(rc, msg)
-        self._h = h
+        self._open(ctx, os.fspath(fwd).encode(), os.fspath(rve).encode(), 2 if self.keep else 1 if singles else 0)
 
     @property
     def info(self):
@@ -785,35 +724,6 @@ class PairedNameStream:
     def n_pairs(self) -> int:
         """pairs delivered so far (all of them once the iteration has ended)"""
         return self.info["pairs"]
-
-    def next_block(self) -> Optional["ReadBlock"]:
-        """The next block, or None at the end of the input."""
-        h = C.c_void_p()
-        n = C.c_uint64(0)
-        rc = nat.lib().vs_fastq_pn_next(self._ctx._h, self._h, self.block_pairs, C.byref(h), C.byref(n))
-        if rc in (nat.VS_E_ARG, nat.VS_E_RANGE):  # (names that do not pair, a name twice, mates out of order, a window without a decision)
-            raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
-        if rc != nat.VS_OK:
-            FastqPair._raise(self._ctx._h, rc)  # ValueError for bytes that are not valid UTF-8
-        return ReadBlock(self._ctx, h) if n.value else None
-
-    def __iter__(self):
-        while True:
-            block = self.next_block()
-            if block is None:
-                return
-            yield block
-
-    def close(self):
-        if self._h:
-            nat.lib().vs_fastq_pn_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def fastq_join(text0: bytes, text1: bytes, eof0: bool = True, eof1: bool = True, ctx: "Context" = None, singles: bool = True, table: int = 0,
@@ -870,7 +780,7 @@ def fastq_join_singles(text0: bytes, text1: bytes, eof0: bool = True, eof1: bool
                  duplicate=None if info[5] == none else (int(info[5] >> 32), int(info[5] & 0xFFFFFFFF)), order=opt(info[6]), first_bad=opt(info[7])))
 
 
-class BamStream:
+class BamStream(_NativeStream):
     """The read pairs of ONE collated BAM file (unaligned BAM from the sequencer, or the unmapped pairs of a host
     alignment after ``samtools collate``) through ``vs_bam_stream_*``: the BGZF members inflated on the device, the records
     found there by following their ``block_size`` chain from the end of the header, the 4-bit bases packed by the packer of
@@ -892,8 +802,13 @@ class BamStream:
     in file order as singles blocks (``ReadBlock.unpaired``) of up to ``block_pairs`` reads, each read as ``samtools fastq
     -s`` writes it (reversed and complemented under 0x10; no bases: a read of length 0)."""
 
+    _entries = ("vs_bam_stream_open_mode", "vs_bam_stream_next", "vs_bam_stream_close")
+
+    @property
+    def _value_codes(self):  # (by name: a file the match refuses)
+        return (nat.VS_E_ARG, nat.VS_E_RANGE) if self.by_name else (nat.VS_E_ARG,)
+
     def __init__(self, path: str, ctx: "Context", block_pairs: int = 1 << 20, by_name: bool = False, singles=None):
-        self._ctx = ctx
         self._h = None
         self.block_pairs = block_pairs
         self.by_name = bool(by_name)
@@ -902,16 +817,7 @@ class BamStream:
         self.keep = singles == "keep"
         if self.keep and not by_name:
             raise ValueError('singles="keep" keeps the singletons of a BAM whose mates are matched by name and needs by_name=True: a collated BAM has none')
-        h = C.c_void_p()
-        rc = nat.lib().vs_bam_stream_open_mode(ctx._h, path.encode(), 2 if self.keep else 1 if by_name else 0, C.byref(h))
-        if rc != nat.VS_OK:
-            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
-            if "cannot open" in msg:
-                raise FileNotFoundError(msg)
-            if rc == nat.VS_E_ARG:
-                raise ValueError(msg)
-            raise nat.NativeError(rc, msg)
-        self._h = h
+        self._open(ctx, path.encode(), 2 if self.keep else 1 if by_name else 0, value_codes=(nat.VS_E_ARG,))
 
     # ---- the member-sharded open of a collated BAM (one process per GPU) ---------------------------------------------------
     @classmethod
@@ -1001,10 +907,7 @@ class BamStream:
         self._ctx, self._h, self.block_pairs, self.by_name, self.keep = ctx, None, block_pairs, False, False
         h = C.c_void_p()
         rc = nat.lib().vs_bam_stream_open_range(ctx._h, mine.path.encode(), rng, C.byref(h))
-        err = None
-        if rc != nat.VS_OK:
-            msg = nat.lib().vs_last_error(ctx._h).decode("utf-8", "replace")
-            err = FileNotFoundError(msg) if "cannot open" in msg else nat.NativeError(rc, msg)
+        err = None if rc == nat.VS_OK else cls._open_error(ctx, rc)
         status = all_gather([0 if err is None else 1])
         if err is not None:
             raise err
@@ -1031,34 +934,6 @@ class BamStream:
     def n_pairs(self) -> int:
         """pairs delivered so far (all of them once the iteration has ended)"""
         return self.info["pairs"]
-
-    def next_block(self) -> Optional["ReadBlock"]:
-        """The next block, or None at the end of the input."""
-        h = C.c_void_p()
-        n = C.c_uint64(0)
-        rc = nat.lib().vs_bam_stream_next(self._ctx._h, self._h, self.block_pairs, C.byref(h), C.byref(n))
-        if rc == nat.VS_E_ARG or (rc == nat.VS_E_RANGE and self.by_name):  # (by name: a file the match refuses)
-            raise ValueError(nat.lib().vs_last_error(self._ctx._h).decode("utf-8", "replace"))
-        nat.check(self._ctx._h, rc)
-        return ReadBlock(self._ctx, h) if n.value else None
-
-    def __iter__(self):
-        while True:
-            block = self.next_block()
-            if block is None:
-                return
-            yield block
-
-    def close(self):
-        if self._h:
-            nat.lib().vs_bam_stream_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def bam_header_bytes(path: str) -> int:
