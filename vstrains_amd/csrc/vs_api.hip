@@ -38,6 +38,7 @@ void vs_tuning_load(VsTuning &t, bool experiment) {
     if (const char *v = getenv("VS_ROWS_SUB")) t.rows_sub = atoi(v) >= 1024 ? (uint32_t)atoi(v) : 0u;
     if (const char *v = getenv("VS_ROWS_PER_STRIP")) t.rows_per_strip = atoi(v) > 0 && atoi(v) <= 64 ? (uint32_t)atoi(v) : 0u;
     if (const char *v = getenv("VS_LOCUS_STAGE")) t.locus_stage = atoi(v) >= 0 ? atoi(v) : -1;
+    if (const char *v = getenv("VS_LOCUS_SCATTER")) t.locus_scatter = atoi(v) > 0 ? atoi(v) : 0;
     t.no_sort = env_on("VS_NO_SORT");
     t.locus_global = env_on("VS_LOCUS_GLOBAL");
     t.no_fast = env_on("VS_NO_FAST");

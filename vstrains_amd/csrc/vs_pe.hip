@@ -1959,6 +1959,7 @@ __device__ __forceinline__ uint32_t vs_locus_key_end(const VsIndexDev &idx, cons
 //                     (key, workgroup) run in the sorted order -- stable, deterministic
 //   k_locus_scatter : workgroup g loads its column as LDS cursors and places its pairs
 #define LOCUS_TPB 1024     // threads per workgroup of the two LDS-histogram sort kernels
+#define LOCUS_SCATTER_U 8u  // pairs a thread of k_locus_scatter has in flight
 // (key_lo, nk): the keys this pass counts / places -- a graph with more keys than one LDS histogram holds (54 k nodes at
 // configs[4]) takes two or three passes over the stored keys instead of the global-atomic sort; `compute`: the first
 // pass derives the keys (the expensive part: a read's seeds are probed) and stores them, the others read them back.
@@ -2185,13 +2186,48 @@ k_locus_count_staged(VsIndexDev idx, VsReadsDev rd, uint64_t n_pairs, uint32_t c
 __global__ void __launch_bounds__(LOCUS_TPB)
 k_locus_scatter(uint32_t key_lo, uint32_t nk, uint64_t n_pairs, uint32_t chunk, uint32_t n_wg, const uint32_t *__restrict__ keys,
                 const uint32_t *__restrict__ first, uint32_t *__restrict__ perm) {
-    for (uint32_t i = threadIdx.x; i < nk; i += LOCUS_TPB) vs_lds[i] = first[(uint64_t)(key_lo + i) * n_wg + blockIdx.x];
+    // Which workgroup places which chunk is free.  Workgroups go to the 8 XCDs round-robin (blockIdx % 8), and the places of
+    // one key in neighbouring chunks are neighbours in perm[]: XCD x takes the x-th eighth of the chunks, so that the runs
+    // that share a line of perm[] meet in one L2 and leave it as one line.  (Measured at 10 M pairs: 0.013 ms of the sort with
+    // the scatter in four launches, 0.01 ms at most in one -- profiles/EXPERIMENTS.md, 2026-10-21.)
+    uint32_t wg = blockIdx.x;
+    if ((n_wg & 7u) == 0u) wg = (blockIdx.x & 7u) * (n_wg >> 3) + (blockIdx.x >> 3);
+    for (uint32_t i = threadIdx.x; i < nk; i += LOCUS_TPB) vs_lds[i] = first[(uint64_t)(key_lo + i) * n_wg + wg];
     __syncthreads();
-    const uint64_t lo = (uint64_t)blockIdx.x * chunk;
+    const uint64_t lo = (uint64_t)wg * chunk;
     const uint64_t hi = lo + chunk < n_pairs ? lo + chunk : n_pairs;
-    for (uint64_t p = lo + threadIdx.x; p < hi; p += LOCUS_TPB) {
-        const uint32_t key = keys[p];
-        if (key - key_lo < nk) perm[atomicAdd(&vs_lds[key - key_lo], 1u)] = (uint32_t)p;
+    if (lo >= hi || !nk) return;  // (uniform; 4 097 pairs leave workgroups 241 .. 255 nothing)
+    // A thread's pairs are a chain each -- key load, returning LDS atomic, scattered store -- so it takes LOCUS_SCATTER_U of
+    // them a turn: pairs lo + tid + LOCUS_TPB * (U * i + j), j < U, coalesced 4-byte loads.  The keys of turn i + 1 are
+    // requested before the atomics of turn i, and the atomics of a turn are all issued before its first store.  Loads and
+    // atomics are straight-line code, so that the compiler counts them and waits for no more than it needs: a pair beyond the
+    // chunk loads the chunk's last key, and a lane with nothing to place adds 0 to a cursor of its own choice (which changes
+    // nothing).  Only the stores are conditional.  (k[], kn[], at[] and on[] are indexed by unrolled constants only: registers.)
+    const uint32_t span = (uint32_t)(hi - lo), turns = (span + LOCUS_SCATTER_U * LOCUS_TPB - 1u) / (LOCUS_SCATTER_U * LOCUS_TPB);
+    const uint32_t idle = (threadIdx.x & 63u) < nk ? threadIdx.x & 63u : 0u;  // (a cursor per lane: no two lanes of a wavefront on one)
+    uint32_t k[LOCUS_SCATTER_U], kn[LOCUS_SCATTER_U], at[LOCUS_SCATTER_U];
+    bool on[LOCUS_SCATTER_U];
+    auto request = [&](uint32_t q0, uint32_t *dst) {  // q: a pair counted from lo
+#pragma unroll
+        for (uint32_t j = 0; j < LOCUS_SCATTER_U; j++) {
+            const uint32_t q = q0 + j * LOCUS_TPB;
+            dst[j] = keys[lo + (q < span ? q : span - 1u)];
+        }
+    };
+    uint32_t q0 = threadIdx.x;  // (q0 + U * LOCUS_TPB cannot wrap: span <= chunk < 2^32 / 256, a workgroup's share of at most 2^32 pairs)
+    request(q0, kn);
+    for (uint32_t t = 0; t < turns; t++, q0 += LOCUS_SCATTER_U * LOCUS_TPB) {
+#pragma unroll
+        for (uint32_t j = 0; j < LOCUS_SCATTER_U; j++) k[j] = kn[j];
+        request(q0 + LOCUS_SCATTER_U * LOCUS_TPB, kn);
+#pragma unroll
+        for (uint32_t j = 0; j < LOCUS_SCATTER_U; j++) {
+            on[j] = q0 + j * LOCUS_TPB < span && k[j] - key_lo < nk;
+            at[j] = atomicAdd(&vs_lds[on[j] ? k[j] - key_lo : idle], on[j] ? 1u : 0u);
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < LOCUS_SCATTER_U; j++)
+            if (on[j]) perm[at[j]] = (uint32_t)(lo + q0 + j * LOCUS_TPB);
     }
 }
 
@@ -2793,8 +2829,10 @@ static int pe_launch(vs_ctx *ctx, const vs_reads *reads, uint32_t *d_node_mat, u
             int rc = vs_scan_u32(ctx, ctx->d_locus_hist.as<const uint32_t>(), ctx->d_locus_hist.as<uint32_t>(), nk * n_wg,
                                  ctx->d_scan_tmp.as<uint64_t>(), nullptr);
             if (rc) return rc;
-            for (uint32_t key_lo = 0; key_lo < nk; key_lo += per_pass) {
-                const uint32_t n_here = (uint32_t)(nk - key_lo < per_pass ? nk - key_lo : per_pass);
+            // (the scatter in launches of pl.locus_scatter_keys keys, at most a pass's: the places one launch writes fit the L2s)
+            const uint32_t sc_keys = pl.locus_scatter_keys;
+            for (uint32_t key_lo = 0; key_lo < nk; key_lo += sc_keys) {
+                const uint32_t n_here = (uint32_t)(nk - key_lo < sc_keys ? nk - key_lo : sc_keys);
                 hipLaunchKernelGGL(k_locus_scatter, dim3(n_wg), dim3(LOCUS_TPB), lds_keys, st, key_lo, n_here, n_pairs, chunk, n_wg,
                                    ctx->d_locus_keys.as<const uint32_t>(), ctx->d_locus_hist.as<const uint32_t>(), ctx->d_perm.as<uint32_t>());
             }

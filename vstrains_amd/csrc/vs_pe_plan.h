@@ -38,6 +38,7 @@ struct VsTuning {
     bool no_sort = false, locus_global = false, no_fast = false, no_std = false, no_agg = false;
     bool no_mid = false;            // VS_NO_MID: overflow pairs straight to k_pe_slow
     int locus_stage = -1;           // VS_LOCUS_STAGE (-1 = by the room the histogram leaves): 0 = the key pass of the locus sort with per-pair loads, N = staged through buffers of N words per wavefront, so that small blocks reach batch cuts and oversize pairs
+    int locus_scatter = 0;          // VS_LOCUS_SCATTER (0 = LOCUS_SCATTER_PAIRS): k_locus_scatter in launches of about N pairs' worth of keys each, so that blocks of a few thousand pairs are placed in several launches
 };
 
 // The probe grid of a read end (round 5).  A match of K bases and more holds s = K - w + 1 consecutive seed starts, so any
@@ -89,6 +90,13 @@ VS_PLAN_FN uint32_t vs_seed_probes(uint32_t len, uint32_t w, uint32_t s) {
 #define LOCUS_STAGE_MAX (LOCUS_STAGE_QUADS * 4u * LOCUS_STAGE_PAIRS - LOCUS_STAGE_SLACK)  // what the lanes' loads cover
 #define LOCUS_STAGE_MIN_PAIRS 48u  // production stages only where a buffer holds this many pairs of the block's longest reads: three lanes in four with a pair (measured: 55 pairs a batch, 2 x 150 bases, win; 34 pairs, 2 x 250 bases, lose to the per-pair loads -- profiles/EXPERIMENTS.md)
 #define LOCUS_LDS_WORDS 40960u    // 160 KB, one workgroup per CU
+// k_locus_scatter writes 4 bytes a pair to places all over perm[]: a launch that places every pair of a large block leaves a
+// line of perm[] in pieces, each piece evicted from an L2 before the next arrives (230 MB written for 40 MB at 10 M pairs).
+// The launch rule therefore cuts the keys of a pass into ranges of about LOCUS_SCATTER_PAIRS pairs' worth, one launch each
+// (the kernel's key_lo / nk filter; a launch reads all the keys, 4 bytes a pair, coalesced), at most LOCUS_SCATTER_MAX of
+// them (measured at 10 M pairs: two and four launches win alike, eight lose to the launches -- profiles/EXPERIMENTS.md).
+#define LOCUS_SCATTER_PAIRS 2621440u  // 2.5 Mi pairs, 10 MB of perm[]
+#define LOCUS_SCATTER_MAX 4u
 #define SLOW_WORDS_PER_NODE 6u
 #define LDS_BUDGET_BYTES (64u * 1024u)
 #define NI_CAP 4096u
@@ -234,6 +242,7 @@ struct PePlan {
     uint64_t locus_keys, locus_hist_words;
     uint32_t locus_stage_words;  // capacity of each of a wavefront's two LDS buffers in the staged key pass (0: per-pair loads)
     uint64_t locus_lds_bytes;    // dynamic LDS of k_locus_count / k_locus_count_staged
+    uint32_t locus_scatter_keys; // keys a launch of k_locus_scatter places (locus_per_pass at most)
     // the counters: pair-major (k_pe_accumulate) or by row owners (pe_count_by_rows)
     uint32_t use_rows, use_table, mark_tiles;
     uint32_t acc_grid, acc_per_wg, acc_fill, acc_task_cap;
@@ -299,6 +308,11 @@ inline PePlan vs_pe_plan(const PePlanIn &in) {
             p.locus_chunk = (uint32_t)((n_pairs + LOCUS_WGS - 1) / LOCUS_WGS);
             p.locus_per_pass = (uint32_t)(nk < LOCUS_LDS_KEYS ? nk : LOCUS_LDS_KEYS);
             p.locus_lds_bytes = sizeof(uint32_t) * (uint64_t)p.locus_per_pass;
+            const uint64_t sc_pairs = tn.locus_scatter > 0 ? (uint64_t)tn.locus_scatter : LOCUS_SCATTER_PAIRS;
+            uint64_t launches = (n_pairs + sc_pairs - 1u) / sc_pairs;
+            if (launches > LOCUS_SCATTER_MAX) launches = LOCUS_SCATTER_MAX;
+            const uint64_t sc_keys = (nk + launches - 1u) / launches;  // (keys are not pairs: a range of keys holds its share of the pairs only about)
+            p.locus_scatter_keys = sc_keys < p.locus_per_pass ? (uint32_t)sc_keys : p.locus_per_pass;
             // the key pass streams the read words through two LDS buffers per wavefront (k_locus_count_staged) where one pass's
             // histogram leaves room for them beside it: not beside a full pass of LOCUS_LDS_KEYS keys, so not in a multi-pass sort
             if (nk < LOCUS_LDS_KEYS && tn.locus_stage != 0) {
