@@ -810,6 +810,34 @@ int vs_node_depth(vs_ctx *ctx, const vs_reads *reads, uint64_t *d_kc);
 int vs_ctx_keep_masks(vs_ctx *ctx, int on);
 int vs_depth_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t plan[8]);
 
+/* ---- contigs threaded through the graph (additions to ABI 11 without a new number: nothing that exists changes) --------
+ * No counterpart in the reference, which takes the contigs' walks from SPAdes' contigs.paths.  A contig that spells a walk
+ * of the graph is a chain of maximal exact matches against consecutive segments, each overlapping the next by k bases;
+ * tests/contig_thread_model.py states the rule window by window, csrc/vs_contig_chain.h at the level of matches.
+ * A match record is five uint32: contig, first base in the contig, segment | strand << 31 (strand 1: on the segment's
+ * reverse complement), first base in that strand's text, length in bases (>= k + 1).  A token is four: contig,
+ * segment | strand << 31, windows of the contig it was chosen for, 1 if it opens a part.
+ *   vs_contig_mems      : reads != NULL: one block through k_contig_mems on the context's CURRENT index -- every maximal
+ *                         exact match of k + 1 bases or more between an end and a strand of a segment, once, in no order.
+ *                         `contig` is the read of a singles block (vs_reads_pack_single), else the end.  Build the block
+ *                         after vs_ctx_keep_masks(ctx, 1): a byte outside ACGT bounds a match only where its mask was
+ *                         kept.  The records stay on the device, in a buffer of the context that grows to what a pass
+ *                         found (the pass then runs a second time; nothing is cut off).  Synchronises the ctx stream.
+ *                         reads == NULL: nothing runs, the last pass's records are meant.  Either way *n = their number,
+ *                         and they are copied to HOST out[cap records] when cap >= *n (out may be NULL: ask, then fetch).
+ *                         VS_E_RANGE: 2^32 ends, or 2^32 probes in one block (about 2^32 * (k + 2 - seed length) bases).
+ *   vs_contig_mems_last : info[0] = records of the last pass, [1] launches of k_contig_mems it took (2: the buffer grew),
+ *                         [2] probes, [3] the buffer's capacity in records when the pass began.
+ *   vs_contig_chain     : host only, a pure function (csrc/vs_contig_chain.h): n_mems records in any order -> tokens[n_mems
+ *                         x 4] (at most one per record) in contig order, *n_tokens, and ambiguous[n_contigs] = windows of
+ *                         each contig with more than one hit.  seg_len[n_segs]: the segments' lengths in bases, in the
+ *                         numbering of the records.  VS_E_ARG: a record names a contig or segment out of range, is
+ *                         shorter than k + 1, or leaves its segment. */
+int vs_contig_mems(vs_ctx *ctx, const vs_reads *reads, uint32_t *out, uint64_t cap, uint64_t *n);
+int vs_contig_mems_last(vs_ctx *ctx, uint64_t info[4]);
+int vs_contig_chain(const uint32_t *mems, uint64_t n_mems, const uint32_t *seg_len, uint32_t n_segs, uint32_t ksize, uint32_t n_contigs,
+                    uint32_t *tokens, uint64_t *n_tokens, uint64_t *ambiguous);
+
 /* Testing aid (ABI 11): the two exclusive scans under the index build, the locus sort, every row_ptr and every member,
  * record and word offset, run alone on values the caller made up, launched exactly as their callers launch them (no kernel
  * of its own).  HOST pointers: in[n + guard] = the n values and behind them `guard` words of a sentinel the caller chose;

@@ -3,6 +3,11 @@
 directory layout, same log lines; the work runs on MI355X through libvstrains_hip.so.
 
     python -m vstrains_amd.cli -a spades -g graph.gfa -p contigs.paths -o OUT -fwd f.fq -rve r.fq
+    python -m vstrains_amd.cli -a spades -g graph.gfa --contigs-fasta contigs.fasta -o OUT -fwd f.fq -rve r.fq
+
+``--contigs-fasta FILE`` (extension, in place of ``-p``): the contigs are threaded through the graph on the device
+(vstrains_amd.contig_paths) and the pipeline goes on with OUT/tmp/contigs_threaded.paths -- for an assembly whose
+contigs.paths is gone, polished or filtered contigs, known genomes as guides, a graph of another de Bruijn assembler.
 
 Not restated: ``-r/--reference_fa`` (hidden debug mode that shells out to minimap2) is accepted
 and refused with a message; the coverage histogram PNG is not drawn.
@@ -97,7 +102,37 @@ def build_parser():
                         "the graph goes on as gfa/graph_depth.gfa with LN:i / KC:i tags -- for one assembly graph run against many "
                         "samples, subsampled or depleted reads, or a GFA that lost its tags; a segment no read touches stops the run; "
                         "the reads are read twice, so they must be regular files (one process only)")
+    # (not listed by --help, whose text is pinned to the reference's flags and the extensions before this one: see the module's
+    # docstring and README.md)
+    p.add_argument("--contigs-fasta", dest="contigs_fasta", default=None, type=str, metavar="FILE", help=argparse.SUPPRESS)
     return p
+
+
+def contigs_fasta_refusal(args, world: int):
+    """None, or why ``--contigs-fasta`` cannot hold, said before anything is written or a device opened."""
+    if args.path_file:
+        return "--contigs-fasta and -p are mutually exclusive: the contigs' paths are either given or threaded from the FASTA"
+    if world > 1:
+        return ("--contigs-fasta threads in one process only; sharing the pass among the %d ranks of this process group is not built: "
+                "run without torchrun" % world)
+    return None
+
+
+def contigs_fasta(args, logger, ctx):
+    """The threading pass on ``-g`` (after ``--depth-from-reads``: on that graph): OUT/tmp/contigs_threaded.paths, which the
+    pipeline then takes as its ``-p``."""
+    from . import contig_paths
+
+    try:
+        text, tally = contig_paths.thread_contigs(ctx, args.gfa_file, args.contigs_fasta)
+    except ValueError as e:
+        logger.error("--contigs-fasta: %s" % e)
+        sys.exit(1)
+    out = args.output_dir + "/tmp/contigs_threaded.paths"
+    with open(out, "w") as fh:
+        fh.write(text)
+    logger.info("contigs threaded through the graph: {0}; the paths go on as {1}".format(contig_paths.tally_line(tally), out))
+    args.path_file = out
 
 
 def depth_from_reads_refusal(args, world: int):
@@ -191,6 +226,10 @@ def main(argv=None, backend=None):
         why = depth_from_reads_refusal(args, pe_inference._rank_world()[1])
         if why is not None:
             raise ValueError(why)
+    if args.contigs_fasta is not None:
+        why = contigs_fasta_refusal(args, pe_inference._rank_world()[1])
+        if why is not None:
+            raise ValueError(why)
     if (not args.gfa_file) or (not os.path.exists(args.gfa_file)):
         _bail("\nPath to the assembly graph is required, (.gfa format)", "Please ensure the path is correct")
     args.pe_text_files = None
@@ -200,7 +239,10 @@ def main(argv=None, backend=None):
             _bail("\nPath to the paired-end information (--pe-text-from) must hold pe_info.gz and st_info.gz, or pe_info and st_info",
                   "Please ensure the path is correct")
     args.assembler = args.assembler.lower()
-    if (not args.path_file) or (not os.path.exists(args.path_file)):
+    if args.contigs_fasta is not None:
+        if not os.path.exists(args.contigs_fasta):
+            _bail("\nPath to the contigs (--contigs-fasta, .fasta format) does not exist", "Please ensure the path is correct")
+    elif (not args.path_file) or (not os.path.exists(args.path_file)):
         _bail("\nPath to Contig file from SPAdes (.paths format) is required for SPAdes assmbler option. e.g., contigs.paths")
     if args.min_len is not None:
         if args.min_len < 0:
@@ -254,7 +296,7 @@ def main(argv=None, backend=None):
     logger.info("Assembly graph file: " + args.gfa_file)
     logger.info("Forward read file: " + args.fwd)
     logger.info("Reverse read file: " + args.rve)
-    logger.info("Contig paths file: " + args.path_file)
+    logger.info("Contig paths file: " + (args.path_file if args.contigs_fasta is None else "threaded from " + args.contigs_fasta))
     logger.info("Output directory: " + os.path.abspath(args.output_dir))
     if args.dev:
         logger.info("*DEBUG MODE is turned ON")
@@ -268,7 +310,7 @@ def main(argv=None, backend=None):
     from .graph import pipeline
 
     if backend is None and (args.no_pe_text or args.sparse_pe_text or args.bgzf_pe_text or args.bam_by_name or args.interleaved or
-                            args.check_names or args.single or args.depth_from_reads):
+                            args.check_names or args.single or args.depth_from_reads or args.contigs_fasta is not None):
         from .graph.hip_ops import HipBackend
 
         backend = HipBackend(args.device, write_info_text=not args.no_pe_text, sparse_info_text=args.sparse_pe_text,
@@ -296,6 +338,8 @@ def main(argv=None, backend=None):
     try:
         if args.depth_from_reads:
             depth_from_reads(args, logger, backend.ctx)
+        if args.contigs_fasta is not None:
+            contigs_fasta(args, logger, backend.ctx)
         timings = pipeline.run(args, logger, backend)
     except BaseException:
         logger.removeHandler(to_file)

@@ -117,6 +117,10 @@ struct vs_ctx {
     // which counts the ends the PE filter drops too, sees where their 'N's are (without it a block whose only bytes outside
     // ACGT are 'N's gives its mask back, vs_reads_finish, and the mapped ingest packs on the host without one)
     bool keep_masks = false;
+    // vs_contig_mems: the match records of the last pass (grow-only, kept for the copy-out call), the scan of the ends'
+    // probe counts, the scan's block sums with the probe total and the record count behind them
+    VsDevBuf d_mems, d_mem_scan, d_mem_tmp;
+    uint64_t mems_info[4] = {0, 0, 0, 0};  // records, launches of k_contig_mems, probes, capacity in records before the pass
     hipStream_t stream = nullptr;
     std::string err;
     FqStage fq_stage[2];

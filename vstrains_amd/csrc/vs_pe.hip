@@ -3242,3 +3242,215 @@ extern "C" int vs_node_depth(vs_ctx *ctx, const vs_reads *reads, uint64_t *d_kc)
     VS_HIP(ctx, hipGetLastError());
     return VS_OK;
 }
+
+// ---- contigs threaded through the graph: the matches (vs_contig_mems) ------------------------------------------------
+// Every maximal exact match of K bases or more between a contig (an end of an ordinary block, masks kept) and a strand of
+// a segment, as a record of VS_MEM_WORDS words (vs_contig_chain.h, where the host chains them into a .paths entry).  The
+// probe grid, the table probe and vs_extend are k_node_depth's: where that kernel adds len - K + 1 to a counter, this one
+// appends {contig, contig offset, segment | strand << 31, segment pos, length}, once per match, by the first grid point
+// inside it.  Contigs are few and long where reads are many and short, so the lanes are dealt over the PROBES of the whole
+// block, not over its ends: k_contig_probes writes every end's probe count, a scan turns them into first probes, and
+// thread t of k_contig_mems takes probe t (its end by a binary search of the scan), 256 probes a workgroup -- a contig of a
+// million bases is spread over two thousand workgroups.  Inside a wavefront the 64 probes' posting counts are scanned
+// and the postings dealt one per lane, 64 at a time, as in k_node_depth.  Appends are claimed per wavefront: one ballot,
+// one atomic on the record count by the first lane that has a match.  The count goes on beyond the buffer's capacity
+// while the stores stop at it, so the host sees a pass that did not fit and runs it once more in a buffer that does.
+#include "vs_contig_chain.h"
+
+#define MEMS_TPB 256u
+#define MEMS_WAVES (MEMS_TPB / 64u)
+#define MEMS_WAVE_WORDS 324u    // the scan of 64 probes' posting counts [65], their payloads, ends and read offsets [4 x 64] (5 KB a workgroup)
+#define MEMS_FIRST_CAP 4096ull  // records of the buffer's first allocation
+
+struct MemsParams {
+    VsIndexDev idx;
+    VsReadsDev rd;
+    const uint32_t *pscan;      // [n_ends + 1] the first probe of every end, the total behind them
+    uint32_t total;             // probes of the block
+    uint32_t shift;             // contig = end >> shift (1: a singles block, whose odd ends are absent)
+    uint32_t *out;              // [cap] records
+    unsigned long long cap;
+    unsigned long long *count;  // records found, stored or not
+};
+
+__global__ void __launch_bounds__(256)
+k_contig_probes(VsReadsDev rd, uint32_t w, uint32_t s, uint32_t *np) {
+    const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (e > rd.n_ends) return;
+    uint32_t v = 0u;
+    if (e < rd.n_ends) {
+        const uint32_t meta = rd.meta[e];
+        if (!((meta >> 24) & VS_FLAG_ABSENT)) v = vs_seed_probes(meta & VS_LEN_MASK, w, s);
+    }
+    np[e] = v;  // (np[n_ends] = 0: its scan is the total)
+}
+
+__global__ void __launch_bounds__(MEMS_TPB)
+k_contig_mems(MemsParams P) {
+    __shared__ uint32_t s_mem[MEMS_WAVES * MEMS_WAVE_WORDS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t N = P.idx.n_nodes, w = P.idx.w, s = P.idx.s, K = P.idx.K;
+    uint32_t *sw = s_mem + wave * MEMS_WAVE_WORDS;
+    uint32_t *s_cnt = sw, *s_pa = sw + 65u, *s_pb = sw + 129u, *s_pe = sw + 193u, *s_pj = sw + 257u;
+    const uint64_t t = (uint64_t)blockIdx.x * MEMS_TPB + tid;  // (a wavefront's 64 probes are consecutive)
+    uint32_t c = 0u, pa = 0u, pb = 0u, pe = 0u, pj = 0u;
+    if (t < P.total) {
+        const uint32_t e = vs_upper_idx(P.pscan, (uint32_t)P.rd.n_ends + 1u, (uint32_t)t);  // pscan[e] <= t < pscan[e + 1]
+        const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+        const uint32_t j = vs_seed_phase(rlen, w, s) + ((uint32_t)t - P.pscan[e]) * s;
+        const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+        const uint32_t *mk = vs_depth_mask(P.rd, meta);
+        if (!(mk && vs_seed_dirty(mk, rbase + j, w))) {
+            uint32_t sr;
+            const uint64_t key = vs_seed_key(P.rd.words, rbase + j, w, &sr);
+            c = vs_probe(P.idx, key, sr, &pa, &pb);
+        }
+        pe = e;
+        pj = j;
+    }
+    s_pa[lane] = pa;
+    s_pb[lane] = pb;
+    s_pe[lane] = pe;
+    s_pj[lane] = pj;
+    s_cnt[lane + 1u] = vs_wave_scan_add(c);
+    if (lane == 0u) s_cnt[0] = 0u;
+    vs_wave_sync();
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[64]);
+    for (uint32_t q0 = 0u; q0 < total; q0 += 64u) {
+        // postings q0 .. q0 + 63 of these probes: one per lane
+        const uint32_t t2 = q0 + lane;
+        bool found = false;
+        uint32_t r_e = 0u, r_off = 0u, r_seg = 0u, r_pos = 0u, r_len = 0u;
+        if (t2 < total) {
+            const uint32_t pr = vs_upper_idx(s_cnt, 65u, t2);
+            const uint32_t k2 = t2 - s_cnt[pr];
+            const uint32_t qa0 = s_pa[pr], qb0 = s_pb[pr], e = s_pe[pr], j = s_pj[pr];
+            const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+            const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+            const uint32_t *mk = vs_depth_mask(P.rd, meta);
+            uint32_t nd, pos, opp;
+            VsNodeMeta nm;
+            if (s_cnt[pr + 1u] - s_cnt[pr] == 1u) {
+                nd = qa0; pos = qb0 & 0x7FFFFFFFu; opp = qb0 >> 31;
+                nm = P.idx.meta[nd];
+            } else {
+                const VsPosting po = vs_posting_unpack(P.idx.postings[qa0 + k2]);
+                nd = po.node; pos = po.pos; opp = po.strand ^ (qb0 >> 31);
+                nm.woff = po.woff; nm.len = po.len;
+            }
+            const uint32_t *tw = opp ? P.idx.rc_words : P.idx.fwd_words;
+            const uint32_t q = opp ? nm.len - pos - w : pos;
+            uint32_t a, qa, len;
+            // (k >= 95: VS_SEED_VERIFIED is 0, the key only nominated the posting and the comparison starts at the seed's first base)
+            if (nd < N && vs_extend(P.rd.words, rbase, rlen, tw, nm.woff * 16u, nm.len, j, q, VS_SEED_VERIFIED(w), s, K, mk, rbase, &a, &qa, &len)) {
+                found = true;
+                r_e = e; r_off = a; r_seg = nd | (opp << 31); r_pos = qa; r_len = len;
+            }
+        }
+        const unsigned long long have = __ballot(found);
+        if (have) {
+            const uint32_t leader = (uint32_t)__ffsll((long long)have) - 1u;
+            unsigned long long base = 0ull;
+            if (lane == leader) base = atomicAdd(P.count, (unsigned long long)__popcll(have));
+            const uint32_t b_lo = (uint32_t)__shfl((int)(uint32_t)base, (int)leader), b_hi = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)leader);
+            const unsigned long long at = (((unsigned long long)b_hi << 32) | b_lo) + (unsigned long long)__popcll(have & ((1ull << lane) - 1ull));
+            if (found && at < P.cap) {
+                uint32_t *rec = P.out + at * VS_MEM_WORDS;
+                rec[0] = r_e >> P.shift;
+                rec[1] = r_off;
+                rec[2] = r_seg;
+                rec[3] = r_pos;
+                rec[4] = r_len;
+            }
+        }
+    }
+}
+
+extern "C" int vs_contig_mems(vs_ctx *ctx, const vs_reads *reads, uint32_t *out, uint64_t cap, uint64_t *n) {
+    if (!ctx || !n) return VS_E_ARG;
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (reads) {
+        if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_contig_mems: build an index first (vs_index_build)");
+        const VsIndexDev &idx = ctx->idx;
+        const uint64_t n_ends = reads->n_ends;
+        if (n_ends > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "vs_contig_mems: a block of 2^32 ends or more");
+        ctx->mems_info[0] = ctx->mems_info[1] = ctx->mems_info[2] = 0;
+        ctx->mems_info[3] = ctx->d_mems.capacity() / (sizeof(uint32_t) * VS_MEM_WORDS);
+        if (n_ends && idx.n_nodes && reads->max_len >= idx.K) {
+            const uint64_t m = n_ends + 1u, nb = (m + 2047u) / 2048u;
+            VS_HIP(ctx, ctx->d_mem_scan.reserve(sizeof(uint32_t) * m));
+            VS_HIP(ctx, ctx->d_mem_tmp.reserve(sizeof(uint64_t) * (nb + 3u)));
+            uint32_t *d_scan = ctx->d_mem_scan.as<uint32_t>();
+            uint64_t *d_tmp = ctx->d_mem_tmp.as<uint64_t>(), *d_total = d_tmp + nb + 1u, *d_count = d_tmp + nb + 2u;
+            hipLaunchKernelGGL(k_contig_probes, dim3((unsigned)((m + 255u) / 256u)), dim3(256), 0, st, reads->dev(), idx.w, idx.s, d_scan);
+            VS_HIP(ctx, hipGetLastError());
+            if (int rc = vs_scan_u32(ctx, d_scan, d_scan, m, d_tmp, d_total)) return rc;
+            uint64_t probes = 0;
+            VS_HIP(ctx, hipMemcpyAsync(&probes, d_total, sizeof probes, hipMemcpyDeviceToHost, st));
+            VS_HIP(ctx, hipStreamSynchronize(st));
+            if (probes > 0xFFFFFFF0ull) return vs_fail(ctx, VS_E_RANGE, "vs_contig_mems: %llu probes in one block: give the contigs in several", (unsigned long long)probes);
+            ctx->mems_info[2] = probes;
+            if (probes) {
+                if (!ctx->d_mems.capacity()) VS_HIP(ctx, ctx->d_mems.reserve(sizeof(uint32_t) * VS_MEM_WORDS * MEMS_FIRST_CAP));
+                MemsParams P;
+                P.idx = idx;
+                P.rd = reads->dev();
+                P.pscan = d_scan;
+                P.total = (uint32_t)probes;
+                P.shift = reads->unpaired ? 1u : 0u;
+                P.count = (unsigned long long *)d_count;
+                uint64_t found = 0;
+                for (int pass = 0;; pass++) {
+                    P.out = ctx->d_mems.as<uint32_t>();
+                    P.cap = ctx->d_mems.capacity() / (sizeof(uint32_t) * VS_MEM_WORDS);
+                    VS_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
+                    hipLaunchKernelGGL(k_contig_mems, dim3((unsigned)((probes + MEMS_TPB - 1u) / MEMS_TPB)), dim3(MEMS_TPB), 0, st, P);
+                    VS_HIP(ctx, hipGetLastError());
+                    VS_HIP(ctx, hipMemcpyAsync(&found, d_count, sizeof found, hipMemcpyDeviceToHost, st));
+                    VS_HIP(ctx, hipStreamSynchronize(st));
+                    ctx->mems_info[1]++;
+                    if (found <= P.cap) break;
+                    // the pass did not fit: once more, in a buffer of the size it asked for (the stream is idle: synchronised above)
+                    if (pass) return vs_fail(ctx, VS_E_STATE, "vs_contig_mems: %llu matches after %llu in the same block", (unsigned long long)found, (unsigned long long)P.cap);
+                    VS_HIP(ctx, ctx->d_mems.reserve(sizeof(uint32_t) * VS_MEM_WORDS * found));
+                }
+                ctx->mems_info[0] = found;
+            }
+        }
+    }
+    *n = ctx->mems_info[0];
+    if (out && *n && cap >= *n) {
+        VS_HIP(ctx, hipMemcpyAsync(out, ctx->d_mems.ptr(), sizeof(uint32_t) * VS_MEM_WORDS * *n, hipMemcpyDeviceToHost, st));
+        VS_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return VS_OK;
+}
+
+extern "C" int vs_contig_mems_last(vs_ctx *ctx, uint64_t info[4]) {
+    if (!ctx || !info) return VS_E_ARG;
+    for (int i = 0; i < 4; i++) info[i] = ctx->mems_info[i];
+    return VS_OK;
+}
+
+extern "C" int vs_contig_chain(const uint32_t *mems, uint64_t n_mems, const uint32_t *seg_len, uint32_t n_segs, uint32_t ksize, uint32_t n_contigs,
+                               uint32_t *tokens, uint64_t *n_tokens, uint64_t *ambiguous) {
+    if ((n_mems && (!mems || !tokens)) || (n_segs && !seg_len) || !n_tokens || (n_contigs && !ambiguous)) return VS_E_ARG;
+    const uint32_t K = ksize + 1u;
+    std::vector<VsMem> v((size_t)n_mems);
+    for (uint64_t i = 0; i < n_mems; i++) {
+        const uint32_t *r = mems + i * VS_MEM_WORDS;
+        v[i] = VsMem{r[0], r[1], r[2], r[3], r[4]};
+        const uint32_t seg = r[2] & 0x7FFFFFFFu;
+        if (r[0] >= n_contigs || seg >= n_segs || r[4] < K || (uint64_t)r[3] + r[4] > seg_len[seg]) return VS_E_ARG;
+    }
+    for (uint32_t c = 0; c < n_contigs; c++) ambiguous[c] = 0;
+    std::vector<VsChainToken> tok;
+    vs_contig_chain_for(v, seg_len, K, tok, ambiguous);
+    for (size_t i = 0; i < tok.size(); i++) {
+        uint32_t *o = tokens + i * VS_TOKEN_WORDS;
+        o[0] = tok[i].contig; o[1] = tok[i].seg; o[2] = tok[i].windows; o[3] = tok[i].first;
+    }
+    *n_tokens = tok.size();
+    return VS_OK;
+}

@@ -1480,6 +1480,27 @@ class Context:
         in the index's own numbering, added to.  Blocks must have been built after ``keep_masks(True)``."""
         nat.check(self._h, nat.lib().vs_node_depth(self._h, reads._h, C.c_void_p(kc_ptr)))
 
+    def contig_mems(self, reads: ReadBlock) -> np.ndarray:
+        """Every maximal exact match of k + 1 bases or more between a contig of the block and a strand of a segment
+        (``vs_contig_mems``): uint32 [n, 5] -- contig, first base in the contig, segment | strand << 31, first base in that
+        strand's text, length -- in no order, the segment in the numbering of the list ``build_index`` was given.  ``contig`` is
+        the read of a singles block.  Build the block after ``keep_masks(True)``, so that an 'N' bounds a match."""
+        n = C.c_uint64(0)
+        nat.check(self._h, nat.lib().vs_contig_mems(self._h, reads._h, None, 0, C.byref(n)))
+        out = np.zeros((int(n.value), 5), dtype=np.uint32)
+        if n.value:
+            nat.check(self._h, nat.lib().vs_contig_mems(self._h, None, out.ctypes.data, n.value, C.byref(n)))
+            if self.node_order is not None:
+                seg = out[:, 2]
+                out[:, 2] = self.node_order[seg & 0x7FFFFFFF].astype(np.uint32) | (seg & 0x80000000)
+        return out
+
+    def contig_mems_last(self) -> dict:
+        """How the last ``contig_mems`` pass went (``vs_contig_mems_last``)."""
+        a = (C.c_uint64 * 4)()
+        nat.check(self._h, nat.lib().vs_contig_mems_last(self._h, a))
+        return dict(records=int(a[0]), launches=int(a[1]), probes=int(a[2]), capacity_before=int(a[3]))
+
     def keep_masks(self, on: bool = True):
         """Read blocks built from now on keep their validity mask (``vs_ctx_keep_masks``): the depth pass counts the ends
         with an 'N' too and has to see where it is."""
@@ -1857,6 +1878,27 @@ def depth_plan(n_nodes: int, ksize: int, n_ends: int, max_len: int, n_cu: int = 
         raise nat.NativeError(rc, "vs_depth_plan refuses %d nodes / %d ends" % (n_nodes, n_ends))
     return dict(route=("none", "lds", "global")[int(a[0])], grid=int(a[1]), ends_per_wg=int(a[2]), wrap_ends=int(a[3]), lds_nodes=int(a[4]),
                 lds_bytes=int(a[5]), node_limit=int(a[6]), threads=int(a[7]))
+
+
+def contig_chain(mems, seg_lens: Sequence[int], ksize: int, n_contigs: int):
+    """Match records (``Context.contig_mems``, any order) chained into .paths entries (``vs_contig_chain``, a pure host
+    function: no device is needed).  -> (per contig its parts, each a list of (segment, strand, windows); per contig the
+    number of its windows with more than one hit)."""
+    mems = np.ascontiguousarray(mems, dtype=np.uint32).reshape(-1, 5)
+    lens = np.ascontiguousarray(seg_lens, dtype=np.uint32)
+    tokens = np.zeros((max(len(mems), 1), 4), dtype=np.uint32)
+    ambiguous = np.zeros(max(n_contigs, 1), dtype=np.uint64)
+    n = C.c_uint64(0)
+    rc = nat.lib().vs_contig_chain(mems.ctypes.data if len(mems) else None, len(mems), lens.ctypes.data if len(lens) else None, len(lens), ksize,
+                                   n_contigs, tokens.ctypes.data, C.byref(n), ambiguous.ctypes.data)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_contig_chain refuses the records: a contig or segment out of range, a match shorter than k + 1 or one that leaves its segment")
+    parts: List[List[List[Tuple[int, int, int]]]] = [[] for _ in range(n_contigs)]
+    for c, seg, windows, first in tokens[: int(n.value)].tolist():
+        if first:
+            parts[c].append([])
+        parts[c][-1].append((seg & 0x7FFFFFFF, seg >> 31, windows))
+    return parts, [int(v) for v in ambiguous[:n_contigs]]
 
 
 class DepthCounter:
