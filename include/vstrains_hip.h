@@ -838,6 +838,44 @@ int vs_contig_mems_last(vs_ctx *ctx, uint64_t info[4]);
 int vs_contig_chain(const uint32_t *mems, uint64_t n_mems, const uint32_t *seg_len, uint32_t n_segs, uint32_t ksize, uint32_t n_contigs,
                     uint32_t *tokens, uint64_t *n_tokens, uint64_t *ambiguous);
 
+/* ---- per-position depth of every segment from the reads (additions to ABI 11 without a new number: nothing that exists
+ * changes) ------------------------------------------------------------------------------------------------------------
+ * No counterpart in the reference.  With K = k + 1, for segment n and forward offset p in [0, len_n - K]:
+ *   cov[n][p] = the number of triples (read end e, read offset i, table entry (n, p)) for which end_e[i : i + K] is a key
+ *               of the reference's table (PE_Inference.py:117-135) holding that entry
+ * -- the triples KC[n] of vs_node_depth counts, kept apart by their entry's offset, so sum_p cov[n][p] == KC[n] exactly
+ * and every rule of that pass holds (palindromes twice, at ONE position; repeats at each; bytes outside ACGT nowhere; short,
+ * empty and absent ends nothing; every end of every block).  The value belongs to the window that STARTS at p: k-mer
+ * coverage, not base coverage.  tests/depth_profile_model.py states it; csrc/vs_cover_plan.h has the slots and the fold rule.
+ * Slots: segment n of the index's own numbering owns len_n - K + 2 of them when len_n >= K, else none: one per window and
+ * one sentinel behind them, which takes the -1 of a match flush with the segment's end and is 0 after every fold.
+ *   vs_cover_layout : d_first: DEVICE pointer to n_nodes + 1 words, written: the first slot of every segment of the
+ *                     context's CURRENT index, in the numbering vs_index_build was given, and the slot total S behind them;
+ *                     *n_slots = S (host).  Synchronises the ctx stream.  VS_E_RANGE: S >= 2^32 (*n_slots is still set).
+ *   vs_node_cover   : one block through k_node_cover on the context's current index: every maximal exact match of K bases
+ *                     or more between an end and a strand of a segment adds +1 to the slot of its first window and -1 to
+ *                     the slot behind its last, on d_diff (DEVICE, S uint32, zero before the first block, wrap-around
+ *                     adds, atomically).  d_first: what vs_cover_layout wrote for THIS index.  Enqueued on the ctx stream.
+ *                     Blocks must have been built after vs_ctx_keep_masks(ctx, 1).  VS_E_RANGE: 2^32 ends, or a block
+ *                     whose ends could put 2^32 on one window (n_ends * 2 * (max_len - K + 1) >= 2^32).
+ *   vs_cover_fold   : d_cov[i] += (excl[i] + d_diff[i]) mod 2^32 for the exclusive scan excl of d_diff over all S slots
+ *                     (scratch of the context: 4 bytes per slot), and d_diff[i] = 0.  d_cov: DEVICE, S uint64 totals.
+ *                     Enqueued on the ctx stream.  Right as long as no window gathered 2^32 since the last fold:
+ *   vs_cover_plan   : host only, a pure function (csrc/vs_cover_plan.h): for a graph of n_nodes nodes at ksize, a block of
+ *                     n_ends ends of at most max_len bases, a device of n_cu compute units, `pending` = plan[5] of the
+ *                     block before (0 after a fold or at the start) and `bound` (0: 2^32; at most 2^32):
+ *                     plan[0] = 1 if k_node_cover is launched (0: no end holds a window); [1] = workgroups; [2] = ends per
+ *                     workgroup; [3] = the block's weight n_ends * 2 * (max_len - K + 1), the most it can add to one slot;
+ *                     [4] = 1 if vs_cover_fold is due BEFORE this block (pending > 0 and pending + weight >= bound);
+ *                     [5] = the weight pending once the block is counted; [6] = LDS bytes per workgroup; [7] = threads per
+ *                     workgroup.  VS_E_RANGE: more than 2^25 - 2 nodes, 2^32 ends, a weight of 2^32 or more, bound or
+ *                     pending beyond 2^32. */
+int vs_cover_layout(vs_ctx *ctx, uint32_t *d_first, uint64_t *n_slots);
+int vs_node_cover(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, uint32_t *d_diff);
+int vs_cover_fold(vs_ctx *ctx, uint32_t *d_diff, uint64_t *d_cov, uint64_t n_slots);
+int vs_cover_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t pending, uint64_t bound,
+                  uint64_t plan[8]);
+
 /* Testing aid (ABI 11): the two exclusive scans under the index build, the locus sort, every row_ptr and every member,
  * record and word offset, run alone on values the caller made up, launched exactly as their callers launch them (no kernel
  * of its own).  HOST pointers: in[n + guard] = the n values and behind them `guard` words of a sentinel the caller chose;

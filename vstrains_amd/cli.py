@@ -105,6 +105,9 @@ def build_parser():
     # (not listed by --help, whose text is pinned to the reference's flags and the extensions before this one: see the module's
     # docstring and README.md)
     p.add_argument("--contigs-fasta", dest="contigs_fasta", default=None, type=str, metavar="FILE", help=argparse.SUPPRESS)
+    # with --depth-from-reads: the same single pass also writes the depth of every window of k + 1 bases (k-mer coverage by window
+    # START, not base coverage) as gfa/graph_depth.bedgraph and a line per segment as gfa/graph_depth.tsv (vstrains_amd.node_depth)
+    p.add_argument("--depth-profile", dest="depth_profile", action="store_true", default=False, help=argparse.SUPPRESS)
     return p
 
 
@@ -133,6 +136,13 @@ def contigs_fasta(args, logger, ctx):
         fh.write(text)
     logger.info("contigs threaded through the graph: {0}; the paths go on as {1}".format(contig_paths.tally_line(tally), out))
     args.path_file = out
+
+
+def depth_profile_refusal(args):
+    """None, or why ``--depth-profile`` cannot hold, said before anything is written: it is a by-product of the depth pass."""
+    if args.depth_profile and not args.depth_from_reads:
+        return "--depth-profile writes the profile of the depth pass: give --depth-from-reads with it"
+    return None
 
 
 def depth_from_reads_refusal(args, world: int):
@@ -165,11 +175,18 @@ def depth_from_reads(args, logger, ctx):
     except ValueError as e:
         logger.error("--depth-from-reads: %s" % e)
         sys.exit(1)
-    ids, kc, ends = node_depth.depth_pass(ctx, args.gfa_file, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=args.interleaved,
-                                          check_names=args.check_names, single=args.single, count_singles=args.count_singles, quiet=True)
+    got = node_depth.depth_pass(ctx, args.gfa_file, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=args.interleaved,
+                                check_names=args.check_names, single=args.single, count_singles=args.count_singles, quiet=True,
+                                profile=args.depth_profile)
+    ids, kc, ends = got[:3]
     out = args.output_dir + "/gfa/graph_depth.gfa"
     with open(out, "wb") as fh:
         fh.write(node_depth.rewrite_gfa(raw, kc.tolist()))
+    if args.depth_profile:
+        lengths, offsets, cov = got[3]
+        node_depth.write_bedgraph(args.output_dir + "/gfa/graph_depth.bedgraph", ids, offsets, cov)
+        node_depth.write_summary(args.output_dir + "/gfa/graph_depth.tsv", ids, lengths, offsets, cov)
+        logger.info("depth profile of every window of k + 1 bases: {0}/gfa/graph_depth.bedgraph, per segment: {0}/gfa/graph_depth.tsv".format(args.output_dir))
     logger.info("segment depth counted from the reads: k = {0}, {1} read ends, KC sum {2}; the graph goes on as {3}".format(k, ends, int(kc.sum()), out))
     empty = [ids[i] for i in range(len(ids)) if kc[i] == 0]
     if empty:
@@ -222,6 +239,9 @@ def main(argv=None, backend=None):
     args.single = pe_inference.unpaired_input(args.single, args.count_singles, pe_inference._rank_world()[1], args.interleaved,
                                               pe_text_from=args.pe_text_from, check_names=args.check_names, bam_by_name=args.bam_by_name,
                                               fwd=args.fwd, rve=args.rve)
+    why = depth_profile_refusal(args)
+    if why is not None:
+        raise ValueError(why)
     if args.depth_from_reads:
         why = depth_from_reads_refusal(args, pe_inference._rank_world()[1])
         if why is not None:

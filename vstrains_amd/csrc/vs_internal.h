@@ -121,6 +121,8 @@ struct vs_ctx {
     // probe counts, the scan's block sums with the probe total and the record count behind them
     VsDevBuf d_mems, d_mem_scan, d_mem_tmp;
     uint64_t mems_info[4] = {0, 0, 0, 0};  // records, launches of k_contig_mems, probes, capacity in records before the pass
+    // vs_cover_layout / vs_cover_fold: the exclusive scan of the difference array (one word per slot) and the scans' block sums
+    VsDevBuf d_cover_scan, d_cover_tmp;
     hipStream_t stream = nullptr;
     std::string err;
     FqStage fq_stage[2];

@@ -3454,3 +3454,201 @@ extern "C" int vs_contig_chain(const uint32_t *mems, uint64_t n_mems, const uint
     *n_tokens = tok.size();
     return VS_OK;
 }
+
+// ---- per-position depth of every segment from the reads (vs_cover_layout / vs_node_cover / vs_cover_fold) -------------
+// cov[n][p] = the triples KC[n] counts (vs_node_depth above) whose table entry is (n, p): what the depth pass sums per
+// segment, kept per window (the definition, the slots and the fold rule: vs_cover_plan.h, tests/depth_profile_model.py).
+// The end batches, the probe grid, the table probe, the posting deal and vs_extend under the mask are k_node_depth's.  Where
+// that kernel keeps len - K + 1 of a match, this one keeps where on the segment it starts and how long it is: a match on the
+// forward text covers the windows from p0 = qa, one on the reverse-complement text those from p0 = len_n - qa - len, both up
+// to p0 + len - K.  It is written down as a DIFFERENCE -- +1 into slot first[n] + p0, -1 into the slot behind its last
+// window -- so a match costs two dword atomics whatever its length, and nothing is combined on chip.  vs_cover_fold turns
+// the differences into counts: one exclusive scan over all slots (every segment's slots sum to 0: the -1 of a match flush
+// with the segment's end stays in the segment's sentinel slot), then excl[i] + diff[i] added to the 64-bit totals.
+#include "vs_cover_plan.h"
+
+struct CoverParams {
+    VsIndexDev idx;
+    VsReadsDev rd;
+    const uint32_t *first;  // [n_nodes + 1] the first slot of every segment, the slot total behind them
+    uint32_t *diff;         // [first[n_nodes]] differences, ADDED to
+    uint64_t ends_per_wg;
+};
+
+__global__ void __launch_bounds__(256)
+k_cover_slots(const VsNodeMeta *meta, uint32_t n_nodes, uint32_t K, uint32_t *cnt) {
+    const uint64_t n = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (n > n_nodes) return;
+    uint32_t v = 0u;
+    if (n < n_nodes) {
+        const uint32_t len = meta[n].len;
+        if (len >= K) v = len - K + 2u;  // its windows and the sentinel
+    }
+    cnt[n] = v;  // (cnt[n_nodes] = 0: its scan is the total)
+}
+
+__global__ void __launch_bounds__(COVER_TPB)
+k_node_cover(CoverParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_mem[COVER_LDS_WORDS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t N = P.idx.n_nodes, w = P.idx.w, s = P.idx.s, K = P.idx.K;
+    uint32_t *s_head = s_mem;
+    uint32_t *sw = s_mem + COVER_HEAD_WORDS + wave * COVER_WAVE_WORDS;
+    uint32_t *s_np = sw, *s_cnt = sw + 65u, *s_pa = sw + 130u, *s_pb = sw + 194u, *s_pj = sw + 258u;
+    const uint64_t e_lo = (uint64_t)blockIdx.x * P.ends_per_wg;
+    const uint64_t e_hi = e_lo + P.ends_per_wg < P.rd.n_ends ? e_lo + P.ends_per_wg : P.rd.n_ends;
+    if (tid == 0u) s_head[0] = 0u;
+    __syncthreads();
+    for (;;) {
+        uint32_t b = 0u;
+        if (lane == 0u) b = atomicAdd(&s_head[0], 64u);
+        b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+        if (e_lo + b >= e_hi) break;
+        const uint64_t e0 = e_lo + b;
+        const uint32_t n_here = e_hi - e0 < 64u ? (uint32_t)(e_hi - e0) : 64u;
+        uint32_t np = 0u;
+        if (lane < n_here) {
+            const uint32_t meta = P.rd.meta[e0 + lane];
+            if (!((meta >> 24) & VS_FLAG_ABSENT)) np = vs_seed_probes(meta & VS_LEN_MASK, w, s);  // (0 for an end shorter than K)
+        }
+        s_np[lane + 1u] = vs_wave_scan_add(np);
+        if (lane == 0u) s_np[0] = 0u;
+        vs_wave_sync();
+        const uint32_t tp = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_np[64]);
+        for (uint32_t p0 = 0u; p0 < tp; p0 += 64u) {
+            // probes p0 .. p0 + 63 of the batch: one per lane
+            const uint32_t t = p0 + lane;
+            uint32_t c = 0u, pa = 0u, pb = 0u, pj = 0u;
+            if (t < tp) {
+                const uint32_t el = vs_upper_idx(s_np, 65u, t);  // the end that owns probe t: s_np[el] <= t < s_np[el + 1]
+                const uint64_t e = e0 + el;
+                const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                const uint32_t j = vs_seed_phase(rlen, w, s) + (t - s_np[el]) * s;
+                const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                if (!(mk && vs_seed_dirty(mk, rbase + j, w))) {
+                    uint32_t sr;
+                    const uint64_t key = vs_seed_key(P.rd.words, rbase + j, w, &sr);
+                    c = vs_probe(P.idx, key, sr, &pa, &pb);
+                }
+                pj = (el << 24) | j;  // (a read offset fits 24 bits: VS_LEN_MASK)
+            }
+            s_pa[lane] = pa;
+            s_pb[lane] = pb;
+            s_pj[lane] = pj;
+            s_cnt[lane + 1u] = vs_wave_scan_add(c);
+            if (lane == 0u) s_cnt[0] = 0u;
+            vs_wave_sync();
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[64]);
+            for (uint32_t q0 = 0u; q0 < total; q0 += 64u) {
+                // postings q0 .. q0 + 63 of these probes: one per lane
+                const uint32_t t2 = q0 + lane;
+                if (t2 < total) {
+                    const uint32_t pr = vs_upper_idx(s_cnt, 65u, t2);
+                    const uint32_t k2 = t2 - s_cnt[pr];
+                    const uint32_t qa0 = s_pa[pr], qb0 = s_pb[pr], ej = s_pj[pr];
+                    const uint32_t j = ej & VS_LEN_MASK;
+                    const uint64_t e = e0 + (ej >> 24);
+                    const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                    const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                    const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                    uint32_t nd, pos, opp;
+                    VsNodeMeta nm;
+                    if (s_cnt[pr + 1u] - s_cnt[pr] == 1u) {
+                        nd = qa0; pos = qb0 & 0x7FFFFFFFu; opp = qb0 >> 31;
+                        nm = P.idx.meta[nd];
+                    } else {
+                        const VsPosting po = vs_posting_unpack(P.idx.postings[qa0 + k2]);
+                        nd = po.node; pos = po.pos; opp = po.strand ^ (qb0 >> 31);
+                        nm.woff = po.woff; nm.len = po.len;
+                    }
+                    const uint32_t *tw = opp ? P.idx.rc_words : P.idx.fwd_words;
+                    const uint32_t q = opp ? nm.len - pos - w : pos;
+                    uint32_t a, qa, len;
+                    // (k >= 95: VS_SEED_VERIFIED is 0, the key only nominated the posting and the comparison starts at the seed's first base)
+                    if (nd < N && vs_extend(P.rd.words, rbase, rlen, tw, nm.woff * 16u, nm.len, j, q, VS_SEED_VERIFIED(w), s, K, mk, rbase, &a, &qa, &len) &&
+                        qa + len <= nm.len) {  // (a match lies inside its strand: no slot beyond the segment's sentinel)
+                        const uint32_t at = P.first[nd] + (opp ? nm.len - qa - len : qa);
+                        atomicAdd(&P.diff[at], 1u);
+                        atomicAdd(&P.diff[at + len - K + 1u], 0xFFFFFFFFu);
+                    }
+                }
+            }
+            vs_wave_sync();  // s_cnt / s_pa / s_pb / s_pj are rewritten by the next 64 probes
+        }
+        vs_wave_sync();  // s_np is rewritten by the next batch
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_cover_fold(const uint32_t *excl, uint32_t *diff, unsigned long long *cov, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t d = diff[i];
+    const uint32_t v = excl[i] + d;  // the count since the last fold, below 2^32 by the plan's rule (a sentinel slot: 0)
+    if (v) cov[i] += (unsigned long long)v;
+    if (d) diff[i] = 0u;
+}
+
+extern "C" int vs_cover_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t pending, uint64_t bound,
+                             uint64_t plan[8]) {
+    if (!plan) return VS_E_ARG;
+    const CoverPlan p = vs_cover_plan_for(n_nodes, ksize + 1u, n_ends, max_len, n_cu, pending, bound);
+    plan[0] = p.launch; plan[1] = p.grid; plan[2] = p.ends_per_wg; plan[3] = p.weight;
+    plan[4] = p.fold_first; plan[5] = p.pending; plan[6] = sizeof(uint32_t) * COVER_LDS_WORDS; plan[7] = COVER_TPB;
+    return p.status;
+}
+
+extern "C" int vs_cover_layout(vs_ctx *ctx, uint32_t *d_first, uint64_t *n_slots) {
+    if (!ctx || !d_first || !n_slots) return VS_E_ARG;
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_cover_layout: build an index first (vs_index_build)");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const VsIndexDev &idx = ctx->idx;
+    const uint64_t m = (uint64_t)idx.n_nodes + 1u, nb = (m + 2047u) / 2048u;
+    VS_HIP(ctx, ctx->d_cover_tmp.reserve(sizeof(uint64_t) * (nb + 2u)));
+    uint64_t *d_tmp = ctx->d_cover_tmp.as<uint64_t>(), *d_total = d_tmp + nb + 1u;
+    hipLaunchKernelGGL(k_cover_slots, dim3((unsigned)((m + 255u) / 256u)), dim3(256), 0, ctx->stream, idx.meta, idx.n_nodes, idx.K, d_first);
+    VS_HIP(ctx, hipGetLastError());
+    if (int rc = vs_scan_u32(ctx, d_first, d_first, m, d_tmp, d_total)) return rc;
+    uint64_t total = 0;
+    VS_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_slots = total;
+    if (total >= (1ull << 32))
+        return vs_fail(ctx, VS_E_RANGE, "vs_cover_layout: %llu slots, and a slot number has 32 bits: profile the graph in parts", (unsigned long long)total);
+    return VS_OK;
+}
+
+extern "C" int vs_node_cover(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, uint32_t *d_diff) {
+    if (!ctx || !reads || !d_first || !d_diff) return VS_E_ARG;
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_node_cover: build an index first (vs_index_build)");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const VsIndexDev &idx = ctx->idx;
+    const CoverPlan pl = vs_cover_plan_for(idx.n_nodes, idx.K, reads->n_ends, (uint32_t)reads->max_len, (uint32_t)ctx->n_cu, 0, 0);
+    if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "vs_node_cover: %s", pl.msg);
+    if (!pl.launch) return VS_OK;  // no end of the block holds a window
+    CoverParams P;
+    P.idx = idx;
+    P.rd = reads->dev();
+    P.first = d_first;
+    P.diff = d_diff;
+    P.ends_per_wg = pl.ends_per_wg;
+    hipLaunchKernelGGL(k_node_cover, dim3(pl.grid), dim3(COVER_TPB), 0, ctx->stream, P);
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}
+
+extern "C" int vs_cover_fold(vs_ctx *ctx, uint32_t *d_diff, uint64_t *d_cov, uint64_t n_slots) {
+    if (!ctx || (n_slots && (!d_diff || !d_cov))) return VS_E_ARG;
+    if (n_slots >= (1ull << 32)) return vs_fail(ctx, VS_E_RANGE, "vs_cover_fold: %llu slots", (unsigned long long)n_slots);
+    if (!n_slots) return VS_OK;
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t nb = (n_slots + 2047u) / 2048u;
+    VS_HIP(ctx, ctx->d_cover_scan.reserve(sizeof(uint32_t) * n_slots));
+    VS_HIP(ctx, ctx->d_cover_tmp.reserve(sizeof(uint64_t) * (nb + 2u)));
+    uint32_t *d_excl = ctx->d_cover_scan.as<uint32_t>();
+    if (int rc = vs_scan_u32(ctx, d_diff, d_excl, n_slots, ctx->d_cover_tmp.as<uint64_t>(), nullptr)) return rc;
+    hipLaunchKernelGGL(k_cover_fold, dim3((unsigned)((n_slots + 255u) / 256u)), dim3(256), 0, ctx->stream, d_excl, d_diff, (unsigned long long *)d_cov, n_slots);
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}

@@ -9,6 +9,13 @@ has no counterpart of this.  ``KC`` is SPAdes' number: the (k+1)-mer occurrences
 PE_Inference.py:117-135) whose read window ``end[i : i + K]`` is a key holding that entry (``tests/node_depth_model.py``);
 every end of the input counts, whatever its mate is like.  No ``DP:f`` is written: the reference's own rule ``kc / ln`` then
 applies, exactly as for a SPAdes GFA.
+
+    ... --profile FILE [--profile-summary FILE] [--depth-stat {sum,median}]
+
+With any of these the same single pass keeps the triples apart by their entry's forward offset ``p`` (``pe.CoverCounter``,
+``tests/depth_profile_model.py``): ``cov[n][p]`` belongs to the WINDOW of ``k + 1`` bases that starts at ``p`` -- k-mer
+coverage, not base coverage -- and ``KC[n]`` is the sum of its row.  ``--profile`` writes it as a bedGraph, ``--profile-summary``
+as one line per segment, ``--depth-stat median`` puts ``median * LN`` into ``KC:i``.
 """
 import argparse
 import contextlib
@@ -21,6 +28,93 @@ DEPTH_TAGS = ("dp", "DP", "kc", "KC", "ln", "LN")
 
 def _is_depth_tag(field: bytes) -> bool:
     return field[:2].decode("latin-1") in DEPTH_TAGS and field[2:3] == b":"
+
+
+def profile_runs(offsets, cov, n: int):
+    """The maximal runs of equal counts of segment ``n``: (start, end, count), 0-based half-open window starts."""
+    import numpy as np
+
+    row = np.asarray(cov[int(offsets[n]):int(offsets[n + 1])])
+    if not row.size:
+        return []
+    cut = np.flatnonzero(row[1:] != row[:-1]) + 1
+    starts = np.concatenate(([0], cut))
+    ends = np.concatenate((cut, [row.size]))
+    return list(zip(starts.tolist(), ends.tolist(), row[starts].tolist()))
+
+
+def _open_text(path: str):
+    if path.endswith(".gz"):
+        import gzip
+
+        return gzip.open(path, "wt", encoding="latin-1", newline="\n")
+    return open(path, "w", encoding="latin-1", newline="\n")
+
+
+def write_bedgraph(path: str, ids, offsets, cov) -> None:
+    """``segment<TAB>start<TAB>end<TAB>count``, one line per maximal run of equal counts, runs of 0 included: every segment of
+    ``k + 1`` bases or more is covered from 0 to ``len - k``, a shorter one has no line.  Segments in file order, no track
+    line; a name ending in ``.gz`` is written through gzip.  The positions are window STARTS (k-mer coverage)."""
+    with _open_text(path) as fh:
+        for n, name in enumerate(ids):
+            fh.write("".join("%s\t%d\t%d\t%d\n" % (name, a, b, v) for a, b, v in profile_runs(offsets, cov, n)))
+
+
+def read_bedgraph(path: str, ids):
+    """What ``write_bedgraph`` wrote, back as ``(offsets, cov)`` over ``ids`` (a segment without a line: an empty range)."""
+    import gzip
+
+    import numpy as np
+
+    rows = dict((name, []) for name in ids)
+    with (gzip.open(path, "rt", encoding="latin-1") if path.endswith(".gz") else open(path, encoding="latin-1")) as fh:
+        for line in fh:
+            name, a, b, v = line.rstrip("\n").split("\t")
+            row = rows[name]
+            if int(a) != len(row) or int(b) <= int(a):
+                raise ValueError("%s: the runs of %s do not follow each other at %s" % (path, name, a))
+            row.extend([int(v)] * (int(b) - int(a)))
+    offsets = np.zeros(len(ids) + 1, dtype=np.int64)
+    np.cumsum([len(rows[name]) for name in ids], out=offsets[1:])
+    return offsets, np.array([v for name in ids for v in rows[name]], dtype=np.int64)
+
+
+SUMMARY_COLUMNS = ("segment", "length", "windows", "KC", "breadth", "min", "median", "max")
+
+
+def profile_summary(lengths, offsets, cov):
+    """Per segment (length, windows, KC, breadth, min, median, max), all integers: ``breadth`` the windows with a count
+    above 0, ``median`` the lower median (the sorted value at index ``(windows - 1) // 2``); a segment without windows gets
+    zeros."""
+    import numpy as np
+
+    out = []
+    for n, ln in enumerate(lengths):
+        row = np.sort(np.asarray(cov[int(offsets[n]):int(offsets[n + 1])], dtype=np.int64))
+        if not row.size:
+            out.append((int(ln), 0, 0, 0, 0, 0, 0))
+            continue
+        out.append((int(ln), int(row.size), int(row.sum()), int((row > 0).sum()), int(row[0]), int(row[(row.size - 1) // 2]), int(row[-1])))
+    return out
+
+
+def write_summary(path: str, ids, lengths, offsets, cov) -> None:
+    """A TSV with a header line and the columns of ``SUMMARY_COLUMNS``, one line per segment in file order."""
+    with _open_text(path) as fh:
+        fh.write("\t".join(SUMMARY_COLUMNS) + "\n")
+        for name, row in zip(ids, profile_summary(lengths, offsets, cov)):
+            fh.write("%s\t%s\n" % (name, "\t".join(str(v) for v in row)))
+
+
+def depth_stat(stat: str, lengths, offsets, cov):
+    """The number that goes into ``KC:i``, per segment: ``sum`` -- the row sum, the depth pass's own ``KC``; ``median`` --
+    ``median * LN``, so that the reference's ``kc / ln`` is the lower median of the windows exactly."""
+    rows = profile_summary(lengths, offsets, cov)
+    if stat == "sum":
+        return [r[2] for r in rows]
+    if stat == "median":
+        return [r[5] * r[0] for r in rows]
+    raise ValueError("no depth statistic %r" % (stat,))
 
 
 def rewrite_gfa(raw: bytes, kc) -> bytes:
@@ -84,11 +178,12 @@ def refuse_ranks(world: int) -> None:
 
 
 def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
-               count_singles: bool = False, quiet: bool = False):
+               count_singles: bool = False, quiet: bool = False, profile: bool = False):
     """Index the segments of ``gfa`` and count every end the chosen input delivers (the input dispatch of
     ``pe_inference.count_links``, one process only).  -> (segment ids in file order, KC int64 in file order, ends counted).
     Replaces the context's index; the context stops keeping masks when the pass is over, so a PE count may follow on it.
-    ``quiet``: the dispatch's progress lines are not printed."""
+    ``quiet``: the dispatch's progress lines are not printed.  ``profile``: the pass counts per window (``pe.CoverCounter``,
+    still one kernel per block; KC is its row sums) and a fourth value follows: (segment lengths, offsets, cov)."""
     from . import pe as host
     from . import pe_inference
 
@@ -97,13 +192,16 @@ def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: b
     inp = pe_inference._resolve_inputs(fwd, rve, world, bam_by_name, interleaved, check_names, single, count_singles, False)
     ids, seqs = host.read_gfa_segments(gfa)
     ctx.build_index(seqs, kmer_size)
-    counter = host.DepthCounter(ctx)  # (the blocks built from here on keep their masks)
+    counter = host.CoverCounter(ctx) if profile else host.DepthCounter(ctx)  # (the blocks built from here on keep their masks)
     try:
         with contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext():
             pe_inference.feed_counter(ctx, counter, inp, 0, 1, stages_follow=False, tally_singles=False)
         ctx.sync()
     finally:
         ctx.keep_masks(False)
+    if profile:
+        offsets, cov = counter.result()
+        return ids, counter.kc(), counter.ends_seen, ([len(q) for q in seqs], offsets, cov)
     return ids, counter.result(), counter.ends_seen
 
 
@@ -123,6 +221,14 @@ def build_parser():
     p.add_argument("--check-names-singles", dest="check_names_singles", action="store_true", default=False, help="as pe_inference")
     p.add_argument("--single", dest="single", action="append", default=[], metavar="FILE", help="as pe_inference (repeatable)")
     p.add_argument("--count-singles", dest="count_singles", action="store_true", default=False, help="as pe_inference")
+    p.add_argument("--profile", dest="profile", type=str, default=None, metavar="FILE",
+                   help="also write the depth of every window of k + 1 bases as a bedGraph (segment, start, end, count; 0-based half-open "
+                        "window STARTS: k-mer coverage, not base coverage; runs of equal counts merged, zeros included; .gz: through gzip)")
+    p.add_argument("--profile-summary", dest="profile_summary", type=str, default=None, metavar="FILE",
+                   help="also write a TSV per segment: length, windows, KC, breadth (windows with a count above 0), min, lower median, max")
+    p.add_argument("--depth-stat", dest="depth_stat", choices=("sum", "median"), default=None,
+                   help="what KC:i holds: sum (default) the (k+1)-mer occurrences, as SPAdes; median: the lower median of the windows' "
+                        "counts times LN, so that kc / ln is that median")
     return p
 
 
@@ -152,13 +258,26 @@ def main(argv=None) -> int:
     from . import pe as host
 
     ctx = host.Context(args.device)
-    ids, kc, ends = depth_pass(ctx, args.gfa, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=interleaved,
-                               check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True)
-    text = rewrite_gfa(raw, kc.tolist())
+    profiled = args.profile is not None or args.profile_summary is not None or args.depth_stat is not None
+    got = depth_pass(ctx, args.gfa, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=interleaved,
+                     check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True, profile=profiled)
+    ids, kc, ends = got[:3]
+    tags = kc.tolist()
+    if profiled:
+        lengths, offsets, cov = got[3]
+        if args.depth_stat == "median":
+            tags = depth_stat("median", lengths, offsets, cov)
+        if args.profile is not None:
+            write_bedgraph(args.profile, ids, offsets, cov)
+        if args.profile_summary is not None:
+            write_summary(args.profile_summary, ids, lengths, offsets, cov)
+    text = rewrite_gfa(raw, tags)
     with open(args.out, "wb") as fh:
         fh.write(text)
+    stored = args.out + "".join("; %s in: %s" % (what, path) for what, path in (("profile", args.profile), ("summary", args.profile_summary))
+                                if path is not None)
     print("node_depth: k = %d, %d read ends counted, %d window-entry coincidences (sum of KC), %d of %d segments with KC = 0; result stored in: %s"
-          % (k, ends, int(kc.sum()), int((kc == 0).sum()), len(ids), args.out))
+          % (k, ends, int(kc.sum()), int((kc == 0).sum()), len(ids), stored))
     return 0
 
 

@@ -1480,6 +1480,23 @@ class Context:
         in the index's own numbering, added to.  Blocks must have been built after ``keep_masks(True)``."""
         nat.check(self._h, nat.lib().vs_node_depth(self._h, reads._h, C.c_void_p(kc_ptr)))
 
+    def cover_layout(self, first_ptr: int) -> int:
+        """The slots of the depth profile (``vs_cover_layout``): ``first_ptr`` is a device pointer to ``n_nodes + 1`` uint32,
+        written with the first slot of every segment in the index's INTERNAL numbering and the slot total behind them -- a
+        segment of ``k + 1`` bases or more owns one slot per window and one sentinel.  -> the slot total."""
+        n = C.c_uint64(0)
+        nat.check(self._h, nat.lib().vs_cover_layout(self._h, C.c_void_p(first_ptr), C.byref(n)))
+        return int(n.value)
+
+    def node_cover(self, reads: ReadBlock, first_ptr: int, diff_ptr: int):
+        """One block through the profile pass (``vs_node_cover``): +1 / -1 per maximal match on the uint32 difference array
+        at ``diff_ptr`` (one word per slot of ``cover_layout``).  Blocks must have been built after ``keep_masks(True)``."""
+        nat.check(self._h, nat.lib().vs_node_cover(self._h, reads._h, C.c_void_p(first_ptr), C.c_void_p(diff_ptr)))
+
+    def cover_fold(self, diff_ptr: int, cov_ptr: int, n_slots: int):
+        """The differences scanned into counts, added to the uint64 totals at ``cov_ptr`` and zeroed (``vs_cover_fold``)."""
+        nat.check(self._h, nat.lib().vs_cover_fold(self._h, C.c_void_p(diff_ptr), C.c_void_p(cov_ptr), n_slots))
+
     def contig_mems(self, reads: ReadBlock) -> np.ndarray:
         """Every maximal exact match of k + 1 bases or more between a contig of the block and a strand of a segment
         (``vs_contig_mems``): uint32 [n, 5] -- contig, first base in the contig, segment | strand << 31, first base in that
@@ -1934,6 +1951,97 @@ class DepthCounter:
         if self.node_rank is not None:
             kc = kc.index_select(0, self.torch.from_numpy(self.node_rank).to(kc.device))
         return kc.cpu().numpy().astype(np.int64)
+
+
+def cover_plan(n_nodes: int, ksize: int, n_ends: int, max_len: int, n_cu: int = 256, pending: int = 0, bound: int = 2 ** 32) -> dict:
+    """The launch ``vs_node_cover`` makes for a block and whether a fold is due before it (``vs_cover_plan``, a pure host
+    function: no device is needed).  ``pending``: the ``pending`` of the block before (0 at the start and after a fold);
+    ``bound``: what the pending weight may not reach between two folds."""
+    a = (C.c_uint64 * 8)()
+    rc = nat.lib().vs_cover_plan(n_nodes, ksize, n_ends, max_len, n_cu, pending, bound, a)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_cover_plan refuses %d nodes / %d ends of up to %d bases (pending %d, bound %d)" % (n_nodes, n_ends, max_len, pending, bound))
+    return dict(launch=bool(a[0]), grid=int(a[1]), ends_per_wg=int(a[2]), weight=int(a[3]), fold_first=bool(a[4]), pending=int(a[5]),
+                lds_bytes=int(a[6]), threads=int(a[7]))
+
+
+class CoverCounter:
+    """The k-mer depth of every window of every segment, counted from the reads on one device (``vs_node_cover``):
+    ``cov[n][p]`` = the (k+1)-mer occurrences ``KC[n]`` counts whose table entry is ``(n, p)`` -- the window that STARTS at
+    forward offset ``p`` (k-mer coverage, not base coverage).  Takes ``DepthCounter``'s place in the input dispatch of
+    ``pe_inference`` (``add``, ``device``, ``single_stats``, ``ends_seen``; the context keeps the masks): one kernel per block,
+    and ``kc()`` is what ``DepthCounter.result()`` gives.  Holds 4 + 8 bytes per slot (a slot per window and one per segment);
+    the context holds 4 more per slot once a fold ran.  ``fold_bound``: ``cover_plan``'s ``bound`` (a test sets it low)."""
+
+    def __init__(self, ctx: Context, fold_bound: int = 2 ** 32, device: Optional[str] = None):
+        import torch
+
+        self.torch = torch
+        self.ctx = ctx
+        self.device = torch.device(device or ("cuda:%d" % ctx.device))
+        self.n = ctx.n_nodes
+        self.ksize = ctx.ksize
+        self.fold_bound = fold_bound
+        self.single_stats = torch.zeros(3, dtype=torch.int64, device=self.device)  # (what the dispatch tallies of a PeCounter: stays zero)
+        self.ends_seen = 0  # ends the blocks delivered (the absent second ends of singles blocks aside)
+        self.folds = 0
+        self.pending = 0    # cover_plan's weight of the blocks since the last fold
+        self.node_rank = getattr(ctx, "node_rank", None)  # (kept here: a later build_index cannot change how the slots are read)
+        with torch.cuda.device(self.device):
+            ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.first = torch.zeros(self.n + 1, dtype=torch.int32, device=self.device)  # (uint32 words)
+            self.slots = ctx.cover_layout(self.first.data_ptr())
+            self.diff = torch.zeros(max(self.slots, 1), dtype=torch.int32, device=self.device)  # (uint32 words, wrap-around adds)
+            self.cov = torch.zeros(max(self.slots, 1), dtype=torch.int64, device=self.device)
+        ctx.keep_masks(True)
+
+    def fold(self):
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.ctx.cover_fold(self.diff.data_ptr(), self.cov.data_ptr(), self.slots)
+        self.pending = 0
+        self.folds += 1
+
+    def add(self, reads: ReadBlock):
+        torch = self.torch
+        info = reads.info
+        n_ends = info["ends"]
+        self.ends_seen += n_ends // 2 if reads.unpaired else n_ends
+        plan = cover_plan(self.n, self.ksize, n_ends, info["max_len"], pending=self.pending, bound=self.fold_bound)
+        if plan["fold_first"]:
+            self.fold()
+        self.pending = plan["pending"]
+        if not self.slots:
+            return
+        with torch.cuda.device(self.device):
+            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.ctx.node_cover(reads, self.first.data_ptr(), self.diff.data_ptr())
+
+    def result(self):
+        """-> (offsets int64 [N + 1], cov int64 [W]): the windows of segment ``n`` of the node list ``Context.build_index`` was
+        given (the GFA's order) are ``cov[offsets[n] : offsets[n + 1]]``, without sentinel slots; a segment shorter than
+        ``k + 1`` bases is an empty range."""
+        if self.pending:
+            self.fold()
+        first = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
+        slots = self.cov[: self.slots].cpu().numpy()
+        windows = np.maximum(first[1:] - first[:-1] - 1, 0)
+        start = first[:-1]
+        if self.node_rank is not None:
+            windows, start = windows[self.node_rank], start[self.node_rank]
+        offsets = np.zeros(self.n + 1, dtype=np.int64)
+        np.cumsum(windows, out=offsets[1:])
+        total = int(offsets[-1])
+        at = np.repeat(start - offsets[:-1], windows) + np.arange(total, dtype=np.int64)
+        return offsets, slots[at].astype(np.int64)
+
+    def kc(self) -> np.ndarray:
+        """The row sums, int64 [N] in the GFA's order: ``KC`` as ``DepthCounter.result()`` gives it."""
+        offsets, cov = self.result()
+        run = np.zeros(cov.size + 1, dtype=np.int64)
+        np.cumsum(cov, out=run[1:])
+        return run[offsets[1:]] - run[offsets[:-1]]
 
 
 # ---- outputs -------------------------------------------------------------------------------------
