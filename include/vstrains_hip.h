@@ -876,6 +876,56 @@ int vs_cover_fold(vs_ctx *ctx, uint32_t *d_diff, uint64_t *d_cov, uint64_t n_slo
 int vs_cover_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t pending, uint64_t bound,
                   uint64_t plan[8]);
 
+/* ---- base pileup of every segment from the reads (additions to ABI 11 without a new number: nothing that exists changes) --
+ * No counterpart in the reference.  With K = k + 1 and a mismatch budget M: a read end e, a strand t of a segment n with
+ * len_n >= K (its forward text or the reverse complement) and a diagonal d = strand offset - read offset make a candidate
+ * alignment whose OVERLAP is the read offsets x with 0 <= x < len_e and 0 <= x + d < len_n.  A position AGREES when the read
+ * byte is one of ACGT and equals the strand's base.  The alignment is ANCHORED when its overlap holds K agreeing positions in
+ * a row (a maximal exact match as vs_node_cover finds them) and CREDITED when at most M positions of the whole overlap do
+ * not agree (a byte outside ACGT does not agree); it counts once, however many exact matches lie on its diagonal; a rejected
+ * one deposits nothing and is tallied.  For every overlap position of a credited alignment, p its forward offset on the
+ * segment: depth[n][p] += 1, and where it does not agree alt[n][p][c] += 1, c the read's base as it reads on the forward
+ * strand (0..3 = ACGT, complemented for the reverse-complement strand; 4 = a byte outside ACGT).  The rules of the depth
+ * pass hold (a palindromic overlap is two alignments; a read fitting twice counts at each; short, empty and absent ends
+ * nothing; every end of every block).  Substitutions only: an indel ends the diagonal.  tests/pileup_model.py states it;
+ * csrc/vs_pileup_plan.h has the slots and the fold rule, csrc/vs_pileup_core.h the walk along the diagonal.
+ * Slots: segment n of the index's own numbering owns len_n + 1 of them when len_n >= K, else none: one per position and one
+ * sentinel behind them, which takes the -1 of an overlap flush with the segment's end and is 0 after every fold.
+ *   vs_pileup_layout    : d_first: DEVICE pointer to n_nodes + 1 words, written: the first slot of every segment of the
+ *                         context's CURRENT index, in the numbering vs_index_build was given, and the slot total S behind
+ *                         them; *n_slots = S (host).  Synchronises the ctx stream.  VS_E_RANGE: S >= 2^32 (*n_slots is set).
+ *   vs_node_pileup      : one block through k_node_pileup on the context's current index.  Every credited alignment adds +1
+ *                         to the slot of its overlap's first forward position and -1 to the slot behind its last, on d_diff
+ *                         (DEVICE, S uint32, zero before the first block, wrap-around adds, atomically; folded into uint64
+ *                         totals by vs_cover_fold, which is generic over a slot array), and 1 to d_alt[slot * 5 + c]
+ *                         (DEVICE, S x 5 uint64, zero before the first block) per non-agreeing position.  d_tally: DEVICE,
+ *                         2 uint64, added to: alignments credited, alignments rejected (anchored, more than max_mismatch
+ *                         non-agreeing positions).  d_first: what vs_pileup_layout wrote for THIS index.  Enqueued on the ctx
+ *                         stream.  Blocks must have been built after vs_ctx_keep_masks(ctx, 1).  VS_E_RANGE: 2^32 ends, or
+ *                         a block whose ends could put 2^32 on one position (n_ends * 2 * max_len >= 2^32).
+ *   vs_pileup_plan      : host only, a pure function (csrc/vs_pileup_plan.h), with the arguments and the fields of
+ *                         vs_cover_plan: plan[0] = 1 if k_node_pileup is launched (0: no end holds K bases); [1] =
+ *                         workgroups; [2] = ends per workgroup; [3] = the block's weight n_ends * 2 * max_len, the most it
+ *                         can add to one slot; [4] = 1 if vs_cover_fold is due BEFORE this block (pending > 0 and pending +
+ *                         weight >= bound); [5] = the weight pending once the block is counted; [6] = LDS bytes per
+ *                         workgroup; [7] = threads per workgroup.  VS_E_RANGE: more than 2^25 - 2 nodes, 2^32 ends, a weight
+ *                         of 2^32 or more, bound or pending beyond 2^32.
+ *   vs_pileup_scan_host : host only, no device: the walk of csrc/vs_pileup_core.h, the code the kernel runs, on HOST buffers.
+ *                         read_words / strand_words: packed texts (2 bits a base, 16 a word, first base lowest; A C G T =
+ *                         0 1 2 3) of rlen / tlen bases, each with 3 zero words behind its last word; read_mask: NULL, or
+ *                         the same layout with 0b11 where the read's byte is outside ACGT.  (a, qa): where on the read and
+ *                         on the strand a maximal exact match starts (a < rlen, qa < tlen; the base before it does not agree
+ *                         or is outside the overlap).  out[0] = 1 if no run of K agreeing bases lies left of it on its
+ *                         diagonal (this match owns the alignment); out[1], out[2] = the overlap [x_lo, x_hi) in read
+ *                         offsets; out[3] = its non-agreeing positions.  VS_E_ARG: a NULL text, K = 0, a or qa outside. */
+int vs_pileup_layout(vs_ctx *ctx, uint32_t *d_first, uint64_t *n_slots);
+int vs_node_pileup(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, uint32_t *d_diff, uint64_t *d_alt, uint32_t max_mismatch,
+                   uint64_t *d_tally);
+int vs_pileup_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t pending, uint64_t bound,
+                   uint64_t plan[8]);
+int vs_pileup_scan_host(const uint32_t *read_words, const uint32_t *read_mask, const uint32_t *strand_words, uint32_t rlen, uint32_t tlen, uint32_t a,
+                        uint32_t qa, uint32_t K, uint32_t out[4]);
+
 /* Testing aid (ABI 11): the two exclusive scans under the index build, the locus sort, every row_ptr and every member,
  * record and word offset, run alone on values the caller made up, launched exactly as their callers launch them (no kernel
  * of its own).  HOST pointers: in[n + guard] = the n values and behind them `guard` words of a sentinel the caller chose;

@@ -108,6 +108,9 @@ def build_parser():
     # with --depth-from-reads: the same single pass also writes the depth of every window of k + 1 bases (k-mer coverage by window
     # START, not base coverage) as gfa/graph_depth.bedgraph and a line per segment as gfa/graph_depth.tsv (vstrains_amd.node_depth)
     p.add_argument("--depth-profile", dest="depth_profile", action="store_true", default=False, help=argparse.SUPPRESS)
+    # with --depth-from-reads: the same read pass also lays every end along its anchors' diagonals across mismatches and writes the
+    # base pileup as gfa/graph_depth.pileup.tsv and its minor bases as gfa/graph_depth.vcf (vstrains_amd.node_depth --pileup --variants)
+    p.add_argument("--depth-pileup", dest="depth_pileup", action="store_true", default=False, help=argparse.SUPPRESS)
     return p
 
 
@@ -145,6 +148,13 @@ def depth_profile_refusal(args):
     return None
 
 
+def depth_pileup_refusal(args):
+    """None, or why ``--depth-pileup`` cannot hold, said before anything is written: it rides on the depth pass."""
+    if args.depth_pileup and not args.depth_from_reads:
+        return "--depth-pileup writes the base pileup of the depth pass: give --depth-from-reads with it"
+    return None
+
+
 def depth_from_reads_refusal(args, world: int):
     """None, or why ``--depth-from-reads`` cannot hold, said before anything is written: under a process group, or -- the
     reads are read twice, once for the depth and once for the PE links -- with an input that is not a regular file (with
@@ -177,7 +187,7 @@ def depth_from_reads(args, logger, ctx):
         sys.exit(1)
     got = node_depth.depth_pass(ctx, args.gfa_file, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=args.interleaved,
                                 check_names=args.check_names, single=args.single, count_singles=args.count_singles, quiet=True,
-                                profile=args.depth_profile)
+                                profile=args.depth_profile, pileup=8 if args.depth_pileup else None)
     ids, kc, ends = got[:3]
     out = args.output_dir + "/gfa/graph_depth.gfa"
     with open(out, "wb") as fh:
@@ -187,6 +197,12 @@ def depth_from_reads(args, logger, ctx):
         node_depth.write_bedgraph(args.output_dir + "/gfa/graph_depth.bedgraph", ids, offsets, cov)
         node_depth.write_summary(args.output_dir + "/gfa/graph_depth.tsv", ids, lengths, offsets, cov)
         logger.info("depth profile of every window of k + 1 bases: {0}/gfa/graph_depth.bedgraph, per segment: {0}/gfa/graph_depth.tsv".format(args.output_dir))
+    if args.depth_pileup:
+        seqs, p_offsets, p_depth, p_alt, (credited, rejected) = got[-1]
+        node_depth.write_pileup(args.output_dir + "/gfa/graph_depth.pileup.tsv", ids, seqs, p_offsets, p_depth, p_alt)
+        node_depth.write_vcf(args.output_dir + "/gfa/graph_depth.vcf", ids, seqs, p_offsets, p_depth, p_alt)
+        logger.info("base pileup of every position: {0}/gfa/graph_depth.pileup.tsv, minor bases: {0}/gfa/graph_depth.vcf ({1} alignments, {2} rejected)"
+                    .format(args.output_dir, credited, rejected))
     logger.info("segment depth counted from the reads: k = {0}, {1} read ends, KC sum {2}; the graph goes on as {3}".format(k, ends, int(kc.sum()), out))
     empty = [ids[i] for i in range(len(ids)) if kc[i] == 0]
     if empty:
@@ -239,7 +255,7 @@ def main(argv=None, backend=None):
     args.single = pe_inference.unpaired_input(args.single, args.count_singles, pe_inference._rank_world()[1], args.interleaved,
                                               pe_text_from=args.pe_text_from, check_names=args.check_names, bam_by_name=args.bam_by_name,
                                               fwd=args.fwd, rve=args.rve)
-    why = depth_profile_refusal(args)
+    why = depth_profile_refusal(args) or depth_pileup_refusal(args)
     if why is not None:
         raise ValueError(why)
     if args.depth_from_reads:

@@ -3652,3 +3652,234 @@ extern "C" int vs_cover_fold(vs_ctx *ctx, uint32_t *d_diff, uint64_t *d_cov, uin
     VS_HIP(ctx, hipGetLastError());
     return VS_OK;
 }
+
+// ---- base pileup of every segment from the reads (vs_pileup_layout / vs_node_pileup; the depth folds by vs_cover_fold) ----
+// One step past vs_extend: the read is laid along the diagonal of an exact anchor ACROSS its mismatches, the overlap is
+// counted once and what differs is written down (the definition, the slots and the fold rule: vs_pileup_plan.h,
+// tests/pileup_model.py; the walk: vs_pileup_core.h).  The end batches, the probe grid, the table probe, the posting deal and
+// vs_extend under the mask are k_node_cover's.  The lane that holds a match (a, qa, len) looks LEFT along the diagonal for
+// another run of K agreeing bases: if there is one, an earlier match owns the alignment and this lane is done -- once per
+// diagonal, with no word passed between lanes.  The owner counts the non-agreeing positions of the whole overlap; above the
+// budget the alignment is rejected and only tallied.  Otherwise the depth is written as a DIFFERENCE, +1 into the slot of the
+// overlap's first forward position and -1 into the slot behind its last (two dword atomics, whatever the overlap's length),
+// and every non-agreeing position costs one 64-bit atomic into alt[slot][c]; an agreeing base costs nothing, the reference
+// base's count being the depth minus the others.  The two tallies are claimed per wavefront by ballot, as k_contig_mems
+// claims its records.
+#include "vs_pileup_core.h"
+#include "vs_pileup_plan.h"
+
+struct PileupParams {
+    VsIndexDev idx;
+    VsReadsDev rd;
+    const uint32_t *first;     // [n_nodes + 1] the first slot of every segment, the slot total behind them
+    uint32_t *diff;            // [first[n_nodes]] differences of the depth, ADDED to
+    unsigned long long *alt;   // [first[n_nodes]][PILEUP_ALT] non-agreeing bases, ADDED to
+    unsigned long long *tally; // [2] alignments credited, alignments rejected, ADDED to
+    uint64_t ends_per_wg;
+    uint32_t max_mismatch;
+};
+
+__global__ void __launch_bounds__(256)
+k_pileup_slots(const VsNodeMeta *meta, uint32_t n_nodes, uint32_t K, uint32_t *cnt) {
+    const uint64_t n = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (n > n_nodes) return;
+    uint32_t v = 0u;
+    if (n < n_nodes) {
+        const uint32_t len = meta[n].len;
+        if (len >= K) v = len + 1u;  // its positions and the sentinel
+    }
+    cnt[n] = v;  // (cnt[n_nodes] = 0: its scan is the total)
+}
+
+__device__ __forceinline__ void vs_pileup_tally(unsigned long long *at, bool mine, uint32_t lane) {
+    const unsigned long long have = __ballot(mine);
+    if (have && lane == (uint32_t)__ffsll((long long)have) - 1u) atomicAdd(at, (unsigned long long)__popcll(have));
+}
+
+__global__ void __launch_bounds__(PILEUP_TPB, 8)  // (eight wavefronts a SIMD: two workgroups a CU, as the plan deals them)
+k_node_pileup(PileupParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_mem[PILEUP_LDS_WORDS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t N = P.idx.n_nodes, w = P.idx.w, s = P.idx.s, K = P.idx.K;
+    uint32_t *s_head = s_mem;
+    uint32_t *sw = s_mem + PILEUP_HEAD_WORDS + wave * PILEUP_WAVE_WORDS;
+    uint32_t *s_np = sw, *s_cnt = sw + 65u, *s_pa = sw + 130u, *s_pb = sw + 194u, *s_pj = sw + 258u;
+    const uint64_t e_lo = (uint64_t)blockIdx.x * P.ends_per_wg;
+    const uint64_t e_hi = e_lo + P.ends_per_wg < P.rd.n_ends ? e_lo + P.ends_per_wg : P.rd.n_ends;
+    if (tid == 0u) s_head[0] = 0u;
+    __syncthreads();
+    for (;;) {
+        uint32_t b = 0u;
+        if (lane == 0u) b = atomicAdd(&s_head[0], 64u);
+        b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+        if (e_lo + b >= e_hi) break;
+        const uint64_t e0 = e_lo + b;
+        const uint32_t n_here = e_hi - e0 < 64u ? (uint32_t)(e_hi - e0) : 64u;
+        uint32_t np = 0u;
+        if (lane < n_here) {
+            const uint32_t meta = P.rd.meta[e0 + lane];
+            if (!((meta >> 24) & VS_FLAG_ABSENT)) np = vs_seed_probes(meta & VS_LEN_MASK, w, s);  // (0 for an end shorter than K)
+        }
+        s_np[lane + 1u] = vs_wave_scan_add(np);
+        if (lane == 0u) s_np[0] = 0u;
+        vs_wave_sync();
+        const uint32_t tp = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_np[64]);
+        for (uint32_t p0 = 0u; p0 < tp; p0 += 64u) {
+            // probes p0 .. p0 + 63 of the batch: one per lane
+            const uint32_t t = p0 + lane;
+            uint32_t c = 0u, pa = 0u, pb = 0u, pj = 0u;
+            if (t < tp) {
+                const uint32_t el = vs_upper_idx(s_np, 65u, t);  // the end that owns probe t: s_np[el] <= t < s_np[el + 1]
+                const uint64_t e = e0 + el;
+                const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                const uint32_t j = vs_seed_phase(rlen, w, s) + (t - s_np[el]) * s;
+                const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                if (!(mk && vs_seed_dirty(mk, rbase + j, w))) {
+                    uint32_t sr;
+                    const uint64_t key = vs_seed_key(P.rd.words, rbase + j, w, &sr);
+                    c = vs_probe(P.idx, key, sr, &pa, &pb);
+                }
+                pj = (el << 24) | j;  // (a read offset fits 24 bits: VS_LEN_MASK)
+            }
+            s_pa[lane] = pa;
+            s_pb[lane] = pb;
+            s_pj[lane] = pj;
+            s_cnt[lane + 1u] = vs_wave_scan_add(c);
+            if (lane == 0u) s_cnt[0] = 0u;
+            vs_wave_sync();
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[64]);
+            for (uint32_t q0 = 0u; q0 < total; q0 += 64u) {
+                // postings q0 .. q0 + 63 of these probes: one per lane
+                const uint32_t t2 = q0 + lane;
+                bool credited = false, rejected = false;
+                if (t2 < total) {
+                    const uint32_t pr = vs_upper_idx(s_cnt, 65u, t2);
+                    const uint32_t k2 = t2 - s_cnt[pr];
+                    const uint32_t qa0 = s_pa[pr], qb0 = s_pb[pr], ej = s_pj[pr];
+                    const uint32_t j = ej & VS_LEN_MASK;
+                    const uint64_t e = e0 + (ej >> 24);
+                    const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                    const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                    const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                    uint32_t nd, pos, opp;
+                    VsNodeMeta nm;
+                    if (s_cnt[pr + 1u] - s_cnt[pr] == 1u) {
+                        nd = qa0; pos = qb0 & 0x7FFFFFFFu; opp = qb0 >> 31;
+                        nm = P.idx.meta[nd];
+                    } else {
+                        const VsPosting po = vs_posting_unpack(P.idx.postings[qa0 + k2]);
+                        nd = po.node; pos = po.pos; opp = po.strand ^ (qb0 >> 31);
+                        nm.woff = po.woff; nm.len = po.len;
+                    }
+                    const uint32_t *tw = opp ? P.idx.rc_words : P.idx.fwd_words;
+                    const uint32_t q = opp ? nm.len - pos - w : pos;
+                    uint32_t a, qa, len;
+                    // (k >= 95: VS_SEED_VERIFIED is 0, the key only nominated the posting and the comparison starts at the seed's first base)
+                    if (nd < N && vs_extend(P.rd.words, rbase, rlen, tw, nm.woff * 16u, nm.len, j, q, VS_SEED_VERIFIED(w), s, K, mk, rbase, &a, &qa, &len) &&
+                        qa + len <= nm.len) {  // (a match lies inside its strand: no slot beyond the segment's sentinel)
+                        const uint64_t tbase = (uint64_t)nm.woff * 16u;
+                        const VsPileupSpan sp = vs_pileup_span(rlen, nm.len, a, qa);
+                        if (vs_pileup_owner(P.rd.words, rbase, tw, tbase, mk, sp, a, K)) {
+                            uint32_t miss = vs_pileup_count(P.rd.words, rbase, tw, tbase, mk, sp);
+                            rejected = miss > P.max_mismatch;
+                            credited = !rejected;
+                            if (credited) {
+                                // the overlap on the strand: [t_lo, t_hi); on the forward text: from p_lo on, as many
+                                const uint32_t t_lo = (uint32_t)((int64_t)sp.x_lo + sp.d), t_hi = (uint32_t)((int64_t)sp.x_hi + sp.d);
+                                const uint32_t at = P.first[nd] + (opp ? nm.len - t_hi : t_lo);
+                                atomicAdd(&P.diff[at], 1u);
+                                atomicAdd(&P.diff[at + (sp.x_hi - sp.x_lo)], 0xFFFFFFFFu);
+                                for (uint32_t x = sp.x_lo; miss && x < sp.x_hi; x += 32u) {
+                                    const uint32_t n = sp.x_hi - x < 32u ? sp.x_hi - x : 32u;
+                                    uint64_t f = vs_pl_differ(P.rd.words, rbase, tw, tbase, mk, x, sp.d, n);
+                                    if (!f) continue;
+                                    const uint64_t rwin = vs_pl_win(P.rd.words, rbase + x);
+                                    const uint64_t mwin = mk ? vs_pl_win(mk, rbase + x) : 0ull;
+                                    while (f) {
+                                        const uint32_t bit = (uint32_t)__ffsll((long long)f) - 1u;  // (even: 2 * the base's place in the window)
+                                        f &= f - 1ull;
+                                        const uint32_t code = (uint32_t)(rwin >> bit) & 3u;
+                                        // the read's base as it reads on the forward strand; a byte outside ACGT: `other`
+                                        const uint32_t col = ((mwin >> bit) & 3ull) ? 4u : (opp ? 3u - code : code);
+                                        const uint32_t ts = t_lo + (x - sp.x_lo) + (bit >> 1);  // strand offset of the base
+                                        const uint64_t slot = (uint64_t)P.first[nd] + (opp ? nm.len - 1u - ts : ts);
+                                        atomicAdd(&P.alt[slot * PILEUP_ALT + col], 1ull);
+                                        miss--;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+                vs_pileup_tally(P.tally, credited, lane);
+                vs_pileup_tally(P.tally + 1, rejected, lane);
+            }
+            vs_wave_sync();  // s_cnt / s_pa / s_pb / s_pj are rewritten by the next 64 probes
+        }
+        vs_wave_sync();  // s_np is rewritten by the next batch
+    }
+}
+
+extern "C" int vs_pileup_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t pending, uint64_t bound,
+                              uint64_t plan[8]) {
+    if (!plan) return VS_E_ARG;
+    const PileupPlan p = vs_pileup_plan_for(n_nodes, ksize + 1u, n_ends, max_len, n_cu, pending, bound);
+    plan[0] = p.launch; plan[1] = p.grid; plan[2] = p.ends_per_wg; plan[3] = p.weight;
+    plan[4] = p.fold_first; plan[5] = p.pending; plan[6] = sizeof(uint32_t) * PILEUP_LDS_WORDS; plan[7] = PILEUP_TPB;
+    return p.status;
+}
+
+extern "C" int vs_pileup_scan_host(const uint32_t *read_words, const uint32_t *read_mask, const uint32_t *strand_words, uint32_t rlen, uint32_t tlen,
+                                   uint32_t a, uint32_t qa, uint32_t K, uint32_t out[4]) {
+    if (!read_words || !strand_words || !out || !K || a >= rlen || qa >= tlen) return VS_E_ARG;
+    const VsPileupSpan sp = vs_pileup_span(rlen, tlen, a, qa);
+    out[0] = vs_pileup_owner(read_words, 0u, strand_words, 0u, read_mask, sp, a, K);
+    out[1] = sp.x_lo;
+    out[2] = sp.x_hi;
+    out[3] = vs_pileup_count(read_words, 0u, strand_words, 0u, read_mask, sp);
+    return VS_OK;
+}
+
+extern "C" int vs_pileup_layout(vs_ctx *ctx, uint32_t *d_first, uint64_t *n_slots) {
+    if (!ctx || !d_first || !n_slots) return VS_E_ARG;
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_pileup_layout: build an index first (vs_index_build)");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const VsIndexDev &idx = ctx->idx;
+    const uint64_t m = (uint64_t)idx.n_nodes + 1u, nb = (m + 2047u) / 2048u;
+    VS_HIP(ctx, ctx->d_cover_tmp.reserve(sizeof(uint64_t) * (nb + 2u)));
+    uint64_t *d_tmp = ctx->d_cover_tmp.as<uint64_t>(), *d_total = d_tmp + nb + 1u;
+    hipLaunchKernelGGL(k_pileup_slots, dim3((unsigned)((m + 255u) / 256u)), dim3(256), 0, ctx->stream, idx.meta, idx.n_nodes, idx.K, d_first);
+    VS_HIP(ctx, hipGetLastError());
+    if (int rc = vs_scan_u32(ctx, d_first, d_first, m, d_tmp, d_total)) return rc;
+    uint64_t total = 0;
+    VS_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_slots = total;
+    if (total >= (1ull << 32))
+        return vs_fail(ctx, VS_E_RANGE, "vs_pileup_layout: %llu slots, and a slot number has 32 bits: pile the graph up in parts", (unsigned long long)total);
+    return VS_OK;
+}
+
+extern "C" int vs_node_pileup(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, uint32_t *d_diff, uint64_t *d_alt, uint32_t max_mismatch,
+                              uint64_t *d_tally) {
+    if (!ctx || !reads || !d_first || !d_diff || !d_alt || !d_tally) return VS_E_ARG;
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_node_pileup: build an index first (vs_index_build)");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const VsIndexDev &idx = ctx->idx;
+    const PileupPlan pl = vs_pileup_plan_for(idx.n_nodes, idx.K, reads->n_ends, (uint32_t)reads->max_len, (uint32_t)ctx->n_cu, 0, 0);
+    if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "vs_node_pileup: %s", pl.msg);
+    if (!pl.launch) return VS_OK;  // no end of the block holds an anchor
+    PileupParams P;
+    P.idx = idx;
+    P.rd = reads->dev();
+    P.first = d_first;
+    P.diff = d_diff;
+    P.alt = (unsigned long long *)d_alt;
+    P.tally = (unsigned long long *)d_tally;
+    P.ends_per_wg = pl.ends_per_wg;
+    P.max_mismatch = max_mismatch;
+    hipLaunchKernelGGL(k_node_pileup, dim3(pl.grid), dim3(PILEUP_TPB), 0, ctx->stream, P);
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}

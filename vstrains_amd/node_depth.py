@@ -16,6 +16,14 @@ With any of these the same single pass keeps the triples apart by their entry's 
 ``tests/depth_profile_model.py``): ``cov[n][p]`` belongs to the WINDOW of ``k + 1`` bases that starts at ``p`` -- k-mer
 coverage, not base coverage -- and ``KC[n]`` is the sum of its row.  ``--profile`` writes it as a bedGraph, ``--profile-summary``
 as one line per segment, ``--depth-stat median`` puts ``median * LN`` into ``KC:i``.
+
+    ... --pileup FILE[.gz] [--variants FILE[.gz]] [--pileup-max-mismatch M] [--min-alt-count C] [--min-alt-frac F]
+
+With ``--pileup`` or ``--variants`` the same read pass also lays every end along the diagonal of each exact anchor of ``k + 1``
+bases ACROSS its mismatches (``pe.PileupCounter``, ``tests/pileup_model.py``): an alignment with at most ``M`` non-agreeing
+positions in its overlap adds one to the depth of every position it covers and is written down where it differs -- BASE
+coverage, substitutions only, no base qualities.  ``--pileup`` writes the A/C/G/T/other table of every position, ``--variants``
+the minor bases above the two thresholds as VCF 4.2.
 """
 import argparse
 import contextlib
@@ -117,6 +125,102 @@ def depth_stat(stat: str, lengths, offsets, cov):
     raise ValueError("no depth statistic %r" % (stat,))
 
 
+PILEUP_COLUMNS = ("segment", "pos", "ref", "A", "C", "G", "T", "other")
+VCF_SOURCE = "vstrains_amd.node_depth"
+
+
+def pileup_counts(seqs, offsets, depth, alt):
+    """-> int64 [P, 5]: A, C, G, T, other per position, in the order of ``offsets``: the alt columns as counted, and in the
+    column of the segment's own base the depth minus every alt column (the reads that agree there).  A segment whose base
+    is not one of ACGT at a position keeps its four columns as counted."""
+    import numpy as np
+
+    depth, counts = np.asarray(depth, dtype=np.int64), np.array(alt, dtype=np.int64).reshape(-1, 5)
+    for n, seq in enumerate(seqs):
+        a, b = int(offsets[n]), int(offsets[n + 1])
+        if b == a:
+            continue
+        ref = np.frombuffer(seq[:b - a].encode("latin-1"), dtype=np.uint8)
+        for col, base in enumerate(b"ACGT"):
+            at = a + np.flatnonzero(ref == base)
+            counts[at, col] = depth[at] - counts[at].sum(axis=1) + counts[at, col]
+    return counts
+
+
+def write_pileup(path: str, ids, seqs, offsets, depth, alt) -> None:
+    """A TSV with a header line and the columns of ``PILEUP_COLUMNS``: one row for every position (1-based) of every segment of
+    ``k + 1`` bases or more, zeros included, segments in file order; a shorter segment has no row.  ``.gz``: through gzip."""
+    counts = pileup_counts(seqs, offsets, depth, alt)
+    with _open_text(path) as fh:
+        fh.write("\t".join(PILEUP_COLUMNS) + "\n")
+        for n, name in enumerate(ids):
+            a, b = int(offsets[n]), int(offsets[n + 1])
+            seq = seqs[n]
+            fh.write("".join("%s\t%d\t%s\t%d\t%d\t%d\t%d\t%d\n" % ((name, p + 1, seq[p]) + tuple(counts[a + p].tolist())) for p in range(b - a)))
+
+
+def variant_records(ids, seqs, offsets, depth, alt, min_alt_count: int = 2, min_alt_frac: float = 0.01):
+    """(segment, 1-based pos, ref, alt base, DP, AD) of every (position, non-reference base) with ``AD >= min_alt_count`` and
+    ``AD >= min_alt_frac * DP`` (and, whatever the thresholds, at least one read), ``DP = A + C + G + T``; in file order, then by position, then by base in ACGT order."""
+    counts = pileup_counts(seqs, offsets, depth, alt)
+    out = []
+    for n, name in enumerate(ids):
+        a, b = int(offsets[n]), int(offsets[n + 1])
+        seq = seqs[n]
+        for p in range(b - a):
+            row = counts[a + p, :4].tolist()
+            dp = sum(row)
+            for base, ad in zip("ACGT", row):
+                if base != seq[p] and ad > 0 and ad >= min_alt_count and ad >= min_alt_frac * dp:
+                    out.append((name, p + 1, seq[p], base, dp, ad))
+    return out
+
+
+def write_vcf(path: str, ids, seqs, offsets, depth, alt, min_alt_count: int = 2, min_alt_frac: float = 0.01) -> None:
+    """VCF 4.2: ``fileformat``, ``source``, a ``contig`` line per segment that has rows, ``INFO`` DP, AD, AF, and one biallelic
+    record per entry of ``variant_records``; ``AF = "%.6f" % (AD / DP)``, ``ID``, ``QUAL`` and ``FILTER`` are ``.``."""
+    with _open_text(path) as fh:
+        fh.write("##fileformat=VCFv4.2\n##source=%s\n" % VCF_SOURCE)
+        for n, name in enumerate(ids):
+            if offsets[n + 1] > offsets[n]:
+                fh.write("##contig=<ID=%s,length=%d>\n" % (name, len(seqs[n])))
+        fh.write('##INFO=<ID=DP,Number=1,Type=Integer,Description="Reads carrying A, C, G or T at the position">\n'
+                 '##INFO=<ID=AD,Number=1,Type=Integer,Description="Reads carrying the alternate base">\n'
+                 '##INFO=<ID=AF,Number=1,Type=Float,Description="AD / DP">\n'
+                 "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
+        for name, pos, ref, base, dp, ad in variant_records(ids, seqs, offsets, depth, alt, min_alt_count, min_alt_frac):
+            fh.write("%s\t%d\t.\t%s\t%s\t.\t.\tDP=%d;AD=%d;AF=%.6f\n" % (name, pos, ref, base, dp, ad, ad / dp))
+
+
+def pileup_refusal(args):
+    """None, or why the pileup's flags cannot hold, said before a device is opened."""
+    asked = args.pileup is not None or args.variants is not None
+    if args.pileup_max_mismatch is not None and args.pileup_max_mismatch < 0:
+        return "--pileup-max-mismatch %d: the budget is an integer from 0 up" % args.pileup_max_mismatch
+    if args.min_alt_count is not None and args.min_alt_count < 0:
+        return "--min-alt-count %d: a count from 0 up is needed" % args.min_alt_count
+    if args.min_alt_frac is not None and not 0.0 <= args.min_alt_frac <= 1.0:
+        return "--min-alt-frac %r: a fraction between 0 and 1 is needed" % args.min_alt_frac
+    if not asked and (args.pileup_max_mismatch is not None or args.min_alt_count is not None or args.min_alt_frac is not None):
+        return "--pileup-max-mismatch, --min-alt-count and --min-alt-frac belong to --pileup / --variants: give one of them"
+    if args.variants is None and (args.min_alt_count is not None or args.min_alt_frac is not None):
+        return "--min-alt-count and --min-alt-frac select the records of --variants: give it"
+    return None
+
+
+class _Both:
+    """Two counters behind one ``add``: what the input dispatch needs of a counter (``pe_inference.feed_counter``), handed on
+    to both, so that the pileup rides on the read pass of the depth."""
+
+    def __init__(self, main, extra):
+        self.main, self.extra = main, extra
+        self.device, self.single_stats = main.device, main.single_stats
+
+    def add(self, reads):
+        self.main.add(reads)
+        self.extra.add(reads)
+
+
 def rewrite_gfa(raw: bytes, kc) -> bytes:
     """``raw`` again, every ``S`` line carrying ``LN:i:<sequence length>`` and ``KC:i:<count>`` right behind its sequence in
     place of any ``dp / DP / kc / KC / ln / LN`` tag it had; its other tags stay, in their order; every other line, and every
@@ -178,12 +282,14 @@ def refuse_ranks(world: int) -> None:
 
 
 def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
-               count_singles: bool = False, quiet: bool = False, profile: bool = False):
+               count_singles: bool = False, quiet: bool = False, profile: bool = False, pileup=None):
     """Index the segments of ``gfa`` and count every end the chosen input delivers (the input dispatch of
     ``pe_inference.count_links``, one process only).  -> (segment ids in file order, KC int64 in file order, ends counted).
     Replaces the context's index; the context stops keeping masks when the pass is over, so a PE count may follow on it.
     ``quiet``: the dispatch's progress lines are not printed.  ``profile``: the pass counts per window (``pe.CoverCounter``,
-    still one kernel per block; KC is its row sums) and a fourth value follows: (segment lengths, offsets, cov)."""
+    still one kernel per block; KC is its row sums) and a fourth value follows: (segment lengths, offsets, cov).  ``pileup``:
+    a mismatch budget; a ``pe.PileupCounter`` then takes every block as well and one more value follows at the end:
+    (segment sequences, offsets, depth, alt, (alignments, rejected)).  Without it no such counter is built."""
     from . import pe as host
     from . import pe_inference
 
@@ -193,16 +299,18 @@ def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: b
     ids, seqs = host.read_gfa_segments(gfa)
     ctx.build_index(seqs, kmer_size)
     counter = host.CoverCounter(ctx) if profile else host.DepthCounter(ctx)  # (the blocks built from here on keep their masks)
+    piles = host.PileupCounter(ctx, max_mismatch=pileup) if pileup is not None else None
     try:
         with contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext():
-            pe_inference.feed_counter(ctx, counter, inp, 0, 1, stages_follow=False, tally_singles=False)
+            pe_inference.feed_counter(ctx, counter if piles is None else _Both(counter, piles), inp, 0, 1, stages_follow=False, tally_singles=False)
         ctx.sync()
     finally:
         ctx.keep_masks(False)
+    piled = () if piles is None else ((seqs,) + piles.result() + (piles.tallies(),),)
     if profile:
         offsets, cov = counter.result()
-        return ids, counter.kc(), counter.ends_seen, ([len(q) for q in seqs], offsets, cov)
-    return ids, counter.result(), counter.ends_seen
+        return (ids, counter.kc(), counter.ends_seen, ([len(q) for q in seqs], offsets, cov)) + piled
+    return (ids, counter.result(), counter.ends_seen) + piled
 
 
 def build_parser():
@@ -229,6 +337,15 @@ def build_parser():
     p.add_argument("--depth-stat", dest="depth_stat", choices=("sum", "median"), default=None,
                    help="what KC:i holds: sum (default) the (k+1)-mer occurrences, as SPAdes; median: the lower median of the windows' "
                         "counts times LN, so that kc / ln is that median")
+    p.add_argument("--pileup", dest="pileup", type=str, default=None, metavar="FILE",
+                   help="also write the base pileup as a TSV (segment, pos, ref, A, C, G, T, other; pos 1-based; one row per position of every "
+                        "segment of k + 1 bases or more, zeros included; base coverage, substitutions only; .gz: through gzip)")
+    p.add_argument("--variants", dest="variants", type=str, default=None, metavar="FILE",
+                   help="also write the minor bases of the pileup as VCF 4.2 (INFO DP, AD, AF; .gz: through gzip)")
+    p.add_argument("--pileup-max-mismatch", dest="pileup_max_mismatch", type=int, default=None, metavar="M",
+                   help="non-agreeing positions an alignment may hold in its overlap [default: 8]")
+    p.add_argument("--min-alt-count", dest="min_alt_count", type=int, default=None, metavar="C", help="--variants: records need AD >= C [default: 2]")
+    p.add_argument("--min-alt-frac", dest="min_alt_frac", type=float, default=None, metavar="F", help="--variants: records need AD >= F * DP [default: 0.01]")
     return p
 
 
@@ -250,6 +367,10 @@ def main(argv=None) -> int:
     if args.gzip_device:
         os.environ["VS_GZIP_DEVICE"] = "1"
     refuse_ranks(int(os.environ.get("WORLD_SIZE", "1")))  # (before a device is opened)
+    why = pileup_refusal(args)
+    if why is not None:
+        print("node_depth: %s" % why, file=sys.stderr)
+        return 1
     world = 1
     pe_inference.interleaved_input(args.fwd, args.rve, world, interleaved)
     pe_inference.check_names_input(args.fwd, args.rve, world, check_names, bam_by_name=args.bam_by_name, interleaved=interleaved)
@@ -259,8 +380,10 @@ def main(argv=None) -> int:
 
     ctx = host.Context(args.device)
     profiled = args.profile is not None or args.profile_summary is not None or args.depth_stat is not None
+    piled = args.pileup is not None or args.variants is not None
     got = depth_pass(ctx, args.gfa, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=interleaved,
-                     check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True, profile=profiled)
+                     check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True, profile=profiled,
+                     pileup=(8 if args.pileup_max_mismatch is None else args.pileup_max_mismatch) if piled else None)
     ids, kc, ends = got[:3]
     tags = kc.tolist()
     if profiled:
@@ -271,10 +394,18 @@ def main(argv=None) -> int:
             write_bedgraph(args.profile, ids, offsets, cov)
         if args.profile_summary is not None:
             write_summary(args.profile_summary, ids, lengths, offsets, cov)
+    if piled:
+        seqs, p_offsets, p_depth, p_alt, _ = got[-1]
+        if args.pileup is not None:
+            write_pileup(args.pileup, ids, seqs, p_offsets, p_depth, p_alt)
+        if args.variants is not None:
+            write_vcf(args.variants, ids, seqs, p_offsets, p_depth, p_alt, 2 if args.min_alt_count is None else args.min_alt_count,
+                      0.01 if args.min_alt_frac is None else args.min_alt_frac)
     text = rewrite_gfa(raw, tags)
     with open(args.out, "wb") as fh:
         fh.write(text)
-    stored = args.out + "".join("; %s in: %s" % (what, path) for what, path in (("profile", args.profile), ("summary", args.profile_summary))
+    stored = args.out + "".join("; %s in: %s" % (what, path) for what, path in (("profile", args.profile), ("summary", args.profile_summary),
+                                                                                  ("pileup", args.pileup), ("variants", args.variants))
                                 if path is not None)
     print("node_depth: k = %d, %d read ends counted, %d window-entry coincidences (sum of KC), %d of %d segments with KC = 0; result stored in: %s"
           % (k, ends, int(kc.sum()), int((kc == 0).sum()), len(ids), stored))

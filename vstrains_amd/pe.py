@@ -1497,6 +1497,22 @@ class Context:
         """The differences scanned into counts, added to the uint64 totals at ``cov_ptr`` and zeroed (``vs_cover_fold``)."""
         nat.check(self._h, nat.lib().vs_cover_fold(self._h, C.c_void_p(diff_ptr), C.c_void_p(cov_ptr), n_slots))
 
+    def pileup_layout(self, first_ptr: int) -> int:
+        """The slots of the base pileup (``vs_pileup_layout``): ``first_ptr`` is a device pointer to ``n_nodes + 1`` uint32,
+        written with the first slot of every segment in the index's INTERNAL numbering and the slot total behind them -- a
+        segment of ``k + 1`` bases or more owns one slot per position and one sentinel.  -> the slot total."""
+        n = C.c_uint64(0)
+        nat.check(self._h, nat.lib().vs_pileup_layout(self._h, C.c_void_p(first_ptr), C.byref(n)))
+        return int(n.value)
+
+    def node_pileup(self, reads: ReadBlock, first_ptr: int, diff_ptr: int, alt_ptr: int, max_mismatch: int, tally_ptr: int):
+        """One block through the pileup pass (``vs_node_pileup``): +1 / -1 per credited alignment on the uint32 difference
+        array at ``diff_ptr`` (one word per slot of ``pileup_layout``), one count per non-agreeing base on the uint64
+        ``[slots, 5]`` array at ``alt_ptr``, and (alignments, rejected) added to the two uint64 at ``tally_ptr``.  Blocks
+        must have been built after ``keep_masks(True)``."""
+        nat.check(self._h, nat.lib().vs_node_pileup(self._h, reads._h, C.c_void_p(first_ptr), C.c_void_p(diff_ptr), C.c_void_p(alt_ptr),
+                                                    max_mismatch, C.c_void_p(tally_ptr)))
+
     def contig_mems(self, reads: ReadBlock) -> np.ndarray:
         """Every maximal exact match of k + 1 bases or more between a contig of the block and a strand of a segment
         (``vs_contig_mems``): uint32 [n, 5] -- contig, first base in the contig, segment | strand << 31, first base in that
@@ -2042,6 +2058,102 @@ class CoverCounter:
         run = np.zeros(cov.size + 1, dtype=np.int64)
         np.cumsum(cov, out=run[1:])
         return run[offsets[1:]] - run[offsets[:-1]]
+
+
+def pileup_plan(n_nodes: int, ksize: int, n_ends: int, max_len: int, n_cu: int = 256, pending: int = 0, bound: int = 2 ** 32) -> dict:
+    """The launch ``vs_node_pileup`` makes for a block and whether a fold is due before it (``vs_pileup_plan``, a pure host
+    function: no device is needed), with ``cover_plan``'s arguments and fields; the weight is ``n_ends * 2 * max_len``."""
+    a = (C.c_uint64 * 8)()
+    rc = nat.lib().vs_pileup_plan(n_nodes, ksize, n_ends, max_len, n_cu, pending, bound, a)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_pileup_plan refuses %d nodes / %d ends of up to %d bases (pending %d, bound %d)" % (n_nodes, n_ends, max_len, pending, bound))
+    return dict(launch=bool(a[0]), grid=int(a[1]), ends_per_wg=int(a[2]), weight=int(a[3]), fold_first=bool(a[4]), pending=int(a[5]),
+                lds_bytes=int(a[6]), threads=int(a[7]))
+
+
+class PileupCounter:
+    """The base pileup of every segment, counted from the reads on one device (``vs_node_pileup``): every read end is laid
+    along the diagonal of each exact anchor of ``k + 1`` bases across its mismatches; an alignment with at most
+    ``max_mismatch`` non-agreeing positions in its overlap adds 1 to the depth of every position it covers and 1 to
+    ``alt[position][base]`` where it differs (``tests/pileup_model.py``) -- BASE coverage, substitutions only.  Takes
+    ``CoverCounter``'s place in the input dispatch of ``pe_inference`` (``add``, ``device``, ``single_stats``, ``ends_seen``;
+    the context keeps the masks): one kernel per block.  Holds 4 + 8 + 40 bytes per slot (a slot per position and one per
+    segment); the context holds 4 more per slot once a fold ran.  ``fold_bound``: ``pileup_plan``'s ``bound``."""
+
+    def __init__(self, ctx: Context, max_mismatch: int = 8, fold_bound: int = 2 ** 32, device: Optional[str] = None):
+        import torch
+
+        if not 0 <= int(max_mismatch) < 2 ** 32:
+            raise ValueError("a mismatch budget of %r: an integer from 0 up is needed" % (max_mismatch,))
+        self.torch = torch
+        self.ctx = ctx
+        self.device = torch.device(device or ("cuda:%d" % ctx.device))
+        self.n = ctx.n_nodes
+        self.ksize = ctx.ksize
+        self.max_mismatch = int(max_mismatch)
+        self.fold_bound = fold_bound
+        self.single_stats = torch.zeros(3, dtype=torch.int64, device=self.device)  # (what the dispatch tallies of a PeCounter: stays zero)
+        self.ends_seen = 0  # ends the blocks delivered (the absent second ends of singles blocks aside)
+        self.folds = 0
+        self.pending = 0    # pileup_plan's weight of the blocks since the last fold
+        self.node_rank = getattr(ctx, "node_rank", None)  # (kept here: a later build_index cannot change how the slots are read)
+        with torch.cuda.device(self.device):
+            ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.first = torch.zeros(self.n + 1, dtype=torch.int32, device=self.device)  # (uint32 words)
+            self.slots = ctx.pileup_layout(self.first.data_ptr())
+            self.diff = torch.zeros(max(self.slots, 1), dtype=torch.int32, device=self.device)  # (uint32 words, wrap-around adds)
+            self.depth = torch.zeros(max(self.slots, 1), dtype=torch.int64, device=self.device)
+            self.alt = torch.zeros((max(self.slots, 1), 5), dtype=torch.int64, device=self.device)
+            self.tally = torch.zeros(2, dtype=torch.int64, device=self.device)
+        ctx.keep_masks(True)
+
+    def fold(self):
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.ctx.cover_fold(self.diff.data_ptr(), self.depth.data_ptr(), self.slots)
+        self.pending = 0
+        self.folds += 1
+
+    def add(self, reads: ReadBlock):
+        torch = self.torch
+        info = reads.info
+        n_ends = info["ends"]
+        self.ends_seen += n_ends // 2 if reads.unpaired else n_ends
+        plan = pileup_plan(self.n, self.ksize, n_ends, info["max_len"], pending=self.pending, bound=self.fold_bound)
+        if plan["fold_first"]:
+            self.fold()
+        self.pending = plan["pending"]
+        if not self.slots:
+            return
+        with torch.cuda.device(self.device):
+            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.ctx.node_pileup(reads, self.first.data_ptr(), self.diff.data_ptr(), self.alt.data_ptr(), self.max_mismatch, self.tally.data_ptr())
+
+    def result(self):
+        """-> (offsets int64 [N + 1], depth int64 [P], alt int64 [P, 5]): the positions of segment ``n`` of the node list
+        ``Context.build_index`` was given (the GFA's order) are rows ``offsets[n] : offsets[n + 1]``, without sentinel slots;
+        a segment shorter than ``k + 1`` bases is an empty range.  ``alt[:, 0..3]``: reads carrying A, C, G, T where the
+        segment has another base; ``alt[:, 4]``: a byte outside ACGT."""
+        if self.pending:
+            self.fold()
+        first = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
+        depth = self.depth[: self.slots].cpu().numpy()
+        alt = self.alt[: self.slots].cpu().numpy()
+        positions = np.maximum(first[1:] - first[:-1] - 1, 0)
+        start = first[:-1]
+        if self.node_rank is not None:
+            positions, start = positions[self.node_rank], start[self.node_rank]
+        offsets = np.zeros(self.n + 1, dtype=np.int64)
+        np.cumsum(positions, out=offsets[1:])
+        total = int(offsets[-1])
+        at = np.repeat(start - offsets[:-1], positions) + np.arange(total, dtype=np.int64)
+        return offsets, depth[at].astype(np.int64), alt[at].astype(np.int64).reshape(total, 5)
+
+    def tallies(self):
+        """-> (alignments credited, alignments rejected for more than ``max_mismatch`` non-agreeing positions)."""
+        t = self.tally.cpu().numpy()
+        return int(t[0]), int(t[1])
 
 
 # ---- outputs -------------------------------------------------------------------------------------
