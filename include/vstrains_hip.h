@@ -926,6 +926,46 @@ int vs_pileup_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t m
 int vs_pileup_scan_host(const uint32_t *read_words, const uint32_t *read_mask, const uint32_t *strand_words, uint32_t rlen, uint32_t tlen, uint32_t a,
                         uint32_t qa, uint32_t K, uint32_t out[4]);
 
+/* ---- which variant sites travel together on one read pair (additions to ABI 11 without a new number: nothing that exists
+ * changes) --  No counterpart in the reference.  A SITE is a position p of a segment n with len_n >= K = k + 1, given as its
+ * pileup slot first[n] + p (vs_pileup_layout); the site list is an ascending array of distinct slots.  A FRAGMENT is the two
+ * ends 2p and 2p + 1 of a block (in a singles block the one present end).  Every alignment the pileup credits (anchored, once
+ * per diagonal, at most max_mismatch non-agreeing positions in its overlap, both strands) makes one RAW observation (site, c)
+ * for every site under its overlap, c the read's byte there as it reads on the forward strand (0..3 = ACGT, complemented on
+ * the reverse-complement strand, 4 = a byte outside ACGT): the column rule of alt, taken at agreeing positions too.  A
+ * fragment with more than 32 raw observations over both ends is OVERFLOW and deposits nothing.  Otherwise it OBSERVES (s, c)
+ * once if every raw observation it holds of site s carries the same c; else s is DISCORDANT for it and left out.  Every pair
+ * s < t of observed sites on one segment with pos_t - pos_s <= span adds 1 to the cell of (s, t) at [c_s][c_t]; a pair on two
+ * segments or further apart is UNSTORED.  tests/site_pairs_model.py states it; csrc/vs_site_pairs_plan.h has the launch and
+ * the rows, csrc/vs_site_pairs_core.h what a lane does.
+ *   vs_site_pairs_rows_host : host only, no device, a pure function.  (seg[i], pos[i]), i < n_sites: the sites, strictly
+ *                             ascending by segment (the index's own numbering), then position.  row_first: n_sites + 1
+ *                             words, written: the cells before every site's and all of them behind; site i's partners are
+ *                             the later sites of its segment within span, contiguous behind it, so the cell of (s, t) is
+ *                             row_first[s] + (t - s - 1).  *n_cells = the total.  VS_E_ARG: not ascending; VS_E_RANGE: 2^29
+ *                             sites or more (an entry is site << 3 | c) or 2^32 cells or more: lower the span.
+ *   vs_site_pairs_plan      : host only, a pure function: plan[0] = 1 if k_node_site_pairs is launched (0: no end holds K
+ *                             bases); [1] = workgroups; [2] = ends per workgroup, a multiple of 64, so that no workgroup
+ *                             and no batch of 64 ends cuts a pair; [3..5] = 0; [6] = LDS bytes per workgroup; [7] = threads
+ *                             per workgroup.  VS_E_ARG: an odd n_ends; VS_E_RANGE: more than 2^25 - 2 nodes, 2^32 ends.
+ *   vs_site_pairs_frag_host : host only, no device: the reduction the kernel runs on one fragment's list
+ *                             (csrc/vs_site_pairs_core.h) on HOST buffers.  raw: n <= 32 entries site << 3 | c in any order;
+ *                             kept: room for 32, written with the observations, ascending; out[0] = how many, out[1] = the
+ *                             discordant sites.  VS_E_ARG: n > 32.
+ *   vs_node_site_pairs      : one block through k_node_site_pairs on the context's current index.  d_first: what
+ *                             vs_pileup_layout wrote for THIS index; d_site_slot: DEVICE, n_sites uint32 ascending;
+ *                             d_row_first: DEVICE, n_sites + 1 uint32 as vs_site_pairs_rows_host made them; d_cells: DEVICE,
+ *                             row_first[n_sites] x 25 uint64, zero before the first block, added to with one atomic per
+ *                             stored pair; d_tally: DEVICE, 5 uint64, added to: fragments with a raw observation, overflow
+ *                             fragments, discordant (fragment, site) incidences, pairs stored, pairs unstored.  Enqueued on
+ *                             the ctx stream; with n_sites == 0 nothing is launched.  Blocks must have been built after
+ *                             vs_ctx_keep_masks(ctx, 1).  VS_E_ARG: an odd number of ends; VS_E_RANGE: 2^29 sites. */
+int vs_site_pairs_rows_host(const uint32_t *seg, const uint32_t *pos, uint64_t n_sites, uint32_t span, uint32_t *row_first, uint64_t *n_cells);
+int vs_site_pairs_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t plan[8]);
+int vs_site_pairs_frag_host(const uint32_t *raw, uint32_t n, uint32_t *kept, uint32_t out[2]);
+int vs_node_site_pairs(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, const uint32_t *d_site_slot, uint32_t n_sites,
+                       const uint32_t *d_row_first, uint64_t *d_cells, uint32_t max_mismatch, uint64_t *d_tally);
+
 /* Testing aid (ABI 11): the two exclusive scans under the index build, the locus sort, every row_ptr and every member,
  * record and word offset, run alone on values the caller made up, launched exactly as their callers launch them (no kernel
  * of its own).  HOST pointers: in[n + guard] = the n values and behind them `guard` words of a sentinel the caller chose;

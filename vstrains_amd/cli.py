@@ -111,6 +111,9 @@ def build_parser():
     # with --depth-from-reads: the same read pass also lays every end along its anchors' diagonals across mismatches and writes the
     # base pileup as gfa/graph_depth.pileup.tsv and its minor bases as gfa/graph_depth.vcf (vstrains_amd.node_depth --pileup --variants)
     p.add_argument("--depth-pileup", dest="depth_pileup", action="store_true", default=False, help=argparse.SUPPRESS)
+    # with --depth-from-reads --depth-pileup: the reads are then read once more and what one read pair carries at the positions of the
+    # records of gfa/graph_depth.vcf is written as gfa/graph_depth.site_pairs.tsv (vstrains_amd.node_depth --variants --site-pairs)
+    p.add_argument("--depth-site-pairs", dest="depth_site_pairs", action="store_true", default=False, help=argparse.SUPPRESS)
     return p
 
 
@@ -152,6 +155,19 @@ def depth_pileup_refusal(args):
     """None, or why ``--depth-pileup`` cannot hold, said before anything is written: it rides on the depth pass."""
     if args.depth_pileup and not args.depth_from_reads:
         return "--depth-pileup writes the base pileup of the depth pass: give --depth-from-reads with it"
+    return None
+
+
+def depth_site_pairs_refusal(args):
+    """None, or why ``--depth-site-pairs`` cannot hold, said before anything is written: its sites are the pileup's records, and
+    the reads are read once more for it."""
+    if not args.depth_site_pairs:
+        return None
+    if not (args.depth_from_reads and args.depth_pileup):
+        return "--depth-site-pairs links the minor bases of the pileup: give --depth-from-reads --depth-pileup with it"
+    for path in [args.fwd, args.rve] + list(args.single or ()):
+        if not os.path.isfile(path):
+            return "--depth-site-pairs reads the reads once more, and %s is not a regular file: write the reads to a file" % path
     return None
 
 
@@ -203,6 +219,14 @@ def depth_from_reads(args, logger, ctx):
         node_depth.write_vcf(args.output_dir + "/gfa/graph_depth.vcf", ids, seqs, p_offsets, p_depth, p_alt)
         logger.info("base pileup of every position: {0}/gfa/graph_depth.pileup.tsv, minor bases: {0}/gfa/graph_depth.vcf ({1} alignments, {2} rejected)"
                     .format(args.output_dir, credited, rejected))
+    if args.depth_site_pairs:
+        records = node_depth.variant_records(ids, seqs, p_offsets, p_depth, p_alt)
+        linked = node_depth.site_pairs_pass(ctx, node_depth.record_sites(ids, records), args.fwd, args.rve, bam_by_name=args.bam_by_name,
+                                            interleaved=args.interleaved, check_names=args.check_names, single=args.single,
+                                            count_singles=args.count_singles, quiet=True)
+        node_depth.write_site_pairs(args.output_dir + "/gfa/graph_depth.site_pairs.tsv", ids, *linked[:4])
+        logger.info("bases that travel together on one read pair: {0}/gfa/graph_depth.site_pairs.tsv ({1})".format(
+            args.output_dir, ", ".join("%d %s" % (v, what) for v, what in zip(linked[4], node_depth.SITE_PAIR_TALLIES))))
     logger.info("segment depth counted from the reads: k = {0}, {1} read ends, KC sum {2}; the graph goes on as {3}".format(k, ends, int(kc.sum()), out))
     empty = [ids[i] for i in range(len(ids)) if kc[i] == 0]
     if empty:
@@ -255,7 +279,7 @@ def main(argv=None, backend=None):
     args.single = pe_inference.unpaired_input(args.single, args.count_singles, pe_inference._rank_world()[1], args.interleaved,
                                               pe_text_from=args.pe_text_from, check_names=args.check_names, bam_by_name=args.bam_by_name,
                                               fwd=args.fwd, rve=args.rve)
-    why = depth_profile_refusal(args) or depth_pileup_refusal(args)
+    why = depth_profile_refusal(args) or depth_pileup_refusal(args) or depth_site_pairs_refusal(args)
     if why is not None:
         raise ValueError(why)
     if args.depth_from_reads:

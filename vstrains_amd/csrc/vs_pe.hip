@@ -3883,3 +3883,230 @@ extern "C" int vs_node_pileup(vs_ctx *ctx, const vs_reads *reads, const uint32_t
     VS_HIP(ctx, hipGetLastError());
     return VS_OK;
 }
+
+// ---- which variant sites travel together on one read pair (vs_node_site_pairs) ----------------------------------------------
+// The first pass of this family that uses the pairing of the reads: what ONE fragment -- the ends 2p and 2p + 1 -- saw at a
+// given list of sites is kept together, and every pair of sites it saw adds 1 to a 5 x 5 cell (the definition, the launch and
+// the rows of the cell table: vs_site_pairs_plan.h, tests/site_pairs_model.py; the range search, the reduction and the cell:
+// vs_site_pairs_core.h).  The end batches, the probe grid, the table probe, the posting deal and vs_extend under the mask are
+// k_node_pileup's.  The lane that holds a match looks up the sites under its overlap FIRST -- two binary searches on the
+// ascending slot list -- and is done if there are none: no owner walk and no count, so with few sites most alignments cost
+// nothing beyond the match.  Otherwise vs_pileup_owner and vs_pileup_count decide as they do for the pileup, and a credited
+// alignment claims room for its sites in its fragment's list in LDS with ONE atomic on the list's counter (a batch of 64 ends
+// is 32 whole fragments: the plan keeps every workgroup's share and every batch at an even end) and stores the entries that
+// still fit among the first 32; the counter runs on, so a fragment with more than 32 raw observations is known as overflow.
+// After the batch's last probe round lane f reduces list f in place (sorted; a site seen with two different columns is
+// discordant and dropped), then the wavefront goes through the fragments that kept two sites or more and deals the pairs of
+// each to its lanes: one 64-bit atomic per stored pair.  The five tallies are summed per batch from ballots and added once.
+#include "vs_site_pairs_core.h"
+#include "vs_site_pairs_plan.h"
+
+struct SitePairsParams {
+    VsIndexDev idx;
+    VsReadsDev rd;
+    const uint32_t *first;       // [n_nodes + 1] the first slot of every segment (vs_pileup_layout)
+    const uint32_t *site_slot;   // [n_sites] the sites' slots, ascending
+    const uint32_t *row_first;   // [n_sites + 1] the cells before every site's (vs_site_pairs_rows_host)
+    unsigned long long *cells;   // [row_first[n_sites]][25] ADDED to
+    unsigned long long *tally;   // [SITE_PAIRS_TALLIES] ADDED to
+    uint64_t ends_per_wg;        // a multiple of 64
+    uint32_t n_sites;
+    uint32_t max_mismatch;
+};
+
+__global__ void __launch_bounds__(SITE_PAIRS_TPB, 6)  // (six wavefronts a SIMD: three workgroups a CU, as the plan deals them)
+k_node_site_pairs(SitePairsParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_mem[SITE_PAIRS_LDS_WORDS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t N = P.idx.n_nodes, w = P.idx.w, s = P.idx.s, K = P.idx.K;
+    uint32_t *s_head = s_mem;
+    uint32_t *sw = s_mem + PILEUP_HEAD_WORDS + wave * SITE_PAIRS_WAVE_WORDS;
+    uint32_t *s_np = sw, *s_cnt = sw + 65u, *s_pa = sw + 130u, *s_pb = sw + 194u, *s_pj = sw + 258u;
+    uint32_t *s_list = sw + PILEUP_WAVE_WORDS;  // list f: its counter at s_list[f * 33], its entries behind it
+    const uint64_t e_lo = (uint64_t)blockIdx.x * P.ends_per_wg;
+    const uint64_t e_hi = e_lo + P.ends_per_wg < P.rd.n_ends ? e_lo + P.ends_per_wg : P.rd.n_ends;
+    if (tid == 0u) s_head[0] = 0u;
+    __syncthreads();
+    for (;;) {
+        uint32_t b = 0u;
+        if (lane == 0u) b = atomicAdd(&s_head[0], 64u);
+        b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+        if (e_lo + b >= e_hi) break;
+        const uint64_t e0 = e_lo + b;  // (even: e_lo and b are multiples of 64)
+        const uint32_t n_here = e_hi - e0 < 64u ? (uint32_t)(e_hi - e0) : 64u;
+        uint32_t np = 0u;
+        if (lane < n_here) {
+            const uint32_t meta = P.rd.meta[e0 + lane];
+            if (!((meta >> 24) & VS_FLAG_ABSENT)) np = vs_seed_probes(meta & VS_LEN_MASK, w, s);  // (0 for an end shorter than K)
+        }
+        s_np[lane + 1u] = vs_wave_scan_add(np);
+        if (lane == 0u) s_np[0] = 0u;
+        if (lane < SITE_PAIRS_FRAGS) s_list[lane * SITE_PAIRS_LIST_WORDS] = 0u;
+        vs_wave_sync();
+        const uint32_t tp = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_np[64]);
+        for (uint32_t p0 = 0u; p0 < tp; p0 += 64u) {
+            // probes p0 .. p0 + 63 of the batch: one per lane
+            const uint32_t t = p0 + lane;
+            uint32_t c = 0u, pa = 0u, pb = 0u, pj = 0u;
+            if (t < tp) {
+                const uint32_t el = vs_upper_idx(s_np, 65u, t);  // the end that owns probe t: s_np[el] <= t < s_np[el + 1]
+                const uint64_t e = e0 + el;
+                const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                const uint32_t j = vs_seed_phase(rlen, w, s) + (t - s_np[el]) * s;
+                const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                if (!(mk && vs_seed_dirty(mk, rbase + j, w))) {
+                    uint32_t sr;
+                    const uint64_t key = vs_seed_key(P.rd.words, rbase + j, w, &sr);
+                    c = vs_probe(P.idx, key, sr, &pa, &pb);
+                }
+                pj = (el << 24) | j;  // (a read offset fits 24 bits: VS_LEN_MASK)
+            }
+            s_pa[lane] = pa;
+            s_pb[lane] = pb;
+            s_pj[lane] = pj;
+            s_cnt[lane + 1u] = vs_wave_scan_add(c);
+            if (lane == 0u) s_cnt[0] = 0u;
+            vs_wave_sync();
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[64]);
+            for (uint32_t q0 = 0u; q0 < total; q0 += 64u) {
+                // postings q0 .. q0 + 63 of these probes: one per lane
+                const uint32_t t2 = q0 + lane;
+                if (t2 >= total) continue;
+                const uint32_t pr = vs_upper_idx(s_cnt, 65u, t2);
+                const uint32_t k2 = t2 - s_cnt[pr];
+                const uint32_t qa0 = s_pa[pr], qb0 = s_pb[pr], ej = s_pj[pr];
+                const uint32_t j = ej & VS_LEN_MASK, el = ej >> 24;
+                const uint64_t e = e0 + el;
+                const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                uint32_t nd, pos, opp;
+                VsNodeMeta nm;
+                if (s_cnt[pr + 1u] - s_cnt[pr] == 1u) {
+                    nd = qa0; pos = qb0 & 0x7FFFFFFFu; opp = qb0 >> 31;
+                    nm = P.idx.meta[nd];
+                } else {
+                    const VsPosting po = vs_posting_unpack(P.idx.postings[qa0 + k2]);
+                    nd = po.node; pos = po.pos; opp = po.strand ^ (qb0 >> 31);
+                    nm.woff = po.woff; nm.len = po.len;
+                }
+                const uint32_t *tw = opp ? P.idx.rc_words : P.idx.fwd_words;
+                const uint32_t q = opp ? nm.len - pos - w : pos;
+                uint32_t a, qa, len;
+                if (!(nd < N && vs_extend(P.rd.words, rbase, rlen, tw, nm.woff * 16u, nm.len, j, q, VS_SEED_VERIFIED(w), s, K, mk, rbase, &a, &qa, &len) &&
+                      qa + len <= nm.len))
+                    continue;
+                const VsPileupSpan sp = vs_pileup_span(rlen, nm.len, a, qa);
+                // the overlap on the strand: [t_lo, t_hi); on the forward text: slots lo .. lo + n - 1 (mirrored on the other strand)
+                const uint32_t t_lo = (uint32_t)((int64_t)sp.x_lo + sp.d), t_hi = (uint32_t)((int64_t)sp.x_hi + sp.d);
+                const uint32_t base = P.first[nd];
+                const uint32_t lo = base + (opp ? nm.len - t_hi : t_lo);
+                uint32_t i0, i1;
+                vs_site_pairs_range(P.site_slot, P.n_sites, lo, lo + (sp.x_hi - sp.x_lo) - 1u, &i0, &i1);
+                if (i0 == i1) continue;  // no site under this alignment
+                const uint64_t tbase = (uint64_t)nm.woff * 16u;
+                if (!vs_pileup_owner(P.rd.words, rbase, tw, tbase, mk, sp, a, K)) continue;
+                if (vs_pileup_count(P.rd.words, rbase, tw, tbase, mk, sp) > P.max_mismatch) continue;  // rejected: observes nothing
+                uint32_t *list = s_list + (el >> 1) * SITE_PAIRS_LIST_WORDS;
+                const uint32_t at = atomicAdd(&list[0], i1 - i0);  // (a fragment's alignments are few and short: no wrap)
+                for (uint32_t i = i0, z = at; i < i1 && z < SITE_PAIRS_CAP; i++, z++) {
+                    const uint32_t p = P.site_slot[i] - base;          // forward position
+                    const uint32_t ts = opp ? nm.len - 1u - p : p;    // strand offset
+                    const uint32_t x = (uint32_t)((int64_t)ts - sp.d);  // read offset, inside [x_lo, x_hi)
+                    list[1u + z] = (i << 3) | vs_site_pairs_col(P.rd.words, rbase, mk, x, opp);
+                }
+            }
+            vs_wave_sync();  // s_cnt / s_pa / s_pb / s_pj are rewritten by the next 64 probes
+        }
+        vs_wave_sync();  // the lists are complete; s_np is rewritten by the next batch
+        // lane f reduces list f
+        uint32_t raw = 0u, kept = 0u, bad = 0u;
+        if (lane < SITE_PAIRS_FRAGS) {
+            raw = s_list[lane * SITE_PAIRS_LIST_WORDS];
+            if (raw && raw <= SITE_PAIRS_CAP) kept = vs_site_pairs_reduce(s_list + lane * SITE_PAIRS_LIST_WORDS + 1u, raw, &bad);
+            s_list[lane * SITE_PAIRS_LIST_WORDS] = kept;
+        }
+        const uint32_t n_seen = (uint32_t)__popcll(__ballot(raw > 0u)), n_over = (uint32_t)__popcll(__ballot(raw > SITE_PAIRS_CAP));
+        uint32_t n_bad = 0u;
+        for (unsigned long long m = __ballot(bad > 0u); m; m &= m - 1ull)  // (discordance is rare: a turn per fragment that has any)
+            n_bad += (uint32_t)__builtin_amdgcn_readlane((int)bad, (int)__ffsll((long long)m) - 1);
+        vs_wave_sync();
+        uint32_t n_stored = 0u, n_unstored = 0u;
+        for (unsigned long long m = __ballot(kept > 1u); m; m &= m - 1ull) {
+            // fragment f's pairs (ia, ib), ia < ib: lane l takes ia = l & 31 and ib = ia + 1 + (l >> 5), + 2 a turn
+            const uint32_t f = (uint32_t)__ffsll((long long)m) - 1u;
+            const uint32_t *list = s_list + f * SITE_PAIRS_LIST_WORDS;
+            const uint32_t n = list[0], ia = lane & 31u;
+            const uint32_t ea = ia < n ? list[1u + ia] : 0u;
+            for (uint32_t step = 1u; step < n; step += 2u) {
+                const uint32_t ib = ia + step + (lane >> 5);
+                bool stored = false, unstored = false;
+                if (ib < n) {  // (then ia < n too)
+                    const uint32_t eb = list[1u + ib];
+                    uint32_t cell;
+                    stored = vs_site_pairs_cell(P.row_first, ea >> 3, eb >> 3, &cell) != 0u;
+                    unstored = !stored;
+                    if (stored) atomicAdd(&P.cells[(uint64_t)cell * SITE_PAIRS_CELL + (ea & 7u) * SITE_PAIRS_COLS + (eb & 7u)], 1ull);
+                }
+                n_stored += (uint32_t)__popcll(__ballot(stored));
+                n_unstored += (uint32_t)__popcll(__ballot(unstored));
+            }
+        }
+        if (lane == 0u) {
+            if (n_seen) atomicAdd(P.tally, (unsigned long long)n_seen);
+            if (n_over) atomicAdd(P.tally + 1, (unsigned long long)n_over);
+            if (n_bad) atomicAdd(P.tally + 2, (unsigned long long)n_bad);
+            if (n_stored) atomicAdd(P.tally + 3, (unsigned long long)n_stored);
+            if (n_unstored) atomicAdd(P.tally + 4, (unsigned long long)n_unstored);
+        }
+        vs_wave_sync();  // the lists are zeroed by the next batch
+    }
+}
+
+extern "C" int vs_site_pairs_plan(uint32_t n_nodes, uint32_t ksize, uint64_t n_ends, uint32_t max_len, uint32_t n_cu, uint64_t plan[8]) {
+    if (!plan) return VS_E_ARG;
+    const SitePairsPlan p = vs_site_pairs_plan_for(n_nodes, ksize + 1u, n_ends, max_len, n_cu);
+    plan[0] = p.launch; plan[1] = p.grid; plan[2] = p.ends_per_wg; plan[3] = 0; plan[4] = 0; plan[5] = 0;
+    plan[6] = sizeof(uint32_t) * SITE_PAIRS_LDS_WORDS; plan[7] = SITE_PAIRS_TPB;
+    return p.status;
+}
+
+extern "C" int vs_site_pairs_rows_host(const uint32_t *seg, const uint32_t *pos, uint64_t n_sites, uint32_t span, uint32_t *row_first, uint64_t *n_cells) {
+    if (!row_first || !n_cells || (n_sites && (!seg || !pos))) return VS_E_ARG;
+    return vs_site_pairs_rows_for(seg, pos, n_sites, span, row_first, n_cells);
+}
+
+extern "C" int vs_site_pairs_frag_host(const uint32_t *raw, uint32_t n, uint32_t *kept, uint32_t out[2]) {
+    if (!kept || !out || n > SITE_PAIRS_CAP || (n && !raw)) return VS_E_ARG;
+    for (uint32_t i = 0; i < n; i++) kept[i] = raw[i];
+    out[0] = vs_site_pairs_reduce(kept, n, &out[1]);
+    return VS_OK;
+}
+
+extern "C" int vs_node_site_pairs(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, const uint32_t *d_site_slot, uint32_t n_sites,
+                                  const uint32_t *d_row_first, uint64_t *d_cells, uint32_t max_mismatch, uint64_t *d_tally) {
+    if (!ctx || !reads || !d_tally) return VS_E_ARG;
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_node_site_pairs: build an index first (vs_index_build)");
+    if (n_sites >= SITE_PAIRS_MAX_SITES) return vs_fail(ctx, VS_E_RANGE, "vs_node_site_pairs: %u sites, and a site number has 29 bits", n_sites);
+    const VsIndexDev &idx = ctx->idx;
+    const SitePairsPlan pl = vs_site_pairs_plan_for(idx.n_nodes, idx.K, reads->n_ends, (uint32_t)reads->max_len, (uint32_t)ctx->n_cu);
+    if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "vs_node_site_pairs: %s", pl.msg);
+    if (!pl.launch || !n_sites) return VS_OK;  // no end of the block holds an anchor, or there is nothing to observe
+    if (!d_first || !d_site_slot || !d_row_first || !d_cells) return VS_E_ARG;
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    SitePairsParams P;
+    P.idx = idx;
+    P.rd = reads->dev();
+    P.first = d_first;
+    P.site_slot = d_site_slot;
+    P.row_first = d_row_first;
+    P.cells = (unsigned long long *)d_cells;
+    P.tally = (unsigned long long *)d_tally;
+    P.ends_per_wg = pl.ends_per_wg;
+    P.n_sites = n_sites;
+    P.max_mismatch = max_mismatch;
+    hipLaunchKernelGGL(k_node_site_pairs, dim3(pl.grid), dim3(SITE_PAIRS_TPB), 0, ctx->stream, P);
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}

@@ -24,6 +24,13 @@ bases ACROSS its mismatches (``pe.PileupCounter``, ``tests/pileup_model.py``): a
 positions in its overlap adds one to the depth of every position it covers and is written down where it differs -- BASE
 coverage, substitutions only, no base qualities.  ``--pileup`` writes the A/C/G/T/other table of every position, ``--variants``
 the minor bases above the two thresholds as VCF 4.2.
+
+    ... --site-pairs FILE[.gz] [--sites VCF[.gz]] [--site-pairs-max-span D]
+
+With ``--site-pairs`` the pass also keeps together what ONE fragment -- the two mates of a pair -- carries at a list of sites
+(``pe.SitePairCounter``, ``tests/site_pairs_model.py``) and writes, for every two sites of one segment at most ``D`` positions
+apart, how many fragments carry which two bases: which minor bases travel together.  The sites are the CHROM / POS of
+``--sites`` (one read pass), or without it the records of ``--variants``, for which the reads are read a second time.
 """
 import argparse
 import contextlib
@@ -208,6 +215,68 @@ def pileup_refusal(args):
     return None
 
 
+SITE_PAIR_COLUMNS = ("segment", "pos_a", "pos_b", "base_a", "base_b", "count")
+SITE_PAIR_BASES = "ACGTN"  # the five columns of a cell: N is `other`
+SITE_PAIR_TALLIES = ("fragments observing", "overflow fragments", "discordant sites", "pairs stored", "pairs unstored")
+
+
+def read_vcf_sites(path: str, ids, seqs, kmer_size: int):
+    """The sites of ``--sites``: any VCF against the segments (``.gz``: through gzip).  Lines that start with ``#`` are skipped
+    and only CHROM and POS (1-based) are read.  -> [(segment index in file order, 0-based position)], in the file's order.  A
+    ``ValueError`` names an unknown segment, a position outside its segment and a segment shorter than ``k + 1`` bases."""
+    import gzip
+
+    index = dict((name, n) for n, name in reversed(list(enumerate(ids))))
+    out = []
+    with (gzip.open(path, "rt", encoding="latin-1") if path.endswith(".gz") else open(path, encoding="latin-1")) as fh:
+        for no, line in enumerate(fh, 1):
+            if line.startswith("#") or not line.strip():
+                continue
+            cols = line.rstrip("\n").split("\t")
+            if len(cols) < 2 or not cols[1].lstrip("-").isdigit():
+                raise ValueError("%s, line %d: CHROM and an integer POS are needed" % (path, no))
+            name, pos = cols[0], int(cols[1])
+            if name not in index:
+                raise ValueError("%s, line %d: the graph has no segment %s" % (path, no, name))
+            n = index[name]
+            if len(seqs[n]) < kmer_size + 1:
+                raise ValueError("%s, line %d: segment %s has %d bases, fewer than k + 1 = %d: it has no positions" % (path, no, name, len(seqs[n]), kmer_size + 1))
+            if not 1 <= pos <= len(seqs[n]):
+                raise ValueError("%s, line %d: position %d is outside segment %s of %d bases" % (path, no, pos, name, len(seqs[n])))
+            out.append((n, pos - 1))
+    return out
+
+
+def write_site_pairs(path: str, ids, seg, pos_a, pos_b, counts) -> None:
+    """A TSV with a header line and the columns of ``SITE_PAIR_COLUMNS``: one row per non-zero count of every stored pair of
+    sites (``pe.SitePairCounter.result``); positions 1-based, bases ``A C G T N`` (``N``: a byte outside ACGT); in the order
+    of the result, then ``base_a``, ``base_b`` in that column order.  ``.gz``: through gzip."""
+    with _open_text(path) as fh:
+        fh.write("\t".join(SITE_PAIR_COLUMNS) + "\n")
+        for n, a, b, cell in zip(seg, pos_a, pos_b, counts):
+            fh.write("".join("%s\t%d\t%d\t%s\t%s\t%d\n" % (ids[int(n)], int(a) + 1, int(b) + 1, SITE_PAIR_BASES[i], SITE_PAIR_BASES[j], int(cell[i][j]))
+                             for i in range(5) for j in range(5) if cell[i][j]))
+
+
+def site_pairs_refusal(args):
+    """None, or why the site-pair flags cannot hold, said before a device is opened."""
+    if args.site_pairs_max_span is not None and args.site_pairs_max_span < 0:
+        return "--site-pairs-max-span %d: a span from 0 up is needed" % args.site_pairs_max_span
+    if args.site_pairs is None:
+        if args.site_pairs_max_span is not None or args.sites is not None:
+            return "--sites and --site-pairs-max-span belong to --site-pairs: give it"
+        return None
+    if args.sites is None:
+        if args.variants is None:
+            return "--site-pairs needs its sites: give --sites VCF, or --variants, whose records are then the sites"
+        # the sites are known only once the reads have been read: they are read a second time
+        for path in [args.fwd, args.rve] + list(args.single):
+            if not os.path.isfile(path):
+                return ("--site-pairs without --sites reads the reads twice, and %s is not a regular file: write the records with --variants first "
+                        "and give them as --sites" % path)
+    return None
+
+
 class _Both:
     """Two counters behind one ``add``: what the input dispatch needs of a counter (``pe_inference.feed_counter``), handed on
     to both, so that the pileup rides on the read pass of the depth."""
@@ -282,14 +351,16 @@ def refuse_ranks(world: int) -> None:
 
 
 def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
-               count_singles: bool = False, quiet: bool = False, profile: bool = False, pileup=None):
+               count_singles: bool = False, quiet: bool = False, profile: bool = False, pileup=None, site_pairs=None):
     """Index the segments of ``gfa`` and count every end the chosen input delivers (the input dispatch of
     ``pe_inference.count_links``, one process only).  -> (segment ids in file order, KC int64 in file order, ends counted).
     Replaces the context's index; the context stops keeping masks when the pass is over, so a PE count may follow on it.
     ``quiet``: the dispatch's progress lines are not printed.  ``profile``: the pass counts per window (``pe.CoverCounter``,
     still one kernel per block; KC is its row sums) and a fourth value follows: (segment lengths, offsets, cov).  ``pileup``:
     a mismatch budget; a ``pe.PileupCounter`` then takes every block as well and one more value follows at the end:
-    (segment sequences, offsets, depth, alt, (alignments, rejected)).  Without it no such counter is built."""
+    (segment sequences, offsets, depth, alt, (alignments, rejected)).  Without it no such counter is built.  ``site_pairs``:
+    (sites, mismatch budget, span); a ``pe.SitePairCounter`` then takes every block as well and its ``result()`` with the five
+    tallies behind it follows as the very last value."""
     from . import pe as host
     from . import pe_inference
 
@@ -300,17 +371,48 @@ def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: b
     ctx.build_index(seqs, kmer_size)
     counter = host.CoverCounter(ctx) if profile else host.DepthCounter(ctx)  # (the blocks built from here on keep their masks)
     piles = host.PileupCounter(ctx, max_mismatch=pileup) if pileup is not None else None
+    linked = host.SitePairCounter(ctx, site_pairs[0], max_mismatch=site_pairs[1], max_span=site_pairs[2]) if site_pairs is not None else None
+    fed = counter if piles is None else _Both(counter, piles)
     try:
         with contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext():
-            pe_inference.feed_counter(ctx, counter if piles is None else _Both(counter, piles), inp, 0, 1, stages_follow=False, tally_singles=False)
+            pe_inference.feed_counter(ctx, fed if linked is None else _Both(fed, linked), inp, 0, 1, stages_follow=False, tally_singles=False)
         ctx.sync()
     finally:
         ctx.keep_masks(False)
     piled = () if piles is None else ((seqs,) + piles.result() + (piles.tallies(),),)
+    if linked is not None:
+        piled += (linked.result() + (linked.tallies(),),)
     if profile:
         offsets, cov = counter.result()
         return (ids, counter.kc(), counter.ends_seen, ([len(q) for q in seqs], offsets, cov)) + piled
     return (ids, counter.result(), counter.ends_seen) + piled
+
+
+def site_pairs_pass(ctx, sites, fwd: str, rve: str, max_mismatch: int = 8, max_span: int = 1000, bam_by_name: bool = False, interleaved=None,
+                    check_names=None, single=(), count_singles: bool = False, quiet: bool = False):
+    """The reads once more, through a ``pe.SitePairCounter`` alone, on the index the context holds (``depth_pass`` built it):
+    the second pass of ``--site-pairs`` without ``--sites``, whose sites are known only when the first is over.
+    -> (seg, pos_a, pos_b, counts, the five tallies)."""
+    from . import pe as host
+    from . import pe_inference
+
+    rank, world = pe_inference._rank_world()
+    refuse_ranks(world)
+    inp = pe_inference._resolve_inputs(fwd, rve, world, bam_by_name, interleaved, check_names, single, count_singles, False)
+    linked = host.SitePairCounter(ctx, sites, max_mismatch=max_mismatch, max_span=max_span)
+    try:
+        with contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext():
+            pe_inference.feed_counter(ctx, linked, inp, 0, 1, stages_follow=False, tally_singles=False)
+        ctx.sync()
+    finally:
+        ctx.keep_masks(False)
+    return linked.result() + (linked.tallies(),)
+
+
+def record_sites(ids, records):
+    """The sites of the records ``variant_records`` made: (segment index in file order, 0-based position), each once."""
+    index = dict((name, n) for n, name in reversed(list(enumerate(ids))))
+    return sorted(set((index[r[0]], r[1] - 1) for r in records))
 
 
 def build_parser():
@@ -346,6 +448,14 @@ def build_parser():
                    help="non-agreeing positions an alignment may hold in its overlap [default: 8]")
     p.add_argument("--min-alt-count", dest="min_alt_count", type=int, default=None, metavar="C", help="--variants: records need AD >= C [default: 2]")
     p.add_argument("--min-alt-frac", dest="min_alt_frac", type=float, default=None, metavar="F", help="--variants: records need AD >= F * DP [default: 0.01]")
+    p.add_argument("--site-pairs", dest="site_pairs", type=str, default=None, metavar="FILE",
+                   help="also write which bases travel together on one read pair at pairs of sites of one segment, as a TSV (segment, pos_a, pos_b, "
+                        "base_a, base_b, count; positions 1-based; non-zero counts only; .gz: through gzip).  The sites: --sites, or the records "
+                        "of --variants, for which the reads are read a second time")
+    p.add_argument("--sites", dest="sites", type=str, default=None, metavar="VCF",
+                   help="--site-pairs: the sites, any VCF against the segments (only CHROM and POS are read; .gz: through gzip); one read pass")
+    p.add_argument("--site-pairs-max-span", dest="site_pairs_max_span", type=int, default=None, metavar="D",
+                   help="--site-pairs: two sites are linked when at most D positions apart [default: 1000]")
     return p
 
 
@@ -367,7 +477,7 @@ def main(argv=None) -> int:
     if args.gzip_device:
         os.environ["VS_GZIP_DEVICE"] = "1"
     refuse_ranks(int(os.environ.get("WORLD_SIZE", "1")))  # (before a device is opened)
-    why = pileup_refusal(args)
+    why = pileup_refusal(args) or site_pairs_refusal(args)
     if why is not None:
         print("node_depth: %s" % why, file=sys.stderr)
         return 1
@@ -378,13 +488,25 @@ def main(argv=None) -> int:
                                 fwd=args.fwd, rve=args.rve)
     from . import pe as host
 
+    sites = None
+    budget = 8 if args.pileup_max_mismatch is None else args.pileup_max_mismatch
+    span = 1000 if args.site_pairs_max_span is None else args.site_pairs_max_span
+    if args.sites is not None:
+        try:
+            sites = read_vcf_sites(args.sites, *host.read_gfa_segments(args.gfa), kmer_size=k)
+        except ValueError as e:
+            print("node_depth: --sites: %s" % e, file=sys.stderr)
+            return 1
     ctx = host.Context(args.device)
     profiled = args.profile is not None or args.profile_summary is not None or args.depth_stat is not None
     piled = args.pileup is not None or args.variants is not None
     got = depth_pass(ctx, args.gfa, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=interleaved,
                      check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True, profile=profiled,
-                     pileup=(8 if args.pileup_max_mismatch is None else args.pileup_max_mismatch) if piled else None)
+                     pileup=budget if piled else None, **(dict(site_pairs=(sites, budget, span)) if sites is not None else {}))
     ids, kc, ends = got[:3]
+    linked = None
+    if sites is not None:
+        got, linked = got[:-1], got[-1]
     tags = kc.tolist()
     if profiled:
         lengths, offsets, cov = got[3]
@@ -401,12 +523,22 @@ def main(argv=None) -> int:
         if args.variants is not None:
             write_vcf(args.variants, ids, seqs, p_offsets, p_depth, p_alt, 2 if args.min_alt_count is None else args.min_alt_count,
                       0.01 if args.min_alt_frac is None else args.min_alt_frac)
+        if args.site_pairs is not None and sites is None:  # the records just written are the sites: the reads once more
+            records = variant_records(ids, seqs, p_offsets, p_depth, p_alt, 2 if args.min_alt_count is None else args.min_alt_count,
+                                      0.01 if args.min_alt_frac is None else args.min_alt_frac)
+            linked = site_pairs_pass(ctx, record_sites(ids, records), args.fwd, args.rve, budget, span, bam_by_name=args.bam_by_name,
+                                     interleaved=interleaved, check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True)
+    if linked is not None:
+        write_site_pairs(args.site_pairs, ids, *linked[:4])
     text = rewrite_gfa(raw, tags)
     with open(args.out, "wb") as fh:
         fh.write(text)
     stored = args.out + "".join("; %s in: %s" % (what, path) for what, path in (("profile", args.profile), ("summary", args.profile_summary),
-                                                                                  ("pileup", args.pileup), ("variants", args.variants))
+                                                                                  ("pileup", args.pileup), ("variants", args.variants),
+                                                                                  ("site pairs", args.site_pairs))
                                 if path is not None)
+    if linked is not None:
+        stored += " (%s)" % ", ".join("%d %s" % (v, what) for v, what in zip(linked[4], SITE_PAIR_TALLIES))
     print("node_depth: k = %d, %d read ends counted, %d window-entry coincidences (sum of KC), %d of %d segments with KC = 0; result stored in: %s"
           % (k, ends, int(kc.sum()), int((kc == 0).sum()), len(ids), stored))
     return 0

@@ -1513,6 +1513,15 @@ class Context:
         nat.check(self._h, nat.lib().vs_node_pileup(self._h, reads._h, C.c_void_p(first_ptr), C.c_void_p(diff_ptr), C.c_void_p(alt_ptr),
                                                     max_mismatch, C.c_void_p(tally_ptr)))
 
+    def node_site_pairs(self, reads: ReadBlock, first_ptr: int, site_slot_ptr: int, n_sites: int, row_first_ptr: int, cells_ptr: int,
+                        max_mismatch: int, tally_ptr: int):
+        """One block through the site-pair pass (``vs_node_site_pairs``): ``site_slot_ptr``: ``n_sites`` ascending uint32 slots
+        of ``pileup_layout``; ``row_first_ptr``: what ``site_pairs_rows`` made of them; one count per stored pair of sites a
+        fragment saw on the uint64 ``[cells, 25]`` array at ``cells_ptr``, and the five tallies added to the uint64 at
+        ``tally_ptr``.  Blocks must have been built after ``keep_masks(True)``."""
+        nat.check(self._h, nat.lib().vs_node_site_pairs(self._h, reads._h, C.c_void_p(first_ptr), C.c_void_p(site_slot_ptr), n_sites,
+                                                        C.c_void_p(row_first_ptr), C.c_void_p(cells_ptr), max_mismatch, C.c_void_p(tally_ptr)))
+
     def contig_mems(self, reads: ReadBlock) -> np.ndarray:
         """Every maximal exact match of k + 1 bases or more between a contig of the block and a strand of a segment
         (``vs_contig_mems``): uint32 [n, 5] -- contig, first base in the contig, segment | strand << 31, first base in that
@@ -2154,6 +2163,123 @@ class PileupCounter:
         """-> (alignments credited, alignments rejected for more than ``max_mismatch`` non-agreeing positions)."""
         t = self.tally.cpu().numpy()
         return int(t[0]), int(t[1])
+
+
+def site_pairs_plan(n_nodes: int, ksize: int, n_ends: int, max_len: int, n_cu: int = 256) -> dict:
+    """The launch ``vs_node_site_pairs`` makes for a block (``vs_site_pairs_plan``, a pure host function: no device is
+    needed): ``ends_per_wg`` is a multiple of 64, so that no workgroup and no batch of 64 ends cuts a pair.  An odd ``n_ends``
+    is refused."""
+    a = (C.c_uint64 * 8)()
+    rc = nat.lib().vs_site_pairs_plan(n_nodes, ksize, n_ends, max_len, n_cu, a)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_site_pairs_plan refuses %d nodes / %d ends of up to %d bases%s"
+                              % (n_nodes, n_ends, max_len, ": fragments are the ends 2p and 2p + 1, an odd number of ends cuts one" if n_ends % 2 else ""))
+    return dict(launch=bool(a[0]), grid=int(a[1]), ends_per_wg=int(a[2]), lds_bytes=int(a[6]), threads=int(a[7]))
+
+
+def site_pairs_rows(seg, pos, span: int) -> Tuple[np.ndarray, int]:
+    """The rows of the cell table (``vs_site_pairs_rows_host``, a pure host function): ``(seg[i], pos[i])`` are the sites,
+    strictly ascending by segment, then position; site i's partners are the later sites of its segment at most ``span``
+    positions behind it, contiguous behind it.  -> (row_first uint32 [n + 1], the number of cells): the cell of (s, t) is
+    ``row_first[s] + (t - s - 1)``.  2^32 cells or more are refused: lower the span."""
+    seg = np.ascontiguousarray(seg, dtype=np.uint32)
+    pos = np.ascontiguousarray(pos, dtype=np.uint32)
+    if seg.shape != pos.shape or seg.ndim != 1 or not 0 <= int(span) < 2 ** 32:
+        raise ValueError("site_pairs_rows: two equally long lists and a span from 0 up are needed")
+    row_first = np.zeros(len(seg) + 1, dtype=np.uint32)
+    total = C.c_uint64(0)
+    rc = nat.lib().vs_site_pairs_rows_host(seg.ctypes.data, pos.ctypes.data, len(seg), int(span), row_first.ctypes.data, C.byref(total))
+    if rc == nat.VS_E_RANGE:
+        raise nat.NativeError(rc, "%d sites within %d positions of each other make %s cells, and a cell number has 32 bits (a site number 29): lower the span"
+                              % (len(seg), span, "2^32 or more" if total.value else "too many"))
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_site_pairs_rows_host: the sites must ascend strictly by segment, then position")
+    return row_first, int(total.value)
+
+
+class SitePairCounter:
+    """Which variant sites travel together on one read pair, counted on one device (``vs_node_site_pairs``): for every
+    fragment -- the two mates of a pair, or one single read -- what the alignments the pileup would credit carry at the given
+    ``sites`` is kept together, and every pair of sites of one segment at most ``max_span`` apart that the fragment saw adds
+    1 to a 5 x 5 cell ``[base at the first][base at the second]`` (A, C, G, T, other; ``tests/site_pairs_model.py``).
+    ``sites``: (segment index in the order ``Context.build_index`` was given, 0-based position); a site named twice is one.
+    Takes ``PileupCounter``'s place in the input dispatch of ``pe_inference`` (``add``, ``device``, ``single_stats``,
+    ``ends_seen``; the context keeps the masks): one kernel per block.  Holds 200 bytes per pair of sites within the span."""
+
+    def __init__(self, ctx: Context, sites, max_mismatch: int = 8, max_span: int = 1000, device: Optional[str] = None):
+        import torch
+
+        if not 0 <= int(max_mismatch) < 2 ** 32:
+            raise ValueError("a mismatch budget of %r: an integer from 0 up is needed" % (max_mismatch,))
+        if not 0 <= int(max_span) < 2 ** 32:
+            raise ValueError("a span of %r: an integer from 0 up is needed" % (max_span,))
+        self.torch = torch
+        self.ctx = ctx
+        self.device = torch.device(device or ("cuda:%d" % ctx.device))
+        self.n = ctx.n_nodes
+        self.ksize = ctx.ksize
+        self.max_mismatch = int(max_mismatch)
+        self.max_span = int(max_span)
+        self.single_stats = torch.zeros(3, dtype=torch.int64, device=self.device)  # (what the dispatch tallies of a PeCounter: stays zero)
+        self.ends_seen = 0  # ends the blocks delivered (the absent second ends of singles blocks aside)
+        node_rank = getattr(ctx, "node_rank", None)
+        with torch.cuda.device(self.device):
+            ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.first = torch.zeros(self.n + 1, dtype=torch.int32, device=self.device)  # (uint32 words)
+            ctx.pileup_layout(self.first.data_ptr())
+            first = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
+            given = np.array([(int(n), int(p)) for n, p in sites], dtype=np.int64).reshape(-1, 2)
+            for n, p in given.tolist():
+                if not 0 <= n < self.n:
+                    raise ValueError("site (%d, %d): there is no segment %d among the %d of the index" % (n, p, n, self.n))
+                r = n if node_rank is None else int(node_rank[n])
+                if first[r + 1] == first[r]:
+                    raise ValueError("site (%d, %d): segment %d is shorter than k + 1 = %d bases and has no positions" % (n, p, n, self.ksize + 1))
+                if not 0 <= p < first[r + 1] - first[r] - 1:
+                    raise ValueError("site (%d, %d): position %d is outside segment %d of %d bases" % (n, p, p, n, first[r + 1] - first[r] - 1))
+            rank = given[:, 0] if node_rank is None else np.asarray(node_rank, dtype=np.int64)[given[:, 0]]
+            slot = np.unique(first[rank] + given[:, 1])  # (ascending; one slot per site, so a site named twice is one)
+            self.site_rank = np.searchsorted(first, slot, side="right") - 1  # the sites' segments, internal numbering
+            self.site_pos = slot - first[self.site_rank]
+            self.site_seg = self.site_rank if ctx.node_order is None else np.asarray(ctx.node_order, dtype=np.int64)[self.site_rank]
+            self.n_sites = len(slot)
+            self.row_first, self.n_cells = site_pairs_rows(self.site_rank, self.site_pos, self.max_span)
+            self.site_slot = torch.from_numpy(slot.astype(np.uint32).view(np.int32)).to(self.device)
+            self.d_row_first = torch.from_numpy(self.row_first.view(np.int32)).to(self.device)
+            self.cells = torch.zeros((max(self.n_cells, 1), 25), dtype=torch.int64, device=self.device)
+            self.tally = torch.zeros(5, dtype=torch.int64, device=self.device)
+        ctx.keep_masks(True)
+
+    def add(self, reads: ReadBlock):
+        torch = self.torch
+        n_ends = reads.info["ends"]
+        self.ends_seen += n_ends // 2 if reads.unpaired else n_ends
+        if not self.n_sites:
+            return
+        with torch.cuda.device(self.device):
+            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.ctx.node_site_pairs(reads, self.first.data_ptr(), self.site_slot.data_ptr(), self.n_sites, self.d_row_first.data_ptr(),
+                                     self.cells.data_ptr(), self.max_mismatch, self.tally.data_ptr())
+
+    def result(self):
+        """-> (seg int64 [P], pos_a int64 [P], pos_b int64 [P], counts int64 [P, 5, 5]): every stored pair of sites with a
+        non-zero cell; ``seg`` in the numbering of the node list ``Context.build_index`` was given (the GFA's), positions
+        0-based, ``pos_a < pos_b``; ``counts[i, a, b]``: fragments that carry column ``a`` at ``pos_a`` and ``b`` at ``pos_b``
+        (A, C, G, T, other).  Ordered by ``seg``, then ``pos_a``, then ``pos_b``."""
+        cells = self.cells[: self.n_cells].cpu().numpy()
+        at = np.flatnonzero(cells.any(axis=1))
+        row_first = self.row_first.astype(np.int64)
+        s = np.searchsorted(row_first, at, side="right") - 1  # (the row that holds the cell: an empty row holds none)
+        t = s + 1 + at - row_first[s]
+        seg, pos_a, pos_b = self.site_seg[s], self.site_pos[s], self.site_pos[t]
+        order = np.lexsort((pos_b, pos_a, seg))
+        return (seg[order].astype(np.int64), pos_a[order].astype(np.int64), pos_b[order].astype(np.int64),
+                cells[at][order].astype(np.int64).reshape(len(at), 5, 5))
+
+    def tallies(self):
+        """-> (fragments with a raw observation, overflow fragments: more than 32 raw observations, nothing deposited,
+        discordant (fragment, site) incidences, pairs stored, pairs unstored: on two segments or further apart than the span)."""
+        return tuple(int(v) for v in self.tally.cpu().numpy())
 
 
 # ---- outputs -------------------------------------------------------------------------------------
