@@ -966,6 +966,49 @@ int vs_site_pairs_frag_host(const uint32_t *raw, uint32_t n, uint32_t *kept, uin
 int vs_node_site_pairs(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, const uint32_t *d_site_slot, uint32_t n_sites,
                        const uint32_t *d_row_first, uint64_t *d_cells, uint32_t max_mismatch, uint64_t *d_tally);
 
+/* ---- the pileup kept apart by strand, and its records found on the device (additions to ABI 11 without a new number:
+ * nothing that exists changes) --  No counterpart in the reference.  Everything the base pileup above defines holds unchanged;
+ * the PLANE of a credited alignment is its strand t: plane 0 -- the end's bytes, as the ingest delivers them, read along the
+ * segment's forward text; plane 1 -- read along its reverse complement (not the mate number, not the end's parity).  For
+ * every overlap position depth[n][p][t] += 1, and where it does not agree alt[n][p][t][c] += 1, c as before.  Summed over t
+ * both tables are the base pileup's exactly and the two tallies are equal; a palindromic overlap puts 1 into each plane; a read
+ * and its reverse complement put the same forward-strand column into different planes.  RECORDS, for one position with the
+ * segment's base ref: count[t][b] = alt[t][b] for b != ref and count[t][ref] = depth[t] - the five alt columns of t; DP = the
+ * sum of count over both planes and A, C, G, T (`other` is left out); for b != ref in ACGT order AD = count[0][b] +
+ * count[1][b], and b is a record when AD > 0, AD >= min_alt_count and (double)AD >= min_alt_frac * (double)DP, one IEEE double
+ * product compared as it stands (0.07 * 100 > 7: no record; 0.29 * 100 <= 29: one).  A record carries DP4 = ref_f, ref_r,
+ * alt_f, alt_r = count[0][ref], count[1][ref], count[0][b], count[1][b]; with min_alt_strand >= 1 it FAILS the strand filter
+ * when alt_f or alt_r is below it, and stays a record.  tests/strand_pileup_model.py states all of it;
+ * csrc/vs_pileup_call_core.h is the rule of one position.  Six uint64 make a record: slot << 5 | strand_fail << 4 | ref << 2 |
+ * alt (2-bit base codes), then DP, ref_f, ref_r, alt_f, alt_r.
+ *   vs_node_pileup_strands : one block through k_node_pileup_strands on the context's current index: vs_node_pileup with the
+ *                            planes kept apart.  n_slots: the S vs_pileup_layout gave for THIS index; d_diff: DEVICE, 2 x S
+ *                            uint32, plane-major, zero before the first block -- each plane is a difference array with its own
+ *                            sentinels and is folded on its own by vs_cover_fold (S slots at d_diff + t * S into S uint64 at
+ *                            d_depth + t * S); d_alt: DEVICE, S x 2 x 5 uint64 [slot][plane][column], zero before the first
+ *                            block; d_tally as vs_node_pileup's.  The fold rule is vs_pileup_plan's, unchanged: one end adds
+ *                            at most its length to one slot of one plane.  Enqueued on the ctx stream.  Blocks must have been
+ *                            built after vs_ctx_keep_masks(ctx, 1).  VS_E_RANGE as vs_node_pileup, and S >= 2^32.
+ *   vs_pileup_call         : the records of all S slots, found by two passes with one lane per slot and the exclusive scan
+ *                            between them; the segment's base comes from the index's own forward text, a sentinel slot emits
+ *                            nothing and is not read.  planes = 2: d_depth [2][S], d_alt [S][2][5] as above; planes = 1: the
+ *                            tables of vs_node_pileup, d_depth [S], d_alt [S][5], folded -- then ref_r = alt_r = 0.  *n (host)
+ *                            = the exact number of records.  With cap >= *n they are written to d_out (DEVICE, cap x 6 uint64)
+ *                            ascending by slot, then alt base; with cap < *n NOTHING is written and the call returns VS_OK:
+ *                            allocate *n records and call again.  Synchronises the ctx stream.  Uses 4 bytes per slot of the
+ *                            context's scratch, shared with vs_cover_fold.  VS_E_ARG: a NULL pointer, planes outside {1, 2},
+ *                            min_alt_frac NaN or negative, min_alt_strand != 0 with one plane; VS_E_RANGE: 2^32 slots or
+ *                            records.
+ *   vs_pileup_call_host    : host only, no device: the rule of csrc/vs_pileup_call_core.h, the code both passes run, on ONE
+ *                            position.  ref: 0..3; depth: `planes` uint64; alt: planes x 5 uint64; out: room for three
+ *                            records, written with *n of them (their slot is 0).  VS_E_ARG as vs_pileup_call, and ref > 3. */
+int vs_node_pileup_strands(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, uint64_t n_slots, uint32_t *d_diff, uint64_t *d_alt,
+                           uint32_t max_mismatch, uint64_t *d_tally);
+int vs_pileup_call(vs_ctx *ctx, const uint32_t *d_first, uint64_t n_slots, uint32_t planes, const uint64_t *d_depth, const uint64_t *d_alt,
+                   uint64_t min_alt_count, double min_alt_frac, uint64_t min_alt_strand, uint64_t *d_out, uint64_t cap, uint64_t *n);
+int vs_pileup_call_host(uint32_t ref, uint32_t planes, const uint64_t *depth, const uint64_t *alt, uint64_t min_alt_count, double min_alt_frac,
+                        uint64_t min_alt_strand, uint64_t out[3][6], uint32_t *n);
+
 /* Testing aid (ABI 11): the two exclusive scans under the index build, the locus sort, every row_ptr and every member,
  * record and word offset, run alone on values the caller made up, launched exactly as their callers launch them (no kernel
  * of its own).  HOST pointers: in[n + guard] = the n values and behind them `guard` words of a sentinel the caller chose;

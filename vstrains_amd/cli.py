@@ -114,6 +114,9 @@ def build_parser():
     # with --depth-from-reads --depth-pileup: the reads are then read once more and what one read pair carries at the positions of the
     # records of gfa/graph_depth.vcf is written as gfa/graph_depth.site_pairs.tsv (vstrains_amd.node_depth --variants --site-pairs)
     p.add_argument("--depth-site-pairs", dest="depth_site_pairs", action="store_true", default=False, help=argparse.SUPPRESS)
+    # with --depth-from-reads --depth-pileup: the pileup keeps the two strands apart and the two files are written in their stranded
+    # form, the records found on the device and carrying DP4 (vstrains_amd.node_depth --pileup --variants --strands)
+    p.add_argument("--depth-strands", dest="depth_strands", action="store_true", default=False, help=argparse.SUPPRESS)
     return p
 
 
@@ -155,6 +158,13 @@ def depth_pileup_refusal(args):
     """None, or why ``--depth-pileup`` cannot hold, said before anything is written: it rides on the depth pass."""
     if args.depth_pileup and not args.depth_from_reads:
         return "--depth-pileup writes the base pileup of the depth pass: give --depth-from-reads with it"
+    return None
+
+
+def depth_strands_refusal(args):
+    """None, or why ``--depth-strands`` cannot hold, said before anything is written: the strands are those of the pileup."""
+    if args.depth_strands and not (args.depth_from_reads and args.depth_pileup):
+        return "--depth-strands keeps the strands of the pileup apart: give --depth-from-reads --depth-pileup with it"
     return None
 
 
@@ -203,7 +213,8 @@ def depth_from_reads(args, logger, ctx):
         sys.exit(1)
     got = node_depth.depth_pass(ctx, args.gfa_file, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=args.interleaved,
                                 check_names=args.check_names, single=args.single, count_singles=args.count_singles, quiet=True,
-                                profile=args.depth_profile, pileup=8 if args.depth_pileup else None)
+                                profile=args.depth_profile, pileup=8 if args.depth_pileup else None,
+                                **(dict(strands=(2, 0.01, 0)) if args.depth_strands else {}))
     ids, kc, ends = got[:3]
     out = args.output_dir + "/gfa/graph_depth.gfa"
     with open(out, "wb") as fh:
@@ -214,13 +225,17 @@ def depth_from_reads(args, logger, ctx):
         node_depth.write_summary(args.output_dir + "/gfa/graph_depth.tsv", ids, lengths, offsets, cov)
         logger.info("depth profile of every window of k + 1 bases: {0}/gfa/graph_depth.bedgraph, per segment: {0}/gfa/graph_depth.tsv".format(args.output_dir))
     if args.depth_pileup:
-        seqs, p_offsets, p_depth, p_alt, (credited, rejected) = got[-1]
-        node_depth.write_pileup(args.output_dir + "/gfa/graph_depth.pileup.tsv", ids, seqs, p_offsets, p_depth, p_alt)
-        node_depth.write_vcf(args.output_dir + "/gfa/graph_depth.vcf", ids, seqs, p_offsets, p_depth, p_alt)
+        seqs, p_offsets, p_depth, p_alt, (credited, rejected) = got[-1][:5]
+        if args.depth_strands:
+            node_depth.write_strand_pileup(args.output_dir + "/gfa/graph_depth.pileup.tsv", ids, seqs, p_offsets, p_depth, p_alt)
+            node_depth.write_strand_vcf(args.output_dir + "/gfa/graph_depth.vcf", ids, seqs, p_offsets, got[-1][5])
+        else:
+            node_depth.write_pileup(args.output_dir + "/gfa/graph_depth.pileup.tsv", ids, seqs, p_offsets, p_depth, p_alt)
+            node_depth.write_vcf(args.output_dir + "/gfa/graph_depth.vcf", ids, seqs, p_offsets, p_depth, p_alt)
         logger.info("base pileup of every position: {0}/gfa/graph_depth.pileup.tsv, minor bases: {0}/gfa/graph_depth.vcf ({1} alignments, {2} rejected)"
                     .format(args.output_dir, credited, rejected))
     if args.depth_site_pairs:
-        records = node_depth.variant_records(ids, seqs, p_offsets, p_depth, p_alt)
+        records = node_depth.strand_records(ids, got[-1][5]) if args.depth_strands else node_depth.variant_records(ids, seqs, p_offsets, p_depth, p_alt)
         linked = node_depth.site_pairs_pass(ctx, node_depth.record_sites(ids, records), args.fwd, args.rve, bam_by_name=args.bam_by_name,
                                             interleaved=args.interleaved, check_names=args.check_names, single=args.single,
                                             count_singles=args.count_singles, quiet=True)
@@ -279,7 +294,7 @@ def main(argv=None, backend=None):
     args.single = pe_inference.unpaired_input(args.single, args.count_singles, pe_inference._rank_world()[1], args.interleaved,
                                               pe_text_from=args.pe_text_from, check_names=args.check_names, bam_by_name=args.bam_by_name,
                                               fwd=args.fwd, rve=args.rve)
-    why = depth_profile_refusal(args) or depth_pileup_refusal(args) or depth_site_pairs_refusal(args)
+    why = depth_profile_refusal(args) or depth_pileup_refusal(args) or depth_strands_refusal(args) or depth_site_pairs_refusal(args)
     if why is not None:
         raise ValueError(why)
     if args.depth_from_reads:

@@ -4110,3 +4110,292 @@ extern "C" int vs_node_site_pairs(vs_ctx *ctx, const vs_reads *reads, const uint
     VS_HIP(ctx, hipGetLastError());
     return VS_OK;
 }
+
+// ---- the pileup kept apart by strand, and its records found on the device (vs_node_pileup_strands / vs_pileup_call) ----------
+// k_node_pileup once more with the one thing it throws away kept: the strand `opp` of a credited alignment is its PLANE (0: the
+// end lies along the segment's forward text, 1: along its reverse complement; tests/strand_pileup_model.py).  Everything up to
+// and including vs_pileup_owner and vs_pileup_count is k_node_pileup's, and so are the workgroup, the LDS and the slots.  The
+// difference array is plane-major, diff[2][S]: the +1 and the -1 of an alignment go to plane `opp`, every plane keeps its own
+// sentinels (the -1 of an overlap flush with the end of the last segment lands in slot S - 1 of ITS plane), and each plane folds
+// by vs_cover_fold on its own.  alt is [S][2][5]: both planes of a slot lie in 80 bytes, one 64-bit atomic per non-agreeing base
+// as before.  The fold bound is vs_pileup_plan's, unchanged: one end adds at most len_e to one slot of ONE plane (one diagonal
+// per read offset through a position of a strand), below the 2 * len_e the plan's weight assumes -- no second plan.
+#include "vs_pileup_call_core.h"
+
+struct PileupStrandsParams {
+    VsIndexDev idx;
+    VsReadsDev rd;
+    const uint32_t *first;     // [n_nodes + 1] the first slot of every segment, the slot total S behind them
+    uint32_t *diff;            // [2][S] differences of the depth per plane, ADDED to
+    unsigned long long *alt;   // [S][2][PILEUP_ALT] non-agreeing bases per plane, ADDED to
+    unsigned long long *tally; // [2] alignments credited, alignments rejected, ADDED to
+    uint64_t n_slots;          // S
+    uint64_t ends_per_wg;
+    uint32_t max_mismatch;
+};
+
+__global__ void __launch_bounds__(PILEUP_TPB, 8)  // (as k_node_pileup)
+k_node_pileup_strands(PileupStrandsParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_mem[PILEUP_LDS_WORDS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t N = P.idx.n_nodes, w = P.idx.w, s = P.idx.s, K = P.idx.K;
+    uint32_t *s_head = s_mem;
+    uint32_t *sw = s_mem + PILEUP_HEAD_WORDS + wave * PILEUP_WAVE_WORDS;
+    uint32_t *s_np = sw, *s_cnt = sw + 65u, *s_pa = sw + 130u, *s_pb = sw + 194u, *s_pj = sw + 258u;
+    const uint64_t e_lo = (uint64_t)blockIdx.x * P.ends_per_wg;
+    const uint64_t e_hi = e_lo + P.ends_per_wg < P.rd.n_ends ? e_lo + P.ends_per_wg : P.rd.n_ends;
+    if (tid == 0u) s_head[0] = 0u;
+    __syncthreads();
+    for (;;) {
+        uint32_t b = 0u;
+        if (lane == 0u) b = atomicAdd(&s_head[0], 64u);
+        b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+        if (e_lo + b >= e_hi) break;
+        const uint64_t e0 = e_lo + b;
+        const uint32_t n_here = e_hi - e0 < 64u ? (uint32_t)(e_hi - e0) : 64u;
+        uint32_t np = 0u;
+        if (lane < n_here) {
+            const uint32_t meta = P.rd.meta[e0 + lane];
+            if (!((meta >> 24) & VS_FLAG_ABSENT)) np = vs_seed_probes(meta & VS_LEN_MASK, w, s);  // (0 for an end shorter than K)
+        }
+        s_np[lane + 1u] = vs_wave_scan_add(np);
+        if (lane == 0u) s_np[0] = 0u;
+        vs_wave_sync();
+        const uint32_t tp = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_np[64]);
+        for (uint32_t p0 = 0u; p0 < tp; p0 += 64u) {
+            // probes p0 .. p0 + 63 of the batch: one per lane
+            const uint32_t t = p0 + lane;
+            uint32_t c = 0u, pa = 0u, pb = 0u, pj = 0u;
+            if (t < tp) {
+                const uint32_t el = vs_upper_idx(s_np, 65u, t);  // the end that owns probe t: s_np[el] <= t < s_np[el + 1]
+                const uint64_t e = e0 + el;
+                const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                const uint32_t j = vs_seed_phase(rlen, w, s) + (t - s_np[el]) * s;
+                const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                if (!(mk && vs_seed_dirty(mk, rbase + j, w))) {
+                    uint32_t sr;
+                    const uint64_t key = vs_seed_key(P.rd.words, rbase + j, w, &sr);
+                    c = vs_probe(P.idx, key, sr, &pa, &pb);
+                }
+                pj = (el << 24) | j;  // (a read offset fits 24 bits: VS_LEN_MASK)
+            }
+            s_pa[lane] = pa;
+            s_pb[lane] = pb;
+            s_pj[lane] = pj;
+            s_cnt[lane + 1u] = vs_wave_scan_add(c);
+            if (lane == 0u) s_cnt[0] = 0u;
+            vs_wave_sync();
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[64]);
+            for (uint32_t q0 = 0u; q0 < total; q0 += 64u) {
+                // postings q0 .. q0 + 63 of these probes: one per lane
+                const uint32_t t2 = q0 + lane;
+                bool credited = false, rejected = false;
+                if (t2 < total) {
+                    const uint32_t pr = vs_upper_idx(s_cnt, 65u, t2);
+                    const uint32_t k2 = t2 - s_cnt[pr];
+                    const uint32_t qa0 = s_pa[pr], qb0 = s_pb[pr], ej = s_pj[pr];
+                    const uint32_t j = ej & VS_LEN_MASK;
+                    const uint64_t e = e0 + (ej >> 24);
+                    const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                    const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                    const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                    uint32_t nd, pos, opp;
+                    VsNodeMeta nm;
+                    if (s_cnt[pr + 1u] - s_cnt[pr] == 1u) {
+                        nd = qa0; pos = qb0 & 0x7FFFFFFFu; opp = qb0 >> 31;
+                        nm = P.idx.meta[nd];
+                    } else {
+                        const VsPosting po = vs_posting_unpack(P.idx.postings[qa0 + k2]);
+                        nd = po.node; pos = po.pos; opp = po.strand ^ (qb0 >> 31);
+                        nm.woff = po.woff; nm.len = po.len;
+                    }
+                    const uint32_t *tw = opp ? P.idx.rc_words : P.idx.fwd_words;
+                    const uint32_t q = opp ? nm.len - pos - w : pos;
+                    uint32_t a, qa, len;
+                    // (k >= 95: VS_SEED_VERIFIED is 0, the key only nominated the posting and the comparison starts at the seed's first base)
+                    if (nd < N && vs_extend(P.rd.words, rbase, rlen, tw, nm.woff * 16u, nm.len, j, q, VS_SEED_VERIFIED(w), s, K, mk, rbase, &a, &qa, &len) &&
+                        qa + len <= nm.len) {  // (a match lies inside its strand: no slot beyond the segment's sentinel)
+                        const uint64_t tbase = (uint64_t)nm.woff * 16u;
+                        const VsPileupSpan sp = vs_pileup_span(rlen, nm.len, a, qa);
+                        if (vs_pileup_owner(P.rd.words, rbase, tw, tbase, mk, sp, a, K)) {
+                            uint32_t miss = vs_pileup_count(P.rd.words, rbase, tw, tbase, mk, sp);
+                            rejected = miss > P.max_mismatch;
+                            credited = !rejected;
+                            if (credited) {
+                                // the overlap on the strand: [t_lo, t_hi); on the forward text: from p_lo on, as many; the plane: opp
+                                const uint32_t t_lo = (uint32_t)((int64_t)sp.x_lo + sp.d), t_hi = (uint32_t)((int64_t)sp.x_hi + sp.d);
+                                const uint32_t at = P.first[nd] + (opp ? nm.len - t_hi : t_lo);
+                                uint32_t *first_slot = P.diff + ((opp ? P.n_slots : 0ull) + at);  // (in the alignment's plane)
+                                atomicAdd(first_slot, 1u);
+                                atomicAdd(first_slot + (sp.x_hi - sp.x_lo), 0xFFFFFFFFu);  // (at most the segment's sentinel: below S)
+                                for (uint32_t x = sp.x_lo; miss && x < sp.x_hi; x += 32u) {
+                                    const uint32_t n = sp.x_hi - x < 32u ? sp.x_hi - x : 32u;
+                                    uint64_t f = vs_pl_differ(P.rd.words, rbase, tw, tbase, mk, x, sp.d, n);
+                                    if (!f) continue;
+                                    const uint64_t rwin = vs_pl_win(P.rd.words, rbase + x);
+                                    const uint64_t mwin = mk ? vs_pl_win(mk, rbase + x) : 0ull;
+                                    while (f) {
+                                        const uint32_t bit = (uint32_t)__ffsll((long long)f) - 1u;  // (even: 2 * the base's place in the window)
+                                        f &= f - 1ull;
+                                        const uint32_t code = (uint32_t)(rwin >> bit) & 3u;
+                                        // the read's base as it reads on the forward strand; a byte outside ACGT: `other`
+                                        // ... and behind the five columns of plane 0 for an alignment of plane 1
+                                        const uint32_t col = ((mwin >> bit) & 3ull) ? (opp ? 4u + PILEUP_ALT : 4u) : (opp ? 3u + PILEUP_ALT - code : code);
+                                        const uint32_t ts = t_lo + (x - sp.x_lo) + (bit >> 1);  // strand offset of the base
+                                        const uint64_t slot = (uint64_t)P.first[nd] + (opp ? nm.len - 1u - ts : ts);
+                                        atomicAdd(&P.alt[slot * (2u * PILEUP_ALT) + col], 1ull);
+                                        miss--;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+                vs_pileup_tally(P.tally, credited, lane);
+                vs_pileup_tally(P.tally + 1, rejected, lane);
+            }
+            vs_wave_sync();  // s_cnt / s_pa / s_pb / s_pj are rewritten by the next 64 probes
+        }
+        vs_wave_sync();  // s_np is rewritten by the next batch
+    }
+}
+
+extern "C" int vs_node_pileup_strands(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, uint64_t n_slots, uint32_t *d_diff, uint64_t *d_alt,
+                                      uint32_t max_mismatch, uint64_t *d_tally) {
+    if (!ctx || !reads || !d_first || !d_diff || !d_alt || !d_tally) return VS_E_ARG;
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_node_pileup_strands: build an index first (vs_index_build)");
+    if (n_slots >= (1ull << 32)) return vs_fail(ctx, VS_E_RANGE, "vs_node_pileup_strands: %llu slots", (unsigned long long)n_slots);
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const VsIndexDev &idx = ctx->idx;
+    const PileupPlan pl = vs_pileup_plan_for(idx.n_nodes, idx.K, reads->n_ends, (uint32_t)reads->max_len, (uint32_t)ctx->n_cu, 0, 0);
+    if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "vs_node_pileup_strands: %s", pl.msg);
+    if (!pl.launch || !n_slots) return VS_OK;  // no end of the block holds an anchor, or no segment has a position
+    PileupStrandsParams P;
+    P.idx = idx;
+    P.rd = reads->dev();
+    P.first = d_first;
+    P.diff = d_diff;
+    P.alt = (unsigned long long *)d_alt;
+    P.tally = (unsigned long long *)d_tally;
+    P.n_slots = n_slots;
+    P.ends_per_wg = pl.ends_per_wg;
+    P.max_mismatch = max_mismatch;
+    hipLaunchKernelGGL(k_node_pileup_strands, dim3(pl.grid), dim3(PILEUP_TPB), 0, ctx->stream, P);
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}
+
+// The caller: one lane per slot, twice.  Pass 1 finds the slot's segment by a binary search on `first`, reads the segment's base
+// from the index's own forward text, applies the rule of vs_pileup_call_core.h and writes how many records the slot makes (0 to
+// 3); vs_scan_u32 gives every slot its place; pass 2 applies the same rule again and writes the records there -- ascending by
+// (slot, alt base), of the exact size, and nothing else leaves the device.  A sentinel slot has no base and emits nothing: its
+// counts are not read and no text behind the segment's is.
+struct PileupCallParams {
+    const uint32_t *first;             // [n_nodes + 1] the first slot of every segment, the slot total behind them
+    const VsNodeMeta *meta;            // [n_nodes]
+    const uint32_t *fwd_words;         // the segments' forward texts
+    const unsigned long long *depth;   // [planes][S]
+    const unsigned long long *alt;     // [S][planes][PILEUP_ALT]
+    uint32_t *count;                   // [S] pass 1: records per slot, written; pass 2: the records before the slot's, read
+    unsigned long long *out;           // pass 2: [n][PILEUP_CALL_WORDS]
+    uint64_t n_slots;                  // S
+    uint64_t min_alt_count, min_alt_strand;
+    double min_alt_frac;
+    uint32_t n_nodes, planes;
+};
+
+// the records of slot i (out: NULL counts them only); 0 for a sentinel slot and for a slot no segment owns
+__device__ __forceinline__ uint32_t vs_pileup_call_lane(const PileupCallParams &P, uint64_t i, uint64_t *out) {
+    const uint32_t n = vs_upper_idx(P.first, P.n_nodes + 1u, (uint32_t)i);  // first[n] <= i < first[n + 1]: segments without slots are skipped
+    if (n >= P.n_nodes) return 0u;
+    const VsNodeMeta nm = P.meta[n];
+    const uint32_t p = (uint32_t)i - P.first[n];
+    if (p >= nm.len) return 0u;  // the sentinel
+    const uint32_t ref = (P.fwd_words[nm.woff + (p >> 4)] >> ((p & 15u) * 2u)) & 3u;
+    uint64_t depth[2] = {P.depth[i], 0ull}, alt[2][5] = {{0ull, 0ull, 0ull, 0ull, 0ull}, {0ull, 0ull, 0ull, 0ull, 0ull}};
+    const unsigned long long *a = P.alt + i * P.planes * PILEUP_ALT;
+#pragma unroll
+    for (uint32_t c = 0u; c < PILEUP_ALT; c++) alt[0][c] = a[c];
+    if (P.planes == 2u) {
+        depth[1] = P.depth[P.n_slots + i];
+#pragma unroll
+        for (uint32_t c = 0u; c < PILEUP_ALT; c++) alt[1][c] = a[PILEUP_ALT + c];
+    }
+    return vs_pileup_call_slot(ref, depth, alt, P.min_alt_count, P.min_alt_frac, P.min_alt_strand, i, out);
+}
+
+__global__ void __launch_bounds__(PILEUP_CALL_TPB)
+k_pileup_call_count(PileupCallParams P) {
+    const uint64_t i = (uint64_t)blockIdx.x * PILEUP_CALL_TPB + threadIdx.x;
+    if (i >= P.n_slots) return;
+    P.count[i] = vs_pileup_call_lane(P, i, nullptr);
+}
+
+__global__ void __launch_bounds__(PILEUP_CALL_TPB)
+k_pileup_call_write(PileupCallParams P) {
+    const uint64_t i = (uint64_t)blockIdx.x * PILEUP_CALL_TPB + threadIdx.x;
+    if (i >= P.n_slots) return;
+    (void)vs_pileup_call_lane(P, i, (uint64_t *)P.out + (uint64_t)P.count[i] * PILEUP_CALL_WORDS);  // (a slot without records writes nothing)
+}
+
+extern "C" int vs_pileup_call_host(uint32_t ref, uint32_t planes, const uint64_t *depth, const uint64_t *alt, uint64_t min_alt_count, double min_alt_frac,
+                                   uint64_t min_alt_strand, uint64_t out[3][6], uint32_t *n) {
+    if (!depth || !alt || !out || !n || ref > 3u || !vs_pileup_call_args_ok(planes, min_alt_frac, min_alt_strand)) return VS_E_ARG;
+    uint64_t d[2] = {depth[0], planes == 2u ? depth[1] : 0ull}, a[2][5];
+    for (uint32_t c = 0u; c < PILEUP_ALT; c++) {
+        a[0][c] = alt[c];
+        a[1][c] = planes == 2u ? alt[PILEUP_ALT + c] : 0ull;
+    }
+    *n = vs_pileup_call_slot(ref, d, a, min_alt_count, min_alt_frac, min_alt_strand, 0ull, &out[0][0]);
+    return VS_OK;
+}
+
+extern "C" int vs_pileup_call(vs_ctx *ctx, const uint32_t *d_first, uint64_t n_slots, uint32_t planes, const uint64_t *d_depth, const uint64_t *d_alt,
+                              uint64_t min_alt_count, double min_alt_frac, uint64_t min_alt_strand, uint64_t *d_out, uint64_t cap, uint64_t *n) {
+    if (!ctx || !n || !d_first || (n_slots && (!d_depth || !d_alt)) || (cap && !d_out)) return VS_E_ARG;
+    if (!vs_pileup_call_args_ok(planes, min_alt_frac, min_alt_strand))
+        return vs_fail(ctx, VS_E_ARG, "vs_pileup_call: one or two planes, a fraction from 0 up, and a strand threshold with two planes only");
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_pileup_call: build an index first (vs_index_build)");
+    if (n_slots >= (1ull << 32)) return vs_fail(ctx, VS_E_RANGE, "vs_pileup_call: %llu slots", (unsigned long long)n_slots);
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    *n = 0;
+    if (!n_slots) {
+        VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return VS_OK;
+    }
+    const VsIndexDev &idx = ctx->idx;
+    const uint64_t nb = (n_slots + 2047u) / 2048u;
+    VS_HIP(ctx, ctx->d_cover_scan.reserve(sizeof(uint32_t) * n_slots));
+    VS_HIP(ctx, ctx->d_cover_tmp.reserve(sizeof(uint64_t) * (nb + 2u)));
+    uint64_t *d_tmp = ctx->d_cover_tmp.as<uint64_t>(), *d_total = d_tmp + nb + 1u;
+    PileupCallParams P;
+    P.first = d_first;
+    P.meta = idx.meta;
+    P.fwd_words = idx.fwd_words;
+    P.depth = (const unsigned long long *)d_depth;
+    P.alt = (const unsigned long long *)d_alt;
+    P.count = ctx->d_cover_scan.as<uint32_t>();
+    P.out = (unsigned long long *)d_out;
+    P.n_slots = n_slots;
+    P.min_alt_count = min_alt_count;
+    P.min_alt_strand = min_alt_strand;
+    P.min_alt_frac = min_alt_frac;
+    P.n_nodes = idx.n_nodes;
+    P.planes = planes;
+    const dim3 grid((unsigned)((n_slots + PILEUP_CALL_TPB - 1u) / PILEUP_CALL_TPB));
+    hipLaunchKernelGGL(k_pileup_call_count, grid, dim3(PILEUP_CALL_TPB), 0, ctx->stream, P);
+    VS_HIP(ctx, hipGetLastError());
+    if (int rc = vs_scan_u32(ctx, P.count, P.count, n_slots, d_tmp, d_total)) return rc;
+    uint64_t total = 0;
+    VS_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n = total;
+    if (total >= (1ull << 32))  // (a place is a 32-bit word of the scan)
+        return vs_fail(ctx, VS_E_RANGE, "vs_pileup_call: %llu records, and a record number has 32 bits: raise the thresholds", (unsigned long long)total);
+    if (!total || cap < total) return VS_OK;  // nothing to write, or no room: the caller allocates *n records and calls again
+    hipLaunchKernelGGL(k_pileup_call_write, grid, dim3(PILEUP_CALL_TPB), 0, ctx->stream, P);
+    VS_HIP(ctx, hipGetLastError());
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VS_OK;
+}

@@ -19,7 +19,8 @@
 // position of a strand there is one diagonal per read offset, so one end has at most len_e alignments per strand covering a
 // position, and two strands: it adds at most 2 * len_e to one slot.  A block of n_ends ends of at most max_len bases weighs
 // n_ends * 2 * max_len, and a fold is due BEFORE a block whose weight, added to the weight pending since the last fold, could
-// reach the bound.
+// reach the bound.  The stranded pileup (vs_node_pileup_strands) keeps the two strands in two difference arrays and folds by
+// this same plan: one end adds at most len_e to a slot of ONE plane, below the 2 * len_e assumed here.
 #ifndef VS_PILEUP_PLAN_H
 #define VS_PILEUP_PLAN_H
 #include <stdint.h>

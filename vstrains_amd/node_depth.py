@@ -27,6 +27,14 @@ the minor bases above the two thresholds as VCF 4.2.
 
     ... --site-pairs FILE[.gz] [--sites VCF[.gz]] [--site-pairs-max-span D]
 
+    ... --strands [--min-alt-strand-count S]
+
+With ``--strands`` the pileup keeps the alignments on a segment's forward text and those on its reverse complement apart
+(``pe.StrandPileupCounter``, ``tests/strand_pileup_model.py``; still one read pass): ``--pileup`` gets the columns of both
+strands, and the records of ``--variants`` are found on the device (``vs_pileup_call``) and carry ``DP4`` -- reads of either
+strand with the reference and with the alternate base.  With ``S`` a record whose alternate base has fewer than ``S`` reads on
+a strand gets the FILTER ``strand``, every other one ``PASS``; no record is removed.
+
 With ``--site-pairs`` the pass also keeps together what ONE fragment -- the two mates of a pair -- carries at a list of sites
 (``pe.SitePairCounter``, ``tests/site_pairs_model.py``) and writes, for every two sites of one segment at most ``D`` positions
 apart, how many fragments carry which two bases: which minor bases travel together.  The sites are the CHROM / POS of
@@ -199,6 +207,82 @@ def write_vcf(path: str, ids, seqs, offsets, depth, alt, min_alt_count: int = 2,
             fh.write("%s\t%d\t.\t%s\t%s\t.\t.\tDP=%d;AD=%d;AF=%.6f\n" % (name, pos, ref, base, dp, ad, ad / dp))
 
 
+STRAND_PILEUP_COLUMNS = ("segment", "pos", "ref", "A+", "C+", "G+", "T+", "other+", "A-", "C-", "G-", "T-", "other-")
+BASES = "ACGT"
+
+
+def strand_pileup_counts(seqs, offsets, depth, alt):
+    """-> int64 [P, 2, 5]: ``pileup_counts`` per plane (``pe.StrandPileupCounter.result``: depth [P, 2], alt [P, 2, 5])."""
+    import numpy as np
+
+    depth, alt = np.asarray(depth, dtype=np.int64).reshape(-1, 2), np.asarray(alt, dtype=np.int64).reshape(-1, 2, 5)
+    return np.stack([pileup_counts(seqs, offsets, depth[:, t], alt[:, t]) for t in range(2)], axis=1)
+
+
+def write_strand_pileup(path: str, ids, seqs, offsets, depth, alt) -> None:
+    """``write_pileup`` with the columns of ``STRAND_PILEUP_COLUMNS``: ``+`` the reads laid along the segment's forward text,
+    ``-`` those along its reverse complement, every base as it reads on the forward strand."""
+    counts = strand_pileup_counts(seqs, offsets, depth, alt).reshape(-1, 10)
+    with _open_text(path) as fh:
+        fh.write("\t".join(STRAND_PILEUP_COLUMNS) + "\n")
+        for n, name in enumerate(ids):
+            a, b = int(offsets[n]), int(offsets[n + 1])
+            seq = seqs[n]
+            fh.write("".join("%s\t%d\t%s\t%s\n" % (name, p + 1, seq[p], "\t".join(str(v) for v in counts[a + p].tolist())) for p in range(b - a)))
+
+
+def call_host(seqs, offsets, depth, alt, min_alt_count: int = 2, min_alt_frac: float = 0.01, min_alt_strand: int = 0):
+    """What ``pe.StrandPileupCounter.call`` (depth [P, 2], alt [P, 2, 5]) or ``pe.PileupCounter.call`` (depth [P], alt [P, 5])
+    gives, made on the host from the tables of ``result()``, position by position through the rule the device runs
+    (``pe.pileup_call_host``): for small tables and tests; no device is needed.  A position whose base is not one of ACGT has
+    no records."""
+    import numpy as np
+
+    from . import pe as host
+
+    depth = np.asarray(depth, dtype=np.int64)
+    planes = 2 if depth.ndim == 2 else 1
+    depth, alt = depth.reshape(-1, planes), np.asarray(alt, dtype=np.int64).reshape(-1, planes, 5)
+    rows = []
+    for n, seq in enumerate(seqs):
+        a, b = int(offsets[n]), int(offsets[n + 1])
+        for p in range(b - a):
+            if seq[p] in BASES:
+                rows += [(n, p) + r for r in host.pileup_call_host(BASES.index(seq[p]), depth[a + p], alt[a + p], min_alt_count, min_alt_frac, min_alt_strand)]
+    got = np.array(rows, dtype=np.int64).reshape(-1, 10)
+    return got[:, 0], got[:, 1], got[:, 3], got[:, 4], got[:, 5], got[:, 6:10], got[:, 2].astype(bool)
+
+
+def strand_records(ids, called, min_alt_strand: int = 0):
+    """(segment, 1-based pos, ref, alt base, DP, AD, (ref_f, ref_r, alt_f, alt_r), FILTER) of every record a counter's
+    ``call()`` found, in its order; FILTER: ``.`` without a strand threshold, else ``PASS`` or ``strand``."""
+    seg, pos0, ref, alt, dp, dp4, fail = called
+    return [(ids[int(n)], int(p) + 1, BASES[int(r)], BASES[int(b)], int(d), int(q[2] + q[3]), tuple(int(v) for v in q),
+             "." if min_alt_strand < 1 else ("strand" if f else "PASS"))
+            for n, p, r, b, d, q, f in zip(seg, pos0, ref, alt, dp, dp4, fail)]
+
+
+def write_strand_vcf(path: str, ids, seqs, offsets, called, min_alt_strand: int = 0) -> None:
+    """``write_vcf`` from the records of ``pe.StrandPileupCounter.call``: INFO gains ``DP4``; with a strand threshold the
+    header gains the FILTER ``strand`` and every record says ``PASS`` or ``strand``, else FILTER stays ``.``.  With
+    ``;DP4=...`` and the FILTER value dropped the records are ``write_vcf``'s, byte for byte."""
+    with _open_text(path) as fh:
+        fh.write("##fileformat=VCFv4.2\n##source=%s\n" % VCF_SOURCE)
+        for n, name in enumerate(ids):
+            if offsets[n + 1] > offsets[n]:
+                fh.write("##contig=<ID=%s,length=%d>\n" % (name, len(seqs[n])))
+        fh.write('##INFO=<ID=DP,Number=1,Type=Integer,Description="Reads carrying A, C, G or T at the position">\n'
+                 '##INFO=<ID=AD,Number=1,Type=Integer,Description="Reads carrying the alternate base">\n'
+                 '##INFO=<ID=AF,Number=1,Type=Float,Description="AD / DP">\n'
+                 '##INFO=<ID=DP4,Number=4,Type=Integer,Description="Reads along the forward text with the reference base, along the reverse '
+                 'complement with it, along the forward text with the alternate base, along the reverse complement with it">\n')
+        if min_alt_strand >= 1:
+            fh.write('##FILTER=<ID=strand,Description="Fewer than %d reads carry the alternate base on one of the two strands">\n' % min_alt_strand)
+        fh.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
+        for name, pos, ref, base, dp, ad, dp4, flt in strand_records(ids, called, min_alt_strand):
+            fh.write("%s\t%d\t.\t%s\t%s\t.\t%s\tDP=%d;AD=%d;AF=%.6f;DP4=%d,%d,%d,%d\n" % ((name, pos, ref, base, flt, dp, ad, ad / dp) + dp4))
+
+
 def pileup_refusal(args):
     """None, or why the pileup's flags cannot hold, said before a device is opened."""
     asked = args.pileup is not None or args.variants is not None
@@ -212,6 +296,13 @@ def pileup_refusal(args):
         return "--pileup-max-mismatch, --min-alt-count and --min-alt-frac belong to --pileup / --variants: give one of them"
     if args.variants is None and (args.min_alt_count is not None or args.min_alt_frac is not None):
         return "--min-alt-count and --min-alt-frac select the records of --variants: give it"
+    strands, strand_count = getattr(args, "strands", False), getattr(args, "min_alt_strand_count", None)
+    if strands and not asked:
+        return "--strands keeps the strands of the pileup apart: give --pileup or --variants with it"
+    if strand_count is not None and not (strands and args.variants is not None):
+        return "--min-alt-strand-count filters the records of --variants by strand: give --strands and --variants with it"
+    if strand_count is not None and strand_count < 1:
+        return "--min-alt-strand-count %d: a count from 1 up is needed" % strand_count
     return None
 
 
@@ -351,7 +442,7 @@ def refuse_ranks(world: int) -> None:
 
 
 def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
-               count_singles: bool = False, quiet: bool = False, profile: bool = False, pileup=None, site_pairs=None):
+               count_singles: bool = False, quiet: bool = False, profile: bool = False, pileup=None, site_pairs=None, strands=None):
     """Index the segments of ``gfa`` and count every end the chosen input delivers (the input dispatch of
     ``pe_inference.count_links``, one process only).  -> (segment ids in file order, KC int64 in file order, ends counted).
     Replaces the context's index; the context stops keeping masks when the pass is over, so a PE count may follow on it.
@@ -360,7 +451,9 @@ def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: b
     a mismatch budget; a ``pe.PileupCounter`` then takes every block as well and one more value follows at the end:
     (segment sequences, offsets, depth, alt, (alignments, rejected)).  Without it no such counter is built.  ``site_pairs``:
     (sites, mismatch budget, span); a ``pe.SitePairCounter`` then takes every block as well and its ``result()`` with the five
-    tallies behind it follows as the very last value."""
+    tallies behind it follows as the very last value.  ``strands``: ``None``, or (min_alt_count, min_alt_frac, min_alt_strand)
+    beside ``pileup``: a ``pe.StrandPileupCounter`` takes the ``PileupCounter``'s place, depth and alt of the pileup's value have
+    its plane axis, and what its ``call()`` found on the device with these thresholds follows as that value's sixth member."""
     from . import pe as host
     from . import pe_inference
 
@@ -370,7 +463,9 @@ def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: b
     ids, seqs = host.read_gfa_segments(gfa)
     ctx.build_index(seqs, kmer_size)
     counter = host.CoverCounter(ctx) if profile else host.DepthCounter(ctx)  # (the blocks built from here on keep their masks)
-    piles = host.PileupCounter(ctx, max_mismatch=pileup) if pileup is not None else None
+    if strands is not None and pileup is None:
+        raise ValueError("the strands are those of the pileup: give its mismatch budget")
+    piles = None if pileup is None else (host.PileupCounter if strands is None else host.StrandPileupCounter)(ctx, max_mismatch=pileup)
     linked = host.SitePairCounter(ctx, site_pairs[0], max_mismatch=site_pairs[1], max_span=site_pairs[2]) if site_pairs is not None else None
     fed = counter if piles is None else _Both(counter, piles)
     try:
@@ -379,7 +474,7 @@ def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: b
         ctx.sync()
     finally:
         ctx.keep_masks(False)
-    piled = () if piles is None else ((seqs,) + piles.result() + (piles.tallies(),),)
+    piled = () if piles is None else ((seqs,) + piles.result() + (piles.tallies(),) + (() if strands is None else (piles.call(*strands),)),)
     if linked is not None:
         piled += (linked.result() + (linked.tallies(),),)
     if profile:
@@ -448,6 +543,12 @@ def build_parser():
                    help="non-agreeing positions an alignment may hold in its overlap [default: 8]")
     p.add_argument("--min-alt-count", dest="min_alt_count", type=int, default=None, metavar="C", help="--variants: records need AD >= C [default: 2]")
     p.add_argument("--min-alt-frac", dest="min_alt_frac", type=float, default=None, metavar="F", help="--variants: records need AD >= F * DP [default: 0.01]")
+    p.add_argument("--strands", dest="strands", action="store_true", default=False,
+                   help="--pileup / --variants: keep the reads laid along a segment's forward text and along its reverse complement apart: the "
+                        "pileup gets the columns A+ C+ G+ T+ other+ A- C- G- T- other-, the records are found on the device and carry DP4")
+    p.add_argument("--min-alt-strand-count", dest="min_alt_strand_count", type=int, default=None, metavar="S",
+                   help="--strands --variants: FILTER is PASS when at least S reads carry the alternate base on EACH strand, else strand; "
+                        "no record is removed [default: FILTER stays .]")
     p.add_argument("--site-pairs", dest="site_pairs", type=str, default=None, metavar="FILE",
                    help="also write which bases travel together on one read pair at pairs of sites of one segment, as a TSV (segment, pos_a, pos_b, "
                         "base_a, base_b, count; positions 1-based; non-zero counts only; .gz: through gzip).  The sites: --sites, or the records "
@@ -498,11 +599,14 @@ def main(argv=None) -> int:
             print("node_depth: --sites: %s" % e, file=sys.stderr)
             return 1
     ctx = host.Context(args.device)
+    min_count, min_frac = 2 if args.min_alt_count is None else args.min_alt_count, 0.01 if args.min_alt_frac is None else args.min_alt_frac
+    strand_count = 0 if args.min_alt_strand_count is None else args.min_alt_strand_count
     profiled = args.profile is not None or args.profile_summary is not None or args.depth_stat is not None
     piled = args.pileup is not None or args.variants is not None
     got = depth_pass(ctx, args.gfa, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=interleaved,
                      check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True, profile=profiled,
-                     pileup=budget if piled else None, **(dict(site_pairs=(sites, budget, span)) if sites is not None else {}))
+                     pileup=budget if piled else None, **(dict(site_pairs=(sites, budget, span)) if sites is not None else {}),
+                     **(dict(strands=(min_count, min_frac, strand_count)) if args.strands else {}))
     ids, kc, ends = got[:3]
     linked = None
     if sites is not None:
@@ -517,15 +621,16 @@ def main(argv=None) -> int:
         if args.profile_summary is not None:
             write_summary(args.profile_summary, ids, lengths, offsets, cov)
     if piled:
-        seqs, p_offsets, p_depth, p_alt, _ = got[-1]
+        seqs, p_offsets, p_depth, p_alt = got[-1][:4]
+        called = got[-1][5] if args.strands else None
         if args.pileup is not None:
-            write_pileup(args.pileup, ids, seqs, p_offsets, p_depth, p_alt)
-        if args.variants is not None:
-            write_vcf(args.variants, ids, seqs, p_offsets, p_depth, p_alt, 2 if args.min_alt_count is None else args.min_alt_count,
-                      0.01 if args.min_alt_frac is None else args.min_alt_frac)
+            (write_strand_pileup if args.strands else write_pileup)(args.pileup, ids, seqs, p_offsets, p_depth, p_alt)
+        if args.variants is not None and args.strands:
+            write_strand_vcf(args.variants, ids, seqs, p_offsets, called, strand_count)
+        elif args.variants is not None:
+            write_vcf(args.variants, ids, seqs, p_offsets, p_depth, p_alt, min_count, min_frac)
         if args.site_pairs is not None and sites is None:  # the records just written are the sites: the reads once more
-            records = variant_records(ids, seqs, p_offsets, p_depth, p_alt, 2 if args.min_alt_count is None else args.min_alt_count,
-                                      0.01 if args.min_alt_frac is None else args.min_alt_frac)
+            records = strand_records(ids, called) if args.strands else variant_records(ids, seqs, p_offsets, p_depth, p_alt, min_count, min_frac)
             linked = site_pairs_pass(ctx, record_sites(ids, records), args.fwd, args.rve, budget, span, bam_by_name=args.bam_by_name,
                                      interleaved=interleaved, check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True)
     if linked is not None:

@@ -1522,6 +1522,25 @@ class Context:
         nat.check(self._h, nat.lib().vs_node_site_pairs(self._h, reads._h, C.c_void_p(first_ptr), C.c_void_p(site_slot_ptr), n_sites,
                                                         C.c_void_p(row_first_ptr), C.c_void_p(cells_ptr), max_mismatch, C.c_void_p(tally_ptr)))
 
+    def node_pileup_strands(self, reads: ReadBlock, first_ptr: int, n_slots: int, diff_ptr: int, alt_ptr: int, max_mismatch: int, tally_ptr: int):
+        """One block through the stranded pileup pass (``vs_node_pileup_strands``): as ``node_pileup``, the alignments on the
+        segment's forward text (plane 0) and on its reverse complement (plane 1) kept apart: ``diff_ptr``: uint32
+        ``[2, n_slots]``, plane-major, every plane a difference array of its own; ``alt_ptr``: uint64 ``[n_slots, 2, 5]``;
+        ``n_slots``: what ``pileup_layout`` gave.  Blocks must have been built after ``keep_masks(True)``."""
+        nat.check(self._h, nat.lib().vs_node_pileup_strands(self._h, reads._h, C.c_void_p(first_ptr), n_slots, C.c_void_p(diff_ptr), C.c_void_p(alt_ptr),
+                                                            max_mismatch, C.c_void_p(tally_ptr)))
+
+    def pileup_call(self, first_ptr: int, n_slots: int, planes: int, depth_ptr: int, alt_ptr: int, min_alt_count: int, min_alt_frac: float,
+                    min_alt_strand: int = 0, out_ptr: int = 0, cap: int = 0) -> int:
+        """The records of a folded pileup, found on the device (``vs_pileup_call``): ``planes`` 1 -- ``depth_ptr`` uint64
+        ``[n_slots]``, ``alt_ptr`` ``[n_slots, 5]``; 2 -- ``[2, n_slots]`` and ``[n_slots, 2, 5]``.  -> the exact number of
+        records; they are written to ``out_ptr`` (device, ``[cap, 6]`` uint64: slot << 5 | strand_fail << 4 | ref << 2 | alt,
+        DP, ref_f, ref_r, alt_f, alt_r; ascending by slot, then alt base) only if ``cap`` holds them all.  Synchronises."""
+        n = C.c_uint64(0)
+        nat.check(self._h, nat.lib().vs_pileup_call(self._h, C.c_void_p(first_ptr), n_slots, planes, C.c_void_p(depth_ptr), C.c_void_p(alt_ptr),
+                                                    min_alt_count, min_alt_frac, min_alt_strand, C.c_void_p(out_ptr) if out_ptr else None, cap, C.byref(n)))
+        return int(n.value)
+
     def contig_mems(self, reads: ReadBlock) -> np.ndarray:
         """Every maximal exact match of k + 1 bases or more between a contig of the block and a strand of a segment
         (``vs_contig_mems``): uint32 [n, 5] -- contig, first base in the contig, segment | strand << 31, first base in that
@@ -2080,6 +2099,55 @@ def pileup_plan(n_nodes: int, ksize: int, n_ends: int, max_len: int, n_cu: int =
                 lds_bytes=int(a[6]), threads=int(a[7]))
 
 
+def pileup_call_host(ref: int, depth, alt, min_alt_count: int = 2, min_alt_frac: float = 0.01, min_alt_strand: int = 0) -> List[Tuple[int, ...]]:
+    """The records of ONE position by the rule the device caller runs (``vs_pileup_call_host``, a pure host function: no device
+    is needed).  ``ref``: the segment's base code 0..3; ``depth``: one count per plane (1 or 2 of them); ``alt``: ``[planes][5]``.
+    -> up to three ``(strand_fail, ref, alt, DP, ref_f, ref_r, alt_f, alt_r)``, in ACGT order of the alt base."""
+    d = np.ascontiguousarray(depth, dtype=np.uint64).reshape(-1)
+    a = np.ascontiguousarray(alt, dtype=np.uint64).reshape(-1)
+    if a.size != 5 * d.size:
+        raise ValueError("pileup_call_host: five alt columns per plane are needed")
+    out = np.zeros((3, 6), dtype=np.uint64)
+    n = C.c_uint32(0)
+    rc = nat.lib().vs_pileup_call_host(ref, d.size, d.ctypes.data, a.ctypes.data, min_alt_count, min_alt_frac, min_alt_strand, out.ctypes.data, C.byref(n))
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_pileup_call_host refuses base %r, %d planes, a fraction of %r, a strand threshold of %r" % (ref, d.size, min_alt_frac, min_alt_strand))
+    return [(int(r[0]) >> 4 & 1, int(r[0]) >> 2 & 3, int(r[0]) & 3) + tuple(int(v) for v in r[1:]) for r in out[:n.value]]
+
+
+def _call_on_device(counter, planes: int, min_alt_count: int, min_alt_frac: float, min_alt_strand: int):
+    """``call()`` of both pileup counters: the device caller on the counter's folded tables, and the records -- nothing else
+    leaves the device -- mapped from slots to the GFA's order and sorted."""
+    torch = counter.torch
+    if not 0 <= int(min_alt_count) < 2 ** 64 or not 0 <= int(min_alt_strand) < 2 ** 64:
+        raise ValueError("call: counts from 0 up are needed")
+    if counter.pending:
+        counter.fold()
+    args = (counter.first.data_ptr(), counter.slots, planes, counter.depth.data_ptr(), counter.alt.data_ptr(), int(min_alt_count), float(min_alt_frac),
+            int(min_alt_strand))
+    with torch.cuda.device(counter.device):
+        counter.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        n = counter.ctx.pileup_call(*args)
+        out = torch.zeros((max(n, 1), 6), dtype=torch.int64, device=counter.device)
+        if n and counter.ctx.pileup_call(*args, out_ptr=out.data_ptr(), cap=n) != n:
+            raise RuntimeError("vs_pileup_call: the number of records changed between two calls on the same tables")
+        rec = out[:n].cpu().numpy()
+    first = counter.first.cpu().numpy().view(np.uint32).astype(np.int64)
+    head = rec[:, 0]
+    slot = head >> 5
+    rank = np.searchsorted(first, slot, side="right") - 1  # (the segment that holds the slot: one without slots holds none)
+    pos0 = slot - first[rank]
+    seg = rank
+    if counter.node_rank is not None:
+        order = np.empty(counter.n, dtype=np.int64)
+        order[np.asarray(counter.node_rank, dtype=np.int64)] = np.arange(counter.n, dtype=np.int64)
+        seg = order[rank]
+    alt = head & 3
+    by = np.lexsort((alt, pos0, seg))
+    return (seg[by].astype(np.int64), pos0[by].astype(np.int64), (head >> 2 & 3)[by].astype(np.int64), alt[by].astype(np.int64),
+            rec[by, 1].astype(np.int64), rec[by, 2:6].astype(np.int64).reshape(n, 4), (head >> 4 & 1)[by].astype(bool))
+
+
 class PileupCounter:
     """The base pileup of every segment, counted from the reads on one device (``vs_node_pileup``): every read end is laid
     along the diagonal of each exact anchor of ``k + 1`` bases across its mismatches; an alignment with at most
@@ -2158,6 +2226,108 @@ class PileupCounter:
         total = int(offsets[-1])
         at = np.repeat(start - offsets[:-1], positions) + np.arange(total, dtype=np.int64)
         return offsets, depth[at].astype(np.int64), alt[at].astype(np.int64).reshape(total, 5)
+
+    def call(self, min_alt_count: int = 2, min_alt_frac: float = 0.01):
+        """The records of ``--variants`` found on the device (``vs_pileup_call`` with one plane): what
+        ``node_depth.variant_records`` makes of ``result()``, without the tables leaving the device.  -> ``(seg, pos0, ref,
+        alt, dp, dp4 [R, 4], strand_fail)`` as ``StrandPileupCounter.call``; ``dp4[:, 1]`` and ``dp4[:, 3]`` are 0."""
+        return _call_on_device(self, 1, min_alt_count, min_alt_frac, 0)
+
+    def tallies(self):
+        """-> (alignments credited, alignments rejected for more than ``max_mismatch`` non-agreeing positions)."""
+        t = self.tally.cpu().numpy()
+        return int(t[0]), int(t[1])
+
+
+class StrandPileupCounter:
+    """The base pileup kept apart by strand, counted from the reads on one device (``vs_node_pileup_strands``): everything
+    ``PileupCounter`` counts, in two PLANES -- 0: the alignments that lay the end, as the ingest delivers it, along the
+    segment's forward text; 1: those along its reverse complement (``tests/strand_pileup_model.py``).  Summed over the planes
+    it is ``PileupCounter``'s result exactly.  Takes ``PileupCounter``'s place in the input dispatch of ``pe_inference``
+    (``add``, ``device``, ``single_stats``, ``ends_seen``; the context keeps the masks): one kernel per block.  Holds 8 + 16 +
+    80 = 104 bytes per slot (a slot per position and one per segment); the context holds 4 more per slot once a fold or a
+    ``call`` ran.  ``fold_bound``: ``pileup_plan``'s ``bound`` -- the plan is the unstranded one: a plane gets at most half
+    the weight it assumes."""
+
+    def __init__(self, ctx: Context, max_mismatch: int = 8, fold_bound: int = 2 ** 32, device: Optional[str] = None):
+        import torch
+
+        if not 0 <= int(max_mismatch) < 2 ** 32:
+            raise ValueError("a mismatch budget of %r: an integer from 0 up is needed" % (max_mismatch,))
+        self.torch = torch
+        self.ctx = ctx
+        self.device = torch.device(device or ("cuda:%d" % ctx.device))
+        self.n = ctx.n_nodes
+        self.ksize = ctx.ksize
+        self.max_mismatch = int(max_mismatch)
+        self.fold_bound = fold_bound
+        self.single_stats = torch.zeros(3, dtype=torch.int64, device=self.device)  # (what the dispatch tallies of a PeCounter: stays zero)
+        self.ends_seen = 0  # ends the blocks delivered (the absent second ends of singles blocks aside)
+        self.folds = 0      # folds of BOTH planes
+        self.pending = 0    # pileup_plan's weight of the blocks since the last fold
+        self.node_rank = getattr(ctx, "node_rank", None)  # (kept here: a later build_index cannot change how the slots are read)
+        with torch.cuda.device(self.device):
+            ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.first = torch.zeros(self.n + 1, dtype=torch.int32, device=self.device)  # (uint32 words)
+            self.slots = ctx.pileup_layout(self.first.data_ptr())
+            self.diff = torch.zeros((2, max(self.slots, 1)), dtype=torch.int32, device=self.device)  # (uint32 words, wrap-around adds; plane-major)
+            self.depth = torch.zeros((2, max(self.slots, 1)), dtype=torch.int64, device=self.device)
+            self.alt = torch.zeros((max(self.slots, 1), 2, 5), dtype=torch.int64, device=self.device)
+            self.tally = torch.zeros(2, dtype=torch.int64, device=self.device)
+        ctx.keep_masks(True)
+
+    def fold(self):
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            for t in range(2):  # (every plane is a difference array of its own: S slots each)
+                self.ctx.cover_fold(self.diff.data_ptr() + 4 * t * self.slots, self.depth.data_ptr() + 8 * t * self.slots, self.slots)
+        self.pending = 0
+        self.folds += 1
+
+    def add(self, reads: ReadBlock):
+        torch = self.torch
+        info = reads.info
+        n_ends = info["ends"]
+        self.ends_seen += n_ends // 2 if reads.unpaired else n_ends
+        plan = pileup_plan(self.n, self.ksize, n_ends, info["max_len"], pending=self.pending, bound=self.fold_bound)
+        if plan["fold_first"]:
+            self.fold()
+        self.pending = plan["pending"]
+        if not self.slots:
+            return
+        with torch.cuda.device(self.device):
+            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.ctx.node_pileup_strands(reads, self.first.data_ptr(), self.slots, self.diff.data_ptr(), self.alt.data_ptr(), self.max_mismatch,
+                                         self.tally.data_ptr())
+
+    def result(self):
+        """-> (offsets int64 [N + 1], depth int64 [P, 2], alt int64 [P, 2, 5]): ``PileupCounter.result`` with a plane axis
+        behind the position's: rows ``offsets[n] : offsets[n + 1]`` are the positions of segment ``n`` in the GFA's order,
+        without sentinel slots."""
+        if self.pending:
+            self.fold()
+        first = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
+        depth = self.depth.cpu().numpy().reshape(2, -1)
+        alt = self.alt.cpu().numpy()
+        positions = np.maximum(first[1:] - first[:-1] - 1, 0)
+        start = first[:-1]
+        if self.node_rank is not None:
+            positions, start = positions[self.node_rank], start[self.node_rank]
+        offsets = np.zeros(self.n + 1, dtype=np.int64)
+        np.cumsum(positions, out=offsets[1:])
+        total = int(offsets[-1])
+        at = np.repeat(start - offsets[:-1], positions) + np.arange(total, dtype=np.int64)
+        return offsets, np.ascontiguousarray(depth[:, at].T).astype(np.int64).reshape(total, 2), alt[at].astype(np.int64).reshape(total, 2, 5)
+
+    def call(self, min_alt_count: int = 2, min_alt_frac: float = 0.01, min_alt_strand: int = 0):
+        """The records of ``--variants``, found on the device (``vs_pileup_call``): every (position, base other than the
+        segment's) with ``AD > 0``, ``AD >= min_alt_count`` and ``AD >= min_alt_frac * DP``, both summed over the planes.
+        -> ``(seg, pos0, ref, alt, dp, dp4 [R, 4], strand_fail)``: ``seg`` in the GFA's order, ``pos0`` 0-based, ``ref`` and
+        ``alt`` base codes (0..3 = ACGT), ``dp4`` = ref_f, ref_r, alt_f, alt_r; ``strand_fail``: ``min_alt_strand >= 1`` and
+        the alt base has fewer reads than that in a plane -- the record stays.  Sorted by segment, position, base.  int64 and
+        bool; only the records leave the device."""
+        return _call_on_device(self, 2, min_alt_count, min_alt_frac, min_alt_strand)
 
     def tallies(self):
         """-> (alignments credited, alignments rejected for more than ``max_mismatch`` non-agreeing positions)."""
