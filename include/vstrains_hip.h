@@ -1009,6 +1009,39 @@ int vs_pileup_call(vs_ctx *ctx, const uint32_t *d_first, uint64_t n_slots, uint3
 int vs_pileup_call_host(uint32_t ref, uint32_t planes, const uint64_t *depth, const uint64_t *alt, uint64_t min_alt_count, double min_alt_frac,
                         uint64_t min_alt_strand, uint64_t out[3][6], uint32_t *n);
 
+/* ---- insertions and deletions of the reads against the segments (additions to ABI 11 without a new number: nothing that
+ * exists changes) --  No counterpart in the reference.  With K = k + 1 and a maximum length G (1 <= G <= 32): R is a read end as
+ * the ingest delivers it, T a strand t of a segment n with len_n >= K, (a, qa, len) a maximal exact match of R with T of at
+ * least K agreeing bases -- the match the base pileup is handed, with its guard qa + len <= len_n.  The match is TESTED when
+ * a > 0 and qa > 0: its left neighbour lies inside both texts and does not agree.  The candidates are tried in the order
+ * deletion 1, insertion 1, deletion 2, ... deletion G, insertion G; the first that holds is the event, a match yields at most
+ * one.  DELETION of L: a >= K and qa >= L + K, and R[a-K .. a) agrees with T[qa-L-K .. qa-L) (the pileup's rule: a byte
+ * outside ACGT does not agree); the strand's bases [qa-L, qa) are missing from the read.  INSERTION of L: a >= L + K and
+ * qa >= K, and R[a-L-K .. a-L) agrees with T[qa-K .. qa); I = R[a-L .. a) stands before strand position qa; if I holds a byte
+ * outside ACGT the event is dropped and tallied and no further candidate is tried.  NORMALISATION, F the segment's forward
+ * text: on strand 1 a deletion of [s, s+L) is forward [len_n-s-L, len_n-s) and an insertion of I before s is revcomp(I) before
+ * len_n - s; then a deletion (u, L) moves to u - 1 while u > 0 and F[u-1] == F[u+L-1], an insertion (u, I) becomes (u - 1,
+ * F[u-1] + I[:-1]) while u > 0 and F[u-1] == I[-1].  The PLANE of an event is t.  An event is two uint64: w0 = slot << 8 |
+ * plane << 7 | kind << 6 | (L - 1), slot = first[n] + u on vs_pileup_layout's layout, kind 0 a deletion, 1 an insertion; w1 =
+ * the inserted bases on the forward strand, 2 bits each, the first lowest, 0 for a deletion.  Per end and per strand: two mates
+ * over one event are two events.  tests/indel_model.py states all of it; csrc/vs_indel_core.h is the code of one match.
+ *   vs_node_indels     : one block through k_node_indels on the context's current index, launched by vs_pileup_plan's plan.
+ *                        d_first: what vs_pileup_layout wrote; max_len: G; d_events: DEVICE, cap x 2 uint64, in no order.  *n
+ *                        (host) = the exact number of events of the block; with *n > cap the buffer's content is undefined:
+ *                        call again with room for *n.  d_tally: DEVICE, four uint64, ADDED to only by a call that fit: matches
+ *                        tested, deletions, insertions, insertions dropped.  Synchronises the ctx stream (the addition to
+ *                        d_tally is enqueued behind it).  Blocks must have been built after vs_ctx_keep_masks(ctx, 1).
+ *                        VS_E_ARG: a NULL pointer, max_len outside 1..32; VS_E_RANGE as vs_node_pileup.
+ *   vs_indel_scan_host : host only, no device: the code a lane runs, on ONE match of a read (packed words, mask or NULL) with
+ *                        a strand (its packed words, and the segment's packed forward text), every array with three zero words
+ *                        behind its last.  out[0]: 0 not tested, 1 tested without an event, 2 an event, 3 dropped; out[1] =
+ *                        kind << 8 | L (2, 3); out[2] = u and out[3] = w1 (2).  VS_E_ARG: a NULL pointer, K == 0, G outside
+ *                        1..32, strand > 1, a >= rlen, qa >= tlen. */
+int vs_node_indels(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, uint32_t max_len, uint64_t *d_events, uint64_t cap, uint64_t *n,
+                   uint64_t *d_tally);
+int vs_indel_scan_host(const uint32_t *read_words, const uint32_t *read_mask, const uint32_t *strand_words, const uint32_t *fwd_words, uint32_t rlen,
+                       uint32_t tlen, uint32_t strand, uint32_t a, uint32_t qa, uint32_t K, uint32_t G, uint64_t out[4]);
+
 /* Testing aid (ABI 11): the two exclusive scans under the index build, the locus sort, every row_ptr and every member,
  * record and word offset, run alone on values the caller made up, launched exactly as their callers launch them (no kernel
  * of its own).  HOST pointers: in[n + guard] = the n values and behind them `guard` words of a sentinel the caller chose;

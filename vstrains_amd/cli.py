@@ -117,6 +117,9 @@ def build_parser():
     # with --depth-from-reads --depth-pileup: the pileup keeps the two strands apart and the two files are written in their stranded
     # form, the records found on the device and carrying DP4 (vstrains_amd.node_depth --pileup --variants --strands)
     p.add_argument("--depth-strands", dest="depth_strands", action="store_true", default=False, help=argparse.SUPPRESS)
+    # with --depth-from-reads --depth-pileup: the same read pass also finds the insertions and deletions of at most 16 bases that the read
+    # ends carry and writes them as gfa/graph_depth.indels.vcf (vstrains_amd.node_depth --indels)
+    p.add_argument("--depth-indels", dest="depth_indels", action="store_true", default=False, help=argparse.SUPPRESS)
     return p
 
 
@@ -168,6 +171,13 @@ def depth_strands_refusal(args):
     return None
 
 
+def depth_indels_refusal(args):
+    """None, or why ``--depth-indels`` cannot hold, said before anything is written: its depth is the pileup's."""
+    if getattr(args, "depth_indels", False) and not (args.depth_from_reads and args.depth_pileup):
+        return "--depth-indels measures its events against the pileup: give --depth-from-reads --depth-pileup with it"
+    return None
+
+
 def depth_site_pairs_refusal(args):
     """None, or why ``--depth-site-pairs`` cannot hold, said before anything is written: its sites are the pileup's records, and
     the reads are read once more for it."""
@@ -214,7 +224,11 @@ def depth_from_reads(args, logger, ctx):
     got = node_depth.depth_pass(ctx, args.gfa_file, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=args.interleaved,
                                 check_names=args.check_names, single=args.single, count_singles=args.count_singles, quiet=True,
                                 profile=args.depth_profile, pileup=8 if args.depth_pileup else None,
-                                **(dict(strands=(2, 0.01, 0)) if args.depth_strands else {}))
+                                **(dict(strands=(2, 0.01, 0)) if args.depth_strands else {}),
+                                **(dict(indels=16) if args.depth_indels else {}))
+    gapped = None
+    if args.depth_indels:
+        got, gapped = got[:-1], got[-1]
     ids, kc, ends = got[:3]
     out = args.output_dir + "/gfa/graph_depth.gfa"
     with open(out, "wb") as fh:
@@ -234,6 +248,11 @@ def depth_from_reads(args, logger, ctx):
             node_depth.write_vcf(args.output_dir + "/gfa/graph_depth.vcf", ids, seqs, p_offsets, p_depth, p_alt)
         logger.info("base pileup of every position: {0}/gfa/graph_depth.pileup.tsv, minor bases: {0}/gfa/graph_depth.vcf ({1} alignments, {2} rejected)"
                     .format(args.output_dir, credited, rejected))
+    if gapped is not None:
+        node_depth.write_indel_vcf(args.output_dir + "/gfa/graph_depth.indels.vcf", ids, seqs, p_offsets,
+                                   node_depth.indel_records(ids, seqs, gapped[0], p_offsets, p_depth, p_alt))
+        logger.info("insertions and deletions of the read ends: {0}/gfa/graph_depth.indels.vcf ({1})"
+                    .format(args.output_dir, ", ".join("%d %s" % (v, what) for v, what in zip(gapped[1], node_depth.INDEL_TALLIES))))
     if args.depth_site_pairs:
         records = node_depth.strand_records(ids, got[-1][5]) if args.depth_strands else node_depth.variant_records(ids, seqs, p_offsets, p_depth, p_alt)
         linked = node_depth.site_pairs_pass(ctx, node_depth.record_sites(ids, records), args.fwd, args.rve, bam_by_name=args.bam_by_name,
@@ -294,7 +313,7 @@ def main(argv=None, backend=None):
     args.single = pe_inference.unpaired_input(args.single, args.count_singles, pe_inference._rank_world()[1], args.interleaved,
                                               pe_text_from=args.pe_text_from, check_names=args.check_names, bam_by_name=args.bam_by_name,
                                               fwd=args.fwd, rve=args.rve)
-    why = depth_profile_refusal(args) or depth_pileup_refusal(args) or depth_strands_refusal(args) or depth_site_pairs_refusal(args)
+    why = depth_profile_refusal(args) or depth_pileup_refusal(args) or depth_strands_refusal(args) or depth_indels_refusal(args) or depth_site_pairs_refusal(args)
     if why is not None:
         raise ValueError(why)
     if args.depth_from_reads:

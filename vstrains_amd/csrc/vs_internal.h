@@ -123,6 +123,8 @@ struct vs_ctx {
     uint64_t mems_info[4] = {0, 0, 0, 0};  // records, launches of k_contig_mems, probes, capacity in records before the pass
     // vs_cover_layout / vs_cover_fold: the exclusive scan of the difference array (one word per slot) and the scans' block sums
     VsDevBuf d_cover_scan, d_cover_tmp;
+    // vs_node_indels: the record count of the pass and its four tallies, added to the caller's only when the pass fit
+    VsDevBuf d_indel_tmp;
     hipStream_t stream = nullptr;
     std::string err;
     FqStage fq_stage[2];

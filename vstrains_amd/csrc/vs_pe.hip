@@ -4399,3 +4399,214 @@ extern "C" int vs_pileup_call(vs_ctx *ctx, const uint32_t *d_first, uint64_t n_s
     VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VS_OK;
 }
+
+// ---- insertions and deletions of a read end against a strand of a segment (vs_node_indels) ---------------------------------
+// What the pileup rejects on both diagonals: an end that carries an insertion or a deletion of at most G bases.  The end
+// batches, the probe grid, the table probe, the posting deal and vs_extend under the mask are k_node_pileup's, and so are the
+// workgroup and the LDS; there is no owner walk, no count and no fold.  The lane that holds a match (a, qa, len) whose left
+// neighbour lies inside both texts -- and so does not agree -- looks LEFT of that breakpoint on the shifted diagonals
+// (vs_indel_core.h: deletion 1, insertion 1, ... insertion G; K agreeing bases make the flank), and on an event mirrors it to
+// the segment's forward text and moves it left as far as it goes.  An event is two uint64: slot << 8 | plane << 7 | kind << 6 |
+// (L - 1), and the inserted bases on the forward strand.  Records are claimed per wavefront: one ballot, one atomic on the
+// record count by the first lane that has one, as k_contig_mems claims its records; the count goes on beyond the buffer's
+// capacity while the stores stop at it.  The four tallies go through vs_pileup_tally into the context's scratch.
+#include "vs_indel_core.h"
+
+struct IndelParams {
+    VsIndexDev idx;
+    VsReadsDev rd;
+    const uint32_t *first;      // [n_nodes + 1] the first slot of every segment (vs_pileup_layout)
+    unsigned long long *out;    // [cap][2] events
+    unsigned long long cap;
+    unsigned long long *count;  // events found, stored or not
+    unsigned long long *tally;  // [4] matches tested, deletions, insertions, insertions dropped: of this pass
+    uint64_t ends_per_wg;
+    uint32_t max_len;           // G
+};
+
+__global__ void __launch_bounds__(PILEUP_TPB, 8)  // (as k_node_pileup)
+k_node_indels(IndelParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_mem[PILEUP_LDS_WORDS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t N = P.idx.n_nodes, w = P.idx.w, s = P.idx.s, K = P.idx.K;
+    uint32_t *s_head = s_mem;
+    uint32_t *sw = s_mem + PILEUP_HEAD_WORDS + wave * PILEUP_WAVE_WORDS;
+    uint32_t *s_np = sw, *s_cnt = sw + 65u, *s_pa = sw + 130u, *s_pb = sw + 194u, *s_pj = sw + 258u;
+    const uint64_t e_lo = (uint64_t)blockIdx.x * P.ends_per_wg;
+    const uint64_t e_hi = e_lo + P.ends_per_wg < P.rd.n_ends ? e_lo + P.ends_per_wg : P.rd.n_ends;
+    if (tid == 0u) s_head[0] = 0u;
+    __syncthreads();
+    for (;;) {
+        uint32_t b = 0u;
+        if (lane == 0u) b = atomicAdd(&s_head[0], 64u);
+        b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+        if (e_lo + b >= e_hi) break;
+        const uint64_t e0 = e_lo + b;
+        const uint32_t n_here = e_hi - e0 < 64u ? (uint32_t)(e_hi - e0) : 64u;
+        uint32_t np = 0u;
+        if (lane < n_here) {
+            const uint32_t meta = P.rd.meta[e0 + lane];
+            if (!((meta >> 24) & VS_FLAG_ABSENT)) np = vs_seed_probes(meta & VS_LEN_MASK, w, s);  // (0 for an end shorter than K)
+        }
+        s_np[lane + 1u] = vs_wave_scan_add(np);
+        if (lane == 0u) s_np[0] = 0u;
+        vs_wave_sync();
+        const uint32_t tp = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_np[64]);
+        for (uint32_t p0 = 0u; p0 < tp; p0 += 64u) {
+            // probes p0 .. p0 + 63 of the batch: one per lane
+            const uint32_t t = p0 + lane;
+            uint32_t c = 0u, pa = 0u, pb = 0u, pj = 0u;
+            if (t < tp) {
+                const uint32_t el = vs_upper_idx(s_np, 65u, t);  // the end that owns probe t: s_np[el] <= t < s_np[el + 1]
+                const uint64_t e = e0 + el;
+                const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                const uint32_t j = vs_seed_phase(rlen, w, s) + (t - s_np[el]) * s;
+                const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                if (!(mk && vs_seed_dirty(mk, rbase + j, w))) {
+                    uint32_t sr;
+                    const uint64_t key = vs_seed_key(P.rd.words, rbase + j, w, &sr);
+                    c = vs_probe(P.idx, key, sr, &pa, &pb);
+                }
+                pj = (el << 24) | j;  // (a read offset fits 24 bits: VS_LEN_MASK)
+            }
+            s_pa[lane] = pa;
+            s_pb[lane] = pb;
+            s_pj[lane] = pj;
+            s_cnt[lane + 1u] = vs_wave_scan_add(c);
+            if (lane == 0u) s_cnt[0] = 0u;
+            vs_wave_sync();
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[64]);
+            for (uint32_t q0 = 0u; q0 < total; q0 += 64u) {
+                // postings q0 .. q0 + 63 of these probes: one per lane
+                const uint32_t t2 = q0 + lane;
+                bool tested = false, dropped = false, found = false;
+                uint32_t kind = 0u;
+                unsigned long long w0 = 0ull, w1 = 0ull;
+                if (t2 < total) {
+                    const uint32_t pr = vs_upper_idx(s_cnt, 65u, t2);
+                    const uint32_t k2 = t2 - s_cnt[pr];
+                    const uint32_t qa0 = s_pa[pr], qb0 = s_pb[pr], ej = s_pj[pr];
+                    const uint32_t j = ej & VS_LEN_MASK;
+                    const uint64_t e = e0 + (ej >> 24);
+                    const uint32_t meta = P.rd.meta[e], rlen = meta & VS_LEN_MASK;
+                    const uint64_t rbase = (uint64_t)P.rd.woff[e] * 16u;
+                    const uint32_t *mk = vs_depth_mask(P.rd, meta);
+                    uint32_t nd, pos, opp;
+                    VsNodeMeta nm;
+                    if (s_cnt[pr + 1u] - s_cnt[pr] == 1u) {
+                        nd = qa0; pos = qb0 & 0x7FFFFFFFu; opp = qb0 >> 31;
+                        nm = P.idx.meta[nd];
+                    } else {
+                        const VsPosting po = vs_posting_unpack(P.idx.postings[qa0 + k2]);
+                        nd = po.node; pos = po.pos; opp = po.strand ^ (qb0 >> 31);
+                        nm.woff = po.woff; nm.len = po.len;
+                    }
+                    const uint32_t *tw = opp ? P.idx.rc_words : P.idx.fwd_words;
+                    const uint32_t q = opp ? nm.len - pos - w : pos;
+                    uint32_t a, qa, len;
+                    // (k >= 95: VS_SEED_VERIFIED is 0, the key only nominated the posting and the comparison starts at the seed's first base)
+                    if (nd < N && vs_extend(P.rd.words, rbase, rlen, tw, nm.woff * 16u, nm.len, j, q, VS_SEED_VERIFIED(w), s, K, mk, rbase, &a, &qa, &len) &&
+                        qa + len <= nm.len && a > 0u && qa > 0u) {  // (the pileup's guard; a left neighbour inside both texts)
+                        const uint64_t tbase = (uint64_t)nm.woff * 16u;
+                        uint32_t L = 0u;
+                        tested = true;
+                        const uint32_t st = vs_indel_find(P.rd.words, rbase, tw, tbase, mk, a, qa, K, P.max_len, &kind, &L);
+                        dropped = st == VS_INDEL_DROPPED;
+                        if (st == VS_INDEL_EVENT) {
+                            uint32_t u;
+                            uint64_t ins;
+                            // (an insertion has a >= L + K: the window starts inside the read)
+                            vs_indel_normalise(P.idx.fwd_words, tbase, nm.len, opp, kind, L, qa, kind == VS_INDEL_INS ? vs_pl_win(P.rd.words, rbase + a - L) : 0ull,
+                                               &u, &ins);
+                            found = true;
+                            w0 = ((unsigned long long)(P.first[nd] + u) << 8) | (unsigned long long)((opp << 7) | (kind << 6) | (L - 1u));
+                            w1 = ins;
+                        }
+                    }
+                }
+                const unsigned long long have = __ballot(found);
+                if (have) {
+                    const uint32_t leader = (uint32_t)__ffsll((long long)have) - 1u;
+                    unsigned long long base = 0ull;
+                    if (lane == leader) base = atomicAdd(P.count, (unsigned long long)__popcll(have));
+                    const uint32_t b_lo = (uint32_t)__shfl((int)(uint32_t)base, (int)leader), b_hi = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)leader);
+                    const unsigned long long at = (((unsigned long long)b_hi << 32) | b_lo) + (unsigned long long)__popcll(have & ((1ull << lane) - 1ull));
+                    if (found && at < P.cap) {
+                        P.out[2ull * at] = w0;
+                        P.out[2ull * at + 1ull] = w1;
+                    }
+                }
+                vs_pileup_tally(P.tally, tested, lane);
+                vs_pileup_tally(P.tally + 1, found && kind == VS_INDEL_DEL, lane);
+                vs_pileup_tally(P.tally + 2, found && kind == VS_INDEL_INS, lane);
+                vs_pileup_tally(P.tally + 3, dropped, lane);
+            }
+            vs_wave_sync();  // s_cnt / s_pa / s_pb / s_pj are rewritten by the next 64 probes
+        }
+        vs_wave_sync();  // s_np is rewritten by the next batch
+    }
+}
+
+__global__ void __launch_bounds__(64)
+k_indel_tally_add(const unsigned long long *pass, unsigned long long *total) {
+    if (threadIdx.x < 4u) total[threadIdx.x] += pass[threadIdx.x];
+}
+
+extern "C" int vs_indel_scan_host(const uint32_t *read_words, const uint32_t *read_mask, const uint32_t *strand_words, const uint32_t *fwd_words, uint32_t rlen,
+                                  uint32_t tlen, uint32_t strand, uint32_t a, uint32_t qa, uint32_t K, uint32_t G, uint64_t out[4]) {
+    if (!read_words || !strand_words || !fwd_words || !out || !K || G < 1u || G > VS_INDEL_MAX_LEN || strand > 1u || a >= rlen || qa >= tlen) return VS_E_ARG;
+    out[0] = VS_INDEL_UNTESTED;
+    out[1] = out[2] = out[3] = 0;
+    if (!a || !qa) return VS_OK;
+    uint32_t kind = 0u, L = 0u;
+    const uint32_t st = vs_indel_find(read_words, 0u, strand_words, 0u, read_mask, a, qa, K, G, &kind, &L);
+    out[0] = st;
+    if (st == VS_INDEL_NONE) return VS_OK;
+    out[1] = ((uint64_t)kind << 8) | L;
+    if (st == VS_INDEL_EVENT) {
+        uint32_t u;
+        vs_indel_normalise(fwd_words, 0u, tlen, strand, kind, L, qa, kind == VS_INDEL_INS ? vs_pl_win(read_words, a - L) : 0ull, &u, &out[3]);
+        out[2] = u;
+    }
+    return VS_OK;
+}
+
+extern "C" int vs_node_indels(vs_ctx *ctx, const vs_reads *reads, const uint32_t *d_first, uint32_t max_len, uint64_t *d_events, uint64_t cap, uint64_t *n,
+                              uint64_t *d_tally) {
+    if (!ctx || !reads || !d_first || !n || !d_tally || (cap && !d_events)) return VS_E_ARG;
+    if (max_len < 1u || max_len > VS_INDEL_MAX_LEN) return vs_fail(ctx, VS_E_ARG, "vs_node_indels: a maximum length of %u: 1 to %u are possible", max_len, VS_INDEL_MAX_LEN);
+    if (!ctx->has_index) return vs_fail(ctx, VS_E_STATE, "vs_node_indels: build an index first (vs_index_build)");
+    VS_HIP(ctx, hipSetDevice(ctx->device));
+    const VsIndexDev &idx = ctx->idx;
+    const PileupPlan pl = vs_pileup_plan_for(idx.n_nodes, idx.K, reads->n_ends, (uint32_t)reads->max_len, (uint32_t)ctx->n_cu, 0, 0);
+    if (pl.status != VS_OK) return vs_fail(ctx, pl.status, "vs_node_indels: %s", pl.msg);
+    *n = 0;
+    if (!pl.launch) {  // no end of the block holds an anchor
+        VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return VS_OK;
+    }
+    VS_HIP(ctx, ctx->d_indel_tmp.reserve(sizeof(uint64_t) * 5u));  // the record count and the pass's four tallies
+    unsigned long long *d_tmp = ctx->d_indel_tmp.as<unsigned long long>();
+    VS_HIP(ctx, hipMemsetAsync(d_tmp, 0, sizeof(uint64_t) * 5u, ctx->stream));
+    IndelParams P;
+    P.idx = idx;
+    P.rd = reads->dev();
+    P.first = d_first;
+    P.out = (unsigned long long *)d_events;
+    P.cap = cap;
+    P.count = d_tmp;
+    P.tally = d_tmp + 1;
+    P.ends_per_wg = pl.ends_per_wg;
+    P.max_len = max_len;
+    hipLaunchKernelGGL(k_node_indels, dim3(pl.grid), dim3(PILEUP_TPB), 0, ctx->stream, P);
+    VS_HIP(ctx, hipGetLastError());
+    uint64_t found = 0;
+    VS_HIP(ctx, hipMemcpyAsync(&found, d_tmp, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
+    VS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n = found;
+    if (found > cap) return VS_OK;  // the pass did not fit: its tallies are not added, the caller calls again with room
+    hipLaunchKernelGGL(k_indel_tally_add, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long *)(d_tmp + 1), (unsigned long long *)d_tally);
+    VS_HIP(ctx, hipGetLastError());
+    return VS_OK;
+}

@@ -35,6 +35,13 @@ strands, and the records of ``--variants`` are found on the device (``vs_pileup_
 strand with the reference and with the alternate base.  With ``S`` a record whose alternate base has fewer than ``S`` reads on
 a strand gets the FILTER ``strand``, every other one ``PASS``; no record is removed.
 
+    ... --indels FILE[.gz] [--indel-max-length G] [--min-indel-count C] [--min-indel-frac F]
+
+With ``--indels`` the same read pass also finds every insertion or deletion of at most ``G`` bases that one read end carries
+against one strand of a segment, with ``k + 1`` exact bases on each side (``pe.IndelCounter``, ``tests/indel_model.py``) -- the
+ends the pileup rejects on both diagonals -- and writes the events, left-aligned and counted by strand, as a VCF 4.2 of its own;
+the depth they are measured against is the pileup's at the anchor base, so the pileup pass runs too.
+
 With ``--site-pairs`` the pass also keeps together what ONE fragment -- the two mates of a pair -- carries at a list of sites
 (``pe.SitePairCounter``, ``tests/site_pairs_model.py``) and writes, for every two sites of one segment at most ``D`` positions
 apart, how many fragments carry which two bases: which minor bases travel together.  The sites are the CHROM / POS of
@@ -283,6 +290,80 @@ def write_strand_vcf(path: str, ids, seqs, offsets, called, min_alt_strand: int 
             fh.write("%s\t%d\t.\t%s\t%s\t.\t%s\tDP=%d;AD=%d;AF=%.6f;DP4=%d,%d,%d,%d\n" % ((name, pos, ref, base, flt, dp, ad, ad / dp) + dp4))
 
 
+INDEL_TALLIES = ("matches tested", "deletions", "insertions", "insertions dropped")
+
+
+def indel_records(ids, seqs, events, offsets, depth, alt, min_count: int = 2, min_frac: float = 0.01, min_strand: int = 0):
+    """The records of ``--indels`` from the events of ``pe.IndelCounter.result`` -- ``(seg, pos0, kind, length, insert, count_f,
+    count_r)`` -- and the tables of a pileup counter's ``result()`` (with or without the plane axis): ``(segment, 1-based POS,
+    REF, ALT, DP, AD, ADF, ADR, FILTER)``, one per event, in the events' order.  With ``pos0 = u > 0`` the anchor is ``F[u-1]``
+    and POS is ``u``: ``F[u-1 : u+L]`` / ``F[u-1]`` for a deletion, ``F[u-1]`` / ``F[u-1] + I`` for an insertion; with
+    ``u == 0`` the anchor is the base BEHIND the event and POS is 1: ``F[0 : L+1]`` / ``F[L]``, and ``F[0]`` / ``I + F[0]``.
+    ``AD = ADF + ADR``; ``DP = AD +`` the reads the pileup has with A, C, G or T at the anchor.  A record needs ``AD >=
+    min_count`` and ``AD >= min_frac * DP``, one double product compared as it stands.  FILTER: ``.`` without a strand
+    threshold, else ``PASS`` when both ``ADF`` and ``ADR`` reach it, else ``strand``; no record is removed for it."""
+    import numpy as np
+
+    depth = np.asarray(depth, dtype=np.int64)
+    alt = np.asarray(alt, dtype=np.int64)
+    if depth.ndim == 2:  # (the planes of pe.StrandPileupCounter: the depth an event is measured against is that of both)
+        depth, alt = depth.sum(axis=1), alt.reshape(-1, 2, 5).sum(axis=1)
+    alt = alt.reshape(-1, 5)
+    out = []
+    for n, u, kind, length, insert, adf, adr in events:
+        seq = seqs[n]
+        if u > 0:
+            at, pos = u - 1, u
+            ref, new = (seq[u - 1:u + length], seq[u - 1]) if kind == 0 else (seq[u - 1], seq[u - 1] + insert)
+        else:
+            at, pos = (length, 1) if kind == 0 else (0, 1)
+            ref, new = (seq[0:length + 1], seq[length]) if kind == 0 else (seq[0], insert + seq[0])
+        row = int(offsets[n]) + at
+        here = int(depth[row] - alt[row, 4]) if seq[at] in BASES else int(alt[row, :4].sum())
+        ad = adf + adr
+        dp = ad + here
+        if ad >= min_count and float(ad) >= min_frac * float(dp):
+            out.append((ids[n], pos, ref, new, dp, ad, adf, adr, "." if min_strand < 1 else ("PASS" if adf >= min_strand and adr >= min_strand else "strand")))
+    return out
+
+
+def write_indel_vcf(path: str, ids, seqs, offsets, records, min_strand: int = 0) -> None:
+    """VCF 4.2 of the records ``indel_records`` made: the header of ``write_vcf`` with ``ADF`` / ``ADR`` behind ``AF`` and, with a
+    strand threshold, the FILTER ``strand``; ``AF = "%.6f" % (AD / DP)``, ``ID`` and ``QUAL`` are ``.``.  ``.gz``: through gzip."""
+    with _open_text(path) as fh:
+        fh.write("##fileformat=VCFv4.2\n##source=%s\n" % VCF_SOURCE)
+        for n, name in enumerate(ids):
+            if offsets[n + 1] > offsets[n]:
+                fh.write("##contig=<ID=%s,length=%d>\n" % (name, len(seqs[n])))
+        fh.write('##INFO=<ID=DP,Number=1,Type=Integer,Description="AD and the reads carrying A, C, G or T at the anchor base">\n'
+                 '##INFO=<ID=AD,Number=1,Type=Integer,Description="Read ends carrying the insertion or deletion">\n'
+                 '##INFO=<ID=AF,Number=1,Type=Float,Description="AD / DP">\n'
+                 '##INFO=<ID=ADF,Number=1,Type=Integer,Description="Read ends carrying it along the forward text">\n'
+                 '##INFO=<ID=ADR,Number=1,Type=Integer,Description="Read ends carrying it along the reverse complement">\n')
+        if min_strand >= 1:
+            fh.write('##FILTER=<ID=strand,Description="Fewer than %d read ends carry the event on one of the two strands">\n' % min_strand)
+        fh.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
+        for name, pos, ref, new, dp, ad, adf, adr, flt in records:
+            fh.write("%s\t%d\t.\t%s\t%s\t.\t%s\tDP=%d;AD=%d;AF=%.6f;ADF=%d;ADR=%d\n" % (name, pos, ref, new, flt, dp, ad, ad / dp, adf, adr))
+
+
+def indel_refusal(args, world: int = 1):
+    """None, or why the flags of ``--indels`` cannot hold, said before a device is opened."""
+    indels = getattr(args, "indels", None)
+    length, count, frac = getattr(args, "indel_max_length", None), getattr(args, "min_indel_count", None), getattr(args, "min_indel_frac", None)
+    if length is not None and not 1 <= length <= 32:
+        return "--indel-max-length %d: a length from 1 to 32 is needed" % length
+    if count is not None and count < 0:
+        return "--min-indel-count %d: a count from 0 up is needed" % count
+    if frac is not None and not 0.0 <= frac <= 1.0:
+        return "--min-indel-frac %r: a fraction between 0 and 1 is needed" % frac
+    if indels is None and (length is not None or count is not None or frac is not None):
+        return "--indel-max-length, --min-indel-count and --min-indel-frac belong to --indels: give it"
+    if indels is not None and world > 1:
+        return "--indels finds its events in one process only, and this process group has %d ranks: run without torchrun" % world
+    return None
+
+
 def pileup_refusal(args):
     """None, or why the pileup's flags cannot hold, said before a device is opened."""
     asked = args.pileup is not None or args.variants is not None
@@ -299,7 +380,7 @@ def pileup_refusal(args):
     strands, strand_count = getattr(args, "strands", False), getattr(args, "min_alt_strand_count", None)
     if strands and not asked:
         return "--strands keeps the strands of the pileup apart: give --pileup or --variants with it"
-    if strand_count is not None and not (strands and args.variants is not None):
+    if strand_count is not None and not (strands and args.variants is not None) and getattr(args, "indels", None) is None:
         return "--min-alt-strand-count filters the records of --variants by strand: give --strands and --variants with it"
     if strand_count is not None and strand_count < 1:
         return "--min-alt-strand-count %d: a count from 1 up is needed" % strand_count
@@ -442,7 +523,7 @@ def refuse_ranks(world: int) -> None:
 
 
 def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: bool = False, interleaved=None, check_names=None, single=(),
-               count_singles: bool = False, quiet: bool = False, profile: bool = False, pileup=None, site_pairs=None, strands=None):
+               count_singles: bool = False, quiet: bool = False, profile: bool = False, pileup=None, site_pairs=None, strands=None, indels=None):
     """Index the segments of ``gfa`` and count every end the chosen input delivers (the input dispatch of
     ``pe_inference.count_links``, one process only).  -> (segment ids in file order, KC int64 in file order, ends counted).
     Replaces the context's index; the context stops keeping masks when the pass is over, so a PE count may follow on it.
@@ -453,7 +534,9 @@ def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: b
     (sites, mismatch budget, span); a ``pe.SitePairCounter`` then takes every block as well and its ``result()`` with the five
     tallies behind it follows as the very last value.  ``strands``: ``None``, or (min_alt_count, min_alt_frac, min_alt_strand)
     beside ``pileup``: a ``pe.StrandPileupCounter`` takes the ``PileupCounter``'s place, depth and alt of the pileup's value have
-    its plane axis, and what its ``call()`` found on the device with these thresholds follows as that value's sixth member."""
+    its plane axis, and what its ``call()`` found on the device with these thresholds follows as that value's sixth member.
+    ``indels``: a maximum length; a ``pe.IndelCounter`` then takes every block as well and (its ``result()``, its four tallies)
+    follows behind everything else."""
     from . import pe as host
     from . import pe_inference
 
@@ -468,6 +551,9 @@ def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: b
     piles = None if pileup is None else (host.PileupCounter if strands is None else host.StrandPileupCounter)(ctx, max_mismatch=pileup)
     linked = host.SitePairCounter(ctx, site_pairs[0], max_mismatch=site_pairs[1], max_span=site_pairs[2]) if site_pairs is not None else None
     fed = counter if piles is None else _Both(counter, piles)
+    gapped = host.IndelCounter(ctx, max_len=indels) if indels is not None else None
+    if gapped is not None:
+        fed = _Both(fed, gapped)
     try:
         with contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext():
             pe_inference.feed_counter(ctx, fed if linked is None else _Both(fed, linked), inp, 0, 1, stages_follow=False, tally_singles=False)
@@ -477,6 +563,8 @@ def depth_pass(ctx, gfa: str, fwd: str, rve: str, kmer_size: int, bam_by_name: b
     piled = () if piles is None else ((seqs,) + piles.result() + (piles.tallies(),) + (() if strands is None else (piles.call(*strands),)),)
     if linked is not None:
         piled += (linked.result() + (linked.tallies(),),)
+    if gapped is not None:
+        piled += ((gapped.result(), gapped.tallies()),)
     if profile:
         offsets, cov = counter.result()
         return (ids, counter.kc(), counter.ends_seen, ([len(q) for q in seqs], offsets, cov)) + piled
@@ -549,6 +637,13 @@ def build_parser():
     p.add_argument("--min-alt-strand-count", dest="min_alt_strand_count", type=int, default=None, metavar="S",
                    help="--strands --variants: FILTER is PASS when at least S reads carry the alternate base on EACH strand, else strand; "
                         "no record is removed [default: FILTER stays .]")
+    p.add_argument("--indels", dest="indels", type=str, default=None, metavar="FILE",
+                   help="also write the insertions and deletions of at most G bases that the read ends carry, k + 1 exact bases on each side, "
+                        "left-aligned and counted by strand, as a VCF 4.2 of its own (INFO DP, AD, AF, ADF, ADR; the pileup pass runs too; "
+                        ".gz: through gzip)")
+    p.add_argument("--indel-max-length", dest="indel_max_length", type=int, default=None, metavar="G", help="--indels: the longest event, 1 to 32 [default: 16]")
+    p.add_argument("--min-indel-count", dest="min_indel_count", type=int, default=None, metavar="C", help="--indels: records need AD >= C [default: 2]")
+    p.add_argument("--min-indel-frac", dest="min_indel_frac", type=float, default=None, metavar="F", help="--indels: records need AD >= F * DP [default: 0.01]")
     p.add_argument("--site-pairs", dest="site_pairs", type=str, default=None, metavar="FILE",
                    help="also write which bases travel together on one read pair at pairs of sites of one segment, as a TSV (segment, pos_a, pos_b, "
                         "base_a, base_b, count; positions 1-based; non-zero counts only; .gz: through gzip).  The sites: --sites, or the records "
@@ -577,6 +672,10 @@ def main(argv=None) -> int:
     check_names = pe_inference.check_names_mode(args.check_names, args.check_names_singles)
     if args.gzip_device:
         os.environ["VS_GZIP_DEVICE"] = "1"
+    why = indel_refusal(args, int(os.environ.get("WORLD_SIZE", "1")))
+    if why is not None:
+        print("node_depth: %s" % why, file=sys.stderr)
+        return 1
     refuse_ranks(int(os.environ.get("WORLD_SIZE", "1")))  # (before a device is opened)
     why = pileup_refusal(args) or site_pairs_refusal(args)
     if why is not None:
@@ -602,12 +701,16 @@ def main(argv=None) -> int:
     min_count, min_frac = 2 if args.min_alt_count is None else args.min_alt_count, 0.01 if args.min_alt_frac is None else args.min_alt_frac
     strand_count = 0 if args.min_alt_strand_count is None else args.min_alt_strand_count
     profiled = args.profile is not None or args.profile_summary is not None or args.depth_stat is not None
-    piled = args.pileup is not None or args.variants is not None
+    piled = args.pileup is not None or args.variants is not None or args.indels is not None  # (--indels alone: its depth is the pileup's)
     got = depth_pass(ctx, args.gfa, args.fwd, args.rve, k, bam_by_name=args.bam_by_name, interleaved=interleaved,
                      check_names=check_names, single=args.single, count_singles=args.count_singles, quiet=True, profile=profiled,
                      pileup=budget if piled else None, **(dict(site_pairs=(sites, budget, span)) if sites is not None else {}),
-                     **(dict(strands=(min_count, min_frac, strand_count)) if args.strands else {}))
+                     **(dict(strands=(min_count, min_frac, strand_count)) if args.strands else {}),
+                     **(dict(indels=16 if args.indel_max_length is None else args.indel_max_length) if args.indels is not None else {}))
     ids, kc, ends = got[:3]
+    gapped = None
+    if args.indels is not None:
+        got, gapped = got[:-1], got[-1]
     linked = None
     if sites is not None:
         got, linked = got[:-1], got[-1]
@@ -629,6 +732,10 @@ def main(argv=None) -> int:
             write_strand_vcf(args.variants, ids, seqs, p_offsets, called, strand_count)
         elif args.variants is not None:
             write_vcf(args.variants, ids, seqs, p_offsets, p_depth, p_alt, min_count, min_frac)
+        if gapped is not None:
+            write_indel_vcf(args.indels, ids, seqs, p_offsets,
+                            indel_records(ids, seqs, gapped[0], p_offsets, p_depth, p_alt, 2 if args.min_indel_count is None else args.min_indel_count,
+                                          0.01 if args.min_indel_frac is None else args.min_indel_frac, strand_count), strand_count)
         if args.site_pairs is not None and sites is None:  # the records just written are the sites: the reads once more
             records = strand_records(ids, called) if args.strands else variant_records(ids, seqs, p_offsets, p_depth, p_alt, min_count, min_frac)
             linked = site_pairs_pass(ctx, record_sites(ids, records), args.fwd, args.rve, budget, span, bam_by_name=args.bam_by_name,
@@ -640,10 +747,13 @@ def main(argv=None) -> int:
         fh.write(text)
     stored = args.out + "".join("; %s in: %s" % (what, path) for what, path in (("profile", args.profile), ("summary", args.profile_summary),
                                                                                   ("pileup", args.pileup), ("variants", args.variants),
-                                                                                  ("site pairs", args.site_pairs))
+                                                                                  ("site pairs", args.site_pairs),
+                                                                                  ("indels", getattr(args, "indels", None)))
                                 if path is not None)
     if linked is not None:
         stored += " (%s)" % ", ".join("%d %s" % (v, what) for v, what in zip(linked[4], SITE_PAIR_TALLIES))
+    if gapped is not None:
+        stored += " (%s)" % ", ".join("%d %s" % (v, what) for v, what in zip(gapped[1], INDEL_TALLIES))
     print("node_depth: k = %d, %d read ends counted, %d window-entry coincidences (sum of KC), %d of %d segments with KC = 0; result stored in: %s"
           % (k, ends, int(kc.sum()), int((kc == 0).sum()), len(ids), stored))
     return 0

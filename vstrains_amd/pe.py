@@ -1541,6 +1541,18 @@ class Context:
                                                     min_alt_count, min_alt_frac, min_alt_strand, C.c_void_p(out_ptr) if out_ptr else None, cap, C.byref(n)))
         return int(n.value)
 
+    def node_indels(self, reads: ReadBlock, first_ptr: int, max_len: int, events_ptr: int, cap: int, tally_ptr: int) -> int:
+        """One block through the indel pass (``vs_node_indels``): every insertion or deletion of at most ``max_len`` bases an end
+        carries against a strand of a segment, as two uint64 (slot << 8 | plane << 7 | kind << 6 | (L - 1), the insert on the
+        forward strand) at ``events_ptr`` (device, ``[cap, 2]``), in no order.  -> the exact number of events of the block;
+        above ``cap`` the buffer holds nothing of use and the four uint64 at ``tally_ptr`` (matches tested, deletions,
+        insertions, insertions dropped) were not added to: call again with room.  Synchronises.  Blocks must have been built
+        after ``keep_masks(True)``."""
+        n = C.c_uint64(0)
+        nat.check(self._h, nat.lib().vs_node_indels(self._h, reads._h, C.c_void_p(first_ptr), max_len, C.c_void_p(events_ptr) if events_ptr else None, cap,
+                                                    C.byref(n), C.c_void_p(tally_ptr)))
+        return int(n.value)
+
     def contig_mems(self, reads: ReadBlock) -> np.ndarray:
         """Every maximal exact match of k + 1 bases or more between a contig of the block and a strand of a segment
         (``vs_contig_mems``): uint32 [n, 5] -- contig, first base in the contig, segment | strand << 31, first base in that
@@ -2333,6 +2345,102 @@ class StrandPileupCounter:
         """-> (alignments credited, alignments rejected for more than ``max_mismatch`` non-agreeing positions)."""
         t = self.tally.cpu().numpy()
         return int(t[0]), int(t[1])
+
+
+def indel_scan_host(read_words, read_mask, strand_words, fwd_words, rlen: int, tlen: int, strand: int, a: int, qa: int, K: int, G: int):
+    """What a lane of ``k_node_indels`` makes of ONE match (``vs_indel_scan_host``, a pure host function: no device is
+    needed).  Packed uint32 arrays with three zero words behind the last; ``read_mask``: ``None`` for an end without a byte
+    outside ACGT.  -> ``(status, kind, L, u, w1)``: status 0 not tested, 1 tested without an event, 2 an event, 3 dropped."""
+    out = np.zeros(4, dtype=np.uint64)
+    rc = nat.lib().vs_indel_scan_host(read_words.ctypes.data, None if read_mask is None else read_mask.ctypes.data, strand_words.ctypes.data,
+                                      fwd_words.ctypes.data, rlen, tlen, strand, a, qa, K, G, out.ctypes.data)
+    if rc != nat.VS_OK:
+        raise nat.NativeError(rc, "vs_indel_scan_host refuses a = %d of %d, qa = %d of %d, strand %d, K = %d, G = %d" % (a, rlen, qa, tlen, strand, K, G))
+    return int(out[0]), int(out[1]) >> 8, int(out[1]) & 0xFF, int(out[2]), int(out[3])
+
+
+class IndelCounter:
+    """The insertions and deletions of at most ``max_len`` bases that the read ends carry against the segments, found on one
+    device (``vs_node_indels``, ``tests/indel_model.py``): K = k + 1 exact bases on each side, every event written down once,
+    left-aligned on the segment's forward text, with the strand it was seen on.  Takes ``PileupCounter``'s place in the input
+    dispatch of ``pe_inference`` (``add``, ``device``, ``single_stats``, ``ends_seen``; the context keeps the masks): one
+    kernel per block, a second launch when the block's events outgrow the buffer (``first_cap`` records to begin with).  The
+    records of every block are merged on the device into a table of distinct records with their counts."""
+
+    def __init__(self, ctx: Context, max_len: int = 16, first_cap: int = 4096, device: Optional[str] = None):
+        import torch
+
+        if not 1 <= int(max_len) <= 32:
+            raise ValueError("a maximum indel length of %r: 1 to 32 are possible" % (max_len,))
+        if int(first_cap) < 1:
+            raise ValueError("a buffer of %r records: one or more are needed" % (first_cap,))
+        self.torch = torch
+        self.ctx = ctx
+        self.device = torch.device(device or ("cuda:%d" % ctx.device))
+        self.n = ctx.n_nodes
+        self.ksize = ctx.ksize
+        self.max_len = int(max_len)
+        self.single_stats = torch.zeros(3, dtype=torch.int64, device=self.device)  # (what the dispatch tallies of a PeCounter: stays zero)
+        self.ends_seen = 0  # ends the blocks delivered (the absent second ends of singles blocks aside)
+        self.launches = 0   # calls of vs_node_indels: one per block, two where the events did not fit
+        self.node_rank = getattr(ctx, "node_rank", None)  # (kept here: a later build_index cannot change how the slots are read)
+        with torch.cuda.device(self.device):
+            ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            self.first = torch.zeros(self.n + 1, dtype=torch.int32, device=self.device)  # (uint32 words)
+            self.slots = ctx.pileup_layout(self.first.data_ptr())
+            self.events = torch.zeros((int(first_cap), 2), dtype=torch.int64, device=self.device)  # (uint64 words)
+            self.keys = torch.zeros((0, 2), dtype=torch.int64, device=self.device)   # the distinct records so far
+            self.counts = torch.zeros(0, dtype=torch.int64, device=self.device)
+            self.tally = torch.zeros(4, dtype=torch.int64, device=self.device)
+        ctx.keep_masks(True)
+
+    def add(self, reads: ReadBlock):
+        torch = self.torch
+        n_ends = reads.info["ends"]
+        self.ends_seen += n_ends // 2 if reads.unpaired else n_ends
+        if not self.slots:
+            return
+        with torch.cuda.device(self.device):
+            self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+            args = (reads, self.first.data_ptr(), self.max_len)
+            n = self.ctx.node_indels(*args, self.events.data_ptr(), self.events.shape[0], self.tally.data_ptr())
+            self.launches += 1
+            if n > self.events.shape[0]:  # the pass did not fit and tallied nothing: once more, with room
+                self.events = torch.zeros((n, 2), dtype=torch.int64, device=self.device)
+                self.launches += 1
+                if self.ctx.node_indels(*args, self.events.data_ptr(), n, self.tally.data_ptr()) != n:
+                    raise RuntimeError("vs_node_indels: the number of events changed between two calls on the same block")
+            if n:
+                keys, inverse = torch.unique(torch.cat((self.keys, self.events[:n])), dim=0, return_inverse=True)
+                counts = torch.zeros(keys.shape[0], dtype=torch.int64, device=self.device)
+                counts.index_add_(0, inverse, torch.cat((self.counts, torch.ones(n, dtype=torch.int64, device=self.device))))
+                self.keys, self.counts = keys, counts
+
+    def result(self):
+        """-> a list of ``(seg, pos0, kind, length, insert, count_f, count_r)``: ``seg`` in the numbering of the node list
+        ``Context.build_index`` was given (the GFA's), ``pos0`` the 0-based forward position of the first deleted base or of
+        the base the insert stands before, ``kind`` 0 a deletion, 1 an insertion, ``insert`` the inserted bases on the forward
+        strand (``""`` for a deletion), the counts those of the ends laid along the forward text and along its reverse
+        complement.  Sorted by segment, position, kind, length, insert."""
+        keys = self.keys.cpu().numpy().view(np.uint64).reshape(-1, 2)
+        counts = self.counts.cpu().numpy()
+        first = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
+        order = None
+        if self.node_rank is not None:
+            order = np.empty(self.n, dtype=np.int64)
+            order[np.asarray(self.node_rank, dtype=np.int64)] = np.arange(self.n, dtype=np.int64)
+        table = {}
+        for (w0, w1), c in zip(keys.tolist(), counts.tolist()):
+            slot, plane, kind, length = w0 >> 8, w0 >> 7 & 1, w0 >> 6 & 1, (w0 & 63) + 1
+            rank = int(np.searchsorted(first, slot, side="right")) - 1  # (the segment that holds the slot: one without slots holds none)
+            seg = rank if order is None else int(order[rank])
+            insert = "".join("ACGT"[w1 >> (2 * i) & 3] for i in range(length)) if kind else ""
+            table.setdefault((seg, slot - int(first[rank]), kind, length, insert), [0, 0])[plane] += c
+        return [key + tuple(v) for key, v in sorted(table.items())]
+
+    def tallies(self):
+        """-> (matches tested, deletions, insertions, insertions dropped for a byte outside ACGT)."""
+        return tuple(int(v) for v in self.tally.cpu().numpy())
 
 
 def site_pairs_plan(n_nodes: int, ksize: int, n_ends: int, max_len: int, n_cu: int = 256) -> dict:
